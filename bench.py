@@ -19,7 +19,16 @@ GPU) and passes their output and exit code through.  With fewer GPUs than ranks 
 "exchange": "gloo (ranks share a device)".  --abi-sharded measures the same workload through ONE process and the C ABI's
 qv_sharded_* handle (a shard per device, ncclAllGather inside libqv) instead of one process per GPU.
 
-Extra objects on the line:
+A plain run does only what the headline needs: set up, warm up, time exactly --steps steps, write the outputs if asked, print
+the line (`roofline`, `cpu_baseline` and `verified_against_oracle` are null there).  --full adds everything else, after the
+timed steps: the CPU oracle's check of the timed results (distances of the returned rows, and membership over the first
+--cpu-sample-rows rows), the objects below, and the full record in a sidecar file.
+
+--dump-outputs DIR writes what the last timed step returned to its caller: DIR/rows.npy (the top-k row ids, float64) and
+DIR/distances.npy (their distances, float32).  Corpus and queries come from fixed seeds, so the same arguments give the same
+inputs on every run, and two builds can be compared output for output.
+
+Extra objects on the line (--full):
   "roofline"     HBM roofline of the dominant kernel k_flat_scan (HIP events around that kernel, separate pass; traffic
                  from the committed rocprofv3 PMC summary); at N > 1 also every GPU's fraction and the measured
                  all-gather + merge latency
@@ -66,6 +75,11 @@ def parse():
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--metric", default="cosine")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the oracle check of the timed results, the roofline pass, the per-GPU and exchange "
+                         "figures at N > 1, `also` and the CPU baselines (the --no-* switches below trim this); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (top-k rows as float64, distances as float32) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="skip the extra configs measured at N=1")
     ap.add_argument("--no-hnsw", action="store_true", help="skip the configs[3] HNSW build + search entries of `also`")
@@ -262,13 +276,21 @@ def write_sidecar(out):
         return None
 
 
-def emit(out):
-    sidecar = write_sidecar(out)
+def emit(out, full=True):
+    sidecar = write_sidecar(out) if full else None
     line = (compact_line(out, sidecar) + "\n").encode()
     if _REAL_STDOUT is None:
         sys.stdout.write(line.decode()); sys.stdout.flush()
     else:
         os.write(_REAL_STDOUT, line)
+
+
+def dump_outputs(path, rows, dist):
+    """--dump-outputs: the result of the last timed step as its caller received it (row ids widened to float64, which holds every
+    uint32 exactly; distances float32)"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rows.npy"), np.asarray(rows).astype(np.float64))
+    np.save(os.path.join(path, "distances.npy"), np.asarray(dist).astype(np.float32))
 
 
 def self_launch(a):
@@ -556,6 +578,25 @@ def run_abi_sharded(a):
     run(a.warmup, a.steps)
     sh.sync(); torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, d_r[total - 1].cpu().numpy().view(np.uint32), d_d[total - 1].cpu().numpy())
+    info = device_info(devices[0])
+    out = {
+        "metric": "flat_cosine_qps_recall_1.0", "value": a.steps / dt, "unit": "queries/s", "n_gpus": G, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": bool(a.full),
+        "config": {"workload": "flat %s scan %dx%d fp32, k=%d, single query per step, recall 1.0 (exact)" % (a.metric, a.rows, dim, k),
+                   "rows_total": a.rows, "rows_per_gpu": [sh.shard_info(g)["rows"] for g in range(G)], "dim": dim, "k": k,
+                   "sharding": "C ABI qv_sharded_*: ONE process, a shard per device, %s of the per-shard top-k inside libqv, merge on the first device"
+                               % ("hipMemcpyPeerAsync (point-to-point)" if a.peer_copy else "ncclAllGather (RCCL)"),
+                   "devices": devices, "device": info["name"], "cus": info["cus"], "corpus_gen_s": round(t_gen, 3), "runtime": short_runtime(runtime_info()),
+                   # how many RCCL ranks took part in the exchange that was timed (0: point-to-point copies / one shard has nobody to talk to)
+                   "rccl_ranks_seen": 0 if a.peer_copy else G},
+        "roofline": None, "cpu_baseline": None, "verified_against_oracle": None,
+    }
+    if not a.full:                                   # the headline only
+        emit(out, full=False)
+        sh.close()
+        return
     # verification: returned distances are the oracle's for the returned rows
     from tests import _oracle as O
     span = quiver_amd.lib().qv_sharded_span(G)
@@ -594,23 +635,13 @@ def run_abi_sharded(a):
     alg_bytes = n_local * dim * 4 + n_local * 8
     kern_ms0 = per_gpu[0]["scan_kernel_ms"]
     achieved = alg_bytes / (kern_ms0 * 1e-3) / 1e9 if kern_ms0 > 0 else 0.0
-    info = device_info(devices[0])
-    out = {
-        "metric": "flat_cosine_qps_recall_1.0", "value": a.steps / dt, "unit": "queries/s", "n_gpus": G, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "flat %s scan %dx%d fp32, k=%d, single query per step, recall 1.0 (exact)" % (a.metric, a.rows, dim, k),
-                   "rows_total": a.rows, "rows_per_gpu": [sh.shard_info(g)["rows"] for g in range(G)], "dim": dim, "k": k,
-                   "sharding": "C ABI qv_sharded_*: ONE process, a shard per device, %s of the per-shard top-k inside libqv, merge on the first device"
-                               % ("hipMemcpyPeerAsync (point-to-point)" if a.peer_copy else "ncclAllGather (RCCL)"),
-                   "devices": devices, "device": info["name"], "cus": info["cus"], "corpus_gen_s": round(t_gen, 3), "runtime": short_runtime(runtime_info()),
-                   # how many RCCL ranks took part in the exchange that was timed (0: point-to-point copies / one shard has nobody to talk to)
-                   "rccl_ranks_seen": 0 if a.peer_copy else G},
+    out.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                      "kernel": "k_flat_scan", "kernel_ms": kern_ms0, "algorithmic_bytes_per_launch": alg_bytes, "per_gpu": per_gpu,
                      "scan_phase_ms": prof["scan_ms"], "allgather_plus_merge_us": (prof["exchange_ms"] + prof["merge_ms"]) * 1e3,
                      "exchange_us": prof["exchange_ms"] * 1e3, "merge_and_download_us": prof["merge_ms"] * 1e3, "launches_timed": prof["searches"]},
-        "cpu_baseline": None, "verified_against_oracle": bool(verified),
-    }
+        "verified_against_oracle": bool(verified),
+    })
     emit(out)
     sh.close()
 
@@ -734,6 +765,42 @@ def main():
         r, d = (b["out_rows"], b["out_dist"]) if (G > 1 or a.force_exchange) else (b["rows"], b["dist"])
         return r.cpu().numpy().view(np.uint32), d.cpu().numpy()
 
+    out = None
+    if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, *result_of(total_steps - 1))
+        info = device_info(device_id)
+        out = {
+            "metric": "flat_cosine_qps_recall_1.0", "value": qps, "unit": "queries/s",
+            "n_gpus": G, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic", "full": bool(a.full),
+            "config": {"workload": "flat %s scan %dx%d fp32, k=%d, single query per step, recall 1.0 (exact, bit-identical to the CPU oracle)" % (a.metric, a.rows, dim, k),
+                       "rows_total": a.rows, "rows_per_gpu": n_local, "dim": dim, "k": k,
+                       "arithmetic": "float64 accumulation over float32 rows, one rounding to float32 (the reference's arithmetic)",
+                       "scan_streams": n_scan_streams,
+                       "sharding": ("contiguous row shards, one process per GPU, per-shard top-k + all-gather (k*8 B/rank) + deterministic merge; "
+                                    "exchange of step i overlaps scan of step i+1") if use_pg else "single shard",
+                       "exchange": None if not use_pg else ("RCCL (torch.distributed nccl backend)" if backend == "nccl" else "gloo (ranks share a device: RCCL needs one device per rank)"),
+                       # HBM per row: float32 tiles + float64 norm + alive bit; QV_FLAG_ROWMAJOR (the device HNSW's gathers) adds a second
+                       # float32 copy, QV_FLAG_BF16_ROWS (the default batched filter) a bfloat16 one: an index serving all three paths holds 2.5x
+                       "device_bytes_per_row": {"this_index": dim * 4 + 8.125, "plus_rowmajor_for_hnsw": dim * 8 + 8.125, "plus_rowmajor_and_bf16_rows": dim * 10 + 8.125},
+                       "device": info["name"], "cus": info["cus"], "corpus_gen_s": round(t_gen, 3),
+                       "runtime": short_runtime(runtime_info()),
+                       # how many RCCL ranks took part in the all-gather that was timed: the process group's size when its backend is nccl
+                       # (= RCCL); 0 when the exchange ran over gloo or there was no exchange
+                       "rccl_ranks_seen": (dist.get_world_size() if (use_pg and backend == "nccl") else 0)},
+            "roofline": None, "cpu_baseline": None, "verified_against_oracle": None,
+        }
+    if not a.full:                                       # the headline only: nothing else runs on the device or the host
+        if rank == 0:
+            emit(out, full=False)
+        if use_pg:
+            dist.barrier()
+            dist.destroy_process_group()
+        idx.close()
+        return
+
     # ---- verification of what was timed: the CPU oracle as the CHECKER (never on the timed path) ----
     verified = True
     if rank == 0:
@@ -799,28 +866,8 @@ def main():
         cpu = cpu_baseline(dim, k, a.cpu_sample_rows, a.cpu_sample_queries, a.rows, a.cpu_threads)
 
     if rank == 0:
-        info = device_info(device_id)
         traffic, traffic_src = pmc_traffic(n_local, dim)
-        out = {
-            "metric": "flat_cosine_qps_recall_1.0", "value": qps, "unit": "queries/s",
-            "n_gpus": G, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "flat %s scan %dx%d fp32, k=%d, single query per step, recall 1.0 (exact, bit-identical to the CPU oracle)" % (a.metric, a.rows, dim, k),
-                       "rows_total": a.rows, "rows_per_gpu": n_local, "dim": dim, "k": k,
-                       "arithmetic": "float64 accumulation over float32 rows, one rounding to float32 (the reference's arithmetic)",
-                       "scan_streams": n_scan_streams,
-                       "sharding": ("contiguous row shards, one process per GPU, per-shard top-k + all-gather (k*8 B/rank) + deterministic merge; "
-                                    "exchange of step i overlaps scan of step i+1") if use_pg else "single shard",
-                       "exchange": None if not use_pg else ("RCCL (torch.distributed nccl backend)" if backend == "nccl" else "gloo (ranks share a device: RCCL needs one device per rank)"),
-                       # HBM per row: float32 tiles + float64 norm + alive bit; QV_FLAG_ROWMAJOR (the device HNSW's gathers) adds a second
-                       # float32 copy, QV_FLAG_BF16_ROWS (the default batched filter) a bfloat16 one: an index serving all three paths holds 2.5x
-                       "device_bytes_per_row": {"this_index": dim * 4 + 8.125, "plus_rowmajor_for_hnsw": dim * 8 + 8.125, "plus_rowmajor_and_bf16_rows": dim * 10 + 8.125},
-                       "device": info["name"], "cus": info["cus"], "corpus_gen_s": round(t_gen, 3),
-                       "runtime": short_runtime(runtime_info()),
-                       # how many RCCL ranks took part in the all-gather that was timed: the process group's size when its backend is nccl
-                       # (= RCCL); 0 when the exchange ran over gloo or there was no exchange
-                       "rccl_ranks_seen": (dist.get_world_size() if (use_pg and backend == "nccl") else 0)},
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "kernel": "k_flat_scan", "kernel_ms": kern_ms, "launches_timed": launches,
@@ -828,7 +875,7 @@ def main():
                          "per_gpu": per_gpu, "allgather_plus_merge_us": exchange_us},
             "cpu_baseline": cpu,
             "verified_against_oracle": bool(verified),
-        }
+        })
         if also:
             out["also"] = also
         emit(out)

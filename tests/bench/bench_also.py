@@ -1,7 +1,7 @@
 """The `also` entries of bench.py's line (N = 1 only): BASELINE.json's other configurations and the serving shapes around them, each
 measured on the corpus the headline run already holds (or a 1M x 768 one), every result compared with the exact scan / the oracle.
 
-bench.py calls `also_entries(...)`; nothing here is part of the timed headline region.  One entry per key of the returned dict;
+bench.py --full calls `also_entries(...)`; nothing here is part of the timed headline region.  One entry per key of the returned dict;
 `bench.compact_also` picks one or two numbers of each for the contract line, the rest goes to the sidecar (profiles/ or gpurun_out/).
 """
 import json

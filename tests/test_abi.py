@@ -100,8 +100,8 @@ def test_header_is_plain_c_and_the_library_fails_loudly_without_a_gpu(tmp_path):
     assert p.returncode == 0, p.stdout + p.stderr
     if quiver_amd.lib().qv_device_count() <= 0:
         assert "no device" in p.stdout and "no CPU path" in p.stdout
-    else:
-        assert p.stdout.startswith("ok:")
+    else:                                        # (RCCL prints its version banner to stdout before: the program's own line is the last)
+        assert p.stdout.splitlines()[-1].startswith("ok:"), p.stdout
 
 
 def test_sharded_placement_rule_and_span():

@@ -98,3 +98,58 @@ def test_membership_check_catches_a_skipped_row():
     assert not bench.membership_check(O, 0, q, rows, 0, er2[1:].astype(np.int64), ed2[1:])          # the best row is missing
     bad = ed.copy(); bad[3] = np.nextafter(bad[3], np.float32(2))
     assert not bench.membership_check(O, 0, q, rows, 0, er.astype(np.int64), bad)                    # a distance one ulp off
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import numpy as np
+    rows = np.array([4294967295, 0, 9999999], dtype=np.uint32)
+    dist = np.array([0.25, 0.5, 1.0], dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "out"), rows, dist)
+    r, d = np.load(tmp_path / "out" / "rows.npy"), np.load(tmp_path / "out" / "distances.npy")
+    assert r.dtype == np.float64 and d.dtype == np.float32
+    assert r.astype(np.uint64).tolist() == rows.tolist() and np.array_equal(d, dist)
+
+
+def _run_bench(args, tmp_path):
+    env = dict(os.environ, QV_BENCH_SIDECAR=str(tmp_path / "full.json"))
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, env=env, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert p.stdout.count("\n") == 1
+    return json.loads(p.stdout)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_and_dumps_the_last_step(tmp_path):
+    """a plain run: exactly --steps timed steps, the headline fields, no extras; --dump-outputs holds the last timed step's top-k,
+    which is the oracle's exact top-k of that step's query (step i searches query i % 256 of the seeded pool)"""
+    import numpy as np
+    from tests import _oracle as O
+    n, dim, k, steps, warmup = 30000, 768, 10, 5, 2
+    line = _run_bench(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--rows", str(n), "--dump-outputs", str(tmp_path / "d")], tmp_path)
+    assert line["steps"] == steps and line["warmup"] == warmup and line["full"] is False
+    assert line["metric"] == "flat_cosine_qps_recall_1.0" and line["unit"] == "queries/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["value"] > 0 and line["ms_per_step"] == pytest.approx(1e3 / line["value"], rel=1e-3)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "also" not in line and "full_record" not in line
+    assert not (tmp_path / "full.json").exists()
+    rows, dist = np.load(tmp_path / "d" / "rows.npy"), np.load(tmp_path / "d" / "distances.npy")
+    assert rows.dtype == np.float64 and dist.dtype == np.float32 and rows.shape == (k,) and dist.shape == (k,)
+    q = O.gen_rows(bench.QUERY_SEED, 0, 256, dim)[(warmup + steps - 1) % 256]
+    er, ed = O.exact_search(0, O.gen_rows(bench.CORPUS_SEED, 0, n, dim), q, k)
+    assert rows.astype(np.int64).tolist() == er.tolist() and np.array_equal(dist.view(np.uint32), ed.view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_full_run_keeps_the_oracle_check_and_the_roofline(tmp_path):
+    line = _run_bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--rows", "30000", "--full", "--no-also", "--no-cpu-baseline"], tmp_path)
+    assert line["full"] is True and line["verified_against_oracle"] is True
+    assert line["roofline"]["bound"] == "hbm" and line["roofline"]["kernel_ms"] > 0 and line["full_record"]
+    assert json.loads((tmp_path / "full.json").read_text())["steps"] == 4

@@ -1,5 +1,5 @@
 for wg in ${WGS:-1 2}; do for u in ${US:-16 24 32}; do
-  echo "wg=$wg u=$u"; QV_SCAN_WG_PER_CU=$wg QV_SCAN_UNROLL=$u python bench.py --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+  echo "wg=$wg u=$u"; QV_SCAN_WG_PER_CU=$wg QV_SCAN_UNROLL=$u python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
