@@ -140,6 +140,17 @@ class DeviceIndex:
         check(lib().qv_index_search_masked(self._h, q.ctypes.data, nq, k, m.ctypes.data, rows.ctypes.data, dist.ctypes.data, cnt.ctypes.data))
         return rows, dist, cnt
 
+    def search_negative(self, query, negative, k_fetch: int):
+        """-> (rows [k_fetch], dist, neg_dist, count): qv_index_search_negative"""
+        q, n = _f32c(query).ravel(), _f32c(negative).ravel()
+        if q.size != self.dim or n.size != self.dim:
+            raise ValueError(f"query dimension mismatch: expected {self.dim}, got {q.size if q.size != self.dim else n.size}")
+        kk = max(int(k_fetch), 0)
+        rows = np.full(max(kk, 1), 0xFFFFFFFF, dtype=np.uint32); dist = np.full(max(kk, 1), np.inf, dtype=np.float32)
+        nd = np.full(max(kk, 1), np.inf, dtype=np.float32); cnt = C.c_uint32(0)
+        check(lib().qv_index_search_negative(self._h, q.ctypes.data, n.ctypes.data, kk, rows.ctypes.data, dist.ctypes.data, nd.ctypes.data, C.byref(cnt)))
+        return rows[:kk], dist[:kk], nd[:kk], int(cnt.value)
+
     def search_batched_device(self, d_queries: int, nq: int, k: int, d_rows_out: int, d_dist_out: int, d_redo_flags: int, stream: int = 0):
         check(lib().qv_index_search_batched_device(self._h, d_queries, nq, k, d_rows_out, d_dist_out, d_redo_flags, stream))
 
