@@ -9,32 +9,14 @@ numpy float64 (IEEE, same roundings as the device's v_fma_f64 on exact products)
 import numpy as np
 import pytest
 
+from tests._order import planted_rows, query_for, scan_split_sum, split_sum, workgroup_sum
+
 U = 2.0 ** -53
 SLACK = 128.0
 
 
 def seq_sum(p):                       # one chain, element order: cumsum adds left to right, one rounding per step
     return float(np.cumsum(p)[-1]) if len(p) else 0.0
-
-
-def split_sum(p, waves, lanes_per_row):
-    """the latency form's order: wave w owns a contiguous run of 16-byte chunks (4 elements each), its lanes split the run,
-    every lane runs a chain, lanes are added pairwise (butterfly), waves in order"""
-    n4 = len(p) // 4
-    n_p = n4 // 8                                        # pieces of 8 chunks
-    tot = None
-    for w in range(waves):
-        p_lo, p_hi = w * n_p // waves, (w + 1) * n_p // waves
-        c0, n = p_lo * 8, (p_hi - p_lo) * 8
-        parts = []
-        for sub in range(lanes_per_row):
-            lo, hi = c0 + sub * n // lanes_per_row, c0 + (sub + 1) * n // lanes_per_row
-            parts.append(seq_sum(p[4 * lo:4 * hi]))
-        while len(parts) > 1:                             # xor-butterfly: (a + b), then pairs of pairs
-            half = len(parts) // 2
-            parts = [parts[i] + parts[i + half] for i in range(half)]
-        tot = parts[0] if tot is None else tot + parts[0]
-    return tot
 
 
 def cosine_finalize(acc, qn, rn):     # distances.go:25-39 (float64, then float32)
@@ -87,3 +69,55 @@ def test_nonnegative_terms_bound_is_the_sum_itself():
             assert s - b <= s_ref <= s + b
             lo, hi, ref = np.float32(np.sqrt(max(s - b, 0.0))), np.float32(np.sqrt(s + b)), np.float32(np.sqrt(s_ref))
             assert lo <= ref <= hi
+
+
+def _scan_cosine_interval(q, r):
+    """k_flat_scan_split's certificate for cosine (qv_scan.hip): S = the eight waves' partial chains added in order, |q| from a
+    sum over the workgroup, B = k_u |q| |r| widened by (|S| + B) 2 k_u for that norm's own error"""
+    dim4 = (q.size + 3) // 4
+    k_u = (2.0 * (4 * dim4) + SLACK) * U
+    q64, r64 = q.astype(np.float64), r.astype(np.float64)
+    p = q64 * r64
+    s = scan_split_sum(np.concatenate([p, np.zeros(4 * dim4 - p.size)]))
+    qn_s = float(np.sqrt(workgroup_sum(q64 * q64)))
+    rn = float(np.sqrt(seq_sum(r64 * r64)))
+    b = k_u * qn_s * rn
+    b = b + (abs(s) + b) * (2.0 * k_u)
+    return s, b, qn_s, rn
+
+
+@pytest.mark.parametrize("dim", [128, 130, 256, 768, 1000, 1536])
+def test_split_scan_cosine_with_a_workgroup_norm(dim):
+    """The split scan's cosine case: the query's norm is a workgroup sum, not the reference's chain, and its error widens the
+    interval.  The reference's distance (chain dot product, chain norm) must lie between the distances of the interval's ends
+    computed with the workgroup norm — on random, nearly parallel and planted (tests/_order.py) pairs — and where the ends agree,
+    the reference has that float32."""
+    rng = np.random.default_rng(31 * dim)
+    pairs = []
+    for t in range(300):
+        scale = 10.0 ** rng.integers(-3, 4)
+        q = (rng.standard_normal(dim) * scale).astype(np.float32)
+        r = (rng.standard_normal(dim) * scale).astype(np.float32)
+        if t % 3 == 0:
+            r = (q * (1.0 + 10.0 ** rng.uniform(-7, -2) * rng.standard_normal(dim))).astype(np.float32)
+        pairs.append((q, r))
+    q = query_for(0, dim, rng)
+    planted = planted_rows(0, dim, q, 12, rng)
+    assert len(planted) >= 6
+    pairs += [(q, r) for r in planted]
+    decided = 0
+    for q, r in pairs:
+        s, b, qn_s, rn = _scan_cosine_interval(q, r)
+        q64, r64 = q.astype(np.float64), r.astype(np.float64)
+        s_ref = seq_sum(q64 * r64)
+        qn = float(np.sqrt(seq_sum(q64 * q64)))
+        d_ref = cosine_finalize(s_ref, qn, rn)
+        d_lo, d_hi = cosine_finalize(s - b, qn_s, rn), cosine_finalize(s + b, qn_s, rn)
+        assert d_hi <= d_ref <= d_lo, (dim, s, b, s_ref, qn, qn_s)
+        if d_lo.tobytes() == d_hi.tobytes():
+            assert d_ref.tobytes() == d_lo.tobytes()
+            decided += 1
+    for q_, r_ in [(q, r) for r in planted]:                 # planted rows: never decided (the fallback runs)
+        s, b, qn_s, rn = _scan_cosine_interval(q_, r_)
+        assert cosine_finalize(s - b, qn_s, rn).tobytes() != cosine_finalize(s + b, qn_s, rn).tobytes()
+    assert decided >= 150                                    # (the random pairs: the certificate holds for most)
