@@ -2364,303 +2364,481 @@ uint32_t batched_cand_cap(uint32_t k) {
 // there everything above one block is padded to whole workgroups of four.
 static uint32_t batched_nq_pad(uint32_t nq, const IndexView& v) { return nq <= 64 ? 64u : (nq <= 128 && filter_mode(v) != 3 ? 128u : (nq + 255) / 256 * 256); }
 
-size_t batched_workspace_bytes(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k) {
-    const uint32_t nq_pad = batched_nq_pad(nq, v);
-    size_t b = scan_workspace_bytes(p, nq, k) + (size_t)(nq + 16) * v.dim4 * 4 * sizeof(double);   // sample scan (partials + query blocks)
-    b = (b + 255) / 256 * 256;
-    b += (size_t)nq_pad * (v.dim4 + 36) * 16 + 1024;         // Qt (chunk count padded to even) / the bf16 hi + lo planes (padded to whole steps; up to eight steps at least for the padded eight-wave kernel)
-    const size_t ccap = batched_cand_cap(k);
-    b += (size_t)nq_pad * 20;                                // cq, mq (m_q and b_q), eq
-    b += (size_t)nq * ccap * 8;                              // candidates: rows + fp32 scores
-    b += (size_t)nq * 8 + 256;                               // capacity word + counters, overflow flags
-    if (batched_large_k(v, k))                               // keys of the upper bounds and of the exact distances, lower bounds, survivors, counters, norms, selection
-        b += (size_t)nq * ccap * (8 + 8 + 4 + 4) + (size_t)nq * (4 + 16) + 1024 + select_workspace_bytes(nq, k) + (size_t)(v.n_tiles + 2) * 8 + 512;
-    b += (size_t)nq * k * 8;                                 // sample rows/dist
-    b += (size_t)nq * k * 16 + 256;                          // k_sample_bound's partial lists (up to four parts per query)
-    b += (size_t)nq_pad * batched_sample_rows(v, k) * 4 + (size_t)nq_pad * (batched_sample_rows(v, k) / 128 + 2) * 4 + 256;   // the sample's scores (bfloat16 filter: bound without an exact scan) and per-group minima
-    return b + 1024;
-}
-
 // the largest multiple of `unit` that fits `want` workgroups (one workgroup per CU is resident: rounding UP past the CU count
 // would leave a second, nearly empty round — 3 831 queries = 60 query blocks took 36 ms against 21 ms for 4 096)
 static uint32_t grid_multiple(uint32_t want, uint32_t unit) { const uint32_t g = want / unit * unit; return g ? g : unit; }
 
-hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws,
-                          uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
-                          hipEvent_t ev0, hipEvent_t ev1) {
-    const uint32_t nq_pad = batched_nq_pad(nq, v);
-    char* w = static_cast<char*>(d_ws);
-    size_t off = scan_workspace_bytes(p, nq, k) + (size_t)(nq + 16) * v.dim4 * 4 * sizeof(double);
-    off = (off + 255) / 256 * 256;
-    float* Qt = reinterpret_cast<float*>(w + off); off += (size_t)nq_pad * (v.dim4 + 36) * 16 + 1024;
-    float* cq = reinterpret_cast<float*>(w + off); off += (size_t)nq_pad * 4;
-    float* mq = reinterpret_cast<float*>(w + off); off += (size_t)nq_pad * 8;      // m_q, b_q
-    float* eq = reinterpret_cast<float*>(w + off); off += (size_t)nq_pad * 8;      // the scores' error bound per query (k_mfma_prep -> k_rescore_select)
-    const uint32_t ccap = batched_cand_cap(k);
-    const bool large_k = batched_large_k(v, k);
-    uint32_t* cand = reinterpret_cast<uint32_t*>(w + off); off += (size_t)nq * ccap * 4;
-    float* cscore = reinterpret_cast<float*>(w + off); off += (size_t)nq * ccap * 4;
-    off = (off + 255) / 256 * 256;
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(w + off) + 1; off += (size_t)nq * 4 + 4;   // cnt[-1]: the capacity, for the filter kernels
-    uint32_t* ovf = reinterpret_cast<uint32_t*>(w + off); off += (size_t)nq * 4;
-    // large k: the selections' arrays
-    uint64_t* keys_hi = nullptr; uint64_t* keys_ex = nullptr; float* lo_b = nullptr; uint32_t* surv = nullptr; uint32_t* nsurv = nullptr; double* qnorms = nullptr; void* sel_ws = nullptr; uint32_t* tp_cnt = nullptr; uint32_t* tp_off = nullptr;
-    if (large_k) {
-        off = (off + 255) / 256 * 256;
-        keys_hi = reinterpret_cast<uint64_t*>(w + off); off += (size_t)nq * ccap * 8;
-        keys_ex = reinterpret_cast<uint64_t*>(w + off); off += (size_t)nq * ccap * 8;
-        lo_b = reinterpret_cast<float*>(w + off); off += (size_t)nq * ccap * 4;
-        surv = reinterpret_cast<uint32_t*>(w + off); off += (size_t)nq * ccap * 4;
-        qnorms = reinterpret_cast<double*>(w + off); off += (size_t)nq * 16;
-        nsurv = reinterpret_cast<uint32_t*>(w + off); off += (size_t)nq * 4;
-        off = (off + 255) / 256 * 256;
-        sel_ws = w + off; off += select_workspace_bytes(nq, k);
-        tp_cnt = reinterpret_cast<uint32_t*>(w + off); off += (size_t)(v.n_tiles + 2) * 4;
-        tp_off = reinterpret_cast<uint32_t*>(w + off); off += (size_t)(v.n_tiles + 2) * 4;
-        off = (off + 255) / 256 * 256;
-    }
-    uint32_t* srows = reinterpret_cast<uint32_t*>(w + off); off += (size_t)nq * k * 4;
-    float* sdist = reinterpret_cast<float*>(w + off); off += (size_t)nq * k * 4;
-    off = (off + 255) / 256 * 256;
-    float* sparts = reinterpret_cast<float*>(w + off); off += (size_t)nq * k * 16;
-    const uint32_t bparts = nq <= 64 ? 4u : (nq <= 128 ? 2u : 1u);       // (four parts at 256 queries: 44 -> 74 us, every workgroup stages its query again)
+// the eight-wave kernels' K loop divides this dimension (k_bf16x1_filter_w8 / _w8x2, and k_bf16rows_filter's): rounds of two steps, four
+// in flight: a multiple of 4 rounds, at least 6
+static bool w8_loop_divides(const IndexView& v) { const uint32_t fsteps = (v.dim4 + 3) / 4; return (v.dim4 & 3u) == 0 && fsteps % 8 == 0 && fsteps >= 16; }
+
+// ---- the route of a batch: which kernels run for this (index, nq, k) --------------------
+// Decided by plan_batched before the first launch, from the index's shape, nq, k, the CU count and the queries' alignment alone.
+// Values under QV_VARIANTS are the measurement build's (make VARIANTS=1): the product library can neither select nor launch them.
+enum class SampleScores {
+    w8_one_term,            // k_bf16x1_filter_w8<., 8, 4, 1, false, false, true>: the eight-wave one-term kernel in its sample form
+    bf16x3,                 // k_bf16x3_filter with a score output
+    exact_scan,             // launch_flat_topk over the sample (QV_MFMA_SAMPLE_GEMM off): its k-th distance is the bound
+};
+enum class SampleBound {
+    scan_kth,               // (SampleScores::exact_scan: nothing to select)
+    prep_group_min,         // one minimum per query and 128-row group, selected inside k_mfma_prep
+    sample_select,          // k_sample_select
+    histogram,              // select_prepare, k_sample_hist<0>, <1>, k_sample_bound_from_state
+#ifdef QV_VARIANTS
+    wave_lists,             // k_sample_bound
+#endif
+};
+enum class MainFilter {
+    mfma_f32,               // k_mfma_filter<., 4>
+    bf16x3,                 // k_bf16x3_filter
+    bf16x3_shared,          // k_bf16x3_filter_shared<., 3, 8>
+    bf16rows,               // k_bf16rows_filter
+    w8x2, w8x2_padded,      // k_bf16x1_filter_w8x2<., 4, 4>, <., 4, 4, true>
+    qreg,                   // launch_qreg_filter (qv_qreg.hip)
+    q64_plane, q64_f32_rows,   // k_bf16rows_filter_q64<., 4, 4>, <., 2, 4, true>
+#ifdef QV_VARIANTS
+    mfma_f32_nj2,           // k_mfma_filter<., 2>
+    one_term_4w,            // k_bf16x3_filter_shared<., 1, 8>
+    w8_4_8_2_plane, w8_16_16, w8_8_16, w8_16_4, w8_16_8, w8_8_4_deferred, w8_8_4,   // k_bf16x1_filter_w8<., RING, AR, 1 (2), on the plane, deferred>
+    w8x2_8_4,               // k_bf16x1_filter_w8x2<., 8, 4>
+#endif
+};
+enum class ExactPass {
+    rescore_select,         // k_rescore_select<., 32>: exact distances and the k best in one kernel
+    // large k: k_cand_narrow or its four-kernel wide form (BatchedRoute::narrow), the survivors' exact distances by one of these, the final selection
+    tile_pass,              // k_tp_count, k_tp_scan, k_tp_scatter, k_tp_exact<., 8>: the corpus once, tile by tile
+    wave_per_32,            // k_cand_exact_wave: a gather, one wave per 32 survivors
+#ifdef QV_VARIANTS
+    rescore_select_u8,      // k_rescore_select<., 8>
+    lane_per_row,           // k_cand_exact<., 32>
+#endif
+};
+struct BatchedRoute {
+    uint32_t nq, k; int cus;
+    uint32_t nq_pad, ccap;          // batched_nq_pad, batched_cand_cap
+    bool large_k, guess;            // batched_large_k, batched_guess
+    uint32_t ks;                    // the rank the bound is taken at in the sample (batched_sample_rank)
+    int fmode, gmode;               // filter_mode; which filter_gamma the main pass obeys
+    // 1. the bound from a sample
+    SampleScores sample; SampleBound bound;
+    uint32_t sample_rows, sample_tiles, sgroups, gstep;   // rows, 64-row tiles and 128-row groups of the sample: every gstep-th group of the corpus
+    uint32_t sample_grid, hist_grid, bparts; size_t select_lds;   // (bparts: partial lists per query that k_sample_bound leaves to k_mfma_prep, else 1)
+    // 2. k_mfma_prep before the main pass: 2 = filter constants only, 3 = operands too, in prep_steps zero-padded steps (0: as many as the dimension has)
+    int prep_what; uint32_t prep_steps;
+    // 3. the filter (bfrows: on the index's bfloat16 plane)
+    MainFilter filter; bool bfrows; uint32_t filter_grid; size_t filter_lds;
+    // 4. the exact stage.  Large k: k_cand_narrow, or k_cand_qnorms, k_cand_bounds, launch_select_topk, k_cand_survive;
+    // at last launch_select_topk_counted, or launch_select_topk
+    ExactPass exact; bool narrow, final_counted; size_t narrow_lds;
+};
+
+// false: this build has no route for the batch (one that only the measurement build's kernels serve)
+static bool plan_batched(const IndexView& v, uint32_t nq, uint32_t k, int cus, bool queries_aligned16, BatchedRoute& r) {
+    r = BatchedRoute{};
+    r.nq = nq; r.k = k; r.cus = cus; r.bparts = 1;
+    r.nq_pad = batched_nq_pad(nq, v);
+    r.ccap = batched_cand_cap(k);
+    r.large_k = batched_large_k(v, k);
     // a guessed bound (batched_guess): rank ks of the small sample, kept in ubuf for the check after the filter (sdist is overwritten by the first selection)
-    const bool guess = batched_guess(v, k);
-    const uint32_t ks = batched_sample_rank(v, k);
-    float* ubuf = guess ? sparts : sdist;
-    // 1. per-query upper bound U_q of the k-th distance from a sample (the first rows)
-    IndexView vs = v;
-    vs.n_rows = batched_sample_rows(v, k);
-    vs.n_tiles = (vs.n_rows + 63) / 64;
+    r.guess = batched_guess(v, k);
+    r.sample_rows = batched_sample_rows(v, k);
+    r.sample_tiles = (r.sample_rows + 63) / 64;
+    r.ks = r.guess ? guess_rank(v.n_rows, r.sample_rows, k) : k;
     // QV_MFMA_FILTER: 1 = fp32 MFMA (BASELINE configs[2] as written), 2 = bf16 x 3 (default: same candidates up to the margin,
     // a quarter of the matrix cycles); the index's choice (qv_index_set_filter), so one process can compare them
-    const int fmode = filter_mode(v);
-    const int bf = fmode >= 2 ? 1 : 0;                                 // bfloat16 operand layout
-    static const int sample_gemm = dev_env_int("QV_MFMA_SAMPLE_GEMM", 1);
+    r.fmode = filter_mode(v);
+    const bool bf = r.fmode >= 2;                                      // bfloat16 operand layout
+    const uint32_t nqb64 = r.nq_pad / 64, fsteps = (v.dim4 + 3) / 4;
+    const bool w8_divides = w8_loop_divides(v);
     static const int share_env = dev_env_int("QV_MFMA_SHARE_ROWS", 1);
-    const bool shared = bf && (nq_pad / 64) % 4 == 0 && share_env == 1;
+    const bool shared = bf && nqb64 % 4 == 0 && share_env == 1;         // whole workgroups of 256 queries: the shared-row kernels
+    // one block of 64 queries on the one-term filter: the one-block kernel, on the bfloat16 plane or (round 4) on float32 rows
     static const int q64_env = dev_env_int("QV_MFMA_Q64", 1);                                     // 2 = off
-    const uint32_t fsteps0 = (v.dim4 + 3) / 4;
-    const bool q64_shape = bf && fmode == 3 && nq_pad == 64 && q64_env == 1 && (v.dim4 & 3u) == 0 && fsteps0 % 4 == 0 && fsteps0 >= 8 && fsteps0 <= 64;
-    const bool q64f = q64_shape && v.bf16 == nullptr;                     // the one-block kernel on float32 rows (round 4)
-    const bool q64 = q64_shape;
-    const int gmode = !bf ? 0 : (fmode == 3 && (shared || q64) ? 2 : 1);   // which filter_gamma the main pass obeys (one term: the shared kernels and the one-block kernel)
+    const bool q64 = r.fmode == 3 && r.nq_pad == 64 && q64_env == 1 && (v.dim4 & 3u) == 0 && fsteps % 4 == 0 && fsteps >= 8 && fsteps <= 64;
+    r.gmode = !bf ? 0 : (r.fmode == 3 && (shared || q64) ? 2 : 1);   // which filter_gamma the main pass obeys (one term: the shared kernels and the one-block kernel)
     // one-term filter on float32 rows at a dimension the eight-wave kernel's loop does not divide: its zero-padded form (round 4);
     // the query operands are then laid out once more, padded, after the sample pass has read them in its own layout
-    static const int w8_env0 = dev_env_int("QV_MFMA_W8", 1);
-    const bool w8_exact = (v.dim4 & 3u) == 0 && fsteps0 % 8 == 0 && fsteps0 >= 16;
-    const bool pad_main = gmode == 2 && shared && !q64 && w8_env0 == 1 && !w8_exact;
-    hipError_t e = hipSuccess;
-    if (sample_gemm == 1 || large_k) {
+    static const int w8_env = dev_env_int("QV_MFMA_W8", 1);                                       // 2 = the four-wave kernel (k_bf16x3_filter_shared<., 1>)
+    const bool w8 = w8_env == 1 && w8_divides;
+    const bool pad_main = r.gmode == 2 && shared && w8_env == 1 && !w8_divides;
+
+    // 1. per-query upper bound U_q of the k-th distance from a sample
+    static const int sample_gemm = dev_env_int("QV_MFMA_SAMPLE_GEMM", 1);
+    if (sample_gemm == 1 || r.large_k) {
         // the sample's scores by the three-term bfloat16 kernel, their upper bounds' k-th smallest as U_q (k_sample_bound): 0.1 ms
         // against 0.24 for an exact scan of the sample.  The fp32-MFMA filter takes its bound the same way (round 3): the query
         // operands are laid out as bfloat16 for the sample and then, in the same buffer, as float32 for the main pass
-        off = (off + 255) / 256 * 256;
-        float* sscore = reinterpret_cast<float*>(w + off); off += (size_t)nq_pad * vs.n_rows * 4 + (size_t)nq_pad * ((vs.n_rows + 127) / 128) * 4;   // every sample row's bound, the group minima behind them
-        hipLaunchKernelGGL(k_mfma_prep, dim3(nq_pad), dim3(64), 0, s, d_queries, nq, nq_pad, v.dim, v.dim4, sdist, 1u, k, v.metric, Qt, cq, mq, eq, cnt, ovf, 1, 1, ccap, 0u);
-        const uint32_t nqb64s = nq_pad / 64;
-        const uint32_t gs = grid_multiple(std::min<uint32_t>((uint32_t)cus, ((vs.n_tiles + 1) / 2 * nqb64s + 3) / 4), nqb64s / std::gcd(nqb64s, 4u));
-        const uint4* Qbf = reinterpret_cast<const uint4*>(Qt);
         // the sample's row groups are spread evenly over the corpus (a corpus stored cluster by cluster: the first S rows would bound nothing)
-        const uint32_t sgroups = (vs.n_rows + 127) / 128, all_groups = v.n_tiles / 2;
-        const uint32_t gstep = sgroups && all_groups > sgroups ? all_groups / sgroups : 1u;
+        r.sgroups = (r.sample_rows + 127) / 128;
+        const uint32_t all_groups = v.n_tiles / 2;
+        r.gstep = r.sgroups && all_groups > r.sgroups ? all_groups / r.sgroups : 1u;
         // one-term path: the sample on the eight-wave one-term kernel (QV_MFMA_SAMPLE1=2: on the three-term kernel, as the other filters' samples)
         static const int sample1_env = dev_env_int("QV_MFMA_SAMPLE1", 1);
-        static const int w8s_env = dev_env_int("QV_MFMA_W8", 1);
-        const bool sample1 = sample1_env == 1 && w8s_env == 1 && gmode == 2 && shared && (v.dim4 & 3u) == 0 && fsteps0 % 8 == 0 && fsteps0 >= 16;
-        const uint32_t gs1 = grid_multiple(std::min<uint32_t>((uint32_t)cus, sgroups * (nq_pad >> 8)), std::max<uint32_t>(nq_pad >> 8, 1u));
-        // large k: the k-th smallest bound by two histogram windows over the bounds (no wave list holds k keys), per-query state in the selection's workspace
-        SelState* sst = nullptr; uint32_t* shist = nullptr;
-
-        const uint32_t hgrid = std::max(1u, std::min(256u, (vs.n_rows + 16 * kSelBlock - 1) / (16 * kSelBlock)));
-        // the eight-wave sample kernel hands out one value per query and 128-row group when the groups outnumber k at least four times
-        const uint32_t sample_groups = (vs.n_rows + 127) / 128;
-        static const int gmin_env = dev_env_int("QV_MFMA_SAMPLE_GROUP_MIN", 1);                      // 2 = every row's bound (round 3)
+        const bool sample1 = sample1_env == 1 && w8_env == 1 && r.gmode == 2 && shared && w8_divides;
+        r.sample = sample1 ? SampleScores::w8_one_term : SampleScores::bf16x3;
+        r.sample_grid = sample1 ? grid_multiple(std::min<uint32_t>((uint32_t)cus, r.sgroups * (r.nq_pad >> 8)), std::max<uint32_t>(r.nq_pad >> 8, 1u))
+                                : grid_multiple(std::min<uint32_t>((uint32_t)cus, ((r.sample_tiles + 1) / 2 * nqb64 + 3) / 4), nqb64 / std::gcd(nqb64, 4u));
         // How the bound is taken from the sample's per-row upper bounds: k_sample_select (per-thread chunk minima, then the rows of the k
         // best chunks: the exact k-th smallest row bound, in LDS) while k chunks fit its LDS — k <= 128 at a million rows; beyond, the
         // histogram kernels (k_sample_hist: two radix windows over every row's bound) or, up to 64, k_sample_bound's wave lists.
         // QV_MFMA_SAMPLE_GROUP_MIN=3 (a measurement): one MINIMUM per query and 128-row group, selected inside k_mfma_prep — 11 us
         // faster at k = 10, 85 at k = 64, and a cliff on a corpus stored cluster by cluster (tools/dev_clustered_bound.py).
-        const uint32_t gmin_mode = gmin_env == 3 && sample1 ? 1u : 0u;
-        const bool group_min = gmin_mode != 0 && sample_groups >= 4 * k && sample_groups <= 4096;
-        const uint32_t gmin_vals = sample_groups;
+        // the eight-wave sample kernel hands out one value per query and 128-row group when the groups outnumber k at least four times
+        static const int gmin_env = dev_env_int("QV_MFMA_SAMPLE_GROUP_MIN", 1);                      // 2 = every row's bound (round 3)
         static const int sel2_env = dev_env_int("QV_MFMA_SAMPLE_SELECT", 1);                        // 2 = k_sample_bound (wave lists) as in round 3
-        const bool sel2 = sel2_env == 1 && !group_min && sample_select_applies(vs.n_rows, ks);
-        const size_t sel2_lds = sel2 ? sample_select_lds_bytes(vs.n_rows, ks) : 0;
-        if (large_k && !sel2 && !group_min) { e = select_prepare(sel_ws, nq, ks, &sst, &shist, s); if (e != hipSuccess) return e; }   // (the histogram kernels' state)
+        if (gmin_env == 3 && sample1 && r.sgroups >= 4 * k && r.sgroups <= 4096) r.bound = SampleBound::prep_group_min;
+        else if (sel2_env == 1 && sample_select_applies(r.sample_rows, r.ks)) { r.bound = SampleBound::sample_select; r.select_lds = sample_select_lds_bytes(r.sample_rows, r.ks); }
+        // large k: the k-th smallest bound by two histogram windows over the bounds (no wave list holds k keys), per-query state in the selection's workspace
+        else if (r.large_k) { r.bound = SampleBound::histogram; r.hist_grid = std::max(1u, std::min(256u, (r.sample_rows + 16 * kSelBlock - 1) / (16 * kSelBlock))); }
 #ifdef QV_VARIANTS
-#define QV_SB_LISTS(MMM) hipLaunchKernelGGL(k_sample_bound<MMM>, dim3(nq, bparts), dim3(1024), 0, s, sscore, vs.n_rows, k, (float)filter_gamma(v.dim, 0) * 1.000001f, bparts > 1 ? sparts : sdist, bparts);
+        else { r.bound = SampleBound::wave_lists; r.bparts = nq <= 64 ? 4u : (nq <= 128 ? 2u : 1u); }   // (four parts at 256 queries: 44 -> 74 us, every workgroup stages its query again)
 #else
-#define QV_SB_LISTS(MMM) return hipErrorNotSupported;     /* unreachable: k_sample_select applies to every sample of at least 4096 rows with k <= 64 */
+        else return false;                                  // (k_sample_select applies to every sample of at least 4096 rows with k <= 64)
 #endif
-#define QV_SB(MMM) { if (sample1) hipLaunchKernelGGL((k_bf16x1_filter_w8<MMM == QV_L2SQ ? QV_L2 : MMM, 8, 4, 1, false, false, true>), dim3(gs1), dim3(512), 0, s, v, Qbf, cq, eq, nq_pad, cand, cscore, cnt, sscore, vs.n_rows, gstep, group_min ? 1u : 0u); \
-                     else hipLaunchKernelGGL(k_bf16x3_filter<MMM == QV_L2SQ ? QV_L2 : MMM>, dim3(gs), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt, sscore, vs.n_rows, gstep); \
-                     if (group_min) { /* the bound is selected inside k_mfma_prep from the group minima */ } \
-                     else if (sel2) { e = set_lds(k_sample_select<MMM>, sel2_lds); if (e != hipSuccess) return e; \
-                                      hipLaunchKernelGGL(k_sample_select<MMM>, dim3(nq), dim3(1024), sel2_lds, s, sscore, vs.n_rows, ks, (float)filter_gamma(v.dim, 0) * 1.000001f, ubuf); } \
-                     else if (large_k) { hipLaunchKernelGGL(k_sample_hist<0>, dim3(hgrid, nq), dim3(kSelBlock), 0, s, sscore, vs.n_rows, ks, sst, shist); \
-                                    hipLaunchKernelGGL(k_sample_hist<1>, dim3(hgrid, nq), dim3(kSelBlock), 0, s, sscore, vs.n_rows, ks, sst, shist); \
-                                    hipLaunchKernelGGL(k_sample_bound_from_state<MMM>, dim3((nq + 255) / 256), dim3(256), 0, s, sst, nq, ks, (float)filter_gamma(v.dim, 0) * 1.000001f, ubuf); } \
-                     else QV_SB_LISTS(MMM) }
-        if (v.metric == QV_COSINE) QV_SB(QV_COSINE) else if (v.metric == QV_DOT) QV_SB(QV_DOT) else if (v.metric == QV_L2) QV_SB(QV_L2) else QV_SB(QV_L2SQ)
-#undef QV_SB
-#undef QV_SB_LISTS
-        hipLaunchKernelGGL(k_mfma_prep, dim3(nq_pad), dim3(64), 0, s, d_queries, nq, nq_pad, v.dim, v.dim4, bparts > 1 && !large_k && !group_min && !sel2 ? sparts : ubuf, large_k || group_min || sel2 ? 1u : bparts, ks, v.metric, Qt, cq, mq, eq, cnt, ovf, gmode, pad_main ? 3 : (bf ? 2 : 3), ccap, pad_main ? w8x2_rounds(v.dim4) : 0u, group_min ? sscore : nullptr, gmin_vals);
+        // 2. the main pass's operands: bfloat16 as the sample's (constants only), unless they are float32 or padded
+        r.prep_what = pad_main ? 3 : (bf ? 2 : 3);
+        r.prep_steps = pad_main ? w8x2_rounds(v.dim4) : 0u;
     } else {
-        ScanPlan ps = plan_scan(vs.n_tiles, cus);
-        e = launch_flat_topk(vs, ps, d_queries, nq, k, d_ws, srows, sdist, s);
-        if (e != hipSuccess) return e;
-        // 2. query re-layout + filter constants
-        hipLaunchKernelGGL(k_mfma_prep, dim3(nq_pad), dim3(64), 0, s, d_queries, nq, nq_pad, v.dim, v.dim4, sdist, 1u, k, v.metric, Qt, cq, mq, eq, cnt, ovf, gmode, 3, ccap, 0u);
+        r.sample = SampleScores::exact_scan; r.bound = SampleBound::scan_kth;
+        r.prep_what = 3; r.prep_steps = 0u;                 // 2. query re-layout + filter constants
     }
+
     // 3. MFMA filter
-    const uint32_t nqb64 = nq_pad / 64;
     // one 4-wave workgroup per CU (512-register waves); every query block gets the same number of waves
     static const int f32_nj = dev_env_int("QV_MFMA_F32_NJ", 4);             // 2 (measurement build): 64 rows per group, two waves per SIMD — 4.25 against 3.06 ms
-    const uint32_t grid = grid_multiple((uint32_t)cus * (!bf && !q64 && f32_nj == 2 ? 2 : 1), nqb64 / std::gcd(nqb64, 4u));
-    if (ev0) (void)hipEventRecord(ev0, s);
     if (q64) {
-        const uint4* Qbf = reinterpret_cast<const uint4*>(Qt);
-        const size_t lds_a = (size_t)fsteps0 * 128 * sizeof(uint4);
-#define QV_FQ1(MMM, NBB, RR) { e = set_lds(k_bf16rows_filter_q64<MMM, NBB, RR>, lds_a); if (e != hipSuccess) return e; \
-                     hipLaunchKernelGGL((k_bf16rows_filter_q64<MMM, NBB, RR>), dim3((uint32_t)cus), dim3(512), lds_a, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); }
         // (one tile per group with sixteen steps in flight, <MMM, 2, 16>, and a plane layout with contiguous KiB per request measure the same
         // 304-315 us at 64 x 1M x 768 as <MMM, 4, 4>: the kernel sits at 4.9-5.0 TB/s whatever each wave keeps in flight)
-#define QV_FQ1F(MMM) { e = set_lds(k_bf16rows_filter_q64<MMM, 2, 4, true>, lds_a); if (e != hipSuccess) return e; \
-                     hipLaunchKernelGGL((k_bf16rows_filter_q64<MMM, 2, 4, true>), dim3((uint32_t)cus), dim3(512), lds_a, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); }
-#define QV_FQ(MMM) { if (q64f) QV_FQ1F(MMM) else QV_FQ1(MMM, 4, 4) }
-        if (v.metric == QV_COSINE) QV_FQ(QV_COSINE) else if (v.metric == QV_DOT) QV_FQ(QV_DOT) else QV_FQ(QV_L2)
-#undef QV_FQ
-#undef QV_FQ1
-#undef QV_FQ1F
+        r.filter = v.bf16 == nullptr ? MainFilter::q64_f32_rows : MainFilter::q64_plane;
+        r.filter_grid = (uint32_t)cus;
+        r.filter_lds = (size_t)fsteps * 128 * sizeof(uint4);
     } else if (shared) {
-        const uint4* Qbf = reinterpret_cast<const uint4*>(Qt);
-        const uint32_t gs = grid_multiple((uint32_t)cus, nqb64 / 4);      // every row group is walked by nqb64/4 workgroups
-        const uint32_t fsteps = (v.dim4 + 3) / 4;
+        r.filter_grid = grid_multiple((uint32_t)cus, nqb64 / 4);      // every row group is walked by nqb64/4 workgroups
         static const int bfrows_env = dev_env_int("QV_MFMA_BF16_ROWS", 1);                        // 2 = ignore the index's bfloat16 plane
-        const bool bfrows = gmode == 2 && v.bf16 != nullptr && bfrows_env == 1 && (v.dim4 & 3u) == 0 && fsteps % 8 == 0 && fsteps >= 16;
-        static const int w8_env = dev_env_int("QV_MFMA_W8", 1);                                   // 2 = the four-wave kernel (k_bf16x3_filter_shared<., 1>)
-        const bool w8 = w8_env == 1 && (v.dim4 & 3u) == 0 && fsteps % 8 == 0 && fsteps >= 16;       // rounds of two steps, four in flight: a multiple of 4 rounds, at least 6
+        r.bfrows = r.gmode == 2 && v.bf16 != nullptr && bfrows_env == 1 && w8_divides;
+        // shipped: the bfloat16 copy's own kernel when the index keeps one; 256 rows per round on float32 rows (k_bf16x1_filter_w8x2)
+        // where the dimension allows the eight-wave shape; the four-wave shared-row kernels otherwise
+        // (the one-term filter as four waves, k_bf16x3_filter_shared<., 1>: only QV_MFMA_W8=2 of the measurement build reaches it — every shape the
+        // eight-wave kernel's loop does not divide takes its zero-padded form, pad_main)
+        if (r.gmode == 2 && (r.bfrows || w8) && qreg_filter_applies(v, r.nq_pad, r.bfrows)) r.filter = MainFilter::qreg;   // query operands in registers (qv_qreg.hip)
+        else if (r.bfrows) { r.filter = MainFilter::bf16rows; r.filter_grid = grid_multiple(2 * (uint32_t)cus, nqb64 / 4); }
+        else if (r.gmode == 2 && w8) r.filter = MainFilter::w8x2;
+        else if (pad_main) r.filter = MainFilter::w8x2_padded;
+#ifdef QV_VARIANTS
+        else if (r.gmode == 2) r.filter = MainFilter::one_term_4w;
+#endif
+        else r.filter = MainFilter::bf16x3_shared;
 #ifdef QV_VARIANTS
         // Measurement build only (make VARIANTS=1 -> libqv_dev.so; profiles/r03_batched_epilogue.txt has what each measured): the
-        // shapes of the eight-wave kernel that lost to the shipped one.  The product library instantiates none of them.
+        // shapes of the eight-wave kernel that lost to the shipped one, ahead of the shipped choice when their switch is set.
+        // The product library instantiates none of them.
         static const int w8_bf = env_int("QV_MFMA_W8_BF", 2);                                  // 1 = the eight-wave kernel on the bfloat16 plane too (485 against 474 us for k_bf16rows_filter)
         static const int w8x2 = env_int("QV_MFMA_W8X2", 1);                                 // 2 = 128 rows per round (k_bf16x1_filter_w8: 607 against 552 us); 3 = 256 with rows 8 steps ahead (spills)
         static const int w8_shape = env_int("QV_MFMA_W8_SHAPE", 1);                           // 7 = the dense pass deferred into the next group's K loop (610.7 against 607.3 us), 5 / 6 = rows 16 rounds ahead (614 / 613), 3 / 4 = query operands 15 steps ahead (644.6 / 648.6)
-#define QV_FS_VARIANTS(MMM)                                                                                                                                                        \
-                     if (bfrows && w8 && w8_bf == 1) hipLaunchKernelGGL((k_bf16x1_filter_w8<MMM, 4, 8, 2, true, false>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else if (!bfrows && gmode == 2 && w8 && w8_shape == 3 && fsteps % 16 == 0 && fsteps >= 32) hipLaunchKernelGGL((k_bf16x1_filter_w8<MMM, 16, 16, 1, false, false>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else if (!bfrows && gmode == 2 && w8 && w8_shape == 4 && fsteps % 16 == 0) hipLaunchKernelGGL((k_bf16x1_filter_w8<MMM, 8, 16, 1, false, false>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else if (!bfrows && gmode == 2 && w8 && w8_shape == 5 && fsteps % 16 == 0 && fsteps >= 32) hipLaunchKernelGGL((k_bf16x1_filter_w8<MMM, 16, 4, 1, false, false>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else if (!bfrows && gmode == 2 && w8 && w8_shape == 6 && fsteps % 16 == 0 && fsteps >= 32) hipLaunchKernelGGL((k_bf16x1_filter_w8<MMM, 16, 8, 1, false, false>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else if (!bfrows && gmode == 2 && w8 && w8x2 == 3) hipLaunchKernelGGL((k_bf16x1_filter_w8x2<MMM, 8, 4>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else if (!bfrows && gmode == 2 && w8 && w8x2 != 1 && w8_shape == 7) hipLaunchKernelGGL((k_bf16x1_filter_w8<MMM, 8, 4, 1, false, true>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else if (!bfrows && gmode == 2 && w8 && w8x2 != 1) hipLaunchKernelGGL((k_bf16x1_filter_w8<MMM, 8, 4, 1, false, false>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else
-#else
-#define QV_FS_VARIANTS(MMM)
+        const bool f32_w8 = !r.bfrows && r.gmode == 2 && w8;
+        if (r.bfrows && w8 && w8_bf == 1) { r.filter = MainFilter::w8_4_8_2_plane; r.filter_grid = grid_multiple((uint32_t)cus, nqb64 / 4); }
+        else if (f32_w8 && w8_shape == 3 && fsteps % 16 == 0 && fsteps >= 32) r.filter = MainFilter::w8_16_16;
+        else if (f32_w8 && w8_shape == 4 && fsteps % 16 == 0) r.filter = MainFilter::w8_8_16;
+        else if (f32_w8 && w8_shape == 5 && fsteps % 16 == 0 && fsteps >= 32) r.filter = MainFilter::w8_16_4;
+        else if (f32_w8 && w8_shape == 6 && fsteps % 16 == 0 && fsteps >= 32) r.filter = MainFilter::w8_16_8;
+        else if (f32_w8 && w8x2 == 3) r.filter = MainFilter::w8x2_8_4;
+        else if (f32_w8 && w8x2 != 1 && w8_shape == 7) r.filter = MainFilter::w8_8_4_deferred;
+        else if (f32_w8 && w8x2 != 1) r.filter = MainFilter::w8_8_4;
 #endif
-        const bool qreg = gmode == 2 && (bfrows || w8) && qreg_filter_applies(v, nq_pad, bfrows);   // query operands in registers (qv_qreg.hip)
-        // shipped: the bfloat16 copy's own kernel when the index keeps one; 256 rows per round on float32 rows (k_bf16x1_filter_w8x2)
-        // where the dimension allows the eight-wave shape; the four-wave shared-row kernels otherwise
-// (the one-term filter as four waves, k_bf16x3_filter_shared<., 1>: only QV_MFMA_W8=2 of the measurement build reaches it — every shape the
-// eight-wave kernel's loop does not divide takes its zero-padded form, pad_main)
+    } else {
+        r.filter = bf ? MainFilter::bf16x3 : MainFilter::mfma_f32;   // L2 and L2SQ share the filter
+        r.filter_grid = grid_multiple((uint32_t)cus * (!bf && f32_nj == 2 ? 2 : 1), nqb64 / std::gcd(nqb64, 4u));
 #ifdef QV_VARIANTS
-#define QV_FS_ONE_TERM_4W(MMM) else if (gmode == 2) hipLaunchKernelGGL((k_bf16x3_filter_shared<MMM, 1, 8>), dim3(gs), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt);
-#else
-#define QV_FS_ONE_TERM_4W(MMM)
+        if (!bf && f32_nj == 2) r.filter = MainFilter::mfma_f32_nj2;
 #endif
-#define QV_FS(MMM) { QV_FS_VARIANTS(MMM)                                                                                                                                           \
-                     if (qreg) { e = launch_qreg_filter(v, Qbf, cq, mq, nq_pad, cand, cscore, cnt, bfrows, cus, s); if (e != hipSuccess) return e; } \
-                     else if (bfrows) hipLaunchKernelGGL((k_bf16rows_filter<MMM>), dim3(grid_multiple(2 * (uint32_t)cus, nqb64 / 4)), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else if (gmode == 2 && w8) hipLaunchKernelGGL((k_bf16x1_filter_w8x2<MMM, 4, 4>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     else if (pad_main) hipLaunchKernelGGL((k_bf16x1_filter_w8x2<MMM, 4, 4, true>), dim3(gs), dim3(512), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                     QV_FS_ONE_TERM_4W(MMM)                                                                                                                                           \
-                     else hipLaunchKernelGGL((k_bf16x3_filter_shared<MMM, 3, 8>), dim3(gs), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); }
-        if (v.metric == QV_COSINE) QV_FS(QV_COSINE) else if (v.metric == QV_DOT) QV_FS(QV_DOT) else QV_FS(QV_L2)
-#undef QV_FS
-#undef QV_FS_VARIANTS
-#undef QV_FS_ONE_TERM_4W
-    } else if (bf) {
-        const uint4* Qbf = reinterpret_cast<const uint4*>(Qt);
-        if (v.metric == QV_COSINE) hipLaunchKernelGGL(k_bf16x3_filter<QV_COSINE>, dim3(grid), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt, (float*)nullptr, 0u, 1u);
-        else if (v.metric == QV_DOT) hipLaunchKernelGGL(k_bf16x3_filter<QV_DOT>, dim3(grid), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt, (float*)nullptr, 0u, 1u);
-        else hipLaunchKernelGGL(k_bf16x3_filter<QV_L2>, dim3(grid), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt, (float*)nullptr, 0u, 1u);
-#ifdef QV_VARIANTS
-    } else if (f32_nj == 2) {
-        if (v.metric == QV_COSINE) hipLaunchKernelGGL((k_mfma_filter<QV_COSINE, 2>), dim3(grid), dim3(256), 0, s, v, Qt, cq, mq, nq_pad, cand, cscore, cnt);
-        else if (v.metric == QV_DOT) hipLaunchKernelGGL((k_mfma_filter<QV_DOT, 2>), dim3(grid), dim3(256), 0, s, v, Qt, cq, mq, nq_pad, cand, cscore, cnt);
-        else hipLaunchKernelGGL((k_mfma_filter<QV_L2, 2>), dim3(grid), dim3(256), 0, s, v, Qt, cq, mq, nq_pad, cand, cscore, cnt);
-#endif
-    } else if (v.metric == QV_COSINE) hipLaunchKernelGGL((k_mfma_filter<QV_COSINE, 4>), dim3(grid), dim3(256), 0, s, v, Qt, cq, mq, nq_pad, cand, cscore, cnt);
-    else if (v.metric == QV_DOT) hipLaunchKernelGGL((k_mfma_filter<QV_DOT, 4>), dim3(grid), dim3(256), 0, s, v, Qt, cq, mq, nq_pad, cand, cscore, cnt);
-    else hipLaunchKernelGGL((k_mfma_filter<QV_L2, 4>), dim3(grid), dim3(256), 0, s, v, Qt, cq, mq, nq_pad, cand, cscore, cnt);   // L2 and L2SQ share the filter
-    if (ev1) (void)hipEventRecord(ev1, s);
-    // 4. exact re-scoring + selection
-    const size_t lds = query_lds_bytes(v.metric, v.dim4) + 4 * 64 * sizeof(uint64_t) + (size_t)kMfmaCandCap * (sizeof(uint32_t) + sizeof(float) + sizeof(uint32_t));   // query, wave lists, survivors, lower bounds, upper bounds' keys
-    // chunk requests per round of the exact pass, all issued before the round's arithmetic (row_accumulate's BAR): a survivor's row is
-    // a gather of dim4 separate lines and the pass is a chain of dim4 / U dependent round trips — 8 / 16 / 32 / 48 / 64 per round:
-    // 64.4 / 58.0 / 54.2 / 55.3 / 55.6 us per launch at 256 x 1M x 768 (left to the compiler's own schedule, as the streaming scans
-    // are for cosine, deeper rounds were slower: 90 us at 16)
-    static const int rs_u = dev_env_int("QV_MFMA_RESCORE_U", 32);
-#define QV_RS1(MMM, UU) { e = set_lds(k_rescore_select<MMM, UU>, lds); if (e != hipSuccess) return e;                                   \
-        hipLaunchKernelGGL((k_rescore_select<MMM, UU>), dim3(nq), dim3(256), lds, s, v, d_queries, cand, cscore, cnt, k, d_rows_out, d_dist_out, ovf, eq); }
-#ifdef QV_VARIANTS
-#define QV_RS(MMM) { if (rs_u == 8) QV_RS1(MMM, 8) else QV_RS1(MMM, 32) }
-#else
-#define QV_RS(MMM) { (void)rs_u; QV_RS1(MMM, 32) }
-#endif
-    if (large_k) {
-        // intervals -> H (k-th smallest upper bound) -> survivors -> exact distances -> the k best; srows / sdist take the first
-        // selection's output (the sample's bound in sdist has been consumed by k_mfma_prep)
-        const dim3 cgrid((ccap + 255) / 256, nq);
-        const size_t lds_x = query_lds_bytes(v.metric, v.dim4);
-        const size_t lds_n = (size_t)ccap * 4 + (size_t)v.dim * 4;
-        static const int narrow_mode = dev_env_int("QV_LK_NARROW", 1);
-        const bool narrow = narrow_mode == 1 && lds_n <= 140 * 1024;       // (beyond: k_cand_qnorms, k_cand_bounds, the selection's kernels, k_cand_survive)
-        const size_t lds_w = 2 * (size_t)kRsSlabBytes + (size_t)((v.dim4 + 7) / 8) * 128;
-        static const int wave_mode = dev_env_int("QV_LK_EXACT_WAVE", 1);
-        const bool wave_exact = wave_mode == 1;                          // (2: the lane-per-row kernel of rounds 4-5, measurement build only)
-        // gather or tile pass: ~2.1 k survivors per query of unstructured rows, 12 KiB of requests each at ~3.5 TB/s, against the
-        // corpus once at ~5.5 TB/s and 60 us for the three sorting kernels (256 queries x 1M x 768: from k ~ 300)
-        static const int tp_mode = dev_env_int("QV_LK_TILE_PASS", 1);   // 2 = never, 3 = always (measurements)
-        const double t_gather = 2.1 * k * nq * (double)v.dim4 * 64.0 / 3.5e12, t_pass = (double)v.n_rows * v.dim4 * 16.0 / 5.5e12 + 60e-6;
-        const bool tile_pass = v.rowmaj == nullptr && (v.dim & 3u) == 0 && (reinterpret_cast<uintptr_t>(d_queries) & 15u) == 0 && (uint64_t)nq * ccap < (1ull << 32) && (uint64_t)nq * v.dim < (1ull << 32) && tp_mode != 2 && (tp_mode == 3 || t_gather > t_pass);
-#ifdef QV_VARIANTS
-#define QV_LK_LANE(MMM) { e = set_lds(k_cand_exact<MMM, 32>, lds_x); if (e != hipSuccess) return e;                                                         \
-        hipLaunchKernelGGL((k_cand_exact<MMM, 32>), dim3(nq, (ccap + 255) / 256), dim3(256), lds_x, s, v, d_queries, surv, nsurv, ccap, qnorms, keys_ex); }
-#else
-#define QV_LK_LANE(MMM) { (void)lds_x; return hipErrorNotSupported; }
-#endif
-#define QV_LK(MMM) { e = set_lds(k_cand_qnorms<MMM>, (size_t)v.dim * 4); if (e != hipSuccess) return e;                                                 \
-        if (narrow) { e = set_lds(k_cand_narrow<MMM>, lds_n); if (e != hipSuccess) return e;                                                                \
-        hipLaunchKernelGGL(k_cand_narrow<MMM>, dim3(nq), dim3(1024), lds_n, s, v, d_queries, cand, cscore, cnt, ccap, eq, k, guess ? ubuf : (const float*)nullptr, ks, qnorms, lo_b, surv, nsurv, ovf, tp_cnt, tile_pass ? v.n_tiles + 1 : 0u); \
-        } else {                                                                                                                                            \
-        hipLaunchKernelGGL(k_cand_qnorms<MMM>, dim3(nq), dim3(64), (size_t)v.dim * 4, s, d_queries, v.dim, qnorms);                                         \
-        hipLaunchKernelGGL(k_cand_bounds<MMM>, cgrid, dim3(256), 0, s, v, cand, cscore, cnt, ccap, eq, qnorms, keys_hi, lo_b, ovf, nsurv);                 \
-        e = launch_select_topk(keys_hi, ccap, ccap, nq, k, k, sel_ws, srows, sdist, s, false, false); if (e != hipSuccess) return e;                       \
-        hipLaunchKernelGGL(k_cand_survive, cgrid, dim3(256), 0, s, cand, cnt, ccap, lo_b, sdist, k, surv, nsurv, guess ? ubuf : (const float*)nullptr, ks, ovf); }                                          \
-        if (tile_pass) {                                                                                                                                    \
-            if (!narrow) (void)hipMemsetAsync(tp_cnt, 0, (size_t)(v.n_tiles + 1) * 4, s);                                                                                 \
-            hipLaunchKernelGGL(k_tp_count, cgrid, dim3(256), 0, s, surv, nsurv, ccap, tp_cnt, keys_ex);                                                     \
-            hipLaunchKernelGGL(k_tp_scan, dim3(1), dim3(1024), 0, s, tp_cnt, v.n_tiles, tp_off);                                                            \
-            hipLaunchKernelGGL(k_tp_scatter, cgrid, dim3(256), 0, s, surv, nsurv, ccap, tp_off, tp_cnt, reinterpret_cast<uint2*>(keys_hi));                \
-            hipLaunchKernelGGL((k_tp_exact<MMM, 8>), dim3(v.n_tiles), dim3(64), 4 * 8192, s, v, d_queries, tp_off, reinterpret_cast<const uint2*>(keys_hi), ccap, qnorms, keys_ex); \
-        } else if (wave_exact) { e = set_lds(k_cand_exact_wave<MMM>, lds_w); if (e != hipSuccess) return e;                                                  \
-            hipLaunchKernelGGL(k_cand_exact_wave<MMM>, dim3(nq, ccap / 32), dim3(64), lds_w, s, v, d_queries, surv, nsurv, ccap, qnorms, keys_ex); }        \
-        else QV_LK_LANE(MMM)                                                                                                                                \
-        e = ccap <= 16384u ? launch_select_topk_counted(keys_ex, ccap, ccap, nsurv, nq, k, k, d_rows_out, d_dist_out, s)                                   \
-                          : launch_select_topk(keys_ex, ccap, ccap, nq, k, k, sel_ws, d_rows_out, d_dist_out, s, false, false); if (e != hipSuccess) return e; }
-        if (v.metric == QV_COSINE) QV_LK(QV_COSINE) else if (v.metric == QV_DOT) QV_LK(QV_DOT) else if (v.metric == QV_L2) QV_LK(QV_L2) else QV_LK(QV_L2SQ)
-#undef QV_LK
-#undef QV_LK_LANE
-        *d_overflow_out = ovf;
-        return hipGetLastError();
     }
-    if (v.metric == QV_COSINE) QV_RS(QV_COSINE) else if (v.metric == QV_DOT) QV_RS(QV_DOT) else if (v.metric == QV_L2) QV_RS(QV_L2) else QV_RS(QV_L2SQ)
-#undef QV_RS
-#undef QV_RS1
-    *d_overflow_out = ovf;
+
+    // 4. exact re-scoring + selection
+    if (!r.large_k) {
+        // chunk requests per round of the exact pass, all issued before the round's arithmetic (row_accumulate's BAR): a survivor's row is
+        // a gather of dim4 separate lines and the pass is a chain of dim4 / U dependent round trips — 8 / 16 / 32 / 48 / 64 per round:
+        // 64.4 / 58.0 / 54.2 / 55.3 / 55.6 us per launch at 256 x 1M x 768 (left to the compiler's own schedule, as the streaming scans
+        // are for cosine, deeper rounds were slower: 90 us at 16)
+        r.exact = ExactPass::rescore_select;
+#ifdef QV_VARIANTS
+        static const int rs_u = dev_env_int("QV_MFMA_RESCORE_U", 32);
+        if (rs_u == 8) r.exact = ExactPass::rescore_select_u8;
+#endif
+        return true;
+    }
+    // intervals -> H (k-th smallest upper bound) -> survivors -> exact distances -> the k best
+    r.narrow_lds = (size_t)r.ccap * 4 + (size_t)v.dim * 4;
+    static const int narrow_mode = dev_env_int("QV_LK_NARROW", 1);
+    r.narrow = narrow_mode == 1 && r.narrow_lds <= 140 * 1024;       // (beyond: k_cand_qnorms, k_cand_bounds, the selection's kernels, k_cand_survive)
+    // gather or tile pass: ~2.1 k survivors per query of unstructured rows, 12 KiB of requests each at ~3.5 TB/s, against the
+    // corpus once at ~5.5 TB/s and 60 us for the three sorting kernels (256 queries x 1M x 768: from k ~ 300)
+    static const int tp_mode = dev_env_int("QV_LK_TILE_PASS", 1);   // 2 = never, 3 = always (measurements)
+    const double t_gather = 2.1 * k * nq * (double)v.dim4 * 64.0 / 3.5e12, t_pass = (double)v.n_rows * v.dim4 * 16.0 / 5.5e12 + 60e-6;
+    const bool tile_pass = v.rowmaj == nullptr && (v.dim & 3u) == 0 && queries_aligned16 && (uint64_t)nq * r.ccap < (1ull << 32) && (uint64_t)nq * v.dim < (1ull << 32) && tp_mode != 2 && (tp_mode == 3 || t_gather > t_pass);
+    static const int wave_mode = dev_env_int("QV_LK_EXACT_WAVE", 1);   // (2: the lane-per-row kernel of rounds 4-5, measurement build only)
+    if (tile_pass) r.exact = ExactPass::tile_pass;
+    else if (wave_mode == 1) r.exact = ExactPass::wave_per_32;
+#ifdef QV_VARIANTS
+    else r.exact = ExactPass::lane_per_row;
+#else
+    else return false;
+#endif
+    r.final_counted = r.ccap <= 16384u;
+    return true;
+}
+
+// ---- the batch's workspace --------------------------------------------------------------
+// ONE description of the buffer: batched_workspace_bytes runs it with a null base for `total`, launch_batched for the pointers.
+// take() moves both `off` (where the next region starts) and `need` (what the caller must provide); the round-ups to 256 bytes move
+// `off` alone and slack() `need` alone — the slack terms are the hand-written size's, which counted no round-up but the first: six
+// round-ups (three without the large-k block) cost 1530 (765) bytes at most, the slack is 3324 (1788), so end <= total.
+struct WsCarver {
+    char* base; size_t off, need;
+    template <typename T> T* take(size_t count) { T* q = base ? reinterpret_cast<T*>(base + off) : nullptr; off += count * sizeof(T); need += count * sizeof(T); return q; }
+    void align256() { off = (off + 255) / 256 * 256; }
+    void slack(size_t bytes) { need += bytes; }
+};
+struct BatchedLayout {
+    float* Qt; float *cq, *mq, *eq;
+    uint32_t* cand; float* cscore; uint32_t *cnt, *ovf;
+    uint64_t *keys_hi, *keys_ex; float* lo_b; uint32_t* surv; double* qnorms; uint32_t* nsurv; void* sel_ws; uint32_t *tp_cnt, *tp_off;   // large k only
+    uint32_t* srows; float *sdist, *sparts, *sscore;
+    float* ubuf;                    // the bound U_q per query, until the check after the filter: sparts under a guessed bound, else sdist (an alias)
+    size_t end, total;
+};
+static BatchedLayout batched_layout(void* base, const IndexView& v, const ScanPlan& p, const BatchedRoute& r) {
+    WsCarver w{static_cast<char*>(base), 0, 0};
+    const size_t nq = r.nq, nq_pad = r.nq_pad, ccap = r.ccap;
+    BatchedLayout L{};
+    w.take<char>(scan_workspace_bytes(p, r.nq, r.k) + (nq + 16) * v.dim4 * 4 * sizeof(double));   // the front is launch_flat_topk's: sample scan (partials + query blocks)
+    w.align256(); w.need = w.off;
+    // Qt (chunk count padded to even) / the bf16 hi + lo planes (padded to whole steps; up to eight steps at least for the padded eight-wave
+    // kernel) and that kernel's KiB of zeros behind them.  The sample pass and the main pass share it: k_mfma_prep lays it out twice.
+    L.Qt = w.take<float>(nq_pad * (v.dim4 + 36) * 4 + 256);
+    L.cq = w.take<float>(nq_pad);
+    L.mq = w.take<float>(nq_pad * 2);                       // m_q, b_q
+    L.eq = w.take<float>(nq_pad * 2);                       // the scores' error bound per query (k_mfma_prep -> k_rescore_select)
+    L.cand = w.take<uint32_t>(nq * ccap);                   // candidates: rows + fp32 scores
+    L.cscore = w.take<float>(nq * ccap);
+    w.align256();
+    w.take<uint32_t>(1);                                    // cnt[-1]: the capacity, for the filter kernels
+    L.cnt = w.take<uint32_t>(nq);
+    L.ovf = w.take<uint32_t>(nq);
+    w.slack(256 - sizeof(uint32_t));                        // (slack kept from the hand-written version, which did not count the capacity word)
+    if (r.large_k) {                                        // the selections' arrays
+        w.align256();
+        L.keys_hi = w.take<uint64_t>(nq * ccap);            // keys of the upper bounds; reused as the tile pass's uint2 scatter target
+        L.keys_ex = w.take<uint64_t>(nq * ccap);            // keys of the exact distances
+        L.lo_b = w.take<float>(nq * ccap);                  // lower bounds
+        L.surv = w.take<uint32_t>(nq * ccap);               // survivors
+        L.qnorms = w.take<double>(nq * 2);
+        L.nsurv = w.take<uint32_t>(nq);
+        w.align256();
+        L.sel_ws = w.take<char>(select_workspace_bytes(r.nq, r.k));
+        L.tp_cnt = w.take<uint32_t>((size_t)v.n_tiles + 2);
+        L.tp_off = w.take<uint32_t>((size_t)v.n_tiles + 2);
+        w.align256();
+        w.slack(1024 + 512);                                // (slack kept from the hand-written version)
+    }
+    L.srows = w.take<uint32_t>(nq * r.k);                   // sample rows/dist
+    L.sdist = w.take<float>(nq * r.k);
+    w.align256();
+    L.sparts = w.take<float>(nq * r.k * 4);                 // k_sample_bound's partial lists (up to four parts per query)
+    w.slack(256);                                           // (slack kept from the hand-written version)
+    L.ubuf = r.guess ? L.sparts : L.sdist;
+    w.align256();
+    // the sample's scores (bfloat16 filter: bound without an exact scan): every sample row's bound, the group minima behind them
+    // (sized as the larger of the hand-written size's sample_rows / 128 + 2 and the hand-written carving's ceil(sample_rows / 128) groups)
+    L.sscore = w.take<float>(nq_pad * r.sample_rows + nq_pad * (r.sample_rows / 128 + 2));
+    w.slack(256 + 1024);                                    // (slack kept from the hand-written version)
+    L.end = w.off; L.total = w.need;
+    return L;
+}
+
+size_t batched_workspace_bytes(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k) {
+    BatchedRoute r;
+    (void)plan_batched(v, nq, k, 1, false, r);              // (the sizes depend on neither the CU count nor the queries' alignment, and are set before any route can fail)
+    return batched_layout(nullptr, v, p, r).total;
+}
+
+// The runtime metric as a compile-time constant M for a generic lambda, over the metrics this path's exact kernels (k_sample_select,
+// k_sample_bound*, k_rescore_select, k_cand_*, k_tp_exact) are instantiated for; the filters' own set: with_filter_metric (qv_filter.h)
+template <typename F> static inline hipError_t with_exact_metric(int metric, F&& f) {
+    switch (metric) {
+        case QV_COSINE: return f(std::integral_constant<int, QV_COSINE>{});
+        case QV_DOT:    return f(std::integral_constant<int, QV_DOT>{});
+        case QV_L2:     return f(std::integral_constant<int, QV_L2>{});
+        default:        return f(std::integral_constant<int, QV_L2SQ>{});
+    }
+}
+
+// 1. per-query upper bound U_q of the k-th distance from a sample: its scores, then their k-th smallest upper bound into L.ubuf
+static hipError_t batched_sample_bound(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, const float* d_queries, void* d_ws, hipStream_t s) {
+    const uint32_t nq = r.nq, nq_pad = r.nq_pad, srows = r.sample_rows;
+    if (r.sample == SampleScores::exact_scan) {
+        IndexView vs = v;
+        vs.n_rows = srows;
+        vs.n_tiles = r.sample_tiles;
+        return launch_flat_topk(vs, plan_scan(vs.n_tiles, r.cus), d_queries, nq, r.k, d_ws, L.srows, L.sdist, s);
+    }
+    hipLaunchKernelGGL(k_mfma_prep, dim3(nq_pad), dim3(64), 0, s, d_queries, nq, nq_pad, v.dim, v.dim4, L.sdist, 1u, r.k, v.metric, L.Qt, L.cq, L.mq, L.eq, L.cnt, L.ovf, 1, 1, r.ccap, 0u);
+    const uint4* Qbf = reinterpret_cast<const uint4*>(L.Qt);
+    SelState* sst = nullptr; uint32_t* shist = nullptr;
+    if (r.bound == SampleBound::histogram) { const hipError_t e = select_prepare(L.sel_ws, nq, r.ks, &sst, &shist, s); if (e != hipSuccess) return e; }   // (the histogram kernels' state)
+    (void)with_filter_metric(v.metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (r.sample == SampleScores::w8_one_term)
+            hipLaunchKernelGGL((k_bf16x1_filter_w8<M, 8, 4, 1, false, false, true>), dim3(r.sample_grid), dim3(512), 0, s, v, Qbf, L.cq, L.eq, nq_pad, L.cand, L.cscore, L.cnt, L.sscore, srows, r.gstep, r.bound == SampleBound::prep_group_min ? 1u : 0u);
+        else
+            hipLaunchKernelGGL(k_bf16x3_filter<M>, dim3(r.sample_grid), dim3(256), 0, s, v, Qbf, L.cq, L.mq, nq_pad, L.cand, L.cscore, L.cnt, L.sscore, srows, r.gstep);
+        return hipSuccess;
+    });
+    const float gref = (float)filter_gamma(v.dim, 0) * 1.000001f;
+    return with_exact_metric(v.metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        switch (r.bound) {
+            case SampleBound::scan_kth: case SampleBound::prep_group_min: break;   // (the bound is selected inside k_mfma_prep from the group minima)
+            case SampleBound::sample_select: {
+                const hipError_t e = set_lds(k_sample_select<M>, r.select_lds); if (e != hipSuccess) return e;
+                hipLaunchKernelGGL(k_sample_select<M>, dim3(nq), dim3(1024), r.select_lds, s, L.sscore, srows, r.ks, gref, L.ubuf);
+            } break;
+            case SampleBound::histogram:
+                hipLaunchKernelGGL(k_sample_hist<0>, dim3(r.hist_grid, nq), dim3(kSelBlock), 0, s, L.sscore, srows, r.ks, sst, shist);
+                hipLaunchKernelGGL(k_sample_hist<1>, dim3(r.hist_grid, nq), dim3(kSelBlock), 0, s, L.sscore, srows, r.ks, sst, shist);
+                hipLaunchKernelGGL(k_sample_bound_from_state<M>, dim3((nq + 255) / 256), dim3(256), 0, s, sst, nq, r.ks, gref, L.ubuf);
+                break;
+#ifdef QV_VARIANTS
+            case SampleBound::wave_lists:
+                hipLaunchKernelGGL(k_sample_bound<M>, dim3(nq, r.bparts), dim3(1024), 0, s, L.sscore, srows, r.k, gref, r.bparts > 1 ? L.sparts : L.sdist, r.bparts);
+                break;
+#endif
+        }
+        return hipSuccess;
+    });
+}
+
+// 2. query re-layout + filter constants from the bound
+static void batched_prep(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, const float* d_queries, hipStream_t s) {
+    hipLaunchKernelGGL(k_mfma_prep, dim3(r.nq_pad), dim3(64), 0, s, d_queries, r.nq, r.nq_pad, v.dim, v.dim4, r.bparts > 1 ? L.sparts : L.ubuf, r.bparts, r.ks, v.metric, L.Qt, L.cq, L.mq, L.eq, L.cnt, L.ovf,
+                       r.gmode, r.prep_what, r.ccap, r.prep_steps, r.bound == SampleBound::prep_group_min ? L.sscore : nullptr, r.sgroups);
+}
+
+// 3. MFMA filter
+static hipError_t batched_filter(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, hipStream_t s) {
+    const uint4* Qbf = reinterpret_cast<const uint4*>(L.Qt);
+    if (r.filter == MainFilter::qreg) return launch_qreg_filter(v, Qbf, L.cq, L.mq, r.nq_pad, L.cand, L.cscore, L.cnt, r.bfrows, r.cus, s);
+    // every filter kernel takes the same arguments (the operands as float32 or bfloat16 planes), some a sample's after them
+    auto go = [&](auto kernel, auto* Q, uint32_t block, auto... sample_args) {
+        const hipError_t e = set_lds(kernel, r.filter_lds); if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(r.filter_grid), dim3(block), r.filter_lds, s, v, Q, L.cq, L.mq, r.nq_pad, L.cand, L.cscore, L.cnt, sample_args...);
+        return hipSuccess;
+    };
+    return with_filter_metric(v.metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        switch (r.filter) {
+            case MainFilter::mfma_f32:      return go(k_mfma_filter<M, 4>, L.Qt, 256);
+            case MainFilter::bf16x3:        return go(k_bf16x3_filter<M>, Qbf, 256, (float*)nullptr, 0u, 1u);
+            case MainFilter::bf16x3_shared: return go(k_bf16x3_filter_shared<M, 3, 8>, Qbf, 256);
+            case MainFilter::bf16rows:      return go(k_bf16rows_filter<M>, Qbf, 256);
+            case MainFilter::w8x2:          return go(k_bf16x1_filter_w8x2<M, 4, 4>, Qbf, 512);
+            case MainFilter::w8x2_padded:   return go(k_bf16x1_filter_w8x2<M, 4, 4, true>, Qbf, 512);
+            case MainFilter::q64_plane:     return go(k_bf16rows_filter_q64<M, 4, 4>, Qbf, 512);
+            case MainFilter::q64_f32_rows:  return go(k_bf16rows_filter_q64<M, 2, 4, true>, Qbf, 512);
+#ifdef QV_VARIANTS
+            case MainFilter::mfma_f32_nj2:  return go(k_mfma_filter<M, 2>, L.Qt, 256);
+            case MainFilter::one_term_4w:   return go(k_bf16x3_filter_shared<M, 1, 8>, Qbf, 256);
+            case MainFilter::w8_4_8_2_plane: return go(k_bf16x1_filter_w8<M, 4, 8, 2, true, false>, Qbf, 512, (float*)nullptr, 0u, 1u, 0u);
+            case MainFilter::w8_16_16:      return go(k_bf16x1_filter_w8<M, 16, 16, 1, false, false>, Qbf, 512, (float*)nullptr, 0u, 1u, 0u);
+            case MainFilter::w8_8_16:       return go(k_bf16x1_filter_w8<M, 8, 16, 1, false, false>, Qbf, 512, (float*)nullptr, 0u, 1u, 0u);
+            case MainFilter::w8_16_4:       return go(k_bf16x1_filter_w8<M, 16, 4, 1, false, false>, Qbf, 512, (float*)nullptr, 0u, 1u, 0u);
+            case MainFilter::w8_16_8:       return go(k_bf16x1_filter_w8<M, 16, 8, 1, false, false>, Qbf, 512, (float*)nullptr, 0u, 1u, 0u);
+            case MainFilter::w8_8_4_deferred: return go(k_bf16x1_filter_w8<M, 8, 4, 1, false, true>, Qbf, 512, (float*)nullptr, 0u, 1u, 0u);
+            case MainFilter::w8_8_4:        return go(k_bf16x1_filter_w8<M, 8, 4, 1, false, false>, Qbf, 512, (float*)nullptr, 0u, 1u, 0u);
+            case MainFilter::w8x2_8_4:      return go(k_bf16x1_filter_w8x2<M, 8, 4>, Qbf, 512);
+#endif
+            default: return hipErrorInvalidValue;            // (qreg: above)
+        }
+    });
+}
+
+// 4. exact re-scoring + selection
+template <int M, int U>
+static hipError_t batched_rescore_select(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, const float* d_queries, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
+    const size_t lds = query_lds_bytes(v.metric, v.dim4) + 4 * 64 * sizeof(uint64_t) + (size_t)kMfmaCandCap * (sizeof(uint32_t) + sizeof(float) + sizeof(uint32_t));   // query, wave lists, survivors, lower bounds, upper bounds' keys
+    const hipError_t e = set_lds(k_rescore_select<M, U>, lds); if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_rescore_select<M, U>), dim3(r.nq), dim3(256), lds, s, v, d_queries, L.cand, L.cscore, L.cnt, r.k, d_rows_out, d_dist_out, L.ovf, L.eq);
+    return hipSuccess;
+}
+static hipError_t batched_exact(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, const float* d_queries, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
+    return with_exact_metric(v.metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        const uint32_t nq = r.nq, k = r.k, ccap = r.ccap;
+        if (r.exact == ExactPass::rescore_select) return batched_rescore_select<M, 32>(v, r, L, d_queries, d_rows_out, d_dist_out, s);
+#ifdef QV_VARIANTS
+        if (r.exact == ExactPass::rescore_select_u8) return batched_rescore_select<M, 8>(v, r, L, d_queries, d_rows_out, d_dist_out, s);
+#endif
+        // large k: intervals -> H (k-th smallest upper bound) -> survivors -> exact distances -> the k best; srows / sdist take the first
+        // selection's output (the sample's bound in sdist has been consumed by k_mfma_prep)
+        hipError_t e;
+        const dim3 cgrid((ccap + 255) / 256, nq);
+        const float* guess_bound = r.guess ? L.ubuf : (const float*)nullptr;
+        const bool tile_pass = r.exact == ExactPass::tile_pass;
+        if (r.narrow) {
+            e = set_lds(k_cand_narrow<M>, r.narrow_lds); if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k_cand_narrow<M>, dim3(nq), dim3(1024), r.narrow_lds, s, v, d_queries, L.cand, L.cscore, L.cnt, ccap, L.eq, k, guess_bound, r.ks, L.qnorms, L.lo_b, L.surv, L.nsurv, L.ovf, L.tp_cnt, tile_pass ? v.n_tiles + 1 : 0u);
+        } else {
+            e = set_lds(k_cand_qnorms<M>, (size_t)v.dim * 4); if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k_cand_qnorms<M>, dim3(nq), dim3(64), (size_t)v.dim * 4, s, d_queries, v.dim, L.qnorms);
+            hipLaunchKernelGGL(k_cand_bounds<M>, cgrid, dim3(256), 0, s, v, L.cand, L.cscore, L.cnt, ccap, L.eq, L.qnorms, L.keys_hi, L.lo_b, L.ovf, L.nsurv);
+            e = launch_select_topk(L.keys_hi, ccap, ccap, nq, k, k, L.sel_ws, L.srows, L.sdist, s, false, false); if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k_cand_survive, cgrid, dim3(256), 0, s, L.cand, L.cnt, ccap, L.lo_b, L.sdist, k, L.surv, L.nsurv, guess_bound, r.ks, L.ovf);
+        }
+        switch (r.exact) {
+            case ExactPass::tile_pass: {
+                uint2* pairs = reinterpret_cast<uint2*>(L.keys_hi);          // (the upper bounds' keys are spent: the scatter target)
+                if (!r.narrow) (void)hipMemsetAsync(L.tp_cnt, 0, (size_t)(v.n_tiles + 1) * 4, s);
+                hipLaunchKernelGGL(k_tp_count, cgrid, dim3(256), 0, s, L.surv, L.nsurv, ccap, L.tp_cnt, L.keys_ex);
+                hipLaunchKernelGGL(k_tp_scan, dim3(1), dim3(1024), 0, s, L.tp_cnt, v.n_tiles, L.tp_off);
+                hipLaunchKernelGGL(k_tp_scatter, cgrid, dim3(256), 0, s, L.surv, L.nsurv, ccap, L.tp_off, L.tp_cnt, pairs);
+                hipLaunchKernelGGL((k_tp_exact<M, 8>), dim3(v.n_tiles), dim3(64), 4 * 8192, s, v, d_queries, L.tp_off, pairs, ccap, L.qnorms, L.keys_ex);
+            } break;
+            case ExactPass::wave_per_32: {
+                const size_t lds_w = 2 * (size_t)kRsSlabBytes + (size_t)((v.dim4 + 7) / 8) * 128;
+                e = set_lds(k_cand_exact_wave<M>, lds_w); if (e != hipSuccess) return e;
+                hipLaunchKernelGGL(k_cand_exact_wave<M>, dim3(nq, ccap / 32), dim3(64), lds_w, s, v, d_queries, L.surv, L.nsurv, ccap, L.qnorms, L.keys_ex);
+            } break;
+#ifdef QV_VARIANTS
+            case ExactPass::lane_per_row: {
+                const size_t lds_x = query_lds_bytes(v.metric, v.dim4);
+                e = set_lds(k_cand_exact<M, 32>, lds_x); if (e != hipSuccess) return e;
+                hipLaunchKernelGGL((k_cand_exact<M, 32>), dim3(nq, (ccap + 255) / 256), dim3(256), lds_x, s, v, d_queries, L.surv, L.nsurv, ccap, L.qnorms, L.keys_ex);
+            } break;
+#endif
+            default: break;
+        }
+        return r.final_counted ? launch_select_topk_counted(L.keys_ex, ccap, ccap, L.nsurv, nq, k, k, d_rows_out, d_dist_out, s)
+                               : launch_select_topk(L.keys_ex, ccap, ccap, nq, k, k, L.sel_ws, d_rows_out, d_dist_out, s, false, false);
+    });
+}
+
+hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws,
+                          uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
+                          hipEvent_t ev0, hipEvent_t ev1) {
+    BatchedRoute r;
+    if (!plan_batched(v, nq, k, cus, (reinterpret_cast<uintptr_t>(d_queries) & 15u) == 0, r)) return hipErrorNotSupported;
+    const BatchedLayout L = batched_layout(d_ws, v, p, r);
+    if (L.end > L.total) return hipErrorInvalidValue;       // (cannot happen: see batched_layout)
+    hipError_t e = batched_sample_bound(v, r, L, d_queries, d_ws, s);
+    if (e != hipSuccess) return e;
+    batched_prep(v, r, L, d_queries, s);
+    if (ev0) (void)hipEventRecord(ev0, s);
+    e = batched_filter(v, r, L, s);
+    if (e != hipSuccess) return e;
+    if (ev1) (void)hipEventRecord(ev1, s);
+    e = batched_exact(v, r, L, d_queries, d_rows_out, d_dist_out, s);
+    if (e != hipSuccess) return e;
+    *d_overflow_out = L.ovf;
     return hipGetLastError();
 }
 

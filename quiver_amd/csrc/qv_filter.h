@@ -1,6 +1,7 @@
 // qv_filter.h — what the batched filter kernels share: the error model of the filters (filter_gamma), operand helpers, the
 // per-wave candidate queue and the filter epilogue (level 1 / dump / dense pass).  Included by qv_batched.hip and qv_qreg.hip.
 #pragma once
+#include <type_traits>
 #include "qv_select.h"
 
 namespace qv {
@@ -15,6 +16,16 @@ __device__ __forceinline__ float f32_up(float x) {
 }
 __device__ __forceinline__ float f32_down(float x) { return -f32_up(-x); }
 constexpr int kMfmaCandCap = 4096;        // candidate slots per query
+
+// The runtime metric as a compile-time constant for a generic lambda: f(m) with M = decltype(m)::value.  The filter kernels (and the
+// sample's score kernels) exist for COSINE, DOT and L2 only: L2 and L2SQ share the filter.
+template <typename F> static inline hipError_t with_filter_metric(int metric, F&& f) {
+    switch (metric) {
+        case QV_COSINE: return f(std::integral_constant<int, QV_COSINE>{});
+        case QV_DOT:    return f(std::integral_constant<int, QV_DOT>{});
+        default:        return f(std::integral_constant<int, QV_L2>{});
+    }
+}
 
 // |S~ - S| <= filter_gamma * |q||r| for the two filter kernels.
 //   fp32 MFMA (k_mfma_filter): a chain of K rounded fp32 multiply-adds: gamma_K = (K+2)u / (1 - (K+2)u), u = 2^-24.

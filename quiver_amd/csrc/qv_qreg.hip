@@ -328,22 +328,28 @@ bool qreg_filter_applies(const IndexView& v, uint32_t nq_pad, bool bfrows) {
     return st == 24 || st == 32 || st == 48;                       // (256 dimensions: measured behind the eight-wave kernel, 0.728 against 0.716 ms per 3 GB batch)
 }
 
+// <STEPS, in accumulation registers, in LDS>: 768 dimensions keep 32 steps' operands in the 256 accumulation registers, 12 in vector
+// registers and 4 in LDS; up to 512 dimensions everything fits the accumulation registers
+template <int M, int SS, int AA, int LL>
+static void qreg_launch(const IndexView& v, const uint4* Qbf, const float* cq, const float* mq, uint32_t nq_pad, uint32_t* cand, float* cscore, uint32_t* cnt, bool bfrows,
+                        uint32_t grid, hipStream_t s) {
+    if (bfrows) hipLaunchKernelGGL((k_qreg_filter<M, SS, AA, LL, QV_QREG_NST, true>), dim3(grid), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt);
+    else hipLaunchKernelGGL((k_qreg_filter<M, SS, AA, LL, QV_QREG_NST, false>), dim3(grid), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt);
+}
 hipError_t launch_qreg_filter(const IndexView& v, const uint4* Qbf, const float* cq, const float* mq, uint32_t nq_pad, uint32_t* cand, float* cscore,
                               uint32_t* cnt, bool bfrows, int cus, hipStream_t s) {
     const uint32_t wgs = nq_pad >> 8;
     uint32_t grid = (uint32_t)cus / wgs * wgs;
     if (!grid) grid = wgs;
     const int st = qreg_steps(v);
-    // <STEPS, in accumulation registers, in LDS>: 768 dimensions keep 32 steps' operands in the 256 accumulation registers, 12 in vector
-    // registers and 4 in LDS; up to 512 dimensions everything fits the accumulation registers
-#define QV_QR1(MMM, SS, AA, LL) { if (bfrows) hipLaunchKernelGGL((k_qreg_filter<MMM, SS, AA, LL, QV_QREG_NST, true>), dim3(grid), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); \
-                                  else hipLaunchKernelGGL((k_qreg_filter<MMM, SS, AA, LL, QV_QREG_NST, false>), dim3(grid), dim3(256), 0, s, v, Qbf, cq, mq, nq_pad, cand, cscore, cnt); }
-#define QV_QR(MMM) { if (st == 48) QV_QR1(MMM, 48, QV_QREG_ASTEPS, QV_QREG_LSTEPS) else if (st == 32) QV_QR1(MMM, 32, 32, 0) else if (st == 24) QV_QR1(MMM, 24, 24, 0) \
-                     else return hipErrorInvalidValue; }
-    if (v.metric == QV_COSINE) QV_QR(QV_COSINE) else if (v.metric == QV_DOT) QV_QR(QV_DOT) else QV_QR(QV_L2)
-#undef QV_QR
-#undef QV_QR1
-    return hipGetLastError();
+    return with_filter_metric(v.metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (st == 48) qreg_launch<M, 48, QV_QREG_ASTEPS, QV_QREG_LSTEPS>(v, Qbf, cq, mq, nq_pad, cand, cscore, cnt, bfrows, grid, s);
+        else if (st == 32) qreg_launch<M, 32, 32, 0>(v, Qbf, cq, mq, nq_pad, cand, cscore, cnt, bfrows, grid, s);
+        else if (st == 24) qreg_launch<M, 24, 24, 0>(v, Qbf, cq, mq, nq_pad, cand, cscore, cnt, bfrows, grid, s);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    });
 }
 
 }  // namespace qv
