@@ -188,6 +188,48 @@ int qv_index_search_device(qv_index* idx, const float* d_queries, uint32_t nq, u
 int qv_index_search_masked(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint64_t* mask,
                            uint32_t* rows_out, float* dist_out, uint32_t* count_out);
 
+/* ---- row sets: device-resident filters, one per query ------------------------------
+ * A filtered Collection.Search (collection.go:679-759) carries its own filter, and real filters come from a small
+ * vocabulary of facet predicates (pkg/facets: equality, range, set) that requests reuse.  A qv_rowset is such a
+ * predicate's match set as a row bitmap of ONE index, uploaded once and resident on the index's device; searches name
+ * it by handle, and every query of a call may name a different one.
+ *   create      mask = ceil(qv_index_rows/64) host words (bit r%64 of word r/64), copied; null = the empty set.
+ *               The set is NOT intersected with the live rows: tombstones set later (qv_index_remove) and rows
+ *               revived later (qv_index_update) are honoured by every search; selecting a dead row selects nothing.
+ *   growth      a set stays valid as its index grows: rows added after the set was created (or last extended by
+ *               qv_rowset_set_rows) are unselected.  No search ever reallocates a set.
+ *   set_rows    selected != 0 adds the listed rows to the set, 0 drops them; a row >= qv_index_rows is
+ *               QV_ERR_OUT_OF_RANGE (nothing is changed then).
+ *   count       rows selected, dead ones included.
+ * Threading: searches naming a set may run concurrently; qv_rowset_set_rows / qv_rowset_destroy need external
+ * exclusion against searches that name that set (the index's mutations need it anyway) — for the device-pointer form
+ * that includes searches still enqueued on the caller's stream: destroy frees the words without waiting for the
+ * device.  The index must outlive its sets. */
+typedef struct qv_rowset qv_rowset;
+int qv_rowset_create(qv_rowset** out, qv_index* idx, const uint64_t* mask);
+int qv_rowset_set_rows(qv_rowset* rs, const uint32_t* rows, uint32_t n, int selected);
+uint64_t qv_rowset_count(const qv_rowset* rs);
+void qv_rowset_destroy(qv_rowset* rs);
+
+/* qv_index_search_masked with one set PER QUERY: sets is a host array of nq handles, a null entry = every row.
+ * Query q gets the first k of the full (distance, row) ranking restricted to the live rows of sets[q] — the rows,
+ * float32 bits, order, padding and check order of qv_index_search_masked with that set as its mask;
+ * count_out[q] = min(k, live rows in sets[q]); an empty intersection is 0 results and QV_OK.  A set of another index,
+ * or a null `sets` with nq > 0, is QV_ERR_INVALID_ARG.  Up to 64 results per query the queries of a call share corpus
+ * passes, 4 / 8 / 16 per pass (16 from 9 queries on, for the metrics that accumulate in float64), each masked by its
+ * own set, and a tile none of the pass's sets selects is not read at all; above
+ * 64, runs of consecutive queries naming the same set go through the selection / ranking paths of qv_index_search over
+ * a candidate bitmap formed on the device.  Concurrent calls of up to 8 queries share passes like qv_index_search's
+ * (a front of their own: qv_index_rowset_coalesce_stats, laid out as qv_index_coalesce_stats). */
+int qv_index_search_rowsets(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
+                            uint32_t* rows_out, float* dist_out, uint32_t* count_out);
+/* Device-pointer form: queries / results on the device, `sets` still a HOST array of handles (read before the call
+ * returns).  Enqueues on `stream`, no synchronisation, nothing about a set is uploaded; every list is k long, padded
+ * with 0xFFFFFFFF / +inf past the query's matches. */
+int qv_index_search_rowsets_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
+                                   uint32_t* d_rows_out, float* d_dist_out, void* stream);
+int qv_index_rowset_coalesce_stats(qv_index* idx, uint64_t out[8]);
+
 /* Search with a negative example, the device part of HybridIndex.searchWithStrategy's exact branch
  * (hybrid_index.go:517-570; the HNSW adapter's is adapter.go:345-437): the k_fetch = max(2k, 30) nearest rows of `query`
  * (as qv_index_search), and for exactly those rows the distance to `negative` (as qv_distance_rows) — one call, one

@@ -61,6 +61,13 @@ PROTOTYPES = {
     "qv_graph_coalesce_early_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_index_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_index_search_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qv_rowset_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
+    "qv_rowset_set_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]),
+    "qv_rowset_count": (C.c_uint64, [C.c_void_p]),
+    "qv_rowset_destroy": (None, [C.c_void_p]),
+    "qv_index_search_rowsets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qv_index_search_rowsets_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qv_index_rowset_coalesce_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_index_search_negative": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, _u32p]),
     "qv_index_search_batched": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_index_search_batched_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

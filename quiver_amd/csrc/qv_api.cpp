@@ -547,15 +547,15 @@ static int coalesce_lanes(const qv_index* idx) {
     return bytes >= ((uint64_t)256 << 20) ? 1 : 4;
 }
 
-int qv_index_search(qv_index* idx, const float* queries, uint32_t nq, uint32_t k,
-                    uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
-    if (!coalesce_applies(idx, queries, nq, k, rows_out, dist_out, count_out)) return search_direct(idx, queries, nq, k, rows_out, dist_out, count_out);
+// Lanes and group sizes of a front by what a pass over this index costs (qv_index_search's front and, with the same thresholds,
+// qv_index_search_rowsets')
+static void configure_front(const qv_index* idx, qvco::Front& front) {
     {   // Lanes by size (coalesce_lanes); and on the smallest collections short shared passes: up to 32 queries a pass is the partial-chain
         // form of the scan (k_flat_scan_split_mq: 16 queries over 10 k x 768 in 87 us), beyond it the multi-query kernels (64 queries: 215 us), so
         // 16 per pass and four passes side by side carry more — callers on 10 k x 768 at 64 / 256 / 1024: 497 k / 473 k / 479 k QPS against 355 k /
         // 280 k / 107 k with passes of up to 256; 10 k x 128: 517 k / 253 k / 256 k against 508 k / 181 k / 101 k.  QV_FLAT_SMALL_GROUP overrides (measurements).
         const int lanes = coalesce_lanes(idx);
-        idx->front.set_lanes(lanes, lanes == 1);
+        front.set_lanes(lanes, lanes == 1);
         static const int small_group = getenv("QV_FLAT_SMALL_GROUP") ? atoi(getenv("QV_FLAT_SMALL_GROUP")) : 0;
         const uint64_t bytes = (uint64_t)idx->n_rows * idx->dim4 * 16;
         // (64 - 256 MiB, still four lanes: 30 k x 768 at 256 / 1024 callers 445 k / 483 k QPS with passes of up to 64 against 425 k / 210 k with 256 and
@@ -565,8 +565,14 @@ int qv_index_search(qv_index* idx, const float* queries, uint32_t nq, uint32_t k
         // with 256; 300 k x 768 374 k / 375 k / 355 k against 302 k / 289 k / 405 k; 1M x 768 200 k / 191 k / 194 k against 207 k / 289 k / 304 k: 128 below 1 GiB)
         static const int big_group = getenv("QV_FLAT_BIG_GROUP") ? atoi(getenv("QV_FLAT_BIG_GROUP")) : 0;
         const uint32_t one_lane = big_group > 0 ? (uint32_t)std::max(big_group, 8) : (bytes < ((uint64_t)1 << 30) ? 128u : 256u);
-        idx->front.set_max_group(lanes > 1 ? (small_group > 0 ? (uint32_t)std::max(small_group, 8) : by_size) : one_lane);
+        front.set_max_group(lanes > 1 ? (small_group > 0 ? (uint32_t)std::max(small_group, 8) : by_size) : one_lane);
     }
+}
+
+int qv_index_search(qv_index* idx, const float* queries, uint32_t nq, uint32_t k,
+                    uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    if (!coalesce_applies(idx, queries, nq, k, rows_out, dist_out, count_out)) return search_direct(idx, queries, nq, k, rows_out, dist_out, count_out);
+    configure_front(idx, idx->front);
     char err[256]; err[0] = 0;
     const int rc = idx->front.submit(
         0, queries, nq, idx->dim, k, rows_out, dist_out, count_out, nullptr,
@@ -687,6 +693,277 @@ int qv_index_search_masked(qv_index* idx, const float* queries, uint32_t nq, uin
         memcpy(rows_out + (size_t)q * k, hr + (size_t)q * kk, (size_t)kk * sizeof(uint32_t));
         memcpy(dist_out + (size_t)q * k, hd + (size_t)q * kk, (size_t)kk * sizeof(float));
         for (uint32_t i = kk; i < k; i++) { rows_out[(size_t)q * k + i] = 0xFFFFFFFFu; dist_out[(size_t)q * k + i] = __builtin_inff(); }
+    }
+    return QV_OK;
+}
+
+// ---------------------------------------------------------------- row sets: one device-resident filter per query --
+int qv_rowset_create(qv_rowset** out, qv_index* idx, const uint64_t* mask) {
+    if (!out) return fail(QV_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    HIPCHK(hipSetDevice(idx->device));
+    qv_rowset* rs = new (std::nothrow) qv_rowset();
+    if (!rs) return fail(QV_ERR_OOM, "out of host memory");
+    rs->idx = idx; rs->device = idx->device;
+    rs->words = (uint32_t)(((uint64_t)idx->n_rows + 63) / 64);
+    rs->host.assign(rs->words, 0);
+    if (mask && rs->words) {
+        memcpy(rs->host.data(), mask, (size_t)rs->words * 8);
+        if (idx->n_rows & 63) rs->host[rs->words - 1] &= (1ull << (idx->n_rows & 63)) - 1;    // rows that do not exist yet start unselected
+    }
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&rs->d_bits), std::max<size_t>((size_t)rs->words * 8, 256));
+    if (e == hipSuccess && rs->words) e = hipMemcpy(rs->d_bits, rs->host.data(), (size_t)rs->words * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);           // (the index's streams are non-blocking: nothing of theirs may overtake the upload)
+    if (e != hipSuccess) {
+        (void)hipFree(rs->d_bits); delete rs;
+        return fail(e == hipErrorOutOfMemory ? QV_ERR_OOM : QV_ERR_DEVICE, "row set upload failed: %s", hipGetErrorString(e));
+    }
+    *out = rs;
+    return QV_OK;
+}
+
+int qv_rowset_set_rows(qv_rowset* rs, const uint32_t* rows, uint32_t n, int selected) {
+    if (!rs) return fail(QV_ERR_INVALID_ARG, "row set is null");
+    if (n == 0) return QV_OK;
+    if (!rows) return fail(QV_ERR_INVALID_ARG, "rows is null");
+    qv_index* idx = rs->idx;
+    for (uint32_t i = 0; i < n; i++)
+        if (rows[i] >= idx->n_rows) return fail(QV_ERR_OUT_OF_RANGE, "row %u out of range (rows: %u)", rows[i], idx->n_rows);
+    HIPCHK(hipSetDevice(idx->device));
+    const uint32_t need = (uint32_t)(((uint64_t)idx->n_rows + 63) / 64);
+    if (need > rs->words) {                                           // the index has grown since: the new rows' words, all unselected
+        hipError_t e = regrow(&rs->d_bits, (size_t)rs->words * 8, (size_t)need * 8);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? QV_ERR_OOM : QV_ERR_DEVICE, "row set growth failed: %s", hipGetErrorString(e));
+        rs->host.resize(need, 0);
+        rs->words = need;
+    }
+    { const int rc0 = rs->stage.ensure((size_t)n * sizeof(uint32_t)); if (rc0 != QV_OK) return rc0; }
+    uint32_t* d = static_cast<uint32_t*>(rs->stage.p);
+    hipError_t e = hipMemcpy(d, rows, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = qv::launch_rowset_set_rows(rs->d_bits, d, n, selected, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row set update failed: %s", hipGetErrorString(e));
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t bit = 1ull << (rows[i] & 63);
+        if (selected) rs->host[rows[i] >> 6] |= bit; else rs->host[rows[i] >> 6] &= ~bit;
+    }
+    return QV_OK;
+}
+
+uint64_t qv_rowset_count(const qv_rowset* rs) {
+    if (!rs) return 0;
+    uint64_t n = 0;
+    for (uint64_t w : rs->host) n += (uint64_t)__builtin_popcountll(w);
+    return n;
+}
+
+void qv_rowset_destroy(qv_rowset* rs) {
+    if (!rs) return;
+    // (no device-wide wait: the caller's exclusion — include/qv.h — says that no search naming this set is in flight or enqueued, and
+    // nothing else reads its words)
+    (void)hipSetDevice(rs->device);
+    (void)hipFree(rs->d_bits);
+    rs->stage.release();
+    delete rs;
+}
+
+static qv::RowSetRef rowset_ref(const qv_rowset* rs) { return rs ? qv::RowSetRef{rs->d_bits, rs->words, 0} : qv::RowSetRef{nullptr, 0, 0}; }
+// live rows of a set, from the host mirrors (the k > 64 paths clamp their list length to it, as qv_index_search_masked does)
+static uint64_t rowset_live(const qv_index* idx, const qv_rowset* rs) {
+    if (!rs) return idx->n_live;
+    uint64_t n = 0;
+    const size_t words = std::min<size_t>(rs->host.size(), idx->alive_host.size());
+    for (size_t w = 0; w < words; w++) n += (uint64_t)__builtin_popcountll(rs->host[w] & idx->alive_host[w]);
+    return n;
+}
+
+// How a call is cut into device work.  Up to kMaxFusedK results and two or more queries: ONE piece, the multi-query scans with a set
+// per query (qv_rowset.hip).  Otherwise runs of consecutive queries naming the same set, each through the paths of qv_index_search
+// over the candidate bitmap alive & set, formed on the device (k_rowset_and) — a single query takes the single-launch scans that
+// way, longer lists the selection and ranking paths.
+struct RowsetPiece { uint32_t q0, nq, kk; bool multi; };
+static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const qv_rowset* const* sets, std::vector<RowsetPiece>& pieces) {
+    const qv::ScanPlan plan = qv::plan_scan((idx->n_rows + 63) / 64, idx->cus);
+    pieces.clear();
+    if (k <= (uint32_t)qv::kMaxFusedK && nq >= 2) {
+        pieces.push_back(RowsetPiece{0, nq, k, true});
+        return qv::rowset_workspace_bytes(plan, nq, k, idx->dim4);
+    }
+    size_t ws = 0;
+    for (uint32_t q = 0; q < nq;) {
+        uint32_t e = q + 1;
+        while (e < nq && sets[e] == sets[q]) e++;
+        // (up to kMaxFusedK the lists are k long whatever the set holds: the scans pad, nothing is counted on the host)
+        const uint32_t kk = k <= (uint32_t)qv::kMaxFusedK ? k : (uint32_t)std::min<uint64_t>(k, rowset_live(idx, sets[q]));
+        pieces.push_back(RowsetPiece{q, e - q, kk, false});
+        if (kk) ws = std::max(ws, search_ws_bytes(idx, e - q, kk, k));
+        q = e;
+    }
+    return ws;
+}
+// enqueue the pieces on s: lists [nq][k], padded past every query's matches.  d_mask: (rows + 63) / 64 words for the candidate bitmaps.
+static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets, const std::vector<RowsetPiece>& pieces,
+                           void* ws, uint64_t* d_mask, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, uint32_t* d_tickets) {
+    const qv::IndexView v = idx->view();
+    const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
+    for (const RowsetPiece& p : pieces) {
+        uint32_t* r_out = d_rows_out + (size_t)p.q0 * k;
+        float* d_out = d_dist_out + (size_t)p.q0 * k;
+        const float* q = d_queries + (size_t)p.q0 * idx->dim;
+        if (p.multi) {
+            std::vector<qv::RowSetRef> refs(p.nq);
+            for (uint32_t i = 0; i < p.nq; i++) refs[i] = rowset_ref(sets[p.q0 + i]);
+            hipEvent_t ev0 = nullptr, ev1 = nullptr;
+            if (idx->profiling && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
+                std::lock_guard<std::mutex> g(idx->prof_mu);
+                idx->prof_events.emplace_back(ev0, ev1);
+            }
+            hipError_t e = qv::launch_rowset_topk(v, plan, q, p.nq, k, refs.data(), ws, r_out, d_out, s, ev0, ev1);
+            if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set scan launch failed: %s", hipGetErrorString(e));
+            continue;
+        }
+        if (p.kk == 0) {
+            hipError_t e = qv::launch_rowset_pad(r_out, d_out, (size_t)p.nq * k, s);
+            if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set pad launch failed: %s", hipGetErrorString(e));
+            continue;
+        }
+        const uint64_t* cand = nullptr;
+        if (sets[p.q0]) {
+            hipError_t e = qv::launch_rowset_and(v, rowset_ref(sets[p.q0]), d_mask, s);
+            if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set bitmap launch failed: %s", hipGetErrorString(e));
+            cand = d_mask;
+        }
+        const int rc = enqueue_search(idx, q, p.nq, p.kk, k, ws, 0, r_out, d_out, s, cand, p.nq == 1 ? d_tickets : nullptr);
+        if (rc != QV_OK) return rc;
+    }
+    return QV_OK;
+}
+
+static int rowsets_check(const qv_index* idx, uint32_t nq, const qv_rowset* const* sets) {
+    if (!sets) return fail(QV_ERR_INVALID_ARG, "sets is null");
+    for (uint32_t q = 0; q < nq; q++)
+        if (sets[q] && sets[q]->idx != idx) return fail(QV_ERR_INVALID_ARG, "row set of query %u belongs to another index", q);
+    return QV_OK;
+}
+
+// one call's worth of queries in a context of the caller's own
+static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
+                          uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (nq == 0) return QV_OK;
+    if (!queries || !count_out || !sets) return fail(QV_ERR_INVALID_ARG, "queries/sets/count_out is null");
+    { const int rc0 = rowsets_check(idx, nq, sets); if (rc0 != QV_OK) return rc0; }
+    if (idx->n_live == 0) { for (uint32_t q = 0; q < nq; q++) count_out[q] = 0; return QV_OK; }      // exact.go:96-98
+    if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");                             // exact.go:104-106
+    if (!rows_out || !dist_out) return fail(QV_ERR_INVALID_ARG, "rows_out/dist_out is null");
+    if (nq > kHostBatch) {
+        for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {
+            const int rc0 = rowsets_direct(idx, queries + (size_t)q0 * idx->dim, std::min(kHostBatch, nq - q0), k, sets + q0,
+                                           rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
+            if (rc0 != QV_OK) return rc0;
+        }
+        return QV_OK;
+    }
+    HIPCHK(hipSetDevice(idx->device));
+    std::vector<RowsetPiece> pieces;
+    const size_t ws_bytes = rowsets_plan(idx, nq, k, sets, pieces);
+    bool any = false;
+    for (const RowsetPiece& p : pieces) any = any || p.kk != 0;
+    if (!any) {                                                       // no set holds a live row: nothing to run
+        for (size_t i = 0; i < (size_t)nq * k; i++) { rows_out[i] = 0xFFFFFFFFu; dist_out[i] = __builtin_inff(); }
+        for (uint32_t q = 0; q < nq; q++) count_out[q] = 0;
+        return QV_OK;
+    }
+    SearchCtx* c = nullptr;
+    int rc = acquire_ctx(idx, &c);
+    if (rc != QV_OK) return rc;
+    CtxGuard guard{idx, c};
+    const size_t words = ((size_t)idx->n_rows + 63) / 64;
+    const size_t qbytes = (size_t)nq * idx->dim * sizeof(float);
+    const size_t obytes = (size_t)nq * k * sizeof(uint32_t);
+    if ((rc = c->d_mask.ensure(words * 8)) || (rc = c->d_q.ensure(qbytes)) || (rc = c->h_q.ensure(qbytes)) || (rc = c->d_rows.ensure(obytes)) ||
+        (rc = c->d_dist.ensure(obytes)) || (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(obytes)) || (rc = c->ws.ensure(ws_bytes)))
+        return rc;
+    if (!c->tickets.p) { if ((rc = c->tickets.ensure(256))) return rc; HIPCHK(hipMemsetAsync(c->tickets.p, 0, 256, c->stream)); }   // (on the stream that reads them: see stream_workspace)
+    memcpy(c->h_q.p, queries, qbytes);
+    HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, qbytes, hipMemcpyHostToDevice, c->stream));
+    rc = rowsets_enqueue(idx, static_cast<const float*>(c->d_q.p), nq, k, sets, pieces, c->ws.p, static_cast<uint64_t*>(c->d_mask.p),
+                         static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<uint32_t*>(c->tickets.p));
+    if (rc != QV_OK) return rc;
+    HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, obytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(rows_out, c->h_rows.p, obytes);
+    memcpy(dist_out, c->h_dist.p, obytes);
+    for (uint32_t q = 0; q < nq; q++) {                               // a list's results end where its padding begins (no row is 0xFFFFFFFF)
+        uint32_t n = 0;
+        while (n < k && rows_out[(size_t)q * k + n] != 0xFFFFFFFFu) n++;
+        for (uint32_t i = n; i < k; i++) { rows_out[(size_t)q * k + i] = 0xFFFFFFFFu; dist_out[(size_t)q * k + i] = __builtin_inff(); }
+        count_out[q] = n;
+    }
+    return QV_OK;
+}
+
+int qv_index_search_rowsets(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
+                            uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    // callers that may share a pass: qv_index_search's rule, with a valid set per query on top (a request that fails a check runs
+    // on its own and reports its error in the usual order)
+    if (!coalesce_applies(idx, queries, nq, k, rows_out, dist_out, count_out) || !sets || rowsets_check(idx, nq, sets) != QV_OK)
+        return rowsets_direct(idx, queries, nq, k, sets, rows_out, dist_out, count_out);
+    configure_front(idx, idx->front_rs);
+    char err[256]; err[0] = 0;
+    const int rc = idx->front_rs.submit(
+        0, queries, nq, idx->dim, k, rows_out, dist_out, count_out, nullptr,
+        [&] { return rowsets_direct(idx, queries, nq, k, sets, rows_out, dist_out, count_out); },
+        [&](qvco::Group& g, auto&) {
+            g.size_outputs(false);
+            std::vector<const qv_rowset*> all(g.nq, nullptr);         // the members' sets side by side, in the order of the group's query block
+            for (uint32_t mi = 0; mi < g.n_mem; mi++) {
+                const qvco::Member& m = g.mbuf[mi];
+                const qv_rowset* const* ms = static_cast<const qv_rowset* const*>(m.tag);
+                for (uint32_t i = 0; i < m.nq; i++) all[m.q0 + i] = ms[i];
+            }
+            return rowsets_direct(idx, g.queries(), g.nq, g.kmax, all.data(), g.rows.data(), g.dist.data(), g.count.data());
+        },
+        [] { return qv_last_error(); }, err, sizeof(err), sets);
+    if (rc != QV_OK && err[0]) return fail(rc, "%s", err);
+    return rc;
+}
+
+int qv_index_rowset_coalesce_stats(qv_index* idx, uint64_t out[8]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    idx->front_rs.stats.read(out);
+    return QV_OK;
+}
+
+int qv_index_search_rowsets_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
+                                   uint32_t* d_rows_out, float* d_dist_out, void* stream) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (nq == 0) return QV_OK;
+    if (!d_queries || !d_rows_out || !d_dist_out) return fail(QV_ERR_INVALID_ARG, "null device pointer");
+    { const int rc0 = rowsets_check(idx, nq, sets); if (rc0 != QV_OK) return rc0; }
+    if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (idx->n_live == 0 || idx->n_rows == 0) {
+        hipError_t e = qv::launch_rowset_pad(d_rows_out, d_dist_out, (size_t)nq * k, s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set pad launch failed: %s", hipGetErrorString(e));
+        return QV_OK;
+    }
+    for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {                // bound the workspace, as the host-pointer form does
+        const uint32_t m = std::min(kHostBatch, nq - q0);
+        std::vector<RowsetPiece> pieces;
+        const size_t ws_bytes = (rowsets_plan(idx, m, k, sets + q0, pieces) + 255) / 256 * 256;
+        const size_t words = ((size_t)idx->n_rows + 63) / 64;
+        void* ws = nullptr;
+        std::unique_lock<std::mutex> ws_hold;
+        uint32_t* tickets = nullptr;
+        int rc = stream_workspace(idx, s, ws_bytes + words * 8, &ws, &ws_hold, &tickets);
+        if (rc != QV_OK) return rc;
+        rc = rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, sets + q0, pieces, ws, reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes),
+                             d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, s, tickets);
+        if (rc != QV_OK) return rc;
     }
     return QV_OK;
 }

@@ -111,6 +111,9 @@ struct qv_index {
     // pass together (qv_coalesce.h): one pass in flight — a flat scan is HBM-bound, a second one beside it only halves both —
     // and up to 256 queries per group, the size the matrix-core filter walks the corpus once for
     qvco::Front front{1, 256, 4};
+    // the same for qv_index_search_rowsets: filtered callers share passes among themselves (a member's tag = its set handles); a front
+    // of its own, so that the unfiltered one's groups, lanes and statistics are what they were
+    qvco::Front front_rs{1, 256, 4};
 
     qv::IndexView view() const {
         qv::IndexView v;
@@ -122,3 +125,15 @@ struct qv_index {
     size_t bf16_tile_bytes() const { return (size_t)(((dim4 + 1) / 2 + 1) / 2) * 2 * 64 * 16; }   // whole 16-dim steps (k_bf16_plane's layout)
 };
 
+
+// A set of rows of ONE index as a bitmap on that index's device (include/qv.h "row sets").  `words` 64-row words are valid: rows
+// beyond them are unselected, which is how a set stays valid while its index grows — the scans take (pointer, words) per query and
+// never touch the allocation.  host mirrors d_bits (qv_rowset_count, and the match counts of the k > 64 paths).
+struct qv_rowset {
+    qv_index* idx = nullptr;
+    int device = 0;                            // idx->device (kept here: destroying a set does not touch its index)
+    uint64_t* d_bits = nullptr;
+    uint32_t words = 0;
+    std::vector<uint64_t> host;
+    Buf stage;                                 // row ids of qv_rowset_set_rows
+};

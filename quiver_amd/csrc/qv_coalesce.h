@@ -80,6 +80,8 @@ class SpinLock {
 struct Member {                       // one caller's request inside a group
     uint32_t q0, nq, k;               // its queries are rows q0 .. q0+nq-1 of the group's block
     uint32_t* rows_out; float* dist_out; uint32_t* count_out; uint32_t* evals_out;
+    const void* tag = nullptr;        // opaque, the caller's own (submit's last argument): what run() needs to know per member beyond its
+                                      // queries — qv_index_search_rowsets hands over its array of nq set handles, valid until the call returns
 };
 
 struct Group {
@@ -164,10 +166,11 @@ class Front {
     // run(Group&, early): run g.queries() (g.nq of them, lists of g.kmax) into g.rows / g.dist / g.count (/ g.evals); returns a
     //               status; may call early() once (see there)
     // last_error(): the thread-local message of a failed run, copied for the members
+    // tag:          kept in the caller's Member record (g.mbuf[i].tag) for run() to read; the front never looks at it
     template <class Solo, class Run, class LastErr>
     int submit(uint64_t key, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                uint32_t* rows_out, float* dist_out, uint32_t* count_out, uint32_t* evals_out,
-               Solo&& solo, Run&& run, LastErr&& last_error, char* err_out, size_t err_cap) {
+               Solo&& solo, Run&& run, LastErr&& last_error, char* err_out, size_t err_cap, const void* tag = nullptr) {
         std::shared_ptr<Group> grp, fresh;
         bool leader = false, has_lane = false, wake_leader = false, counted = false;
         uint32_t my = 0, q0 = 0;                                               // this caller's place in its group
@@ -233,7 +236,7 @@ class Front {
             }
         }
         if (grp) {                                                             // this caller's record and queries, in its own place
-            grp->mbuf[my] = Member{q0, nq, k, rows_out, dist_out, count_out, evals_out};
+            grp->mbuf[my] = Member{q0, nq, k, rows_out, dist_out, count_out, evals_out, tag};
             memcpy(grp->qbuf.get() + (size_t)q0 * dim, queries, (size_t)nq * dim * sizeof(float));
             grp->copied.fetch_add(1, std::memory_order_release);
         }

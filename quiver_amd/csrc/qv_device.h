@@ -168,6 +168,25 @@ hipError_t launch_lookup_payload(const uint32_t* d_packed, const uint32_t* d_bas
 hipError_t launch_merge_pairs(const float* d_dist, const uint32_t* d_rows, uint32_t n_lists, uint32_t k,
                               uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
 
+// --- row sets (qv_rowset.hip): one candidate bitmap per query ----------------------------------
+// A query's set as the kernels see it: `words` 64-row words at `bits` (rows beyond them are unselected); bits == null: every row.
+struct RowSetRef { const uint64_t* bits; uint32_t words; uint32_t pad_; };
+// Exact multi-query scan, k <= kMaxFusedK, query q restricted to alive & h_sets[q] (a HOST array: the table travels to the device as
+// kernel arguments, nothing is uploaded).  d_ws: rowset_workspace_bytes.  Writes [nq][k] lists padded with 0xFFFFFFFF / +inf.
+size_t rowset_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t dim4);
+hipError_t launch_rowset_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, const RowSetRef* h_sets,
+                              void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// d_out[t] = alive[t] & set[t] over the index's tiles (the candidate bitmap of the single-query and k > 64 paths)
+hipError_t launch_rowset_and(const IndexView& v, const RowSetRef& set, uint64_t* d_out, hipStream_t s);
+// n padding entries (0xFFFFFFFF / +inf): the lists of queries whose set holds no live row
+hipError_t launch_rowset_pad(uint32_t* d_rows, float* d_dist, size_t n, hipStream_t s);
+// set / clear the listed rows' bits (d_rows on the device, every row < words * 64)
+hipError_t launch_rowset_set_rows(uint64_t* d_bits, const uint32_t* d_rows, uint32_t n, int selected, hipStream_t s);
+// pieces of the multi-query scans that qv_rowset.hip shares with qv_scan.hip: the query blocks of the scalar-operand form
+// (qblk[group][dim4 * 4][qb], qb = 4, 8 or — the float64-accumulating metrics — 16) and the merge of partial[nq][n_lists][k] into [nq][k] results
+hipError_t launch_prep_qblk(int metric, uint32_t qb, const float* d_queries, uint32_t nq, uint32_t dim, uint32_t dim4, void* d_qblk, hipStream_t s);
+hipError_t launch_merge_lists(const uint64_t* d_partial, uint32_t n_lists, uint32_t nq, uint32_t k, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+
 // Batched path: fp32-MFMA filter + exact re-scoring (results identical to launch_flat_topk).
 // *d_overflow_out -> [nq] flags (device): 1 = candidate buffer overflowed, caller must redo that
 // query with launch_flat_topk.

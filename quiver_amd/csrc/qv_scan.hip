@@ -1305,6 +1305,28 @@ hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* 
 
 
 
+// for qv_rowset.hip: the multi-query scans' query blocks and list merge, as launch_flat_topk issues them
+hipError_t launch_prep_qblk(int metric, uint32_t qb, const float* d_queries, uint32_t nq, uint32_t dim, uint32_t dim4, void* d_qblk, hipStream_t s) {
+    if (nq == 0 || (qb != 4 && qb != 8 && qb != 16)) return hipErrorInvalidValue;
+    const uint32_t groups = (nq + qb - 1) / qb, per = dim4 * 4 * qb;
+    QV_DISPATCH_METRIC(metric, {
+        using QT = typename MT<MM>::Q;
+        if (qb == 16) {                                               // (the float64-accumulating metrics only, as in launch_flat_topk)
+            if constexpr (MM == QV_L2SQ || MM == QV_COSINE_F32 || MM == QV_L2_F32 || MM == QV_DOT_F32) return hipErrorInvalidValue;
+            else hipLaunchKernelGGL((k_prep_qblk<MM, 16>), dim3((per + 255) / 256, groups), dim3(256), 0, s, d_queries, nq, dim, dim4, static_cast<QT*>(d_qblk));
+        } else if (qb == 8) hipLaunchKernelGGL((k_prep_qblk<MM, 8>), dim3((per + 255) / 256, groups), dim3(256), 0, s, d_queries, nq, dim, dim4, static_cast<QT*>(d_qblk));
+        else hipLaunchKernelGGL((k_prep_qblk<MM, 4>), dim3((per + 255) / 256, groups), dim3(256), 0, s, d_queries, nq, dim, dim4, static_cast<QT*>(d_qblk));
+    });
+    return hipGetLastError();
+}
+hipError_t launch_merge_lists(const uint64_t* d_partial, uint32_t n_lists, uint32_t nq, uint32_t k, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
+    if (k == 0 || k > (uint32_t)kMaxFusedK || n_lists == 0 || nq == 0) return hipErrorInvalidValue;
+    const uint32_t total = n_lists * k;
+    const uint32_t mblock = total >= 16 * 64 * 4 ? kMergeBlock : (total >= 4 * 64 ? 256 : 64);
+    hipLaunchKernelGGL(k_merge_lists, dim3(nq), dim3(mblock), 0, s, d_partial, n_lists, k, d_rows_out, d_dist_out);
+    return hipGetLastError();
+}
+
 // the exact scan for the queries whose flags are set, decided and listed on the device (see k_flat_scan_redo)
 size_t redo_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k) {
     return ((size_t)kRedoSlots * p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + ((size_t)nq * 4 + 255) / 256 * 256 + ((size_t)(nq + 1) * 4 + 255) / 256 * 256;

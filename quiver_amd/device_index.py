@@ -140,6 +140,69 @@ class DeviceIndex:
         check(lib().qv_index_search_masked(self._h, q.ctypes.data, nq, k, m.ctypes.data, rows.ctypes.data, dist.ctypes.data, cnt.ctypes.data))
         return rows, dist, cnt
 
+    # ---- row sets: device-resident filters, one per query ----
+    def _mask_words(self, mask) -> np.ndarray:
+        m = np.asarray(mask)
+        words = (self.rows() + 63) // 64
+        if m.dtype == np.bool_:
+            if m.size != self.rows():
+                raise ValueError("mask must have one entry per row")
+            pad = np.zeros(words * 64, dtype=np.uint8); pad[:m.size] = m
+            m = np.packbits(pad, bitorder="little").view(np.uint64)
+        m = np.ascontiguousarray(m, dtype=np.uint64)
+        if m.size != words:
+            raise ValueError("mask must have ceil(rows/64) words")
+        return m
+
+    def rowset(self, mask_or_rows=None, *, rows=None) -> "RowSet":
+        """a set of this index's rows, resident on its device (qv_rowset_create): from a bool mask [rows], packed uint64 words
+        [ceil(rows/64)], a list of row numbers (any other integer array), or None for the empty set.  A uint64 array is ALWAYS read as
+        packed words: row numbers of that dtype (or of any other) go in `rows=`, which is never read as a mask.  Rows added to the
+        index later start unselected; tombstones are honoured by the searches, not folded in here."""
+        return RowSet(self, mask_or_rows, rows=rows)
+
+    def _set_handles(self, sets, nq: int):
+        if sets is None or isinstance(sets, RowSet):
+            sets = [sets] * nq
+        sets = list(sets)
+        if len(sets) != nq:
+            raise ValueError("sets must be a RowSet, None, or one of either per query (%d), got %d" % (nq, len(sets)))
+        arr = (C.c_void_p * max(nq, 1))()
+        for i, s in enumerate(sets):
+            if s is not None and not isinstance(s, RowSet):
+                raise TypeError("sets[%d] is not a RowSet" % i)
+            arr[i] = None if s is None else s.handle.value
+        return arr, sets                                   # (the list keeps the RowSet objects alive across the call)
+
+    def search_rowsets(self, queries, k: int, sets):
+        """exact top-k of every query among the live rows of ITS set (qv_index_search_rowsets): `sets` is a RowSet, None (every row),
+        or a sequence of one of either per query.  -> (rows [nq,k] uint32, dist [nq,k] float32, count [nq] uint32)"""
+        q = _f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dimension mismatch: expected {self.dim}, got {q.shape[1]}")
+        nq = q.shape[0]
+        arr, keep = self._set_handles(sets, nq)
+        kk = max(int(k), 0)
+        rows = np.full((nq, max(kk, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full((nq, max(kk, 1)), np.inf, dtype=np.float32)
+        count = np.zeros(nq, dtype=np.uint32)
+        check(lib().qv_index_search_rowsets(self._h, q.ctypes.data, nq, kk, arr, rows.ctypes.data, dist.ctypes.data, count.ctypes.data))
+        del keep
+        return rows[:, :kk], dist[:, :kk], count
+
+    def search_rowsets_device(self, d_queries: int, nq: int, k: int, sets, d_rows_out: int, d_dist_out: int, stream: int = 0):
+        """the same with queries / results on the device; enqueues on `stream`, no synchronisation (qv_index_search_rowsets_device)"""
+        arr, keep = self._set_handles(sets, nq)
+        check(lib().qv_index_search_rowsets_device(self._h, d_queries, nq, k, arr, d_rows_out, d_dist_out, stream))
+        del keep
+
+    def rowset_coalesce_stats(self) -> dict:
+        out = (C.c_uint64 * 8)()
+        check(lib().qv_index_rowset_coalesce_stats(self._h, out))
+        return dict(zip(("solo", "led", "rode", "groups", "group_queries", "lingers", "linger_ns", "group_pass_ns"), [int(x) for x in out]))
+
     def search_negative(self, query, negative, k_fetch: int):
         """-> (rows [k_fetch], dist, neg_dist, count): qv_index_search_negative"""
         q, n = _f32c(query).ravel(), _f32c(negative).ravel()
@@ -180,6 +243,57 @@ class DeviceIndex:
         ms, n = C.c_double(0), C.c_uint64(0)
         check(lib().qv_index_profile_read(self._h, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
+
+
+class RowSet:
+    """One ``qv_rowset``: a facet predicate's match set as a row bitmap on the index's device, uploaded once and named by handle in
+    DeviceIndex.search_rowsets.  The index must outlive every search that names the set."""
+
+    def __init__(self, index: DeviceIndex, mask_or_rows=None, *, rows=None):
+        self._h = C.c_void_p()
+        self._index = index                                # the index must outlive its sets
+        if rows is not None and mask_or_rows is not None:
+            raise ValueError("give a mask or rows=, not both")
+        m = None if mask_or_rows is None else np.asarray(mask_or_rows)
+        listed = m is not None and m.dtype != np.bool_ and m.dtype != np.uint64       # uint64 = packed mask words; row numbers of that dtype: rows=
+        if rows is not None:
+            m, listed = np.asarray(rows), True
+            if m.size and (m.dtype.kind not in "iu" or int(m.min()) < 0 or int(m.max()) > 0xFFFFFFFF):
+                raise ValueError("rows= must hold row numbers")
+        words = None if (m is None or listed) else index._mask_words(m)
+        check(lib().qv_rowset_create(C.byref(self._h), index.handle, None if words is None else words.ctypes.data))
+        if listed and m.size:
+            self.set_rows(m, True)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set_rows(self, rows, selected: bool = True):
+        """add (selected) or drop the listed rows"""
+        r = np.ascontiguousarray(rows, dtype=np.uint32).ravel()
+        check(lib().qv_rowset_set_rows(self._h, r.ctypes.data, r.size, 1 if selected else 0))
+
+    def count(self) -> int:
+        """rows selected, dead ones included"""
+        return int(lib().qv_rowset_count(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().qv_rowset_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceGraph:

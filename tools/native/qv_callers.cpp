@@ -110,4 +110,58 @@ int qvc_run(int kind, void* handle, const float* queries, uint32_t n_queries, ui
     return first_rc.load();
 }
 
+// Filtered callers: thread t searches with ITS OWN filter, one query per call in a closed loop (a filtered Collection.Search per
+// request, collection.go:679-759).  masks == null: qv_index_search_rowsets with the device-resident set sets[t % n_sets]; otherwise
+// qv_index_search_masked with the host bitmap masks + (t % n_sets) * mask_words — what the same threads had to do before there were
+// row sets.  Thread t walks the query pool from t with stride n_threads.  No result is kept (tests/test_gpu_rowsets.py checks results).
+int qvc_run_rowsets(void* index, const float* queries, uint32_t n_queries, uint32_t dim, uint32_t k, uint32_t n_threads, double seconds,
+                    uint64_t max_calls_per_thread, void* const* sets, const uint64_t* masks, uint64_t mask_words, uint32_t n_sets,
+                    uint64_t* calls_out, uint64_t* errors_out, double* elapsed_s_out, double* lat_p50_us, double* lat_p99_us) {
+    if (!index || !queries || !n_queries || !n_threads || !k || !n_sets || (!sets && !masks)) return QV_ERR_INVALID_ARG;
+    qv_index* idx = static_cast<qv_index*>(index);
+    std::atomic<uint64_t> calls{0}, errors{0};
+    std::atomic<int> ready{0}, first_rc{0}; std::atomic<bool> go{false};
+    std::vector<std::vector<float>> lat(n_threads);
+    std::vector<std::thread> th;
+    std::chrono::steady_clock::time_point t_start;
+    for (uint32_t t = 0; t < n_threads; t++)
+        th.emplace_back([&, t] {
+            std::vector<uint32_t> rows(k); std::vector<float> dist(k); uint32_t count = 0;
+            const qv_rowset* mine = masks ? nullptr : static_cast<const qv_rowset*>(sets[t % n_sets]);
+            const uint64_t* mask = masks ? masks + (size_t)(t % n_sets) * mask_words : nullptr;
+            lat[t].reserve(4096);
+            ready.fetch_add(1);
+            while (!go.load(std::memory_order_acquire)) std::this_thread::yield();
+            const auto deadline = t_start + std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(seconds));
+            uint64_t n = 0;
+            for (uint32_t qi = t % n_queries;; qi = (qi + n_threads) % n_queries) {
+                if (max_calls_per_thread && n >= max_calls_per_thread) break;
+                const auto t0 = std::chrono::steady_clock::now();
+                if (t0 >= deadline) break;
+                const float* q = queries + (size_t)qi * dim;
+                const int rc = mask ? qv_index_search_masked(idx, q, 1, k, mask, rows.data(), dist.data(), &count)
+                                    : qv_index_search_rowsets(idx, q, 1, k, &mine, rows.data(), dist.data(), &count);
+                const auto t1 = std::chrono::steady_clock::now();
+                n++;
+                if (rc != QV_OK) { errors.fetch_add(1); int z = 0; first_rc.compare_exchange_strong(z, rc); continue; }
+                lat[t].push_back(std::chrono::duration<float, std::micro>(t1 - t0).count());
+            }
+            calls.fetch_add(n);
+        });
+    while (ready.load() < (int)n_threads) std::this_thread::yield();
+    t_start = std::chrono::steady_clock::now();
+    go.store(true, std::memory_order_release);
+    for (auto& x : th) x.join();
+    const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    std::vector<float> all;
+    for (auto& v : lat) all.insert(all.end(), v.begin(), v.end());
+    std::sort(all.begin(), all.end());
+    if (calls_out) *calls_out = calls.load();
+    if (errors_out) *errors_out = errors.load();
+    if (elapsed_s_out) *elapsed_s_out = el;
+    if (lat_p50_us) *lat_p50_us = all.empty() ? 0.0 : all[all.size() / 2];
+    if (lat_p99_us) *lat_p99_us = all.empty() ? 0.0 : all[std::min(all.size() - 1, all.size() * 99 / 100)];
+    return first_rc.load();
+}
+
 }  // extern "C"

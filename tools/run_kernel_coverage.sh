@@ -14,7 +14,7 @@ for chunk in "tests/test_gpu_flat.py tests/test_gpu_small.py tests/test_gpu_scan
              "tests/test_gpu_graph.py tests/test_gpu_build.py tests/test_gpu_host.py" \
              "tests/test_gpu_concurrent.py tests/test_gpu_sharded.py tests/test_gpu_sharded_abi.py tests/test_gpu_sharded_index.py" \
              "tests/test_gpu_fullsize.py tests/test_derived_kats.py tests/test_gpu_coverage.py" \
-             "tests/test_gpu_order_sensitive.py"; do
+             "tests/test_gpu_order_sensitive.py tests/test_gpu_rowsets.py"; do
     n=$((n + 1))
     files=""; for f in $chunk; do [ -f $f ] && files="$files $f"; done
     (cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $cov/c$n -o t -- python3 -m pytest -q -m gpu -p no:cacheprovider --rootdir $root $(for f in $files; do echo $root/$f; done) > $cov/c$n.log 2>&1)
