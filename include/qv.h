@@ -100,6 +100,11 @@ typedef enum qv_status {
 #define QV_FLAG_BF16_ROWS   2ull /* also keep a bfloat16 copy of the rows (+50 % memory): the batched path's filter reads it
                                     instead of the float32 rows (half the bytes); results are unchanged — the filter only
                                     selects candidates for the exact re-score */
+#define QV_FLAG_NO_SCAN_PLANE 4ull /* cosine and dot indexes keep the bfloat16 copy by default (+dim * 2 bytes per row: 3080 -> 4616
+                                    bytes per row at 768 dimensions) because the single-query scan of a large corpus rejects rows
+                                    on it and reads the float32 rows of the few survivors only (qv_index_set_bound_scan).  This
+                                    flag leaves the copy out: memory and every search are as without that scan.  The copy is an
+                                    accelerator, never a requirement: an index whose copy cannot be allocated carries on without it */
 
 /* ---- lifecycle ------------------------------------------------------------------ */
 
@@ -258,6 +263,27 @@ int qv_index_search_batched(qv_index* idx, const float* queries, uint32_t nq, ui
 #define QV_FILTER_OFF       4   /* no filter: every batch of this index takes the exact scans (what tests of those scans choose) */
 int qv_index_set_filter(qv_index* idx, int filter);
 
+/* The single-query scan that rejects rows on the bfloat16 copy (cosine and dot, 1 <= k <= 64, a dimension that is a multiple of
+ * 16): stage 1 streams the copy, derives a certified interval of every row's distance and ends with the k-th smallest upper
+ * bound; the rows whose lower bound is within it (k plus a handful) get their distances from the float32 rows in the scan's own
+ * arithmetic.  Results are
+ * bit-identical to the exact scan's; when the bound cannot decide (too many survivors, a query whose norm is not a number, huge or
+ * vanishing) the exact scan answers instead, decided on the device.  QV_BOUND_SCAN_AUTO: from the measured row count on;
+ * QV_BOUND_SCAN_ALWAYS: whenever the copy exists and the shape applies; QV_BOUND_SCAN_NEVER.  The environment variable
+ * QV_BOUND_SCAN (1 always, 2 never; read once per process) sets the default of indexes that never call this. */
+#define QV_BOUND_SCAN_AUTO   0
+#define QV_BOUND_SCAN_ALWAYS 1
+#define QV_BOUND_SCAN_NEVER  2
+int qv_index_set_bound_scan(qv_index* idx, int mode);
+/* out[0] = survivors stage 1 passed on in the last such search, out[1] = searches handed back to the exact scan so far,
+ * out[2] = searches that took the path so far, out[3] = 1 when the index holds the bfloat16 copy.  Waits for the device. */
+int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]);
+/* The interval stage 1 derives for one row, on the host (the kernel's own function compiled for the CPU; metric QV_COSINE or
+ * QV_DOT): s = the float32 chain of the query times the row's bfloat16 copy, qn = |query|, rn = |row|, rres = |row - bf16(row)|
+ * rounded up.  Returns 1 when the row is one the bound says nothing about (always a survivor), 0 otherwise with
+ * [*d_lo, *d_hi] containing the float32 distance, < 0 on an error. */
+int qv_scan_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi);
+
 /* Device-pointer form of the batched path: enqueues on `stream`, no sync.  d_redo_flags_out[nq]
  * (uint32) is set to 1 for queries whose candidate buffer overflowed or — 16 or more results per query over 131 072 rows or
  * more, where the k-th distance's bound is a guess from a sample of 32 768 rows or more — whose guess did not hold (fewer than k candidates
@@ -405,7 +431,7 @@ int qv_graph_stats(const qv_graph* g, double* build_seconds, uint64_t* build_bat
  *                    the k best of the gathered lists, the whole batch at once.  Beyond (a filtered Collection.Search asks
  *                    for k = Index.Size(), collection.go:679-682): every shard ranks its rows (radix sort), the sorted runs
  *                    are exchanged and one stable radix sort on the first device merges them
- *   flags            QV_FLAG_ROWMAJOR and QV_FLAG_BF16_ROWS pass through to the shards; QV_SHARDED_PEER_COPY replaces the collective with
+ *   flags            QV_FLAG_ROWMAJOR, QV_FLAG_BF16_ROWS and QV_FLAG_NO_SCAN_PLANE pass through to the shards; QV_SHARDED_PEER_COPY replaces the collective with
  *                    point-to-point copies into the first device (and lets several shards share one device, which
  *                    RCCL does not allow: how the tests exercise 3 and 8 shards on a 1-GPU box)
  * Threading: as qv_index — searches, qv_sharded_distance_rows and qv_sharded_get_row(s) may run concurrently from many
@@ -467,6 +493,8 @@ int qv_sharded_sync(qv_sharded* s);                            /* wait for every
  * scan KERNEL is bracketed by events on its own stream (qv_index_profile): qv_sharded_profile_read_shard returns the summed
  * kernel time and launch count of one shard since the last read — the per-GPU roofline numerator. */
 int qv_sharded_set_filter(qv_sharded* s, int filter);          /* qv_index_set_filter on every shard */
+int qv_sharded_set_bound_scan(qv_sharded* s, int mode);       /* qv_index_set_bound_scan on every shard */
+int qv_sharded_bound_scan_stats(qv_sharded* s, uint64_t out[4]);   /* qv_index_bound_scan_stats: [0] of the first shard, [1] [2] summed, [3] 1 when every shard holds the copy */
 int qv_sharded_profile(qv_sharded* s, int enable);
 int qv_sharded_profile_read(qv_sharded* s, double* scan_ms_sum, double* exchange_ms_sum, double* merge_ms_sum, uint64_t* searches);
 int qv_sharded_profile_read_shard(qv_sharded* s, int shard, double* scan_kernel_ms_sum, uint64_t* launches);

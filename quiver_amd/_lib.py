@@ -13,6 +13,8 @@ QV_ERR_INVALID_ARG, QV_ERR_DIM_MISMATCH, QV_ERR_K_NOT_POSITIVE, QV_ERR_OUT_OF_RA
 QV_ERR_NO_DEVICE, QV_ERR_DEVICE, QV_ERR_OOM, QV_ERR_UNSUPPORTED = -5, -6, -7, -8
 QV_FLAG_ROWMAJOR = 1
 QV_FLAG_BF16_ROWS = 2
+QV_FLAG_NO_SCAN_PLANE = 4
+QV_BOUND_SCAN_AUTO, QV_BOUND_SCAN_ALWAYS, QV_BOUND_SCAN_NEVER = 0, 1, 2
 QV_SHARDED_PEER_COPY = 1 << 32
 
 # include/qv.h qv_metric
@@ -79,6 +81,11 @@ PROTOTYPES = {
     "qv_merge_topk_shards_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_index_set_filter": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_sharded_set_filter": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_set_bound_scan": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_sharded_set_bound_scan": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_bound_scan_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_sharded_bound_scan_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_scan_bound_interval": (C.c_int, [C.c_int, C.c_uint32, C.c_float, C.c_double, C.c_double, C.c_float, _f32p, _f32p]),
     "qv_index_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "qv_graph_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

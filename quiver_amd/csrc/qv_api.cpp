@@ -116,8 +116,16 @@ int ensure_rows(qv_index* idx, uint64_t rows, bool exact) {
     if (e == hipSuccess) e = regrow(&idx->d_rres, used_tiles * 64 * sizeof(float), new_tiles * 64 * sizeof(float));
     if (e == hipSuccess && (idx->flags & QV_FLAG_ROWMAJOR))
         e = regrow(&idx->d_rowmaj, (size_t)idx->n_rows * idx->dim * sizeof(float), new_tiles * 64 * (size_t)idx->dim * sizeof(float));
-    if (e == hipSuccess && (idx->flags & QV_FLAG_BF16_ROWS))
-        e = regrow(&idx->d_bf16, used_tiles * idx->bf16_tile_bytes(), new_tiles * idx->bf16_tile_bytes());
+    if (e == hipSuccess && idx->wants_plane()) {
+        // the bfloat16 copy: required under QV_FLAG_BF16_ROWS; otherwise (the default on cosine / dot indexes, for the single-query bound
+        // scan) an accelerator — when it does not fit, the index frees it and carries on without: searches take the exact scan
+        hipError_t eb = getenv("QV_TEST_PLANE_OOM") && !(idx->flags & QV_FLAG_BF16_ROWS) ? hipErrorOutOfMemory
+                                                                                          : regrow(&idx->d_bf16, used_tiles * idx->bf16_tile_bytes(), new_tiles * idx->bf16_tile_bytes());
+        if (eb == hipErrorOutOfMemory && !(idx->flags & QV_FLAG_BF16_ROWS)) {
+            (void)hipGetLastError();
+            (void)hipFree(idx->d_bf16); idx->d_bf16 = nullptr; idx->plane_lost = true;
+        } else e = eb;
+    }
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? QV_ERR_OOM : QV_ERR_DEVICE, "device allocation for %llu rows failed: %s", (unsigned long long)(new_tiles * 64), hipGetErrorString(e));
     idx->cap_tiles = new_tiles;
@@ -185,6 +193,11 @@ int qv_index_create(qv_index** out, uint32_t dim, qv_metric metric, int device, 
     if (!idx) return fail(QV_ERR_OOM, "out of host memory");
     idx->device = device; idx->cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
     idx->dim = dim; idx->dim4 = (dim + 3) / 4; idx->metric = (int)metric; idx->flags = flags;
+    if (hipMalloc(reinterpret_cast<void**>(&idx->d_bound_stats), 64) != hipSuccess || hipMemset(idx->d_bound_stats, 0, 64) != hipSuccess ||
+        hipStreamSynchronize(nullptr) != hipSuccess) {
+        (void)hipFree(idx->d_bound_stats); delete idx;
+        return fail(QV_ERR_OOM, "device allocation of the index's counters failed");
+    }
     *out = idx;
     return QV_OK;
 }
@@ -195,7 +208,7 @@ void qv_index_destroy(qv_index* idx) {
     (void)hipDeviceSynchronize();
     for (SearchCtx* c : idx->all_ctx) { c->release(); delete c; }
     for (auto& kv : idx->stream_ws) { kv.second->ws.release(); kv.second->tickets.release(); delete kv.second; }
-    (void)hipFree(idx->d_tiles); (void)hipFree(idx->d_rnorm); (void)hipFree(idx->d_alive); (void)hipFree(idx->d_rres); (void)hipFree(idx->d_rowmaj); (void)hipFree(idx->d_bf16);
+    (void)hipFree(idx->d_tiles); (void)hipFree(idx->d_rnorm); (void)hipFree(idx->d_alive); (void)hipFree(idx->d_rres); (void)hipFree(idx->d_rowmaj); (void)hipFree(idx->d_bf16); (void)hipFree(idx->d_bound_stats);
     idx->mut_stage.release();
     delete idx;
 }
@@ -383,13 +396,15 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
                 idx->prof_events.emplace_back(ev0, ev1);
             } else { ev0 = ev1 = nullptr; }
         }
-        if (d_tickets && qv::flat_small_applies(v, nq, kk) && !qv::flat_split_applies(v, nq, kk)) {   // small collection: scan + merge in one launch
+        // (a masked search keeps the exact scan: its candidates are not the index's live rows)
+        uint32_t* bound_stats = d_tickets && !d_candidates && qv::bound_scan_applies(v, nq, kk) ? idx->d_bound_stats : nullptr;
+        if (!bound_stats && d_tickets && qv::flat_small_applies(v, nq, kk) && !qv::flat_split_applies(v, nq, kk)) {   // small collection: scan + merge in one launch
             hipError_t e = qv::launch_flat_small(v, d_queries, nq, kk, ws, d_tickets, d_rows_out, d_dist_out, nq == 1 ? done_flag : nullptr, done_seq, s, ev0, ev1);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "small scan launch failed: %s", hipGetErrorString(e));
             if (flag_used) *flag_used = nq == 1 && done_flag != nullptr;
             return QV_OK;
         }
-        hipError_t e = qv::launch_flat_topk(v, plan, d_queries, nq, kk, ws, d_rows_out, d_dist_out, s, ev0, ev1, d_tickets, nq == 1 ? done_flag : nullptr, done_seq, flag_used);
+        hipError_t e = qv::launch_flat_topk(v, plan, d_queries, nq, kk, ws, d_rows_out, d_dist_out, s, ev0, ev1, d_tickets, nq == 1 ? done_flag : nullptr, done_seq, flag_used, bound_stats);
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "flat scan launch failed: %s", hipGetErrorString(e));
         return QV_OK;
     }
@@ -425,7 +440,8 @@ static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uin
     const qv::ScanPlan plan = qv::plan_scan(n_tiles, idx->cus);
     if (kk <= (uint32_t)qv::kMaxFusedK && kk == k_stride)   // partial lists + the multi-query kernels' query blocks (the small scan's lists fit in them)
         return std::max(qv::flat_small_workspace_bytes(std::min(nq, 4u), kk),
-                        qv::scan_workspace_bytes(plan, nq, kk) + std::max((size_t)(nq + 16) * idx->dim4 * 4 * sizeof(double), qv::mq64_workspace_bytes(nq, idx->dim4)));
+                        qv::scan_workspace_bytes(plan, nq, kk) + std::max(std::max((size_t)(nq + 16) * idx->dim4 * 4 * sizeof(double), qv::mq64_workspace_bytes(nq, idx->dim4)),
+                                                                          nq == 1 ? qv::bound_scan_workspace_bytes(plan, kk, n_tiles) : (size_t)0));   // (the bound scan's lists sit behind the exact scan's)
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
     return qv::full_sort_workspace_bytes(n_tiles);
@@ -1139,6 +1155,31 @@ int qv_index_set_filter(qv_index* idx, int filter) {
     if (filter < 0 || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be 0 (automatic), 1 (fp32 MFMA), 2 (bfloat16 x 3), 3 (bfloat16 x 1) or 4 (off); got %d", filter);
     idx->filter = filter;
     return QV_OK;
+}
+
+int qv_index_set_bound_scan(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    idx->bound_scan = mode;
+    return QV_OK;
+}
+
+int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t h[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(h, idx->d_bound_stats, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = idx->d_bf16 != nullptr ? 1 : 0;
+    return QV_OK;
+}
+
+int qv_scan_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {
+    if (metric != QV_COSINE && metric != QV_DOT) return fail(QV_ERR_UNSUPPORTED, "the bound scan's metrics are cosine and dot; got %d", metric);
+    if (!d_lo || !d_hi || dim == 0) return fail(QV_ERR_INVALID_ARG, "d_lo/d_hi is null or dim is 0");
+    int unsure = 0;
+    (void)qv::host_bound_interval(metric, dim, s, qn, rn, rres, d_lo, d_hi, &unsure);
+    return unsure;
 }
 
 int qv_index_profile(qv_index* idx, int enable) {

@@ -93,7 +93,10 @@ struct qv_index {
     uint64_t* d_alive = nullptr;
     float* d_rres = nullptr;                   // |r - bf16(r)| per row: refreshed by every call that writes rows
     float* d_rowmaj = nullptr;
-    uint16_t* d_bf16 = nullptr;                // QV_FLAG_BF16_ROWS: refreshed by every call that writes rows
+    uint16_t* d_bf16 = nullptr;                // the bfloat16 copy (QV_FLAG_BF16_ROWS, and by default on cosine / dot indexes): refreshed by every call that writes rows
+    bool plane_lost = false;                   // the default copy could not be allocated: the index carries on without it
+    int bound_scan = 0;                        // qv_index_set_bound_scan
+    uint32_t* d_bound_stats = nullptr;         // [0] survivors of the last bound scan, [1] hand-backs, [2] bound scans (written by the kernels)
     std::vector<uint64_t> alive_host;          // mirror of d_alive, for size bookkeeping and validation
     Buf mut_stage;                             // grow-only staging buffer of the mutating calls (add / remove / update run under the
                                                // caller's exclusion, so one buffer serves them all: no hipMalloc per single-row Insert)
@@ -117,9 +120,14 @@ struct qv_index {
 
     qv::IndexView view() const {
         qv::IndexView v;
-        v.tiles = d_tiles; v.rnorm = d_rnorm; v.alive = d_alive; v.rres = d_rres; v.rowmaj = d_rowmaj; v.bf16 = d_bf16;
+        v.tiles = d_tiles; v.rnorm = d_rnorm; v.alive = d_alive; v.rres = d_rres; v.rowmaj = d_rowmaj;
+        v.bf16 = (flags & QV_FLAG_BF16_ROWS) ? d_bf16 : nullptr; v.plane = d_bf16; v.bound_scan = bound_scan;
         v.dim = dim; v.dim4 = dim4; v.n_rows = n_rows; v.n_tiles = (n_rows + 63) / 64; v.metric = metric; v.filter = filter;
         return v;
+    }
+    // cosine and dot indexes keep the bfloat16 copy unless told not to (QV_FLAG_NO_SCAN_PLANE) or it could not be allocated
+    bool wants_plane() const {
+        return (flags & QV_FLAG_BF16_ROWS) || (!(flags & QV_FLAG_NO_SCAN_PLANE) && !plane_lost && (metric == QV_COSINE || metric == QV_DOT));
     }
     size_t tile_bytes() const { return (size_t)dim4 * 64 * 16; }
     size_t bf16_tile_bytes() const { return (size_t)(((dim4 + 1) / 2 + 1) / 2) * 2 * 64 * 16; }   // whole 16-dim steps (k_bf16_plane's layout)

@@ -41,6 +41,10 @@ struct IndexView {
     uint32_t  n_tiles;    // ceil(n_rows/64)
     int       metric;
     int       filter;     // batched path's filter kernel: 0 = the library's rule, 1 fp32 MFMA chain, 2 bfloat16 x 3, 3 bfloat16 x 1 (qv_index_set_filter)
+    uint16_t* plane;      // may be null: the same bfloat16 copy whenever the index keeps one — cosine and dot indexes do by default, for the
+                          // single-query bound scan (qv_bound.hip); `bf16` above is set only under QV_FLAG_BF16_ROWS, so the batched path's
+                          // choice of kernels is what the flag alone decides.  The calls that write rows refresh `plane`.
+    int       bound_scan; // qv_index_set_bound_scan: 0 from the measured row count on, 1 whenever it applies, 2 never
 };
 
 struct GraphView {
@@ -133,7 +137,19 @@ hipError_t launch_fetch_rows(const IndexView& v, const uint32_t* d_rows, uint32_
 hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k,
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
                             hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, uint32_t* d_tickets = nullptr,
-                            uint32_t* done_flag = nullptr, uint32_t done_seq = 0, bool* flag_used = nullptr);   // done_flag: see launch_flat_small (k_flat_scan_split only)
+                            uint32_t* done_flag = nullptr, uint32_t done_seq = 0, bool* flag_used = nullptr,   // done_flag: see launch_flat_small (k_flat_scan_split only)
+                            uint32_t* d_bound_stats = nullptr);   // the index's bound-scan counters: with them (and tickets) a single query may take launch_bound_scan
+// The single-query scan on the bfloat16 copy (qv_bound.hip): stage 1 streams v.plane and lists the rows whose certified lower bound of
+// the distance is within the k-th smallest upper bound, stage 2 computes those rows' distances in the scan's own arithmetic and writes
+// the k results, or sets *gate (a device word) when the exact scan must answer instead; the caller then issues the exact scan with that
+// gate (it leaves at once when the word is zero).  d_ctrl: the stream's zeroed control words (kept zero); d_stats: the index's counters.
+bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k);
+size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles);
+hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
+                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s);
+// the interval of one row on the HOST (qv_scan_bound_interval): qv_bound.h's function compiled for the CPU
+float host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi, int* unsure);
+constexpr uint32_t kBoundCtrlWord = 16;   // the bound scan's control words start here in the stream's 64 ticket words
 bool flat_split_applies(const IndexView& v, uint32_t nq, uint32_t k);   // launch_flat_topk will take the tile-over-eight-waves form (given tickets)
 // The exact scan (k <= kMaxFusedK) for exactly the queries whose d_flags word is non-zero — the ones a filter handed back —, listed and
 // scanned on the device: nothing is read back.  Results replace rows / distances [q][k_stride] of those queries.  d_ws: redo_workspace_bytes.

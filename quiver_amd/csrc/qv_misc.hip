@@ -251,7 +251,7 @@ k_bf16_plane(IndexView v, uint32_t t0, uint32_t n_tiles) {
         uint4 o;
         o.x = __builtin_bit_cast(uint32_t, p0); o.y = __builtin_bit_cast(uint32_t, p1); o.z = __builtin_bit_cast(uint32_t, p2); o.w = __builtin_bit_cast(uint32_t, p3);
         const uint32_t steps8 = (dim8 + 1) / 2;
-        reinterpret_cast<uint4*>(v.bf16)[((((size_t)t * steps8 + (c8 >> 1)) * 2 + (r >> 5)) * 2 + (c8 & 1)) * 32 + (r & 31)] = o;
+        reinterpret_cast<uint4*>(v.plane)[((((size_t)t * steps8 + (c8 >> 1)) * 2 + (r >> 5)) * 2 + (c8 & 1)) * 32 + (r & 31)] = o;
     }
 }
 // |r - bf16(r)| of the rows of tiles [t0, t0 + n_tiles): what the one-term bfloat16 filter drops of a row (qv_batched.hip: its
@@ -290,7 +290,7 @@ static hipError_t refresh_bf16(const IndexView& v, uint32_t t0, uint32_t t1, hip
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (!v.bf16) return hipSuccess;
+    if (!v.plane) return hipSuccess;
     const uint64_t total = (uint64_t)(t1 - t0 + 1) * ((v.dim4 + 1) / 2) * 64;
     hipLaunchKernelGGL(k_bf16_plane, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, s, v, t0, t1 - t0 + 1);
     return hipGetLastError();

@@ -1,6 +1,7 @@
 // qv_scan.hip — flat scan + fused top-k (single- and multi-query), list merges
 // (shared helpers, the arithmetic contract and the build flags: qv_kernels.h)
 #include "qv_kernels.h"
+#include "qv_bound.h"
 
 namespace qv {
 
@@ -18,8 +19,10 @@ template <int M, int U, bool FUSE = false>
 __global__ void __launch_bounds__(kScanBlock)
 k_flat_scan(IndexView v, const float* __restrict__ queries, uint32_t k, uint64_t* __restrict__ partial,
             uint32_t* __restrict__ tickets = nullptr, uint32_t* __restrict__ rows_out = nullptr, float* __restrict__ dist_out = nullptr,
-            uint32_t* done_flag = nullptr, uint32_t done_seq = 0) {
+            uint32_t* done_flag = nullptr, uint32_t done_seq = 0, const uint32_t* __restrict__ gate = nullptr) {
     using Q = typename MT<M>::Q;
+    // gate: the launch behind a bound scan (k_bound_rescore wrote the word): zero = that scan has answered, leave at once
+    if constexpr (FUSE) { if (gate != nullptr && *gate == 0u) return; }
     extern __shared__ __align__(16) unsigned char smem[];
     Q* q_lds = reinterpret_cast<Q*>(smem);
     uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (((size_t)v.dim4 * 4 * sizeof(Q)) + 15) / 16 * 16);  // [kScanWaves][64]
@@ -1024,6 +1027,228 @@ k_merge_shards(const uint32_t* __restrict__ packed, const uint32_t* __restrict__
     }
 }
 
+
+// ---------------------------------------------------------------- one query over a large corpus: reject rows on the bfloat16 copy --
+// k_flat_scan runs at the memory's rate (0.90 of the HBM peak at 10M x 768), so a single query gets faster only by reading fewer
+// bytes.  Of N rows k are returned; the others only have to be REJECTED, and that takes a certified lower bound of the distance,
+// not the float64 chain.  Three launches and the gated exact scan behind them:
+//   k_bound_scan     k_flat_scan's shape — lane == row, a wave owns whole tiles — over the index's bfloat16 copy (IndexView::plane: half
+//                    the bytes; per 16-dimension step a lane reads its two 16-byte halves, the wave two contiguous 512-byte runs per
+//                    request), the query in float32 from LDS, one float32 fma chain S~ per row, and from it the interval [d_lo, d_hi]
+//                    of the reference's float32 distance (qv_bound.h).  d_lo goes out as one ordered word per row (4 bytes against the
+//                    row's 2 dim); the UPPER bounds go through k_flat_scan's own selection — wave lists, the workgroups' lists published,
+//                    the last workgroup merges — so the launch ends with H, the exact k-th smallest upper bound over all live rows.
+//                    Any k rows' upper bounds cap the k-th distance: every row of the answer has d_lo <= H.
+//   k_bound_collect  the rows with d_lo <= H (not strict: ties go on) — k plus a handful on ordinary data — listed with one returning
+//                    atomic per wave and batch that has any.
+//   k_bound_rescore  one workgroup: those rows walked as ONE float64 chain over the float32 tiles — row_accumulate + finalize, the
+//                    query's norm as its chain: the exact scan's bits —, the k best (distance, row) keys written where the exact scan
+//                    writes them.  When the list overflowed, H is not finite (fewer than k rows with a bound), or |q| is not a norm
+//                    the bound works with, it sets the gate word instead and the exact scan launched behind it answers
+//                    (k_flat_scan<., ., true>'s `gate`: otherwise that launch leaves at once).  Nothing is read on the host.
+// (Measured first and not kept: candidates taken DURING the scan against a device-wide threshold word seeded from the waves' first
+// tiles — the tiles walked before the seed's merge lands let 20 - 50 k rows through at k = 64; profiles/LAB_r07_bound_scan.md.)
+// The control words live in the stream's zeroed ticket words and are left zero.
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t kBoundCandCap = 4096;       // rows stage 3 walks exactly (an i.i.d. 10M x 768 corpus leaves k + a few)
+constexpr uint32_t kBoundMaxDim = 4096;
+struct BoundCtrl { uint32_t thr_inv, cand_cnt, ticket, flag; };   // thr_inv = ~(ordered image of H): zero = no finite H
+
+template <int U, bool QN>
+__device__ __forceinline__ void bound_block(const u4* __restrict__ p, const float* __restrict__ q_lds, uint32_t s0, float& acc, double& qa) {
+    u4 x[2 * U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        x[2 * u] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 128]);
+        x[2 * u + 1] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 128 + 32]);
+    }
+    __builtin_amdgcn_sched_barrier(0);                                 // all requests of the block ahead of the arithmetic (see row_accumulate)
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const f4* qq = reinterpret_cast<const f4*>(q_lds + (size_t)(s0 + u) * 16);
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const u4 w = x[2 * u + h];
+            const f4 qa4 = qq[2 * h], qb4 = qq[2 * h + 1];
+            const float qe[8] = {qa4.x, qa4.y, qa4.z, qa4.w, qb4.x, qb4.y, qb4.z, qb4.w};
+            const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {                              // bfloat16 -> float32 is a shift / a mask: exact
+                acc = __builtin_fmaf(qe[2 * j], __uint_as_float(ww[j] << 16), acc);
+                acc = __builtin_fmaf(qe[2 * j + 1], __uint_as_float(ww[j] & 0xFFFF0000u), acc);
+                if constexpr (QN) { const double a = (double)qe[2 * j], b = (double)qe[2 * j + 1]; qa = __builtin_fma(a, a, qa); qa = __builtin_fma(b, b, qa); }
+            }
+        }
+    }
+}
+// S~ of this lane's row of one tile (p = the tile in the copy + the lane's place in a step); QN: |q|^2 as the reference's chain rides along
+template <bool QN>
+__device__ __forceinline__ float bound_tile(const u4* __restrict__ p, const float* __restrict__ q_lds, uint32_t steps, double* qn2) {
+    float acc = 0.f; double qa = 0.0;
+    uint32_t s = 0;
+    for (; s + 8 <= steps; s += 8) bound_block<8, QN>(p, q_lds, s, acc, qa);
+    if (s + 4 <= steps) { bound_block<4, QN>(p, q_lds, s, acc, qa); s += 4; }
+    if (s + 2 <= steps) { bound_block<2, QN>(p, q_lds, s, acc, qa); s += 2; }
+    if (s < steps) bound_block<1, QN>(p, q_lds, s, acc, qa);
+    if constexpr (QN) *qn2 = qa;
+    return acc;
+}
+
+template <int M>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
+             uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* q_lds = reinterpret_cast<float*>(smem);                     // [dim], dim a multiple of 16
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (size_t)v.dim * sizeof(float));   // [kScanWaves][64]
+    __shared__ uint32_t s_last;
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (uint32_t i = threadIdx.x; i < v.dim; i += blockDim.x) q_lds[i] = query[i];
+    __syncthreads();
+    const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves, kth = k - 1;
+    const double gamma = bound_scan_gamma(v.dim);
+    const u4* plane = reinterpret_cast<const u4*>(v.plane) + ((lane >> 5) * 64 + (lane & 31));
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    double qn = 0.0;
+
+    auto finish_tile = [&](uint32_t t, float s, bool first) {
+        const uint32_t row = t * 64 + lane;
+        const double rn = v.rnorm[row];
+        const float rr = v.rres[row];
+        const uint64_t am = v.alive[t];                                // wave-uniform
+        float lo, hi;
+        (void)bound_scan_interval<M>(s, qn, rn, rr, v.dim, gamma, lo, hi);
+        const bool live = (am >> lane) & 1ull;                         // (dead rows and the last tile's padding: never candidates, never in a bound)
+        __builtin_nontemporal_store(live ? ord_f32(lo) : 0xFFFFFFFFu, &lo_all[row]);
+        const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+        if (first) { list = wave_sort64(key, lane); thr = readlane64(list, kth); }
+        else list_insert(list, thr, key, kth, lane);
+    };
+
+    uint32_t t = blockIdx.x * kScanWaves + wave;
+    if (t < v.n_tiles) {                                               // first tile: sorted outright, |q| rides along
+        double qn2 = 0.0;
+        const float s = bound_tile<true>(plane + (size_t)t * steps * 128, q_lds, steps, &qn2);
+        qn = __builtin_sqrt(qn2);
+        finish_tile(t, s, true);
+        t += tw;
+    }
+    for (; t < v.n_tiles; t += tw) finish_tile(t, bound_tile<false>(plane + (size_t)t * steps * 128, q_lds, steps, nullptr), false);
+
+    // the upper bounds' lists: waves -> wave 0 -> published; the last workgroup to finish merges (k_flat_scan<., ., true>'s protocol)
+    wl[wave * 64 + lane] = list;
+    __syncthreads();
+    if (wave == 0) {
+        for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list, thr, lane < k ? wl[w * 64 + lane] : kDeadKey, kth, lane);
+        uint64_t* mine = partial + (size_t)blockIdx.x * k;
+        if (lane < k) (void)atomicExch(reinterpret_cast<unsigned long long*>(&mine[lane]), (unsigned long long)list);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // every lane's exchange has returned: the list is at the memory side
+        uint32_t last = 0;
+        if (lane == 0) last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+        last = __builtin_amdgcn_readfirstlane(last);
+        if (last && lane == 0) ctrl->ticket = 0;                       // for the next launch on these words (stream order)
+        if (lane == 0) s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    merge_lists_last_workgroup(partial, gridDim.x, k, seed_rows, seed_dist);
+    if (wave == 0 && lane == kth) {                                    // (this lane wrote them) H: a finite k-th upper bound, or none
+        const uint32_t o = ord_f32(seed_dist[kth]);
+        ctrl->thr_inv = (seed_rows[kth] != 0xFFFFFFFFu && o < 0xFF800000u) ? ~o : 0u;
+        ctrl->cand_cnt = 0;
+    }
+}
+
+// the rows with d_lo <= H, four per thread and step
+__global__ void __launch_bounds__(256)
+k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand) {
+    const uint32_t inv = ctrl->thr_inv;
+    if (inv == 0u) return;                                             // no H: k_bound_rescore hands the query back
+    const uint32_t H = ~inv, lane = lane_id();
+    for (uint32_t base = blockIdx.x * 1024u; base < n; base += gridDim.x * 1024u) {
+        const uint32_t i = base + threadIdx.x * 4u;
+        u4 x = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        if (i < n) x = __builtin_nontemporal_load(reinterpret_cast<const u4*>(lo_all + i));
+        const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const bool c = xs[j] <= H && xs[j] != 0xFFFFFFFFu;
+            const uint64_t m = __ballot(c);
+            if (m) {
+                uint32_t b0 = 0;
+                if (lane == (uint32_t)__builtin_ctzll(m)) b0 = atomicAdd(&ctrl->cand_cnt, (uint32_t)__builtin_popcountll(m));
+                b0 = __builtin_amdgcn_readlane(b0, (uint32_t)__builtin_ctzll(m));
+                const uint32_t slot = b0 + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+                if (c && slot < kBoundCandCap) cand[slot] = i + (uint32_t)j;
+            }
+        }
+    }
+}
+
+template <int M>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand,
+                uint32_t* __restrict__ stats, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out) {
+    using Q = typename MT<M>::Q;
+    extern __shared__ __align__(16) unsigned char smem[];
+    Q* q_lds = reinterpret_cast<Q*>(smem);
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (((size_t)v.dim4 * 4 * sizeof(Q)) + 15) / 16 * 16);   // [kScanWaves][64]
+    __shared__ double s_qn;
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t cnt = ctrl->cand_cnt, thr_inv = ctrl->thr_inv;
+    const uint32_t ns = cnt < kBoundCandCap ? cnt : kBoundCandCap, kth = k - 1;
+    stage_query<M>(q_lds, query, v.dim, v.dim4);
+    __syncthreads();
+    // the survivors' rows and norms are requested before the query's norm is walked
+    const f4* tiles = reinterpret_cast<const f4*>(v.tiles);
+    if (wave == kScanWaves - 1) {
+        // |q| as the reference's chain (distances.go:20): cosine's finalize takes it, and both metrics' hand-back rule
+        double ma = 0.0;
+        for (uint32_t i = 0; i < v.dim; i++) { const double a = (double)q_lds[i]; ma = __builtin_fma(a, a, ma); }
+        if (lane == 0) s_qn = __builtin_sqrt(ma);
+    }
+    __syncthreads();
+    const double qn = s_qn;
+    const bool hand_back = cnt > kBoundCandCap || thr_inv == 0u || !bound_scan_norm_ok(qn, v.dim);
+    if (threadIdx.x == 0) {
+        stats[0] = cnt;
+        if (hand_back) (void)atomicAdd(&stats[1], 1u);
+        (void)atomicAdd(&stats[2], 1u);
+        ctrl->flag = hand_back ? 1u : 0u;                              // the exact scan behind this launch reads it
+        ctrl->cand_cnt = 0; ctrl->thr_inv = 0;                         // zero, as the words are kept
+    }
+    if (hand_back) return;
+    QConst qc; qc.qn = 0.0; qc.qn32 = 0.0f;
+    if constexpr (M == QV_COSINE) qc.qn = qn;
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    for (uint32_t base = wave * 64; base < ns; base += kScanWaves * 64) {
+        const uint32_t i = base + lane;
+        uint64_t key = kDeadKey;
+        if (i < ns) {
+            const uint32_t row = cand[i];
+            const typename MT<M>::A acc = row_accumulate<M, kUnroll, false, true>(tiles + (size_t)(row >> 6) * v.dim4 * 64 + (row & 63), 64, q_lds, v.dim4);
+            double rn = 0.0;
+            if constexpr (MT<M>::needs_rnorm) rn = v.rnorm[row];
+            key = make_key(finalize<M>(acc, qc, rn), row);
+        }
+        if (base == wave * 64) { list = wave_sort64(key, lane); thr = readlane64(list, kth); }
+        else list_insert(list, thr, key, kth, lane);
+    }
+    __syncthreads();
+    wl[wave * 64 + lane] = list;
+    __syncthreads();
+    if (wave == 0) {
+        for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list, thr, lane < k ? wl[w * 64 + lane] : kDeadKey, kth, lane);
+        if (lane < k) {
+            const bool dead = list == kDeadKey;
+            rows_out[lane] = dead ? 0xFFFFFFFFu : (uint32_t)list;
+            dist_out[lane] = dead ? __uint_as_float(0x7F800000u) : unord_f32((uint32_t)(list >> 32));
+        }
+    }
+}
+
 ScanPlan plan_scan(uint32_t n_tiles, int cus) {
     ScanPlan p;
     p.block = kScanBlock;
@@ -1150,9 +1375,58 @@ bool flat_split_mq_applies(const IndexView& v, uint32_t nq, uint32_t k) {
     return split == 1 && split_metric && nq >= 2 && nq <= (uint32_t)nq_max && k >= 1 && k <= (uint32_t)kMaxFusedK && v.dim4 >= (uint32_t)min_dim4 && lds <= (size_t)160 * 1024 &&
            v.n_tiles >= 2 && v.n_tiles <= (uint32_t)split_max && reads <= 600ull * 1000 * 1000;
 }
+// The bound scan (k_bound_scan / k_bound_rescore above): one query, a fused-list k, cosine or dot, the bfloat16 copy at hand, a width the copy
+// covers in whole 16-dimension steps.  Automatic from kBoundScanMinRows rows (measured: profiles/LAB_r07_bound_scan.md); the index's setter
+// (IndexView::bound_scan) or QV_BOUND_SCAN = 1 takes it whenever it applies, 2 never.
+constexpr uint32_t kBoundScanMinRows = 300000;   // one query, us, exact / bound scan at k = 1, 10, 64: 100 k x 768 65 / 63, 66 / 70, 86 / 122; 300 k x 768 154 / 107, 158 / 114, 190 / 169; 1M x 128 89 / 64, 93 / 68, 134 / 114
+bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) {
+    static const int env_mode = env_int("QV_BOUND_SCAN", 0);
+    const int mode = v.bound_scan ? v.bound_scan : env_mode;
+    if (mode == 2 || nq != 1 || k < 1 || k > (uint32_t)kMaxFusedK || (v.metric != QV_COSINE && v.metric != QV_DOT) || v.plane == nullptr) return false;
+    if ((v.dim & 15u) != 0 || v.dim > kBoundMaxDim || v.n_tiles < 8) return false;
+    return mode == 1 || v.n_rows >= kBoundScanMinRows;
+}
+size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles) {
+    return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)n_tiles * 64 * sizeof(uint32_t);
+}
+hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
+                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s) {
+    if (!bound_scan_applies(v, 1, k) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    const uint32_t grid = p.grid;
+    char* w = static_cast<char*>(d_ws);
+    uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256;
+    uint32_t* seed_rows = reinterpret_cast<uint32_t*>(w); w += 256;
+    float* seed_dist = reinterpret_cast<float*>(w); w += 256;
+    uint32_t* cand = reinterpret_cast<uint32_t*>(w); w += (size_t)kBoundCandCap * sizeof(uint32_t);
+    uint32_t* lo_all = reinterpret_cast<uint32_t*>(w);
+    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
+    BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
+    const size_t lds1 = (size_t)v.dim * sizeof(float) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    hipError_t e = hipSuccess;
+#define QV_BOUND(MMM)                                                                                                        \
+    {                                                                                                                         \
+        e = set_lds(k_bound_scan<MMM>, lds1); if (e != hipSuccess) return e;                                                  \
+        e = set_lds(k_bound_rescore<MMM>, lds2); if (e != hipSuccess) return e;                                               \
+        hipLaunchKernelGGL((k_bound_scan<MMM>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, k, ctrl, lo_all, partial, seed_rows, seed_dist); \
+        hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, ctrl, cand);                      \
+        hipLaunchKernelGGL((k_bound_rescore<MMM>), dim3(1), dim3(kScanBlock), lds2, s, v, d_query, k, ctrl, cand, d_stats, d_rows_out, d_dist_out); \
+    }
+    if (v.metric == QV_COSINE) QV_BOUND(QV_COSINE) else QV_BOUND(QV_DOT)
+#undef QV_BOUND
+    *gate_out = &ctrl->flag;
+    return hipGetLastError();
+}
+float host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi, int* unsure) {
+    const double gamma = bound_scan_gamma(dim);
+    const bool sure = metric == QV_COSINE ? bound_scan_interval<QV_COSINE>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi) : bound_scan_interval<QV_DOT>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi);
+    *unsure = sure ? 0 : 1;
+    return 0.f;
+}
+
 hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k,
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
-                            hipEvent_t ev0, hipEvent_t ev1, uint32_t* d_tickets, uint32_t* done_flag, uint32_t done_seq, bool* flag_used) {
+                            hipEvent_t ev0, hipEvent_t ev1, uint32_t* d_tickets, uint32_t* done_flag, uint32_t done_seq, bool* flag_used, uint32_t* d_bound_stats) {
     if (k == 0 || k > (uint32_t)kMaxFusedK || nq == 0) return hipErrorInvalidValue;
     const size_t lds = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     uint64_t* partial = static_cast<uint64_t*>(d_ws);
@@ -1260,6 +1534,24 @@ hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* 
         // one query, the caller's tickets at hand: scan + merge in ONE launch (the last workgroup merges).  QV_SCAN_FUSE=0 (read once)
         // keeps the two launches, for measurements.
         static const int fuse = dev_env_int("QV_SCAN_FUSE", 1);
+        if (d_tickets && d_bound_stats && p.grid > 1 && bound_scan_applies(v, nq, k)) {
+            // the bound scan on the bfloat16 copy, its exact re-score, and the exact scan behind them that runs only when they hand the query back
+            static const int trace = env_int("QV_TRACE", 0);
+            if (trace) fprintf(stderr, "qv: scan kernel = k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
+            const uint32_t* gate = nullptr;
+            if (ev0) (void)hipEventRecord(ev0, s);
+            e = launch_bound_scan(v, p, d_queries, k, static_cast<char*>(d_ws) + scan_workspace_bytes(p, 1, k), d_tickets + kBoundCtrlWord, d_bound_stats, d_rows_out, d_dist_out, &gate, s);
+            if (e != hipSuccess) return e;
+            QV_DISPATCH_METRIC(v.metric, {
+                if constexpr (MM == QV_COSINE || MM == QV_DOT) {
+                    e = set_lds((k_flat_scan<MM, kUnroll, true>), lds);
+                    if (e != hipSuccess) return e;
+                    hipLaunchKernelGGL((k_flat_scan<MM, kUnroll, true>), dim3(p.grid, 1), dim3(p.block), lds, s, v, d_queries, k, partial, d_tickets, d_rows_out, d_dist_out, (uint32_t*)nullptr, 0u, gate);
+                }
+            });
+            if (ev1) (void)hipEventRecord(ev1, s);
+            return hipGetLastError();
+        }
         if (d_tickets && fuse && flat_split_applies(v, nq, k)) {
             static const int split_grid = dev_env_int("QV_SCAN_SPLIT_GRID", 0);
             const uint32_t grid = std::min<uint32_t>(v.n_tiles, std::min<uint32_t>(split_grid ? (uint32_t)split_grid : (uint32_t)p.cus, p.n_lists * 4u));
@@ -1281,7 +1573,7 @@ hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* 
                 e = set_lds((k_flat_scan<MM, kUnroll, true>), lds);
                 if (e != hipSuccess) return e;
                 if (ev0) (void)hipEventRecord(ev0, s);
-                hipLaunchKernelGGL((k_flat_scan<MM, kUnroll, true>), dim3(p.grid, nq), dim3(p.block), lds, s, v, d_queries, k, partial, d_tickets, d_rows_out, d_dist_out, done_flag, done_seq);
+                hipLaunchKernelGGL((k_flat_scan<MM, kUnroll, true>), dim3(p.grid, nq), dim3(p.block), lds, s, v, d_queries, k, partial, d_tickets, d_rows_out, d_dist_out, done_flag, done_seq, (const uint32_t*)nullptr);
                 if (ev1) (void)hipEventRecord(ev1, s);
             });
             if (flag_used) *flag_used = done_flag != nullptr;

@@ -550,7 +550,7 @@ int qv_sharded_create(qv_sharded** out, uint32_t dim, qv_metric metric, const in
     for (int g = 0; g < n_devices && rc == QV_OK; g++) {
         Shard& x = s->sh[(size_t)g];
         x.device = devices[g]; x.base = (uint32_t)g * s->span;
-        rc = qv_index_create(&x.idx, dim, metric, x.device, flags & (QV_FLAG_ROWMAJOR | QV_FLAG_BF16_ROWS));
+        rc = qv_index_create(&x.idx, dim, metric, x.device, flags & (QV_FLAG_ROWMAJOR | QV_FLAG_BF16_ROWS | QV_FLAG_NO_SCAN_PLANE));
     }
     if (rc == QV_OK && !s->rccl) {                                         // peer copies between distinct devices need peer access
         for (int g = 1; g < n_devices; g++) {
@@ -885,6 +885,30 @@ int qv_sharded_set_filter(qv_sharded* s, int filter) {
     std::unique_lock<std::shared_mutex> l(s->mu);
     reap_retired(s);
     for (auto& x : s->sh) { const int rc = qv_index_set_filter(x.idx, filter); if (rc != QV_OK) return rc; }
+    return QV_OK;
+}
+
+int qv_sharded_set_bound_scan(qv_sharded* s, int mode) {
+    if (!s) return fail(QV_ERR_INVALID_ARG, "handle is null");
+    std::unique_lock<std::shared_mutex> l(s->mu);
+    reap_retired(s);
+    for (auto& x : s->sh) { const int rc = qv_index_set_bound_scan(x.idx, mode); if (rc != QV_OK) return rc; }
+    return QV_OK;
+}
+
+int qv_sharded_bound_scan_stats(qv_sharded* s, uint64_t out[4]) {
+    if (!s || !out) return fail(QV_ERR_INVALID_ARG, "handle/out is null");
+    std::unique_lock<std::shared_mutex> l(s->mu);
+    out[0] = out[1] = out[2] = 0; out[3] = 1;
+    bool first = true;
+    for (auto& x : s->sh) {
+        uint64_t o[4];
+        const int rc = qv_index_bound_scan_stats(x.idx, o);
+        if (rc != QV_OK) return rc;
+        if (first) out[0] = o[0];
+        first = false;
+        out[1] += o[1]; out[2] += o[2]; out[3] &= o[3];
+    }
     return QV_OK;
 }
 

@@ -17,12 +17,13 @@ def _f32c(a) -> np.ndarray:
 class DeviceIndex:
     default_filter = "auto"        # the filter kernel new indexes choose (set_filter); tests and bench.py compare the kernels through it
 
-    def __init__(self, dim: int, metric="cosine", device: int = 0, rowmajor: bool = False, bf16_rows: bool = False, filter=None):
+    def __init__(self, dim: int, metric="cosine", device: int = 0, rowmajor: bool = False, bf16_rows: bool = False, filter=None, scan_plane: bool = True):
         self._h = C.c_void_p()
         self.dim = int(dim)
         self.metric = metric_id(metric)
         self.device = device
-        check(lib().qv_index_create(C.byref(self._h), self.dim, self.metric, device, (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0)))
+        check(lib().qv_index_create(C.byref(self._h), self.dim, self.metric, device, (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) |
+                                    (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE)))   # scan_plane=False: no default bfloat16 copy (cosine / dot), no bound scan
         f = filter if filter is not None else DeviceIndex.default_filter
         if f not in ("auto", 0):
             self.set_filter(f)
@@ -231,6 +232,19 @@ class DeviceIndex:
 
 
     FILTERS = {"auto": 0, "fp32": 1, "bf16x3": 2, "bf16x1": 3, "off": 4}
+
+    BOUND_SCAN = {"auto": 0, "always": 1, "never": 2}
+
+    def set_bound_scan(self, mode):
+        """the single-query scan that rejects rows on the bfloat16 copy: "auto" (from the measured row count on), "always" (whenever the
+        copy exists and the shape applies), "never" (qv_index_set_bound_scan)"""
+        check(lib().qv_index_set_bound_scan(self._h, self.BOUND_SCAN.get(mode, mode)))
+
+    def bound_scan_stats(self) -> dict:
+        """candidates of the last bound scan, searches it handed back to the exact scan, searches that took it, whether the copy exists"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_index_bound_scan_stats(self._h, out))
+        return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
     def set_filter(self, filter):
         """the batched path's filter kernel: "auto", "fp32" (fp32 MFMA chain), "bf16x3", "bf16x1", or "off" — exact scans only (qv_index_set_filter)"""
@@ -446,11 +460,11 @@ class ShardedIndex:
     one RCCL all-gather of the per-shard top-k per search, merge on the first device.  `devices` may repeat a device only
     with peer_copy=True (point-to-point exchange instead of the collective)."""
 
-    def __init__(self, dim: int, metric="cosine", devices=(0,), rowmajor: bool = False, peer_copy: bool = False, bf16_rows: bool = False):
+    def __init__(self, dim: int, metric="cosine", devices=(0,), rowmajor: bool = False, peer_copy: bool = False, bf16_rows: bool = False, scan_plane: bool = True):
         self._h = C.c_void_p()
         self.dim = int(dim)
         devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-        flags = (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_SHARDED_PEER_COPY if peer_copy else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0)
+        flags = (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_SHARDED_PEER_COPY if peer_copy else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) | (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE)
         check(lib().qv_sharded_create(C.byref(self._h), self.dim, metric_id(metric), devs, len(devices), flags))
 
     def close(self):
@@ -568,6 +582,14 @@ class ShardedIndex:
         out = np.empty(r.size, dtype=np.float32)
         check(lib().qv_sharded_distance_rows(self._h, q.ctypes.data, r.ctypes.data, r.size, out.ctypes.data))
         return out
+
+    def set_bound_scan(self, mode):
+        check(lib().qv_sharded_set_bound_scan(self._h, DeviceIndex.BOUND_SCAN.get(mode, mode)))
+
+    def bound_scan_stats(self) -> dict:
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_sharded_bound_scan_stats(self._h, out))
+        return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
     def set_filter(self, filter):
         check(lib().qv_sharded_set_filter(self._h, DeviceIndex.FILTERS.get(filter, filter)))
