@@ -101,7 +101,7 @@ typedef enum qv_status {
                                     instead of the float32 rows (half the bytes); results are unchanged — the filter only
                                     selects candidates for the exact re-score */
 #define QV_FLAG_NO_SCAN_PLANE 4ull /* cosine and dot indexes keep the bfloat16 copy by default (+dim * 2 bytes per row: 3080 -> 4616
-                                    bytes per row at 768 dimensions) because the single-query scan of a large corpus rejects rows
+                                    bytes per row at 768 dimensions) because the scan of a large corpus for 1 to 8 queries rejects rows
                                     on it and reads the float32 rows of the few survivors only (qv_index_set_bound_scan).  This
                                     flag leaves the copy out: memory and every search are as without that scan.  The copy is an
                                     accelerator, never a requirement: an index whose copy cannot be allocated carries on without it */
@@ -275,9 +275,20 @@ int qv_index_set_filter(qv_index* idx, int filter);
 #define QV_BOUND_SCAN_ALWAYS 1
 #define QV_BOUND_SCAN_NEVER  2
 int qv_index_set_bound_scan(qv_index* idx, int mode);
-/* out[0] = survivors stage 1 passed on in the last such search, out[1] = searches handed back to the exact scan so far,
- * out[2] = searches that took the path so far, out[3] = 1 when the index holds the bfloat16 copy.  Waits for the device. */
+/* The same scan as a SHARED pass: 2 to 8 queries of one call — or of concurrent callers whose queries were put together — read the
+ * copy once (4 or 8 queries per pass).  Interval, threshold and exact re-score are per query, so every answer is bit-identical to
+ * the exact scan's, and a query the bound cannot decide is handed back alone: the others of the pass keep their answers.  Same
+ * conditions and the same setter; no mask, no row set, k <= 64.  Automatic mode takes it only from the measured shapes on (a floor
+ * on rows and on the dimension: every query writes and reads 8 bytes per row whatever the width), and leaves short corpora to the
+ * form they had. */
+/* out[0] = survivors stage 1 passed on in the last such search (after a shared pass: the largest count among its queries),
+ * out[1] = QUERIES handed back to the exact scan so far, out[2] = QUERIES that took the path so far (a shared pass of nq adds nq),
+ * out[3] = 1 when the index holds the bfloat16 copy.  Waits for the device. */
 int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]);
+/* Whether a search of nq queries for k results over rows x dim of `metric` would take the path under `mode` (QV_BOUND_SCAN_*;
+ * has_plane: the index holds the copy) — the dispatch's own rule, on the host, without an index or a device.  1 / 0, < 0 on an
+ * error.  (A mask, a row set or a k above the live rows are the caller's to know: they never take it.) */
+int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane);
 /* The interval stage 1 derives for one row, on the host (the kernel's own function compiled for the CPU; metric QV_COSINE or
  * QV_DOT): s = the float32 chain of the query times the row's bfloat16 copy, qn = |query|, rn = |row|, rres = |row - bf16(row)|
  * rounded up.  Returns 1 when the row is one the bound says nothing about (always a survivor), 0 otherwise with

@@ -439,9 +439,10 @@ static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uin
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     const qv::ScanPlan plan = qv::plan_scan(n_tiles, idx->cus);
     if (kk <= (uint32_t)qv::kMaxFusedK && kk == k_stride)   // partial lists + the multi-query kernels' query blocks (the small scan's lists fit in them)
-        return std::max(qv::flat_small_workspace_bytes(std::min(nq, 4u), kk),
+        return std::max({qv::flat_small_workspace_bytes(std::min(nq, 4u), kk),
                         qv::scan_workspace_bytes(plan, nq, kk) + std::max(std::max((size_t)(nq + 16) * idx->dim4 * 4 * sizeof(double), qv::mq64_workspace_bytes(nq, idx->dim4)),
-                                                                          nq == 1 ? qv::bound_scan_workspace_bytes(plan, kk, n_tiles) : (size_t)0));   // (the bound scan's lists sit behind the exact scan's)
+                                                                          nq == 1 ? qv::bound_scan_workspace_bytes(plan, kk, n_tiles) : (size_t)0),   // (the bound scan's lists sit behind the exact scan's)
+                                 nq >= 2 && nq <= 8 && qv::bound_scan_applies(idx->view(), nq, kk) ? qv::bound_scan_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim) : (size_t)0});   // (a shared bound pass has the workspace to itself)
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
     return qv::full_sort_workspace_bytes(n_tiles);
@@ -1180,6 +1181,11 @@ int qv_scan_bound_interval(int metric, uint32_t dim, float s, double qn, double 
     int unsure = 0;
     (void)qv::host_bound_interval(metric, dim, s, qn, rn, rres, d_lo, d_hi, &unsure);
     return unsure;
+}
+
+int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane) {
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    return qv::host_bound_applies(metric, dim, rows, nq, k, mode, has_plane);
 }
 
 int qv_index_profile(qv_index* idx, int enable) {

@@ -1160,16 +1160,13 @@ k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl
     }
 }
 
-// the rows with d_lo <= H, four per thread and step
-__global__ void __launch_bounds__(256)
-k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand) {
-    const uint32_t inv = ctrl->thr_inv;
-    if (inv == 0u) return;                                             // no H: k_bound_rescore hands the query back
-    const uint32_t H = ~inv, lane = lane_id();
+// the rows with d_lo <= H, four per thread and step (lo: one query's ordered words; cnt: its counter; cand: its list)
+__device__ __forceinline__ void bound_collect(const uint32_t* __restrict__ lo, uint32_t n /* multiple of 64 */, uint32_t H, uint32_t* __restrict__ cnt, uint32_t* __restrict__ cand) {
+    const uint32_t lane = lane_id();
     for (uint32_t base = blockIdx.x * 1024u; base < n; base += gridDim.x * 1024u) {
         const uint32_t i = base + threadIdx.x * 4u;
         u4 x = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-        if (i < n) x = __builtin_nontemporal_load(reinterpret_cast<const u4*>(lo_all + i));
+        if (i < n) x = __builtin_nontemporal_load(reinterpret_cast<const u4*>(lo + i));
         const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -1177,7 +1174,7 @@ k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 6
             const uint64_t m = __ballot(c);
             if (m) {
                 uint32_t b0 = 0;
-                if (lane == (uint32_t)__builtin_ctzll(m)) b0 = atomicAdd(&ctrl->cand_cnt, (uint32_t)__builtin_popcountll(m));
+                if (lane == (uint32_t)__builtin_ctzll(m)) b0 = atomicAdd(cnt, (uint32_t)__builtin_popcountll(m));
                 b0 = __builtin_amdgcn_readlane(b0, (uint32_t)__builtin_ctzll(m));
                 const uint32_t slot = b0 + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
                 if (c && slot < kBoundCandCap) cand[slot] = i + (uint32_t)j;
@@ -1185,11 +1182,18 @@ k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 6
         }
     }
 }
+__global__ void __launch_bounds__(256)
+k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand) {
+    const uint32_t inv = ctrl->thr_inv;
+    if (inv == 0u) return;                                             // no H: k_bound_rescore hands the query back
+    bound_collect(lo_all, n, ~inv, &ctrl->cand_cnt, cand);
+}
 
-template <int M>
-__global__ void __launch_bounds__(kScanBlock)
-k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand,
-                uint32_t* __restrict__ stats, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out) {
+// One query's survivors walked exactly by one workgroup (cnt: how many the collect counted; has_H: it had a threshold).  decided(hand_back)
+// runs on thread 0 once the query's norm is known; a query handed back writes nothing.
+template <int M, typename F>
+__device__ __forceinline__ void bound_rescore_query(const IndexView& v, const float* __restrict__ query, uint32_t k, uint32_t cnt, bool has_H, const uint32_t* __restrict__ cand,
+                                                    uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, F decided) {
     using Q = typename MT<M>::Q;
     extern __shared__ __align__(16) unsigned char smem[];
     Q* q_lds = reinterpret_cast<Q*>(smem);
@@ -1197,7 +1201,6 @@ k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundC
     __shared__ double s_qn;
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t cnt = ctrl->cand_cnt, thr_inv = ctrl->thr_inv;
     const uint32_t ns = cnt < kBoundCandCap ? cnt : kBoundCandCap, kth = k - 1;
     stage_query<M>(q_lds, query, v.dim, v.dim4);
     __syncthreads();
@@ -1211,14 +1214,8 @@ k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundC
     }
     __syncthreads();
     const double qn = s_qn;
-    const bool hand_back = cnt > kBoundCandCap || thr_inv == 0u || !bound_scan_norm_ok(qn, v.dim);
-    if (threadIdx.x == 0) {
-        stats[0] = cnt;
-        if (hand_back) (void)atomicAdd(&stats[1], 1u);
-        (void)atomicAdd(&stats[2], 1u);
-        ctrl->flag = hand_back ? 1u : 0u;                              // the exact scan behind this launch reads it
-        ctrl->cand_cnt = 0; ctrl->thr_inv = 0;                         // zero, as the words are kept
-    }
+    const bool hand_back = cnt > kBoundCandCap || !has_H || !bound_scan_norm_ok(qn, v.dim);
+    if (threadIdx.x == 0) decided(hand_back);
     if (hand_back) return;
     QConst qc; qc.qn = 0.0; qc.qn32 = 0.0f;
     if constexpr (M == QV_COSINE) qc.qn = qn;
@@ -1247,6 +1244,178 @@ k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundC
             dist_out[lane] = dead ? __uint_as_float(0x7F800000u) : unord_f32((uint32_t)(list >> 32));
         }
     }
+}
+
+template <int M>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand,
+                uint32_t* __restrict__ stats, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out) {
+    const uint32_t cnt = ctrl->cand_cnt, thr_inv = ctrl->thr_inv;
+    bound_rescore_query<M>(v, query, k, cnt, thr_inv != 0u, cand, rows_out, dist_out, [&](bool hand_back) {
+        stats[0] = cnt;
+        if (hand_back) (void)atomicAdd(&stats[1], 1u);
+        (void)atomicAdd(&stats[2], 1u);
+        ctrl->flag = hand_back ? 1u : 0u;                              // the exact scan behind this launch reads it
+        ctrl->cand_cnt = 0; ctrl->thr_inv = 0;                         // zero, as the words are kept
+    });
+}
+
+// ---------------------------------------------------------------- the bound scan as a shared pass: 2 - 8 queries over the bfloat16 copy --
+// Callers that arrive together share a pass (qv_coalesce.h), and a pass of 2 - 8 queries read the float32 tiles (k_flat_scan_mq) while the
+// copy lay idle.  Here the copy is read ONCE for QB = 4 or 8 queries; interval, threshold, collect and exact re-score are the single-query
+// path's, per query, so the answers are the exact scan's bits.
+//   k_bound_prep_mq  the query block qblk[step][16][QB] in float32 (slots past nq: zeros) and |q_j| as the reference's float64 chain, once.
+//   k_bound_scan_mq  k_bound_scan's walk — lane == row, a wave owns whole tiles, the lane's two 16-byte halves per step, each bfloat16
+//                    widened once — with the query values as SCALAR operands (uniform loads of qblk: per dimension the QB values are
+//                    contiguous, so a query PAIR is one 64-bit scalar operand of a packed float32 fma whose two halves are two queries'
+//                    chains: 64 packed fmas + 16 widenings per step and lane at QB = 8 where one fma per query and element is 128 + 16).
+//                    Each (query, row) sum is still ONE in-order chain of dim fmas, one rounding each: qv_bound.h's gamma as it stands.
+//                    d_lo -> lo_all[q][n_tiles * 64]; d_hi -> per-query wave lists -> partial[q][grid][k], k_flat_scan_mq's layout.
+//   k_merge_lists    per query over its upper-bound lists: its k-th entry is H (valid: the row is a row and the bound is finite).
+//   k_bound_collect_mq / k_bound_rescore_mq   blockIdx.y / blockIdx.x = query: a candidate list, a counter (BoundCtrl::cand_cnt of its
+//                    own, left zero) and a hand-back flag per query.  A query is handed back on its own grounds; launch_flat_redo_flagged
+//                    behind the re-score redoes exactly the flagged ones with the exact scan, on the device.
+// (Measured: profiles/LAB_r08_bound_scan_mq.md.)
+constexpr uint32_t kBoundMqMax = 8;            // queries per shared pass (BoundCtrl x 8 behind kBoundCtrlWord fit the stream's 64 ticket words)
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+template <int QB>
+__global__ void __launch_bounds__(256)
+k_bound_prep_mq(const float* __restrict__ queries, uint32_t nq, uint32_t dim, float* __restrict__ qblk, double* __restrict__ qnorm, uint32_t* __restrict__ stats) {
+    __shared__ float s_q[kBoundMaxDim];
+    const uint32_t nb = gridDim.x - QB;                                // blocks [0, nb): the block; [nb, nb + QB): one query's norm each
+    if (blockIdx.x < nb) {
+        const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < dim * QB) {
+            const uint32_t j = i % QB, d = i / QB;
+            qblk[i] = j < nq ? queries[(size_t)j * dim + d] : 0.f;
+        }
+        if (i == 0) stats[0] = 0;                                      // the pass's largest survivor count (k_bound_rescore_mq)
+        return;
+    }
+    const uint32_t j = blockIdx.x - nb;
+    if (j >= nq) { if (threadIdx.x == 0) qnorm[j] = 0.0; return; }
+    for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) s_q[i] = queries[(size_t)j * dim + i];
+    __syncthreads();
+    if (threadIdx.x == 0) {                                            // the reference's chain (distances.go:20), as k_bound_rescore walks it
+        double ma = 0.0;
+        for (uint32_t i = 0; i < dim; i++) { const double a = (double)s_q[i]; ma = __builtin_fma(a, a, ma); }
+        qnorm[j] = __builtin_sqrt(ma);
+    }
+}
+
+template <int QB, int U>
+__device__ __forceinline__ void bound_block_mq(const u4* __restrict__ p, const float* __restrict__ qblk, uint32_t s0, f2 (&acc)[QB / 2]) {
+    u4 x[2 * U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        x[2 * u] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 128]);
+        x[2 * u + 1] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 128 + 32]);
+    }
+    __builtin_amdgcn_sched_barrier(0);                                 // all requests of the block ahead of the arithmetic (see row_accumulate)
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const f2* qq = reinterpret_cast<const f2*>(qblk + (size_t)(s0 + u) * 16 * QB);   // global, uniform -> scalar loads
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const u4 w = x[2 * u + h];
+            const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int g = 0; g < 4; g++) {                              // bfloat16 -> float32 is a shift / a mask: exact
+                const float r0 = __uint_as_float(ww[g] << 16), r1 = __uint_as_float(ww[g] & 0xFFFF0000u);
+                const f2 rr0 = {r0, r0}, rr1 = {r1, r1};
+#pragma unroll
+                for (int j = 0; j < QB / 2; j++) acc[j] = __builtin_elementwise_fma(qq[(h * 8 + g * 2) * (QB / 2) + j], rr0, acc[j]);
+#pragma unroll
+                for (int j = 0; j < QB / 2; j++) acc[j] = __builtin_elementwise_fma(qq[(h * 8 + g * 2 + 1) * (QB / 2) + j], rr1, acc[j]);
+            }
+        }
+    }
+}
+
+template <int M, int QB>
+__global__ void __launch_bounds__(kScanBlock, 2)
+k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __restrict__ qnorm, uint32_t nq, uint32_t k,
+                uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64]
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves, kth = k - 1;
+    const size_t n = (size_t)v.n_tiles * 64;
+    const double gamma = bound_scan_gamma(v.dim);
+    const u4* plane = reinterpret_cast<const u4*>(v.plane) + ((lane >> 5) * 64 + (lane & 31));
+    uint64_t list[QB], thr[QB];
+    double qn[QB];
+#pragma unroll
+    for (int j = 0; j < QB; j++) { list[j] = kDeadKey; thr[j] = kDeadKey; qn[j] = qnorm[j]; }
+    bool first = true;
+    for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+        f2 acc[QB / 2];
+#pragma unroll
+        for (int j = 0; j < QB / 2; j++) acc[j] = f2{0.f, 0.f};
+        const u4* p = plane + (size_t)t * steps * 128;
+        uint32_t s = 0;
+        for (; s + 8 <= steps; s += 8) bound_block_mq<QB, 8>(p, qblk, s, acc);
+        if (s + 4 <= steps) { bound_block_mq<QB, 4>(p, qblk, s, acc); s += 4; }
+        if (s + 2 <= steps) { bound_block_mq<QB, 2>(p, qblk, s, acc); s += 2; }
+        if (s < steps) bound_block_mq<QB, 1>(p, qblk, s, acc);
+        const uint32_t row = t * 64 + lane;
+        const double rn = v.rnorm[row];
+        const float rr = v.rres[row];
+        const bool live = (v.alive[t] >> lane) & 1ull;                 // (dead rows and the last tile's padding: never candidates, never in a bound)
+#pragma unroll
+        for (int j = 0; j < QB; j++) {
+            if ((uint32_t)j < nq) {                                    // (uniform) slots past nq produce nothing
+                float lo, hi;
+                (void)bound_scan_interval<M>((j & 1) ? acc[j / 2].y : acc[j / 2].x, qn[j], rn, rr, v.dim, gamma, lo, hi);
+                __builtin_nontemporal_store(live ? ord_f32(lo) : 0xFFFFFFFFu, &lo_all[(size_t)j * n + row]);
+                const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+                if (first) { list[j] = wave_sort64(key, lane); thr[j] = readlane64(list[j], kth); }
+                else list_insert(list[j], thr[j], key, kth, lane);
+            }
+        }
+        first = false;
+    }
+#pragma unroll
+    for (int j = 0; j < QB; j++) wl[((size_t)wave * QB + j) * 64 + lane] = list[j];
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int j = 0; j < QB; j++) {
+            if ((uint32_t)j < nq) {
+                for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list[j], thr[j], lane < k ? wl[((size_t)w * QB + j) * 64 + lane] : kDeadKey, kth, lane);
+                if (lane < k) partial[((size_t)j * gridDim.x + blockIdx.x) * k + lane] = list[j];
+            }
+        }
+    }
+}
+
+// H of query blockIdx.y: the k-th entry of its merged upper-bound list (seed_rows / seed_dist [nq][k])
+__global__ void __launch_bounds__(256)
+k_bound_collect_mq(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, uint32_t k, const uint32_t* __restrict__ seed_rows, const float* __restrict__ seed_dist,
+                   BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand) {
+    const uint32_t j = blockIdx.y;
+    const uint32_t H = ord_f32(seed_dist[(size_t)j * k + k - 1]);
+    if (seed_rows[(size_t)j * k + k - 1] == 0xFFFFFFFFu || H >= 0xFF800000u) return;   // no H: k_bound_rescore_mq hands the query back
+    bound_collect(lo_all + (size_t)j * n, n, H, &ctrl[j].cand_cnt, cand + (size_t)j * kBoundCandCap);
+}
+
+template <int M>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_rescore_mq(IndexView v, const float* __restrict__ queries, uint32_t k, const uint32_t* __restrict__ seed_rows, const float* __restrict__ seed_dist,
+                   BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand, uint32_t* __restrict__ flags, uint32_t* __restrict__ stats,
+                   uint32_t* __restrict__ rows_out, float* __restrict__ dist_out) {
+    const uint32_t j = blockIdx.x;
+    const uint32_t cnt = ctrl[j].cand_cnt;
+    const bool has_H = seed_rows[(size_t)j * k + k - 1] != 0xFFFFFFFFu && ord_f32(seed_dist[(size_t)j * k + k - 1]) < 0xFF800000u;
+    bound_rescore_query<M>(v, queries + (size_t)j * v.dim, k, cnt, has_H, cand + (size_t)j * kBoundCandCap, rows_out + (size_t)j * k, dist_out + (size_t)j * k, [&](bool hand_back) {
+        (void)atomicMax(&stats[0], cnt);
+        if (hand_back) (void)atomicAdd(&stats[1], 1u);
+        (void)atomicAdd(&stats[2], 1u);
+        flags[j] = hand_back ? 1u : 0u;                                // launch_flat_redo_flagged behind this launch reads them
+        ctrl[j].cand_cnt = 0;                                          // zero, as the words are kept
+    });
 }
 
 ScanPlan plan_scan(uint32_t n_tiles, int cus) {
@@ -1378,14 +1547,30 @@ bool flat_split_mq_applies(const IndexView& v, uint32_t nq, uint32_t k) {
 // The bound scan (k_bound_scan / k_bound_rescore above): one query, a fused-list k, cosine or dot, the bfloat16 copy at hand, a width the copy
 // covers in whole 16-dimension steps.  Automatic from kBoundScanMinRows rows (measured: profiles/LAB_r07_bound_scan.md); the index's setter
 // (IndexView::bound_scan) or QV_BOUND_SCAN = 1 takes it whenever it applies, 2 never.
+// 2 - 8 queries (k_bound_scan_mq): the same conditions, and nq planes of lower bounds that stay under 2 GiB.  Its automatic rule is a floor on
+// rows that depends on the width — every query pays 8 bytes per row for its lower bounds whatever the width — per QB: the smallest measured
+// shape from which the path wins at every measured nq and k of that QB (profiles/LAB_r08_bound_scan_mq.md); narrower than
+// kBoundMqNarrowDim it is never automatic.
 constexpr uint32_t kBoundScanMinRows = 300000;   // one query, us, exact / bound scan at k = 1, 10, 64: 100 k x 768 65 / 63, 66 / 70, 86 / 122; 300 k x 768 154 / 107, 158 / 114, 190 / 169; 1M x 128 89 / 64, 93 / 68, 134 / 114
-bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) {
-    static const int env_mode = env_int("QV_BOUND_SCAN", 0);
-    const int mode = v.bound_scan ? v.bound_scan : env_mode;
-    if (mode == 2 || nq != 1 || k < 1 || k > (uint32_t)kMaxFusedK || (v.metric != QV_COSINE && v.metric != QV_DOT) || v.plane == nullptr) return false;
-    if ((v.dim & 15u) != 0 || v.dim > kBoundMaxDim || v.n_tiles < 8) return false;
-    return mode == 1 || v.n_rows >= kBoundScanMinRows;
+// us per call, exact (k_flat_scan_mq) / bound, at k = 1, 10, 64:
+//   QB = 4   300 k x 768  nq 2: 195 / 154, 204 / 160, 273 / 223; nq 4: 193 / 160, 207 / 175, 276 / 271      1M x 128  nq 4: 97 / 93, 117 / 103, 214 / 216 (a loss)
+//            10M x 128    nq 2: 781 / 527, 793 / 532, 907 / 593; nq 4: 790 / 575, 793 / 587, 913 / 711
+//   QB = 8   300 k x 768  nq 8: 232 / 233, 254 / 264, 370 / 427 (losses)      1M x 768  nq 5: 526 / 449, 545 / 464, 695 / 598; nq 8: 526 / 456, 542 / 473, 697 / 694
+//            1M x 128     nq 8: 122 / 124, 145 / 157, 330 / 367 (losses)      10M x 128 nq 5: 888 / 638, 892 / 657, 1162 / 849; nq 8: 869 / 734, 905 / 775, 1161 / 1093
+constexpr uint32_t kBoundMqMinDim = 768, kBoundMqMinRows4 = 300000, kBoundMqMinRows8 = 1000000;   // rows of at least 768 dimensions: QB = 4 (2 - 4 queries), QB = 8 (5 - 8)
+constexpr uint32_t kBoundMqNarrowDim = 128, kBoundMqNarrowRows = 10000000;                        // 128 <= dim < 768 (nothing between was measured): both QB
+static int bound_scan_mode(int mode) { static const int env_mode = env_int("QV_BOUND_SCAN", 0); return mode ? mode : env_mode; }
+bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane) {
+    mode = bound_scan_mode(mode);
+    const uint32_t n_tiles = (n_rows + 63) / 64;
+    if (mode == 2 || nq < 1 || nq > kBoundMqMax || k < 1 || k > (uint32_t)kMaxFusedK || (metric != QV_COSINE && metric != QV_DOT) || !has_plane) return false;
+    if ((dim & 15u) != 0 || dim > kBoundMaxDim || n_tiles < 8) return false;
+    if (nq == 1) return mode == 1 || n_rows >= kBoundScanMinRows;
+    if ((uint64_t)nq * n_tiles * 256 > (2ull << 30)) return false;
+    const uint32_t min_rows = dim >= kBoundMqMinDim ? (nq <= 4 ? kBoundMqMinRows4 : kBoundMqMinRows8) : kBoundMqNarrowRows;
+    return mode == 1 || (dim >= kBoundMqNarrowDim && n_rows >= min_rows);
 }
+bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) { return bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr); }
 size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles) {
     return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)n_tiles * 64 * sizeof(uint32_t);
 }
@@ -1424,6 +1609,52 @@ float host_bound_interval(int metric, uint32_t dim, float s, double qn, double r
     return 0.f;
 }
 
+// the shared pass of 2 - 8 queries: d_ws = bound_scan_mq_workspace_bytes, d_ctrl = kBoundMqMax BoundCtrl (zero, left zero).  The exact scan of the
+// queries handed back is part of it (launch_flat_redo_flagged, in the bytes the lower bounds leave behind): nothing is read on the host.
+static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim) {
+    return up256((size_t)nq * p.grid * k * sizeof(uint64_t)) + 2 * up256((size_t)kBoundMqMax * 64 * 4) + 256 + 256 + up256((size_t)dim * kBoundMqMax * sizeof(float)) +
+           std::max((size_t)nq * kBoundCandCap * sizeof(uint32_t) + (size_t)nq * n_tiles * 64 * sizeof(uint32_t), redo_workspace_bytes(p, nq, k));
+}
+hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
+                                uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
+    if (nq < 2 || !bound_scan_applies(v, nq, k) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    const uint32_t grid = p.grid;
+    char* w = static_cast<char*>(d_ws);
+    uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += up256((size_t)nq * grid * k * sizeof(uint64_t));
+    uint32_t* seed_rows = reinterpret_cast<uint32_t*>(w); w += up256((size_t)kBoundMqMax * 64 * 4);
+    float* seed_dist = reinterpret_cast<float*>(w); w += up256((size_t)kBoundMqMax * 64 * 4);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(w); w += 256;
+    double* qnorm = reinterpret_cast<double*>(w); w += 256;
+    float* qblk = reinterpret_cast<float*>(w); w += up256((size_t)v.dim * kBoundMqMax * sizeof(float));
+    void* redo_ws = w;                                                 // (cand and lo_all are dead once the re-score has run)
+    uint32_t* cand = reinterpret_cast<uint32_t*>(w); w += (size_t)nq * kBoundCandCap * sizeof(uint32_t);
+    uint32_t* lo_all = reinterpret_cast<uint32_t*>(w);
+    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
+    BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
+    const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    hipError_t e = hipSuccess;
+#define QV_BOUND_MQ(MMM, QQ)                                                                                                 \
+    {                                                                                                                         \
+        const size_t lds1 = (size_t)kScanWaves * QQ * 64 * sizeof(uint64_t);                                                  \
+        e = set_lds(k_bound_rescore_mq<MMM>, lds2); if (e != hipSuccess) return e;                                            \
+        hipLaunchKernelGGL((k_bound_prep_mq<QQ>), dim3((v.dim * QQ + 255) / 256 + QQ), dim3(256), 0, s, d_queries, nq, v.dim, qblk, qnorm, d_stats); \
+        hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial); \
+        hipLaunchKernelGGL(k_merge_lists, dim3(nq), dim3(mblock), 0, s, partial, grid, k, seed_rows, seed_dist);             \
+        hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand); \
+        hipLaunchKernelGGL((k_bound_rescore_mq<MMM>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out); \
+    }
+    const uint32_t total = grid * k, mblock = total >= 16 * 64 * 4 ? kMergeBlock : (total >= 4 * 64 ? 256 : 64);
+    if (v.metric == QV_COSINE) { if (nq <= 4) QV_BOUND_MQ(QV_COSINE, 4) else QV_BOUND_MQ(QV_COSINE, 8) }
+    else { if (nq <= 4) QV_BOUND_MQ(QV_DOT, 4) else QV_BOUND_MQ(QV_DOT, 8) }
+#undef QV_BOUND_MQ
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_flat_redo_flagged(v, p, d_queries, nq, k, k, flags, redo_ws, d_rows_out, d_dist_out, s);
+}
+int host_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane) { return bound_scan_rule(metric, dim, rows, nq, k, mode, has_plane != 0) ? 1 : 0; }
+
+
 hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k,
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
                             hipEvent_t ev0, hipEvent_t ev1, uint32_t* d_tickets, uint32_t* done_flag, uint32_t done_seq, bool* flag_used, uint32_t* d_bound_stats) {
@@ -1432,6 +1663,15 @@ hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* 
     uint64_t* partial = static_cast<uint64_t*>(d_ws);
     hipError_t e = hipSuccess;
     static const int mq_min = dev_env_int("QV_MQ_MIN", 2);                // nq >= this: queries share a corpus pass
+    // 2 - 8 queries sharing one pass over the bfloat16 copy (forced on, it goes ahead of the short-corpus form; on its own it leaves that form its shapes)
+    if ((int)nq >= mq_min && nq >= 2 && d_tickets && d_bound_stats && bound_scan_applies(v, nq, k) && (bound_scan_mode(v.bound_scan) == 1 || !flat_split_mq_applies(v, nq, k))) {
+        static const int trace = env_int("QV_TRACE", 0);
+        if (trace) fprintf(stderr, "qv: scan kernel = k_bound_scan_mq QB=%d (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
+        if (ev0) (void)hipEventRecord(ev0, s);
+        e = launch_bound_scan_mq(v, p, d_queries, nq, k, d_ws, d_tickets + kBoundCtrlWord, d_bound_stats, d_rows_out, d_dist_out, s);
+        if (ev1) (void)hipEventRecord(ev1, s);
+        return e;
+    }
     if ((int)nq >= mq_min && flat_split_mq_applies(v, nq, k)) {
         // a shared pass of a few queries over a short corpus of wide rows: the tile-over-eight-waves form, up to 8 queries per workgroup row
         const uint32_t grid = std::min<uint32_t>(v.n_tiles, std::min<uint32_t>((uint32_t)p.cus, p.n_lists * 4u));
