@@ -294,6 +294,18 @@ int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, 
  * rounded up.  Returns 1 when the row is one the bound says nothing about (always a survivor), 0 otherwise with
  * [*d_lo, *d_hi] containing the float32 distance, < 0 on an error. */
 int qv_scan_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi);
+/* FOR TESTS: one of the arrays ingest derives per row, copied to the host raw — no kernel, no decoding — after the device has
+ * finished the index's work.  QV_DEBUG_RNORM: |r|, one double per row slot; QV_DEBUG_RRES: |r - bf16(r)| rounded up, one float per
+ * row slot; QV_DEBUG_PLANE: the bfloat16 copy's bytes ([tile][16-dim step][32-row block][8-dim half][row of block][8 values]).
+ * The extent is tiles in use x 64 slots (tiles in use x the copy's bytes per tile, 2 * 64 * 16 * ceil(dim / 16), for the copy); slots
+ * past the last row and dead rows hold whatever was written there last.  QV_ERR_UNSUPPORTED for an array this index does not keep
+ * (the copy without QV_FLAG_BF16_ROWS on a metric other than cosine / dot, under QV_FLAG_NO_SCAN_PLANE or after a failed
+ * allocation; the residual and the norm on metrics whose ingest does not compute them), QV_ERR_INVALID_ARG when `bytes` is less
+ * than the extent. */
+#define QV_DEBUG_RNORM 0
+#define QV_DEBUG_RRES  1
+#define QV_DEBUG_PLANE 2
+int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes);
 
 /* Device-pointer form of the batched path: enqueues on `stream`, no sync.  d_redo_flags_out[nq]
  * (uint32) is set to 1 for queries whose candidate buffer overflowed or — 16 or more results per query over 131 072 rows or

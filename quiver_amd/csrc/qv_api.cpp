@@ -1183,6 +1183,31 @@ int qv_scan_bound_interval(int metric, uint32_t dim, float s, double qn, double 
     return unsure;
 }
 
+int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    const int m = idx->metric;
+    const bool f64norm = m == QV_COSINE || m == QV_DOT || m == QV_L2 || m == QV_L2SQ;   // the metrics ingest keeps |r| and the residual for
+    const size_t tiles = ((size_t)idx->n_rows + 63) / 64;
+    const void* src = nullptr; size_t need = 0;
+    if (what == QV_DEBUG_RNORM) {
+        if (!f64norm && m != QV_COSINE_F32) return fail(QV_ERR_UNSUPPORTED, "metric %d keeps no row norms", m);
+        src = idx->d_rnorm; need = tiles * 64 * sizeof(double);
+    } else if (what == QV_DEBUG_RRES) {
+        if (!f64norm) return fail(QV_ERR_UNSUPPORTED, "metric %d keeps no bfloat16 residuals", m);
+        src = idx->d_rres; need = tiles * 64 * sizeof(float);
+    } else if (what == QV_DEBUG_PLANE) {
+        if (!idx->wants_plane() || (tiles && !idx->d_bf16)) return fail(QV_ERR_UNSUPPORTED, "this index keeps no bfloat16 copy");
+        src = idx->d_bf16; need = tiles * idx->bf16_tile_bytes();
+    } else return fail(QV_ERR_INVALID_ARG, "what must be 0 (norms), 1 (residuals) or 2 (the bfloat16 copy); got %d", what);
+    if (bytes < need) return fail(QV_ERR_INVALID_ARG, "%zu bytes given, %zu needed", bytes, need);
+    if (need == 0) return QV_OK;
+    if (!out) return fail(QV_ERR_INVALID_ARG, "out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, src, need, hipMemcpyDeviceToHost));
+    return QV_OK;
+}
+
 int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane) {
     if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
     return qv::host_bound_applies(metric, dim, rows, nq, k, mode, has_plane);

@@ -257,8 +257,8 @@ k_bf16_plane(IndexView v, uint32_t t0, uint32_t n_tiles) {
 // |r - bf16(r)| of the rows of tiles [t0, t0 + n_tiles): what the one-term bfloat16 filter drops of a row (qv_batched.hip: its
 // margin is |q - qh||r| + |qh||r - rh|, a third of the worst case 2 * 2^-8 |q||r| on ordinary data).  Lane == row, one wave per
 // tile, 1 KiB per request; the value only feeds a bound, so it is rounded UP (float64 sum, correctly rounded sqrt, one more
-// float32 step than round-to-nearest) and the order of the additions is free.  Elements below 2^-126 in magnitude count whole:
-// the matrix core may flush such an operand.
+// float32 step than round-to-nearest) and the order of the additions is free.  Elements whose bfloat16 IMAGE is below 2^-126 in
+// magnitude count whole (an element just under 2^-126 that rounds up to it does not): the matrix core may flush such an operand.
 __global__ void __launch_bounds__(64)
 k_row_residual(IndexView v, uint32_t t0) {
     const uint32_t t = t0 + blockIdx.x, lane = threadIdx.x;

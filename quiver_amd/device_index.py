@@ -246,6 +246,19 @@ class DeviceIndex:
         check(lib().qv_index_bound_scan_stats(self._h, out))
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
+    DEBUG_READ = {"rnorm": (0, np.float64), "rres": (1, np.float32), "plane": (2, np.uint16)}
+
+    def debug_read(self, what: str) -> np.ndarray:
+        """FOR TESTS (qv_index_debug_read): one of the arrays ingest derives per row, as the device holds it — "rnorm" (float64 per row
+        slot), "rres" (float32 per row slot) or "plane" (the bfloat16 copy as uint16 words in ITS layout: the caller decodes it) — over
+        the tiles in use.  Raises QvError(QV_ERR_UNSUPPORTED) for an array this index does not keep."""
+        code, dtype = self.DEBUG_READ[what]
+        tiles = (self.rows() + 63) // 64
+        per_tile = 2 * 64 * 8 * ((self.dim + 15) // 16) if what == "plane" else 64     # uint16 words of a tile of the copy: qv_index::bf16_tile_bytes() / 2 (qv_api_internal.h)
+        out = np.empty(tiles * per_tile, dtype=dtype)
+        check(lib().qv_index_debug_read(self._h, code, out.ctypes.data, out.nbytes))
+        return out
+
     def set_filter(self, filter):
         """the batched path's filter kernel: "auto", "fp32" (fp32 MFMA chain), "bf16x3", "bf16x1", or "off" — exact scans only (qv_index_set_filter)"""
         check(lib().qv_index_set_filter(self._h, self.FILTERS.get(filter, filter)))

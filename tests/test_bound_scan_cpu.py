@@ -13,58 +13,8 @@ import quiver_amd
 from quiver_amd import _lib
 from tests import _extremes as X
 from tests import _oracle as O
+from tests._bound import COSINE, DOT, interval, query_ok
 from tests._order import planted_rows, query_for
-
-COSINE, DOT = 0, 3
-
-
-def bf16(x):
-    """round to nearest even, as the device's conversion (finite values; NaN and Inf pass through)"""
-    b = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    r = ((b + 0x7FFF + ((b >> 16) & 1)) >> 16) << 16
-    keep = ~np.isfinite(x)
-    r[keep] = b[keep] & 0xFFFF0000
-    return (r & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
-
-
-def chain32(q, rh):
-    """the float32 fma chain in element order (a product of 24 x 8 bits is exact in float64; one rounding to float32 per step)"""
-    acc = np.float32(0.0)
-    with np.errstate(all="ignore"):
-        for a, b in zip(q.astype(np.float64), rh.astype(np.float64)):
-            acc = np.float32(a * b + np.float64(acc))
-    return acc
-
-
-def chain_norm(v):
-    s = 0.0
-    with np.errstate(all="ignore"):
-        for a in v.astype(np.float64):
-            s = a * a + s                     # exact product of float32 values: fma == multiply-add
-        return float(np.sqrt(s))
-
-
-def residual_up(r, rh):
-    with np.errstate(all="ignore"):
-        d = r.astype(np.float64) - rh.astype(np.float64)
-        v = np.float32(np.sqrt(float(np.sum(d * d))) * (1.0 + 1e-12))
-    if np.isfinite(v):
-        v = np.nextafter(v, np.float32(np.inf)) if (v != 0 or np.any(d != 0)) else v
-    return v
-
-
-def query_ok(qn, dim):
-    tiny = max(float(np.sqrt(np.float32(dim) * np.float32(2.4e-32))), 1.0e-14)
-    return bool(qn >= tiny and qn < 1.0e18)
-
-
-def interval(metric, q, r):
-    rh = bf16(r)
-    lo, hi = C.c_float(0), C.c_float(0)
-    qn, rn = chain_norm(q), chain_norm(r)
-    rc = _lib.lib().qv_scan_bound_interval(metric, q.size, C.c_float(chain32(q, rh)), qn, rn, C.c_float(residual_up(r, rh)), C.byref(lo), C.byref(hi))
-    assert rc in (0, 1), _lib.lib().qv_last_error()
-    return rc == 1, np.float32(lo.value), np.float32(hi.value), qn
 
 
 def check(metric, q, r):
