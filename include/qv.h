@@ -189,7 +189,9 @@ int qv_index_search_device(qv_index* idx, const float* d_queries, uint32_t nq, u
  * Collection.Search (collection.go:679-759 ranks ALL rows — searchK = Index.Size() — and keeps the first k
  * whose metadata matches; when the match set is known up front the same k results come from a top-k over
  * the matching rows, without producing or downloading the full ranking).  count_out[q] =
- * min(k, live rows selected by mask); other arguments and ordering as qv_index_search. */
+ * min(k, live rows selected by mask); other arguments and ordering as qv_index_search.  Up to 8 queries and 64 results of a
+ * cosine / dot index take the bound scan on the bfloat16 copy over the candidates under the modes of qv_index_set_bound_scan
+ * (the rule: qv_scan_bound_applies_filtered), with the exact scan's rows and bits. */
 int qv_index_search_masked(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint64_t* mask,
                            uint32_t* rows_out, float* dist_out, uint32_t* count_out);
 
@@ -225,7 +227,10 @@ void qv_rowset_destroy(qv_rowset* rs);
  * own set, and a tile none of the pass's sets selects is not read at all; above
  * 64, runs of consecutive queries naming the same set go through the selection / ranking paths of qv_index_search over
  * a candidate bitmap formed on the device.  Concurrent calls of up to 8 queries share passes like qv_index_search's
- * (a front of their own: qv_index_rowset_coalesce_stats, laid out as qv_index_coalesce_stats). */
+ * (a front of their own: qv_index_rowset_coalesce_stats, laid out as qv_index_coalesce_stats).  A call (or shared pass) of 1 - 8
+ * queries, k <= 64, takes the bound scan on the bfloat16 copy under the modes of qv_index_set_bound_scan, query j restricted to
+ * live & sets[j] (qv_scan_bound_applies_filtered is the rule; qv_index_bound_scan_stats counts these searches too): same rows, bits,
+ * order, counts and padding; a set holding fewer than k live rows is answered by the exact scan, decided on the device. */
 int qv_index_search_rowsets(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
                             uint32_t* rows_out, float* dist_out, uint32_t* count_out);
 /* Device-pointer form: queries / results on the device, `sets` still a HOST array of handles (read before the call
@@ -270,7 +275,10 @@ int qv_index_set_filter(qv_index* idx, int filter);
  * bit-identical to the exact scan's; when the bound cannot decide (too many survivors, a query whose norm is not a number, huge or
  * vanishing) the exact scan answers instead, decided on the device.  QV_BOUND_SCAN_AUTO: from the measured row count on;
  * QV_BOUND_SCAN_ALWAYS: whenever the copy exists and the shape applies; QV_BOUND_SCAN_NEVER.  The environment variable
- * QV_BOUND_SCAN (1 always, 2 never; read once per process) sets the default of indexes that never call this. */
+ * QV_BOUND_SCAN (1 always, 2 never; read once per process) sets the default of indexes that never call this.
+ * Filtered searches (qv_index_search_masked, qv_index_search_rowsets and its device form) take the bound scan under the same modes:
+ * ALWAYS whenever the shape applies, NEVER never, AUTO by qv_scan_bound_applies_filtered (the measured shapes).
+ * qv_sharded_search_masked keeps the exact scan. */
 #define QV_BOUND_SCAN_AUTO   0
 #define QV_BOUND_SCAN_ALWAYS 1
 #define QV_BOUND_SCAN_NEVER  2
@@ -287,8 +295,18 @@ int qv_index_set_bound_scan(qv_index* idx, int mode);
 int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]);
 /* Whether a search of nq queries for k results over rows x dim of `metric` would take the path under `mode` (QV_BOUND_SCAN_*;
  * has_plane: the index holds the copy) — the dispatch's own rule, on the host, without an index or a device.  1 / 0, < 0 on an
- * error.  (A mask, a row set or a k above the live rows are the caller's to know: they never take it.) */
+ * error.  (A k above the live rows is the caller's to know; a mask or a row set: qv_scan_bound_applies_filtered.) */
 int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane);
+/* The same rule for a filtered search (qv_index_search_masked, qv_index_search_rowsets and its device form): candidate_tiles = how many
+ * 64-row tiles hold a candidate of any query of the pass, as the host knows it without a device read — a row set counts its non-empty
+ * words (tombstones are not subtracted), a null set every tile, a pass of several queries min(tiles, the sum over its queries); a mask the
+ * non-empty words of live & mask.  QV_BOUND_SCAN_ALWAYS: whenever qv_scan_bound_applies' conditions hold (metric, whole 16-dimension
+ * steps, k <= 64, 1 - 8 queries, the copy, 8 tiles or more); QV_BOUND_SCAN_NEVER: never; QV_BOUND_SCAN_AUTO: the shapes measured
+ * faster than the exact filtered scan (profiles/LAB_r09_bound_scan_filtered.md) — rows of 768 dimensions or more; one query from
+ * 300 000 rows with a tenth of the tiles or more; 2 - 4 queries from 1M rows with nine tenths of the tiles (from 10M: a fifth);
+ * 5 - 8 queries from 1M rows with nine tenths of the tiles and k <= 10 (from 10M: any k) — never below the unfiltered floors and
+ * never with candidate_tiles == 0.  (A row set that selects fewer than k rows counts as no candidate tile.) */
+int qv_scan_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles);
 /* The interval stage 1 derives for one row, on the host (the kernel's own function compiled for the CPU; metric QV_COSINE or
  * QV_DOT): s = the float32 chain of the query times the row's bfloat16 copy, qn = |query|, rn = |row|, rres = |row - bf16(row)|
  * rounded up.  Returns 1 when the row is one the bound says nothing about (always a survivor), 0 otherwise with

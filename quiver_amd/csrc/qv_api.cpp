@@ -383,7 +383,8 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
                           void* ws, size_t ws_bytes, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
                           const uint64_t* d_candidates = nullptr /* row bitmap replacing the tombstone bitmap (filtered search) */,
                           uint32_t* d_tickets = nullptr /* the stream's tickets: allows the single-launch small scan */,
-                          uint32_t* done_flag = nullptr, uint32_t done_seq = 0, bool* flag_used = nullptr) {
+                          uint32_t* done_flag = nullptr, uint32_t done_seq = 0, bool* flag_used = nullptr,
+                          uint32_t candidate_tiles = 0 /* with d_candidates: the tiles that hold a candidate (an upper bound known on the host) */) {
     qv::IndexView v = idx->view();
     if (d_candidates) v.alive = const_cast<uint64_t*>(d_candidates);   // read-only in every scan kernel
     const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
@@ -396,15 +397,16 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
                 idx->prof_events.emplace_back(ev0, ev1);
             } else { ev0 = ev1 = nullptr; }
         }
-        // (a masked search keeps the exact scan: its candidates are not the index's live rows)
-        uint32_t* bound_stats = d_tickets && !d_candidates && qv::bound_scan_applies(v, nq, kk) ? idx->d_bound_stats : nullptr;
+        // (a masked search: the bound scan's forms that skip tiles without a candidate, under the filtered rule — given tickets)
+        const uint32_t cand_tiles = d_candidates ? candidate_tiles : qv::kBoundNoFilter;
+        uint32_t* bound_stats = d_tickets && (d_candidates ? qv::bound_scan_applies_filtered(v, nq, kk, cand_tiles) : qv::bound_scan_applies(v, nq, kk)) ? idx->d_bound_stats : nullptr;
         if (!bound_stats && d_tickets && qv::flat_small_applies(v, nq, kk) && !qv::flat_split_applies(v, nq, kk)) {   // small collection: scan + merge in one launch
             hipError_t e = qv::launch_flat_small(v, d_queries, nq, kk, ws, d_tickets, d_rows_out, d_dist_out, nq == 1 ? done_flag : nullptr, done_seq, s, ev0, ev1);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "small scan launch failed: %s", hipGetErrorString(e));
             if (flag_used) *flag_used = nq == 1 && done_flag != nullptr;
             return QV_OK;
         }
-        hipError_t e = qv::launch_flat_topk(v, plan, d_queries, nq, kk, ws, d_rows_out, d_dist_out, s, ev0, ev1, d_tickets, nq == 1 ? done_flag : nullptr, done_seq, flag_used, bound_stats);
+        hipError_t e = qv::launch_flat_topk(v, plan, d_queries, nq, kk, ws, d_rows_out, d_dist_out, s, ev0, ev1, d_tickets, nq == 1 ? done_flag : nullptr, done_seq, flag_used, bound_stats, cand_tiles);
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "flat scan launch failed: %s", hipGetErrorString(e));
         return QV_OK;
     }
@@ -435,14 +437,14 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
     return QV_OK;
 }
 
-static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride) {
+static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool bound_filtered = false /* a filtered call the bound scan will answer */) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     const qv::ScanPlan plan = qv::plan_scan(n_tiles, idx->cus);
     if (kk <= (uint32_t)qv::kMaxFusedK && kk == k_stride)   // partial lists + the multi-query kernels' query blocks (the small scan's lists fit in them)
         return std::max({qv::flat_small_workspace_bytes(std::min(nq, 4u), kk),
                         qv::scan_workspace_bytes(plan, nq, kk) + std::max(std::max((size_t)(nq + 16) * idx->dim4 * 4 * sizeof(double), qv::mq64_workspace_bytes(nq, idx->dim4)),
                                                                           nq == 1 ? qv::bound_scan_workspace_bytes(plan, kk, n_tiles) : (size_t)0),   // (the bound scan's lists sit behind the exact scan's)
-                                 nq >= 2 && nq <= 8 && qv::bound_scan_applies(idx->view(), nq, kk) ? qv::bound_scan_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim) : (size_t)0});   // (a shared bound pass has the workspace to itself)
+                                 nq >= 2 && nq <= 8 && (bound_filtered || qv::bound_scan_applies(idx->view(), nq, kk)) ? qv::bound_scan_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim) : (size_t)0});   // (a shared bound pass has the workspace to itself)
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
     return qv::full_sort_workspace_bytes(n_tiles);
@@ -682,10 +684,12 @@ int qv_index_search_masked(qv_index* idx, const float* queries, uint32_t nq, uin
     if ((rc = c->h_mask.ensure(words * 8)) || (rc = c->d_mask.ensure(words * 8))) return rc;
     uint64_t* hm = static_cast<uint64_t*>(c->h_mask.p);
     uint64_t matching = 0;
+    uint32_t cand_tiles = 0;                                          // tiles that hold a candidate: the filtered bound-scan rule's input
     for (size_t w = 0; w < words; w++) {
         const uint64_t a = w < idx->alive_host.size() ? idx->alive_host[w] : 0;
         hm[w] = a & mask[w];
         matching += (uint64_t)__builtin_popcountll(hm[w]);
+        cand_tiles += hm[w] != 0 ? 1u : 0u;
     }
     const uint32_t kk = (uint32_t)std::min<uint64_t>(k, matching);                // the first k matches of the full ranking
     for (uint32_t q = 0; q < nq; q++) count_out[q] = kk;
@@ -693,13 +697,23 @@ int qv_index_search_masked(qv_index* idx, const float* queries, uint32_t nq, uin
     const size_t qbytes = (size_t)nq * idx->dim * sizeof(float);
     const size_t obytes = (size_t)nq * kk * sizeof(uint32_t);
     if ((rc = c->d_q.ensure(qbytes)) || (rc = c->h_q.ensure(qbytes)) || (rc = c->d_rows.ensure(obytes)) || (rc = c->d_dist.ensure(obytes)) ||
-        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(obytes)) || (rc = c->ws.ensure(search_ws_bytes(idx, nq, kk, kk))))
+        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(obytes)))
         return rc;
+    // the bound scan under the mask when the filtered rule takes it: then, and only then, the call carries the context's ticket words
+    // (without them every path is the one a masked search has always taken)
+    const bool bound = kk <= (uint32_t)qv::kMaxFusedK && qv::bound_scan_applies_filtered(idx->view(), nq, kk, cand_tiles);
+    if ((rc = c->ws.ensure(search_ws_bytes(idx, nq, kk, kk, bound)))) return rc;
+    uint32_t* tickets = nullptr;
+    if (bound) {
+        if (!c->tickets.p) { if ((rc = c->tickets.ensure(256))) return rc; HIPCHK(hipMemsetAsync(c->tickets.p, 0, 256, c->stream)); }   // (on the stream that reads them: see stream_workspace)
+        tickets = static_cast<uint32_t*>(c->tickets.p);
+    }
     memcpy(c->h_q.p, queries, qbytes);
     HIPCHK(hipMemcpyAsync(c->d_mask.p, c->h_mask.p, words * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, qbytes, hipMemcpyHostToDevice, c->stream));
     rc = enqueue_search(idx, static_cast<const float*>(c->d_q.p), nq, kk, kk, c->ws.p, c->ws.cap,
-                        static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<const uint64_t*>(c->d_mask.p));
+                        static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<const uint64_t*>(c->d_mask.p),
+                        tickets, nullptr, 0, nullptr, cand_tiles);
     if (rc != QV_OK) return rc;
     HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, obytes, hipMemcpyDeviceToHost, c->stream));
@@ -729,6 +743,7 @@ int qv_rowset_create(qv_rowset** out, qv_index* idx, const uint64_t* mask) {
         memcpy(rs->host.data(), mask, (size_t)rs->words * 8);
         if (idx->n_rows & 63) rs->host[rs->words - 1] &= (1ull << (idx->n_rows & 63)) - 1;    // rows that do not exist yet start unselected
     }
+    for (uint64_t w : rs->host) { rs->tiles += w != 0 ? 1u : 0u; rs->selected += (uint64_t)__builtin_popcountll(w); }
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&rs->d_bits), std::max<size_t>((size_t)rs->words * 8, 256));
     if (e == hipSuccess && rs->words) e = hipMemcpy(rs->d_bits, rs->host.data(), (size_t)rs->words * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);           // (the index's streams are non-blocking: nothing of theirs may overtake the upload)
@@ -763,7 +778,12 @@ int qv_rowset_set_rows(qv_rowset* rs, const uint32_t* rows, uint32_t n, int sele
     if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row set update failed: %s", hipGetErrorString(e));
     for (uint32_t i = 0; i < n; i++) {
         const uint64_t bit = 1ull << (rows[i] & 63);
-        if (selected) rs->host[rows[i] >> 6] |= bit; else rs->host[rows[i] >> 6] &= ~bit;
+        uint64_t& w = rs->host[rows[i] >> 6];
+        const uint64_t before = w;
+        if (selected) w |= bit; else w &= ~bit;
+        if (w != before) { if (selected) rs->selected++; else rs->selected--; }
+        if (before == 0 && w != 0) rs->tiles++;                       // the count of non-empty words
+        else if (before != 0 && w == 0) rs->tiles--;
     }
     return QV_OK;
 }
@@ -799,13 +819,24 @@ static uint64_t rowset_live(const qv_index* idx, const qv_rowset* rs) {
 // per query (qv_rowset.hip).  Otherwise runs of consecutive queries naming the same set, each through the paths of qv_index_search
 // over the candidate bitmap alive & set, formed on the device (k_rowset_and) — a single query takes the single-launch scans that
 // way, longer lists the selection and ranking paths.
-struct RowsetPiece { uint32_t q0, nq, kk; bool multi; };
+// bound: a multi piece of 2 - 8 queries that the filtered bound-scan rule takes (launch_bound_scan_mq with the sets) — decided here, once, so
+// that the workspace and the launch agree.  cand_tiles: the tiles that hold a candidate of any query of the piece, as the host knows it: a
+// set counts its non-empty words (qv_rowset::tiles; tombstones are not subtracted), a null set every tile, a pass min(n_tiles, the sum).
+struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; };
+static uint32_t rowsets_cand_tiles(const qv_index* idx, const qv_rowset* const* sets, uint32_t nq) {
+    const uint32_t n_tiles = (idx->n_rows + 63) / 64;
+    uint64_t sum = 0;
+    for (uint32_t q = 0; q < nq; q++) sum += sets[q] ? sets[q]->tiles : n_tiles;
+    return (uint32_t)std::min<uint64_t>(sum, n_tiles);
+}
 static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const qv_rowset* const* sets, std::vector<RowsetPiece>& pieces) {
     const qv::ScanPlan plan = qv::plan_scan((idx->n_rows + 63) / 64, idx->cus);
     pieces.clear();
     if (k <= (uint32_t)qv::kMaxFusedK && nq >= 2) {
-        pieces.push_back(RowsetPiece{0, nq, k, true});
-        return qv::rowset_workspace_bytes(plan, nq, k, idx->dim4);
+        const uint32_t ct = rowsets_cand_tiles(idx, sets, nq);
+        const bool bound = nq <= 8 && qv::bound_scan_applies_filtered(idx->view(), nq, k, ct);   // (9 or more are not cut into bound passes)
+        pieces.push_back(RowsetPiece{0, nq, k, true, bound, ct});
+        return std::max(qv::rowset_workspace_bytes(plan, nq, k, idx->dim4), bound ? qv::bound_scan_mq_workspace_bytes(plan, nq, k, (idx->n_rows + 63) / 64, idx->dim) : (size_t)0);
     }
     size_t ws = 0;
     for (uint32_t q = 0; q < nq;) {
@@ -813,7 +844,10 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const q
         while (e < nq && sets[e] == sets[q]) e++;
         // (up to kMaxFusedK the lists are k long whatever the set holds: the scans pad, nothing is counted on the host)
         const uint32_t kk = k <= (uint32_t)qv::kMaxFusedK ? k : (uint32_t)std::min<uint64_t>(k, rowset_live(idx, sets[q]));
-        pieces.push_back(RowsetPiece{q, e - q, kk, false});
+        // (a set that selects fewer than kk rows has no threshold: the bound pass would only precede the exact scan that answers — reported
+        //  as no candidate tile, which the automatic rule declines; "always" still takes the path)
+        const bool too_few = sets[q] && sets[q]->selected < kk;
+        pieces.push_back(RowsetPiece{q, e - q, kk, false, false, sets[q] && !too_few ? std::min<uint32_t>(sets[q]->tiles, (idx->n_rows + 63) / 64) : 0u});
         if (kk) ws = std::max(ws, search_ws_bytes(idx, e - q, kk, k));
         q = e;
     }
@@ -836,7 +870,12 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
                 std::lock_guard<std::mutex> g(idx->prof_mu);
                 idx->prof_events.emplace_back(ev0, ev1);
             }
-            hipError_t e = qv::launch_rowset_topk(v, plan, q, p.nq, k, refs.data(), ws, r_out, d_out, s, ev0, ev1);
+            hipError_t e = hipSuccess;
+            if (p.bound && d_tickets) {                               // the pass on the bfloat16 copy, each query over its own candidates
+                if (ev0) (void)hipEventRecord(ev0, s);
+                e = qv::launch_bound_scan_mq(v, plan, q, p.nq, k, ws, d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, r_out, d_out, s, refs.data());
+                if (ev1) (void)hipEventRecord(ev1, s);
+            } else e = qv::launch_rowset_topk(v, plan, q, p.nq, k, refs.data(), ws, r_out, d_out, s, ev0, ev1);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set scan launch failed: %s", hipGetErrorString(e));
             continue;
         }
@@ -851,7 +890,7 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set bitmap launch failed: %s", hipGetErrorString(e));
             cand = d_mask;
         }
-        const int rc = enqueue_search(idx, q, p.nq, p.kk, k, ws, 0, r_out, d_out, s, cand, p.nq == 1 ? d_tickets : nullptr);
+        const int rc = enqueue_search(idx, q, p.nq, p.kk, k, ws, 0, r_out, d_out, s, cand, p.nq == 1 ? d_tickets : nullptr, nullptr, 0, nullptr, p.cand_tiles);
         if (rc != QV_OK) return rc;
     }
     return QV_OK;
@@ -1211,6 +1250,11 @@ int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {
 int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane) {
     if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
     return qv::host_bound_applies(metric, dim, rows, nq, k, mode, has_plane);
+}
+
+int qv_scan_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles) {
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    return qv::host_bound_applies_filtered(metric, dim, rows, nq, k, mode, has_plane, candidate_tiles);
 }
 
 int qv_index_profile(qv_index* idx, int enable) {

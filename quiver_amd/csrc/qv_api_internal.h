@@ -143,5 +143,7 @@ struct qv_rowset {
     uint64_t* d_bits = nullptr;
     uint32_t words = 0;
     std::vector<uint64_t> host;
+    uint32_t tiles = 0;                        // non-empty words of `host`: the tiles a scan under this set can have to read (the filtered bound-scan rule's input)
+    uint64_t selected = 0;                     // bits set in `host`, dead rows included: fewer than k means no threshold under this set (the rule's other input)
     Buf stage;                                 // row ids of qv_rowset_set_rows
 };

@@ -138,23 +138,32 @@ hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* 
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
                             hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, uint32_t* d_tickets = nullptr,
                             uint32_t* done_flag = nullptr, uint32_t done_seq = 0, bool* flag_used = nullptr,   // done_flag: see launch_flat_small (k_flat_scan_split only)
-                            uint32_t* d_bound_stats = nullptr);   // the index's bound-scan counters: with them (and tickets) a single query may take launch_bound_scan
+                            uint32_t* d_bound_stats = nullptr,   // the index's bound-scan counters: with them (and tickets) a single query may take launch_bound_scan
+                            uint32_t candidate_tiles = 0xFFFFFFFFu);   // not kBoundNoFilter: v.alive is a filter's candidate bitmap with at most so many non-empty tiles
 // The single-query scan on the bfloat16 copy (qv_bound.hip): stage 1 streams v.plane and lists the rows whose certified lower bound of
 // the distance is within the k-th smallest upper bound, stage 2 computes those rows' distances in the scan's own arithmetic and writes
 // the k results, or sets *gate (a device word) when the exact scan must answer instead; the caller then issues the exact scan with that
 // gate (it leaves at once when the word is zero).  d_ctrl: the stream's zeroed control words (kept zero); d_stats: the index's counters.
+struct RowSetRef;
+constexpr uint32_t kBoundNoFilter = 0xFFFFFFFFu;   // candidate_tiles of an unfiltered search
 bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k);
+// ... under a filter (candidate_tiles: the tiles that hold a candidate of any query of the pass, an upper bound known on the host)
+bool bound_scan_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
 size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles);
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s);
+                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s,
+                             bool masked = false);   // v.alive is a filter's candidate bitmap: the form that does not request tiles without a candidate (k_bound_scan<., true>)
 // ... and for the 2 - 8 queries of a shared pass (k_bound_scan_mq): d_ws bound_scan_mq_workspace_bytes, d_ctrl 8 BoundCtrl; the exact scan of
 // the queries it hands back is enqueued behind it (launch_flat_redo_flagged)
 size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim);
 hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                                uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+                                uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
+                                const RowSetRef* h_sets = nullptr);   // a HOST array of nq sets, at most 8: query j over alive & h_sets[j] (k_bound_scan_mq<., ., true>, the redo included)
 // bound_scan_applies without an index (qv_scan_bound_applies): mode 0 = automatic (QV_BOUND_SCAN decides), 1 always, 2 never
 bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane);
 int host_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane);
+bool bound_scan_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane, uint32_t candidate_tiles);
+int host_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles);
 // the interval of one row on the HOST (qv_scan_bound_interval): qv_bound.h's function compiled for the CPU
 float host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi, int* unsure);
 constexpr uint32_t kBoundCtrlWord = 16;   // the bound scan's control words start here in the stream's 64 ticket words
@@ -163,7 +172,8 @@ bool flat_split_applies(const IndexView& v, uint32_t nq, uint32_t k);   // launc
 // scanned on the device: nothing is read back.  Results replace rows / distances [q][k_stride] of those queries.  d_ws: redo_workspace_bytes.
 size_t redo_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k);
 hipError_t launch_flat_redo_flagged(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, uint32_t k_stride, const uint32_t* d_flags,
-                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
+                                    const RowSetRef* h_sets = nullptr);   // a HOST array of nq <= 8 sets (cosine / dot): query q is redone over alive & h_sets[q], tiles without a candidate skipped
 // Small collections (<= 256 tiles, <= 4 queries, k <= 16): scan + merge in ONE launch (the last workgroup to finish merges).
 // d_ws: flat_small_workspace_bytes (partial lists); d_tickets: 64 zeroed words that belong to the caller's stream alone (the kernel
 // leaves them zero).  done_flag (optional, device-visible host memory): receives done_seq after the results have been written.

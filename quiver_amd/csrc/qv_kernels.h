@@ -41,6 +41,14 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, uint32_t src /*unifor
     uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(x >> 32), src);
     return ((uint64_t)hi << 32) | lo;
 }
+// a query's candidates of tile t, alive & set (RowSetRef: words past the set's length are zero, null bits = every row).  Callers keep query
+// j's set in lane j (mine: this lane holds one; every other lane: 0) and read the word back with readlane64 (qv_rowset.hip, k_bound_scan_mq<., ., true>)
+__device__ __forceinline__ uint64_t rowset_word(const uint64_t* __restrict__ alive, const RowSetRef& r, bool mine, uint32_t t) {
+    if (!mine) return 0ull;
+    const uint64_t a = alive[t];
+    if (r.bits == nullptr) return a;
+    return t < r.words ? (a & r.bits[t]) : 0ull;
+}
 // lane i <- lane i-1 (lane 0 keeps its value); full-wave shift right by one
 __device__ __forceinline__ uint64_t wave_shr1(uint64_t x) {
     // DPP wave_shr:1 (0x138) is a gfx9-family control; bound_ctrl=0 keeps lane 0's old value

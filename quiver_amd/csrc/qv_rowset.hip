@@ -22,13 +22,7 @@ bool flat_split_mq_applies(const IndexView& v, uint32_t nq, uint32_t k);      //
 constexpr uint32_t kRsChunk = 64;                       // queries per launch: their sets travel as kernel arguments (1 KiB)
 struct RowSetTable { RowSetRef e[kRsChunk]; };
 
-// lane j < nqg: alive & set_j for tile t; every other lane: 0
-__device__ __forceinline__ uint64_t rowset_word(const uint64_t* __restrict__ alive, const RowSetRef& r, bool mine, uint32_t t) {
-    if (!mine) return 0ull;
-    const uint64_t a = alive[t];
-    if (r.bits == nullptr) return a;
-    return t < r.words ? (a & r.bits[t]) : 0ull;
-}
+// (rowset_word — lane j < nqg: alive & set_j for tile t; every other lane: 0 — is qv_kernels.h's: the bound scan's set forms use it too)
 
 // ---------------------------------------------------------------- whole tiles per wave (k_flat_scan_mq<., ., ., true> with a set per query) --
 // grid = (workgroups, groups of QB queries of this launch's chunk); qblk / partial / nq are the chunk's own.

@@ -362,11 +362,19 @@ __global__ void k_redo_compact(const uint32_t* __restrict__ flags, uint32_t nq, 
     if (threadIdx.x == 0) count[0] = s_n;
 }
 
-template <int M, int U>
+// SETS (the queries a bound pass under filters handed back, k_flat_scan_redo<., ., true>): listed query qi is rescanned over alive & set_qi, the
+// pass's table of at most kBoundSets entries indexed by qi (uniform: the pair is a scalar load from the kernel arguments), and a tile that
+// holds none of its candidates is not requested — a set of fewer than k live rows has no threshold and is ALWAYS handed back, so the empty
+// set and the "12 matching rows" set would otherwise each cost a pass over the corpus.  first_tile is the first tile the wave READS.
+constexpr uint32_t kBoundSets = 8;
+struct BoundSetTable { RowSetRef e[kBoundSets]; };
+struct NoSets {};                                                      // the last kernel argument of the forms without sets
+template <bool SETS> using SetsArg = typename std::conditional<SETS, BoundSetTable, NoSets>::type;
+template <int M, int U, bool SETS = false>
 __global__ void __launch_bounds__(kScanBlock)
 k_flat_scan_redo(IndexView v, const float* __restrict__ queries, uint32_t k, uint32_t k_stride, const uint32_t* __restrict__ list, const uint32_t* __restrict__ count,
                  uint32_t first, uint64_t* __restrict__ partial /* [kRedoSlots][grid][k] */, uint32_t* __restrict__ tickets /* [nq] by list position */,
-                 uint32_t* __restrict__ rows_out, float* __restrict__ dist_out) {
+                 uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, SetsArg<SETS> tab) {
     using Q = typename MT<M>::Q;
     const uint32_t n = count[0];
     if (first >= n) return;                                           // (the usual case: nothing was handed back)
@@ -386,7 +394,14 @@ k_flat_scan_redo(IndexView v, const float* __restrict__ queries, uint32_t k, uin
         uint64_t lst = kDeadKey, thr = kDeadKey;
         QConst qc; qc.qn = 0.0; qc.qn32 = 0.0f;
         bool first_tile = true;
+        RowSetRef rs = RowSetRef{nullptr, 0, 0};
+        if constexpr (SETS) rs = tab.e[qi & (kBoundSets - 1)];
         for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+            uint64_t am;                                               // wave-uniform
+            if constexpr (SETS) {
+                am = rowset_word(v.alive, rs, true, t);
+                if (am == 0ull) continue;
+            }
             typename MT<M>::A qn2 = 0, acc;
             if (first_tile) { acc = row_accumulate<M, U, true>(tiles + (size_t)t * v.dim4 * 64 + lane, 64, q_lds, v.dim4, &qn2); qc = qconst_from_norm2<M>(qn2); }
             else acc = row_accumulate<M, U, false>(tiles + (size_t)t * v.dim4 * 64 + lane, 64, q_lds, v.dim4);
@@ -394,7 +409,7 @@ k_flat_scan_redo(IndexView v, const float* __restrict__ queries, uint32_t k, uin
             double rn = 0.0;
             if constexpr (MT<M>::needs_rnorm) rn = v.rnorm[row];
             const float dist = finalize<M>(acc, qc, rn);
-            const uint64_t am = v.alive[t];
+            if constexpr (!SETS) am = v.alive[t];
             const uint64_t key = ((am >> lane) & 1ull) ? make_key(dist, row) : kDeadKey;
             if (first_tile) { lst = wave_sort64(key, lane); thr = readlane64(lst, kth); first_tile = false; }
             else list_insert(lst, thr, key, kth, lane);
@@ -1094,7 +1109,11 @@ __device__ __forceinline__ float bound_tile(const u4* __restrict__ p, const floa
     return acc;
 }
 
-template <int M>
+// SKIP (k_bound_scan<., true>: v.alive is a filter's candidate bitmap, alive & set — k_rowset_and's or the masked upload): a tile whose word is
+// zero is not requested, neither its copy nor rnorm nor rres.  Its 64 lower-bound words are WRITTEN as 0xFFFFFFFF all the same: k_bound_collect
+// reads every word and the workspace is reused, so an unwritten tile would hold an earlier search's bounds; 256 bytes stored against dim * 128
+// bytes not read, and the collect stays as it is.  |q|^2 rides along the first tile the wave READS; a wave that reads none publishes a dead list.
+template <int M, bool SKIP = false>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
              uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
@@ -1112,11 +1131,13 @@ k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl
     uint64_t list = kDeadKey, thr = kDeadKey;
     double qn = 0.0;
 
+    uint64_t am_read = 0ull;                                           // (SKIP) the word of the tile being walked
     auto finish_tile = [&](uint32_t t, float s, bool first) {
         const uint32_t row = t * 64 + lane;
         const double rn = v.rnorm[row];
         const float rr = v.rres[row];
-        const uint64_t am = v.alive[t];                                // wave-uniform
+        uint64_t am;                                                   // wave-uniform
+        if constexpr (SKIP) am = am_read; else am = v.alive[t];
         float lo, hi;
         (void)bound_scan_interval<M>(s, qn, rn, rr, v.dim, gamma, lo, hi);
         const bool live = (am >> lane) & 1ull;                         // (dead rows and the last tile's padding: never candidates, never in a bound)
@@ -1127,14 +1148,32 @@ k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl
     };
 
     uint32_t t = blockIdx.x * kScanWaves + wave;
-    if (t < v.n_tiles) {                                               // first tile: sorted outright, |q| rides along
-        double qn2 = 0.0;
-        const float s = bound_tile<true>(plane + (size_t)t * steps * 128, q_lds, steps, &qn2);
-        qn = __builtin_sqrt(qn2);
-        finish_tile(t, s, true);
-        t += tw;
+    if constexpr (SKIP) {
+        bool first = true;
+        uint64_t am_next = t < v.n_tiles ? v.alive[t] : 0ull;
+        for (; t < v.n_tiles; t += tw) {
+            const uint64_t am = am_next;
+            if (t + tw < v.n_tiles) am_next = v.alive[t + tw];         // (the next tile's word: in flight behind this tile's rows)
+            if (am == 0ull) { __builtin_nontemporal_store(0xFFFFFFFFu, &lo_all[t * 64 + lane]); continue; }
+            am_read = am;
+            if (first) {
+                double qn2 = 0.0;
+                const float s = bound_tile<true>(plane + (size_t)t * steps * 128, q_lds, steps, &qn2);
+                qn = __builtin_sqrt(qn2);
+                finish_tile(t, s, true);
+                first = false;
+            } else finish_tile(t, bound_tile<false>(plane + (size_t)t * steps * 128, q_lds, steps, nullptr), false);
+        }
+    } else {
+        if (t < v.n_tiles) {                                           // first tile: sorted outright, |q| rides along
+            double qn2 = 0.0;
+            const float s = bound_tile<true>(plane + (size_t)t * steps * 128, q_lds, steps, &qn2);
+            qn = __builtin_sqrt(qn2);
+            finish_tile(t, s, true);
+            t += tw;
+        }
+        for (; t < v.n_tiles; t += tw) finish_tile(t, bound_tile<false>(plane + (size_t)t * steps * 128, q_lds, steps, nullptr), false);
     }
-    for (; t < v.n_tiles; t += tw) finish_tile(t, bound_tile<false>(plane + (size_t)t * steps * 128, q_lds, steps, nullptr), false);
 
     // the upper bounds' lists: waves -> wave 0 -> published; the last workgroup to finish merges (k_flat_scan<., ., true>'s protocol)
     wl[wave * 64 + lane] = list;
@@ -1333,10 +1372,19 @@ __device__ __forceinline__ void bound_block_mq(const u4* __restrict__ p, const f
     }
 }
 
-template <int M, int QB>
+// SETS (k_bound_scan_mq<., ., true>: a pass under filters, query j restricted to am_j = alive & set_j): the sets' (bits, words) pairs arrive as kernel
+// arguments, as in k_rowset_scan_mq, and lane j keeps query j's — eight pairs held as scalars spilled 168 SGPRs there, and this kernel
+// already spends its scalar file on the packed-fma query operands.  rowset_word for the wave's NEXT tile is fetched while the current one is
+// walked and read back per query with readlane64 (wave-uniform again).  Bit `lane` of am_j gates query j's lower-bound word (a
+// non-candidate writes 0xFFFFFFFF) and its upper-bound key (kDeadKey), so H_j is the k-th smallest upper bound over query j's OWN
+// candidates and a set of fewer than k live rows has none (handed back).  A tile that no query selects is not requested — copy, rnorm,
+// rres —; its nq x 64 lower-bound words are written as 0xFFFFFFFF (256 bytes per query against dim * 128 of copy): k_bound_collect_mq
+// reads every word of a workspace that earlier searches have used, and stays as it is.  `first` is the first tile the wave READS.
+// The interval arithmetic is untouched.  A masked call (one bitmap for all queries, in v.alive) is this form with a table of null sets.
+template <int M, int QB, bool SETS = false>
 __global__ void __launch_bounds__(kScanBlock, 2)
 k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __restrict__ qnorm, uint32_t nq, uint32_t k,
-                uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */) {
+                uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */, SetsArg<SETS> tab) {
     extern __shared__ __align__(16) unsigned char smem[];
     uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64]
     const uint32_t lane = lane_id();
@@ -1350,7 +1398,26 @@ k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __res
 #pragma unroll
     for (int j = 0; j < QB; j++) { list[j] = kDeadKey; thr[j] = kDeadKey; qn[j] = qnorm[j]; }
     bool first = true;
+    const bool mine = SETS && lane < nq;
+    RowSetRef rs = RowSetRef{nullptr, 0, 0};
+    uint64_t w_next = 0ull;
+    if constexpr (SETS) {
+        static_assert(QB <= (int)kBoundSets, "one table entry per query of the pass");
+        rs = tab.e[mine ? lane : 0u];                                 // lane j: query j's set
+        const uint32_t t0 = blockIdx.x * kScanWaves + wave;
+        if (t0 < v.n_tiles) w_next = rowset_word(v.alive, rs, mine, t0);
+    }
     for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+        const uint64_t w = w_next;                                     // (SETS) lane j: am_j of this tile
+        if constexpr (SETS) {
+            if (t + tw < v.n_tiles) w_next = rowset_word(v.alive, rs, mine, t + tw);
+            if (__ballot(w != 0ull) == 0ull) {                         // nobody's candidate in this tile
+#pragma unroll
+                for (int j = 0; j < QB; j++)
+                    if ((uint32_t)j < nq) __builtin_nontemporal_store(0xFFFFFFFFu, &lo_all[(size_t)j * n + t * 64 + lane]);
+                continue;
+            }
+        }
         f2 acc[QB / 2];
 #pragma unroll
         for (int j = 0; j < QB / 2; j++) acc[j] = f2{0.f, 0.f};
@@ -1363,10 +1430,13 @@ k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __res
         const uint32_t row = t * 64 + lane;
         const double rn = v.rnorm[row];
         const float rr = v.rres[row];
-        const bool live = (v.alive[t] >> lane) & 1ull;                 // (dead rows and the last tile's padding: never candidates, never in a bound)
+        bool live_all = false;
+        if constexpr (!SETS) live_all = (v.alive[t] >> lane) & 1ull;   // (dead rows and the last tile's padding: never candidates, never in a bound)
 #pragma unroll
         for (int j = 0; j < QB; j++) {
             if ((uint32_t)j < nq) {                                    // (uniform) slots past nq produce nothing
+                bool live;
+                if constexpr (SETS) live = (readlane64(w, (uint32_t)j) >> lane) & 1ull; else live = live_all;
                 float lo, hi;
                 (void)bound_scan_interval<M>((j & 1) ? acc[j / 2].y : acc[j / 2].x, qn[j], rn, rr, v.dim, gamma, lo, hi);
                 __builtin_nontemporal_store(live ? ord_f32(lo) : 0xFFFFFFFFu, &lo_all[(size_t)j * n + row]);
@@ -1571,12 +1641,50 @@ bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uin
     return mode == 1 || (dim >= kBoundMqNarrowDim && n_rows >= min_rows);
 }
 bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) { return bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr); }
+// Under a filter (a candidate bitmap in v.alive, or a row set per query): candidate_tiles = the tiles that hold a candidate of any query of
+// the pass, as the host knows it without a device read (an upper bound: sets count their non-empty words, tombstones are not subtracted, a pass
+// takes min(n_tiles, the sum over its queries) — so eight queries naming ONE striped set look like eight distinct ones).  "always" takes
+// the path whenever the unfiltered conditions hold, "never" never.  Automatic: the cells of profiles/LAB_r09_bound_scan_filtered.md in which
+// "always" beat the exact filtered scan by more than both arms' spread at k = 10 AND 64 (or, where said, at k = 10 only), for every kind of
+// set that maps to the same host-side inputs; measured at 768 dimensions only, so narrower rows are declined; no floor below the
+// unfiltered ones.  us per call, exact / bound, 768 dims, k = 10 and 64 (f = candidate_tiles / tiles as the host computes it):
+//   one query     300 k: f 1.0 167 / 125, 201 / 181; one tile in ten 167 / 64, 201 / 122       1M: f 1.0 460 / 286, 496 / 349; one tile in ten 457 / 80, 489 / 137
+//   QB = 4        300 k: nq 2 170 / 166, 212 / 230; nq 4 176 / 179, 250 / 274 (losses: declined below 1M)
+//                 1M: f >= 0.9 nq 2 466 / 331, 506 / 398; nq 4 472 / 355, 551 / 451; striped sets (f 0.2 / 0.4) nq 2 126 / 141, nq 4 same set 111 / 140 (losses)
+//                 10M: nq 2 4406 / 2496; nq 4 4406 / 2670; striped (f 0.2) nq 2 1251 / 697, same set 671 / 439
+//   QB = 8 (nq 8) 1M: f 1.0 k = 10 557 / 486, density 0.01 one set 455 / 429; k = 64 740 / 702 but density 0.01 one set 477 / 495 (a loss with the same
+//                 inputs: k > 10 declined); striped f 0.8 distinct 416 / 390, one set 171 / 226 (a loss: f < 0.9 declined)
+//                 10M: f 1.0 5044 / 3819, 5373 / 4088; striped f 0.8 distinct 2806 / 2323, one set 912 / 917 (a loss: f < 0.9 declined)
+//   nq 3 and 5 - 7 were not run: the bound pass gets cheaper with fewer queries (a lower-bound plane and a collect each) while the exact pass of
+//   a QB costs the same at any fill (LAB_r08: 526 / 526 us at nq 5 / 8), so they are bracketed by the nq = 4 and nq = 8 cells.
+constexpr uint32_t kBoundFiltMinDim = 768, kBoundFiltMqRows = 1000000, kBoundFiltBigRows = 10000000, kBoundFiltQb8SmallK = 10;
+bool bound_scan_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane, uint32_t candidate_tiles) {
+    mode = bound_scan_mode(mode);
+    if (mode == 2 || !bound_scan_rule(metric, dim, n_rows, nq, k, 1, has_plane)) return false;
+    if (mode == 1) return true;
+    const uint64_t n_tiles = ((uint64_t)n_rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
+    if (ct == 0 || dim < kBoundFiltMinDim || !bound_scan_rule(metric, dim, n_rows, nq, k, 0, has_plane)) return false;   // (never below the unfiltered floors)
+    if (nq == 1) return ct * 10 >= n_tiles;                                                      // from kBoundScanMinRows rows; one tile in ten is the sparsest measured
+    if (n_rows < kBoundFiltMqRows) return false;
+    if (nq <= 4) return n_rows >= kBoundFiltBigRows ? ct * 5 >= n_tiles : ct * 10 >= n_tiles * 9;
+    return ct * 10 >= n_tiles * 9 && (n_rows >= kBoundFiltBigRows || k <= kBoundFiltQb8SmallK);
+}
+bool bound_scan_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
+    return bound_scan_rule_filtered(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr, candidate_tiles);
+}
+// QV_TRACE for the filtered paths' lines: read per call, as launch_rowset_topk reads it (a getenv beside a launch of several kernels), so that
+// a process can switch the trace on after its first search; the unfiltered lines keep their one read per process
+static bool trace_filtered() { return env_int("QV_TRACE", 0) != 0; }
+static bool bound_scan_takes(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
+    return candidate_tiles == kBoundNoFilter ? bound_scan_applies(v, nq, k) : bound_scan_applies_filtered(v, nq, k, candidate_tiles);
+}
 size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles) {
     return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)n_tiles * 64 * sizeof(uint32_t);
 }
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s) {
-    if (!bound_scan_applies(v, 1, k) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked) {
+    // (masked: the caller has asked bound_scan_applies_filtered; here only the conditions the kernels need)
+    if (!(masked ? bound_scan_rule(v.metric, v.dim, v.n_rows, 1, k, 1, v.plane != nullptr) : bound_scan_applies(v, 1, k)) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
     const uint32_t grid = p.grid;
     char* w = static_cast<char*>(d_ws);
     uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256;
@@ -1591,9 +1699,10 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
     hipError_t e = hipSuccess;
 #define QV_BOUND(MMM)                                                                                                        \
     {                                                                                                                         \
-        e = set_lds(k_bound_scan<MMM>, lds1); if (e != hipSuccess) return e;                                                  \
+        e = masked ? set_lds((k_bound_scan<MMM, true>), lds1) : set_lds(k_bound_scan<MMM>, lds1); if (e != hipSuccess) return e; \
         e = set_lds(k_bound_rescore<MMM>, lds2); if (e != hipSuccess) return e;                                               \
-        hipLaunchKernelGGL((k_bound_scan<MMM>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, k, ctrl, lo_all, partial, seed_rows, seed_dist); \
+        if (masked) hipLaunchKernelGGL((k_bound_scan<MMM, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, k, ctrl, lo_all, partial, seed_rows, seed_dist); \
+        else hipLaunchKernelGGL((k_bound_scan<MMM>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, k, ctrl, lo_all, partial, seed_rows, seed_dist); \
         hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, ctrl, cand);                      \
         hipLaunchKernelGGL((k_bound_rescore<MMM>), dim3(1), dim3(kScanBlock), lds2, s, v, d_query, k, ctrl, cand, d_stats, d_rows_out, d_dist_out); \
     }
@@ -1617,8 +1726,13 @@ size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k,
            std::max((size_t)nq * kBoundCandCap * sizeof(uint32_t) + (size_t)nq * n_tiles * 64 * sizeof(uint32_t), redo_workspace_bytes(p, nq, k));
 }
 hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                                uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
-    if (nq < 2 || !bound_scan_applies(v, nq, k) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+                                uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets) {
+    // h_sets (optional, a HOST array of nq): query j restricted to alive & h_sets[j] — k_bound_scan_mq<., ., true> and the set-carrying redo; the
+    // caller has asked bound_scan_applies_filtered, here only the conditions the kernels need.  Null: the unfiltered pass.
+    if (nq < 2 || !(h_sets ? bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, 1, v.plane != nullptr) : bound_scan_applies(v, nq, k)) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    BoundSetTable tab;
+    for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
+    if (h_sets && trace_filtered()) fprintf(stderr, "qv: scan kernel = k_bound_scan_mq sets QB=%d (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
     const uint32_t grid = p.grid;
     char* w = static_cast<char*>(d_ws);
     uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += up256((size_t)nq * grid * k * sizeof(uint64_t));
@@ -1639,7 +1753,8 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
         const size_t lds1 = (size_t)kScanWaves * QQ * 64 * sizeof(uint64_t);                                                  \
         e = set_lds(k_bound_rescore_mq<MMM>, lds2); if (e != hipSuccess) return e;                                            \
         hipLaunchKernelGGL((k_bound_prep_mq<QQ>), dim3((v.dim * QQ + 255) / 256 + QQ), dim3(256), 0, s, d_queries, nq, v.dim, qblk, qnorm, d_stats); \
-        hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial); \
+        if (h_sets) hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, tab); \
+        else hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, NoSets{}); \
         hipLaunchKernelGGL(k_merge_lists, dim3(nq), dim3(mblock), 0, s, partial, grid, k, seed_rows, seed_dist);             \
         hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand); \
         hipLaunchKernelGGL((k_bound_rescore_mq<MMM>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out); \
@@ -1650,25 +1765,31 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
 #undef QV_BOUND_MQ
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_flat_redo_flagged(v, p, d_queries, nq, k, k, flags, redo_ws, d_rows_out, d_dist_out, s);
+    return launch_flat_redo_flagged(v, p, d_queries, nq, k, k, flags, redo_ws, d_rows_out, d_dist_out, s, h_sets);
+}
+int host_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles) {
+    return bound_scan_rule_filtered(metric, dim, rows, nq, k, mode, has_plane != 0, candidate_tiles) ? 1 : 0;
 }
 int host_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane) { return bound_scan_rule(metric, dim, rows, nq, k, mode, has_plane != 0) ? 1 : 0; }
 
 
 hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k,
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
-                            hipEvent_t ev0, hipEvent_t ev1, uint32_t* d_tickets, uint32_t* done_flag, uint32_t done_seq, bool* flag_used, uint32_t* d_bound_stats) {
+                            hipEvent_t ev0, hipEvent_t ev1, uint32_t* d_tickets, uint32_t* done_flag, uint32_t done_seq, bool* flag_used, uint32_t* d_bound_stats,
+                            uint32_t candidate_tiles) {
     if (k == 0 || k > (uint32_t)kMaxFusedK || nq == 0) return hipErrorInvalidValue;
     const size_t lds = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     uint64_t* partial = static_cast<uint64_t*>(d_ws);
     hipError_t e = hipSuccess;
     static const int mq_min = dev_env_int("QV_MQ_MIN", 2);                // nq >= this: queries share a corpus pass
     // 2 - 8 queries sharing one pass over the bfloat16 copy (forced on, it goes ahead of the short-corpus form; on its own it leaves that form its shapes)
-    if ((int)nq >= mq_min && nq >= 2 && d_tickets && d_bound_stats && bound_scan_applies(v, nq, k) && (bound_scan_mode(v.bound_scan) == 1 || !flat_split_mq_applies(v, nq, k))) {
+    const bool filtered = candidate_tiles != kBoundNoFilter;         // v.alive is a filter's candidate bitmap: one for all queries of the call
+    if ((int)nq >= mq_min && nq >= 2 && d_tickets && d_bound_stats && bound_scan_takes(v, nq, k, candidate_tiles) && (bound_scan_mode(v.bound_scan) == 1 || !flat_split_mq_applies(v, nq, k))) {
         static const int trace = env_int("QV_TRACE", 0);
-        if (trace) fprintf(stderr, "qv: scan kernel = k_bound_scan_mq QB=%d (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
+        if (trace && !filtered) fprintf(stderr, "qv: scan kernel = k_bound_scan_mq QB=%d (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
         if (ev0) (void)hipEventRecord(ev0, s);
-        e = launch_bound_scan_mq(v, p, d_queries, nq, k, d_ws, d_tickets + kBoundCtrlWord, d_bound_stats, d_rows_out, d_dist_out, s);
+        const RowSetRef every[kBoundMqMax] = {};                       // (the bitmap is v.alive itself: every query's set is "every row" of it)
+        e = launch_bound_scan_mq(v, p, d_queries, nq, k, d_ws, d_tickets + kBoundCtrlWord, d_bound_stats, d_rows_out, d_dist_out, s, filtered ? every : nullptr);
         if (ev1) (void)hipEventRecord(ev1, s);
         return e;
     }
@@ -1774,13 +1895,14 @@ hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* 
         // one query, the caller's tickets at hand: scan + merge in ONE launch (the last workgroup merges).  QV_SCAN_FUSE=0 (read once)
         // keeps the two launches, for measurements.
         static const int fuse = dev_env_int("QV_SCAN_FUSE", 1);
-        if (d_tickets && d_bound_stats && p.grid > 1 && bound_scan_applies(v, nq, k)) {
+        if (d_tickets && d_bound_stats && p.grid > 1 && bound_scan_takes(v, nq, k, candidate_tiles)) {
             // the bound scan on the bfloat16 copy, its exact re-score, and the exact scan behind them that runs only when they hand the query back
             static const int trace = env_int("QV_TRACE", 0);
-            if (trace) fprintf(stderr, "qv: scan kernel = k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
+            if (filtered && trace_filtered()) fprintf(stderr, "qv: scan kernel = k_bound_scan masked (tiles=%u, candidate tiles<=%u, k=%u)\n", v.n_tiles, candidate_tiles, k);
+            if (!filtered && trace) fprintf(stderr, "qv: scan kernel = k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
             const uint32_t* gate = nullptr;
             if (ev0) (void)hipEventRecord(ev0, s);
-            e = launch_bound_scan(v, p, d_queries, k, static_cast<char*>(d_ws) + scan_workspace_bytes(p, 1, k), d_tickets + kBoundCtrlWord, d_bound_stats, d_rows_out, d_dist_out, &gate, s);
+            e = launch_bound_scan(v, p, d_queries, k, static_cast<char*>(d_ws) + scan_workspace_bytes(p, 1, k), d_tickets + kBoundCtrlWord, d_bound_stats, d_rows_out, d_dist_out, &gate, s, filtered);
             if (e != hipSuccess) return e;
             QV_DISPATCH_METRIC(v.metric, {
                 if constexpr (MM == QV_COSINE || MM == QV_DOT) {
@@ -1864,8 +1986,10 @@ size_t redo_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k) {
     return ((size_t)kRedoSlots * p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + ((size_t)nq * 4 + 255) / 256 * 256 + ((size_t)(nq + 1) * 4 + 255) / 256 * 256;
 }
 hipError_t launch_flat_redo_flagged(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, uint32_t k_stride, const uint32_t* d_flags,
-                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
-    if (k == 0 || k > (uint32_t)kMaxFusedK || nq == 0) return hipErrorInvalidValue;
+                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets) {
+    if (k == 0 || k > (uint32_t)kMaxFusedK || nq == 0 || (h_sets && nq > kBoundSets)) return hipErrorInvalidValue;
+    BoundSetTable tab;
+    for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
     char* w = static_cast<char*>(d_ws);
     uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += ((size_t)kRedoSlots * p.grid * k * sizeof(uint64_t) + 255) / 256 * 256;
     uint32_t* list = reinterpret_cast<uint32_t*>(w); w += ((size_t)nq * 4 + 255) / 256 * 256;
@@ -1876,10 +2000,19 @@ hipError_t launch_flat_redo_flagged(const IndexView& v, const ScanPlan& p, const
     for (uint32_t first = 0; first < nq; first += kRedoSlots) {
         QV_DISPATCH_METRIC(v.metric, {
             // (the flags come from the batched filter path: its four metrics)
+            if constexpr (MM == QV_COSINE || MM == QV_DOT) {         // (sets come with a bound pass: its two metrics)
+                if (h_sets) {
+                    e = set_lds((k_flat_scan_redo<MM, kUnroll, true>), lds);
+                    if (e != hipSuccess) return e;
+                    hipLaunchKernelGGL((k_flat_scan_redo<MM, kUnroll, true>), dim3(p.grid), dim3(p.block), lds, s, v, d_queries, k, k_stride, list, count, first, partial, count + 1, d_rows_out, d_dist_out, tab);
+                    continue;
+                }
+            }
             if constexpr (MM == QV_COSINE || MM == QV_L2 || MM == QV_L2SQ || MM == QV_DOT) {
+                if (h_sets) return hipErrorInvalidValue;
                 e = set_lds((k_flat_scan_redo<MM, kUnroll>), lds);
                 if (e != hipSuccess) return e;
-                hipLaunchKernelGGL((k_flat_scan_redo<MM, kUnroll>), dim3(p.grid), dim3(p.block), lds, s, v, d_queries, k, k_stride, list, count, first, partial, count + 1, d_rows_out, d_dist_out);
+                hipLaunchKernelGGL((k_flat_scan_redo<MM, kUnroll>), dim3(p.grid), dim3(p.block), lds, s, v, d_queries, k, k_stride, list, count, first, partial, count + 1, d_rows_out, d_dist_out, NoSets{});
             } else return hipErrorInvalidValue;
         });
     }

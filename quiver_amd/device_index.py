@@ -14,6 +14,15 @@ def _f32c(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def scan_bound_applies_filtered(metric, dim: int, rows: int, nq: int, k: int, mode="auto", has_plane: bool = True, candidate_tiles: int = 0) -> bool:
+    """whether a FILTERED search (search_masked, search_rowsets, search_rowsets_device) of that shape takes the bound scan on the bfloat16
+    copy under `mode`; candidate_tiles: the 64-row tiles that hold a candidate of any query of the pass (qv_scan_bound_applies_filtered)"""
+    rc = lib().qv_scan_bound_applies_filtered(metric_id(metric), dim, rows, nq, k, DeviceIndex.BOUND_SCAN.get(mode, mode), 1 if has_plane else 0, candidate_tiles)
+    if rc < 0:
+        check(rc)
+    return bool(rc)
+
+
 class DeviceIndex:
     default_filter = "auto"        # the filter kernel new indexes choose (set_filter); tests and bench.py compare the kernels through it
 
