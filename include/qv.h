@@ -104,7 +104,12 @@ typedef enum qv_status {
                                     bytes per row at 768 dimensions) because the scan of a large corpus for 1 to 8 queries rejects rows
                                     on it and reads the float32 rows of the few survivors only (qv_index_set_bound_scan).  This
                                     flag leaves the copy out: memory and every search are as without that scan.  The copy is an
-                                    accelerator, never a requirement: an index whose copy cannot be allocated carries on without it */
+                                    accelerator, never a requirement: an index whose copy cannot be allocated carries on without it.
+                                    Wherever they keep that copy by default, indexes whose dimension is a multiple of 16 up to 4096
+                                    also keep an 8-bit plane of the rows with a scale and a residual per row (+dim + 8 bytes per
+                                    row: 4616 -> 5392 at 768 dimensions), on which a single unfiltered query rejects rows first
+                                    (qv_index_set_bound_plane).  This flag leaves out both; an 8-bit plane that cannot be
+                                    allocated is given up alone and searches start on the bfloat16 copy */
 
 /* ---- lifecycle ------------------------------------------------------------------ */
 
@@ -293,6 +298,37 @@ int qv_index_set_bound_scan(qv_index* idx, int mode);
  * out[1] = QUERIES handed back to the exact scan so far, out[2] = QUERIES that took the path so far (a shared pass of nq adds nq),
  * out[3] = 1 when the index holds the bfloat16 copy.  Waits for the device. */
 int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]);
+/* Which plane serves a single unfiltered query's bound scan FIRST.  With the 8-bit plane (see QV_FLAG_NO_SCAN_PLANE) stage 1 reads
+ * a quarter of the float32 bytes: integer dot products of the quantised query with the row's int8 image, a certified interval from
+ * the row's stored scale and residual, the same threshold, collection and exact re-score.  A search that stage cannot decide (more
+ * candidates than its list holds, no finite threshold, a query it cannot quantise) goes on to the bfloat16 stage, and from there, if
+ * need be, to the exact scan — all decided on the device; results are bit-identical to the exact scan's in every case.
+ * QV_BOUND_PLANE_AUTO: the 8-bit stage from its measured row count and width on (never below the bound scan's own floor);
+ * QV_BOUND_PLANE_8BIT: whenever the bound scan takes the search and the plane is held; QV_BOUND_PLANE_BF16: never.  Independent of
+ * qv_index_set_bound_scan, which decides WHETHER a search takes the bound scan; this decides which plane it starts on.  The
+ * environment variable QV_BOUND_PLANE (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that never call this.
+ * Masked searches, row-set searches and shared passes of 2 - 8 queries stay on the bfloat16 copy. */
+#define QV_BOUND_PLANE_AUTO 0
+#define QV_BOUND_PLANE_8BIT 1
+#define QV_BOUND_PLANE_BF16 2
+int qv_index_set_bound_plane(qv_index* idx, int mode);
+/* out[0] = survivors the 8-bit stage passed on in the last such search, out[1] = searches it handed on to the bfloat16 stage so far,
+ * out[2] = searches that took the 8-bit stage so far, out[3] = 1 when the index holds the 8-bit plane.  Waits for the device.
+ * qv_index_bound_scan_stats keeps its meaning: a search the 8-bit stage took counts as a bound-scan search there, and its hand-backs
+ * are the searches that reached the exact scan. */
+int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]);
+/* Whether a search would take the 8-bit stage first: qv_scan_bound_applies' conditions under `mode`, one query, the plane held
+ * (has_plane8), and `plane_mode` (QV_BOUND_PLANE_*) — the dispatch's own rule, without an index or a device.  1 / 0, < 0 on an error. */
+int qv_scan_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8);
+/* The interval the 8-bit stage derives for one row, on the host (the kernel's own function): isum = sum qq_i r8_i, the integer dot
+ * product of the quantised query (qq = rint(q / sq), sq = max|q_i| / 16256) with the row's bytes, qn = |query|, qres = |q - sq qq|
+ * rounded up, rn = |row|, rscale8 / rres8 = the row's scale and residual (qv_scan_quantize_row8).  Returns 1 when the bound says
+ * nothing about the row or the query (always a survivor), 0 otherwise with [*d_lo, *d_hi] containing the float32 distance, < 0 on an error. */
+int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, double qn, double qres, double rn, float rscale8, float rres8, float* d_lo, float* d_hi);
+/* One row as the index keeps it in the 8-bit plane: out_bytes[dim] = clamp(rint(r_i / scale), -127, 127), *out_scale = max|r_i| / 127
+ * rounded up, *out_res = |r - scale r8| computed in float64 from those bytes and rounded up — NaN for a row the bound says nothing
+ * about (a non-finite element, no non-zero element, a norm that is huge or vanishing). */
+int qv_scan_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res);
 /* Whether a search of nq queries for k results over rows x dim of `metric` would take the path under `mode` (QV_BOUND_SCAN_*;
  * has_plane: the index holds the copy) — the dispatch's own rule, on the host, without an index or a device.  1 / 0, < 0 on an
  * error.  (A k above the live rows is the caller's to know; a mask or a row set: qv_scan_bound_applies_filtered.) */
@@ -536,6 +572,8 @@ int qv_sharded_sync(qv_sharded* s);                            /* wait for every
 int qv_sharded_set_filter(qv_sharded* s, int filter);          /* qv_index_set_filter on every shard */
 int qv_sharded_set_bound_scan(qv_sharded* s, int mode);       /* qv_index_set_bound_scan on every shard */
 int qv_sharded_bound_scan_stats(qv_sharded* s, uint64_t out[4]);   /* qv_index_bound_scan_stats: [0] of the first shard, [1] [2] summed, [3] 1 when every shard holds the copy */
+int qv_sharded_set_bound_plane(qv_sharded* s, int mode);      /* qv_index_set_bound_plane on every shard */
+int qv_sharded_bound_scan8_stats(qv_sharded* s, uint64_t out[4]);  /* qv_index_bound_scan8_stats, put together as qv_sharded_bound_scan_stats does */
 int qv_sharded_profile(qv_sharded* s, int enable);
 int qv_sharded_profile_read(qv_sharded* s, double* scan_ms_sum, double* exchange_ms_sum, double* merge_ms_sum, uint64_t* searches);
 int qv_sharded_profile_read_shard(qv_sharded* s, int shard, double* scan_kernel_ms_sum, uint64_t* launches);

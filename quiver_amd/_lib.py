@@ -86,6 +86,13 @@ PROTOTYPES = {
     "qv_index_bound_scan_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_sharded_bound_scan_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_scan_bound_interval": (C.c_int, [C.c_int, C.c_uint32, C.c_float, C.c_double, C.c_double, C.c_float, _f32p, _f32p]),
+    "qv_index_set_bound_plane": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_sharded_set_bound_plane": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_bound_scan8_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_sharded_bound_scan8_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_scan_bound8_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
+    "qv_scan_bound_interval8": (C.c_int, [C.c_int, C.c_uint32, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, _f32p, _f32p]),
+    "qv_scan_quantize_row8": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, _f32p, _f32p]),
     "qv_index_debug_read": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "qv_scan_bound_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
     "qv_scan_bound_applies_filtered": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32]),

@@ -126,6 +126,22 @@ int ensure_rows(qv_index* idx, uint64_t rows, bool exact) {
             (void)hipFree(idx->d_bf16); idx->d_bf16 = nullptr; idx->plane_lost = true;
         } else e = eb;
     }
+    if (e == hipSuccess && idx->wants_plane8()) {
+        // the 8-bit plane and its row state: an accelerator in front of that copy — when it does not fit, the index frees it and searches
+        // start on the bfloat16 copy (QV_TEST_PLANE8_OOM: the same for tests)
+        hipError_t e8 = getenv("QV_TEST_PLANE8_OOM") ? hipErrorOutOfMemory : regrow(&idx->d_plane8, used_tiles * idx->plane8_tile_bytes(), new_tiles * idx->plane8_tile_bytes());
+        if (e8 == hipSuccess) e8 = regrow(&idx->d_rscale8, used_tiles * 64 * sizeof(float), new_tiles * 64 * sizeof(float));
+        if (e8 == hipSuccess) e8 = regrow(&idx->d_rres8, used_tiles * 64 * sizeof(float), new_tiles * 64 * sizeof(float));
+        if (e8 == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            (void)hipFree(idx->d_plane8); (void)hipFree(idx->d_rscale8); (void)hipFree(idx->d_rres8);
+            idx->d_plane8 = nullptr; idx->d_rscale8 = nullptr; idx->d_rres8 = nullptr; idx->plane8_lost = true;
+        } else e = e8;
+    }
+    if (idx->plane_lost && idx->d_plane8) {                            // (the 8-bit stage hands back to the bfloat16 stage: never one without the other)
+        (void)hipFree(idx->d_plane8); (void)hipFree(idx->d_rscale8); (void)hipFree(idx->d_rres8);
+        idx->d_plane8 = nullptr; idx->d_rscale8 = nullptr; idx->d_rres8 = nullptr; idx->plane8_lost = true;
+    }
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? QV_ERR_OOM : QV_ERR_DEVICE, "device allocation for %llu rows failed: %s", (unsigned long long)(new_tiles * 64), hipGetErrorString(e));
     idx->cap_tiles = new_tiles;
@@ -209,6 +225,7 @@ void qv_index_destroy(qv_index* idx) {
     for (SearchCtx* c : idx->all_ctx) { c->release(); delete c; }
     for (auto& kv : idx->stream_ws) { kv.second->ws.release(); kv.second->tickets.release(); delete kv.second; }
     (void)hipFree(idx->d_tiles); (void)hipFree(idx->d_rnorm); (void)hipFree(idx->d_alive); (void)hipFree(idx->d_rres); (void)hipFree(idx->d_rowmaj); (void)hipFree(idx->d_bf16); (void)hipFree(idx->d_bound_stats);
+    (void)hipFree(idx->d_plane8); (void)hipFree(idx->d_rscale8); (void)hipFree(idx->d_rres8);
     idx->mut_stage.release();
     delete idx;
 }
@@ -1212,6 +1229,40 @@ int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]) {
     HIPCHK(hipMemcpy(h, idx->d_bound_stats, sizeof(h), hipMemcpyDeviceToHost));
     out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = idx->d_bf16 != nullptr ? 1 : 0;
     return QV_OK;
+}
+
+int qv_index_set_bound_plane(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", mode);
+    idx->bound_plane = mode;
+    return QV_OK;
+}
+
+int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t h[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kBound8StatsWord, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = idx->d_plane8 != nullptr ? 1 : 0;
+    return QV_OK;
+}
+
+int qv_scan_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8) {
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
+    return qv::host_bound8_applies(metric, dim, rows, nq, k, mode, plane_mode, has_plane8);
+}
+
+int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, double qn, double qres, double rn, float rscale8, float rres8, float* d_lo, float* d_hi) {
+    if (metric != QV_COSINE && metric != QV_DOT) return fail(QV_ERR_UNSUPPORTED, "the bound scan's metrics are cosine and dot; got %d", metric);
+    if (!d_lo || !d_hi || dim == 0) return fail(QV_ERR_INVALID_ARG, "d_lo/d_hi is null or dim is 0");
+    return qv::host_bound_interval8(metric, dim, (long long)isum, sq, qn, qres, rn, rscale8, rres8, d_lo, d_hi);
+}
+
+int qv_scan_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res) {
+    if (!row || !out_bytes || !out_scale || !out_res || dim == 0) return fail(QV_ERR_INVALID_ARG, "row/out is null or dim is 0");
+    return qv::host_quantize_row8(dim, row, out_bytes, out_scale, out_res);
 }
 
 int qv_scan_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {

@@ -96,6 +96,11 @@ struct qv_index {
     uint16_t* d_bf16 = nullptr;                // the bfloat16 copy (QV_FLAG_BF16_ROWS, and by default on cosine / dot indexes): refreshed by every call that writes rows
     bool plane_lost = false;                   // the default copy could not be allocated: the index carries on without it
     int bound_scan = 0;                        // qv_index_set_bound_scan
+    int8_t* d_plane8 = nullptr;                // the int8 copy and its row state (scale, residual): kept with the default bfloat16 copy, refreshed with it
+    float* d_rscale8 = nullptr;
+    float* d_rres8 = nullptr;
+    bool plane8_lost = false;                  // it could not be allocated: the index carries on with the bfloat16 copy
+    int bound_plane = 0;                       // qv_index_set_bound_plane
     uint32_t* d_bound_stats = nullptr;         // [0] survivors of the last bound scan, [1] hand-backs, [2] bound scans (written by the kernels)
     std::vector<uint64_t> alive_host;          // mirror of d_alive, for size bookkeeping and validation
     Buf mut_stage;                             // grow-only staging buffer of the mutating calls (add / remove / update run under the
@@ -122,6 +127,7 @@ struct qv_index {
         qv::IndexView v;
         v.tiles = d_tiles; v.rnorm = d_rnorm; v.alive = d_alive; v.rres = d_rres; v.rowmaj = d_rowmaj;
         v.bf16 = (flags & QV_FLAG_BF16_ROWS) ? d_bf16 : nullptr; v.plane = d_bf16; v.bound_scan = bound_scan;
+        v.plane8 = d_plane8; v.rscale8 = d_rscale8; v.rres8 = d_rres8; v.bound_plane = bound_plane;
         v.dim = dim; v.dim4 = dim4; v.n_rows = n_rows; v.n_tiles = (n_rows + 63) / 64; v.metric = metric; v.filter = filter;
         return v;
     }
@@ -129,6 +135,11 @@ struct qv_index {
     bool wants_plane() const {
         return (flags & QV_FLAG_BF16_ROWS) || (!(flags & QV_FLAG_NO_SCAN_PLANE) && !plane_lost && (metric == QV_COSINE || metric == QV_DOT));
     }
+    // ... and the 8-bit plane wherever they keep that copy BY DEFAULT and the 8-bit stage can walk the rows (whole 16-dimension steps, int32 sums)
+    bool wants_plane8() const {
+        return !(flags & QV_FLAG_NO_SCAN_PLANE) && !plane_lost && !plane8_lost && (metric == QV_COSINE || metric == QV_DOT) && (dim & 15u) == 0 && dim <= 4096;
+    }
+    size_t plane8_tile_bytes() const { return (size_t)dim * 64; }
     size_t tile_bytes() const { return (size_t)dim4 * 64 * 16; }
     size_t bf16_tile_bytes() const { return (size_t)(((dim4 + 1) / 2 + 1) / 2) * 2 * 64 * 16; }   // whole 16-dim steps (k_bf16_plane's layout)
 };

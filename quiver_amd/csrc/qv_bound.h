@@ -39,4 +39,69 @@ __host__ __device__ __forceinline__ bool bound_scan_interval(float s, double qn,
     return true;
 }
 
+// ---- the 8-bit plane (k_bound_scan8): the same interval from integers ----
+// The index keeps r8 = an int8 image of every row with one float32 scale per row (bound8_scale / bound8_quant below) and
+// rres8 = |r - scale r8|, computed in float64 FROM THE BYTES STORED and rounded up (k_row_state8), so nothing below depends on how
+// the quantiser rounds.  The query is quantised once per workgroup: qq_i = rint(q_i / sq), sq = max|q_i| / 16256, split into two
+// int8 terms qq = 128 hi + lo (|hi| <= 127, |lo| <= 64).  Stage 1 computes I = 128 sum hi_i r8_i + sum lo_i r8_i = sum qq_i r8_i with
+// integer dot products (each sum is exact in int32 up to 4096 dimensions: 4096 * 127 * 127 < 2^31; their combination is exact in
+// float64) and S~ = sq * scale * I in float64.  With qh = sq qq, rh = scale r8 (so qh.rh = sq scale I as real numbers),
+// qres = |q - qh| (float64, rounded up, computed by the caller beside the reference's |q| chain) and S the reference's float64 chain:
+//   |S~ - qh.rh|  <= 2 * 2^-53 |qh.rh| (1 + 2^-53) <= 2.3e-16 (|q| + qres)(|r| + rres8)     (the two float64 multiplies)
+//   |qh.rh - q.rh| <= qres |rh| <= qres (|r| + rres8)                                        (Cauchy-Schwarz)
+//   |q.rh - q.r|   <= |q| rres8                                                              (Cauchy-Schwarz)
+//   |q.r - S|      <= dim 2^-53 |q||r| <= 4.6e-13 |q||r|                                     (the float64 chain's own error, dim <= 4096)
+// so |S~ - S| <= |q| rres8 + qres (|r| + rres8) + 1e-12 (|q| + qres)(|r| + rres8): the last term is the slack for the two multiplies,
+// the chain, and the roundings of qres itself (each of its terms is off by at most 2^-52 |q_i|); the factor 1 + 1e-9 covers this
+// line's own roundings and S~ +- m, as in bound_scan_interval.  There is no float32 chain: no gamma_K term and no underflow term
+// (integers do not underflow; a row or a query whose norm is vanishing or huge is declined as before).  The distance interval is
+// [finalize(S~ + m), finalize(S~ - m)] with the reference's own |q| and |r|, exactly as above.
+constexpr int kBound8QueryMax = 16256;           // 127 * 128: the quantised query's largest magnitude
+
+// scale = max|r_i| / 127 rounded UP (one float32 step), so that |r_i / scale| <= 127 before rounding; 0 for a row without a scale
+__host__ __device__ static inline float bound8_scale(float maxabs) {
+    if (!(maxabs > 0.0f) || maxabs == __builtin_inff()) return 0.0f;
+    const float s = maxabs / 127.0f;
+    union { float f; uint32_t u; } c; c.f = s; c.u += 1u;
+    return c.f == __builtin_inff() ? s : c.f;
+}
+__host__ __device__ static inline int bound8_quant(float x, float scale) {
+    float v = __builtin_rintf(x / scale);
+    v = __builtin_fminf(__builtin_fmaxf(v, -127.0f), 127.0f);          // (a NaN quotient comes out as -127: such a row is declined anyway)
+    return (int)v;
+}
+// the residual's float32: sqrt of the float64 sum, a hair up, then one float32 step up — k_row_residual's rounding
+__host__ __device__ static inline float bound8_res_up(double s2) {
+    const float r = (float)(__builtin_sqrt(s2) * (1.0 + 1e-12));
+    if (!(r == r) || r == __builtin_inff()) return __builtin_nanf("");
+    union { float f; uint32_t u; } c; c.f = r;
+    if (r == 0.f) c.u = s2 == 0.0 ? 0u : 1u; else c.u += 1u;
+    return c.f;
+}
+// One row's state from its statistics: bad = a non-finite element, maxabs, n2 = sum r_i^2 (float64), s2 = sum (r_i - scale r8_i)^2.
+// NaN: a row the bound says nothing about.
+__host__ __device__ static inline float bound8_row_res(bool bad, float maxabs, double n2, double s2, uint32_t dim) {
+    if (bad || !(maxabs > 0.0f) || maxabs == __builtin_inff() || !bound_scan_norm_ok(__builtin_sqrt(n2), dim)) return __builtin_nanf("");
+    return bound8_res_up(s2);
+}
+
+// isum = I, sq = the query's scale, qn = |q| (the reference's chain), qres = |q - sq qq| rounded up, rn = |r| (stored),
+// rscale / rres8 = the row's scale and residual.  false: a row (or a query) the bound says nothing about — always a candidate
+// (d_lo = -inf), never lowers a threshold (d_hi = NaN).
+template <int M>
+__host__ __device__ __forceinline__ bool bound_scan_interval8(long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, uint32_t dim,
+                                                              float& d_lo, float& d_hi) {
+    static_assert(M == QV_COSINE || M == QV_DOT, "the bound scan's metrics");
+    const double rr = (double)rres8, sc = (double)rscale;
+    const bool sure = bound_scan_norm_ok(rn, dim) && bound_scan_norm_ok(qn, dim) && rr >= 0.0 && rr < 1.0e18 && qres >= 0.0 && qres < 1.0e18 &&
+                      sq > 0.0 && sq < 1.0e36 && sc > 0.0 && sc < 1.0e36;
+    if (!sure) { d_lo = -__builtin_inff(); d_hi = __builtin_nanf(""); return false; }
+    const double s = sq * sc * (double)isum;
+    const double m = (qn * rr + qres * (rn + rr) + 1e-12 * (qn + qres) * (rn + rr)) * (1.0 + 1e-9);
+    QConst qc; qc.qn = qn; qc.qn32 = 0.0f;
+    d_lo = finalize<M>(s + m, qc, rn);
+    d_hi = finalize<M>(s - m, qc, rn);
+    return true;
+}
+
 }  // namespace qv

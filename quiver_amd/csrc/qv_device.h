@@ -45,6 +45,11 @@ struct IndexView {
                           // single-query bound scan (qv_bound.hip); `bf16` above is set only under QV_FLAG_BF16_ROWS, so the batched path's
                           // choice of kernels is what the flag alone decides.  The calls that write rows refresh `plane`.
     int       bound_scan; // qv_index_set_bound_scan: 0 from the measured row count on, 1 whenever it applies, 2 never
+    int8_t*   plane8;     // may be null: the int8 copy of the rows, [tile][dim/16][64 rows][16 values], one scale per row (k_row_state8);
+                          // kept wherever `plane` is kept by default and dim is a multiple of 16 up to 4096.  Refreshed with `plane`.
+    float*    rscale8;    // per row: max|r_i| / 127 rounded up (0: no scale)
+    float*    rres8;      // per row: |r - rscale8 r8| rounded up; NaN = a row the 8-bit bound says nothing about
+    int       bound_plane; // qv_index_set_bound_plane: 0 the 8-bit stage from its measured row count on, 1 whenever it applies, 2 never
 };
 
 struct GraphView {
@@ -152,7 +157,8 @@ bool bound_scan_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, ui
 size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles);
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                              uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s,
-                             bool masked = false);   // v.alive is a filter's candidate bitmap: the form that does not request tiles without a candidate (k_bound_scan<., true>)
+                             bool masked = false,   // v.alive is a filter's candidate bitmap: the form that does not request tiles without a candidate (k_bound_scan<., true>)
+                             bool plane8_first = false);   // the 8-bit stage (k_bound_scan8) in front, the bfloat16 stage gated behind it: d_ctrl = 2 BoundCtrl
 // ... and for the 2 - 8 queries of a shared pass (k_bound_scan_mq): d_ws bound_scan_mq_workspace_bytes, d_ctrl 8 BoundCtrl; the exact scan of
 // the queries it hands back is enqueued behind it (launch_flat_redo_flagged)
 size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim);
@@ -166,6 +172,14 @@ bool bound_scan_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_
 int host_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles);
 // the interval of one row on the HOST (qv_scan_bound_interval): qv_bound.h's function compiled for the CPU
 float host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi, int* unsure);
+// The 8-bit stage in front of it (k_bound_scan8): the same chain over v.plane8; a search it cannot decide goes to the bfloat16 stage, which
+// runs gated behind it.  plane_mode: QV_BOUND_PLANE_* (0 automatic: QV_BOUND_PLANE decides, 1 the 8-bit stage whenever it applies, 2 never).
+bool bound_scan8_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode, bool has_plane8);
+bool bound_scan8_applies(const IndexView& v, uint32_t nq, uint32_t k);
+int host_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8);
+int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, float* d_lo, float* d_hi);
+int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res);
+constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches
 constexpr uint32_t kBoundCtrlWord = 16;   // the bound scan's control words start here in the stream's 64 ticket words
 bool flat_split_applies(const IndexView& v, uint32_t nq, uint32_t k);   // launch_flat_topk will take the tile-over-eight-waves form (given tickets)
 // The exact scan (k <= kMaxFusedK) for exactly the queries whose d_flags word is non-zero — the ones a filter handed back —, listed and

@@ -2,6 +2,7 @@
 // (shared helpers, the arithmetic contract and the build flags: qv_kernels.h)
 #include <algorithm>
 #include "qv_kernels.h"
+#include "qv_bound.h"
 
 namespace qv {
 
@@ -284,9 +285,59 @@ k_row_residual(IndexView v, uint32_t t0) {
     if (r == r && r != __builtin_inff()) up = r == 0.f ? (s2 == 0.0 ? 0.f : __uint_as_float(1u)) : __uint_as_float(__float_as_uint(r) + 1u);
     v.rres[(size_t)t * 64 + lane] = up;
 }
+// The 8-bit plane of tiles [t0, t0 + n_tiles) and its row state (qv_bound.h: bound8_scale / bound8_quant / bound8_row_res): plane8 is
+// [tile][16-dim step][64 rows][16 values] — lane == row, one dwordx4 per lane and step, a wave's request one contiguous KiB, as for the
+// float32 tiles.  One wave per tile, two walks of the tile: the row's largest magnitude (and whether it has one), then the bytes and
+// the residual |r - scale r8| FROM THE BYTES WRITTEN, in float64, rounded up.  dim is a multiple of 16 (the index keeps no plane otherwise).
+__global__ void __launch_bounds__(64)
+k_row_state8(IndexView v, uint32_t t0) {
+    const uint32_t t = t0 + blockIdx.x, lane = threadIdx.x, steps = v.dim >> 4;
+    const f4* src = reinterpret_cast<const f4*>(v.tiles) + (size_t)t * v.dim4 * 64 + lane;
+    float maxabs = 0.f; bool bad = false; double n2 = 0.0;
+    for (uint32_t c = 0; c < v.dim4; c++) {
+        const f4 x = src[(size_t)c * 64];
+        const float e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            bad |= !((e[j] - e[j]) == 0.0f);
+            maxabs = __builtin_fmaxf(maxabs, __builtin_fabsf(e[j]));
+            n2 = __builtin_fma((double)e[j], (double)e[j], n2);
+        }
+    }
+    const float scale = bad ? 0.0f : bound8_scale(maxabs);
+    const float div = scale > 0.0f ? scale : 1.0f;
+    double s2 = 0.0;
+    uint4* dst = reinterpret_cast<uint4*>(v.plane8) + (size_t)t * steps * 64 + lane;
+    for (uint32_t s = 0; s < steps; s++) {
+        uint32_t w[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const f4 x = src[(size_t)(4 * s + c) * 64];
+            const float e[4] = {x.x, x.y, x.z, x.w};
+            uint32_t word = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int b = scale > 0.0f ? bound8_quant(e[j], div) : 0;
+                const double d = (double)e[j] - (double)scale * (double)b;
+                s2 = __builtin_fma(d, d, s2);
+                word |= ((uint32_t)b & 0xFFu) << (8 * j);
+            }
+            w[c] = word;
+        }
+        uint4 o; o.x = w[0]; o.y = w[1]; o.z = w[2]; o.w = w[3];
+        dst[(size_t)s * 64] = o;
+    }
+    v.rscale8[(size_t)t * 64 + lane] = scale;
+    v.rres8[(size_t)t * 64 + lane] = bound8_row_res(bad, maxabs, n2, s2, v.dim);
+}
 static hipError_t refresh_bf16(const IndexView& v, uint32_t t0, uint32_t t1, hipStream_t s) {
     if (v.rres && (v.metric == QV_COSINE || v.metric == QV_DOT || v.metric == QV_L2 || v.metric == QV_L2SQ)) {
         hipLaunchKernelGGL(k_row_residual, dim3(t1 - t0 + 1), dim3(64), 0, s, v, t0);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (v.plane8) {                                                    // (the 8-bit plane and its row state: never behind the tiles either)
+        hipLaunchKernelGGL(k_row_state8, dim3(t1 - t0 + 1), dim3(64), 0, s, v, t0);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -1109,6 +1109,35 @@ __device__ __forceinline__ float bound_tile(const u4* __restrict__ p, const floa
     return acc;
 }
 
+// The end of a bound scan's stage 1 (k_bound_scan, k_bound_scan8): the upper bounds' lists go waves -> wave 0 -> published; the last workgroup
+// to finish merges (k_flat_scan<., ., true>'s protocol) and leaves H, the exact k-th smallest upper bound, in the control words.
+__device__ __forceinline__ void bound_scan_tail(uint64_t list, uint64_t thr, uint64_t* wl /* LDS [kScanWaves][64] */, uint32_t wave, uint32_t lane, uint32_t k, BoundCtrl* __restrict__ ctrl,
+                                                uint64_t* __restrict__ partial, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
+    __shared__ uint32_t s_last;
+    const uint32_t kth = k - 1;
+    wl[wave * 64 + lane] = list;
+    __syncthreads();
+    if (wave == 0) {
+        for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list, thr, lane < k ? wl[w * 64 + lane] : kDeadKey, kth, lane);
+        uint64_t* mine = partial + (size_t)blockIdx.x * k;
+        if (lane < k) (void)atomicExch(reinterpret_cast<unsigned long long*>(&mine[lane]), (unsigned long long)list);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // every lane's exchange has returned: the list is at the memory side
+        uint32_t last = 0;
+        if (lane == 0) last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+        last = __builtin_amdgcn_readfirstlane(last);
+        if (last && lane == 0) ctrl->ticket = 0;                       // for the next launch on these words (stream order)
+        if (lane == 0) s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    merge_lists_last_workgroup(partial, gridDim.x, k, seed_rows, seed_dist);
+    if (wave == 0 && lane == kth) {                                    // (this lane wrote them) H: a finite k-th upper bound, or none
+        const uint32_t o = ord_f32(seed_dist[kth]);
+        ctrl->thr_inv = (seed_rows[kth] != 0xFFFFFFFFu && o < 0xFF800000u) ? ~o : 0u;
+        ctrl->cand_cnt = 0;
+    }
+}
+
 // SKIP (k_bound_scan<., true>: v.alive is a filter's candidate bitmap, alive & set — k_rowset_and's or the masked upload): a tile whose word is
 // zero is not requested, neither its copy nor rnorm nor rres.  Its 64 lower-bound words are WRITTEN as 0xFFFFFFFF all the same: k_bound_collect
 // reads every word and the workspace is reused, so an unwritten tile would hold an earlier search's bounds; 256 bytes stored against dim * 128
@@ -1116,11 +1145,12 @@ __device__ __forceinline__ float bound_tile(const u4* __restrict__ p, const floa
 template <int M, bool SKIP = false>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
-             uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
+             uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist,
+             const uint32_t* __restrict__ gate = nullptr /* behind the 8-bit stage (k_bound_rescore<., true> wrote the word): zero = it has answered, leave at once */) {
+    if (gate != nullptr && *gate == 0u) return;
     extern __shared__ __align__(16) unsigned char smem[];
     float* q_lds = reinterpret_cast<float*>(smem);                     // [dim], dim a multiple of 16
     uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (size_t)v.dim * sizeof(float));   // [kScanWaves][64]
-    __shared__ uint32_t s_last;
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (uint32_t i = threadIdx.x; i < v.dim; i += blockDim.x) q_lds[i] = query[i];
@@ -1175,28 +1205,7 @@ k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl
         for (; t < v.n_tiles; t += tw) finish_tile(t, bound_tile<false>(plane + (size_t)t * steps * 128, q_lds, steps, nullptr), false);
     }
 
-    // the upper bounds' lists: waves -> wave 0 -> published; the last workgroup to finish merges (k_flat_scan<., ., true>'s protocol)
-    wl[wave * 64 + lane] = list;
-    __syncthreads();
-    if (wave == 0) {
-        for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list, thr, lane < k ? wl[w * 64 + lane] : kDeadKey, kth, lane);
-        uint64_t* mine = partial + (size_t)blockIdx.x * k;
-        if (lane < k) (void)atomicExch(reinterpret_cast<unsigned long long*>(&mine[lane]), (unsigned long long)list);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // every lane's exchange has returned: the list is at the memory side
-        uint32_t last = 0;
-        if (lane == 0) last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-        last = __builtin_amdgcn_readfirstlane(last);
-        if (last && lane == 0) ctrl->ticket = 0;                       // for the next launch on these words (stream order)
-        if (lane == 0) s_last = last;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    merge_lists_last_workgroup(partial, gridDim.x, k, seed_rows, seed_dist);
-    if (wave == 0 && lane == kth) {                                    // (this lane wrote them) H: a finite k-th upper bound, or none
-        const uint32_t o = ord_f32(seed_dist[kth]);
-        ctrl->thr_inv = (seed_rows[kth] != 0xFFFFFFFFu && o < 0xFF800000u) ? ~o : 0u;
-        ctrl->cand_cnt = 0;
-    }
+    bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
 }
 
 // the rows with d_lo <= H, four per thread and step (lo: one query's ordered words; cnt: its counter; cand: its list)
@@ -1222,7 +1231,9 @@ __device__ __forceinline__ void bound_collect(const uint32_t* __restrict__ lo, u
     }
 }
 __global__ void __launch_bounds__(256)
-k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand) {
+k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand,
+                const uint32_t* __restrict__ gate = nullptr /* as k_bound_scan's */) {
+    if (gate != nullptr && *gate == 0u) return;
     const uint32_t inv = ctrl->thr_inv;
     if (inv == 0u) return;                                             // no H: k_bound_rescore hands the query back
     bound_collect(lo_all, n, ~inv, &ctrl->cand_cnt, cand);
@@ -1285,18 +1296,150 @@ __device__ __forceinline__ void bound_rescore_query(const IndexView& v, const fl
     }
 }
 
-template <int M>
+// P8: the re-score behind the 8-bit stage (ctrl = that stage's words, next = the bfloat16 stage's).  It answers, or sets its own flag — the
+// word the bfloat16 stage's three launches are gated on — and then that stage decides or hands on to the exact scan.  An 8-bit search counts
+// as a bound-scan search in stats[0 .. 2]; its own counters sit at kBound8StatsWord.
+// gate (the bfloat16 stage behind the 8-bit one): zero = the 8-bit stage has answered and has cleared this stage's flag for the exact scan
+// behind; non-zero = this stage runs, and zeroes the word, which it is the last to read.
+template <int M, bool P8 = false>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand,
-                uint32_t* __restrict__ stats, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out) {
+                uint32_t* __restrict__ stats, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, uint32_t* gate = nullptr, BoundCtrl* next = nullptr) {
+    if (gate != nullptr && *gate == 0u) return;
     const uint32_t cnt = ctrl->cand_cnt, thr_inv = ctrl->thr_inv;
     bound_rescore_query<M>(v, query, k, cnt, thr_inv != 0u, cand, rows_out, dist_out, [&](bool hand_back) {
-        stats[0] = cnt;
-        if (hand_back) (void)atomicAdd(&stats[1], 1u);
-        (void)atomicAdd(&stats[2], 1u);
-        ctrl->flag = hand_back ? 1u : 0u;                              // the exact scan behind this launch reads it
+        if constexpr (P8) {
+            stats[kBound8StatsWord] = cnt;
+            if (hand_back) (void)atomicAdd(&stats[kBound8StatsWord + 1], 1u);
+            (void)atomicAdd(&stats[kBound8StatsWord + 2], 1u);
+            if (!hand_back) { stats[0] = cnt; (void)atomicAdd(&stats[2], 1u); next->flag = 0u; }
+        } else {
+            stats[0] = cnt;
+            if (hand_back) (void)atomicAdd(&stats[1], 1u);
+            (void)atomicAdd(&stats[2], 1u);
+            if (gate != nullptr) *gate = 0u;                           // (every thread read it before the barriers in front of this call)
+        }
+        ctrl->flag = hand_back ? 1u : 0u;                              // the launch behind this one reads it
         ctrl->cand_cnt = 0; ctrl->thr_inv = 0;                         // zero, as the words are kept
     });
+}
+
+// ---------------------------------------------------------------- one query: reject rows on the 8-bit plane first --
+// k_bound_scan's walk and tail over IndexView::plane8 — a quarter of the float32 bytes: per 16-dimension step a lane reads its row's 16
+// int8 values (one dwordx4, the wave one contiguous KiB).  The query is quantised once per workgroup into LDS as two int8 terms
+// (qv_bound.h: qq = 128 hi + lo), a row's sum is eight integer dot products per step, exact, and the interval comes from
+// bound_scan_interval8.  Lower bounds, upper bounds, H, k_bound_collect and the re-score are the bfloat16 stage's own; what this stage
+// cannot decide (more than kBoundCandCap candidates, no finite H, a query it cannot quantise) goes to the bfloat16 stage, gated
+// behind it, not to the exact scan: corpora with many rows within the 8-bit margin of the k-th distance keep the bfloat16 stage's time.
+typedef int i32;
+template <int U>
+__device__ __forceinline__ void bound8_block(const u4* __restrict__ p, const u4* __restrict__ qh, const u4* __restrict__ ql, uint32_t s0, i32 (&acc)[4]) {
+    u4 x[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) x[u] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 64]);
+    __builtin_amdgcn_sched_barrier(0);                                 // all requests of the block ahead of the arithmetic (see row_accumulate)
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const u4 h = qh[s0 + u], l = ql[s0 + u];
+        acc[0] = __builtin_amdgcn_sdot4((i32)h.x, (i32)x[u].x, acc[0], false);
+        acc[1] = __builtin_amdgcn_sdot4((i32)h.y, (i32)x[u].y, acc[1], false);
+        acc[0] = __builtin_amdgcn_sdot4((i32)h.z, (i32)x[u].z, acc[0], false);
+        acc[1] = __builtin_amdgcn_sdot4((i32)h.w, (i32)x[u].w, acc[1], false);
+        acc[2] = __builtin_amdgcn_sdot4((i32)l.x, (i32)x[u].x, acc[2], false);
+        acc[3] = __builtin_amdgcn_sdot4((i32)l.y, (i32)x[u].y, acc[3], false);
+        acc[2] = __builtin_amdgcn_sdot4((i32)l.z, (i32)x[u].z, acc[2], false);
+        acc[3] = __builtin_amdgcn_sdot4((i32)l.w, (i32)x[u].w, acc[3], false);
+    }
+}
+// I of this lane's row of one tile (p = the tile in the plane + the lane)
+__device__ __forceinline__ long long bound8_tile(const u4* __restrict__ p, const u4* __restrict__ qh, const u4* __restrict__ ql, uint32_t steps) {
+    i32 acc[4] = {0, 0, 0, 0};
+    uint32_t s = 0;
+    for (; s + 16 <= steps; s += 16) bound8_block<16>(p, qh, ql, s, acc);
+    if (s + 8 <= steps) { bound8_block<8>(p, qh, ql, s, acc); s += 8; }
+    if (s + 4 <= steps) { bound8_block<4>(p, qh, ql, s, acc); s += 4; }
+    if (s + 2 <= steps) { bound8_block<2>(p, qh, ql, s, acc); s += 2; }
+    if (s < steps) bound8_block<1>(p, qh, ql, s, acc);
+    return ((long long)acc[0] + (long long)acc[1]) * 128ll + ((long long)acc[2] + (long long)acc[3]);   // (each partial sum exact in int32: dim <= kBoundMaxDim)
+}
+
+template <int M>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_scan8(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
+              uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    int8_t* qh8 = reinterpret_cast<int8_t*>(smem);                     // [dim] hi terms, [dim] lo terms, dim a multiple of 16
+    int8_t* ql8 = qh8 + v.dim;
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (size_t)v.dim * 2);   // [kScanWaves][64]
+    __shared__ float s_max[kScanWaves];
+    __shared__ uint32_t s_bad[kScanWaves];
+    __shared__ double s_res[kScanWaves];
+    __shared__ double s_qn;
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves;
+
+    // the query, quantised: sq = max|q_i| / 16256, qq = rint(q / sq) = 128 hi + lo; qres = |q - sq qq| rounded up
+    float mx = 0.f; bool bad = false;
+    for (uint32_t i = threadIdx.x; i < v.dim; i += blockDim.x) { const float x = query[i]; bad |= !((x - x) == 0.0f); mx = __builtin_fmaxf(mx, __builtin_fabsf(x)); }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) mx = __builtin_fmaxf(mx, __shfl_xor(mx, m));
+    const bool wbad = __ballot(bad) != 0ull;
+    if (lane == 0) { s_max[wave] = mx; s_bad[wave] = wbad ? 1u : 0u; }
+    __syncthreads();
+    uint32_t anybad = 0;
+    for (uint32_t w = 0; w < kScanWaves; w++) { mx = __builtin_fmaxf(mx, s_max[w]); anybad |= s_bad[w]; }
+    const bool q_ok = !anybad && mx > 0.0f;
+    const double sq = q_ok ? (double)mx / (double)kBound8QueryMax : 1.0;
+    double r2 = 0.0;
+    for (uint32_t i = threadIdx.x; i < v.dim; i += blockDim.x) {
+        const double x = q_ok ? (double)query[i] : 0.0;
+        const double qq = __builtin_rint(x / sq);                      // |qq| <= 16256
+        const double hi = __builtin_rint(qq * (1.0 / 128.0)), lo = qq - 128.0 * hi;   // |hi| <= 127, |lo| <= 64: exact
+        qh8[i] = (int8_t)(int)hi; ql8[i] = (int8_t)(int)lo;
+        const double d = x - sq * qq;
+        r2 = __builtin_fma(d, d, r2);
+    }
+    r2 = wave_sum_f64(r2);
+    if (lane == 0) s_res[wave] = r2;
+    if (wave == kScanWaves - 1) {
+        // |q| as the reference's chain (distances.go:20), one wave: 64 values per request, walked in order
+        double ma = 0.0;
+        for (uint32_t b = 0; b < v.dim; b += 64) {
+            const float x = b + lane < v.dim ? query[b + lane] : 0.f;
+            const uint32_t n = v.dim - b < 64u ? v.dim - b : 64u;
+            for (uint32_t j = 0; j < n; j++) { const double a = (double)__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), j)); ma = __builtin_fma(a, a, ma); }
+        }
+        if (lane == 0) s_qn = __builtin_sqrt(ma);
+    }
+    __syncthreads();
+    double qres2 = 0.0;
+    for (uint32_t w = 0; w < kScanWaves; w++) qres2 += s_res[w];
+    const double qn = s_qn;
+    // (a query without a scale: every row comes out "unsure", no H, and the re-score hands the search on)
+    const double qres = q_ok ? __builtin_sqrt(qres2) * (1.0 + 1e-9) + 1e-300 : __builtin_nan("");
+
+    const u4* qh = reinterpret_cast<const u4*>(qh8);
+    const u4* ql = reinterpret_cast<const u4*>(ql8);
+    const u4* plane = reinterpret_cast<const u4*>(v.plane8) + lane;
+    const uint32_t kth = k - 1;
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    bool first = true;
+    for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+        const uint32_t row = t * 64 + lane;
+        const double rn = v.rnorm[row];                                // (requested ahead of the tile's bytes: there when the sums are)
+        const float sc = v.rscale8[row], rr = v.rres8[row];
+        const uint64_t am = v.alive[t];                                // wave-uniform
+        const long long isum = bound8_tile(plane + (size_t)t * steps * 64, qh, ql, steps);
+        float lo, hi;
+        (void)bound_scan_interval8<M>(isum, sq, qn, qres, rn, sc, rr, v.dim, lo, hi);
+        const bool live = (am >> lane) & 1ull;                         // (dead rows and the last tile's padding: never candidates, never in a bound)
+        __builtin_nontemporal_store(live ? ord_f32(lo) : 0xFFFFFFFFu, &lo_all[row]);
+        const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+        if (first) { list = wave_sort64(key, lane); thr = readlane64(list, kth); first = false; }
+        else list_insert(list, thr, key, kth, lane);
+    }
+    bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
 }
 
 // ---------------------------------------------------------------- the bound scan as a shared pass: 2 - 8 queries over the bfloat16 copy --
@@ -1641,6 +1784,28 @@ bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uin
     return mode == 1 || (dim >= kBoundMqNarrowDim && n_rows >= min_rows);
 }
 bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) { return bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr); }
+// The 8-bit stage in front of it (k_bound_scan8): one unfiltered query the bound scan takes, on an index that holds the 8-bit plane.  The index's
+// plane setter (IndexView::bound_plane) or QV_BOUND_PLANE = 1 puts it first whenever that holds, 2 never; automatic from the smallest
+// measured row count from which 8-bit-first beats bfloat16-first at every measured k — never below kBoundScanMinRows, so a corpus under
+// that floor runs what it ran before whatever mode forces the bound scan itself.  profiles/LAB_r10_bound_scan_8bit.md; us per query,
+// bfloat16 first / 8-bit first, at k = 1, 10, 64 (the 8-bit stage passes on 3 - 4 times the rows, and one workgroup walks them: its
+// k = 64 figures carry 0.1 - 0.15 ms of re-score):
+//   768 dims   300 k 109 / 106, 117 / 124, 173 / 276 (losses)   1M 275 / 188, 277 / 209, 339 / 361 (a loss at k = 64)
+//              3M 752 / 436, 737 / 456, 799 / 618                10M 2386 / 1263, 2352 / 1269, 2417 / 1457
+//   128 dims   1M 62 / 53, 66 / 58, 111 / 113 (a loss at k = 64)  10M 457 / 259, 462 / 265, 502 / 318
+// narrower than kBound8NarrowDim nothing was measured: never automatic.
+constexpr uint32_t kBound8MinDim = 768, kBound8MinRows = 3000000;            // rows of at least 768 dimensions
+constexpr uint32_t kBound8NarrowDim = 128, kBound8NarrowRows = 10000000;     // 128 <= dim < 768 (nothing between was measured)
+static_assert(kBound8MinRows >= kBoundScanMinRows && kBound8NarrowRows >= kBoundScanMinRows, "the 8-bit floors are never below the bound scan's");
+static int bound_plane_mode(int mode) { static const int env_mode = env_int("QV_BOUND_PLANE", 0); return mode ? mode : env_mode; }
+bool bound_scan8_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode, bool has_plane8) {
+    plane_mode = bound_plane_mode(plane_mode);
+    if (plane_mode == 2 || nq != 1 || !has_plane8 || !bound_scan_rule(metric, dim, n_rows, 1, k, mode, true)) return false;
+    return plane_mode == 1 || (dim >= kBound8NarrowDim && n_rows >= (dim >= kBound8MinDim ? kBound8MinRows : kBound8NarrowRows));
+}
+bool bound_scan8_applies(const IndexView& v, uint32_t nq, uint32_t k) {
+    return v.plane != nullptr && bound_scan8_rule(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane, v.plane8 != nullptr);
+}
 // Under a filter (a candidate bitmap in v.alive, or a row set per query): candidate_tiles = the tiles that hold a candidate of any query of
 // the pass, as the host knows it without a device read (an upper bound: sets count their non-empty words, tombstones are not subtracted, a pass
 // takes min(n_tiles, the sum over its queries) — so eight queries naming ONE striped set look like eight distinct ones).  "always" takes
@@ -1682,7 +1847,7 @@ size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tile
     return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)n_tiles * 64 * sizeof(uint32_t);
 }
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked) {
+                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked, bool plane8_first) {
     // (masked: the caller has asked bound_scan_applies_filtered; here only the conditions the kernels need)
     if (!(masked ? bound_scan_rule(v.metric, v.dim, v.n_rows, 1, k, 1, v.plane != nullptr) : bound_scan_applies(v, 1, k)) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
     const uint32_t grid = p.grid;
@@ -1697,14 +1862,39 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
     const size_t lds1 = (size_t)v.dim * sizeof(float) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     hipError_t e = hipSuccess;
+    if (plane8_first) {
+        // the 8-bit stage on the second set of control words, in the same workspace (the stages run one after the other); the bfloat16 stage
+        // behind it is gated on that stage's flag and leaves at once when it has answered
+        if (masked || !bound_scan8_applies(v, 1, k)) return hipErrorInvalidValue;
+        BoundCtrl* ctrl8 = ctrl + 1;
+        uint32_t* gate8 = &ctrl8->flag;
+        const size_t lds8 = (size_t)v.dim * 2 + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+#define QV_BOUND8(MMM)                                                                                                       \
+    {                                                                                                                         \
+        e = set_lds(k_bound_scan8<MMM>, lds8); if (e != hipSuccess) return e;                                                 \
+        e = set_lds((k_bound_rescore<MMM, true>), lds2); if (e != hipSuccess) return e;                                       \
+        e = set_lds(k_bound_scan<MMM>, lds1); if (e != hipSuccess) return e;                                                  \
+        e = set_lds(k_bound_rescore<MMM>, lds2); if (e != hipSuccess) return e;                                               \
+        hipLaunchKernelGGL((k_bound_scan8<MMM>), dim3(grid), dim3(kScanBlock), lds8, s, v, d_query, k, ctrl8, lo_all, partial, seed_rows, seed_dist); \
+        hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, ctrl8, cand, (const uint32_t*)nullptr); \
+        hipLaunchKernelGGL((k_bound_rescore<MMM, true>), dim3(1), dim3(kScanBlock), lds2, s, v, d_query, k, ctrl8, cand, d_stats, d_rows_out, d_dist_out, (uint32_t*)nullptr, ctrl); \
+        hipLaunchKernelGGL((k_bound_scan<MMM>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, k, ctrl, lo_all, partial, seed_rows, seed_dist, (const uint32_t*)gate8); \
+        hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, ctrl, cand, (const uint32_t*)gate8); \
+        hipLaunchKernelGGL((k_bound_rescore<MMM>), dim3(1), dim3(kScanBlock), lds2, s, v, d_query, k, ctrl, cand, d_stats, d_rows_out, d_dist_out, gate8, (BoundCtrl*)nullptr); \
+    }
+        if (v.metric == QV_COSINE) QV_BOUND8(QV_COSINE) else QV_BOUND8(QV_DOT)
+#undef QV_BOUND8
+        *gate_out = &ctrl->flag;
+        return hipGetLastError();
+    }
 #define QV_BOUND(MMM)                                                                                                        \
     {                                                                                                                         \
         e = masked ? set_lds((k_bound_scan<MMM, true>), lds1) : set_lds(k_bound_scan<MMM>, lds1); if (e != hipSuccess) return e; \
         e = set_lds(k_bound_rescore<MMM>, lds2); if (e != hipSuccess) return e;                                               \
-        if (masked) hipLaunchKernelGGL((k_bound_scan<MMM, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, k, ctrl, lo_all, partial, seed_rows, seed_dist); \
-        else hipLaunchKernelGGL((k_bound_scan<MMM>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, k, ctrl, lo_all, partial, seed_rows, seed_dist); \
-        hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, ctrl, cand);                      \
-        hipLaunchKernelGGL((k_bound_rescore<MMM>), dim3(1), dim3(kScanBlock), lds2, s, v, d_query, k, ctrl, cand, d_stats, d_rows_out, d_dist_out); \
+        if (masked) hipLaunchKernelGGL((k_bound_scan<MMM, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, k, ctrl, lo_all, partial, seed_rows, seed_dist, (const uint32_t*)nullptr); \
+        else hipLaunchKernelGGL((k_bound_scan<MMM>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, k, ctrl, lo_all, partial, seed_rows, seed_dist, (const uint32_t*)nullptr); \
+        hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, ctrl, cand, (const uint32_t*)nullptr); \
+        hipLaunchKernelGGL((k_bound_rescore<MMM>), dim3(1), dim3(kScanBlock), lds2, s, v, d_query, k, ctrl, cand, d_stats, d_rows_out, d_dist_out, (uint32_t*)nullptr, (BoundCtrl*)nullptr); \
     }
     if (v.metric == QV_COSINE) QV_BOUND(QV_COSINE) else QV_BOUND(QV_DOT)
 #undef QV_BOUND
@@ -1716,6 +1906,35 @@ float host_bound_interval(int metric, uint32_t dim, float s, double qn, double r
     const bool sure = metric == QV_COSINE ? bound_scan_interval<QV_COSINE>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi) : bound_scan_interval<QV_DOT>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi);
     *unsure = sure ? 0 : 1;
     return 0.f;
+}
+
+int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, float* d_lo, float* d_hi) {
+    const bool sure = metric == QV_COSINE ? bound_scan_interval8<QV_COSINE>(isum, sq, qn, qres, rn, rscale, rres8, dim, *d_lo, *d_hi)
+                                          : bound_scan_interval8<QV_DOT>(isum, sq, qn, qres, rn, rscale, rres8, dim, *d_lo, *d_hi);
+    return sure ? 0 : 1;
+}
+// one row as k_row_state8 (qv_misc.hip) leaves it: the bytes, the scale, the residual from the bytes (NaN: a row the bound says nothing about)
+int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res) {
+    float maxabs = 0.f; bool bad = false; double n2 = 0.0;
+    for (uint32_t i = 0; i < dim; i++) {
+        bad |= !((row[i] - row[i]) == 0.0f);
+        maxabs = __builtin_fmaxf(maxabs, __builtin_fabsf(row[i]));
+        n2 = __builtin_fma((double)row[i], (double)row[i], n2);
+    }
+    const float scale = bad ? 0.0f : bound8_scale(maxabs);
+    double s2 = 0.0;
+    for (uint32_t i = 0; i < dim; i++) {
+        const int b = scale > 0.0f ? bound8_quant(row[i], scale) : 0;
+        const double d = (double)row[i] - (double)scale * (double)b;
+        s2 = __builtin_fma(d, d, s2);
+        out_bytes[i] = (int8_t)b;
+    }
+    *out_scale = scale;
+    *out_res = bound8_row_res(bad, maxabs, n2, s2, dim);
+    return 0;
+}
+int host_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8) {
+    return bound_scan8_rule(metric, dim, rows, nq, k, mode, plane_mode, has_plane8 != 0) ? 1 : 0;
 }
 
 // the shared pass of 2 - 8 queries: d_ws = bound_scan_mq_workspace_bytes, d_ctrl = kBoundMqMax BoundCtrl (zero, left zero).  The exact scan of the
@@ -1899,10 +2118,12 @@ hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* 
             // the bound scan on the bfloat16 copy, its exact re-score, and the exact scan behind them that runs only when they hand the query back
             static const int trace = env_int("QV_TRACE", 0);
             if (filtered && trace_filtered()) fprintf(stderr, "qv: scan kernel = k_bound_scan masked (tiles=%u, candidate tiles<=%u, k=%u)\n", v.n_tiles, candidate_tiles, k);
-            if (!filtered && trace) fprintf(stderr, "qv: scan kernel = k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
+            const bool plane8_first = !filtered && bound_scan8_applies(v, nq, k);   // the 8-bit stage first; the bfloat16 stage gated behind it
+            if (!filtered && trace && !plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
+            if (plane8_first && trace) fprintf(stderr, "qv: scan kernel = k_bound_scan8 + k_bound_collect + k_bound_rescore, then gated k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
             const uint32_t* gate = nullptr;
             if (ev0) (void)hipEventRecord(ev0, s);
-            e = launch_bound_scan(v, p, d_queries, k, static_cast<char*>(d_ws) + scan_workspace_bytes(p, 1, k), d_tickets + kBoundCtrlWord, d_bound_stats, d_rows_out, d_dist_out, &gate, s, filtered);
+            e = launch_bound_scan(v, p, d_queries, k, static_cast<char*>(d_ws) + scan_workspace_bytes(p, 1, k), d_tickets + kBoundCtrlWord, d_bound_stats, d_rows_out, d_dist_out, &gate, s, filtered, plane8_first);
             if (e != hipSuccess) return e;
             QV_DISPATCH_METRIC(v.metric, {
                 if constexpr (MM == QV_COSINE || MM == QV_DOT) {

@@ -912,6 +912,30 @@ int qv_sharded_bound_scan_stats(qv_sharded* s, uint64_t out[4]) {
     return QV_OK;
 }
 
+int qv_sharded_set_bound_plane(qv_sharded* s, int mode) {
+    if (!s) return fail(QV_ERR_INVALID_ARG, "handle is null");
+    std::unique_lock<std::shared_mutex> l(s->mu);
+    reap_retired(s);
+    for (auto& x : s->sh) { const int rc = qv_index_set_bound_plane(x.idx, mode); if (rc != QV_OK) return rc; }
+    return QV_OK;
+}
+
+int qv_sharded_bound_scan8_stats(qv_sharded* s, uint64_t out[4]) {
+    if (!s || !out) return fail(QV_ERR_INVALID_ARG, "handle/out is null");
+    std::unique_lock<std::shared_mutex> l(s->mu);
+    out[0] = out[1] = out[2] = 0; out[3] = 1;
+    bool first = true;
+    for (auto& x : s->sh) {
+        uint64_t o[4];
+        const int rc = qv_index_bound_scan8_stats(x.idx, o);
+        if (rc != QV_OK) return rc;
+        if (first) out[0] = o[0];
+        first = false;
+        out[1] += o[1]; out[2] += o[2]; out[3] &= o[3];
+    }
+    return QV_OK;
+}
+
 int qv_sharded_profile(qv_sharded* s, int enable) {
     if (!s) return fail(QV_ERR_INVALID_ARG, "handle is null");
     std::unique_lock<std::shared_mutex> l(s->mu);

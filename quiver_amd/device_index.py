@@ -255,6 +255,19 @@ class DeviceIndex:
         check(lib().qv_index_bound_scan_stats(self._h, out))
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
+    BOUND_PLANE = {"auto": 0, "8bit": 1, "bf16": 2}
+
+    def set_bound_plane(self, mode):
+        """which plane a single unfiltered query's bound scan starts on: "auto" (the 8-bit plane from its measured shapes on), "8bit"
+        (whenever the bound scan takes the search and the plane is held), "bf16" (qv_index_set_bound_plane)"""
+        check(lib().qv_index_set_bound_plane(self._h, self.BOUND_PLANE.get(mode, mode)))
+
+    def bound_scan8_stats(self) -> dict:
+        """survivors of the last 8-bit stage, searches it handed on to the bfloat16 stage, searches that took it, whether the plane exists"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_index_bound_scan8_stats(self._h, out))
+        return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
+
     DEBUG_READ = {"rnorm": (0, np.float64), "rres": (1, np.float32), "plane": (2, np.uint16)}
 
     def debug_read(self, what: str) -> np.ndarray:
@@ -611,6 +624,14 @@ class ShardedIndex:
     def bound_scan_stats(self) -> dict:
         out = (C.c_uint64 * 4)()
         check(lib().qv_sharded_bound_scan_stats(self._h, out))
+        return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
+
+    def set_bound_plane(self, mode):
+        check(lib().qv_sharded_set_bound_plane(self._h, DeviceIndex.BOUND_PLANE.get(mode, mode)))
+
+    def bound_scan8_stats(self) -> dict:
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_sharded_bound_scan8_stats(self._h, out))
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
     def set_filter(self, filter):
