@@ -343,6 +343,15 @@ int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, 
  * 5 - 8 queries from 1M rows with nine tenths of the tiles and k <= 10 (from 10M: any k) — never below the unfiltered floors and
  * never with candidate_tiles == 0.  (A row set that selects fewer than k rows counts as no candidate tile.) */
 int qv_scan_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles);
+/* Which kernels would answer a fused flat search (k <= 64) of nq queries over rows x dim of `metric` on a device of `cus` compute units —
+ * the dispatch's own decision (plan_flat), on the host, without an index or a device.  tickets: the call carries its stream's ticket
+ * words (the host-pointer and device-pointer searches do; the batched path's sample scan and the sharded paths do not); bound_mode /
+ * plane_mode: QV_BOUND_SCAN_* / QV_BOUND_PLANE_*; has_plane / has_plane8: the index holds the bfloat16 copy / the 8-bit plane;
+ * candidate_tiles: 0xFFFFFFFF for an unfiltered search, else as qv_scan_bound_applies_filtered takes it.  Returns the route in priority
+ * order — 0 small, 1 bound_mq, 2 split_mq, 3 mq64, 4 mq, 5 bound, 6 bound8_first, 7 split, 8 fused, 9 two_launch —
+ * or < 0 for arguments no route serves.  (More than 32 queries on route 3: the last 1 - 8 are split off as a pass of their own.) */
+int qv_scan_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
+                  uint32_t candidate_tiles);
 /* The interval stage 1 derives for one row, on the host (the kernel's own function compiled for the CPU; metric QV_COSINE or
  * QV_DOT): s = the float32 chain of the query times the row's bfloat16 copy, qn = |query|, rn = |row|, rres = |row - bf16(row)|
  * rounded up.  Returns 1 when the row is one the bound says nothing about (always a survivor), 0 otherwise with

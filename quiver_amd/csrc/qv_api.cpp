@@ -394,6 +394,14 @@ int qv_index_get_rows(qv_index* idx, const uint32_t* rows, uint32_t n, float* ou
     return QV_OK;
 }
 
+// The route of a fused flat search (kk <= kMaxFusedK, kk == k_stride), for the launch (enqueue_search) and for the workspace
+// (search_ws_bytes): the same question with the same inputs, so what is launched is what was sized.  tickets: the call carries the
+// stream's ticket words (and with them the index's bound-scan counters); cand_tiles: kBoundNoFilter, or a filtered call's candidate tiles.
+static qv::FlatPlan flat_plan(const qv_index* idx, uint32_t nq, uint32_t kk, bool tickets, uint32_t cand_tiles) {
+    const qv::IndexView v = idx->view();
+    return qv::plan_flat(v, qv::plan_scan(v.n_tiles, idx->cus), nq, kk, tickets, tickets, cand_tiles);
+}
+
 // shared by the host and device entry points: enqueue nq searches of list length kk
 // (kk = min(k, live)), results written with row stride k_stride
 static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
@@ -416,15 +424,10 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
         }
         // (a masked search: the bound scan's forms that skip tiles without a candidate, under the filtered rule — given tickets)
         const uint32_t cand_tiles = d_candidates ? candidate_tiles : qv::kBoundNoFilter;
-        uint32_t* bound_stats = d_tickets && (d_candidates ? qv::bound_scan_applies_filtered(v, nq, kk, cand_tiles) : qv::bound_scan_applies(v, nq, kk)) ? idx->d_bound_stats : nullptr;
-        if (!bound_stats && d_tickets && qv::flat_small_applies(v, nq, kk) && !qv::flat_split_applies(v, nq, kk)) {   // small collection: scan + merge in one launch
-            hipError_t e = qv::launch_flat_small(v, d_queries, nq, kk, ws, d_tickets, d_rows_out, d_dist_out, nq == 1 ? done_flag : nullptr, done_seq, s, ev0, ev1);
-            if (e != hipSuccess) return fail(QV_ERR_DEVICE, "small scan launch failed: %s", hipGetErrorString(e));
-            if (flag_used) *flag_used = nq == 1 && done_flag != nullptr;
-            return QV_OK;
-        }
-        hipError_t e = qv::launch_flat_topk(v, plan, d_queries, nq, kk, ws, d_rows_out, d_dist_out, s, ev0, ev1, d_tickets, nq == 1 ? done_flag : nullptr, done_seq, flag_used, bound_stats, cand_tiles);
-        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "flat scan launch failed: %s", hipGetErrorString(e));
+        const qv::FlatPlan fp = flat_plan(idx, nq, kk, d_tickets != nullptr, cand_tiles);
+        hipError_t e = qv::launch_flat_topk(v, plan, fp, d_queries, nq, kk, ws, d_rows_out, d_dist_out, s, ev0, ev1, d_tickets, nq == 1 ? done_flag : nullptr, done_seq, flag_used,
+                                            fp.bound() ? idx->d_bound_stats : nullptr, cand_tiles);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "%s scan launch failed: %s", fp.route == qv::FlatRoute::small ? "small" : "flat", hipGetErrorString(e));
         return QV_OK;
     }
     // 64 < k <= 8192 (the negative-example branches fetch max(2k, 30), hybrid_index.go:516-522; BatchSearch takes any k,
@@ -454,14 +457,18 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
     return QV_OK;
 }
 
-static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool bound_filtered = false /* a filtered call the bound scan will answer */) {
+// tickets / cand_tiles: as the call will be enqueued (flat_plan) — a call whose route is a bound scan is sized for it, no other call is
+static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles = qv::kBoundNoFilter) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     const qv::ScanPlan plan = qv::plan_scan(n_tiles, idx->cus);
-    if (kk <= (uint32_t)qv::kMaxFusedK && kk == k_stride)   // partial lists + the multi-query kernels' query blocks (the small scan's lists fit in them)
+    if (kk <= (uint32_t)qv::kMaxFusedK && kk == k_stride) {   // partial lists + the multi-query kernels' query blocks (the small scan's lists fit in them)
+        const qv::FlatPlan fp = flat_plan(idx, nq, kk, tickets, cand_tiles);
+        const bool bound1 = fp.route == qv::FlatRoute::bound || fp.route == qv::FlatRoute::bound8_first;
         return std::max({qv::flat_small_workspace_bytes(std::min(nq, 4u), kk),
                         qv::scan_workspace_bytes(plan, nq, kk) + std::max(std::max((size_t)(nq + 16) * idx->dim4 * 4 * sizeof(double), qv::mq64_workspace_bytes(nq, idx->dim4)),
-                                                                          nq == 1 ? qv::bound_scan_workspace_bytes(plan, kk, n_tiles) : (size_t)0),   // (the bound scan's lists sit behind the exact scan's)
-                                 nq >= 2 && nq <= 8 && (bound_filtered || qv::bound_scan_applies(idx->view(), nq, kk)) ? qv::bound_scan_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim) : (size_t)0});   // (a shared bound pass has the workspace to itself)
+                                                                          bound1 ? qv::bound_scan_workspace_bytes(plan, kk, n_tiles) : (size_t)0),   // (the bound scan's lists sit behind the exact scan's)
+                                 fp.route == qv::FlatRoute::bound_mq ? qv::bound_scan_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim) : (size_t)0});   // (a shared bound pass has the workspace to itself)
+    }
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
     return qv::full_sort_workspace_bytes(n_tiles);
@@ -498,7 +505,7 @@ static int exact_search_host(qv_index* idx, const float* queries, uint32_t nq, u
     const size_t qbytes = (size_t)nq * idx->dim * sizeof(float);
     const size_t obytes = (size_t)nq * kk * sizeof(uint32_t);
     if ((rc = c->d_q.ensure(qbytes)) || (rc = c->h_q.ensure(qbytes)) || (rc = c->d_rows.ensure(obytes)) || (rc = c->d_dist.ensure(obytes)) ||
-        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(obytes)) || (rc = c->ws.ensure(search_ws_bytes(idx, nq, kk, kk))))
+        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(obytes)) || (rc = c->ws.ensure(search_ws_bytes(idx, nq, kk, kk, true))))
         return rc;
     memcpy(c->h_q.p, queries, qbytes);
     // small result sets are written by the last kernel straight into the (device-visible) pinned buffers: two copy commands less
@@ -654,7 +661,7 @@ int qv_index_search_negative(qv_index* idx, const float* query, const float* neg
     CtxGuard guard{idx, c};
     const size_t vbytes = (size_t)idx->dim * sizeof(float), obytes = (size_t)kk * 4;
     if ((rc = c->d_q.ensure(2 * vbytes)) || (rc = c->h_q.ensure(2 * vbytes)) || (rc = c->d_rows.ensure(obytes)) || (rc = c->d_dist.ensure(2 * obytes)) ||
-        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(2 * obytes)) || (rc = c->ws.ensure(search_ws_bytes(idx, 1, kk, kk))))
+        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(2 * obytes)) || (rc = c->ws.ensure(search_ws_bytes(idx, 1, kk, kk, false))))
         return rc;
     memcpy(c->h_q.p, query, vbytes);
     memcpy(static_cast<char*>(c->h_q.p) + vbytes, negative, vbytes);
@@ -718,8 +725,8 @@ int qv_index_search_masked(qv_index* idx, const float* queries, uint32_t nq, uin
         return rc;
     // the bound scan under the mask when the filtered rule takes it: then, and only then, the call carries the context's ticket words
     // (without them every path is the one a masked search has always taken)
-    const bool bound = kk <= (uint32_t)qv::kMaxFusedK && qv::bound_scan_applies_filtered(idx->view(), nq, kk, cand_tiles);
-    if ((rc = c->ws.ensure(search_ws_bytes(idx, nq, kk, kk, bound)))) return rc;
+    const bool bound = kk <= (uint32_t)qv::kMaxFusedK && flat_plan(idx, nq, kk, true, cand_tiles).bound();
+    if ((rc = c->ws.ensure(search_ws_bytes(idx, nq, kk, kk, bound, cand_tiles)))) return rc;
     uint32_t* tickets = nullptr;
     if (bound) {
         if (!c->tickets.p) { if ((rc = c->tickets.ensure(256))) return rc; HIPCHK(hipMemsetAsync(c->tickets.p, 0, 256, c->stream)); }   // (on the stream that reads them: see stream_workspace)
@@ -865,7 +872,7 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const q
         //  as no candidate tile, which the automatic rule declines; "always" still takes the path)
         const bool too_few = sets[q] && sets[q]->selected < kk;
         pieces.push_back(RowsetPiece{q, e - q, kk, false, false, sets[q] && !too_few ? std::min<uint32_t>(sets[q]->tiles, (idx->n_rows + 63) / 64) : 0u});
-        if (kk) ws = std::max(ws, search_ws_bytes(idx, e - q, kk, k));
+        if (kk) ws = std::max(ws, search_ws_bytes(idx, e - q, kk, k, e - q == 1, sets[q] ? pieces.back().cand_tiles : qv::kBoundNoFilter));   // (as rowsets_enqueue passes them on)
         q = e;
     }
     return ws;
@@ -1060,7 +1067,7 @@ int qv_index_search_device(qv_index* idx, const float* d_queries, uint32_t nq, u
     void* ws = nullptr;
     std::unique_lock<std::mutex> ws_hold;
     uint32_t* tickets = nullptr;
-    int rc = stream_workspace(idx, s, search_ws_bytes(idx, nq, kk, k), &ws, &ws_hold, &tickets);
+    int rc = stream_workspace(idx, s, search_ws_bytes(idx, nq, kk, k, true), &ws, &ws_hold, &tickets);
     if (rc != QV_OK) return rc;
     return enqueue_search(idx, d_queries, nq, kk, k, ws, 0, d_rows_out, d_dist_out, s, nullptr, tickets);
 }
@@ -1079,7 +1086,7 @@ int qv_internal_search_candidates_device(qv_index* idx, const float* d_queries, 
     const uint32_t kk = (uint32_t)std::min<uint64_t>(k_stride, matching);
     void* ws = nullptr;
     std::unique_lock<std::mutex> ws_hold;
-    int rc = stream_workspace(idx, s, search_ws_bytes(idx, nq, kk, k_stride), &ws, &ws_hold);
+    int rc = stream_workspace(idx, s, search_ws_bytes(idx, nq, kk, k_stride, false), &ws, &ws_hold);
     if (rc != QV_OK) return rc;
     return enqueue_search(idx, d_queries, nq, kk, k_stride, ws, 0, d_rows_out, d_dist_out, s, d_candidates);
 }
@@ -1268,9 +1275,7 @@ int qv_scan_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, flo
 int qv_scan_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {
     if (metric != QV_COSINE && metric != QV_DOT) return fail(QV_ERR_UNSUPPORTED, "the bound scan's metrics are cosine and dot; got %d", metric);
     if (!d_lo || !d_hi || dim == 0) return fail(QV_ERR_INVALID_ARG, "d_lo/d_hi is null or dim is 0");
-    int unsure = 0;
-    (void)qv::host_bound_interval(metric, dim, s, qn, rn, rres, d_lo, d_hi, &unsure);
-    return unsure;
+    return qv::host_bound_interval(metric, dim, s, qn, rn, rres, d_lo, d_hi);
 }
 
 int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {
@@ -1301,6 +1306,14 @@ int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {
 int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane) {
     if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
     return qv::host_bound_applies(metric, dim, rows, nq, k, mode, has_plane);
+}
+
+int qv_scan_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
+                  uint32_t candidate_tiles) {
+    if (bound_mode < 0 || bound_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "bound_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", bound_mode);
+    if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
+    const int route = qv::host_flat_route(metric, dim, rows, nq, k, cus, tickets, bound_mode, plane_mode, has_plane, has_plane8, candidate_tiles);
+    return route >= 0 ? route : fail(QV_ERR_INVALID_ARG, "no fused flat search has these arguments (metric %d, dim %u, rows %u, nq %u, k %u, cus %d)", metric, dim, rows, nq, k, cus);
 }
 
 int qv_scan_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles) {

@@ -1,4 +1,4 @@
-// qv_bound.h — the interval the single-query bound scan (qv_scan.hip: k_bound_scan) derives for one row from the bfloat16 copy.
+// qv_bound.h — the interval the single-query bound scan (qv_bound_scan.hip: k_bound_scan) derives for one row from the bfloat16 copy.
 // ONE statement of it for the device and the host (qv_scan_bound_interval: what the CPU test of the bound calls).
 //
 // Stage 1 computes S~ = a float32 chain of K = dim fused multiply-adds over q_i * rh_i, with q the caller's float32 query and

@@ -1,0 +1,824 @@
+// qv_bound_scan.hip — the bound scan: a fused flat search (k <= 64, cosine / dot) answered from the index's reduced copies of the rows — the
+// bfloat16 copy, with the 8-bit plane in front of it for one unfiltered query — by rejecting rows on a certified interval of the distance
+// (qv_bound.h) and re-scoring the few survivors in the exact scan's arithmetic.  One query, the shared pass of 2 - 8, their filtered forms;
+// the rules that say when each applies; the launchers and workspace sizes; the interval and the 8-bit row state compiled for the host.
+// Which search takes the path is decided by plan_flat (qv_scan.hip); the exact scan that answers what a bound pass hands back
+// (k_flat_scan<., ., true> behind its gate, launch_flat_redo_flagged) and the list merge (launch_merge_lists) live there too.
+#include "qv_kernels.h"
+#include "qv_bound.h"
+
+namespace qv {
+
+// ---------------------------------------------------------------- one query over a large corpus: reject rows on the bfloat16 copy --
+// k_flat_scan runs at the memory's rate (0.90 of the HBM peak at 10M x 768), so a single query gets faster only by reading fewer
+// bytes.  Of N rows k are returned; the others only have to be REJECTED, and that takes a certified lower bound of the distance,
+// not the float64 chain.  Three launches and the gated exact scan behind them:
+//   k_bound_scan     k_flat_scan's shape — lane == row, a wave owns whole tiles — over the index's bfloat16 copy (IndexView::plane: half
+//                    the bytes; per 16-dimension step a lane reads its two 16-byte halves, the wave two contiguous 512-byte runs per
+//                    request), the query in float32 from LDS, one float32 fma chain S~ per row, and from it the interval [d_lo, d_hi]
+//                    of the reference's float32 distance (qv_bound.h).  d_lo goes out as one ordered word per row (4 bytes against the
+//                    row's 2 dim); the UPPER bounds go through k_flat_scan's own selection — wave lists, the workgroups' lists published,
+//                    the last workgroup merges — so the launch ends with H, the exact k-th smallest upper bound over all live rows.
+//                    Any k rows' upper bounds cap the k-th distance: every row of the answer has d_lo <= H.
+//   k_bound_collect  the rows with d_lo <= H (not strict: ties go on) — k plus a handful on ordinary data — listed with one returning
+//                    atomic per wave and batch that has any.
+//   k_bound_rescore  one workgroup: those rows walked as ONE float64 chain over the float32 tiles — row_accumulate + finalize, the
+//                    query's norm as its chain: the exact scan's bits —, the k best (distance, row) keys written where the exact scan
+//                    writes them.  When the list overflowed, H is not finite (fewer than k rows with a bound), or |q| is not a norm
+//                    the bound works with, it sets the gate word instead and the exact scan launched behind it answers
+//                    (k_flat_scan<., ., true>'s `gate`: otherwise that launch leaves at once).  Nothing is read on the host.
+// (Measured first and not kept: candidates taken DURING the scan against a device-wide threshold word seeded from the waves' first
+// tiles — the tiles walked before the seed's merge lands let 20 - 50 k rows through at k = 64; profiles/LAB_r07_bound_scan.md.)
+// The control words live in the stream's zeroed ticket words and are left zero.
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t kBoundCandCap = 4096;       // rows stage 3 walks exactly (an i.i.d. 10M x 768 corpus leaves k + a few)
+constexpr uint32_t kBoundMaxDim = 4096;
+struct BoundCtrl { uint32_t thr_inv, cand_cnt, ticket, flag; };   // thr_inv = ~(ordered image of H): zero = no finite H
+
+template <int U, bool QN>
+__device__ __forceinline__ void bound_block(const u4* __restrict__ p, const float* __restrict__ q_lds, uint32_t s0, float& acc, double& qa) {
+    u4 x[2 * U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        x[2 * u] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 128]);
+        x[2 * u + 1] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 128 + 32]);
+    }
+    __builtin_amdgcn_sched_barrier(0);                                 // all requests of the block ahead of the arithmetic (see row_accumulate)
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const f4* qq = reinterpret_cast<const f4*>(q_lds + (size_t)(s0 + u) * 16);
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const u4 w = x[2 * u + h];
+            const f4 qa4 = qq[2 * h], qb4 = qq[2 * h + 1];
+            const float qe[8] = {qa4.x, qa4.y, qa4.z, qa4.w, qb4.x, qb4.y, qb4.z, qb4.w};
+            const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {                              // bfloat16 -> float32 is a shift / a mask: exact
+                acc = __builtin_fmaf(qe[2 * j], __uint_as_float(ww[j] << 16), acc);
+                acc = __builtin_fmaf(qe[2 * j + 1], __uint_as_float(ww[j] & 0xFFFF0000u), acc);
+                if constexpr (QN) { const double a = (double)qe[2 * j], b = (double)qe[2 * j + 1]; qa = __builtin_fma(a, a, qa); qa = __builtin_fma(b, b, qa); }
+            }
+        }
+    }
+}
+// S~ of this lane's row of one tile (p = the tile in the copy + the lane's place in a step); QN: |q|^2 as the reference's chain rides along
+template <bool QN>
+__device__ __forceinline__ float bound_tile(const u4* __restrict__ p, const float* __restrict__ q_lds, uint32_t steps, double* qn2) {
+    float acc = 0.f; double qa = 0.0;
+    uint32_t s = 0;
+    for (; s + 8 <= steps; s += 8) bound_block<8, QN>(p, q_lds, s, acc, qa);
+    if (s + 4 <= steps) { bound_block<4, QN>(p, q_lds, s, acc, qa); s += 4; }
+    if (s + 2 <= steps) { bound_block<2, QN>(p, q_lds, s, acc, qa); s += 2; }
+    if (s < steps) bound_block<1, QN>(p, q_lds, s, acc, qa);
+    if constexpr (QN) *qn2 = qa;
+    return acc;
+}
+
+// The end of a bound scan's stage 1 (k_bound_scan, k_bound_scan8): the upper bounds' lists go waves -> wave 0 -> published; the last workgroup
+// to finish merges (k_flat_scan<., ., true>'s protocol) and leaves H, the exact k-th smallest upper bound, in the control words.
+__device__ __forceinline__ void bound_scan_tail(uint64_t list, uint64_t thr, uint64_t* wl /* LDS [kScanWaves][64] */, uint32_t wave, uint32_t lane, uint32_t k, BoundCtrl* __restrict__ ctrl,
+                                                uint64_t* __restrict__ partial, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
+    __shared__ uint32_t s_last;
+    const uint32_t kth = k - 1;
+    wl[wave * 64 + lane] = list;
+    __syncthreads();
+    if (wave == 0) {
+        for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list, thr, lane < k ? wl[w * 64 + lane] : kDeadKey, kth, lane);
+        uint64_t* mine = partial + (size_t)blockIdx.x * k;
+        if (lane < k) (void)atomicExch(reinterpret_cast<unsigned long long*>(&mine[lane]), (unsigned long long)list);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // every lane's exchange has returned: the list is at the memory side
+        uint32_t last = 0;
+        if (lane == 0) last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+        last = __builtin_amdgcn_readfirstlane(last);
+        if (last && lane == 0) ctrl->ticket = 0;                       // for the next launch on these words (stream order)
+        if (lane == 0) s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    merge_lists_last_workgroup(partial, gridDim.x, k, seed_rows, seed_dist);
+    if (wave == 0 && lane == kth) {                                    // (this lane wrote them) H: a finite k-th upper bound, or none
+        const uint32_t o = ord_f32(seed_dist[kth]);
+        ctrl->thr_inv = (seed_rows[kth] != 0xFFFFFFFFu && o < 0xFF800000u) ? ~o : 0u;
+        ctrl->cand_cnt = 0;
+    }
+}
+
+// SKIP (k_bound_scan<., true>: v.alive is a filter's candidate bitmap, alive & set — k_rowset_and's or the masked upload): a tile whose word is
+// zero is not requested, neither its copy nor rnorm nor rres.  Its 64 lower-bound words are WRITTEN as 0xFFFFFFFF all the same: k_bound_collect
+// reads every word and the workspace is reused, so an unwritten tile would hold an earlier search's bounds; 256 bytes stored against dim * 128
+// bytes not read, and the collect stays as it is.  |q|^2 rides along the first tile the wave READS; a wave that reads none publishes a dead list.
+template <int M, bool SKIP = false>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
+             uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist,
+             const uint32_t* __restrict__ gate = nullptr /* behind the 8-bit stage (k_bound_rescore<., true> wrote the word): zero = it has answered, leave at once */) {
+    if (gate != nullptr && *gate == 0u) return;
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* q_lds = reinterpret_cast<float*>(smem);                     // [dim], dim a multiple of 16
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (size_t)v.dim * sizeof(float));   // [kScanWaves][64]
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (uint32_t i = threadIdx.x; i < v.dim; i += blockDim.x) q_lds[i] = query[i];
+    __syncthreads();
+    const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves, kth = k - 1;
+    const double gamma = bound_scan_gamma(v.dim);
+    const u4* plane = reinterpret_cast<const u4*>(v.plane) + ((lane >> 5) * 64 + (lane & 31));
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    double qn = 0.0;
+
+    uint64_t am_read = 0ull;                                           // (SKIP) the word of the tile being walked
+    auto finish_tile = [&](uint32_t t, float s, bool first) {
+        const uint32_t row = t * 64 + lane;
+        const double rn = v.rnorm[row];
+        const float rr = v.rres[row];
+        uint64_t am;                                                   // wave-uniform
+        if constexpr (SKIP) am = am_read; else am = v.alive[t];
+        float lo, hi;
+        (void)bound_scan_interval<M>(s, qn, rn, rr, v.dim, gamma, lo, hi);
+        const bool live = (am >> lane) & 1ull;                         // (dead rows and the last tile's padding: never candidates, never in a bound)
+        __builtin_nontemporal_store(live ? ord_f32(lo) : 0xFFFFFFFFu, &lo_all[row]);
+        const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+        if (first) { list = wave_sort64(key, lane); thr = readlane64(list, kth); }
+        else list_insert(list, thr, key, kth, lane);
+    };
+
+    uint32_t t = blockIdx.x * kScanWaves + wave;
+    if constexpr (SKIP) {
+        bool first = true;
+        uint64_t am_next = t < v.n_tiles ? v.alive[t] : 0ull;
+        for (; t < v.n_tiles; t += tw) {
+            const uint64_t am = am_next;
+            if (t + tw < v.n_tiles) am_next = v.alive[t + tw];         // (the next tile's word: in flight behind this tile's rows)
+            if (am == 0ull) { __builtin_nontemporal_store(0xFFFFFFFFu, &lo_all[t * 64 + lane]); continue; }
+            am_read = am;
+            if (first) {
+                double qn2 = 0.0;
+                const float s = bound_tile<true>(plane + (size_t)t * steps * 128, q_lds, steps, &qn2);
+                qn = __builtin_sqrt(qn2);
+                finish_tile(t, s, true);
+                first = false;
+            } else finish_tile(t, bound_tile<false>(plane + (size_t)t * steps * 128, q_lds, steps, nullptr), false);
+        }
+    } else {
+        if (t < v.n_tiles) {                                           // first tile: sorted outright, |q| rides along
+            double qn2 = 0.0;
+            const float s = bound_tile<true>(plane + (size_t)t * steps * 128, q_lds, steps, &qn2);
+            qn = __builtin_sqrt(qn2);
+            finish_tile(t, s, true);
+            t += tw;
+        }
+        for (; t < v.n_tiles; t += tw) finish_tile(t, bound_tile<false>(plane + (size_t)t * steps * 128, q_lds, steps, nullptr), false);
+    }
+
+    bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
+}
+
+// the rows with d_lo <= H, four per thread and step (lo: one query's ordered words; cnt: its counter; cand: its list)
+__device__ __forceinline__ void bound_collect(const uint32_t* __restrict__ lo, uint32_t n /* multiple of 64 */, uint32_t H, uint32_t* __restrict__ cnt, uint32_t* __restrict__ cand) {
+    const uint32_t lane = lane_id();
+    for (uint32_t base = blockIdx.x * 1024u; base < n; base += gridDim.x * 1024u) {
+        const uint32_t i = base + threadIdx.x * 4u;
+        u4 x = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        if (i < n) x = __builtin_nontemporal_load(reinterpret_cast<const u4*>(lo + i));
+        const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const bool c = xs[j] <= H && xs[j] != 0xFFFFFFFFu;
+            const uint64_t m = __ballot(c);
+            if (m) {
+                uint32_t b0 = 0;
+                if (lane == (uint32_t)__builtin_ctzll(m)) b0 = atomicAdd(cnt, (uint32_t)__builtin_popcountll(m));
+                b0 = __builtin_amdgcn_readlane(b0, (uint32_t)__builtin_ctzll(m));
+                const uint32_t slot = b0 + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+                if (c && slot < kBoundCandCap) cand[slot] = i + (uint32_t)j;
+            }
+        }
+    }
+}
+__global__ void __launch_bounds__(256)
+k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand,
+                const uint32_t* __restrict__ gate = nullptr /* as k_bound_scan's */) {
+    if (gate != nullptr && *gate == 0u) return;
+    const uint32_t inv = ctrl->thr_inv;
+    if (inv == 0u) return;                                             // no H: k_bound_rescore hands the query back
+    bound_collect(lo_all, n, ~inv, &ctrl->cand_cnt, cand);
+}
+
+// One query's survivors walked exactly by one workgroup (cnt: how many the collect counted; has_H: it had a threshold).  decided(hand_back)
+// runs on thread 0 once the query's norm is known; a query handed back writes nothing.
+template <int M, typename F>
+__device__ __forceinline__ void bound_rescore_query(const IndexView& v, const float* __restrict__ query, uint32_t k, uint32_t cnt, bool has_H, const uint32_t* __restrict__ cand,
+                                                    uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, F decided) {
+    using Q = typename MT<M>::Q;
+    extern __shared__ __align__(16) unsigned char smem[];
+    Q* q_lds = reinterpret_cast<Q*>(smem);
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (((size_t)v.dim4 * 4 * sizeof(Q)) + 15) / 16 * 16);   // [kScanWaves][64]
+    __shared__ double s_qn;
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t ns = cnt < kBoundCandCap ? cnt : kBoundCandCap, kth = k - 1;
+    stage_query<M>(q_lds, query, v.dim, v.dim4);
+    __syncthreads();
+    // the survivors' rows and norms are requested before the query's norm is walked
+    const f4* tiles = reinterpret_cast<const f4*>(v.tiles);
+    if (wave == kScanWaves - 1) {
+        // |q| as the reference's chain (distances.go:20): cosine's finalize takes it, and both metrics' hand-back rule
+        double ma = 0.0;
+        for (uint32_t i = 0; i < v.dim; i++) { const double a = (double)q_lds[i]; ma = __builtin_fma(a, a, ma); }
+        if (lane == 0) s_qn = __builtin_sqrt(ma);
+    }
+    __syncthreads();
+    const double qn = s_qn;
+    const bool hand_back = cnt > kBoundCandCap || !has_H || !bound_scan_norm_ok(qn, v.dim);
+    if (threadIdx.x == 0) decided(hand_back);
+    if (hand_back) return;
+    QConst qc; qc.qn = 0.0; qc.qn32 = 0.0f;
+    if constexpr (M == QV_COSINE) qc.qn = qn;
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    for (uint32_t base = wave * 64; base < ns; base += kScanWaves * 64) {
+        const uint32_t i = base + lane;
+        uint64_t key = kDeadKey;
+        if (i < ns) {
+            const uint32_t row = cand[i];
+            const typename MT<M>::A acc = row_accumulate<M, kUnroll, false, true>(tiles + (size_t)(row >> 6) * v.dim4 * 64 + (row & 63), 64, q_lds, v.dim4);
+            double rn = 0.0;
+            if constexpr (MT<M>::needs_rnorm) rn = v.rnorm[row];
+            key = make_key(finalize<M>(acc, qc, rn), row);
+        }
+        if (base == wave * 64) { list = wave_sort64(key, lane); thr = readlane64(list, kth); }
+        else list_insert(list, thr, key, kth, lane);
+    }
+    __syncthreads();
+    wl[wave * 64 + lane] = list;
+    __syncthreads();
+    if (wave == 0) {
+        for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list, thr, lane < k ? wl[w * 64 + lane] : kDeadKey, kth, lane);
+        if (lane < k) {
+            const bool dead = list == kDeadKey;
+            rows_out[lane] = dead ? 0xFFFFFFFFu : (uint32_t)list;
+            dist_out[lane] = dead ? __uint_as_float(0x7F800000u) : unord_f32((uint32_t)(list >> 32));
+        }
+    }
+}
+
+// P8: the re-score behind the 8-bit stage (ctrl = that stage's words, next = the bfloat16 stage's).  It answers, or sets its own flag — the
+// word the bfloat16 stage's three launches are gated on — and then that stage decides or hands on to the exact scan.  An 8-bit search counts
+// as a bound-scan search in stats[0 .. 2]; its own counters sit at kBound8StatsWord.
+// gate (the bfloat16 stage behind the 8-bit one): zero = the 8-bit stage has answered and has cleared this stage's flag for the exact scan
+// behind; non-zero = this stage runs, and zeroes the word, which it is the last to read.
+template <int M, bool P8 = false>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand,
+                uint32_t* __restrict__ stats, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, uint32_t* gate = nullptr, BoundCtrl* next = nullptr) {
+    if (gate != nullptr && *gate == 0u) return;
+    const uint32_t cnt = ctrl->cand_cnt, thr_inv = ctrl->thr_inv;
+    bound_rescore_query<M>(v, query, k, cnt, thr_inv != 0u, cand, rows_out, dist_out, [&](bool hand_back) {
+        if constexpr (P8) {
+            stats[kBound8StatsWord] = cnt;
+            if (hand_back) (void)atomicAdd(&stats[kBound8StatsWord + 1], 1u);
+            (void)atomicAdd(&stats[kBound8StatsWord + 2], 1u);
+            if (!hand_back) { stats[0] = cnt; (void)atomicAdd(&stats[2], 1u); next->flag = 0u; }
+        } else {
+            stats[0] = cnt;
+            if (hand_back) (void)atomicAdd(&stats[1], 1u);
+            (void)atomicAdd(&stats[2], 1u);
+            if (gate != nullptr) *gate = 0u;                           // (every thread read it before the barriers in front of this call)
+        }
+        ctrl->flag = hand_back ? 1u : 0u;                              // the launch behind this one reads it
+        ctrl->cand_cnt = 0; ctrl->thr_inv = 0;                         // zero, as the words are kept
+    });
+}
+
+// ---------------------------------------------------------------- one query: reject rows on the 8-bit plane first --
+// k_bound_scan's walk and tail over IndexView::plane8 — a quarter of the float32 bytes: per 16-dimension step a lane reads its row's 16
+// int8 values (one dwordx4, the wave one contiguous KiB).  The query is quantised once per workgroup into LDS as two int8 terms
+// (qv_bound.h: qq = 128 hi + lo), a row's sum is eight integer dot products per step, exact, and the interval comes from
+// bound_scan_interval8.  Lower bounds, upper bounds, H, k_bound_collect and the re-score are the bfloat16 stage's own; what this stage
+// cannot decide (more than kBoundCandCap candidates, no finite H, a query it cannot quantise) goes to the bfloat16 stage, gated
+// behind it, not to the exact scan: corpora with many rows within the 8-bit margin of the k-th distance keep the bfloat16 stage's time.
+typedef int i32;
+template <int U>
+__device__ __forceinline__ void bound8_block(const u4* __restrict__ p, const u4* __restrict__ qh, const u4* __restrict__ ql, uint32_t s0, i32 (&acc)[4]) {
+    u4 x[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) x[u] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 64]);
+    __builtin_amdgcn_sched_barrier(0);                                 // all requests of the block ahead of the arithmetic (see row_accumulate)
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const u4 h = qh[s0 + u], l = ql[s0 + u];
+        acc[0] = __builtin_amdgcn_sdot4((i32)h.x, (i32)x[u].x, acc[0], false);
+        acc[1] = __builtin_amdgcn_sdot4((i32)h.y, (i32)x[u].y, acc[1], false);
+        acc[0] = __builtin_amdgcn_sdot4((i32)h.z, (i32)x[u].z, acc[0], false);
+        acc[1] = __builtin_amdgcn_sdot4((i32)h.w, (i32)x[u].w, acc[1], false);
+        acc[2] = __builtin_amdgcn_sdot4((i32)l.x, (i32)x[u].x, acc[2], false);
+        acc[3] = __builtin_amdgcn_sdot4((i32)l.y, (i32)x[u].y, acc[3], false);
+        acc[2] = __builtin_amdgcn_sdot4((i32)l.z, (i32)x[u].z, acc[2], false);
+        acc[3] = __builtin_amdgcn_sdot4((i32)l.w, (i32)x[u].w, acc[3], false);
+    }
+}
+// I of this lane's row of one tile (p = the tile in the plane + the lane)
+__device__ __forceinline__ long long bound8_tile(const u4* __restrict__ p, const u4* __restrict__ qh, const u4* __restrict__ ql, uint32_t steps) {
+    i32 acc[4] = {0, 0, 0, 0};
+    uint32_t s = 0;
+    for (; s + 16 <= steps; s += 16) bound8_block<16>(p, qh, ql, s, acc);
+    if (s + 8 <= steps) { bound8_block<8>(p, qh, ql, s, acc); s += 8; }
+    if (s + 4 <= steps) { bound8_block<4>(p, qh, ql, s, acc); s += 4; }
+    if (s + 2 <= steps) { bound8_block<2>(p, qh, ql, s, acc); s += 2; }
+    if (s < steps) bound8_block<1>(p, qh, ql, s, acc);
+    return ((long long)acc[0] + (long long)acc[1]) * 128ll + ((long long)acc[2] + (long long)acc[3]);   // (each partial sum exact in int32: dim <= kBoundMaxDim)
+}
+
+template <int M>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_scan8(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
+              uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    int8_t* qh8 = reinterpret_cast<int8_t*>(smem);                     // [dim] hi terms, [dim] lo terms, dim a multiple of 16
+    int8_t* ql8 = qh8 + v.dim;
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (size_t)v.dim * 2);   // [kScanWaves][64]
+    __shared__ float s_max[kScanWaves];
+    __shared__ uint32_t s_bad[kScanWaves];
+    __shared__ double s_res[kScanWaves];
+    __shared__ double s_qn;
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves;
+
+    // the query, quantised: sq = max|q_i| / 16256, qq = rint(q / sq) = 128 hi + lo; qres = |q - sq qq| rounded up
+    float mx = 0.f; bool bad = false;
+    for (uint32_t i = threadIdx.x; i < v.dim; i += blockDim.x) { const float x = query[i]; bad |= !((x - x) == 0.0f); mx = __builtin_fmaxf(mx, __builtin_fabsf(x)); }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) mx = __builtin_fmaxf(mx, __shfl_xor(mx, m));
+    const bool wbad = __ballot(bad) != 0ull;
+    if (lane == 0) { s_max[wave] = mx; s_bad[wave] = wbad ? 1u : 0u; }
+    __syncthreads();
+    uint32_t anybad = 0;
+    for (uint32_t w = 0; w < kScanWaves; w++) { mx = __builtin_fmaxf(mx, s_max[w]); anybad |= s_bad[w]; }
+    const bool q_ok = !anybad && mx > 0.0f;
+    const double sq = q_ok ? (double)mx / (double)kBound8QueryMax : 1.0;
+    double r2 = 0.0;
+    for (uint32_t i = threadIdx.x; i < v.dim; i += blockDim.x) {
+        const double x = q_ok ? (double)query[i] : 0.0;
+        const double qq = __builtin_rint(x / sq);                      // |qq| <= 16256
+        const double hi = __builtin_rint(qq * (1.0 / 128.0)), lo = qq - 128.0 * hi;   // |hi| <= 127, |lo| <= 64: exact
+        qh8[i] = (int8_t)(int)hi; ql8[i] = (int8_t)(int)lo;
+        const double d = x - sq * qq;
+        r2 = __builtin_fma(d, d, r2);
+    }
+    r2 = wave_sum_f64(r2);
+    if (lane == 0) s_res[wave] = r2;
+    if (wave == kScanWaves - 1) {
+        // |q| as the reference's chain (distances.go:20), one wave: 64 values per request, walked in order
+        double ma = 0.0;
+        for (uint32_t b = 0; b < v.dim; b += 64) {
+            const float x = b + lane < v.dim ? query[b + lane] : 0.f;
+            const uint32_t n = v.dim - b < 64u ? v.dim - b : 64u;
+            for (uint32_t j = 0; j < n; j++) { const double a = (double)__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), j)); ma = __builtin_fma(a, a, ma); }
+        }
+        if (lane == 0) s_qn = __builtin_sqrt(ma);
+    }
+    __syncthreads();
+    double qres2 = 0.0;
+    for (uint32_t w = 0; w < kScanWaves; w++) qres2 += s_res[w];
+    const double qn = s_qn;
+    // (a query without a scale: every row comes out "unsure", no H, and the re-score hands the search on)
+    const double qres = q_ok ? __builtin_sqrt(qres2) * (1.0 + 1e-9) + 1e-300 : __builtin_nan("");
+
+    const u4* qh = reinterpret_cast<const u4*>(qh8);
+    const u4* ql = reinterpret_cast<const u4*>(ql8);
+    const u4* plane = reinterpret_cast<const u4*>(v.plane8) + lane;
+    const uint32_t kth = k - 1;
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    bool first = true;
+    for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+        const uint32_t row = t * 64 + lane;
+        const double rn = v.rnorm[row];                                // (requested ahead of the tile's bytes: there when the sums are)
+        const float sc = v.rscale8[row], rr = v.rres8[row];
+        const uint64_t am = v.alive[t];                                // wave-uniform
+        const long long isum = bound8_tile(plane + (size_t)t * steps * 64, qh, ql, steps);
+        float lo, hi;
+        (void)bound_scan_interval8<M>(isum, sq, qn, qres, rn, sc, rr, v.dim, lo, hi);
+        const bool live = (am >> lane) & 1ull;                         // (dead rows and the last tile's padding: never candidates, never in a bound)
+        __builtin_nontemporal_store(live ? ord_f32(lo) : 0xFFFFFFFFu, &lo_all[row]);
+        const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+        if (first) { list = wave_sort64(key, lane); thr = readlane64(list, kth); first = false; }
+        else list_insert(list, thr, key, kth, lane);
+    }
+    bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
+}
+
+// ---------------------------------------------------------------- the bound scan as a shared pass: 2 - 8 queries over the bfloat16 copy --
+// Callers that arrive together share a pass (qv_coalesce.h), and a pass of 2 - 8 queries read the float32 tiles (k_flat_scan_mq) while the
+// copy lay idle.  Here the copy is read ONCE for QB = 4 or 8 queries; interval, threshold, collect and exact re-score are the single-query
+// path's, per query, so the answers are the exact scan's bits.
+//   k_bound_prep_mq  the query block qblk[step][16][QB] in float32 (slots past nq: zeros) and |q_j| as the reference's float64 chain, once.
+//   k_bound_scan_mq  k_bound_scan's walk — lane == row, a wave owns whole tiles, the lane's two 16-byte halves per step, each bfloat16
+//                    widened once — with the query values as SCALAR operands (uniform loads of qblk: per dimension the QB values are
+//                    contiguous, so a query PAIR is one 64-bit scalar operand of a packed float32 fma whose two halves are two queries'
+//                    chains: 64 packed fmas + 16 widenings per step and lane at QB = 8 where one fma per query and element is 128 + 16).
+//                    Each (query, row) sum is still ONE in-order chain of dim fmas, one rounding each: qv_bound.h's gamma as it stands.
+//                    d_lo -> lo_all[q][n_tiles * 64]; d_hi -> per-query wave lists -> partial[q][grid][k], k_flat_scan_mq's layout.
+//   k_merge_lists    per query over its upper-bound lists: its k-th entry is H (valid: the row is a row and the bound is finite).
+//   k_bound_collect_mq / k_bound_rescore_mq   blockIdx.y / blockIdx.x = query: a candidate list, a counter (BoundCtrl::cand_cnt of its
+//                    own, left zero) and a hand-back flag per query.  A query is handed back on its own grounds; launch_flat_redo_flagged
+//                    behind the re-score redoes exactly the flagged ones with the exact scan, on the device.
+// (Measured: profiles/LAB_r08_bound_scan_mq.md.)
+constexpr uint32_t kBoundMqMax = 8;            // queries per shared pass (BoundCtrl x 8 behind kBoundCtrlWord fit the stream's 64 ticket words)
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+template <int QB>
+__global__ void __launch_bounds__(256)
+k_bound_prep_mq(const float* __restrict__ queries, uint32_t nq, uint32_t dim, float* __restrict__ qblk, double* __restrict__ qnorm, uint32_t* __restrict__ stats) {
+    __shared__ float s_q[kBoundMaxDim];
+    const uint32_t nb = gridDim.x - QB;                                // blocks [0, nb): the block; [nb, nb + QB): one query's norm each
+    if (blockIdx.x < nb) {
+        const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < dim * QB) {
+            const uint32_t j = i % QB, d = i / QB;
+            qblk[i] = j < nq ? queries[(size_t)j * dim + d] : 0.f;
+        }
+        if (i == 0) stats[0] = 0;                                      // the pass's largest survivor count (k_bound_rescore_mq)
+        return;
+    }
+    const uint32_t j = blockIdx.x - nb;
+    if (j >= nq) { if (threadIdx.x == 0) qnorm[j] = 0.0; return; }
+    for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) s_q[i] = queries[(size_t)j * dim + i];
+    __syncthreads();
+    if (threadIdx.x == 0) {                                            // the reference's chain (distances.go:20), as k_bound_rescore walks it
+        double ma = 0.0;
+        for (uint32_t i = 0; i < dim; i++) { const double a = (double)s_q[i]; ma = __builtin_fma(a, a, ma); }
+        qnorm[j] = __builtin_sqrt(ma);
+    }
+}
+
+template <int QB, int U>
+__device__ __forceinline__ void bound_block_mq(const u4* __restrict__ p, const float* __restrict__ qblk, uint32_t s0, f2 (&acc)[QB / 2]) {
+    u4 x[2 * U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        x[2 * u] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 128]);
+        x[2 * u + 1] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 128 + 32]);
+    }
+    __builtin_amdgcn_sched_barrier(0);                                 // all requests of the block ahead of the arithmetic (see row_accumulate)
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const f2* qq = reinterpret_cast<const f2*>(qblk + (size_t)(s0 + u) * 16 * QB);   // global, uniform -> scalar loads
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const u4 w = x[2 * u + h];
+            const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int g = 0; g < 4; g++) {                              // bfloat16 -> float32 is a shift / a mask: exact
+                const float r0 = __uint_as_float(ww[g] << 16), r1 = __uint_as_float(ww[g] & 0xFFFF0000u);
+                const f2 rr0 = {r0, r0}, rr1 = {r1, r1};
+#pragma unroll
+                for (int j = 0; j < QB / 2; j++) acc[j] = __builtin_elementwise_fma(qq[(h * 8 + g * 2) * (QB / 2) + j], rr0, acc[j]);
+#pragma unroll
+                for (int j = 0; j < QB / 2; j++) acc[j] = __builtin_elementwise_fma(qq[(h * 8 + g * 2 + 1) * (QB / 2) + j], rr1, acc[j]);
+            }
+        }
+    }
+}
+
+// SETS (k_bound_scan_mq<., ., true>: a pass under filters, query j restricted to am_j = alive & set_j): the sets' (bits, words) pairs arrive as kernel
+// arguments, as in k_rowset_scan_mq, and lane j keeps query j's — eight pairs held as scalars spilled 168 SGPRs there, and this kernel
+// already spends its scalar file on the packed-fma query operands.  rowset_word for the wave's NEXT tile is fetched while the current one is
+// walked and read back per query with readlane64 (wave-uniform again).  Bit `lane` of am_j gates query j's lower-bound word (a
+// non-candidate writes 0xFFFFFFFF) and its upper-bound key (kDeadKey), so H_j is the k-th smallest upper bound over query j's OWN
+// candidates and a set of fewer than k live rows has none (handed back).  A tile that no query selects is not requested — copy, rnorm,
+// rres —; its nq x 64 lower-bound words are written as 0xFFFFFFFF (256 bytes per query against dim * 128 of copy): k_bound_collect_mq
+// reads every word of a workspace that earlier searches have used, and stays as it is.  `first` is the first tile the wave READS.
+// The interval arithmetic is untouched.  A masked call (one bitmap for all queries, in v.alive) is this form with a table of null sets.
+template <int M, int QB, bool SETS = false>
+__global__ void __launch_bounds__(kScanBlock, 2)
+k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __restrict__ qnorm, uint32_t nq, uint32_t k,
+                uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */, SetsArg<SETS> tab) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64]
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves, kth = k - 1;
+    const size_t n = (size_t)v.n_tiles * 64;
+    const double gamma = bound_scan_gamma(v.dim);
+    const u4* plane = reinterpret_cast<const u4*>(v.plane) + ((lane >> 5) * 64 + (lane & 31));
+    uint64_t list[QB], thr[QB];
+    double qn[QB];
+#pragma unroll
+    for (int j = 0; j < QB; j++) { list[j] = kDeadKey; thr[j] = kDeadKey; qn[j] = qnorm[j]; }
+    bool first = true;
+    const bool mine = SETS && lane < nq;
+    RowSetRef rs = RowSetRef{nullptr, 0, 0};
+    uint64_t w_next = 0ull;
+    if constexpr (SETS) {
+        static_assert(QB <= (int)kBoundSets, "one table entry per query of the pass");
+        rs = tab.e[mine ? lane : 0u];                                 // lane j: query j's set
+        const uint32_t t0 = blockIdx.x * kScanWaves + wave;
+        if (t0 < v.n_tiles) w_next = rowset_word(v.alive, rs, mine, t0);
+    }
+    for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+        const uint64_t w = w_next;                                     // (SETS) lane j: am_j of this tile
+        if constexpr (SETS) {
+            if (t + tw < v.n_tiles) w_next = rowset_word(v.alive, rs, mine, t + tw);
+            if (__ballot(w != 0ull) == 0ull) {                         // nobody's candidate in this tile
+#pragma unroll
+                for (int j = 0; j < QB; j++)
+                    if ((uint32_t)j < nq) __builtin_nontemporal_store(0xFFFFFFFFu, &lo_all[(size_t)j * n + t * 64 + lane]);
+                continue;
+            }
+        }
+        f2 acc[QB / 2];
+#pragma unroll
+        for (int j = 0; j < QB / 2; j++) acc[j] = f2{0.f, 0.f};
+        const u4* p = plane + (size_t)t * steps * 128;
+        uint32_t s = 0;
+        for (; s + 8 <= steps; s += 8) bound_block_mq<QB, 8>(p, qblk, s, acc);
+        if (s + 4 <= steps) { bound_block_mq<QB, 4>(p, qblk, s, acc); s += 4; }
+        if (s + 2 <= steps) { bound_block_mq<QB, 2>(p, qblk, s, acc); s += 2; }
+        if (s < steps) bound_block_mq<QB, 1>(p, qblk, s, acc);
+        const uint32_t row = t * 64 + lane;
+        const double rn = v.rnorm[row];
+        const float rr = v.rres[row];
+        bool live_all = false;
+        if constexpr (!SETS) live_all = (v.alive[t] >> lane) & 1ull;   // (dead rows and the last tile's padding: never candidates, never in a bound)
+#pragma unroll
+        for (int j = 0; j < QB; j++) {
+            if ((uint32_t)j < nq) {                                    // (uniform) slots past nq produce nothing
+                bool live;
+                if constexpr (SETS) live = (readlane64(w, (uint32_t)j) >> lane) & 1ull; else live = live_all;
+                float lo, hi;
+                (void)bound_scan_interval<M>((j & 1) ? acc[j / 2].y : acc[j / 2].x, qn[j], rn, rr, v.dim, gamma, lo, hi);
+                __builtin_nontemporal_store(live ? ord_f32(lo) : 0xFFFFFFFFu, &lo_all[(size_t)j * n + row]);
+                const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+                if (first) { list[j] = wave_sort64(key, lane); thr[j] = readlane64(list[j], kth); }
+                else list_insert(list[j], thr[j], key, kth, lane);
+            }
+        }
+        first = false;
+    }
+#pragma unroll
+    for (int j = 0; j < QB; j++) wl[((size_t)wave * QB + j) * 64 + lane] = list[j];
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int j = 0; j < QB; j++) {
+            if ((uint32_t)j < nq) {
+                for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list[j], thr[j], lane < k ? wl[((size_t)w * QB + j) * 64 + lane] : kDeadKey, kth, lane);
+                if (lane < k) partial[((size_t)j * gridDim.x + blockIdx.x) * k + lane] = list[j];
+            }
+        }
+    }
+}
+
+// H of query blockIdx.y: the k-th entry of its merged upper-bound list (seed_rows / seed_dist [nq][k])
+__global__ void __launch_bounds__(256)
+k_bound_collect_mq(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, uint32_t k, const uint32_t* __restrict__ seed_rows, const float* __restrict__ seed_dist,
+                   BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand) {
+    const uint32_t j = blockIdx.y;
+    const uint32_t H = ord_f32(seed_dist[(size_t)j * k + k - 1]);
+    if (seed_rows[(size_t)j * k + k - 1] == 0xFFFFFFFFu || H >= 0xFF800000u) return;   // no H: k_bound_rescore_mq hands the query back
+    bound_collect(lo_all + (size_t)j * n, n, H, &ctrl[j].cand_cnt, cand + (size_t)j * kBoundCandCap);
+}
+
+template <int M>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_rescore_mq(IndexView v, const float* __restrict__ queries, uint32_t k, const uint32_t* __restrict__ seed_rows, const float* __restrict__ seed_dist,
+                   BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand, uint32_t* __restrict__ flags, uint32_t* __restrict__ stats,
+                   uint32_t* __restrict__ rows_out, float* __restrict__ dist_out) {
+    const uint32_t j = blockIdx.x;
+    const uint32_t cnt = ctrl[j].cand_cnt;
+    const bool has_H = seed_rows[(size_t)j * k + k - 1] != 0xFFFFFFFFu && ord_f32(seed_dist[(size_t)j * k + k - 1]) < 0xFF800000u;
+    bound_rescore_query<M>(v, queries + (size_t)j * v.dim, k, cnt, has_H, cand + (size_t)j * kBoundCandCap, rows_out + (size_t)j * k, dist_out + (size_t)j * k, [&](bool hand_back) {
+        (void)atomicMax(&stats[0], cnt);
+        if (hand_back) (void)atomicAdd(&stats[1], 1u);
+        (void)atomicAdd(&stats[2], 1u);
+        flags[j] = hand_back ? 1u : 0u;                                // launch_flat_redo_flagged behind this launch reads them
+        ctrl[j].cand_cnt = 0;                                          // zero, as the words are kept
+    });
+}
+
+// The bound scan (k_bound_scan / k_bound_rescore above): one query, a fused-list k, cosine or dot, the bfloat16 copy at hand, a width the copy
+// covers in whole 16-dimension steps.  Automatic from kBoundScanMinRows rows (measured: profiles/LAB_r07_bound_scan.md); the index's setter
+// (IndexView::bound_scan) or QV_BOUND_SCAN = 1 takes it whenever it applies, 2 never.
+// 2 - 8 queries (k_bound_scan_mq): the same conditions, and nq planes of lower bounds that stay under 2 GiB.  Its automatic rule is a floor on
+// rows that depends on the width — every query pays 8 bytes per row for its lower bounds whatever the width — per QB: the smallest measured
+// shape from which the path wins at every measured nq and k of that QB (profiles/LAB_r08_bound_scan_mq.md); narrower than
+// kBoundMqNarrowDim it is never automatic.
+constexpr uint32_t kBoundScanMinRows = 300000;   // one query, us, exact / bound scan at k = 1, 10, 64: 100 k x 768 65 / 63, 66 / 70, 86 / 122; 300 k x 768 154 / 107, 158 / 114, 190 / 169; 1M x 128 89 / 64, 93 / 68, 134 / 114
+// us per call, exact (k_flat_scan_mq) / bound, at k = 1, 10, 64:
+//   QB = 4   300 k x 768  nq 2: 195 / 154, 204 / 160, 273 / 223; nq 4: 193 / 160, 207 / 175, 276 / 271      1M x 128  nq 4: 97 / 93, 117 / 103, 214 / 216 (a loss)
+//            10M x 128    nq 2: 781 / 527, 793 / 532, 907 / 593; nq 4: 790 / 575, 793 / 587, 913 / 711
+//   QB = 8   300 k x 768  nq 8: 232 / 233, 254 / 264, 370 / 427 (losses)      1M x 768  nq 5: 526 / 449, 545 / 464, 695 / 598; nq 8: 526 / 456, 542 / 473, 697 / 694
+//            1M x 128     nq 8: 122 / 124, 145 / 157, 330 / 367 (losses)      10M x 128 nq 5: 888 / 638, 892 / 657, 1162 / 849; nq 8: 869 / 734, 905 / 775, 1161 / 1093
+constexpr uint32_t kBoundMqMinDim = 768, kBoundMqMinRows4 = 300000, kBoundMqMinRows8 = 1000000;   // rows of at least 768 dimensions: QB = 4 (2 - 4 queries), QB = 8 (5 - 8)
+constexpr uint32_t kBoundMqNarrowDim = 128, kBoundMqNarrowRows = 10000000;                        // 128 <= dim < 768 (nothing between was measured): both QB
+int bound_scan_mode(int mode) { static const int env_mode = env_int("QV_BOUND_SCAN", 0); return mode ? mode : env_mode; }
+bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane) {
+    mode = bound_scan_mode(mode);
+    const uint32_t n_tiles = (n_rows + 63) / 64;
+    if (mode == 2 || nq < 1 || nq > kBoundMqMax || k < 1 || k > (uint32_t)kMaxFusedK || (metric != QV_COSINE && metric != QV_DOT) || !has_plane) return false;
+    if ((dim & 15u) != 0 || dim > kBoundMaxDim || n_tiles < 8) return false;
+    if (nq == 1) return mode == 1 || n_rows >= kBoundScanMinRows;
+    if ((uint64_t)nq * n_tiles * 256 > (2ull << 30)) return false;
+    const uint32_t min_rows = dim >= kBoundMqMinDim ? (nq <= 4 ? kBoundMqMinRows4 : kBoundMqMinRows8) : kBoundMqNarrowRows;
+    return mode == 1 || (dim >= kBoundMqNarrowDim && n_rows >= min_rows);
+}
+bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) { return bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr); }
+// The 8-bit stage in front of it (k_bound_scan8): one unfiltered query the bound scan takes, on an index that holds the 8-bit plane.  The index's
+// plane setter (IndexView::bound_plane) or QV_BOUND_PLANE = 1 puts it first whenever that holds, 2 never; automatic from the smallest
+// measured row count from which 8-bit-first beats bfloat16-first at every measured k — never below kBoundScanMinRows, so a corpus under
+// that floor runs what it ran before whatever mode forces the bound scan itself.  profiles/LAB_r10_bound_scan_8bit.md; us per query,
+// bfloat16 first / 8-bit first, at k = 1, 10, 64 (the 8-bit stage passes on 3 - 4 times the rows, and one workgroup walks them: its
+// k = 64 figures carry 0.1 - 0.15 ms of re-score):
+//   768 dims   300 k 109 / 106, 117 / 124, 173 / 276 (losses)   1M 275 / 188, 277 / 209, 339 / 361 (a loss at k = 64)
+//              3M 752 / 436, 737 / 456, 799 / 618                10M 2386 / 1263, 2352 / 1269, 2417 / 1457
+//   128 dims   1M 62 / 53, 66 / 58, 111 / 113 (a loss at k = 64)  10M 457 / 259, 462 / 265, 502 / 318
+// narrower than kBound8NarrowDim nothing was measured: never automatic.
+constexpr uint32_t kBound8MinDim = 768, kBound8MinRows = 3000000;            // rows of at least 768 dimensions
+constexpr uint32_t kBound8NarrowDim = 128, kBound8NarrowRows = 10000000;     // 128 <= dim < 768 (nothing between was measured)
+static_assert(kBound8MinRows >= kBoundScanMinRows && kBound8NarrowRows >= kBoundScanMinRows, "the 8-bit floors are never below the bound scan's");
+static int bound_plane_mode(int mode) { static const int env_mode = env_int("QV_BOUND_PLANE", 0); return mode ? mode : env_mode; }
+bool bound_scan8_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode, bool has_plane8) {
+    plane_mode = bound_plane_mode(plane_mode);
+    if (plane_mode == 2 || nq != 1 || !has_plane8 || !bound_scan_rule(metric, dim, n_rows, 1, k, mode, true)) return false;
+    return plane_mode == 1 || (dim >= kBound8NarrowDim && n_rows >= (dim >= kBound8MinDim ? kBound8MinRows : kBound8NarrowRows));
+}
+bool bound_scan8_applies(const IndexView& v, uint32_t nq, uint32_t k) {
+    return v.plane != nullptr && bound_scan8_rule(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane, v.plane8 != nullptr);
+}
+// Under a filter (a candidate bitmap in v.alive, or a row set per query): candidate_tiles = the tiles that hold a candidate of any query of
+// the pass, as the host knows it without a device read (an upper bound: sets count their non-empty words, tombstones are not subtracted, a pass
+// takes min(n_tiles, the sum over its queries) — so eight queries naming ONE striped set look like eight distinct ones).  "always" takes
+// the path whenever the unfiltered conditions hold, "never" never.  Automatic: the cells of profiles/LAB_r09_bound_scan_filtered.md in which
+// "always" beat the exact filtered scan by more than both arms' spread at k = 10 AND 64 (or, where said, at k = 10 only), for every kind of
+// set that maps to the same host-side inputs; measured at 768 dimensions only, so narrower rows are declined; no floor below the
+// unfiltered ones.  us per call, exact / bound, 768 dims, k = 10 and 64 (f = candidate_tiles / tiles as the host computes it):
+//   one query     300 k: f 1.0 167 / 125, 201 / 181; one tile in ten 167 / 64, 201 / 122       1M: f 1.0 460 / 286, 496 / 349; one tile in ten 457 / 80, 489 / 137
+//   QB = 4        300 k: nq 2 170 / 166, 212 / 230; nq 4 176 / 179, 250 / 274 (losses: declined below 1M)
+//                 1M: f >= 0.9 nq 2 466 / 331, 506 / 398; nq 4 472 / 355, 551 / 451; striped sets (f 0.2 / 0.4) nq 2 126 / 141, nq 4 same set 111 / 140 (losses)
+//                 10M: nq 2 4406 / 2496; nq 4 4406 / 2670; striped (f 0.2) nq 2 1251 / 697, same set 671 / 439
+//   QB = 8 (nq 8) 1M: f 1.0 k = 10 557 / 486, density 0.01 one set 455 / 429; k = 64 740 / 702 but density 0.01 one set 477 / 495 (a loss with the same
+//                 inputs: k > 10 declined); striped f 0.8 distinct 416 / 390, one set 171 / 226 (a loss: f < 0.9 declined)
+//                 10M: f 1.0 5044 / 3819, 5373 / 4088; striped f 0.8 distinct 2806 / 2323, one set 912 / 917 (a loss: f < 0.9 declined)
+//   nq 3 and 5 - 7 were not run: the bound pass gets cheaper with fewer queries (a lower-bound plane and a collect each) while the exact pass of
+//   a QB costs the same at any fill (LAB_r08: 526 / 526 us at nq 5 / 8), so they are bracketed by the nq = 4 and nq = 8 cells.
+constexpr uint32_t kBoundFiltMinDim = 768, kBoundFiltMqRows = 1000000, kBoundFiltBigRows = 10000000, kBoundFiltQb8SmallK = 10;
+bool bound_scan_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane, uint32_t candidate_tiles) {
+    mode = bound_scan_mode(mode);
+    if (mode == 2 || !bound_scan_rule(metric, dim, n_rows, nq, k, 1, has_plane)) return false;
+    if (mode == 1) return true;
+    const uint64_t n_tiles = ((uint64_t)n_rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
+    if (ct == 0 || dim < kBoundFiltMinDim || !bound_scan_rule(metric, dim, n_rows, nq, k, 0, has_plane)) return false;   // (never below the unfiltered floors)
+    if (nq == 1) return ct * 10 >= n_tiles;                                                      // from kBoundScanMinRows rows; one tile in ten is the sparsest measured
+    if (n_rows < kBoundFiltMqRows) return false;
+    if (nq <= 4) return n_rows >= kBoundFiltBigRows ? ct * 5 >= n_tiles : ct * 10 >= n_tiles * 9;
+    return ct * 10 >= n_tiles * 9 && (n_rows >= kBoundFiltBigRows || k <= kBoundFiltQb8SmallK);
+}
+bool bound_scan_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
+    return bound_scan_rule_filtered(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr, candidate_tiles);
+}
+size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles) {
+    return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)n_tiles * 64 * sizeof(uint32_t);
+}
+hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
+                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked, bool plane8_first) {
+    // (whether the path is TAKEN is plan_flat's decision; here only what the kernels need: metric, width, the copy, k — bound_scan_rule's "always")
+    if (!bound_scan_rule(v.metric, v.dim, v.n_rows, 1, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    if (plane8_first && (masked || !v.plane8)) return hipErrorInvalidValue;
+    const uint32_t grid = p.grid;
+    char* w = static_cast<char*>(d_ws);
+    uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256;
+    uint32_t* seed_rows = reinterpret_cast<uint32_t*>(w); w += 256;
+    float* seed_dist = reinterpret_cast<float*>(w); w += 256;
+    uint32_t* cand = reinterpret_cast<uint32_t*>(w); w += (size_t)kBoundCandCap * sizeof(uint32_t);
+    uint32_t* lo_all = reinterpret_cast<uint32_t*>(w);
+    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
+    BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
+    const size_t lds1 = (size_t)v.dim * sizeof(float) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    const size_t lds8 = (size_t)v.dim * 2 + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    auto run = [&](auto Mc) -> hipError_t {
+        constexpr int M = decltype(Mc)::value;
+        // one stage on the control words c: its scan, the collect, the re-score.  gate: the flag of the stage in front (null: none);
+        // next: the stage behind, whose flag an answering 8-bit stage clears; scan_gate: k_bound_scan's own gate argument (k_bound_scan8 has none)
+        // (attrs: the dynamic LDS of a stage's two kernels, for every stage before anything is launched — a call that fails enqueues nothing)
+        auto attrs = [&](auto scan, size_t lds_scan, auto rescore) -> hipError_t {
+            const hipError_t e = set_lds(scan, lds_scan);
+            return e != hipSuccess ? e : set_lds(rescore, lds2);
+        };
+        auto stage = [&](auto scan, size_t lds_scan, auto rescore, BoundCtrl* c, uint32_t* gate, BoundCtrl* next, auto... scan_gate) {
+            hipLaunchKernelGGL(scan, dim3(grid), dim3(kScanBlock), lds_scan, s, v, d_query, k, c, lo_all, partial, seed_rows, seed_dist, scan_gate...);
+            hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, c, cand, (const uint32_t*)gate);
+            hipLaunchKernelGGL(rescore, dim3(1), dim3(kScanBlock), lds2, s, v, d_query, k, c, cand, d_stats, d_rows_out, d_dist_out, gate, next);
+        };
+        const uint32_t* const no_gate = nullptr;
+        hipError_t e = masked ? attrs(k_bound_scan<M, true>, lds1, k_bound_rescore<M>) : attrs(k_bound_scan<M>, lds1, k_bound_rescore<M>);
+        if (e == hipSuccess && plane8_first) e = attrs(k_bound_scan8<M>, lds8, k_bound_rescore<M, true>);
+        if (e != hipSuccess) return e;
+        if (plane8_first) {
+            // the 8-bit stage on the second set of control words, in the same workspace (the stages run one after the other); the bfloat16 stage
+            // behind it is gated on that stage's flag and leaves at once when it has answered
+            BoundCtrl* ctrl8 = ctrl + 1;
+            uint32_t* gate8 = &ctrl8->flag;
+            stage(k_bound_scan8<M>, lds8, k_bound_rescore<M, true>, ctrl8, (uint32_t*)nullptr, ctrl);
+            stage(k_bound_scan<M>, lds1, k_bound_rescore<M>, ctrl, gate8, (BoundCtrl*)nullptr, (const uint32_t*)gate8);
+        } else if (masked) stage(k_bound_scan<M, true>, lds1, k_bound_rescore<M>, ctrl, (uint32_t*)nullptr, (BoundCtrl*)nullptr, no_gate);
+        else stage(k_bound_scan<M>, lds1, k_bound_rescore<M>, ctrl, (uint32_t*)nullptr, (BoundCtrl*)nullptr, no_gate);
+        return hipSuccess;
+    };
+    const hipError_t e = v.metric == QV_COSINE ? run(std::integral_constant<int, QV_COSINE>{}) : run(std::integral_constant<int, QV_DOT>{});
+    if (e != hipSuccess) return e;
+    *gate_out = &ctrl->flag;
+    return hipGetLastError();
+}
+// the interval of one row on the host; 1: a row the bound says nothing about ("unsure"), as host_bound_interval8 reports it
+int host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {
+    const double gamma = bound_scan_gamma(dim);
+    const bool sure = metric == QV_COSINE ? bound_scan_interval<QV_COSINE>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi) : bound_scan_interval<QV_DOT>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi);
+    return sure ? 0 : 1;
+}
+
+int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, float* d_lo, float* d_hi) {
+    const bool sure = metric == QV_COSINE ? bound_scan_interval8<QV_COSINE>(isum, sq, qn, qres, rn, rscale, rres8, dim, *d_lo, *d_hi)
+                                          : bound_scan_interval8<QV_DOT>(isum, sq, qn, qres, rn, rscale, rres8, dim, *d_lo, *d_hi);
+    return sure ? 0 : 1;
+}
+// one row as k_row_state8 (qv_misc.hip) leaves it: the bytes, the scale, the residual from the bytes (NaN: a row the bound says nothing about)
+int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res) {
+    float maxabs = 0.f; bool bad = false; double n2 = 0.0;
+    for (uint32_t i = 0; i < dim; i++) {
+        bad |= !((row[i] - row[i]) == 0.0f);
+        maxabs = __builtin_fmaxf(maxabs, __builtin_fabsf(row[i]));
+        n2 = __builtin_fma((double)row[i], (double)row[i], n2);
+    }
+    const float scale = bad ? 0.0f : bound8_scale(maxabs);
+    double s2 = 0.0;
+    for (uint32_t i = 0; i < dim; i++) {
+        const int b = scale > 0.0f ? bound8_quant(row[i], scale) : 0;
+        const double d = (double)row[i] - (double)scale * (double)b;
+        s2 = __builtin_fma(d, d, s2);
+        out_bytes[i] = (int8_t)b;
+    }
+    *out_scale = scale;
+    *out_res = bound8_row_res(bad, maxabs, n2, s2, dim);
+    return 0;
+}
+int host_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8) {
+    return bound_scan8_rule(metric, dim, rows, nq, k, mode, plane_mode, has_plane8 != 0) ? 1 : 0;
+}
+
+// the shared pass of 2 - 8 queries: d_ws = bound_scan_mq_workspace_bytes, d_ctrl = kBoundMqMax BoundCtrl (zero, left zero).  The exact scan of the
+// queries handed back is part of it (launch_flat_redo_flagged, in the bytes the lower bounds leave behind): nothing is read on the host.
+static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim) {
+    return up256((size_t)nq * p.grid * k * sizeof(uint64_t)) + 2 * up256((size_t)kBoundMqMax * 64 * 4) + 256 + 256 + up256((size_t)dim * kBoundMqMax * sizeof(float)) +
+           std::max((size_t)nq * kBoundCandCap * sizeof(uint32_t) + (size_t)nq * n_tiles * 64 * sizeof(uint32_t), redo_workspace_bytes(p, nq, k));
+}
+hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
+                                uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets) {
+    // h_sets (optional, a HOST array of nq): query j restricted to alive & h_sets[j] — k_bound_scan_mq<., ., true> and the set-carrying redo.
+    // Null: the unfiltered pass.  (Whether the path is TAKEN is the caller's decision — plan_flat, or the row-set path's one question to
+    // bound_scan_applies_filtered; here only what the kernels need: metric, width, the copy, k, nq planes of lower bounds under 2 GiB.)
+    if (nq < 2 || !bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    BoundSetTable tab;
+    for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
+    if (h_sets && trace_filtered()) fprintf(stderr, "qv: scan kernel = k_bound_scan_mq sets QB=%d (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
+    const uint32_t grid = p.grid;
+    char* w = static_cast<char*>(d_ws);
+    uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += up256((size_t)nq * grid * k * sizeof(uint64_t));
+    uint32_t* seed_rows = reinterpret_cast<uint32_t*>(w); w += up256((size_t)kBoundMqMax * 64 * 4);
+    float* seed_dist = reinterpret_cast<float*>(w); w += up256((size_t)kBoundMqMax * 64 * 4);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(w); w += 256;
+    double* qnorm = reinterpret_cast<double*>(w); w += 256;
+    float* qblk = reinterpret_cast<float*>(w); w += up256((size_t)v.dim * kBoundMqMax * sizeof(float));
+    void* redo_ws = w;                                                 // (cand and lo_all are dead once the re-score has run)
+    uint32_t* cand = reinterpret_cast<uint32_t*>(w); w += (size_t)nq * kBoundCandCap * sizeof(uint32_t);
+    uint32_t* lo_all = reinterpret_cast<uint32_t*>(w);
+    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
+    BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
+    const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    hipError_t e = hipSuccess;
+#define QV_BOUND_MQ(MMM, QQ)                                                                                                 \
+    {                                                                                                                         \
+        const size_t lds1 = (size_t)kScanWaves * QQ * 64 * sizeof(uint64_t);                                                  \
+        e = set_lds(k_bound_rescore_mq<MMM>, lds2); if (e != hipSuccess) return e;                                            \
+        hipLaunchKernelGGL((k_bound_prep_mq<QQ>), dim3((v.dim * QQ + 255) / 256 + QQ), dim3(256), 0, s, d_queries, nq, v.dim, qblk, qnorm, d_stats); \
+        if (h_sets) hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, tab); \
+        else hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, NoSets{}); \
+        e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s); if (e != hipSuccess) return e;                 \
+        hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand); \
+        hipLaunchKernelGGL((k_bound_rescore_mq<MMM>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out); \
+    }
+    if (v.metric == QV_COSINE) { if (nq <= 4) QV_BOUND_MQ(QV_COSINE, 4) else QV_BOUND_MQ(QV_COSINE, 8) }
+    else { if (nq <= 4) QV_BOUND_MQ(QV_DOT, 4) else QV_BOUND_MQ(QV_DOT, 8) }
+#undef QV_BOUND_MQ
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_flat_redo_flagged(v, p, d_queries, nq, k, k, flags, redo_ws, d_rows_out, d_dist_out, s, h_sets);
+}
+int host_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles) {
+    return bound_scan_rule_filtered(metric, dim, rows, nq, k, mode, has_plane != 0, candidate_tiles) ? 1 : 0;
+}
+int host_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane) { return bound_scan_rule(metric, dim, rows, nq, k, mode, has_plane != 0) ? 1 : 0; }
+
+}  // namespace qv

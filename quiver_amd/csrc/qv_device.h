@@ -1,5 +1,5 @@
 // qv_device.h — internal interface between the C-ABI layer (qv_api.cpp) and the
-// gfx950 kernels (qv_scan/qv_rank/qv_batched/qv_hnsw/qv_misc.hip; shared helpers in qv_kernels.h).  Not installed; include/qv.h is the public ABI.
+// gfx950 kernels (qv_scan/qv_bound_scan/qv_rank/qv_batched/qv_hnsw/qv_misc.hip; shared helpers in qv_kernels.h).  Not installed; include/qv.h is the public ABI.
 //
 // HBM layout of an index ("row tiles", the SoA layout of DESIGN.md §3):
 //   tiles   float  [n_tiles][dim4][64][4]   tile t holds rows 64t..64t+63; within a
@@ -42,7 +42,7 @@ struct IndexView {
     int       metric;
     int       filter;     // batched path's filter kernel: 0 = the library's rule, 1 fp32 MFMA chain, 2 bfloat16 x 3, 3 bfloat16 x 1 (qv_index_set_filter)
     uint16_t* plane;      // may be null: the same bfloat16 copy whenever the index keeps one — cosine and dot indexes do by default, for the
-                          // single-query bound scan (qv_bound.hip); `bf16` above is set only under QV_FLAG_BF16_ROWS, so the batched path's
+                          // single-query bound scan (qv_bound_scan.hip); `bf16` above is set only under QV_FLAG_BF16_ROWS, so the batched path's
                           // choice of kernels is what the flag alone decides.  The calls that write rows refresh `plane`.
     int       bound_scan; // qv_index_set_bound_scan: 0 from the measured row count on, 1 whenever it applies, 2 never
     int8_t*   plane8;     // may be null: the int8 copy of the rows, [tile][dim/16][64 rows][16 values], one scale per row (k_row_state8);
@@ -139,13 +139,49 @@ hipError_t launch_fetch_rows(const IndexView& v, const uint32_t* d_rows, uint32_
 // ev0/ev1 (optional): recorded immediately before/after the scan kernel on `s`.
 // d_tickets (optional): 64 zeroed words that belong to the caller's stream alone — with them a single query is ONE launch (the last
 // workgroup of the scan merges the lists); without, scan + k_merge_lists.
-hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k,
+// Which kernels answer the call is decided ONCE, by plan_flat, before the first launch (the batched path's plan_batched / BatchedRoute
+// is the model): the launch, the workspace sizes (qv_api.cpp) and the QV_TRACE lines read the plan.  The routes in priority order:
+enum class FlatRoute : int {
+    small = 0,      // no bound route, tickets, flat_small_applies and not flat_split_applies: k_flat_scan_small, scan + merge in one launch
+    bound_mq,       // 2 - 8 queries, tickets and counters, the bound rule takes them (filtered: its filtered form), and "always" or no short-corpus
+                    // form: launch_bound_scan_mq, one pass over the bfloat16 copy, the exact redo of hand-backs behind it
+    split_mq,       // 2 or more queries, flat_split_mq_applies: k_flat_scan_split_mq + k_merge_lists
+    mq64,           // 9 or more cosine / dot queries over 16 tiles per wave or more: launch_flat_scan_mq64 + k_merge_lists
+    mq,             // 2 or more queries: k_flat_scan_mq, qb = 4 / 8 / 16 per corpus pass (16 never for the all-float32 metrics) + k_merge_lists
+    bound,          // one query, tickets and counters, the bound rule takes it: launch_bound_scan and the gated exact scan behind it
+    bound8_first,   // ... unfiltered and bound_scan8_applies: the 8-bit stage in front
+    split,          // tickets, flat_split_applies: k_flat_scan_split, a tile over eight waves
+    fused,          // one query, tickets, more than one workgroup: k_flat_scan<., ., true>, the last workgroup merges
+    two_launch,     // everything else: k_flat_scan + k_merge_lists
+};
+struct FlatPass {                   // what one pass over the corpus is launched from
+    FlatRoute route = FlatRoute::two_launch;
+    uint32_t  qb = 0;               // queries per corpus pass (bound_mq, split_mq, mq)
+    bool      filtered = false;     // v.alive is a filter's candidate bitmap: the bound routes' forms that skip tiles without a candidate
+};
+struct FlatPlan : FlatPass {        // the call's pass; mq64 with more than 32 queries of which the last 1 - 8 are split off: the pass of
+    uint32_t rem = 0;               // the first nq - rem, and the pass of the last rem behind it (never a bound route)
+    FlatPass tail;
+    bool bound() const { return route == FlatRoute::bound_mq || route == FlatRoute::bound || route == FlatRoute::bound8_first; }
+};
+// tickets / stats: the call carries the stream's ticket words / the index's bound-scan counters; candidate_tiles: kBoundNoFilter, or the
+// tiles that hold a candidate of a filtered call (an upper bound known on the host)
+FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k, bool tickets, bool stats, uint32_t candidate_tiles);
+// plan_flat without an index or a device (qv_scan_route): the route's number, < 0 for arguments no route serves
+int host_flat_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
+                    uint32_t candidate_tiles);
+// f = plan_flat for the same v, p, nq, k, d_tickets != null, d_bound_stats != null and candidate_tiles.  d_ws: the route's share of qv_api.cpp's
+// search_ws_bytes, which is sized from the same plan.
+hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const FlatPlan& f, const float* d_queries, uint32_t nq, uint32_t k,
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
                             hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, uint32_t* d_tickets = nullptr,
-                            uint32_t* done_flag = nullptr, uint32_t done_seq = 0, bool* flag_used = nullptr,   // done_flag: see launch_flat_small (k_flat_scan_split only)
-                            uint32_t* d_bound_stats = nullptr,   // the index's bound-scan counters: with them (and tickets) a single query may take launch_bound_scan
+                            uint32_t* done_flag = nullptr, uint32_t done_seq = 0, bool* flag_used = nullptr,   // done_flag: see launch_flat_small (small, split and fused)
+                            uint32_t* d_bound_stats = nullptr,   // the index's bound-scan counters (the bound routes)
                             uint32_t candidate_tiles = 0xFFFFFFFFu);   // not kBoundNoFilter: v.alive is a filter's candidate bitmap with at most so many non-empty tiles
-// The single-query scan on the bfloat16 copy (qv_bound.hip): stage 1 streams v.plane and lists the rows whose certified lower bound of
+// ... for callers without tickets (the batched path's sample scan): routes split_mq, mq64, mq or two_launch
+hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k,
+                            void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+// The single-query scan on the bfloat16 copy (qv_bound_scan.hip): stage 1 streams v.plane and lists the rows whose certified lower bound of
 // the distance is within the k-th smallest upper bound, stage 2 computes those rows' distances in the scan's own arithmetic and writes
 // the k results, or sets *gate (a device word) when the exact scan must answer instead; the caller then issues the exact scan with that
 // gate (it leaves at once when the word is zero).  d_ctrl: the stream's zeroed control words (kept zero); d_stats: the index's counters.
@@ -167,11 +203,12 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
                                 const RowSetRef* h_sets = nullptr);   // a HOST array of nq sets, at most 8: query j over alive & h_sets[j] (k_bound_scan_mq<., ., true>, the redo included)
 // bound_scan_applies without an index (qv_scan_bound_applies): mode 0 = automatic (QV_BOUND_SCAN decides), 1 always, 2 never
 bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane);
+int bound_scan_mode(int mode);   // the mode in force: the index's own, else QV_BOUND_SCAN (read once)
 int host_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane);
 bool bound_scan_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane, uint32_t candidate_tiles);
 int host_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles);
-// the interval of one row on the HOST (qv_scan_bound_interval): qv_bound.h's function compiled for the CPU
-float host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi, int* unsure);
+// the interval of one row on the HOST (qv_scan_bound_interval): qv_bound.h's function compiled for the CPU; 1 = a row the bound says nothing about
+int host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi);
 // The 8-bit stage in front of it (k_bound_scan8): the same chain over v.plane8; a search it cannot decide goes to the bfloat16 stage, which
 // runs gated behind it.  plane_mode: QV_BOUND_PLANE_* (0 automatic: QV_BOUND_PLANE decides, 1 the 8-bit stage whenever it applies, 2 never).
 bool bound_scan8_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode, bool has_plane8);
@@ -181,7 +218,7 @@ int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, do
 int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res);
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches
 constexpr uint32_t kBoundCtrlWord = 16;   // the bound scan's control words start here in the stream's 64 ticket words
-bool flat_split_applies(const IndexView& v, uint32_t nq, uint32_t k);   // launch_flat_topk will take the tile-over-eight-waves form (given tickets)
+bool flat_split_applies(const IndexView& v, uint32_t nq, uint32_t k);   // the tile-over-eight-waves form's own conditions (plan_flat: route split, given tickets)
 // The exact scan (k <= kMaxFusedK) for exactly the queries whose d_flags word is non-zero — the ones a filter handed back —, listed and
 // scanned on the device: nothing is read back.  Results replace rows / distances [q][k_stride] of those queries.  d_ws: redo_workspace_bytes.
 size_t redo_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k);

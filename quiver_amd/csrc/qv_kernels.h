@@ -385,5 +385,189 @@ template <typename F> static inline hipError_t set_lds(F f, size_t bytes) {
         default: return hipErrorInvalidValue;                    \
     }
 
+// QV_TRACE for the filtered paths' lines: read per call, as launch_rowset_topk reads it (a getenv beside a launch of several kernels), so that
+// a process can switch the trace on after its first search; the unfiltered lines keep their one read per process
+static inline bool trace_filtered() { return env_int("QV_TRACE", 0) != 0; }
+
+// ---------------------------------------------------------------- merge of per-workgroup lists --
+__device__ __forceinline__ uint64_t wave_min64(uint64_t x) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        uint32_t lo = __shfl_xor((uint32_t)x, off), hi = __shfl_xor((uint32_t)(x >> 32), off);
+        uint64_t y = ((uint64_t)hi << 32) | lo;
+        x = y < x ? y : x;
+    }
+    return x;
+}
+
+// One workgroup per query merges n_lists sorted lists of k keys into the final top-k.
+// Bound trick: the smallest k-th entry over all lists, B, is an upper bound of the final
+// k-th key (that list alone holds k keys <= B), so only keys <= B can be in the answer.
+// Typically a few dozen of the n_lists*k keys survive; one wave insertion-sorts them.
+constexpr int kMergeBlock = 1024;
+constexpr int kMergeCap = 2048;                       // survivors kept in LDS; more -> general path
+constexpr int kMergeHeads = 128;                      // sampled list heads ranked in LDS
+
+// The merge itself, for one query: src = its n_lists lists of k keys, rows_out / dist_out = its k results.  AT: the lists were
+// published by other workgroups of the SAME launch (returning atomic exchanges, then a ticket: k_flat_scan<., ., true>) and are read
+// with agent-scope atomic loads; otherwise by an earlier launch, and plain loads do.
+template <bool AT>
+__device__ void merge_lists_body(const uint64_t* __restrict__ src, uint32_t n_lists, uint32_t k, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out,
+                                 uint32_t* done_flag = nullptr, uint32_t done_seq = 0) {
+    auto ld = [](const uint64_t* p) -> uint64_t {
+        if constexpr (AT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else return *p;
+    };
+
+    __shared__ uint64_t wl[kMergeBlock / 64][64];
+    __shared__ uint64_t surv[kMergeCap];
+    __shared__ uint32_t hd[kMergeHeads], hlt[kMergeHeads], hle[kMergeHeads];
+    __shared__ uint64_t s_bound, s_b1;
+    __shared__ uint32_t s_nsurv;
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t nw = blockDim.x >> 6;
+    const uint32_t total = n_lists * k;
+    const uint32_t kth = k - 1;
+
+    // every global load of the common case is issued up front (one HBM/L2 latency, not three):
+    // this thread's <= 8 keys, one list's k-th key, one sampled list head
+    const bool small = total <= blockDim.x * 8;
+    uint64_t mine[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) { uint32_t i = u * blockDim.x + threadIdx.x; mine[u] = (small && i < total) ? ld(src + i) : kDeadKey; }
+    // sampled heads: m = min(n_lists, kMergeHeads) lists at a fixed stride.  Any k different
+    // lists each hold a key <= the k-th smallest of their heads, so a subset still gives a
+    // valid (slightly looser) bound, and the O(m^2) rank count stays ~0.5 us on one CU.
+    const uint32_t m = n_lists < (uint32_t)kMergeHeads ? n_lists : (uint32_t)kMergeHeads;
+    const uint32_t hstride = n_lists / m;
+    const bool use_heads = m >= k;
+    uint64_t b = kDeadKey;
+    for (uint32_t w = threadIdx.x; w < n_lists; w += blockDim.x) { uint64_t x = ld(src + (size_t)w * k + kth); b = x < b ? x : b; }
+    if (use_heads)
+        for (uint32_t w = threadIdx.x; w < m; w += blockDim.x) { hd[w] = (uint32_t)(ld(src + (size_t)w * hstride * k) >> 32); hlt[w] = 0; hle[w] = 0; }
+
+    // phase A: two upper bounds of the final k-th key.
+    //   B0 = min over lists of their k-th key (that list alone has k keys <= B0);
+    //   B1 = from the k-th smallest sampled HEAD — the tight one when the winners are spread
+    //        over many lists, which is the common case.  Rank counting on the 32 distance bits:
+    //        head i qualifies when #{j: d_j < d_i} <= k-1 < #{j: d_j <= d_i}; then every key
+    //        with distance <= d_i is kept.
+    b = wave_min64(b);
+    if (lane == 0) wl[wave][0] = b;
+    if (threadIdx.x == 0) { s_nsurv = 0; s_b1 = kDeadKey; }
+    __syncthreads();
+    if (use_heads) {
+        const uint32_t segs = blockDim.x >= m ? blockDim.x / m : 1;   // thread -> (head i, segment of j)
+        const uint32_t per = (m + segs - 1) / segs;
+        for (uint32_t i = threadIdx.x % m, sgm = blockDim.x >= m ? threadIdx.x / m : 0; sgm < segs && i < m; i += blockDim.x) {
+            const uint32_t h = hd[i];
+            uint32_t clt = 0, cle = 0;
+            const uint32_t j0 = sgm * per, j1 = min(j0 + per, m);
+            uint32_t j = j0;
+            for (; j + 16 <= j1; j += 16) {                           // batch the (broadcast) LDS reads
+                uint32_t x[16];
+#pragma unroll
+                for (int u = 0; u < 16; u++) x[u] = hd[j + u];
+#pragma unroll
+                for (int u = 0; u < 16; u++) { clt += x[u] < h ? 1u : 0u; cle += x[u] <= h ? 1u : 0u; }
+            }
+            for (; j < j1; j++) { uint32_t x = hd[j]; clt += x < h ? 1u : 0u; cle += x <= h ? 1u : 0u; }
+            if (clt) atomicAdd(&hlt[i], clt);
+            if (cle) atomicAdd(&hle[i], cle);
+            if (blockDim.x >= m) break;
+        }
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < m; i += blockDim.x)
+            if (hlt[i] <= kth && kth < hle[i] && hd[i] != 0xFFFFFFFFu) s_b1 = ((uint64_t)hd[i] << 32) | 0xFFFFFFFFull;
+    }
+    if (wave == 0) {
+        uint64_t x = lane < nw ? wl[lane][0] : kDeadKey;
+        x = wave_min64(x);
+        if (lane == 0) s_bound = x;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_b1 < s_bound) s_bound = s_b1;
+    __syncthreads();
+    const uint64_t bound = s_bound;
+    // phase B: keep keys <= bound
+    auto keep = [&](uint64_t key) {
+        if (key != kDeadKey && key <= bound) {
+            uint32_t pos = atomicAdd(&s_nsurv, 1u);
+            if (pos < (uint32_t)kMergeCap) surv[pos] = key;
+        }
+    };
+    if (small) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) keep(mine[u]);
+    } else {
+        for (uint32_t base = 0; base < total; base += blockDim.x * 8) {
+            uint64_t key[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) { uint32_t i = base + u * blockDim.x + threadIdx.x; key[u] = i < total ? ld(src + i) : kDeadKey; }
+#pragma unroll
+            for (int u = 0; u < 8; u++) keep(key[u]);
+        }
+    }
+    __syncthreads();
+    const uint32_t ns = s_nsurv;
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    if (ns <= 64) {
+        // phase C (common): one wave bitonic-sorts the survivors
+        if (wave != 0) return;
+        list = wave_sort64(lane < ns ? surv[lane] : kDeadKey, lane);
+    } else if (ns <= (uint32_t)kMergeCap) {
+        if (wave != 0) return;
+        list = wave_sort64(surv[lane], lane);
+        thr = readlane64(list, kth);
+        for (uint32_t base = 64; base < ns; base += 64) {
+            uint32_t i = base + lane;
+            uint64_t key = i < ns ? surv[i] : kDeadKey;
+            list_insert(list, thr, key, kth, lane);
+        }
+    } else {
+        // general path (tiny indexes whose lists are mostly shorter than k): every wave
+        // reduces a slice, wave 0 merges the waves
+        for (uint32_t base = wave * 64; base < total; base += nw * 64) {
+            uint32_t i = base + lane;
+            uint64_t key = i < total ? ld(src + i) : kDeadKey;
+            list_insert(list, thr, key, kth, lane);
+        }
+        wl[wave][lane] = list;
+        __syncthreads();
+        if (wave != 0) return;
+        for (uint32_t w = 1; w < nw; w++) {
+            uint64_t key = lane < k ? wl[w][lane] : kDeadKey;
+            list_insert(list, thr, key, kth, lane);
+        }
+    }
+    const bool dead = list == kDeadKey;
+    const uint32_t r_out = dead ? 0xFFFFFFFFu : (uint32_t)list;
+    const float d_out = dead ? __uint_as_float(0x7F800000u) : unord_f32((uint32_t)(list >> 32));
+    if (!done_flag) {
+        if (lane < k) { rows_out[lane] = r_out; dist_out[lane] = d_out; }
+    } else {
+        // the host polls a sequence number instead of waiting for the stream (k_flat_scan_small's hand-over: system-scope stores for
+        // the results, and once they are acknowledged the sequence number on the same path)
+        if (lane < k) {
+            __hip_atomic_store(&rows_out[lane], r_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&dist_out[lane], d_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) __hip_atomic_store(done_flag, done_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+// (out of line: the scan's loop keeps its own register allocation and schedule — tests/test_isa_guard.py counts its loads in flight)
+__device__ __noinline__ inline void merge_lists_last_workgroup(const uint64_t* src, uint32_t n_lists, uint32_t k, uint32_t* rows_out, float* dist_out, uint32_t* done_flag = nullptr, uint32_t done_seq = 0) {
+    merge_lists_body<true>(src, n_lists, k, rows_out, dist_out, done_flag, done_seq);
+}
+
+// The row sets of a bound pass under filters as a kernel argument (k_bound_scan_mq<., ., true>, k_flat_scan_redo<., ., true>): at most kBoundSets
+// (bits, words) pairs indexed by the query, uniform, so a pair is a scalar load from the kernel arguments.
+constexpr uint32_t kBoundSets = 8;
+struct BoundSetTable { RowSetRef e[kBoundSets]; };
+struct NoSets {};                                                      // the last kernel argument of the forms without sets
+template <bool SETS> using SetsArg = typename std::conditional<SETS, BoundSetTable, NoSets>::type;
+
 
 }  // namespace qv

@@ -10,7 +10,7 @@ from quiver_amd import _lib
 from tests import _oracle as O
 
 COSINE, DOT = 0, 3
-CAND_CAP = 4096                                    # kBoundCandCap (qv_scan.hip): more survivors than this and the exact scan answers
+CAND_CAP = 4096                                    # kBoundCandCap (qv_bound_scan.hip): more survivors than this and the exact scan answers
 
 
 def bf16(x):

@@ -1,4 +1,4 @@
-"""The dispatch rule of the bound scan (quiver_amd/csrc/qv_scan.hip: bound_scan_rule) on the host, through qv_scan_bound_applies: which
+"""The dispatch rule of the bound scan (quiver_amd/csrc/qv_bound_scan.hip: bound_scan_rule) on the host, through qv_scan_bound_applies: which
 (metric, dim, rows, nq, k, mode) take the path on the bfloat16 copy — one query as before, 2 to 8 queries as a shared pass.
 
 The shared pass keeps the single-query sum: k_bound_scan_mq's packed fmas pair two QUERIES, each half one (query, row) chain of dim

@@ -1,4 +1,4 @@
-"""The single-query bound scan (k_bound_scan + k_bound_rescore, quiver_amd/csrc/qv_scan.hip): stage 1 rejects rows on the index's bfloat16
+"""The single-query bound scan (k_bound_scan + k_bound_rescore, quiver_amd/csrc/qv_bound_scan.hip): stage 1 rejects rows on the index's bfloat16
 copy, stage 2 walks the survivors' float32 rows in the exact scan's arithmetic.  The path is forced on by the index's setter (its
 automatic threshold is 300 000 rows); every result is compared, rows and float32 bits, with the exact scan of the SAME index (the
 setter's "never") and, for a few queries, with the CPU oracle — and the statistics say which path answered: a test here must not pass

@@ -1,4 +1,4 @@
-"""The 8-bit stage of the single-query bound scan (k_bound_scan8, quiver_amd/csrc/qv_scan.hip): stage 1 rejects rows on the index's int8
+"""The 8-bit stage of the single-query bound scan (k_bound_scan8, quiver_amd/csrc/qv_bound_scan.hip): stage 1 rejects rows on the index's int8
 plane with integer dot products, the survivors are walked in the exact scan's arithmetic, and a search the stage cannot decide goes on
 to the bfloat16 stage gated behind it, then to the exact scan.  Every case forces the bound scan and the 8-bit plane by the index's
 setters; every result is compared, rows and float32 bits, with the exact scan of the SAME index and with the CPU oracle — and the

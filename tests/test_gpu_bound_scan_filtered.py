@@ -1,4 +1,4 @@
-"""The bound scan under filters (k_bound_scan<., true>, k_bound_scan_mq<., ., true>, k_flat_scan_redo<., ., true>; quiver_amd/csrc/qv_scan.hip):
+"""The bound scan under filters (k_bound_scan<., true>, k_bound_scan_mq<., ., true>, k_flat_scan_redo<., ., true>; quiver_amd/csrc/qv_bound_scan.hip, the redo in qv_scan.hip):
 filtered searches of 1 to 8 queries read the bfloat16 copy, each query restricted to its own candidates live & set.  Every call runs under
 "always" and again under "never" (today's exact filtered scan: k_rowset_scan_mq, k_flat_scan over the candidate bitmap) and must give the
 same rows, counts and float32 bits; the statistics say which path answered — `searches` rises by the number of queries, `hand_backs` by

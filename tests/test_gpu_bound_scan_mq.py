@@ -1,4 +1,4 @@
-"""The bound scan as a shared pass (k_bound_scan_mq + k_bound_collect_mq + k_bound_rescore_mq, quiver_amd/csrc/qv_scan.hip): 2 to 8 queries
+"""The bound scan as a shared pass (k_bound_scan_mq + k_bound_collect_mq + k_bound_rescore_mq, quiver_amd/csrc/qv_bound_scan.hip): 2 to 8 queries
 read the index's bfloat16 copy once, 4 or 8 per pass; interval, threshold, collect and exact re-score are per query.  The path is forced on
 by the index's setter; every call is compared, rows, counts and float32 bits, with the same call under "never" (k_flat_scan_mq on the
 float32 tiles), one query per case with the CPU oracle — and the statistics say which path answered: `searches` must rise by exactly the

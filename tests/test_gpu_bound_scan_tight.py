@@ -1,4 +1,4 @@
-"""Both bound-scan kernels (k_bound_scan, k_bound_scan_mq: quiver_amd/csrc/qv_scan.hip) where the interval of qv_bound.h is TIGHT.
+"""Both bound-scan kernels (k_bound_scan, k_bound_scan_mq: quiver_amd/csrc/qv_bound_scan.hip) where the interval of qv_bound.h is TIGHT.
 
 tests/test_gpu_bound_scan.py and tests/test_gpu_bound_scan_mq.py compare rows and bits with the exact scan on corpora where the margin is
 tens of times wider than the error it covers: a residual several times too small, one left stale by an update or lost in a growth
