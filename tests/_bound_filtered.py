@@ -154,6 +154,7 @@ def clusters(metric):
 
 # ---- 7. the tight corpus under a filter ------------------------------------------------------------------------------------------------
 TIGHT_DIMS, TIGHT_KS = (16, 128), (1, 10)
+TIGHT_WIDE = ((240, 1), (240, 10), (2048, 10))      # (dim, k) of tests/_tight.PLANTED_WIDE: every block of the step ladder; the widest gamma the construction holds at
 
 
 @functools.lru_cache(maxsize=None)

@@ -25,7 +25,13 @@ from tests import _oracle as O
 
 PLANTED_DIMS = (16, 48, 128, 768)
 PLANTED_KS = (1, 10, 64)
-SHORT = 0.9                                        # the residual fault every planted case must catch: 10 % short
+# Wider rows, as (dim, k): 240 dimensions (15 steps: every block of the kernels' step ladder in one walk) and 2048, where gamma is half
+# the margin's room.  The construction ends near there: r*'s residual is 2^-8 / 1.16 of |r*|, so a residual 10 % short frees 3.4e-4 |q||r*|
+# of sum, of which r*'s own gamma term takes one gamma and a competitor's upper bound, gamma above its sum, another: 2 gamma < 3.4e-4 holds
+# to about 2800 dimensions (gamma is about dim x 2^-24), and with the bisection's aim, 0.15 of the way or more beyond r*, to about 2500.  At
+# 4096 (gamma = 2.4e-4) `planted` finds no competitor that discriminates and says so; tests/test_bound_tight_cpu.py keeps that on record.
+PLANTED_WIDE = ((240, 1), (240, 10), (240, 64), (2048, 10))
+SHORT = 0.9                                       # the residual fault every planted case must catch: 10 % short
 
 
 def _dist64(metric, q, rows):

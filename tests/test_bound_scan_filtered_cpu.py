@@ -182,6 +182,16 @@ def test_the_tight_corpus_stays_tight_under_its_set(metric, dim, k):
     """(a) - (d) of tests/_tight.conditions over alive = the set: r* is the k-th neighbour, H is the best competitor's upper bound, r*
     survives it with the reference's residual and not with one 10 % short — and again with the best competitor left out of the set, where H
     is the NEXT competitor's upper bound.  The ordinary queries beside it are not handed back either: `back == 0` for the whole pass."""
+    tight_corpus_stays_tight_under_its_set(metric, dim, k)
+
+
+@pytest.mark.parametrize("metric", [B.COSINE, B.DOT])
+@pytest.mark.parametrize("dim,k", F.TIGHT_WIDE)
+def test_the_tight_corpus_stays_tight_under_its_set_at_wider_rows(metric, dim, k):
+    tight_corpus_stays_tight_under_its_set(metric, dim, k)
+
+
+def tight_corpus_stays_tight_under_its_set(metric, dim, k):
     from tests import _tight as T
     t = F.tight(metric, dim, k)
     case = t["case"]

@@ -14,6 +14,24 @@ from tests import _tight as T
 @pytest.mark.parametrize("dim", T.PLANTED_DIMS)
 @pytest.mark.parametrize("k", T.PLANTED_KS)
 def test_planted_case_discriminates(metric, dim, k):
+    planted_case_discriminates(metric, dim, k)
+
+
+@pytest.mark.parametrize("metric", [B.COSINE, B.DOT])
+@pytest.mark.parametrize("dim,k", T.PLANTED_WIDE)
+def test_planted_case_discriminates_at_wider_rows(metric, dim, k):
+    planted_case_discriminates(metric, dim, k)
+
+
+def test_no_planted_case_at_the_widest_rows():
+    """at 4096 dimensions gamma alone is wider than the room a residual 10 % short leaves (tests/_tight.py): the construction says so
+    instead of returning a case that proves nothing"""
+    for metric in (B.COSINE, B.DOT):
+        with pytest.raises(AssertionError, match="competitors that discriminate"):
+            T.planted(metric, 4096, 10)
+
+
+def planted_case_discriminates(metric, dim, k):
     case = T.planted(metric, dim, k)
     n = len(case["rows"])
     assert 4000 <= n <= 8000 and n % 64 != 0

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import quiver_amd
+from tests import _bound as B
 from tests import _extremes as X
 from tests import _oracle as O
 from tests._order import planted_rows, query_for
@@ -34,7 +35,8 @@ def both(idx, q, k):
 @pytest.mark.parametrize("metric", ["cosine", "dot"])
 @pytest.mark.parametrize("dim", [16, 128, 768, 1536])
 def test_rows_and_bits_of_the_exact_scan(metric, dim):
-    """k = 1 / 10 / 63 / 64, a ragged last tile (n is no multiple of 64), against the exact scan and the oracle"""
+    """k = 1 / 10 / 63 / 64, a ragged last tile (n is no multiple of 64), against the exact scan and the oracle; stage 1's survivor count
+    against the CPU model's (tests/_bound.py)"""
     n = 20_011 if dim <= 768 else 9_003
     idx = quiver_amd.DeviceIndex(dim, metric)
     idx.add_synthetic(4100 + dim, 0, n)
@@ -42,11 +44,14 @@ def test_rows_and_bits_of_the_exact_scan(metric, dim):
     qs = O.gen_rows(4101 + dim, 0, 3, dim)
     corpus = O.gen_rows(4100 + dim, 0, n, dim)
     mid = quiver_amd.metric_id(metric)
+    state = B.RowState(corpus)
+    stage1 = [B.stage1(mid, state, q) for q in qs]
     for k in (1, 10, 63, 64):
         for i in range(3):
             (r, d, c), took, back, cand = both(idx, qs[i], k)
             assert took == 1 and back == 0, (k, i, took, back)
             assert k <= cand <= 4096
+            assert cand == B.decide(stage1[i], k)["count"], (k, i, cand)
             if i == 0:
                 er, ed = O.exact_search(mid, corpus, qs[i], k)
                 assert np.array_equal(r[0], er) and np.array_equal(d[0].view(np.uint32), ed.view(np.uint32))

@@ -13,6 +13,7 @@ from tests import _bound as B
 from tests import _bound8 as B8
 from tests import _extremes as X
 from tests import _oracle as O
+from tests import _widths as W
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +41,8 @@ def answered_by_the_8bit_stage(inc):
 @pytest.mark.parametrize("metric", ["cosine", "dot"])
 @pytest.mark.parametrize("dim", [16, 128, 768, 1536])
 def test_rows_and_bits_of_the_exact_scan_and_the_oracle(metric, dim):
-    """k = 1 / 10 / 63 / 64, a ragged last tile, several workgroups"""
+    """k = 1 / 10 / 63 / 64, a ragged last tile, several workgroups; stage 1's survivor count against the CPU model's (tests/_bound8.py's
+    intervals, once per query: tests/_widths.stage8_of)"""
     n = 20_011 if dim <= 768 else 9_003
     idx = quiver_amd.DeviceIndex(dim, metric)
     idx.add_synthetic(5100 + dim, 0, n)
@@ -48,11 +50,14 @@ def test_rows_and_bits_of_the_exact_scan_and_the_oracle(metric, dim):
     qs = O.gen_rows(5101 + dim, 0, 2, dim)
     corpus = O.gen_rows(5100 + dim, 0, n, dim)
     mid = quiver_amd.metric_id(metric)
+    state8 = B8.RowState8(corpus)
+    stage8 = [W.stage8_of(mid, state8, q) for q in qs]
     for k in (1, 10, 63, 64):
         for i in range(2):
             (r, d, c), inc = both(idx, qs[i], k)
             assert answered_by_the_8bit_stage(inc), (k, i, inc)
             assert k <= inc["cand8"] <= 4096 and inc["cand"] == inc["cand8"], inc
+            assert inc["cand8"] == B.decide(stage8[i], k)["count"], (k, i, inc)
             er, ed = O.exact_search(mid, corpus, qs[i], k)
             assert int(c[0]) == k and np.array_equal(r[0], er) and np.array_equal(d[0].view(np.uint32), ed.view(np.uint32))
     idx.close()

@@ -197,7 +197,16 @@ def test_the_planted_neighbour_under_its_own_set(metric, dim, k):
     lower bound is just inside it (tests/test_bound_scan_filtered_cpu.py establishes (a) - (d) over the set).  The planted query sits in an
     odd and in an even slot of a pass of four — the two halves of a packed fma — beside ordinary queries with other sets; then the set
     omits the best competitor and H is the next one's."""
-    from tests import _tight as T
+    planted_neighbour_under_its_own_set(metric, dim, k)
+
+
+@pytest.mark.parametrize("metric", [B.COSINE, B.DOT])
+@pytest.mark.parametrize("dim,k", F.TIGHT_WIDE)
+def test_the_planted_neighbour_under_its_own_set_at_wider_rows(metric, dim, k):
+    planted_neighbour_under_its_own_set(metric, dim, k)
+
+
+def planted_neighbour_under_its_own_set(metric, dim, k):
     t = F.tight(metric, dim, k)
     case = t["case"]
     idx = quiver_amd.DeviceIndex(dim, NAME[metric]); idx.add(case["rows"])

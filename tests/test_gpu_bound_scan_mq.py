@@ -8,9 +8,11 @@ import pytest
 
 import quiver_amd
 from quiver_amd.device_index import device_info
+from tests import _bound as B
 from tests import _callers
 from tests import _extremes as X
 from tests import _oracle as O
+from tests import _widths as W
 from tests._order import planted_rows, query_for
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +43,7 @@ def oracle_agrees(mid, corpus, q, k, r, d, alive=None):
 @pytest.mark.parametrize("dim", [16, 48, 128, 768])
 def test_rows_and_bits_of_the_exact_scan(metric, dim):
     """1, 3, 8 and 48 steps of 16 dimensions (every tail of the step walk: 1, 2 + 1, 8, 8 x 6), a ragged last tile, both QB with empty
-    slots and across the 4 / 8 edge, k = 1 / 10 / 63 / 64"""
+    slots and across the 4 / 8 edge, k = 1 / 10 / 63 / 64; the pass's largest survivor count against the CPU model's (tests/_bound.py)"""
     n = 20_011
     idx = quiver_amd.DeviceIndex(dim, metric)
     idx.add_synthetic(5100 + dim, 0, n)
@@ -49,11 +51,20 @@ def test_rows_and_bits_of_the_exact_scan(metric, dim):
     qs = O.gen_rows(5101 + dim, 0, 8, dim)
     corpus = O.gen_rows(5100 + dim, 0, n, dim)
     mid = quiver_amd.metric_id(metric)
+    state = B.RowState(corpus)
+    sums = W.chain32_queries(qs, state.rh)                                # tests/_bound.chain32_rows, the eight queries at once
+    model = {}
+    for j in range(8):
+        qn = B.chain_norm(qs[j])
+        unsure, lo, hi = B.intervals(mid, dim, sums[j], qn, state.rn, state.rres)
+        for k in (1, 10, 63, 64):
+            model[j, k] = B.decide({"lo": lo, "hi": hi, "unsure": unsure, "qn": qn, "dim": dim}, k)["count"]
     for case, nq in enumerate((2, 3, 4, 5, 7, 8)):
         for k in (1, 10, 63, 64):
             (r, d, c), took, back, cand = both(idx, qs[:nq], k)
             assert took == nq and back == 0, (nq, k, took, back)
             assert k <= cand <= 4096, (nq, k, cand)
+            assert cand == max(model[j, k] for j in range(nq)), (nq, k, cand)
             if k == (1, 10, 63, 64)[case % 4]:
                 j = nq - 1                                                # the last filled slot of the group
                 assert oracle_agrees(mid, corpus, qs[j], k, r[j], d[j]), (nq, k)

@@ -50,6 +50,17 @@ def planted_forms(idx, case, er, ed, others):
 @pytest.mark.parametrize("dim", T.PLANTED_DIMS)
 @pytest.mark.parametrize("k", T.PLANTED_KS)
 def test_planted_neighbour_that_needs_the_whole_margin(metric, dim, k):
+    planted_neighbour_that_needs_the_whole_margin(metric, dim, k)
+
+
+@pytest.mark.parametrize("metric", ["cosine", "dot"])
+@pytest.mark.parametrize("dim,k", T.PLANTED_WIDE)
+def test_planted_neighbour_that_needs_the_whole_margin_at_wider_rows(metric, dim, k):
+    """240 dimensions: every block of the step ladder in one walk; 2048: the widest gamma at which the construction holds (tests/_tight.py)"""
+    planted_neighbour_that_needs_the_whole_margin(metric, dim, k)
+
+
+def planted_neighbour_that_needs_the_whole_margin(metric, dim, k):
     case = T.planted(quiver_amd.metric_id(metric), dim, k)
     er, ed, _ = T.conditions(case)                                        # (a) - (d): the case discriminates
     idx = quiver_amd.DeviceIndex(dim, metric); idx.add(case["rows"])
