@@ -245,6 +245,64 @@ int qv_index_search_rowsets_device(qv_index* idx, const float* d_queries, uint32
                                    uint32_t* d_rows_out, float* d_dist_out, void* stream);
 int qv_index_rowset_coalesce_stats(qv_index* idx, uint64_t out[8]);
 
+/* ---- facet columns: row sets from predicates, set algebra, on the device -------------
+ * A qv_rowset_create needs a bitmap the HOST has already evaluated.  A qv_column keeps one typed value per row of ONE
+ * index on that index's device, beside the vectors, so that a filter value nobody has asked for before is one kernel
+ * pass over the columns (qv_rowset_create_where) instead of a walk over every row's metadata, an upload and a
+ * synchronisation; and two sets are combined where they live (qv_rowset_combine).  The sets these calls make are
+ * ordinary row sets: the same words, host mirror and counts that qv_rowset_create leaves for the same bitmap, so every
+ * search that names a set takes them alike.
+ *   types       QV_COL_F64: a JSON number as Go decodes it (float64).  QV_COL_U32: a dictionary code or rank the host
+ *               assigns (strings, bools, "%v" forms); ranks in sorted string order turn string < / > into unsigned
+ *               comparisons.
+ *   set         values[n] (double or uint32_t by type) for rows [first_row, first_row + n); present[n] bytes, 0 = the
+ *               row has no value (null = all present).  first_row + n <= qv_index_rows, else QV_ERR_OUT_OF_RANGE and
+ *               nothing changes.  Rows never set, and rows added to the index later, have no value.  Overwrites in
+ *               place; grows like a row set (no search or evaluation reallocates).  Synchronous.
+ *   rows        the column's extent: one past the last row ever set.
+ * Threading: evaluations naming a column may run concurrently; qv_column_set / qv_column_destroy need external
+ * exclusion against them.  The index must outlive its columns. */
+typedef struct qv_column qv_column;
+#define QV_COL_F64 0
+#define QV_COL_U32 1
+int qv_column_create(qv_column** out, qv_index* idx, int type);
+int qv_column_set(qv_column* col, uint32_t first_row, uint32_t n, const void* values, const uint8_t* present);
+uint32_t qv_column_rows(const qv_column* col);
+void qv_column_destroy(qv_column* col);
+
+#define QV_PRED_EQ 0      /* F64: fabs(x - v) <= 1e-9 in float64 (valuesEqual, collection.go:600-607); U32: x == v */
+#define QV_PRED_NE 1      /* the negation of EQ on rows that HAVE a value */
+#define QV_PRED_LT 2
+#define QV_PRED_LE 3
+#define QV_PRED_GT 4
+#define QV_PRED_GE 5      /* plain IEEE / unsigned comparisons (compareValues, :609-632) */
+#define QV_PRED_IN 6      /* EQ against any of 1..256 literals */
+#define QV_PRED_NOT_IN 7  /* EQ against none of them */
+#define QV_PRED_PRESENT 8 /* no literal (facets.NewExistsFilter) */
+#define QV_PRED_ABSENT 9  /* no literal */
+/* The set of rows r < qv_index_rows for which EVERY predicate p holds: cols[p] ops[p] literals[lit_off[p] .. lit_off[p+1])
+ * (lit_off has n_preds + 1 entries, lit_off[0] = 0, ascending).  Literals are doubles for both column types (a uint32 code is
+ * exact in a double; a U32 literal that is not an integer in [0, 2^32) is QV_ERR_INVALID_ARG).  EQ .. GE take exactly one
+ * literal, IN / NOT_IN 1..256, PRESENT / ABSENT none.  A row without a value in cols[p] fails p for every op except ABSENT
+ * (NE and NOT_IN included, as matchesFilter returns false for a missing field, collection.go:533-536); a column shorter
+ * than the index has no value for the rows past its extent.  1 <= n_preds <= 8; a column of another index, an op out of
+ * range, or a wrong literal count is QV_ERR_INVALID_ARG.  One kernel pass: a 64-row tile whose word is already zero
+ * after predicate p reads nothing of the columns after it, so put the most selective predicate first.  Like
+ * qv_rowset_create the set is NOT intersected with the live rows.  Synchronous (the words are read back for the host
+ * mirror: rows / 8 bytes); threading as qv_rowset_create. */
+int qv_rowset_create_where(qv_rowset** out, qv_index* idx, const qv_column* const* cols, const int* ops,
+                           const double* literals, const uint32_t* lit_off, uint32_t n_preds);
+#define QV_SET_AND 0
+#define QV_SET_OR 1
+#define QV_SET_ANDNOT 2
+/* dst = a OP b, word by word on the device; dst may be a or b; all three of one index, else QV_ERR_INVALID_ARG.  A set
+ * shorter than the index (made before it grew) reads as zeros past its end; dst is extended to the index's current rows.
+ * Synchronous; exclusion as qv_rowset_set_rows for dst. */
+int qv_rowset_combine(qv_rowset* dst, const qv_rowset* a, const qv_rowset* b, int op);
+/* The set's words AS THE DEVICE HOLDS THEM (qv_rowset_count reads the host mirror: tests compare the two): the first
+ * min(n_words, the set's words) 64-row words into words_out, zeros after them.  Synchronous. */
+int qv_rowset_read(const qv_rowset* rs, uint64_t* words_out, uint32_t n_words);
+
 /* Search with a negative example, the device part of HybridIndex.searchWithStrategy's exact branch
  * (hybrid_index.go:517-570; the HNSW adapter's is adapter.go:345-437): the k_fetch = max(2k, 30) nearest rows of `query`
  * (as qv_index_search), and for exactly those rows the distance to `negative` (as qv_distance_rows) — one call, one
@@ -417,7 +475,8 @@ int qv_merge_topk_shards_device(const uint32_t* d_packed_lists, const uint32_t* 
 /* Measurement aid: when enabled, every flat-scan kernel launched through
  * qv_index_search_device is bracketed by HIP events on the caller's stream;
  * qv_index_profile_read synchronises those events and returns the summed kernel
- * time and the number of launches since the last read.  Off by default. */
+ * time and the number of launches since the last read.  Off by default.  The kernels of
+ * qv_rowset_create_where and qv_rowset_combine are bracketed the same way (on the null stream). */
 int qv_index_profile(qv_index* idx, int enable);
 int qv_index_profile_read(qv_index* idx, double* scan_ms_sum_out, uint64_t* launches_out);
 

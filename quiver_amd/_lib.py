@@ -15,6 +15,8 @@ QV_FLAG_ROWMAJOR = 1
 QV_FLAG_BF16_ROWS = 2
 QV_FLAG_NO_SCAN_PLANE = 4
 QV_BOUND_SCAN_AUTO, QV_BOUND_SCAN_ALWAYS, QV_BOUND_SCAN_NEVER = 0, 1, 2
+QV_COL_F64, QV_COL_U32 = 0, 1
+QV_SET_AND, QV_SET_OR, QV_SET_ANDNOT = 0, 1, 2
 QV_SHARDED_PEER_COPY = 1 << 32
 
 # include/qv.h qv_metric
@@ -70,6 +72,13 @@ PROTOTYPES = {
     "qv_index_search_rowsets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_index_search_rowsets_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_index_rowset_coalesce_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_column_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int]),
+    "qv_column_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "qv_column_rows": (C.c_uint32, [C.c_void_p]),
+    "qv_column_destroy": (None, [C.c_void_p]),
+    "qv_rowset_create_where": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "qv_rowset_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "qv_rowset_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "qv_index_search_negative": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, _u32p]),
     "qv_index_search_batched": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_index_search_batched_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -839,6 +839,177 @@ static uint64_t rowset_live(const qv_index* idx, const qv_rowset* rs) {
     return n;
 }
 
+// ---------------------------------------------------------------- facet columns: row sets made on the device (qv_where.hip) --
+int qv_column_create(qv_column** out, qv_index* idx, int type) {
+    if (!out) return fail(QV_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (type != QV_COL_F64 && type != QV_COL_U32) return fail(QV_ERR_INVALID_ARG, "unknown column type %d", type);
+    qv_column* col = new (std::nothrow) qv_column();
+    if (!col) return fail(QV_ERR_OOM, "out of host memory");
+    col->idx = idx; col->device = idx->device; col->type = type;
+    *out = col;
+    return QV_OK;
+}
+
+int qv_column_set(qv_column* col, uint32_t first_row, uint32_t n, const void* values, const uint8_t* present) {
+    if (!col) return fail(QV_ERR_INVALID_ARG, "column is null");
+    qv_index* idx = col->idx;
+    if ((uint64_t)first_row + n > idx->n_rows)
+        return fail(QV_ERR_OUT_OF_RANGE, "rows [%u, %llu) reach past the index (rows: %u)", first_row, (unsigned long long)first_row + n, idx->n_rows);
+    if (n == 0) return QV_OK;
+    if (!values) return fail(QV_ERR_INVALID_ARG, "values is null");
+    HIPCHK(hipSetDevice(idx->device));
+    if (((uint64_t)first_row + n + 63) / 64 > col->cap_tiles) {       // to the index's current rows, as a row set grows: new tiles are zero (no value)
+        const uint32_t need = (uint32_t)(((uint64_t)idx->n_rows + 63) / 64);
+        const size_t tb = 64 * col->elem();
+        hipError_t e = regrow(reinterpret_cast<char**>(&col->d_values), (size_t)col->cap_tiles * tb, (size_t)need * tb);
+        if (e == hipSuccess) e = regrow(&col->d_present, (size_t)col->cap_tiles * 8, (size_t)need * 8);    // (a failure here leaves the values longer than the presence words: harmless)
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? QV_ERR_OOM : QV_ERR_DEVICE, "column growth failed: %s", hipGetErrorString(e));
+        col->cap_tiles = need;
+    }
+    const uint8_t* d_bytes = nullptr;
+    if (present) {
+        const int rc0 = col->stage.ensure(n);
+        if (rc0 != QV_OK) return rc0;
+        d_bytes = static_cast<const uint8_t*>(col->stage.p);
+    }
+    hipError_t e = hipMemcpy(static_cast<char*>(col->d_values) + (size_t)first_row * col->elem(), values, (size_t)n * col->elem(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && present) e = hipMemcpy(col->stage.p, present, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = qv::launch_column_presence(col->d_present, first_row, n, d_bytes, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return fail(QV_ERR_DEVICE, "column update failed: %s", hipGetErrorString(e));
+    col->rows = std::max(col->rows, first_row + n);
+    return QV_OK;
+}
+
+uint32_t qv_column_rows(const qv_column* col) { return col ? col->rows : 0; }
+
+void qv_column_destroy(qv_column* col) {
+    if (!col) return;
+    (void)hipSetDevice(col->device);                                  // (no device-wide wait: the caller's exclusion says that no evaluation naming this column is running)
+    (void)hipFree(col->d_values);
+    (void)hipFree(col->d_present);
+    col->stage.release();
+    delete col;
+}
+
+// qv_index_profile around a kernel on the null stream: both events or neither, the first recorded at once; the pair joins the index's
+// list only when both are recorded behind a launch that succeeded, and is destroyed otherwise
+static void profile_events_begin(hipEvent_t* ev0, hipEvent_t* ev1) {
+    *ev0 = nullptr; *ev1 = nullptr;
+    if (hipEventCreate(ev0) != hipSuccess) { *ev0 = nullptr; return; }
+    if (hipEventCreate(ev1) != hipSuccess) { (void)hipEventDestroy(*ev0); *ev0 = nullptr; *ev1 = nullptr; return; }
+    if (hipEventRecord(*ev0, nullptr) != hipSuccess) { (void)hipEventDestroy(*ev0); (void)hipEventDestroy(*ev1); *ev0 = nullptr; *ev1 = nullptr; }
+}
+static void profile_events_end(qv_index* idx, hipEvent_t ev0, hipEvent_t ev1, bool launched) {
+    if (!ev0) return;
+    if (launched && hipEventRecord(ev1, nullptr) == hipSuccess) {
+        std::lock_guard<std::mutex> g(idx->prof_mu);
+        idx->prof_events.emplace_back(ev0, ev1);
+        return;
+    }
+    (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
+}
+
+// the host mirror and the counts the searches read, from the words a kernel has just written (the null stream: the copy waits for it)
+static int rowset_mirror(qv_rowset* rs) {
+    rs->host.assign(rs->words, 0);
+    if (rs->words) HIPCHK(hipMemcpy(rs->host.data(), rs->d_bits, (size_t)rs->words * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    rs->tiles = 0; rs->selected = 0;
+    for (uint64_t w : rs->host) { rs->tiles += w != 0 ? 1u : 0u; rs->selected += (uint64_t)__builtin_popcountll(w); }
+    return QV_OK;
+}
+
+int qv_rowset_create_where(qv_rowset** out, qv_index* idx, const qv_column* const* cols, const int* ops,
+                           const double* literals, const uint32_t* lit_off, uint32_t n_preds) {
+    if (!out) return fail(QV_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (n_preds < 1 || n_preds > qv::kWherePreds) return fail(QV_ERR_INVALID_ARG, "1 to %u predicates per evaluation, got %u", qv::kWherePreds, n_preds);
+    if (!cols || !ops || !lit_off) return fail(QV_ERR_INVALID_ARG, "cols, ops or lit_off is null");
+    if (lit_off[0] != 0) return fail(QV_ERR_INVALID_ARG, "lit_off[0] must be 0");
+    qv::WhereTable tab{};
+    tab.n = n_preds;
+    for (uint32_t p = 0; p < n_preds; p++) {
+        const qv_column* c = cols[p];
+        if (!c) return fail(QV_ERR_INVALID_ARG, "cols[%u] is null", p);
+        if (c->idx != idx) return fail(QV_ERR_INVALID_ARG, "cols[%u] belongs to another index", p);
+        const int op = ops[p];
+        if (op < QV_PRED_EQ || op > QV_PRED_ABSENT) return fail(QV_ERR_INVALID_ARG, "ops[%u] = %d is not a predicate", p, op);
+        if (lit_off[p + 1] < lit_off[p]) return fail(QV_ERR_INVALID_ARG, "lit_off must ascend");
+        const uint32_t nl = lit_off[p + 1] - lit_off[p];
+        const bool list = op == QV_PRED_IN || op == QV_PRED_NOT_IN, none = op == QV_PRED_PRESENT || op == QV_PRED_ABSENT;
+        if (none ? nl != 0 : (list ? (nl < 1 || nl > qv::kWhereLits) : nl != 1))
+            return fail(QV_ERR_INVALID_ARG, "predicate %u (op %d) takes %s, got %u", p, op, none ? "no literal" : (list ? "1 to 256 literals" : "one literal"), nl);
+        if (nl && !literals) return fail(QV_ERR_INVALID_ARG, "literals is null");
+        if (c->type == QV_COL_U32)
+            for (uint32_t i = lit_off[p]; i < lit_off[p + 1]; i++) {
+                const double v = literals[i];
+                if (!(v >= 0.0 && v < 4294967296.0) || v != (double)(uint32_t)v)
+                    return fail(QV_ERR_INVALID_ARG, "literal %u of predicate %u is not a uint32 code", i - lit_off[p], p);
+            }
+        qv::WherePred& w = tab.p[p];
+        w.values = c->d_values; w.present = c->d_present; w.tiles = (uint32_t)(((uint64_t)c->rows + 63) / 64);
+        w.type = c->type; w.op = op; w.lit0 = lit_off[p]; w.n_lit = nl;
+    }
+    HIPCHK(hipSetDevice(idx->device));
+    qv_rowset* rs = new (std::nothrow) qv_rowset();
+    if (!rs) return fail(QV_ERR_OOM, "out of host memory");
+    rs->idx = idx; rs->device = idx->device;
+    rs->words = (uint32_t)(((uint64_t)idx->n_rows + 63) / 64);
+    const size_t lit_bytes = std::max<size_t>((size_t)lit_off[n_preds] * sizeof(double), 8);
+    int rc = rs->stage.ensure(lit_bytes);
+    hipError_t e = hipSuccess;
+    if (rc == QV_OK) {
+        e = hipMalloc(reinterpret_cast<void**>(&rs->d_bits), std::max<size_t>((size_t)rs->words * 8, 256));
+        if (e == hipSuccess && lit_off[n_preds]) e = hipMemcpy(rs->stage.p, literals, (size_t)lit_off[n_preds] * sizeof(double), hipMemcpyHostToDevice);
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;                      // qv_index_profile: the evaluation kernel alone
+        if (e == hipSuccess && idx->profiling) profile_events_begin(&ev0, &ev1);
+        if (e == hipSuccess) e = qv::launch_rowset_where(tab, static_cast<const double*>(rs->stage.p), idx->n_rows, rs->d_bits, idx->cus, nullptr);
+        profile_events_end(idx, ev0, ev1, e == hipSuccess);
+        if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? QV_ERR_OOM : QV_ERR_DEVICE, "row set evaluation failed: %s", hipGetErrorString(e));
+    }
+    if (rc == QV_OK) rc = rowset_mirror(rs);
+    if (rc != QV_OK) { (void)hipFree(rs->d_bits); rs->stage.release(); delete rs; return rc; }
+    *out = rs;
+    return QV_OK;
+}
+
+int qv_rowset_combine(qv_rowset* dst, const qv_rowset* a, const qv_rowset* b, int op) {
+    if (!dst || !a || !b) return fail(QV_ERR_INVALID_ARG, "row set is null");
+    if (op != QV_SET_AND && op != QV_SET_OR && op != QV_SET_ANDNOT) return fail(QV_ERR_INVALID_ARG, "unknown set operation %d", op);
+    qv_index* idx = dst->idx;
+    if (a->idx != idx || b->idx != idx) return fail(QV_ERR_INVALID_ARG, "row sets of different indexes");
+    HIPCHK(hipSetDevice(idx->device));
+    const uint32_t need = (uint32_t)(((uint64_t)idx->n_rows + 63) / 64);
+    if (need > dst->words) {                                          // (dst may be a or b: they are read through the handles below, after this)
+        hipError_t e = regrow(&dst->d_bits, (size_t)dst->words * 8, (size_t)need * 8);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? QV_ERR_OOM : QV_ERR_DEVICE, "row set growth failed: %s", hipGetErrorString(e));
+        dst->host.resize(need, 0);
+        dst->words = need;
+    }
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;                          // qv_index_profile: the kernel alone
+    if (idx->profiling) profile_events_begin(&ev0, &ev1);
+    hipError_t e = qv::launch_rowset_combine(rowset_ref(a), rowset_ref(b), op, dst->words, dst->d_bits, nullptr);
+    profile_events_end(idx, ev0, ev1, e == hipSuccess);
+    if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row set combination failed: %s", hipGetErrorString(e));
+    return rowset_mirror(dst);
+}
+
+int qv_rowset_read(const qv_rowset* rs, uint64_t* words_out, uint32_t n_words) {
+    if (!rs) return fail(QV_ERR_INVALID_ARG, "row set is null");
+    if (n_words == 0) return QV_OK;
+    if (!words_out) return fail(QV_ERR_INVALID_ARG, "words_out is null");
+    HIPCHK(hipSetDevice(rs->device));
+    const uint32_t m = std::min(n_words, rs->words);
+    if (m) HIPCHK(hipMemcpy(words_out, rs->d_bits, (size_t)m * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    memset(words_out + m, 0, (size_t)(n_words - m) * 8);
+    return QV_OK;
+}
+
 // How a call is cut into device work.  Up to kMaxFusedK results and two or more queries: ONE piece, the multi-query scans with a set
 // per query (qv_rowset.hip).  Otherwise runs of consecutive queries naming the same set, each through the paths of qv_index_search
 // over the candidate bitmap alive & set, formed on the device (k_rowset_and) — a single query takes the single-launch scans that

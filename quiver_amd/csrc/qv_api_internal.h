@@ -156,5 +156,20 @@ struct qv_rowset {
     std::vector<uint64_t> host;
     uint32_t tiles = 0;                        // non-empty words of `host`: the tiles a scan under this set can have to read (the filtered bound-scan rule's input)
     uint64_t selected = 0;                     // bits set in `host`, dead rows included: fewer than k means no threshold under this set (the rule's other input)
-    Buf stage;                                 // row ids of qv_rowset_set_rows
+    Buf stage;                                 // row ids of qv_rowset_set_rows; the literals of qv_rowset_create_where
+};
+
+// One typed value per row of ONE index on that index's device (include/qv.h "facet columns").  Storage is whole 64-row tiles
+// (cap_tiles of them, zero-filled when grown: a tile inside the capacity can always be loaded); `rows` is the extent, and a
+// presence word past ceil(rows / 64) is never read — rows beyond have no value, which is how a column stays valid while its index grows.
+struct qv_column {
+    qv_index* idx = nullptr;
+    int device = 0;
+    int type = 0;                              // QV_COL_*
+    void* d_values = nullptr;                  // double or uint32_t per row
+    uint64_t* d_present = nullptr;             // bit r % 64 of word r / 64: row r has a value
+    uint32_t cap_tiles = 0;
+    uint32_t rows = 0;
+    Buf stage;                                 // presence bytes of qv_column_set
+    size_t elem() const { return type == QV_COL_F64 ? sizeof(double) : sizeof(uint32_t); }
 };

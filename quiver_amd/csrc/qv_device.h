@@ -267,6 +267,20 @@ hipError_t launch_rowset_and(const IndexView& v, const RowSetRef& set, uint64_t*
 hipError_t launch_rowset_pad(uint32_t* d_rows, float* d_dist, size_t n, hipStream_t s);
 // set / clear the listed rows' bits (d_rows on the device, every row < words * 64)
 hipError_t launch_rowset_set_rows(uint64_t* d_bits, const uint32_t* d_rows, uint32_t n, int selected, hipStream_t s);
+// --- row sets made on the device (qv_where.hip): predicates over typed columns, set algebra ----
+// One comparison of a conjunction as the kernel sees it: the column's values (double or uint32_t per row, by `type`) and presence words
+// (`tiles` of them are valid: rows beyond have no value), the op (QV_PRED_*) and its literals d_lits[lit0 .. lit0 + n_lit).
+constexpr uint32_t kWherePreds = 8;
+constexpr uint32_t kWhereLits = 256;                    // literals of one IN / NOT_IN
+struct WherePred { const void* values; const uint64_t* present; uint32_t tiles; int type; int op; uint32_t lit0; uint32_t n_lit; uint32_t pad_; };
+struct WhereTable { WherePred p[kWherePreds]; uint32_t n; uint32_t pad_; };
+// d_out[t] = the rows r < n_rows of tile t for which every predicate holds, for all ceil(n_rows / 64) tiles (bits past n_rows: zero).
+// The table travels as kernel arguments; d_lits is on the device.
+hipError_t launch_rowset_where(const WhereTable& tab, const double* d_lits, uint32_t n_rows, uint64_t* d_out, int cus, hipStream_t s);
+// d_dst[t] = a[t] OP b[t] (QV_SET_*) for t < words; a set shorter than that reads as zeros; d_dst may be a.bits or b.bits
+hipError_t launch_rowset_combine(const RowSetRef& a, const RowSetRef& b, int op, uint32_t words, uint64_t* d_dst, hipStream_t s);
+// presence bits of rows [first_row, first_row + n): bit = d_bytes[i] != 0 (null: all set); every other bit of the words stays
+hipError_t launch_column_presence(uint64_t* d_present, uint32_t first_row, uint32_t n, const uint8_t* d_bytes, hipStream_t s);
 // pieces of the multi-query scans that qv_rowset.hip shares with qv_scan.hip: the query blocks of the scalar-operand form
 // (qblk[group][dim4 * 4][qb], qb = 4, 8 or — the float64-accumulating metrics — 16) and the merge of partial[nq][n_lists][k] into [nq][k] results
 hipError_t launch_prep_qblk(int metric, uint32_t qb, const float* d_queries, uint32_t nq, uint32_t dim, uint32_t dim4, void* d_qblk, hipStream_t s);

@@ -208,6 +208,43 @@ class DeviceIndex:
         check(lib().qv_index_search_rowsets_device(self._h, d_queries, nq, k, arr, d_rows_out, d_dist_out, stream))
         del keep
 
+    # ---- facet columns: row sets from predicates, on the device ----
+    COLUMN_TYPES = {"f64": 0, "u32": 1}
+
+    PREDICATES = {"==": 0, "=": 0, "eq": 0, "!=": 1, "ne": 1, "<": 2, "lt": 2, "<=": 3, "le": 3, ">": 4, "gt": 4, ">=": 5, "ge": 5,
+                  "in": 6, "not_in": 7, "present": 8, "absent": 9}
+
+    def column(self, type) -> "Column":
+        """one typed value per row of this index, resident on its device (qv_column_create): "f64" (a JSON number) or "u32" (a
+        dictionary code or rank the host assigns).  Rows never set, and rows added later, have no value."""
+        return Column(self, type)
+
+    def rowset_where(self, predicates) -> "RowSet":
+        """the rows for which EVERY (column, op, literal_or_list) holds, evaluated in one pass on the device (qv_rowset_create_where):
+        op is a key of PREDICATES or a QV_PRED_* code; "present" / "absent" take None.  A row without a value fails every op but
+        "absent".  1 to 8 predicates, most selective first: a tile no row of which passes reads no later column."""
+        preds = list(predicates)
+        n = len(preds)
+        cols = (C.c_void_p * max(n, 1))()
+        ops = (C.c_int * max(n, 1))()
+        off = np.zeros(n + 1, dtype=np.uint32)
+        lits = []
+        for i, (col, op, lit) in enumerate(preds):
+            if not isinstance(col, Column):
+                raise TypeError("predicate %d does not name a Column" % i)
+            cols[i] = col.handle.value
+            ops[i] = self.PREDICATES[op.lower()] if isinstance(op, str) else int(op)
+            if lit is not None:
+                lits.extend(np.asarray(lit, dtype=np.float64).ravel().tolist())
+            off[i + 1] = len(lits)
+        lit_arr = np.asarray(lits, dtype=np.float64)
+        rs = RowSet.__new__(RowSet)
+        rs._h = C.c_void_p()
+        rs._index = self
+        check(lib().qv_rowset_create_where(C.byref(rs._h), self._h, cols, ops, lit_arr.ctypes.data if lit_arr.size else None, off.ctypes.data, n))
+        del preds                                           # (kept the Column objects alive across the call)
+        return rs
+
     def rowset_coalesce_stats(self) -> dict:
         out = (C.c_uint64 * 8)()
         check(lib().qv_index_rowset_coalesce_stats(self._h, out))
@@ -327,9 +364,82 @@ class RowSet:
         """rows selected, dead ones included"""
         return int(lib().qv_rowset_count(self._h))
 
+    def words(self) -> np.ndarray:
+        """the bitmap as the DEVICE holds it, one uint64 per 64 rows of the index as it is now (qv_rowset_read); count() reads the host mirror"""
+        out = np.zeros((self._index.rows() + 63) // 64, dtype=np.uint64)
+        check(lib().qv_rowset_read(self._h, out.ctypes.data, out.size))
+        return out
+
+    SET_OPS = {"and": 0, "&": 0, "or": 1, "|": 1, "andnot": 2, "-": 2}
+
+    def combine(self, a: "RowSet", b: "RowSet", op) -> "RowSet":
+        """self = a OP b on the device, in place (qv_rowset_combine): "and", "or" or "andnot"; a or b may be self"""
+        check(lib().qv_rowset_combine(self._h, a.handle, b.handle, self.SET_OPS[op] if isinstance(op, str) else int(op)))
+        return self
+
+    def _combined(self, other: "RowSet", op: str) -> "RowSet":
+        if not isinstance(other, RowSet):
+            return NotImplemented
+        return RowSet(self._index).combine(self, other, op)
+
+    def __and__(self, other):
+        return self._combined(other, "and")
+
+    def __or__(self, other):
+        return self._combined(other, "or")
+
+    def __sub__(self, other):
+        return self._combined(other, "andnot")
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             lib().qv_rowset_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Column:
+    """One ``qv_column``: a typed value per row of a DeviceIndex, on its device, for DeviceIndex.rowset_where.  The index must
+    outlive the column."""
+
+    def __init__(self, index: DeviceIndex, type):
+        self._h = C.c_void_p()
+        self._index = index
+        self.type = DeviceIndex.COLUMN_TYPES[type.lower()] if isinstance(type, str) else int(type)
+        check(lib().qv_column_create(C.byref(self._h), index.handle, self.type))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set(self, first_row: int, values, present=None):
+        """values for rows [first_row, first_row + len(values)); present: a bool per value, False = the row has no value (None: all have)"""
+        v = np.ascontiguousarray(values, dtype=np.float64 if self.type == _lib.QV_COL_F64 else np.uint32).ravel()
+        p = None
+        if present is not None:
+            p = np.ascontiguousarray(np.asarray(present).ravel() != 0, dtype=np.uint8)
+            if p.size != v.size:
+                raise ValueError("present must have one entry per value")
+        check(lib().qv_column_set(self._h, int(first_row), v.size, v.ctypes.data, None if p is None else p.ctypes.data))
+
+    def rows(self) -> int:
+        """one past the last row ever set"""
+        return int(lib().qv_column_rows(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().qv_column_destroy(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
