@@ -303,6 +303,51 @@ int qv_rowset_combine(qv_rowset* dst, const qv_rowset* a, const qv_rowset* b, in
  * min(n_words, the set's words) 64-row words into words_out, zeros after them.  Synchronous. */
 int qv_rowset_read(const qv_rowset* rs, uint64_t* words_out, uint32_t n_words);
 
+/* ---- filtered search by predicate, in one call ---------------------------------------
+ * A filter that carries a per-request literal (price < 37.5, ts >= now - 1h, an IN list from the user) is never asked
+ * twice: making a qv_rowset for it costs an allocation, a pass on the null stream, a download of rows / 8 bytes for the
+ * host mirror and a synchronisation, in front of the search, and a destroy behind it.  qv_index_search_where takes the
+ * conjunction itself, one per query: a qv_where is the argument list of qv_rowset_create_where, and query q gets exactly
+ * what qv_index_search_rowsets returns when sets[q] is the set qv_rowset_create_where makes from filters[q] — the same
+ * rows, float32 bits, (distance, row) order, counts and padding; tombstones honoured, a column shorter than the index has
+ * no value past its extent, a row without a value fails every op but ABSENT.  n_preds == 0: every row (a null set).
+ * The sets live in the call's workspace only: no qv_rowset is created, nothing runs on the null stream, nothing but the
+ * results is downloaded, and once the call's buffers have grown nothing is allocated or freed.  All filters of a call
+ * (or of a shared pass) are evaluated in front of the scan by launches of up to QV_WHERE_FILTERS_PER_LAUNCH conjunctions
+ * each; bytewise-equal filters are evaluated once.  Everything the qv_where structs point to is read before the call returns.
+ * Checks, in order: a null index / queries / count_out / filters; an empty index -> 0 results and QV_OK; k == 0 ->
+ * QV_ERR_K_NOT_POSITIVE; then every filter by qv_rowset_create_where's own check (same codes and wording, the message
+ * prefixed with the query's number).
+ * Routing: the host does not know how many rows a filter selects.  One query is planned as for a set that may select every
+ * tile; a call or shared pass of several queries holding such a filter is declined by QV_BOUND_SCAN_AUTO and takes the exact
+ * row-set scan (QV_BOUND_SCAN_ALWAYS still takes the bound scan); a filter that selects fewer than k rows is answered by the
+ * exact scan, decided on the device.  A mis-route costs time, never bits.
+ * k > 64 (host form only): runs of consecutive queries with bytewise-equal filters are materialised as a temporary row
+ * set (this may synchronise), take the selection / ranking paths of qv_index_search_rowsets, and the set is freed before
+ * the call returns.
+ * Calls of up to 8 queries and k <= 64 share passes with each other AND with concurrent qv_index_search_rowsets calls
+ * (the same front: qv_index_rowset_coalesce_stats counts them). */
+typedef struct qv_where {                /* one conjunction: the arguments of qv_rowset_create_where */
+    const qv_column* const* cols;
+    const int* ops;
+    const double* literals;
+    const uint32_t* lit_off;
+    uint32_t n_preds;
+} qv_where;
+#define QV_WHERE_FILTERS_PER_LAUNCH 8    /* conjunctions one evaluation launch carries (their tables are kernel arguments) */
+#define QV_WHERE_DEVICE_LITERALS 16      /* literals ONE filter of the device-pointer form may carry in total */
+int qv_index_search_where(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_where* filters /* host, [nq] */,
+                          uint32_t* rows_out, float* dist_out, uint32_t* count_out);
+/* Device-pointer form: queries / results on the device, `filters` a HOST array (read before the call returns).  Enqueues
+ * on `stream`, no synchronisation; every list is k long, padded with 0xFFFFFFFF / +inf past the query's matches.  The
+ * predicate tables AND the literals travel as kernel arguments, so that no staging buffer exists which a later call
+ * could overwrite while this one is still enqueued: a filter whose literals number more than QV_WHERE_DEVICE_LITERALS
+ * (an EQ or a range needs 1 - 2; a long IN list does not fit) is QV_ERR_UNSUPPORTED, and so is k > 64 — both decided on
+ * the host before anything is enqueued (use the host form, or qv_rowset_create_where + qv_index_search_rowsets_device).
+ * Check order: null arguments, k == 0, k > 64, every filter as above, the literal limit; an empty index pads every list. */
+int qv_index_search_where_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const qv_where* filters /* HOST, [nq] */,
+                                 uint32_t* d_rows_out, float* d_dist_out, void* stream);
+
 /* Search with a negative example, the device part of HybridIndex.searchWithStrategy's exact branch
  * (hybrid_index.go:517-570; the HNSW adapter's is adapter.go:345-437): the k_fetch = max(2k, 30) nearest rows of `query`
  * (as qv_index_search), and for exactly those rows the distance to `negative` (as qv_distance_rows) — one call, one

@@ -77,6 +77,8 @@ PROTOTYPES = {
     "qv_column_rows": (C.c_uint32, [C.c_void_p]),
     "qv_column_destroy": (None, [C.c_void_p]),
     "qv_rowset_create_where": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "qv_index_search_where": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qv_index_search_where_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_rowset_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "qv_rowset_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "qv_index_search_negative": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, _u32p]),

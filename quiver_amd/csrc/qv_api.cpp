@@ -922,15 +922,13 @@ static int rowset_mirror(qv_rowset* rs) {
     return QV_OK;
 }
 
-int qv_rowset_create_where(qv_rowset** out, qv_index* idx, const qv_column* const* cols, const int* ops,
-                           const double* literals, const uint32_t* lit_off, uint32_t n_preds) {
-    if (!out) return fail(QV_ERR_INVALID_ARG, "out is null");
-    *out = nullptr;
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+// One conjunction's arguments, checked and turned into the table the kernels read (tab: zeroed by the caller): the checks of
+// qv_rowset_create_where, which qv_index_search_where makes per query through this same function (its message names the query in front)
+static int where_check(const qv_index* idx, const qv_column* const* cols, const int* ops, const double* literals, const uint32_t* lit_off,
+                       uint32_t n_preds, qv::WhereTable& tab) {
     if (n_preds < 1 || n_preds > qv::kWherePreds) return fail(QV_ERR_INVALID_ARG, "1 to %u predicates per evaluation, got %u", qv::kWherePreds, n_preds);
     if (!cols || !ops || !lit_off) return fail(QV_ERR_INVALID_ARG, "cols, ops or lit_off is null");
     if (lit_off[0] != 0) return fail(QV_ERR_INVALID_ARG, "lit_off[0] must be 0");
-    qv::WhereTable tab{};
     tab.n = n_preds;
     for (uint32_t p = 0; p < n_preds; p++) {
         const qv_column* c = cols[p];
@@ -954,17 +952,23 @@ int qv_rowset_create_where(qv_rowset** out, qv_index* idx, const qv_column* cons
         w.values = c->d_values; w.present = c->d_present; w.tiles = (uint32_t)(((uint64_t)c->rows + 63) / 64);
         w.type = c->type; w.op = op; w.lit0 = lit_off[p]; w.n_lit = nl;
     }
+    return QV_OK;
+}
+
+// a real set from a checked conjunction: allocation, the pass on the null stream, the mirror (qv_rowset_create_where; and the runs of
+// a k > 64 qv_index_search_where, which frees the set again before it returns)
+static int rowset_from_where(qv_index* idx, const qv::WhereTable& tab, const double* literals, uint32_t n_lits, qv_rowset** out) {
     HIPCHK(hipSetDevice(idx->device));
     qv_rowset* rs = new (std::nothrow) qv_rowset();
     if (!rs) return fail(QV_ERR_OOM, "out of host memory");
     rs->idx = idx; rs->device = idx->device;
     rs->words = (uint32_t)(((uint64_t)idx->n_rows + 63) / 64);
-    const size_t lit_bytes = std::max<size_t>((size_t)lit_off[n_preds] * sizeof(double), 8);
+    const size_t lit_bytes = std::max<size_t>((size_t)n_lits * sizeof(double), 8);
     int rc = rs->stage.ensure(lit_bytes);
     hipError_t e = hipSuccess;
     if (rc == QV_OK) {
         e = hipMalloc(reinterpret_cast<void**>(&rs->d_bits), std::max<size_t>((size_t)rs->words * 8, 256));
-        if (e == hipSuccess && lit_off[n_preds]) e = hipMemcpy(rs->stage.p, literals, (size_t)lit_off[n_preds] * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess && n_lits) e = hipMemcpy(rs->stage.p, literals, (size_t)n_lits * sizeof(double), hipMemcpyHostToDevice);
         hipEvent_t ev0 = nullptr, ev1 = nullptr;                      // qv_index_profile: the evaluation kernel alone
         if (e == hipSuccess && idx->profiling) profile_events_begin(&ev0, &ev1);
         if (e == hipSuccess) e = qv::launch_rowset_where(tab, static_cast<const double*>(rs->stage.p), idx->n_rows, rs->d_bits, idx->cus, nullptr);
@@ -975,6 +979,16 @@ int qv_rowset_create_where(qv_rowset** out, qv_index* idx, const qv_column* cons
     if (rc != QV_OK) { (void)hipFree(rs->d_bits); rs->stage.release(); delete rs; return rc; }
     *out = rs;
     return QV_OK;
+}
+
+int qv_rowset_create_where(qv_rowset** out, qv_index* idx, const qv_column* const* cols, const int* ops,
+                           const double* literals, const uint32_t* lit_off, uint32_t n_preds) {
+    if (!out) return fail(QV_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    qv::WhereTable tab{};
+    { const int rc0 = where_check(idx, cols, ops, literals, lit_off, n_preds, tab); if (rc0 != QV_OK) return rc0; }
+    return rowset_from_where(idx, tab, literals, lit_off[n_preds], out);
 }
 
 int qv_rowset_combine(qv_rowset* dst, const qv_rowset* a, const qv_rowset* b, int op) {
@@ -1010,6 +1024,27 @@ int qv_rowset_read(const qv_rowset* rs, uint64_t* words_out, uint32_t n_words) {
     return QV_OK;
 }
 
+// A checked conjunction of qv_index_search_where: the table the kernels read and the caller's literals (valid until its call returns);
+// tab.n == 0: no predicate, every row.
+struct WhereSpec { qv::WhereTable tab; const double* lits; uint32_t n_lits; };
+static bool where_same(const WhereSpec& a, const WhereSpec& b) {      // bytewise equal: one evaluation serves both
+    return a.n_lits == b.n_lits && memcmp(&a.tab, &b.tab, sizeof(a.tab)) == 0 && (a.n_lits == 0 || memcmp(a.lits, b.lits, (size_t)a.n_lits * sizeof(double)) == 0);
+}
+// The filter of ONE query, as rowsets_plan / rowsets_enqueue / rowsets_direct take it: a set handle; or a conjunction that the call evaluates into
+// a TRANSIENT set in its own workspace (where_enqueue places `bits`; `anded`: the words are alive & where already, a candidate bitmap); or
+// neither: every row.  What the host cannot know of a transient set — its non-empty tiles, its rows, whether they are fewer than k — the plan
+// replaces by "every tile may hold a candidate"; a filter that selects fewer than k rows is decided on the device as for any set.
+struct RsFilter {
+    const qv_rowset* set = nullptr;
+    const WhereSpec* where = nullptr;
+    const uint64_t* bits = nullptr;
+    bool anded = false;
+};
+static bool rs_same(const RsFilter& a, const RsFilter& b) { return a.set == b.set && a.where == b.where && a.bits == b.bits; }
+static qv::RowSetRef rs_ref(const qv_index* idx, const RsFilter& f) {
+    return f.where ? qv::RowSetRef{f.bits, (uint32_t)(((uint64_t)idx->n_rows + 63) / 64), 0} : rowset_ref(f.set);
+}
+
 // How a call is cut into device work.  Up to kMaxFusedK results and two or more queries: ONE piece, the multi-query scans with a set
 // per query (qv_rowset.hip).  Otherwise runs of consecutive queries naming the same set, each through the paths of qv_index_search
 // over the candidate bitmap alive & set, formed on the device (k_rowset_and) — a single query takes the single-launch scans that
@@ -1017,39 +1052,103 @@ int qv_rowset_read(const qv_rowset* rs, uint64_t* words_out, uint32_t n_words) {
 // bound: a multi piece of 2 - 8 queries that the filtered bound-scan rule takes (launch_bound_scan_mq with the sets) — decided here, once, so
 // that the workspace and the launch agree.  cand_tiles: the tiles that hold a candidate of any query of the piece, as the host knows it: a
 // set counts its non-empty words (qv_rowset::tiles; tombstones are not subtracted), a null set every tile, a pass min(n_tiles, the sum).
+// Transient sets: a multi piece that holds one reports NO candidate tile, which the automatic rule declines and "always" still takes; a
+// single query is planned with every tile a candidate.  Either way a mis-route costs time, never bits.
 struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; };
-static uint32_t rowsets_cand_tiles(const qv_index* idx, const qv_rowset* const* sets, uint32_t nq) {
+static uint32_t rowsets_cand_tiles(const qv_index* idx, const RsFilter* fl, uint32_t nq) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     uint64_t sum = 0;
-    for (uint32_t q = 0; q < nq; q++) sum += sets[q] ? sets[q]->tiles : n_tiles;
+    for (uint32_t q = 0; q < nq; q++) {
+        if (fl[q].where) return 0;
+        sum += fl[q].set ? fl[q].set->tiles : n_tiles;
+    }
     return (uint32_t)std::min<uint64_t>(sum, n_tiles);
 }
-static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const qv_rowset* const* sets, std::vector<RowsetPiece>& pieces) {
-    const qv::ScanPlan plan = qv::plan_scan((idx->n_rows + 63) / 64, idx->cus);
+static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const RsFilter* fl, std::vector<RowsetPiece>& pieces) {
+    const uint32_t n_tiles = (idx->n_rows + 63) / 64;
+    const qv::ScanPlan plan = qv::plan_scan(n_tiles, idx->cus);
     pieces.clear();
     if (k <= (uint32_t)qv::kMaxFusedK && nq >= 2) {
-        const uint32_t ct = rowsets_cand_tiles(idx, sets, nq);
+        const uint32_t ct = rowsets_cand_tiles(idx, fl, nq);
         const bool bound = nq <= 8 && qv::bound_scan_applies_filtered(idx->view(), nq, k, ct);   // (9 or more are not cut into bound passes)
         pieces.push_back(RowsetPiece{0, nq, k, true, bound, ct});
-        return std::max(qv::rowset_workspace_bytes(plan, nq, k, idx->dim4), bound ? qv::bound_scan_mq_workspace_bytes(plan, nq, k, (idx->n_rows + 63) / 64, idx->dim) : (size_t)0);
+        return std::max(qv::rowset_workspace_bytes(plan, nq, k, idx->dim4), bound ? qv::bound_scan_mq_workspace_bytes(plan, nq, k, n_tiles, idx->dim) : (size_t)0);
     }
     size_t ws = 0;
     for (uint32_t q = 0; q < nq;) {
         uint32_t e = q + 1;
-        while (e < nq && sets[e] == sets[q]) e++;
+        while (e < nq && rs_same(fl[e], fl[q])) e++;
+        const qv_rowset* set = fl[q].set;
+        const bool transient = fl[q].where != nullptr;                // (only with k <= kMaxFusedK: the k > 64 form of qv_index_search_where makes real sets first)
         // (up to kMaxFusedK the lists are k long whatever the set holds: the scans pad, nothing is counted on the host)
-        const uint32_t kk = k <= (uint32_t)qv::kMaxFusedK ? k : (uint32_t)std::min<uint64_t>(k, rowset_live(idx, sets[q]));
+        const uint32_t kk = k <= (uint32_t)qv::kMaxFusedK ? k : (uint32_t)std::min<uint64_t>(k, rowset_live(idx, set));
         // (a set that selects fewer than kk rows has no threshold: the bound pass would only precede the exact scan that answers — reported
         //  as no candidate tile, which the automatic rule declines; "always" still takes the path)
-        const bool too_few = sets[q] && sets[q]->selected < kk;
-        pieces.push_back(RowsetPiece{q, e - q, kk, false, false, sets[q] && !too_few ? std::min<uint32_t>(sets[q]->tiles, (idx->n_rows + 63) / 64) : 0u});
-        if (kk) ws = std::max(ws, search_ws_bytes(idx, e - q, kk, k, e - q == 1, sets[q] ? pieces.back().cand_tiles : qv::kBoundNoFilter));   // (as rowsets_enqueue passes them on)
+        const bool too_few = !transient && set && set->selected < kk;
+        const uint32_t ct = transient ? n_tiles : (set && !too_few ? std::min<uint32_t>(set->tiles, n_tiles) : 0u);
+        pieces.push_back(RowsetPiece{q, e - q, kk, false, false, ct});
+        if (kk) ws = std::max(ws, search_ws_bytes(idx, e - q, kk, k, e - q == 1, set || transient ? ct : qv::kBoundNoFilter));   // (as rowsets_enqueue passes them on)
         q = e;
     }
     return ws;
 }
+
+// The conjunctions a call has to evaluate: bytewise-equal ones once.  uniq: the first query of each distinct one; slot[q]: which of
+// them query q reads (0xFFFFFFFF: none); lit_base: where each one's literals start when they are staged side by side; args_fit: every
+// one's literals fit the kernel arguments, nothing needs staging.
+struct WherePlan { std::vector<uint32_t> uniq, slot, lit_base; uint32_t n_lits = 0; bool args_fit = true; };
+static void where_plan(const RsFilter* fl, uint32_t nq, WherePlan& wp) {
+    wp.slot.assign(nq, 0xFFFFFFFFu);
+    std::multimap<uint64_t, uint32_t> seen;                            // hash of table and literals -> slot
+    for (uint32_t q = 0; q < nq; q++) {
+        const WhereSpec* w = fl[q].where;
+        if (!w) continue;
+        uint64_t h = 1469598103934665603ull;
+        auto mix = [&h](const void* p, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(p); for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ull; };
+        mix(&w->tab, sizeof(w->tab));
+        if (w->n_lits) mix(w->lits, (size_t)w->n_lits * sizeof(double));
+        uint32_t u = 0xFFFFFFFFu;
+        const auto range = seen.equal_range(h);
+        for (auto it = range.first; it != range.second; ++it)
+            if (where_same(*fl[wp.uniq[it->second]].where, *w)) { u = it->second; break; }
+        if (u == 0xFFFFFFFFu) {
+            u = (uint32_t)wp.uniq.size();
+            wp.uniq.push_back(q); wp.lit_base.push_back(wp.n_lits);
+            wp.n_lits += w->n_lits;
+            wp.args_fit = wp.args_fit && w->n_lits <= qv::kWhereArgLits;
+            seen.emplace(h, u);
+        }
+        wp.slot[q] = u;
+    }
+}
+static size_t where_stride_words(const qv_index* idx) { return ((((size_t)idx->n_rows + 63) / 64) * 8 + 255) / 256 * 256 / 8; }   // a transient set's words, 256-byte aligned
+// Enqueue the evaluations on s, in front of the call's scans: launches of up to kWhereMqFilters conjunctions (k_where_mq), conjunction u into
+// d_where + u * where_stride_words — or, for a call of ONE query, alive & where straight into d_mask: its candidate bitmap, no k_rowset_and.
+// d_lits: the literals staged on the device (wp.lit_base); null: they travel as kernel arguments (wp.args_fit).  Sets fl[q].bits / anded.
+static int where_enqueue(qv_index* idx, RsFilter* fl, uint32_t nq, const WherePlan& wp, uint64_t* d_where, uint64_t* d_mask, const double* d_lits, hipStream_t s) {
+    const bool lone = nq == 1;
+    const size_t stride = where_stride_words(idx);
+    for (size_t u0 = 0; u0 < wp.uniq.size(); u0 += qv::kWhereMqFilters) {
+        qv::WhereMqArgs a;
+        memset(&a, 0, sizeof(a));
+        a.n = (uint32_t)std::min<size_t>(qv::kWhereMqFilters, wp.uniq.size() - u0);
+        for (uint32_t i = 0; i < a.n; i++) {
+            const WhereSpec& w = *fl[wp.uniq[u0 + i]].where;
+            a.tab[i] = w.tab;
+            a.out[i] = lone ? d_mask : d_where + (u0 + i) * stride;
+            if (d_lits) a.lit_base[i] = wp.lit_base[u0 + i];
+            else if (w.n_lits) memcpy(a.lits[i], w.lits, (size_t)w.n_lits * sizeof(double));
+        }
+        hipError_t e = qv::launch_where_mq(a, d_lits, lone ? idx->d_alive : nullptr, idx->n_rows, idx->cus, s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "filter evaluation launch failed: %s", hipGetErrorString(e));
+    }
+    for (uint32_t q = 0; q < nq; q++)
+        if (fl[q].where) { fl[q].bits = lone ? d_mask : d_where + (size_t)wp.slot[q] * stride; fl[q].anded = lone; }
+    return QV_OK;
+}
+
 // enqueue the pieces on s: lists [nq][k], padded past every query's matches.  d_mask: (rows + 63) / 64 words for the candidate bitmaps.
-static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets, const std::vector<RowsetPiece>& pieces,
+static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const RsFilter* fl, const std::vector<RowsetPiece>& pieces,
                            void* ws, uint64_t* d_mask, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, uint32_t* d_tickets) {
     const qv::IndexView v = idx->view();
     const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
@@ -1059,7 +1158,7 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
         const float* q = d_queries + (size_t)p.q0 * idx->dim;
         if (p.multi) {
             std::vector<qv::RowSetRef> refs(p.nq);
-            for (uint32_t i = 0; i < p.nq; i++) refs[i] = rowset_ref(sets[p.q0 + i]);
+            for (uint32_t i = 0; i < p.nq; i++) refs[i] = rs_ref(idx, fl[p.q0 + i]);
             hipEvent_t ev0 = nullptr, ev1 = nullptr;
             if (idx->profiling && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
                 std::lock_guard<std::mutex> g(idx->prof_mu);
@@ -1079,9 +1178,11 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set pad launch failed: %s", hipGetErrorString(e));
             continue;
         }
+        const RsFilter& f = fl[p.q0];
         const uint64_t* cand = nullptr;
-        if (sets[p.q0]) {
-            hipError_t e = qv::launch_rowset_and(v, rowset_ref(sets[p.q0]), d_mask, s);
+        if (f.where && f.anded) cand = f.bits;                        // (where_enqueue wrote alive & where there)
+        else if (f.set || f.where) {
+            hipError_t e = qv::launch_rowset_and(v, rs_ref(idx, f), d_mask, s);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set bitmap launch failed: %s", hipGetErrorString(e));
             cand = d_mask;
         }
@@ -1098,27 +1199,26 @@ static int rowsets_check(const qv_index* idx, uint32_t nq, const qv_rowset* cons
     return QV_OK;
 }
 
-// one call's worth of queries in a context of the caller's own
-static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
+// one call's worth of queries in a context of the caller's own.  idx, queries, count_out, fl: checked by the entry points (each in its
+// own order), the filters valid; from the empty index on the order is one.
+static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const RsFilter* fl_in,
                           uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
     if (nq == 0) return QV_OK;
-    if (!queries || !count_out || !sets) return fail(QV_ERR_INVALID_ARG, "queries/sets/count_out is null");
-    { const int rc0 = rowsets_check(idx, nq, sets); if (rc0 != QV_OK) return rc0; }
     if (idx->n_live == 0) { for (uint32_t q = 0; q < nq; q++) count_out[q] = 0; return QV_OK; }      // exact.go:96-98
     if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");                             // exact.go:104-106
     if (!rows_out || !dist_out) return fail(QV_ERR_INVALID_ARG, "rows_out/dist_out is null");
     if (nq > kHostBatch) {
         for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {
-            const int rc0 = rowsets_direct(idx, queries + (size_t)q0 * idx->dim, std::min(kHostBatch, nq - q0), k, sets + q0,
+            const int rc0 = rowsets_direct(idx, queries + (size_t)q0 * idx->dim, std::min(kHostBatch, nq - q0), k, fl_in + q0,
                                            rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
             if (rc0 != QV_OK) return rc0;
         }
         return QV_OK;
     }
     HIPCHK(hipSetDevice(idx->device));
+    std::vector<RsFilter> fl(fl_in, fl_in + nq);                      // (the transient sets' words are placed below)
     std::vector<RowsetPiece> pieces;
-    const size_t ws_bytes = rowsets_plan(idx, nq, k, sets, pieces);
+    const size_t ws_bytes = rowsets_plan(idx, nq, k, fl.data(), pieces);
     bool any = false;
     for (const RowsetPiece& p : pieces) any = any || p.kk != 0;
     if (!any) {                                                       // no set holds a live row: nothing to run
@@ -1139,7 +1239,24 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
     if (!c->tickets.p) { if ((rc = c->tickets.ensure(256))) return rc; HIPCHK(hipMemsetAsync(c->tickets.p, 0, 256, c->stream)); }   // (on the stream that reads them: see stream_workspace)
     memcpy(c->h_q.p, queries, qbytes);
     HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, qbytes, hipMemcpyHostToDevice, c->stream));
-    rc = rowsets_enqueue(idx, static_cast<const float*>(c->d_q.p), nq, k, sets, pieces, c->ws.p, static_cast<uint64_t*>(c->d_mask.p),
+    WherePlan wp;
+    where_plan(fl.data(), nq, wp);
+    if (!wp.uniq.empty()) {                                           // the call's transient sets, in the context's own buffers, on its stream
+        if (nq > 1 && (rc = c->d_where.ensure(wp.uniq.size() * where_stride_words(idx) * 8))) return rc;
+        const double* d_lits = nullptr;
+        if (!wp.args_fit) {                                           // a long IN list: the literals side by side through the pinned buffer
+            const size_t lbytes = (size_t)wp.n_lits * sizeof(double);
+            if ((rc = c->h_lits.ensure(lbytes)) || (rc = c->d_lits.ensure(lbytes))) return rc;
+            for (size_t u = 0; u < wp.uniq.size(); u++) {
+                const WhereSpec& w = *fl[wp.uniq[u]].where;
+                if (w.n_lits) memcpy(static_cast<double*>(c->h_lits.p) + wp.lit_base[u], w.lits, (size_t)w.n_lits * sizeof(double));
+            }
+            HIPCHK(hipMemcpyAsync(c->d_lits.p, c->h_lits.p, lbytes, hipMemcpyHostToDevice, c->stream));
+            d_lits = static_cast<const double*>(c->d_lits.p);
+        }
+        if ((rc = where_enqueue(idx, fl.data(), nq, wp, static_cast<uint64_t*>(c->d_where.p), static_cast<uint64_t*>(c->d_mask.p), d_lits, c->stream))) return rc;
+    }
+    rc = rowsets_enqueue(idx, static_cast<const float*>(c->d_q.p), nq, k, fl.data(), pieces, c->ws.p, static_cast<uint64_t*>(c->d_mask.p),
                          static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<uint32_t*>(c->tickets.p));
     if (rc != QV_OK) return rc;
     HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
@@ -1156,30 +1273,52 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
     return QV_OK;
 }
 
+// qv_index_search_rowsets' own checks, in its order, in front of rowsets_direct
+static int rowsets_direct_sets(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
+                               uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (nq == 0) return QV_OK;
+    if (!queries || !count_out || !sets) return fail(QV_ERR_INVALID_ARG, "queries/sets/count_out is null");
+    { const int rc0 = rowsets_check(idx, nq, sets); if (rc0 != QV_OK) return rc0; }
+    std::vector<RsFilter> fl(nq);
+    for (uint32_t q = 0; q < nq; q++) fl[q].set = sets[q];
+    return rowsets_direct(idx, queries, nq, k, fl.data(), rows_out, dist_out, count_out);
+}
+
+// Callers that may share a pass (coalesce_applies holds, every filter is valid): through the ONE front of the filtered searches, whichever
+// kind of filter they carry — a member's tag is its array of nq RsFilter, valid until its call returns.  The leader runs the group as one
+// call: its conjunctions are evaluated together in front of the pass (where_enqueue), its handles read as they are.
+static int rowsets_submit(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const RsFilter* fl,
+                          uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    configure_front(idx, idx->front_rs);
+    char err[256]; err[0] = 0;
+    const int rc = idx->front_rs.submit(
+        0, queries, nq, idx->dim, k, rows_out, dist_out, count_out, nullptr,
+        [&] { return rowsets_direct(idx, queries, nq, k, fl, rows_out, dist_out, count_out); },
+        [&](qvco::Group& g, auto&) {
+            g.size_outputs(false);
+            std::vector<RsFilter> all(g.nq);                          // the members' filters side by side, in the order of the group's query block
+            for (uint32_t mi = 0; mi < g.n_mem; mi++) {
+                const qvco::Member& m = g.mbuf[mi];
+                const RsFilter* mf = static_cast<const RsFilter*>(m.tag);
+                for (uint32_t i = 0; i < m.nq; i++) all[m.q0 + i] = mf[i];
+            }
+            return rowsets_direct(idx, g.queries(), g.nq, g.kmax, all.data(), g.rows.data(), g.dist.data(), g.count.data());
+        },
+        [] { return qv_last_error(); }, err, sizeof(err), fl);
+    if (rc != QV_OK && err[0]) return fail(rc, "%s", err);
+    return rc;
+}
+
 int qv_index_search_rowsets(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
                             uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
     // callers that may share a pass: qv_index_search's rule, with a valid set per query on top (a request that fails a check runs
     // on its own and reports its error in the usual order)
     if (!coalesce_applies(idx, queries, nq, k, rows_out, dist_out, count_out) || !sets || rowsets_check(idx, nq, sets) != QV_OK)
-        return rowsets_direct(idx, queries, nq, k, sets, rows_out, dist_out, count_out);
-    configure_front(idx, idx->front_rs);
-    char err[256]; err[0] = 0;
-    const int rc = idx->front_rs.submit(
-        0, queries, nq, idx->dim, k, rows_out, dist_out, count_out, nullptr,
-        [&] { return rowsets_direct(idx, queries, nq, k, sets, rows_out, dist_out, count_out); },
-        [&](qvco::Group& g, auto&) {
-            g.size_outputs(false);
-            std::vector<const qv_rowset*> all(g.nq, nullptr);         // the members' sets side by side, in the order of the group's query block
-            for (uint32_t mi = 0; mi < g.n_mem; mi++) {
-                const qvco::Member& m = g.mbuf[mi];
-                const qv_rowset* const* ms = static_cast<const qv_rowset* const*>(m.tag);
-                for (uint32_t i = 0; i < m.nq; i++) all[m.q0 + i] = ms[i];
-            }
-            return rowsets_direct(idx, g.queries(), g.nq, g.kmax, all.data(), g.rows.data(), g.dist.data(), g.count.data());
-        },
-        [] { return qv_last_error(); }, err, sizeof(err), sets);
-    if (rc != QV_OK && err[0]) return fail(rc, "%s", err);
-    return rc;
+        return rowsets_direct_sets(idx, queries, nq, k, sets, rows_out, dist_out, count_out);
+    RsFilter fl[kCoalesceMaxNq];
+    for (uint32_t q = 0; q < nq; q++) fl[q].set = sets[q];
+    return rowsets_submit(idx, queries, nq, k, fl, rows_out, dist_out, count_out);
 }
 
 int qv_index_rowset_coalesce_stats(qv_index* idx, uint64_t out[8]) {
@@ -1204,15 +1343,130 @@ int qv_index_search_rowsets_device(qv_index* idx, const float* d_queries, uint32
     }
     for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {                // bound the workspace, as the host-pointer form does
         const uint32_t m = std::min(kHostBatch, nq - q0);
+        std::vector<RsFilter> fl(m);
+        for (uint32_t q = 0; q < m; q++) fl[q].set = sets[q0 + q];
         std::vector<RowsetPiece> pieces;
-        const size_t ws_bytes = (rowsets_plan(idx, m, k, sets + q0, pieces) + 255) / 256 * 256;
+        const size_t ws_bytes = (rowsets_plan(idx, m, k, fl.data(), pieces) + 255) / 256 * 256;
         const size_t words = ((size_t)idx->n_rows + 63) / 64;
         void* ws = nullptr;
         std::unique_lock<std::mutex> ws_hold;
         uint32_t* tickets = nullptr;
         int rc = stream_workspace(idx, s, ws_bytes + words * 8, &ws, &ws_hold, &tickets);
         if (rc != QV_OK) return rc;
-        rc = rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, sets + q0, pieces, ws, reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes),
+        rc = rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, ws, reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes),
+                             d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, s, tickets);
+        if (rc != QV_OK) return rc;
+    }
+    return QV_OK;
+}
+
+// ---------------------------------------------------------------- filtered search by predicate: the sets live in the call's workspace --
+// filters[q] checked by qv_rowset_create_where's own function; n_preds == 0: every row.  The message names the query.
+static int where_spec(const qv_index* idx, const qv_where& w, uint32_t q, WhereSpec& out) {
+    memset(&out, 0, sizeof(out));
+    if (w.n_preds == 0) return QV_OK;
+    const int rc = where_check(idx, w.cols, w.ops, w.literals, w.lit_off, w.n_preds, out.tab);
+    if (rc != QV_OK) {
+        char msg[400];
+        snprintf(msg, sizeof(msg), "%s", qv_last_error());
+        return fail(rc, "filter of query %u: %s", q, msg);
+    }
+    out.lits = w.literals; out.n_lits = w.lit_off[w.n_preds];
+    return QV_OK;
+}
+
+// k > 64: runs of consecutive queries with bytewise-equal filters as a temporary REAL set each (the existing internals: an allocation, the
+// null stream, the mirror — the selection and ranking paths clamp their list lengths to counts only the host mirror has), then the set
+// paths of qv_index_search_rowsets; the sets are freed before return
+static int where_wide(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const WhereSpec* specs,
+                      uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    std::vector<qv_rowset*> made;
+    std::vector<RsFilter> fl(nq);
+    int rc = QV_OK;
+    for (uint32_t q = 0; q < nq && rc == QV_OK;) {
+        uint32_t e = q + 1;
+        while (e < nq && where_same(specs[e], specs[q])) e++;
+        if (specs[q].tab.n) {
+            qv_rowset* rs = nullptr;
+            rc = rowset_from_where(idx, specs[q].tab, specs[q].lits, specs[q].n_lits, &rs);
+            if (rc == QV_OK) { made.push_back(rs); for (uint32_t i = q; i < e; i++) fl[i].set = rs; }
+        }
+        q = e;
+    }
+    if (rc == QV_OK) rc = rowsets_direct(idx, queries, nq, k, fl.data(), rows_out, dist_out, count_out);
+    char msg[400];
+    if (rc != QV_OK) snprintf(msg, sizeof(msg), "%s", qv_last_error());
+    for (qv_rowset* rs : made) qv_rowset_destroy(rs);
+    return rc == QV_OK ? QV_OK : fail(rc, "%s", msg);
+}
+
+int qv_index_search_where(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_where* filters,
+                          uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (nq == 0) return QV_OK;
+    if (!queries || !count_out || !filters) return fail(QV_ERR_INVALID_ARG, "queries/filters/count_out is null");
+    if (idx->n_live == 0) { for (uint32_t q = 0; q < nq; q++) count_out[q] = 0; return QV_OK; }      // qv_index_search_rowsets' order: exact.go:96-98
+    if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");                             // exact.go:104-106
+    if (!rows_out || !dist_out) return fail(QV_ERR_INVALID_ARG, "rows_out/dist_out is null");
+    WhereSpec small_specs[kCoalesceMaxNq];                            // (a single-query caller allocates nothing)
+    RsFilter small_fl[kCoalesceMaxNq];
+    std::vector<WhereSpec> big_specs;
+    std::vector<RsFilter> big_fl;
+    WhereSpec* specs = small_specs; RsFilter* fl = small_fl;
+    if (nq > kCoalesceMaxNq) { big_specs.resize(nq); big_fl.resize(nq); specs = big_specs.data(); fl = big_fl.data(); }
+    for (uint32_t q = 0; q < nq; q++) {
+        const int rc0 = where_spec(idx, filters[q], q, specs[q]);
+        if (rc0 != QV_OK) return rc0;
+    }
+    if (k > (uint32_t)qv::kMaxFusedK) return where_wide(idx, queries, nq, k, specs, rows_out, dist_out, count_out);
+    for (uint32_t q = 0; q < nq; q++) fl[q].where = specs[q].tab.n ? &specs[q] : nullptr;
+    if (!coalesce_applies(idx, queries, nq, k, rows_out, dist_out, count_out)) return rowsets_direct(idx, queries, nq, k, fl, rows_out, dist_out, count_out);
+    return rowsets_submit(idx, queries, nq, k, fl, rows_out, dist_out, count_out);
+}
+
+int qv_index_search_where_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const qv_where* filters,
+                                 uint32_t* d_rows_out, float* d_dist_out, void* stream) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (nq == 0) return QV_OK;
+    if (!d_queries || !d_rows_out || !d_dist_out) return fail(QV_ERR_INVALID_ARG, "null device pointer");
+    if (!filters) return fail(QV_ERR_INVALID_ARG, "filters is null");
+    if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");
+    if (k > (uint32_t)qv::kMaxFusedK)
+        return fail(QV_ERR_UNSUPPORTED, "the device-pointer form takes k <= %d (longer lists need a set's host mirror): got %u", qv::kMaxFusedK, k);
+    std::vector<WhereSpec> specs(nq);
+    for (uint32_t q = 0; q < nq; q++) {
+        const int rc0 = where_spec(idx, filters[q], q, specs[q]);
+        if (rc0 != QV_OK) return rc0;
+    }
+    // the literals travel as kernel arguments: a staging buffer would be overwritten by the stream's next call while this one is still enqueued
+    for (uint32_t q = 0; q < nq; q++)
+        if (specs[q].n_lits > qv::kWhereArgLits)
+            return fail(QV_ERR_UNSUPPORTED, "filter of query %u carries %u literals: the device-pointer form takes up to %u per filter", q, specs[q].n_lits, qv::kWhereArgLits);
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (idx->n_live == 0 || idx->n_rows == 0) {
+        hipError_t e = qv::launch_rowset_pad(d_rows_out, d_dist_out, (size_t)nq * k, s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set pad launch failed: %s", hipGetErrorString(e));
+        return QV_OK;
+    }
+    const size_t stride = where_stride_words(idx) * 8;                // the candidate bitmap, and each transient set behind it: 256-byte aligned
+    for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {
+        const uint32_t m = std::min(kHostBatch, nq - q0);
+        std::vector<RsFilter> fl(m);
+        for (uint32_t q = 0; q < m; q++) fl[q].where = specs[q0 + q].tab.n ? &specs[q0 + q] : nullptr;
+        std::vector<RowsetPiece> pieces;
+        const size_t ws_bytes = (rowsets_plan(idx, m, k, fl.data(), pieces) + 255) / 256 * 256;
+        WherePlan wp;
+        where_plan(fl.data(), m, wp);
+        void* ws = nullptr;
+        std::unique_lock<std::mutex> ws_hold;
+        uint32_t* tickets = nullptr;
+        int rc = stream_workspace(idx, s, ws_bytes + stride + (m > 1 ? wp.uniq.size() * stride : 0), &ws, &ws_hold, &tickets);
+        if (rc != QV_OK) return rc;
+        uint64_t* d_mask = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes);
+        uint64_t* d_where = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes + stride);
+        if ((rc = where_enqueue(idx, fl.data(), m, wp, d_where, d_mask, nullptr, s))) return rc;
+        rc = rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, ws, d_mask,
                              d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, s, tickets);
         if (rc != QV_OK) return rc;
     }

@@ -68,9 +68,11 @@ struct SearchCtx {
     hipStream_t stream = nullptr;
     Buf d_q, d_rows, d_dist, d_ids, d_mask, ws, tickets;
     PinBuf h_q, h_rows, h_dist, h_ids, h_mask, h_flag;
+    Buf d_where, d_lits; PinBuf h_lits;      // qv_index_search_where: the call's transient sets, and its literals when they do not fit the kernel arguments
     uint32_t flag_seq = 0;                   // sequence number the small scan writes into h_flag when its results are in h_rows / h_dist
     void release() {
         d_q.release(); d_rows.release(); d_dist.release(); d_ids.release(); d_mask.release(); ws.release(); tickets.release();
+        d_where.release(); d_lits.release(); h_lits.release();
         h_q.release(); h_rows.release(); h_dist.release(); h_ids.release(); h_mask.release(); h_flag.release();
         if (stream) (void)hipStreamDestroy(stream);
         stream = nullptr;

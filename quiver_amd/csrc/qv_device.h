@@ -277,6 +277,21 @@ struct WhereTable { WherePred p[kWherePreds]; uint32_t n; uint32_t pad_; };
 // d_out[t] = the rows r < n_rows of tile t for which every predicate holds, for all ceil(n_rows / 64) tiles (bits past n_rows: zero).
 // The table travels as kernel arguments; d_lits is on the device.
 hipError_t launch_rowset_where(const WhereTable& tab, const double* d_lits, uint32_t n_rows, uint64_t* d_out, int cus, hipStream_t s);
+// Several conjunctions in ONE launch (k_where_mq: grid y = the filter), for the sets that live only as long as a search call
+// (qv_index_search_where): filter f < n writes its words to out[f] (ceil(n_rows / 64) of them).  Everything travels as KERNEL
+// ARGUMENTS, 3.7 KiB of the 4 KiB there are — which is what fixes kWhereMqFilters.  Literals: d_lits == null — filter f's are lits[f]
+// (at most kWhereArgLits of them; WherePred::lit0 counts from 0 there), nothing for a device-pointer call to stage; otherwise
+// d_lits[lit_base[f] + lit0 ...] on the device.  d_alive != null: the words are ANDed with the index's alive words (a candidate bitmap outright).
+constexpr uint32_t kWhereMqFilters = 8;                 // QV_WHERE_FILTERS_PER_LAUNCH of include/qv.h
+constexpr uint32_t kWhereArgLits = 16;                  // QV_WHERE_DEVICE_LITERALS of include/qv.h
+struct WhereMqArgs {
+    WhereTable tab[kWhereMqFilters];
+    double lits[kWhereMqFilters][kWhereArgLits];
+    uint64_t* out[kWhereMqFilters];
+    uint32_t lit_base[kWhereMqFilters];
+    uint32_t n; uint32_t pad_;
+};
+hipError_t launch_where_mq(const WhereMqArgs& a, const double* d_lits, const uint64_t* d_alive, uint32_t n_rows, int cus, hipStream_t s);
 // d_dst[t] = a[t] OP b[t] (QV_SET_*) for t < words; a set shorter than that reads as zeros; d_dst may be a.bits or b.bits
 hipError_t launch_rowset_combine(const RowSetRef& a, const RowSetRef& b, int op, uint32_t words, uint64_t* d_dst, hipStream_t s);
 // presence bits of rows [first_row, first_row + n): bit = d_bytes[i] != 0 (null: all set); every other bit of the words stays

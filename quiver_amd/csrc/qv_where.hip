@@ -75,6 +75,46 @@ __device__ __forceinline__ void where_pred(const WherePred& p, LP lits, uint32_t
     }
 }
 
+// The body of one wave's group of U consecutive tiles from t0, for both kernels below — the ONE statement of a conjunction: start from
+// the mask of rows below n_rows (ANDed with the index's alive words where the caller wants a candidate bitmap outright), per predicate
+// the presence words and where_pred, a tile whose word is zero reading nothing more; lane u < U then stores tile t0 + u's word.
+template <int U, typename LP>
+__device__ __forceinline__ void where_tiles(const WhereTable& tab, LP lits, const uint64_t* __restrict__ alive, uint32_t t0, uint32_t lane,
+                                            uint32_t n_rows, uint32_t n_tiles, uint64_t* __restrict__ out) {
+    constexpr int kWhereTiles = U;
+    uint64_t acc[kWhereTiles];
+#pragma unroll
+    for (int u = 0; u < kWhereTiles; u++) {
+        const uint64_t r0 = (uint64_t)(t0 + u) * 64;
+        acc[u] = r0 + 64 <= n_rows ? ~0ull : (r0 < n_rows ? (1ull << (n_rows - r0)) - 1 : 0ull);
+        if (alive != nullptr && acc[u]) acc[u] &= alive[t0 + u];          // (acc != 0: the tile is inside the index)
+    }
+#pragma unroll
+    for (int pi = 0; pi < (int)kWherePreds; pi++) {
+        if ((uint32_t)pi >= tab.n) break;
+        const WherePred& p = tab.p[pi];
+        bool any = false;
+#pragma unroll
+        for (int u = 0; u < kWhereTiles; u++) {
+            if (acc[u]) {                                         // a tile whose word is zero reads nothing more, its presence word included
+                const uint64_t pres = t0 + u < p.tiles ? p.present[t0 + u] : 0ull;    // a column shorter than the index: no value
+                acc[u] &= p.op == QV_PRED_ABSENT ? ~pres : pres;
+            }
+            any = any || acc[u] != 0;
+        }
+        if (!any) break;
+        if (p.op == QV_PRED_PRESENT || p.op == QV_PRED_ABSENT) continue;
+        if (p.type == QV_COL_F64) where_pred<double, U>(p, lits, t0, lane, acc);
+        else where_pred<uint32_t, U>(p, lits, t0, lane, acc);
+    }
+    if (lane < (uint32_t)kWhereTiles && t0 + lane < n_tiles) {
+        uint64_t w = acc[0];
+#pragma unroll
+        for (int u = 1; u < kWhereTiles; u++) w = lane == (uint32_t)u ? acc[u] : w;
+        out[t0 + lane] = w;
+    }
+}
+
 template <int U, bool LDS>
 __global__ void __launch_bounds__(kWhereBlock)
 k_rowset_where(WhereTable tab, const double* __restrict__ lits, uint32_t n_lits, uint32_t n_rows, uint32_t n_tiles, uint64_t* __restrict__ out) {
@@ -88,43 +128,25 @@ k_rowset_where(WhereTable tab, const double* __restrict__ lits, uint32_t n_lits,
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t waves = gridDim.x * (kWhereBlock / 64);
     for (uint32_t g = blockIdx.x * (kWhereBlock / 64) + wave; (uint64_t)g * kWhereTiles < n_tiles; g += waves) {
-        const uint32_t t0 = g * kWhereTiles;
-        uint64_t acc[kWhereTiles];
-#pragma unroll
-        for (int u = 0; u < kWhereTiles; u++) {
-            const uint64_t r0 = (uint64_t)(t0 + u) * 64;
-            acc[u] = r0 + 64 <= n_rows ? ~0ull : (r0 < n_rows ? (1ull << (n_rows - r0)) - 1 : 0ull);
-        }
-#pragma unroll
-        for (int pi = 0; pi < (int)kWherePreds; pi++) {
-            if ((uint32_t)pi >= tab.n) break;
-            const WherePred& p = tab.p[pi];
-            bool any = false;
-#pragma unroll
-            for (int u = 0; u < kWhereTiles; u++) {
-                if (acc[u]) {                                         // a tile whose word is zero reads nothing more, its presence word included
-                    const uint64_t pres = t0 + u < p.tiles ? p.present[t0 + u] : 0ull;    // a column shorter than the index: no value
-                    acc[u] &= p.op == QV_PRED_ABSENT ? ~pres : pres;
-                }
-                any = any || acc[u] != 0;
-            }
-            if (!any) break;
-            if (p.op == QV_PRED_PRESENT || p.op == QV_PRED_ABSENT) continue;
-            if constexpr (LDS) {
-                if (p.type == QV_COL_F64) where_pred<double, U>(p, static_cast<const double*>(s_lits), t0, lane, acc);
-                else where_pred<uint32_t, U>(p, static_cast<const double*>(s_lits), t0, lane, acc);
-            } else {
-                if (p.type == QV_COL_F64) where_pred<double, U>(p, lits, t0, lane, acc);
-                else where_pred<uint32_t, U>(p, lits, t0, lane, acc);
-            }
-        }
-        if (lane < (uint32_t)kWhereTiles && t0 + lane < n_tiles) {
-            uint64_t w = acc[0];
-#pragma unroll
-            for (int u = 1; u < kWhereTiles; u++) w = lane == (uint32_t)u ? acc[u] : w;
-            out[t0 + lane] = w;
-        }
+        if constexpr (LDS) where_tiles<U>(tab, static_cast<const double*>(s_lits), nullptr, g * kWhereTiles, lane, n_rows, n_tiles, out);
+        else where_tiles<U>(tab, lits, nullptr, g * kWhereTiles, lane, n_rows, n_tiles, out);
     }
+}
+
+// Up to kWhereMqFilters conjunctions in one launch, for qv_index_search_where: grid y = the filter, grid x = k_rowset_where's grid-stride
+// over groups of kWhereTiles tiles; filter f writes a.out[f].  The filters of a launch mostly name the same columns, so their value tiles
+// meet in the cache (the per-predicate load chain that profiles/rowset_where_notes.md names as the limit is where_tiles', unchanged).
+// ARGLITS: the literals are a.lits[f] in the kernel-argument segment (uniform loads, like the table); otherwise lits + a.lit_base[f].
+template <int U, bool ARGLITS>
+__global__ void __launch_bounds__(kWhereBlock)
+k_where_mq(WhereMqArgs a, const double* __restrict__ lits, const uint64_t* __restrict__ alive, uint32_t n_rows, uint32_t n_tiles) {
+    const uint32_t f = blockIdx.y;                                    // (the launch's grid y is a.n)
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t waves = gridDim.x * (kWhereBlock / 64);
+    const double* fl = ARGLITS ? a.lits[f] : lits + a.lit_base[f];
+    for (uint32_t g = blockIdx.x * (kWhereBlock / 64) + wave; (uint64_t)g * U < n_tiles; g += waves)
+        where_tiles<U>(a.tab[f], fl, alive, g * U, lane, n_rows, n_tiles, a.out[f]);
 }
 
 // The shape is kWhereTiles tiles per wave, literals as kWhereLdsLits says: what profiles/rowset_where_notes.md measured best.  The
@@ -152,6 +174,24 @@ hipError_t launch_rowset_where(const WhereTable& tab, const double* d_lits, uint
 #else
     launch_where<kWhereTiles, kWhereLdsLits != 0>(tab, d_lits, n_lits, n_rows, n_tiles, d_out, cus, s);
 #endif
+    return hipGetLastError();
+}
+
+hipError_t launch_where_mq(const WhereMqArgs& a, const double* d_lits, const uint64_t* d_alive, uint32_t n_rows, int cus, hipStream_t s) {
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)n_rows + 63) / 64);
+    if (n_tiles == 0 || a.n == 0) return hipSuccess;
+    if (a.n > kWhereMqFilters) return hipErrorInvalidValue;
+    for (uint32_t f = 0; f < a.n; f++) {
+        const WhereTable& t = a.tab[f];
+        if (t.n > kWherePreds || !a.out[f]) return hipErrorInvalidValue;
+        const uint32_t n_lits = t.n ? t.p[t.n - 1].lit0 + t.p[t.n - 1].n_lit : 0;
+        if (n_lits > (d_lits ? kWherePreds * kWhereLits : kWhereArgLits)) return hipErrorInvalidValue;
+    }
+    const uint32_t groups = (n_tiles + kWhereTiles - 1) / kWhereTiles;
+    const uint32_t want = (groups + kWhereBlock / 64 - 1) / (kWhereBlock / 64);
+    const uint32_t grid = std::max(1u, std::min(want, (uint32_t)cus * 8u));      // as launch_where: every wave slot per filter row of the grid, grid stride beyond
+    if (d_lits) hipLaunchKernelGGL((k_where_mq<kWhereTiles, false>), dim3(grid, a.n), dim3(kWhereBlock), 0, s, a, d_lits, d_alive, n_rows, n_tiles);
+    else hipLaunchKernelGGL((k_where_mq<kWhereTiles, true>), dim3(grid, a.n), dim3(kWhereBlock), 0, s, a, d_lits, d_alive, n_rows, n_tiles);
     return hipGetLastError();
 }
 

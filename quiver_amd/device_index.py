@@ -23,6 +23,83 @@ def scan_bound_applies_filtered(metric, dim: int, rows: int, nq: int, k: int, mo
     return bool(rc)
 
 
+PREDICATES = {"==": 0, "=": 0, "eq": 0, "!=": 1, "ne": 1, "<": 2, "lt": 2, "<=": 3, "le": 3, ">": 4, "gt": 4, ">=": 5, "ge": 5,
+              "in": 6, "not_in": 7, "present": 8, "absent": 9}
+WHERE_FILTERS_PER_LAUNCH = 8                     # QV_WHERE_FILTERS_PER_LAUNCH of include/qv.h
+WHERE_DEVICE_LITERALS = 16                       # QV_WHERE_DEVICE_LITERALS
+
+
+class QvWhere(C.Structure):
+    """qv_where of include/qv.h: one conjunction, the arguments of qv_rowset_create_where"""
+    _fields_ = [("cols", C.POINTER(C.c_void_p)), ("ops", C.POINTER(C.c_int)), ("literals", C.POINTER(C.c_double)),
+                ("lit_off", C.POINTER(C.c_uint32)), ("n_preds", C.c_uint32)]
+
+
+def _is_predicate(x) -> bool:
+    return isinstance(x, tuple) and len(x) == 3 and isinstance(x[1], (str, int, np.integer)) and not isinstance(x[1], bool)
+
+
+def broadcast_filters(filters, nq: int) -> list:
+    """the `filters` argument of DeviceIndex.search_where as one list of predicates per query: None -> no predicate for any query; ONE
+    list of (column, op, literal_or_list) tuples -> that list for every query; otherwise a sequence of nq entries, each such a list or
+    None (no predicate: every row).  Pure."""
+    if filters is None:
+        return [[] for _ in range(nq)]
+    filters = list(filters)
+    if all(_is_predicate(f) for f in filters):              # (an empty list: the empty conjunction for every query)
+        return [list(filters) for _ in range(nq)]
+    if len(filters) != nq:
+        raise ValueError("filters must be None, one list of predicates, or one list (or None) per query (%d), got %d" % (nq, len(filters)))
+    out = []
+    for i, f in enumerate(filters):
+        f = [] if f is None else list(f)
+        if not all(_is_predicate(p) for p in f):
+            raise TypeError("filters[%d] is not a list of (column, op, literal_or_list) tuples" % i)
+        out.append(f)
+    return out
+
+
+def pack_predicates(preds, handle_of=None):
+    """one conjunction as the arrays qv_where points to -> (column handles [n] uint64, ops [n] int32, literals float64, lit_off [n + 1]
+    uint32).  op: a key of PREDICATES or a QV_PRED_* code; a literal: None, a number or a list of numbers.  handle_of(column) -> the
+    qv_column handle as an int (the default reads Column.handle).  Pure: no library call."""
+    if handle_of is None:
+        def handle_of(col):
+            if not isinstance(col, Column):
+                raise TypeError("a predicate does not name a Column")
+            return col.handle.value
+    preds = list(preds)
+    n = len(preds)
+    cols = np.zeros(n, dtype=np.uint64)
+    ops = np.zeros(n, dtype=np.int32)
+    off = np.zeros(n + 1, dtype=np.uint32)
+    lits = []
+    for i, (col, op, lit) in enumerate(preds):
+        cols[i] = handle_of(col) or 0
+        ops[i] = PREDICATES[op.lower()] if isinstance(op, str) else int(op)
+        if lit is not None:
+            lits.extend(np.asarray(lit, dtype=np.float64).ravel().tolist())
+        off[i + 1] = len(lits)
+    return cols, ops, np.asarray(lits, dtype=np.float64), off
+
+
+def pack_where(per_query, handle_of=None):
+    """lists of predicates, one per query -> (a ctypes array of QvWhere, the numpy arrays it points into: keep them until the call
+    has returned).  Pure: no library call."""
+    arr = (QvWhere * max(len(per_query), 1))()
+    keep = []
+    for q, preds in enumerate(per_query):
+        cols, ops, lits, off = pack_predicates(preds, handle_of)
+        keep.append((cols, ops, lits, off))
+        w = arr[q]
+        w.n_preds = len(cols)
+        w.cols = C.cast(cols.ctypes.data, C.POINTER(C.c_void_p)) if cols.size else None
+        w.ops = C.cast(ops.ctypes.data, C.POINTER(C.c_int)) if ops.size else None
+        w.literals = C.cast(lits.ctypes.data, C.POINTER(C.c_double)) if lits.size else None
+        w.lit_off = C.cast(off.ctypes.data, C.POINTER(C.c_uint32))
+    return arr, keep
+
+
 class DeviceIndex:
     default_filter = "auto"        # the filter kernel new indexes choose (set_filter); tests and bench.py compare the kernels through it
 
@@ -211,8 +288,7 @@ class DeviceIndex:
     # ---- facet columns: row sets from predicates, on the device ----
     COLUMN_TYPES = {"f64": 0, "u32": 1}
 
-    PREDICATES = {"==": 0, "=": 0, "eq": 0, "!=": 1, "ne": 1, "<": 2, "lt": 2, "<=": 3, "le": 3, ">": 4, "gt": 4, ">=": 5, "ge": 5,
-                  "in": 6, "not_in": 7, "present": 8, "absent": 9}
+    PREDICATES = PREDICATES                      # (the module's table: pack_predicates reads the same one)
 
     def column(self, type) -> "Column":
         """one typed value per row of this index, resident on its device (qv_column_create): "f64" (a JSON number) or "u32" (a
@@ -244,6 +320,36 @@ class DeviceIndex:
         check(lib().qv_rowset_create_where(C.byref(rs._h), self._h, cols, ops, lit_arr.ctypes.data if lit_arr.size else None, off.ctypes.data, n))
         del preds                                           # (kept the Column objects alive across the call)
         return rs
+
+    def search_where(self, queries, k: int, filters):
+        """exact top-k of every query among the live rows that pass ITS conjunction of column predicates, evaluated on the device inside
+        the call (qv_index_search_where): no RowSet is made, nothing but the results comes back.  `filters`: one list of (column, op,
+        literal_or_list) per query (as rowset_where takes; None or [] = every row), or ONE such list for all queries, or None.
+        -> (rows [nq,k] uint32, dist [nq,k] float32, count [nq] uint32), what search_rowsets returns for the sets rowset_where makes."""
+        q = _f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dimension mismatch: expected {self.dim}, got {q.shape[1]}")
+        nq = q.shape[0]
+        per_query = broadcast_filters(filters, nq)
+        arr, keep = pack_where(per_query)
+        kk = max(int(k), 0)
+        rows = np.full((nq, max(kk, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full((nq, max(kk, 1)), np.inf, dtype=np.float32)
+        count = np.zeros(nq, dtype=np.uint32)
+        check(lib().qv_index_search_where(self._h, q.ctypes.data, nq, kk, arr, rows.ctypes.data, dist.ctypes.data, count.ctypes.data))
+        del keep, per_query                                # (kept the arrays and the Column objects alive across the call)
+        return rows[:, :kk], dist[:, :kk], count
+
+    def search_where_device(self, d_queries: int, nq: int, k: int, filters, d_rows_out: int, d_dist_out: int, stream: int = 0):
+        """the same with queries / results on the device; enqueues on `stream`, no synchronisation (qv_index_search_where_device).
+        k <= 64 and at most WHERE_DEVICE_LITERALS literals per filter, else QvError(QV_ERR_UNSUPPORTED) with nothing enqueued; the
+        filter arrays are read before the call returns."""
+        per_query = broadcast_filters(filters, nq)
+        arr, keep = pack_where(per_query)
+        check(lib().qv_index_search_where_device(self._h, d_queries, nq, k, arr, d_rows_out, d_dist_out, stream))
+        del keep, per_query
 
     def rowset_coalesce_stats(self) -> dict:
         out = (C.c_uint64 * 8)()

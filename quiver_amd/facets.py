@@ -167,6 +167,16 @@ def plan(filters, dictionaries):
     return out
 
 
+def fused_predicates(pl):
+    """the predicates of a plan that ONE qv_index_search_where conjunction expresses — every filter a single term, 1 to 8 predicates in
+    all — or None: the plan needs set algebra (a mixed-type field), more passes, matches no row, or holds no filter (FacetColumns.rowset
+    then answers for the snapshot's rows only).  Pure: reads the plan."""
+    if not pl or any(len(terms) != 1 for terms in pl):
+        return None
+    preds = [p for terms in pl for p in terms[0]]
+    return preds if 1 <= len(preds) <= MAX_PREDS else None
+
+
 def _eval_pred(p, arrays):
     vals, pres = arrays[p.field][p.kind]
     if p.op == PRESENT:
@@ -281,3 +291,16 @@ class FacetColumns:
             else:
                 out.combine(out, any_term, "and"); any_term.close()
         return out
+
+    def search(self, queries, k, filters):
+        """DeviceIndex.search_rowsets over rowset(filters) for every query, without making the set where one conjunction expresses the
+        filters (fused_predicates): then the predicates are evaluated inside the search call (DeviceIndex.search_where).  Otherwise the
+        set is made, searched and closed.  -> (rows, dist, count)"""
+        preds = fused_predicates(plan(filters, self.dictionaries))
+        if preds is not None:
+            return self.index.search_where(queries, k, [(self.columns[p.field][p.kind], p.op, p.literals or None) for p in preds])
+        s = self.rowset(filters)
+        try:
+            return self.index.search_rowsets(queries, k, s)
+        finally:
+            s.close()
