@@ -107,8 +107,9 @@ typedef enum qv_status {
                                     accelerator, never a requirement: an index whose copy cannot be allocated carries on without it.
                                     Wherever they keep that copy by default, indexes whose dimension is a multiple of 16 up to 4096
                                     also keep an 8-bit plane of the rows with a scale and a residual per row (+dim + 8 bytes per
-                                    row: 4616 -> 5392 at 768 dimensions), on which a single unfiltered query rejects rows first
-                                    (qv_index_set_bound_plane).  This flag leaves out both; an 8-bit plane that cannot be
+                                    row: 4616 -> 5392 at 768 dimensions), on which a single query rejects rows first — unfiltered
+                                    (qv_index_set_bound_plane) or under a mask, a row set or a where-filter
+                                    (qv_index_set_bound_plane_filtered).  This flag leaves out both; an 8-bit plane that cannot be
                                     allocated is given up alone and searches start on the bfloat16 copy */
 
 /* ---- lifecycle ------------------------------------------------------------------ */
@@ -410,7 +411,9 @@ int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]);
  * QV_BOUND_PLANE_8BIT: whenever the bound scan takes the search and the plane is held; QV_BOUND_PLANE_BF16: never.  Independent of
  * qv_index_set_bound_scan, which decides WHETHER a search takes the bound scan; this decides which plane it starts on.  The
  * environment variable QV_BOUND_PLANE (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that never call this.
- * Masked searches, row-set searches and shared passes of 2 - 8 queries stay on the bfloat16 copy. */
+ * This setter speaks of unfiltered searches only: a single masked, row-set or where-filtered query has a setter of its own
+ * (qv_index_set_bound_plane_filtered).  Shared passes of 2 - 8 queries, filtered or not, stay on the bfloat16 copy, and
+ * qv_sharded_search_masked keeps the exact scan. */
 #define QV_BOUND_PLANE_AUTO 0
 #define QV_BOUND_PLANE_8BIT 1
 #define QV_BOUND_PLANE_BF16 2
@@ -420,6 +423,29 @@ int qv_index_set_bound_plane(qv_index* idx, int mode);
  * qv_index_bound_scan_stats keeps its meaning: a search the 8-bit stage took counts as a bound-scan search there, and its hand-backs
  * are the searches that reached the exact scan. */
 int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]);
+/* ---- the 8-bit stage under a filter ----
+ * Which plane serves a single FILTERED query's bound scan first: qv_index_search_masked, qv_index_search_rowsets and
+ * qv_index_search_where with one query, their device forms, and a shared pass of the row-set front that holds one caller — at
+ * k <= 64, cosine or dot, a dimension that is a multiple of 16.  The 8-bit stage walks the call's candidate bitmap (live & set): a
+ * 64-row tile without a candidate is not read at all, rows outside the set are never candidates and never in the threshold, and a
+ * set with fewer than k live rows has no threshold in either stage and ends in the exact filtered scan, decided on the device.
+ * Results are the exact filtered scan's rows and float32 bits in every case.  `mode` takes the QV_BOUND_PLANE_* values:
+ * QV_BOUND_PLANE_8BIT whenever the filtered bound scan takes the search (qv_scan_bound_applies_filtered) and the plane is held;
+ * QV_BOUND_PLANE_BF16 never; QV_BOUND_PLANE_AUTO (the default) the shapes measured faster — see qv_scan_bound8_applies_filtered.
+ * Independent of qv_index_set_bound_plane; the same external exclusion as the other setters (no search of the index in flight).
+ * The environment variable QV_BOUND_PLANE_FILTERED (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that
+ * never call this.  qv_index_bound_scan8_stats counts these searches, their survivors and their hand-ons as it counts the
+ * unfiltered ones.  Out of scope: shared passes of 2 - 8 queries stay on the bfloat16 copy; qv_sharded_search_masked keeps the exact scan. */
+int qv_index_set_bound_plane_filtered(qv_index* idx, int mode);
+/* Whether a filtered search would take the 8-bit stage first — the dispatch's own rule, on the host: one query, the plane held
+ * (has_plane8), qv_scan_bound_applies_filtered(metric, dim, rows, 1, k, mode, has_plane = 1, candidate_tiles) true (the stage never
+ * starts a search the bound scan would not take), and plane_mode_filtered (QV_BOUND_PLANE_*) not BF16.  8BIT: whenever those hold.
+ * AUTO: the shapes measured faster than starting on the bfloat16 copy at every measured k (profiles/LAB_r11_bound_scan8_filtered.md) —
+ * rows of 768 dimensions or more, 3 000 000 rows or more, nine tenths of the tiles or more holding a candidate (a mask or set of
+ * any density that is spread over the index, a where-filter); sparser candidate tiles lost or gained nothing at k = 64 and are
+ * declined, narrower rows were not measured.  Never below the unfiltered 8-bit floors.  1 / 0, < 0 on an error. */
+int qv_scan_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8,
+                                    uint32_t candidate_tiles);
 /* Whether a search would take the 8-bit stage first: qv_scan_bound_applies' conditions under `mode`, one query, the plane held
  * (has_plane8), and `plane_mode` (QV_BOUND_PLANE_*) — the dispatch's own rule, without an index or a device.  1 / 0, < 0 on an error. */
 int qv_scan_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8);
@@ -455,6 +481,11 @@ int qv_scan_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint
  * or < 0 for arguments no route serves.  (More than 32 queries on route 3: the last 1 - 8 are split off as a pass of their own.) */
 int qv_scan_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
                   uint32_t candidate_tiles);
+/* qv_scan_route with the filtered plane mode as an argument (QV_BOUND_PLANE_*, as qv_index_set_bound_plane_filtered takes it): a filtered
+ * single query that qv_scan_bound8_applies_filtered takes is route 6 (bound8_first), as route 5 serves both forms; unfiltered calls
+ * do not depend on the argument.  qv_scan_route is this function with QV_BOUND_PLANE_BF16: a filtered call never on route 6. */
+int qv_scan_route_ex(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
+                     uint32_t candidate_tiles, int plane_mode_filtered);
 /* The interval stage 1 derives for one row, on the host (the kernel's own function compiled for the CPU; metric QV_COSINE or
  * QV_DOT): s = the float32 chain of the query times the row's bfloat16 copy, qn = |query|, rn = |row|, rres = |row - bf16(row)|
  * rounded up.  Returns 1 when the row is one the bound says nothing about (always a survivor), 0 otherwise with

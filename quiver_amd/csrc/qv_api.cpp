@@ -1670,6 +1670,13 @@ int qv_index_set_bound_plane(qv_index* idx, int mode) {
     return QV_OK;
 }
 
+int qv_index_set_bound_plane_filtered(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", mode);
+    idx->bound_plane_filtered = mode;
+    return QV_OK;
+}
+
 int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]) {
     if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
     HIPCHK(hipSetDevice(idx->device));
@@ -1684,6 +1691,12 @@ int qv_scan_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq,
     if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
     if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
     return qv::host_bound8_applies(metric, dim, rows, nq, k, mode, plane_mode, has_plane8);
+}
+
+int qv_scan_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8, uint32_t candidate_tiles) {
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    if (plane_mode_filtered < 0 || plane_mode_filtered > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered);
+    return qv::host_bound8_applies_filtered(metric, dim, rows, nq, k, mode, plane_mode_filtered, has_plane8, candidate_tiles);
 }
 
 int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, double qn, double qres, double rn, float rscale8, float rres8, float* d_lo, float* d_hi) {
@@ -1735,9 +1748,15 @@ int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, 
 
 int qv_scan_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
                   uint32_t candidate_tiles) {
+    return qv_scan_route_ex(metric, dim, rows, nq, k, cus, tickets, bound_mode, plane_mode, has_plane, has_plane8, candidate_tiles, QV_BOUND_PLANE_BF16);
+}
+
+int qv_scan_route_ex(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
+                     uint32_t candidate_tiles, int plane_mode_filtered) {
+    if (plane_mode_filtered < 0 || plane_mode_filtered > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered);
     if (bound_mode < 0 || bound_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "bound_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", bound_mode);
     if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
-    const int route = qv::host_flat_route(metric, dim, rows, nq, k, cus, tickets, bound_mode, plane_mode, has_plane, has_plane8, candidate_tiles);
+    const int route = qv::host_flat_route(metric, dim, rows, nq, k, cus, tickets, bound_mode, plane_mode, has_plane, has_plane8, candidate_tiles, plane_mode_filtered);
     return route >= 0 ? route : fail(QV_ERR_INVALID_ARG, "no fused flat search has these arguments (metric %d, dim %u, rows %u, nq %u, k %u, cus %d)", metric, dim, rows, nq, k, cus);
 }
 

@@ -1,5 +1,5 @@
 // qv_bound_scan.hip — the bound scan: a fused flat search (k <= 64, cosine / dot) answered from the index's reduced copies of the rows — the
-// bfloat16 copy, with the 8-bit plane in front of it for one unfiltered query — by rejecting rows on a certified interval of the distance
+// bfloat16 copy, with the 8-bit plane in front of it for one query, unfiltered or filtered — by rejecting rows on a certified interval of the distance
 // (qv_bound.h) and re-scoring the few survivors in the exact scan's arithmetic.  One query, the shared pass of 2 - 8, their filtered forms;
 // the rules that say when each applies; the launchers and workspace sizes; the interval and the 8-bit row state compiled for the host.
 // Which search takes the path is decided by plan_flat (qv_scan.hip); the exact scan that answers what a bound pass hands back
@@ -329,7 +329,11 @@ __device__ __forceinline__ long long bound8_tile(const u4* __restrict__ p, const
     return ((long long)acc[0] + (long long)acc[1]) * 128ll + ((long long)acc[2] + (long long)acc[3]);   // (each partial sum exact in int32: dim <= kBoundMaxDim)
 }
 
-template <int M>
+// SKIP (k_bound_scan8<., true>: v.alive is a filter's candidate bitmap, as for k_bound_scan<., true>): the wave holds the word of the tile it
+// walks and has the next one's in flight behind that tile's bytes; a tile whose word is zero is not requested — plane, rnorm, rscale8, rres8 —
+// and its 64 lower-bound words are written as 0xFFFFFFFF (k_bound_collect reads every word of a reused workspace).  The query's scale, terms
+// and norm are the workgroup's, computed before the walk, so a wave that reads no tile just publishes a dead list.
+template <int M, bool SKIP = false>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_scan8(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
               uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
@@ -391,11 +395,20 @@ k_bound_scan8(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtr
     const uint32_t kth = k - 1;
     uint64_t list = kDeadKey, thr = kDeadKey;
     bool first = true;
-    for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+    uint32_t t = blockIdx.x * kScanWaves + wave;
+    uint64_t am_next = 0ull;                                           // (SKIP) the word of the wave's next tile
+    if constexpr (SKIP) am_next = t < v.n_tiles ? v.alive[t] : 0ull;
+    for (; t < v.n_tiles; t += tw) {
+        uint64_t am;                                                   // wave-uniform
+        if constexpr (SKIP) {
+            am = am_next;
+            if (t + tw < v.n_tiles) am_next = v.alive[t + tw];         // (in flight behind this tile's bytes)
+            if (am == 0ull) { __builtin_nontemporal_store(0xFFFFFFFFu, &lo_all[t * 64 + lane]); continue; }
+        }
         const uint32_t row = t * 64 + lane;
         const double rn = v.rnorm[row];                                // (requested ahead of the tile's bytes: there when the sums are)
         const float sc = v.rscale8[row], rr = v.rres8[row];
-        const uint64_t am = v.alive[t];                                // wave-uniform
+        if constexpr (!SKIP) am = v.alive[t];
         const long long isum = bound8_tile(plane + (size_t)t * steps * 64, qh, ql, steps);
         float lo, hi;
         (void)bound_scan_interval8<M>(isum, sq, qn, qres, rn, sc, rr, v.dim, lo, hi);
@@ -677,6 +690,37 @@ bool bound_scan_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_
 bool bound_scan_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
     return bound_scan_rule_filtered(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr, candidate_tiles);
 }
+// The 8-bit stage in front of a FILTERED single query (k_bound_scan8<., true>): whenever the filtered bound rule takes the search (asked with
+// the copy held: the stage never starts a search the bound scan would not take), one query, the plane held, and the index's filtered plane
+// setter (IndexView::bound_plane_filtered) or QV_BOUND_PLANE_FILTERED — a knob of its own, independent of the unfiltered one — allows it:
+// 1 whenever that holds, 2 never.  Automatic: per candidate fraction f = candidate_tiles / tiles the host can tell apart, the smallest
+// measured row count from which 8-bit-first beat the parent commit's library (bfloat16 first) by more than both arms' spread at EVERY
+// measured k, never below the unfiltered 8-bit floor; 768 dimensions only, so narrower rows are declined.
+// profiles/LAB_r11_bound_scan8_filtered.md; us per call, parent / 8-bit first, 768 dims, k = 1, 10, 64 (four runs each, spreads <= 8 us):
+//   f >= 0.9   every tile          1M 272 / 189, 278 / 211, 340 / 362 (a loss at k = 64)   3M 732 / 429, 740 / 458, 800 / 618   10M 2326 / 1248, 2332 / 1269, 2399 / 1458
+//              a random 1 % set    1M 177 / 142, 183 / 152, 233 / 229                      3M 425 / 273, 434 / 293, 489 / 392   10M 1233 / 690, 1241 / 712, 1298 / 829
+//              where, 10 % sel.    1M 273 / 193, 279 / 211, 336 / 305                      3M 739 / 436, 746 / 464, 804 / 576   10M 2352 / 1274, 2358 / 1299, 2412 / 1404
+//              where, 100 % sel.   1M 273 / 193, 282 / 215, 345 / 366 (a loss at k = 64)   3M 739 / 438, 748 / 466, 807 / 626   10M 2350 / 1274, 2355 / 1296, 2423 / 1485
+//   f = 0.1    one tile in ten     1M 70 / 88, 75 / 107, 132 / 206 (losses)                3M 237 / 158, 248 / 186, 370 / 369 (k = 64: no gain)
+//                                  10M 295 / 217, 303 / 235, 362 / 365 (a loss at k = 64): declined at every row count
+//   0.1 < f < 0.9 was not measured: declined.  So: f >= 0.9 from kBound8MinRows rows of kBound8MinDim dimensions or more.
+static bool bound8_filtered_auto(uint32_t dim, uint32_t n_rows, uint32_t candidate_tiles) {
+    const uint64_t n_tiles = ((uint64_t)n_rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
+    return dim >= kBound8MinDim && n_rows >= kBound8MinRows && ct * 10 >= n_tiles * 9;
+}
+static int bound_plane_filtered_mode(int mode) { static const int env_mode = env_int("QV_BOUND_PLANE_FILTERED", 0); return mode ? mode : env_mode; }
+bool bound_scan8_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, bool has_plane8, uint32_t candidate_tiles) {
+    plane_mode_filtered = bound_plane_filtered_mode(plane_mode_filtered);
+    if (plane_mode_filtered == 2 || nq != 1 || !has_plane8 || !bound_scan_rule_filtered(metric, dim, n_rows, 1, k, mode, true, candidate_tiles)) return false;
+    if (plane_mode_filtered == 1) return true;
+    return bound8_filtered_auto(dim, n_rows, candidate_tiles);
+}
+bool bound_scan8_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
+    return v.plane != nullptr && bound_scan8_rule_filtered(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_filtered, v.plane8 != nullptr, candidate_tiles);
+}
+int host_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8, uint32_t candidate_tiles) {
+    return bound_scan8_rule_filtered(metric, dim, rows, nq, k, mode, plane_mode_filtered, has_plane8 != 0, candidate_tiles) ? 1 : 0;
+}
 size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles) {
     return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)n_tiles * 64 * sizeof(uint32_t);
 }
@@ -684,7 +728,7 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
                              uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked, bool plane8_first) {
     // (whether the path is TAKEN is plan_flat's decision; here only what the kernels need: metric, width, the copy, k — bound_scan_rule's "always")
     if (!bound_scan_rule(v.metric, v.dim, v.n_rows, 1, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
-    if (plane8_first && (masked || !v.plane8)) return hipErrorInvalidValue;
+    if (plane8_first && !v.plane8) return hipErrorInvalidValue;
     const uint32_t grid = p.grid;
     char* w = static_cast<char*>(d_ws);
     uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256;
@@ -713,9 +757,15 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
         };
         const uint32_t* const no_gate = nullptr;
         hipError_t e = masked ? attrs(k_bound_scan<M, true>, lds1, k_bound_rescore<M>) : attrs(k_bound_scan<M>, lds1, k_bound_rescore<M>);
-        if (e == hipSuccess && plane8_first) e = attrs(k_bound_scan8<M>, lds8, k_bound_rescore<M, true>);
+        if (e == hipSuccess && plane8_first) e = masked ? attrs(k_bound_scan8<M, true>, lds8, k_bound_rescore<M, true>) : attrs(k_bound_scan8<M>, lds8, k_bound_rescore<M, true>);
         if (e != hipSuccess) return e;
-        if (plane8_first) {
+        if (plane8_first && masked) {
+            // the same two stages under a filter: both skip the tiles without a candidate, and the exact scan behind them walks the candidate bitmap
+            BoundCtrl* ctrl8 = ctrl + 1;
+            uint32_t* gate8 = &ctrl8->flag;
+            stage(k_bound_scan8<M, true>, lds8, k_bound_rescore<M, true>, ctrl8, (uint32_t*)nullptr, ctrl);
+            stage(k_bound_scan<M, true>, lds1, k_bound_rescore<M>, ctrl, gate8, (BoundCtrl*)nullptr, (const uint32_t*)gate8);
+        } else if (plane8_first) {
             // the 8-bit stage on the second set of control words, in the same workspace (the stages run one after the other); the bfloat16 stage
             // behind it is gated on that stage's flag and leaves at once when it has answered
             BoundCtrl* ctrl8 = ctrl + 1;

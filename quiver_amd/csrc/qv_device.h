@@ -50,6 +50,7 @@ struct IndexView {
     float*    rscale8;    // per row: max|r_i| / 127 rounded up (0: no scale)
     float*    rres8;      // per row: |r - rscale8 r8| rounded up; NaN = a row the 8-bit bound says nothing about
     int       bound_plane; // qv_index_set_bound_plane: 0 the 8-bit stage from its measured row count on, 1 whenever it applies, 2 never
+    int       bound_plane_filtered; // qv_index_set_bound_plane_filtered: the same three values for a filtered single query, a knob of its own
 };
 
 struct GraphView {
@@ -149,7 +150,7 @@ enum class FlatRoute : int {
     mq64,           // 9 or more cosine / dot queries over 16 tiles per wave or more: launch_flat_scan_mq64 + k_merge_lists
     mq,             // 2 or more queries: k_flat_scan_mq, qb = 4 / 8 / 16 per corpus pass (16 never for the all-float32 metrics) + k_merge_lists
     bound,          // one query, tickets and counters, the bound rule takes it: launch_bound_scan and the gated exact scan behind it
-    bound8_first,   // ... unfiltered and bound_scan8_applies: the 8-bit stage in front
+    bound8_first,   // ... and bound_scan8_applies (unfiltered) or bound_scan8_applies_filtered (filtered): the 8-bit stage in front
     split,          // tickets, flat_split_applies: k_flat_scan_split, a tile over eight waves
     fused,          // one query, tickets, more than one workgroup: k_flat_scan<., ., true>, the last workgroup merges
     two_launch,     // everything else: k_flat_scan + k_merge_lists
@@ -169,7 +170,7 @@ struct FlatPlan : FlatPass {        // the call's pass; mq64 with more than 32 q
 FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k, bool tickets, bool stats, uint32_t candidate_tiles);
 // plan_flat without an index or a device (qv_scan_route): the route's number, < 0 for arguments no route serves
 int host_flat_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
-                    uint32_t candidate_tiles);
+                    uint32_t candidate_tiles, int plane_mode_filtered);
 // f = plan_flat for the same v, p, nq, k, d_tickets != null, d_bound_stats != null and candidate_tiles.  d_ws: the route's share of qv_api.cpp's
 // search_ws_bytes, which is sized from the same plan.
 hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const FlatPlan& f, const float* d_queries, uint32_t nq, uint32_t k,
@@ -194,7 +195,7 @@ size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tile
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                              uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s,
                              bool masked = false,   // v.alive is a filter's candidate bitmap: the form that does not request tiles without a candidate (k_bound_scan<., true>)
-                             bool plane8_first = false);   // the 8-bit stage (k_bound_scan8) in front, the bfloat16 stage gated behind it: d_ctrl = 2 BoundCtrl
+                             bool plane8_first = false);   // the 8-bit stage (k_bound_scan8; masked: its skipping form) in front, the bfloat16 stage gated behind it: d_ctrl = 2 BoundCtrl
 // ... and for the 2 - 8 queries of a shared pass (k_bound_scan_mq): d_ws bound_scan_mq_workspace_bytes, d_ctrl 8 BoundCtrl; the exact scan of
 // the queries it hands back is enqueued behind it (launch_flat_redo_flagged)
 size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim);
@@ -214,6 +215,11 @@ int host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn,
 bool bound_scan8_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode, bool has_plane8);
 bool bound_scan8_applies(const IndexView& v, uint32_t nq, uint32_t k);
 int host_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8);
+// ... in front of a filtered single query (k_bound_scan8<., true>): the filtered bound rule's yes, the plane, and a mode of its own
+// (QV_BOUND_PLANE_* again; 0 automatic: QV_BOUND_PLANE_FILTERED decides)
+bool bound_scan8_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, bool has_plane8, uint32_t candidate_tiles);
+bool bound_scan8_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
+int host_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8, uint32_t candidate_tiles);
 int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, float* d_lo, float* d_hi);
 int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res);
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches

@@ -1045,9 +1045,13 @@ FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t 
         f.route = head.route; f.qb = head.qb;
         return f;
     }
-    // 5. one query: the bound scan on the bfloat16 copy (the 8-bit stage first, unfiltered, where that applies), its exact re-score, and
-    // the exact scan behind them that runs only when they hand the query back
-    if (nq == 1 && bound_takes && p.grid > 1) { f.route = !f.filtered && bound_scan8_applies(v, nq, k) ? FlatRoute::bound8_first : FlatRoute::bound; return f; }
+    // 5. one query: the bound scan on the bfloat16 copy (the 8-bit stage first where its rule — the unfiltered or the filtered one — says so),
+    // its exact re-score, and the exact scan behind them that runs only when they hand the query back
+    if (nq == 1 && bound_takes && p.grid > 1) {
+        const bool first8 = f.filtered ? bound_scan8_applies_filtered(v, nq, k, candidate_tiles) : bound_scan8_applies(v, nq, k);
+        f.route = first8 ? FlatRoute::bound8_first : FlatRoute::bound;
+        return f;
+    }
     // 6. a short corpus of wide rows: a tile over eight waves
     if (tickets && fuse && flat_split_applies(v, nq, k)) { f.route = FlatRoute::split; return f; }
     // 7. one query, the caller's tickets at hand: scan + merge in ONE launch (the last workgroup merges)
@@ -1055,11 +1059,11 @@ FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t 
     return f;                                                         // 8. scan, then k_merge_lists
 }
 int host_flat_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
-                    uint32_t candidate_tiles) {
+                    uint32_t candidate_tiles, int plane_mode_filtered) {
     if (k == 0 || k > (uint32_t)kMaxFusedK || nq == 0 || dim == 0 || rows == 0 || cus <= 0 || metric < QV_COSINE || metric > QV_L2SQ_F64) return -1;
     IndexView v = {};
     v.dim = dim; v.dim4 = (dim + 3) / 4; v.n_rows = rows; v.n_tiles = (rows + 63) / 64; v.metric = metric;
-    v.bound_scan = bound_mode; v.bound_plane = plane_mode;
+    v.bound_scan = bound_mode; v.bound_plane = plane_mode; v.bound_plane_filtered = plane_mode_filtered;
     static uint16_t a_plane; static int8_t a_plane8;                   // (the rules ask whether a copy is held, never what it holds)
     if (has_plane) v.plane = &a_plane;
     if (has_plane8) v.plane8 = &a_plane8;
@@ -1154,7 +1158,11 @@ static hipError_t route_bound(const IndexView& v, const ScanPlan& p, const FlatP
     hipStream_t s = c.s;
     const bool plane8_first = f.route == FlatRoute::bound8_first;    // the 8-bit stage first; the bfloat16 stage gated behind it
     const size_t lds = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
-    if (f.filtered) { if (trace_filtered()) fprintf(stderr, "qv: scan kernel = k_bound_scan masked (tiles=%u, candidate tiles<=%u, k=%u)\n", v.n_tiles, c.candidate_tiles, k); }
+    if (f.filtered) {
+        if (!trace_filtered()) {}
+        else if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8 masked + k_bound_collect + k_bound_rescore, then gated k_bound_scan masked + k_bound_collect + k_bound_rescore (tiles=%u, candidate tiles<=%u, k=%u)\n", v.n_tiles, c.candidate_tiles, k);
+        else fprintf(stderr, "qv: scan kernel = k_bound_scan masked (tiles=%u, candidate tiles<=%u, k=%u)\n", v.n_tiles, c.candidate_tiles, k);
+    }
     else if (trace_unfiltered()) {
         if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8 + k_bound_collect + k_bound_rescore, then gated k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
         else fprintf(stderr, "qv: scan kernel = k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);

@@ -405,6 +405,12 @@ class DeviceIndex:
         (whenever the bound scan takes the search and the plane is held), "bf16" (qv_index_set_bound_plane)"""
         check(lib().qv_index_set_bound_plane(self._h, self.BOUND_PLANE.get(mode, mode)))
 
+    def set_bound_plane_filtered(self, mode):
+        """which plane a single FILTERED query's bound scan starts on (search_masked, search_rowsets, search_where and their device forms):
+        "auto" (the measured shapes), "8bit" (whenever the filtered bound scan takes the search and the plane is held), "bf16"; a knob of
+        its own, independent of set_bound_plane (qv_index_set_bound_plane_filtered)"""
+        check(lib().qv_index_set_bound_plane_filtered(self._h, self.BOUND_PLANE.get(mode, mode)))
+
     def bound_scan8_stats(self) -> dict:
         """survivors of the last 8-bit stage, searches it handed on to the bfloat16 stage, searches that took it, whether the plane exists"""
         out = (C.c_uint64 * 4)()
