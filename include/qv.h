@@ -412,8 +412,8 @@ int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]);
  * qv_index_set_bound_scan, which decides WHETHER a search takes the bound scan; this decides which plane it starts on.  The
  * environment variable QV_BOUND_PLANE (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that never call this.
  * This setter speaks of unfiltered searches only: a single masked, row-set or where-filtered query has a setter of its own
- * (qv_index_set_bound_plane_filtered).  Shared passes of 2 - 8 queries, filtered or not, stay on the bfloat16 copy, and
- * qv_sharded_search_masked keeps the exact scan. */
+ * (qv_index_set_bound_plane_filtered), an unfiltered shared pass of 2 - 8 queries too (qv_index_set_bound_plane_mq).  Shared passes
+ * under a mask, row sets or where-filters stay on the bfloat16 copy, and qv_sharded_search_masked keeps the exact scan. */
 #define QV_BOUND_PLANE_AUTO 0
 #define QV_BOUND_PLANE_8BIT 1
 #define QV_BOUND_PLANE_BF16 2
@@ -435,8 +435,31 @@ int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]);
  * Independent of qv_index_set_bound_plane; the same external exclusion as the other setters (no search of the index in flight).
  * The environment variable QV_BOUND_PLANE_FILTERED (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that
  * never call this.  qv_index_bound_scan8_stats counts these searches, their survivors and their hand-ons as it counts the
- * unfiltered ones.  Out of scope: shared passes of 2 - 8 queries stay on the bfloat16 copy; qv_sharded_search_masked keeps the exact scan. */
+ * unfiltered ones.  Out of scope: FILTERED shared passes of 2 - 8 queries stay on the bfloat16 copy; qv_sharded_search_masked keeps the exact scan. */
 int qv_index_set_bound_plane_filtered(qv_index* idx, int mode);
+/* ---- the 8-bit stage in front of a shared pass ----
+ * Which plane serves an UNFILTERED shared pass of 2 - 8 queries first: qv_index_search and qv_index_search_device with 2 - 8 queries, the
+ * passes that concurrent single-query callers share, and shards through their own index.  The 8-bit plane is read once for the 4 or 8
+ * queries of the pass; interval, threshold, collection and exact re-score are per query, as in the single-query stage.  A query that
+ * stage cannot decide (more candidates than its list holds, no finite threshold, a query it cannot quantise) is handed on ALONE to the
+ * bfloat16 shared pass, whose launches are enqueued behind and leave at once when no query was handed on; from there, if need be, to
+ * the exact scan — all decided on the device; every answer is bit-identical to the exact scan's.  `mode` takes the QV_BOUND_PLANE_*
+ * values: QV_BOUND_PLANE_8BIT whenever the bound scan takes the pass and the plane is held; QV_BOUND_PLANE_BF16 never;
+ * QV_BOUND_PLANE_AUTO (the default) the shapes measured faster — see qv_scan_bound8_applies_mq.  Independent of
+ * qv_index_set_bound_plane and qv_index_set_bound_plane_filtered; the same external exclusion (no search of the index in flight).
+ * The environment variable QV_BOUND_PLANE_MQ (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that never
+ * call this.  A pass under a mask, row sets or where-filters stays on the bfloat16 copy.
+ * Counters: qv_index_bound_scan8_stats out[0] = the largest survivor count among the pass's queries in the 8-bit stage, out[1] += the
+ * queries handed on to the bfloat16 stage, out[2] += nq.  qv_index_bound_scan_stats counts the pass's nq queries once in out[2],
+ * out[1] += the queries that reached the exact scan, out[0] = the largest survivor count in the stage that answered. */
+int qv_index_set_bound_plane_mq(qv_index* idx, int mode);
+/* Whether a shared pass would take the 8-bit stage first — the dispatch's own rule, on the host: 2 <= nq <= 8, the plane held
+ * (has_plane8), qv_scan_bound_applies(metric, dim, rows, nq, k, mode, has_plane = 1) true (the stage never starts a pass the bound scan
+ * would not take), and plane_mode_mq (QV_BOUND_PLANE_*) not BF16.  8BIT: whenever those hold.  AUTO: the shapes measured faster than
+ * starting on the bfloat16 copy at every measured k and nq of the pass's size class (2 - 4 or 5 - 8 queries) —
+ * profiles/LAB_r12_bound_scan8_mq.md.  The route (qv_scan_route) is 1, bound_mq, either way: the plane is a decision inside it.
+ * 1 / 0, < 0 on an error. */
+int qv_scan_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, int has_plane8);
 /* Whether a filtered search would take the 8-bit stage first — the dispatch's own rule, on the host: one query, the plane held
  * (has_plane8), qv_scan_bound_applies_filtered(metric, dim, rows, 1, k, mode, has_plane = 1, candidate_tiles) true (the stage never
  * starts a search the bound scan would not take), and plane_mode_filtered (QV_BOUND_PLANE_*) not BF16.  8BIT: whenever those hold.
@@ -717,6 +740,7 @@ int qv_sharded_set_filter(qv_sharded* s, int filter);          /* qv_index_set_f
 int qv_sharded_set_bound_scan(qv_sharded* s, int mode);       /* qv_index_set_bound_scan on every shard */
 int qv_sharded_bound_scan_stats(qv_sharded* s, uint64_t out[4]);   /* qv_index_bound_scan_stats: [0] of the first shard, [1] [2] summed, [3] 1 when every shard holds the copy */
 int qv_sharded_set_bound_plane(qv_sharded* s, int mode);      /* qv_index_set_bound_plane on every shard */
+int qv_sharded_set_bound_plane_mq(qv_sharded* s, int mode);   /* qv_index_set_bound_plane_mq on every shard */
 int qv_sharded_bound_scan8_stats(qv_sharded* s, uint64_t out[4]);  /* qv_index_bound_scan8_stats, put together as qv_sharded_bound_scan_stats does */
 int qv_sharded_profile(qv_sharded* s, int enable);
 int qv_sharded_profile_read(qv_sharded* s, double* scan_ms_sum, double* exchange_ms_sum, double* merge_ms_sum, uint64_t* searches);

@@ -10,4 +10,15 @@ the Go packages they stand in for.
 from ._lib import QvError, lib, load_library, METRICS, metric_id  # noqa: F401
 from .device_index import DeviceIndex, RowSet, Column, DeviceGraph, GraphReplicas, ShardedIndex  # noqa: F401
 
-__all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex"]
+
+def scan_bound8_applies_mq(metric, dim: int, rows: int, nq: int, k: int, mode="auto", plane_mode_mq="auto", has_plane8: bool = True) -> bool:
+    """whether an unfiltered shared pass of nq queries would start on the 8-bit plane — the dispatch's own rule, on the host, without an index
+    or a device (qv_scan_bound8_applies_mq); metric: a name or an id, mode / plane_mode_mq: as set_bound_scan / set_bound_plane_mq take them"""
+    from ._lib import check
+    m = metric_id(metric) if isinstance(metric, str) else int(metric)
+    rc = lib().qv_scan_bound8_applies_mq(m, dim, rows, nq, k, DeviceIndex.BOUND_SCAN.get(mode, mode), DeviceIndex.BOUND_PLANE.get(plane_mode_mq, plane_mode_mq), 1 if has_plane8 else 0)
+    if rc < 0:
+        check(rc)
+    return rc == 1
+
+__all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq"]

@@ -1677,6 +1677,13 @@ int qv_index_set_bound_plane_filtered(qv_index* idx, int mode) {
     return QV_OK;
 }
 
+int qv_index_set_bound_plane_mq(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", mode);
+    idx->bound_plane_mq = mode;
+    return QV_OK;
+}
+
 int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]) {
     if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
     HIPCHK(hipSetDevice(idx->device));
@@ -1697,6 +1704,12 @@ int qv_scan_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uin
     if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
     if (plane_mode_filtered < 0 || plane_mode_filtered > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered);
     return qv::host_bound8_applies_filtered(metric, dim, rows, nq, k, mode, plane_mode_filtered, has_plane8, candidate_tiles);
+}
+
+int qv_scan_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, int has_plane8) {
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    if (plane_mode_mq < 0 || plane_mode_mq > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_mq);
+    return qv::host_bound8_applies_mq(metric, dim, rows, nq, k, mode, plane_mode_mq, has_plane8);
 }
 
 int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, double qn, double qres, double rn, float rscale8, float rres8, float* d_lo, float* d_hi) {

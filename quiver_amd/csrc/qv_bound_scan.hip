@@ -1,6 +1,7 @@
 // qv_bound_scan.hip — the bound scan: a fused flat search (k <= 64, cosine / dot) answered from the index's reduced copies of the rows — the
-// bfloat16 copy, with the 8-bit plane in front of it for one query, unfiltered or filtered — by rejecting rows on a certified interval of the distance
-// (qv_bound.h) and re-scoring the few survivors in the exact scan's arithmetic.  One query, the shared pass of 2 - 8, their filtered forms;
+// bfloat16 copy, with the 8-bit plane in front of it for one query, unfiltered or filtered, and for an unfiltered shared pass of 2 - 8 — by rejecting
+// rows on a certified interval of the distance (qv_bound.h) and re-scoring the few survivors in the exact scan's arithmetic.  One query, the shared
+// pass of 2 - 8, their filtered forms (a filtered shared pass stays on the bfloat16 copy);
 // the rules that say when each applies; the launchers and workspace sizes; the interval and the 8-bit row state compiled for the host.
 // Which search takes the path is decided by plan_flat (qv_scan.hip); the exact scan that answers what a bound pass hands back
 // (k_flat_scan<., ., true> behind its gate, launch_flat_redo_flagged) and the list merge (launch_merge_lists) live there too.
@@ -442,7 +443,9 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 
 template <int QB>
 __global__ void __launch_bounds__(256)
-k_bound_prep_mq(const float* __restrict__ queries, uint32_t nq, uint32_t dim, float* __restrict__ qblk, double* __restrict__ qnorm, uint32_t* __restrict__ stats) {
+k_bound_prep_mq(const float* __restrict__ queries, uint32_t nq, uint32_t dim, float* __restrict__ qblk, double* __restrict__ qnorm, uint32_t* __restrict__ stats,
+                const uint32_t* __restrict__ gate = nullptr /* behind the 8-bit stage: the count of queries it handed on; zero = leave at once */) {
+    if (gate != nullptr && *gate == 0u) return;
     __shared__ float s_q[kBoundMaxDim];
     const uint32_t nb = gridDim.x - QB;                                // blocks [0, nb): the block; [nb, nb + QB): one query's norm each
     if (blockIdx.x < nb) {
@@ -451,7 +454,7 @@ k_bound_prep_mq(const float* __restrict__ queries, uint32_t nq, uint32_t dim, fl
             const uint32_t j = i % QB, d = i / QB;
             qblk[i] = j < nq ? queries[(size_t)j * dim + d] : 0.f;
         }
-        if (i == 0) stats[0] = 0;                                      // the pass's largest survivor count (k_bound_rescore_mq)
+        if (i == 0 && gate == nullptr) stats[0] = 0;                   // the pass's largest survivor count (k_bound_rescore_mq; behind the 8-bit stage it holds that stage's)
         return;
     }
     const uint32_t j = blockIdx.x - nb;
@@ -506,7 +509,9 @@ __device__ __forceinline__ void bound_block_mq(const u4* __restrict__ p, const f
 template <int M, int QB, bool SETS = false>
 __global__ void __launch_bounds__(kScanBlock, 2)
 k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __restrict__ qnorm, uint32_t nq, uint32_t k,
-                uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */, SetsArg<SETS> tab) {
+                uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */, SetsArg<SETS> tab,
+                const uint32_t* __restrict__ gate = nullptr /* as k_bound_prep_mq's */) {
+    if (gate != nullptr && *gate == 0u) return;
     extern __shared__ __align__(16) unsigned char smem[];
     uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64]
     const uint32_t lane = lane_id();
@@ -586,28 +591,219 @@ k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __res
 // H of query blockIdx.y: the k-th entry of its merged upper-bound list (seed_rows / seed_dist [nq][k])
 __global__ void __launch_bounds__(256)
 k_bound_collect_mq(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, uint32_t k, const uint32_t* __restrict__ seed_rows, const float* __restrict__ seed_dist,
-                   BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand) {
+                   BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand,
+                   const uint32_t* __restrict__ hand = nullptr /* behind the 8-bit stage: only the queries it handed on (hand[j] != 0) are collected */) {
     const uint32_t j = blockIdx.y;
+    if (hand != nullptr && hand[j] == 0u) return;
     const uint32_t H = ord_f32(seed_dist[(size_t)j * k + k - 1]);
     if (seed_rows[(size_t)j * k + k - 1] == 0xFFFFFFFFu || H >= 0xFF800000u) return;   // no H: k_bound_rescore_mq hands the query back
     bound_collect(lo_all + (size_t)j * n, n, H, &ctrl[j].cand_cnt, cand + (size_t)j * kBoundCandCap);
 }
 
-template <int M>
+// STAGE 0: the pass on the bfloat16 copy alone.  STAGE 1: the 8-bit stage of a pass (k_bound_scan8_mq below): a query it decides is answered
+// and counted here as a bound-scan search; every other one gets its hand-on word hand[j] set and the pass-wide count hand[kBoundMqMax]
+// bumped — the words the bfloat16 stage behind is gated on (k_bound_prep8_mq cleared them).  STAGE 2: that bfloat16 stage: only the queries
+// handed on are walked, counted and written; the others keep the answers they have.
+template <int M, int STAGE = 0>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_rescore_mq(IndexView v, const float* __restrict__ queries, uint32_t k, const uint32_t* __restrict__ seed_rows, const float* __restrict__ seed_dist,
                    BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand, uint32_t* __restrict__ flags, uint32_t* __restrict__ stats,
-                   uint32_t* __restrict__ rows_out, float* __restrict__ dist_out) {
+                   uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, uint32_t* __restrict__ hand = nullptr) {
     const uint32_t j = blockIdx.x;
+    if constexpr (STAGE == 2) { if (hand[j] == 0u) return; }
     const uint32_t cnt = ctrl[j].cand_cnt;
     const bool has_H = seed_rows[(size_t)j * k + k - 1] != 0xFFFFFFFFu && ord_f32(seed_dist[(size_t)j * k + k - 1]) < 0xFF800000u;
     bound_rescore_query<M>(v, queries + (size_t)j * v.dim, k, cnt, has_H, cand + (size_t)j * kBoundCandCap, rows_out + (size_t)j * k, dist_out + (size_t)j * k, [&](bool hand_back) {
-        (void)atomicMax(&stats[0], cnt);
-        if (hand_back) (void)atomicAdd(&stats[1], 1u);
-        (void)atomicAdd(&stats[2], 1u);
-        flags[j] = hand_back ? 1u : 0u;                                // launch_flat_redo_flagged behind this launch reads them
+        if constexpr (STAGE == 1) {
+            (void)atomicMax(&stats[kBound8StatsWord], cnt);
+            (void)atomicAdd(&stats[kBound8StatsWord + 2], 1u);
+            if (hand_back) { (void)atomicAdd(&stats[kBound8StatsWord + 1], 1u); (void)atomicAdd(&hand[kBoundMqMax], 1u); }
+            else { (void)atomicMax(&stats[0], cnt); (void)atomicAdd(&stats[2], 1u); }
+            hand[j] = hand_back ? 1u : 0u;
+            flags[j] = 0u;                                             // (the bfloat16 stage sets it if it hands the query back in turn)
+        } else {
+            (void)atomicMax(&stats[0], cnt);
+            if (hand_back) (void)atomicAdd(&stats[1], 1u);
+            (void)atomicAdd(&stats[2], 1u);
+            flags[j] = hand_back ? 1u : 0u;                            // launch_flat_redo_flagged behind this launch reads them
+        }
         ctrl[j].cand_cnt = 0;                                          // zero, as the words are kept
     });
+}
+
+// ---------------------------------------------------------------- the shared pass of 2 - 8 queries: reject rows on the 8-bit plane first --
+// k_bound_scan8's stage for QB = 4 or 8 queries at once: the plane is read ONCE per pass, a quarter of the float32 bytes, and what the stage
+// cannot decide for a query goes — that query alone — to the bfloat16 shared pass above, whose launches sit gated behind it.
+//   k_bound_prep8_mq  one workgroup per query slot: k_bound_scan8's prologue (finiteness, max|q|, sq, the two int8 terms, qres rounded up,
+//                     |q| as the reference's chain), written once: the terms as qterm[step][QB][hi 16 bytes, lo 16 bytes], the scalars as
+//                     qpar[0 .. 8) = |q_j|, [8 .. 16) = sq_j, [16 .. 24) = qres_j.  Slots past nq hold zeros.  It clears the words the pass
+//                     uses as flags: the hand-on words and their count, and the pass's survivor maxima in the counters.
+//   k_bound_scan8_mq  k_bound_scan8's walk — lane == row, a wave owns whole tiles, one 16-byte load per lane and step, the 16 / 8 / 4 / 2 / 1
+//                     ladder — with the query terms as SCALAR operands of the dot-product instruction (uniform loads of qterm, as
+//                     k_bound_scan_mq reads its float32 block: 8 dwords per query and step).  Per (query, row) the four int32 partial sums of
+//                     bound8_block, combined in int64, and bound_scan_interval8 as it stands.  d_lo -> lo_all[j][n_tiles * 64]; d_hi ->
+//                     per-query wave lists -> partial[j][grid][k]: k_bound_scan_mq's layout, so k_merge_lists and k_bound_collect_mq follow.
+//                     THE PRE-TEST: d_lo is computed first; when ord_f32(d_lo) is strictly above the distance word of the wave's current
+//                     k-th upper bound of that query, the row's d_hi >= d_lo is above it too and list_insert would reject its key — so
+//                     when that holds for every lane of the wave (ballot) d_hi is not computed at all.  The lists, H_j and the survivors are
+//                     what they are without it; "unsure" rows (d_lo = -inf) are never skipped.  The first tile a wave walks is sorted outright.
+//   k_bound_rescore_mq<., 1>, then the bfloat16 stage's five launches, each of which leaves at once when nothing was handed on.
+// (Measured: profiles/LAB_r12_bound_scan8_mq.md.)
+constexpr uint32_t kBound8MqHandWord = 16;     // in the pass's 64 flag words: [0, 8) the exact scan's flags, [16, 24) hand-on words, [24] their count
+template <int QB>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_prep8_mq(const float* __restrict__ queries, uint32_t nq, uint32_t dim, int8_t* __restrict__ qterm, double* __restrict__ qpar, uint32_t* __restrict__ hand,
+                 uint32_t* __restrict__ stats) {
+    __shared__ float s_max[kScanWaves];
+    __shared__ uint32_t s_bad[kScanWaves];
+    __shared__ double s_res[kScanWaves];
+    const uint32_t j = blockIdx.x;                                     // < QB
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (j == 0 && threadIdx.x <= kBoundMqMax) hand[threadIdx.x] = 0u;
+    if (j == 0 && threadIdx.x == 0) { stats[0] = 0u; stats[kBound8StatsWord] = 0u; }   // the pass's largest survivor counts (k_bound_rescore_mq)
+    if (j >= nq) {
+        for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) {
+            qterm[(((size_t)(i >> 4) * QB + j) * 2) * 16 + (i & 15u)] = 0; qterm[(((size_t)(i >> 4) * QB + j) * 2 + 1) * 16 + (i & 15u)] = 0;
+        }
+        if (threadIdx.x == 0) { qpar[j] = 0.0; qpar[kBoundMqMax + j] = 1.0; qpar[2 * kBoundMqMax + j] = __builtin_nan(""); }
+        return;
+    }
+    const float* __restrict__ query = queries + (size_t)j * dim;
+    // as k_bound_scan8 quantises its query: sq = max|q_i| / 16256, qq = rint(q / sq) = 128 hi + lo; qres = |q - sq qq| rounded up
+    float mx = 0.f; bool bad = false;
+    for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) { const float x = query[i]; bad |= !((x - x) == 0.0f); mx = __builtin_fmaxf(mx, __builtin_fabsf(x)); }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) mx = __builtin_fmaxf(mx, __shfl_xor(mx, m));
+    const bool wbad = __ballot(bad) != 0ull;
+    if (lane == 0) { s_max[wave] = mx; s_bad[wave] = wbad ? 1u : 0u; }
+    __syncthreads();
+    uint32_t anybad = 0;
+    for (uint32_t w = 0; w < kScanWaves; w++) { mx = __builtin_fmaxf(mx, s_max[w]); anybad |= s_bad[w]; }
+    const bool q_ok = !anybad && mx > 0.0f;
+    const double sq = q_ok ? (double)mx / (double)kBound8QueryMax : 1.0;
+    double r2 = 0.0;
+    for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) {
+        const double x = q_ok ? (double)query[i] : 0.0;
+        const double qq = __builtin_rint(x / sq);                      // |qq| <= 16256
+        const double hi = __builtin_rint(qq * (1.0 / 128.0)), lo = qq - 128.0 * hi;   // |hi| <= 127, |lo| <= 64: exact
+        qterm[(((size_t)(i >> 4) * QB + j) * 2) * 16 + (i & 15u)] = (int8_t)(int)hi;
+        qterm[(((size_t)(i >> 4) * QB + j) * 2 + 1) * 16 + (i & 15u)] = (int8_t)(int)lo;
+        const double d = x - sq * qq;
+        r2 = __builtin_fma(d, d, r2);
+    }
+    r2 = wave_sum_f64(r2);
+    if (lane == 0) s_res[wave] = r2;
+    double ma = 0.0;
+    if (wave == kScanWaves - 1) {
+        // |q| as the reference's chain (distances.go:20), one wave: 64 values per request, walked in order
+        for (uint32_t b = 0; b < dim; b += 64) {
+            const float x = b + lane < dim ? query[b + lane] : 0.f;
+            const uint32_t n = dim - b < 64u ? dim - b : 64u;
+            for (uint32_t e = 0; e < n; e++) { const double a = (double)__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), e)); ma = __builtin_fma(a, a, ma); }
+        }
+    }
+    __syncthreads();
+    if (wave == kScanWaves - 1 && lane == 0) {
+        double qres2 = 0.0;
+        for (uint32_t w = 0; w < kScanWaves; w++) qres2 += s_res[w];
+        qpar[j] = __builtin_sqrt(ma);
+        qpar[kBoundMqMax + j] = sq;
+        // (a query without a scale: every row comes out "unsure", no H, and the re-score hands the query on)
+        qpar[2 * kBoundMqMax + j] = q_ok ? __builtin_sqrt(qres2) * (1.0 + 1e-9) + 1e-300 : __builtin_nan("");
+    }
+}
+
+// acc[j][0 .. 3]: bound8_block's four partial sums for query j (hi terms in [0], [1], lo terms in [2], [3])
+template <int QB, int U>
+__device__ __forceinline__ void bound8_block_mq(const u4* __restrict__ p, const u4* __restrict__ qterm, uint32_t s0, i32 (&acc)[QB][4]) {
+    u4 x[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) x[u] = __builtin_nontemporal_load(&p[(size_t)(s0 + u) * 64]);
+    __builtin_amdgcn_sched_barrier(0);                                 // all requests of the block ahead of the arithmetic (see row_accumulate)
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const u4* qt = qterm + (size_t)(s0 + u) * QB * 2;              // global, uniform -> scalar loads
+#pragma unroll
+        for (int j = 0; j < QB; j++) {
+            const u4 h = qt[2 * j], l = qt[2 * j + 1];
+            acc[j][0] = __builtin_amdgcn_sdot4((i32)h.x, (i32)x[u].x, acc[j][0], false);
+            acc[j][1] = __builtin_amdgcn_sdot4((i32)h.y, (i32)x[u].y, acc[j][1], false);
+            acc[j][0] = __builtin_amdgcn_sdot4((i32)h.z, (i32)x[u].z, acc[j][0], false);
+            acc[j][1] = __builtin_amdgcn_sdot4((i32)h.w, (i32)x[u].w, acc[j][1], false);
+            acc[j][2] = __builtin_amdgcn_sdot4((i32)l.x, (i32)x[u].x, acc[j][2], false);
+            acc[j][3] = __builtin_amdgcn_sdot4((i32)l.y, (i32)x[u].y, acc[j][3], false);
+            acc[j][2] = __builtin_amdgcn_sdot4((i32)l.z, (i32)x[u].z, acc[j][2], false);
+            acc[j][3] = __builtin_amdgcn_sdot4((i32)l.w, (i32)x[u].w, acc[j][3], false);
+        }
+    }
+}
+
+template <int M, int QB>
+__global__ void __launch_bounds__(kScanBlock, 2)
+k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __restrict__ qpar, uint32_t nq, uint32_t k,
+                 uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64]
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves, kth = k - 1;
+    const size_t n = (size_t)v.n_tiles * 64;
+    const u4* plane = reinterpret_cast<const u4*>(v.plane8) + lane;
+    uint64_t list[QB], thr[QB];
+#pragma unroll
+    for (int j = 0; j < QB; j++) { list[j] = kDeadKey; thr[j] = kDeadKey; }
+    bool first = true;
+    for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+        const uint32_t row = t * 64 + lane;
+        const double rn = v.rnorm[row];                                // (requested ahead of the tile's bytes: there when the sums are)
+        const float sc = v.rscale8[row], rr = v.rres8[row];
+        const bool live = (v.alive[t] >> lane) & 1ull;                 // (dead rows and the last tile's padding: never candidates, never in a bound)
+        i32 acc[QB][4];
+#pragma unroll
+        for (int j = 0; j < QB; j++) { acc[j][0] = 0; acc[j][1] = 0; acc[j][2] = 0; acc[j][3] = 0; }
+        const u4* p = plane + (size_t)t * steps * 64;
+        uint32_t s = 0;
+        for (; s + 16 <= steps; s += 16) bound8_block_mq<QB, 16>(p, qterm, s, acc);
+        if (s + 8 <= steps) { bound8_block_mq<QB, 8>(p, qterm, s, acc); s += 8; }
+        if (s + 4 <= steps) { bound8_block_mq<QB, 4>(p, qterm, s, acc); s += 4; }
+        if (s + 2 <= steps) { bound8_block_mq<QB, 2>(p, qterm, s, acc); s += 2; }
+        if (s < steps) bound8_block_mq<QB, 1>(p, qterm, s, acc);
+#pragma unroll
+        for (int j = 0; j < QB; j++) {
+            if ((uint32_t)j < nq) {                                    // (uniform) slots past nq produce nothing
+                // (each partial sum exact in int32: dim <= kBoundMaxDim)
+                const long long isum = ((long long)acc[j][0] + (long long)acc[j][1]) * 128ll + ((long long)acc[j][2] + (long long)acc[j][3]);
+                const double qn = qpar[j], sq = qpar[kBoundMqMax + j], qres = qpar[2 * kBoundMqMax + j];   // uniform
+                float lo, hi;
+                (void)bound_scan_interval8<M>(isum, sq, qn, qres, rn, sc, rr, v.dim, lo, hi);   // (only d_lo is used of this call: d_hi's chain is dead code here)
+                const uint32_t olo = live ? ord_f32(lo) : 0xFFFFFFFFu;
+                __builtin_nontemporal_store(olo, &lo_all[(size_t)j * n + row]);
+                if (first) {
+                    (void)bound_scan_interval8<M>(isum, sq, qn, qres, rn, sc, rr, v.dim, lo, hi);
+                    const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+                    list[j] = wave_sort64(key, lane); thr[j] = readlane64(list[j], kth);
+                } else if (__ballot(live && olo <= (uint32_t)(thr[j] >> 32)) != 0ull) {   // the pre-test: nobody below the k-th upper bound -> no d_hi, no insert
+                    (void)bound_scan_interval8<M>(isum, sq, qn, qres, rn, sc, rr, v.dim, lo, hi);
+                    const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+                    list_insert(list[j], thr[j], key, kth, lane);
+                }
+            }
+        }
+        first = false;
+    }
+#pragma unroll
+    for (int j = 0; j < QB; j++) wl[((size_t)wave * QB + j) * 64 + lane] = list[j];
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int j = 0; j < QB; j++) {
+            if ((uint32_t)j < nq) {
+                for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list[j], thr[j], lane < k ? wl[((size_t)w * QB + j) * 64 + lane] : kDeadKey, kth, lane);
+                if (lane < k) partial[((size_t)j * gridDim.x + blockIdx.x) * k + lane] = list[j];
+            }
+        }
+    }
 }
 
 // The bound scan (k_bound_scan / k_bound_rescore above): one query, a fused-list k, cosine or dot, the bfloat16 copy at hand, a width the copy
@@ -658,6 +854,43 @@ bool bound_scan8_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, ui
 }
 bool bound_scan8_applies(const IndexView& v, uint32_t nq, uint32_t k) {
     return v.plane != nullptr && bound_scan8_rule(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane, v.plane8 != nullptr);
+}
+// The 8-bit stage in front of an UNFILTERED shared pass of 2 - 8 queries (k_bound_scan8_mq): a pass the bound scan takes (asked with the copy
+// held: the stage never starts a pass the bound scan would not take), the plane held, and the index's shared-pass plane setter
+// (IndexView::bound_plane_mq) or QV_BOUND_PLANE_MQ — a knob of its own — allows it: 1 whenever that holds, 2 never.  Automatic: per QB the
+// smallest measured row count from which 8-bit-first beat bfloat16-first at every measured k and nq of that QB in both rounds, never below
+// bound_scan_rule's own floors; profiles/LAB_r12_bound_scan8_mq.md.
+// us per call, bfloat16 first / 8-bit first, at k = 1, 10, 64 (the slower round of the 8-bit arm against the faster of the bfloat16 arm):
+//   QB = 4   768 dims   300 k  nq 2: 152 / 132, 161 / 146, 225 / 310; nq 4: 161 / 139, 172 / 160, 269 / 360 (losses at k = 64)
+//                       1M     nq 2: 318 / 209, 324 / 236, 392 / 399; nq 4: 334 / 225, 347 / 258, 443 / 474 (losses at k = 64)
+//                       3M     nq 2: 777 / 442, 787 / 473, 849 / 645; nq 4: 797 / 462, 814 / 498, 907 / 722
+//                       10M    nq 2: 2421 / 1297, 2421 / 1314, 2500 / 1506; nq 4: 2470 / 1350, 2484 / 1371, 2590 / 1630
+//            128 dims   10M    nq 2: 468 / 302, 473 / 320, 531 / 435; nq 4: 514 / 362, 522 / 419, 660 / 643
+//   QB = 8   768 dims   300 k  nq 5: 228 / 173, 246 / 198, 362 / 414; nq 8: 234 / 184, 264 / 227, 426 / 489 (losses at k = 64)
+//                       1M     nq 5: 456 / 269, 468 / 314, 599 / 572; nq 8: 465 / 291, 475 / 350, 695 / 690 (k = 64: 5 % and 1 %, no gain to speak of: declined)
+//                       3M     nq 5: 1078 / 557, 1100 / 620, 1269 / 935; nq 8: 1114 / 607, 1146 / 694, 1289 / 1113
+//                       10M    nq 5: 3342 / 1663, 3352 / 1740, 3566 / 2144; nq 8: 3461 / 1794, 3491 / 1996, 3805 / 2536
+//            128 dims   10M    nq 5: 608 / 493, 628 / 569, 833 / 848; nq 8: 721 / 619, 760 / 741, 1086 / 1166 (losses at k = 64: QB = 8 is never automatic below 768 dimensions)
+constexpr uint32_t kBound8MqMinDim = 768, kBound8MqMinRows4 = 3000000, kBound8MqMinRows8 = 3000000;   // rows of at least 768 dimensions, QB = 4 / QB = 8
+constexpr uint32_t kBound8MqNarrowDim = 128, kBound8MqNarrowRows4 = 10000000, kBound8MqNarrowRows8 = 0;   // 128 <= dim < 768 (nothing between was measured); 0: never automatic
+static_assert(kBound8MqMinRows4 >= kBoundMqMinRows4 && kBound8MqMinRows8 >= kBoundMqMinRows8 && kBound8MqNarrowRows4 >= kBoundMqNarrowRows, "the 8-bit floors are never below the shared pass's");
+static bool bound8_mq_auto(uint32_t dim, uint32_t n_rows, uint32_t nq) {
+    if (dim < kBound8MqNarrowDim) return false;
+    const uint32_t floor = dim >= kBound8MqMinDim ? (nq <= 4 ? kBound8MqMinRows4 : kBound8MqMinRows8) : (nq <= 4 ? kBound8MqNarrowRows4 : kBound8MqNarrowRows8);
+    return floor != 0 && n_rows >= floor;
+}
+static int bound_plane_mq_mode(int mode) { static const int env_mode = env_int("QV_BOUND_PLANE_MQ", 0); return mode ? mode : env_mode; }
+bool bound_scan8_rule_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, bool has_plane8) {
+    plane_mode_mq = bound_plane_mq_mode(plane_mode_mq);
+    if (plane_mode_mq == 2 || nq < 2 || nq > kBoundMqMax || !has_plane8 || !bound_scan_rule(metric, dim, n_rows, nq, k, mode, true)) return false;
+    if (plane_mode_mq == 1) return true;
+    return bound8_mq_auto(dim, n_rows, nq);
+}
+bool bound_scan8_applies_mq(const IndexView& v, uint32_t nq, uint32_t k) {
+    return v.plane != nullptr && bound_scan8_rule_mq(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_mq, v.plane8 != nullptr);
+}
+int host_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, int has_plane8) {
+    return bound_scan8_rule_mq(metric, dim, rows, nq, k, mode, plane_mode_mq, has_plane8 != 0) ? 1 : 0;
 }
 // Under a filter (a candidate bitmap in v.alive, or a row set per query): candidate_tiles = the tiles that hold a candidate of any query of
 // the pass, as the host knows it without a device read (an upper bound: sets count their non-empty words, tombstones are not subtracted, a pass
@@ -825,11 +1058,15 @@ size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k,
            std::max((size_t)nq * kBoundCandCap * sizeof(uint32_t) + (size_t)nq * n_tiles * 64 * sizeof(uint32_t), redo_workspace_bytes(p, nq, k));
 }
 hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                                uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets) {
+                                uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets, bool plane8_first) {
+    // plane8_first (unfiltered passes only): the 8-bit stage — k_bound_prep8_mq, k_bound_scan8_mq, merge, collect, k_bound_rescore_mq<., 1> — in
+    // front, in the same workspace (the stages run one after the other: the query terms lie where the float32 block goes, the scalars where
+    // the norms go), and the bfloat16 stage's launches gated on the count of queries it handed on.
     // h_sets (optional, a HOST array of nq): query j restricted to alive & h_sets[j] — k_bound_scan_mq<., ., true> and the set-carrying redo.
     // Null: the unfiltered pass.  (Whether the path is TAKEN is the caller's decision — plan_flat, or the row-set path's one question to
     // bound_scan_applies_filtered; here only what the kernels need: metric, width, the copy, k, nq planes of lower bounds under 2 GiB.)
     if (nq < 2 || !bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    if (plane8_first && (h_sets || !v.plane8)) return hipErrorInvalidValue;
     BoundSetTable tab;
     for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
     if (h_sets && trace_filtered()) fprintf(stderr, "qv: scan kernel = k_bound_scan_mq sets QB=%d (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
@@ -848,16 +1085,31 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
     BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
     const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     hipError_t e = hipSuccess;
+    static_assert(2 * kBoundMaxDim * kBoundMqMax <= kBoundMaxDim * kBoundMqMax * sizeof(float) && 3 * kBoundMqMax * sizeof(double) <= 256 &&
+                  (kBound8MqHandWord + kBoundMqMax + 1) * 4 <= 256, "the 8-bit stage's terms, scalars and hand-on words fit the bfloat16 stage's");
+    uint32_t* hand = flags + kBound8MqHandWord;
+    const uint32_t* gate = plane8_first ? hand + kBoundMqMax : nullptr;
+    const uint32_t* hand_in = plane8_first ? hand : nullptr;
 #define QV_BOUND_MQ(MMM, QQ)                                                                                                 \
     {                                                                                                                         \
         const size_t lds1 = (size_t)kScanWaves * QQ * 64 * sizeof(uint64_t);                                                  \
         e = set_lds(k_bound_rescore_mq<MMM>, lds2); if (e != hipSuccess) return e;                                            \
-        hipLaunchKernelGGL((k_bound_prep_mq<QQ>), dim3((v.dim * QQ + 255) / 256 + QQ), dim3(256), 0, s, d_queries, nq, v.dim, qblk, qnorm, d_stats); \
-        if (h_sets) hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, tab); \
-        else hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, NoSets{}); \
-        e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s); if (e != hipSuccess) return e;                 \
-        hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand); \
-        hipLaunchKernelGGL((k_bound_rescore_mq<MMM>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out); \
+        if (plane8_first) {                                                                                                   \
+            e = set_lds((k_bound_rescore_mq<MMM, 1>), lds2); if (e != hipSuccess) return e;                                   \
+            e = set_lds((k_bound_rescore_mq<MMM, 2>), lds2); if (e != hipSuccess) return e;                                   \
+            hipLaunchKernelGGL((k_bound_prep8_mq<QQ>), dim3(QQ), dim3(kScanBlock), 0, s, d_queries, nq, v.dim, reinterpret_cast<int8_t*>(qblk), qnorm, hand, d_stats); \
+            hipLaunchKernelGGL((k_bound_scan8_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, reinterpret_cast<const u4*>(qblk), qnorm, nq, k, lo_all, partial); \
+            e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s); if (e != hipSuccess) return e;             \
+            hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand, (const uint32_t*)nullptr); \
+            hipLaunchKernelGGL((k_bound_rescore_mq<MMM, 1>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, hand); \
+        }                                                                                                                     \
+        hipLaunchKernelGGL((k_bound_prep_mq<QQ>), dim3((v.dim * QQ + 255) / 256 + QQ), dim3(256), 0, s, d_queries, nq, v.dim, qblk, qnorm, d_stats, gate); \
+        if (h_sets) hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, tab, gate); \
+        else hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, NoSets{}, gate); \
+        e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s, gate); if (e != hipSuccess) return e;           \
+        hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand, hand_in); \
+        if (plane8_first) hipLaunchKernelGGL((k_bound_rescore_mq<MMM, 2>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, hand); \
+        else hipLaunchKernelGGL((k_bound_rescore_mq<MMM>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, (uint32_t*)nullptr); \
     }
     if (v.metric == QV_COSINE) { if (nq <= 4) QV_BOUND_MQ(QV_COSINE, 4) else QV_BOUND_MQ(QV_COSINE, 8) }
     else { if (nq <= 4) QV_BOUND_MQ(QV_DOT, 4) else QV_BOUND_MQ(QV_DOT, 8) }

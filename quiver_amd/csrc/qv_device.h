@@ -51,6 +51,7 @@ struct IndexView {
     float*    rres8;      // per row: |r - rscale8 r8| rounded up; NaN = a row the 8-bit bound says nothing about
     int       bound_plane; // qv_index_set_bound_plane: 0 the 8-bit stage from its measured row count on, 1 whenever it applies, 2 never
     int       bound_plane_filtered; // qv_index_set_bound_plane_filtered: the same three values for a filtered single query, a knob of its own
+    int       bound_plane_mq; // qv_index_set_bound_plane_mq: the same three values for an unfiltered shared pass of 2 - 8 queries, a knob of its own
 };
 
 struct GraphView {
@@ -201,7 +202,8 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
 size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim);
 hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                                 uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
-                                const RowSetRef* h_sets = nullptr);   // a HOST array of nq sets, at most 8: query j over alive & h_sets[j] (k_bound_scan_mq<., ., true>, the redo included)
+                                const RowSetRef* h_sets = nullptr,   // a HOST array of nq sets, at most 8: query j over alive & h_sets[j] (k_bound_scan_mq<., ., true>, the redo included)
+                                bool plane8_first = false);   // (unfiltered passes) the 8-bit stage (k_bound_scan8_mq) in front, the bfloat16 stage's launches gated behind it
 // bound_scan_applies without an index (qv_scan_bound_applies): mode 0 = automatic (QV_BOUND_SCAN decides), 1 always, 2 never
 bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane);
 int bound_scan_mode(int mode);   // the mode in force: the index's own, else QV_BOUND_SCAN (read once)
@@ -220,6 +222,11 @@ int host_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, ui
 bool bound_scan8_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, bool has_plane8, uint32_t candidate_tiles);
 bool bound_scan8_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
 int host_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8, uint32_t candidate_tiles);
+// ... in front of an unfiltered shared pass of 2 - 8 queries (k_bound_scan8_mq): the bound rule's yes for that nq, the plane, and a mode of
+// its own (QV_BOUND_PLANE_* again; 0 automatic: QV_BOUND_PLANE_MQ decides).  A decision inside route bound_mq, as the plane is inside route 5 / 6.
+bool bound_scan8_rule_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, bool has_plane8);
+bool bound_scan8_applies_mq(const IndexView& v, uint32_t nq, uint32_t k);
+int host_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, int has_plane8);
 int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, float* d_lo, float* d_hi);
 int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res);
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches
@@ -305,7 +312,8 @@ hipError_t launch_column_presence(uint64_t* d_present, uint32_t first_row, uint3
 // pieces of the multi-query scans that qv_rowset.hip shares with qv_scan.hip: the query blocks of the scalar-operand form
 // (qblk[group][dim4 * 4][qb], qb = 4, 8 or — the float64-accumulating metrics — 16) and the merge of partial[nq][n_lists][k] into [nq][k] results
 hipError_t launch_prep_qblk(int metric, uint32_t qb, const float* d_queries, uint32_t nq, uint32_t dim, uint32_t dim4, void* d_qblk, hipStream_t s);
-hipError_t launch_merge_lists(const uint64_t* d_partial, uint32_t n_lists, uint32_t nq, uint32_t k, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+hipError_t launch_merge_lists(const uint64_t* d_partial, uint32_t n_lists, uint32_t nq, uint32_t k, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
+                              const uint32_t* d_gate = nullptr);   // a device word: zero = the launch leaves at once (the bfloat16 shared pass behind the 8-bit one)
 
 // Batched path: fp32-MFMA filter + exact re-scoring (results identical to launch_flat_topk).
 // *d_overflow_out -> [nq] flags (device): 1 = candidate buffer overflowed, caller must redo that

@@ -786,7 +786,8 @@ hipError_t launch_flat_keys_mq(const IndexView& v, const ScanPlan& p, const floa
 // One workgroup per query merges n_lists sorted lists of k keys into the final top-k (merge_lists_body, qv_kernels.h).
 __global__ void __launch_bounds__(kMergeBlock)
 k_merge_lists(const uint64_t* __restrict__ partial, uint32_t n_lists, uint32_t k,
-              uint32_t* __restrict__ rows_out, float* __restrict__ dist_out) {
+              uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, const uint32_t* __restrict__ gate = nullptr /* a device word; zero = leave at once */) {
+    if (gate != nullptr && *gate == 0u) return;
     const uint32_t qi = blockIdx.x;
     merge_lists_body<false>(partial + (size_t)qi * n_lists * k, n_lists, k, rows_out + (size_t)qi * k, dist_out + (size_t)qi * k);
 }
@@ -1064,6 +1065,7 @@ int host_flat_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32
     IndexView v = {};
     v.dim = dim; v.dim4 = (dim + 3) / 4; v.n_rows = rows; v.n_tiles = (rows + 63) / 64; v.metric = metric;
     v.bound_scan = bound_mode; v.bound_plane = plane_mode; v.bound_plane_filtered = plane_mode_filtered;
+    v.bound_plane_mq = QV_BOUND_PLANE_BF16;                            // (the shared pass's plane is a decision inside route 1: no route depends on it)
     static uint16_t a_plane; static int8_t a_plane8;                   // (the rules ask whether a copy is held, never what it holds)
     if (has_plane) v.plane = &a_plane;
     if (has_plane8) v.plane8 = &a_plane8;
@@ -1079,10 +1081,14 @@ struct FlatCall {
     uint32_t* d_tickets; uint32_t* done_flag; uint32_t done_seq; bool* flag_used; uint32_t* d_bound_stats; uint32_t candidate_tiles;
 };
 static hipError_t route_bound_mq(const IndexView& v, const ScanPlan& p, const FlatPass& f, const FlatCall& c) {
-    if (!f.filtered && trace_unfiltered()) fprintf(stderr, "qv: scan kernel = k_bound_scan_mq QB=%d (nq=%u, tiles=%u)\n", (int)f.qb, c.nq, v.n_tiles);
+    const bool plane8_first = !f.filtered && bound_scan8_applies_mq(v, c.nq, c.k);   // the plane: a decision inside the route, as first8 is for routes 5 / 6
+    if (!f.filtered && trace_unfiltered()) {
+        if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8_mq QB=%d + k_merge_lists + k_bound_collect_mq + k_bound_rescore_mq, then gated k_bound_scan_mq + k_merge_lists + k_bound_collect_mq + k_bound_rescore_mq (nq=%u, tiles=%u)\n", (int)f.qb, c.nq, v.n_tiles);
+        else fprintf(stderr, "qv: scan kernel = k_bound_scan_mq QB=%d (nq=%u, tiles=%u)\n", (int)f.qb, c.nq, v.n_tiles);
+    }
     if (c.ev0) (void)hipEventRecord(c.ev0, c.s);
     const RowSetRef every[kBoundSets] = {};                           // (the bitmap is v.alive itself: every query's set is "every row" of it)
-    const hipError_t e = launch_bound_scan_mq(v, p, c.d_queries, c.nq, c.k, c.d_ws, c.d_tickets + kBoundCtrlWord, c.d_bound_stats, c.d_rows_out, c.d_dist_out, c.s, f.filtered ? every : nullptr);
+    const hipError_t e = launch_bound_scan_mq(v, p, c.d_queries, c.nq, c.k, c.d_ws, c.d_tickets + kBoundCtrlWord, c.d_bound_stats, c.d_rows_out, c.d_dist_out, c.s, f.filtered ? every : nullptr, plane8_first);
     if (c.ev1) (void)hipEventRecord(c.ev1, c.s);
     return e;
 }
@@ -1311,11 +1317,11 @@ hipError_t launch_prep_qblk(int metric, uint32_t qb, const float* d_queries, uin
     });
     return hipGetLastError();
 }
-hipError_t launch_merge_lists(const uint64_t* d_partial, uint32_t n_lists, uint32_t nq, uint32_t k, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
+hipError_t launch_merge_lists(const uint64_t* d_partial, uint32_t n_lists, uint32_t nq, uint32_t k, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const uint32_t* d_gate) {
     if (k == 0 || k > (uint32_t)kMaxFusedK || n_lists == 0 || nq == 0) return hipErrorInvalidValue;
     const uint32_t total = n_lists * k;
     const uint32_t mblock = merge_block(total);
-    hipLaunchKernelGGL(k_merge_lists, dim3(nq), dim3(mblock), 0, s, d_partial, n_lists, k, d_rows_out, d_dist_out);
+    hipLaunchKernelGGL(k_merge_lists, dim3(nq), dim3(mblock), 0, s, d_partial, n_lists, k, d_rows_out, d_dist_out, d_gate);
     return hipGetLastError();
 }
 

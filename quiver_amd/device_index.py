@@ -411,6 +411,12 @@ class DeviceIndex:
         its own, independent of set_bound_plane (qv_index_set_bound_plane_filtered)"""
         check(lib().qv_index_set_bound_plane_filtered(self._h, self.BOUND_PLANE.get(mode, mode)))
 
+    def set_bound_plane_mq(self, mode):
+        """which plane an unfiltered SHARED PASS of 2 - 8 queries starts on (search / search_device with 2 - 8 queries, the passes concurrent
+        single-query callers share): "auto" (the measured shapes), "8bit" (whenever the bound scan takes the pass and the plane is held),
+        "bf16"; a knob of its own, independent of set_bound_plane and set_bound_plane_filtered (qv_index_set_bound_plane_mq)"""
+        check(lib().qv_index_set_bound_plane_mq(self._h, self.BOUND_PLANE.get(mode, mode)))
+
     def bound_scan8_stats(self) -> dict:
         """survivors of the last 8-bit stage, searches it handed on to the bfloat16 stage, searches that took it, whether the plane exists"""
         out = (C.c_uint64 * 4)()
@@ -850,6 +856,9 @@ class ShardedIndex:
 
     def set_bound_plane(self, mode):
         check(lib().qv_sharded_set_bound_plane(self._h, DeviceIndex.BOUND_PLANE.get(mode, mode)))
+
+    def set_bound_plane_mq(self, mode):
+        check(lib().qv_sharded_set_bound_plane_mq(self._h, DeviceIndex.BOUND_PLANE.get(mode, mode)))
 
     def bound_scan8_stats(self) -> dict:
         out = (C.c_uint64 * 4)()
