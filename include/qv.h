@@ -412,8 +412,8 @@ int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]);
  * qv_index_set_bound_scan, which decides WHETHER a search takes the bound scan; this decides which plane it starts on.  The
  * environment variable QV_BOUND_PLANE (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that never call this.
  * This setter speaks of unfiltered searches only: a single masked, row-set or where-filtered query has a setter of its own
- * (qv_index_set_bound_plane_filtered), an unfiltered shared pass of 2 - 8 queries too (qv_index_set_bound_plane_mq).  Shared passes
- * under a mask, row sets or where-filters stay on the bfloat16 copy, and qv_sharded_search_masked keeps the exact scan. */
+ * (qv_index_set_bound_plane_filtered), an unfiltered shared pass of 2 - 8 queries too (qv_index_set_bound_plane_mq), and so has a shared
+ * pass under a mask, row sets or where-filters (qv_index_set_bound_plane_filtered_mq).  qv_sharded_search_masked keeps the exact scan. */
 #define QV_BOUND_PLANE_AUTO 0
 #define QV_BOUND_PLANE_8BIT 1
 #define QV_BOUND_PLANE_BF16 2
@@ -435,7 +435,8 @@ int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]);
  * Independent of qv_index_set_bound_plane; the same external exclusion as the other setters (no search of the index in flight).
  * The environment variable QV_BOUND_PLANE_FILTERED (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that
  * never call this.  qv_index_bound_scan8_stats counts these searches, their survivors and their hand-ons as it counts the
- * unfiltered ones.  Out of scope: FILTERED shared passes of 2 - 8 queries stay on the bfloat16 copy; qv_sharded_search_masked keeps the exact scan. */
+ * unfiltered ones.  FILTERED shared passes of 2 - 8 queries have a setter of their own (qv_index_set_bound_plane_filtered_mq); out of
+ * scope: qv_sharded_search_masked keeps the exact scan. */
 int qv_index_set_bound_plane_filtered(qv_index* idx, int mode);
 /* ---- the 8-bit stage in front of a shared pass ----
  * Which plane serves an UNFILTERED shared pass of 2 - 8 queries first: qv_index_search and qv_index_search_device with 2 - 8 queries, the
@@ -448,11 +449,40 @@ int qv_index_set_bound_plane_filtered(qv_index* idx, int mode);
  * QV_BOUND_PLANE_AUTO (the default) the shapes measured faster — see qv_scan_bound8_applies_mq.  Independent of
  * qv_index_set_bound_plane and qv_index_set_bound_plane_filtered; the same external exclusion (no search of the index in flight).
  * The environment variable QV_BOUND_PLANE_MQ (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that never
- * call this.  A pass under a mask, row sets or where-filters stays on the bfloat16 copy.
+ * call this.  A pass under a mask, row sets or where-filters is not moved by this setter: qv_index_set_bound_plane_filtered_mq.
  * Counters: qv_index_bound_scan8_stats out[0] = the largest survivor count among the pass's queries in the 8-bit stage, out[1] += the
  * queries handed on to the bfloat16 stage, out[2] += nq.  qv_index_bound_scan_stats counts the pass's nq queries once in out[2],
  * out[1] += the queries that reached the exact scan, out[0] = the largest survivor count in the stage that answered. */
 int qv_index_set_bound_plane_mq(qv_index* idx, int mode);
+/* ---- the 8-bit stage in front of a filtered shared pass ----
+ * Which plane serves a FILTERED shared pass of 2 - 8 queries first: qv_index_search_masked (one bitmap for all queries),
+ * qv_index_search_rowsets and qv_index_search_where with 2 - 8 queries (a set or a predicate per query), their device forms, and the
+ * passes in which the row-set front puts concurrent filtered callers together — at k <= 64, cosine or dot, a dimension that is a multiple
+ * of 16.  The 8-bit plane is read once for the pass, each query over its OWN candidates (live & set): a 64-row tile no query selects is
+ * not read at all, a row outside a query's set is neither its candidate nor in its threshold.  A query that stage cannot decide (more
+ * candidates than its list holds, no finite threshold, a query it cannot quantise, fewer than k candidates in its set) is handed on ALONE
+ * to the filtered bfloat16 shared pass, whose launches are enqueued behind and leave at once when no query was handed on; from there, if
+ * need be, to the exact filtered scan — all decided on the device; every answer is bit-identical to the exact filtered scan's.  `mode`
+ * takes the QV_BOUND_PLANE_* values: QV_BOUND_PLANE_8BIT whenever the filtered bound scan takes the pass and the plane is held —
+ * where-filters counted as "every tile may hold a candidate", so such a pass takes the bound scan, 8-bit first, whenever the filtered
+ * bound rule accepts a pass over every tile; QV_BOUND_PLANE_BF16 never (routing is then what it was before this setter existed);
+ * QV_BOUND_PLANE_AUTO (the default) the shapes measured faster — see qv_scan_bound8_applies_filtered_mq.  Independent of
+ * qv_index_set_bound_plane, qv_index_set_bound_plane_filtered and qv_index_set_bound_plane_mq: none of those moves a filtered shared
+ * pass, and this one moves nothing else.  The same external exclusion (no search of the index in flight).  The environment variable
+ * QV_BOUND_PLANE_FILTERED_MQ (1 8-bit, 2 bfloat16; read once per process) sets the default of indexes that never call this.
+ * Counters: as qv_index_set_bound_plane_mq's.  Out of scope: qv_sharded_search_masked keeps the exact scan, and there are no sharded
+ * setters for this mode because shards have no row sets; 9 or more queries, k > 64 and other metrics are not covered. */
+int qv_index_set_bound_plane_filtered_mq(qv_index* idx, int mode);
+/* Whether a filtered shared pass would take the 8-bit stage first — the dispatch's own rule, on the host: 2 <= nq <= 8, the plane held
+ * (has_plane8), qv_scan_bound_applies_filtered(metric, dim, rows, nq, k, mode, has_plane = 1, candidate_tiles) true (the stage never starts
+ * a pass the filtered bound scan would not take), and plane_mode_filtered_mq (QV_BOUND_PLANE_*) not BF16.  8BIT: whenever those hold.
+ * AUTO: only cells measured faster than starting on the bfloat16 copy at every measured k, never above what qv_scan_bound8_applies_mq
+ * allows for the same nq (profiles/LAB_r13_bound_scan8_filtered_mq.md): rows of 768 dimensions or more, 3 000 000 rows or more, nine
+ * tenths of the tiles or more holding a candidate of some query of the pass (null sets, sets of any density spread over the index,
+ * where-filters); 1 000 000 rows lost at k = 64, sparser candidate tiles gained nothing to speak of at k = 64 and are declined.
+ * 1 / 0, < 0 on an error. */
+int qv_scan_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered_mq, int has_plane8,
+                                       uint32_t candidate_tiles);
 /* Whether a shared pass would take the 8-bit stage first — the dispatch's own rule, on the host: 2 <= nq <= 8, the plane held
  * (has_plane8), qv_scan_bound_applies(metric, dim, rows, nq, k, mode, has_plane = 1) true (the stage never starts a pass the bound scan
  * would not take), and plane_mode_mq (QV_BOUND_PLANE_*) not BF16.  8BIT: whenever those hold.  AUTO: the shapes measured faster than

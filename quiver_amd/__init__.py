@@ -21,4 +21,18 @@ def scan_bound8_applies_mq(metric, dim: int, rows: int, nq: int, k: int, mode="a
         check(rc)
     return rc == 1
 
-__all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq"]
+
+def scan_bound8_applies_filtered_mq(metric, dim: int, rows: int, nq: int, k: int, mode="auto", plane_mode_filtered_mq="auto", has_plane8: bool = True,
+                                    candidate_tiles: int = 0xFFFFFFFF) -> bool:
+    """whether a FILTERED shared pass of nq queries would start on the 8-bit plane — the dispatch's own rule, on the host, without an index or a
+    device (qv_scan_bound8_applies_filtered_mq); candidate_tiles: the 64-row tiles that hold a candidate of any query of the pass (more than
+    the index has: every tile); mode / plane_mode_filtered_mq: as set_bound_scan / set_bound_plane_filtered_mq take them"""
+    from ._lib import check
+    m = metric_id(metric) if isinstance(metric, str) else int(metric)
+    rc = lib().qv_scan_bound8_applies_filtered_mq(m, dim, rows, nq, k, DeviceIndex.BOUND_SCAN.get(mode, mode),
+                                                  DeviceIndex.BOUND_PLANE.get(plane_mode_filtered_mq, plane_mode_filtered_mq), 1 if has_plane8 else 0, candidate_tiles)
+    if rc < 0:
+        check(rc)
+    return rc == 1
+
+__all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq", "scan_bound8_applies_filtered_mq"]

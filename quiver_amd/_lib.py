@@ -104,6 +104,8 @@ PROTOTYPES = {
     "qv_index_set_bound_plane_filtered": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_set_bound_plane_mq": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_sharded_set_bound_plane_mq": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_set_bound_plane_filtered_mq": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_scan_bound8_applies_filtered_mq": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     "qv_scan_bound8_applies_mq": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "qv_scan_bound8_applies_filtered": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     "qv_scan_route_ex": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]),

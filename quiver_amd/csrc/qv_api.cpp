@@ -1052,15 +1052,18 @@ static qv::RowSetRef rs_ref(const qv_index* idx, const RsFilter& f) {
 // bound: a multi piece of 2 - 8 queries that the filtered bound-scan rule takes (launch_bound_scan_mq with the sets) — decided here, once, so
 // that the workspace and the launch agree.  cand_tiles: the tiles that hold a candidate of any query of the piece, as the host knows it: a
 // set counts its non-empty words (qv_rowset::tiles; tombstones are not subtracted), a null set every tile, a pass min(n_tiles, the sum).
-// Transient sets: a multi piece that holds one reports NO candidate tile, which the automatic rule declines and "always" still takes; a
-// single query is planned with every tile a candidate.  Either way a mis-route costs time, never bits.
-struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; };
-static uint32_t rowsets_cand_tiles(const qv_index* idx, const RsFilter* fl, uint32_t nq) {
+// Transient sets: a multi piece that holds one reports NO candidate tile to the bfloat16 pass's rule, which its automatic form declines and
+// "always" still takes; a single query is planned with every tile a candidate.  Either way a mis-route costs time, never bits.
+// bound8: a bound piece that starts on the 8-bit plane (k_bound_scan8_mq<., ., true>) — decided here too.  Its rule is asked with a second
+// count in which a transient set is EVERY tile, as the single query is planned: when it says yes the piece is a bound piece, 8-bit first,
+// whatever the first count said; with that rule's mode at "bf16" the first question alone decides, as before.
+struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; bool bound8; };
+static uint32_t rowsets_cand_tiles(const qv_index* idx, const RsFilter* fl, uint32_t nq, bool transient_every_tile = false) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     uint64_t sum = 0;
     for (uint32_t q = 0; q < nq; q++) {
-        if (fl[q].where) return 0;
-        sum += fl[q].set ? fl[q].set->tiles : n_tiles;
+        if (fl[q].where && !transient_every_tile) return 0;
+        sum += fl[q].set && !fl[q].where ? fl[q].set->tiles : n_tiles;
     }
     return (uint32_t)std::min<uint64_t>(sum, n_tiles);
 }
@@ -1070,8 +1073,9 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const R
     pieces.clear();
     if (k <= (uint32_t)qv::kMaxFusedK && nq >= 2) {
         const uint32_t ct = rowsets_cand_tiles(idx, fl, nq);
-        const bool bound = nq <= 8 && qv::bound_scan_applies_filtered(idx->view(), nq, k, ct);   // (9 or more are not cut into bound passes)
-        pieces.push_back(RowsetPiece{0, nq, k, true, bound, ct});
+        const bool bound8 = nq <= 8 && qv::bound_scan8_applies_filtered_mq(idx->view(), nq, k, rowsets_cand_tiles(idx, fl, nq, true));
+        const bool bound = bound8 || (nq <= 8 && qv::bound_scan_applies_filtered(idx->view(), nq, k, ct));   // (9 or more are not cut into bound passes)
+        pieces.push_back(RowsetPiece{0, nq, k, true, bound, ct, bound8});
         return std::max(qv::rowset_workspace_bytes(plan, nq, k, idx->dim4), bound ? qv::bound_scan_mq_workspace_bytes(plan, nq, k, n_tiles, idx->dim) : (size_t)0);
     }
     size_t ws = 0;
@@ -1086,7 +1090,7 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const R
         //  as no candidate tile, which the automatic rule declines; "always" still takes the path)
         const bool too_few = !transient && set && set->selected < kk;
         const uint32_t ct = transient ? n_tiles : (set && !too_few ? std::min<uint32_t>(set->tiles, n_tiles) : 0u);
-        pieces.push_back(RowsetPiece{q, e - q, kk, false, false, ct});
+        pieces.push_back(RowsetPiece{q, e - q, kk, false, false, ct, false});
         if (kk) ws = std::max(ws, search_ws_bytes(idx, e - q, kk, k, e - q == 1, set || transient ? ct : qv::kBoundNoFilter));   // (as rowsets_enqueue passes them on)
         q = e;
     }
@@ -1165,9 +1169,9 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
                 idx->prof_events.emplace_back(ev0, ev1);
             }
             hipError_t e = hipSuccess;
-            if (p.bound && d_tickets) {                               // the pass on the bfloat16 copy, each query over its own candidates
+            if (p.bound && d_tickets) {                               // the pass on the reduced copies (p.bound8: the 8-bit plane first), each query over its own candidates
                 if (ev0) (void)hipEventRecord(ev0, s);
-                e = qv::launch_bound_scan_mq(v, plan, q, p.nq, k, ws, d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, r_out, d_out, s, refs.data());
+                e = qv::launch_bound_scan_mq(v, plan, q, p.nq, k, ws, d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, r_out, d_out, s, refs.data(), p.bound8);
                 if (ev1) (void)hipEventRecord(ev1, s);
             } else e = qv::launch_rowset_topk(v, plan, q, p.nq, k, refs.data(), ws, r_out, d_out, s, ev0, ev1);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set scan launch failed: %s", hipGetErrorString(e));
@@ -1684,6 +1688,13 @@ int qv_index_set_bound_plane_mq(qv_index* idx, int mode) {
     return QV_OK;
 }
 
+int qv_index_set_bound_plane_filtered_mq(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", mode);
+    idx->bound_plane_filtered_mq = mode;
+    return QV_OK;
+}
+
 int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]) {
     if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
     HIPCHK(hipSetDevice(idx->device));
@@ -1710,6 +1721,12 @@ int qv_scan_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t 
     if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
     if (plane_mode_mq < 0 || plane_mode_mq > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_mq);
     return qv::host_bound8_applies_mq(metric, dim, rows, nq, k, mode, plane_mode_mq, has_plane8);
+}
+
+int qv_scan_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered_mq, int has_plane8, uint32_t candidate_tiles) {
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    if (plane_mode_filtered_mq < 0 || plane_mode_filtered_mq > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered_mq);
+    return qv::host_bound8_applies_filtered_mq(metric, dim, rows, nq, k, mode, plane_mode_filtered_mq, has_plane8, candidate_tiles);
 }
 
 int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, double qn, double qres, double rn, float rscale8, float rres8, float* d_lo, float* d_hi) {

@@ -105,6 +105,7 @@ struct qv_index {
     int bound_plane = 0;                       // qv_index_set_bound_plane
     int bound_plane_filtered = 0;              // qv_index_set_bound_plane_filtered
     int bound_plane_mq = 0;                    // qv_index_set_bound_plane_mq
+    int bound_plane_filtered_mq = 0;           // qv_index_set_bound_plane_filtered_mq
     uint32_t* d_bound_stats = nullptr;         // [0] survivors of the last bound scan, [1] hand-backs, [2] bound scans (written by the kernels)
     std::vector<uint64_t> alive_host;          // mirror of d_alive, for size bookkeeping and validation
     Buf mut_stage;                             // grow-only staging buffer of the mutating calls (add / remove / update run under the
@@ -131,7 +132,7 @@ struct qv_index {
         qv::IndexView v;
         v.tiles = d_tiles; v.rnorm = d_rnorm; v.alive = d_alive; v.rres = d_rres; v.rowmaj = d_rowmaj;
         v.bf16 = (flags & QV_FLAG_BF16_ROWS) ? d_bf16 : nullptr; v.plane = d_bf16; v.bound_scan = bound_scan;
-        v.plane8 = d_plane8; v.rscale8 = d_rscale8; v.rres8 = d_rres8; v.bound_plane = bound_plane; v.bound_plane_filtered = bound_plane_filtered; v.bound_plane_mq = bound_plane_mq;
+        v.plane8 = d_plane8; v.rscale8 = d_rscale8; v.rres8 = d_rres8; v.bound_plane = bound_plane; v.bound_plane_filtered = bound_plane_filtered; v.bound_plane_mq = bound_plane_mq; v.bound_plane_filtered_mq = bound_plane_filtered_mq;
         v.dim = dim; v.dim4 = dim4; v.n_rows = n_rows; v.n_tiles = (n_rows + 63) / 64; v.metric = metric; v.filter = filter;
         return v;
     }

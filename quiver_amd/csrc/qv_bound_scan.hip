@@ -1,7 +1,7 @@
 // qv_bound_scan.hip — the bound scan: a fused flat search (k <= 64, cosine / dot) answered from the index's reduced copies of the rows — the
-// bfloat16 copy, with the 8-bit plane in front of it for one query, unfiltered or filtered, and for an unfiltered shared pass of 2 - 8 — by rejecting
+// bfloat16 copy, with the 8-bit plane in front of it for one query and for a shared pass of 2 - 8, each unfiltered or filtered — by rejecting
 // rows on a certified interval of the distance (qv_bound.h) and re-scoring the few survivors in the exact scan's arithmetic.  One query, the shared
-// pass of 2 - 8, their filtered forms (a filtered shared pass stays on the bfloat16 copy);
+// pass of 2 - 8, their filtered forms;
 // the rules that say when each applies; the launchers and workspace sizes; the interval and the 8-bit row state compiled for the host.
 // Which search takes the path is decided by plan_flat (qv_scan.hip); the exact scan that answers what a bound pass hands back
 // (k_flat_scan<., ., true> behind its gate, launch_flat_redo_flagged) and the list merge (launch_merge_lists) live there too.
@@ -739,10 +739,20 @@ __device__ __forceinline__ void bound8_block_mq(const u4* __restrict__ p, const 
     }
 }
 
-template <int M, int QB>
+// SETS (k_bound_scan8_mq<., ., true>: a pass under filters, query j restricted to am_j = alive & set_j): this walk under k_bound_scan_mq<., ., true>'s
+// candidate handling.  Lane j < nq keeps query j's (bits, words) pair — in lanes, not scalars: the scalar file is spent on the query terms —,
+// rowset_word for the wave's NEXT tile is in flight while the current one is walked, and am_j comes back per query with readlane64.  A tile
+// no query selects requests nothing — plane8, rnorm, rscale8, rres8 — and its nq x 64 lower-bound words are written as 0xFFFFFFFF
+// (k_bound_collect_mq reads every word of a reused workspace, and stays as it is).  Bit `lane` of am_j gates query j's lower-bound word
+// (0xFFFFFFFF) and its upper-bound key (kDeadKey): H_j is the k-th smallest upper bound over query j's OWN candidates, and a set of fewer
+// than k live rows has none (handed on).  `first` is the first tile the wave READS; a query with no candidate in it keeps its dead list and
+// a threshold word of 0xFFFFFFFF, which is what sorting 64 dead keys gives.  The pre-test runs over query j's own candidates; a query with
+// no candidate in a tile computes no interval at all.  A wave that reads no tile publishes dead lists.  The integer walk, the int64
+// combination and bound_scan_interval8 are untouched.  A masked call (one bitmap in v.alive) is this form with a table of null sets.
+template <int M, int QB, bool SETS = false>
 __global__ void __launch_bounds__(kScanBlock, 2)
 k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __restrict__ qpar, uint32_t nq, uint32_t k,
-                 uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */) {
+                 uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */, SetsArg<SETS> tab) {
     extern __shared__ __align__(16) unsigned char smem[];
     uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64]
     const uint32_t lane = lane_id();
@@ -754,11 +764,31 @@ k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __rest
 #pragma unroll
     for (int j = 0; j < QB; j++) { list[j] = kDeadKey; thr[j] = kDeadKey; }
     bool first = true;
+    const bool mine = SETS && lane < nq;
+    RowSetRef rs = RowSetRef{nullptr, 0, 0};
+    uint64_t w_next = 0ull;
+    if constexpr (SETS) {
+        static_assert(QB <= (int)kBoundSets, "one table entry per query of the pass");
+        rs = tab.e[mine ? lane : 0u];                                 // lane j: query j's set
+        const uint32_t t0 = blockIdx.x * kScanWaves + wave;
+        if (t0 < v.n_tiles) w_next = rowset_word(v.alive, rs, mine, t0);
+    }
     for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+        const uint64_t w = w_next;                                     // (SETS) lane j: am_j of this tile
+        if constexpr (SETS) {
+            if (t + tw < v.n_tiles) w_next = rowset_word(v.alive, rs, mine, t + tw);
+            if (__ballot(w != 0ull) == 0ull) {                         // nobody's candidate in this tile
+#pragma unroll
+                for (int j = 0; j < QB; j++)
+                    if ((uint32_t)j < nq) __builtin_nontemporal_store(0xFFFFFFFFu, &lo_all[(size_t)j * n + t * 64 + lane]);
+                continue;
+            }
+        }
         const uint32_t row = t * 64 + lane;
         const double rn = v.rnorm[row];                                // (requested ahead of the tile's bytes: there when the sums are)
         const float sc = v.rscale8[row], rr = v.rres8[row];
-        const bool live = (v.alive[t] >> lane) & 1ull;                 // (dead rows and the last tile's padding: never candidates, never in a bound)
+        bool live_all = false;
+        if constexpr (!SETS) live_all = (v.alive[t] >> lane) & 1ull;   // (dead rows and the last tile's padding: never candidates, never in a bound)
         i32 acc[QB][4];
 #pragma unroll
         for (int j = 0; j < QB; j++) { acc[j][0] = 0; acc[j][1] = 0; acc[j][2] = 0; acc[j][3] = 0; }
@@ -772,6 +802,15 @@ k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __rest
 #pragma unroll
         for (int j = 0; j < QB; j++) {
             if ((uint32_t)j < nq) {                                    // (uniform) slots past nq produce nothing
+                bool live;
+                if constexpr (SETS) {
+                    const uint64_t am = readlane64(w, (uint32_t)j);    // wave-uniform again
+                    if (am == 0ull) {                                  // not this query's tile: no interval; (first) the list and the threshold stay dead
+                        __builtin_nontemporal_store(0xFFFFFFFFu, &lo_all[(size_t)j * n + row]);
+                        continue;
+                    }
+                    live = (am >> lane) & 1ull;
+                } else live = live_all;
                 // (each partial sum exact in int32: dim <= kBoundMaxDim)
                 const long long isum = ((long long)acc[j][0] + (long long)acc[j][1]) * 128ll + ((long long)acc[j][2] + (long long)acc[j][3]);
                 const double qn = qpar[j], sq = qpar[kBoundMqMax + j], qres = qpar[2 * kBoundMqMax + j];   // uniform
@@ -954,6 +993,52 @@ bool bound_scan8_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, u
 int host_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8, uint32_t candidate_tiles) {
     return bound_scan8_rule_filtered(metric, dim, rows, nq, k, mode, plane_mode_filtered, has_plane8 != 0, candidate_tiles) ? 1 : 0;
 }
+// The 8-bit stage in front of a FILTERED shared pass of 2 - 8 queries (k_bound_scan8_mq<., ., true>: a mask, a row set per query, where-filters,
+// the row-set front's shared passes): whenever the filtered bound rule takes the pass (asked with the copy held: the stage never starts a pass
+// the filtered bound scan would not take), the plane held, and the index's setter for such passes (IndexView::bound_plane_filtered_mq) or
+// QV_BOUND_PLANE_FILTERED_MQ — a knob of its own, independent of the three others — allows it: 1 whenever that holds, 2 never.
+// Automatic: a cell is taken only when 8-bit first beat bfloat16 first at every measured k, the slower 8-bit round against the faster
+// bfloat16 round, by more than both arms' round-to-round spread; never above what bound8_mq_auto allows for the same nq, never below
+// kBound8MinDim dimensions.  profiles/LAB_r13_bound_scan8_filtered_mq.md; us per call, bfloat16 first / 8-bit first (the faster bfloat16 round
+// against the slower 8-bit round), 768 dims, k = 1, 10, 64; f = candidate_tiles / tiles as the host computes it:
+//   f = 1.0   null sets         1M   nq 2: 317 / 210, 323 / 237, 395 / 400; nq 4: 332 / 224, 349 / 258, 443 / 474; nq 8: 464 / 293, 474 / 357, 691 / 695 (losses at k = 64)
+//                               3M   nq 2: 777 / 468, 788 / 496, 853 / 666; nq 4: 799 / 511, 813 / 548, 910 / 768; nq 5: 1082 / 594, 1103 / 651, 1264 / 952; nq 8: 1112 / 645, 1154 / 727, 1292 / 1135
+//                               10M  nq 2: 2440 / 1294, 2447 / 1312, 2519 / 1508; nq 4: 2502 / 1348, 2508 / 1371, 2621 / 1622; nq 5: 3370 / 1635, 3399 / 1723, 3581 / 2142; nq 8: 3491 / 1788, 3524 / 2021, 3818 / 2523
+//             a random 1 % set per query   1M nq 4: 307 / 205, 318 / 228, 360 / 302; nq 8: 462 / 272, 461 / 308, 526 / 404   3M nq 4: 764 / 485, 772 / 508, 827 / 613; nq 8: 1114 / 605, 1143 / 651, 1100 / 787
+//                               10M  nq 4: 2364 / 1261, 2367 / 1288, 2448 / 1451; nq 8: 3499 / 1717, 3527 / 1779, 3664 / 2003
+//             where, 10 % each  1M   nq 4: 343 / 235, 354 / 268, 428 / 405; nq 8: 503 / 328, 515 / 386, 659 / 588   3M nq 4: 848 / 554, 858 / 586, 932 / 749; nq 8: 1212 / 725, 1249 / 808, 1301 / 1101
+//                               10M  nq 4: 2645 / 1472, 2659 / 1510, 2733 / 1697; nq 8: 3846 / 2114, 3890 / 2240, 4077 / 2741
+//   one striped set, one tile in ten, named by every query (f = 0.1 nq: 0.2 / 0.4 / 0.5 / 0.8)
+//                               1M   nq 2: 119 / 103, 122 / 123, 181 / 224; nq 4: 122 / 111, 133 / 134, 212 / 300; nq 8: 198 / 150, 215 / 182, 340 / 397 (losses from k = 10 on)
+//                               3M   nq 2: 364 / 233, 376 / 269, 511 / 469; nq 4: 386 / 264, 406 / 313, 589 / 574; nq 8: 1005 / 449, 1048 / 530, 1209 / 904
+//                               10M  nq 2: 390 / 269, 399 / 294, 474 / 447; nq 4: 426 / 302, 441 / 346, 554 / 544; nq 8: 875 / 458, 906 / 532, 1106 / 832
+//             (wins at 3M and 10M at every k, but 2 - 6 % at k = 64 for 2 - 4 queries: no gain to speak of there, and nothing between these
+//              fractions and 0.9 was measured with distinct sets: f < 0.9 is declined)
+// A where-filter is counted as f = 1.0 whatever it selects (the host cannot know), and only one selecting 10 % was measured: a very selective
+// predicate, whose exact row-set scan reads next to nothing, is an UNMEASURED cell that AUTO takes — the bound pass still writes and collects
+// nq x tiles x 256 bytes of lower-bound words (0.3 GB, written and read again, for 8 queries at 10M rows).  "bf16" restores the earlier routing for such hosts.
+// So: f >= 0.9 from 3 000 000 rows of 768 dimensions or more, both QB; 1M loses at k = 64 with every tile a candidate.  Spreads <= 83 us at 10M, <= 11 us below.
+constexpr uint32_t kBound8FiltMqMinDim = 768, kBound8FiltMqMinRows4 = 3000000, kBound8FiltMqMinRows8 = 3000000;   // rows of at least 768 dimensions, QB = 4 / QB = 8; 0: never automatic
+static_assert(kBound8FiltMqMinDim >= kBound8MinDim && (kBound8FiltMqMinRows4 == 0 || kBound8FiltMqMinRows4 >= kBound8MqMinRows4) &&
+              (kBound8FiltMqMinRows8 == 0 || kBound8FiltMqMinRows8 >= kBound8MqMinRows8), "the filtered floors are never below the unfiltered shared pass's");
+static bool bound8_filtered_mq_auto(uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t candidate_tiles) {
+    const uint64_t n_tiles = ((uint64_t)n_rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
+    const uint32_t floor = nq <= 4 ? kBound8FiltMqMinRows4 : kBound8FiltMqMinRows8;
+    return dim >= kBound8FiltMqMinDim && floor != 0 && n_rows >= floor && ct * 10 >= n_tiles * 9 && bound8_mq_auto(dim, n_rows, nq);
+}
+static int bound_plane_filtered_mq_mode(int mode) { static const int env_mode = env_int("QV_BOUND_PLANE_FILTERED_MQ", 0); return mode ? mode : env_mode; }
+bool bound_scan8_rule_filtered_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_fmq, bool has_plane8, uint32_t candidate_tiles) {
+    plane_mode_fmq = bound_plane_filtered_mq_mode(plane_mode_fmq);
+    if (plane_mode_fmq == 2 || nq < 2 || nq > kBoundMqMax || !has_plane8 || !bound_scan_rule_filtered(metric, dim, n_rows, nq, k, mode, true, candidate_tiles)) return false;
+    if (plane_mode_fmq == 1) return true;
+    return bound8_filtered_mq_auto(dim, n_rows, nq, candidate_tiles);
+}
+bool bound_scan8_applies_filtered_mq(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
+    return v.plane != nullptr && bound_scan8_rule_filtered_mq(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_filtered_mq, v.plane8 != nullptr, candidate_tiles);
+}
+int host_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_fmq, int has_plane8, uint32_t candidate_tiles) {
+    return bound_scan8_rule_filtered_mq(metric, dim, rows, nq, k, mode, plane_mode_fmq, has_plane8 != 0, candidate_tiles) ? 1 : 0;
+}
 size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles) {
     return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)n_tiles * 64 * sizeof(uint32_t);
 }
@@ -1059,17 +1144,20 @@ size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k,
 }
 hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                                 uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets, bool plane8_first) {
-    // plane8_first (unfiltered passes only): the 8-bit stage — k_bound_prep8_mq, k_bound_scan8_mq, merge, collect, k_bound_rescore_mq<., 1> — in
-    // front, in the same workspace (the stages run one after the other: the query terms lie where the float32 block goes, the scalars where
+    // plane8_first: the 8-bit stage — k_bound_prep8_mq, k_bound_scan8_mq (with h_sets: its set form over the same table), merge, collect,
+    // k_bound_rescore_mq<., 1> — in front, in the same workspace (the stages run one after the other: the query terms lie where the float32 block goes, the scalars where
     // the norms go), and the bfloat16 stage's launches gated on the count of queries it handed on.
     // h_sets (optional, a HOST array of nq): query j restricted to alive & h_sets[j] — k_bound_scan_mq<., ., true> and the set-carrying redo.
     // Null: the unfiltered pass.  (Whether the path is TAKEN is the caller's decision — plan_flat, or the row-set path's one question to
     // bound_scan_applies_filtered; here only what the kernels need: metric, width, the copy, k, nq planes of lower bounds under 2 GiB.)
     if (nq < 2 || !bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
-    if (plane8_first && (h_sets || !v.plane8)) return hipErrorInvalidValue;
+    if (plane8_first && !v.plane8) return hipErrorInvalidValue;
     BoundSetTable tab;
     for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
-    if (h_sets && trace_filtered()) fprintf(stderr, "qv: scan kernel = k_bound_scan_mq sets QB=%d (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
+    if (h_sets && trace_filtered()) {
+        if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8_mq sets QB=%d, then gated k_bound_scan_mq sets (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
+        else fprintf(stderr, "qv: scan kernel = k_bound_scan_mq sets QB=%d (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
+    }
     const uint32_t grid = p.grid;
     char* w = static_cast<char*>(d_ws);
     uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += up256((size_t)nq * grid * k * sizeof(uint64_t));
@@ -1098,7 +1186,8 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
             e = set_lds((k_bound_rescore_mq<MMM, 1>), lds2); if (e != hipSuccess) return e;                                   \
             e = set_lds((k_bound_rescore_mq<MMM, 2>), lds2); if (e != hipSuccess) return e;                                   \
             hipLaunchKernelGGL((k_bound_prep8_mq<QQ>), dim3(QQ), dim3(kScanBlock), 0, s, d_queries, nq, v.dim, reinterpret_cast<int8_t*>(qblk), qnorm, hand, d_stats); \
-            hipLaunchKernelGGL((k_bound_scan8_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, reinterpret_cast<const u4*>(qblk), qnorm, nq, k, lo_all, partial); \
+            if (h_sets) hipLaunchKernelGGL((k_bound_scan8_mq<MMM, QQ, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, reinterpret_cast<const u4*>(qblk), qnorm, nq, k, lo_all, partial, tab); \
+            else hipLaunchKernelGGL((k_bound_scan8_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, reinterpret_cast<const u4*>(qblk), qnorm, nq, k, lo_all, partial, NoSets{}); \
             e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s); if (e != hipSuccess) return e;             \
             hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand, (const uint32_t*)nullptr); \
             hipLaunchKernelGGL((k_bound_rescore_mq<MMM, 1>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, hand); \

@@ -52,6 +52,7 @@ struct IndexView {
     int       bound_plane; // qv_index_set_bound_plane: 0 the 8-bit stage from its measured row count on, 1 whenever it applies, 2 never
     int       bound_plane_filtered; // qv_index_set_bound_plane_filtered: the same three values for a filtered single query, a knob of its own
     int       bound_plane_mq; // qv_index_set_bound_plane_mq: the same three values for an unfiltered shared pass of 2 - 8 queries, a knob of its own
+    int       bound_plane_filtered_mq; // qv_index_set_bound_plane_filtered_mq: the same three values for a filtered shared pass of 2 - 8 queries, a knob of its own
 };
 
 struct GraphView {
@@ -203,7 +204,7 @@ size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k,
 hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                                 uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
                                 const RowSetRef* h_sets = nullptr,   // a HOST array of nq sets, at most 8: query j over alive & h_sets[j] (k_bound_scan_mq<., ., true>, the redo included)
-                                bool plane8_first = false);   // (unfiltered passes) the 8-bit stage (k_bound_scan8_mq) in front, the bfloat16 stage's launches gated behind it
+                                bool plane8_first = false);   // the 8-bit stage (k_bound_scan8_mq; with h_sets its set form) in front, the bfloat16 stage's launches gated behind it
 // bound_scan_applies without an index (qv_scan_bound_applies): mode 0 = automatic (QV_BOUND_SCAN decides), 1 always, 2 never
 bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane);
 int bound_scan_mode(int mode);   // the mode in force: the index's own, else QV_BOUND_SCAN (read once)
@@ -227,6 +228,11 @@ int host_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32
 bool bound_scan8_rule_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, bool has_plane8);
 bool bound_scan8_applies_mq(const IndexView& v, uint32_t nq, uint32_t k);
 int host_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, int has_plane8);
+// ... in front of a FILTERED shared pass of 2 - 8 queries (k_bound_scan8_mq<., ., true>): the filtered bound rule's yes for that nq and those
+// candidate tiles, the plane, and a mode of its own (QV_BOUND_PLANE_* again; 0 automatic: QV_BOUND_PLANE_FILTERED_MQ decides)
+bool bound_scan8_rule_filtered_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_fmq, bool has_plane8, uint32_t candidate_tiles);
+bool bound_scan8_applies_filtered_mq(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
+int host_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_fmq, int has_plane8, uint32_t candidate_tiles);
 int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, float* d_lo, float* d_hi);
 int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res);
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches

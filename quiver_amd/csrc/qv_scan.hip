@@ -1065,7 +1065,7 @@ int host_flat_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32
     IndexView v = {};
     v.dim = dim; v.dim4 = (dim + 3) / 4; v.n_rows = rows; v.n_tiles = (rows + 63) / 64; v.metric = metric;
     v.bound_scan = bound_mode; v.bound_plane = plane_mode; v.bound_plane_filtered = plane_mode_filtered;
-    v.bound_plane_mq = QV_BOUND_PLANE_BF16;                            // (the shared pass's plane is a decision inside route 1: no route depends on it)
+    v.bound_plane_mq = QV_BOUND_PLANE_BF16; v.bound_plane_filtered_mq = QV_BOUND_PLANE_BF16;   // (the shared pass's plane is a decision inside route 1: no route depends on it)
     static uint16_t a_plane; static int8_t a_plane8;                   // (the rules ask whether a copy is held, never what it holds)
     if (has_plane) v.plane = &a_plane;
     if (has_plane8) v.plane8 = &a_plane8;
@@ -1081,7 +1081,8 @@ struct FlatCall {
     uint32_t* d_tickets; uint32_t* done_flag; uint32_t done_seq; bool* flag_used; uint32_t* d_bound_stats; uint32_t candidate_tiles;
 };
 static hipError_t route_bound_mq(const IndexView& v, const ScanPlan& p, const FlatPass& f, const FlatCall& c) {
-    const bool plane8_first = !f.filtered && bound_scan8_applies_mq(v, c.nq, c.k);   // the plane: a decision inside the route, as first8 is for routes 5 / 6
+    // the plane: a decision inside the route, as first8 is for routes 5 / 6 (a masked pass: the filtered shared pass's own rule and knob)
+    const bool plane8_first = f.filtered ? bound_scan8_applies_filtered_mq(v, c.nq, c.k, c.candidate_tiles) : bound_scan8_applies_mq(v, c.nq, c.k);
     if (!f.filtered && trace_unfiltered()) {
         if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8_mq QB=%d + k_merge_lists + k_bound_collect_mq + k_bound_rescore_mq, then gated k_bound_scan_mq + k_merge_lists + k_bound_collect_mq + k_bound_rescore_mq (nq=%u, tiles=%u)\n", (int)f.qb, c.nq, v.n_tiles);
         else fprintf(stderr, "qv: scan kernel = k_bound_scan_mq QB=%d (nq=%u, tiles=%u)\n", (int)f.qb, c.nq, v.n_tiles);

@@ -417,6 +417,13 @@ class DeviceIndex:
         "bf16"; a knob of its own, independent of set_bound_plane and set_bound_plane_filtered (qv_index_set_bound_plane_mq)"""
         check(lib().qv_index_set_bound_plane_mq(self._h, self.BOUND_PLANE.get(mode, mode)))
 
+    def set_bound_plane_filtered_mq(self, mode):
+        """which plane a FILTERED shared pass of 2 - 8 queries starts on (search_masked, search_rowsets, search_where and their device forms
+        with 2 - 8 queries, the passes that concurrent row-set or where-filter callers share): "auto" (the measured shapes), "8bit" (whenever
+        the filtered bound scan takes the pass and the plane is held), "bf16"; a knob of its own, independent of set_bound_plane,
+        set_bound_plane_filtered and set_bound_plane_mq (qv_index_set_bound_plane_filtered_mq)"""
+        check(lib().qv_index_set_bound_plane_filtered_mq(self._h, self.BOUND_PLANE.get(mode, mode)))
+
     def bound_scan8_stats(self) -> dict:
         """survivors of the last 8-bit stage, searches it handed on to the bfloat16 stage, searches that took it, whether the plane exists"""
         out = (C.c_uint64 * 4)()
