@@ -31,6 +31,10 @@ type rows interface {
 	close()
 }
 
+// FlagL2ScanPlane (QV_FLAG_L2_SCAN_PLANE): an L2 index keeps the bfloat16 copy and the 8-bit plane that cosine and dot
+// indexes keep by default (+3 * dim + 8 bytes per row).  On every other metric it does nothing.
+const FlagL2ScanPlane uint64 = C.QV_FLAG_L2_SCAN_PLANE
+
 // Index implements core.Index and core.BatchIndex (pkg/core/collection.go:78-96) on libqv.  String ids and metadata
 // never leave Go; the device sees row numbers, the analogue of hnsw.Node.VectorIndex (pkg/hnsw/hnsw.go:94).
 //
@@ -48,7 +52,8 @@ type Index struct {
 
 // New replaces hybrid.NewExactIndex (pkg/hybrid/exact.go:29-35) for one GPU.  dim is Collection.Dimension
 // (collection.go:105): the dimension lock-in of the first Insert (exact.go:43-47) happens here.
-// flags: C.QV_FLAG_BF16_ROWS for collections that serve BatchSearch traffic (+50 % device memory, faster batches).
+// flags: C.QV_FLAG_BF16_ROWS for collections that serve BatchSearch traffic (+50 % device memory, faster batches);
+// FlagL2ScanPlane for a Euclidean collection whose searches of 1 to 8 queries should be able to take the bound scan.
 func New(dim int, m Metric, device int, flags uint64) (*Index, error) {
 	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
 	var h *C.qv_index

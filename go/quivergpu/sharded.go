@@ -11,7 +11,7 @@ import "C"
 // The returned *Index is the same type with the same methods as New's: core.Index + core.BatchIndex, any k, filtered
 // search, negative examples.  Row ids are `shard*span + local row` and stay stable as shards grow.
 //
-// flags: C.QV_FLAG_BF16_ROWS passes through to every shard; C.QV_SHARDED_PEER_COPY replaces the collective with
+// flags: C.QV_FLAG_BF16_ROWS and FlagL2ScanPlane pass through to every shard; C.QV_SHARDED_PEER_COPY replaces the collective with
 // point-to-point copies into the first device (and allows a device to be listed more than once).
 func NewSharded(dim int, m Metric, devices []int, flags uint64) (*Index, error) {
 	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread

@@ -110,7 +110,22 @@ typedef enum qv_status {
                                     row: 4616 -> 5392 at 768 dimensions), on which a single query rejects rows first — unfiltered
                                     (qv_index_set_bound_plane) or under a mask, a row set or a where-filter
                                     (qv_index_set_bound_plane_filtered).  This flag leaves out both; an 8-bit plane that cannot be
-                                    allocated is given up alone and searches start on the bfloat16 copy */
+                                    allocated is given up alone and searches start on the bfloat16 copy.  A Euclidean index created
+                                    with QV_FLAG_L2_SCAN_PLANE keeps the same planes; this flag beside that one wins: no planes */
+#define QV_FLAG_L2_SCAN_PLANE 8ull /* a QV_L2 index keeps what cosine and dot indexes keep by default — the bfloat16 copy, and for a
+                                    dimension that is a multiple of 16 up to 4096 the 8-bit plane with its scale and residual per row
+                                    (+3 * dim + 8 bytes per row) — in the same layout, refreshed by the same calls, given up in the
+                                    same way when an allocation fails.  Its searches of 1 to 8 queries for k <= 64 can then take the
+                                    bound scan (qv_index_set_bound_scan and the plane setters govern it unchanged), with the exact
+                                    scan's rows and float32 bits.  The automatic rules take such an index from the shapes measured
+                                    for it (profiles/LAB_r14_bound_scan_l2.md): dot's floors, except that one unfiltered query on rows
+                                    narrower than 768 dimensions waits for 10M rows, and a filtered search for nine tenths of the tiles
+                                    holding a candidate.  On every other metric the flag does nothing; QV_L2SQ, QV_L2_F32 and QV_L2SQ_F64 keep no
+                                    planes.  QV_FLAG_BF16_ROWS alone on a QV_L2 index stays a copy for the batched filter: no bound scan */
+/* FOR THE qv_scan_* RULE FUNCTIONS ONLY: "a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE", where they take a metric.  They accept it
+ * wherever they accept QV_COSINE and QV_DOT (plain QV_L2 keeps answering 0); qv_index_metric still answers QV_L2, and qv_index_create
+ * rejects the code. */
+#define QV_RULE_L2_PLANES 0x101
 
 /* ---- lifecycle ------------------------------------------------------------------ */
 
@@ -377,8 +392,8 @@ int qv_index_search_batched(qv_index* idx, const float* queries, uint32_t nq, ui
 #define QV_FILTER_OFF       4   /* no filter: every batch of this index takes the exact scans (what tests of those scans choose) */
 int qv_index_set_filter(qv_index* idx, int filter);
 
-/* The single-query scan that rejects rows on the bfloat16 copy (cosine and dot, 1 <= k <= 64, a dimension that is a multiple of
- * 16): stage 1 streams the copy, derives a certified interval of every row's distance and ends with the k-th smallest upper
+/* The single-query scan that rejects rows on the bfloat16 copy (cosine, dot, and QV_L2 indexes created with QV_FLAG_L2_SCAN_PLANE;
+ * 1 <= k <= 64, a dimension that is a multiple of 16): stage 1 streams the copy, derives a certified interval of every row's distance and ends with the k-th smallest upper
  * bound; the rows whose lower bound is within it (k plus a handful) get their distances from the float32 rows in the scan's own
  * arithmetic.  Results are
  * bit-identical to the exact scan's; when the bound cannot decide (too many survivors, a query whose norm is not a number, huge or
@@ -505,7 +520,8 @@ int qv_scan_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq,
 /* The interval the 8-bit stage derives for one row, on the host (the kernel's own function): isum = sum qq_i r8_i, the integer dot
  * product of the quantised query (qq = rint(q / sq), sq = max|q_i| / 16256) with the row's bytes, qn = |query|, qres = |q - sq qq|
  * rounded up, rn = |row|, rscale8 / rres8 = the row's scale and residual (qv_scan_quantize_row8).  Returns 1 when the bound says
- * nothing about the row or the query (always a survivor), 0 otherwise with [*d_lo, *d_hi] containing the float32 distance, < 0 on an error. */
+ * nothing about the row or the query (always a survivor), 0 otherwise with [*d_lo, *d_hi] containing the float32 distance, < 0 on an error.
+ * metric: QV_COSINE, QV_DOT or QV_L2 (the interval does not depend on how an index was created); every other metric: QV_ERR_UNSUPPORTED. */
 int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, double qn, double qres, double rn, float rscale8, float rres8, float* d_lo, float* d_hi);
 /* One row as the index keeps it in the 8-bit plane: out_bytes[dim] = clamp(rint(r_i / scale), -127, 127), *out_scale = max|r_i| / 127
  * rounded up, *out_res = |r - scale r8| computed in float64 from those bytes and rounded up — NaN for a row the bound says nothing
@@ -513,7 +529,9 @@ int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, d
 int qv_scan_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res);
 /* Whether a search of nq queries for k results over rows x dim of `metric` would take the path under `mode` (QV_BOUND_SCAN_*;
  * has_plane: the index holds the copy) — the dispatch's own rule, on the host, without an index or a device.  1 / 0, < 0 on an
- * error.  (A k above the live rows is the caller's to know; a mask or a row set: qv_scan_bound_applies_filtered.) */
+ * error.  (A k above the live rows is the caller's to know; a mask or a row set: qv_scan_bound_applies_filtered.)  The metrics are
+ * QV_COSINE, QV_DOT and the rule code QV_RULE_L2_PLANES (every one of these rule functions and qv_scan_route take it); the automatic mode
+ * takes the last one from the shapes measured for it (dot's floors but for the two cases named at QV_FLAG_L2_SCAN_PLANE).  Plain QV_L2 and every other metric: 0. */
 int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane);
 /* The same rule for a filtered search (qv_index_search_masked, qv_index_search_rowsets and its device form): candidate_tiles = how many
  * 64-row tiles hold a candidate of any query of the pass, as the host knows it without a device read — a row set counts its non-empty
@@ -540,16 +558,20 @@ int qv_scan_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t
 int qv_scan_route_ex(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
                      uint32_t candidate_tiles, int plane_mode_filtered);
 /* The interval stage 1 derives for one row, on the host (the kernel's own function compiled for the CPU; metric QV_COSINE or
- * QV_DOT): s = the float32 chain of the query times the row's bfloat16 copy, qn = |query|, rn = |row|, rres = |row - bf16(row)|
+ * QV_DOT; every other metric: QV_ERR_UNSUPPORTED — QV_L2 included, whose interval is qv_scan_bound_interval_l2 below): s = the float32 chain of the query times the row's bfloat16 copy, qn = |query|, rn = |row|, rres = |row - bf16(row)|
  * rounded up.  Returns 1 when the row is one the bound says nothing about (always a survivor), 0 otherwise with
  * [*d_lo, *d_hi] containing the float32 distance, < 0 on an error. */
 int qv_scan_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi);
+/* The same for QV_L2: the interval of the Euclidean distance from the same stage-1 inputs (it does not depend on how an index was created).
+ * An entry point of its own, because qv_scan_bound_interval has always answered QV_ERR_UNSUPPORTED for QV_L2 and keeps doing so;
+ * qv_scan_bound_interval8 takes QV_L2 as a metric.  Same return values. */
+int qv_scan_bound_interval_l2(uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi);
 /* FOR TESTS: one of the arrays ingest derives per row, copied to the host raw — no kernel, no decoding — after the device has
  * finished the index's work.  QV_DEBUG_RNORM: |r|, one double per row slot; QV_DEBUG_RRES: |r - bf16(r)| rounded up, one float per
  * row slot; QV_DEBUG_PLANE: the bfloat16 copy's bytes ([tile][16-dim step][32-row block][8-dim half][row of block][8 values]).
  * The extent is tiles in use x 64 slots (tiles in use x the copy's bytes per tile, 2 * 64 * 16 * ceil(dim / 16), for the copy); slots
  * past the last row and dead rows hold whatever was written there last.  QV_ERR_UNSUPPORTED for an array this index does not keep
- * (the copy without QV_FLAG_BF16_ROWS on a metric other than cosine / dot, under QV_FLAG_NO_SCAN_PLANE or after a failed
+ * (the copy without QV_FLAG_BF16_ROWS on a metric other than cosine / dot / QV_L2 with QV_FLAG_L2_SCAN_PLANE, under QV_FLAG_NO_SCAN_PLANE or after a failed
  * allocation; the residual and the norm on metrics whose ingest does not compute them), QV_ERR_INVALID_ARG when `bytes` is less
  * than the extent. */
 #define QV_DEBUG_RNORM 0
@@ -705,7 +727,7 @@ int qv_graph_stats(const qv_graph* g, double* build_seconds, uint64_t* build_bat
  *                    the k best of the gathered lists, the whole batch at once.  Beyond (a filtered Collection.Search asks
  *                    for k = Index.Size(), collection.go:679-682): every shard ranks its rows (radix sort), the sorted runs
  *                    are exchanged and one stable radix sort on the first device merges them
- *   flags            QV_FLAG_ROWMAJOR, QV_FLAG_BF16_ROWS and QV_FLAG_NO_SCAN_PLANE pass through to the shards; QV_SHARDED_PEER_COPY replaces the collective with
+ *   flags            QV_FLAG_ROWMAJOR, QV_FLAG_BF16_ROWS, QV_FLAG_NO_SCAN_PLANE and QV_FLAG_L2_SCAN_PLANE pass through to the shards; QV_SHARDED_PEER_COPY replaces the collective with
  *                    point-to-point copies into the first device (and lets several shards share one device, which
  *                    RCCL does not allow: how the tests exercise 3 and 8 shards on a 1-GPU box)
  * Threading: as qv_index — searches, qv_sharded_distance_rows and qv_sharded_get_row(s) may run concurrently from many

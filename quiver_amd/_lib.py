@@ -14,6 +14,8 @@ QV_ERR_NO_DEVICE, QV_ERR_DEVICE, QV_ERR_OOM, QV_ERR_UNSUPPORTED = -5, -6, -7, -8
 QV_FLAG_ROWMAJOR = 1
 QV_FLAG_BF16_ROWS = 2
 QV_FLAG_NO_SCAN_PLANE = 4
+QV_FLAG_L2_SCAN_PLANE = 8      # a QV_L2 index keeps the bfloat16 copy and the 8-bit plane: its searches can take the bound scan
+QV_RULE_L2_PLANES = 0x101      # such an index, as the qv_scan_* rule functions take it where they take a metric
 QV_BOUND_SCAN_AUTO, QV_BOUND_SCAN_ALWAYS, QV_BOUND_SCAN_NEVER = 0, 1, 2
 QV_COL_F64, QV_COL_U32 = 0, 1
 QV_SET_AND, QV_SET_OR, QV_SET_ANDNOT = 0, 1, 2
@@ -97,6 +99,7 @@ PROTOTYPES = {
     "qv_index_bound_scan_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_sharded_bound_scan_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_scan_bound_interval": (C.c_int, [C.c_int, C.c_uint32, C.c_float, C.c_double, C.c_double, C.c_float, _f32p, _f32p]),
+    "qv_scan_bound_interval_l2": (C.c_int, [C.c_uint32, C.c_float, C.c_double, C.c_double, C.c_float, _f32p, _f32p]),
     "qv_index_set_bound_plane": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_sharded_set_bound_plane": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_bound_scan8_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

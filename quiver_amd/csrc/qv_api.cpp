@@ -117,7 +117,7 @@ int ensure_rows(qv_index* idx, uint64_t rows, bool exact) {
     if (e == hipSuccess && (idx->flags & QV_FLAG_ROWMAJOR))
         e = regrow(&idx->d_rowmaj, (size_t)idx->n_rows * idx->dim * sizeof(float), new_tiles * 64 * (size_t)idx->dim * sizeof(float));
     if (e == hipSuccess && idx->wants_plane()) {
-        // the bfloat16 copy: required under QV_FLAG_BF16_ROWS; otherwise (the default on cosine / dot indexes, for the single-query bound
+        // the bfloat16 copy: required under QV_FLAG_BF16_ROWS; otherwise (the default on cosine / dot indexes and on QV_FLAG_L2_SCAN_PLANE ones, for the single-query bound
         // scan) an accelerator — when it does not fit, the index frees it and carries on without: searches take the exact scan
         hipError_t eb = getenv("QV_TEST_PLANE_OOM") && !(idx->flags & QV_FLAG_BF16_ROWS) ? hipErrorOutOfMemory
                                                                                           : regrow(&idx->d_bf16, used_tiles * idx->bf16_tile_bytes(), new_tiles * idx->bf16_tile_bytes());
@@ -1730,7 +1730,7 @@ int qv_scan_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, 
 }
 
 int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, double qn, double qres, double rn, float rscale8, float rres8, float* d_lo, float* d_hi) {
-    if (metric != QV_COSINE && metric != QV_DOT) return fail(QV_ERR_UNSUPPORTED, "the bound scan's metrics are cosine and dot; got %d", metric);
+    if (metric != QV_COSINE && metric != QV_DOT && metric != QV_L2) return fail(QV_ERR_UNSUPPORTED, "the bound scan's metrics are cosine, dot and l2; got %d", metric);
     if (!d_lo || !d_hi || dim == 0) return fail(QV_ERR_INVALID_ARG, "d_lo/d_hi is null or dim is 0");
     return qv::host_bound_interval8(metric, dim, (long long)isum, sq, qn, qres, rn, rscale8, rres8, d_lo, d_hi);
 }
@@ -1741,9 +1741,16 @@ int qv_scan_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, flo
 }
 
 int qv_scan_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {
-    if (metric != QV_COSINE && metric != QV_DOT) return fail(QV_ERR_UNSUPPORTED, "the bound scan's metrics are cosine and dot; got %d", metric);
+    // (QV_L2 stays unsupported HERE, as callers of this entry point have known it: its interval is qv_scan_bound_interval_l2)
+    if (metric != QV_COSINE && metric != QV_DOT)
+        return fail(QV_ERR_UNSUPPORTED, "the bound scan's metrics are cosine, dot and l2, and this function serves cosine and dot (l2: qv_scan_bound_interval_l2); got %d", metric);
     if (!d_lo || !d_hi || dim == 0) return fail(QV_ERR_INVALID_ARG, "d_lo/d_hi is null or dim is 0");
     return qv::host_bound_interval(metric, dim, s, qn, rn, rres, d_lo, d_hi);
+}
+
+int qv_scan_bound_interval_l2(uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {
+    if (!d_lo || !d_hi || dim == 0) return fail(QV_ERR_INVALID_ARG, "d_lo/d_hi is null or dim is 0");
+    return qv::host_bound_interval(QV_L2, dim, s, qn, rn, rres, d_lo, d_hi);
 }
 
 int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {

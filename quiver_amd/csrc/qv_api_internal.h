@@ -134,15 +134,20 @@ struct qv_index {
         v.bf16 = (flags & QV_FLAG_BF16_ROWS) ? d_bf16 : nullptr; v.plane = d_bf16; v.bound_scan = bound_scan;
         v.plane8 = d_plane8; v.rscale8 = d_rscale8; v.rres8 = d_rres8; v.bound_plane = bound_plane; v.bound_plane_filtered = bound_plane_filtered; v.bound_plane_mq = bound_plane_mq; v.bound_plane_filtered_mq = bound_plane_filtered_mq;
         v.dim = dim; v.dim4 = dim4; v.n_rows = n_rows; v.n_tiles = (n_rows + 63) / 64; v.metric = metric; v.filter = filter;
+        v.l2_planes = l2_planes() ? 1 : 0;
         return v;
     }
-    // cosine and dot indexes keep the bfloat16 copy unless told not to (QV_FLAG_NO_SCAN_PLANE) or it could not be allocated
+    // a Euclidean index that asked for the scan planes (QV_FLAG_L2_SCAN_PLANE; on every other metric the flag does nothing)
+    // (QV_FLAG_NO_SCAN_PLANE beside it wins, also where QV_FLAG_BF16_ROWS keeps a copy for the batched filter: no bound scan on that copy)
+    bool l2_planes() const { return metric == QV_L2 && (flags & QV_FLAG_L2_SCAN_PLANE) != 0 && !(flags & QV_FLAG_NO_SCAN_PLANE); }
+    bool plane_metric() const { return metric == QV_COSINE || metric == QV_DOT || l2_planes(); }
+    // cosine and dot indexes — and such a Euclidean one — keep the bfloat16 copy unless told not to (QV_FLAG_NO_SCAN_PLANE) or it could not be allocated
     bool wants_plane() const {
-        return (flags & QV_FLAG_BF16_ROWS) || (!(flags & QV_FLAG_NO_SCAN_PLANE) && !plane_lost && (metric == QV_COSINE || metric == QV_DOT));
+        return (flags & QV_FLAG_BF16_ROWS) || (!(flags & QV_FLAG_NO_SCAN_PLANE) && !plane_lost && plane_metric());
     }
     // ... and the 8-bit plane wherever they keep that copy BY DEFAULT and the 8-bit stage can walk the rows (whole 16-dimension steps, int32 sums)
     bool wants_plane8() const {
-        return !(flags & QV_FLAG_NO_SCAN_PLANE) && !plane_lost && !plane8_lost && (metric == QV_COSINE || metric == QV_DOT) && (dim & 15u) == 0 && dim <= 4096;
+        return !(flags & QV_FLAG_NO_SCAN_PLANE) && !plane_lost && !plane8_lost && plane_metric() && (dim & 15u) == 0 && dim <= 4096;
     }
     size_t plane8_tile_bytes() const { return (size_t)dim * 64; }
     size_t tile_bytes() const { return (size_t)dim4 * 64 * 16; }

@@ -12,6 +12,26 @@
 // 1e-12 for the float64 chains (S, the stored norms).  The distance is a monotone (non-increasing) function of the sum — the
 // division, the clamp, the subtraction and both roundings of finalize<M> are — so the float32 distance of the reference lies in
 // [finalize(S~ + m), finalize(S~ - m)], with the reference's own |q| and |r| in it: nothing else has to be rounded outward.
+//
+// ---- the Euclidean distance (QV_L2) from the same sums ----
+// The margin m above bounds |S~ - q.r| against the REAL dot product (the derivation passes through it; its last term is then slack), for the
+// bfloat16 chain and for the 8-bit integers alike, so stage 1 is untouched.  The reference (distances.go:48-54; acc1<QV_L2> / finalize<QV_L2>)
+// computes d_i = (double)fl32(q_i - r_i), D = a float64 fma chain of d_i^2, and returns (float)sqrt(D).  With E = |q - r|^2 = |q|^2 + |r|^2 - 2 q.r
+// as real numbers:
+//   fl32(q_i - r_i) = (q_i - r_i)(1 + delta), |delta| <= 2^-24   (a float32 difference in the subnormal range is exact: no underflow term)
+//   d_i^2 does not underflow in float64 (|d_i| >= 2^-149 or 0), and the chain of dim non-negative terms adds at most (dim + 1) 2^-53 relative
+//   so D in E [1 - theta, 1 + theta] with theta = 1.2e-7 >= 2^-23 + 2^-48 + 4097 * 2^-53 (dim <= 4096).
+// A = qn^2 + rn^2 from the norms at hand (float64 chains of dim terms and a square root each, squared again here): off by less than
+// 1e-12 A from |q|^2 + |r|^2, and A - 2 S~ is formed here with three more roundings of at most 2^-53 A each (|S~| <= A / 2 + m): together
+// below the 2e-12 A the interval carries.  So
+//   E in [A - 2 S~ - 2 m - 2e-12 A, A - 2 S~ + 2 m + 2e-12 A] = [E_lo, E_hi]
+//   D_lo = max(0, E_lo) (1 - theta)(1 - 1e-9),  D_hi = E_hi (1 + theta)(1 + 1e-9)      (the last factor: these lines' own roundings)
+// and the float32 distance of the reference lies in [finalize<QV_L2>(D_lo), finalize<QV_L2>(D_hi)]: the square root is the correctly
+// rounded one the exact scan takes and the float32 rounding is monotone, so nothing else is rounded outward.  A row equal to the query
+// has E = 0 >= E_lo, hence d_lo = 0.0 exactly.  E_hi that is NaN or negative (norms that are not numbers; never for a sum within its
+// margin) makes the row "unsure".  Rows within about 2 sqrt(m) of the query have d_lo = 0: they cost survivors only where the k-th
+// neighbour itself is that close — cosine's near-duplicate behaviour, in distance.  A zero query is legitimate here, but its norm is not one the
+// bound works with (bound_scan_norm_ok): the re-score hands such a query back to the exact scan, as for cosine and dot.
 #pragma once
 #include "qv_kernels.h"
 #include "qv_filter.h"
@@ -24,15 +44,29 @@ __host__ __device__ static inline double bound_scan_gamma(uint32_t dim) { return
 // not vanishing (underflow is outside the error model)
 __host__ __device__ static inline bool bound_scan_norm_ok(double n, uint32_t dim) { return n >= (double)filter_tiny_norm(dim) && n < 1.0e18; }
 
+constexpr double kBoundL2Theta = 1.2e-7, kBoundL2NormSlack = 2e-12;
+// the Euclidean interval from s = S~ (float64), its margin m, and the two norms; false: E_hi is not a non-negative number
+__host__ __device__ __forceinline__ bool bound_l2_ends(double s, double m, double qn, double rn, float& d_lo, float& d_hi) {
+    const double A = __builtin_fma(qn, qn, rn * rn);
+    const double c = A - 2.0 * s, w = 2.0 * m + kBoundL2NormSlack * A;
+    const double e_lo = c - w, e_hi = c + w;
+    if (!(e_hi >= 0.0)) { d_lo = -__builtin_inff(); d_hi = __builtin_nanf(""); return false; }
+    QConst qc; qc.qn = qn; qc.qn32 = 0.0f;
+    d_lo = finalize<QV_L2>((e_lo > 0.0 ? e_lo : 0.0) * ((1.0 - kBoundL2Theta) * (1.0 - 1e-9)), qc, rn);
+    d_hi = finalize<QV_L2>(e_hi * ((1.0 + kBoundL2Theta) * (1.0 + 1e-9)), qc, rn);
+    return true;
+}
+
 // s = S~, qn = |q| (the reference's chain), rn = |r| (stored), rres = |r - bf16(r)| rounded up (stored).  false: a row the bound says
 // nothing about — always a candidate (d_lo = -inf), never lowers a threshold (d_hi = NaN).
 template <int M>
 __host__ __device__ __forceinline__ bool bound_scan_interval(float s, double qn, double rn, float rres, uint32_t dim, double gamma, float& d_lo, float& d_hi) {
-    static_assert(M == QV_COSINE || M == QV_DOT, "the bound scan's metrics");
+    static_assert(M == QV_COSINE || M == QV_DOT || M == QV_L2, "the bound scan's metrics");
     const double rr = (double)rres;
     const bool sure = bound_scan_norm_ok(rn, dim) && rr >= 0.0 && rr < 1.0e18 && (s - s) == 0.0f;
     if (!sure) { d_lo = -__builtin_inff(); d_hi = __builtin_nanf(""); return false; }
     const double m = qn * (rr + gamma * (rn + rr)) * (1.0 + 1e-9);     // (the factor: this line's own roundings, and S~ +- m below)
+    if constexpr (M == QV_L2) return bound_l2_ends((double)s, m, qn, rn, d_lo, d_hi);
     QConst qc; qc.qn = qn; qc.qn32 = 0.0f;
     d_lo = finalize<M>((double)s + m, qc, rn);
     d_hi = finalize<M>((double)s - m, qc, rn);
@@ -91,13 +125,14 @@ __host__ __device__ static inline float bound8_row_res(bool bad, float maxabs, d
 template <int M>
 __host__ __device__ __forceinline__ bool bound_scan_interval8(long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, uint32_t dim,
                                                               float& d_lo, float& d_hi) {
-    static_assert(M == QV_COSINE || M == QV_DOT, "the bound scan's metrics");
+    static_assert(M == QV_COSINE || M == QV_DOT || M == QV_L2, "the bound scan's metrics");
     const double rr = (double)rres8, sc = (double)rscale;
     const bool sure = bound_scan_norm_ok(rn, dim) && bound_scan_norm_ok(qn, dim) && rr >= 0.0 && rr < 1.0e18 && qres >= 0.0 && qres < 1.0e18 &&
                       sq > 0.0 && sq < 1.0e36 && sc > 0.0 && sc < 1.0e36;
     if (!sure) { d_lo = -__builtin_inff(); d_hi = __builtin_nanf(""); return false; }
     const double s = sq * sc * (double)isum;
     const double m = (qn * rr + qres * (rn + rr) + 1e-12 * (qn + qres) * (rn + rr)) * (1.0 + 1e-9);
+    if constexpr (M == QV_L2) return bound_l2_ends(s, m, qn, rn, d_lo, d_hi);
     QConst qc; qc.qn = qn; qc.qn32 = 0.0f;
     d_lo = finalize<M>(s + m, qc, rn);
     d_hi = finalize<M>(s - m, qc, rn);

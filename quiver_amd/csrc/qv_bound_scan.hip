@@ -1,4 +1,4 @@
-// qv_bound_scan.hip — the bound scan: a fused flat search (k <= 64, cosine / dot) answered from the index's reduced copies of the rows — the
+// qv_bound_scan.hip — the bound scan: a fused flat search (k <= 64; cosine, dot, or a Euclidean index created with QV_FLAG_L2_SCAN_PLANE) answered from the index's reduced copies of the rows — the
 // bfloat16 copy, with the 8-bit plane in front of it for one query and for a shared pass of 2 - 8, each unfiltered or filtered — by rejecting
 // rows on a certified interval of the distance (qv_bound.h) and re-scoring the few survivors in the exact scan's arithmetic.  One query, the shared
 // pass of 2 - 8, their filtered forms;
@@ -224,7 +224,7 @@ __device__ __forceinline__ void bound_rescore_query(const IndexView& v, const fl
     // the survivors' rows and norms are requested before the query's norm is walked
     const f4* tiles = reinterpret_cast<const f4*>(v.tiles);
     if (wave == kScanWaves - 1) {
-        // |q| as the reference's chain (distances.go:20): cosine's finalize takes it, and both metrics' hand-back rule
+        // |q| as the reference's chain (distances.go:20): cosine's finalize takes it, and every metric's hand-back rule
         double ma = 0.0;
         for (uint32_t i = 0; i < v.dim; i++) { const double a = (double)q_lds[i]; ma = __builtin_fma(a, a, ma); }
         if (lane == 0) s_qn = __builtin_sqrt(ma);
@@ -852,6 +852,22 @@ k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __rest
 // rows that depends on the width — every query pays 8 bytes per row for its lower bounds whatever the width — per QB: the smallest measured
 // shape from which the path wins at every measured nq and k of that QB (profiles/LAB_r08_bound_scan_mq.md); narrower than
 // kBoundMqNarrowDim it is never automatic.
+// A Euclidean index that holds the planes (the rule code QV_RULE_L2_PLANES; plain QV_L2 never): the same conditions, the same bytes streamed and
+// a few more flops per row for the interval.  "always" takes whatever cosine and dot take.  AUTOMATIC: only cells that were measured for it, a
+// cell kept where the arm beat the arm it replaces by more than both arms' spread at every measured k (profiles/LAB_r14_bound_scan_l2.md;
+// 1, 2, 4, 8 queries, k = 1, 10, 64, unfiltered and under a where-filter selecting 10 %, which the host counts as every tile a candidate).
+// us per call, exact / bfloat16 first / 8-bit first, one query, k = 1, 10, 64:
+//   768 dims   300 k 145 / 108 / 104, 149 / 116 / 125, 184 / 178 / 244      1M 455 / 269 / 189, 458 / 271 / 208, 489 / 331 / 355
+//              3M 1335 / 728 / 425, 1340 / 730 / 433, 1368 / 789 / 596      10M 4462 / 2324 / 1248, 4458 / 2331 / 1273, 4485 / 2388 / 1450
+//   128 dims   10M 740 / 453 / 257, 743 / 458 / 262, 778 / 497 / 317
+// bfloat16 first won all 120 cells; 8-bit first lost at 300 k, at 1M unfiltered with k = 64, and with 8 queries at 10M x 128 — cosine's losses, all
+// below the 8-bit floors below, which therefore hold for it unchanged.  Two constants of its own, where dot's floors accept cells that were
+// not measured for it: ONE unfiltered query on rows narrower than 768 dimensions is taken from 10M rows of 128 dimensions or more only (dot: any
+// width from 300 k rows; 1M x 128 was not measured here), and a FILTERED search only with nine tenths of the tiles holding a candidate (dot: one
+// query down to a tenth, 2 - 4 queries at 10M rows down to a fifth; sparse sets were not measured here).
+constexpr uint32_t kBoundL2NarrowDim = 128, kBoundL2NarrowRows = 10000000, kBoundL2WideDim = 768;
+static bool rule_metric_ok(int metric) { return metric == QV_COSINE || metric == QV_DOT || metric == QV_RULE_L2_PLANES; }
+static int rule_metric(const IndexView& v) { return v.metric == QV_L2 && v.l2_planes ? QV_RULE_L2_PLANES : v.metric; }
 constexpr uint32_t kBoundScanMinRows = 300000;   // one query, us, exact / bound scan at k = 1, 10, 64: 100 k x 768 65 / 63, 66 / 70, 86 / 122; 300 k x 768 154 / 107, 158 / 114, 190 / 169; 1M x 128 89 / 64, 93 / 68, 134 / 114
 // us per call, exact (k_flat_scan_mq) / bound, at k = 1, 10, 64:
 //   QB = 4   300 k x 768  nq 2: 195 / 154, 204 / 160, 273 / 223; nq 4: 193 / 160, 207 / 175, 276 / 271      1M x 128  nq 4: 97 / 93, 117 / 103, 214 / 216 (a loss)
@@ -864,14 +880,18 @@ int bound_scan_mode(int mode) { static const int env_mode = env_int("QV_BOUND_SC
 bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane) {
     mode = bound_scan_mode(mode);
     const uint32_t n_tiles = (n_rows + 63) / 64;
-    if (mode == 2 || nq < 1 || nq > kBoundMqMax || k < 1 || k > (uint32_t)kMaxFusedK || (metric != QV_COSINE && metric != QV_DOT) || !has_plane) return false;
+    if (mode == 2 || nq < 1 || nq > kBoundMqMax || k < 1 || k > (uint32_t)kMaxFusedK || !rule_metric_ok(metric) || !has_plane) return false;
     if ((dim & 15u) != 0 || dim > kBoundMaxDim || n_tiles < 8) return false;
-    if (nq == 1) return mode == 1 || n_rows >= kBoundScanMinRows;
+    if (nq == 1) {
+        if (mode == 1) return true;
+        if (metric == QV_RULE_L2_PLANES && dim < kBoundL2WideDim) return dim >= kBoundL2NarrowDim && n_rows >= kBoundL2NarrowRows;
+        return n_rows >= kBoundScanMinRows;
+    }
     if ((uint64_t)nq * n_tiles * 256 > (2ull << 30)) return false;
     const uint32_t min_rows = dim >= kBoundMqMinDim ? (nq <= 4 ? kBoundMqMinRows4 : kBoundMqMinRows8) : kBoundMqNarrowRows;
     return mode == 1 || (dim >= kBoundMqNarrowDim && n_rows >= min_rows);
 }
-bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) { return bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr); }
+bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) { return bound_scan_rule(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr); }
 // The 8-bit stage in front of it (k_bound_scan8): one unfiltered query the bound scan takes, on an index that holds the 8-bit plane.  The index's
 // plane setter (IndexView::bound_plane) or QV_BOUND_PLANE = 1 puts it first whenever that holds, 2 never; automatic from the smallest
 // measured row count from which 8-bit-first beats bfloat16-first at every measured k — never below kBoundScanMinRows, so a corpus under
@@ -892,7 +912,7 @@ bool bound_scan8_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, ui
     return plane_mode == 1 || (dim >= kBound8NarrowDim && n_rows >= (dim >= kBound8MinDim ? kBound8MinRows : kBound8NarrowRows));
 }
 bool bound_scan8_applies(const IndexView& v, uint32_t nq, uint32_t k) {
-    return v.plane != nullptr && bound_scan8_rule(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane, v.plane8 != nullptr);
+    return v.plane != nullptr && bound_scan8_rule(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane, v.plane8 != nullptr);
 }
 // The 8-bit stage in front of an UNFILTERED shared pass of 2 - 8 queries (k_bound_scan8_mq): a pass the bound scan takes (asked with the copy
 // held: the stage never starts a pass the bound scan would not take), the plane held, and the index's shared-pass plane setter
@@ -926,7 +946,7 @@ bool bound_scan8_rule_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq,
     return bound8_mq_auto(dim, n_rows, nq);
 }
 bool bound_scan8_applies_mq(const IndexView& v, uint32_t nq, uint32_t k) {
-    return v.plane != nullptr && bound_scan8_rule_mq(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_mq, v.plane8 != nullptr);
+    return v.plane != nullptr && bound_scan8_rule_mq(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_mq, v.plane8 != nullptr);
 }
 int host_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, int has_plane8) {
     return bound_scan8_rule_mq(metric, dim, rows, nq, k, mode, plane_mode_mq, has_plane8 != 0) ? 1 : 0;
@@ -954,13 +974,14 @@ bool bound_scan_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_
     if (mode == 1) return true;
     const uint64_t n_tiles = ((uint64_t)n_rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
     if (ct == 0 || dim < kBoundFiltMinDim || !bound_scan_rule(metric, dim, n_rows, nq, k, 0, has_plane)) return false;   // (never below the unfiltered floors)
+    if (metric == QV_RULE_L2_PLANES && ct * 10 < n_tiles * 9) return false;                      // (sparser filters were not measured for it)
     if (nq == 1) return ct * 10 >= n_tiles;                                                      // from kBoundScanMinRows rows; one tile in ten is the sparsest measured
     if (n_rows < kBoundFiltMqRows) return false;
     if (nq <= 4) return n_rows >= kBoundFiltBigRows ? ct * 5 >= n_tiles : ct * 10 >= n_tiles * 9;
     return ct * 10 >= n_tiles * 9 && (n_rows >= kBoundFiltBigRows || k <= kBoundFiltQb8SmallK);
 }
 bool bound_scan_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
-    return bound_scan_rule_filtered(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr, candidate_tiles);
+    return bound_scan_rule_filtered(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr, candidate_tiles);
 }
 // The 8-bit stage in front of a FILTERED single query (k_bound_scan8<., true>): whenever the filtered bound rule takes the search (asked with
 // the copy held: the stage never starts a search the bound scan would not take), one query, the plane held, and the index's filtered plane
@@ -988,7 +1009,7 @@ bool bound_scan8_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32
     return bound8_filtered_auto(dim, n_rows, candidate_tiles);
 }
 bool bound_scan8_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
-    return v.plane != nullptr && bound_scan8_rule_filtered(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_filtered, v.plane8 != nullptr, candidate_tiles);
+    return v.plane != nullptr && bound_scan8_rule_filtered(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_filtered, v.plane8 != nullptr, candidate_tiles);
 }
 int host_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8, uint32_t candidate_tiles) {
     return bound_scan8_rule_filtered(metric, dim, rows, nq, k, mode, plane_mode_filtered, has_plane8 != 0, candidate_tiles) ? 1 : 0;
@@ -1034,7 +1055,7 @@ bool bound_scan8_rule_filtered_mq(int metric, uint32_t dim, uint32_t n_rows, uin
     return bound8_filtered_mq_auto(dim, n_rows, nq, candidate_tiles);
 }
 bool bound_scan8_applies_filtered_mq(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
-    return v.plane != nullptr && bound_scan8_rule_filtered_mq(v.metric, v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_filtered_mq, v.plane8 != nullptr, candidate_tiles);
+    return v.plane != nullptr && bound_scan8_rule_filtered_mq(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_filtered_mq, v.plane8 != nullptr, candidate_tiles);
 }
 int host_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_fmq, int has_plane8, uint32_t candidate_tiles) {
     return bound_scan8_rule_filtered_mq(metric, dim, rows, nq, k, mode, plane_mode_fmq, has_plane8 != 0, candidate_tiles) ? 1 : 0;
@@ -1045,7 +1066,7 @@ size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tile
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                              uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked, bool plane8_first) {
     // (whether the path is TAKEN is plan_flat's decision; here only what the kernels need: metric, width, the copy, k — bound_scan_rule's "always")
-    if (!bound_scan_rule(v.metric, v.dim, v.n_rows, 1, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    if (!bound_scan_rule(rule_metric(v), v.dim, v.n_rows, 1, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
     if (plane8_first && !v.plane8) return hipErrorInvalidValue;
     const uint32_t grid = p.grid;
     char* w = static_cast<char*>(d_ws);
@@ -1094,7 +1115,8 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
         else stage(k_bound_scan<M>, lds1, k_bound_rescore<M>, ctrl, (uint32_t*)nullptr, (BoundCtrl*)nullptr, no_gate);
         return hipSuccess;
     };
-    const hipError_t e = v.metric == QV_COSINE ? run(std::integral_constant<int, QV_COSINE>{}) : run(std::integral_constant<int, QV_DOT>{});
+    const hipError_t e = v.metric == QV_COSINE ? run(std::integral_constant<int, QV_COSINE>{})
+                       : v.metric == QV_DOT  ? run(std::integral_constant<int, QV_DOT>{}) : run(std::integral_constant<int, QV_L2>{});
     if (e != hipSuccess) return e;
     *gate_out = &ctrl->flag;
     return hipGetLastError();
@@ -1102,13 +1124,16 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
 // the interval of one row on the host; 1: a row the bound says nothing about ("unsure"), as host_bound_interval8 reports it
 int host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {
     const double gamma = bound_scan_gamma(dim);
-    const bool sure = metric == QV_COSINE ? bound_scan_interval<QV_COSINE>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi) : bound_scan_interval<QV_DOT>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi);
+    const bool sure = metric == QV_COSINE ? bound_scan_interval<QV_COSINE>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi)
+                    : metric == QV_DOT  ? bound_scan_interval<QV_DOT>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi)
+                                        : bound_scan_interval<QV_L2>(s, qn, rn, rres, dim, gamma, *d_lo, *d_hi);
     return sure ? 0 : 1;
 }
 
 int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, float* d_lo, float* d_hi) {
     const bool sure = metric == QV_COSINE ? bound_scan_interval8<QV_COSINE>(isum, sq, qn, qres, rn, rscale, rres8, dim, *d_lo, *d_hi)
-                                          : bound_scan_interval8<QV_DOT>(isum, sq, qn, qres, rn, rscale, rres8, dim, *d_lo, *d_hi);
+                    : metric == QV_DOT  ? bound_scan_interval8<QV_DOT>(isum, sq, qn, qres, rn, rscale, rres8, dim, *d_lo, *d_hi)
+                                        : bound_scan_interval8<QV_L2>(isum, sq, qn, qres, rn, rscale, rres8, dim, *d_lo, *d_hi);
     return sure ? 0 : 1;
 }
 // one row as k_row_state8 (qv_misc.hip) leaves it: the bytes, the scale, the residual from the bytes (NaN: a row the bound says nothing about)
@@ -1150,7 +1175,7 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
     // h_sets (optional, a HOST array of nq): query j restricted to alive & h_sets[j] — k_bound_scan_mq<., ., true> and the set-carrying redo.
     // Null: the unfiltered pass.  (Whether the path is TAKEN is the caller's decision — plan_flat, or the row-set path's one question to
     // bound_scan_applies_filtered; here only what the kernels need: metric, width, the copy, k, nq planes of lower bounds under 2 GiB.)
-    if (nq < 2 || !bound_scan_rule(v.metric, v.dim, v.n_rows, nq, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    if (nq < 2 || !bound_scan_rule(rule_metric(v), v.dim, v.n_rows, nq, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
     if (plane8_first && !v.plane8) return hipErrorInvalidValue;
     BoundSetTable tab;
     for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
@@ -1201,7 +1226,8 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
         else hipLaunchKernelGGL((k_bound_rescore_mq<MMM>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, (uint32_t*)nullptr); \
     }
     if (v.metric == QV_COSINE) { if (nq <= 4) QV_BOUND_MQ(QV_COSINE, 4) else QV_BOUND_MQ(QV_COSINE, 8) }
-    else { if (nq <= 4) QV_BOUND_MQ(QV_DOT, 4) else QV_BOUND_MQ(QV_DOT, 8) }
+    else if (v.metric == QV_DOT) { if (nq <= 4) QV_BOUND_MQ(QV_DOT, 4) else QV_BOUND_MQ(QV_DOT, 8) }
+    else { if (nq <= 4) QV_BOUND_MQ(QV_L2, 4) else QV_BOUND_MQ(QV_L2, 8) }
 #undef QV_BOUND_MQ
     e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -53,6 +53,7 @@ struct IndexView {
     int       bound_plane_filtered; // qv_index_set_bound_plane_filtered: the same three values for a filtered single query, a knob of its own
     int       bound_plane_mq; // qv_index_set_bound_plane_mq: the same three values for an unfiltered shared pass of 2 - 8 queries, a knob of its own
     int       bound_plane_filtered_mq; // qv_index_set_bound_plane_filtered_mq: the same three values for a filtered shared pass of 2 - 8 queries, a knob of its own
+    int       l2_planes;  // a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE: the *_applies wrappers ask the rules as QV_RULE_L2_PLANES (0 on every other index)
 };
 
 struct GraphView {

@@ -1061,8 +1061,11 @@ FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t 
 }
 int host_flat_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
                     uint32_t candidate_tiles, int plane_mode_filtered) {
+    const bool l2_planes = metric == QV_RULE_L2_PLANES;               // (the rule code: a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE)
+    if (l2_planes) metric = QV_L2;
     if (k == 0 || k > (uint32_t)kMaxFusedK || nq == 0 || dim == 0 || rows == 0 || cus <= 0 || metric < QV_COSINE || metric > QV_L2SQ_F64) return -1;
     IndexView v = {};
+    v.l2_planes = l2_planes ? 1 : 0;
     v.dim = dim; v.dim4 = (dim + 3) / 4; v.n_rows = rows; v.n_tiles = (rows + 63) / 64; v.metric = metric;
     v.bound_scan = bound_mode; v.bound_plane = plane_mode; v.bound_plane_filtered = plane_mode_filtered;
     v.bound_plane_mq = QV_BOUND_PLANE_BF16; v.bound_plane_filtered_mq = QV_BOUND_PLANE_BF16;   // (the shared pass's plane is a decision inside route 1: no route depends on it)
@@ -1180,7 +1183,7 @@ static hipError_t route_bound(const IndexView& v, const ScanPlan& p, const FlatP
                                      f.filtered, plane8_first);
     if (e != hipSuccess) return e;
     QV_DISPATCH_METRIC(v.metric, {
-        if constexpr (MM == QV_COSINE || MM == QV_DOT) {
+        if constexpr (MM == QV_COSINE || MM == QV_DOT || MM == QV_L2) {
             e = set_lds((k_flat_scan<MM, kUnroll, true>), lds);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL((k_flat_scan<MM, kUnroll, true>), dim3(p.grid, 1), dim3(p.block), lds, s, v, c.d_queries, k, static_cast<uint64_t*>(c.d_ws), c.d_tickets, c.d_rows_out, c.d_dist_out, (uint32_t*)nullptr, 0u, gate);
@@ -1345,7 +1348,7 @@ hipError_t launch_flat_redo_flagged(const IndexView& v, const ScanPlan& p, const
     for (uint32_t first = 0; first < nq; first += kRedoSlots) {
         QV_DISPATCH_METRIC(v.metric, {
             // (the flags come from the batched filter path: its four metrics)
-            if constexpr (MM == QV_COSINE || MM == QV_DOT) {         // (sets come with a bound pass: its two metrics)
+            if constexpr (MM == QV_COSINE || MM == QV_DOT || MM == QV_L2) {   // (sets come with a bound pass: its three metrics)
                 if (h_sets) {
                     e = set_lds((k_flat_scan_redo<MM, kUnroll, true>), lds);
                     if (e != hipSuccess) return e;

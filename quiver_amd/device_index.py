@@ -103,13 +103,14 @@ def pack_where(per_query, handle_of=None):
 class DeviceIndex:
     default_filter = "auto"        # the filter kernel new indexes choose (set_filter); tests and bench.py compare the kernels through it
 
-    def __init__(self, dim: int, metric="cosine", device: int = 0, rowmajor: bool = False, bf16_rows: bool = False, filter=None, scan_plane: bool = True):
+    def __init__(self, dim: int, metric="cosine", device: int = 0, rowmajor: bool = False, bf16_rows: bool = False, filter=None, scan_plane: bool = True, l2_scan_plane: bool = False):
         self._h = C.c_void_p()
         self.dim = int(dim)
         self.metric = metric_id(metric)
         self.device = device
         check(lib().qv_index_create(C.byref(self._h), self.dim, self.metric, device, (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) |
-                                    (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE)))   # scan_plane=False: no default bfloat16 copy (cosine / dot), no bound scan
+                                    (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE) |   # scan_plane=False: no default bfloat16 copy (cosine / dot), no bound scan
+                                    (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0)))   # l2_scan_plane=True: an "l2" index keeps the planes cosine / dot keep by default
         f = filter if filter is not None else DeviceIndex.default_filter
         if f not in ("auto", 0):
             self.set_filter(f)
@@ -730,11 +731,11 @@ class ShardedIndex:
     one RCCL all-gather of the per-shard top-k per search, merge on the first device.  `devices` may repeat a device only
     with peer_copy=True (point-to-point exchange instead of the collective)."""
 
-    def __init__(self, dim: int, metric="cosine", devices=(0,), rowmajor: bool = False, peer_copy: bool = False, bf16_rows: bool = False, scan_plane: bool = True):
+    def __init__(self, dim: int, metric="cosine", devices=(0,), rowmajor: bool = False, peer_copy: bool = False, bf16_rows: bool = False, scan_plane: bool = True, l2_scan_plane: bool = False):
         self._h = C.c_void_p()
         self.dim = int(dim)
         devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-        flags = (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_SHARDED_PEER_COPY if peer_copy else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) | (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE)
+        flags = (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_SHARDED_PEER_COPY if peer_copy else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) | (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE) | (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0)
         check(lib().qv_sharded_create(C.byref(self._h), self.dim, metric_id(metric), devs, len(devices), flags))
 
     def close(self):
