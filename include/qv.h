@@ -392,6 +392,52 @@ int qv_index_search_batched(qv_index* idx, const float* queries, uint32_t nq, ui
 #define QV_FILTER_OFF       4   /* no filter: every batch of this index takes the exact scans (what tests of those scans choose) */
 int qv_index_set_filter(qv_index* idx, int filter);
 
+/* ---- filtered batches: 9 or more queries, a filter per query, on the batched path ----
+ * A call — or a pass that concurrent callers share — of 9 or more queries, k <= 64, through qv_index_search_rowsets or
+ * qv_index_search_where can take the batched path above instead of ceil(nq / 8) or ceil(nq / 16) exact corpus passes: the sample bound
+ * is taken over each query's own set, the matrix-core filter walks the corpus once for all of them, a candidate outside its query's
+ * set is dropped where it leaves the filter kernel, and the exact re-score ranks what is left.  Query q gets exactly what the exact
+ * filtered scan returns for live & set_q: rows, float32 bits, (distance, row) order, counts and padding.  The filter is a qv_rowset, a
+ * null set or a qv_where conjunction, mixed freely; metrics and shapes are those of the batched path (cosine, dot, L2, L2SQ; never an
+ * index under QV_FILTER_OFF); any nq, a remainder of up to 64 queries beyond a multiple of 256 as a pass of its own.
+ * A query the path cannot decide — more candidates than its list holds, a guessed bound that failed its check — and a query whose set
+ * is SPARSE are handed back to the exact row-set scan, alone; the others keep their answers.  Sparse: the filter kernels test every
+ * row against every query's threshold whatever the sets say, so the work a set causes grows as the inverse of its share of the rows;
+ * below `sparse_ppm` millionths of the rows the exact scan is the cheaper answer.  The share is counted on the device, on the sample,
+ * per query (a where-filter's is known nowhere else); the host counts a qv_rowset's selected rows, and a piece goes batched only when
+ * at least 9 of its queries are not known sparse that way — those that are ride along, in place, and come back through the same flag.
+ * A mis-route costs time, never bits.
+ *   mode         QV_FILTERED_BATCH_ALWAYS: whenever the above holds.  QV_FILTERED_BATCH_NEVER: the exact passes, as before this setter
+ *                existed.  QV_FILTERED_BATCH_AUTO (the default): only shapes measured faster than the exact passes by more than both
+ *                arms' spread, never below 300 000 rows; see qv_batched_applies_filtered.  The environment variable
+ *                QV_FILTERED_BATCH (1 always, 2 never; read once per process) sets the default of indexes that never call this.
+ *   sparse_ppm   0 .. 1000000; 0 = never hand a query back as sparse; 0xFFFFFFFF = the default (10 000: a hundredth of the rows).
+ * Needs external exclusion against running searches, like the other setters.
+ * Out of scope, all unchanged: the device-pointer forms (qv_index_search_rowsets_device, qv_index_search_where_device: nobody reads the
+ * redo flags there), qv_index_search_masked with 9 or more queries, k > 64, qv_sharded_*, and skipping tiles in the filter (it reads
+ * every row whatever the sets select). */
+#define QV_FILTERED_BATCH_AUTO   0
+#define QV_FILTERED_BATCH_ALWAYS 1
+#define QV_FILTERED_BATCH_NEVER  2
+int qv_index_set_filtered_batch(qv_index* idx, int mode, uint32_t sparse_ppm);
+/* out[0] = QUERIES that took the filtered batched path so far, out[1] = queries it handed back for an overflowing candidate list, no
+ * bound or a failed guess, out[2] = queries it handed back as sparse, out[3] = batches.  Counted when a call returns; does not wait. */
+int qv_index_filtered_batch_stats(qv_index* idx, uint64_t out[4]);
+/* The dispatch's own rule, without an index or a device: would a piece of nq filtered queries, k results each, over `rows` rows of
+ * `dim` dimensions take the batched path under `filter` (QV_FILTER_*) and `mode` (QV_FILTERED_BATCH_*; AUTO reads QV_FILTERED_BATCH
+ * first)?  n_not_sparse: how many of the piece's queries the host does not know to be sparse — a null set counts, a qv_where counts
+ * (the device decides), a qv_rowset counts when selected / rows is at or above the floor.  1 / 0, < 0 on an argument error.  NEVER: 0.
+ * Any mode: 0 for fewer than 9 queries or 9 not-sparse ones, k > 64, a metric or shape the batched path does not take, QV_FILTER_OFF.
+ * AUTO: 0 below 300 000 rows; beyond, only cells measured faster by more than both arms' spread.  The cells measured so far
+ * (profiles/LAB_r15_filtered_batch.md: 300k and 1M x 768, one call) are wins by 1.3 - 20 x for random sets and predicates, and losses
+ * for one tile-aligned set named by every query, which these arguments cannot tell apart; 10M rows and 128 dimensions are
+ * unmeasured.  So AUTO takes nothing yet: ask for the path with QV_FILTERED_BATCH_ALWAYS.  Monotone in n_not_sparse. */
+int qv_batched_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse);
+/* What the batched path's plan chose for the sample of a batch of nq queries, k results: its rows; the step of its 128-row groups —
+ * sample position i is row (i / 128) * group_step * 128 + i % 128 of the corpus; and the rank its bound is taken at (k, or more under
+ * a guessed bound).  QV_ERR_UNSUPPORTED when this index has no such route.  For tests and reports. */
+int qv_batched_sample_plan(qv_index* idx, uint32_t nq, uint32_t k, uint32_t* sample_rows, uint32_t* group_step, uint32_t* rank);
+
 /* The single-query scan that rejects rows on the bfloat16 copy (cosine, dot, and QV_L2 indexes created with QV_FLAG_L2_SCAN_PLANE;
  * 1 <= k <= 64, a dimension that is a multiple of 16): stage 1 streams the copy, derives a certified interval of every row's distance and ends with the k-th smallest upper
  * bound; the rows whose lower bound is within it (k plus a handful) get their distances from the float32 rows in the scan's own

@@ -35,4 +35,18 @@ def scan_bound8_applies_filtered_mq(metric, dim: int, rows: int, nq: int, k: int
         check(rc)
     return rc == 1
 
-__all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq", "scan_bound8_applies_filtered_mq"]
+def batched_applies_filtered(metric, dim: int, rows: int, nq: int, k: int, filter="auto", mode="auto", n_not_sparse: int | None = None) -> bool:
+    """whether a piece of nq FILTERED queries (a row set, no set or a where-filter each) would take the batched path — the dispatch's own rule, on
+    the host, without an index or a device (qv_batched_applies_filtered); filter / mode: as set_filter / set_filtered_batch take them;
+    n_not_sparse: the queries the host does not know to be below the sparse floor (None: all of them)"""
+    from ._lib import check
+    m = metric_id(metric) if isinstance(metric, str) else int(metric)
+    rc = lib().qv_batched_applies_filtered(m, dim, rows, nq, k, DeviceIndex.FILTERS.get(filter, filter), DeviceIndex.FILTERED_BATCH.get(mode, mode),
+                                           nq if n_not_sparse is None else n_not_sparse)
+    if rc < 0:
+        check(rc)
+    return rc == 1
+
+
+__all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq", "scan_bound8_applies_filtered_mq",
+           "batched_applies_filtered"]

@@ -17,6 +17,7 @@ QV_FLAG_NO_SCAN_PLANE = 4
 QV_FLAG_L2_SCAN_PLANE = 8      # a QV_L2 index keeps the bfloat16 copy and the 8-bit plane: its searches can take the bound scan
 QV_RULE_L2_PLANES = 0x101      # such an index, as the qv_scan_* rule functions take it where they take a metric
 QV_BOUND_SCAN_AUTO, QV_BOUND_SCAN_ALWAYS, QV_BOUND_SCAN_NEVER = 0, 1, 2
+QV_FILTERED_BATCH_AUTO, QV_FILTERED_BATCH_ALWAYS, QV_FILTERED_BATCH_NEVER = 0, 1, 2
 QV_COL_F64, QV_COL_U32 = 0, 1
 QV_SET_AND, QV_SET_OR, QV_SET_ANDNOT = 0, 1, 2
 QV_SHARDED_PEER_COPY = 1 << 32
@@ -93,6 +94,10 @@ PROTOTYPES = {
     "qv_merge_topk_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_merge_topk_shards_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_index_set_filter": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_set_filtered_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "qv_index_filtered_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_batched_applies_filtered": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32]),
+    "qv_batched_sample_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
     "qv_sharded_set_filter": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_set_bound_scan": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_sharded_set_bound_scan": (C.c_int, [C.c_void_p, C.c_int]),

@@ -1057,7 +1057,9 @@ static qv::RowSetRef rs_ref(const qv_index* idx, const RsFilter& f) {
 // bound8: a bound piece that starts on the 8-bit plane (k_bound_scan8_mq<., ., true>) — decided here too.  Its rule is asked with a second
 // count in which a transient set is EVERY tile, as the single query is planned: when it says yes the piece is a bound piece, 8-bit first,
 // whatever the first count said; with that rule's mode at "bf16" the first question alone decides, as before.
-struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; bool bound8; };
+// batched: a multi piece of 9 or more queries that takes the matrix-core filter with a set per query (launch_batched with BatchedSets;
+// filtered_batch_takes is the rule) — decided here too, and only for the host forms, whose caller reads the redo flags.
+struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; bool bound8; bool batched = false; };
 static uint32_t rowsets_cand_tiles(const qv_index* idx, const RsFilter* fl, uint32_t nq, bool transient_every_tile = false) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     uint64_t sum = 0;
@@ -1067,10 +1069,29 @@ static uint32_t rowsets_cand_tiles(const qv_index* idx, const RsFilter* fl, uint
     }
     return (uint32_t)std::min<uint64_t>(sum, n_tiles);
 }
-static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const RsFilter* fl, std::vector<RowsetPiece>& pieces) {
+// The filtered batch's rule for one piece.  What the host knows of a query's share of the rows: a null set is every row, a set its
+// selected bits against the sparse floor, a where-filter nothing — it counts as dense and the device decides (k_sets_sparse).  Known-sparse
+// queries of a piece that goes batched ride along, in place, and come back through the sparse flag.
+static uint32_t rowsets_not_sparse(const qv_index* idx, const RsFilter* fl, uint32_t nq) {
+    const uint64_t ppm = qv::filtered_batch_ppm(idx->filtered_batch_ppm);
+    uint32_t n = 0;
+    for (uint32_t q = 0; q < nq; q++)
+        n += fl[q].where || !fl[q].set || fl[q].set->selected * 1000000ull >= ppm * (uint64_t)idx->n_rows ? 1u : 0u;
+    return n;
+}
+static bool filtered_batch_takes(const qv_index* idx, uint32_t nq, uint32_t k, const RsFilter* fl) {
+    if (nq < qv::kFilteredBatchMinQueries || k > (uint32_t)qv::kMaxFusedK || idx->n_live < 4 * (uint64_t)k) return false;
+    if (!qv::filtered_batch_rule(idx->metric, idx->dim, idx->n_rows, nq, k, idx->filter, idx->filtered_batch, rowsets_not_sparse(idx, fl, nq))) return false;
+    return qv::batched_sets_supported(idx->view(), nq, k, idx->cus);   // (the route: sample scores from a filter kernel)
+}
+static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const RsFilter* fl, std::vector<RowsetPiece>& pieces, bool allow_batched = false) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     const qv::ScanPlan plan = qv::plan_scan(n_tiles, idx->cus);
     pieces.clear();
+    if (allow_batched && filtered_batch_takes(idx, nq, k, fl)) {
+        pieces.push_back(RowsetPiece{0, nq, k, true, false, rowsets_cand_tiles(idx, fl, nq), false, true});
+        return qv::batched_workspace_bytes(idx->view(), plan, nq, k);
+    }
     if (k <= (uint32_t)qv::kMaxFusedK && nq >= 2) {
         const uint32_t ct = rowsets_cand_tiles(idx, fl, nq);
         const bool bound8 = nq <= 8 && qv::bound_scan8_applies_filtered_mq(idx->view(), nq, k, rowsets_cand_tiles(idx, fl, nq, true));
@@ -1153,13 +1174,26 @@ static int where_enqueue(qv_index* idx, RsFilter* fl, uint32_t nq, const WherePl
 
 // enqueue the pieces on s: lists [nq][k], padded past every query's matches.  d_mask: (rows + 63) / 64 words for the candidate bitmaps.
 static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const RsFilter* fl, const std::vector<RowsetPiece>& pieces,
-                           void* ws, uint64_t* d_mask, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, uint32_t* d_tickets) {
+                           void* ws, uint64_t* d_mask, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, uint32_t* d_tickets,
+                           const qv::RowSetRef* d_sets = nullptr /* a batched piece: the call's table on the device, [nq] */, uint32_t** d_flags_out = nullptr) {
     const qv::IndexView v = idx->view();
     const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
     for (const RowsetPiece& p : pieces) {
         uint32_t* r_out = d_rows_out + (size_t)p.q0 * k;
         float* d_out = d_dist_out + (size_t)p.q0 * k;
         const float* q = d_queries + (size_t)p.q0 * idx->dim;
+        if (p.batched) {                                              // sample bound over the sets, the filter, the exact re-score: one corpus pass for the piece
+            if (!d_sets || !d_flags_out) return fail(QV_ERR_DEVICE, "filtered batch without its set table");
+            hipEvent_t ev0 = nullptr, ev1 = nullptr;
+            if (idx->profiling && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
+                std::lock_guard<std::mutex> g(idx->prof_mu);
+                idx->prof_events.emplace_back(ev0, ev1);
+            }
+            const qv::BatchedSets bs{d_sets + p.q0, qv::filtered_batch_ppm(idx->filtered_batch_ppm)};
+            hipError_t e = qv::launch_batched(v, plan, q, p.nq, k, ws, r_out, d_out, d_flags_out, idx->cus, s, ev0, ev1, &bs);
+            if (e != hipSuccess) return fail(QV_ERR_DEVICE, "filtered batch launch failed: %s", hipGetErrorString(e));
+            continue;
+        }
         if (p.multi) {
             std::vector<qv::RowSetRef> refs(p.nq);
             for (uint32_t i = 0; i < p.nq; i++) refs[i] = rs_ref(idx, fl[p.q0 + i]);
@@ -1220,9 +1254,20 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
         return QV_OK;
     }
     HIPCHK(hipSetDevice(idx->device));
+    // a filtered batch beyond 256 queries with a short remainder: the remainder as a call of its own, as qv_index_search_batched cuts it
+    // (padded to whole workgroups of 256 it would cost a second walk for a few queries); each part decides its route for itself
+    if (filtered_batch_takes(idx, nq, k, fl_in)) {
+        if (const uint32_t tail = nq > 256 && nq % 256 >= 1 && nq % 256 <= 64 ? nq % 256 : 0) {
+            const uint32_t head = nq - tail;
+            const int rc0 = rowsets_direct(idx, queries, head, k, fl_in, rows_out, dist_out, count_out);
+            if (rc0 != QV_OK) return rc0;
+            return rowsets_direct(idx, queries + (size_t)head * idx->dim, tail, k, fl_in + head, rows_out + (size_t)head * k, dist_out + (size_t)head * k, count_out + head);
+        }
+    }
     std::vector<RsFilter> fl(fl_in, fl_in + nq);                      // (the transient sets' words are placed below)
     std::vector<RowsetPiece> pieces;
-    const size_t ws_bytes = rowsets_plan(idx, nq, k, fl.data(), pieces);
+    const size_t ws_bytes = rowsets_plan(idx, nq, k, fl.data(), pieces, true);
+    const bool batched = pieces.size() == 1 && pieces[0].batched;
     bool any = false;
     for (const RowsetPiece& p : pieces) any = any || p.kk != 0;
     if (!any) {                                                       // no set holds a live row: nothing to run
@@ -1260,14 +1305,57 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
         }
         if ((rc = where_enqueue(idx, fl.data(), nq, wp, static_cast<uint64_t*>(c->d_where.p), static_cast<uint64_t*>(c->d_mask.p), d_lits, c->stream))) return rc;
     }
+    const size_t fbytes = 2 * (size_t)nq * sizeof(uint32_t);           // a batched piece: its redo flags, then its sparse flags
+    uint32_t* d_flags = nullptr;
+    if (batched) {                                                    // the sets' table: pinned memory -> the context's device array, on the call's stream
+        const size_t sbytes = (size_t)nq * sizeof(qv::RowSetRef);
+        if ((rc = c->h_sets.ensure(sbytes)) || (rc = c->d_sets.ensure(sbytes)) || (rc = c->h_ids.ensure(fbytes))) return rc;
+        qv::RowSetRef* refs = static_cast<qv::RowSetRef*>(c->h_sets.p);
+        for (uint32_t q = 0; q < nq; q++) refs[q] = rs_ref(idx, fl[q]);
+        HIPCHK(hipMemcpyAsync(c->d_sets.p, c->h_sets.p, sbytes, hipMemcpyHostToDevice, c->stream));
+    }
     rc = rowsets_enqueue(idx, static_cast<const float*>(c->d_q.p), nq, k, fl.data(), pieces, c->ws.p, static_cast<uint64_t*>(c->d_mask.p),
-                         static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<uint32_t*>(c->tickets.p));
+                         static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<uint32_t*>(c->tickets.p),
+                         batched ? static_cast<const qv::RowSetRef*>(c->d_sets.p) : nullptr, batched ? &d_flags : nullptr);
     if (rc != QV_OK) return rc;
     HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, obytes, hipMemcpyDeviceToHost, c->stream));
+    if (batched) HIPCHK(hipMemcpyAsync(c->h_ids.p, d_flags, fbytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(rows_out, c->h_rows.p, obytes);
     memcpy(dist_out, c->h_dist.p, obytes);
+    if (batched) {
+        // The queries the batch handed back — more candidates than slots, a guessed bound that failed its check, a sparse set — through the
+        // exact row-set pieces, with their filters, in this context: the transient where-words are still in d_where.
+        const uint32_t* flags = static_cast<const uint32_t*>(c->h_ids.p);
+        std::vector<uint32_t> redo;
+        uint64_t n_sparse = 0;
+        for (uint32_t q = 0; q < nq; q++) if (flags[q] || flags[nq + q]) { redo.push_back(q); n_sparse += flags[nq + q] ? 1 : 0; }
+        idx->fb_stats[0] += nq; idx->fb_stats[1] += redo.size() - n_sparse; idx->fb_stats[2] += n_sparse; idx->fb_stats[3] += 1;
+        if (!redo.empty()) {
+            const uint32_t nr = (uint32_t)redo.size();
+            std::vector<RsFilter> rfl(nr);
+            for (uint32_t i = 0; i < nr; i++) {
+                rfl[i] = fl[redo[i]];
+                memcpy(static_cast<float*>(c->h_q.p) + (size_t)i * idx->dim, queries + (size_t)redo[i] * idx->dim, idx->dim * sizeof(float));
+            }
+            std::vector<RowsetPiece> rpieces;
+            const size_t rws = rowsets_plan(idx, nr, k, rfl.data(), rpieces);
+            if ((rc = c->ws.ensure(rws))) return rc;
+            const size_t rq = (size_t)nr * idx->dim * sizeof(float), ro = (size_t)nr * k * sizeof(uint32_t);
+            HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, rq, hipMemcpyHostToDevice, c->stream));
+            rc = rowsets_enqueue(idx, static_cast<const float*>(c->d_q.p), nr, k, rfl.data(), rpieces, c->ws.p, static_cast<uint64_t*>(c->d_mask.p),
+                                 static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<uint32_t*>(c->tickets.p));
+            if (rc != QV_OK) return rc;
+            HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, ro, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, ro, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            for (uint32_t i = 0; i < nr; i++) {
+                memcpy(rows_out + (size_t)redo[i] * k, static_cast<const uint32_t*>(c->h_rows.p) + (size_t)i * k, k * sizeof(uint32_t));
+                memcpy(dist_out + (size_t)redo[i] * k, static_cast<const float*>(c->h_dist.p) + (size_t)i * k, k * sizeof(float));
+            }
+        }
+    }
     for (uint32_t q = 0; q < nq; q++) {                               // a list's results end where its padding begins (no row is 0xFFFFFFFF)
         uint32_t n = 0;
         while (n < k && rows_out[(size_t)q * k + n] != 0xFFFFFFFFu) n++;
@@ -1692,6 +1780,35 @@ int qv_index_set_bound_plane_filtered_mq(qv_index* idx, int mode) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
     if (mode < 0 || mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", mode);
     idx->bound_plane_filtered_mq = mode;
+    return QV_OK;
+}
+
+int qv_index_set_filtered_batch(qv_index* idx, int mode, uint32_t sparse_ppm) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_FILTERED_BATCH_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    if (sparse_ppm != 0xFFFFFFFFu && sparse_ppm > 1000000u)
+        return fail(QV_ERR_INVALID_ARG, "sparse_ppm is a share of the rows in millionths, 0 .. 1000000, or 0xFFFFFFFF for the default; got %u", sparse_ppm);
+    idx->filtered_batch = mode;
+    idx->filtered_batch_ppm = sparse_ppm;
+    return QV_OK;
+}
+
+int qv_index_filtered_batch_stats(qv_index* idx, uint64_t out[4]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    for (int i = 0; i < 4; i++) out[i] = idx->fb_stats[i].load();
+    return QV_OK;
+}
+
+int qv_batched_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse) {
+    if (mode < 0 || mode > QV_FILTERED_BATCH_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
+    return qv::filtered_batch_rule(metric, dim, rows, nq, k, filter, mode, std::min(n_not_sparse, nq)) ? 1 : 0;
+}
+
+int qv_batched_sample_plan(qv_index* idx, uint32_t nq, uint32_t k, uint32_t* sample_rows, uint32_t* group_step, uint32_t* rank) {
+    if (!idx || !sample_rows || !group_step || !rank) return fail(QV_ERR_INVALID_ARG, "index/sample_rows/group_step/rank is null");
+    if (!qv::batched_sample_plan(idx->view(), nq, k, idx->cus, sample_rows, group_step, rank))
+        return fail(QV_ERR_UNSUPPORTED, "no batched route with a sample from a filter kernel for %u queries, k %u on this index", nq, k);
     return QV_OK;
 }
 

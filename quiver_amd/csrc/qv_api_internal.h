@@ -6,6 +6,7 @@
 #include "qv_coalesce.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -69,10 +70,12 @@ struct SearchCtx {
     Buf d_q, d_rows, d_dist, d_ids, d_mask, ws, tickets;
     PinBuf h_q, h_rows, h_dist, h_ids, h_mask, h_flag;
     Buf d_where, d_lits; PinBuf h_lits;      // qv_index_search_where: the call's transient sets, and its literals when they do not fit the kernel arguments
+    Buf d_sets; PinBuf h_sets;               // a filtered batch: the call's RowSetRef table, staged from pinned memory on the call's stream
     uint32_t flag_seq = 0;                   // sequence number the small scan writes into h_flag when its results are in h_rows / h_dist
     void release() {
         d_q.release(); d_rows.release(); d_dist.release(); d_ids.release(); d_mask.release(); ws.release(); tickets.release();
         d_where.release(); d_lits.release(); h_lits.release();
+        d_sets.release(); h_sets.release();
         h_q.release(); h_rows.release(); h_dist.release(); h_ids.release(); h_mask.release(); h_flag.release();
         if (stream) (void)hipStreamDestroy(stream);
         stream = nullptr;
@@ -106,6 +109,9 @@ struct qv_index {
     int bound_plane_filtered = 0;              // qv_index_set_bound_plane_filtered
     int bound_plane_mq = 0;                    // qv_index_set_bound_plane_mq
     int bound_plane_filtered_mq = 0;           // qv_index_set_bound_plane_filtered_mq
+    int filtered_batch = 0;                    // qv_index_set_filtered_batch: QV_FILTERED_BATCH_*
+    uint32_t filtered_batch_ppm = 0xFFFFFFFFu; // ... and its sparse floor in millionths of the rows (0xFFFFFFFF: the default, 0: never sparse)
+    std::atomic<uint64_t> fb_stats[4] = {};    // qv_index_filtered_batch_stats: queries on the path, handed back (overflow / no bound / failed guess), handed back as sparse, batches
     uint32_t* d_bound_stats = nullptr;         // [0] survivors of the last bound scan, [1] hand-backs, [2] bound scans (written by the kernels)
     std::vector<uint64_t> alive_host;          // mirror of d_alive, for size bookkeeping and validation
     Buf mut_stage;                             // grow-only staging buffer of the mutating calls (add / remove / update run under the

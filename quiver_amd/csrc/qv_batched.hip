@@ -30,10 +30,15 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
                             float* __restrict__ Qt, float* __restrict__ cq, float* __restrict__ mq /*[2][nq_pad]: m_q, b_q*/, float* __restrict__ eq /*[nq_pad][2]*/,
                             uint32_t* __restrict__ cand_cnt, uint32_t* __restrict__ overflow, int bf16x3, int what, uint32_t cand_cap,
                             uint32_t steps_pad /* bfloat16 layout: steps of 16 dimensions per query block, zero padded (0 = ceil(dim / 16)) */,
-                            const float* __restrict__ group_min = nullptr, uint32_t n_groups = 0 /* the sample's per-group minima [nq_pad][n_groups]: the bound is selected here */) {
+                            const float* __restrict__ group_min = nullptr, uint32_t n_groups = 0 /* the sample's per-group minima [nq_pad][n_groups]: the bound is selected here */,
+                            const RowSetRef* sets = nullptr /* a filtered batch's table, one set per query (device): handed to the filter kernels' flush beside the cap */) {
     // what: 1 = operand layout only, 2 = filter constants only (needs sample_dist), 3 = both
     const uint32_t q = blockIdx.x;                     // one block per (padded) query
-    if (q == 0 && threadIdx.x == 0) cand_cnt[-1] = cand_cap;           // candidate slots per query, for the filter kernels (CandOut)
+    if (q == 0 && threadIdx.x == 0) {                                  // the words in front of the counters (kCandHeadWords)
+        cand_cnt[-1] = cand_cap;                                       // candidate slots per query, for the filter kernels (CandOut)
+        cand_cnt[-2] = 0u;
+        *reinterpret_cast<const RowSetRef**>(cand_cnt - kCandHeadWords) = sets;   // the batch's row sets, for cand_flush (null: unfiltered)
+    }
     const uint32_t dim4p = (dim4 + 1) & ~1u;           // chunk count padded to even: the MFMA step eats two chunks
     if (!(what & 1)) {
     } else if (bf16x3) {
@@ -213,7 +218,7 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
 // with the epilogue compiled out, -DQV_MFMA_F32_NOEPI) runs under the other's matrix instructions; the price is the query operand
 // read once per 64 rows instead of once per 128 by twice the waves: 16 bytes per cycle and CU from L2, ~10 TB/s over the chip —
 // measured 4.25 against 3.06 ms, same results.  Round 6 built it, measured it and ships NJ = 4 alone (NJ = 2: measurement build).
-template <int METRIC, int NJ>
+template <int METRIC, int NJ, bool SETS = false>
 __global__ void __launch_bounds__(256, NJ == 2 ? 2 : 1)
 k_mfma_filter(IndexView v, const float* __restrict__ Qt, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq_pad,
               uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt) {
@@ -401,7 +406,7 @@ __device__ __forceinline__ float sample_bound_finish(float x, float gref) {
 // a subtract, a second convert per pair of floats); queries are split once by k_mfma_prep.
 // Operand mapping: lane 32h + j supplies dims 16s + 8h .. +7 of query / row j of its 32-block for BOTH operands, so whatever
 // order the instruction walks k in, A and B agree on it.
-template <int METRIC>
+template <int METRIC, bool SETS = false>
 __global__ void __launch_bounds__(256, 1)
 k_bf16x3_filter(IndexView v, const uint4* __restrict__ Qbf, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq_pad,
                 uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt,
@@ -554,7 +559,7 @@ k_bf16x3_filter(IndexView v, const uint4* __restrict__ Qbf, const float* __restr
 // Here wave w fetches and splits only rows 32w .. 32w+31 of the group and publishes the two bfloat16 planes in LDS (8 KiB per
 // step, three stages, one barrier per step); all four read their B operands from there: half the L1 traffic, a quarter of the
 // vector instructions and of the row loads per wave.
-template <int METRIC, int TERMS, int RING>
+template <int METRIC, int TERMS, int RING, bool SETS = false>
 __global__ void __launch_bounds__(256, 1)
 k_bf16x3_filter_shared(IndexView v, const uint4* __restrict__ Qbf, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq_pad,
                        uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt) {
@@ -782,7 +787,7 @@ k_bf16x3_filter_shared(IndexView v, const uint4* __restrict__ Qbf, const float* 
 // behind them up (measured: the same time as the four-wave kernel).  Dimensions that are a multiple of 128, nq_pad of 256.
 // BF: the rows come from the index's bfloat16 copy (QV_FLAG_BF16_ROWS): a wave's 1-KiB request IS one 32-row B operand of one step,
 // no conversion; a round is then two steps (eight pieces, one per wave: piece w = step w>>2 of the round, block w&3).
-template <int METRIC, int RING, int AR, int SPB, bool BF, bool DEFER, bool SAMPLE = false>
+template <int METRIC, int RING, int AR, int SPB, bool BF, bool DEFER, bool SAMPLE = false, bool SETS = false>
 __global__ void __launch_bounds__(512, 1)
 k_bf16x1_filter_w8(IndexView v, const uint4* __restrict__ Qbf, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq_pad,
                    uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt,
@@ -1064,7 +1069,7 @@ __host__ __device__ static inline uint32_t w8x2_rounds(uint32_t dim4) { const ui
 // least); a chunk past the row's last one is requested from the row's first chunk instead (a valid address) and replaced by zeros,
 // and k_mfma_prep pads the query operands with zeros to the same count: +0 terms, the scores and their error bounds are unchanged.
 // The predicates are wave-uniform (scalar compares) and exist only in this instantiation.
-template <int METRIC, int RING, int AR, bool PAD = false>
+template <int METRIC, int RING, int AR, bool PAD = false, bool SETS = false>
 __global__ void __launch_bounds__(512, 1)
 k_bf16x1_filter_w8x2(IndexView v, const uint4* __restrict__ Qbf, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq_pad,
                      uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt) {
@@ -1252,7 +1257,7 @@ k_bf16x1_filter_w8x2(IndexView v, const uint4* __restrict__ Qbf, const float* __
 // IS the lane's B operand.  The pipelined form only: dimensions that are a multiple of 128 (16-dim steps in rounds of eight).
 // Two workgroups per CU (256 registers per lane: the lean rings leave room; the float32-row kernel at that occupancy spills into its
 // loop, 1.47 ms against 1.0): a second wave per SIMD covers the other's barriers — 0.86 -> 0.79 ms, 256 x 10M x 768 5.73 -> 5.09 ms.
-template <int METRIC>
+template <int METRIC, bool SETS = false>
 __global__ void __launch_bounds__(256, 2)
 k_bf16rows_filter(IndexView v, const uint4* __restrict__ Qbf, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq_pad,
                   uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt) {
@@ -1366,7 +1371,7 @@ k_bf16rows_filter(IndexView v, const uint4* __restrict__ Qbf, const float* __res
 // F32 (round 4): the same kernel on the float32 tiles of an index WITHOUT the copy — a lane's two 16-byte chunk requests are its B operand's
 // eight dimensions, converted right before use (4 v_cvt_pk_bf16_f32); no LDS for rows, no barrier: what 9-64 queries cost on the default
 // index was the per-wave three-term kernel (0.61-0.64 ms at 1M x 768).
-template <int METRIC, int NB, int R, bool F32 = false>
+template <int METRIC, int NB, int R, bool F32 = false, bool SETS = false>
 __global__ void __launch_bounds__(512, 1)
 k_bf16rows_filter_q64(IndexView v, const uint4* __restrict__ Qbf, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq_pad,
                       uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt) {
@@ -2601,7 +2606,7 @@ struct WsCarver {
 };
 struct BatchedLayout {
     float* Qt; float *cq, *mq, *eq;
-    uint32_t* cand; float* cscore; uint32_t *cnt, *ovf;
+    uint32_t* cand; float* cscore; uint32_t *cnt, *ovf, *sparse, *n_in;
     uint64_t *keys_hi, *keys_ex; float* lo_b; uint32_t* surv; double* qnorms; uint32_t* nsurv; void* sel_ws; uint32_t *tp_cnt, *tp_off;   // large k only
     uint32_t* srows; float *sdist, *sparts, *sscore;
     float* ubuf;                    // the bound U_q per query, until the check after the filter: sparts under a guessed bound, else sdist (an alias)
@@ -2622,9 +2627,11 @@ static BatchedLayout batched_layout(void* base, const IndexView& v, const ScanPl
     L.cand = w.take<uint32_t>(nq * ccap);                   // candidates: rows + fp32 scores
     L.cscore = w.take<float>(nq * ccap);
     w.align256();
-    w.take<uint32_t>(1);                                    // cnt[-1]: the capacity, for the filter kernels
+    w.take<uint32_t>(kCandHeadWords);                       // cnt[-4 .. -1]: the row sets' table and the capacity, for the filter kernels
     L.cnt = w.take<uint32_t>(nq);
     L.ovf = w.take<uint32_t>(nq);
+    L.sparse = w.take<uint32_t>(nq);                        // a filtered batch: the queries handed back as sparse, right behind the redo flags (launch_batched)
+    L.n_in = w.take<uint32_t>(nq);                          // ... and their in-set sample rows
     w.slack(256 - sizeof(uint32_t));                        // (slack kept from the hand-written version, which did not count the capacity word)
     if (r.large_k) {                                        // the selections' arrays
         w.align256();
@@ -2662,6 +2669,50 @@ size_t batched_workspace_bytes(const IndexView& v, const ScanPlan& p, uint32_t n
     return batched_layout(nullptr, v, p, r).total;
 }
 
+// A filtered batch (BatchedSets) needs every sample row's bound in L.sscore between the score kernel and a selection of its own: the
+// exact-scan sample has no such array, and the group minima mix rows inside and outside a set.  Up to kMaxFusedK results: the candidate
+// lists keep kMfmaCandCap slots, and the exact row-set scans that redo a handed-back query go no further.
+static bool batched_sets_route(const BatchedRoute& r) {
+    return r.k <= (uint32_t)kMaxFusedK && r.sample != SampleScores::exact_scan && (r.bound == SampleBound::sample_select || r.bound == SampleBound::histogram);
+}
+bool batched_sets_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus) {
+    BatchedRoute r;
+    return k >= 1 && k <= (uint32_t)kMaxFusedK && batched_supported(v, nq, k) && plan_batched(v, nq, k, cus, true, r) && batched_sets_route(r);
+}
+bool batched_sample_plan(const IndexView& v, uint32_t nq, uint32_t k, int cus, uint32_t* sample_rows, uint32_t* gstep, uint32_t* rank) {
+    BatchedRoute r;
+    if (nq == 0 || k == 0 || k > (uint32_t)kMaxBatchedK || !plan_batched(v, nq, k, cus, true, r) || r.sample == SampleScores::exact_scan) return false;
+    *sample_rows = r.sample_rows; *gstep = r.gstep; *rank = r.ks;
+    return true;
+}
+// Which filtered calls (or shared passes) of 9 or more queries take the batched path instead of ceil(nq / 8) or ceil(nq / 16) exact corpus
+// passes.  QV_FILTERED_BATCH (1 always, 2 never; read once) is the default of indexes whose setter was never called.  "Always": whenever
+// batched_supported holds for the piece, k <= kMaxFusedK, and at least kFilteredBatchMinQueries of its queries are not known sparse on the
+// host (a piece of known-sparse sets would only be handed back whole).  Automatic: the cells measured faster than the exact passes by
+// more than both arms' spread, never below kFilteredBatchAutoMinRows rows.
+// Measured (profiles/LAB_r15_filtered_batch.md; one call of 16 / 64 / 256 queries, 300k and 1M x 768, cosine and L2, k = 10 and 64, floor off;
+// us per call, exact passes / batched): 1M, 256 queries, k = 10: a set per query of every row 21189 / 1248, of 1 % of the rows 20817 / 1467,
+// where-filters of 10 % 24299 / 4419; 64 queries 5317 / 855, 5247 / 995, 6140 / 1666; 16 queries 1436 / 692, 1370 / 706, 1619 / 917; 300k
+// rows: 256 queries 7678 / 795, 16 queries 583 / 378 — every cell with random sets or predicates a win down to the smallest share
+// measured, 1 % (hence kFilteredBatchDefaultPpm).  The losses: ONE set of whole tiles named by every query, one tile in twenty or in a
+// hundred — 16 queries 365 / 635 and 195 / 608 at 1M, and with k = 64 the guessed bound fails on a sample that is in step with the
+// stripes (every query handed back: 5023 / 6033 at 256 queries) — because the exact pass skips the tiles no set of the pass selects.
+// The rule's inputs cannot tell such a piece from one of random sets (n_not_sparse counts rows, not tiles), 10M rows, 128 dimensions,
+// dot and L2SQ are unmeasured, and under the callers' front 256 where-filtered callers gain throughput at twice the p99: the automatic mode
+// takes no cell yet, and kFilteredBatchAutoMeasured is where the floors go once they are.
+constexpr bool kFilteredBatchAutoMeasured = false;
+static int filtered_batch_mode(int mode) { static const int env_mode = env_int("QV_FILTERED_BATCH", 0); return mode ? mode : env_mode; }
+bool filtered_batch_rule(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse) {
+    mode = filtered_batch_mode(mode);
+    if (mode == 2 || nq < kFilteredBatchMinQueries || n_not_sparse < kFilteredBatchMinQueries || k == 0 || k > (uint32_t)kMaxFusedK) return false;
+    if (rows == 0 || rows > 0xFFFFFFFFull || dim == 0) return false;
+    IndexView v{};
+    v.metric = metric; v.dim = dim; v.dim4 = (dim + 3) / 4; v.n_rows = (uint32_t)rows; v.n_tiles = (uint32_t)((rows + 63) / 64); v.filter = filter;
+    if (!batched_supported(v, nq, k)) return false;
+    if (mode == 1) return true;
+    return kFilteredBatchAutoMeasured && rows >= kFilteredBatchAutoMinRows;
+}
+
 // The runtime metric as a compile-time constant M for a generic lambda, over the metrics this path's exact kernels (k_sample_select,
 // k_sample_bound*, k_rescore_select, k_cand_*, k_tp_exact) are instantiated for; the filters' own set: with_filter_metric (qv_filter.h)
 template <typename F> static inline hipError_t with_exact_metric(int metric, F&& f) {
@@ -2674,7 +2725,11 @@ template <typename F> static inline hipError_t with_exact_metric(int metric, F&&
 }
 
 // 1. per-query upper bound U_q of the k-th distance from a sample: its scores, then their k-th smallest upper bound into L.ubuf
-static hipError_t batched_sample_bound(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, const float* d_queries, void* d_ws, hipStream_t s) {
+// sets: a filtered batch (batched_sets_route) — the bounds of sample rows outside a query's set become +inf between the score kernel and the
+// selection (launch_sets_sample_mask), so that U_q is the ks-th smallest upper bound over sample & live & set_q: a bound of the k-th
+// distance over live & set_q, as any subset's is
+static hipError_t batched_sample_bound(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, const float* d_queries, void* d_ws, hipStream_t s,
+                                       const RowSetRef* d_sets = nullptr) {
     const uint32_t nq = r.nq, nq_pad = r.nq_pad, srows = r.sample_rows;
     if (r.sample == SampleScores::exact_scan) {
         IndexView vs = v;
@@ -2682,7 +2737,7 @@ static hipError_t batched_sample_bound(const IndexView& v, const BatchedRoute& r
         vs.n_tiles = r.sample_tiles;
         return launch_flat_topk(vs, plan_scan(vs.n_tiles, r.cus), d_queries, nq, r.k, d_ws, L.srows, L.sdist, s);
     }
-    hipLaunchKernelGGL(k_mfma_prep, dim3(nq_pad), dim3(64), 0, s, d_queries, nq, nq_pad, v.dim, v.dim4, L.sdist, 1u, r.k, v.metric, L.Qt, L.cq, L.mq, L.eq, L.cnt, L.ovf, 1, 1, r.ccap, 0u);
+    hipLaunchKernelGGL(k_mfma_prep, dim3(nq_pad), dim3(64), 0, s, d_queries, nq, nq_pad, v.dim, v.dim4, L.sdist, 1u, r.k, v.metric, L.Qt, L.cq, L.mq, L.eq, L.cnt, L.ovf, 1, 1, r.ccap, 0u, nullptr, 0u, d_sets);
     const uint4* Qbf = reinterpret_cast<const uint4*>(L.Qt);
     SelState* sst = nullptr; uint32_t* shist = nullptr;
     if (r.bound == SampleBound::histogram) { const hipError_t e = select_prepare(L.sel_ws, nq, r.ks, &sst, &shist, s); if (e != hipSuccess) return e; }   // (the histogram kernels' state)
@@ -2694,6 +2749,10 @@ static hipError_t batched_sample_bound(const IndexView& v, const BatchedRoute& r
             hipLaunchKernelGGL(k_bf16x3_filter<M>, dim3(r.sample_grid), dim3(256), 0, s, v, Qbf, L.cq, L.mq, nq_pad, L.cand, L.cscore, L.cnt, L.sscore, srows, r.gstep);
         return hipSuccess;
     });
+    if (d_sets) {
+        const hipError_t e = launch_sets_sample_mask(v, d_sets, nq, L.sscore, srows, r.gstep, L.n_in, s);
+        if (e != hipSuccess) return e;
+    }
     const float gref = (float)filter_gamma(v.dim, 0) * 1.000001f;
     return with_exact_metric(v.metric, [&](auto m) {
         constexpr int M = decltype(m)::value;
@@ -2719,15 +2778,17 @@ static hipError_t batched_sample_bound(const IndexView& v, const BatchedRoute& r
 }
 
 // 2. query re-layout + filter constants from the bound
-static void batched_prep(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, const float* d_queries, hipStream_t s) {
+static void batched_prep(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, const float* d_queries, hipStream_t s, const RowSetRef* d_sets = nullptr) {
     hipLaunchKernelGGL(k_mfma_prep, dim3(r.nq_pad), dim3(64), 0, s, d_queries, r.nq, r.nq_pad, v.dim, v.dim4, r.bparts > 1 ? L.sparts : L.ubuf, r.bparts, r.ks, v.metric, L.Qt, L.cq, L.mq, L.eq, L.cnt, L.ovf,
-                       r.gmode, r.prep_what, r.ccap, r.prep_steps, r.bound == SampleBound::prep_group_min ? L.sscore : nullptr, r.sgroups);
+                       r.gmode, r.prep_what, r.ccap, r.prep_steps, r.bound == SampleBound::prep_group_min ? L.sscore : nullptr, r.sgroups, d_sets);
 }
 
 // 3. MFMA filter
-static hipError_t batched_filter(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, hipStream_t s) {
+// sets: a filtered batch — the kernels' flush variant that tests every record against its query's set (CandOutT<true>, qv_filter.h); an unfiltered
+// batch launches exactly the instantiations it launched before
+static hipError_t batched_filter(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, hipStream_t s, bool sets = false) {
     const uint4* Qbf = reinterpret_cast<const uint4*>(L.Qt);
-    if (r.filter == MainFilter::qreg) return launch_qreg_filter(v, Qbf, L.cq, L.mq, r.nq_pad, L.cand, L.cscore, L.cnt, r.bfrows, r.cus, s);
+    if (r.filter == MainFilter::qreg) return sets ? hipErrorNotSupported : launch_qreg_filter(v, Qbf, L.cq, L.mq, r.nq_pad, L.cand, L.cscore, L.cnt, r.bfrows, r.cus, s);
     // every filter kernel takes the same arguments (the operands as float32 or bfloat16 planes), some a sample's after them
     auto go = [&](auto kernel, auto* Q, uint32_t block, auto... sample_args) {
         const hipError_t e = set_lds(kernel, r.filter_lds); if (e != hipSuccess) return e;
@@ -2736,6 +2797,17 @@ static hipError_t batched_filter(const IndexView& v, const BatchedRoute& r, cons
     };
     return with_filter_metric(v.metric, [&](auto m) {
         constexpr int M = decltype(m)::value;
+        if (sets) switch (r.filter) {
+            case MainFilter::mfma_f32:      return go(k_mfma_filter<M, 4, true>, L.Qt, 256);
+            case MainFilter::bf16x3:        return go(k_bf16x3_filter<M, true>, Qbf, 256, (float*)nullptr, 0u, 1u);
+            case MainFilter::bf16x3_shared: return go(k_bf16x3_filter_shared<M, 3, 8, true>, Qbf, 256);
+            case MainFilter::bf16rows:      return go(k_bf16rows_filter<M, true>, Qbf, 256);
+            case MainFilter::w8x2:          return go(k_bf16x1_filter_w8x2<M, 4, 4, false, true>, Qbf, 512);
+            case MainFilter::w8x2_padded:   return go(k_bf16x1_filter_w8x2<M, 4, 4, true, true>, Qbf, 512);
+            case MainFilter::q64_plane:     return go(k_bf16rows_filter_q64<M, 4, 4, false, true>, Qbf, 512);
+            case MainFilter::q64_f32_rows:  return go(k_bf16rows_filter_q64<M, 2, 4, true, true>, Qbf, 512);
+            default: return hipErrorNotSupported;            // (the measurement build's shapes have no such variant)
+        }
         switch (r.filter) {
             case MainFilter::mfma_f32:      return go(k_mfma_filter<M, 4>, L.Qt, 256);
             case MainFilter::bf16x3:        return go(k_bf16x3_filter<M>, Qbf, 256, (float*)nullptr, 0u, 1u);
@@ -2824,16 +2896,33 @@ static hipError_t batched_exact(const IndexView& v, const BatchedRoute& r, const
 
 hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws,
                           uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
-                          hipEvent_t ev0, hipEvent_t ev1) {
+                          hipEvent_t ev0, hipEvent_t ev1, const BatchedSets* sets) {
     BatchedRoute r;
     if (!plan_batched(v, nq, k, cus, (reinterpret_cast<uintptr_t>(d_queries) & 15u) == 0, r)) return hipErrorNotSupported;
+    const RowSetRef* d_sets = sets ? sets->d_sets : nullptr;
+    if (d_sets && !batched_sets_route(r)) return hipErrorNotSupported;   // (a missing route is an error, never an unfiltered answer)
+    if (d_sets && r.filter == MainFilter::qreg) {
+        // the register-resident kernel has no flush variant (its instantiations are many: three operand splits, both row forms): a filtered
+        // batch of whole workgroups takes what plan_batched chooses where that kernel does not apply
+        const uint32_t nqb64 = r.nq_pad / 64;
+        if (r.bfrows) { r.filter = MainFilter::bf16rows; r.filter_grid = grid_multiple(2 * (uint32_t)cus, nqb64 / 4); }
+        else r.filter = MainFilter::w8x2;
+    }
     const BatchedLayout L = batched_layout(d_ws, v, p, r);
     if (L.end > L.total) return hipErrorInvalidValue;       // (cannot happen: see batched_layout)
-    hipError_t e = batched_sample_bound(v, r, L, d_queries, d_ws, s);
+    if (d_sets && trace_filtered())
+        fprintf(stderr, "qv: filtered batch = k_sets_sample_mask + k_sets_sparse around the filter, nq %u k %u sample %u rows step %u rank %u floor %u ppm\n", nq, k, r.sample_rows, r.gstep, r.ks, sets->sparse_ppm);
+    hipError_t e = batched_sample_bound(v, r, L, d_queries, d_ws, s, d_sets);
     if (e != hipSuccess) return e;
-    batched_prep(v, r, L, d_queries, s);
+    batched_prep(v, r, L, d_queries, s, d_sets);
+    if (d_sets) {
+        // sparse sets, decided per query on the device: the padded queries' constants (nothing passes) and both flags — behind k_mfma_prep,
+        // which has just written the constants and cleared the redo flags
+        e = launch_sets_sparse(nq, r.nq_pad, L.n_in, r.sample_rows, sets->sparse_ppm, L.cq, L.mq, L.ovf, L.sparse, s);
+        if (e != hipSuccess) return e;
+    }
     if (ev0) (void)hipEventRecord(ev0, s);
-    e = batched_filter(v, r, L, s);
+    e = batched_filter(v, r, L, s, d_sets != nullptr);
     if (e != hipSuccess) return e;
     if (ev1) (void)hipEventRecord(ev1, s);
     e = batched_exact(v, r, L, d_queries, d_rows_out, d_dist_out, s);

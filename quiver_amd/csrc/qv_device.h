@@ -329,7 +329,29 @@ bool   batched_supported(const IndexView& v, uint32_t nq, uint32_t k);
 size_t batched_workspace_bytes(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k);
 hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws,
                           uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
-                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const struct BatchedSets* sets = nullptr);
+// A filtered batch, k <= kMaxFusedK: query q over alive & d_sets[q] (a DEVICE array of nq sets; null bits = every row).  The sample's bound is
+// taken over the set, the filter's flush drops rows outside it, and a query whose set holds fewer than sparse_ppm millionths of the sample's
+// rows is handed back without candidates (0: never).  With sets, *d_overflow_out -> [2][nq]: the redo flags, then 1 = handed back as sparse
+// (those are flagged in both).  Same workspace (batched_workspace_bytes).
+struct BatchedSets { const RowSetRef* d_sets; uint32_t sparse_ppm; };
+// whether launch_batched takes sets for this shape: batched_supported, k <= kMaxFusedK, and a route whose sample scores come from a filter
+// kernel with every row's bound selected outside k_mfma_prep (the exact-scan sample of QV_MFMA_SAMPLE_GEMM is declined)
+bool batched_sets_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus);
+// what plan_batched chose for the sample: its rows, every gstep-th 128-row group of the corpus, and the rank the bound is taken at
+bool batched_sample_plan(const IndexView& v, uint32_t nq, uint32_t k, int cus, uint32_t* sample_rows, uint32_t* gstep, uint32_t* rank);
+// The dispatch's rule for a filtered call or shared pass (qv_batched_applies_filtered; mode: QV_FILTERED_BATCH_*, 0 = QV_FILTERED_BATCH of the
+// environment, else automatic): n_not_sparse = the piece's queries whose set the HOST does not know to be below the sparse floor.
+bool filtered_batch_rule(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse);
+constexpr uint32_t kFilteredBatchMinQueries = 9;
+constexpr uint32_t kFilteredBatchDefaultPpm = 10000;      // the sparse floor where the index sets none: a hundredth of the rows
+constexpr uint32_t kFilteredBatchAutoMinRows = 300000;    // automatic mode takes nothing below the smallest measured shape
+inline uint32_t filtered_batch_ppm(uint32_t ppm) { return ppm == 0xFFFFFFFFu ? kFilteredBatchDefaultPpm : ppm; }
+// qv_batched_sets.hip — the two launches a filtered batch adds around the sample's selection and behind k_mfma_prep
+hipError_t launch_sets_sample_mask(const IndexView& v, const RowSetRef* d_sets, uint32_t nq, float* d_bounds, uint32_t sample_rows, uint32_t gstep,
+                                   uint32_t* d_n_in, hipStream_t s);
+hipError_t launch_sets_sparse(uint32_t nq, uint32_t nq_pad, const uint32_t* d_n_in, uint32_t sample_rows, uint32_t sparse_ppm, float* d_cq, float* d_mq,
+                              uint32_t* d_ovf, uint32_t* d_sparse, hipStream_t s);
 
 // the one-term bfloat16 filter with the query operands in registers (qv_qreg.hip): same arguments and candidates as the eight-wave kernels
 bool qreg_filter_applies(const IndexView& v, uint32_t nq_pad, bool bfrows);

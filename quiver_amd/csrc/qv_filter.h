@@ -123,24 +123,46 @@ struct CandQueue { uint32_t* rec; uint32_t cap; };                    // this WA
 // cap: slots per query.  kMfmaCandCap for k <= 64; a batch asking for more per query (k up to kMaxBatchedK) gets batched_cand_cap(k).
 // The filter kernels read it from the word in front of the counters (cand_cnt[-1], written by k_mfma_prep), so that none of their
 // signatures changes with it.
+//
+// A filtered batch (a row set per query: qv_batched_sets.hip) travels the same way: kCandHeadWords words sit in front of the counters,
+// [-4, -3] the address of the batch's RowSetRef table (one entry per query; null: an unfiltered batch), [-2] unused, [-1] the cap — all
+// written by k_mfma_prep.  The set test is HERE, where a record leaves the wave's queue for its query's list: a row outside the query's
+// set is dropped before the atomic, so the lists, the counters, the overflow test and everything behind them (k_rescore_select, the
+// large-k narrowing, the redo flags) see candidates of live & set_q only.  The per-score tests do not change.  The test is compiled
+// into the flush only for a filtered batch (CandOutT<true> below), so an unfiltered batch runs the kernels it always ran.
+constexpr int kCandHeadWords = 4;
+__device__ __forceinline__ const RowSetRef* cand_sets(const uint32_t* cand_cnt) { return *reinterpret_cast<const RowSetRef* const*>(cand_cnt - kCandHeadWords); }
+__device__ __forceinline__ bool rowset_has(const RowSetRef& r, uint32_t row) {       // (RowSetRef: null bits = every row, words past the set's length are zero)
+    if (r.bits == nullptr) return true;
+    return (row >> 6) < r.words && ((r.bits[row >> 6] >> (row & 63u)) & 1ull) != 0;
+}
 __device__ __forceinline__ void cand_append_global(uint32_t q, uint32_t row, float score, uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score,
-                                                   uint32_t* __restrict__ cand_cnt, uint32_t cap) {
+                                                   uint32_t* __restrict__ cand_cnt, uint32_t cap, const RowSetRef* __restrict__ sets = nullptr) {
+    if (sets != nullptr && !rowset_has(sets[q], row)) return;
     const uint32_t slot = atomicAdd(&cand_cnt[q], 1u);
     if (slot < cap) {
         cand_rows[(size_t)q * cap + slot] = row;
         cand_score[(size_t)q * cap + slot] = score;
     }
 }
-struct CandOut { uint32_t* rows; float* score; uint32_t* cnt; uint32_t cap; };      // the per-query candidate lists in global memory
+// SETS: the flush variant, chosen by the launcher per batch (a template parameter of every filter kernel, false for an unfiltered batch): with the
+// test inside the one shared flush the unfiltered batch paid for it — eight scalar registers in kernels at their limit, k_bf16rows_filter_q64
+// 0.267 -> 0.318 ms at 64 x 1M x 768, k_bf16rows_filter 0.385 -> 0.402 — so an unfiltered batch runs the code it ran before
+template <bool SETS> struct CandOutT { uint32_t* rows; float* score; uint32_t* cnt; uint32_t cap; };      // the per-query candidate lists in global memory
+using CandOut = CandOutT<false>;
 // every lane of the wave calls this: the wave's n queued records go to the per-query lists
-__device__ __forceinline__ void cand_flush(const CandQueue& cqu, uint32_t n, const CandOut& out) {
+template <bool SETS>
+__device__ __forceinline__ void cand_flush(const CandQueue& cqu, uint32_t n, const CandOutT<SETS>& out) {
     __threadfence_block();
+    const RowSetRef* sets = nullptr;
+    if constexpr (SETS) sets = cand_sets(out.cnt);
     for (uint32_t i = lane_id(); i < n; i += 64)
-        cand_append_global(cqu.rec[kCandQueueWords * i], cqu.rec[kCandQueueWords * i + 1], __uint_as_float(cqu.rec[kCandQueueWords * i + 2]), out.rows, out.score, out.cnt, out.cap);
+        cand_append_global(cqu.rec[kCandQueueWords * i], cqu.rec[kCandQueueWords * i + 1], __uint_as_float(cqu.rec[kCandQueueWords * i + 2]), out.rows, out.score, out.cnt, out.cap, sets);
     __threadfence_block();
 }
 // called by ALL lanes of a wave (converged) with the wave's mask m (non-zero) of the lanes that append their record; n = the queue's fill
-__device__ __forceinline__ void cand_push(const CandQueue& cqu, uint32_t& n, uint64_t m, uint32_t q, uint32_t row, float score, const CandOut& out) {
+template <bool SETS>
+__device__ __forceinline__ void cand_push(const CandQueue& cqu, uint32_t& n, uint64_t m, uint32_t q, uint32_t row, float score, const CandOutT<SETS>& out) {
     const uint32_t lane = lane_id();
     const uint32_t cnt = (uint32_t)__builtin_popcountll(m);
     if (__builtin_expect(n + cnt > cqu.cap, 0)) { cand_flush(cqu, n, out); n = 0; }
@@ -157,7 +179,7 @@ __device__ __forceinline__ void cand_push(const CandQueue& cqu, uint32_t& n, uin
     __shared__ uint32_t name##_rec[(WAVES) * (CAP) * kCandQueueWords];        \
     const CandQueue name{name##_rec + (threadIdx.x >> 6) * (CAP) * kCandQueueWords, (CAP)}; \
     uint32_t name##_n = 0;                                                    \
-    const CandOut name##_out{cand_rows, cand_score, cand_cnt, cand_cnt[-1]}
+    const CandOutT<SETS> name##_out{cand_rows, cand_score, cand_cnt, cand_cnt[-1]}
 
 // The filter test on a wave's 64 x 128 scores: acc[i][j][r] = S~[query 64*qb64 + 32*i + (r&3)+8*(r>>2)+4*half][row 64*(t0|t1) + 32*(j&1) + l31];
 // a row that may be in some query's top-k goes to that query's candidate list with its score.
@@ -208,9 +230,9 @@ constexpr uint32_t kEpiEntryWords = 20;                               // 16 scor
 struct EpiDump { uint32_t* area; uint32_t cap; };                     // this WAVE's dump area in LDS, cap entries of kEpiEntryWords words (16-byte aligned)
 
 // the dense pass: entries [0, n) of the wave's dump area, 16 (entry, score) pairs per entry, 64 pairs per round
-template <int METRIC>
+template <int METRIC, bool SETS>
 __device__ __forceinline__ void epi_dense_pass(const EpiDump& du, uint32_t n, const float* sc, const float* sm, uint32_t qbase, uint32_t qglobal,
-                                               const CandQueue& cqu, uint32_t& cqn, const CandOut& out) {
+                                               const CandQueue& cqu, uint32_t& cqn, const CandOutT<SETS>& out) {
     __threadfence_block();                                            // the dump's LDS writes, before other lanes of the wave read them
     const uint32_t lane = lane_id();
     for (uint32_t p = lane; p < 16 * n + 63; p += 64) {              // the loop count is wave-uniform (cand_push is a wave operation)
@@ -237,11 +259,11 @@ __device__ __forceinline__ void epi_dense_pass(const EpiDump& du, uint32_t n, co
 // The epilogue of one row group in pieces — row block J (level 1 + dump), then the dense pass — so that a kernel can run them one
 // at a time between the steps of the NEXT group's K loop (k_bf16x1_filter_w8), where they cost memory-wait time instead of their own.
 // n: entries in the wave's dump area (wave-uniform), carried from block to block.
-template <int METRIC, int NI, int NJ, int J>
+template <int METRIC, int NI, int NJ, int J, bool SETS>
 __device__ __forceinline__ void filter_epilogue_block(const f16v (&acc)[NI][NJ], uint32_t t0, uint32_t t1, const float* sc, const float* sm,
                                                       uint32_t qbase, uint32_t half, uint32_t l31, uint32_t qglobal, float tiny_rn, const EpiConsts& ec,
                                                       const double (&rnd)[NJ], const float (&rho)[NJ], const uint64_t (&alv)[NJ / 2], const CandQueue& cqu, uint32_t& cqn,
-                                                      const CandOut& out, const EpiDump& du, uint32_t& n) {
+                                                      const CandOutT<SETS>& out, const EpiDump& du, uint32_t& n) {
     constexpr int j = J;
     const uint32_t t = j < 2 ? t0 : t1;
     if (j >= 2 && t1 == t0) return;
@@ -295,10 +317,10 @@ __device__ __forceinline__ uint64_t epi_level1(const f16v& a, float cmin, float 
     return __ballot((!(mx < thr_lo) || unsure) && live);
 }
 // the dump of one row block whose level-1 mask pm is not empty (wave-uniform call)
-template <int METRIC>
+template <int METRIC, bool SETS>
 __device__ __forceinline__ void epi_dump(const f16v& a, uint64_t pm, uint32_t row, float rn, float rho, uint32_t i, uint32_t half, bool unsure,
                                          const float* sc, const float* sm, uint32_t qbase, uint32_t qglobal, const CandQueue& cqu, uint32_t& cqn,
-                                         const CandOut& out, const EpiDump& du, uint32_t& n) {
+                                         const CandOutT<SETS>& out, const EpiDump& du, uint32_t& n) {
     const bool pre = (pm >> lane_id()) & 1ull;
     const uint32_t cnt = (uint32_t)__builtin_popcountll(pm), rank = (uint32_t)__builtin_popcountll(pm & ((1ull << lane_id()) - 1ull));
     for (uint32_t done = 0; done < cnt;) {                  // one round, unless the dump area fills up (wave-uniform loop)
@@ -314,9 +336,9 @@ __device__ __forceinline__ void epi_dump(const f16v& a, uint64_t pm, uint32_t ro
         n += now; done += now;
     }
 }
-template <int METRIC>
+template <int METRIC, bool SETS>
 __device__ __forceinline__ void filter_epilogue_finish(const float* sc, const float* sm, uint32_t qbase, uint32_t qglobal, const CandQueue& cqu, uint32_t& cqn,
-                                                       const CandOut& out, const EpiDump& du, uint32_t& n) {
+                                                       const CandOutT<SETS>& out, const EpiDump& du, uint32_t& n) {
 #if defined(QV_DBG_EPI) && QV_DBG_EPI == 3                               // measurement build: level 1 + dump, no dense pass
     if (n == 0xFFFFFFFFu) out.cnt[0] = 1;
     n = 0;
@@ -325,10 +347,10 @@ __device__ __forceinline__ void filter_epilogue_finish(const float* sc, const fl
     if (n) epi_dense_pass<METRIC>(du, n, sc, sm, qbase, qglobal, cqu, cqn, out);
     n = 0;
 }
-template <int METRIC, int NI, int NJ>
+template <int METRIC, int NI, int NJ, bool SETS>
 __device__ __forceinline__ void filter_epilogue(const IndexView& v, const f16v (&acc)[NI][NJ], uint32_t t0, uint32_t t1, const float* sc, const float* sm,
                                                 uint32_t qbase, uint32_t half, uint32_t l31, uint32_t qglobal, float tiny_rn, const EpiConsts& ec,
-                                                const double (&rnd)[NJ], const float (&rho)[NJ], const uint64_t (&alv)[NJ / 2], const CandQueue& cqu, uint32_t& cqn, const CandOut& out,
+                                                const double (&rnd)[NJ], const float (&rho)[NJ], const uint64_t (&alv)[NJ / 2], const CandQueue& cqu, uint32_t& cqn, const CandOutT<SETS>& out,
                                                 const EpiDump& du) {
         uint32_t* const cand_cnt = out.cnt; (void)cand_cnt; (void)v;
 #if defined(QV_DBG_EPI) && QV_DBG_EPI == 1                               // measurement build: no epilogue (the accumulators stay live through one compare)

@@ -110,6 +110,7 @@ k_qreg_filter(IndexView v, const uint4* __restrict__ Qbf, const float* __restric
     // residuals (64 floats), the alive word — one 256-byte request per wave, issued with the tile's first stage.
     constexpr int kRcTiles = 8;
     __shared__ __align__(16) uint32_t s_rc[kRcTiles][256];
+    constexpr bool SETS = false;                                     // (the flush variant: a filtered batch takes the eight-wave kernels instead, launch_batched)
     QV_CAND_QUEUE(cqu, 4, 128);                                      // 6 KiB
     QV_EPI_DUMP(du, 4, 16);                                          // 5 KiB
     const uint32_t lane = lane_id();

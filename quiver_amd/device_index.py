@@ -448,6 +448,31 @@ class DeviceIndex:
         """the batched path's filter kernel: "auto", "fp32" (fp32 MFMA chain), "bf16x3", "bf16x1", or "off" — exact scans only (qv_index_set_filter)"""
         check(lib().qv_index_set_filter(self._h, self.FILTERS.get(filter, filter)))
 
+    FILTERED_BATCH = {"auto": 0, "always": 1, "never": 2}
+
+    def set_filtered_batch(self, mode, sparse_ppm=None):
+        """whether a call or shared pass of 9 or more FILTERED queries (search_rowsets, search_where; k <= 64) takes the batched path with a
+        set per query: "auto" (the shapes measured faster), "always" (whenever the batched path takes the shape), "never" (the exact
+        passes).  sparse_ppm: the share of the rows, in millionths, below which a query's set is handed back to the exact scan; None =
+        the default, 0 = never (qv_index_set_filtered_batch)"""
+        ppm = 0xFFFFFFFF if sparse_ppm is None else int(sparse_ppm)
+        check(lib().qv_index_set_filtered_batch(self._h, self.FILTERED_BATCH.get(mode, mode), ppm))
+
+    def filtered_batch_stats(self) -> dict:
+        """queries that took the filtered batched path, queries it handed back (overflow, no bound, a failed guess), queries it handed back
+        as sparse, batches (qv_index_filtered_batch_stats)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_index_filtered_batch_stats(self._h, out))
+        return {"queries": int(out[0]), "hand_backs": int(out[1]), "sparse": int(out[2]), "batches": int(out[3])}
+
+    def batched_sample_plan(self, nq: int, k: int) -> dict:
+        """the sample the batched path's plan chose for nq queries, k results: "rows" sample rows, every "group_step"-th 128-row group of
+        the corpus — sample position i is corpus row (i // 128) * group_step * 128 + i % 128 — and the "rank" its bound is taken at
+        (qv_batched_sample_plan)"""
+        sr, gs, rk = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib().qv_batched_sample_plan(self._h, nq, k, C.byref(sr), C.byref(gs), C.byref(rk)))
+        return {"rows": int(sr.value), "group_step": int(gs.value), "rank": int(rk.value)}
+
     def profile(self, enable: bool):
         check(lib().qv_index_profile(self._h, 1 if enable else 0))
 
