@@ -182,6 +182,26 @@ func (h *Graph) Delete(node uint32) error {
 	return nil
 }
 
+// Remove is hnsw.HNSW.Delete (hnsw.go:741-842) for the listed nodes, as if one by one in list order, applied to the device
+// graph in place (qv_graph_remove): every node each of them lists loses its links to it, the node becomes a tombstone, and
+// the entry point moves the way the reference moves it (:796-827).  Nothing is re-uploaded; the rows leave the vector
+// storage too.  A node that is already deleted, or listed twice, is skipped; a node beyond the graph is an error and changes nothing.
+func (h *Graph) Remove(nodes []uint32) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	h.mu.Lock()
+	defer h.mu.Unlock()
+	if len(nodes) == 0 {
+		return nil
+	}
+	if C.qv_graph_remove(h.g, u32p(nodes), C.uint32_t(len(nodes))) != C.QV_OK {
+		return lastErr()
+	}
+	if C.qv_index_remove(h.idx, u32p(nodes), C.uint32_t(len(nodes))) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
 // Adjacency is the flat form of hnsw.Node.Level / Connections (hnsw.go:44-56) that qv_graph_create takes and qv_graph_export
 // returns: Levels[i] = -1 for a nil node; level 0 as degree + MaxM0 links per node; each (node, level >= 1) as a block of
 // 1 + M words (degree, links), node i's first block at UpOff[i].

@@ -738,6 +738,29 @@ void qv_graph_destroy(qv_graph* g);
 uint32_t qv_graph_batch_size(uint32_t nodes_linked, uint32_t batch_max, uint32_t ramp_div);
 int qv_graph_create_empty(qv_graph** out, qv_index* idx, uint32_t capacity_nodes, uint32_t m, uint32_t max_m0, uint32_t ef_construction);
 int qv_graph_insert(qv_graph* g, uint32_t first_row, uint32_t n, const int8_t* levels, uint32_t batch_max, uint32_t ramp_div);
+/* hnsw.HNSW.Delete (hnsw.go:741-842) for the listed nodes, AS IF ONE BY ONE IN LIST ORDER, on the device, in place.  The graph
+ * must be one that qv_graph_insert extends (qv_graph_create_empty / qv_graph_build / qv_graph_make_buildable); any other
+ * answers QV_ERR_UNSUPPORTED like qv_graph_insert.
+ *   lists      for every listed node d that is live at its turn, every level l <= level(d) and every x in conn_d[l] that is live
+ *              at that moment (d itself included: a device-built node of level >= 1 links to itself below its connected level),
+ *              every occurrence of d leaves conn_x[l]; the rest keeps its order, and the per-link distances the next prune ranks
+ *              by move with the links.  A link to d from a node that d does not list STAYS (the reference leaves it; the
+ *              traversals skip dead nodes).
+ *   tombstone  level[d] = -1; the node's row in the index stays the caller's to remove (qv_index_remove)
+ *   entry      changes only when the entry point is deleted (:796-827): the only node -> entry 0, level -1; else the first
+ *              connection of d's highest non-empty level whose node is live, with that level (its lower levels next, while
+ *              the first connection is dead); else the first live node other than d, with that node's level; else it stays.
+ *              A replacement listed later is replaced again at its turn.  qv_graph_info reports the reference's EntryPoint /
+ *              CurrentLevel; while that names a dead node the traversals and qv_graph_insert start from the first live node
+ *              (:355-363, :621-629), and a graph without a live node answers every query with count 0.
+ *   arguments  a node >= n_nodes: QV_ERR_OUT_OF_RANGE, nothing changed; a node already dead or listed twice: skipped; n == 0: QV_OK
+ * Synchronous; needs the same external exclusion as qv_graph_insert.  Traversals of a graph with tombstones test node levels on
+ * every hop (the level-0 fast paths are for graphs without). */
+int qv_graph_remove(qv_graph* g, const uint32_t* nodes, uint32_t n);
+/* The adjacency list of (nodes[i], levels[i]) for each i — one gather kernel, one download — so that a host mirror follows a
+ * small edit without qv_graph_export's copy of the whole graph.  deg_out [n]; links_out [n][max(max_m0, max_m)], zero beyond
+ * the degree.  A dead node, or a level the node does not have, answers degree 0; a node >= n_nodes QV_ERR_OUT_OF_RANGE. */
+int qv_graph_export_lists(qv_graph* g, const uint32_t* nodes, const int* levels, uint32_t n, uint32_t* deg_out, uint32_t* links_out);
 /* A graph uploaded with qv_graph_create (built on the host) carries no per-link distances, which the device-side
  * construction works on: this scores every existing link once (one wavefront per adjacency list, the traversal's
  * arithmetic: computeDistance(node.Vector, conn.Vector), hnsw.go:438), after which qv_graph_insert can extend the graph.

@@ -9,6 +9,13 @@
 #include <cstring>
 #include <chrono>
 
+// The in-place edits of a device graph are referred to weakly: a libqv (or a stand-in for it) without them leaves the addresses
+// null, and Delete / Insert then take the path they took before these entry points existed.
+extern "C" {
+int qv_graph_remove(qv_graph* g, const uint32_t* nodes, uint32_t n) __attribute__((weak));
+int qv_graph_export_lists(qv_graph* g, const uint32_t* nodes, const int* levels, uint32_t n, uint32_t* deg_out, uint32_t* links_out) __attribute__((weak));
+}
+
 namespace quiver {
 
 namespace {
@@ -434,7 +441,6 @@ Error HNSW::insertLocked(const std::string& id, const float* v, uint32_t len) {
     if (by_id_.count(id)) return fmt("vector with ID %s already exists", id.c_str());   // :269-272
     Error ei = ensureIndex(len);
     if (!ei.empty()) return ei;
-    dg_dirty_ = true; bg_synced_ = false;                              // the host graph moves on without the device graph's link distances
     int level = RandomLevel();                                         // :275
     int oldLevel = cur_level_;                                         // :276
     uint32_t row = 0;
@@ -442,10 +448,15 @@ Error HNSW::insertLocked(const std::string& id, const float* v, uint32_t len) {
     uint32_t idx = (uint32_t)nodes_.size();
     if (row != idx) return "internal: device row and node index diverged";
     nodes_.emplace_back();
-    Node& nd = nodes_.back();
-    nd.id = id; nd.vec.assign(v, v + len); nd.level = level; nd.alive = true;
-    nd.conn.assign((size_t)level + 1, {});                             // :287-298
+    {
+        Node& nd = nodes_.back();
+        nd.id = id; nd.vec.assign(v, v + len); nd.level = level; nd.alive = true;
+        nd.conn.assign((size_t)level + 1, {});                         // :287-298
+    }
     by_id_[id] = idx; size_++;                                         // :301-303
+    // a graph whose device copy is current is extended there, as a batch of one (exactly Insert), and the lists that changed come back
+    if (nodes_.size() > 1 && deviceEditable(idx) && connectOnDevice(idx, level, oldLevel)) { device_inserts_++; edited_in_place_ = true; return ""; }
+    dg_dirty_ = true; bg_synced_ = false;                              // the host graph moves on without the device graph's link distances
     if (nodes_.size() == 1) { entry_ = 0; cur_level_ = level; return ""; }   // :306-311
     Error e = connectNode(idx, v, level, oldLevel);                    // :315
     if (!e.empty()) {                                                  // :316-322 rollback keeps the slot
@@ -455,6 +466,54 @@ Error HNSW::insertLocked(const std::string& id, const float* v, uint32_t len) {
     }
     if (level > oldLevel && level > cur_level_) { entry_ = idx; cur_level_ = level; }   // :325-332
     return "";
+}
+
+// The device graph can be edited in place: it is the current copy of nodes_ (built or extended on the device, so it carries the link
+// distances), the configuration is one the device build takes, the library has the entry points, and the graph names the entry
+// point this side does (a graph uploaded while EntryPoint named a deleted node carries the first live node instead).
+bool HNSW::deviceEditable(uint32_t device_nodes) const {
+    if (!qv_graph_remove || !qv_graph_export_lists) return false;
+    if (!(bg_synced_ && bg_ && dg_ == bg_ && !dg_dirty_.load())) return false;
+    if (!(M_ <= 64 && maxM0_ <= 64 && efC_ <= 512 && maxLevel_ <= 64)) return false;
+    uint32_t n = 0, ep = 0; int lvl = -1;
+    if (qv_graph_info(bg_, &n, nullptr, nullptr, nullptr, &ep, &lvl) != QV_OK) return false;
+    return n == device_nodes && ep == entry_ && lvl == cur_level_;
+}
+
+// connectNode (hnsw.go:337-468) and the entry-point update (:325-332) of the node just appended, as a device batch of one.  What
+// changed comes back list by list: the node's own lists, and those of its forward neighbours at the connected level (the back-links
+// and their prune, :413-460).  false: nothing of the host graph was changed and the device copy is to be marked stale.
+bool HNSW::connectOnDevice(uint32_t nodeIdx, int level, int graphLevel) {
+    const int8_t lv = (int8_t)level;
+    if (qv_graph_insert(bg_, nodeIdx, 1, &lv, 1, 0) != QV_OK) {        // the device graph may be half extended: the next batch uploads a new one
+        if (dg_ == bg_) dg_ = nullptr;
+        qv_graph_destroy(bg_); bg_ = nullptr;
+        return false;
+    }
+    const uint32_t stride = (uint32_t)std::max(maxM0_, M_);
+    std::vector<uint32_t> nn((size_t)level + 1, nodeIdx), deg((size_t)level + 1), links(((size_t)level + 1) * stride);
+    std::vector<int> ll((size_t)level + 1);
+    for (int l = 0; l <= level; l++) ll[(size_t)l] = l;
+    if (qv_graph_export_lists(bg_, nn.data(), ll.data(), (uint32_t)level + 1, deg.data(), links.data()) != QV_OK) return false;
+    const int c = std::min(level, graphLevel);                         // :383
+    std::vector<uint32_t> nbs, ndeg, nlinks;
+    if (c >= 0) {
+        for (uint32_t j = 0; j < deg[(size_t)c]; j++) {
+            const uint32_t nb = links[(size_t)c * stride + j];
+            if (nb != nodeIdx && ok(nb) && c <= nodes_[nb].level && std::find(nbs.begin(), nbs.end(), nb) == nbs.end()) nbs.push_back(nb);
+        }
+        if (!nbs.empty()) {
+            std::vector<int> nl(nbs.size(), c);
+            ndeg.resize(nbs.size()); nlinks.resize(nbs.size() * stride);
+            if (qv_graph_export_lists(bg_, nbs.data(), nl.data(), (uint32_t)nbs.size(), ndeg.data(), nlinks.data()) != QV_OK) return false;
+        }
+    }
+    uint32_t ep = 0; int lvl = -1;
+    if (qv_graph_info(bg_, nullptr, nullptr, nullptr, nullptr, &ep, &lvl) != QV_OK) return false;
+    for (int l = 0; l <= level; l++) nodes_[nodeIdx].conn[(size_t)l].assign(links.begin() + (size_t)l * stride, links.begin() + (size_t)l * stride + deg[(size_t)l]);
+    for (size_t i = 0; i < nbs.size(); i++) nodes_[nbs[i]].conn[(size_t)c].assign(nlinks.begin() + i * stride, nlinks.begin() + i * stride + ndeg[i]);
+    entry_ = ep; cur_level_ = lvl;                                     // :325-332, replayed by qv_graph_insert
+    return true;
 }
 
 // n Inserts connected on the device.  Same checks and bookkeeping as Insert; the connectNode work of all n nodes is
@@ -526,7 +585,7 @@ Error HNSW::InsertBatch(const std::vector<std::string>& ids, const float* packed
     if (!e.empty()) return e;
     if (had_nodes && entry_ == eff_entry && cur_level_ == level_before) entry_ = entry_before;   // the build did not move it
     if (dg_ && dg_ != bg_) qv_graph_destroy(dg_);
-    dg_ = bg_; dg_dirty_ = false;                                      // the graph just built is the one SearchBatch walks
+    dg_ = bg_; dg_dirty_ = false; edited_in_place_ = false;            // the graph just built is the one SearchBatch walks
     return "";
 }
 
@@ -556,7 +615,9 @@ Error HNSW::Delete(const std::string& id) {                            // hnsw.g
     if (it == by_id_.end()) return fmt("vector with ID %s not found", id.c_str());   // :745-749
     uint32_t idx = it->second;
     if (!ok(idx)) return fmt("vector index %u is invalid", idx);       // :752-755
-    dg_dirty_ = true; bg_synced_ = false;
+    // a device graph that is the current copy of nodes_ takes the same edit in place (qv_graph_remove) and stays current
+    const bool on_device = deviceEditable((uint32_t)nodes_.size());
+    if (!on_device) { dg_dirty_ = true; bg_synced_ = false; }
     Node& nd = nodes_[idx];
     for (int level = 0; level <= nd.level; level++) {                  // :762
         if (level >= (int)nd.conn.size()) continue;
@@ -588,6 +649,13 @@ Error HNSW::Delete(const std::string& id) {                            // hnsw.g
     by_id_.erase(it);
     size_--;
     (void)qv_index_remove(h_, &idx, 1);
+    if (on_device) {
+        // any error, or a graph that ends up naming another entry point, only costs the next search an upload: never a result
+        uint32_t ep = 0; int lvl = -1;
+        if (qv_graph_remove(bg_, &idx, 1) == QV_OK && qv_graph_info(bg_, nullptr, nullptr, nullptr, nullptr, &ep, &lvl) == QV_OK &&
+            ep == entry_ && lvl == cur_level_) { device_removes_++; edited_in_place_ = true; }
+        else { dg_dirty_ = true; bg_synced_ = false; }
+    }
     return "";
 }
 
@@ -603,7 +671,7 @@ Error HNSW::Search(const float* q, uint32_t len, int k, std::vector<HNSWResult>*
         { std::lock_guard<std::mutex> lk(dg_mu_); uploaded = dg_ != nullptr && !dg_dirty_.load(); }   // dg_ is written under dg_mu_ by whichever SEARCH uploads the copy
         device_current = uploaded && !nodes_.empty() && size_ > 0 && k > 0 && k <= 512 && efS_ <= 512 && M_ <= 64 && maxM0_ <= 64 &&
                          (int)len == dim_;
-        if (!device_current) return searchLocked(q, len, k, out);
+        if (!device_current) { if (size_ > 0) host_searches_++; return searchLocked(q, len, k, out); }
     }
     std::vector<std::vector<HNSWResult>> one;
     Error e = SearchBatch(q, len, 1, k, &one, nullptr);                // (takes the lock itself; a mutation in between only means a fresh upload)
@@ -703,6 +771,7 @@ Error HNSW::syncDeviceGraph() {
     if (uplinks.empty()) uplinks.assign((size_t)1 + M_, 0);
     if (qv_graph_create(&dg_, h_, n, levels.data(), (uint32_t)maxM0_, (uint32_t)M_, l0deg.data(), l0links.data(), upoff.data(), uplinks.data(),
                         std::max(blocks, 1u), entry, cur_level_) != QV_OK) return qv_err();
+    full_uploads_++;
     dg_dirty_ = false;
     return "";
 }
@@ -1198,6 +1267,7 @@ uint32_t qvh_hybrid_exact_device_rows(void* p) { return static_cast<HybridIndex*
 int qvh_hybrid_hnsw_built_on_device(void* p) { return static_cast<HybridIndex*>(p)->hnsw().graph().BuiltOnDevice() ? 1 : 0; }
 uint32_t qvh_hnsw_device_fallbacks(void* p) { return static_cast<HNSW*>(p)->DeviceFallbacks(); }
 uint32_t qvh_hnsw_topups(void* p) { return static_cast<HNSW*>(p)->TopUps(); }
+void qvh_hnsw_device_state(void* p, uint64_t out[4]) { static_cast<HNSW*>(p)->DeviceState(out); }
 uint32_t qvh_hnsw_size(void* p) { return static_cast<HNSW*>(p)->Size(); }
 uint32_t qvh_hnsw_nodes(void* p) { return static_cast<HNSW*>(p)->Nodes(); }
 int qvh_hnsw_node_level(void* p, uint32_t n) { return static_cast<HNSW*>(p)->NodeLevel(n); }

@@ -139,7 +139,9 @@ public:
     uint32_t Size() const { return size_.load(); }                    // hnsw.go:253-255 atomic.LoadUint32
     // introspection for graph-equality tests
     uint32_t Nodes() const { std::shared_lock<std::shared_mutex> l(mu_); return (uint32_t)nodes_.size(); }
-    bool BuiltOnDevice() const { return bg_synced_ && bg_ != nullptr; }
+    // the graph is what InsertBatch built: no Delete or lone Insert since (those keep the device graph current where they can —
+    // DeviceState — but the graph is then no longer a batch build's)
+    bool BuiltOnDevice() const { return bg_synced_ && bg_ != nullptr && !edited_in_place_; }
     int NodeLevel(uint32_t n) const { return n < nodes_.size() && nodes_[n].alive ? nodes_[n].level : -1; }
     const std::vector<uint32_t>* Links(uint32_t n, int level) const;
     void EntryPoint(uint32_t* ep, int* lvl) const { *ep = entry_; *lvl = cur_level_; }
@@ -185,6 +187,15 @@ private:
     qv_graph* dg_ = nullptr; std::atomic<bool> dg_dirty_{true}; std::atomic<uint32_t> device_fallbacks_{0}, topups_{0};
     qv_graph* bg_ = nullptr; bool bg_synced_ = true;   // graph under device-side construction (== dg_ while in sync with nodes_)
     Error syncDeviceGraph();
+    // Delete and a lone Insert edit the device graph in place (qv_graph_remove, qv_graph_insert of one node + qv_graph_export_lists)
+    // while it is the current copy of nodes_ and names the same entry point; otherwise they mark it stale as before
+    bool deviceEditable(uint32_t device_nodes) const;
+    bool connectOnDevice(uint32_t nodeIdx, int level, int graphLevel);   // connectNode + the entry-point update, on the device
+    bool edited_in_place_ = false;                 // a Delete / lone Insert since the last InsertBatch went to the device graph
+    std::atomic<uint64_t> full_uploads_{0}, device_removes_{0}, device_inserts_{0}, host_searches_{0};
+public:
+    // [0] uploads of the whole graph, [1] Deletes applied on the device, [2] lone Inserts connected on the device, [3] Searches the host drove hop by hop
+    void DeviceState(uint64_t out[4]) const { out[0] = full_uploads_; out[1] = device_removes_; out[2] = device_inserts_; out[3] = host_searches_; }
 };
 
 class HNSWAdapter {          // pkg/hnsw/adapter.go + pkg/hybrid/hnsw_adapter.go

@@ -139,6 +139,13 @@ hipError_t launch_build_links(const BuildView& b, uint32_t first, uint32_t n, in
     return hipGetLastError();
 }
 
+// the segment heads alone: qv_graph_remove.hip groups its keys by target list the same way
+hipError_t launch_build_heads(const uint64_t* d_sorted, uint32_t n_keys, uint32_t* d_seg_start, uint32_t* d_seg_n, hipStream_t s) {
+    if (n_keys == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_build_heads, dim3((n_keys + 255) / 256), dim3(256), 0, s, d_sorted, n_keys, d_seg_start, d_seg_n);
+    return hipGetLastError();
+}
+
 hipError_t launch_build_compact_redo(const uint32_t* d_count, uint32_t n, uint32_t* d_redo_idx, uint32_t* d_redo_n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_build_compact_redo, dim3((n + 255) / 256), dim3(256), 0, s, d_count, n, d_redo_idx, d_redo_n);

@@ -430,6 +430,22 @@ hipError_t launch_build_links(const BuildView& b, uint32_t first, uint32_t n, in
                               const uint32_t* d_count, const float* d_self, uint64_t* d_keys_a, uint64_t* d_keys_b, uint32_t* d_hist,
                               uint32_t* d_seg_start, uint32_t* d_counters, uint32_t merge_grid, hipStream_t s);
 
+hipError_t launch_build_heads(const uint64_t* d_sorted, uint32_t n_keys, uint32_t* d_seg_start, uint32_t* d_seg_n, hipStream_t s);
+
+// Delete on a device-resident graph (qv_graph_remove.hip).  d_work: [3][n_work] (node, level, place in the call's list) of every
+// list of the m listed nodes; d_snode ascending with d_srank the place of each; keys: n_work * max(max_m0, max_m) each; *d_seg_n zeroed.
+// The lists of the survivors are compacted; launch_graph_tombstone then marks the listed nodes dead.
+hipError_t launch_graph_remove(const BuildView& b, uint32_t n_nodes, const uint32_t* d_work, uint32_t n_work, const uint32_t* d_snode,
+                               const uint32_t* d_srank, uint32_t m, uint64_t* d_keys_a, uint64_t* d_keys_b, uint32_t* d_hist,
+                               uint32_t* d_seg_start, uint32_t* d_seg_n, uint32_t grid, hipStream_t s);
+hipError_t launch_graph_tombstone(int8_t* d_level, const uint32_t* d_snode, uint32_t m, hipStream_t s);
+// the same for ONE node of level `level` (a host's Delete): one launch, nothing uploaded; d's own lists are left as they are
+hipError_t launch_graph_remove_one(const BuildView& b, uint32_t n_nodes, uint32_t d, int level, hipStream_t s);
+hipError_t launch_graph_tombstone_one(int8_t* d_level, uint32_t d, hipStream_t s);
+// the lists of n (node, level) pairs: degree [n] and links [n][max(max_m0, max_m)]; degree 0 for a dead node or a level it lacks
+hipError_t launch_export_lists(const GraphView& g, const uint32_t* d_nodes, const int* d_levels, uint32_t n, uint32_t* d_deg_out,
+                               uint32_t* d_links_out, hipStream_t s);
+
 // distance of one query to n listed rows (lane == listed row, sequential accumulation)
 hipError_t launch_distance_rows(const IndexView& v, const float* d_query, const uint32_t* d_rows, uint32_t n,
                                 float* d_dist_out, hipStream_t s);

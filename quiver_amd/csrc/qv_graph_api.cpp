@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <functional>
+#include <limits>
 #include <shared_mutex>
 
 // Everything ONE host-pointer traversal call owns while it runs: stream, converted-query workspace, result buffers, its redo
@@ -36,6 +37,7 @@ struct GraphCtx {
 
 struct qv_graph {
     qv_index* idx = nullptr;
+    int device = 0;                             // idx->device, kept here: qv_graph_destroy must not read an index its owner freed first
     qv::GraphView g{};
     // device arrays, sized by cap_nodes / cap_blocks
     int8_t* d_level = nullptr; uint32_t* d_l0deg = nullptr; uint32_t* d_l0links = nullptr; uint32_t* d_upoff = nullptr; uint32_t* d_uplinks = nullptr;
@@ -77,6 +79,13 @@ struct qv_graph {
     PinBuf h_counters;                          // counters read back: a pinned member, never the stack (an early return must not leave a copy in flight into a dead frame)
     // build workspace
     Buf b_self, b_keys_a, b_keys_b, b_hist, b_seg, b_redo, b_counters;
+    // in-place edits (qv_graph_remove / qv_graph_export_lists): the reference's EntryPoint may name a deleted node (Delete finds no
+    // replacement, hnsw.go:803-827) while every walk starts from the first live node (:355-363, :621-629).  g.entry is what the
+    // kernels start from, always live while n_live > 0; ref_entry is what qv_graph_info reports while entry_dead.
+    uint32_t ref_entry = 0; bool entry_dead = false;
+    uint32_t n_live = 0, live_from = 0;         // live nodes; no node below live_from is live
+    Buf r_work, r_snode, r_srank, x_nodes, x_levels, x_deg, x_links;
+    PinBuf x_host;
     double build_seconds = 0.0; uint64_t build_redo = 0, build_batches = 0;
 
     qv::BuildView bview() const {
@@ -84,6 +93,15 @@ struct qv_graph {
         b.level = d_level; b.l0_deg = d_l0deg; b.l0_links = d_l0links; b.l0_dist = d_l0dist; b.up_off = d_upoff; b.up_links = d_uplinks; b.up_dist = d_updist;
         b.cap_nodes = cap_nodes; b.max_m0 = g.max_m0; b.max_m = g.max_m;
         return b;
+    }
+    uint32_t info_entry() const { return entry_dead ? ref_entry : g.entry; }
+    // after the reference's EntryPoint / the liveness of nodes changed: the node the walks start from
+    void set_entry(uint32_t ref) {
+        ref_entry = ref;
+        entry_dead = !(ref < g.n_nodes && h_level[ref] >= 0);
+        if (!entry_dead) { g.entry = ref; return; }
+        while (live_from < g.n_nodes && h_level[live_from] < 0) live_from++;
+        g.entry = live_from < g.n_nodes ? live_from : ref;
     }
     void refresh_view() {
         g.level = d_level; g.l0_deg = d_l0deg; g.l0_links = d_l0links; g.up_off = d_upoff; g.up_links = d_uplinks;
@@ -182,7 +200,7 @@ int qv_graph_create(qv_graph** out, qv_index* idx, uint32_t n_nodes, const int8_
     HIPCHK(hipSetDevice(idx->device));
     qv_graph* g = new (std::nothrow) qv_graph();
     if (!g) return fail(QV_ERR_OOM, "out of host memory");
-    g->idx = idx;
+    g->idx = idx; g->device = idx->device;
     g->g.max_m0 = max_m0; g->g.max_m = max_m ? max_m : 1;
     int rc = graph_common_init(g);
     if (rc == QV_OK) rc = graph_reserve(g, n_nodes, std::max(n_up_blocks, 1u));
@@ -197,14 +215,14 @@ int qv_graph_create(qv_graph** out, qv_index* idx, uint32_t n_nodes, const int8_
     g->n_blocks = n_up_blocks;
     g->g.n_nodes = n_nodes; g->g.entry = entry; g->g.cur_level = cur_level;
     g->g.has_dead = false;
-    for (uint32_t i = 0; i < n_nodes; i++) if (levels[i] < 0) { g->g.has_dead = true; break; }
+    for (uint32_t i = 0; i < n_nodes; i++) { if (levels[i] < 0) g->g.has_dead = true; else g->n_live++; }
     *out = g;
     return QV_OK;
 }
 
 void qv_graph_destroy(qv_graph* g) {
     if (!g) return;
-    if (g->idx) (void)hipSetDevice(g->idx->device);
+    (void)hipSetDevice(g->device);
     if (g->ev_last) { (void)hipEventSynchronize(g->ev_last); (void)hipEventDestroy(g->ev_last); }
     for (GraphCtx* c : g->all_ctx) { c->release(); delete c; }
     if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
@@ -214,6 +232,8 @@ void qv_graph_destroy(qv_graph* g) {
     g->d_qblk.release(); g->d_rows.release(); g->d_dist.release(); g->d_cnt.release(); g->d_ev.release();
     g->h_counters.release();
     { auto& hb = g->hubs; hb.tiles.release(); hb.rnorm.release(); hb.rows.release(); hb.l0_hub.release(); hb.slot_of.release(); hb.hist.release(); hb.table.release(); }
+    g->r_work.release(); g->r_snode.release(); g->r_srank.release(); g->x_nodes.release(); g->x_levels.release(); g->x_deg.release(); g->x_links.release();
+    g->x_host.release();
     g->b_self.release(); g->b_keys_a.release(); g->b_keys_b.release(); g->b_hist.release(); g->b_seg.release(); g->b_redo.release(); g->b_counters.release();
     delete g;
 }
@@ -511,6 +531,11 @@ int qv_graph_search(qv_graph* g, const float* queries, uint32_t nq, uint32_t k, 
     if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");                      // hnsw.go:610-612
     if (k > 512 || ef_search > 512) return fail(QV_ERR_UNSUPPORTED, "k and efSearch above 512 are not supported on the device path");
     if (g->g.n_nodes == 0) return fail(QV_ERR_INVALID_ARG, "graph is empty");
+    if (g->n_live == 0) {                                               // every node deleted: hnsw.go:632-634 returns nothing
+        for (size_t i = 0; i < (size_t)nq * k; i++) { rows_out[i] = 0xFFFFFFFFu; dist_out[i] = std::numeric_limits<float>::infinity(); }
+        for (uint32_t q = 0; q < nq; q++) { count_out[q] = 0; if (evals_out) evals_out[q] = 0; }
+        return QV_OK;
+    }
     qv_index* idx = g->idx;
     HIPCHK(hipSetDevice(idx->device));
     // Small calls — the reference's host sends one query per call, concurrently (hnsw.go:602-606) — that find two batches already
@@ -552,6 +577,7 @@ int qv_graph_search_device(qv_graph* g, const float* d_queries, uint32_t nq, uin
     if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");                      // hnsw.go:610-612
     if (k > 512 || ef_search > 512) return fail(QV_ERR_UNSUPPORTED, "k and efSearch above 512 are not supported on the device path");
     if (g->g.n_nodes == 0) return fail(QV_ERR_INVALID_ARG, "graph is empty");
+    if (g->n_live == 0) return fail(QV_ERR_INVALID_ARG, "graph has no live node");
     qv_index* idx = g->idx;
     HIPCHK(hipSetDevice(idx->device));
     std::lock_guard<std::mutex> lock(g->mu);
@@ -590,7 +616,7 @@ int qv_graph_create_empty(qv_graph** out, qv_index* idx, uint32_t capacity_nodes
     HIPCHK(hipSetDevice(idx->device));
     qv_graph* g = new (std::nothrow) qv_graph();
     if (!g) return fail(QV_ERR_OOM, "out of host memory");
-    g->idx = idx; g->buildable = true; g->efc = ef_construction;
+    g->idx = idx; g->device = idx->device; g->buildable = true; g->efc = ef_construction;
     g->g.max_m0 = max_m0; g->g.max_m = m; g->g.n_nodes = 0; g->g.entry = 0; g->g.cur_level = -1; g->g.has_dead = false;
     int rc = graph_common_init(g);
     if (rc == QV_OK) rc = graph_reserve(g, std::max(capacity_nodes, 64u), std::max(capacity_nodes / 3 + capacity_nodes / 64, 64u));
@@ -681,11 +707,25 @@ int qv_graph_insert(qv_graph* g, uint32_t first_row, uint32_t n, const int8_t* l
     while (done < n) {
         const uint32_t at = first_row + done;
         if (at == 0) {                                                  // first node: entry point, nothing to connect (hnsw.go:306-311)
-            g->g.n_nodes = 1; g->g.entry = 0; g->g.cur_level = levels[0];
+            g->g.n_nodes = 1; g->g.cur_level = levels[0]; g->n_live = 1; g->live_from = 0; g->set_entry(0);
             done = 1; g->build_batches++;
             continue;
         }
         const uint32_t B = std::min(std::min(qv_graph_batch_size(at, batch_max, ramp_div), bmax), n - done);
+        if (g->n_live == 0) {
+            // every node before the batch is deleted: connectNode finds no entry to walk from (:355-363) and links nothing; the
+            // nodes only take part in the entry-point update (:325-332)
+            const int snap0 = g->g.cur_level;
+            uint32_t ref = g->info_entry();
+            for (uint32_t i = 0; i < B; i++) {
+                const int lv = levels[done + i];
+                if (lv > snap0 && lv > g->g.cur_level) { ref = at + i; g->g.cur_level = lv; }
+            }
+            done += B; g->build_batches++; g->n_live = B;
+            g->g.n_nodes = at + B;
+            g->set_entry(ref);
+            continue;
+        }
         // search phase against the graph as it stands (n_nodes = at)
         g->g.n_nodes = at;
         qv::HnswOpts wo = wave_opts(g);
@@ -713,12 +753,14 @@ int qv_graph_insert(qv_graph* g, uint32_t first_row, uint32_t n, const int8_t* l
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "graph build launch failed: %s", hipGetErrorString(e));
         // entry-point update, node by node (hnsw.go:325-332: level > oldCurrentLevel, then > CurrentLevel as it stands)
         const int snap = g->g.cur_level;
+        uint32_t ref = g->info_entry();
         for (uint32_t i = 0; i < B; i++) {
             const int lv = levels[done + i];
-            if (lv > snap && lv > g->g.cur_level) { g->g.entry = at + i; g->g.cur_level = lv; }
+            if (lv > snap && lv > g->g.cur_level) { ref = at + i; g->g.cur_level = lv; }
         }
-        done += B; g->build_batches++;
+        done += B; g->build_batches++; g->n_live += B;
         g->g.n_nodes = at + B;
+        g->set_entry(ref);
     }
     HIPCHK(hipEventRecord(g->ev_last, s));
     if ((rc = g->h_counters.ensure(64))) return rc;
@@ -752,7 +794,7 @@ int qv_graph_info(const qv_graph* g, uint32_t* n_nodes, uint32_t* n_up_blocks, u
     if (n_up_blocks) *n_up_blocks = g->n_blocks;
     if (max_m0) *max_m0 = g->g.max_m0;
     if (max_m) *max_m = g->g.max_m;
-    if (entry) *entry = g->g.entry;
+    if (entry) *entry = g->info_entry();
     if (cur_level) *cur_level = g->g.cur_level;
     return QV_OK;
 }
@@ -778,6 +820,170 @@ int qv_graph_export(qv_graph* g, int8_t* levels, uint32_t* l0_deg, uint32_t* l0_
     if (up_off) HIPCHK(hipMemcpy(up_off, g->d_upoff, n * 4, hipMemcpyDeviceToHost));
     if (up_links && g->n_blocks) HIPCHK(hipMemcpy(up_links, g->d_uplinks, (size_t)g->n_blocks * (1 + g->g.max_m) * 4, hipMemcpyDeviceToHost));
     return QV_OK;
+}
+
+}  // extern "C"
+
+// ---- edits in place ----------------------------------------------------------------------------------------------------
+namespace {
+
+// the lists of n (node, level) pairs through one gather kernel and one download per piece; g->mu held, nothing in flight
+int export_lists_locked(qv_graph* g, const uint32_t* nodes, const int* levels, uint32_t n, uint32_t* deg_out, uint32_t* links_out) {
+    const uint32_t stride = std::max(g->g.max_m0, g->g.max_m);
+    const uint32_t piece = 65536;
+    hipStream_t s = g->stream;
+    for (uint32_t i0 = 0; i0 < n; i0 += piece) {
+        const uint32_t m = std::min(piece, n - i0);
+        const size_t in_words = (size_t)2 * m, out_words = (size_t)m * (1 + stride);
+        int rc;
+        if ((rc = g->x_nodes.ensure((size_t)m * 4)) || (rc = g->x_levels.ensure((size_t)m * 4)) || (rc = g->x_deg.ensure((size_t)m * 4)) ||
+            (rc = g->x_links.ensure((size_t)m * stride * 4)) || (rc = g->x_host.ensure((in_words + out_words) * 4)))
+            return rc;
+        uint32_t* h = static_cast<uint32_t*>(g->x_host.p);
+        memcpy(h, nodes + i0, (size_t)m * 4); memcpy(h + m, levels + i0, (size_t)m * 4);
+        HIPCHK(hipMemcpyAsync(g->x_nodes.p, h, (size_t)m * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->x_levels.p, h + m, (size_t)m * 4, hipMemcpyHostToDevice, s));
+        hipError_t e = qv::launch_export_lists(g->g, static_cast<const uint32_t*>(g->x_nodes.p), static_cast<const int*>(g->x_levels.p), m,
+                                               static_cast<uint32_t*>(g->x_deg.p), static_cast<uint32_t*>(g->x_links.p), s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "graph list export launch failed: %s", hipGetErrorString(e));
+        HIPCHK(hipMemcpyAsync(h + in_words, g->x_deg.p, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h + in_words + m, g->x_links.p, (size_t)m * stride * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        memcpy(deg_out + i0, h + in_words, (size_t)m * 4);
+        memcpy(links_out + (size_t)i0 * stride, h + in_words + m, (size_t)m * stride * 4);
+    }
+    return QV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qv_graph_export_lists(qv_graph* g, const uint32_t* nodes, const int* levels, uint32_t n, uint32_t* deg_out, uint32_t* links_out) {
+    if (!g) return fail(QV_ERR_INVALID_ARG, "graph is null");
+    if (n == 0) return QV_OK;
+    if (!nodes || !levels || !deg_out || !links_out) return fail(QV_ERR_INVALID_ARG, "null argument");
+    for (uint32_t i = 0; i < n; i++)
+        if (nodes[i] >= g->g.n_nodes) return fail(QV_ERR_OUT_OF_RANGE, "node %u is not in the graph (nodes: %u)", nodes[i], g->g.n_nodes);
+    HIPCHK(hipSetDevice(g->idx->device));
+    std::lock_guard<std::mutex> lock(g->mu);
+    HIPCHK(hipEventSynchronize(g->ev_last));
+    return export_lists_locked(g, nodes, levels, n, deg_out, links_out);
+}
+
+int qv_graph_remove(qv_graph* g, const uint32_t* nodes, uint32_t n) {
+    if (!g) return fail(QV_ERR_INVALID_ARG, "graph is null");
+    if (n == 0) return QV_OK;
+    if (!nodes) return fail(QV_ERR_INVALID_ARG, "nodes is null");
+    if (!g->buildable) return fail(QV_ERR_UNSUPPORTED, "this graph was uploaded without link distances (qv_graph_create): call qv_graph_make_buildable first");
+    for (uint32_t i = 0; i < n; i++)
+        if (nodes[i] >= g->g.n_nodes) return fail(QV_ERR_OUT_OF_RANGE, "node %u is not in the graph (nodes: %u)", nodes[i], g->g.n_nodes);
+    qv_index* idx = g->idx;
+    HIPCHK(hipSetDevice(idx->device));
+    std::lock_guard<std::mutex> lock(g->mu);
+    HIPCHK(hipEventSynchronize(g->ev_last));                            // no traversal in flight while the lists change
+    // the nodes that are deleted, in list order: live now, first mention only (hnsw.go:745-755 answers the others with an error)
+    std::vector<uint32_t> ord;
+    {
+        std::vector<std::pair<uint32_t, uint32_t>> np;                  // (node, place)
+        for (uint32_t i = 0; i < n; i++) if (g->h_level[nodes[i]] >= 0) np.emplace_back(nodes[i], i);
+        std::sort(np.begin(), np.end());
+        std::vector<std::pair<uint32_t, uint32_t>> pn;                  // (place, node)
+        for (size_t i = 0; i < np.size(); i++) if (i == 0 || np[i].first != np[i - 1].first) pn.emplace_back(np[i].second, np[i].first);
+        std::sort(pn.begin(), pn.end());
+        ord.reserve(pn.size());
+        for (auto& p : pn) ord.push_back(p.second);
+    }
+    if (ord.empty()) return QV_OK;
+    const uint32_t stride = std::max(g->g.max_m0, g->g.max_m);
+    hipStream_t s = g->stream;
+    uint32_t ref = g->info_entry();                                     // the reference's EntryPoint as the deletions go by
+    std::vector<uint32_t> host, cdeg, clinks, cnodes; std::vector<int> clev;
+    int rc = QV_OK;
+    // entry point, hnsw.go:796-827, at d's turn: d's lists are what they were then (later deletions do not touch a nil node; the
+    // one-node path leaves d's own self-links in them, dropped here), and its level is still on the device
+    auto entry_step = [&](uint32_t d) -> int {
+        if (ref == d) {
+            if (g->g.n_nodes == 1) { ref = 0; g->g.cur_level = -1; }                        // :798-801
+            else {
+                const int lv = (int)g->h_level[d];
+                cnodes.assign((size_t)lv + 1, d); clev.resize((size_t)lv + 1);
+                for (int l = 0; l <= lv; l++) clev[(size_t)l] = lv - l;
+                cdeg.resize((size_t)lv + 1); clinks.resize(((size_t)lv + 1) * stride);
+                const int erc = export_lists_locked(g, cnodes.data(), clev.data(), (uint32_t)lv + 1, cdeg.data(), clinks.data());
+                if (erc != QV_OK) return erc;
+                bool found = false;
+                for (int j = 0; j <= lv && !found; j++) {                                    // :806-817 the first connection of each level, top down
+                    uint32_t c = 0xFFFFFFFFu;
+                    for (uint32_t t = 0; t < cdeg[(size_t)j] && c == 0xFFFFFFFFu; t++) if (clinks[(size_t)j * stride + t] != d) c = clinks[(size_t)j * stride + t];
+                    if (c == 0xFFFFFFFFu) continue;                                          // an empty list
+                    if (c < g->g.n_nodes && g->h_level[c] >= 0) { ref = c; g->g.cur_level = lv - j; found = true; }
+                }
+                if (!found) {                                                                // :820-828 the first valid node
+                    while (g->live_from < g->g.n_nodes && g->h_level[g->live_from] < 0) g->live_from++;
+                    for (uint32_t t = g->live_from; t < g->g.n_nodes; t++)
+                        if (t != d && g->h_level[t] >= 0) { ref = t; g->g.cur_level = (int)g->h_level[t]; break; }
+                }
+            }
+        }
+        g->h_level[d] = (int8_t)-1; g->n_live--;                                             // :832
+        return QV_OK;
+    };
+    if (ord.size() == 1) {
+        // one node — a host's Delete: one launch over its lists, nothing uploaded, no workspace
+        const uint32_t d = ord[0];
+        hipError_t e = qv::launch_graph_remove_one(g->bview(), g->g.n_nodes, d, (int)g->h_level[d], s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "graph remove launch failed: %s", hipGetErrorString(e));
+        if (ref == d) HIPCHK(hipStreamSynchronize(s));
+        rc = entry_step(d);
+        e = qv::launch_graph_tombstone_one(g->d_level, d, s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "graph remove launch failed: %s", hipGetErrorString(e));
+        HIPCHK(hipStreamSynchronize(s));
+        ord.clear();
+    }
+    // A piece of the list at a time (a deletion after another IS a call after another): at most 16384 nodes and 32768 lists
+    for (size_t c0 = 0; c0 < ord.size() && rc == QV_OK;) {
+        size_t c1 = c0; uint32_t n_work = 0;
+        while (c1 < ord.size() && c1 - c0 < 16384 && (c1 == c0 || n_work + (uint32_t)g->h_level[ord[c1]] + 1 <= 32768u)) { n_work += (uint32_t)g->h_level[ord[c1]] + 1; c1++; }
+        const uint32_t m = (uint32_t)(c1 - c0);
+        // [snode m][srank m][work: node n_work, level n_work, place n_work]
+        host.assign((size_t)2 * m + (size_t)3 * n_work, 0);
+        {
+            std::vector<std::pair<uint32_t, uint32_t>> sn(m);
+            for (uint32_t i = 0; i < m; i++) sn[i] = {ord[c0 + i], i};
+            std::sort(sn.begin(), sn.end());
+            for (uint32_t i = 0; i < m; i++) { host[i] = sn[i].first; host[m + i] = sn[i].second; }
+            uint32_t* work = host.data() + (size_t)2 * m; uint32_t w = 0;
+            for (uint32_t i = 0; i < m; i++)
+                for (int l = 0; l <= (int)g->h_level[ord[c0 + i]]; l++, w++) { work[w] = ord[c0 + i]; work[n_work + w] = (uint32_t)l; work[(size_t)2 * n_work + w] = i; }
+        }
+        const size_t nk = (size_t)n_work * stride;
+        if ((rc = g->r_work.ensure(host.size() * 4)) || (rc = g->b_keys_a.ensure(nk * 8)) || (rc = g->b_keys_b.ensure(nk * 8)) ||
+            (rc = g->b_hist.ensure(qv::radix_hist_words((uint32_t)nk) * 4)) || (rc = g->b_seg.ensure(nk * 4)) || (rc = g->b_counters.ensure(64)))
+            break;
+        uint32_t* dw = static_cast<uint32_t*>(g->r_work.p);
+        uint32_t* counters = static_cast<uint32_t*>(g->b_counters.p);
+        HIPCHK(hipMemcpy(dw, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(counters, 0, 64, s));
+        hipError_t e = qv::launch_graph_remove(g->bview(), g->g.n_nodes, dw + (size_t)2 * m, n_work, dw, dw + m, m, static_cast<uint64_t*>(g->b_keys_a.p),
+                                               static_cast<uint64_t*>(g->b_keys_b.p), static_cast<uint32_t*>(g->b_hist.p), static_cast<uint32_t*>(g->b_seg.p),
+                                               counters + 1, (uint32_t)idx->cus * 16, s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "graph remove launch failed: %s", hipGetErrorString(e));
+        HIPCHK(hipStreamSynchronize(s));
+        for (uint32_t i = 0; i < m && rc == QV_OK; i++) rc = entry_step(ord[c0 + i]);
+        if (rc != QV_OK) break;
+        e = qv::launch_graph_tombstone(g->d_level, dw, m, s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "graph remove launch failed: %s", hipGetErrorString(e));
+        HIPCHK(hipStreamSynchronize(s));
+        c0 = c1;
+    }
+    g->g.has_dead = true;
+    g->set_entry(ref);
+    {   // the hubs answer for rows by node number: none of them survives a deletion
+        std::unique_lock<std::shared_mutex> wl(g->hubs.mu);
+        g->hubs.H = 0; g->hubs.nodes_at = 0xFFFFFFFFu; g->hubs.writes_at = ~0ull;
+    }
+    return rc;
 }
 
 }  // extern "C"

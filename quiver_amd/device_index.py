@@ -681,6 +681,23 @@ class DeviceGraph:
         levels = np.ascontiguousarray(levels, dtype=np.int8)
         check(lib().qv_graph_insert(self._g, first_row, levels.size, levels.ctypes.data, batch_max, ramp_div))
 
+    def remove(self, nodes):
+        """hnsw.HNSW.Delete (hnsw.go:741-842) for the listed nodes, as if one by one in list order, in place on the device
+        (qv_graph_remove); the rows stay the caller's to remove from the index"""
+        nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.uint32)
+        check(lib().qv_graph_remove(self._g, nodes.ctypes.data, nodes.size))
+
+    def export_lists(self, nodes, levels):
+        """(deg [n], links [n, max(max_m0, max_m)]) of the lists (nodes[i], levels[i]); degree 0 for a dead node or a level it lacks"""
+        nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.uint32)
+        levels = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.int32)
+        if nodes.size != levels.size:
+            raise ValueError("nodes and levels must have the same length")
+        i = self.info()
+        deg = np.zeros(nodes.size, dtype=np.uint32); links = np.zeros((nodes.size, max(i["max_m0"], i["max_m"])), dtype=np.uint32)
+        check(lib().qv_graph_export_lists(self._g, nodes.ctypes.data, levels.ctypes.data, nodes.size, deg.ctypes.data, links.ctypes.data))
+        return deg, links
+
     def info(self) -> dict:
         v = [C.c_uint32(0) for _ in range(5)]; lv = C.c_int(0)
         check(lib().qv_graph_info(self._g, *[C.byref(x) for x in v], C.byref(lv)))

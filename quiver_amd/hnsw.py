@@ -105,6 +105,13 @@ class HNSW:
     def topups(self) -> int:
         return int(hlib().qvh_hnsw_topups(self._h))
 
+    def device_state(self) -> dict:
+        """what the mutations cost so far: uploads of the whole graph, Deletes / lone Inserts applied to the device graph in place
+        (qv_graph_remove, qv_graph_insert of one node), and Searches the host drove hop by hop because the device copy was stale"""
+        out = (C.c_uint64 * 4)()
+        hlib().qvh_hnsw_device_state(self._h, out)
+        return {"full_uploads": int(out[0]), "device_removes": int(out[1]), "device_inserts": int(out[2]), "host_searches": int(out[3])}
+
     def Size(self) -> int:
         return hlib().qvh_hnsw_size(self._h)
 
