@@ -1094,8 +1094,10 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const R
     }
     if (k <= (uint32_t)qv::kMaxFusedK && nq >= 2) {
         const uint32_t ct = rowsets_cand_tiles(idx, fl, nq);
-        const bool bound8 = nq <= 8 && qv::bound_scan8_applies_filtered_mq(idx->view(), nq, k, rowsets_cand_tiles(idx, fl, nq, true));
-        const bool bound = bound8 || (nq <= 8 && qv::bound_scan_applies_filtered(idx->view(), nq, k, ct));   // (9 or more are not cut into bound passes)
+        const qv::IndexView v = idx->view();
+        const qv::BoundKnobs knobs = qv::bound_knobs(v);
+        const bool bound8 = nq <= 8 && qv::bound_scan_decide(qv::bound_ask(v, nq, k, rowsets_cand_tiles(idx, fl, nq, true)), knobs) == qv::BoundStages::plane8_first;
+        const bool bound = bound8 || (nq <= 8 && qv::bound_scan_decide(qv::bound_ask(v, nq, k, ct), knobs) != qv::BoundStages::none);   // (9 or more are not cut into bound passes)
         pieces.push_back(RowsetPiece{0, nq, k, true, bound, ct, bound8});
         return std::max(qv::rowset_workspace_bytes(plan, nq, k, idx->dim4), bound ? qv::bound_scan_mq_workspace_bytes(plan, nq, k, n_tiles, idx->dim) : (size_t)0);
     }
@@ -1741,7 +1743,7 @@ int qv_index_set_filter(qv_index* idx, int filter) {
 int qv_index_set_bound_scan(qv_index* idx, int mode) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
     if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    idx->bound_scan = mode;
+    idx->bound.scan = mode;
     return QV_OK;
 }
 
@@ -1755,33 +1757,17 @@ int qv_index_bound_scan_stats(qv_index* idx, uint64_t out[4]) {
     return QV_OK;
 }
 
-int qv_index_set_bound_plane(qv_index* idx, int mode) {
+// the four plane knobs, one per form of the bound scan (qv::BoundForm)
+static int set_bound_plane(qv_index* idx, qv::BoundForm form, int mode) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
     if (mode < 0 || mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", mode);
-    idx->bound_plane = mode;
+    idx->bound.plane[form] = mode;
     return QV_OK;
 }
-
-int qv_index_set_bound_plane_filtered(qv_index* idx, int mode) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (mode < 0 || mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", mode);
-    idx->bound_plane_filtered = mode;
-    return QV_OK;
-}
-
-int qv_index_set_bound_plane_mq(qv_index* idx, int mode) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (mode < 0 || mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", mode);
-    idx->bound_plane_mq = mode;
-    return QV_OK;
-}
-
-int qv_index_set_bound_plane_filtered_mq(qv_index* idx, int mode) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (mode < 0 || mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", mode);
-    idx->bound_plane_filtered_mq = mode;
-    return QV_OK;
-}
+int qv_index_set_bound_plane(qv_index* idx, int mode) { return set_bound_plane(idx, qv::bound_one, mode); }
+int qv_index_set_bound_plane_filtered(qv_index* idx, int mode) { return set_bound_plane(idx, qv::bound_one_filtered, mode); }
+int qv_index_set_bound_plane_mq(qv_index* idx, int mode) { return set_bound_plane(idx, qv::bound_mq, mode); }
+int qv_index_set_bound_plane_filtered_mq(qv_index* idx, int mode) { return set_bound_plane(idx, qv::bound_mq_filtered, mode); }
 
 int qv_index_set_filtered_batch(qv_index* idx, int mode, uint32_t sparse_ppm) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
@@ -1822,28 +1808,36 @@ int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]) {
     return QV_OK;
 }
 
-int qv_scan_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8) {
+// The six rule exports: views of the one decision (qv::bound_scan_decide) for a call given without an index.  form: the form the export
+// speaks for (it says no to any other; -1: whichever the call has); want: the stage asked after — plane8_first, or any stage at all.  The
+// 8-bit rules are asked with the bfloat16 copy held; a filtered rule takes every candidate count as a count.
+static int bound_export(int form, qv::BoundStages want, int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, const char* plane_name, int plane_mode,
+                        int has_plane, int has_plane8, uint32_t candidate_tiles) {
     if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
-    return qv::host_bound8_applies(metric, dim, rows, nq, k, mode, plane_mode, has_plane8);
+    if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "%s must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_name, plane_mode);
+    const qv::BoundAsk ask = {metric, dim, rows, nq, k, candidate_tiles, has_plane != 0, has_plane8 != 0};
+    qv::BoundKnobs knobs = {mode, {0, 0, 0, 0}};
+    knobs.plane[qv::bound_form(ask)] = plane_mode;
+    if (form >= 0 && form != qv::bound_form(ask)) return 0;
+    const qv::BoundStages got = qv::bound_scan_decide(ask, knobs);
+    return (want == qv::BoundStages::plane8_first ? got == want : got != qv::BoundStages::none) ? 1 : 0;
+}
+static uint32_t as_count(uint32_t candidate_tiles) { return std::min(candidate_tiles, qv::kBoundNoFilter - 1); }
+
+int qv_scan_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8) {
+    return bound_export(qv::bound_one, qv::BoundStages::plane8_first, metric, dim, rows, nq, k, mode, "plane_mode", plane_mode, 1, has_plane8, qv::kBoundNoFilter);
 }
 
 int qv_scan_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8, uint32_t candidate_tiles) {
-    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    if (plane_mode_filtered < 0 || plane_mode_filtered > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered);
-    return qv::host_bound8_applies_filtered(metric, dim, rows, nq, k, mode, plane_mode_filtered, has_plane8, candidate_tiles);
+    return bound_export(qv::bound_one_filtered, qv::BoundStages::plane8_first, metric, dim, rows, nq, k, mode, "plane_mode_filtered", plane_mode_filtered, 1, has_plane8, as_count(candidate_tiles));
 }
 
 int qv_scan_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, int has_plane8) {
-    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    if (plane_mode_mq < 0 || plane_mode_mq > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_mq);
-    return qv::host_bound8_applies_mq(metric, dim, rows, nq, k, mode, plane_mode_mq, has_plane8);
+    return bound_export(qv::bound_mq, qv::BoundStages::plane8_first, metric, dim, rows, nq, k, mode, "plane_mode_mq", plane_mode_mq, 1, has_plane8, qv::kBoundNoFilter);
 }
 
 int qv_scan_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered_mq, int has_plane8, uint32_t candidate_tiles) {
-    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    if (plane_mode_filtered_mq < 0 || plane_mode_filtered_mq > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered_mq);
-    return qv::host_bound8_applies_filtered_mq(metric, dim, rows, nq, k, mode, plane_mode_filtered_mq, has_plane8, candidate_tiles);
+    return bound_export(qv::bound_mq_filtered, qv::BoundStages::plane8_first, metric, dim, rows, nq, k, mode, "plane_mode_filtered_mq", plane_mode_filtered_mq, 1, has_plane8, as_count(candidate_tiles));
 }
 
 int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, double qn, double qres, double rn, float rscale8, float rres8, float* d_lo, float* d_hi) {
@@ -1896,8 +1890,7 @@ int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {
 }
 
 int qv_scan_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane) {
-    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    return qv::host_bound_applies(metric, dim, rows, nq, k, mode, has_plane);
+    return bound_export(-1, qv::BoundStages::bf16, metric, dim, rows, nq, k, mode, "", 0, has_plane, 0, qv::kBoundNoFilter);
 }
 
 int qv_scan_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
@@ -1915,8 +1908,7 @@ int qv_scan_route_ex(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint3
 }
 
 int qv_scan_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles) {
-    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    return qv::host_bound_applies_filtered(metric, dim, rows, nq, k, mode, has_plane, candidate_tiles);
+    return bound_export(-1, qv::BoundStages::bf16, metric, dim, rows, nq, k, mode, "", 0, has_plane, 0, as_count(candidate_tiles));
 }
 
 int qv_index_profile(qv_index* idx, int enable) {

@@ -100,15 +100,11 @@ struct qv_index {
     float* d_rowmaj = nullptr;
     uint16_t* d_bf16 = nullptr;                // the bfloat16 copy (QV_FLAG_BF16_ROWS, and by default on cosine / dot indexes): refreshed by every call that writes rows
     bool plane_lost = false;                   // the default copy could not be allocated: the index carries on without it
-    int bound_scan = 0;                        // qv_index_set_bound_scan
+    qv::BoundKnobs bound = {};                 // qv_index_set_bound_scan, and by qv::BoundForm the four qv_index_set_bound_plane*
     int8_t* d_plane8 = nullptr;                // the int8 copy and its row state (scale, residual): kept with the default bfloat16 copy, refreshed with it
     float* d_rscale8 = nullptr;
     float* d_rres8 = nullptr;
     bool plane8_lost = false;                  // it could not be allocated: the index carries on with the bfloat16 copy
-    int bound_plane = 0;                       // qv_index_set_bound_plane
-    int bound_plane_filtered = 0;              // qv_index_set_bound_plane_filtered
-    int bound_plane_mq = 0;                    // qv_index_set_bound_plane_mq
-    int bound_plane_filtered_mq = 0;           // qv_index_set_bound_plane_filtered_mq
     int filtered_batch = 0;                    // qv_index_set_filtered_batch: QV_FILTERED_BATCH_*
     uint32_t filtered_batch_ppm = 0xFFFFFFFFu; // ... and its sparse floor in millionths of the rows (0xFFFFFFFF: the default, 0: never sparse)
     std::atomic<uint64_t> fb_stats[4] = {};    // qv_index_filtered_batch_stats: queries on the path, handed back (overflow / no bound / failed guess), handed back as sparse, batches
@@ -137,8 +133,8 @@ struct qv_index {
     qv::IndexView view() const {
         qv::IndexView v;
         v.tiles = d_tiles; v.rnorm = d_rnorm; v.alive = d_alive; v.rres = d_rres; v.rowmaj = d_rowmaj;
-        v.bf16 = (flags & QV_FLAG_BF16_ROWS) ? d_bf16 : nullptr; v.plane = d_bf16; v.bound_scan = bound_scan;
-        v.plane8 = d_plane8; v.rscale8 = d_rscale8; v.rres8 = d_rres8; v.bound_plane = bound_plane; v.bound_plane_filtered = bound_plane_filtered; v.bound_plane_mq = bound_plane_mq; v.bound_plane_filtered_mq = bound_plane_filtered_mq;
+        v.bf16 = (flags & QV_FLAG_BF16_ROWS) ? d_bf16 : nullptr; v.plane = d_bf16; v.bound_scan = bound.scan;
+        v.plane8 = d_plane8; v.rscale8 = d_rscale8; v.rres8 = d_rres8; v.bound_plane = bound.plane[qv::bound_one]; v.bound_plane_filtered = bound.plane[qv::bound_one_filtered]; v.bound_plane_mq = bound.plane[qv::bound_mq]; v.bound_plane_filtered_mq = bound.plane[qv::bound_mq_filtered];
         v.dim = dim; v.dim4 = dim4; v.n_rows = n_rows; v.n_tiles = (n_rows + 63) / 64; v.metric = metric; v.filter = filter;
         v.l2_planes = l2_planes() ? 1 : 0;
         return v;

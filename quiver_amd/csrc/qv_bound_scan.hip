@@ -866,8 +866,6 @@ k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __rest
 // width from 300 k rows; 1M x 128 was not measured here), and a FILTERED search only with nine tenths of the tiles holding a candidate (dot: one
 // query down to a tenth, 2 - 4 queries at 10M rows down to a fifth; sparse sets were not measured here).
 constexpr uint32_t kBoundL2NarrowDim = 128, kBoundL2NarrowRows = 10000000, kBoundL2WideDim = 768;
-static bool rule_metric_ok(int metric) { return metric == QV_COSINE || metric == QV_DOT || metric == QV_RULE_L2_PLANES; }
-static int rule_metric(const IndexView& v) { return v.metric == QV_L2 && v.l2_planes ? QV_RULE_L2_PLANES : v.metric; }
 constexpr uint32_t kBoundScanMinRows = 300000;   // one query, us, exact / bound scan at k = 1, 10, 64: 100 k x 768 65 / 63, 66 / 70, 86 / 122; 300 k x 768 154 / 107, 158 / 114, 190 / 169; 1M x 128 89 / 64, 93 / 68, 134 / 114
 // us per call, exact (k_flat_scan_mq) / bound, at k = 1, 10, 64:
 //   QB = 4   300 k x 768  nq 2: 195 / 154, 204 / 160, 273 / 223; nq 4: 193 / 160, 207 / 175, 276 / 271      1M x 128  nq 4: 97 / 93, 117 / 103, 214 / 216 (a loss)
@@ -876,22 +874,6 @@ constexpr uint32_t kBoundScanMinRows = 300000;   // one query, us, exact / bound
 //            1M x 128     nq 8: 122 / 124, 145 / 157, 330 / 367 (losses)      10M x 128 nq 5: 888 / 638, 892 / 657, 1162 / 849; nq 8: 869 / 734, 905 / 775, 1161 / 1093
 constexpr uint32_t kBoundMqMinDim = 768, kBoundMqMinRows4 = 300000, kBoundMqMinRows8 = 1000000;   // rows of at least 768 dimensions: QB = 4 (2 - 4 queries), QB = 8 (5 - 8)
 constexpr uint32_t kBoundMqNarrowDim = 128, kBoundMqNarrowRows = 10000000;                        // 128 <= dim < 768 (nothing between was measured): both QB
-int bound_scan_mode(int mode) { static const int env_mode = env_int("QV_BOUND_SCAN", 0); return mode ? mode : env_mode; }
-bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane) {
-    mode = bound_scan_mode(mode);
-    const uint32_t n_tiles = (n_rows + 63) / 64;
-    if (mode == 2 || nq < 1 || nq > kBoundMqMax || k < 1 || k > (uint32_t)kMaxFusedK || !rule_metric_ok(metric) || !has_plane) return false;
-    if ((dim & 15u) != 0 || dim > kBoundMaxDim || n_tiles < 8) return false;
-    if (nq == 1) {
-        if (mode == 1) return true;
-        if (metric == QV_RULE_L2_PLANES && dim < kBoundL2WideDim) return dim >= kBoundL2NarrowDim && n_rows >= kBoundL2NarrowRows;
-        return n_rows >= kBoundScanMinRows;
-    }
-    if ((uint64_t)nq * n_tiles * 256 > (2ull << 30)) return false;
-    const uint32_t min_rows = dim >= kBoundMqMinDim ? (nq <= 4 ? kBoundMqMinRows4 : kBoundMqMinRows8) : kBoundMqNarrowRows;
-    return mode == 1 || (dim >= kBoundMqNarrowDim && n_rows >= min_rows);
-}
-bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) { return bound_scan_rule(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr); }
 // The 8-bit stage in front of it (k_bound_scan8): one unfiltered query the bound scan takes, on an index that holds the 8-bit plane.  The index's
 // plane setter (IndexView::bound_plane) or QV_BOUND_PLANE = 1 puts it first whenever that holds, 2 never; automatic from the smallest
 // measured row count from which 8-bit-first beats bfloat16-first at every measured k — never below kBoundScanMinRows, so a corpus under
@@ -904,21 +886,11 @@ bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k) { return bo
 // narrower than kBound8NarrowDim nothing was measured: never automatic.
 constexpr uint32_t kBound8MinDim = 768, kBound8MinRows = 3000000;            // rows of at least 768 dimensions
 constexpr uint32_t kBound8NarrowDim = 128, kBound8NarrowRows = 10000000;     // 128 <= dim < 768 (nothing between was measured)
-static_assert(kBound8MinRows >= kBoundScanMinRows && kBound8NarrowRows >= kBoundScanMinRows, "the 8-bit floors are never below the bound scan's");
-static int bound_plane_mode(int mode) { static const int env_mode = env_int("QV_BOUND_PLANE", 0); return mode ? mode : env_mode; }
-bool bound_scan8_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode, bool has_plane8) {
-    plane_mode = bound_plane_mode(plane_mode);
-    if (plane_mode == 2 || nq != 1 || !has_plane8 || !bound_scan_rule(metric, dim, n_rows, 1, k, mode, true)) return false;
-    return plane_mode == 1 || (dim >= kBound8NarrowDim && n_rows >= (dim >= kBound8MinDim ? kBound8MinRows : kBound8NarrowRows));
-}
-bool bound_scan8_applies(const IndexView& v, uint32_t nq, uint32_t k) {
-    return v.plane != nullptr && bound_scan8_rule(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane, v.plane8 != nullptr);
-}
 // The 8-bit stage in front of an UNFILTERED shared pass of 2 - 8 queries (k_bound_scan8_mq): a pass the bound scan takes (asked with the copy
 // held: the stage never starts a pass the bound scan would not take), the plane held, and the index's shared-pass plane setter
 // (IndexView::bound_plane_mq) or QV_BOUND_PLANE_MQ — a knob of its own — allows it: 1 whenever that holds, 2 never.  Automatic: per QB the
 // smallest measured row count from which 8-bit-first beat bfloat16-first at every measured k and nq of that QB in both rounds, never below
-// bound_scan_rule's own floors; profiles/LAB_r12_bound_scan8_mq.md.
+// the shared pass's own floors; profiles/LAB_r12_bound_scan8_mq.md.
 // us per call, bfloat16 first / 8-bit first, at k = 1, 10, 64 (the slower round of the 8-bit arm against the faster of the bfloat16 arm):
 //   QB = 4   768 dims   300 k  nq 2: 152 / 132, 161 / 146, 225 / 310; nq 4: 161 / 139, 172 / 160, 269 / 360 (losses at k = 64)
 //                       1M     nq 2: 318 / 209, 324 / 236, 392 / 399; nq 4: 334 / 225, 347 / 258, 443 / 474 (losses at k = 64)
@@ -932,25 +904,6 @@ bool bound_scan8_applies(const IndexView& v, uint32_t nq, uint32_t k) {
 //            128 dims   10M    nq 5: 608 / 493, 628 / 569, 833 / 848; nq 8: 721 / 619, 760 / 741, 1086 / 1166 (losses at k = 64: QB = 8 is never automatic below 768 dimensions)
 constexpr uint32_t kBound8MqMinDim = 768, kBound8MqMinRows4 = 3000000, kBound8MqMinRows8 = 3000000;   // rows of at least 768 dimensions, QB = 4 / QB = 8
 constexpr uint32_t kBound8MqNarrowDim = 128, kBound8MqNarrowRows4 = 10000000, kBound8MqNarrowRows8 = 0;   // 128 <= dim < 768 (nothing between was measured); 0: never automatic
-static_assert(kBound8MqMinRows4 >= kBoundMqMinRows4 && kBound8MqMinRows8 >= kBoundMqMinRows8 && kBound8MqNarrowRows4 >= kBoundMqNarrowRows, "the 8-bit floors are never below the shared pass's");
-static bool bound8_mq_auto(uint32_t dim, uint32_t n_rows, uint32_t nq) {
-    if (dim < kBound8MqNarrowDim) return false;
-    const uint32_t floor = dim >= kBound8MqMinDim ? (nq <= 4 ? kBound8MqMinRows4 : kBound8MqMinRows8) : (nq <= 4 ? kBound8MqNarrowRows4 : kBound8MqNarrowRows8);
-    return floor != 0 && n_rows >= floor;
-}
-static int bound_plane_mq_mode(int mode) { static const int env_mode = env_int("QV_BOUND_PLANE_MQ", 0); return mode ? mode : env_mode; }
-bool bound_scan8_rule_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, bool has_plane8) {
-    plane_mode_mq = bound_plane_mq_mode(plane_mode_mq);
-    if (plane_mode_mq == 2 || nq < 2 || nq > kBoundMqMax || !has_plane8 || !bound_scan_rule(metric, dim, n_rows, nq, k, mode, true)) return false;
-    if (plane_mode_mq == 1) return true;
-    return bound8_mq_auto(dim, n_rows, nq);
-}
-bool bound_scan8_applies_mq(const IndexView& v, uint32_t nq, uint32_t k) {
-    return v.plane != nullptr && bound_scan8_rule_mq(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_mq, v.plane8 != nullptr);
-}
-int host_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, int has_plane8) {
-    return bound_scan8_rule_mq(metric, dim, rows, nq, k, mode, plane_mode_mq, has_plane8 != 0) ? 1 : 0;
-}
 // Under a filter (a candidate bitmap in v.alive, or a row set per query): candidate_tiles = the tiles that hold a candidate of any query of
 // the pass, as the host knows it without a device read (an upper bound: sets count their non-empty words, tombstones are not subtracted, a pass
 // takes min(n_tiles, the sum over its queries) — so eight queries naming ONE striped set look like eight distinct ones).  "always" takes
@@ -968,21 +921,6 @@ int host_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq,
 //   nq 3 and 5 - 7 were not run: the bound pass gets cheaper with fewer queries (a lower-bound plane and a collect each) while the exact pass of
 //   a QB costs the same at any fill (LAB_r08: 526 / 526 us at nq 5 / 8), so they are bracketed by the nq = 4 and nq = 8 cells.
 constexpr uint32_t kBoundFiltMinDim = 768, kBoundFiltMqRows = 1000000, kBoundFiltBigRows = 10000000, kBoundFiltQb8SmallK = 10;
-bool bound_scan_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane, uint32_t candidate_tiles) {
-    mode = bound_scan_mode(mode);
-    if (mode == 2 || !bound_scan_rule(metric, dim, n_rows, nq, k, 1, has_plane)) return false;
-    if (mode == 1) return true;
-    const uint64_t n_tiles = ((uint64_t)n_rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
-    if (ct == 0 || dim < kBoundFiltMinDim || !bound_scan_rule(metric, dim, n_rows, nq, k, 0, has_plane)) return false;   // (never below the unfiltered floors)
-    if (metric == QV_RULE_L2_PLANES && ct * 10 < n_tiles * 9) return false;                      // (sparser filters were not measured for it)
-    if (nq == 1) return ct * 10 >= n_tiles;                                                      // from kBoundScanMinRows rows; one tile in ten is the sparsest measured
-    if (n_rows < kBoundFiltMqRows) return false;
-    if (nq <= 4) return n_rows >= kBoundFiltBigRows ? ct * 5 >= n_tiles : ct * 10 >= n_tiles * 9;
-    return ct * 10 >= n_tiles * 9 && (n_rows >= kBoundFiltBigRows || k <= kBoundFiltQb8SmallK);
-}
-bool bound_scan_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
-    return bound_scan_rule_filtered(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.plane != nullptr, candidate_tiles);
-}
 // The 8-bit stage in front of a FILTERED single query (k_bound_scan8<., true>): whenever the filtered bound rule takes the search (asked with
 // the copy held: the stage never starts a search the bound scan would not take), one query, the plane held, and the index's filtered plane
 // setter (IndexView::bound_plane_filtered) or QV_BOUND_PLANE_FILTERED — a knob of its own, independent of the unfiltered one — allows it:
@@ -997,29 +935,12 @@ bool bound_scan_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, ui
 //   f = 0.1    one tile in ten     1M 70 / 88, 75 / 107, 132 / 206 (losses)                3M 237 / 158, 248 / 186, 370 / 369 (k = 64: no gain)
 //                                  10M 295 / 217, 303 / 235, 362 / 365 (a loss at k = 64): declined at every row count
 //   0.1 < f < 0.9 was not measured: declined.  So: f >= 0.9 from kBound8MinRows rows of kBound8MinDim dimensions or more.
-static bool bound8_filtered_auto(uint32_t dim, uint32_t n_rows, uint32_t candidate_tiles) {
-    const uint64_t n_tiles = ((uint64_t)n_rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
-    return dim >= kBound8MinDim && n_rows >= kBound8MinRows && ct * 10 >= n_tiles * 9;
-}
-static int bound_plane_filtered_mode(int mode) { static const int env_mode = env_int("QV_BOUND_PLANE_FILTERED", 0); return mode ? mode : env_mode; }
-bool bound_scan8_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, bool has_plane8, uint32_t candidate_tiles) {
-    plane_mode_filtered = bound_plane_filtered_mode(plane_mode_filtered);
-    if (plane_mode_filtered == 2 || nq != 1 || !has_plane8 || !bound_scan_rule_filtered(metric, dim, n_rows, 1, k, mode, true, candidate_tiles)) return false;
-    if (plane_mode_filtered == 1) return true;
-    return bound8_filtered_auto(dim, n_rows, candidate_tiles);
-}
-bool bound_scan8_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
-    return v.plane != nullptr && bound_scan8_rule_filtered(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_filtered, v.plane8 != nullptr, candidate_tiles);
-}
-int host_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8, uint32_t candidate_tiles) {
-    return bound_scan8_rule_filtered(metric, dim, rows, nq, k, mode, plane_mode_filtered, has_plane8 != 0, candidate_tiles) ? 1 : 0;
-}
 // The 8-bit stage in front of a FILTERED shared pass of 2 - 8 queries (k_bound_scan8_mq<., ., true>: a mask, a row set per query, where-filters,
 // the row-set front's shared passes): whenever the filtered bound rule takes the pass (asked with the copy held: the stage never starts a pass
 // the filtered bound scan would not take), the plane held, and the index's setter for such passes (IndexView::bound_plane_filtered_mq) or
 // QV_BOUND_PLANE_FILTERED_MQ — a knob of its own, independent of the three others — allows it: 1 whenever that holds, 2 never.
 // Automatic: a cell is taken only when 8-bit first beat bfloat16 first at every measured k, the slower 8-bit round against the faster
-// bfloat16 round, by more than both arms' round-to-round spread; never above what bound8_mq_auto allows for the same nq, never below
+// bfloat16 round, by more than both arms' round-to-round spread; never above what the unfiltered pass's 8-bit floors allow for the same nq, never below
 // kBound8MinDim dimensions.  profiles/LAB_r13_bound_scan8_filtered_mq.md; us per call, bfloat16 first / 8-bit first (the faster bfloat16 round
 // against the slower 8-bit round), 768 dims, k = 1, 10, 64; f = candidate_tiles / tiles as the host computes it:
 //   f = 1.0   null sets         1M   nq 2: 317 / 210, 323 / 237, 395 / 400; nq 4: 332 / 224, 349 / 258, 443 / 474; nq 8: 464 / 293, 474 / 357, 691 / 695 (losses at k = 64)
@@ -1040,33 +961,100 @@ int host_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32
 // nq x tiles x 256 bytes of lower-bound words (0.3 GB, written and read again, for 8 queries at 10M rows).  "bf16" restores the earlier routing for such hosts.
 // So: f >= 0.9 from 3 000 000 rows of 768 dimensions or more, both QB; 1M loses at k = 64 with every tile a candidate.  Spreads <= 83 us at 10M, <= 11 us below.
 constexpr uint32_t kBound8FiltMqMinDim = 768, kBound8FiltMqMinRows4 = 3000000, kBound8FiltMqMinRows8 = 3000000;   // rows of at least 768 dimensions, QB = 4 / QB = 8; 0: never automatic
-static_assert(kBound8FiltMqMinDim >= kBound8MinDim && (kBound8FiltMqMinRows4 == 0 || kBound8FiltMqMinRows4 >= kBound8MqMinRows4) &&
-              (kBound8FiltMqMinRows8 == 0 || kBound8FiltMqMinRows8 >= kBound8MqMinRows8), "the filtered floors are never below the unfiltered shared pass's");
-static bool bound8_filtered_mq_auto(uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t candidate_tiles) {
-    const uint64_t n_tiles = ((uint64_t)n_rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
-    const uint32_t floor = nq <= 4 ? kBound8FiltMqMinRows4 : kBound8FiltMqMinRows8;
-    return dim >= kBound8FiltMqMinDim && floor != 0 && n_rows >= floor && ct * 10 >= n_tiles * 9 && bound8_mq_auto(dim, n_rows, nq);
+// ---- the ONE decision: which stages answer a call (bound_scan_decide; plan_flat and the row-set front ask it, the launchers never) ----
+// All six forms — one query or a shared pass of 2 - 8, filtered or not, with or without the 8-bit plane first — share one skeleton, written once
+// below: "never" on the bound scan's knob, or a call the kernels cannot serve -> none; the bfloat16 stage under "always", else where the automatic
+// rule of the call's class takes it; then the 8-bit stage in front under the FORM's own plane knob: "bf16" or no plane held -> the bfloat16 stage
+// alone, "8bit" -> in front, else where the 8-bit stage's automatic rule takes it.  (So the 8-bit stage never starts a call the bound scan
+// would not take, and every plane knob is independent of the others.)  What differs between the forms is data: the measured constants above,
+// gathered in two tables.  An automatic rule is the unfiltered floor of its class and, under a filter, the filter's conditions ON TOP: a
+// filtered form is never taken below the unfiltered floors.  Classes: one query, QB = 4 (2 - 4 queries), QB = 8 (5 - 8 queries).
+constexpr uint32_t kBoundWideDim = 768;   // where every rule's wide class starts (128 dimensions were measured, nothing between)
+static_assert(kBoundMqMinDim == kBoundWideDim && kBoundL2WideDim == kBoundWideDim && kBound8MinDim == kBoundWideDim && kBound8MqMinDim == kBoundWideDim &&
+              kBoundFiltMinDim == kBoundWideDim && kBound8FiltMqMinDim == kBoundWideDim, "the rules share one wide class");
+enum { kRulesBf16 = 0, kRulesBf16L2 = 1, kRulesPlane8 = 2 };          // the bfloat16 stage for cosine and dot / on L2 planes; the 8-bit stage (any metric)
+struct BoundFloor { uint32_t wide_rows, narrow_dim, narrow_rows; };   // from wide_rows rows of kBoundWideDim dimensions or more, from narrow_rows rows of
+                                                                      // narrow_dim <= dim < kBoundWideDim, never narrower; 0 rows: never automatic
+constexpr BoundFloor kBoundFloor[3][3] = {
+    {{kBoundScanMinRows, 0, kBoundScanMinRows},                       // one query: any width the kernels serve
+     {kBoundMqMinRows4, kBoundMqNarrowDim, kBoundMqNarrowRows}, {kBoundMqMinRows8, kBoundMqNarrowDim, kBoundMqNarrowRows}},
+    {{kBoundScanMinRows, kBoundL2NarrowDim, kBoundL2NarrowRows},      // L2 planes: one query's narrow rows are its own, the shared passes' are cosine's
+     {kBoundMqMinRows4, kBoundMqNarrowDim, kBoundMqNarrowRows}, {kBoundMqMinRows8, kBoundMqNarrowDim, kBoundMqNarrowRows}},
+    {{kBound8MinRows, kBound8NarrowDim, kBound8NarrowRows},
+     {kBound8MqMinRows4, kBound8MqNarrowDim, kBound8MqNarrowRows4}, {kBound8MqMinRows8, kBound8MqNarrowDim, kBound8MqNarrowRows8}},
+};
+struct BoundFilterFloor {                                             // under a filter, ct = min(candidate_tiles, n_tiles):
+    uint32_t min_dim, min_rows;                                       // never narrower, never fewer rows (0 rows: never automatic)
+    uint32_t tenths;                                                  // ct * 10 >= n_tiles * tenths
+    uint32_t big_rows, big_tenths;                                    // ... from big_rows rows on, big_tenths in its place (0 rows: no such size)
+    uint32_t small_k;                                                 // ... and below big_rows rows only k <= small_k (0: any k)
+};
+constexpr BoundFilterFloor kBoundFilterFloor[3][3] = {
+    {{kBoundFiltMinDim, kBoundScanMinRows, 1, 0, 0, 0},               // one query: from kBoundScanMinRows rows; one tile in ten is the sparsest measured
+     {kBoundFiltMinDim, kBoundFiltMqRows, 9, kBoundFiltBigRows, 2, 0},   // QB = 4: nine tenths from 1M rows, a fifth from 10M
+     {kBoundFiltMinDim, kBoundFiltMqRows, 9, kBoundFiltBigRows, 9, kBoundFiltQb8SmallK}},   // QB = 8: nine tenths, and below 10M rows k <= 10
+    {{kBoundFiltMinDim, kBoundScanMinRows, 9, 0, 0, 0},               // L2 planes: nine tenths throughout (sparser filters were not measured for it)
+     {kBoundFiltMinDim, kBoundFiltMqRows, 9, 0, 0, 0}, {kBoundFiltMinDim, kBoundFiltMqRows, 9, kBoundFiltBigRows, 9, kBoundFiltQb8SmallK}},
+    {{kBound8MinDim, kBound8MinRows, 9, 0, 0, 0},                     // the 8-bit stage: f >= 0.9 in every class
+     {kBound8FiltMqMinDim, kBound8FiltMqMinRows4, 9, 0, 0, 0}, {kBound8FiltMqMinDim, kBound8FiltMqMinRows8, 9, 0, 0, 0}},
+};
+constexpr bool bound_floors_nest() {
+    for (int c = 0; c < 3; c++) {
+        const BoundFloor &b = kBoundFloor[kRulesBf16][c], &l = kBoundFloor[kRulesBf16L2][c], &p = kBoundFloor[kRulesPlane8][c];
+        const BoundFilterFloor& pf = kBoundFilterFloor[kRulesPlane8][c];
+        if (p.wide_rows < b.wide_rows || p.wide_rows < l.wide_rows || p.narrow_dim < b.narrow_dim || p.narrow_dim < l.narrow_dim) return false;
+        if (p.narrow_rows != 0 && (p.narrow_rows < b.narrow_rows || p.narrow_rows < l.narrow_rows)) return false;
+        if (pf.min_dim < kBound8MinDim || (pf.min_rows != 0 && pf.min_rows < p.wide_rows)) return false;
+    }
+    return true;
 }
-static int bound_plane_filtered_mq_mode(int mode) { static const int env_mode = env_int("QV_BOUND_PLANE_FILTERED_MQ", 0); return mode ? mode : env_mode; }
-bool bound_scan8_rule_filtered_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_fmq, bool has_plane8, uint32_t candidate_tiles) {
-    plane_mode_fmq = bound_plane_filtered_mq_mode(plane_mode_fmq);
-    if (plane_mode_fmq == 2 || nq < 2 || nq > kBoundMqMax || !has_plane8 || !bound_scan_rule_filtered(metric, dim, n_rows, nq, k, mode, true, candidate_tiles)) return false;
-    if (plane_mode_fmq == 1) return true;
-    return bound8_filtered_mq_auto(dim, n_rows, nq, candidate_tiles);
+static_assert(bound_floors_nest(), "the 8-bit floors are never below the bound scan's own, class by class, and its filtered floors never below its unfiltered ones");
+static int rule_metric(const IndexView& v) { return v.metric == QV_L2 && v.l2_planes ? QV_RULE_L2_PLANES : v.metric; }
+BoundAsk bound_ask(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
+    return {rule_metric(v), v.dim, v.n_rows, nq, k, candidate_tiles, v.plane != nullptr, v.plane8 != nullptr};
 }
-bool bound_scan8_applies_filtered_mq(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
-    return v.plane != nullptr && bound_scan8_rule_filtered_mq(rule_metric(v), v.dim, v.n_rows, nq, k, v.bound_scan, v.bound_plane_filtered_mq, v.plane8 != nullptr, candidate_tiles);
+BoundKnobs bound_knobs(const IndexView& v) { return {v.bound_scan, {v.bound_plane, v.bound_plane_filtered, v.bound_plane_mq, v.bound_plane_filtered_mq}}; }
+int bound_scan_mode(int mode) { static const int env_mode = env_int("QV_BOUND_SCAN", 0); return mode ? mode : env_mode; }
+static int bound_plane_mode(BoundForm form, int mode) {                // the form's plane mode in force: the index's own, else its variable (read once)
+    static const int env_mode[4] = {env_int("QV_BOUND_PLANE", 0), env_int("QV_BOUND_PLANE_FILTERED", 0), env_int("QV_BOUND_PLANE_MQ", 0), env_int("QV_BOUND_PLANE_FILTERED_MQ", 0)};
+    return mode ? mode : env_mode[form];
 }
-int host_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_fmq, int has_plane8, uint32_t candidate_tiles) {
-    return bound_scan8_rule_filtered_mq(metric, dim, rows, nq, k, mode, plane_mode_fmq, has_plane8 != 0, candidate_tiles) ? 1 : 0;
+// what the kernels need, whatever the knobs say: metric, k, nq, the copy, a width it covers in whole 16-dimension steps, 8 tiles, and nq planes
+// of lower bounds that stay under 2 GiB
+bool bound_scan_kernels_serve(const BoundAsk& a) {
+    const uint32_t n_tiles = (a.n_rows + 63) / 64;
+    const bool metric_ok = a.rule_metric == QV_COSINE || a.rule_metric == QV_DOT || a.rule_metric == QV_RULE_L2_PLANES;
+    if (a.nq < 1 || a.nq > kBoundMqMax || a.k < 1 || a.k > (uint32_t)kMaxFusedK || !metric_ok || !a.has_plane) return false;
+    if ((a.dim & 15u) != 0 || a.dim > kBoundMaxDim || n_tiles < 8) return false;
+    return a.nq == 1 || (uint64_t)a.nq * n_tiles * 256 <= (2ull << 30);
+}
+static bool bound_auto(const BoundAsk& a, int rules) {
+    const int cls = a.nq == 1 ? 0 : a.nq <= 4 ? 1 : 2;
+    const BoundFloor& f = kBoundFloor[rules][cls];
+    const uint32_t floor = a.dim >= kBoundWideDim ? f.wide_rows : a.dim >= f.narrow_dim ? f.narrow_rows : 0u;
+    if (floor == 0 || a.n_rows < floor) return false;
+    if (a.candidate_tiles == kBoundNoFilter) return true;
+    const BoundFilterFloor& g = kBoundFilterFloor[rules][cls];
+    const uint64_t n_tiles = ((uint64_t)a.n_rows + 63) / 64, ct = std::min<uint64_t>(a.candidate_tiles, n_tiles);
+    if (ct == 0 || a.dim < g.min_dim || g.min_rows == 0 || a.n_rows < g.min_rows) return false;
+    const bool big = g.big_rows != 0 && a.n_rows >= g.big_rows;
+    return ct * 10 >= n_tiles * (big ? g.big_tenths : g.tenths) && (big || g.small_k == 0 || a.k <= g.small_k);
+}
+BoundStages bound_scan_decide(const BoundAsk& a, const BoundKnobs& knobs) {
+    const int scan = bound_scan_mode(knobs.scan);
+    if (scan == 2 || !bound_scan_kernels_serve(a)) return BoundStages::none;
+    if (scan != 1 && !bound_auto(a, a.rule_metric == QV_RULE_L2_PLANES ? kRulesBf16L2 : kRulesBf16)) return BoundStages::none;
+    const int plane = bound_plane_mode(bound_form(a), knobs.plane[bound_form(a)]);
+    if (plane == 2 || !a.has_plane8) return BoundStages::bf16;
+    return plane == 1 || bound_auto(a, kRulesPlane8) ? BoundStages::plane8_first : BoundStages::bf16;
 }
 size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles) {
     return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)n_tiles * 64 * sizeof(uint32_t);
 }
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                              uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked, bool plane8_first) {
-    // (whether the path is TAKEN is plan_flat's decision; here only what the kernels need: metric, width, the copy, k — bound_scan_rule's "always")
-    if (!bound_scan_rule(rule_metric(v), v.dim, v.n_rows, 1, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    // (whether the path is TAKEN is plan_flat's decision; here only what the kernels need: metric, width, the copy, k)
+    if (!bound_scan_kernels_serve(bound_ask(v, 1, k, kBoundNoFilter)) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
     if (plane8_first && !v.plane8) return hipErrorInvalidValue;
     const uint32_t grid = p.grid;
     char* w = static_cast<char*>(d_ws);
@@ -1080,8 +1068,9 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
     const size_t lds1 = (size_t)v.dim * sizeof(float) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     const size_t lds8 = (size_t)v.dim * 2 + (size_t)kScanWaves * 64 * sizeof(uint64_t);
-    auto run = [&](auto Mc) -> hipError_t {
+    auto run = [&](auto Mc, auto Mk) -> hipError_t {
         constexpr int M = decltype(Mc)::value;
+        constexpr bool MASKED = decltype(Mk)::value;                  // under a filter every stage skips the tiles without a candidate, and the exact scan behind them walks the candidate bitmap
         // one stage on the control words c: its scan, the collect, the re-score.  gate: the flag of the stage in front (null: none);
         // next: the stage behind, whose flag an answering 8-bit stage clears; scan_gate: k_bound_scan's own gate argument (k_bound_scan8 has none)
         // (attrs: the dynamic LDS of a stage's two kernels, for every stage before anything is launched — a call that fails enqueues nothing)
@@ -1095,28 +1084,24 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
             hipLaunchKernelGGL(rescore, dim3(1), dim3(kScanBlock), lds2, s, v, d_query, k, c, cand, d_stats, d_rows_out, d_dist_out, gate, next);
         };
         const uint32_t* const no_gate = nullptr;
-        hipError_t e = masked ? attrs(k_bound_scan<M, true>, lds1, k_bound_rescore<M>) : attrs(k_bound_scan<M>, lds1, k_bound_rescore<M>);
-        if (e == hipSuccess && plane8_first) e = masked ? attrs(k_bound_scan8<M, true>, lds8, k_bound_rescore<M, true>) : attrs(k_bound_scan8<M>, lds8, k_bound_rescore<M, true>);
+        hipError_t e = attrs(k_bound_scan<M, MASKED>, lds1, k_bound_rescore<M>);
+        if (e == hipSuccess && plane8_first) e = attrs(k_bound_scan8<M, MASKED>, lds8, k_bound_rescore<M, true>);
         if (e != hipSuccess) return e;
-        if (plane8_first && masked) {
-            // the same two stages under a filter: both skip the tiles without a candidate, and the exact scan behind them walks the candidate bitmap
-            BoundCtrl* ctrl8 = ctrl + 1;
-            uint32_t* gate8 = &ctrl8->flag;
-            stage(k_bound_scan8<M, true>, lds8, k_bound_rescore<M, true>, ctrl8, (uint32_t*)nullptr, ctrl);
-            stage(k_bound_scan<M, true>, lds1, k_bound_rescore<M>, ctrl, gate8, (BoundCtrl*)nullptr, (const uint32_t*)gate8);
-        } else if (plane8_first) {
+        if (plane8_first) {
             // the 8-bit stage on the second set of control words, in the same workspace (the stages run one after the other); the bfloat16 stage
             // behind it is gated on that stage's flag and leaves at once when it has answered
             BoundCtrl* ctrl8 = ctrl + 1;
             uint32_t* gate8 = &ctrl8->flag;
-            stage(k_bound_scan8<M>, lds8, k_bound_rescore<M, true>, ctrl8, (uint32_t*)nullptr, ctrl);
-            stage(k_bound_scan<M>, lds1, k_bound_rescore<M>, ctrl, gate8, (BoundCtrl*)nullptr, (const uint32_t*)gate8);
-        } else if (masked) stage(k_bound_scan<M, true>, lds1, k_bound_rescore<M>, ctrl, (uint32_t*)nullptr, (BoundCtrl*)nullptr, no_gate);
-        else stage(k_bound_scan<M>, lds1, k_bound_rescore<M>, ctrl, (uint32_t*)nullptr, (BoundCtrl*)nullptr, no_gate);
+            stage(k_bound_scan8<M, MASKED>, lds8, k_bound_rescore<M, true>, ctrl8, (uint32_t*)nullptr, ctrl);
+            stage(k_bound_scan<M, MASKED>, lds1, k_bound_rescore<M>, ctrl, gate8, (BoundCtrl*)nullptr, (const uint32_t*)gate8);
+        } else stage(k_bound_scan<M, MASKED>, lds1, k_bound_rescore<M>, ctrl, (uint32_t*)nullptr, (BoundCtrl*)nullptr, no_gate);
         return hipSuccess;
     };
-    const hipError_t e = v.metric == QV_COSINE ? run(std::integral_constant<int, QV_COSINE>{})
-                       : v.metric == QV_DOT  ? run(std::integral_constant<int, QV_DOT>{}) : run(std::integral_constant<int, QV_L2>{});
+    auto run_metric = [&](auto Mk) -> hipError_t {
+        return v.metric == QV_COSINE ? run(std::integral_constant<int, QV_COSINE>{}, Mk)
+             : v.metric == QV_DOT  ? run(std::integral_constant<int, QV_DOT>{}, Mk) : run(std::integral_constant<int, QV_L2>{}, Mk);
+    };
+    const hipError_t e = masked ? run_metric(std::true_type{}) : run_metric(std::false_type{});
     if (e != hipSuccess) return e;
     *gate_out = &ctrl->flag;
     return hipGetLastError();
@@ -1156,9 +1141,6 @@ int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float*
     *out_res = bound8_row_res(bad, maxabs, n2, s2, dim);
     return 0;
 }
-int host_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8) {
-    return bound_scan8_rule(metric, dim, rows, nq, k, mode, plane_mode, has_plane8 != 0) ? 1 : 0;
-}
 
 // the shared pass of 2 - 8 queries: d_ws = bound_scan_mq_workspace_bytes, d_ctrl = kBoundMqMax BoundCtrl (zero, left zero).  The exact scan of the
 // queries handed back is part of it (launch_flat_redo_flagged, in the bytes the lower bounds leave behind): nothing is read on the host.
@@ -1173,9 +1155,9 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
     // k_bound_rescore_mq<., 1> — in front, in the same workspace (the stages run one after the other: the query terms lie where the float32 block goes, the scalars where
     // the norms go), and the bfloat16 stage's launches gated on the count of queries it handed on.
     // h_sets (optional, a HOST array of nq): query j restricted to alive & h_sets[j] — k_bound_scan_mq<., ., true> and the set-carrying redo.
-    // Null: the unfiltered pass.  (Whether the path is TAKEN is the caller's decision — plan_flat, or the row-set path's one question to
-    // bound_scan_applies_filtered; here only what the kernels need: metric, width, the copy, k, nq planes of lower bounds under 2 GiB.)
-    if (nq < 2 || !bound_scan_rule(rule_metric(v), v.dim, v.n_rows, nq, k, 1, v.plane != nullptr) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
+    // Null: the unfiltered pass.  (Whether the path is TAKEN is the caller's decision — plan_flat, or the row-set path's questions to
+    // bound_scan_decide; here only what the kernels need: metric, width, the copy, k, nq planes of lower bounds under 2 GiB.)
+    if (nq < 2 || !bound_scan_kernels_serve(bound_ask(v, nq, k, kBoundNoFilter)) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
     if (plane8_first && !v.plane8) return hipErrorInvalidValue;
     BoundSetTable tab;
     for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
@@ -1203,39 +1185,42 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
     uint32_t* hand = flags + kBound8MqHandWord;
     const uint32_t* gate = plane8_first ? hand + kBoundMqMax : nullptr;
     const uint32_t* hand_in = plane8_first ? hand : nullptr;
-#define QV_BOUND_MQ(MMM, QQ)                                                                                                 \
-    {                                                                                                                         \
-        const size_t lds1 = (size_t)kScanWaves * QQ * 64 * sizeof(uint64_t);                                                  \
-        e = set_lds(k_bound_rescore_mq<MMM>, lds2); if (e != hipSuccess) return e;                                            \
-        if (plane8_first) {                                                                                                   \
-            e = set_lds((k_bound_rescore_mq<MMM, 1>), lds2); if (e != hipSuccess) return e;                                   \
-            e = set_lds((k_bound_rescore_mq<MMM, 2>), lds2); if (e != hipSuccess) return e;                                   \
-            hipLaunchKernelGGL((k_bound_prep8_mq<QQ>), dim3(QQ), dim3(kScanBlock), 0, s, d_queries, nq, v.dim, reinterpret_cast<int8_t*>(qblk), qnorm, hand, d_stats); \
-            if (h_sets) hipLaunchKernelGGL((k_bound_scan8_mq<MMM, QQ, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, reinterpret_cast<const u4*>(qblk), qnorm, nq, k, lo_all, partial, tab); \
-            else hipLaunchKernelGGL((k_bound_scan8_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, reinterpret_cast<const u4*>(qblk), qnorm, nq, k, lo_all, partial, NoSets{}); \
-            e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s); if (e != hipSuccess) return e;             \
-            hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand, (const uint32_t*)nullptr); \
-            hipLaunchKernelGGL((k_bound_rescore_mq<MMM, 1>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, hand); \
-        }                                                                                                                     \
-        hipLaunchKernelGGL((k_bound_prep_mq<QQ>), dim3((v.dim * QQ + 255) / 256 + QQ), dim3(256), 0, s, d_queries, nq, v.dim, qblk, qnorm, d_stats, gate); \
-        if (h_sets) hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, tab, gate); \
-        else hipLaunchKernelGGL((k_bound_scan_mq<MMM, QQ>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, NoSets{}, gate); \
-        e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s, gate); if (e != hipSuccess) return e;           \
-        hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand, hand_in); \
-        if (plane8_first) hipLaunchKernelGGL((k_bound_rescore_mq<MMM, 2>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, hand); \
-        else hipLaunchKernelGGL((k_bound_rescore_mq<MMM>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, (uint32_t*)nullptr); \
-    }
-    if (v.metric == QV_COSINE) { if (nq <= 4) QV_BOUND_MQ(QV_COSINE, 4) else QV_BOUND_MQ(QV_COSINE, 8) }
-    else if (v.metric == QV_DOT) { if (nq <= 4) QV_BOUND_MQ(QV_DOT, 4) else QV_BOUND_MQ(QV_DOT, 8) }
-    else { if (nq <= 4) QV_BOUND_MQ(QV_L2, 4) else QV_BOUND_MQ(QV_L2, 8) }
-#undef QV_BOUND_MQ
+    auto run = [&](auto Mc, auto Qc, auto Sc) -> hipError_t {
+        constexpr int M = decltype(Mc)::value, QB = decltype(Qc)::value;
+        constexpr bool SETS = decltype(Sc)::value;
+        SetsArg<SETS> sets{};
+        if constexpr (SETS) sets = tab;
+        const size_t lds1 = (size_t)kScanWaves * QB * 64 * sizeof(uint64_t);
+        // (the dynamic LDS of every re-score before anything is launched)
+        e = set_lds(k_bound_rescore_mq<M>, lds2);
+        if (e == hipSuccess && plane8_first) e = set_lds((k_bound_rescore_mq<M, 1>), lds2);
+        if (e == hipSuccess && plane8_first) e = set_lds((k_bound_rescore_mq<M, 2>), lds2);
+        if (e != hipSuccess) return e;
+        if (plane8_first) {
+            hipLaunchKernelGGL((k_bound_prep8_mq<QB>), dim3(QB), dim3(kScanBlock), 0, s, d_queries, nq, v.dim, reinterpret_cast<int8_t*>(qblk), qnorm, hand, d_stats);
+            hipLaunchKernelGGL((k_bound_scan8_mq<M, QB, SETS>), dim3(grid), dim3(kScanBlock), lds1, s, v, reinterpret_cast<const u4*>(qblk), qnorm, nq, k, lo_all, partial, sets);
+            e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand, (const uint32_t*)nullptr);
+            hipLaunchKernelGGL((k_bound_rescore_mq<M, 1>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, hand);
+        }
+        hipLaunchKernelGGL((k_bound_prep_mq<QB>), dim3((v.dim * QB + 255) / 256 + QB), dim3(256), 0, s, d_queries, nq, v.dim, qblk, qnorm, d_stats, gate);
+        hipLaunchKernelGGL((k_bound_scan_mq<M, QB, SETS>), dim3(grid), dim3(kScanBlock), lds1, s, v, qblk, qnorm, nq, k, lo_all, partial, sets, gate);
+        e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s, gate);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_bound_collect_mq, dim3(cgrid, nq), dim3(256), 0, s, lo_all, n_pad, k, seed_rows, seed_dist, ctrl, cand, hand_in);
+        if (plane8_first) hipLaunchKernelGGL((k_bound_rescore_mq<M, 2>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, hand);
+        else hipLaunchKernelGGL((k_bound_rescore_mq<M>), dim3(nq), dim3(kScanBlock), lds2, s, v, d_queries, k, seed_rows, seed_dist, ctrl, cand, flags, d_stats, d_rows_out, d_dist_out, (uint32_t*)nullptr);
+        return hipSuccess;
+    };
+    auto run_sets = [&](auto Mc, auto Qc) -> hipError_t { return h_sets ? run(Mc, Qc, std::true_type{}) : run(Mc, Qc, std::false_type{}); };
+    auto run_qb = [&](auto Mc) -> hipError_t { return nq <= 4 ? run_sets(Mc, std::integral_constant<int, 4>{}) : run_sets(Mc, std::integral_constant<int, 8>{}); };
+    e = v.metric == QV_COSINE ? run_qb(std::integral_constant<int, QV_COSINE>{})
+      : v.metric == QV_DOT  ? run_qb(std::integral_constant<int, QV_DOT>{}) : run_qb(std::integral_constant<int, QV_L2>{});
+    if (e != hipSuccess) return e;
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_flat_redo_flagged(v, p, d_queries, nq, k, k, flags, redo_ws, d_rows_out, d_dist_out, s, h_sets);
 }
-int host_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles) {
-    return bound_scan_rule_filtered(metric, dim, rows, nq, k, mode, has_plane != 0, candidate_tiles) ? 1 : 0;
-}
-int host_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane) { return bound_scan_rule(metric, dim, rows, nq, k, mode, has_plane != 0) ? 1 : 0; }
 
 }  // namespace qv

@@ -53,7 +53,7 @@ struct IndexView {
     int       bound_plane_filtered; // qv_index_set_bound_plane_filtered: the same three values for a filtered single query, a knob of its own
     int       bound_plane_mq; // qv_index_set_bound_plane_mq: the same three values for an unfiltered shared pass of 2 - 8 queries, a knob of its own
     int       bound_plane_filtered_mq; // qv_index_set_bound_plane_filtered_mq: the same three values for a filtered shared pass of 2 - 8 queries, a knob of its own
-    int       l2_planes;  // a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE: the *_applies wrappers ask the rules as QV_RULE_L2_PLANES (0 on every other index)
+    int       l2_planes;  // a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE: bound_ask asks the rules as QV_RULE_L2_PLANES (0 on every other index)
 };
 
 struct GraphView {
@@ -144,16 +144,18 @@ hipError_t launch_fetch_rows(const IndexView& v, const uint32_t* d_rows, uint32_
 // d_tickets (optional): 64 zeroed words that belong to the caller's stream alone — with them a single query is ONE launch (the last
 // workgroup of the scan merges the lists); without, scan + k_merge_lists.
 // Which kernels answer the call is decided ONCE, by plan_flat, before the first launch (the batched path's plan_batched / BatchedRoute
-// is the model): the launch, the workspace sizes (qv_api.cpp) and the QV_TRACE lines read the plan.  The routes in priority order:
+// is the model): the launch, the workspace sizes (qv_api.cpp) and the QV_TRACE lines read the plan.  Whether the bound scan takes the call, and
+// with which stages, is ONE question to bound_scan_decide (below; qv_bound_scan.hip) inside plan_flat: its answer is the three bound routes and
+// FlatPass::plane8_first, and nothing behind the plan asks again.  The routes in priority order:
 enum class FlatRoute : int {
     small = 0,      // no bound route, tickets, flat_small_applies and not flat_split_applies: k_flat_scan_small, scan + merge in one launch
-    bound_mq,       // 2 - 8 queries, tickets and counters, the bound rule takes them (filtered: its filtered form), and "always" or no short-corpus
-                    // form: launch_bound_scan_mq, one pass over the bfloat16 copy, the exact redo of hand-backs behind it
+    bound_mq,       // 2 - 8 queries, tickets and counters, bound_scan_decide takes them, and "always" or no short-corpus form: launch_bound_scan_mq, one
+                    // pass over the bfloat16 copy (FlatPass::plane8_first: the 8-bit stage in front of it), the exact redo of hand-backs behind it
     split_mq,       // 2 or more queries, flat_split_mq_applies: k_flat_scan_split_mq + k_merge_lists
     mq64,           // 9 or more cosine / dot queries over 16 tiles per wave or more: launch_flat_scan_mq64 + k_merge_lists
     mq,             // 2 or more queries: k_flat_scan_mq, qb = 4 / 8 / 16 per corpus pass (16 never for the all-float32 metrics) + k_merge_lists
-    bound,          // one query, tickets and counters, the bound rule takes it: launch_bound_scan and the gated exact scan behind it
-    bound8_first,   // ... and bound_scan8_applies (unfiltered) or bound_scan8_applies_filtered (filtered): the 8-bit stage in front
+    bound,          // one query, tickets and counters, bound_scan_decide takes it: launch_bound_scan and the gated exact scan behind it
+    bound8_first,   // ... and answers BoundStages::plane8_first: the 8-bit stage in front
     split,          // tickets, flat_split_applies: k_flat_scan_split, a tile over eight waves
     fused,          // one query, tickets, more than one workgroup: k_flat_scan<., ., true>, the last workgroup merges
     two_launch,     // everything else: k_flat_scan + k_merge_lists
@@ -162,6 +164,7 @@ struct FlatPass {                   // what one pass over the corpus is launched
     FlatRoute route = FlatRoute::two_launch;
     uint32_t  qb = 0;               // queries per corpus pass (bound_mq, split_mq, mq)
     bool      filtered = false;     // v.alive is a filter's candidate bitmap: the bound routes' forms that skip tiles without a candidate
+    bool      plane8_first = false; // bound_mq and bound8_first: the 8-bit stage in front of the bfloat16 stage (for one query the route's number says it too)
 };
 struct FlatPlan : FlatPass {        // the call's pass; mq64 with more than 32 queries of which the last 1 - 8 are split off: the pass of
     uint32_t rem = 0;               // the first nq - rem, and the pass of the last rem behind it (never a bound route)
@@ -185,15 +188,34 @@ hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const FlatPla
 // ... for callers without tickets (the batched path's sample scan): routes split_mq, mq64, mq or two_launch
 hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k,
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+struct RowSetRef;
+constexpr uint32_t kBoundNoFilter = 0xFFFFFFFFu;   // candidate_tiles of an unfiltered search
+// WHICH stages answer a call is one decision, bound_scan_decide (qv_bound_scan.hip), for all forms of the bound scan: one query or a shared pass of
+// 2 - 8, unfiltered or under a filter, the bfloat16 stage alone or the 8-bit stage (k_bound_scan8 / k_bound_scan8_mq) in front of it.  plan_flat
+// asks it once per call and records the answer in the plan; the row-set front (qv_api.cpp: rowsets_plan) asks it for its own pieces; the
+// qv_scan_bound*_applies exports are views of it.  The launchers only check what their kernels need (bound_scan_kernels_serve).
+struct BoundAsk {                 // the call, as the rules see it
+    int rule_metric;              // the index's metric; QV_RULE_L2_PLANES for a QV_L2 index that holds the planes
+    uint32_t dim, n_rows, nq, k;
+    uint32_t candidate_tiles;     // kBoundNoFilter, or the tiles that hold a candidate of any query of the pass (an upper bound known on the host)
+    bool has_plane, has_plane8;   // the bfloat16 copy / the 8-bit plane is held
+};
+enum BoundForm { bound_one = 0, bound_one_filtered, bound_mq, bound_mq_filtered };   // follows from nq and candidate_tiles; each has a plane knob of its own
+inline BoundForm bound_form(const BoundAsk& a) { return (BoundForm)((a.nq > 1 ? 2 : 0) + (a.candidate_tiles != kBoundNoFilter ? 1 : 0)); }
+struct BoundKnobs {               // host only.  0: the environment variable decides (read once), else automatic — the measured floors
+    int scan;                     // qv_index_set_bound_scan / QV_BOUND_SCAN: 1 whenever the kernels serve the call, 2 never
+    int plane[4];                 // by BoundForm: qv_index_set_bound_plane, _filtered, _mq, _filtered_mq / QV_BOUND_PLANE, _FILTERED, _MQ, _FILTERED_MQ:
+};                                // 1 the 8-bit stage first whenever the bound scan takes the call and the plane is held, 2 never
+enum class BoundStages { none, bf16, plane8_first };
+BoundStages bound_scan_decide(const BoundAsk& a, const BoundKnobs& knobs);
+bool bound_scan_kernels_serve(const BoundAsk& a);   // the kernels' own limits: metric, k, 1 - 8 queries, the copy, whole 16-dimension steps, 8 tiles, lower bounds under 2 GiB
+BoundAsk bound_ask(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
+BoundKnobs bound_knobs(const IndexView& v);
+int bound_scan_mode(int mode);   // the mode in force: the index's own, else QV_BOUND_SCAN (read once)
 // The single-query scan on the bfloat16 copy (qv_bound_scan.hip): stage 1 streams v.plane and lists the rows whose certified lower bound of
 // the distance is within the k-th smallest upper bound, stage 2 computes those rows' distances in the scan's own arithmetic and writes
 // the k results, or sets *gate (a device word) when the exact scan must answer instead; the caller then issues the exact scan with that
 // gate (it leaves at once when the word is zero).  d_ctrl: the stream's zeroed control words (kept zero); d_stats: the index's counters.
-struct RowSetRef;
-constexpr uint32_t kBoundNoFilter = 0xFFFFFFFFu;   // candidate_tiles of an unfiltered search
-bool bound_scan_applies(const IndexView& v, uint32_t nq, uint32_t k);
-// ... under a filter (candidate_tiles: the tiles that hold a candidate of any query of the pass, an upper bound known on the host)
-bool bound_scan_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
 size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles);
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                              uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s,
@@ -206,34 +228,8 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
                                 uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
                                 const RowSetRef* h_sets = nullptr,   // a HOST array of nq sets, at most 8: query j over alive & h_sets[j] (k_bound_scan_mq<., ., true>, the redo included)
                                 bool plane8_first = false);   // the 8-bit stage (k_bound_scan8_mq; with h_sets its set form) in front, the bfloat16 stage's launches gated behind it
-// bound_scan_applies without an index (qv_scan_bound_applies): mode 0 = automatic (QV_BOUND_SCAN decides), 1 always, 2 never
-bool bound_scan_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane);
-int bound_scan_mode(int mode);   // the mode in force: the index's own, else QV_BOUND_SCAN (read once)
-int host_bound_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane);
-bool bound_scan_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, bool has_plane, uint32_t candidate_tiles);
-int host_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles);
 // the interval of one row on the HOST (qv_scan_bound_interval): qv_bound.h's function compiled for the CPU; 1 = a row the bound says nothing about
 int host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi);
-// The 8-bit stage in front of it (k_bound_scan8): the same chain over v.plane8; a search it cannot decide goes to the bfloat16 stage, which
-// runs gated behind it.  plane_mode: QV_BOUND_PLANE_* (0 automatic: QV_BOUND_PLANE decides, 1 the 8-bit stage whenever it applies, 2 never).
-bool bound_scan8_rule(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode, bool has_plane8);
-bool bound_scan8_applies(const IndexView& v, uint32_t nq, uint32_t k);
-int host_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8);
-// ... in front of a filtered single query (k_bound_scan8<., true>): the filtered bound rule's yes, the plane, and a mode of its own
-// (QV_BOUND_PLANE_* again; 0 automatic: QV_BOUND_PLANE_FILTERED decides)
-bool bound_scan8_rule_filtered(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, bool has_plane8, uint32_t candidate_tiles);
-bool bound_scan8_applies_filtered(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
-int host_bound8_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered, int has_plane8, uint32_t candidate_tiles);
-// ... in front of an unfiltered shared pass of 2 - 8 queries (k_bound_scan8_mq): the bound rule's yes for that nq, the plane, and a mode of
-// its own (QV_BOUND_PLANE_* again; 0 automatic: QV_BOUND_PLANE_MQ decides).  A decision inside route bound_mq, as the plane is inside route 5 / 6.
-bool bound_scan8_rule_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, bool has_plane8);
-bool bound_scan8_applies_mq(const IndexView& v, uint32_t nq, uint32_t k);
-int host_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_mq, int has_plane8);
-// ... in front of a FILTERED shared pass of 2 - 8 queries (k_bound_scan8_mq<., ., true>): the filtered bound rule's yes for that nq and those
-// candidate tiles, the plane, and a mode of its own (QV_BOUND_PLANE_* again; 0 automatic: QV_BOUND_PLANE_FILTERED_MQ decides)
-bool bound_scan8_rule_filtered_mq(int metric, uint32_t dim, uint32_t n_rows, uint32_t nq, uint32_t k, int mode, int plane_mode_fmq, bool has_plane8, uint32_t candidate_tiles);
-bool bound_scan8_applies_filtered_mq(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
-int host_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_fmq, int has_plane8, uint32_t candidate_tiles);
 int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, float* d_lo, float* d_hi);
 int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res);
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches

@@ -998,10 +998,8 @@ bool flat_split_mq_applies(const IndexView& v, uint32_t nq, uint32_t k) {
 }
 // ---------------------------------------------------------------- which kernels answer a fused flat search: decided once --
 // plan_flat is the ONE statement of the priority order (FlatRoute, qv_device.h); the launch below, the workspace sizes and the trace
-// lines read the plan.  The knobs are read once per process (all but QV_BOUND_SCAN / QV_BOUND_PLANE in the measurement build only).
-static bool bound_scan_takes(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
-    return candidate_tiles == kBoundNoFilter ? bound_scan_applies(v, nq, k) : bound_scan_applies_filtered(v, nq, k, candidate_tiles);
-}
+// lines read the plan — the bound scan's stages included: bound_scan_decide (qv_bound_scan.hip) is asked here, once per call, and nowhere
+// behind.  The knobs are read once per process (all but QV_BOUND_SCAN / QV_BOUND_PLANE* in the measurement build only).
 static int mq_min_queries() { static const int mq_min = dev_env_int("QV_MQ_MIN", 2); return mq_min; }   // nq >= this: queries share a corpus pass
 static int mq_qb_forced() { static const int qb = dev_env_int("QV_MQ_QB", 0); return qb; }
 // A pass of n queries that carries no tickets (routes 3, 4 and 8): the short-corpus form, the f64 matrix cores, or QB queries per corpus
@@ -1026,13 +1024,14 @@ FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t 
     f.filtered = candidate_tiles != kBoundNoFilter;                  // v.alive is a filter's candidate bitmap: one for all queries of the call
     // QV_SCAN_FUSE=0 keeps the two launches of a single query, for measurements
     static const int fuse = dev_env_int("QV_SCAN_FUSE", 1);
-    const bool bound_takes = tickets && stats && bound_scan_takes(v, nq, k, candidate_tiles);
+    const BoundStages stages = tickets && stats ? bound_scan_decide(bound_ask(v, nq, k, candidate_tiles), bound_knobs(v)) : BoundStages::none;
+    const bool bound_takes = stages != BoundStages::none;
     // 1. a small collection: scan + merge in one launch
     if (!bound_takes && tickets && flat_small_applies(v, nq, k) && !flat_split_applies(v, nq, k)) { f.route = FlatRoute::small; return f; }
     if ((int)nq >= mq_min_queries()) {
         // 2. 2 - 8 queries sharing one pass over the bfloat16 copy (forced on, it goes ahead of the short-corpus form; on its own it leaves that form its shapes)
         if (nq >= 2 && bound_takes && (bound_scan_mode(v.bound_scan) == 1 || !flat_split_mq_applies(v, nq, k))) {
-            f.route = FlatRoute::bound_mq; f.qb = nq <= 4 ? 4u : 8u;
+            f.route = FlatRoute::bound_mq; f.qb = nq <= 4 ? 4u : 8u; f.plane8_first = stages == BoundStages::plane8_first;
             return f;
         }
         // 3. / 4.  A last pass of 8 queries or fewer costs a whole 32-query pass of the matrix kernel (1.15 ms at 1M x 768) but only an
@@ -1046,11 +1045,11 @@ FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t 
         f.route = head.route; f.qb = head.qb;
         return f;
     }
-    // 5. one query: the bound scan on the bfloat16 copy (the 8-bit stage first where its rule — the unfiltered or the filtered one — says so),
-    // its exact re-score, and the exact scan behind them that runs only when they hand the query back
+    // 5. one query: the bound scan on the bfloat16 copy (the 8-bit stage first where the decision says so), its exact re-score, and the
+    // exact scan behind them that runs only when they hand the query back
     if (nq == 1 && bound_takes && p.grid > 1) {
-        const bool first8 = f.filtered ? bound_scan8_applies_filtered(v, nq, k, candidate_tiles) : bound_scan8_applies(v, nq, k);
-        f.route = first8 ? FlatRoute::bound8_first : FlatRoute::bound;
+        f.plane8_first = stages == BoundStages::plane8_first;
+        f.route = f.plane8_first ? FlatRoute::bound8_first : FlatRoute::bound;
         return f;
     }
     // 6. a short corpus of wide rows: a tile over eight waves
@@ -1084,8 +1083,7 @@ struct FlatCall {
     uint32_t* d_tickets; uint32_t* done_flag; uint32_t done_seq; bool* flag_used; uint32_t* d_bound_stats; uint32_t candidate_tiles;
 };
 static hipError_t route_bound_mq(const IndexView& v, const ScanPlan& p, const FlatPass& f, const FlatCall& c) {
-    // the plane: a decision inside the route, as first8 is for routes 5 / 6 (a masked pass: the filtered shared pass's own rule and knob)
-    const bool plane8_first = f.filtered ? bound_scan8_applies_filtered_mq(v, c.nq, c.k, c.candidate_tiles) : bound_scan8_applies_mq(v, c.nq, c.k);
+    const bool plane8_first = f.plane8_first;                         // the plane: a bit of the plan inside the route, where routes 5 / 6 are two numbers
     if (!f.filtered && trace_unfiltered()) {
         if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8_mq QB=%d + k_merge_lists + k_bound_collect_mq + k_bound_rescore_mq, then gated k_bound_scan_mq + k_merge_lists + k_bound_collect_mq + k_bound_rescore_mq (nq=%u, tiles=%u)\n", (int)f.qb, c.nq, v.n_tiles);
         else fprintf(stderr, "qv: scan kernel = k_bound_scan_mq QB=%d (nq=%u, tiles=%u)\n", (int)f.qb, c.nq, v.n_tiles);
@@ -1166,7 +1164,7 @@ static hipError_t route_mq(const IndexView& v, const ScanPlan& p, uint32_t qb, c
 static hipError_t route_bound(const IndexView& v, const ScanPlan& p, const FlatPass& f, const FlatCall& c) {
     const uint32_t k = c.k;
     hipStream_t s = c.s;
-    const bool plane8_first = f.route == FlatRoute::bound8_first;    // the 8-bit stage first; the bfloat16 stage gated behind it
+    const bool plane8_first = f.plane8_first;                        // (route bound8_first) the 8-bit stage first; the bfloat16 stage gated behind it
     const size_t lds = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     if (f.filtered) {
         if (!trace_filtered()) {}

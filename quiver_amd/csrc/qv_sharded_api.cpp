@@ -912,21 +912,17 @@ int qv_sharded_bound_scan_stats(qv_sharded* s, uint64_t out[4]) {
     return QV_OK;
 }
 
-int qv_sharded_set_bound_plane(qv_sharded* s, int mode) {
+// a plane knob on every shard (the filtered forms' knobs have no sharded setter)
+static int set_bound_plane(qv_sharded* s, int (*set)(qv_index*, int), int mode) {
     if (!s) return fail(QV_ERR_INVALID_ARG, "handle is null");
     std::unique_lock<std::shared_mutex> l(s->mu);
     reap_retired(s);
-    for (auto& x : s->sh) { const int rc = qv_index_set_bound_plane(x.idx, mode); if (rc != QV_OK) return rc; }
+    for (auto& x : s->sh) { const int rc = set(x.idx, mode); if (rc != QV_OK) return rc; }
     return QV_OK;
 }
+int qv_sharded_set_bound_plane(qv_sharded* s, int mode) { return set_bound_plane(s, qv_index_set_bound_plane, mode); }
 
-int qv_sharded_set_bound_plane_mq(qv_sharded* s, int mode) {
-    if (!s) return fail(QV_ERR_INVALID_ARG, "handle is null");
-    std::unique_lock<std::shared_mutex> l(s->mu);
-    reap_retired(s);
-    for (auto& x : s->sh) { const int rc = qv_index_set_bound_plane_mq(x.idx, mode); if (rc != QV_OK) return rc; }
-    return QV_OK;
-}
+int qv_sharded_set_bound_plane_mq(qv_sharded* s, int mode) { return set_bound_plane(s, qv_index_set_bound_plane_mq, mode); }
 
 int qv_sharded_bound_scan8_stats(qv_sharded* s, uint64_t out[4]) {
     if (!s || !out) return fail(QV_ERR_INVALID_ARG, "handle/out is null");

@@ -401,29 +401,33 @@ class DeviceIndex:
 
     BOUND_PLANE = {"auto": 0, "8bit": 1, "bf16": 2}
 
+    def _set_bound_plane(self, form, mode):
+        """one of the four plane knobs: form "" / "_filtered" / "_mq" / "_filtered_mq" names its setter (qv_index_set_bound_plane*)"""
+        check(getattr(lib(), "qv_index_set_bound_plane" + form)(self._h, self.BOUND_PLANE.get(mode, mode)))
+
     def set_bound_plane(self, mode):
         """which plane a single unfiltered query's bound scan starts on: "auto" (the 8-bit plane from its measured shapes on), "8bit"
         (whenever the bound scan takes the search and the plane is held), "bf16" (qv_index_set_bound_plane)"""
-        check(lib().qv_index_set_bound_plane(self._h, self.BOUND_PLANE.get(mode, mode)))
+        self._set_bound_plane("", mode)
 
     def set_bound_plane_filtered(self, mode):
         """which plane a single FILTERED query's bound scan starts on (search_masked, search_rowsets, search_where and their device forms):
         "auto" (the measured shapes), "8bit" (whenever the filtered bound scan takes the search and the plane is held), "bf16"; a knob of
         its own, independent of set_bound_plane (qv_index_set_bound_plane_filtered)"""
-        check(lib().qv_index_set_bound_plane_filtered(self._h, self.BOUND_PLANE.get(mode, mode)))
+        self._set_bound_plane("_filtered", mode)
 
     def set_bound_plane_mq(self, mode):
         """which plane an unfiltered SHARED PASS of 2 - 8 queries starts on (search / search_device with 2 - 8 queries, the passes concurrent
         single-query callers share): "auto" (the measured shapes), "8bit" (whenever the bound scan takes the pass and the plane is held),
         "bf16"; a knob of its own, independent of set_bound_plane and set_bound_plane_filtered (qv_index_set_bound_plane_mq)"""
-        check(lib().qv_index_set_bound_plane_mq(self._h, self.BOUND_PLANE.get(mode, mode)))
+        self._set_bound_plane("_mq", mode)
 
     def set_bound_plane_filtered_mq(self, mode):
         """which plane a FILTERED shared pass of 2 - 8 queries starts on (search_masked, search_rowsets, search_where and their device forms
         with 2 - 8 queries, the passes that concurrent row-set or where-filter callers share): "auto" (the measured shapes), "8bit" (whenever
         the filtered bound scan takes the pass and the plane is held), "bf16"; a knob of its own, independent of set_bound_plane,
         set_bound_plane_filtered and set_bound_plane_mq (qv_index_set_bound_plane_filtered_mq)"""
-        check(lib().qv_index_set_bound_plane_filtered_mq(self._h, self.BOUND_PLANE.get(mode, mode)))
+        self._set_bound_plane("_filtered_mq", mode)
 
     def bound_scan8_stats(self) -> dict:
         """survivors of the last 8-bit stage, searches it handed on to the bfloat16 stage, searches that took it, whether the plane exists"""

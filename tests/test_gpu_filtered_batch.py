@@ -13,6 +13,7 @@ import pytest
 
 import quiver_amd
 from quiver_amd import QvError
+from quiver_amd.device_index import broadcast_filters, pack_where
 from tests import _oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -261,15 +262,30 @@ def test_concurrent_callers_share_filtered_batches():
     idx = c.idx
     want = [c.oracle(t, k, c.masks[t] if t % 2 == 0 else c.wmasks[t]) for t in range(threads)]
 
+    # Every caller packs its arguments and result arrays ONCE and then calls the C ABI itself, as search_rowsets / search_where do per call:
+    # between two calls it holds the interpreter for microseconds.  Through the wrappers a call costs tens of microseconds of interpreter
+    # time, one caller at a time, against a pass of about a hundred: the callers then reach the front a few per pass, and a group above 8
+    # formed only behind a fresh index's first, slow pass — in 11 of 12 fresh indexes, and in none of 40 later storms (measured).  Called
+    # directly, each of 16 storms on 4 indexes held 9 - 19 batched groups.
     def storm():
         out, errs = {}, []
         gate = threading.Barrier(threads)
 
         def caller(t):
             try:
+                q = np.ascontiguousarray(c.qs[t:t + 1], dtype=np.float32)
+                if t % 2 == 0:
+                    fn, (arr, keep) = quiver_amd.lib().qv_index_search_rowsets, idx._set_handles(c.sets[t], 1)
+                else:
+                    fn, (arr, keep) = quiver_amd.lib().qv_index_search_where, pack_where(broadcast_filters([c.filters[t]], 1))
+                res = [(np.full((1, k), 0xFFFFFFFF, np.uint32), np.full((1, k), np.inf, np.float32), np.zeros(1, np.uint32)) for _ in range(calls)]
+                args = [(idx._h, q.ctypes.data, 1, k, arr, r.ctypes.data, d.ctypes.data, n_found.ctypes.data) for r, d, n_found in res]
                 gate.wait()
                 for it in range(calls):
-                    out[(t, it)] = idx.search_rowsets(c.qs[t:t + 1], k, c.sets[t]) if t % 2 == 0 else idx.search_where(c.qs[t:t + 1], k, [c.filters[t]])
+                    rc = fn(*args[it])
+                    assert rc == 0, (t, it, rc)
+                    out[(t, it)] = res[it]
+                del keep                                                  # (what arr points into, alive across the calls)
             except Exception as e:                                        # noqa: BLE001
                 errs.append(e)
         th = [threading.Thread(target=caller, args=(t,)) for t in range(threads)]
