@@ -433,6 +433,23 @@ int qv_index_filtered_batch_stats(qv_index* idx, uint64_t out[4]);
  * for one tile-aligned set named by every query, which these arguments cannot tell apart; 10M rows and 128 dimensions are
  * unmeasured.  So AUTO takes nothing yet: ask for the path with QV_FILTERED_BATCH_ALWAYS.  Monotone in n_not_sparse. */
 int qv_batched_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse);
+/* Which main filter kernel a FILTERED batch of that shape launches, without an index or a device: the batched path's plan for (metric,
+ * dim, rows, nq, k, filter), then the substitution a batch with sets applies where the planned kernel has no variant that tests the
+ * sets (the register-resident one: the bfloat16-copy kernel or the 256-row eight-wave kernel instead).  has_bf16_plane: the index was
+ * created with QV_FLAG_BF16_ROWS; cus: the device's compute units (the kernel chosen does not depend on them).  *nq_pad: the query
+ * count the batch is padded to (64, 128 or a multiple of 256); *kernel: one of QV_BATCHED_FILTER_*.  Environment switches read once
+ * per process apply as they do to a search.  QV_ERR_UNSUPPORTED where no filtered batch runs: k > 64, too few queries or rows for the
+ * batched path, a metric it does not take, QV_FILTER_OFF.  For tests and reports: says nothing about mode or the sparse floor. */
+#define QV_BATCHED_FILTER_MFMA_F32      0   /* float32 matrix-core chain (QV_FILTER_FP32) */
+#define QV_BATCHED_FILTER_BF16X3        1   /* three bfloat16 terms, a wave per query block: up to 128 padded queries, or a one-term shape no other kernel takes */
+#define QV_BATCHED_FILTER_BF16X3_SHARED 2   /* three bfloat16 terms, whole workgroups of 256 queries sharing rows */
+#define QV_BATCHED_FILTER_BF16ROWS      3   /* one term on the index's bfloat16 copy, whole workgroups */
+#define QV_BATCHED_FILTER_W8X2          4   /* one term on float32 rows, eight waves, 256 rows per round */
+#define QV_BATCHED_FILTER_W8X2_PADDED   5   /* the same with zero-padded steps: dimensions its loop does not divide */
+#define QV_BATCHED_FILTER_Q64_PLANE     6   /* one term, one block of 64 queries, on the bfloat16 copy */
+#define QV_BATCHED_FILTER_Q64_F32_ROWS  7   /* one term, one block of 64 queries, on float32 rows */
+int qv_batched_filter_route(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_bf16_plane, int cus,
+                            uint32_t* nq_pad, int* kernel);
 /* What the batched path's plan chose for the sample of a batch of nq queries, k results: its rows; the step of its 128-row groups —
  * sample position i is row (i / 128) * group_step * 128 + i % 128 of the corpus; and the rank its bound is taken at (k, or more under
  * a guessed bound).  QV_ERR_UNSUPPORTED when this index has no such route.  For tests and reports. */

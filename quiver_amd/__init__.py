@@ -48,5 +48,17 @@ def batched_applies_filtered(metric, dim: int, rows: int, nq: int, k: int, filte
     return rc == 1
 
 
+def batched_filter_route(metric, dim: int, rows: int, nq: int, k: int, filter="auto", bf16_rows: bool = False, cus: int = 256):
+    """(padded query count, main filter kernel) of a FILTERED batch of that shape — the batched path's plan and the substitution a batch with
+    sets applies, on the host, without an index or a device (qv_batched_filter_route); the kernel as a name of DeviceIndex.BATCHED_FILTERS;
+    filter: as set_filter takes it; bf16_rows: the index keeps the bfloat16 copy of its rows.  QvError (unsupported) where no filtered batch runs"""
+    import ctypes as C
+    from ._lib import check
+    m = metric_id(metric) if isinstance(metric, str) else int(metric)
+    pad, code = C.c_uint32(0), C.c_int(-1)
+    check(lib().qv_batched_filter_route(m, dim, rows, nq, k, DeviceIndex.FILTERS.get(filter, filter), 1 if bf16_rows else 0, cus, C.byref(pad), C.byref(code)))
+    return int(pad.value), DeviceIndex.BATCHED_FILTERS[code.value]
+
+
 __all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq", "scan_bound8_applies_filtered_mq",
-           "batched_applies_filtered"]
+           "batched_applies_filtered", "batched_filter_route"]

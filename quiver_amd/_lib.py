@@ -97,6 +97,7 @@ PROTOTYPES = {
     "qv_index_set_filtered_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "qv_index_filtered_batch_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_batched_applies_filtered": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32]),
+    "qv_batched_filter_route": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, _u32p, C.POINTER(C.c_int)]),
     "qv_batched_sample_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
     "qv_sharded_set_filter": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_set_bound_scan": (C.c_int, [C.c_void_p, C.c_int]),

@@ -1332,7 +1332,12 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
         const uint32_t* flags = static_cast<const uint32_t*>(c->h_ids.p);
         std::vector<uint32_t> redo;
         uint64_t n_sparse = 0;
-        for (uint32_t q = 0; q < nq; q++) if (flags[q] || flags[nq + q]) { redo.push_back(q); n_sparse += flags[nq + q] ? 1 : 0; }
+        for (uint32_t q = 0; q < nq; q++) {
+            // (k_sets_sparse flags a sparse query in both arrays: the redo flags alone say which answers are not final, also to the kernels
+            // behind the filter — a sparse flag without its redo flag is a broken batch, not something to paper over here)
+            if (flags[nq + q] && !flags[q]) return fail(QV_ERR_DEVICE, "filtered batch: query %u is flagged sparse but not for the redo", q);
+            if (flags[q]) { redo.push_back(q); n_sparse += flags[nq + q] ? 1 : 0; }
+        }
         idx->fb_stats[0] += nq; idx->fb_stats[1] += redo.size() - n_sparse; idx->fb_stats[2] += n_sparse; idx->fb_stats[3] += 1;
         if (!redo.empty()) {
             const uint32_t nr = (uint32_t)redo.size();
@@ -1789,6 +1794,15 @@ int qv_batched_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_
     if (mode < 0 || mode > QV_FILTERED_BATCH_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
     if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
     return qv::filtered_batch_rule(metric, dim, rows, nq, k, filter, mode, std::min(n_not_sparse, nq)) ? 1 : 0;
+}
+
+int qv_batched_filter_route(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_bf16_plane, int cus, uint32_t* nq_pad, int* kernel) {
+    if (!nq_pad || !kernel) return fail(QV_ERR_INVALID_ARG, "nq_pad/kernel is null");
+    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
+    if (cus < 1) return fail(QV_ERR_INVALID_ARG, "cus must be positive; got %d", cus);
+    if (!qv::batched_sets_filter(metric, dim, rows, nq, k, filter, has_bf16_plane != 0, cus, nq_pad, kernel))
+        return fail(QV_ERR_UNSUPPORTED, "no filtered batched route for %u queries, k %u over %llu rows of %u dimensions", nq, k, (unsigned long long)rows, dim);
+    return QV_OK;
 }
 
 int qv_batched_sample_plan(qv_index* idx, uint32_t nq, uint32_t k, uint32_t* sample_rows, uint32_t* group_step, uint32_t* rank) {

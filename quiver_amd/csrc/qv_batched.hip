@@ -161,6 +161,7 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
     if (threadIdx.x == 0 && (what & 2)) {
         float c_ = __uint_as_float(0x7F800000u), m_ = 0.f, b_ = 0.f;       // padded queries: +inf threshold, nothing passes
         float ea_ = 0.f, eb_ = 0.f;
+        bool given_up = false;
         if (q < nq) {
             const double qn = __builtin_sqrt(n2);
             // |S~ - S| <= ea |r| + eb |r - rh|: per query what the filter's scores can be off by (one-term filter: the query's own
@@ -195,19 +196,26 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
                 c = n2 * (1.0 - 2e-6) - T;                           // A_q; test: 2S~ >= A_q + (1-2e-6)|r|^2 - B_q|r| - 2 eb |r - rh|
                 m = 2.0 * (ea + 1e-6 * qn);                          // B_q
                 b_ = f32_up((float)(2.0 * eb));
-                if (!(U == U) || U > 1.0e18 || qn < (double)filter_tiny_norm(dim) || !(qn < 1.0e18)) { c = -3.0e38; m = 0.0; b_ = 0.f; }   // (a query norm >= 1e18 or NaN: its float32 scores may overflow)
+                if (!(U == U) || U > 1.0e18) { c = -3.0e38; m = 0.0; b_ = 0.f; }
             } else {
                 c = metric == QV_COSINE ? (1.0 - U - 4e-7) * qn : (1.0 - U - 4e-7 * (1.0 + __builtin_fabs(U)));
                 m = ea + 1e-6 * qn;
                 b_ = f32_up((float)eb);
-                if (!(U == U) || U > 3.0e38 || qn < (double)filter_tiny_norm(dim) || !(qn < 1.0e18)) { c = -3.0e38; m = 0.0; b_ = 0.f; }   // no bound: everything is a candidate (overflow -> exact path); bf16 operands below 2^-126 flush
+                if (!(U == U) || U > 3.0e38) { c = -3.0e38; m = 0.0; b_ = 0.f; }   // no bound: everything is a candidate (overflow -> exact path)
             }
             c_ = f32_down((float)c);                                         // round towards "keep more"
             m_ = f32_up((float)m);
+            // A query the norm guard gives up on — a norm that is NaN, infinite, >= 1e18 (its float32 scores may overflow) or below
+            // filter_tiny_norm (bf16 operands below 2^-126 flush) — has scores that say nothing: -inf and NaN among them, which no
+            // threshold lets through, and the rows they belong to may be in its answer.  "Everything is a candidate" used to hand it
+            // back by overflowing its list, which a set of fewer rows than the list has slots (or an index of few live rows) does not
+            // do: such a query then lost the rows whose score was -inf.  It is handed back HERE, with the padded queries' constants.
+            given_up = qn < (double)filter_tiny_norm(dim) || !(qn < 1.0e18);
+            if (given_up) { c_ = __uint_as_float(0x7F800000u); m_ = 0.f; b_ = 0.f; }
         }
         cq[q] = c_; mq[q] = m_; mq[nq_pad + q] = b_;
         eq[2 * q] = ea_; eq[2 * q + 1] = eb_;
-        if (q < nq) { cand_cnt[q] = 0; overflow[q] = 0; }
+        if (q < nq) { cand_cnt[q] = 0; overflow[q] = given_up ? 1u : 0u; }
     }
 }
 
@@ -2679,6 +2687,44 @@ bool batched_sets_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus
     BatchedRoute r;
     return k >= 1 && k <= (uint32_t)kMaxFusedK && batched_supported(v, nq, k) && plan_batched(v, nq, k, cus, true, r) && batched_sets_route(r);
 }
+// The register-resident kernel has no flush variant (its instantiations are many: three operand splits, both row forms): a filtered
+// batch of whole workgroups takes what plan_batched chooses where that kernel does not apply.  Shared by launch_batched and
+// batched_sets_filter, so that what the latter reports is what the former launches.
+static void batched_sets_remap(BatchedRoute& r) {
+    if (r.filter != MainFilter::qreg) return;
+    const uint32_t nqb64 = r.nq_pad / 64;
+    if (r.bfrows) { r.filter = MainFilter::bf16rows; r.filter_grid = grid_multiple(2 * (uint32_t)r.cus, nqb64 / 4); }
+    else r.filter = MainFilter::w8x2;
+}
+// an index's shape as the rules that take no index see it (filtered_batch_rule, batched_sets_filter); plane: it keeps the bfloat16 copy the
+// batched filter reads (QV_FLAG_BF16_ROWS) — the plan asks only whether there is one, so the view carries a marker that nothing reads through
+static IndexView shape_view(int metric, uint32_t dim, uint64_t rows, int filter, bool plane = false) {
+    static uint16_t plane_marker;
+    IndexView v{};
+    v.metric = metric; v.dim = dim; v.dim4 = (dim + 3) / 4; v.n_rows = (uint32_t)rows; v.n_tiles = (uint32_t)((rows + 63) / 64); v.filter = filter;
+    v.bf16 = plane ? &plane_marker : nullptr;
+    return v;
+}
+bool batched_sets_filter(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool plane, int cus, uint32_t* nq_pad, int* code) {
+    if (rows == 0 || rows > 0xFFFFFFFFull || dim == 0 || cus < 1) return false;
+    const IndexView v = shape_view(metric, dim, rows, filter, plane);
+    BatchedRoute r;
+    if (k < 1 || k > (uint32_t)kMaxFusedK || !batched_supported(v, nq, k) || !plan_batched(v, nq, k, cus, true, r) || !batched_sets_route(r)) return false;
+    batched_sets_remap(r);
+    switch (r.filter) {                                     // the codes of include/qv.h (QV_BATCHED_FILTER_*)
+        case MainFilter::mfma_f32:      *code = 0; break;
+        case MainFilter::bf16x3:        *code = 1; break;
+        case MainFilter::bf16x3_shared: *code = 2; break;
+        case MainFilter::bf16rows:      *code = 3; break;
+        case MainFilter::w8x2:          *code = 4; break;
+        case MainFilter::w8x2_padded:   *code = 5; break;
+        case MainFilter::q64_plane:     *code = 6; break;
+        case MainFilter::q64_f32_rows:  *code = 7; break;
+        default: return false;                              // (the measurement build's shapes have no flush variant: batched_filter refuses them)
+    }
+    *nq_pad = r.nq_pad;
+    return true;
+}
 bool batched_sample_plan(const IndexView& v, uint32_t nq, uint32_t k, int cus, uint32_t* sample_rows, uint32_t* gstep, uint32_t* rank) {
     BatchedRoute r;
     if (nq == 0 || k == 0 || k > (uint32_t)kMaxBatchedK || !plan_batched(v, nq, k, cus, true, r) || r.sample == SampleScores::exact_scan) return false;
@@ -2706,8 +2752,7 @@ bool filtered_batch_rule(int metric, uint32_t dim, uint64_t rows, uint32_t nq, u
     mode = filtered_batch_mode(mode);
     if (mode == 2 || nq < kFilteredBatchMinQueries || n_not_sparse < kFilteredBatchMinQueries || k == 0 || k > (uint32_t)kMaxFusedK) return false;
     if (rows == 0 || rows > 0xFFFFFFFFull || dim == 0) return false;
-    IndexView v{};
-    v.metric = metric; v.dim = dim; v.dim4 = (dim + 3) / 4; v.n_rows = (uint32_t)rows; v.n_tiles = (uint32_t)((rows + 63) / 64); v.filter = filter;
+    const IndexView v = shape_view(metric, dim, rows, filter);
     if (!batched_supported(v, nq, k)) return false;
     if (mode == 1) return true;
     return kFilteredBatchAutoMeasured && rows >= kFilteredBatchAutoMinRows;
@@ -2901,13 +2946,7 @@ hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_
     if (!plan_batched(v, nq, k, cus, (reinterpret_cast<uintptr_t>(d_queries) & 15u) == 0, r)) return hipErrorNotSupported;
     const RowSetRef* d_sets = sets ? sets->d_sets : nullptr;
     if (d_sets && !batched_sets_route(r)) return hipErrorNotSupported;   // (a missing route is an error, never an unfiltered answer)
-    if (d_sets && r.filter == MainFilter::qreg) {
-        // the register-resident kernel has no flush variant (its instantiations are many: three operand splits, both row forms): a filtered
-        // batch of whole workgroups takes what plan_batched chooses where that kernel does not apply
-        const uint32_t nqb64 = r.nq_pad / 64;
-        if (r.bfrows) { r.filter = MainFilter::bf16rows; r.filter_grid = grid_multiple(2 * (uint32_t)cus, nqb64 / 4); }
-        else r.filter = MainFilter::w8x2;
-    }
+    if (d_sets) batched_sets_remap(r);
     const BatchedLayout L = batched_layout(d_ws, v, p, r);
     if (L.end > L.total) return hipErrorInvalidValue;       // (cannot happen: see batched_layout)
     if (d_sets && trace_filtered())

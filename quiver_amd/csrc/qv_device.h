@@ -339,6 +339,10 @@ bool batched_sample_plan(const IndexView& v, uint32_t nq, uint32_t k, int cus, u
 // The dispatch's rule for a filtered call or shared pass (qv_batched_applies_filtered; mode: QV_FILTERED_BATCH_*, 0 = QV_FILTERED_BATCH of the
 // environment, else automatic): n_not_sparse = the piece's queries whose set the HOST does not know to be below the sparse floor.
 bool filtered_batch_rule(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse);
+// Which main filter kernel a FILTERED batch of this shape launches (qv_batched_filter_route): plan_batched, then the remap launch_batched
+// applies to a batch with sets.  plane: the index keeps the bfloat16 copy the batched filter reads.  *code: QV_BATCHED_FILTER_* of
+// include/qv.h; false where batched_sets_supported is.
+bool batched_sets_filter(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool plane, int cus, uint32_t* nq_pad, int* code);
 constexpr uint32_t kFilteredBatchMinQueries = 9;
 constexpr uint32_t kFilteredBatchDefaultPpm = 10000;      // the sparse floor where the index sets none: a hundredth of the rows
 constexpr uint32_t kFilteredBatchAutoMinRows = 300000;    // automatic mode takes nothing below the smallest measured shape

@@ -469,6 +469,9 @@ class DeviceIndex:
         check(lib().qv_index_filtered_batch_stats(self._h, out))
         return {"queries": int(out[0]), "hand_backs": int(out[1]), "sparse": int(out[2]), "batches": int(out[3])}
 
+    # QV_BATCHED_FILTER_* of include/qv.h, by code
+    BATCHED_FILTERS = ("mfma_f32", "bf16x3", "bf16x3_shared", "bf16rows", "w8x2", "w8x2_padded", "q64_plane", "q64_f32_rows")
+
     def batched_sample_plan(self, nq: int, k: int) -> dict:
         """the sample the batched path's plan chose for nq queries, k results: "rows" sample rows, every "group_step"-th 128-row group of
         the corpus — sample position i is corpus row (i // 128) * group_step * 128 + i % 128 — and the "rank" its bound is taken at

@@ -10,6 +10,8 @@ Value classes (the letters are the ones the tests and DESIGN.md §2 use):
 TEST INFRASTRUCTURE ONLY."""
 import numpy as np
 
+from tests import _oracle as O
+
 NAN_BITS = (0x7FC00000, 0xFFC00000, 0x7F800001, 0xFF800001)
 NANS = np.array(NAN_BITS, dtype=np.uint32).view(np.float32)
 G_NORMS = (0.5e18, 0.999e18, 1.001e18, 2e18, 1e30)
@@ -83,3 +85,43 @@ def class_rows(rng, dim, per_class=1):
             for name, v in variants(cls, rng, unit(rng, dim)):
                 out.append((cls, name, v))
     return out
+
+
+# corpora and queries of the search tests: ordinary generator rows with extreme rows written in
+def _corpus(seed, n, dim, regime, q_ord):
+    """rows [n, dim] with extreme rows written in; `q_ord` (ordinary queries) get scaled copies of themselves at G norms"""
+    rng = np.random.default_rng(seed)
+    rows = O.gen_rows(seed, 0, n, dim)
+    ext = [v for _, _, v in class_rows(rng, dim, per_class=2)]
+    for i, q in enumerate(q_ord[:2]):                                   # the query's own direction, scaled across the guard
+        ext += [scaled(q / np.float32(np.linalg.norm(q)), g) for g in G_NORMS]
+    pos = rng.choice(n, size=len(ext), replace=False)
+    pos[:3] = [0, n - 1, n // 2]                                        # first / last row / a middle tile boundary
+    for p, v in zip(pos, ext):
+        rows[p] = v
+    if regime == "many":
+        # ~20 % of the rows, in thirds: whole-NaN rows (NaN under every metric); rows with one +inf element (+inf under the L1 / L2
+        # metrics, float32 and float64; NaN under cosine; -inf or +inf under dot, by the sign of the query's element); rows holding
+        # +3e38 and -3e38 (+inf under the float32 metrics, finite and far under the float64 ones).  Cosine never gives +inf.
+        bad = rng.choice(n, size=n // 5, replace=False)
+        a, b = bad.size // 3, 2 * bad.size // 3
+        rows[bad[:a]] = NANS[rng.integers(0, 4, size=a)][:, None]
+        rows[bad[a:b], 0] = np.inf
+        rows[bad[b:], 0] = np.float32(3.0e38)
+        rows[bad[b:], -1] = np.float32(-3.0e38)
+    return rows
+
+
+def _queries(seed, rows, dim, n_ord=4):
+    """(queries, is_extreme): ordinary queries, scaled copies of corpus rows at G norms, and every other class"""
+    rng = np.random.default_rng(seed + 1)
+    qo = O.gen_rows(seed + 1, 0, n_ord, dim)
+    ext = [v for c, _, v in class_rows(rng, dim) if c != "G"]
+    with np.errstate(all="ignore"):                                    # NaN payload rows widen with a warning
+        nrm = np.linalg.norm(rows.astype(np.float64), axis=1)
+    src = int(np.nonzero(np.isfinite(rows).all(axis=1) & (nrm > 0.5) & (nrm < 2.0))[0][0])   # the first ordinary row
+    r0 = rows[src] / np.float32(nrm[src])
+    ext += [scaled(r0, g) for g in G_NORMS]
+    qs = np.concatenate([qo, np.stack(ext)]).astype(np.float32)
+    flag = np.r_[np.zeros(n_ord, bool), np.ones(len(ext), bool)]
+    return qs, flag

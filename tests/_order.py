@@ -29,6 +29,7 @@ from fractions import Fraction
 import numpy as np
 
 from oracle import oracle_np as ONP
+from tests import _oracle as O
 
 COSINE, L2, L2SQ, DOT, L1, COSINE_F32, L2_F32, DOT_F32, L2SQ_F64 = range(9)
 F64_METRICS = (COSINE, L2, DOT, L1, L2SQ_F64)          # the float64 chains: every exact path, split forms included
@@ -434,3 +435,53 @@ def query_for(metric, dim, rng):
 def oracle_chain(metric, q, r):
     """the numpy restatement of the reference (oracle/oracle_np.py), for cross-checking the models' "chain" """
     return ONP.distance(metric, q, r)
+
+
+# ------------------------------------------------------------------------------------------- corpora of planted rows --
+DIFF = (L2, L2SQ, L1, L2_F32, L2SQ_F64)
+SEP = 2.0 ** 28                  # the queries of a difference metric sit SEP apart in the last column (every planted delta is
+                                 # below 2^25 there); fillers sit 2^30 away from all of them
+
+
+def _case(metric, dim, nq, seed, n_fill, dup=0):
+    """-> (queries [nq, dim], corpus [n, dim], planted ids per query).  Difference metrics: each query gets its own copy of the
+    planted rows (shifted with it in the last column, where planted deltas are 0).  Dot / cosine: the queries are one query
+    scaled by powers of two (every product, and the chain, scales exactly), all sharing the planted rows."""
+    rng = np.random.default_rng(seed)
+    q = query_for(metric, dim, rng)
+    planted = planted_rows(metric, dim, q, 40, rng, max_scale=0)
+    assert len(planted) >= 8, (metric, dim, len(planted))
+    planted = np.array(planted, np.float32)
+    if dup:
+        planted = np.concatenate([planted, planted[:dup]])            # equal distances: the heaps' tie rules
+    qs, rows, own = [], [], []
+    for j in range(nq):
+        if metric in DIFF:
+            qj = q.copy(); qj[-1] = j * SEP
+            pj = planted.copy(); pj[:, -1] = j * SEP
+            own.append(np.arange(j * len(planted), (j + 1) * len(planted)))
+            rows.append(pj)
+        else:
+            qj = (q * np.float32(2.0 ** (j % 3 - 1))).astype(np.float32)
+            if j == 0:
+                rows.append(planted)
+            own.append(np.arange(len(planted)))
+        qs.append(qj)
+    if metric in DIFF:
+        fill = (rng.standard_normal((n_fill, dim)) * 2.0 ** 20).astype(np.float32)
+        fill[:, -1] = -(2.0 ** 30)
+    elif metric in (DOT, DOT_F32):
+        fill = (-np.sign(q) * rng.uniform(0.5, 2.0, size=(n_fill, dim))).astype(np.float32)      # every dot with a query < 0
+    else:
+        fill = (-q * (1.0 + 0.3 * rng.standard_normal((n_fill, dim)))).astype(np.float32)        # anti-parallel: distance ~2
+    corpus = np.concatenate(rows + [fill])
+    perm = rng.permutation(corpus.shape[0])                           # planted rows spread over tiles and workgroups
+    inv = np.empty_like(perm); inv[perm] = np.arange(perm.size)
+    corpus = np.ascontiguousarray(corpus[perm])
+    own = [np.sort(inv[o]) for o in own]
+    qs = np.ascontiguousarray(np.stack(qs))
+    for j in range(nq):                                               # the planted rows ARE the nearest, and order-sensitive
+        d = O.all_distances(metric, corpus, qs[j])
+        mask = np.ones(corpus.shape[0], bool); mask[own[j]] = False
+        assert d[own[j]].max() < d[mask].min(), (metric, dim, j)
+    return qs, corpus, own

@@ -21,7 +21,8 @@ def _declared_symbols():
 def test_header_declares_the_expected_surface():
     syms = _declared_symbols()
     for must in ("qv_index_create", "qv_index_add", "qv_index_remove", "qv_index_search", "qv_distance_rows",
-                 "qv_distance_pairs", "qv_index_size", "qv_index_destroy", "qv_last_error"):
+                 "qv_distance_pairs", "qv_index_size", "qv_index_destroy", "qv_last_error", "qv_batched_applies_filtered",
+                 "qv_batched_filter_route"):
         assert must in syms
 
 

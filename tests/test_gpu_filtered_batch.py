@@ -15,6 +15,7 @@ import quiver_amd
 from quiver_amd import QvError
 from quiver_amd.device_index import broadcast_filters, pack_where
 from tests import _oracle as O
+from tests.test_filtered_batch_edges_cpu import route_of
 
 pytestmark = pytest.mark.gpu
 
@@ -114,6 +115,7 @@ def test_every_route_equals_the_oracle_and_the_exact_passes(dim, kw, metric):
     probe = [q for q in (0, 7, 14, 21, 28, 35)]                           # one query of every kind (q mod 6 = 0, 1, 2, 3, 4, 5), all inside the smallest batch
     want_sets = {q: c.oracle(q, max(KS), c.masks[q]) for q in probe}
     want_where = {q: c.oracle(q, max(KS), c.wmasks[q]) for q in probe}
+    plane, codes = bool(kw.get("bf16_rows")), {}                           # the main filter kernel of every cell's pieces (qv_batched_filter_route)
     never = {}
     for nq in NQS:
         for k in KS:
@@ -128,6 +130,8 @@ def test_every_route_equals_the_oracle_and_the_exact_passes(dim, kw, metric):
                 for form, call, want in (("sets", lambda: idx.search_rowsets(c.qs[:nq], k, c.sets[:nq]), want_sets),
                                          ("where", lambda: idx.search_where(c.qs[:nq], k, c.filters[:nq]), want_where)):
                     where = (metric, dim, tuple(kw), filt, form, nq, k)
+                    for piece in ((256, 44) if nq == 300 else (nq,)):
+                        codes[(filt, piece)] = quiver_amd.batched_filter_route(metric, dim, N_SMALL, piece, k, filt, plane)[1]
                     got, moved = _run(idx, "always", call)
                     assert moved["queries"] == nq, (where, moved)                      # every query took the path ...
                     assert moved["batches"] == (2 if nq == 300 else 1), (where, moved)   # ... 300 as 256 and a tail of 44
@@ -136,6 +140,8 @@ def test_every_route_equals_the_oracle_and_the_exact_passes(dim, kw, metric):
                     for q in probe:
                         ro, do = want[q]
                         _is_oracle(got, q, (ro[:k], do[:k]), k, where)
+    # which flush variants this parametrisation launched: the table tests/test_filtered_batch_edges_cpu.py states, whose union over ROUTES is all eight
+    assert codes == {(filt, piece): route_of(filt, dim, plane, piece) for filt in ("bf16x1", "bf16x3", "fp32") for piece in (40, 100, 256, 44)}, codes
 
 
 # ---- 2. the guessed bound: k >= 16 on 131 072 rows or more.  One set is confined to the first third of the rows: the rank k S / N assumes a set

@@ -18,53 +18,7 @@ from tests import _order as OR
 pytestmark = pytest.mark.gpu
 
 NAMES = {0: "cosine", 1: "l2", 2: "l2sq", 3: "dot", 4: "l1", 5: "cosine_f32", 6: "l2_f32", 7: "dot_f32", 8: "l2sq_f64"}
-DIFF = (OR.L2, OR.L2SQ, OR.L1, OR.L2_F32, OR.L2SQ_F64)
-SEP = 2.0 ** 28                  # the queries of a difference metric sit SEP apart in the last column (every planted delta is
-                                 # below 2^25 there); fillers sit 2^30 away from all of them
-
-
-def _case(metric, dim, nq, seed, n_fill, dup=0):
-    """-> (queries [nq, dim], corpus [n, dim], planted ids per query).  Difference metrics: each query gets its own copy of the
-    planted rows (shifted with it in the last column, where planted deltas are 0).  Dot / cosine: the queries are one query
-    scaled by powers of two (every product, and the chain, scales exactly), all sharing the planted rows."""
-    rng = np.random.default_rng(seed)
-    q = OR.query_for(metric, dim, rng)
-    planted = OR.planted_rows(metric, dim, q, 40, rng, max_scale=0)
-    assert len(planted) >= 8, (metric, dim, len(planted))
-    planted = np.array(planted, np.float32)
-    if dup:
-        planted = np.concatenate([planted, planted[:dup]])            # equal distances: the heaps' tie rules
-    qs, rows, own = [], [], []
-    for j in range(nq):
-        if metric in DIFF:
-            qj = q.copy(); qj[-1] = j * SEP
-            pj = planted.copy(); pj[:, -1] = j * SEP
-            own.append(np.arange(j * len(planted), (j + 1) * len(planted)))
-            rows.append(pj)
-        else:
-            qj = (q * np.float32(2.0 ** (j % 3 - 1))).astype(np.float32)
-            if j == 0:
-                rows.append(planted)
-            own.append(np.arange(len(planted)))
-        qs.append(qj)
-    if metric in DIFF:
-        fill = (rng.standard_normal((n_fill, dim)) * 2.0 ** 20).astype(np.float32)
-        fill[:, -1] = -(2.0 ** 30)
-    elif metric in (OR.DOT, OR.DOT_F32):
-        fill = (-np.sign(q) * rng.uniform(0.5, 2.0, size=(n_fill, dim))).astype(np.float32)      # every dot with a query < 0
-    else:
-        fill = (-q * (1.0 + 0.3 * rng.standard_normal((n_fill, dim)))).astype(np.float32)        # anti-parallel: distance ~2
-    corpus = np.concatenate(rows + [fill])
-    perm = rng.permutation(corpus.shape[0])                           # planted rows spread over tiles and workgroups
-    inv = np.empty_like(perm); inv[perm] = np.arange(perm.size)
-    corpus = np.ascontiguousarray(corpus[perm])
-    own = [np.sort(inv[o]) for o in own]
-    qs = np.ascontiguousarray(np.stack(qs))
-    for j in range(nq):                                               # the planted rows ARE the nearest, and order-sensitive
-        d = O.all_distances(metric, corpus, qs[j])
-        mask = np.ones(corpus.shape[0], bool); mask[own[j]] = False
-        assert d[own[j]].max() < d[mask].min(), (metric, dim, j)
-    return qs, corpus, own
+_case = OR._case                 # (shared with tests/test_gpu_filtered_batch_edges.py)
 
 
 def _same(got_r, got_d, got_c, want_r, want_d, what):
