@@ -23,9 +23,9 @@ namespace qv {
 //                    Any k rows' upper bounds cap the k-th distance: every row of the answer has d_lo <= H.
 //   k_bound_collect  the rows with d_lo <= H (not strict: ties go on) — k plus a handful on ordinary data — listed with one returning
 //                    atomic per wave and batch that has any.
-//   k_bound_rescore  one workgroup: those rows walked as ONE float64 chain over the float32 tiles — row_accumulate + finalize, the
-//                    query's norm as its chain: the exact scan's bits —, the k best (distance, row) keys written where the exact scan
-//                    writes them.  When the list overflowed, H is not finite (fewer than k rows with a bound), or |q| is not a norm
+//   k_bound_rescore  a wave per survivor on a small fixed grid: each row requested whole, then walked as ONE float64 chain — row_accumulate's
+//                    chain + finalize, the query's norm as its chain: the exact scan's bits —, the last workgroup merges the lists and writes
+//                    the k best (distance, row) keys where the exact scan writes them.  When the list overflowed, H is not finite (fewer than k rows with a bound), or |q| is not a norm
 //                    the bound works with, it sets the gate word instead and the exact scan launched behind it answers
 //                    (k_flat_scan<., ., true>'s `gate`: otherwise that launch leaves at once).  Nothing is read on the host.
 // (Measured first and not kept: candidates taken DURING the scan against a device-wide threshold word seeded from the waves' first
@@ -206,7 +206,8 @@ k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 6
     bound_collect(lo_all, n, ~inv, &ctrl->cand_cnt, cand);
 }
 
-// One query's survivors walked exactly by one workgroup (cnt: how many the collect counted; has_H: it had a threshold).  decided(hand_back)
+// One query's survivors walked exactly by one workgroup, lane == survivor — the shared pass's re-score (k_bound_rescore_mq: a workgroup per query;
+// the single query's k_bound_rescore below spreads its survivors over waves and workgroups instead) (cnt: how many the collect counted; has_H: it had a threshold).  decided(hand_back)
 // runs on thread 0 once the query's norm is known; a query handed back writes nothing.
 template <int M, typename F>
 __device__ __forceinline__ void bound_rescore_query(const IndexView& v, const float* __restrict__ query, uint32_t k, uint32_t cnt, bool has_H, const uint32_t* __restrict__ cand,
@@ -263,18 +264,116 @@ __device__ __forceinline__ void bound_rescore_query(const IndexView& v, const fl
     }
 }
 
+// The single query's re-score: a WAVE per survivor, kBoundRescoreGrid workgroups at most (a fixed grid chosen at launch; the count lives on the
+// device).  bound_rescore_query above puts lane == survivor: with a few tens of survivors one wave works, and each lane walks its row's
+// chunks — 1 KiB apart — sixteen at a time behind a barrier, a dozen rounds of gather latency in front of one dependent chain (52 us for
+// 42 survivors at 768 dimensions; profiles/LAB_r10_bound_scan_8bit.md).  Here a wave requests ALL of a survivor's chunks at once, spread over
+// its lanes, stages them in LDS, and then runs the one in-order chain acc1<M> over elements 0 .. dim - 1 against the staged query in
+// MT<M>::Q, then finalize<M>: row_accumulate's chain in its order, so the exact scan's bits.  (Every lane runs the same chain on the same
+// LDS words: a broadcast, no divergence.)  The keys go through the wave's list, the waves' lists through wave 0, the workgroups' lists
+// through `partial` (stage 1's, dead since H was computed) and a ticket on the stage's control words (bound_scan_tail's protocol); the
+// LAST workgroup merges them and writes the k results.
+// Exactly one thread — thread 0 of that last workgroup, when every workgroup has read the control words and the gate — decides
+// hand-back and writes stats[], ctrl->flag, next->flag, the zeroed control words and the gate, with the values the one-workgroup kernel wrote.
 // P8: the re-score behind the 8-bit stage (ctrl = that stage's words, next = the bfloat16 stage's).  It answers, or sets its own flag — the
 // word the bfloat16 stage's three launches are gated on — and then that stage decides or hands on to the exact scan.  An 8-bit search counts
 // as a bound-scan search in stats[0 .. 2]; its own counters sit at kBound8StatsWord.
 // gate (the bfloat16 stage behind the 8-bit one): zero = the 8-bit stage has answered and has cleared this stage's flag for the exact scan
-// behind; non-zero = this stage runs, and zeroes the word, which it is the last to read.
+// behind; non-zero = this stage runs, and its last workgroup zeroes the word, which this launch is the last to read.
+constexpr uint32_t kBoundRescoreGrid = 64;     // 256 waves: one round for a few hundred survivors
 template <int M, bool P8 = false>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand,
-                uint32_t* __restrict__ stats, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, uint32_t* gate = nullptr, BoundCtrl* next = nullptr) {
+                uint32_t* __restrict__ stats, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, uint32_t* gate, BoundCtrl* next,
+                uint64_t* __restrict__ partial /* [gridDim.x][k] */) {
     if (gate != nullptr && *gate == 0u) return;
+    using Q = typename MT<M>::Q;
+    extern __shared__ __align__(16) unsigned char smem[];
+    Q* q_lds = reinterpret_cast<Q*>(smem);
+    const size_t q_bytes = (((size_t)v.dim4 * 4 * sizeof(Q)) + 15) / 16 * 16;
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem + q_bytes);       // [kScanWaves][64]
+    float* rbuf = reinterpret_cast<float*>(smem + q_bytes + (size_t)kScanWaves * 64 * sizeof(uint64_t));   // [kScanWaves][dim4 * 4]: a wave's survivor
+    __shared__ double s_qn;
+    __shared__ uint32_t s_last;
     const uint32_t cnt = ctrl->cand_cnt, thr_inv = ctrl->thr_inv;
-    bound_rescore_query<M>(v, query, k, cnt, thr_inv != 0u, cand, rows_out, dist_out, [&](bool hand_back) {
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t ns = cnt < kBoundCandCap ? cnt : kBoundCandCap, kth = k - 1;
+    // The workgroups that have a survivor — one at least, which then decides for a search without any.  The others only take their ticket:
+    // with a handful of survivors the launch costs what one workgroup costs.  Should such a workgroup draw the LAST ticket, it goes on
+    // as the one that decides and merges (every list is published by then), and prepares the query for that.
+    const uint32_t active = std::max(1u, std::min((uint32_t)gridDim.x, (ns + kScanWaves - 1) / kScanWaves));
+    const bool idle = blockIdx.x >= active;
+    if (idle) {
+        if (threadIdx.x == 0) s_last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;   // (behind this workgroup's reads of ctrl and the gate)
+        __syncthreads();
+        if (!s_last) return;
+    }
+    stage_query<M>(q_lds, query, v.dim, v.dim4);
+    __syncthreads();
+    if (wave == kScanWaves - 1) {
+        // |q| as the reference's chain (distances.go:20): cosine's finalize takes it, and every metric's hand-back rule
+        double ma = 0.0;
+        for (uint32_t i = 0; i < v.dim; i++) { const double a = (double)q_lds[i]; ma = __builtin_fma(a, a, ma); }
+        if (lane == 0) s_qn = __builtin_sqrt(ma);
+    }
+    __syncthreads();
+    const double qn = s_qn;
+    const bool hand_back = cnt > kBoundCandCap || thr_inv == 0u || !bound_scan_norm_ok(qn, v.dim);   // (the same in every workgroup)
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    if (!hand_back && !idle) {
+        QConst qc; qc.qn = 0.0; qc.qn32 = 0.0f;
+        if constexpr (M == QV_COSINE) qc.qn = qn;
+        const f4* tiles = reinterpret_cast<const f4*>(v.tiles);
+        f4* mine = reinterpret_cast<f4*>(rbuf + (size_t)wave * v.dim4 * 4);
+        bool first = true;
+        for (uint32_t i = blockIdx.x * kScanWaves + wave; i < ns; i += active * kScanWaves) {   // (wave-uniform)
+            const uint32_t row = cand[i];
+            const f4* src = tiles + (size_t)(row >> 6) * v.dim4 * 64 + (row & 63);
+            double rn = 0.0;
+            if constexpr (MT<M>::needs_rnorm) rn = v.rnorm[row];
+            // the row's chunks, lane by lane, four requests of a lane in flight together (768 dimensions: all three)
+            for (uint32_t c0 = 0; c0 < v.dim4; c0 += 256) {
+                f4 x[4];
+#pragma unroll
+                for (uint32_t u = 0; u < 4; u++) { const uint32_t c = c0 + u * 64 + lane; if (c < v.dim4) x[u] = __builtin_nontemporal_load(&src[(size_t)c * 64]); }
+#pragma unroll
+                for (uint32_t u = 0; u < 4; u++) { const uint32_t c = c0 + u * 64 + lane; if (c < v.dim4) mine[c] = x[u]; }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the wave's own LDS writes before its reads of other lanes' chunks
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            typename MT<M>::A acc = 0;
+            for (uint32_t c = 0; c < v.dim4; c++) {                    // ONE chain, element order: row_accumulate's
+                const f4 r = mine[c];
+                const Q* qq = q_lds + (size_t)c * 4;
+                acc1<M>(acc, qq[0], r.x); acc1<M>(acc, qq[1], r.y); acc1<M>(acc, qq[2], r.z); acc1<M>(acc, qq[3], r.w);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // ... and those reads before the next survivor's writes
+            __builtin_amdgcn_wave_barrier();
+            const uint64_t key = lane == 0 ? make_key(finalize<M>(acc, qc, rn), row) : kDeadKey;
+            if (first) { list = wave_sort64(key, lane); thr = readlane64(list, kth); first = false; }
+            else list_insert(list, thr, key, kth, lane);
+        }
+    }
+    wl[wave * 64 + lane] = list;
+    __syncthreads();
+    if (wave == 0 && !idle) {
+        if (!hand_back) {
+            for (uint32_t w = 1; w < kScanWaves; w++) list_insert(list, thr, lane < k ? wl[w * 64 + lane] : kDeadKey, kth, lane);
+            uint64_t* out = partial + (size_t)blockIdx.x * k;
+            if (lane < k) (void)atomicExch(reinterpret_cast<unsigned long long*>(&out[lane]), (unsigned long long)list);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // every lane's exchange has returned: the list is at the memory side
+        }
+        uint32_t last = 0;
+        if (lane == 0) last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;   // (behind this workgroup's reads of ctrl and the gate)
+        last = __builtin_amdgcn_readfirstlane(last);
+        if (lane == 0) s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    if (threadIdx.x == 0) {
+        ctrl->ticket = 0;                                              // for the next launch on these words (stream order)
         if constexpr (P8) {
             stats[kBound8StatsWord] = cnt;
             if (hand_back) (void)atomicAdd(&stats[kBound8StatsWord + 1], 1u);
@@ -284,11 +383,13 @@ k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundC
             stats[0] = cnt;
             if (hand_back) (void)atomicAdd(&stats[1], 1u);
             (void)atomicAdd(&stats[2], 1u);
-            if (gate != nullptr) *gate = 0u;                           // (every thread read it before the barriers in front of this call)
+            if (gate != nullptr) *gate = 0u;                           // (every workgroup read it before it took its ticket)
         }
         ctrl->flag = hand_back ? 1u : 0u;                              // the launch behind this one reads it
         ctrl->cand_cnt = 0; ctrl->thr_inv = 0;                         // zero, as the words are kept
-    });
+    }
+    if (hand_back) return;                                             // a query handed back writes nothing
+    merge_lists_last_workgroup(partial, active, k, rows_out, dist_out);
 }
 
 // ---------------------------------------------------------------- one query: reject rows on the 8-bit plane first --
@@ -1066,7 +1167,9 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
     const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
     BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
     const size_t lds1 = (size_t)v.dim * sizeof(float) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
-    const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    // the re-score: the staged query, the waves' lists, a survivor's row per wave; its grid never exceeds stage 1's, whose `partial` it publishes in
+    const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t) + (size_t)kScanWaves * v.dim4 * 4 * sizeof(float);
+    const uint32_t rgrid = std::min(kBoundRescoreGrid, grid);
     const size_t lds8 = (size_t)v.dim * 2 + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     auto run = [&](auto Mc, auto Mk) -> hipError_t {
         constexpr int M = decltype(Mc)::value;
@@ -1081,7 +1184,7 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
         auto stage = [&](auto scan, size_t lds_scan, auto rescore, BoundCtrl* c, uint32_t* gate, BoundCtrl* next, auto... scan_gate) {
             hipLaunchKernelGGL(scan, dim3(grid), dim3(kScanBlock), lds_scan, s, v, d_query, k, c, lo_all, partial, seed_rows, seed_dist, scan_gate...);
             hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, c, cand, (const uint32_t*)gate);
-            hipLaunchKernelGGL(rescore, dim3(1), dim3(kScanBlock), lds2, s, v, d_query, k, c, cand, d_stats, d_rows_out, d_dist_out, gate, next);
+            hipLaunchKernelGGL(rescore, dim3(rgrid), dim3(kScanBlock), lds2, s, v, d_query, k, c, cand, d_stats, d_rows_out, d_dist_out, gate, next, partial);
         };
         const uint32_t* const no_gate = nullptr;
         hipError_t e = attrs(k_bound_scan<M, MASKED>, lds1, k_bound_rescore<M>);
