@@ -30,13 +30,20 @@ type Graph struct {
 // GraphConfig is hnsw.Config (hnsw.go:27-41); zero values take the reference's defaults 16 / 2M / 200 / 100 (hnsw.go:223-237).
 type GraphConfig struct {
 	M, MaxM0, EfConstruction, EfSearch int
+	// GraphPlane: the vector storage also keeps a bfloat16 copy of the rows in row order (FlagGraphPlane: +2 * dim bytes per row),
+	// on which batch searches can reject neighbours (SetRejectPlane).  Results do not depend on it.
+	GraphPlane bool
 }
 
 // NewGraph creates the vector storage (a qv_index with a row-major copy for the per-hop gathers) and an empty graph over it.
 func NewGraph(dim int, m Metric, device int, capacity int, cfg GraphConfig) (*Graph, error) {
 	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
 	var idx *C.qv_index
-	if C.qv_index_create(&idx, C.uint32_t(dim), C.qv_metric(m), C.int(device), C.QV_FLAG_ROWMAJOR) != C.QV_OK {
+	flags := uint64(C.QV_FLAG_ROWMAJOR)
+	if cfg.GraphPlane {
+		flags |= FlagGraphPlane
+	}
+	if C.qv_index_create(&idx, C.uint32_t(dim), C.qv_metric(m), C.int(device), C.uint64_t(flags)) != C.QV_OK {
 		return nil, lastErr()
 	}
 	var g *C.qv_graph
@@ -180,6 +187,43 @@ func (h *Graph) Delete(node uint32) error {
 		return lastErr()
 	}
 	return nil
+}
+
+// Modes of SetRejectPlane (QV_GRAPH_REJECT_*).
+const (
+	RejectAuto   = int(C.QV_GRAPH_REJECT_AUTO)   // where it was measured faster (qv.h: cosine, dim 768, 1M to below 2M nodes, 8192 queries or more, list sizes 64 to 256)
+	RejectAlways = int(C.QV_GRAPH_REJECT_ALWAYS) // wherever it applies (qv_graph_reject_applies)
+	RejectNever  = int(C.QV_GRAPH_REJECT_NEVER)
+)
+
+// SetRejectPlane chooses whether batch searches of more than max(compute units, 768) queries reject neighbours on the storage's
+// row-order bfloat16 copy (GraphConfig.GraphPlane) before they read a float32 row (qv_graph_set_reject_plane).  Exclusive, like Insert.
+func (h *Graph) SetRejectPlane(mode int) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	h.mu.Lock()
+	defer h.mu.Unlock()
+	if C.qv_graph_set_reject_plane(h.g, C.int(mode)) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
+// RejectStats is qv_graph_reject_stats: the evaluations made in rejecting hops, those rejected on the copy, the queries that finished
+// in the rejecting form, and whether the storage holds the copy.  Waits for the device.
+type RejectStats struct {
+	Evals, Rejected, Queries uint64
+	Plane                    bool
+}
+
+func (h *Graph) RejectStats() (RejectStats, error) {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	h.mu.RLock()
+	defer h.mu.RUnlock()
+	out := make([]uint64, 4)
+	if C.qv_graph_reject_stats(h.g, (*C.uint64_t)(unsafe.Pointer(&out[0]))) != C.QV_OK {
+		return RejectStats{}, lastErr()
+	}
+	return RejectStats{Evals: out[0], Rejected: out[1], Queries: out[2], Plane: out[3] != 0}, nil
 }
 
 // Remove is hnsw.HNSW.Delete (hnsw.go:741-842) for the listed nodes, as if one by one in list order, applied to the device

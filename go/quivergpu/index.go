@@ -35,6 +35,11 @@ type rows interface {
 // indexes keep by default (+3 * dim + 8 bytes per row).  On every other metric it does nothing.
 const FlagL2ScanPlane uint64 = C.QV_FLAG_L2_SCAN_PLANE
 
+// FlagGraphPlane (QV_FLAG_GRAPH_PLANE): a row-major cosine or dot index whose dimension is a multiple of 64 up to 4096 also keeps a
+// bfloat16 copy of the rows in row order (+2 * dim bytes per row), on which a graph's batch searches can reject neighbours
+// (Graph.SetRejectPlane).  Elsewhere it does nothing.
+const FlagGraphPlane uint64 = C.QV_FLAG_GRAPH_PLANE
+
 // Index implements core.Index and core.BatchIndex (pkg/core/collection.go:78-96) on libqv.  String ids and metadata
 // never leave Go; the device sees row numbers, the analogue of hnsw.Node.VectorIndex (pkg/hnsw/hnsw.go:94).
 //

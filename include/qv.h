@@ -122,6 +122,14 @@ typedef enum qv_status {
                                     narrower than 768 dimensions waits for 10M rows, and a filtered search for nine tenths of the tiles
                                     holding a candidate.  On every other metric the flag does nothing; QV_L2SQ, QV_L2_F32 and QV_L2SQ_F64 keep no
                                     planes.  QV_FLAG_BF16_ROWS alone on a QV_L2 index stays a copy for the batched filter: no bound scan */
+#define QV_FLAG_GRAPH_PLANE 16ull /* a QV_FLAG_ROWMAJOR index of metric QV_COSINE or QV_DOT whose dimension is a multiple of 64 up to 4096
+                                    also keeps `rowmaj16`: a bfloat16 copy of the rows in ROW order, [rows][dim] (+dim * 2 bytes per row:
+                                    7688 -> 9224 at 768 dimensions for an index that serves flat, graph and batch), each element the
+                                    round-to-nearest-even conversion the per-row residual |r - bf16(r)| is measured against, written by
+                                    every call that writes rows.  A graph traversal can then reject neighbours on it
+                                    (qv_graph_set_reject_plane).  Opt-in: without the flag nothing is kept and every traversal launches the
+                                    kernels it always launched.  Without QV_FLAG_ROWMAJOR, on another metric or another dimension the flag
+                                    does nothing and creation still succeeds; a copy that cannot be allocated is given up alone */
 /* FOR THE qv_scan_* RULE FUNCTIONS ONLY: "a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE", where they take a metric.  They accept it
  * wherever they accept QV_COSINE and QV_DOT (plain QV_L2 keeps answering 0); qv_index_metric still answers QV_L2, and qv_index_create
  * rejects the code. */
@@ -640,6 +648,8 @@ int qv_scan_bound_interval_l2(uint32_t dim, float s, double qn, double rn, float
 #define QV_DEBUG_RNORM 0
 #define QV_DEBUG_RRES  1
 #define QV_DEBUG_PLANE 2
+#define QV_DEBUG_ROWMAJ16 3   /* the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE), raw: rows x dim uint16, rows ever added; QV_ERR_UNSUPPORTED when an index created
+                                 with the flag keeps none; an index created without the flag does not know the code (QV_ERR_INVALID_ARG, as before) */
 int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes);
 
 /* Device-pointer form of the batched path: enqueues on `stream`, no sync.  d_redo_flags_out[nq]
@@ -795,6 +805,47 @@ int qv_graph_export(qv_graph* g, int8_t* levels, uint32_t* l0_deg, uint32_t* l0_
  * kernel (equal distances), qv_graph_search queries redone for the same reason. */
 int qv_graph_stats(const qv_graph* g, double* build_seconds, uint64_t* build_batches, uint64_t* build_redo, uint64_t* search_redo);
 
+/* ---- rejecting neighbours on the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE) ----
+ * searchLayer drops a neighbour whose distance is not below the worst of a full result heap and never looks at that distance again
+ * (hnsw.go:536-563).  On an index that keeps `rowmaj16`, a hop of the wave-per-query traversal that STARTS with a full list reads each
+ * new neighbour's bfloat16 row (half the bytes), takes the bound scan's interval of its distance (qv_scan_bound_interval: the same
+ * float32 chain, the same margin) and drops it when the lower end is not below the hop-start worst distance — exactly the rows the
+ * reference drops at their turn, whatever is admitted before them.  The others ("survivors", and every row the bound says nothing
+ * about) are evaluated from their float32 rows as before.  Rows, float32 bits, counts and evals_out are those of the unchanged
+ * traversal.  A query whose norm the bound declines (zero, not a number, huge) walks as before.
+ *   QV_GRAPH_REJECT_AUTO    the cells it was measured faster in (profiles/LAB_r17_graph_reject.md): QV_COSINE, dim == 768, a graph of 1 000 000 to
+ *                           1 999 999 nodes, calls of 8192 queries or more, a list size max(ef_search, k) of 64 to 256.  There "always" ran
+ *                           13 - 31 % ahead of "never" (1M x 768, MaxLevel 1, both corpora of the benchmark, list sizes 64 / 128 / 256, 8192 and
+ *                           32 768 queries per call, every cell beyond both arms' spread).  Within those cells the rule interpolates
+ *                           between the measured list sizes, takes calls larger than 32 768 and graphs up to twice the measured size, and
+ *                           does not ask for the graph's MaxLevel (16 was not measured).  QV_DOT, every other dimension (128 among them),
+ *                           10M nodes, smaller graphs and calls and other list sizes were NOT measured and launch the unchanged kernels
+ *                           unless told "always".
+ *   QV_GRAPH_REJECT_ALWAYS  wherever it applies (qv_graph_reject_applies)
+ *   QV_GRAPH_REJECT_NEVER   the unchanged kernels
+ * The environment variable QV_GRAPH_REJECT (1 always, 2 never; read once per process) sets the default of every graph.
+ * qv_graph_set_reject_plane needs the same external exclusion against searches as qv_graph_insert.
+ * Out of scope, all unchanged and none of them reads the copy: the latency form (calls of up to max(compute units, 768) queries, and
+ * with it coalesced concurrent callers); the exact-heap kernel; construction searches; the upper levels; graphs with tombstones;
+ * graphs with more than 32 level-0 links per node; QV_L2 and the float32-chain metrics; an 8-bit plane for the graph; dropping the
+ * float32 row-major copy. */
+#define QV_GRAPH_REJECT_AUTO   0
+#define QV_GRAPH_REJECT_ALWAYS 1
+#define QV_GRAPH_REJECT_NEVER  2
+int qv_graph_set_reject_plane(qv_graph* g, int mode);
+/* out[2] queries whose level-0 walk finished unflagged in the rejecting form (a query flagged for the exact-heap kernel — equal distances,
+ * a NaN — or declined for its norm is not one), out[0] the evaluations those queries made in rejecting hops, out[1] the ones of them
+ * rejected on the copy, out[3] 1 when the graph's index holds the copy.  Added once per query by the kernel; the call waits for the
+ * device. */
+int qv_graph_reject_stats(qv_graph* g, uint64_t* out);   /* out: 4 values */
+/* The dispatch's own rule, on the host: 1 when a qv_graph_search* call of nq queries takes the rejecting form.  Any mode answers 0
+ * without the copy, on a metric other than QV_COSINE / QV_DOT, for a graph with tombstones, for max_m0 > 32 and for a call the
+ * latency form takes (nq <= max(cus, 768)); QV_GRAPH_REJECT_AUTO answers 1 only within the measured floors above.  ef_search: the
+ * list size the call walks with, max(efSearch, k).
+ * < 0: an argument error (unknown metric or mode, cus <= 0, dim == 0). */
+int qv_graph_reject_applies(int metric, uint32_t dim, uint32_t n_nodes, uint32_t nq, uint32_t ef_search, int cus, int mode, int has_plane,
+                            int has_tombstones, uint32_t max_m0);
+
 /* ---- one corpus over the GPUs of a node --------------------------------
  * No reference counterpart (the reference is one process on CPU cores): this is what lets the Go host reach all the
  * GPUs of a node through ONE handle — what core.Index (pkg/core/collection.go:78-96) is for one GPU (qv_index),
@@ -813,7 +864,7 @@ int qv_graph_stats(const qv_graph* g, double* build_seconds, uint64_t* build_bat
  *                    the k best of the gathered lists, the whole batch at once.  Beyond (a filtered Collection.Search asks
  *                    for k = Index.Size(), collection.go:679-682): every shard ranks its rows (radix sort), the sorted runs
  *                    are exchanged and one stable radix sort on the first device merges them
- *   flags            QV_FLAG_ROWMAJOR, QV_FLAG_BF16_ROWS, QV_FLAG_NO_SCAN_PLANE and QV_FLAG_L2_SCAN_PLANE pass through to the shards; QV_SHARDED_PEER_COPY replaces the collective with
+ *   flags            QV_FLAG_ROWMAJOR, QV_FLAG_BF16_ROWS, QV_FLAG_NO_SCAN_PLANE, QV_FLAG_L2_SCAN_PLANE and QV_FLAG_GRAPH_PLANE pass through to the shards; QV_SHARDED_PEER_COPY replaces the collective with
  *                    point-to-point copies into the first device (and lets several shards share one device, which
  *                    RCCL does not allow: how the tests exercise 3 and 8 shards on a 1-GPU box)
  * Threading: as qv_index — searches, qv_sharded_distance_rows and qv_sharded_get_row(s) may run concurrently from many

@@ -15,6 +15,9 @@ QV_FLAG_ROWMAJOR = 1
 QV_FLAG_BF16_ROWS = 2
 QV_FLAG_NO_SCAN_PLANE = 4
 QV_FLAG_L2_SCAN_PLANE = 8      # a QV_L2 index keeps the bfloat16 copy and the 8-bit plane: its searches can take the bound scan
+QV_FLAG_GRAPH_PLANE = 16       # a row-major cosine / dot index also keeps a bfloat16 copy in row order: graph traversals can reject neighbours on it
+QV_GRAPH_REJECT_AUTO, QV_GRAPH_REJECT_ALWAYS, QV_GRAPH_REJECT_NEVER = 0, 1, 2
+QV_DEBUG_RNORM, QV_DEBUG_RRES, QV_DEBUG_PLANE, QV_DEBUG_ROWMAJ16 = 0, 1, 2, 3
 QV_RULE_L2_PLANES = 0x101      # such an index, as the qv_scan_* rule functions take it where they take a metric
 QV_BOUND_SCAN_AUTO, QV_BOUND_SCAN_ALWAYS, QV_BOUND_SCAN_NEVER = 0, 1, 2
 QV_FILTERED_BATCH_AUTO, QV_FILTERED_BATCH_ALWAYS, QV_FILTERED_BATCH_NEVER = 0, 1, 2
@@ -142,6 +145,9 @@ PROTOTYPES = {
     "qv_graph_info": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p, _u32p, _u32p, C.POINTER(C.c_int)]),
     "qv_graph_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_graph_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "qv_graph_set_reject_plane": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_graph_reject_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_graph_reject_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     "qv_sharded_span": (C.c_uint32, [C.c_int]),
     "qv_sharded_plan_add": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
     "qv_sharded_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_uint64]),

@@ -116,6 +116,16 @@ int ensure_rows(qv_index* idx, uint64_t rows, bool exact) {
     if (e == hipSuccess) e = regrow(&idx->d_rres, used_tiles * 64 * sizeof(float), new_tiles * 64 * sizeof(float));
     if (e == hipSuccess && (idx->flags & QV_FLAG_ROWMAJOR))
         e = regrow(&idx->d_rowmaj, (size_t)idx->n_rows * idx->dim * sizeof(float), new_tiles * 64 * (size_t)idx->dim * sizeof(float));
+    if (e == hipSuccess && idx->wants_rowmaj16()) {
+        // the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE): an accelerator — when it does not fit, the index frees it and graph traversals walk as without
+        // (QV_TEST_ROWMAJ16_OOM: the same for tests)
+        hipError_t eg = getenv("QV_TEST_ROWMAJ16_OOM") ? hipErrorOutOfMemory
+                                                       : regrow(&idx->d_rowmaj16, (size_t)idx->n_rows * idx->dim * sizeof(uint16_t), new_tiles * 64 * (size_t)idx->dim * sizeof(uint16_t));
+        if (eg == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            (void)hipFree(idx->d_rowmaj16); idx->d_rowmaj16 = nullptr; idx->rowmaj16_lost = true;
+        } else e = eg;
+    }
     if (e == hipSuccess && idx->wants_plane()) {
         // the bfloat16 copy: required under QV_FLAG_BF16_ROWS; otherwise (the default on cosine / dot indexes and on QV_FLAG_L2_SCAN_PLANE ones, for the single-query bound
         // scan) an accelerator — when it does not fit, the index frees it and carries on without: searches take the exact scan
@@ -224,7 +234,7 @@ void qv_index_destroy(qv_index* idx) {
     (void)hipDeviceSynchronize();
     for (SearchCtx* c : idx->all_ctx) { c->release(); delete c; }
     for (auto& kv : idx->stream_ws) { kv.second->ws.release(); kv.second->tickets.release(); delete kv.second; }
-    (void)hipFree(idx->d_tiles); (void)hipFree(idx->d_rnorm); (void)hipFree(idx->d_alive); (void)hipFree(idx->d_rres); (void)hipFree(idx->d_rowmaj); (void)hipFree(idx->d_bf16); (void)hipFree(idx->d_bound_stats);
+    (void)hipFree(idx->d_tiles); (void)hipFree(idx->d_rnorm); (void)hipFree(idx->d_alive); (void)hipFree(idx->d_rres); (void)hipFree(idx->d_rowmaj); (void)hipFree(idx->d_rowmaj16); (void)hipFree(idx->d_bf16); (void)hipFree(idx->d_bound_stats);
     (void)hipFree(idx->d_plane8); (void)hipFree(idx->d_rscale8); (void)hipFree(idx->d_rres8);
     idx->mut_stage.release();
     delete idx;
@@ -1893,7 +1903,10 @@ int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {
     } else if (what == QV_DEBUG_PLANE) {
         if (!idx->wants_plane() || (tiles && !idx->d_bf16)) return fail(QV_ERR_UNSUPPORTED, "this index keeps no bfloat16 copy");
         src = idx->d_bf16; need = tiles * idx->bf16_tile_bytes();
-    } else return fail(QV_ERR_INVALID_ARG, "what must be 0 (norms), 1 (residuals) or 2 (the bfloat16 copy); got %d", what);
+    } else if (what == QV_DEBUG_ROWMAJ16 && (idx->flags & QV_FLAG_GRAPH_PLANE)) {   // (an index created without the flag answers as it always did: an unknown code)
+        if (!idx->wants_rowmaj16() || (tiles && !idx->d_rowmaj16)) return fail(QV_ERR_UNSUPPORTED, "this index keeps no row-order bfloat16 copy");
+        src = idx->d_rowmaj16; need = (size_t)idx->n_rows * idx->dim * sizeof(uint16_t);
+    } else return fail(QV_ERR_INVALID_ARG, "what must be 0 (norms), 1 (residuals), 2 (the bfloat16 copy) or 3 (the row-order bfloat16 copy); got %d", what);
     if (bytes < need) return fail(QV_ERR_INVALID_ARG, "%zu bytes given, %zu needed", bytes, need);
     if (need == 0) return QV_OK;
     if (!out) return fail(QV_ERR_INVALID_ARG, "out is null");

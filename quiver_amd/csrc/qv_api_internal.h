@@ -98,6 +98,8 @@ struct qv_index {
     uint64_t* d_alive = nullptr;
     float* d_rres = nullptr;                   // |r - bf16(r)| per row: refreshed by every call that writes rows
     float* d_rowmaj = nullptr;
+    uint16_t* d_rowmaj16 = nullptr;            // the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE): written wherever d_rowmaj is
+    bool rowmaj16_lost = false;                // it could not be allocated: the index carries on without it
     uint16_t* d_bf16 = nullptr;                // the bfloat16 copy (QV_FLAG_BF16_ROWS, and by default on cosine / dot indexes): refreshed by every call that writes rows
     bool plane_lost = false;                   // the default copy could not be allocated: the index carries on without it
     qv::BoundKnobs bound = {};                 // qv_index_set_bound_scan, and by qv::BoundForm the four qv_index_set_bound_plane*
@@ -137,6 +139,7 @@ struct qv_index {
         v.plane8 = d_plane8; v.rscale8 = d_rscale8; v.rres8 = d_rres8; v.bound_plane = bound.plane[qv::bound_one]; v.bound_plane_filtered = bound.plane[qv::bound_one_filtered]; v.bound_plane_mq = bound.plane[qv::bound_mq]; v.bound_plane_filtered_mq = bound.plane[qv::bound_mq_filtered];
         v.dim = dim; v.dim4 = dim4; v.n_rows = n_rows; v.n_tiles = (n_rows + 63) / 64; v.metric = metric; v.filter = filter;
         v.l2_planes = l2_planes() ? 1 : 0;
+        v.rowmaj16 = d_rowmaj16;
         return v;
     }
     // a Euclidean index that asked for the scan planes (QV_FLAG_L2_SCAN_PLANE; on every other metric the flag does nothing)
@@ -150,6 +153,10 @@ struct qv_index {
     // ... and the 8-bit plane wherever they keep that copy BY DEFAULT and the 8-bit stage can walk the rows (whole 16-dimension steps, int32 sums)
     bool wants_plane8() const {
         return !(flags & QV_FLAG_NO_SCAN_PLANE) && !plane_lost && !plane8_lost && plane_metric() && (dim & 15u) == 0 && dim <= 4096;
+    }
+    // the row-order bfloat16 copy a graph's rejecting hops read: asked for, beside the float32 row-major copy, on the bound's metrics, whole 64-element slabs
+    bool wants_rowmaj16() const {
+        return (flags & QV_FLAG_GRAPH_PLANE) && (flags & QV_FLAG_ROWMAJOR) && !rowmaj16_lost && (metric == QV_COSINE || metric == QV_DOT) && (dim & 63u) == 0 && dim <= 4096;
     }
     size_t plane8_tile_bytes() const { return (size_t)dim * 64; }
     size_t tile_bytes() const { return (size_t)dim4 * 64 * 16; }

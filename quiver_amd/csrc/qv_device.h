@@ -15,6 +15,7 @@
 //   rres    float  [n_tiles*64]              per-row |r - bf16(r)|, rounded up: what the one-term bfloat16 filter loses of a row
 //                                            (qv_batched.hip: its error bound is per row and per query, not a worst case)
 //   rowmaj  float  [rows][dim]               optional row-major copy (QV_FLAG_ROWMAJOR)
+//   rowmaj16 bf16  [rows][dim]               optional bfloat16 image of it (QV_FLAG_GRAPH_PLANE): what a rejecting graph hop reads
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,6 +55,8 @@ struct IndexView {
     int       bound_plane_mq; // qv_index_set_bound_plane_mq: the same three values for an unfiltered shared pass of 2 - 8 queries, a knob of its own
     int       bound_plane_filtered_mq; // qv_index_set_bound_plane_filtered_mq: the same three values for a filtered shared pass of 2 - 8 queries, a knob of its own
     int       l2_planes;  // a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE: bound_ask asks the rules as QV_RULE_L2_PLANES (0 on every other index)
+    uint16_t* rowmaj16;   // may be null: bfloat16 copy of the rows in row order, [rows][dim] (QV_FLAG_GRAPH_PLANE: cosine / dot, rowmaj kept, dim a multiple of
+                          // 64 up to 4096); element = (__bf16)x, the conversion k_row_residual measures.  Written wherever rowmaj is (k_rowmaj16)
 };
 
 struct GraphView {
@@ -90,6 +93,8 @@ struct HnswOpts {
     uint32_t        front     = 0;        // set by launch_hnsw_search_wave for its wave-per-query form: which parts of the round-6 hop are on (qv_hnsw.hip)
     uint32_t*       next      = nullptr;  // set by launch_hnsw_search_wave: the call's query counter (zeroed by k_hnsw_prep_queries): a wave slot that
                                           // finishes its traversal takes the next unclaimed query instead of a fixed stride of them
+    unsigned long long* rj_stats = nullptr; // [3] the graph's reject counters (qv_graph_reject_stats); non-null = this call asked for the rejecting
+                                          // form (qv_graph_reject_applies said yes): launch_hnsw_search_wave takes it where its own conditions hold
 };
 
 // the mutable arrays of a graph under construction (qv_build.hip); every link carries its distance
@@ -369,6 +374,7 @@ uint32_t hnsw_vis_hash_cap(uint32_t ef);                 // hash entries per wav
 
 // wave-resident form (no LDS heaps); count_out = 0xFFFFFFFE for queries that met equal distances / NaN
 uint32_t hnsw_wave_grid(int cus, int metric, uint32_t dim4);
+uint32_t hnsw_lat_nq_cap(int cus);                        // the largest call launch_hnsw_search_wave hands to its latency form
 hipError_t launch_hub_build(const IndexView& v, const GraphView& g, const uint32_t* d_hub_rows, uint32_t H, float* d_hub_tiles, double* d_hub_rnorm,
                             uint16_t* d_slot_of, uint16_t* d_l0_hub, hipStream_t s);
 hipError_t launch_hub_table(const IndexView& v, const float* d_hub_tiles, const double* d_hub_rnorm, uint32_t H, const float* d_queries, void* d_qblk, uint32_t nq,

@@ -51,6 +51,11 @@ struct qv_graph {
     Buf vis_bits; uint32_t vis_bits_words = 0, vis_bits_slots = 0;
     uint32_t grid = 0;                          // wave slots of the wave-resident kernel
     std::atomic<uint64_t> tie_reruns{0};
+    // rejecting neighbours on the index's row-order bfloat16 copy (qv_graph_set_reject_plane): the mode, and the kernel's counters
+    // (three device words, allocated and zeroed with the graph: graph_common_init)
+    static int reject_default() { static const int m = [] { const char* e = getenv("QV_GRAPH_REJECT"); const int x = e ? atoi(e) : 0; return x == 1 || x == 2 ? x : 0; }(); return m; }
+    int reject_mode = reject_default();
+    unsigned long long* d_rj_stats = nullptr;
     std::mutex mu;                              // the graph's OWN buffers below (device-form traversals, construction, export): one user at a time
     // host-pointer searches: a context each (pool), and a front that lets concurrent small calls share a traversal batch
     // (qv_coalesce.h).  A traversal is a chain of hops, so a lone batch does not fill the chip and a second caller should not wait for the
@@ -181,6 +186,10 @@ int graph_common_init(qv_graph* g) {
     g->grid = qv::hnsw_wave_grid(g->idx->cus, g->idx->metric, g->idx->dim4);
     HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&g->ev_last, hipEventDisableTiming));
+    // the reject counters (qv_graph_reject_stats): three device words, zeroed here once — no traversal call allocates or synchronises for them
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g->d_rj_stats), 32));
+    HIPCHK(hipMemset(g->d_rj_stats, 0, 32));
+    HIPCHK(hipStreamSynchronize(nullptr));                              // (the graph's streams are non-blocking: the fill has run before a kernel adds)
     return QV_OK;
 }
 
@@ -229,6 +238,7 @@ void qv_graph_destroy(qv_graph* g) {
     (void)hipFree(g->d_level); (void)hipFree(g->d_l0deg); (void)hipFree(g->d_l0links); (void)hipFree(g->d_upoff); (void)hipFree(g->d_uplinks);
     (void)hipFree(g->d_l0dist); (void)hipFree(g->d_updist);
     g->vis_hash.release(); g->vis_bits.release();
+    (void)hipFree(g->d_rj_stats);
     g->d_qblk.release(); g->d_rows.release(); g->d_dist.release(); g->d_cnt.release(); g->d_ev.release();
     g->h_counters.release();
     { auto& hb = g->hubs; hb.tiles.release(); hb.rnorm.release(); hb.rows.release(); hb.l0_hub.release(); hb.slot_of.release(); hb.hist.release(); hb.table.release(); }
@@ -323,6 +333,10 @@ int traverse_wave(qv_graph* g, const float* dq, void* qblk, Buf* table, uint32_t
                   uint32_t* d_rows, float* d_dist, uint32_t* d_cnt, uint32_t* d_ev, hipStream_t s) {
     qv_index* idx = g->idx;
     auto& hb = g->hubs;
+    if (!hubs_possible(g, nq) &&
+        qv_graph_reject_applies(idx->metric, idx->dim, g->g.n_nodes, nq, std::max(ef, k), idx->cus, g->reject_mode, idx->d_rowmaj16 != nullptr, g->g.has_dead ? 1 : 0, g->g.max_m0) == 1) {
+        wo.rj_stats = g->d_rj_stats;
+    }
     if (hubs_possible(g, nq)) {
         {
             std::shared_lock<std::shared_mutex> rl(hb.mu);
@@ -556,6 +570,43 @@ int qv_graph_search(qv_graph* g, const float* queries, uint32_t nq, uint32_t k, 
         [] { return qv_last_error(); }, err, sizeof(err));
     if (rc != QV_OK && err[0]) return fail(rc, "%s", err);
     return rc;
+}
+
+int qv_graph_set_reject_plane(qv_graph* g, int mode) {
+    if (!g) return fail(QV_ERR_INVALID_ARG, "graph is null");
+    if (mode < QV_GRAPH_REJECT_AUTO || mode > QV_GRAPH_REJECT_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (auto), 1 (always) or 2 (never); got %d", mode);
+    g->reject_mode = mode;
+    return QV_OK;
+}
+int qv_graph_reject_stats(qv_graph* g, uint64_t* out) {
+    if (!g || !out) return fail(QV_ERR_INVALID_ARG, "graph/out is null");
+    out[0] = out[1] = out[2] = 0;
+    out[3] = g->idx->d_rowmaj16 ? 1 : 0;
+    HIPCHK(hipSetDevice(g->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (g->d_rj_stats) {
+        unsigned long long h[3] = {0, 0, 0};
+        HIPCHK(hipMemcpy(h, g->d_rj_stats, sizeof(h), hipMemcpyDeviceToHost));
+        out[0] = h[0]; out[1] = h[1]; out[2] = h[2];
+    }
+    return QV_OK;
+}
+// The rule of traverse_wave, stated once.  AUTO takes the cells measured faster and nothing more (profiles/LAB_r17_graph_reject.md: 1M x 768, cosine,
+// MaxLevel 1, list sizes 64 / 128 / 256, 8192 and 32768 queries per call — "always" ahead of "never" by 13 - 31 %, beyond both arms' spread, in every cell).
+int qv_graph_reject_applies(int metric, uint32_t dim, uint32_t n_nodes, uint32_t nq, uint32_t ef_search, int cus, int mode, int has_plane,
+                            int has_tombstones, uint32_t max_m0) {
+    if (metric < 0 || metric >= QV_METRIC_COUNT) return fail(QV_ERR_INVALID_ARG, "unknown metric %d", metric);
+    if (mode < QV_GRAPH_REJECT_AUTO || mode > QV_GRAPH_REJECT_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (auto), 1 (always) or 2 (never); got %d", mode);
+    if (cus <= 0) return fail(QV_ERR_INVALID_ARG, "cus must be positive");
+    if (dim == 0) return fail(QV_ERR_INVALID_ARG, "dimension must be positive");
+    if (mode == QV_GRAPH_REJECT_NEVER || !has_plane || has_tombstones || max_m0 > 32u) return 0;
+    if (metric != QV_COSINE && metric != QV_DOT) return 0;
+    if ((dim & 63u) != 0 || dim > 4096u) return 0;                       // (an index of such a dimension keeps no copy: has_plane cannot be true)
+    if (nq <= qv::hnsw_lat_nq_cap(cus)) return 0;                        // the latency form's calls
+    if (mode == QV_GRAPH_REJECT_ALWAYS) return 1;
+    // AUTO: the measured cells.  Dot, other dimensions, smaller and larger graphs, smaller calls and other list sizes are unmeasured: they keep the unchanged kernels.
+    // One dimension and one graph size were measured: the rule takes that dimension and graphs from that size to below twice it.
+    return metric == QV_COSINE && dim == 768u && n_nodes >= 1000000u && n_nodes < 2000000u && nq >= 8192u && ef_search >= 64u && ef_search <= 256u ? 1 : 0;
 }
 
 int qv_graph_coalesce_stats(qv_graph* g, uint64_t out[8]) {

@@ -2,6 +2,7 @@
 // traversals in flight and, for batches of at most one query per CU, as a workgroup of eight waves per query: "the latency form")
 // (shared helpers, the arithmetic contract and the build flags: qv_kernels.h)
 #include "qv_kernels.h"
+#include "qv_bound.h"
 
 namespace qv {
 
@@ -495,7 +496,9 @@ __device__ __forceinline__ void slab_accumulate_qreg(typename MT<M>::A& acc, con
     }
 }
 // The caller has waited for slab 0 (vmcnt(0)).  n <= 32.  qres: the query's float32 words in LDS.
-template <int M>
+// PRE = false: no slab is there yet (the survivors of a rejecting hop, compacted in batch[0..n)): slab 0 is requested here and every
+// slab is walked at position `lane` — the same chain through the same resident query, one round trip more.
+template <int M, bool PRE = true>
 __device__ __forceinline__ float hnsw_eval_hop_front(const IndexView& v, const lds_u32* batch_l, lds_u8* slabs_l, const QConst& qc, uint32_t n, uint32_t pos, uint32_t lane,
                                                      const lds_u32* qres) {
     const uint32_t nslab = v.dim4 >> 3;
@@ -508,20 +511,76 @@ __device__ __forceinline__ float hnsw_eval_hop_front(const IndexView& v, const l
     typename MT<M>::A acc = 0;
     uint32_t qw = qres[lane & 31u];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if constexpr (!PRE) dma_issue_slab<kHnswSlab>(role, 0, v.dim4, slabs_l);   // (every earlier read of the buffer has been waited for)
     for (uint32_t sl = 0; sl < nslab; sl++) {
-        if (sl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // slab sl has landed
+        if (sl || !PRE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // slab sl has landed
         uint32_t qn = 0;
         if (sl + 1 < nslab) {                                           // the next slab lands while this one is consumed
             dma_issue_slab<kHnswSlab>(role, sl + 1, v.dim4, slabs_l + ((sl + 1) & 1) * kHnswSlabBytes);
             qn = qres[(sl + 1) * 32u + (lane & 31u)];
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (me) slab_accumulate_qreg<M>(acc, slabs_l + (sl & 1) * kHnswSlabBytes, sl ? lane : pos, qw);
+        if (me) slab_accumulate_qreg<M>(acc, slabs_l + (sl & 1) * kHnswSlabBytes, (sl || !PRE) ? lane : pos, qw);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this slab's buffer is read before it is refilled
         qw = qn;
     }
     return me ? finalize<M>(acc, qc, rn) : 0.0f;
+}
+
+// ---- a hop that rejects on the row-order bfloat16 copy (IndexView::rowmaj16) ------------------------------------------------------
+// A hop that STARTS with a full list admits only rows below the worst distance w it starts with (hnsw.go:553 is a strict <, and w only
+// falls within a hop), and the reference never looks at a rejected row's distance again.  So the hop's front requests slab 0 of every
+// link from rowmaj16 instead — 128 bytes = 64 elements of a row, the same piece shape, swizzle and buffers — and stage 1 below walks
+// the new rows' bfloat16 images: lane r computes S~ as ONE float32 chain of dim fused multiply-adds over the caller's float32 query
+// words (resident, by v_readlane) times the widened elements, in element order.  That is the chain qv_bound.h states its margin for
+// (K = dim roundings, no partial chains), so bound_scan_interval<M> applies as it stands; a row whose lower end is not below w is
+// dropped without its float32 row being read, every other row is evaluated as always (hnsw_eval_hop_front<M, false>).
+// One slab of the image: 8 chunks of 8 elements; lane i of the wave holds query word 64 sl + i.
+__device__ __forceinline__ void slab_accumulate_bf16(float& acc, const lds_u8* buf, uint32_t r, uint32_t qw) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(3))) u4* lds_u4p;
+    const uint32_t mg = r >> 3, mr = r & 7, msw = mr ^ (mg & 1);
+    const lds_u8* mine = buf + mg * 1024 + mr * 128;
+    u4 x[2];
+    x[0] = *(lds_u4p)(mine + ((0u ^ msw) << 4));
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        const int cur = c & 1, nxt = cur ^ 1;
+        if (c + 1 < 8) x[nxt] = *(lds_u4p)(mine + (((uint32_t)(c + 1) ^ msw) << 4));
+        // a word holds elements 2j (low half) and 2j + 1 (high half); widening a bfloat16 is a shift
+#define QV_BF2(W, J) acc = __builtin_fmaf(__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)qw, 8 * c + J)), __uint_as_float((W) << 16), acc); \
+                     acc = __builtin_fmaf(__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)qw, 8 * c + J + 1)), __uint_as_float((W) & 0xFFFF0000u), acc);
+        QV_BF2(x[cur].x, 0) QV_BF2(x[cur].y, 2) QV_BF2(x[cur].z, 4) QV_BF2(x[cur].w, 6)
+#undef QV_BF2
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// S~ of the rows batch[0..n) (n <= 32) on lanes 0..n-1.  The caller has waited for slab 0 of the image (vmcnt(0)); row r's slab 0 sits at
+// adjacency position `pos`, its later slabs at position r.  dim is a multiple of 64.  qres: the query's float32 words in LDS.
+__device__ __forceinline__ float hnsw_hop_chain16(const IndexView& v, const lds_u32* batch_l, lds_u8* slabs_l, uint32_t n, uint32_t pos, uint32_t lane,
+                                                  const lds_u32* qres) {
+    const uint32_t nslab = v.dim >> 6;
+    const bool me = lane < n;
+    DmaRole role;                                                       // (a row of the image is dim / 2 float32 words, dim4 / 2 chunks)
+    dma_role(role, reinterpret_cast<const float*>(v.rowmaj16), v.dim >> 1, batch_l, n, lane);
+    float acc = 0.0f;
+    uint32_t qw = qres[lane];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    for (uint32_t sl = 0; sl < nslab; sl++) {
+        if (sl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // slab sl has landed
+        uint32_t qn = 0;
+        if (sl + 1 < nslab) {                                           // the next slab lands while this one is consumed
+            dma_issue_slab<kHnswSlab>(role, sl + 1, v.dim4 >> 1, slabs_l + ((sl + 1) & 1) * kHnswSlabBytes);
+            qn = qres[(sl + 1) * 64u + lane];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (me) slab_accumulate_bf16(acc, slabs_l + (sl & 1) * kHnswSlabBytes, sl ? lane : pos, qw);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this slab's buffer is read before it is refilled
+        qw = qn;
+    }
+    return acc;
 }
 
 #ifdef QV_HNSW_P512
@@ -1057,7 +1116,9 @@ k_hnsw_search(IndexView v, GraphView g, const typename MT<M>::Q* __restrict__ qb
 }
 
 
-template <int M, int U, int S, bool QLDS, int W = 1>
+// RJ (W == 1, QLDS, cosine and dot; launch_hnsw_search_wave): level-0 hops of the bucketed path that start with a full list reject on the
+// row-order bfloat16 copy first ("a hop that rejects on the row-order bfloat16 copy" above).  RJ = false is the kernel as it was.
+template <int M, int U, int S, bool QLDS, int W = 1, bool RJ = false>
 __global__ void __launch_bounds__(64 * W)
 k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict__ qblk, const double* __restrict__ qconst, uint32_t nq, uint32_t k, uint32_t ef_search,
                    HnswOpts o,
@@ -1115,6 +1176,9 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
     uint64_t expd[S];         // wave-uniform: bit l of expd[s] = entry (s,l) already expanded
     uint32_t n_list = 0; bool tie = false;
     uint32_t n_eval = 0;
+    // RJ: the margin's gamma (once), whether the bound works with this query's norm (once per query, wave-uniform), and the query's counters
+    double rj_gamma = 0.0; bool rj_q = false; uint32_t rj_ev = 0, rj_rej = 0;
+    if constexpr (RJ) rj_gamma = bound_scan_gamma(v.dim);
 
     // distance of the query to batch[lane] for lane < n  ->  64-bit key (all lanes return; dead beyond n)
     auto eval_keys = [&](uint32_t n) -> uint64_t {
@@ -1279,6 +1343,7 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
         q_g = qblk + (size_t)qi * v.dim4 * 4;
         qc.qn = qconst[(size_t)qi * 2]; qc.qn32 = (float)qconst[(size_t)qi * 2 + 1];
         n_eval = 0; tie = false;
+        if constexpr (RJ) { rj_q = bound_scan_norm_ok(qc.qn, v.dim) && o.hub_H == 0; rj_ev = 0; rj_rej = 0; }
         if (front) {                                                    // the query's float32 words into LDS, once per traversal
             const uint32_t qbytes = v.dim * 4u;
             const float* q32 = o.q32 + (size_t)qi * v.dim;
@@ -1321,6 +1386,7 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
                 uint32_t nb;
                 bool fronted = false, ffresh = false, fhub = false; uint32_t fc = 0xFFFFFFFFu, fold = kVisEmpty, fpos = 0, nrow = 0, frank = 0; uint32_t* fword = nullptr;
                 uint64_t fmask = 0; float fdtab = 0.0f;
+                bool rj_hop = false; uint32_t rj_w = 0;                      // RJ: this hop rejects on the bfloat16 image; the worst distance it starts with
                 if (first) {                                                 // :492-506: the entry point itself
                     first = false;
                     wsync();
@@ -1358,6 +1424,7 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
                             hl = (o.l0_hub && lane < g.max_m0) ? (uint32_t)o.l0_hub[(size_t)cur * g.max_m0 + lane] : 0xFFFFu;
                         }
                         if (fdeg > 32u) fdeg = 32u;
+                        if constexpr (RJ) { if (rj_q && n_list >= ef) { rj_hop = true; rj_w = (uint32_t)(entry_at(ef - 1) >> 32); } }
                         fc = lane < fdeg ? cl : 0xFFFFFFFFu;
                         bool valid = fc < g.n_nodes;
                         if ((repeats_in_list(fc, fdeg) >> lane) & 1ull) valid = false;   // (a repeated node counts at its first occurrence, see below)
@@ -1372,11 +1439,11 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
                             if (lane < 32u) batch[32 + lane] = (valid && !fhub) ? fc : c0;   // every adjacency position names a row that exists
                             wfence();
                             HTICK(2);
-                            DmaRole r0;
-                            dma_role(r0, v.rowmaj, v.dim, batch_l + 32, fdeg, lane);
+                            DmaRole r0;                                      // (a rejecting hop: slab 0 of the bfloat16 image, dim / 2 words a row)
+                            dma_role(r0, rj_hop ? reinterpret_cast<const float*>(v.rowmaj16) : v.rowmaj, rj_hop ? v.dim >> 1 : v.dim, batch_l + 32, fdeg, lane);
                             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #ifndef QV_HNSW_P512
-                            dma_issue_slab<kHnswSlab>(r0, 0, v.dim4, slabs_l);       // slab 0 of every such link, beside the visited test
+                            dma_issue_slab<kHnswSlab>(r0, 0, rj_hop ? v.dim4 >> 1 : v.dim4, slabs_l);       // slab 0 of every such link, beside the visited test
 #endif
                         }
                         float dtab = 0.0f;
@@ -1484,7 +1551,33 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
                 uint64_t have;                                               // the lanes of kx that hold a neighbour (adjacency order = lane order)
                 if (fronted) {
                     float dd = 0.0f;
-                    if (nrow) {
+                    bool rj_keep = true; uint32_t erank = frank;             // RJ: this link survived stage 1; its rank among the survivors
+                    if (rj_hop) {
+                        if constexpr (RJ) {
+                            // stage 1: S~ of every new row from its image, the bound scan's interval, and out with the rows whose lower end is
+                            // not below the worst distance the hop started with.  A row the bound says nothing about always survives.
+                            const bool me = lane < nrow;
+                            const uint32_t myrow = me ? batch_l[lane] : 0u;
+                            double rn = 0.0; float rr = 0.0f;
+                            if (me) { rn = v.rnorm[myrow]; rr = v.rres[myrow]; }  // (land beside the image's slabs)
+                            const float sc = nrow ? hnsw_hop_chain16(v, batch_l, slabs_l, nrow, fpos, lane, qres_l) : 0.0f;
+                            bool keep = false;
+                            if (me) {
+                                float d_lo, d_hi;
+                                const bool sure = bound_scan_interval<M>(sc, qc.qn, rn, rr, v.dim, rj_gamma, d_lo, d_hi);
+                                keep = !(sure && d_lo == d_lo && ord_f32(d_lo) >= rj_w);
+                            }
+                            const uint64_t km = __ballot(keep);              // over the compacted rows
+                            const uint32_t ns = (uint32_t)__builtin_popcountll(km);
+                            rj_ev += nb; rj_rej += nrow - ns;
+                            wfence();                                        // stage 1's reads of batch[] are done
+                            if (keep) batch[__builtin_popcountll(km & ((1ull << lane) - 1))] = myrow;
+                            wfence();
+                            if (ns) dd = hnsw_eval_hop_front<M, false>(v, batch_l, slabs_l, qc, ns, 0u, lane, qres_l);
+                            rj_keep = (km >> frank) & 1ull;                  // back at the adjacency positions (frank: the link's compacted lane)
+                            erank = (uint32_t)__builtin_popcountll(km & ((1ull << frank) - 1));
+                        }
+                    } else if (nrow) {
 #ifdef QV_HNSW_P512
                         if constexpr (M == QV_COSINE || M == QV_DOT) dd = hnsw_eval_hop_p512<M>(v, batch_l, slabs_l, qc, nrow, lane, qres_l);
                         else dd = hnsw_eval_hop_front<M>(v, batch_l, slabs_l, qc, nrow, fpos, lane, qres_l);
@@ -1493,9 +1586,9 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
 #endif
                     }
                     // back to the adjacency positions: the lane of link p takes its row's distance from compacted lane frank(p), or the hub table's
-                    const float drow = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)(frank << 2), (int)__float_as_uint(dd)));
-                    kx = ffresh ? make_key(fhub ? fdtab : drow, fc) : kDeadKey;
-                    have = fmask;
+                    const float drow = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)(erank << 2), (int)__float_as_uint(dd)));
+                    kx = ffresh && rj_keep ? make_key(fhub ? fdtab : drow, fc) : kDeadKey;
+                    have = rj_hop ? __ballot(ffresh && rj_keep) : fmask;      // (a rejected row is visited and counted, and never becomes a key)
                     vis_bucket_settle(tab, bmask, bshift, fc, ffresh, fold);
                 } else { kx = eval_keys(nb); have = __ballot(lane < nb); }
                 n_eval += nb;
@@ -1570,6 +1663,11 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
             }
         }
         if (lane == 0) { count_out[qi] = cnt; if (evals_out) evals_out[qi] = n_eval; }
+        if constexpr (RJ) {                                             // the graph's counters, once per query (vector atomics, nothing returned)
+            if (lane == 0 && o.rj_stats && rj_q && !tie) {              // (a flagged query is redone from scratch by the exact-heap kernel: its partial walk counts nowhere)
+                atomicAdd(o.rj_stats, (unsigned long long)rj_ev); atomicAdd(o.rj_stats + 1, (unsigned long long)rj_rej); atomicAdd(o.rj_stats + 2, 1ull);
+            }
+        }
 #ifdef QV_HNSW_PROF
         if (lane == 0 && (blockIdx.x == 3 || blockIdx.x == 777) && qi >= nq - gridDim.x)
         {
@@ -1724,6 +1822,11 @@ uint32_t hnsw_wave_grid(int cus, int metric, uint32_t dim4) {
     per_cu = std::min<uint32_t>(per_cu, (uint32_t)cap);
     return (uint32_t)cus * per_cu;
 }
+// the largest call the latency form takes where it fits (two tiers, see below): max(compute units, QV_HNSW_LAT_TIER2 = 768) queries
+uint32_t hnsw_lat_nq_cap(int cus) {
+    static const int lat_tier2 = dev_env_int("QV_HNSW_LAT_TIER2", 768);
+    return std::max<uint32_t>((uint32_t)std::max(cus, 0), (uint32_t)lat_tier2);
+}
 hipError_t launch_hnsw_search_wave(const IndexView& v, const GraphView& g, const float* d_queries, void* d_qblk, uint32_t nq, uint32_t k, uint32_t ef,
                                    const HnswOpts& o, uint32_t grid, uint32_t* d_rows_out, float* d_dist_out,
                                    uint32_t* d_count_out, uint32_t* d_evals_out, hipStream_t s) {
@@ -1766,14 +1869,13 @@ hipError_t launch_hnsw_search_wave(const IndexView& v, const GraphView& g, const
     // (QV_HNSW_LAT_TIER2, default 768 queries) — 16 rows at once and the visited table in global memory, so that two workgroups share a CU:
     // one call of 384 / 512 / 768 / 1024 queries 6.75 / 7.13 / 7.47 / 7.89 ms a wave per query, 4.75 / 5.17 / 6.94 / 7.52 ms in this form (with the
     // exact-heap pass of their flagged queries; 8192 queries: 319 k QPS a wave per query, 264 k in this form, 183 k one workgroup per CU)
-    static const int lat_tier2 = dev_env_int("QV_HNSW_LAT_TIER2", 768);
     const bool tier2 = nq > (uint32_t)lat_cus;
     for (ol.lat_rows = tier2 ? 16u : 32u; ol.lat_rows >= 8; ol.lat_rows >>= 1) {   // the hop's rows at once; half / a quarter of them where the dimension asks for it
         lat_fixed = (size_t)kLatQOff + lat_q_bytes(v.dim4, qsize) + lat_rows_bytes(v.dim4, ol.lat_rows);
         if (lat_fixed <= (size_t)(tier2 ? 80 : 160) * 1024) break;
     }
     const bool lat_metric = v.metric == QV_COSINE || v.metric == QV_DOT || v.metric == QV_L2 || v.metric == QV_L1 || v.metric == QV_L2SQ_F64;
-    const uint32_t lat_nq_cap = std::max<uint32_t>((uint32_t)lat_cus, (uint32_t)lat_tier2);
+    const uint32_t lat_nq_cap = hnsw_lat_nq_cap(lat_cus);
     if (lat_env == 1 && lat_metric && hnsw_qlds_ok(v) && nq <= lat_nq_cap && ol.lat_rows >= 8) {
         ol.vis_lds = !tier2 && lat_fixed + (size_t)o.vis_cap * 4 <= (size_t)160 * 1024 ? 1u : 0u;
         const size_t lds_lat = lat_fixed + (ol.vis_lds ? (size_t)o.vis_cap * 4 : 0);
@@ -1791,11 +1893,26 @@ hipError_t launch_hnsw_search_wave(const IndexView& v, const GraphView& g, const
 #undef QV_HWL
         return e != hipSuccess ? e : hipGetLastError();
     }
-#define QV_HW(SS) if (deep) { QV_HWD(SS, true); } else { QV_HWD(SS, false); }
+    // The rejecting form (HnswOpts::rj_stats: the caller's rule asked for it): the kernel's own conditions — the bucketed path will be taken at
+    // level 0 (front bit 1, no tombstones, at most 32 level-0 links), a plain Search, the image there in whole 64-element slabs, no hubs, and a
+    // call beyond the latency form's reach.  Anything else launches the kernels above, as without the flag.
+    const bool rj = on.rj_stats != nullptr && v.rowmaj16 != nullptr && deep && (on.front & 1u) && !o.qlevel && !g.has_dead && g.max_m0 <= 32u && on.hub_H == 0 &&
+                    !on.hist && (v.metric == QV_COSINE || v.metric == QV_DOT) && (v.dim & 63u) == 0 && v.dim >= 64 && nq > lat_nq_cap;
+#define QV_HWR(SS) QV_DISPATCH_METRIC(v.metric, {                                                                     \
+        if constexpr (MM == QV_COSINE || MM == QV_DOT) {                                                              \
+            e = set_lds(k_hnsw_search_wave<MM, 4, SS, true, 1, true>, lds);                                           \
+            if (e != hipSuccess) return e;                                                                            \
+            hipLaunchKernelGGL((k_hnsw_search_wave<MM, 4, SS, true, 1, true>), dim3(grid), dim3(64), lds, s, v, g, static_cast<const typename MT<MM>::Q*>(d_qblk), \
+                               static_cast<const double*>(d_qconst), nq, k, ef, on,                                  \
+                               d_rows_out, d_dist_out, d_count_out, d_evals_out);                                     \
+        }                                                                                                             \
+    })
+#define QV_HW(SS) if (rj) { QV_HWR(SS); } else if (deep) { QV_HWD(SS, true); } else { QV_HWD(SS, false); }
     // list registers: S x 64 entries.  One notch more than efx needs where that is free (<= 128 VGPRs either way), so that a tie
     // group at the end of the result heap has room (ef <= 127 -> S = 2, ef = 128..256 -> S = 4; S = 8 would cost a wave per SIMD)
     if (efx < 128) { QV_HW(2); } else if (efx < 256) { QV_HW(4); } else if (efx < 320) { QV_HW(5); } else if (efx < 512) { QV_HW(8); } else { QV_HW(9); }
 #undef QV_HW
+#undef QV_HWR
 #undef QV_HWD
     return hipGetLastError();
 }

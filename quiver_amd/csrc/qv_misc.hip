@@ -330,7 +330,31 @@ k_row_state8(IndexView v, uint32_t t0) {
     v.rscale8[(size_t)t * 64 + lane] = scale;
     v.rres8[(size_t)t * 64 + lane] = bound8_row_res(bad, maxabs, n2, s2, v.dim);
 }
+// The row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE) of the rows of tiles [t0, t0 + n_tiles): rowmaj16[row][e] = (__bf16)row[e], round to nearest
+// even — the very conversion k_row_residual measures, from the same tiles, so rres[row] >= |r - rh| holds for the image a graph hop reads.
+// One thread per (row, chunk of four elements), the chunk index fastest: a row's 2 * dim bytes are written contiguously.  Whole tiles are
+// written (the storage is whole tiles; slots past the last row hold the zero rows the tiles hold).
+__global__ void __launch_bounds__(256)
+k_rowmaj16(IndexView v, uint32_t t0, uint32_t n_tiles) {
+    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+    const uint64_t total = (uint64_t)n_tiles * 64 * v.dim4;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t c = (uint32_t)(i % v.dim4);
+        const uint64_t rr = i / v.dim4;
+        const uint32_t r = (uint32_t)(rr & 63), t = t0 + (uint32_t)(rr >> 6);
+        const f4 a = reinterpret_cast<const f4*>(v.tiles)[((size_t)t * v.dim4 + c) * 64 + r];
+        const bf2 p0 = {(__bf16)a.x, (__bf16)a.y}, p1 = {(__bf16)a.z, (__bf16)a.w};
+        uint2 o; o.x = __builtin_bit_cast(uint32_t, p0); o.y = __builtin_bit_cast(uint32_t, p1);
+        reinterpret_cast<uint2*>(v.rowmaj16 + ((size_t)t * 64 + r) * v.dim)[c] = o;      // (dim is a multiple of 64 here: dim == 4 * dim4)
+    }
+}
 static hipError_t refresh_bf16(const IndexView& v, uint32_t t0, uint32_t t1, hipStream_t s) {
+    if (v.rowmaj16) {                                                  // (never behind the rows either)
+        const uint64_t total = (uint64_t)(t1 - t0 + 1) * 64 * v.dim4;
+        hipLaunchKernelGGL(k_rowmaj16, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, s, v, t0, t1 - t0 + 1);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     if (v.rres && (v.metric == QV_COSINE || v.metric == QV_DOT || v.metric == QV_L2 || v.metric == QV_L2SQ)) {
         hipLaunchKernelGGL(k_row_residual, dim3(t1 - t0 + 1), dim3(64), 0, s, v, t0);
         const hipError_t e = hipGetLastError();

@@ -103,14 +103,16 @@ def pack_where(per_query, handle_of=None):
 class DeviceIndex:
     default_filter = "auto"        # the filter kernel new indexes choose (set_filter); tests and bench.py compare the kernels through it
 
-    def __init__(self, dim: int, metric="cosine", device: int = 0, rowmajor: bool = False, bf16_rows: bool = False, filter=None, scan_plane: bool = True, l2_scan_plane: bool = False):
+    def __init__(self, dim: int, metric="cosine", device: int = 0, rowmajor: bool = False, bf16_rows: bool = False, filter=None, scan_plane: bool = True, l2_scan_plane: bool = False,
+                 graph_plane: bool = False):
         self._h = C.c_void_p()
         self.dim = int(dim)
         self.metric = metric_id(metric)
         self.device = device
         check(lib().qv_index_create(C.byref(self._h), self.dim, self.metric, device, (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) |
                                     (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE) |   # scan_plane=False: no default bfloat16 copy (cosine / dot), no bound scan
-                                    (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0)))   # l2_scan_plane=True: an "l2" index keeps the planes cosine / dot keep by default
+                                    (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0) |   # l2_scan_plane=True: an "l2" index keeps the planes cosine / dot keep by default
+                                    (_lib.QV_FLAG_GRAPH_PLANE if graph_plane else 0)))   # graph_plane=True (with rowmajor): a bfloat16 copy in row order for DeviceGraph.set_reject_plane
         f = filter if filter is not None else DeviceIndex.default_filter
         if f not in ("auto", 0):
             self.set_filter(f)
@@ -435,13 +437,18 @@ class DeviceIndex:
         check(lib().qv_index_bound_scan8_stats(self._h, out))
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
-    DEBUG_READ = {"rnorm": (0, np.float64), "rres": (1, np.float32), "plane": (2, np.uint16)}
+    DEBUG_READ = {"rnorm": (0, np.float64), "rres": (1, np.float32), "plane": (2, np.uint16), "rowmaj16": (3, np.uint16)}
 
     def debug_read(self, what: str) -> np.ndarray:
         """FOR TESTS (qv_index_debug_read): one of the arrays ingest derives per row, as the device holds it — "rnorm" (float64 per row
         slot), "rres" (float32 per row slot) or "plane" (the bfloat16 copy as uint16 words in ITS layout: the caller decodes it) — over
-        the tiles in use.  Raises QvError(QV_ERR_UNSUPPORTED) for an array this index does not keep."""
+        the tiles in use; "rowmaj16": the row-order bfloat16 copy (graph_plane=True) as uint16 [rows, dim].  Raises
+        QvError(QV_ERR_UNSUPPORTED) for an array this index does not keep."""
         code, dtype = self.DEBUG_READ[what]
+        if what == "rowmaj16":
+            out = np.empty((self.rows(), self.dim), dtype=dtype)
+            check(lib().qv_index_debug_read(self._h, code, out.ctypes.data, out.nbytes))
+            return out
         tiles = (self.rows() + 63) // 64
         per_tile = 2 * 64 * 8 * ((self.dim + 15) // 16) if what == "plane" else 64     # uint16 words of a tile of the copy: qv_index::bf16_tile_bytes() / 2 (qv_api_internal.h)
         out = np.empty(tiles * per_tile, dtype=dtype)
@@ -715,6 +722,21 @@ class DeviceGraph:
         check(lib().qv_graph_stats(self._g, C.byref(sec), C.byref(a), C.byref(b), C.byref(c)))
         return {"build_seconds": sec.value, "build_batches": a.value, "build_redo": b.value, "search_redo": c.value}
 
+    REJECT_PLANE = {"auto": 0, "always": 1, "never": 2}
+
+    def set_reject_plane(self, mode):
+        """whether traversals reject neighbours on the index's row-order bfloat16 copy (DeviceIndex(..., rowmajor=True, graph_plane=True)):
+        "auto" (where measured faster: cosine, 768 dimensions, 1M to below 2M nodes, 8192 queries or more, list sizes 64 to 256), "always" (wherever it applies: graph_reject_applies) or "never".  Results do not depend on it
+        (qv_graph_set_reject_plane)."""
+        check(lib().qv_graph_set_reject_plane(self._g, self.REJECT_PLANE.get(mode, mode)))
+
+    def reject_stats(self) -> dict:
+        """evaluations made in rejecting hops, those rejected on the copy, queries that finished unflagged in the rejecting form, and whether the
+        graph's index holds the copy (qv_graph_reject_stats; waits for the device)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_graph_reject_stats(self._g, out))
+        return {"evals": int(out[0]), "rejected": int(out[1]), "queries": int(out[2]), "plane": bool(out[3])}
+
     def export(self):
         """(levels, l0_deg, l0_links [n, max_m0], up_off, up_links [blocks, 1 + max_m]) — the form qv_graph_create takes"""
         i = self.info()
@@ -780,11 +802,12 @@ class ShardedIndex:
     one RCCL all-gather of the per-shard top-k per search, merge on the first device.  `devices` may repeat a device only
     with peer_copy=True (point-to-point exchange instead of the collective)."""
 
-    def __init__(self, dim: int, metric="cosine", devices=(0,), rowmajor: bool = False, peer_copy: bool = False, bf16_rows: bool = False, scan_plane: bool = True, l2_scan_plane: bool = False):
+    def __init__(self, dim: int, metric="cosine", devices=(0,), rowmajor: bool = False, peer_copy: bool = False, bf16_rows: bool = False, scan_plane: bool = True, l2_scan_plane: bool = False,
+                 graph_plane: bool = False):
         self._h = C.c_void_p()
         self.dim = int(dim)
         devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-        flags = (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_SHARDED_PEER_COPY if peer_copy else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) | (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE) | (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0)
+        flags = (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_SHARDED_PEER_COPY if peer_copy else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) | (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE) | (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0) | (_lib.QV_FLAG_GRAPH_PLANE if graph_plane else 0)
         check(lib().qv_sharded_create(C.byref(self._h), self.dim, metric_id(metric), devs, len(devices), flags))
 
     def close(self):
@@ -948,6 +971,17 @@ def sharded_plan_add(rows_per_shard, n: int) -> np.ndarray:
     give = np.zeros(have.size, dtype=np.uint64)
     check(lib().qv_sharded_plan_add(have.ctypes.data, have.size, n, give.ctypes.data))
     return give
+
+
+def graph_reject_applies(metric, dim: int, n_nodes: int, nq: int, ef_search: int, cus: int, mode="auto", has_plane: bool = True, has_tombstones: bool = False,
+                         max_m0: int = 32) -> bool:
+    """the traversal dispatch's own rule: whether a DeviceGraph.search call of nq queries takes the form that rejects neighbours on the
+    row-order bfloat16 copy (qv_graph_reject_applies)"""
+    rc = lib().qv_graph_reject_applies(metric_id(metric), dim, n_nodes, nq, ef_search, cus, DeviceGraph.REJECT_PLANE.get(mode, mode), 1 if has_plane else 0,
+                                       1 if has_tombstones else 0, max_m0)
+    if rc < 0:
+        check(rc)
+    return bool(rc)
 
 
 def graph_batch_size(nodes_linked: int, batch_max: int, ramp_div: int) -> int:

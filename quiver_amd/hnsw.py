@@ -23,6 +23,7 @@ class Config:                          # hnsw.go:27-41
     MaxLevel: int = 0
     DistanceFunc: object = "hnsw_euclidean"
     Seed: int = 1                      # the reference: time.Now().UnixNano() (hnsw.go:248)
+    GraphPlane: bool = False           # the device index also keeps the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE): large batches reject neighbours on it
 
 
 @dataclass
@@ -42,6 +43,8 @@ class HNSW:
     def __init__(self, config: Config = None, device: int = 0):
         c = config or Config()
         self._h = hlib().qvh_hnsw_new(_mid(c.DistanceFunc), device, c.M, c.MaxM0, c.EfConstruction, c.EfSearch, c.MaxLevel, c.Seed)
+        if c.GraphPlane:
+            hlib().qvh_hnsw_set_graph_plane(self._h, 1)
 
     def __del__(self):
         try:
