@@ -412,31 +412,52 @@ static qv::FlatPlan flat_plan(const qv_index* idx, uint32_t nq, uint32_t kk, boo
     return qv::plan_flat(v, qv::plan_scan(v.n_tiles, idx->cus), nq, kk, tickets, tickets, cand_tiles);
 }
 
+// qv_index_profile: an event pair around one launch — both events or neither (none while profiling is off, or when an event cannot be
+// made).  A launcher that takes (ev0, ev1) records them around its scan kernel itself; around one that takes none the pair is recorded
+// here, on `s` (record).  The pair joins the index's list only behind a launch that succeeded, both events recorded, and is destroyed otherwise.
+struct ProfilePair { hipEvent_t ev0 = nullptr, ev1 = nullptr; };
+static ProfilePair profile_begin(const qv_index* idx, bool record = false, hipStream_t s = nullptr) {
+    ProfilePair p;
+    if (!idx->profiling || hipEventCreate(&p.ev0) != hipSuccess) return ProfilePair{};
+    if (hipEventCreate(&p.ev1) != hipSuccess) { (void)hipEventDestroy(p.ev0); return ProfilePair{}; }
+    if (record && hipEventRecord(p.ev0, s) != hipSuccess) { (void)hipEventDestroy(p.ev0); (void)hipEventDestroy(p.ev1); return ProfilePair{}; }
+    return p;
+}
+static void profile_end(qv_index* idx, const ProfilePair& p, bool launched, bool record = false, hipStream_t s = nullptr) {
+    if (!p.ev0) return;
+    if (launched && (!record || hipEventRecord(p.ev1, s) == hipSuccess)) {
+        std::lock_guard<std::mutex> g(idx->prof_mu);
+        idx->prof_events.emplace_back(p.ev0, p.ev1);
+        return;
+    }
+    (void)hipEventDestroy(p.ev0); (void)hipEventDestroy(p.ev1);
+}
+
+// what a call may hand enqueue_search beside its queries and outputs
+struct SearchExtras {
+    const uint64_t* d_candidates = nullptr;   // row bitmap replacing the tombstone bitmap (filtered search)
+    uint32_t candidate_tiles = 0;             // with d_candidates: the tiles that hold a candidate (an upper bound known on the host)
+    uint32_t* d_tickets = nullptr;            // the stream's tickets: allows the single-launch small scan
+    uint32_t* done_flag = nullptr;            // one query: the word the last kernel writes done_seq into behind its results; *flag_used: it will
+    uint32_t done_seq = 0;
+    bool* flag_used = nullptr;
+};
+
 // shared by the host and device entry points: enqueue nq searches of list length kk
 // (kk = min(k, live)), results written with row stride k_stride
 static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
-                          void* ws, size_t ws_bytes, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
-                          const uint64_t* d_candidates = nullptr /* row bitmap replacing the tombstone bitmap (filtered search) */,
-                          uint32_t* d_tickets = nullptr /* the stream's tickets: allows the single-launch small scan */,
-                          uint32_t* done_flag = nullptr, uint32_t done_seq = 0, bool* flag_used = nullptr,
-                          uint32_t candidate_tiles = 0 /* with d_candidates: the tiles that hold a candidate (an upper bound known on the host) */) {
+                          void* ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const SearchExtras& x = SearchExtras()) {
     qv::IndexView v = idx->view();
-    if (d_candidates) v.alive = const_cast<uint64_t*>(d_candidates);   // read-only in every scan kernel
+    if (x.d_candidates) v.alive = const_cast<uint64_t*>(x.d_candidates);   // read-only in every scan kernel
     const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
-    (void)ws_bytes;
     if (kk <= (uint32_t)qv::kMaxFusedK && kk == k_stride) {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (idx->profiling) {
-            if (hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
-                std::lock_guard<std::mutex> g(idx->prof_mu);
-                idx->prof_events.emplace_back(ev0, ev1);
-            } else { ev0 = ev1 = nullptr; }
-        }
+        const ProfilePair pp = profile_begin(idx);
         // (a masked search: the bound scan's forms that skip tiles without a candidate, under the filtered rule — given tickets)
-        const uint32_t cand_tiles = d_candidates ? candidate_tiles : qv::kBoundNoFilter;
-        const qv::FlatPlan fp = flat_plan(idx, nq, kk, d_tickets != nullptr, cand_tiles);
-        hipError_t e = qv::launch_flat_topk(v, plan, fp, d_queries, nq, kk, ws, d_rows_out, d_dist_out, s, ev0, ev1, d_tickets, nq == 1 ? done_flag : nullptr, done_seq, flag_used,
-                                            fp.bound() ? idx->d_bound_stats : nullptr, cand_tiles);
+        const uint32_t cand_tiles = x.d_candidates ? x.candidate_tiles : qv::kBoundNoFilter;
+        const qv::FlatPlan fp = flat_plan(idx, nq, kk, x.d_tickets != nullptr, cand_tiles);
+        hipError_t e = qv::launch_flat_topk(v, plan, fp, d_queries, nq, kk, ws, d_rows_out, d_dist_out, s, pp.ev0, pp.ev1, x.d_tickets, nq == 1 ? x.done_flag : nullptr, x.done_seq,
+                                            x.flag_used, fp.bound() ? idx->d_bound_stats : nullptr, cand_tiles);
+        profile_end(idx, pp, e == hipSuccess);
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "%s scan launch failed: %s", fp.route == qv::FlatRoute::small ? "small" : "flat", hipGetErrorString(e));
         return QV_OK;
     }
@@ -444,12 +465,9 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
     // :677-811), and any shorter list whose output stride differs from its length: one key per row, then a radix SELECT
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) {   // (several queries: shared corpus passes through the key-per-row path below)
         // up to 128: the scan's own stream with 2 keys per lane in the wave's list, then a selection over the waves' lists
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (idx->profiling && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
-            std::lock_guard<std::mutex> g(idx->prof_mu);
-            idx->prof_events.emplace_back(ev0, ev1);
-        }
-        hipError_t e = qv::launch_flat_wide(v, plan, d_queries, nq, kk, k_stride, ws, d_rows_out, d_dist_out, s, ev0, ev1);
+        const ProfilePair pp = profile_begin(idx);
+        hipError_t e = qv::launch_flat_wide(v, plan, d_queries, nq, kk, k_stride, ws, d_rows_out, d_dist_out, s, pp.ev0, pp.ev1);
+        profile_end(idx, pp, e == hipSuccess);
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "wide scan launch failed: %s", hipGetErrorString(e));
         return QV_OK;
     }
@@ -484,65 +502,162 @@ static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uin
     return qv::full_sort_workspace_bytes(n_tiles);
 }
 
-constexpr uint32_t kHostBatch = 8192;   // queries per device pass of the host-pointer entry points
-
-// the exact scans (single-query / multi-query / full ranking), host pointers
-static int exact_search_host(qv_index* idx, const float* queries, uint32_t nq, uint32_t k,
-                             uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+// ---------------------------------------------------------------- what every host-pointer search is made of: checks, passes, a staged call --
+// The argument checks of the host forms, in the reference's order; each form passes its own wording.  *done: nothing to run, the call
+// returns QV_OK — no query, or (exact.go:96-98) an empty index: an empty result and a nil error.  check_host_inputs ends in front of
+// the empty index, where qv_index_search_rowsets checks its sets; check_host_outputs goes on from there.
+static int check_host_inputs(const qv_index* idx, uint32_t nq, bool inputs, const char* inputs_null, bool* done) {
+    *done = false;
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (nq == 0) return QV_OK;
-    if (!queries || !count_out) return fail(QV_ERR_INVALID_ARG, "queries/count_out is null");
-    if (idx->n_live == 0) {                                           // exact.go:96-98: empty index -> empty result, nil error
-        for (uint32_t q = 0; q < nq; q++) count_out[q] = 0;
-        return QV_OK;
-    }
+    if (nq == 0) { *done = true; return QV_OK; }
+    if (!inputs) return fail(QV_ERR_INVALID_ARG, "%s", inputs_null);
+    return QV_OK;
+}
+static int check_host_outputs(const qv_index* idx, uint32_t nq, uint32_t k, bool outputs, const char* outputs_null, uint32_t* count_out, bool* done) {
+    *done = idx->n_live == 0;
+    if (*done) { for (uint32_t q = 0; q < nq; q++) count_out[q] = 0; return QV_OK; }
     if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");        // exact.go:104-106
-    if (!rows_out || !dist_out) return fail(QV_ERR_INVALID_ARG, "rows_out/dist_out is null");
-    if (nq > kHostBatch) {                                                        // bound the workspace: very large batches go in slices
-        for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {
-            const int rc0 = exact_search_host(idx, queries + (size_t)q0 * idx->dim, std::min(kHostBatch, nq - q0), k,
-                                              rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
-            if (rc0 != QV_OK) return rc0;
-        }
+    if (!outputs) return fail(QV_ERR_INVALID_ARG, "%s", outputs_null);
+    return QV_OK;
+}
+static int check_host_args(const qv_index* idx, uint32_t nq, uint32_t k, bool inputs, const char* inputs_null, bool outputs, const char* outputs_null,
+                           uint32_t* count_out, bool* done) {
+    const int rc = check_host_inputs(idx, nq, inputs, inputs_null, done);
+    return rc != QV_OK || *done ? rc : check_host_outputs(idx, nq, k, outputs, outputs_null, count_out, done);
+}
+
+// Very large batches go in passes, which bounds the workspace and the staging buffers: fn(q0, m) for every pass of at most `batch` queries
+constexpr uint32_t kHostBatch = 8192;   // queries per device pass of the host-pointer entry points
+extern "C++" {
+template <typename Fn> static int in_passes(uint32_t nq, uint32_t batch, Fn&& fn) {
+    for (uint32_t q0 = 0; q0 < nq; q0 += batch) {
+        const int rc = fn(q0, std::min(batch, nq - q0));
+        if (rc != QV_OK) return rc;
+    }
+    return QV_OK;
+}
+}
+
+// The matrix-core filter walks the corpus once per 256 queries, so 257-320 queries cost two walks (2.6 ms against 1.4 ms at 1M x 768)
+// while a batch of 64 or fewer costs half a walk: beyond 256 queries a remainder of 1..64 goes in a call of its own (0 = no split).
+static uint32_t short_tail(uint32_t nq) {
+    const uint32_t rem = nq % 256;
+    return nq > 256 && rem >= 1 && rem <= 64 ? rem : 0;
+}
+
+// list i of n staged lists (stride `stride`, kk results each) into the caller's arrays at stride k, as list dest[i] (null: i), padded past kk
+static void deliver_lists(const uint32_t* h_rows, const float* h_dist, uint32_t n, uint32_t stride, uint32_t kk, uint32_t k,
+                          uint32_t* rows_out, float* dist_out, const uint32_t* dest = nullptr) {
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t* r = rows_out + (size_t)(dest ? dest[i] : i) * k;
+        float* d = dist_out + (size_t)(dest ? dest[i] : i) * k;
+        memcpy(r, h_rows + (size_t)i * stride, (size_t)kk * sizeof(uint32_t));
+        memcpy(d, h_dist + (size_t)i * stride, (size_t)kk * sizeof(float));
+        for (uint32_t j = kk; j < k; j++) { r[j] = 0xFFFFFFFFu; d[j] = __builtin_inff(); }
+    }
+}
+// the listed queries side by side (a redo: the queries a batch handed back)
+static void gather_queries(float* dst, const float* queries, const std::vector<uint32_t>& which, uint32_t dim) {
+    for (size_t i = 0; i < which.size(); i++) memcpy(dst + i * dim, queries + (size_t)which[i] * dim, dim * sizeof(float));
+}
+
+// One staged host-pointer call: what every such form does around its launches.  A pooled context of its own (stream, pinned and device
+// staging, workspace, ticket words) from open / acquire until the struct goes or release(); queries go pinned -> device, lists come
+// device -> pinned -> the caller's arrays.  The forms keep what is theirs: which filter, which plan, which launch.
+struct HostCall {
+    qv_index* idx;
+    SearchCtx* c = nullptr;
+    explicit HostCall(qv_index* i) : idx(i) {}
+    ~HostCall() { release(); }
+    HostCall(const HostCall&) = delete;
+    HostCall& operator=(const HostCall&) = delete;
+
+    int open() { HIPCHK(hipSetDevice(idx->device)); return acquire(); }
+    int acquire() { return acquire_ctx(idx, &c); }
+    void release() { if (c) release_ctx(idx, c); c = nullptr; }
+    // staging for n_vec query vectors and n_lists lists of list_len results (dist_planes: distance arrays behind each other per call)
+    int reserve(size_t n_vec, size_t n_lists, size_t list_len, size_t dist_planes = 1) {
+        const size_t qbytes = n_vec * idx->dim * sizeof(float), obytes = n_lists * list_len * sizeof(uint32_t);
+        int rc;
+        if ((rc = c->d_q.ensure(qbytes)) || (rc = c->h_q.ensure(qbytes)) || (rc = c->d_rows.ensure(obytes)) || (rc = c->d_dist.ensure(dist_planes * obytes)) ||
+            (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(dist_planes * obytes)))
+            return rc;
+        planes = dist_planes;
         return QV_OK;
     }
+    int workspace(size_t bytes) { return c->ws.ensure(bytes); }
+    // The context's ticket words (the single-launch scans'; the bound scans' control words behind them): zeroed once, left zero by the
+    // kernels.  Zeroed ON THE CONTEXT'S STREAM, ahead of the kernels that read them, for the reason given in stream_workspace.
+    int tickets(uint32_t** out) {
+        if (!c->tickets.p) {
+            const int rc = c->tickets.ensure(256);
+            if (rc != QV_OK) return rc;
+            HIPCHK(hipMemsetAsync(c->tickets.p, 0, 256, c->stream));
+        }
+        *out = static_cast<uint32_t*>(c->tickets.p);
+        return QV_OK;
+    }
+    // queries: into pinned memory (stage / stage_gather), from there to the device (send)
+    void stage(const float* vectors, size_t n_vec, size_t at_vec = 0) { memcpy(h_queries() + at_vec * idx->dim, vectors, n_vec * idx->dim * sizeof(float)); }
+    void stage_gather(const float* queries, const std::vector<uint32_t>& which) { gather_queries(h_queries(), queries, which, idx->dim); }
+    int send(size_t n_vec) {
+        HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, n_vec * idx->dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        return QV_OK;
+    }
+    // results: n lists at staging stride `stride`, device -> pinned; enqueued, not waited for (sync)
+    int fetch(size_t n, size_t stride) {
+        const size_t obytes = n * stride * sizeof(uint32_t);
+        HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, planes * obytes, hipMemcpyDeviceToHost, c->stream));
+        return QV_OK;
+    }
+    int sync() { HIPCHK(hipStreamSynchronize(c->stream)); return QV_OK; }
+    // ... and pinned -> the caller's arrays at stride k (deliver_lists)
+    void deliver(uint32_t n, uint32_t stride, uint32_t kk, uint32_t k, uint32_t* rows_out, float* dist_out, const uint32_t* dest = nullptr) const {
+        deliver_lists(h_rows(), h_dist(), n, stride, kk, k, rows_out, dist_out, dest);
+    }
+
+    hipStream_t stream() const { return c->stream; }
+    void* ws() const { return c->ws.p; }
+    float* h_queries() const { return static_cast<float*>(c->h_q.p); }
+    const float* d_queries() const { return static_cast<const float*>(c->d_q.p); }
+    uint32_t* d_rows() const { return static_cast<uint32_t*>(c->d_rows.p); }
+    float* d_dist() const { return static_cast<float*>(c->d_dist.p); }
+    uint32_t* h_rows() const { return static_cast<uint32_t*>(c->h_rows.p); }
+    float* h_dist() const { return static_cast<float*>(c->h_dist.p); }
+private:
+    size_t planes = 1;
+};
+
+// one pass of the exact scans (single-query / multi-query / full ranking): up to kHostBatch queries, the arguments checked
+static int exact_pass(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
     const uint32_t kk = std::min(k, idx->n_live);                                // exact.go:109-111
-    HIPCHK(hipSetDevice(idx->device));
-    SearchCtx* c = nullptr;
-    int rc = acquire_ctx(idx, &c);
-    if (rc != QV_OK) return rc;
-    CtxGuard guard{idx, c};
-    const size_t qbytes = (size_t)nq * idx->dim * sizeof(float);
-    const size_t obytes = (size_t)nq * kk * sizeof(uint32_t);
-    if ((rc = c->d_q.ensure(qbytes)) || (rc = c->h_q.ensure(qbytes)) || (rc = c->d_rows.ensure(obytes)) || (rc = c->d_dist.ensure(obytes)) ||
-        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(obytes)) || (rc = c->ws.ensure(search_ws_bytes(idx, nq, kk, kk, true))))
-        return rc;
-    memcpy(c->h_q.p, queries, qbytes);
+    HostCall hc(idx);
+    int rc;
+    if ((rc = hc.open()) || (rc = hc.reserve(nq, nq, kk)) || (rc = hc.workspace(search_ws_bytes(idx, nq, kk, kk, true)))) return rc;
+    SearchCtx* c = hc.c;
+    hc.stage(queries, nq);
     // small result sets are written by the last kernel straight into the (device-visible) pinned buffers: two copy commands less
     // on the latency path of a single query; large ones go through device buffers and DMA.  On a small corpus (few workgroups,
     // each staging the query once) the query is read from the pinned buffer too: no copy command at all.
     const bool direct = (size_t)nq * kk <= 1024;
     const bool q_direct = direct && nq <= 4 && idx->n_rows <= 262144;
-    if (!q_direct) HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, qbytes, hipMemcpyHostToDevice, c->stream));
+    if (!q_direct && (rc = hc.send(nq))) return rc;
     // small collections: one launch for scan + merge, and the host polls a sequence number the kernel writes behind its results
     // instead of waiting for the stream
-    uint32_t* tickets = nullptr; uint32_t* flag = nullptr; bool flag_used = false;
-    if (!c->tickets.p) { if ((rc = c->tickets.ensure(256))) return rc; HIPCHK(hipMemsetAsync(c->tickets.p, 0, 256, c->stream)); }   // (on the stream that reads them: see stream_workspace)
-    tickets = static_cast<uint32_t*>(c->tickets.p);                    // single-launch scans: the small collection's, and one query over a large one
+    SearchExtras x;
+    bool flag_used = false;
+    if ((rc = hc.tickets(&x.d_tickets))) return rc;                    // single-launch scans: the small collection's, and one query over a large one
     // (any single query whose scan is short enough to poll for: up to ~4 GB of rows, about half a millisecond)
     if (direct && (q_direct || (nq == 1 && (uint64_t)idx->n_rows * idx->dim4 * 16 <= (4ull << 30)))) {
         if (!c->h_flag.p) { if ((rc = c->h_flag.ensure(64))) return rc; *static_cast<volatile uint32_t*>(c->h_flag.p) = 0; }
-        flag = static_cast<uint32_t*>(c->h_flag.p);
+        x.done_flag = static_cast<uint32_t*>(c->h_flag.p);
         c->flag_seq++;
     }
-    rc = enqueue_search(idx, static_cast<const float*>(q_direct ? c->h_q.p : c->d_q.p), nq, kk, kk, c->ws.p, c->ws.cap,
-                        static_cast<uint32_t*>(direct ? c->h_rows.p : c->d_rows.p), static_cast<float*>(direct ? c->h_dist.p : c->d_dist.p), c->stream,
-                        nullptr, tickets, flag, c->flag_seq, &flag_used);
+    x.done_seq = c->flag_seq; x.flag_used = &flag_used;
+    rc = enqueue_search(idx, q_direct ? hc.h_queries() : hc.d_queries(), nq, kk, kk, hc.ws(), direct ? hc.h_rows() : hc.d_rows(), direct ? hc.h_dist() : hc.d_dist(), hc.stream(), x);
     if (rc != QV_OK) return rc;
-    if (!direct) {
-        HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, obytes, hipMemcpyDeviceToHost, c->stream));
-    }
+    if (!direct && (rc = hc.fetch(nq, kk))) return rc;
     bool seen = false;
     if (flag_used) {
         const volatile uint32_t* f = static_cast<const volatile uint32_t*>(c->h_flag.p);
@@ -552,18 +667,23 @@ static int exact_search_host(qv_index* idx, const float* queries, uint32_t nq, u
             if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;   // something else holds the GPU: wait properly
         }
         std::atomic_thread_fence(std::memory_order_acquire);
-        if (seen && (c->flag_seq & 63u) == 0) HIPCHK(hipStreamSynchronize(c->stream));   // (lets the runtime retire its finished commands now and then)
+        if (seen && (c->flag_seq & 63u) == 0 && (rc = hc.sync())) return rc;   // (lets the runtime retire its finished commands now and then)
     }
-    if (!seen) HIPCHK(hipStreamSynchronize(c->stream));
-    const uint32_t* hr = static_cast<const uint32_t*>(c->h_rows.p);
-    const float* hd = static_cast<const float*>(c->h_dist.p);
-    for (uint32_t q = 0; q < nq; q++) {
-        memcpy(rows_out + (size_t)q * k, hr + (size_t)q * kk, (size_t)kk * sizeof(uint32_t));
-        memcpy(dist_out + (size_t)q * k, hd + (size_t)q * kk, (size_t)kk * sizeof(float));
-        for (uint32_t i = kk; i < k; i++) { rows_out[(size_t)q * k + i] = 0xFFFFFFFFu; dist_out[(size_t)q * k + i] = __builtin_inff(); }
-        count_out[q] = kk;
-    }
+    if (!seen && (rc = hc.sync())) return rc;
+    hc.deliver(nq, kk, kk, k, rows_out, dist_out);
+    for (uint32_t q = 0; q < nq; q++) count_out[q] = kk;
     return QV_OK;
+}
+
+// the exact scans, host pointers
+static int exact_search_host(qv_index* idx, const float* queries, uint32_t nq, uint32_t k,
+                             uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    bool done;
+    if (const int rc = check_host_args(idx, nq, k, queries && count_out, "queries/count_out is null", rows_out && dist_out, "rows_out/dist_out is null", count_out, &done); rc != QV_OK || done)
+        return rc;
+    return in_passes(nq, kHostBatch, [&](uint32_t q0, uint32_t m) {
+        return exact_pass(idx, queries + (size_t)q0 * idx->dim, m, k, rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
+    });
 }
 
 // one call's worth of queries, in a context of the caller's own (what qv_index_search was before callers could share passes)
@@ -622,21 +742,29 @@ static void configure_front(const qv_index* idx, qvco::Front& front) {
     }
 }
 
+// One call through a coalescing front (coalesce_applies holds): the caller runs alone (solo), leads a group — group(g): the members' queries
+// side by side in g, its outputs sized — or rides one.  tag: what a leader needs of each member beside its queries.
+extern "C++" {
+template <typename Solo, typename GroupRun>
+static int front_submit(const qv_index* idx, qvco::Front& front, const float* queries, uint32_t nq, uint32_t k,
+                        uint32_t* rows_out, float* dist_out, uint32_t* count_out, const void* tag, Solo&& solo, GroupRun&& group) {
+    configure_front(idx, front);
+    char err[256]; err[0] = 0;
+    const int rc = front.submit(
+        0, queries, nq, idx->dim, k, rows_out, dist_out, count_out, nullptr, solo,
+        [&](qvco::Group& g, auto&) { g.size_outputs(false); return group(g); },
+        [] { return qv_last_error(); }, err, sizeof(err), tag);
+    if (rc != QV_OK && err[0]) return fail(rc, "%s", err);                // (a rider's message comes from the thread that ran its group)
+    return rc;
+}
+}
+
 int qv_index_search(qv_index* idx, const float* queries, uint32_t nq, uint32_t k,
                     uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
     if (!coalesce_applies(idx, queries, nq, k, rows_out, dist_out, count_out)) return search_direct(idx, queries, nq, k, rows_out, dist_out, count_out);
-    configure_front(idx, idx->front);
-    char err[256]; err[0] = 0;
-    const int rc = idx->front.submit(
-        0, queries, nq, idx->dim, k, rows_out, dist_out, count_out, nullptr,
-        [&] { return search_direct(idx, queries, nq, k, rows_out, dist_out, count_out); },
-        [&](qvco::Group& g, auto&) {
-            g.size_outputs(false);
-            return search_direct(idx, g.queries(), g.nq, g.kmax, g.rows.data(), g.dist.data(), g.count.data());
-        },
-        [] { return qv_last_error(); }, err, sizeof(err));
-    if (rc != QV_OK && err[0]) return fail(rc, "%s", err);                // (a rider's message comes from the thread that ran its group)
-    return rc;
+    return front_submit(idx, idx->front, queries, nq, k, rows_out, dist_out, count_out, nullptr,
+                        [&] { return search_direct(idx, queries, nq, k, rows_out, dist_out, count_out); },
+                        [&](qvco::Group& g) { return search_direct(idx, g.queries(), g.nq, g.kmax, g.rows.data(), g.dist.data(), g.count.data()); });
 }
 
 int qv_index_coalesce_stats(qv_index* idx, uint64_t out[8]) {
@@ -658,61 +786,36 @@ int qv_index_coalesce_early_rounds(qv_index* idx, uint64_t* out) {
 // records by (score, string id).
 int qv_index_search_negative(qv_index* idx, const float* query, const float* negative, uint32_t k_fetch,
                              uint32_t* rows_out, float* dist_out, float* neg_dist_out, uint32_t* count_out) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (!query || !negative || !count_out) return fail(QV_ERR_INVALID_ARG, "query/negative/count_out is null");
-    if (idx->n_live == 0) { *count_out = 0; return QV_OK; }                     // exact.go:96-98
-    if (k_fetch == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive"); // exact.go:104-106
-    if (!rows_out || !dist_out || !neg_dist_out) return fail(QV_ERR_INVALID_ARG, "rows_out/dist_out/neg_dist_out is null");
+    bool done;
+    if (const int rc0 = check_host_args(idx, 1, k_fetch, query && negative && count_out, "query/negative/count_out is null",
+                                        rows_out && dist_out && neg_dist_out, "rows_out/dist_out/neg_dist_out is null", count_out, &done); rc0 != QV_OK || done)
+        return rc0;
     const uint32_t kk = std::min(k_fetch, idx->n_live);
-    HIPCHK(hipSetDevice(idx->device));
-    SearchCtx* c = nullptr;
-    int rc = acquire_ctx(idx, &c);
+    HostCall hc(idx);
+    int rc;
+    if ((rc = hc.open()) || (rc = hc.reserve(2, 1, kk, 2)) || (rc = hc.workspace(search_ws_bytes(idx, 1, kk, kk, false)))) return rc;
+    hc.stage(query, 1);
+    hc.stage(negative, 1, 1);
+    if ((rc = hc.send(2))) return rc;
+    rc = enqueue_search(idx, hc.d_queries(), 1, kk, kk, hc.ws(), hc.d_rows(), hc.d_dist(), hc.stream());
     if (rc != QV_OK) return rc;
-    CtxGuard guard{idx, c};
-    const size_t vbytes = (size_t)idx->dim * sizeof(float), obytes = (size_t)kk * 4;
-    if ((rc = c->d_q.ensure(2 * vbytes)) || (rc = c->h_q.ensure(2 * vbytes)) || (rc = c->d_rows.ensure(obytes)) || (rc = c->d_dist.ensure(2 * obytes)) ||
-        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(2 * obytes)) || (rc = c->ws.ensure(search_ws_bytes(idx, 1, kk, kk, false))))
-        return rc;
-    memcpy(c->h_q.p, query, vbytes);
-    memcpy(static_cast<char*>(c->h_q.p) + vbytes, negative, vbytes);
-    HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, 2 * vbytes, hipMemcpyHostToDevice, c->stream));
-    float* d_dist = static_cast<float*>(c->d_dist.p);
-    rc = enqueue_search(idx, static_cast<const float*>(c->d_q.p), 1, kk, kk, c->ws.p, c->ws.cap, static_cast<uint32_t*>(c->d_rows.p), d_dist, c->stream);
-    if (rc != QV_OK) return rc;
-    hipError_t e = qv::launch_distance_rows(idx->view(), static_cast<const float*>(c->d_q.p) + idx->dim, static_cast<const uint32_t*>(c->d_rows.p), kk, d_dist + kk, c->stream);
+    hipError_t e = qv::launch_distance_rows(idx->view(), hc.d_queries() + idx->dim, hc.d_rows(), kk, hc.d_dist() + kk, hc.stream());   // the second plane: the distances to the negative example
     if (e != hipSuccess) return fail(QV_ERR_DEVICE, "distance_rows launch failed: %s", hipGetErrorString(e));
-    HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_dist.p, d_dist, 2 * obytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(rows_out, c->h_rows.p, obytes);
-    memcpy(dist_out, c->h_dist.p, obytes);
-    memcpy(neg_dist_out, static_cast<const char*>(c->h_dist.p) + obytes, obytes);
-    for (uint32_t i = kk; i < k_fetch; i++) { rows_out[i] = 0xFFFFFFFFu; dist_out[i] = __builtin_inff(); neg_dist_out[i] = __builtin_inff(); }
+    if ((rc = hc.fetch(1, kk)) || (rc = hc.sync())) return rc;
+    hc.deliver(1, kk, kk, k_fetch, rows_out, dist_out);
+    memcpy(neg_dist_out, hc.h_dist() + kk, (size_t)kk * sizeof(float));
+    for (uint32_t i = kk; i < k_fetch; i++) neg_dist_out[i] = __builtin_inff();
     *count_out = kk;
     return QV_OK;
 }
 
-int qv_index_search_masked(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint64_t* mask,
-                           uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (nq == 0) return QV_OK;
-    if (!queries || !count_out || !mask) return fail(QV_ERR_INVALID_ARG, "queries/mask/count_out is null");
-    if (idx->n_live == 0) { for (uint32_t q = 0; q < nq; q++) count_out[q] = 0; return QV_OK; }      // exact.go:96-98
-    if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");                             // exact.go:104-106
-    if (!rows_out || !dist_out) return fail(QV_ERR_INVALID_ARG, "rows_out/dist_out is null");
-    if (nq > kHostBatch) {
-        for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {
-            const int rc0 = qv_index_search_masked(idx, queries + (size_t)q0 * idx->dim, std::min(kHostBatch, nq - q0), k, mask,
-                                                   rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
-            if (rc0 != QV_OK) return rc0;
-        }
-        return QV_OK;
-    }
-    HIPCHK(hipSetDevice(idx->device));
-    SearchCtx* c = nullptr;
-    int rc = acquire_ctx(idx, &c);
+// one pass of qv_index_search_masked: up to kHostBatch queries, the arguments checked
+static int masked_pass(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint64_t* mask,
+                       uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    HostCall hc(idx);
+    int rc = hc.open();
     if (rc != QV_OK) return rc;
-    CtxGuard guard{idx, c};
+    SearchCtx* c = hc.c;
     // candidates = live AND selected; the tile loop reads whole 64-row words, so the bitmap covers every tile
     const size_t words = ((size_t)idx->n_rows + 63) / 64;
     if ((rc = c->h_mask.ensure(words * 8)) || (rc = c->d_mask.ensure(words * 8))) return rc;
@@ -728,38 +831,33 @@ int qv_index_search_masked(qv_index* idx, const float* queries, uint32_t nq, uin
     const uint32_t kk = (uint32_t)std::min<uint64_t>(k, matching);                // the first k matches of the full ranking
     for (uint32_t q = 0; q < nq; q++) count_out[q] = kk;
     if (kk == 0) return QV_OK;
-    const size_t qbytes = (size_t)nq * idx->dim * sizeof(float);
-    const size_t obytes = (size_t)nq * kk * sizeof(uint32_t);
-    if ((rc = c->d_q.ensure(qbytes)) || (rc = c->h_q.ensure(qbytes)) || (rc = c->d_rows.ensure(obytes)) || (rc = c->d_dist.ensure(obytes)) ||
-        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(obytes)))
-        return rc;
+    if ((rc = hc.reserve(nq, nq, kk))) return rc;
     // the bound scan under the mask when the filtered rule takes it: then, and only then, the call carries the context's ticket words
     // (without them every path is the one a masked search has always taken)
     const bool bound = kk <= (uint32_t)qv::kMaxFusedK && flat_plan(idx, nq, kk, true, cand_tiles).bound();
-    if ((rc = c->ws.ensure(search_ws_bytes(idx, nq, kk, kk, bound, cand_tiles)))) return rc;
-    uint32_t* tickets = nullptr;
-    if (bound) {
-        if (!c->tickets.p) { if ((rc = c->tickets.ensure(256))) return rc; HIPCHK(hipMemsetAsync(c->tickets.p, 0, 256, c->stream)); }   // (on the stream that reads them: see stream_workspace)
-        tickets = static_cast<uint32_t*>(c->tickets.p);
-    }
-    memcpy(c->h_q.p, queries, qbytes);
+    if ((rc = hc.workspace(search_ws_bytes(idx, nq, kk, kk, bound, cand_tiles)))) return rc;
+    SearchExtras x;
+    x.d_candidates = static_cast<const uint64_t*>(c->d_mask.p); x.candidate_tiles = cand_tiles;
+    if (bound && (rc = hc.tickets(&x.d_tickets))) return rc;
+    hc.stage(queries, nq);
     HIPCHK(hipMemcpyAsync(c->d_mask.p, c->h_mask.p, words * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, qbytes, hipMemcpyHostToDevice, c->stream));
-    rc = enqueue_search(idx, static_cast<const float*>(c->d_q.p), nq, kk, kk, c->ws.p, c->ws.cap,
-                        static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<const uint64_t*>(c->d_mask.p),
-                        tickets, nullptr, 0, nullptr, cand_tiles);
+    if ((rc = hc.send(nq))) return rc;
+    rc = enqueue_search(idx, hc.d_queries(), nq, kk, kk, hc.ws(), hc.d_rows(), hc.d_dist(), hc.stream(), x);
     if (rc != QV_OK) return rc;
-    HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, obytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const uint32_t* hr = static_cast<const uint32_t*>(c->h_rows.p);
-    const float* hd = static_cast<const float*>(c->h_dist.p);
-    for (uint32_t q = 0; q < nq; q++) {
-        memcpy(rows_out + (size_t)q * k, hr + (size_t)q * kk, (size_t)kk * sizeof(uint32_t));
-        memcpy(dist_out + (size_t)q * k, hd + (size_t)q * kk, (size_t)kk * sizeof(float));
-        for (uint32_t i = kk; i < k; i++) { rows_out[(size_t)q * k + i] = 0xFFFFFFFFu; dist_out[(size_t)q * k + i] = __builtin_inff(); }
-    }
+    if ((rc = hc.fetch(nq, kk)) || (rc = hc.sync())) return rc;
+    hc.deliver(nq, kk, kk, k, rows_out, dist_out);
     return QV_OK;
+}
+
+int qv_index_search_masked(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint64_t* mask,
+                           uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    bool done;
+    if (const int rc = check_host_args(idx, nq, k, queries && count_out && mask, "queries/mask/count_out is null", rows_out && dist_out, "rows_out/dist_out is null", count_out, &done);
+        rc != QV_OK || done)
+        return rc;
+    return in_passes(nq, kHostBatch, [&](uint32_t q0, uint32_t m) {
+        return masked_pass(idx, queries + (size_t)q0 * idx->dim, m, k, mask, rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
+    });
 }
 
 // ---------------------------------------------------------------- row sets: one device-resident filter per query --
@@ -904,24 +1002,6 @@ void qv_column_destroy(qv_column* col) {
     delete col;
 }
 
-// qv_index_profile around a kernel on the null stream: both events or neither, the first recorded at once; the pair joins the index's
-// list only when both are recorded behind a launch that succeeded, and is destroyed otherwise
-static void profile_events_begin(hipEvent_t* ev0, hipEvent_t* ev1) {
-    *ev0 = nullptr; *ev1 = nullptr;
-    if (hipEventCreate(ev0) != hipSuccess) { *ev0 = nullptr; return; }
-    if (hipEventCreate(ev1) != hipSuccess) { (void)hipEventDestroy(*ev0); *ev0 = nullptr; *ev1 = nullptr; return; }
-    if (hipEventRecord(*ev0, nullptr) != hipSuccess) { (void)hipEventDestroy(*ev0); (void)hipEventDestroy(*ev1); *ev0 = nullptr; *ev1 = nullptr; }
-}
-static void profile_events_end(qv_index* idx, hipEvent_t ev0, hipEvent_t ev1, bool launched) {
-    if (!ev0) return;
-    if (launched && hipEventRecord(ev1, nullptr) == hipSuccess) {
-        std::lock_guard<std::mutex> g(idx->prof_mu);
-        idx->prof_events.emplace_back(ev0, ev1);
-        return;
-    }
-    (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-}
-
 // the host mirror and the counts the searches read, from the words a kernel has just written (the null stream: the copy waits for it)
 static int rowset_mirror(qv_rowset* rs) {
     rs->host.assign(rs->words, 0);
@@ -979,10 +1059,9 @@ static int rowset_from_where(qv_index* idx, const qv::WhereTable& tab, const dou
     if (rc == QV_OK) {
         e = hipMalloc(reinterpret_cast<void**>(&rs->d_bits), std::max<size_t>((size_t)rs->words * 8, 256));
         if (e == hipSuccess && n_lits) e = hipMemcpy(rs->stage.p, literals, (size_t)n_lits * sizeof(double), hipMemcpyHostToDevice);
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;                      // qv_index_profile: the evaluation kernel alone
-        if (e == hipSuccess && idx->profiling) profile_events_begin(&ev0, &ev1);
+        const ProfilePair pp = e == hipSuccess ? profile_begin(idx, true, nullptr) : ProfilePair();   // qv_index_profile: the evaluation kernel alone, on the null stream
         if (e == hipSuccess) e = qv::launch_rowset_where(tab, static_cast<const double*>(rs->stage.p), idx->n_rows, rs->d_bits, idx->cus, nullptr);
-        profile_events_end(idx, ev0, ev1, e == hipSuccess);
+        profile_end(idx, pp, e == hipSuccess, true, nullptr);
         if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? QV_ERR_OOM : QV_ERR_DEVICE, "row set evaluation failed: %s", hipGetErrorString(e));
     }
     if (rc == QV_OK) rc = rowset_mirror(rs);
@@ -1014,10 +1093,9 @@ int qv_rowset_combine(qv_rowset* dst, const qv_rowset* a, const qv_rowset* b, in
         dst->host.resize(need, 0);
         dst->words = need;
     }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;                          // qv_index_profile: the kernel alone
-    if (idx->profiling) profile_events_begin(&ev0, &ev1);
+    const ProfilePair pp = profile_begin(idx, true, nullptr);         // qv_index_profile: the kernel alone, on the null stream
     hipError_t e = qv::launch_rowset_combine(rowset_ref(a), rowset_ref(b), op, dst->words, dst->d_bits, nullptr);
-    profile_events_end(idx, ev0, ev1, e == hipSuccess);
+    profile_end(idx, pp, e == hipSuccess, true, nullptr);
     if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row set combination failed: %s", hipGetErrorString(e));
     return rowset_mirror(dst);
 }
@@ -1184,6 +1262,13 @@ static int where_enqueue(qv_index* idx, RsFilter* fl, uint32_t nq, const WherePl
     return QV_OK;
 }
 
+// nothing can match (an empty index, a set without a live row): every one of n result slots padded (0xFFFFFFFF, +inf) by a kernel on s
+static int pad_lists(uint32_t* d_rows_out, float* d_dist_out, size_t n, hipStream_t s) {
+    hipError_t e = qv::launch_rowset_pad(d_rows_out, d_dist_out, n, s);
+    if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set pad launch failed: %s", hipGetErrorString(e));
+    return QV_OK;
+}
+
 // enqueue the pieces on s: lists [nq][k], padded past every query's matches.  d_mask: (rows + 63) / 64 words for the candidate bitmaps.
 static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const RsFilter* fl, const std::vector<RowsetPiece>& pieces,
                            void* ws, uint64_t* d_mask, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, uint32_t* d_tickets,
@@ -1196,36 +1281,28 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
         const float* q = d_queries + (size_t)p.q0 * idx->dim;
         if (p.batched) {                                              // sample bound over the sets, the filter, the exact re-score: one corpus pass for the piece
             if (!d_sets || !d_flags_out) return fail(QV_ERR_DEVICE, "filtered batch without its set table");
-            hipEvent_t ev0 = nullptr, ev1 = nullptr;
-            if (idx->profiling && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
-                std::lock_guard<std::mutex> g(idx->prof_mu);
-                idx->prof_events.emplace_back(ev0, ev1);
-            }
+            const ProfilePair pp = profile_begin(idx);
             const qv::BatchedSets bs{d_sets + p.q0, qv::filtered_batch_ppm(idx->filtered_batch_ppm)};
-            hipError_t e = qv::launch_batched(v, plan, q, p.nq, k, ws, r_out, d_out, d_flags_out, idx->cus, s, ev0, ev1, &bs);
+            hipError_t e = qv::launch_batched(v, plan, q, p.nq, k, ws, r_out, d_out, d_flags_out, idx->cus, s, pp.ev0, pp.ev1, &bs);
+            profile_end(idx, pp, e == hipSuccess);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "filtered batch launch failed: %s", hipGetErrorString(e));
             continue;
         }
         if (p.multi) {
             std::vector<qv::RowSetRef> refs(p.nq);
             for (uint32_t i = 0; i < p.nq; i++) refs[i] = rs_ref(idx, fl[p.q0 + i]);
-            hipEvent_t ev0 = nullptr, ev1 = nullptr;
-            if (idx->profiling && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
-                std::lock_guard<std::mutex> g(idx->prof_mu);
-                idx->prof_events.emplace_back(ev0, ev1);
-            }
-            hipError_t e = hipSuccess;
-            if (p.bound && d_tickets) {                               // the pass on the reduced copies (p.bound8: the 8-bit plane first), each query over its own candidates
-                if (ev0) (void)hipEventRecord(ev0, s);
-                e = qv::launch_bound_scan_mq(v, plan, q, p.nq, k, ws, d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, r_out, d_out, s, refs.data(), p.bound8);
-                if (ev1) (void)hipEventRecord(ev1, s);
-            } else e = qv::launch_rowset_topk(v, plan, q, p.nq, k, refs.data(), ws, r_out, d_out, s, ev0, ev1);
+            // the pass on the reduced copies (p.bound8: the 8-bit plane first), each query over its own candidates: its launcher takes no events
+            const bool bound = p.bound && d_tickets;
+            const ProfilePair pp = profile_begin(idx, bound, s);
+            hipError_t e = bound ? qv::launch_bound_scan_mq(v, plan, q, p.nq, k, ws, d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, r_out, d_out, s, refs.data(), p.bound8)
+                                 : qv::launch_rowset_topk(v, plan, q, p.nq, k, refs.data(), ws, r_out, d_out, s, pp.ev0, pp.ev1);
+            profile_end(idx, pp, e == hipSuccess, bound, s);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set scan launch failed: %s", hipGetErrorString(e));
             continue;
         }
         if (p.kk == 0) {
-            hipError_t e = qv::launch_rowset_pad(r_out, d_out, (size_t)p.nq * k, s);
-            if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set pad launch failed: %s", hipGetErrorString(e));
+            const int rc = pad_lists(r_out, d_out, (size_t)p.nq * k, s);
+            if (rc != QV_OK) return rc;
             continue;
         }
         const RsFilter& f = fl[p.q0];
@@ -1236,7 +1313,9 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set bitmap launch failed: %s", hipGetErrorString(e));
             cand = d_mask;
         }
-        const int rc = enqueue_search(idx, q, p.nq, p.kk, k, ws, 0, r_out, d_out, s, cand, p.nq == 1 ? d_tickets : nullptr, nullptr, 0, nullptr, p.cand_tiles);
+        SearchExtras x;
+        x.d_candidates = cand; x.candidate_tiles = p.cand_tiles; x.d_tickets = p.nq == 1 ? d_tickets : nullptr;
+        const int rc = enqueue_search(idx, q, p.nq, p.kk, k, ws, r_out, d_out, s, x);
         if (rc != QV_OK) return rc;
     }
     return QV_OK;
@@ -1249,31 +1328,18 @@ static int rowsets_check(const qv_index* idx, uint32_t nq, const qv_rowset* cons
     return QV_OK;
 }
 
-// one call's worth of queries in a context of the caller's own.  idx, queries, count_out, fl: checked by the entry points (each in its
-// own order), the filters valid; from the empty index on the order is one.
-static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const RsFilter* fl_in,
-                          uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
-    if (nq == 0) return QV_OK;
-    if (idx->n_live == 0) { for (uint32_t q = 0; q < nq; q++) count_out[q] = 0; return QV_OK; }      // exact.go:96-98
-    if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");                             // exact.go:104-106
-    if (!rows_out || !dist_out) return fail(QV_ERR_INVALID_ARG, "rows_out/dist_out is null");
-    if (nq > kHostBatch) {
-        for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {
-            const int rc0 = rowsets_direct(idx, queries + (size_t)q0 * idx->dim, std::min(kHostBatch, nq - q0), k, fl_in + q0,
-                                           rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
-            if (rc0 != QV_OK) return rc0;
-        }
-        return QV_OK;
-    }
+// one pass of rowsets_direct: up to kHostBatch queries in a context of the call's own, the arguments checked
+static int rowsets_pass(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const RsFilter* fl_in,
+                        uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
     HIPCHK(hipSetDevice(idx->device));
-    // a filtered batch beyond 256 queries with a short remainder: the remainder as a call of its own, as qv_index_search_batched cuts it
-    // (padded to whole workgroups of 256 it would cost a second walk for a few queries); each part decides its route for itself
+    // a filtered batch with a short remainder (short_tail): the remainder as a pass of its own, as qv_index_search_batched cuts it; each
+    // part decides its route for itself — and takes its context for itself, which is why this pass has none yet
     if (filtered_batch_takes(idx, nq, k, fl_in)) {
-        if (const uint32_t tail = nq > 256 && nq % 256 >= 1 && nq % 256 <= 64 ? nq % 256 : 0) {
+        if (const uint32_t tail = short_tail(nq)) {
             const uint32_t head = nq - tail;
-            const int rc0 = rowsets_direct(idx, queries, head, k, fl_in, rows_out, dist_out, count_out);
+            const int rc0 = rowsets_pass(idx, queries, head, k, fl_in, rows_out, dist_out, count_out);
             if (rc0 != QV_OK) return rc0;
-            return rowsets_direct(idx, queries + (size_t)head * idx->dim, tail, k, fl_in + head, rows_out + (size_t)head * k, dist_out + (size_t)head * k, count_out + head);
+            return rowsets_pass(idx, queries + (size_t)head * idx->dim, tail, k, fl_in + head, rows_out + (size_t)head * k, dist_out + (size_t)head * k, count_out + head);
         }
     }
     std::vector<RsFilter> fl(fl_in, fl_in + nq);                      // (the transient sets' words are placed below)
@@ -1287,19 +1353,16 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
         for (uint32_t q = 0; q < nq; q++) count_out[q] = 0;
         return QV_OK;
     }
-    SearchCtx* c = nullptr;
-    int rc = acquire_ctx(idx, &c);
+    HostCall hc(idx);
+    int rc = hc.acquire();
     if (rc != QV_OK) return rc;
-    CtxGuard guard{idx, c};
+    SearchCtx* c = hc.c;
     const size_t words = ((size_t)idx->n_rows + 63) / 64;
-    const size_t qbytes = (size_t)nq * idx->dim * sizeof(float);
-    const size_t obytes = (size_t)nq * k * sizeof(uint32_t);
-    if ((rc = c->d_mask.ensure(words * 8)) || (rc = c->d_q.ensure(qbytes)) || (rc = c->h_q.ensure(qbytes)) || (rc = c->d_rows.ensure(obytes)) ||
-        (rc = c->d_dist.ensure(obytes)) || (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(obytes)) || (rc = c->ws.ensure(ws_bytes)))
-        return rc;
-    if (!c->tickets.p) { if ((rc = c->tickets.ensure(256))) return rc; HIPCHK(hipMemsetAsync(c->tickets.p, 0, 256, c->stream)); }   // (on the stream that reads them: see stream_workspace)
-    memcpy(c->h_q.p, queries, qbytes);
-    HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, qbytes, hipMemcpyHostToDevice, c->stream));
+    uint32_t* tickets = nullptr;
+    if ((rc = c->d_mask.ensure(words * 8)) || (rc = hc.reserve(nq, nq, k)) || (rc = hc.workspace(ws_bytes)) || (rc = hc.tickets(&tickets))) return rc;
+    uint64_t* d_mask = static_cast<uint64_t*>(c->d_mask.p);
+    hc.stage(queries, nq);
+    if ((rc = hc.send(nq))) return rc;
     WherePlan wp;
     where_plan(fl.data(), nq, wp);
     if (!wp.uniq.empty()) {                                           // the call's transient sets, in the context's own buffers, on its stream
@@ -1315,7 +1378,7 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
             HIPCHK(hipMemcpyAsync(c->d_lits.p, c->h_lits.p, lbytes, hipMemcpyHostToDevice, c->stream));
             d_lits = static_cast<const double*>(c->d_lits.p);
         }
-        if ((rc = where_enqueue(idx, fl.data(), nq, wp, static_cast<uint64_t*>(c->d_where.p), static_cast<uint64_t*>(c->d_mask.p), d_lits, c->stream))) return rc;
+        if ((rc = where_enqueue(idx, fl.data(), nq, wp, static_cast<uint64_t*>(c->d_where.p), d_mask, d_lits, c->stream))) return rc;
     }
     const size_t fbytes = 2 * (size_t)nq * sizeof(uint32_t);           // a batched piece: its redo flags, then its sparse flags
     uint32_t* d_flags = nullptr;
@@ -1326,16 +1389,12 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
         for (uint32_t q = 0; q < nq; q++) refs[q] = rs_ref(idx, fl[q]);
         HIPCHK(hipMemcpyAsync(c->d_sets.p, c->h_sets.p, sbytes, hipMemcpyHostToDevice, c->stream));
     }
-    rc = rowsets_enqueue(idx, static_cast<const float*>(c->d_q.p), nq, k, fl.data(), pieces, c->ws.p, static_cast<uint64_t*>(c->d_mask.p),
-                         static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<uint32_t*>(c->tickets.p),
+    rc = rowsets_enqueue(idx, hc.d_queries(), nq, k, fl.data(), pieces, hc.ws(), d_mask, hc.d_rows(), hc.d_dist(), hc.stream(), tickets,
                          batched ? static_cast<const qv::RowSetRef*>(c->d_sets.p) : nullptr, batched ? &d_flags : nullptr);
-    if (rc != QV_OK) return rc;
-    HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, obytes, hipMemcpyDeviceToHost, c->stream));
+    if (rc != QV_OK || (rc = hc.fetch(nq, k))) return rc;
     if (batched) HIPCHK(hipMemcpyAsync(c->h_ids.p, d_flags, fbytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(rows_out, c->h_rows.p, obytes);
-    memcpy(dist_out, c->h_dist.p, obytes);
+    if ((rc = hc.sync())) return rc;
+    hc.deliver(nq, k, k, k, rows_out, dist_out);
     if (batched) {
         // The queries the batch handed back — more candidates than slots, a guessed bound that failed its check, a sparse set — through the
         // exact row-set pieces, with their filters, in this context: the transient where-words are still in d_where.
@@ -1352,25 +1411,14 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
         if (!redo.empty()) {
             const uint32_t nr = (uint32_t)redo.size();
             std::vector<RsFilter> rfl(nr);
-            for (uint32_t i = 0; i < nr; i++) {
-                rfl[i] = fl[redo[i]];
-                memcpy(static_cast<float*>(c->h_q.p) + (size_t)i * idx->dim, queries + (size_t)redo[i] * idx->dim, idx->dim * sizeof(float));
-            }
+            for (uint32_t i = 0; i < nr; i++) rfl[i] = fl[redo[i]];
             std::vector<RowsetPiece> rpieces;
             const size_t rws = rowsets_plan(idx, nr, k, rfl.data(), rpieces);
-            if ((rc = c->ws.ensure(rws))) return rc;
-            const size_t rq = (size_t)nr * idx->dim * sizeof(float), ro = (size_t)nr * k * sizeof(uint32_t);
-            HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, rq, hipMemcpyHostToDevice, c->stream));
-            rc = rowsets_enqueue(idx, static_cast<const float*>(c->d_q.p), nr, k, rfl.data(), rpieces, c->ws.p, static_cast<uint64_t*>(c->d_mask.p),
-                                 static_cast<uint32_t*>(c->d_rows.p), static_cast<float*>(c->d_dist.p), c->stream, static_cast<uint32_t*>(c->tickets.p));
-            if (rc != QV_OK) return rc;
-            HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, ro, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, ro, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            for (uint32_t i = 0; i < nr; i++) {
-                memcpy(rows_out + (size_t)redo[i] * k, static_cast<const uint32_t*>(c->h_rows.p) + (size_t)i * k, k * sizeof(uint32_t));
-                memcpy(dist_out + (size_t)redo[i] * k, static_cast<const float*>(c->h_dist.p) + (size_t)i * k, k * sizeof(float));
-            }
+            hc.stage_gather(queries, redo);
+            if ((rc = hc.workspace(rws)) || (rc = hc.send(nr))) return rc;
+            rc = rowsets_enqueue(idx, hc.d_queries(), nr, k, rfl.data(), rpieces, hc.ws(), d_mask, hc.d_rows(), hc.d_dist(), hc.stream(), tickets);
+            if (rc != QV_OK || (rc = hc.fetch(nr, k)) || (rc = hc.sync())) return rc;
+            hc.deliver(nr, k, k, k, rows_out, dist_out, redo.data());
         }
     }
     for (uint32_t q = 0; q < nq; q++) {                               // a list's results end where its padding begins (no row is 0xFFFFFFFF)
@@ -1382,12 +1430,22 @@ static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint
     return QV_OK;
 }
 
-// qv_index_search_rowsets' own checks, in its order, in front of rowsets_direct
+// one call's worth of queries.  idx, queries, count_out, fl: checked by the entry points (each in its own order), the filters valid;
+// from the empty index on the order is one.
+static int rowsets_direct(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const RsFilter* fl,
+                          uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    bool done;
+    if (const int rc = check_host_outputs(idx, nq, k, rows_out && dist_out, "rows_out/dist_out is null", count_out, &done); rc != QV_OK || done) return rc;
+    return in_passes(nq, kHostBatch, [&](uint32_t q0, uint32_t m) {
+        return rowsets_pass(idx, queries + (size_t)q0 * idx->dim, m, k, fl + q0, rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
+    });
+}
+
+// qv_index_search_rowsets' own checks, in its order — the sets in front of the empty index — in front of rowsets_direct
 static int rowsets_direct_sets(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
                                uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (nq == 0) return QV_OK;
-    if (!queries || !count_out || !sets) return fail(QV_ERR_INVALID_ARG, "queries/sets/count_out is null");
+    bool done;
+    if (const int rc = check_host_inputs(idx, nq, queries && count_out && sets, "queries/sets/count_out is null", &done); rc != QV_OK || done) return rc;
     { const int rc0 = rowsets_check(idx, nq, sets); if (rc0 != QV_OK) return rc0; }
     std::vector<RsFilter> fl(nq);
     for (uint32_t q = 0; q < nq; q++) fl[q].set = sets[q];
@@ -1399,24 +1457,17 @@ static int rowsets_direct_sets(qv_index* idx, const float* queries, uint32_t nq,
 // call: its conjunctions are evaluated together in front of the pass (where_enqueue), its handles read as they are.
 static int rowsets_submit(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const RsFilter* fl,
                           uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
-    configure_front(idx, idx->front_rs);
-    char err[256]; err[0] = 0;
-    const int rc = idx->front_rs.submit(
-        0, queries, nq, idx->dim, k, rows_out, dist_out, count_out, nullptr,
-        [&] { return rowsets_direct(idx, queries, nq, k, fl, rows_out, dist_out, count_out); },
-        [&](qvco::Group& g, auto&) {
-            g.size_outputs(false);
-            std::vector<RsFilter> all(g.nq);                          // the members' filters side by side, in the order of the group's query block
-            for (uint32_t mi = 0; mi < g.n_mem; mi++) {
-                const qvco::Member& m = g.mbuf[mi];
-                const RsFilter* mf = static_cast<const RsFilter*>(m.tag);
-                for (uint32_t i = 0; i < m.nq; i++) all[m.q0 + i] = mf[i];
-            }
-            return rowsets_direct(idx, g.queries(), g.nq, g.kmax, all.data(), g.rows.data(), g.dist.data(), g.count.data());
-        },
-        [] { return qv_last_error(); }, err, sizeof(err), fl);
-    if (rc != QV_OK && err[0]) return fail(rc, "%s", err);
-    return rc;
+    return front_submit(idx, idx->front_rs, queries, nq, k, rows_out, dist_out, count_out, fl,
+                        [&] { return rowsets_direct(idx, queries, nq, k, fl, rows_out, dist_out, count_out); },
+                        [&](qvco::Group& g) {
+                            std::vector<RsFilter> all(g.nq);          // the members' filters side by side, in the order of the group's query block
+                            for (uint32_t mi = 0; mi < g.n_mem; mi++) {
+                                const qvco::Member& m = g.mbuf[mi];
+                                const RsFilter* mf = static_cast<const RsFilter*>(m.tag);
+                                for (uint32_t i = 0; i < m.nq; i++) all[m.q0 + i] = mf[i];
+                            }
+                            return rowsets_direct(idx, g.queries(), g.nq, g.kmax, all.data(), g.rows.data(), g.dist.data(), g.count.data());
+                        });
 }
 
 int qv_index_search_rowsets(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
@@ -1445,13 +1496,8 @@ int qv_index_search_rowsets_device(qv_index* idx, const float* d_queries, uint32
     if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");
     HIPCHK(hipSetDevice(idx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (idx->n_live == 0 || idx->n_rows == 0) {
-        hipError_t e = qv::launch_rowset_pad(d_rows_out, d_dist_out, (size_t)nq * k, s);
-        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set pad launch failed: %s", hipGetErrorString(e));
-        return QV_OK;
-    }
-    for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {                // bound the workspace, as the host-pointer form does
-        const uint32_t m = std::min(kHostBatch, nq - q0);
+    if (idx->n_live == 0 || idx->n_rows == 0) return pad_lists(d_rows_out, d_dist_out, (size_t)nq * k, s);
+    return in_passes(nq, kHostBatch, [&](uint32_t q0, uint32_t m) {   // bound the workspace, as the host-pointer form does
         std::vector<RsFilter> fl(m);
         for (uint32_t q = 0; q < m; q++) fl[q].set = sets[q0 + q];
         std::vector<RowsetPiece> pieces;
@@ -1460,13 +1506,11 @@ int qv_index_search_rowsets_device(qv_index* idx, const float* d_queries, uint32
         void* ws = nullptr;
         std::unique_lock<std::mutex> ws_hold;
         uint32_t* tickets = nullptr;
-        int rc = stream_workspace(idx, s, ws_bytes + words * 8, &ws, &ws_hold, &tickets);
+        const int rc = stream_workspace(idx, s, ws_bytes + words * 8, &ws, &ws_hold, &tickets);
         if (rc != QV_OK) return rc;
-        rc = rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, ws, reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes),
-                             d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, s, tickets);
-        if (rc != QV_OK) return rc;
-    }
-    return QV_OK;
+        return rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, ws, reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes),
+                               d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, s, tickets);
+    });
 }
 
 // ---------------------------------------------------------------- filtered search by predicate: the sets live in the call's workspace --
@@ -1511,12 +1555,10 @@ static int where_wide(qv_index* idx, const float* queries, uint32_t nq, uint32_t
 
 int qv_index_search_where(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, const qv_where* filters,
                           uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (nq == 0) return QV_OK;
-    if (!queries || !count_out || !filters) return fail(QV_ERR_INVALID_ARG, "queries/filters/count_out is null");
-    if (idx->n_live == 0) { for (uint32_t q = 0; q < nq; q++) count_out[q] = 0; return QV_OK; }      // qv_index_search_rowsets' order: exact.go:96-98
-    if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");                             // exact.go:104-106
-    if (!rows_out || !dist_out) return fail(QV_ERR_INVALID_ARG, "rows_out/dist_out is null");
+    bool done;                                                        // (the filters are checked behind k and the outputs)
+    if (const int rc = check_host_args(idx, nq, k, queries && count_out && filters, "queries/filters/count_out is null", rows_out && dist_out, "rows_out/dist_out is null", count_out, &done);
+        rc != QV_OK || done)
+        return rc;
     WhereSpec small_specs[kCoalesceMaxNq];                            // (a single-query caller allocates nothing)
     RsFilter small_fl[kCoalesceMaxNq];
     std::vector<WhereSpec> big_specs;
@@ -1553,14 +1595,9 @@ int qv_index_search_where_device(qv_index* idx, const float* d_queries, uint32_t
             return fail(QV_ERR_UNSUPPORTED, "filter of query %u carries %u literals: the device-pointer form takes up to %u per filter", q, specs[q].n_lits, qv::kWhereArgLits);
     HIPCHK(hipSetDevice(idx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (idx->n_live == 0 || idx->n_rows == 0) {
-        hipError_t e = qv::launch_rowset_pad(d_rows_out, d_dist_out, (size_t)nq * k, s);
-        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set pad launch failed: %s", hipGetErrorString(e));
-        return QV_OK;
-    }
+    if (idx->n_live == 0 || idx->n_rows == 0) return pad_lists(d_rows_out, d_dist_out, (size_t)nq * k, s);
     const size_t stride = where_stride_words(idx) * 8;                // the candidate bitmap, and each transient set behind it: 256-byte aligned
-    for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {
-        const uint32_t m = std::min(kHostBatch, nq - q0);
+    return in_passes(nq, kHostBatch, [&](uint32_t q0, uint32_t m) {
         std::vector<RsFilter> fl(m);
         for (uint32_t q = 0; q < m; q++) fl[q].where = specs[q0 + q].tab.n ? &specs[q0 + q] : nullptr;
         std::vector<RowsetPiece> pieces;
@@ -1575,11 +1612,9 @@ int qv_index_search_where_device(qv_index* idx, const float* d_queries, uint32_t
         uint64_t* d_mask = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes);
         uint64_t* d_where = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes + stride);
         if ((rc = where_enqueue(idx, fl.data(), m, wp, d_where, d_mask, nullptr, s))) return rc;
-        rc = rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, ws, d_mask,
-                             d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, s, tickets);
-        if (rc != QV_OK) return rc;
-    }
-    return QV_OK;
+        return rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, ws, d_mask,
+                               d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, s, tickets);
+    });
 }
 
 int qv_index_search_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k,
@@ -1590,89 +1625,55 @@ int qv_index_search_device(qv_index* idx, const float* d_queries, uint32_t nq, u
     if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");
     HIPCHK(hipSetDevice(idx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (idx->n_live == 0) {                                           // pad everything: no results
-        HIPCHK(hipMemsetAsync(d_rows_out, 0xFF, (size_t)nq * k * sizeof(uint32_t), s));
-        std::vector<float> inf((size_t)nq * k, __builtin_inff());
-        HIPCHK(hipMemcpyAsync(d_dist_out, inf.data(), inf.size() * sizeof(float), hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return QV_OK;
-    }
+    if (idx->n_live == 0) return pad_lists(d_rows_out, d_dist_out, (size_t)nq * k, s);   // no results
     const uint32_t kk = std::min(k, idx->n_live);
     void* ws = nullptr;
     std::unique_lock<std::mutex> ws_hold;
-    uint32_t* tickets = nullptr;
-    int rc = stream_workspace(idx, s, search_ws_bytes(idx, nq, kk, k, true), &ws, &ws_hold, &tickets);
+    SearchExtras x;
+    int rc = stream_workspace(idx, s, search_ws_bytes(idx, nq, kk, k, true), &ws, &ws_hold, &x.d_tickets);
     if (rc != QV_OK) return rc;
-    return enqueue_search(idx, d_queries, nq, kk, k, ws, 0, d_rows_out, d_dist_out, s, nullptr, tickets);
+    return enqueue_search(idx, d_queries, nq, kk, k, ws, d_rows_out, d_dist_out, s, x);
 }
 
-}  // extern "C"
-
-// Internal (qv_api_internal.h), for the sharded handle: the exact scan over the rows selected by a DEVICE bitmap d_candidates
-// (already ANDed with the live rows by the caller; `matching` = its population count), enqueued on `stream`, no
-// synchronisation.  Writes [nq][k_stride] lists: min(k_stride, matching) results, the rest padded (0xFFFFFFFF, +inf).
-int qv_internal_search_candidates_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k_stride, const uint64_t* d_candidates,
-                                         uint64_t matching, uint32_t* d_rows_out, float* d_dist_out, void* stream) {
-    if (!idx || !d_queries || !d_candidates || !d_rows_out || !d_dist_out || k_stride == 0) return fail(QV_ERR_INVALID_ARG, "null argument");
-    if (nq == 0) return QV_OK;
-    HIPCHK(hipSetDevice(idx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t kk = (uint32_t)std::min<uint64_t>(k_stride, matching);
-    void* ws = nullptr;
-    std::unique_lock<std::mutex> ws_hold;
-    int rc = stream_workspace(idx, s, search_ws_bytes(idx, nq, kk, k_stride, false), &ws, &ws_hold);
-    if (rc != QV_OK) return rc;
-    return enqueue_search(idx, d_queries, nq, kk, k_stride, ws, 0, d_rows_out, d_dist_out, s, d_candidates);
+// the short tail of an unfiltered batch: one the exact scan's shared pass takes (up to 8 queries) or the filter itself
+static uint32_t batched_tail(const qv::IndexView& v, uint32_t nq, uint32_t k) {
+    const uint32_t rem = short_tail(nq);
+    return rem && (rem <= 8 || qv::batched_supported(v, rem, k)) ? rem : 0;
 }
 
-// Internal, for the sharded handle: the exact scan for the queries of a batch whose d_flags word is set (handed back by
-// qv_index_search_batched_device), enqueued on `stream` behind the batch — listed and scanned on the device, nothing read back.
-int qv_internal_redo_flagged_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_flags,
-                                    uint32_t* d_rows_out, float* d_dist_out, void* stream) {
-    if (!idx || !d_queries || !d_flags || !d_rows_out || !d_dist_out || k == 0 || k > (uint32_t)qv::kMaxSelectK) return fail(QV_ERR_INVALID_ARG, "bad argument");
-    if (nq == 0) return QV_OK;
-    HIPCHK(hipSetDevice(idx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// m queries of a larger device batch, from query q0, as a call of their own: by the filter where it takes that many, else by the exact
+// scan with their flags cleared
+static int batched_device_part(qv_index* idx, const float* d_queries, uint32_t q0, uint32_t m, uint32_t k,
+                               uint32_t* d_rows_out, float* d_dist_out, uint32_t* d_redo_flags_out, void* stream) {
+    const float* q = d_queries + (size_t)q0 * idx->dim;
+    if (qv::batched_supported(idx->view(), m, k))
+        return qv_index_search_batched_device(idx, q, m, k, d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, d_redo_flags_out + q0, stream);
+    HIPCHK(hipMemsetAsync(d_redo_flags_out + q0, 0, (size_t)m * sizeof(uint32_t), static_cast<hipStream_t>(stream)));
+    return qv_index_search_device(idx, q, m, k, d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, stream);
+}
+
+// one pass of qv_index_search_batched_device: up to kHostBatch queries that the filter takes
+static int batched_device_pass(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k,
+                               uint32_t* d_rows_out, float* d_dist_out, uint32_t* d_redo_flags_out, void* stream) {
     const qv::IndexView v = idx->view();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const uint32_t tail = batched_tail(v, nq, k)) {
+        const int rc0 = qv_index_search_batched_device(idx, d_queries, nq - tail, k, d_rows_out, d_dist_out, d_redo_flags_out, stream);
+        if (rc0 != QV_OK) return rc0;
+        return batched_device_part(idx, d_queries, nq - tail, tail, k, d_rows_out, d_dist_out, d_redo_flags_out, stream);
+    }
     const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
     void* ws = nullptr;
     std::unique_lock<std::mutex> ws_hold;
-    if (k > (uint32_t)qv::kMaxFusedK) {                               // the selection path's hand-backs: QV_ERR_UNSUPPORTED = the caller reads the flags itself
-        int rc0 = stream_workspace(idx, s, qv::flat_select_redo_workspace_bytes(v.n_tiles, nq, k, v.dim, v.dim4), &ws, &ws_hold);
-        if (rc0 != QV_OK) return rc0;
-        hipError_t e0 = qv::launch_flat_select_redo(v, plan, d_queries, nq, k, k, d_flags, ws, d_rows_out, d_dist_out, s);
-        if (e0 == hipErrorNotSupported) return QV_ERR_UNSUPPORTED;
-        if (e0 != hipSuccess) return fail(QV_ERR_DEVICE, "redo launch failed: %s", hipGetErrorString(e0));
-        return QV_OK;
-    }
-    int rc = stream_workspace(idx, s, qv::redo_workspace_bytes(plan, nq, k), &ws, &ws_hold);
+    int rc = stream_workspace(idx, s, qv::batched_workspace_bytes(v, plan, nq, k), &ws, &ws_hold);
     if (rc != QV_OK) return rc;
-    hipError_t e = qv::launch_flat_redo_flagged(v, plan, d_queries, nq, k, k, d_flags, ws, d_rows_out, d_dist_out, s);
-    if (e != hipSuccess) return fail(QV_ERR_DEVICE, "redo launch failed: %s", hipGetErrorString(e));
+    const ProfilePair pp = profile_begin(idx);
+    uint32_t* d_ovf = nullptr;
+    hipError_t e = qv::launch_batched(v, plan, d_queries, nq, k, ws, d_rows_out, d_dist_out, &d_ovf, idx->cus, s, pp.ev0, pp.ev1);
+    profile_end(idx, pp, e == hipSuccess);
+    if (e != hipSuccess) return fail(QV_ERR_DEVICE, "batched launch failed: %s", hipGetErrorString(e));
+    HIPCHK(hipMemcpyAsync(d_redo_flags_out, d_ovf, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     return QV_OK;
-}
-
-void qv_internal_drop_stream_workspace(qv_index* idx, void* stream) {
-    if (!idx) return;
-    Workspace* w = nullptr;
-    {
-        std::lock_guard<std::mutex> g(idx->ws_mu);
-        auto it = idx->stream_ws.find(static_cast<hipStream_t>(stream));
-        if (it == idx->stream_ws.end()) return;
-        w = it->second;
-        idx->stream_ws.erase(it);
-    }
-    { std::lock_guard<std::mutex> hold(w->mu); w->ws.release(); w->tickets.release(); }   // (hipFree waits for the device: nothing of the stream's is still running on it)
-    delete w;
-}
-
-extern "C" {
-
-// The filter walks the corpus once per 256 queries, so 257-320 queries cost two walks (2.6 ms against 1.4 ms at 1M x 768) while
-// a batch of 64 or fewer costs half a walk: a small tail goes in a call of its own (0 = no split).
-static uint32_t batched_tail(const qv::IndexView& v, uint32_t nq, uint32_t k) {
-    const uint32_t rem = nq & 255u;
-    return nq > 256 && rem >= 1 && rem <= 64 && (rem <= 8 || qv::batched_supported(v, rem, k)) ? rem : 0;
 }
 
 int qv_index_search_batched_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k,
@@ -1681,50 +1682,75 @@ int qv_index_search_batched_device(qv_index* idx, const float* d_queries, uint32
     if (nq == 0) return QV_OK;
     if (!d_queries || !d_rows_out || !d_dist_out || !d_redo_flags_out) return fail(QV_ERR_INVALID_ARG, "null device pointer");
     if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");
-    const qv::IndexView v = idx->view();
-    if (k > idx->n_live || idx->n_live < 4 * (uint64_t)k || !qv::batched_supported(v, nq, k))
+    if (k > idx->n_live || idx->n_live < 4 * (uint64_t)k || !qv::batched_supported(idx->view(), nq, k))
         return fail(QV_ERR_UNSUPPORTED, "the MFMA batched path does not apply to this index/query shape; use qv_index_search_device");
     HIPCHK(hipSetDevice(idx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (nq > kHostBatch) {                                                        // bound the workspace (sample scores + candidate slots: ~160 KB per query)
-        for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {
-            const uint32_t m = std::min(kHostBatch, nq - q0);
-            int rc0;
-            if (qv::batched_supported(v, m, k))
-                rc0 = qv_index_search_batched_device(idx, d_queries + (size_t)q0 * idx->dim, m, k, d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, d_redo_flags_out + q0, stream);
-            else {
-                HIPCHK(hipMemsetAsync(d_redo_flags_out + q0, 0, (size_t)m * sizeof(uint32_t), s));
-                rc0 = qv_index_search_device(idx, d_queries + (size_t)q0 * idx->dim, m, k, d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, stream);
-            }
-            if (rc0 != QV_OK) return rc0;
-        }
-        return QV_OK;
-    }
-    if (const uint32_t tail = batched_tail(v, nq, k)) {
+    // bound the workspace (sample scores + candidate slots: ~160 KB per query): the one pass of a call that fits, else every slice as a call of its own
+    return in_passes(nq, kHostBatch, [&](uint32_t q0, uint32_t m) {
+        return m == nq ? batched_device_pass(idx, d_queries, nq, k, d_rows_out, d_dist_out, d_redo_flags_out, stream)
+                       : batched_device_part(idx, d_queries, q0, m, k, d_rows_out, d_dist_out, d_redo_flags_out, stream);
+    });
+}
+
+// one pass of qv_index_search_batched: up to kHostBatch queries, the arguments checked
+static int batched_pass(qv_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    const uint32_t kk = std::min(k, idx->n_live);
+    const qv::IndexView v = idx->view();
+    // the MFMA filter pays off for many queries over a large cosine/dot corpus; everything else
+    // (and any k > 64) takes the exact multi-query scan, which returns the same result
+    if (!qv::batched_supported(v, nq, kk) || kk != k || idx->n_live < 4 * kk)
+        return exact_search_host(idx, queries, nq, k, rows_out, dist_out, count_out);
+    if (const uint32_t tail = batched_tail(v, nq, kk)) {              // (each part falls back to the exact scan by itself)
         const uint32_t head = nq - tail;
-        int rc0 = qv_index_search_batched_device(idx, d_queries, head, k, d_rows_out, d_dist_out, d_redo_flags_out, stream);
+        const int rc0 = batched_pass(idx, queries, head, k, rows_out, dist_out, count_out);
         if (rc0 != QV_OK) return rc0;
-        const float* tq = d_queries + (size_t)head * idx->dim;
-        if (qv::batched_supported(v, tail, k))
-            return qv_index_search_batched_device(idx, tq, tail, k, d_rows_out + (size_t)head * k, d_dist_out + (size_t)head * k, d_redo_flags_out + head, stream);
-        HIPCHK(hipMemsetAsync(d_redo_flags_out + head, 0, (size_t)tail * sizeof(uint32_t), s));
-        return qv_index_search_device(idx, tq, tail, k, d_rows_out + (size_t)head * k, d_dist_out + (size_t)head * k, stream);
+        return batched_pass(idx, queries + (size_t)head * idx->dim, tail, k, rows_out + (size_t)head * k, dist_out + (size_t)head * k, count_out + head);
     }
-    const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
-    void* ws = nullptr;
-    std::unique_lock<std::mutex> ws_hold;
-    int rc = stream_workspace(idx, s, qv::batched_workspace_bytes(v, plan, nq, k), &ws, &ws_hold);
-    if (rc != QV_OK) return rc;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (idx->profiling && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
-        std::lock_guard<std::mutex> g(idx->prof_mu);
-        idx->prof_events.emplace_back(ev0, ev1);
+    std::vector<uint32_t> redo;
+    {
+        HostCall hc(idx);                                             // (gone before the redo: the exact scan takes its own context, a call never holds two)
+        const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
+        const size_t fbytes = (size_t)nq * sizeof(uint32_t);
+        int rc;
+        if ((rc = hc.open()) || (rc = hc.reserve(nq, nq, kk)) || (rc = hc.c->h_ids.ensure(fbytes)) || (rc = hc.workspace(qv::batched_workspace_bytes(v, plan, nq, kk)))) return rc;
+        hc.stage(queries, nq);
+        if ((rc = hc.send(nq))) return rc;
+        uint32_t* d_ovf = nullptr;
+        const ProfilePair pp = profile_begin(idx);
+        hipError_t e = qv::launch_batched(v, plan, hc.d_queries(), nq, kk, hc.ws(), hc.d_rows(), hc.d_dist(), &d_ovf, idx->cus, hc.stream(), pp.ev0, pp.ev1);
+        profile_end(idx, pp, e == hipSuccess);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "batched launch failed: %s", hipGetErrorString(e));
+        if ((rc = hc.fetch(nq, kk))) return rc;
+        HIPCHK(hipMemcpyAsync(hc.c->h_ids.p, d_ovf, fbytes, hipMemcpyDeviceToHost, hc.stream()));
+        if ((rc = hc.sync())) return rc;
+        hc.deliver(nq, kk, kk, k, rows_out, dist_out);
+        for (uint32_t q = 0; q < nq; q++) count_out[q] = kk;
+        // queries whose candidate buffer overflowed (loose sample bound, e.g. a corpus sorted by cluster):
+        // redo them with the exact scan
+        const uint32_t* ovf = static_cast<const uint32_t*>(hc.c->h_ids.p);
+        for (uint32_t q = 0; q < nq; q++) if (ovf[q]) redo.push_back(q);
+        idx->batched_redo += redo.size();
     }
-    uint32_t* d_ovf = nullptr;
-    hipError_t e = qv::launch_batched(v, plan, d_queries, nq, k, ws, d_rows_out, d_dist_out, &d_ovf, idx->cus, s, ev0, ev1);
-    if (e != hipSuccess) return fail(QV_ERR_DEVICE, "batched launch failed: %s", hipGetErrorString(e));
-    HIPCHK(hipMemcpyAsync(d_redo_flags_out, d_ovf, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    if (!redo.empty()) {
+        const uint32_t nr = (uint32_t)redo.size();
+        std::vector<float> rq((size_t)nr * idx->dim), rd((size_t)nr * kk);
+        std::vector<uint32_t> rr((size_t)nr * kk), rc2(nr);
+        gather_queries(rq.data(), queries, redo, idx->dim);
+        const int rc = exact_search_host(idx, rq.data(), nr, kk, rr.data(), rd.data(), rc2.data());
+        if (rc != QV_OK) return rc;
+        deliver_lists(rr.data(), rd.data(), nr, kk, kk, k, rows_out, dist_out, redo.data());
+    }
     return QV_OK;
+}
+
+int qv_index_search_batched(qv_index* idx, const float* queries, uint32_t nq, uint32_t k,
+                            uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
+    bool done;
+    if (const int rc = check_host_args(idx, nq, k, queries && count_out, "queries/count_out is null", rows_out && dist_out, "rows_out/dist_out is null", count_out, &done); rc != QV_OK || done)
+        return rc;
+    return in_passes(nq, kHostBatch, [&](uint32_t q0, uint32_t m) {   // (each pass decides for itself whether the filter takes it)
+        return batched_pass(idx, queries + (size_t)q0 * idx->dim, m, k, rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
+    });
 }
 
 int qv_merge_topk_device(const float* d_dist_lists, const uint32_t* d_row_lists, uint32_t n_lists, uint32_t k,
@@ -1960,87 +1986,6 @@ int qv_index_profile_read(qv_index* idx, double* scan_ms_sum_out, uint64_t* laun
     return QV_OK;
 }
 
-int qv_index_search_batched(qv_index* idx, const float* queries, uint32_t nq, uint32_t k,
-                            uint32_t* rows_out, float* dist_out, uint32_t* count_out) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (nq == 0) return QV_OK;
-    if (!queries || !count_out) return fail(QV_ERR_INVALID_ARG, "queries/count_out is null");
-    if (idx->n_live == 0) { for (uint32_t q = 0; q < nq; q++) count_out[q] = 0; return QV_OK; }
-    if (k == 0) return fail(QV_ERR_K_NOT_POSITIVE, "k must be positive");
-    if (!rows_out || !dist_out) return fail(QV_ERR_INVALID_ARG, "rows_out/dist_out is null");
-    const uint32_t kk = std::min(k, idx->n_live);
-    const qv::IndexView v = idx->view();
-    // the MFMA filter pays off for many queries over a large cosine/dot corpus; everything else
-    // (and any k > 64) takes the exact multi-query scan, which returns the same result
-    if (!qv::batched_supported(v, nq, kk) || kk != k || idx->n_live < 4 * kk)
-        return exact_search_host(idx, queries, nq, k, rows_out, dist_out, count_out);
-    if (nq > kHostBatch) {
-        for (uint32_t q0 = 0; q0 < nq; q0 += kHostBatch) {
-            const int rc0 = qv_index_search_batched(idx, queries + (size_t)q0 * idx->dim, std::min(kHostBatch, nq - q0), k,
-                                                    rows_out + (size_t)q0 * k, dist_out + (size_t)q0 * k, count_out + q0);
-            if (rc0 != QV_OK) return rc0;
-        }
-        return QV_OK;
-    }
-    if (const uint32_t tail = batched_tail(v, nq, kk)) {              // qv_index_search_batched falls back to the exact scan by itself
-        const uint32_t head = nq - tail;
-        const int rc0 = qv_index_search_batched(idx, queries, head, k, rows_out, dist_out, count_out);
-        if (rc0 != QV_OK) return rc0;
-        return qv_index_search_batched(idx, queries + (size_t)head * idx->dim, tail, k, rows_out + (size_t)head * k, dist_out + (size_t)head * k, count_out + head);
-    }
-    HIPCHK(hipSetDevice(idx->device));
-    SearchCtx* c = nullptr;
-    int rc = acquire_ctx(idx, &c);
-    if (rc != QV_OK) return rc;
-    CtxGuard guard{idx, c};
-    const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
-    const size_t qbytes = (size_t)nq * idx->dim * sizeof(float);
-    const size_t obytes = (size_t)nq * kk * sizeof(uint32_t);
-    const size_t fbytes = (size_t)nq * sizeof(uint32_t);
-    if ((rc = c->d_q.ensure(qbytes)) || (rc = c->h_q.ensure(qbytes)) || (rc = c->d_rows.ensure(obytes)) || (rc = c->d_dist.ensure(obytes)) ||
-        (rc = c->h_rows.ensure(obytes)) || (rc = c->h_dist.ensure(obytes)) || (rc = c->h_ids.ensure(fbytes)) ||
-        (rc = c->ws.ensure(qv::batched_workspace_bytes(v, plan, nq, kk))))
-        return rc;
-    memcpy(c->h_q.p, queries, qbytes);
-    HIPCHK(hipMemcpyAsync(c->d_q.p, c->h_q.p, qbytes, hipMemcpyHostToDevice, c->stream));
-    uint32_t* d_ovf = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (idx->profiling && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
-        std::lock_guard<std::mutex> g(idx->prof_mu);
-        idx->prof_events.emplace_back(ev0, ev1);
-    }
-    hipError_t e = qv::launch_batched(v, plan, static_cast<const float*>(c->d_q.p), nq, kk, c->ws.p, static_cast<uint32_t*>(c->d_rows.p),
-                                      static_cast<float*>(c->d_dist.p), &d_ovf, idx->cus, c->stream, ev0, ev1);
-    if (e != hipSuccess) return fail(QV_ERR_DEVICE, "batched launch failed: %s", hipGetErrorString(e));
-    HIPCHK(hipMemcpyAsync(c->h_rows.p, c->d_rows.p, obytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_dist.p, c->d_dist.p, obytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_ids.p, d_ovf, fbytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(rows_out, c->h_rows.p, obytes);
-    memcpy(dist_out, c->h_dist.p, obytes);
-    for (uint32_t q = 0; q < nq; q++) count_out[q] = kk;
-    // queries whose candidate buffer overflowed (loose sample bound, e.g. a corpus sorted by cluster):
-    // redo them with the exact scan
-    const uint32_t* ovf = static_cast<const uint32_t*>(c->h_ids.p);
-    std::vector<uint32_t> redo;
-    for (uint32_t q = 0; q < nq; q++) if (ovf[q]) redo.push_back(q);
-    idx->batched_redo += redo.size();
-    guard.c = nullptr; release_ctx(idx, c);                          // the exact scan takes its own context
-    if (!redo.empty()) {
-        std::vector<float> rq((size_t)redo.size() * idx->dim);
-        for (size_t i = 0; i < redo.size(); i++) memcpy(&rq[i * idx->dim], queries + (size_t)redo[i] * idx->dim, idx->dim * sizeof(float));
-        std::vector<uint32_t> rr((size_t)redo.size() * kk), rc2(redo.size());
-        std::vector<float> rd((size_t)redo.size() * kk);
-        rc = exact_search_host(idx, rq.data(), (uint32_t)redo.size(), kk, rr.data(), rd.data(), rc2.data());
-        if (rc != QV_OK) return rc;
-        for (size_t i = 0; i < redo.size(); i++) {
-            memcpy(rows_out + (size_t)redo[i] * kk, &rr[i * kk], kk * sizeof(uint32_t));
-            memcpy(dist_out + (size_t)redo[i] * kk, &rd[i * kk], kk * sizeof(float));
-        }
-    }
-    return QV_OK;
-}
-
 int qv_distance_rows_device(qv_index* idx, const float* d_query, const uint32_t* d_rows, uint32_t n,
                             float* d_dist_out, void* stream) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
@@ -2120,3 +2065,63 @@ int qv_distance_pairs(qv_metric metric, const float* a, const float* b, uint32_t
 }
 
 }  // extern "C"
+
+// Internal (qv_api_internal.h), for the sharded handle: the exact scan over the rows selected by a DEVICE bitmap d_candidates
+// (already ANDed with the live rows by the caller; `matching` = its population count), enqueued on `stream`, no
+// synchronisation.  Writes [nq][k_stride] lists: min(k_stride, matching) results, the rest padded (0xFFFFFFFF, +inf).
+int qv_internal_search_candidates_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k_stride, const uint64_t* d_candidates,
+                                         uint64_t matching, uint32_t* d_rows_out, float* d_dist_out, void* stream) {
+    if (!idx || !d_queries || !d_candidates || !d_rows_out || !d_dist_out || k_stride == 0) return fail(QV_ERR_INVALID_ARG, "null argument");
+    if (nq == 0) return QV_OK;
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t kk = (uint32_t)std::min<uint64_t>(k_stride, matching);
+    void* ws = nullptr;
+    std::unique_lock<std::mutex> ws_hold;
+    int rc = stream_workspace(idx, s, search_ws_bytes(idx, nq, kk, k_stride, false), &ws, &ws_hold);
+    if (rc != QV_OK) return rc;
+    SearchExtras x;
+    x.d_candidates = d_candidates;
+    return enqueue_search(idx, d_queries, nq, kk, k_stride, ws, d_rows_out, d_dist_out, s, x);
+}
+
+// Internal, for the sharded handle: the exact scan for the queries of a batch whose d_flags word is set (handed back by
+// qv_index_search_batched_device), enqueued on `stream` behind the batch — listed and scanned on the device, nothing read back.
+int qv_internal_redo_flagged_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_flags,
+                                    uint32_t* d_rows_out, float* d_dist_out, void* stream) {
+    if (!idx || !d_queries || !d_flags || !d_rows_out || !d_dist_out || k == 0 || k > (uint32_t)qv::kMaxSelectK) return fail(QV_ERR_INVALID_ARG, "bad argument");
+    if (nq == 0) return QV_OK;
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const qv::IndexView v = idx->view();
+    const qv::ScanPlan plan = qv::plan_scan(v.n_tiles, idx->cus);
+    void* ws = nullptr;
+    std::unique_lock<std::mutex> ws_hold;
+    if (k > (uint32_t)qv::kMaxFusedK) {                               // the selection path's hand-backs: QV_ERR_UNSUPPORTED = the caller reads the flags itself
+        int rc0 = stream_workspace(idx, s, qv::flat_select_redo_workspace_bytes(v.n_tiles, nq, k, v.dim, v.dim4), &ws, &ws_hold);
+        if (rc0 != QV_OK) return rc0;
+        hipError_t e0 = qv::launch_flat_select_redo(v, plan, d_queries, nq, k, k, d_flags, ws, d_rows_out, d_dist_out, s);
+        if (e0 == hipErrorNotSupported) return QV_ERR_UNSUPPORTED;
+        if (e0 != hipSuccess) return fail(QV_ERR_DEVICE, "redo launch failed: %s", hipGetErrorString(e0));
+        return QV_OK;
+    }
+    int rc = stream_workspace(idx, s, qv::redo_workspace_bytes(plan, nq, k), &ws, &ws_hold);
+    if (rc != QV_OK) return rc;
+    hipError_t e = qv::launch_flat_redo_flagged(v, plan, d_queries, nq, k, k, d_flags, ws, d_rows_out, d_dist_out, s);
+    if (e != hipSuccess) return fail(QV_ERR_DEVICE, "redo launch failed: %s", hipGetErrorString(e));
+    return QV_OK;
+}
+
+void qv_internal_drop_stream_workspace(qv_index* idx, void* stream) {
+    if (!idx) return;
+    Workspace* w = nullptr;
+    {
+        std::lock_guard<std::mutex> g(idx->ws_mu);
+        auto it = idx->stream_ws.find(static_cast<hipStream_t>(stream));
+        if (it == idx->stream_ws.end()) return;
+        w = it->second;
+        idx->stream_ws.erase(it);
+    }
+    { std::lock_guard<std::mutex> hold(w->mu); w->ws.release(); w->tickets.release(); }   // (hipFree waits for the device: nothing of the stream's is still running on it)
+    delete w;
+}

@@ -109,7 +109,7 @@ def test_search_device(name):
 
 
 def test_search_device_on_an_empty_index_pads_every_list():
-    """(synchronises, by contract: only the padding is asserted)"""
+    """only the padding is asserted"""
     c = B.search_case("empty", "cosine", 600, 16, 2, 10)
     idx = quiver_amd.DeviceIndex(16, "cosine")
     call = _search_call(idx, c)

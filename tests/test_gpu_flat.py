@@ -406,6 +406,31 @@ def test_very_large_host_batch_is_sliced_without_changing_results():
         assert r[i].tolist() == ro.tolist() and d[i].tobytes() == do.tobytes()
     r2, d2, _ = idx.search(qs, k, batched=True)
     assert np.array_equal(r, r2) and np.array_equal(d.view(np.uint32), d2.view(np.uint32))
+    # the filtered host forms: a filter per query drawn from four (the masked form takes one for all), against the same call made in two
+    # halves of at most 8192 queries each, and against the oracle at the ends of the slices
+    n, nq = 200, 8192 + 5
+    rows, qs = O.gen_rows(31339, 0, n, dim), O.gen_rows(31340, 0, nq, dim)
+    idx = quiver_amd.DeviceIndex(dim, "cosine")
+    idx.add(rows)
+    masks = [np.arange(n) % 4 != j for j in range(4)]
+    pick = np.arange(nq) % 4
+    sets = [idx.rowset(m) for m in masks]
+    col = idx.column("u32")
+    col.set(0, np.arange(n) % 4)
+    forms = {
+        "masked": (lambda a, b: idx.search_masked(qs[a:b], k, masks[1]), lambda i: masks[1]),
+        "rowsets": (lambda a, b: idx.search_rowsets(qs[a:b], k, [sets[j] for j in pick[a:b]]), lambda i: masks[pick[i]]),
+        "where": (lambda a, b: idx.search_where(qs[a:b], k, [[(col, "!=", int(j))] for j in pick[a:b]]), lambda i: masks[pick[i]]),
+    }
+    for form, (call, mask_of) in forms.items():
+        r, d, c = call(0, nq)
+        assert (c == k).all(), form
+        halves = [call(0, 4100), call(4100, nq)]
+        assert np.array_equal(r, np.concatenate([h[0] for h in halves])), form
+        assert np.array_equal(_bits(d), _bits(np.concatenate([h[1] for h in halves]))), form
+        for i in (0, 8191, 8192, nq - 1):
+            ro, do = O.exact_search(0, rows, qs[i], k, alive=mask_of(i).astype(np.uint8))
+            assert r[i].tolist() == ro.tolist() and d[i].tobytes() == do.tobytes(), (form, i)
 
 
 @pytest.mark.parametrize("metric,n,dim,nq,k,frac", [
