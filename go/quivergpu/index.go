@@ -35,6 +35,11 @@ type rows interface {
 // indexes keep by default (+3 * dim + 8 bytes per row).  On every other metric it does nothing.
 const FlagL2ScanPlane uint64 = C.QV_FLAG_L2_SCAN_PLANE
 
+// FlagNoPlane6 (QV_FLAG_NO_PLANE6): an index that keeps the 8-bit plane and whose dimension is a multiple of 64 also keeps a 6-bit plane
+// (+0.75 * dim + 4 bytes per row), on which a single unfiltered query over a large corpus rejects rows first; this flag leaves it out.
+// (The library's plane knobs have no Go setters: the automatic rules and the QV_BOUND_PLANE* environment variables govern a Go host.)
+const FlagNoPlane6 uint64 = C.QV_FLAG_NO_PLANE6
+
 // FlagGraphPlane (QV_FLAG_GRAPH_PLANE): a row-major cosine or dot index whose dimension is a multiple of 64 up to 4096 also keeps a
 // bfloat16 copy of the rows in row order (+2 * dim bytes per row), on which a graph's batch searches can reject neighbours
 // (Graph.SetRejectPlane).  Elsewhere it does nothing.

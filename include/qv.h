@@ -122,6 +122,12 @@ typedef enum qv_status {
                                     narrower than 768 dimensions waits for 10M rows, and a filtered search for nine tenths of the tiles
                                     holding a candidate.  On every other metric the flag does nothing; QV_L2SQ, QV_L2_F32 and QV_L2SQ_F64 keep no
                                     planes.  QV_FLAG_BF16_ROWS alone on a QV_L2 index stays a copy for the batched filter: no bound scan */
+#define QV_FLAG_NO_PLANE6 32ull  /* wherever they keep the 8-bit plane, indexes whose dimension is a multiple of 64 also keep a 6-bit plane of the rows
+                                    with a residual per row (+dim * 0.75 + 4 bytes per row: 5392 -> 5972 at 768 dimensions; the scale is the 8-bit
+                                    plane's), on which a single unfiltered query rejects rows before the 8-bit plane is read for the few
+                                    thousand rows left (qv_index_set_bound_plane6).  This flag leaves that plane out alone;
+                                    QV_FLAG_NO_SCAN_PLANE leaves it out with the others.  A 6-bit plane that cannot be allocated is given up
+                                    alone and searches start on the 8-bit plane; it is never kept without the 8-bit plane */
 #define QV_FLAG_GRAPH_PLANE 16ull /* a QV_FLAG_ROWMAJOR index of metric QV_COSINE or QV_DOT whose dimension is a multiple of 64 up to 4096
                                     also keeps `rowmaj16`: a bfloat16 copy of the rows in ROW order, [rows][dim] (+dim * 2 bytes per row:
                                     7688 -> 9224 at 768 dimensions for an index that serves flat, graph and batch), each element the
@@ -509,6 +515,38 @@ int qv_index_set_bound_plane(qv_index* idx, int mode);
  * qv_index_bound_scan_stats keeps its meaning: a search the 8-bit stage took counts as a bound-scan search there, and its hand-backs
  * are the searches that reached the exact scan. */
 int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]);
+/* ---- the 6-bit stage in front of the 8-bit one ----
+ * Whether a single UNFILTERED query that would start on the 8-bit plane starts on the 6-bit plane instead (see QV_FLAG_NO_PLANE6):
+ * stage 1 reads three quarters of the 8-bit bytes with an interval about four times as wide, its candidates (tens of thousands of 10M
+ * rows) are refined on the 8-bit plane by a gather, and the 8-bit stage's collection and exact re-score finish as ever.  A search the
+ * 6-bit stage cannot decide (more than 262 144 candidates, no finite threshold, a query it cannot quantise) goes on to the bfloat16
+ * stage — all decided on the device; results are bit-identical to the exact scan's in every case.  QV_BOUND_PLANE6_AUTO: the shapes
+ * measured faster than 8-bit first (qv_scan_bound6_applies), never below the 8-bit stage's floor; QV_BOUND_PLANE6_ALWAYS: whenever the
+ * 8-bit stage would be first and the plane is held; QV_BOUND_PLANE6_NEVER: never.  Independent of the other setters; filtered searches
+ * and shared passes are not moved by it.  The environment variable QV_BOUND_PLANE6 (1 always, 2 never; read once per process) sets the
+ * default of indexes that never call this. */
+#define QV_BOUND_PLANE6_AUTO 0
+#define QV_BOUND_PLANE6_ALWAYS 1
+#define QV_BOUND_PLANE6_NEVER 2
+int qv_index_set_bound_plane6(qv_index* idx, int mode);
+/* out[0] = candidates the 6-bit stage passed to the refine in the last such search, out[1] = searches it handed on to the bfloat16 stage
+ * so far, out[2] = searches that took the 6-bit stage so far, out[3] = 1 when the index holds the 6-bit plane.  Waits for the device.
+ * qv_index_bound_scan8_stats and qv_index_bound_scan_stats keep their meaning: such a search counts as an 8-bit search there. */
+int qv_index_bound_scan6_stats(qv_index* idx, uint64_t out[4]);
+/* Whether a search would take the 6-bit stage first — the dispatch's own rule, on the host: qv_scan_bound8_applies(metric, dim, rows, nq, k,
+ * mode, plane_mode, has_plane8) true, one query, the 6-bit plane held (has_plane6; a dimension that is a multiple of 64), and plane6_mode
+ * (QV_BOUND_PLANE6_*).  It never says yes where qv_scan_bound8_applies says no.  AUTO: the cells measured faster
+ * (profiles/LAB_r20_bound_scan6.md).  1 / 0, < 0 on an error. */
+int qv_scan_bound6_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int plane6_mode, int has_plane8, int has_plane6);
+/* One row as the index keeps it in the 6-bit plane (dim a multiple of 64): codes c6_i = clamp(rint(r_i / (4 scale8)), -32, 31) stored
+ * biased (c6 + 32) in six bits; out_bytes[dim * 3 / 4]: per group of 64 dimensions the row's three 16-byte pieces X, Y, Z — dims 0 - 47 of
+ * the group in the low six bits of their bytes, dims 48 - 63 as three 2-bit parts (bits 0 - 1, 2 - 3, 4 - 5 of the code) in the top two bits
+ * of the bytes of X, Y, Z.  scale8: the row's 8-bit scale (qv_scan_quantize_row8).  *out_res = |r - 4 scale8 c6| computed in float64 from
+ * those codes and rounded up — NaN for a row qv_scan_quantize_row8 declines.  The interval: qv_scan_bound_interval8 with
+ * isum = sum qq_i (c6_i + 32) - 32 sum qq_i, rscale8 = 4 scale8, rres8 = *out_res. */
+int qv_scan_quantize_row6(uint32_t dim, const float* row, float scale8, uint8_t* out_bytes, float* out_res);
+/* ... and those bytes back into the biased codes, out_codes[dim] in 0 .. 63. */
+int qv_scan_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes);
 /* ---- the 8-bit stage under a filter ----
  * Which plane serves a single FILTERED query's bound scan first: qv_index_search_masked, qv_index_search_rowsets and
  * qv_index_search_where with one query, their device forms, and a shared pass of the row-set front that holds one caller — at
@@ -648,6 +686,9 @@ int qv_scan_bound_interval_l2(uint32_t dim, float s, double qn, double rn, float
 #define QV_DEBUG_RNORM 0
 #define QV_DEBUG_RRES  1
 #define QV_DEBUG_PLANE 2
+#define QV_DEBUG_PLANE6 4     /* the 6-bit plane, raw: [tile][dim / 64][3][64 rows][16 bytes] (qv_scan_quantize_row6's pieces); an index that keeps none: an unknown code */
+#define QV_DEBUG_RRES6  5     /* |r - 4 rscale8 c6| rounded up, one float per row slot */
+#define QV_DEBUG_RSCALE8 6    /* the 8-bit plane's scale, one float per row slot (indexes that keep the 6-bit plane) */
 #define QV_DEBUG_ROWMAJ16 3   /* the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE), raw: rows x dim uint16, rows ever added; QV_ERR_UNSUPPORTED when an index created
                                  with the flag keeps none; an index created without the flag does not know the code (QV_ERR_INVALID_ARG, as before) */
 int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes);
@@ -930,6 +971,7 @@ int qv_sharded_set_bound_scan(qv_sharded* s, int mode);       /* qv_index_set_bo
 int qv_sharded_bound_scan_stats(qv_sharded* s, uint64_t out[4]);   /* qv_index_bound_scan_stats: [0] of the first shard, [1] [2] summed, [3] 1 when every shard holds the copy */
 int qv_sharded_set_bound_plane(qv_sharded* s, int mode);      /* qv_index_set_bound_plane on every shard */
 int qv_sharded_set_bound_plane_mq(qv_sharded* s, int mode);   /* qv_index_set_bound_plane_mq on every shard */
+int qv_sharded_set_bound_plane6(qv_sharded* s, int mode);     /* qv_index_set_bound_plane6 on every shard */
 int qv_sharded_bound_scan8_stats(qv_sharded* s, uint64_t out[4]);  /* qv_index_bound_scan8_stats, put together as qv_sharded_bound_scan_stats does */
 int qv_sharded_profile(qv_sharded* s, int enable);
 int qv_sharded_profile_read(qv_sharded* s, double* scan_ms_sum, double* exchange_ms_sum, double* merge_ms_sum, uint64_t* searches);

@@ -18,6 +18,8 @@ QV_FLAG_L2_SCAN_PLANE = 8      # a QV_L2 index keeps the bfloat16 copy and the 8
 QV_FLAG_GRAPH_PLANE = 16       # a row-major cosine / dot index also keeps a bfloat16 copy in row order: graph traversals can reject neighbours on it
 QV_GRAPH_REJECT_AUTO, QV_GRAPH_REJECT_ALWAYS, QV_GRAPH_REJECT_NEVER = 0, 1, 2
 QV_DEBUG_RNORM, QV_DEBUG_RRES, QV_DEBUG_PLANE, QV_DEBUG_ROWMAJ16 = 0, 1, 2, 3
+QV_DEBUG_PLANE6, QV_DEBUG_RRES6, QV_DEBUG_RSCALE8 = 4, 5, 6
+QV_FLAG_NO_PLANE6 = 32         # no 6-bit plane beside the 8-bit one (dim * 0.75 + 4 bytes per row)
 QV_RULE_L2_PLANES = 0x101      # such an index, as the qv_scan_* rule functions take it where they take a metric
 QV_BOUND_SCAN_AUTO, QV_BOUND_SCAN_ALWAYS, QV_BOUND_SCAN_NEVER = 0, 1, 2
 QV_FILTERED_BATCH_AUTO, QV_FILTERED_BATCH_ALWAYS, QV_FILTERED_BATCH_NEVER = 0, 1, 2
@@ -112,6 +114,12 @@ PROTOTYPES = {
     "qv_index_set_bound_plane": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_sharded_set_bound_plane": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_bound_scan8_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_index_set_bound_plane6": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_sharded_set_bound_plane6": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_bound_scan6_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_scan_bound6_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "qv_scan_quantize_row6": (C.c_int, [C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, _f32p]),
+    "qv_scan_unpack_row6": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),
     "qv_sharded_bound_scan8_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_index_set_bound_plane_filtered": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_set_bound_plane_mq": (C.c_int, [C.c_void_p, C.c_int]),

@@ -152,6 +152,21 @@ int ensure_rows(qv_index* idx, uint64_t rows, bool exact) {
         (void)hipFree(idx->d_plane8); (void)hipFree(idx->d_rscale8); (void)hipFree(idx->d_rres8);
         idx->d_plane8 = nullptr; idx->d_rscale8 = nullptr; idx->d_rres8 = nullptr; idx->plane8_lost = true;
     }
+    if (e == hipSuccess && idx->wants_plane6()) {
+        // the 6-bit plane and its residual: an accelerator in front of the 8-bit plane — when it does not fit, the index frees it and
+        // searches start on the 8-bit plane (QV_TEST_PLANE6_OOM: the same for tests)
+        hipError_t e6 = getenv("QV_TEST_PLANE6_OOM") ? hipErrorOutOfMemory : regrow(&idx->d_plane6, used_tiles * idx->plane6_tile_bytes(), new_tiles * idx->plane6_tile_bytes());
+        if (e6 == hipSuccess) e6 = regrow(&idx->d_rres6, used_tiles * 64 * sizeof(float), new_tiles * 64 * sizeof(float));
+        if (e6 == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            (void)hipFree(idx->d_plane6); (void)hipFree(idx->d_rres6);
+            idx->d_plane6 = nullptr; idx->d_rres6 = nullptr; idx->plane6_lost = true;
+        } else e = e6;
+    }
+    if (!idx->d_plane8 && idx->d_plane6) {                             // (the refine reads the 8-bit plane and its scale: never the 6-bit plane without it)
+        (void)hipFree(idx->d_plane6); (void)hipFree(idx->d_rres6);
+        idx->d_plane6 = nullptr; idx->d_rres6 = nullptr; idx->plane6_lost = true;
+    }
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? QV_ERR_OOM : QV_ERR_DEVICE, "device allocation for %llu rows failed: %s", (unsigned long long)(new_tiles * 64), hipGetErrorString(e));
     idx->cap_tiles = new_tiles;
@@ -236,6 +251,7 @@ void qv_index_destroy(qv_index* idx) {
     for (auto& kv : idx->stream_ws) { kv.second->ws.release(); kv.second->tickets.release(); delete kv.second; }
     (void)hipFree(idx->d_tiles); (void)hipFree(idx->d_rnorm); (void)hipFree(idx->d_alive); (void)hipFree(idx->d_rres); (void)hipFree(idx->d_rowmaj); (void)hipFree(idx->d_rowmaj16); (void)hipFree(idx->d_bf16); (void)hipFree(idx->d_bound_stats);
     (void)hipFree(idx->d_plane8); (void)hipFree(idx->d_rscale8); (void)hipFree(idx->d_rres8);
+    (void)hipFree(idx->d_plane6); (void)hipFree(idx->d_rres6);
     idx->mut_stage.release();
     delete idx;
 }
@@ -1810,6 +1826,13 @@ int qv_index_set_bound_plane_filtered(qv_index* idx, int mode) { return set_boun
 int qv_index_set_bound_plane_mq(qv_index* idx, int mode) { return set_bound_plane(idx, qv::bound_mq, mode); }
 int qv_index_set_bound_plane_filtered_mq(qv_index* idx, int mode) { return set_bound_plane(idx, qv::bound_mq_filtered, mode); }
 
+int qv_index_set_bound_plane6(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_PLANE6_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (6-bit first) or 2 (never); got %d", mode);
+    idx->bound.plane6 = mode;
+    return QV_OK;
+}
+
 int qv_index_set_filtered_batch(qv_index* idx, int mode, uint32_t sparse_ppm) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
     if (mode < 0 || mode > QV_FILTERED_BATCH_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
@@ -1858,6 +1881,16 @@ int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]) {
     return QV_OK;
 }
 
+int qv_index_bound_scan6_stats(qv_index* idx, uint64_t out[4]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t h[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kBound6StatsWord, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = idx->d_plane6 != nullptr ? 1 : 0;
+    return QV_OK;
+}
+
 // The six rule exports: views of the one decision (qv::bound_scan_decide) for a call given without an index.  form: the form the export
 // speaks for (it says no to any other; -1: whichever the call has); want: the stage asked after — plane8_first, or any stage at all.  The
 // 8-bit rules are asked with the bfloat16 copy held; a filtered rule takes every candidate count as a count.
@@ -1870,7 +1903,7 @@ static int bound_export(int form, qv::BoundStages want, int metric, uint32_t dim
     knobs.plane[qv::bound_form(ask)] = plane_mode;
     if (form >= 0 && form != qv::bound_form(ask)) return 0;
     const qv::BoundStages got = qv::bound_scan_decide(ask, knobs);
-    return (want == qv::BoundStages::plane8_first ? got == want : got != qv::BoundStages::none) ? 1 : 0;
+    return (want == qv::BoundStages::plane8_first ? qv::bound_stages_8bit(got) : got != qv::BoundStages::none) ? 1 : 0;
 }
 static uint32_t as_count(uint32_t candidate_tiles) { return std::min(candidate_tiles, qv::kBoundNoFilter - 1); }
 
@@ -1888,6 +1921,28 @@ int qv_scan_bound8_applies_mq(int metric, uint32_t dim, uint32_t rows, uint32_t 
 
 int qv_scan_bound8_applies_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode_filtered_mq, int has_plane8, uint32_t candidate_tiles) {
     return bound_export(qv::bound_mq_filtered, qv::BoundStages::plane8_first, metric, dim, rows, nq, k, mode, "plane_mode_filtered_mq", plane_mode_filtered_mq, 1, has_plane8, as_count(candidate_tiles));
+}
+
+int qv_scan_bound6_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int plane6_mode, int has_plane8, int has_plane6) {
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
+    if (plane6_mode < 0 || plane6_mode > QV_BOUND_PLANE6_NEVER) return fail(QV_ERR_INVALID_ARG, "plane6_mode must be 0 (automatic), 1 (6-bit first) or 2 (never); got %d", plane6_mode);
+    qv::BoundAsk ask = {metric, dim, rows, nq, k, qv::kBoundNoFilter, true, has_plane8 != 0};
+    ask.has_plane6 = has_plane6 != 0;
+    qv::BoundKnobs knobs = {mode, {0, 0, 0, 0}};
+    knobs.plane[qv::bound_one] = plane_mode; knobs.plane6 = plane6_mode;
+    if (qv::bound_form(ask) != qv::bound_one) return 0;
+    return qv::bound_scan_decide(ask, knobs) == qv::BoundStages::plane6_first ? 1 : 0;
+}
+
+int qv_scan_quantize_row6(uint32_t dim, const float* row, float scale8, uint8_t* out_bytes, float* out_res) {
+    if (!row || !out_bytes || !out_res || dim == 0 || (dim & 63u) != 0) return fail(QV_ERR_INVALID_ARG, "row/out is null or dim is not a positive multiple of 64");
+    return qv::host_quantize_row6(dim, row, scale8, out_bytes, out_res);
+}
+
+int qv_scan_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes) {
+    if (!bytes || !out_codes || dim == 0 || (dim & 63u) != 0) return fail(QV_ERR_INVALID_ARG, "bytes/out is null or dim is not a positive multiple of 64");
+    return qv::host_unpack_row6(dim, bytes, out_codes);
 }
 
 int qv_scan_bound_interval8(int metric, uint32_t dim, int64_t isum, double sq, double qn, double qres, double rn, float rscale8, float rres8, float* d_lo, float* d_hi) {
@@ -1932,6 +1987,10 @@ int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {
     } else if (what == QV_DEBUG_ROWMAJ16 && (idx->flags & QV_FLAG_GRAPH_PLANE)) {   // (an index created without the flag answers as it always did: an unknown code)
         if (!idx->wants_rowmaj16() || (tiles && !idx->d_rowmaj16)) return fail(QV_ERR_UNSUPPORTED, "this index keeps no row-order bfloat16 copy");
         src = idx->d_rowmaj16; need = (size_t)idx->n_rows * idx->dim * sizeof(uint16_t);
+    } else if ((what == QV_DEBUG_PLANE6 || what == QV_DEBUG_RRES6 || what == QV_DEBUG_RSCALE8) && idx->wants_plane6()) {   // (an index that keeps no such plane answers as it always did: an unknown code)
+        if (tiles && !idx->d_plane6) return fail(QV_ERR_UNSUPPORTED, "this index keeps no 6-bit plane");
+        if (what == QV_DEBUG_PLANE6) { src = idx->d_plane6; need = tiles * idx->plane6_tile_bytes(); }
+        else { src = what == QV_DEBUG_RRES6 ? idx->d_rres6 : idx->d_rscale8; need = tiles * 64 * sizeof(float); }
     } else return fail(QV_ERR_INVALID_ARG, "what must be 0 (norms), 1 (residuals), 2 (the bfloat16 copy) or 3 (the row-order bfloat16 copy); got %d", what);
     if (bytes < need) return fail(QV_ERR_INVALID_ARG, "%zu bytes given, %zu needed", bytes, need);
     if (need == 0) return QV_OK;

@@ -107,6 +107,9 @@ struct qv_index {
     float* d_rscale8 = nullptr;
     float* d_rres8 = nullptr;
     bool plane8_lost = false;                  // it could not be allocated: the index carries on with the bfloat16 copy
+    uint8_t* d_plane6 = nullptr;               // the 6-bit plane and its residual: kept with the 8-bit plane (whose scale it shares), refreshed with it
+    float* d_rres6 = nullptr;
+    bool plane6_lost = false;                  // it could not be allocated: the index carries on with the 8-bit plane
     int filtered_batch = 0;                    // qv_index_set_filtered_batch: QV_FILTERED_BATCH_*
     uint32_t filtered_batch_ppm = 0xFFFFFFFFu; // ... and its sparse floor in millionths of the rows (0xFFFFFFFF: the default, 0: never sparse)
     std::atomic<uint64_t> fb_stats[4] = {};    // qv_index_filtered_batch_stats: queries on the path, handed back (overflow / no bound / failed guess), handed back as sparse, batches
@@ -140,6 +143,7 @@ struct qv_index {
         v.dim = dim; v.dim4 = dim4; v.n_rows = n_rows; v.n_tiles = (n_rows + 63) / 64; v.metric = metric; v.filter = filter;
         v.l2_planes = l2_planes() ? 1 : 0;
         v.rowmaj16 = d_rowmaj16;
+        v.plane6 = d_plane6; v.rres6 = d_rres6; v.bound_plane6 = bound.plane6;
         return v;
     }
     // a Euclidean index that asked for the scan planes (QV_FLAG_L2_SCAN_PLANE; on every other metric the flag does nothing)
@@ -158,7 +162,10 @@ struct qv_index {
     bool wants_rowmaj16() const {
         return (flags & QV_FLAG_GRAPH_PLANE) && (flags & QV_FLAG_ROWMAJOR) && !rowmaj16_lost && (metric == QV_COSINE || metric == QV_DOT) && (dim & 63u) == 0 && dim <= 4096;
     }
+    // ... and the 6-bit plane wherever they keep the 8-bit one, unless told not to (QV_FLAG_NO_PLANE6), on rows of whole 64-dimension groups
+    bool wants_plane6() const { return wants_plane8() && !(flags & QV_FLAG_NO_PLANE6) && !plane6_lost && (dim & 63u) == 0; }
     size_t plane8_tile_bytes() const { return (size_t)dim * 64; }
+    size_t plane6_tile_bytes() const { return (size_t)dim * 48; }
     size_t tile_bytes() const { return (size_t)dim4 * 64 * 16; }
     size_t bf16_tile_bytes() const { return (size_t)(((dim4 + 1) / 2 + 1) / 2) * 2 * 64 * 16; }   // whole 16-dim steps (k_bf16_plane's layout)
 };

@@ -119,6 +119,36 @@ __host__ __device__ static inline float bound8_row_res(bool bad, float maxabs, d
     return bound8_res_up(s2);
 }
 
+// ---- the 6-bit plane (k_bound_scan6): the 8-bit interval with a coarser image of the row ----
+// An index that keeps the 8-bit plane and whose dimension is a multiple of 64 also keeps c6_i = clamp(rint(r_i / (4 rscale8)), -32, 31),
+// stored biased as u_i = c6_i + 32 in six bits (bound6_pack below), and rres6 = |r - 4 rscale8 c6|, computed in float64 FROM THE CODES
+// STORED and rounded up with bound8_res_up (k_row_state6); rows bound8_row_res declines are declined here (NaN).  No scale of its own:
+// 4 rscale8 is exact in float32 (rscale8 < 1e36 is asked below).  Stage 1 computes I6 = sum qq_i u_i - 32 sum qq_i = sum qq_i c6_i with
+// the same two int8 query terms (u_i <= 63 is a non-negative int8; each partial sum stays exact in int32: 4096 * 127 * 63 < 2^31) and
+// calls bound_scan_interval8(I6, sq, qn, qres, rn, 4 rscale8, rres6).  The proof above holds line for line with rh = 4 rscale8 c6 and
+// rres6 in the place of rres8: it uses of rh only that qh.rh = sq scale I as real numbers and |r - rh| <= the stored residual.
+constexpr int kBound6Bias = 32;
+__host__ __device__ static inline int bound6_quant(float x, float scale8) {
+    float v = __builtin_rintf(x / (4.0f * scale8));
+    v = __builtin_fminf(__builtin_fmaxf(v, -32.0f), 31.0f);            // (a NaN quotient comes out as -32: such a row is declined anyway)
+    return (int)v;
+}
+// The plane's layout, [tile][group of 64 dims][3][64 rows][16 B]: where the biased code of dimension d of a row's group lives in the row's
+// three 16-byte pieces X, Y, Z.  Dims 0 - 47: the low six bits of byte d & 15 of piece d >> 4.  Dims 48 - 63: two bits in the top of byte
+// d - 48 of each piece, X the code's bits 0 - 1, Y its bits 2 - 3, Z its bits 4 - 5.
+__host__ __device__ static inline void bound6_pack(uint8_t (&g)[48], uint32_t d, uint32_t u) {
+    if (d < 48u) { g[d] = (uint8_t)((g[d] & 0xC0u) | (u & 0x3Fu)); return; }
+    const uint32_t j = d - 48u;
+    g[j] = (uint8_t)((g[j] & 0x3Fu) | ((u & 3u) << 6));
+    g[16 + j] = (uint8_t)((g[16 + j] & 0x3Fu) | (((u >> 2) & 3u) << 6));
+    g[32 + j] = (uint8_t)((g[32 + j] & 0x3Fu) | (((u >> 4) & 3u) << 6));
+}
+__host__ __device__ static inline uint32_t bound6_unpack(const uint8_t (&g)[48], uint32_t d) {
+    if (d < 48u) return g[d] & 0x3Fu;
+    const uint32_t j = d - 48u;
+    return (uint32_t)(g[j] >> 6) | ((uint32_t)(g[16 + j] >> 6) << 2) | ((uint32_t)(g[32 + j] >> 6) << 4);
+}
+
 // isum = I, sq = the query's scale, qn = |q| (the reference's chain), qres = |q - sq qq| rounded up, rn = |r| (stored),
 // rscale / rres8 = the row's scale and residual.  false: a row (or a query) the bound says nothing about — always a candidate
 // (d_lo = -inf), never lowers a threshold (d_hi = NaN).

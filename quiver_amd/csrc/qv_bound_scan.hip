@@ -78,7 +78,8 @@ __device__ __forceinline__ float bound_tile(const u4* __restrict__ p, const floa
 
 // The end of a bound scan's stage 1 (k_bound_scan, k_bound_scan8): the upper bounds' lists go waves -> wave 0 -> published; the last workgroup
 // to finish merges (k_flat_scan<., ., true>'s protocol) and leaves H, the exact k-th smallest upper bound, in the control words.
-__device__ __forceinline__ void bound_scan_tail(uint64_t list, uint64_t thr, uint64_t* wl /* LDS [kScanWaves][64] */, uint32_t wave, uint32_t lane, uint32_t k, BoundCtrl* __restrict__ ctrl,
+// true: this workgroup was the last (every other one has taken its ticket, so has read whatever it reads of the control words).
+__device__ __forceinline__ bool bound_scan_tail(uint64_t list, uint64_t thr, uint64_t* wl /* LDS [kScanWaves][64] */, uint32_t wave, uint32_t lane, uint32_t k, BoundCtrl* __restrict__ ctrl,
                                                 uint64_t* __restrict__ partial, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
     __shared__ uint32_t s_last;
     const uint32_t kth = k - 1;
@@ -96,13 +97,14 @@ __device__ __forceinline__ void bound_scan_tail(uint64_t list, uint64_t thr, uin
         if (lane == 0) s_last = last;
     }
     __syncthreads();
-    if (!s_last) return;
+    if (!s_last) return false;
     merge_lists_last_workgroup(partial, gridDim.x, k, seed_rows, seed_dist);
     if (wave == 0 && lane == kth) {                                    // (this lane wrote them) H: a finite k-th upper bound, or none
         const uint32_t o = ord_f32(seed_dist[kth]);
         ctrl->thr_inv = (seed_rows[kth] != 0xFFFFFFFFu && o < 0xFF800000u) ? ~o : 0u;
         ctrl->cand_cnt = 0;
     }
+    return true;
 }
 
 // SKIP (k_bound_scan<., true>: v.alive is a filter's candidate bitmap, alive & set — k_rowset_and's or the masked upload): a tile whose word is
@@ -172,11 +174,14 @@ k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl
         for (; t < v.n_tiles; t += tw) finish_tile(t, bound_tile<false>(plane + (size_t)t * steps * 128, q_lds, steps, nullptr), false);
     }
 
-    bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
+    (void)bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
 }
 
 // the rows with d_lo <= H, four per thread and step (lo: one query's ordered words; cnt: its counter; cand: its list)
-__device__ __forceinline__ void bound_collect(const uint32_t* __restrict__ lo, uint32_t n /* multiple of 64 */, uint32_t H, uint32_t* __restrict__ cnt, uint32_t* __restrict__ cand) {
+// cap: the list's capacity (the count goes on past it: the stage behind reads the overflow from it); ids: lo is a compact array and
+// ids[i] the row behind entry i (k_bound_refine8's), null: entry i is row i
+__device__ __forceinline__ void bound_collect(const uint32_t* __restrict__ lo, uint32_t n /* multiple of 64 */, uint32_t H, uint32_t* __restrict__ cnt, uint32_t* __restrict__ cand,
+                                              uint32_t cap = kBoundCandCap, const uint32_t* __restrict__ ids = nullptr) {
     const uint32_t lane = lane_id();
     for (uint32_t base = blockIdx.x * 1024u; base < n; base += gridDim.x * 1024u) {
         const uint32_t i = base + threadIdx.x * 4u;
@@ -192,18 +197,21 @@ __device__ __forceinline__ void bound_collect(const uint32_t* __restrict__ lo, u
                 if (lane == (uint32_t)__builtin_ctzll(m)) b0 = atomicAdd(cnt, (uint32_t)__builtin_popcountll(m));
                 b0 = __builtin_amdgcn_readlane(b0, (uint32_t)__builtin_ctzll(m));
                 const uint32_t slot = b0 + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-                if (c && slot < kBoundCandCap) cand[slot] = i + (uint32_t)j;
+                if (c && slot < cap) cand[slot] = ids ? ids[i + (uint32_t)j] : i + (uint32_t)j;
             }
         }
     }
 }
 __global__ void __launch_bounds__(256)
 k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand,
-                const uint32_t* __restrict__ gate = nullptr /* as k_bound_scan's */) {
+                const uint32_t* __restrict__ gate = nullptr /* as k_bound_scan's */, uint32_t cap = kBoundCandCap,
+                const uint32_t* __restrict__ n_ptr = nullptr /* behind k_bound_refine8: the compact array's length (a multiple of 64), on the device */,
+                const uint32_t* __restrict__ ids = nullptr /* ... and its rows */) {
     if (gate != nullptr && *gate == 0u) return;
     const uint32_t inv = ctrl->thr_inv;
     if (inv == 0u) return;                                             // no H: k_bound_rescore hands the query back
-    bound_collect(lo_all, n, ~inv, &ctrl->cand_cnt, cand);
+    if (n_ptr != nullptr) n = *n_ptr;
+    bound_collect(lo_all, n, ~inv, &ctrl->cand_cnt, cand, cap, ids);
 }
 
 // One query's survivors walked exactly by one workgroup, lane == survivor — the shared pass's re-score (k_bound_rescore_mq: a workgroup per query;
@@ -281,6 +289,7 @@ __device__ __forceinline__ void bound_rescore_query(const IndexView& v, const fl
 // gate (the bfloat16 stage behind the 8-bit one): zero = the 8-bit stage has answered and has cleared this stage's flag for the exact scan
 // behind; non-zero = this stage runs, and its last workgroup zeroes the word, which this launch is the last to read.
 constexpr uint32_t kBoundRescoreGrid = 64;     // 256 waves: one round for a few hundred survivors
+constexpr uint32_t kBoundRefineGrid = 256;     // k_bound_refine8: 1024 waves, a batch of 16 candidates each: one round for 16 384 candidates
 template <int M, bool P8 = false>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand,
@@ -431,6 +440,69 @@ __device__ __forceinline__ long long bound8_tile(const u4* __restrict__ p, const
     return ((long long)acc[0] + (long long)acc[1]) * 128ll + ((long long)acc[2] + (long long)acc[3]);   // (each partial sum exact in int32: dim <= kBoundMaxDim)
 }
 
+// The query of an integer stage, once per workgroup (k_bound_scan8, k_bound_scan6, k_bound_refine8): sq = max|q_i| / 16256, qq = rint(q / sq)
+// = 128 hi + lo into LDS as two int8 terms, qres = |q - sq qq| rounded up (NaN: a query without a scale — every row comes out "unsure",
+// no H, and the re-score hands the search on), qn = |q| as the reference's chain.  SUM: qsum = sum qq_i as well (the 6-bit plane's codes are
+// stored biased).  Ends behind a barrier: the terms are in LDS.
+template <bool SUM>
+__device__ __forceinline__ void bound8_stage_query(const float* __restrict__ query, uint32_t dim, int8_t* qh8, int8_t* ql8, uint32_t lane, uint32_t wave,
+                                                   double& sq_out, double& qn_out, double& qres_out, long long& qsum_out) {
+    __shared__ float s_max[kScanWaves];
+    __shared__ uint32_t s_bad[kScanWaves];
+    __shared__ double s_res[kScanWaves];
+    __shared__ double s_qn;
+    __shared__ int s_sum[kScanWaves];
+    // the query, quantised: sq = max|q_i| / 16256, qq = rint(q / sq) = 128 hi + lo; qres = |q - sq qq| rounded up
+    float mx = 0.f; bool bad = false;
+    for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) { const float x = query[i]; bad |= !((x - x) == 0.0f); mx = __builtin_fmaxf(mx, __builtin_fabsf(x)); }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) mx = __builtin_fmaxf(mx, __shfl_xor(mx, m));
+    const bool wbad = __ballot(bad) != 0ull;
+    if (lane == 0) { s_max[wave] = mx; s_bad[wave] = wbad ? 1u : 0u; }
+    __syncthreads();
+    uint32_t anybad = 0;
+    for (uint32_t w = 0; w < kScanWaves; w++) { mx = __builtin_fmaxf(mx, s_max[w]); anybad |= s_bad[w]; }
+    const bool q_ok = !anybad && mx > 0.0f;
+    const double sq = q_ok ? (double)mx / (double)kBound8QueryMax : 1.0;
+    double r2 = 0.0;
+    int qs = 0;
+    for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) {
+        const double x = q_ok ? (double)query[i] : 0.0;
+        const double qq = __builtin_rint(x / sq);                      // |qq| <= 16256
+        const double hi = __builtin_rint(qq * (1.0 / 128.0)), lo = qq - 128.0 * hi;   // |hi| <= 127, |lo| <= 64: exact
+        qh8[i] = (int8_t)(int)hi; ql8[i] = (int8_t)(int)lo;
+        if constexpr (SUM) qs += (int)qq;                              // (exact: dim * 16256 < 2^31)
+        const double d = x - sq * qq;
+        r2 = __builtin_fma(d, d, r2);
+    }
+    r2 = wave_sum_f64(r2);
+    if (lane == 0) s_res[wave] = r2;
+    if constexpr (SUM) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) qs += __shfl_xor(qs, m);
+        if (lane == 0) s_sum[wave] = qs;
+    }
+    if (wave == kScanWaves - 1) {
+        // |q| as the reference's chain (distances.go:20), one wave: 64 values per request, walked in order
+        double ma = 0.0;
+        for (uint32_t b = 0; b < dim; b += 64) {
+            const float x = b + lane < dim ? query[b + lane] : 0.f;
+            const uint32_t n = dim - b < 64u ? dim - b : 64u;
+            for (uint32_t j = 0; j < n; j++) { const double a = (double)__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), j)); ma = __builtin_fma(a, a, ma); }
+        }
+        if (lane == 0) s_qn = __builtin_sqrt(ma);
+    }
+    __syncthreads();
+    double qres2 = 0.0;
+    for (uint32_t w = 0; w < kScanWaves; w++) qres2 += s_res[w];
+    qn_out = s_qn;
+    sq_out = sq;
+    // (a query without a scale: every row comes out "unsure", no H, and the re-score hands the search on)
+    qres_out = q_ok ? __builtin_sqrt(qres2) * (1.0 + 1e-9) + 1e-300 : __builtin_nan("");
+    qsum_out = 0;
+    if constexpr (SUM) { for (uint32_t w = 0; w < kScanWaves; w++) qsum_out += (long long)s_sum[w]; }
+}
+
 // SKIP (k_bound_scan8<., true>: v.alive is a filter's candidate bitmap, as for k_bound_scan<., true>): the wave holds the word of the tile it
 // walks and has the next one's in flight behind that tile's bytes; a tile whose word is zero is not requested — plane, rnorm, rscale8, rres8 —
 // and its 64 lower-bound words are written as 0xFFFFFFFF (k_bound_collect reads every word of a reused workspace).  The query's scale, terms
@@ -443,53 +515,11 @@ k_bound_scan8(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtr
     int8_t* qh8 = reinterpret_cast<int8_t*>(smem);                     // [dim] hi terms, [dim] lo terms, dim a multiple of 16
     int8_t* ql8 = qh8 + v.dim;
     uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (size_t)v.dim * 2);   // [kScanWaves][64]
-    __shared__ float s_max[kScanWaves];
-    __shared__ uint32_t s_bad[kScanWaves];
-    __shared__ double s_res[kScanWaves];
-    __shared__ double s_qn;
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves;
-
-    // the query, quantised: sq = max|q_i| / 16256, qq = rint(q / sq) = 128 hi + lo; qres = |q - sq qq| rounded up
-    float mx = 0.f; bool bad = false;
-    for (uint32_t i = threadIdx.x; i < v.dim; i += blockDim.x) { const float x = query[i]; bad |= !((x - x) == 0.0f); mx = __builtin_fmaxf(mx, __builtin_fabsf(x)); }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) mx = __builtin_fmaxf(mx, __shfl_xor(mx, m));
-    const bool wbad = __ballot(bad) != 0ull;
-    if (lane == 0) { s_max[wave] = mx; s_bad[wave] = wbad ? 1u : 0u; }
-    __syncthreads();
-    uint32_t anybad = 0;
-    for (uint32_t w = 0; w < kScanWaves; w++) { mx = __builtin_fmaxf(mx, s_max[w]); anybad |= s_bad[w]; }
-    const bool q_ok = !anybad && mx > 0.0f;
-    const double sq = q_ok ? (double)mx / (double)kBound8QueryMax : 1.0;
-    double r2 = 0.0;
-    for (uint32_t i = threadIdx.x; i < v.dim; i += blockDim.x) {
-        const double x = q_ok ? (double)query[i] : 0.0;
-        const double qq = __builtin_rint(x / sq);                      // |qq| <= 16256
-        const double hi = __builtin_rint(qq * (1.0 / 128.0)), lo = qq - 128.0 * hi;   // |hi| <= 127, |lo| <= 64: exact
-        qh8[i] = (int8_t)(int)hi; ql8[i] = (int8_t)(int)lo;
-        const double d = x - sq * qq;
-        r2 = __builtin_fma(d, d, r2);
-    }
-    r2 = wave_sum_f64(r2);
-    if (lane == 0) s_res[wave] = r2;
-    if (wave == kScanWaves - 1) {
-        // |q| as the reference's chain (distances.go:20), one wave: 64 values per request, walked in order
-        double ma = 0.0;
-        for (uint32_t b = 0; b < v.dim; b += 64) {
-            const float x = b + lane < v.dim ? query[b + lane] : 0.f;
-            const uint32_t n = v.dim - b < 64u ? v.dim - b : 64u;
-            for (uint32_t j = 0; j < n; j++) { const double a = (double)__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), j)); ma = __builtin_fma(a, a, ma); }
-        }
-        if (lane == 0) s_qn = __builtin_sqrt(ma);
-    }
-    __syncthreads();
-    double qres2 = 0.0;
-    for (uint32_t w = 0; w < kScanWaves; w++) qres2 += s_res[w];
-    const double qn = s_qn;
-    // (a query without a scale: every row comes out "unsure", no H, and the re-score hands the search on)
-    const double qres = q_ok ? __builtin_sqrt(qres2) * (1.0 + 1e-9) + 1e-300 : __builtin_nan("");
+    double sq, qn, qres; long long qsum;
+    bound8_stage_query<false>(query, v.dim, qh8, ql8, lane, wave, sq, qn, qres, qsum);
 
     const u4* qh = reinterpret_cast<const u4*>(qh8);
     const u4* ql = reinterpret_cast<const u4*>(ql8);
@@ -520,7 +550,201 @@ k_bound_scan8(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtr
         if (first) { list = wave_sort64(key, lane); thr = readlane64(list, kth); first = false; }
         else list_insert(list, thr, key, kth, lane);
     }
-    bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
+    (void)bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
+}
+
+// ---------------------------------------------------------------- one unfiltered query: reject rows on the 6-bit plane first --
+// The 8-bit stage streams 0.80 of the memory's rate and leaves 42 survivors of 10M rows at k = 10 where the re-score takes several hundred
+// in one round: the margin is far tighter than the funnel behind it needs.  So stage 1 reads IndexView::plane6 instead — three quarters
+// of the 8-bit bytes, an interval about four times as wide (qv_bound.h) — and the 8-bit plane is read for ITS candidates only:
+//   k_bound_scan6    k_bound_scan8's prologue, walk, epilogue and tail over the 6-bit plane: per group of 64 dimensions a lane reads its
+//                    row's three 16-byte pieces (each a contiguous KiB of the wave), unpacks four times 16 biased codes and takes the same
+//                    eight integer dot products per 16 dimensions; I6 = sum qq u - 32 sum qq.  Lower bounds, upper bounds and H6 as ever.
+//   k_bound_collect  with the 6-bit stage's capacity, kBound6CandCap rows.
+//   k_bound_refine8  a fixed grid, wave-strided over that list in batches of 16 (batches of 64 were measured first: four dependent rounds of
+//                    gathers per batch on a sixteenth of the CUs; profiles/LAB_r20_bound_scan6.md): per candidate the wave gathers the row's
+//                    16-byte pieces from plane8 (lane == step, a KiB apart), forms the exact 8-bit sum with the query terms k_bound_scan6
+//                    left in the workspace, lane j keeps candidate j's; from there k_bound_scan8's epilogue — bound_scan_interval8, the lower bound into a COMPACT array indexed by
+//                    candidate slot (the head of lo_all, dead since the collect), the upper bound's key into the wave's list, bound_scan_tail
+//                    into the 8-bit stage's control words.  H8 from the candidates alone is valid: every row of the true top k is a 6-bit
+//                    candidate, so k upper bounds of rows are at hand, and any k rows' upper bounds cap the k-th distance.
+//   k_bound_collect  over the compact array (its length by pointer, the candidates' rows as an indirection) into the 8-bit stage's list,
+//   and the unchanged k_bound_rescore<M, true> finishes.  A search the 6-bit stage cannot decide — more than kBound6CandCap candidates, no
+// finite H6, a query it cannot quantise — leaves the 8-bit control words WITHOUT H (every refine wave publishes a dead list), so that re-score
+// hands on to the gated bfloat16 stage: no gated full 8-bit stage in between (a gated launch costs every query 4.9 us).  More than
+// kBoundCandCap survivors of the refine hand on in the same way.  Nothing is read on the host.
+struct BoundQuery8 { double sq, qn, qres, pad; int8_t terms[2 * kBoundMaxDim]; };   // bound8_stage_query's results: [dim] hi terms, [dim] lo terms
+template <int U>
+__device__ __forceinline__ void bound6_block(const u4* __restrict__ p, const u4* __restrict__ qh, const u4* __restrict__ ql, uint32_t g0, i32 (&acc)[4]) {
+    u4 x[3 * U];
+#pragma unroll
+    for (int u = 0; u < 3 * U; u++) x[u] = __builtin_nontemporal_load(&p[((size_t)g0 * 3 + u) * 64]);
+    __builtin_amdgcn_sched_barrier(0);                                 // all requests of the block ahead of the arithmetic (see row_accumulate)
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const uint32_t X[4] = {x[3 * u].x, x[3 * u].y, x[3 * u].z, x[3 * u].w};
+        const uint32_t Y[4] = {x[3 * u + 1].x, x[3 * u + 1].y, x[3 * u + 1].z, x[3 * u + 1].w};
+        const uint32_t Z[4] = {x[3 * u + 2].x, x[3 * u + 2].y, x[3 * u + 2].z, x[3 * u + 2].w};
+        uint32_t c[4][4];                                              // [16-dimension step of the group][dword]: biased codes, a byte each
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            c[0][j] = X[j] & 0x3F3F3F3Fu; c[1][j] = Y[j] & 0x3F3F3F3Fu; c[2][j] = Z[j] & 0x3F3F3F3Fu;
+            c[3][j] = ((X[j] >> 6) & 0x03030303u) | ((Y[j] >> 4) & 0x0C0C0C0Cu) | ((Z[j] >> 2) & 0x30303030u);
+        }
+#pragma unroll
+        for (int st = 0; st < 4; st++) {
+            const u4 h = qh[(g0 + u) * 4 + st], l = ql[(g0 + u) * 4 + st];
+            acc[0] = __builtin_amdgcn_sdot4((i32)h.x, (i32)c[st][0], acc[0], false);
+            acc[1] = __builtin_amdgcn_sdot4((i32)h.y, (i32)c[st][1], acc[1], false);
+            acc[0] = __builtin_amdgcn_sdot4((i32)h.z, (i32)c[st][2], acc[0], false);
+            acc[1] = __builtin_amdgcn_sdot4((i32)h.w, (i32)c[st][3], acc[1], false);
+            acc[2] = __builtin_amdgcn_sdot4((i32)l.x, (i32)c[st][0], acc[2], false);
+            acc[3] = __builtin_amdgcn_sdot4((i32)l.y, (i32)c[st][1], acc[3], false);
+            acc[2] = __builtin_amdgcn_sdot4((i32)l.z, (i32)c[st][2], acc[2], false);
+            acc[3] = __builtin_amdgcn_sdot4((i32)l.w, (i32)c[st][3], acc[3], false);
+        }
+    }
+}
+// sum qq_i u_i of this lane's row of one tile (p = the tile in the plane + the lane); blocks of six groups: 18 KiB of a wave requested ahead
+__device__ __forceinline__ long long bound6_tile(const u4* __restrict__ p, const u4* __restrict__ qh, const u4* __restrict__ ql, uint32_t groups) {
+    i32 acc[4] = {0, 0, 0, 0};
+    uint32_t g = 0;
+    for (; g + 6 <= groups; g += 6) bound6_block<6>(p, qh, ql, g, acc);
+    if (g + 3 <= groups) { bound6_block<3>(p, qh, ql, g, acc); g += 3; }
+    if (g + 2 <= groups) { bound6_block<2>(p, qh, ql, g, acc); g += 2; }
+    if (g < groups) bound6_block<1>(p, qh, ql, g, acc);
+    return ((long long)acc[0] + (long long)acc[1]) * 128ll + ((long long)acc[2] + (long long)acc[3]);   // (each partial sum exact in int32: codes <= 63)
+}
+
+template <int M>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_scan6(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
+              uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist,
+              BoundQuery8* __restrict__ qst /* the quantised query, for k_bound_refine8 behind (workgroup 0 writes it) */) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    int8_t* qh8 = reinterpret_cast<int8_t*>(smem);                     // [dim] hi terms, [dim] lo terms, dim a multiple of 64
+    int8_t* ql8 = qh8 + v.dim;
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (size_t)v.dim * 2);   // [kScanWaves][64]
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t groups = v.dim >> 6, tw = gridDim.x * kScanWaves;
+    double sq, qn, qres; long long qsum;
+    bound8_stage_query<true>(query, v.dim, qh8, ql8, lane, wave, sq, qn, qres, qsum);
+    const long long bias = (long long)kBound6Bias * qsum;
+    if (blockIdx.x == 0) {
+        for (uint32_t i = threadIdx.x; i < v.dim / 8; i += blockDim.x) reinterpret_cast<u4*>(qst->terms)[i] = reinterpret_cast<const u4*>(smem)[i];
+        if (threadIdx.x == 0) { qst->sq = sq; qst->qn = qn; qst->qres = qres; }
+    }
+
+    const u4* qh = reinterpret_cast<const u4*>(qh8);
+    const u4* ql = reinterpret_cast<const u4*>(ql8);
+    const u4* plane = reinterpret_cast<const u4*>(v.plane6) + lane;
+    const uint32_t kth = k - 1;
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    bool first = true;
+    for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+        const uint32_t row = t * 64 + lane;
+        const double rn = v.rnorm[row];                                // (requested ahead of the tile's bytes: there when the sums are)
+        const float sc = 4.0f * v.rscale8[row], rr = v.rres6[row];     // (4 rscale8: exact)
+        const uint64_t am = v.alive[t];                                // wave-uniform
+        const long long isum = bound6_tile(plane + (size_t)t * groups * 192, qh, ql, groups) - bias;
+        float lo, hi;
+        (void)bound_scan_interval8<M>(isum, sq, qn, qres, rn, sc, rr, v.dim, lo, hi);
+        const bool live = (am >> lane) & 1ull;                         // (dead rows and the last tile's padding: never candidates, never in a bound)
+        __builtin_nontemporal_store(live ? ord_f32(lo) : 0xFFFFFFFFu, &lo_all[row]);
+        const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+        if (first) { list = wave_sort64(key, lane); thr = readlane64(list, kth); first = false; }
+        else list_insert(list, thr, key, kth, lane);
+    }
+    (void)bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
+}
+
+// ctrl6: the 6-bit stage's words (H6 and its collect's count; zeroed here by the last workgroup); ctrl8: the 8-bit stage's, which this kernel
+// leaves as k_bound_scan8 leaves them.  lo8: the compact array, entry = candidate slot, written in whole batches of 64 (slots past the
+// count: 0xFFFFFFFF); *n8: its length for the collect behind.  stats: the index's counters.
+constexpr int kRefineBatch = 16;               // candidates of a batch: their pieces are requested together (a lane: 16 dwordx4 in flight), lanes 0 - 15 keep the sums
+template <int M>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_refine8(IndexView v, const BoundQuery8* __restrict__ qst, uint32_t k, BoundCtrl* __restrict__ ctrl6, BoundCtrl* __restrict__ ctrl8, const uint32_t* __restrict__ cand6,
+                uint32_t* __restrict__ lo8, uint32_t* __restrict__ n8, uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist,
+                uint32_t* __restrict__ stats) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    int8_t* qh8 = reinterpret_cast<int8_t*>(smem);
+    int8_t* ql8 = qh8 + v.dim;
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem + (size_t)v.dim * 2);   // [kScanWaves][64]
+    const uint32_t cnt = __builtin_amdgcn_readfirstlane(ctrl6->cand_cnt), inv6 = __builtin_amdgcn_readfirstlane(ctrl6->thr_inv);   // (read by every workgroup before its ticket)
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves;
+    // the query as k_bound_scan6 quantised it (the |q| chain is dim dependent steps: not walked a second time in front of a short kernel)
+    for (uint32_t i = threadIdx.x; i < v.dim / 8; i += blockDim.x) reinterpret_cast<u4*>(smem)[i] = reinterpret_cast<const u4*>(qst->terms)[i];
+    const double sq = qst->sq, qn = qst->qn, qres = qst->qres;
+    __syncthreads();
+    const bool hand_back = inv6 == 0u || cnt > kBound6CandCap;        // (a query without a scale had no H6)
+    const uint32_t ns = hand_back ? 0u : cnt;
+
+    const u4* qh = reinterpret_cast<const u4*>(qh8);
+    const u4* ql = reinterpret_cast<const u4*>(ql8);
+    const u4* plane = reinterpret_cast<const u4*>(v.plane8);
+    const uint32_t kth = k - 1;
+    uint64_t list = kDeadKey, thr = kDeadKey;
+    bool first = true;
+    for (uint32_t b = (blockIdx.x * kScanWaves + wave) * kRefineBatch; b < ns; b += tw * kRefineBatch) {   // (wave-uniform)
+        const uint32_t slot = b + lane;
+        const bool mine_on = lane < (uint32_t)kRefineBatch, live = mine_on && slot < ns;
+        const uint32_t row = live ? cand6[slot] : 0u;                  // (row 0 is a row of the index: a slot past the count reads it and drops the sum)
+        const double rn = v.rnorm[row];
+        const float sc = v.rscale8[row], rr = v.rres8[row];
+        i32 ah[kRefineBatch], al[kRefineBatch];
+#pragma unroll
+        for (int u = 0; u < kRefineBatch; u++) { ah[u] = 0; al[u] = 0; }
+        for (uint32_t s0 = 0; s0 < steps; s0 += 64) {
+            const uint32_t st = s0 + lane;
+            const bool on = st < steps;
+            u4 x[kRefineBatch];
+#pragma unroll
+            for (int u = 0; u < kRefineBatch; u++) {
+                const uint32_t r = __builtin_amdgcn_readlane(row, u);
+                x[u] = u4{0u, 0u, 0u, 0u};
+                if (on) x[u] = __builtin_nontemporal_load(&plane[((size_t)(r >> 6) * steps + st) * 64 + (r & 63u)]);
+            }
+            const u4 zero = {0u, 0u, 0u, 0u};
+            const u4 h = on ? qh[st] : zero, l = on ? ql[st] : zero;
+#pragma unroll
+            for (int u = 0; u < kRefineBatch; u++) {
+                ah[u] = __builtin_amdgcn_sdot4((i32)h.x, (i32)x[u].x, ah[u], false);
+                ah[u] = __builtin_amdgcn_sdot4((i32)h.y, (i32)x[u].y, ah[u], false);
+                ah[u] = __builtin_amdgcn_sdot4((i32)h.z, (i32)x[u].z, ah[u], false);
+                ah[u] = __builtin_amdgcn_sdot4((i32)h.w, (i32)x[u].w, ah[u], false);
+                al[u] = __builtin_amdgcn_sdot4((i32)l.x, (i32)x[u].x, al[u], false);
+                al[u] = __builtin_amdgcn_sdot4((i32)l.y, (i32)x[u].y, al[u], false);
+                al[u] = __builtin_amdgcn_sdot4((i32)l.z, (i32)x[u].z, al[u], false);
+                al[u] = __builtin_amdgcn_sdot4((i32)l.w, (i32)x[u].w, al[u], false);
+            }
+        }
+        long long mine = 0;
+#pragma unroll
+        for (int u = 0; u < kRefineBatch; u++) {                       // (the row's sums are exact in int32: dim <= kBoundMaxDim)
+            i32 a = ah[u], c = al[u];
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) { a += __shfl_xor(a, m); c += __shfl_xor(c, m); }
+            if (lane == (uint32_t)u) mine = (long long)a * 128ll + (long long)c;
+        }
+        float lo, hi;
+        (void)bound_scan_interval8<M>(mine, sq, qn, qres, rn, sc, rr, v.dim, lo, hi);
+        if (mine_on) lo8[slot] = live ? ord_f32(lo) : 0xFFFFFFFFu;     // (slot < the count rounded up to the batch <= n_tiles * 64)
+        const uint64_t key = live ? (((uint64_t)ord_f32(hi) << 32) | row) : kDeadKey;
+        if (first) { list = wave_sort64(key, lane); thr = readlane64(list, kth); first = false; }
+        else list_insert(list, thr, key, kth, lane);
+    }
+    if (!bound_scan_tail(list, thr, wl, wave, lane, k, ctrl8, partial, seed_rows, seed_dist)) return;
+    if (threadIdx.x == 0) {
+        stats[kBound6StatsWord] = cnt;
+        if (hand_back) (void)atomicAdd(&stats[kBound6StatsWord + 1], 1u);
+        (void)atomicAdd(&stats[kBound6StatsWord + 2], 1u);
+        *n8 = (ns + (uint32_t)kRefineBatch - 1u) / (uint32_t)kRefineBatch * (uint32_t)kRefineBatch;
+        ctrl6->cand_cnt = 0; ctrl6->thr_inv = 0;                       // zero, as the words are kept
+    }
 }
 
 // ---------------------------------------------------------------- the bound scan as a shared pass: 2 - 8 queries over the bfloat16 copy --
@@ -1062,6 +1286,20 @@ constexpr uint32_t kBoundFiltMinDim = 768, kBoundFiltMqRows = 1000000, kBoundFil
 // nq x tiles x 256 bytes of lower-bound words (0.3 GB, written and read again, for 8 queries at 10M rows).  "bf16" restores the earlier routing for such hosts.
 // So: f >= 0.9 from 3 000 000 rows of 768 dimensions or more, both QB; 1M loses at k = 64 with every tile a candidate.  Spreads <= 83 us at 10M, <= 11 us below.
 constexpr uint32_t kBound8FiltMqMinDim = 768, kBound8FiltMqMinRows4 = 3000000, kBound8FiltMqMinRows8 = 3000000;   // rows of at least 768 dimensions, QB = 4 / QB = 8; 0: never automatic
+// The 6-bit stage in front of the 8-bit one (k_bound_scan6 + k_bound_refine8): one UNFILTERED query the 8-bit stage takes, on an index that
+// holds the 6-bit plane.  The index's setter (IndexView::bound_plane6) or QV_BOUND_PLANE6 = 1 puts it first whenever that holds, 2 never.
+// Automatic: the cells in which 6-bit first beat 8-bit first in both rounds by more than the rounds' disagreement, never below the 8-bit
+// stage's own floor; profiles/LAB_r20_bound_scan6.md; us per query, 8-bit first / 6-bit first (candidates of the 6-bit stage), at k = 1, 10, 64:
+//   768 dims   3M  420 / 384 (840), 426 / 443 (5 324), 486 / 615 (15 416): losses from k = 10 on
+//              10M 1283 / 1042 (675), 1288 / 1112 (6 089), 1343 / 1360 (21 432): a loss at k = 64
+//              1M  189 / 243, 193 / 280, 250 / 440 (losses; the refine in batches of 64)
+//   128 dims   10M 270 / 236 (49), 273 / 246 (190), 324 / 334 (871): a loss at k = 64
+//   1536 dims  3M  808 / 880 (9 615), 809 / 1047 (28 608), 880 / 1436 (79 492) (losses; the refine in batches of 64)
+// The refine and its collect cost about 13 us per thousand candidates, and the candidates grow with k and with the width.  So: from
+// 10M rows, 128 <= dim < 1536, k <= 10; nothing between the measured k = 10 and k = 64 is taken.
+constexpr uint32_t kBound6MinRows = 10000000, kBound6MaxDim = 1536;           // 768 <= dim < 1536
+constexpr uint32_t kBound6NarrowDim = 128, kBound6NarrowRows = 10000000;      // 128 <= dim < 768 (nothing between was measured)
+constexpr uint32_t kBound6MaxK = 10;
 // ---- the ONE decision: which stages answer a call (bound_scan_decide; plan_flat and the row-set front ask it, the launchers never) ----
 // All six forms — one query or a shared pass of 2 - 8, filtered or not, with or without the 8-bit plane first — share one skeleton, written once
 // below: "never" on the bound scan's knob, or a call the kernels cannot serve -> none; the bfloat16 stage under "always", else where the automatic
@@ -1112,9 +1350,9 @@ constexpr bool bound_floors_nest() {
 static_assert(bound_floors_nest(), "the 8-bit floors are never below the bound scan's own, class by class, and its filtered floors never below its unfiltered ones");
 static int rule_metric(const IndexView& v) { return v.metric == QV_L2 && v.l2_planes ? QV_RULE_L2_PLANES : v.metric; }
 BoundAsk bound_ask(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
-    return {rule_metric(v), v.dim, v.n_rows, nq, k, candidate_tiles, v.plane != nullptr, v.plane8 != nullptr};
+    return {rule_metric(v), v.dim, v.n_rows, nq, k, candidate_tiles, v.plane != nullptr, v.plane8 != nullptr, v.plane8 != nullptr && v.plane6 != nullptr};
 }
-BoundKnobs bound_knobs(const IndexView& v) { return {v.bound_scan, {v.bound_plane, v.bound_plane_filtered, v.bound_plane_mq, v.bound_plane_filtered_mq}}; }
+BoundKnobs bound_knobs(const IndexView& v) { return {v.bound_scan, {v.bound_plane, v.bound_plane_filtered, v.bound_plane_mq, v.bound_plane_filtered_mq}, v.bound_plane6}; }
 int bound_scan_mode(int mode) { static const int env_mode = env_int("QV_BOUND_SCAN", 0); return mode ? mode : env_mode; }
 static int bound_plane_mode(BoundForm form, int mode) {                // the form's plane mode in force: the index's own, else its variable (read once)
     static const int env_mode[4] = {env_int("QV_BOUND_PLANE", 0), env_int("QV_BOUND_PLANE_FILTERED", 0), env_int("QV_BOUND_PLANE_MQ", 0), env_int("QV_BOUND_PLANE_FILTERED_MQ", 0)};
@@ -1141,28 +1379,47 @@ static bool bound_auto(const BoundAsk& a, int rules) {
     const bool big = g.big_rows != 0 && a.n_rows >= g.big_rows;
     return ct * 10 >= n_tiles * (big ? g.big_tenths : g.tenths) && (big || g.small_k == 0 || a.k <= g.small_k);
 }
+// The 6-bit stage's automatic rule (one unfiltered query): never below the 8-bit stage's own floor, and only the cells measured faster than
+// 8-bit first by more than the rounds' disagreement (profiles/LAB_r20_bound_scan6.md).
+static bool bound6_auto(const BoundAsk& a) {
+    if (!bound_auto(a, kRulesPlane8)) return false;
+    const uint32_t floor = a.dim >= kBound6MaxDim ? 0u : a.dim >= kBoundWideDim ? kBound6MinRows : a.dim >= kBound6NarrowDim ? kBound6NarrowRows : 0u;
+    return floor != 0 && a.n_rows >= floor && a.k <= kBound6MaxK;
+}
 BoundStages bound_scan_decide(const BoundAsk& a, const BoundKnobs& knobs) {
     const int scan = bound_scan_mode(knobs.scan);
     if (scan == 2 || !bound_scan_kernels_serve(a)) return BoundStages::none;
     if (scan != 1 && !bound_auto(a, a.rule_metric == QV_RULE_L2_PLANES ? kRulesBf16L2 : kRulesBf16)) return BoundStages::none;
     const int plane = bound_plane_mode(bound_form(a), knobs.plane[bound_form(a)]);
     if (plane == 2 || !a.has_plane8) return BoundStages::bf16;
-    return plane == 1 || bound_auto(a, kRulesPlane8) ? BoundStages::plane8_first : BoundStages::bf16;
+    if (plane != 1 && !bound_auto(a, kRulesPlane8)) return BoundStages::bf16;
+    // the 6-bit stage in front of the 8-bit one: one unfiltered query, the plane held (whole 64-dimension groups), its own knob
+    if (bound_form(a) != bound_one || !a.has_plane6 || (a.dim & 63u) != 0) return BoundStages::plane8_first;
+    static const int env6 = env_int("QV_BOUND_PLANE6", 0);
+    const int plane6 = knobs.plane6 ? knobs.plane6 : env6;
+    if (plane6 == 2) return BoundStages::plane8_first;
+    return plane6 == 1 || bound6_auto(a) ? BoundStages::plane6_first : BoundStages::plane8_first;
 }
 size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles) {
-    return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)n_tiles * 64 * sizeof(uint32_t);
+    // (the 6-bit stage's list and the compact array's length are part of it on every index: the size does not depend on the plan's stages)
+    return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)kBound6CandCap * sizeof(uint32_t) + 256 + sizeof(BoundQuery8) +
+           (size_t)n_tiles * 64 * sizeof(uint32_t);
 }
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked, bool plane8_first) {
+                             uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked, bool plane8_first, bool plane6_first) {
     // (whether the path is TAKEN is plan_flat's decision; here only what the kernels need: metric, width, the copy, k)
     if (!bound_scan_kernels_serve(bound_ask(v, 1, k, kBoundNoFilter)) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
     if (plane8_first && !v.plane8) return hipErrorInvalidValue;
+    if (plane6_first && (!plane8_first || masked || !v.plane6 || !v.rres6 || (v.dim & 63u) != 0)) return hipErrorInvalidValue;
     const uint32_t grid = p.grid;
     char* w = static_cast<char*>(d_ws);
     uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256;
     uint32_t* seed_rows = reinterpret_cast<uint32_t*>(w); w += 256;
     float* seed_dist = reinterpret_cast<float*>(w); w += 256;
     uint32_t* cand = reinterpret_cast<uint32_t*>(w); w += (size_t)kBoundCandCap * sizeof(uint32_t);
+    uint32_t* cand6 = reinterpret_cast<uint32_t*>(w); w += (size_t)kBound6CandCap * sizeof(uint32_t);
+    uint32_t* n8 = reinterpret_cast<uint32_t*>(w); w += 256;
+    BoundQuery8* qst = reinterpret_cast<BoundQuery8*>(w); w += sizeof(BoundQuery8);
     uint32_t* lo_all = reinterpret_cast<uint32_t*>(w);
     const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
     BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
@@ -1177,20 +1434,38 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
         // one stage on the control words c: its scan, the collect, the re-score.  gate: the flag of the stage in front (null: none);
         // next: the stage behind, whose flag an answering 8-bit stage clears; scan_gate: k_bound_scan's own gate argument (k_bound_scan8 has none)
         // (attrs: the dynamic LDS of a stage's two kernels, for every stage before anything is launched — a call that fails enqueues nothing)
+        const uint32_t* const no_gate = nullptr;
         auto attrs = [&](auto scan, size_t lds_scan, auto rescore) -> hipError_t {
             const hipError_t e = set_lds(scan, lds_scan);
             return e != hipSuccess ? e : set_lds(rescore, lds2);
         };
         auto stage = [&](auto scan, size_t lds_scan, auto rescore, BoundCtrl* c, uint32_t* gate, BoundCtrl* next, auto... scan_gate) {
             hipLaunchKernelGGL(scan, dim3(grid), dim3(kScanBlock), lds_scan, s, v, d_query, k, c, lo_all, partial, seed_rows, seed_dist, scan_gate...);
-            hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, c, cand, (const uint32_t*)gate);
+            hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, c, cand, (const uint32_t*)gate, kBoundCandCap, no_gate, no_gate);
             hipLaunchKernelGGL(rescore, dim3(rgrid), dim3(kScanBlock), lds2, s, v, d_query, k, c, cand, d_stats, d_rows_out, d_dist_out, gate, next, partial);
         };
-        const uint32_t* const no_gate = nullptr;
         hipError_t e = attrs(k_bound_scan<M, MASKED>, lds1, k_bound_rescore<M>);
         if (e == hipSuccess && plane8_first) e = attrs(k_bound_scan8<M, MASKED>, lds8, k_bound_rescore<M, true>);
+        if constexpr (!MASKED) {
+            if (e == hipSuccess && plane6_first) e = set_lds(k_bound_scan6<M>, lds8);
+            if (e == hipSuccess && plane6_first) e = set_lds(k_bound_refine8<M>, lds8);
+        }
         if (e != hipSuccess) return e;
-        if (plane8_first) {
+        if (plane6_first) {
+            if constexpr (!MASKED) {
+                // the 6-bit stage on the third set of control words; its refine leaves the 8-bit stage's words as k_bound_scan8 would (or without
+                // H: a hand-back), the compact array of 8-bit lower bounds in the head of lo_all, and that stage's collect and re-score finish
+                BoundCtrl *ctrl8 = ctrl + 1, *ctrl6 = ctrl + 2;
+                uint32_t* gate8 = &ctrl8->flag;
+                const uint32_t fgrid = std::min(kBoundRefineGrid, grid), cgrid8 = std::min(cgrid, kBound6CandCap / 1024u);
+                hipLaunchKernelGGL(k_bound_scan6<M>, dim3(grid), dim3(kScanBlock), lds8, s, v, d_query, k, ctrl6, lo_all, partial, seed_rows, seed_dist, qst);
+                hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, ctrl6, cand6, no_gate, kBound6CandCap, no_gate, no_gate);
+                hipLaunchKernelGGL(k_bound_refine8<M>, dim3(fgrid), dim3(kScanBlock), lds8, s, v, (const BoundQuery8*)qst, k, ctrl6, ctrl8, cand6, lo_all, n8, partial, seed_rows, seed_dist, d_stats);
+                hipLaunchKernelGGL(k_bound_collect, dim3(cgrid8), dim3(256), 0, s, lo_all, 0u, ctrl8, cand, no_gate, kBoundCandCap, (const uint32_t*)n8, (const uint32_t*)cand6);
+                hipLaunchKernelGGL((k_bound_rescore<M, true>), dim3(rgrid), dim3(kScanBlock), lds2, s, v, d_query, k, ctrl8, cand, d_stats, d_rows_out, d_dist_out, (uint32_t*)nullptr, ctrl, partial);
+                stage(k_bound_scan<M, MASKED>, lds1, k_bound_rescore<M>, ctrl, gate8, (BoundCtrl*)nullptr, (const uint32_t*)gate8);
+            }
+        } else if (plane8_first) {
             // the 8-bit stage on the second set of control words, in the same workspace (the stages run one after the other); the bfloat16 stage
             // behind it is gated on that stage's flag and leaves at once when it has answered
             BoundCtrl* ctrl8 = ctrl + 1;
@@ -1242,6 +1517,41 @@ int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float*
     }
     *out_scale = scale;
     *out_res = bound8_row_res(bad, maxabs, n2, s2, dim);
+    return 0;
+}
+
+// one row as k_row_state6 (qv_misc.hip) leaves it: per group of 64 dimensions the pieces X, Y, Z (48 bytes), the residual from the codes
+int host_quantize_row6(uint32_t dim, const float* row, float scale8, uint8_t* out_bytes, float* out_res) {
+    float maxabs = 0.f; bool bad = false; double n2 = 0.0;
+    for (uint32_t i = 0; i < dim; i++) {
+        bad |= !((row[i] - row[i]) == 0.0f);
+        maxabs = __builtin_fmaxf(maxabs, __builtin_fabsf(row[i]));
+        n2 = __builtin_fma((double)row[i], (double)row[i], n2);
+    }
+    const float div = scale8 > 0.0f ? scale8 : 1.0f;
+    const double step = 4.0 * (double)scale8;
+    double s2 = 0.0;
+    for (uint32_t g = 0; g < dim / 64; g++) {
+        uint8_t piece[48] = {};
+        for (uint32_t d = 0; d < 64; d++) {
+            const float x = row[g * 64 + d];
+            const int q = scale8 > 0.0f ? bound6_quant(x, div) : 0;
+            const double e = (double)x - step * (double)q;
+            s2 = __builtin_fma(e, e, s2);
+            bound6_pack(piece, d, (uint32_t)(q + kBound6Bias));
+        }
+        for (uint32_t i = 0; i < 48; i++) out_bytes[g * 48 + i] = piece[i];
+    }
+    const float res8 = bound8_row_res(bad, maxabs, n2, 0.0, dim);      // (whether the 8-bit state declines the row: NaN)
+    *out_res = res8 == res8 ? bound8_res_up(s2) : __builtin_nanf("");
+    return 0;
+}
+int host_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes) {
+    for (uint32_t g = 0; g < dim / 64; g++) {
+        uint8_t piece[48];
+        for (uint32_t i = 0; i < 48; i++) piece[i] = bytes[g * 48 + i];
+        for (uint32_t d = 0; d < 64; d++) out_codes[g * 64 + d] = (uint8_t)bound6_unpack(piece, d);
+    }
     return 0;
 }
 

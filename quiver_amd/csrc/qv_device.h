@@ -57,6 +57,10 @@ struct IndexView {
     int       l2_planes;  // a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE: bound_ask asks the rules as QV_RULE_L2_PLANES (0 on every other index)
     uint16_t* rowmaj16;   // may be null: bfloat16 copy of the rows in row order, [rows][dim] (QV_FLAG_GRAPH_PLANE: cosine / dot, rowmaj kept, dim a multiple of
                           // 64 up to 4096); element = (__bf16)x, the conversion k_row_residual measures.  Written wherever rowmaj is (k_rowmaj16)
+    uint8_t*  plane6;     // may be null: the 6-bit plane, [tile][dim/64][3][64 rows][16 B] (qv_bound.h: bound6_pack), kept wherever plane8 is kept and dim is a
+                          // multiple of 64 — never without plane8, whose scale it shares.  Refreshed with it (k_row_state6).
+    float*    rres6;      // per row: |r - 4 rscale8 c6| rounded up; NaN = a row the 6-bit bound says nothing about
+    int       bound_plane6; // qv_index_set_bound_plane6: 0 the 6-bit stage in front of the 8-bit one from its measured shapes on, 1 whenever that one is taken, 2 never
 };
 
 struct GraphView {
@@ -170,6 +174,7 @@ struct FlatPass {                   // what one pass over the corpus is launched
     uint32_t  qb = 0;               // queries per corpus pass (bound_mq, split_mq, mq)
     bool      filtered = false;     // v.alive is a filter's candidate bitmap: the bound routes' forms that skip tiles without a candidate
     bool      plane8_first = false; // bound_mq and bound8_first: the 8-bit stage in front of the bfloat16 stage (for one query the route's number says it too)
+    bool      plane6_first = false; // bound8_first, unfiltered only: the 6-bit stage in front of the 8-bit stage's refine (a decision inside the route, as the plane is inside bound_mq)
 };
 struct FlatPlan : FlatPass {        // the call's pass; mq64 with more than 32 queries of which the last 1 - 8 are split off: the pass of
     uint32_t rem = 0;               // the first nq - rem, and the pass of the last rem behind it (never a bound route)
@@ -204,14 +209,18 @@ struct BoundAsk {                 // the call, as the rules see it
     uint32_t dim, n_rows, nq, k;
     uint32_t candidate_tiles;     // kBoundNoFilter, or the tiles that hold a candidate of any query of the pass (an upper bound known on the host)
     bool has_plane, has_plane8;   // the bfloat16 copy / the 8-bit plane is held
+    bool has_plane6 = false;      // ... and the 6-bit plane
 };
 enum BoundForm { bound_one = 0, bound_one_filtered, bound_mq, bound_mq_filtered };   // follows from nq and candidate_tiles; each has a plane knob of its own
 inline BoundForm bound_form(const BoundAsk& a) { return (BoundForm)((a.nq > 1 ? 2 : 0) + (a.candidate_tiles != kBoundNoFilter ? 1 : 0)); }
 struct BoundKnobs {               // host only.  0: the environment variable decides (read once), else automatic — the measured floors
     int scan;                     // qv_index_set_bound_scan / QV_BOUND_SCAN: 1 whenever the kernels serve the call, 2 never
     int plane[4];                 // by BoundForm: qv_index_set_bound_plane, _filtered, _mq, _filtered_mq / QV_BOUND_PLANE, _FILTERED, _MQ, _FILTERED_MQ:
-};                                // 1 the 8-bit stage first whenever the bound scan takes the call and the plane is held, 2 never
-enum class BoundStages { none, bf16, plane8_first };
+                                  // 1 the 8-bit stage first whenever the bound scan takes the call and the plane is held, 2 never
+    int plane6 = 0;               // qv_index_set_bound_plane6 / QV_BOUND_PLANE6 (one unfiltered query only): 1 the 6-bit stage first whenever the 8-bit stage would be and the plane is held, 2 never
+};
+enum class BoundStages { none, bf16, plane8_first, plane6_first };   // plane6_first: plane8_first with the 6-bit stage in front (bound_one only)
+inline bool bound_stages_8bit(BoundStages s) { return s == BoundStages::plane8_first || s == BoundStages::plane6_first; }
 BoundStages bound_scan_decide(const BoundAsk& a, const BoundKnobs& knobs);
 bool bound_scan_kernels_serve(const BoundAsk& a);   // the kernels' own limits: metric, k, 1 - 8 queries, the copy, whole 16-dimension steps, 8 tiles, lower bounds under 2 GiB
 BoundAsk bound_ask(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
@@ -225,7 +234,8 @@ size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tile
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                              uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s,
                              bool masked = false,   // v.alive is a filter's candidate bitmap: the form that does not request tiles without a candidate (k_bound_scan<., true>)
-                             bool plane8_first = false);   // the 8-bit stage (k_bound_scan8; masked: its skipping form) in front, the bfloat16 stage gated behind it: d_ctrl = 2 BoundCtrl
+                             bool plane8_first = false,   // the 8-bit stage (k_bound_scan8; masked: its skipping form) in front, the bfloat16 stage gated behind it: d_ctrl = 2 BoundCtrl
+                             bool plane6_first = false);  // (with plane8_first, unmasked) k_bound_scan6 + k_bound_refine8 in the place of k_bound_scan8: d_ctrl = 3 BoundCtrl
 // ... and for the 2 - 8 queries of a shared pass (k_bound_scan_mq): d_ws bound_scan_mq_workspace_bytes, d_ctrl 8 BoundCtrl; the exact scan of
 // the queries it hands back is enqueued behind it (launch_flat_redo_flagged)
 size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim);
@@ -237,6 +247,12 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
 int host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi);
 int host_bound_interval8(int metric, uint32_t dim, long long isum, double sq, double qn, double qres, double rn, float rscale, float rres8, float* d_lo, float* d_hi);
 int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float* out_scale, float* out_res);
+// one row as k_row_state6 leaves it: out_bytes[dim * 3 / 4] = the row's three 16-byte pieces per 64-dimension group, in the order X, Y, Z
+// (scale8: the row's 8-bit scale, as host_quantize_row8 gives it); and those bytes back into biased codes u[dim]
+int host_quantize_row6(uint32_t dim, const float* row, float scale8, uint8_t* out_bytes, float* out_res);
+int host_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes);
+constexpr uint32_t kBound6StatsWord = 7;   // the 6-bit stage's counters: [7] candidates it passed to the refine, [8] hand-backs, [9] searches
+constexpr uint32_t kBound6CandCap = 262144;   // rows the refine walks on the 8-bit plane (1 MiB of the workspace)
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches
 constexpr uint32_t kBoundCtrlWord = 16;   // the bound scan's control words start here in the stream's 64 ticket words
 bool flat_split_applies(const IndexView& v, uint32_t nq, uint32_t k);   // the tile-over-eight-waves form's own conditions (plan_flat: route split, given tickets)

@@ -330,6 +330,48 @@ k_row_state8(IndexView v, uint32_t t0) {
     v.rscale8[(size_t)t * 64 + lane] = scale;
     v.rres8[(size_t)t * 64 + lane] = bound8_row_res(bad, maxabs, n2, s2, v.dim);
 }
+// The 6-bit plane of tiles [t0, t0 + n_tiles) and its residual (qv_bound.h: bound6_quant, bound6_pack's layout): launched behind k_row_state8,
+// whose scale it reads.  One wave per tile, lane == row: per group of 64 dimensions the lane's three 16-byte pieces X, Y, Z, each a
+// contiguous KiB of the wave; rres6 = |r - 4 rscale8 c6| from the codes written, in float64, rounded up; a row the 8-bit state declines
+// (rres8 is NaN) is declined here.  dim is a multiple of 64 (the index keeps no 6-bit plane otherwise).
+__global__ void __launch_bounds__(64)
+k_row_state6(IndexView v, uint32_t t0) {
+    const uint32_t t = t0 + blockIdx.x, lane = threadIdx.x, groups = v.dim >> 6;
+    const f4* src = reinterpret_cast<const f4*>(v.tiles) + (size_t)t * v.dim4 * 64 + lane;
+    const float scale = v.rscale8[(size_t)t * 64 + lane];
+    const float res8 = v.rres8[(size_t)t * 64 + lane];
+    const float div = scale > 0.0f ? scale : 1.0f;
+    const double step = 4.0 * (double)scale;
+    double s2 = 0.0;
+    uint4* dst = reinterpret_cast<uint4*>(v.plane6) + (size_t)t * groups * 3 * 64 + lane;
+    for (uint32_t g = 0; g < groups; g++) {
+        uint32_t w[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+        for (int c = 0; c < 16; c++) {                                 // chunk c: dims 4 c .. 4 c + 3 of the group
+            const f4 x = src[(size_t)(16 * g + c) * 64];
+            const float e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int q = scale > 0.0f ? bound6_quant(e[j], div) : 0;
+                const double d = (double)e[j] - step * (double)q;
+                s2 = __builtin_fma(d, d, s2);
+                const uint32_t u = (uint32_t)(q + kBound6Bias);
+                if (c < 12) w[c >> 2][c & 3] |= u << (8 * j);
+                else {
+                    w[0][c - 12] |= (u & 3u) << (8 * j + 6);
+                    w[1][c - 12] |= ((u >> 2) & 3u) << (8 * j + 6);
+                    w[2][c - 12] |= ((u >> 4) & 3u) << (8 * j + 6);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            uint4 o; o.x = w[c][0]; o.y = w[c][1]; o.z = w[c][2]; o.w = w[c][3];
+            dst[((size_t)g * 3 + c) * 64] = o;
+        }
+    }
+    v.rres6[(size_t)t * 64 + lane] = res8 == res8 ? bound8_res_up(s2) : __builtin_nanf("");
+}
 // The row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE) of the rows of tiles [t0, t0 + n_tiles): rowmaj16[row][e] = (__bf16)row[e], round to nearest
 // even — the very conversion k_row_residual measures, from the same tiles, so rres[row] >= |r - rh| holds for the image a graph hop reads.
 // One thread per (row, chunk of four elements), the chunk index fastest: a row's 2 * dim bytes are written contiguously.  Whole tiles are
@@ -362,8 +404,13 @@ static hipError_t refresh_bf16(const IndexView& v, uint32_t t0, uint32_t t1, hip
     }
     if (v.plane8) {                                                    // (the 8-bit plane and its row state: never behind the tiles either)
         hipLaunchKernelGGL(k_row_state8, dim3(t1 - t0 + 1), dim3(64), 0, s, v, t0);
-        const hipError_t e = hipGetLastError();
+        hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
+        if (v.plane6) {                                                // (behind it: the scale is the 8-bit plane's)
+            hipLaunchKernelGGL(k_row_state6, dim3(t1 - t0 + 1), dim3(64), 0, s, v, t0);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
     }
     if (!v.plane) return hipSuccess;
     const uint64_t total = (uint64_t)(t1 - t0 + 1) * ((v.dim4 + 1) / 2) * 64;

@@ -1031,7 +1031,7 @@ FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t 
     if ((int)nq >= mq_min_queries()) {
         // 2. 2 - 8 queries sharing one pass over the bfloat16 copy (forced on, it goes ahead of the short-corpus form; on its own it leaves that form its shapes)
         if (nq >= 2 && bound_takes && (bound_scan_mode(v.bound_scan) == 1 || !flat_split_mq_applies(v, nq, k))) {
-            f.route = FlatRoute::bound_mq; f.qb = nq <= 4 ? 4u : 8u; f.plane8_first = stages == BoundStages::plane8_first;
+            f.route = FlatRoute::bound_mq; f.qb = nq <= 4 ? 4u : 8u; f.plane8_first = bound_stages_8bit(stages);
             return f;
         }
         // 3. / 4.  A last pass of 8 queries or fewer costs a whole 32-query pass of the matrix kernel (1.15 ms at 1M x 768) but only an
@@ -1048,7 +1048,8 @@ FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t 
     // 5. one query: the bound scan on the bfloat16 copy (the 8-bit stage first where the decision says so), its exact re-score, and the
     // exact scan behind them that runs only when they hand the query back
     if (nq == 1 && bound_takes && p.grid > 1) {
-        f.plane8_first = stages == BoundStages::plane8_first;
+        f.plane8_first = bound_stages_8bit(stages);
+        f.plane6_first = stages == BoundStages::plane6_first;          // (never under a filter: bound_scan_decide)
         f.route = f.plane8_first ? FlatRoute::bound8_first : FlatRoute::bound;
         return f;
     }
@@ -1172,13 +1173,14 @@ static hipError_t route_bound(const IndexView& v, const ScanPlan& p, const FlatP
         else fprintf(stderr, "qv: scan kernel = k_bound_scan masked (tiles=%u, candidate tiles<=%u, k=%u)\n", v.n_tiles, c.candidate_tiles, k);
     }
     else if (trace_unfiltered()) {
-        if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8 + k_bound_collect + k_bound_rescore, then gated k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
+        if (f.plane6_first) fprintf(stderr, "qv: scan kernel = k_bound_scan6 + k_bound_collect + k_bound_refine8 + k_bound_collect + k_bound_rescore, then gated k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
+        else if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8 + k_bound_collect + k_bound_rescore, then gated k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
         else fprintf(stderr, "qv: scan kernel = k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
     }
     const uint32_t* gate = nullptr;
     if (c.ev0) (void)hipEventRecord(c.ev0, s);
     hipError_t e = launch_bound_scan(v, p, c.d_queries, k, static_cast<char*>(c.d_ws) + scan_workspace_bytes(p, 1, k), c.d_tickets + kBoundCtrlWord, c.d_bound_stats, c.d_rows_out, c.d_dist_out, &gate, s,
-                                     f.filtered, plane8_first);
+                                     f.filtered, plane8_first, f.plane6_first && !f.filtered);
     if (e != hipSuccess) return e;
     QV_DISPATCH_METRIC(v.metric, {
         if constexpr (MM == QV_COSINE || MM == QV_DOT || MM == QV_L2) {

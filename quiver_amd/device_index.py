@@ -104,7 +104,7 @@ class DeviceIndex:
     default_filter = "auto"        # the filter kernel new indexes choose (set_filter); tests and bench.py compare the kernels through it
 
     def __init__(self, dim: int, metric="cosine", device: int = 0, rowmajor: bool = False, bf16_rows: bool = False, filter=None, scan_plane: bool = True, l2_scan_plane: bool = False,
-                 graph_plane: bool = False):
+                 graph_plane: bool = False, plane6: bool = True):
         self._h = C.c_void_p()
         self.dim = int(dim)
         self.metric = metric_id(metric)
@@ -112,6 +112,7 @@ class DeviceIndex:
         check(lib().qv_index_create(C.byref(self._h), self.dim, self.metric, device, (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) |
                                     (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE) |   # scan_plane=False: no default bfloat16 copy (cosine / dot), no bound scan
                                     (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0) |   # l2_scan_plane=True: an "l2" index keeps the planes cosine / dot keep by default
+                                    (0 if plane6 else _lib.QV_FLAG_NO_PLANE6) |   # plane6=False: no 6-bit plane beside the 8-bit one
                                     (_lib.QV_FLAG_GRAPH_PLANE if graph_plane else 0)))   # graph_plane=True (with rowmajor): a bfloat16 copy in row order for DeviceGraph.set_reject_plane
         f = filter if filter is not None else DeviceIndex.default_filter
         if f not in ("auto", 0):
@@ -437,7 +438,21 @@ class DeviceIndex:
         check(lib().qv_index_bound_scan8_stats(self._h, out))
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
-    DEBUG_READ = {"rnorm": (0, np.float64), "rres": (1, np.float32), "plane": (2, np.uint16), "rowmaj16": (3, np.uint16)}
+    BOUND_PLANE6 = {"auto": 0, "always": 1, "never": 2}
+
+    def set_bound_plane6(self, mode):
+        """whether a single unfiltered query that would start on the 8-bit plane starts on the 6-bit plane: "auto" (the measured shapes),
+        "always" (whenever the 8-bit stage would be first and the plane is held), "never" (qv_index_set_bound_plane6)"""
+        check(lib().qv_index_set_bound_plane6(self._h, self.BOUND_PLANE6.get(mode, mode)))
+
+    def bound_scan6_stats(self) -> dict:
+        """candidates the last 6-bit stage passed to the refine, searches it handed on to the bfloat16 stage, searches that took it, whether the plane exists"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_index_bound_scan6_stats(self._h, out))
+        return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
+
+    DEBUG_READ = {"rnorm": (0, np.float64), "rres": (1, np.float32), "plane": (2, np.uint16), "rowmaj16": (3, np.uint16),
+                  "plane6": (4, np.uint8), "rres6": (5, np.float32), "rscale8": (6, np.float32)}
 
     def debug_read(self, what: str) -> np.ndarray:
         """FOR TESTS (qv_index_debug_read): one of the arrays ingest derives per row, as the device holds it — "rnorm" (float64 per row
@@ -450,7 +465,7 @@ class DeviceIndex:
             check(lib().qv_index_debug_read(self._h, code, out.ctypes.data, out.nbytes))
             return out
         tiles = (self.rows() + 63) // 64
-        per_tile = 2 * 64 * 8 * ((self.dim + 15) // 16) if what == "plane" else 64     # uint16 words of a tile of the copy: qv_index::bf16_tile_bytes() / 2 (qv_api_internal.h)
+        per_tile = 2 * 64 * 8 * ((self.dim + 15) // 16) if what == "plane" else self.dim * 48 if what == "plane6" else 64     # uint16 words of a tile of the copy: qv_index::bf16_tile_bytes() / 2 (qv_api_internal.h)
         out = np.empty(tiles * per_tile, dtype=dtype)
         check(lib().qv_index_debug_read(self._h, code, out.ctypes.data, out.nbytes))
         return out
@@ -933,6 +948,9 @@ class ShardedIndex:
         out = (C.c_uint64 * 4)()
         check(lib().qv_sharded_bound_scan_stats(self._h, out))
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
+
+    def set_bound_plane6(self, mode):
+        check(lib().qv_sharded_set_bound_plane6(self._h, DeviceIndex.BOUND_PLANE6.get(mode, mode)))
 
     def set_bound_plane(self, mode):
         check(lib().qv_sharded_set_bound_plane(self._h, DeviceIndex.BOUND_PLANE.get(mode, mode)))
