@@ -666,6 +666,35 @@ int qv_scan_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t
  * do not depend on the argument.  qv_scan_route is this function with QV_BOUND_PLANE_BF16: a filtered call never on route 6. */
 int qv_scan_route_ex(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
                      uint32_t candidate_tiles, int plane_mode_filtered);
+/* How a search workspace is cut into regions, on the host, without an index or a device: the layout function the launcher itself takes
+ * its pointers from, run on a null base.  kind: QV_WS_*; the shape as the layout sees it — rows x dim on a device of `cus` compute
+ * units, nq queries, lists of k; `flags` per kind (below; 0 elsewhere).  *total: the bytes the caller must provide; *end: where the last
+ * region ends (end <= total).  regions (may be null with cap 0): up to cap entries of four words in the layout's order — offset, bytes, the
+ * alignment of the type read there, 1 for a region that overlays earlier ones (an alias) — and *n_regions how many the layout has.
+ * The kinds' own arguments: QV_WS_MERGE_SELECT — `rows` = entries per gathered list, flags = lists; QV_WS_MERGE_RANKED — `rows` = keys;
+ * QV_WS_FLAT (a fused flat search, k <= 64) — flags = QV_WS_FLAT_*: what lies behind the partial lists; QV_WS_ROWSETS_CALL /
+ * QV_WS_WHERE_CALL (a shared pass of the device-pointer row-set / where searches, k <= 64, nq >= 2) — flags bit 0: sized for the
+ * shared bound pass too, bits 8 and up (WHERE_CALL): distinct filters.  < 0 on an error. */
+#define QV_WS_BOUND 0             /* the single-query bound scan */
+#define QV_WS_BOUND_MQ 1          /* the shared bound pass of 2 - 8 queries */
+#define QV_WS_REDO 2              /* the exact scan of flagged queries */
+#define QV_WS_SELECT 3            /* the radix selection's own workspace */
+#define QV_WS_FLAT_WIDE 4         /* 64 < k <= 128, one query: wave lists + selection */
+#define QV_WS_FLAT_SELECT 5       /* a key per row + selection */
+#define QV_WS_FLAT_SELECT_REDO 6  /* ... for flagged queries */
+#define QV_WS_MERGE_SELECT 7      /* the sharded merge by selection */
+#define QV_WS_MERGE_RANKED 8      /* the sharded merge by full sort */
+#define QV_WS_FULL_SORT 9         /* the full ranking */
+#define QV_WS_MQ64 10             /* the f64 matrix-core scan's query workspace */
+#define QV_WS_ROWSET 11           /* the row-set scan */
+#define QV_WS_FLAT 12             /* the fused flat search */
+#define QV_WS_ROWSETS_CALL 13     /* the row-set workspace with the call's candidate bitmap behind it */
+#define QV_WS_WHERE_CALL 14       /* ... with the candidate bitmap and the transient sets behind it */
+#define QV_WS_FLAT_PLAIN 0        /* query blocks, or the matrix-core scan's block */
+#define QV_WS_FLAT_BOUND 1        /* ... or the single-query bound scan's buffer */
+#define QV_WS_FLAT_BOUND_MQ 2     /* ... and the shared bound pass, which has the workspace to itself */
+int qv_scan_workspace_layout(int kind, int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int cus, uint32_t flags,
+                             uint64_t* total, uint64_t* end, uint32_t* n_regions, uint64_t* regions, uint32_t cap);
 /* The interval stage 1 derives for one row, on the host (the kernel's own function compiled for the CPU; metric QV_COSINE or
  * QV_DOT; every other metric: QV_ERR_UNSUPPORTED — QV_L2 included, whose interval is qv_scan_bound_interval_l2 below): s = the float32 chain of the query times the row's bfloat16 copy, qn = |query|, rn = |row|, rres = |row - bf16(row)|
  * rounded up.  Returns 1 when the row is one the bound says nothing about (always a survivor), 0 otherwise with

@@ -129,6 +129,8 @@ PROTOTYPES = {
     "qv_scan_bound8_applies_mq": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "qv_scan_bound8_applies_filtered": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     "qv_scan_route_ex": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]),
+    "qv_scan_workspace_layout": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _u32p, C.POINTER(C.c_uint64), C.c_uint32]),
     "qv_scan_bound8_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "qv_scan_bound_interval8": (C.c_int, [C.c_int, C.c_uint32, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, _f32p, _f32p]),
     "qv_scan_quantize_row8": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, _f32p, _f32p]),

@@ -505,13 +505,11 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
 static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles = qv::kBoundNoFilter) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     const qv::ScanPlan plan = qv::plan_scan(n_tiles, idx->cus);
-    if (kk <= (uint32_t)qv::kMaxFusedK && kk == k_stride) {   // partial lists + the multi-query kernels' query blocks (the small scan's lists fit in them)
+    if (kk <= (uint32_t)qv::kMaxFusedK && kk == k_stride) {
         const qv::FlatPlan fp = flat_plan(idx, nq, kk, tickets, cand_tiles);
-        const bool bound1 = fp.route == qv::FlatRoute::bound || fp.route == qv::FlatRoute::bound8_first;
-        return std::max({qv::flat_small_workspace_bytes(std::min(nq, 4u), kk),
-                        qv::scan_workspace_bytes(plan, nq, kk) + std::max(std::max((size_t)(nq + 16) * idx->dim4 * 4 * sizeof(double), qv::mq64_workspace_bytes(nq, idx->dim4)),
-                                                                          bound1 ? qv::bound_scan_workspace_bytes(plan, kk, n_tiles) : (size_t)0),   // (the bound scan's lists sit behind the exact scan's)
-                                 fp.route == qv::FlatRoute::bound_mq ? qv::bound_scan_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim) : (size_t)0});   // (a shared bound pass has the workspace to itself)
+        const qv::FlatWs what = fp.route == qv::FlatRoute::bound_mq ? qv::FlatWs::call_bound_mq
+                              : fp.route == qv::FlatRoute::bound || fp.route == qv::FlatRoute::bound8_first ? qv::FlatWs::call_bound : qv::FlatWs::call;
+        return qv::flat_layout(nullptr, what, plan, nq, kk, n_tiles, idx->dim).total;
     }
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
@@ -1252,7 +1250,7 @@ static void where_plan(const RsFilter* fl, uint32_t nq, WherePlan& wp) {
         wp.slot[q] = u;
     }
 }
-static size_t where_stride_words(const qv_index* idx) { return ((((size_t)idx->n_rows + 63) / 64) * 8 + 255) / 256 * 256 / 8; }   // a transient set's words, 256-byte aligned
+static size_t where_stride_words(const qv_index* idx) { return qv::up256((((size_t)idx->n_rows + 63) / 64) * 8) / 8; }   // a transient set's words, 256-byte aligned
 // Enqueue the evaluations on s, in front of the call's scans: launches of up to kWhereMqFilters conjunctions (k_where_mq), conjunction u into
 // d_where + u * where_stride_words — or, for a call of ONE query, alive & where straight into d_mask: its candidate bitmap, no k_rowset_and.
 // d_lits: the literals staged on the device (wp.lit_base); null: they travel as kernel arguments (wp.args_fit).  Sets fl[q].bits / anded.
@@ -1503,6 +1501,19 @@ int qv_index_rowset_coalesce_stats(qv_index* idx, uint64_t out[8]) {
     return QV_OK;
 }
 
+// The buffer of a device-pointer row-set or where search: the passes' workspace (rowsets_plan), the call's candidate bitmap behind it and,
+// behind that, a where search's transient sets (one per distinct filter, none for a lone query: its filter goes straight into the bitmap) —
+// every region on a 256-byte boundary.  mask_bytes: the bitmap's words as the call reserves them (a where search: one set's stride).
+struct FilteredCallLayout { void* ws; uint64_t *d_mask, *d_where; size_t end, total; };
+static FilteredCallLayout filtered_call_layout(void* base, size_t plan_bytes, size_t mask_bytes, size_t n_where, size_t where_stride_bytes, qv::WsLog* log = nullptr) {
+    qv::WsCarver w{static_cast<char*>(base), 0, 0, log};
+    FilteredCallLayout L{};
+    L.ws = w.take256<char>(plan_bytes);
+    L.d_mask = w.take<uint64_t>(mask_bytes / 8);
+    if (n_where) L.d_where = w.take<uint64_t>(n_where * where_stride_bytes / 8);
+    return w.finish(L);
+}
+
 int qv_index_search_rowsets_device(qv_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const qv_rowset* const* sets,
                                    uint32_t* d_rows_out, float* d_dist_out, void* stream) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
@@ -1517,14 +1528,15 @@ int qv_index_search_rowsets_device(qv_index* idx, const float* d_queries, uint32
         std::vector<RsFilter> fl(m);
         for (uint32_t q = 0; q < m; q++) fl[q].set = sets[q0 + q];
         std::vector<RowsetPiece> pieces;
-        const size_t ws_bytes = (rowsets_plan(idx, m, k, fl.data(), pieces) + 255) / 256 * 256;
+        const size_t plan_bytes = rowsets_plan(idx, m, k, fl.data(), pieces);
         const size_t words = ((size_t)idx->n_rows + 63) / 64;
         void* ws = nullptr;
         std::unique_lock<std::mutex> ws_hold;
         uint32_t* tickets = nullptr;
-        const int rc = stream_workspace(idx, s, ws_bytes + words * 8, &ws, &ws_hold, &tickets);
+        const int rc = stream_workspace(idx, s, filtered_call_layout(nullptr, plan_bytes, words * 8, 0, 0).total, &ws, &ws_hold, &tickets);
         if (rc != QV_OK) return rc;
-        return rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, ws, reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes),
+        const FilteredCallLayout L = filtered_call_layout(ws, plan_bytes, words * 8, 0, 0);
+        return rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, L.ws, L.d_mask,
                                d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, s, tickets);
     });
 }
@@ -1617,18 +1629,18 @@ int qv_index_search_where_device(qv_index* idx, const float* d_queries, uint32_t
         std::vector<RsFilter> fl(m);
         for (uint32_t q = 0; q < m; q++) fl[q].where = specs[q0 + q].tab.n ? &specs[q0 + q] : nullptr;
         std::vector<RowsetPiece> pieces;
-        const size_t ws_bytes = (rowsets_plan(idx, m, k, fl.data(), pieces) + 255) / 256 * 256;
+        const size_t plan_bytes = rowsets_plan(idx, m, k, fl.data(), pieces);
         WherePlan wp;
         where_plan(fl.data(), m, wp);
+        const size_t n_where = m > 1 ? wp.uniq.size() : 0;
         void* ws = nullptr;
         std::unique_lock<std::mutex> ws_hold;
         uint32_t* tickets = nullptr;
-        int rc = stream_workspace(idx, s, ws_bytes + stride + (m > 1 ? wp.uniq.size() * stride : 0), &ws, &ws_hold, &tickets);
+        int rc = stream_workspace(idx, s, filtered_call_layout(nullptr, plan_bytes, stride, n_where, stride).total, &ws, &ws_hold, &tickets);
         if (rc != QV_OK) return rc;
-        uint64_t* d_mask = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes);
-        uint64_t* d_where = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + ws_bytes + stride);
-        if ((rc = where_enqueue(idx, fl.data(), m, wp, d_where, d_mask, nullptr, s))) return rc;
-        return rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, ws, d_mask,
+        const FilteredCallLayout L = filtered_call_layout(ws, plan_bytes, stride, n_where, stride);
+        if ((rc = where_enqueue(idx, fl.data(), m, wp, L.d_where, L.d_mask, nullptr, s))) return rc;
+        return rowsets_enqueue(idx, d_queries + (size_t)q0 * idx->dim, m, k, fl.data(), pieces, L.ws, L.d_mask,
                                d_rows_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, s, tickets);
     });
 }
@@ -2021,6 +2033,46 @@ int qv_scan_route_ex(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint3
 
 int qv_scan_bound_applies_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int has_plane, uint32_t candidate_tiles) {
     return bound_export(-1, qv::BoundStages::bf16, metric, dim, rows, nq, k, mode, "", 0, has_plane, 0, as_count(candidate_tiles));
+}
+
+int qv_scan_workspace_layout(int kind, int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int cus, uint32_t flags,
+                             uint64_t* total, uint64_t* end, uint32_t* n_regions, uint64_t* regions, uint32_t cap) {
+    if (!total || !end || !n_regions || (cap && !regions)) return fail(QV_ERR_INVALID_ARG, "total/end/n_regions/regions is null");
+    if (metric < QV_COSINE || metric > QV_L2SQ_F64 || dim == 0 || rows == 0 || rows > 0xFFFFFFF0ull || nq == 0 || k == 0 || cus < 1)
+        return fail(QV_ERR_INVALID_ARG, "no workspace has these arguments (metric %d, dim %u, rows %llu, nq %u, k %u, cus %d)", metric, dim, (unsigned long long)rows, nq, k, cus);
+    const uint32_t n_tiles = (uint32_t)((rows + 63) / 64), dim4 = (dim + 3) / 4;
+    const qv::ScanPlan p = qv::plan_scan(n_tiles, cus);
+    qv::WsLog log;
+    switch (kind) {
+        case QV_WS_BOUND:            (void)qv::bound_scan_workspace_bytes(p, k, n_tiles, &log); break;
+        case QV_WS_BOUND_MQ:         (void)qv::bound_scan_mq_workspace_bytes(p, nq, k, n_tiles, dim, &log); break;
+        case QV_WS_REDO:             (void)qv::redo_workspace_bytes(p, nq, k, &log); break;
+        case QV_WS_SELECT:           (void)qv::select_workspace_bytes(nq, k, &log); break;
+        case QV_WS_FLAT_WIDE:        (void)qv::flat_wide_workspace_bytes(p, nq, k, &log); break;
+        case QV_WS_FLAT_SELECT:      (void)qv::flat_select_workspace_bytes(n_tiles, nq, k, dim4, &log); break;
+        case QV_WS_FLAT_SELECT_REDO: (void)qv::flat_select_redo_workspace_bytes(n_tiles, nq, k, dim, dim4, &log); break;
+        case QV_WS_MERGE_SELECT:     (void)qv::merge_select_workspace_bytes(flags, nq, (uint32_t)rows, k, &log); break;
+        case QV_WS_MERGE_RANKED:     (void)qv::merge_ranked_workspace_bytes(rows, &log); break;
+        case QV_WS_FULL_SORT:        (void)qv::full_sort_workspace_bytes(n_tiles, &log); break;
+        case QV_WS_MQ64:             (void)qv::mq64_workspace_bytes(nq, dim4, &log); break;
+        case QV_WS_ROWSET:           (void)qv::rowset_workspace_bytes(p, nq, k, dim4, &log); break;
+        case QV_WS_FLAT:
+            if (flags > QV_WS_FLAT_BOUND_MQ) return fail(QV_ERR_INVALID_ARG, "flags must be one of QV_WS_FLAT_*; got %u", flags);
+            (void)qv::flat_layout(nullptr, flags == QV_WS_FLAT_BOUND_MQ ? qv::FlatWs::call_bound_mq : flags == QV_WS_FLAT_BOUND ? qv::FlatWs::call_bound : qv::FlatWs::call, p, nq, k, n_tiles, dim, &log);
+            break;
+        case QV_WS_ROWSETS_CALL: case QV_WS_WHERE_CALL: {                 // (the plan of a shared pass: rowsets_plan's k <= kMaxFusedK, nq >= 2 branch)
+            const size_t plan_bytes = std::max(qv::rowset_workspace_bytes(p, nq, k, dim4), (flags & 1u) ? qv::bound_scan_mq_workspace_bytes(p, nq, k, n_tiles, dim) : (size_t)0);
+            const size_t words = n_tiles, stride = qv::up256(words * 8);
+            if (kind == QV_WS_ROWSETS_CALL) (void)filtered_call_layout(nullptr, plan_bytes, words * 8, 0, 0, &log);
+            else (void)filtered_call_layout(nullptr, plan_bytes, stride, flags >> 8, stride, &log);
+        } break;
+        default: return fail(QV_ERR_INVALID_ARG, "kind must be one of QV_WS_*; got %d", kind);
+    }
+    *total = log.total; *end = log.end; *n_regions = log.n;
+    for (uint32_t i = 0; i < std::min(std::min(log.n, cap), qv::WsLog::kCap); i++) {
+        regions[4 * i] = log.r[i].off; regions[4 * i + 1] = log.r[i].bytes; regions[4 * i + 2] = log.r[i].align; regions[4 * i + 3] = log.r[i].alias ? 1 : 0;
+    }
+    return QV_OK;
 }
 
 int qv_index_profile(qv_index* idx, int enable) {

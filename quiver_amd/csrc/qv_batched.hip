@@ -2602,16 +2602,9 @@ static bool plan_batched(const IndexView& v, uint32_t nq, uint32_t k, int cus, b
 }
 
 // ---- the batch's workspace --------------------------------------------------------------
-// ONE description of the buffer: batched_workspace_bytes runs it with a null base for `total`, launch_batched for the pointers.
-// take() moves both `off` (where the next region starts) and `need` (what the caller must provide); the round-ups to 256 bytes move
-// `off` alone and slack() `need` alone — the slack terms are the hand-written size's, which counted no round-up but the first: six
-// round-ups (three without the large-k block) cost 1530 (765) bytes at most, the slack is 3324 (1788), so end <= total.
-struct WsCarver {
-    char* base; size_t off, need;
-    template <typename T> T* take(size_t count) { T* q = base ? reinterpret_cast<T*>(base + off) : nullptr; off += count * sizeof(T); need += count * sizeof(T); return q; }
-    void align256() { off = (off + 255) / 256 * 256; }
-    void slack(size_t bytes) { need += bytes; }
-};
+// ONE description of the buffer (WsCarver, qv_workspace.h): batched_workspace_bytes runs it with a null base for `total`, launch_batched
+// for the pointers.  The slack terms are the hand-written size's, which counted no round-up but the first: six round-ups (three without
+// the large-k block) cost 1530 (765) bytes at most, the slack is 3324 (1788), so end <= total.
 struct BatchedLayout {
     float* Qt; float *cq, *mq, *eq;
     uint32_t* cand; float* cscore; uint32_t *cnt, *ovf, *sparse, *n_in;
@@ -2624,7 +2617,7 @@ static BatchedLayout batched_layout(void* base, const IndexView& v, const ScanPl
     WsCarver w{static_cast<char*>(base), 0, 0};
     const size_t nq = r.nq, nq_pad = r.nq_pad, ccap = r.ccap;
     BatchedLayout L{};
-    w.take<char>(scan_workspace_bytes(p, r.nq, r.k) + (nq + 16) * v.dim4 * 4 * sizeof(double));   // the front is launch_flat_topk's: sample scan (partials + query blocks)
+    w.take<char>(flat_layout(nullptr, FlatWs::sample, p, r.nq, r.k, v.n_tiles, v.dim).total);   // the front is launch_flat_topk's: sample scan (partials + query blocks)
     w.align256(); w.need = w.off;
     // Qt (chunk count padded to even) / the bf16 hi + lo planes (padded to whole steps; up to eight steps at least for the padded eight-wave
     // kernel) and that kernel's KiB of zeros behind them.  The sample pass and the main pass share it: k_mfma_prep lays it out twice.

@@ -1400,11 +1400,23 @@ BoundStages bound_scan_decide(const BoundAsk& a, const BoundKnobs& knobs) {
     if (plane6 == 2) return BoundStages::plane8_first;
     return plane6 == 1 || bound6_auto(a) ? BoundStages::plane6_first : BoundStages::plane8_first;
 }
-size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles) {
-    // (the 6-bit stage's list and the compact array's length are part of it on every index: the size does not depend on the plan's stages)
-    return ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + 512 + (size_t)kBoundCandCap * sizeof(uint32_t) + (size_t)kBound6CandCap * sizeof(uint32_t) + 256 + sizeof(BoundQuery8) +
-           (size_t)n_tiles * 64 * sizeof(uint32_t);
+// the single-query bound scan's buffer (the 6-bit stage's list and the compact array's length are part of it on every index: the size does
+// not depend on the plan's stages)
+struct BoundLayout { uint64_t* partial; uint32_t* seed_rows; float* seed_dist; uint32_t *cand, *cand6, *n8; BoundQuery8* qst; uint32_t* lo_all; size_t end, total; };
+static BoundLayout bound_layout(void* base, const ScanPlan& p, uint32_t k, uint32_t n_tiles, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    BoundLayout L{};
+    L.partial = w.take256<uint64_t>((size_t)p.grid * k);             // stage 1's lists; the re-score publishes in them
+    L.seed_rows = w.take<uint32_t>(64);                               // the k best upper bounds' rows ...
+    L.seed_dist = w.take<float>(64);                                  // ... and values
+    L.cand = w.take<uint32_t>(kBoundCandCap);                         // survivors the re-score walks
+    L.cand6 = w.take<uint32_t>(kBound6CandCap);                       // the 6-bit stage's candidates, for the refine
+    L.n8 = w.take<uint32_t>(64);                                      // the compact array's length (one word of 256 bytes)
+    L.qst = w.take<BoundQuery8>(1);                                   // the 8-bit query state the 6-bit stage leaves for the refine
+    L.lo_all = w.take<uint32_t>((size_t)n_tiles * 64);                // a lower bound per row slot
+    return w.finish(L);
 }
+size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles, WsLog* log) { return bound_layout(nullptr, p, k, n_tiles, log).total; }
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                              uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s, bool masked, bool plane8_first, bool plane6_first) {
     // (whether the path is TAKEN is plan_flat's decision; here only what the kernels need: metric, width, the copy, k)
@@ -1412,15 +1424,11 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
     if (plane8_first && !v.plane8) return hipErrorInvalidValue;
     if (plane6_first && (!plane8_first || masked || !v.plane6 || !v.rres6 || (v.dim & 63u) != 0)) return hipErrorInvalidValue;
     const uint32_t grid = p.grid;
-    char* w = static_cast<char*>(d_ws);
-    uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += ((size_t)p.grid * k * sizeof(uint64_t) + 255) / 256 * 256;
-    uint32_t* seed_rows = reinterpret_cast<uint32_t*>(w); w += 256;
-    float* seed_dist = reinterpret_cast<float*>(w); w += 256;
-    uint32_t* cand = reinterpret_cast<uint32_t*>(w); w += (size_t)kBoundCandCap * sizeof(uint32_t);
-    uint32_t* cand6 = reinterpret_cast<uint32_t*>(w); w += (size_t)kBound6CandCap * sizeof(uint32_t);
-    uint32_t* n8 = reinterpret_cast<uint32_t*>(w); w += 256;
-    BoundQuery8* qst = reinterpret_cast<BoundQuery8*>(w); w += sizeof(BoundQuery8);
-    uint32_t* lo_all = reinterpret_cast<uint32_t*>(w);
+    const BoundLayout L = bound_layout(d_ws, p, k, v.n_tiles);
+    uint64_t* partial = L.partial;
+    uint32_t *seed_rows = L.seed_rows, *cand = L.cand, *cand6 = L.cand6, *n8 = L.n8, *lo_all = L.lo_all;
+    float* seed_dist = L.seed_dist;
+    BoundQuery8* qst = L.qst;
     const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
     BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
     const size_t lds1 = (size_t)v.dim * sizeof(float) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
@@ -1557,11 +1565,24 @@ int host_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes) {
 
 // the shared pass of 2 - 8 queries: d_ws = bound_scan_mq_workspace_bytes, d_ctrl = kBoundMqMax BoundCtrl (zero, left zero).  The exact scan of the
 // queries handed back is part of it (launch_flat_redo_flagged, in the bytes the lower bounds leave behind): nothing is read on the host.
-static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim) {
-    return up256((size_t)nq * p.grid * k * sizeof(uint64_t)) + 2 * up256((size_t)kBoundMqMax * 64 * 4) + 256 + 256 + up256((size_t)dim * kBoundMqMax * sizeof(float)) +
-           std::max((size_t)nq * kBoundCandCap * sizeof(uint32_t) + (size_t)nq * n_tiles * 64 * sizeof(uint32_t), redo_workspace_bytes(p, nq, k));
+struct BoundMqLayout { uint64_t* partial; uint32_t* seed_rows; float* seed_dist; uint32_t* flags; double* qnorm; float* qblk; uint32_t *cand, *lo_all; void* redo_ws; size_t end, total; };
+static BoundMqLayout bound_mq_layout(void* base, const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    BoundMqLayout L{};
+    L.partial = w.take256<uint64_t>((size_t)nq * p.grid * k);
+    L.seed_rows = w.take256<uint32_t>((size_t)kBoundMqMax * 64);
+    L.seed_dist = w.take256<float>((size_t)kBoundMqMax * 64);
+    L.flags = w.take<uint32_t>(64);                                   // [0, 8) the exact scan's flags; the 8-bit stage's hand-on words from kBound8MqHandWord
+    L.qnorm = w.take<double>(32);                                     // the queries' norms (the 8-bit stage: its three scalars per query)
+    L.qblk = w.take256<float>((size_t)dim * kBoundMqMax);             // the query block (the 8-bit stage: its terms)
+    WsCarver redo = w.overlay();                                      // (cand and lo_all are dead once the re-score has run: the redo of hand-backs takes their bytes)
+    L.cand = w.take<uint32_t>((size_t)nq * kBoundCandCap);
+    L.lo_all = w.take<uint32_t>((size_t)nq * n_tiles * 64);
+    L.redo_ws = redo.take<char>(redo_workspace_bytes(p, nq, k));
+    w.cover(redo);
+    return w.finish(L);
 }
+size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log) { return bound_mq_layout(nullptr, p, nq, k, n_tiles, dim, log).total; }
 hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                                 uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets, bool plane8_first) {
     // plane8_first: the 8-bit stage — k_bound_prep8_mq, k_bound_scan8_mq (with h_sets: its set form over the same table), merge, collect,
@@ -1579,16 +1600,12 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
         else fprintf(stderr, "qv: scan kernel = k_bound_scan_mq sets QB=%d (nq=%u, tiles=%u)\n", nq <= 4 ? 4 : 8, nq, v.n_tiles);
     }
     const uint32_t grid = p.grid;
-    char* w = static_cast<char*>(d_ws);
-    uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += up256((size_t)nq * grid * k * sizeof(uint64_t));
-    uint32_t* seed_rows = reinterpret_cast<uint32_t*>(w); w += up256((size_t)kBoundMqMax * 64 * 4);
-    float* seed_dist = reinterpret_cast<float*>(w); w += up256((size_t)kBoundMqMax * 64 * 4);
-    uint32_t* flags = reinterpret_cast<uint32_t*>(w); w += 256;
-    double* qnorm = reinterpret_cast<double*>(w); w += 256;
-    float* qblk = reinterpret_cast<float*>(w); w += up256((size_t)v.dim * kBoundMqMax * sizeof(float));
-    void* redo_ws = w;                                                 // (cand and lo_all are dead once the re-score has run)
-    uint32_t* cand = reinterpret_cast<uint32_t*>(w); w += (size_t)nq * kBoundCandCap * sizeof(uint32_t);
-    uint32_t* lo_all = reinterpret_cast<uint32_t*>(w);
+    const BoundMqLayout L = bound_mq_layout(d_ws, p, nq, k, v.n_tiles, v.dim);
+    uint64_t* partial = L.partial;
+    uint32_t *seed_rows = L.seed_rows, *flags = L.flags, *cand = L.cand, *lo_all = L.lo_all;
+    float *seed_dist = L.seed_dist, *qblk = L.qblk;
+    double* qnorm = L.qnorm;
+    void* redo_ws = L.redo_ws;
     const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
     BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
     const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);

@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "qv_workspace.h"
 
 namespace qv {
 
@@ -125,12 +126,23 @@ ScanPlan plan_scan(uint32_t n_tiles, int cus);
 
 // exact multi-query scan on the f64 matrix cores (qv_mq64.hip): 0 = not applicable, else 16-query blocks per pass
 int mq64_blocks(int metric, uint32_t dim4, uint32_t nq);
-size_t mq64_workspace_bytes(uint32_t nq, uint32_t dim4);
+size_t mq64_workspace_bytes(uint32_t nq, uint32_t dim4, WsLog* log = nullptr);
 hipError_t launch_flat_scan_mq64(const IndexView& v, int cus, const float* d_queries, uint32_t nq, uint32_t k, void* d_qws, uint64_t* partial,
                                  uint32_t* grid_out, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 
-// bytes of workspace for nq queries at list length k (partial lists)
-size_t scan_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k);
+// The workspace of a fused flat search (k <= kMaxFusedK), the ONE statement of it: the partial lists of nq queries at list length k, then
+// one tail — the multi-query kernels' query blocks, or the matrix-core scan's block (mq64_workspace_bytes), or (call_bound) the
+// single-query bound scan's buffer, all three starting at `tail` — and over the whole of it the small scan's lists and (call_bound_mq) the
+// shared bound pass's buffer, which have the workspace to themselves and start at `partial`.
+enum class FlatWs {
+    lists,          // the partial lists alone: a caller that lays its own tail at `tail` (the row-set scan)
+    sample,         // ... and the query blocks (the batch's front: its sample scan)
+    call,           // a search call: every tail a route without a bound scan reads, and the small scan's lists
+    call_bound,     // ... whose route is bound / bound8_first
+    call_bound_mq,  // ... whose route is bound_mq
+};
+struct FlatLayout { uint64_t* partial; void* tail; size_t end, total; };
+FlatLayout flat_layout(void* base, FlatWs what, const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr);
 
 // --- ingest ---------------------------------------------------------------------
 // d_rows [n][dim] row-major on device -> tiles at rows [row0, row0+n); computes rnorm;
@@ -147,7 +159,7 @@ hipError_t launch_fetch_rows(const IndexView& v, const uint32_t* d_rows, uint32_
 
 // --- search ---------------------------------------------------------------------
 // Flat scan + fused top-k for k <= kMaxFusedK.  d_queries [nq][dim] float32 on device.
-// d_ws: workspace of scan_workspace_bytes().  Writes d_rows_out/d_dist_out [nq][k]
+// d_ws: workspace of flat_layout().  Writes d_rows_out/d_dist_out [nq][k]
 // (padded with 0xFFFFFFFF / +inf).
 // ev0/ev1 (optional): recorded immediately before/after the scan kernel on `s`.
 // d_tickets (optional): 64 zeroed words that belong to the caller's stream alone — with them a single query is ONE launch (the last
@@ -230,7 +242,7 @@ int bound_scan_mode(int mode);   // the mode in force: the index's own, else QV_
 // the distance is within the k-th smallest upper bound, stage 2 computes those rows' distances in the scan's own arithmetic and writes
 // the k results, or sets *gate (a device word) when the exact scan must answer instead; the caller then issues the exact scan with that
 // gate (it leaves at once when the word is zero).  d_ctrl: the stream's zeroed control words (kept zero); d_stats: the index's counters.
-size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles);
+size_t bound_scan_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles, WsLog* log = nullptr);
 hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                              uint32_t* d_rows_out, float* d_dist_out, const uint32_t** gate_out, hipStream_t s,
                              bool masked = false,   // v.alive is a filter's candidate bitmap: the form that does not request tiles without a candidate (k_bound_scan<., true>)
@@ -238,7 +250,7 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
                              bool plane6_first = false);  // (with plane8_first, unmasked) k_bound_scan6 + k_bound_refine8 in the place of k_bound_scan8: d_ctrl = 3 BoundCtrl
 // ... and for the 2 - 8 queries of a shared pass (k_bound_scan_mq): d_ws bound_scan_mq_workspace_bytes, d_ctrl 8 BoundCtrl; the exact scan of
 // the queries it hands back is enqueued behind it (launch_flat_redo_flagged)
-size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim);
+size_t bound_scan_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr);
 hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                                 uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
                                 const RowSetRef* h_sets = nullptr,   // a HOST array of nq sets, at most 8: query j over alive & h_sets[j] (k_bound_scan_mq<., ., true>, the redo included)
@@ -258,7 +270,7 @@ constexpr uint32_t kBoundCtrlWord = 16;   // the bound scan's control words star
 bool flat_split_applies(const IndexView& v, uint32_t nq, uint32_t k);   // the tile-over-eight-waves form's own conditions (plan_flat: route split, given tickets)
 // The exact scan (k <= kMaxFusedK) for exactly the queries whose d_flags word is non-zero — the ones a filter handed back —, listed and
 // scanned on the device: nothing is read back.  Results replace rows / distances [q][k_stride] of those queries.  d_ws: redo_workspace_bytes.
-size_t redo_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k);
+size_t redo_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, WsLog* log = nullptr);
 hipError_t launch_flat_redo_flagged(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, uint32_t k_stride, const uint32_t* d_flags,
                                     void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s,
                                     const RowSetRef* h_sets = nullptr);   // a HOST array of nq <= 8 sets (cosine / dot): query q is redone over alive & h_sets[q], tiles without a candidate skipped
@@ -275,12 +287,12 @@ hipError_t launch_merge_shards(const uint32_t* d_packed, const uint32_t* d_bases
 // The same merge for lists of any length (k > kMaxFusedK: a filtered search asks every shard for its full ranking): the valid
 // entries of the G sorted lists [planes][nq][kcap] of query q become 64-bit keys (distance, global row), one stable radix sort
 // orders them, the first k_out are written (padded with 0xFFFFFFFF / +inf).  d_ws: merge_ranked_workspace_bytes(G * kcap).
-size_t merge_ranked_workspace_bytes(uint64_t n_keys);
+size_t merge_ranked_workspace_bytes(uint64_t n_keys, WsLog* log = nullptr);
 hipError_t launch_merge_ranked(const uint32_t* d_packed, const uint32_t* d_bases, uint32_t n_lists, uint32_t nq, uint32_t q, uint32_t kcap, uint32_t planes,
                                uint32_t k_out, void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
 // The merge for kMaxFusedK < k_out <= kMaxSelectK, every query of the batch in one go: keys of all gathered entries, then the radix
 // selection of the kk = min(k_out, valid entries) smallest (qv_select.hip) — 6 launches for the batch instead of 18 per query.
-size_t merge_select_workspace_bytes(uint32_t n_lists, uint32_t nq, uint32_t kcap, uint32_t k_out);
+size_t merge_select_workspace_bytes(uint32_t n_lists, uint32_t nq, uint32_t kcap, uint32_t k_out, WsLog* log = nullptr);
 hipError_t launch_merge_select(const uint32_t* d_packed, const uint32_t* d_bases, uint32_t n_lists, uint32_t nq, uint32_t kcap, uint32_t planes,
                                uint32_t k_out, uint32_t kk, void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
 // payload lookup after a merge: out[i] = payload plane `plane` of the list entry that produced merged global row rows[i]
@@ -295,7 +307,7 @@ hipError_t launch_merge_pairs(const float* d_dist, const uint32_t* d_rows, uint3
 struct RowSetRef { const uint64_t* bits; uint32_t words; uint32_t pad_; };
 // Exact multi-query scan, k <= kMaxFusedK, query q restricted to alive & h_sets[q] (a HOST array: the table travels to the device as
 // kernel arguments, nothing is uploaded).  d_ws: rowset_workspace_bytes.  Writes [nq][k] lists padded with 0xFFFFFFFF / +inf.
-size_t rowset_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t dim4);
+size_t rowset_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t dim4, WsLog* log = nullptr);
 hipError_t launch_rowset_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, const RowSetRef* h_sets,
                               void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // d_out[t] = alive[t] & set[t] over the index's tiles (the candidate bitmap of the single-query and k > 64 paths)
@@ -407,14 +419,14 @@ hipError_t launch_hnsw_search_wave(const IndexView& v, const GraphView& g, const
 // window0_counted: the kernel that made the keys also counted the selection's first window (select_prepare before it: qv_select.h)
 struct SelState;
 uint32_t select_cap(uint32_t kk);
-size_t select_workspace_bytes(uint32_t nq, uint32_t kk);
+size_t select_workspace_bytes(uint32_t nq, uint32_t kk, WsLog* log = nullptr);
 hipError_t select_prepare(void* d_ws, uint32_t nq, uint32_t kk, SelState** st_out, uint32_t** hist_out, hipStream_t s);
 hipError_t launch_select_topk(const uint64_t* d_keys, size_t stride, uint32_t n, uint32_t nq, uint32_t kk, uint32_t k_stride, void* d_ws,
                               uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool window0_counted = false, bool ordered = true,
                               const uint32_t* d_active = nullptr /* device word: queries from *d_active on are left alone */);
 // 64 < kk <= kMaxWideK: the scan with a list of 2 keys per lane (same stream as launch_flat_topk, no key per row written),
 // then the selection over the waves' lists.  ev0 / ev1 as launch_flat_topk.
-size_t flat_wide_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t kk);
+size_t flat_wide_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t kk, WsLog* log = nullptr);
 hipError_t launch_flat_wide(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // keys [nq][n_tiles * 64] of nq >= 2 queries, QB (4 or 8) queries per corpus pass (k_flat_keys_mq); d_qws: flat_keys_mq_workspace_bytes
@@ -423,18 +435,18 @@ hipError_t launch_flat_keys_mq(const IndexView& v, const ScanPlan& p, const floa
                                const uint32_t* d_active = nullptr /* device word: only the first *d_active queries are worked on */);
 // scan + selection for nq queries at list length kk <= kMaxSelectK: every query's keys (one 8-byte key per row, k_flat_keys), then
 // launch_select_topk; queries go in groups so that the keys of a group stay under flat_select_group_bytes
-size_t flat_select_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim4);
+size_t flat_select_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim4, WsLog* log = nullptr);
 hipError_t launch_flat_select(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
                               void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
 // The same for the queries whose flags are set (64 < kk <= kMaxSelectK: the batched filter's hand-backs above the wave lists' range), decided
 // and listed on the device: nothing is read back.  Results replace rows / distances [q][k_stride] of those queries.
-size_t flat_select_redo_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim, uint32_t dim4);
+size_t flat_select_redo_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log = nullptr);
 hipError_t launch_flat_select_redo(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride, const uint32_t* d_flags,
                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
 
 // Full ranking path (any k): all distances -> 64-bit keys -> stable radix sort -> first k.
 // d_keys_a/d_keys_b: two buffers of n_tiles*64 u64; d_hist: radix histogram workspace.
-size_t  full_sort_workspace_bytes(uint32_t n_tiles);
+size_t  full_sort_workspace_bytes(uint32_t n_tiles, WsLog* log = nullptr);
 hipError_t launch_flat_fullsort(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k,
                                 void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
 

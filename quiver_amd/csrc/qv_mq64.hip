@@ -564,10 +564,26 @@ int mq64_blocks(int metric, uint32_t dim4, uint32_t nq) {
     if (mq64_lds_bytes(dim4, sh) * sh.wgs > 158 * 1024) return 0;
     return 16 * sh.h * sh.nb;
 }
-// query fragments + query constants + the sample pass's bounds
-size_t mq64_workspace_bytes(uint32_t nq, uint32_t dim4) {
-    return (size_t)(nq + 32) * dim4 * 4 * sizeof(float) + 256 + (size_t)(nq + 32) * sizeof(double) + 256 + (size_t)(nq + 32) * sizeof(uint64_t) + 256 + 256;
+// query fragments + query constants + the sample pass's bounds + the bounded kernel's overflow word, for whole groups of Q queries.  The
+// size counts nq + 32 queries whatever the shape: the groups' padding stays within that because Q <= 32 for every Mq64Shape, and the
+// rest is slack.
+struct Mq64Layout { float* qfrag; double* qconst; uint64_t* bound; uint32_t* overflow; size_t end, total; };
+static Mq64Layout mq64_layout(void* base, uint32_t nq, uint32_t dim4, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    const Mq64Shape sh = mq64_shape(nq);
+    const size_t Q = (size_t)16 * sh.h * sh.nb, padded = (nq + Q - 1) / Q * Q, spare = (size_t)nq + 32 - std::min<size_t>(padded, (size_t)nq + 32);
+    Mq64Layout L{};
+    L.qfrag = w.take<float>(padded * dim4 * 4);
+    w.align256(); w.slack(256);                                       // (the size counts a flat 256 bytes for each round-up)
+    L.qconst = w.take<double>(padded);
+    w.align256(); w.slack(256);
+    L.bound = w.take<uint64_t>(padded);
+    w.align256(); w.slack(256);
+    L.overflow = w.take<uint32_t>(64);
+    w.slack(spare * ((size_t)dim4 * 4 * sizeof(float) + sizeof(double) + sizeof(uint64_t)));   // (the queries counted beyond the groups' padding)
+    return w.finish(L);
 }
+size_t mq64_workspace_bytes(uint32_t nq, uint32_t dim4, WsLog* log) { return mq64_layout(nullptr, nq, dim4, log).total; }
 
 // partial[(q * grid + wg) * k + i]; returns the grid used through *grid_out.  ev0/ev1 bracket the full pass.
 hipError_t launch_flat_scan_mq64(const IndexView& v, int cus, const float* d_queries, uint32_t nq, uint32_t k, void* d_qws, uint64_t* partial,
@@ -575,12 +591,12 @@ hipError_t launch_flat_scan_mq64(const IndexView& v, int cus, const float* d_que
     if (mq64_blocks(v.metric, v.dim4, nq) == 0) return hipErrorInvalidValue;
     const Mq64Shape sh = mq64_shape(nq);
     const uint32_t B = (uint32_t)(sh.h * sh.nb), Q = 16u * B, groups = (nq + Q - 1) / Q;
-    auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
-    unsigned char* ws = static_cast<unsigned char*>(d_qws);
-    float* qfrag = reinterpret_cast<float*>(ws);
-    double* qconst = reinterpret_cast<double*>(ws + up256((size_t)groups * Q * v.dim4 * 4 * sizeof(float)));
-    uint64_t* bound = reinterpret_cast<uint64_t*>(reinterpret_cast<unsigned char*>(qconst) + up256((size_t)groups * Q * sizeof(double)));
-    uint32_t* overflow = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(bound) + up256((size_t)groups * Q * sizeof(uint64_t)));
+    const Mq64Layout L = mq64_layout(d_qws, nq, v.dim4);
+    if (L.end > L.total) return hipErrorInvalidValue;                 // (cannot happen while Q <= 32: see mq64_layout)
+    float* qfrag = L.qfrag;
+    double* qconst = L.qconst;
+    uint64_t* bound = L.bound;
+    uint32_t* overflow = L.overflow;
     const uint32_t want = (v.n_tiles + (uint32_t)sh.w - 1) / (uint32_t)sh.w;
     uint32_t grid = std::max(1u, std::min(want, (uint32_t)cus * (uint32_t)sh.wgs));
     // the sample: one tile per wave of `sgrid` workgroups, spread evenly over the corpus (QV_MQ64_SAMPLE tiles, 0 = no sample

@@ -243,10 +243,21 @@ k_shard_keys_all(const uint32_t* __restrict__ packed, const uint32_t* __restrict
     keys[(size_t)q * stride + i] = key;
 }
 
-size_t merge_select_workspace_bytes(uint32_t n_lists, uint32_t nq, uint32_t kcap, uint32_t k_out) {
-    const size_t stride = ((size_t)n_lists * kcap + 1) & ~(size_t)1;
-    return (size_t)nq * stride * sizeof(uint64_t) + 256 + select_workspace_bytes(nq, k_out);
+// keys of every query's gathered entries (an even stride), then the selection's workspace; shared by the three buffers of "keys, then a
+// selection" below
+struct KeysSelectLayout { uint64_t* keys; void* sel_ws; size_t end, total; };
+static KeysSelectLayout keys_select_cut(WsCarver& w, size_t n_keys, uint32_t nq, uint32_t kk) {
+    KeysSelectLayout L{};
+    L.keys = w.take<uint64_t>(n_keys);
+    w.align256(); w.slack(256);                                       // (the sizes count a flat 256 bytes for this round-up)
+    L.sel_ws = w.take<char>(select_workspace_bytes(nq, kk));
+    return L;
 }
+static KeysSelectLayout merge_select_layout(void* base, uint32_t n_lists, uint32_t nq, uint32_t kcap, uint32_t k_out, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    return w.finish(keys_select_cut(w, (size_t)nq * (((size_t)n_lists * kcap + 1) & ~(size_t)1), nq, k_out));
+}
+size_t merge_select_workspace_bytes(uint32_t n_lists, uint32_t nq, uint32_t kcap, uint32_t k_out, WsLog* log) { return merge_select_layout(nullptr, n_lists, nq, kcap, k_out, log).total; }
 
 // merge of the gathered per-shard lists for kMaxFusedK < k_out <= kMaxSelectK, all nq queries in one go: keys, then the radix
 // selection (qv_select.hip) of the min(k_out, valid entries) smallest; outputs [nq][k_out], padded
@@ -255,24 +266,35 @@ hipError_t launch_merge_select(const uint32_t* d_packed, const uint32_t* d_bases
     const uint64_t n64 = (uint64_t)n_lists * kcap;
     if (n_lists == 0 || kcap == 0 || k_out == 0 || kk == 0 || kk > k_out || planes < 2 || n64 > 0x7FFFFF00ull || kk > n64) return hipErrorInvalidValue;
     const uint32_t stride = ((uint32_t)n64 + 1u) & ~1u;
-    uint64_t* keys = static_cast<uint64_t*>(d_ws);
-    void* sel_ws = static_cast<char*>(d_ws) + ((size_t)nq * stride * sizeof(uint64_t) + 255) / 256 * 256;
+    const KeysSelectLayout L = merge_select_layout(d_ws, n_lists, nq, kcap, k_out);
+    uint64_t* keys = L.keys;
+    void* sel_ws = L.sel_ws;
     hipLaunchKernelGGL(k_shard_keys_all, dim3((stride + 255) / 256, nq), dim3(256), 0, s, d_packed, d_bases, n_lists, nq, kcap, planes, stride, keys);
     return launch_select_topk(keys, stride, stride, nq, kk, k_out, sel_ws, d_rows_out, d_dist_out, s);
 }
 
-size_t merge_ranked_workspace_bytes(uint64_t n_keys) {
-    return 2 * n_keys * sizeof(uint64_t) + radix_hist_words((uint32_t)n_keys) * sizeof(uint32_t) + 256;
+// a full sort's buffer: the keys, the sort's second buffer, the radix histograms
+struct SortLayout { uint64_t *ka, *kb; uint32_t* hist; size_t end, total; };
+static SortLayout sort_layout(void* base, size_t n_keys, size_t hist_words, WsLog* log) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    SortLayout L{};
+    L.ka = w.take<uint64_t>(n_keys);
+    L.kb = w.take<uint64_t>(n_keys);
+    L.hist = w.take<uint32_t>(hist_words);
+    w.slack(256);                                                      // (counted by both sizes; no region uses it)
+    return w.finish(L);
 }
+static SortLayout merge_ranked_layout(void* base, uint64_t n_keys, WsLog* log = nullptr) { return sort_layout(base, n_keys, radix_hist_words((uint32_t)n_keys), log); }
+size_t merge_ranked_workspace_bytes(uint64_t n_keys, WsLog* log) { return merge_ranked_layout(nullptr, n_keys, log).total; }
 
 hipError_t launch_merge_ranked(const uint32_t* d_packed, const uint32_t* d_bases, uint32_t n_lists, uint32_t nq, uint32_t q, uint32_t kcap, uint32_t planes,
                                uint32_t k_out, void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
     const uint64_t n64 = (uint64_t)n_lists * kcap;
     if (n_lists == 0 || kcap == 0 || k_out == 0 || planes < 2 || n64 > 0xFFFFFF00ull) return hipErrorInvalidValue;
     const uint32_t n = (uint32_t)n64;
-    uint64_t* ka = static_cast<uint64_t*>(d_ws);
-    uint64_t* kb = ka + n;
-    uint32_t* hist = reinterpret_cast<uint32_t*>(kb + n);
+    const SortLayout L = merge_ranked_layout(d_ws, n64);
+    uint64_t *ka = L.ka, *kb = L.kb;
+    uint32_t* hist = L.hist;
     hipLaunchKernelGGL(k_shard_keys, dim3((n + 255) / 256), dim3(256), 0, s, d_packed, d_bases, n_lists, nq, q, kcap, planes, ka);
     uint64_t* in = nullptr;
     hipError_t e = launch_radix_sort_hi32(ka, kb, n, hist, &in, s);
@@ -314,10 +336,18 @@ static uint32_t flat_select_group(uint32_t n_tiles, uint32_t nq) {
     const size_t per_query = (size_t)n_tiles * 64 * sizeof(uint64_t);
     return (uint32_t)std::max<size_t>(1, std::min<size_t>(nq, ((size_t)1 << 30) / per_query));
 }
-size_t flat_select_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim4) {
+// a group's keys, the selection's workspace, and — a group of two or more: shared corpus passes — the key kernel's query blocks
+struct FlatSelectLayout { uint64_t* keys; void *sel_ws, *qws; size_t end, total; };
+static FlatSelectLayout flat_select_layout(void* base, uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim4, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
     const uint32_t g = flat_select_group(n_tiles, nq);
-    return (size_t)g * n_tiles * 64 * sizeof(uint64_t) + 256 + select_workspace_bytes(g, kk) + 256 + (g >= 2 ? flat_keys_mq_workspace_bytes(g, dim4) : 0);
+    const KeysSelectLayout ks = keys_select_cut(w, (size_t)g * n_tiles * 64, g, kk);
+    FlatSelectLayout L{ks.keys, ks.sel_ws, nullptr, 0, 0};
+    w.align256(); w.slack(256);                                       // (a flat 256 bytes for this round-up too)
+    if (g >= 2) L.qws = w.take<char>(flat_keys_mq_workspace_bytes(g, dim4));
+    return w.finish(L);
 }
+size_t flat_select_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim4, WsLog* log) { return flat_select_layout(nullptr, n_tiles, nq, kk, dim4, log).total; }
 static hipError_t flat_select_impl(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const uint32_t* d_active);
 hipError_t launch_flat_select(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
@@ -330,11 +360,11 @@ static hipError_t flat_select_impl(const IndexView& v, const ScanPlan& p, const 
                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const uint32_t* d_active) {
     const uint32_t n = v.n_tiles * 64;
     const uint32_t g = flat_select_group(v.n_tiles, nq);
-    uint64_t* keys = static_cast<uint64_t*>(d_ws);
-    void* sel_ws = static_cast<char*>(d_ws) + ((size_t)g * n * sizeof(uint64_t) + 255) / 256 * 256;
+    const FlatSelectLayout L = flat_select_layout(d_ws, v.n_tiles, nq, kk, v.dim4);
+    uint64_t* keys = L.keys;
+    void *sel_ws = L.sel_ws, *qws = L.qws;
     const uint32_t batch = key_batch(v.metric, v.dim4, true);
     const size_t lds = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * batch * 64 * sizeof(uint64_t) + (size_t)kSelBins * sizeof(uint32_t);
-    void* qws = static_cast<char*>(sel_ws) + (select_workspace_bytes(g, kk) + 255) / 256 * 256;
     for (uint32_t q0 = 0; q0 < nq; q0 += g) {
         const uint32_t m = std::min(g, nq - q0);
         if (m >= 2) {
@@ -414,45 +444,52 @@ k_lk_redo_scatter(const uint32_t* __restrict__ list, const uint32_t* __restrict_
         dist_out[(size_t)q * k_stride + i] = t_dist[(size_t)j * k_stride + i];
     }
 }
-static size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-size_t flat_select_redo_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim, uint32_t dim4) {
+struct FlatSelectRedoLayout { uint32_t *list, *count; float* rq; uint32_t* t_rows; float* t_dist; void* select_ws; size_t end, total; };
+static FlatSelectRedoLayout flat_select_redo_layout(void* base, uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
     const uint32_t slots = lk_redo_slots(n_tiles, nq);
-    return up256((size_t)nq * 4) + up256((size_t)(nq + 2) * 4) + up256((size_t)slots * dim * 4) + 2 * up256((size_t)slots * kk * 4) + flat_select_workspace_bytes(n_tiles, slots, kk, dim4) + 256;
+    FlatSelectRedoLayout L{};
+    L.list = w.take256<uint32_t>(nq);                                  // the flagged queries, in order
+    L.count = w.take256<uint32_t>((size_t)nq + 2);                     // [0] how many, [1 + r] entries of round r
+    L.rq = w.take256<float>((size_t)slots * dim);                      // a round's gathered vectors
+    L.t_rows = w.take256<uint32_t>((size_t)slots * kk);                // ... and its results, before the scatter
+    L.t_dist = w.take256<float>((size_t)slots * kk);
+    L.select_ws = w.take<char>(flat_select_workspace_bytes(n_tiles, slots, kk, dim4));
+    w.slack(256);                                                      // (counted by the size; no region uses it)
+    return w.finish(L);
 }
+size_t flat_select_redo_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log) { return flat_select_redo_layout(nullptr, n_tiles, nq, kk, dim, dim4, log).total; }
 hipError_t launch_flat_select_redo(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride, const uint32_t* d_flags,
                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
     if (nq == 0) return hipSuccess;
     const uint32_t slots = lk_redo_slots(v.n_tiles, nq);
     if (kk <= (uint32_t)kMaxFusedK || kk > (uint32_t)kMaxSelectK || kk != k_stride || slots < 2) return hipErrorNotSupported;   // (a corpus whose keys leave room for one query at a time: the caller's host path)
-    char* w = static_cast<char*>(d_ws);
-    uint32_t* list = reinterpret_cast<uint32_t*>(w); w += up256((size_t)nq * 4);
-    uint32_t* count = reinterpret_cast<uint32_t*>(w); w += up256((size_t)(nq + 2) * 4);
-    float* rq = reinterpret_cast<float*>(w); w += up256((size_t)slots * v.dim * 4);
-    uint32_t* t_rows = reinterpret_cast<uint32_t*>(w); w += up256((size_t)slots * kk * 4);
-    float* t_dist = reinterpret_cast<float*>(w); w += up256((size_t)slots * kk * 4);
+    const FlatSelectRedoLayout L = flat_select_redo_layout(d_ws, v.n_tiles, nq, kk, v.dim, v.dim4);
+    uint32_t *list = L.list, *count = L.count, *t_rows = L.t_rows;
+    float *rq = L.rq, *t_dist = L.t_dist;
     hipLaunchKernelGGL(k_lk_redo_list, dim3(1), dim3(1024), 0, s, d_flags, nq, slots, list, count);
     uint32_t round = 0;
     for (uint32_t first = 0; first < nq; first += slots, round++) {
         hipLaunchKernelGGL(k_lk_redo_gather, dim3(slots), dim3(256), 0, s, d_queries, v.dim, list, count, first, rq);
-        hipError_t e = flat_select_impl(v, p, rq, slots, kk, k_stride, w, t_rows, t_dist, s, count + 1 + round);
+        hipError_t e = flat_select_impl(v, p, rq, slots, kk, k_stride, L.select_ws, t_rows, t_dist, s, count + 1 + round);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_lk_redo_scatter, dim3(slots), dim3(256), 0, s, list, count, first, t_rows, t_dist, k_stride, d_rows_out, d_dist_out);
     }
     return hipGetLastError();
 }
 
-size_t full_sort_workspace_bytes(uint32_t n_tiles) {
-    size_t n = (size_t)n_tiles * 64;
-    size_t nblocks = (n + kRadixTile - 1) / kRadixTile;
-    return 2 * n * sizeof(uint64_t) + (256 * nblocks + 512) * sizeof(uint32_t) + 256;
+static SortLayout full_sort_layout(void* base, uint32_t n_tiles, WsLog* log = nullptr) {
+    const size_t n = (size_t)n_tiles * 64, nblocks = (n + kRadixTile - 1) / kRadixTile;
+    return sort_layout(base, n, 256 * nblocks + 512, log);
 }
+size_t full_sort_workspace_bytes(uint32_t n_tiles, WsLog* log) { return full_sort_layout(nullptr, n_tiles, log).total; }
 
 hipError_t launch_flat_fullsort(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k,
                                 void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
     const uint32_t n = v.n_tiles * 64;
-    uint64_t* ka = static_cast<uint64_t*>(d_ws);
-    uint64_t* kb = ka + n;
-    uint32_t* hist = reinterpret_cast<uint32_t*>(kb + n);
+    const SortLayout L = full_sort_layout(d_ws, v.n_tiles);
+    uint64_t *ka = L.ka, *kb = L.kb;
+    uint32_t* hist = L.hist;
     const uint32_t batch = key_batch(v.metric, v.dim4, false);
     const size_t lds = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * batch * 64 * sizeof(uint64_t);
     hipError_t e = hipSuccess;

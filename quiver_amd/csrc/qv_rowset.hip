@@ -259,15 +259,24 @@ hipError_t launch_rowset_set_rows(uint64_t* d_bits, const uint32_t* d_rows, uint
     return hipGetLastError();
 }
 
-static size_t rowset_qblk_bytes(uint32_t dim4) { return ((size_t)(kRsChunk + 16) * dim4 * 4 * sizeof(double) + 255) / 256 * 256; }
-size_t rowset_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t dim4) { return scan_workspace_bytes(p, nq, k) + rowset_qblk_bytes(dim4); }
+// the flat call's partial lists (flat_layout), with one launch's query blocks as the tail: at most kRsChunk queries, in whole groups of up to 16
+struct RowsetLayout { uint64_t* partial; void* qblk; size_t end, total; };
+static RowsetLayout rowset_layout(void* base, const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t dim4, WsLog* log = nullptr) {
+    const FlatLayout f = flat_layout(base, FlatWs::lists, p, nq, k, 0, dim4 * 4, log);   // (the lists alone read neither the tiles nor the width)
+    WsCarver w{static_cast<char*>(base), f.end, f.total, log};
+    RowsetLayout L{f.partial, nullptr, 0, 0};
+    L.qblk = w.take256<double>((size_t)(kRsChunk + 16) * dim4 * 4);
+    return w.finish(L);
+}
+size_t rowset_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t dim4, WsLog* log) { return rowset_layout(nullptr, p, nq, k, dim4, log).total; }
 
 hipError_t launch_rowset_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, const RowSetRef* h_sets,
                               void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (k == 0 || k > (uint32_t)kMaxFusedK || nq == 0 || !h_sets) return hipErrorInvalidValue;
     const int trace = env_int("QV_TRACE", 0);                         // QV_TRACE=1: name the scan kernel chosen, on stderr (read per call: a getenv beside a launch)
-    uint64_t* partial_all = static_cast<uint64_t*>(d_ws);
-    void* qblk = static_cast<char*>(d_ws) + scan_workspace_bytes(p, nq, k);
+    const RowsetLayout L = rowset_layout(d_ws, p, nq, k, v.dim4);
+    uint64_t* partial_all = L.partial;
+    void* qblk = L.qblk;
     // a short corpus of wide rows: the tile-over-eight-waves form, in launches of up to 32 queries (the rule and its measurements:
     // flat_split_mq_applies); otherwise whole tiles per wave, up to kRsChunk queries per launch.  The rule admits 2 .. 32 queries, so it
     // is asked with one launch's width; its byte bound is then held against the CALL's whole count, every group of 8 reading the corpus

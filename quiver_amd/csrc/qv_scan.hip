@@ -764,7 +764,7 @@ k_flat_keys_mq(IndexView v, const typename MT<M>::Q* __restrict__ qblk, uint32_t
     }
 }
 
-size_t flat_keys_mq_workspace_bytes(uint32_t nq, uint32_t dim4) { return ((size_t)(nq + 8) * dim4 * 4 * sizeof(double) + 255) / 256 * 256; }
+size_t flat_keys_mq_workspace_bytes(uint32_t nq, uint32_t dim4) { return up256((size_t)(nq + 8) * dim4 * 4 * sizeof(double)); }
 // keys of nq >= 2 queries in shared corpus passes; d_qws: flat_keys_mq_workspace_bytes
 hipError_t launch_flat_keys_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint64_t* d_keys, void* d_qws, hipStream_t s, const uint32_t* d_active) {
     const uint32_t want = (v.n_tiles + kScanWaves - 1) / kScanWaves;
@@ -892,7 +892,23 @@ ScanPlan plan_scan(uint32_t n_tiles, int cus) {
     return p;
 }
 
-size_t scan_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k) { return ((size_t)p.n_lists * 4 * nq * k * sizeof(uint64_t) + 255) / 256 * 256; }   // x4: the multi-query scan may use up to 8 WG/CU
+FlatLayout flat_layout(void* base, FlatWs what, const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    const WsCarver whole = w.overlay();
+    const uint32_t dim4 = (dim + 3) / 4;
+    FlatLayout L{};
+    L.partial = w.take256<uint64_t>((size_t)p.n_lists * 4 * nq * k);   // x4: the multi-query scan may use up to 8 WG/CU
+    const WsCarver tail = w.overlay();
+    L.tail = base ? w.base + w.off : nullptr;
+    if (what == FlatWs::lists) return w.finish(L);
+    w.take<double>((size_t)(nq + 16) * dim4 * 4);                      // the multi-query kernels' query blocks (k_prep_qblk: whole groups of up to 16)
+    if (what == FlatWs::sample) return w.finish(L);
+    WsCarver m = tail; m.take<char>(mq64_workspace_bytes(nq, dim4)); w.cover(m);
+    if (what == FlatWs::call_bound) { WsCarver b = tail; b.take<char>(bound_scan_workspace_bytes(p, k, n_tiles)); w.cover(b); }   // (the bound scan's lists sit behind the exact scan's)
+    WsCarver s = whole; s.take<uint64_t>(flat_small_workspace_bytes(std::min(nq, 4u), k) / sizeof(uint64_t)); w.cover(s);   // (the small scan's lists: at most four queries')
+    if (what == FlatWs::call_bound_mq) { WsCarver b = whole; b.take<char>(bound_scan_mq_workspace_bytes(p, nq, k, n_tiles, dim)); w.cover(b); }   // (a shared bound pass has the workspace to itself)
+    return w.finish(L);
+}
 
 hipError_t launch_merge_pairs(const float* d_dist, const uint32_t* d_rows, uint32_t n_lists, uint32_t k,
                               uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
@@ -938,17 +954,24 @@ hipError_t launch_flat_small(const IndexView& v, const float* d_queries, uint32_
 
 // 64 < kk <= kMaxWideK: the scan with R keys per lane, then the selection over the waves' lists
 static uint32_t wide_regs(uint32_t) { return 2u; }
-size_t flat_wide_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t kk) {
-    const size_t n = (size_t)p.grid * kScanWaves * 64 * wide_regs(kk);
-    return (size_t)nq * n * sizeof(uint64_t) + 256 + select_workspace_bytes(nq, kk);
+struct FlatWideLayout { uint64_t* lists; void* sel_ws; size_t end, total; };
+static FlatWideLayout flat_wide_layout(void* base, const ScanPlan& p, uint32_t nq, uint32_t kk, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    FlatWideLayout L{};
+    L.lists = w.take<uint64_t>((size_t)nq * p.grid * kScanWaves * 64 * wide_regs(kk));   // every wave's list of R keys per lane
+    w.align256(); w.slack(256);                                       // (the size counts a flat 256 bytes for this round-up)
+    L.sel_ws = w.take<char>(select_workspace_bytes(nq, kk));
+    return w.finish(L);
 }
+size_t flat_wide_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t kk, WsLog* log) { return flat_wide_layout(nullptr, p, nq, kk, log).total; }
 hipError_t launch_flat_wide(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (kk <= (uint32_t)kMaxFusedK || kk > (uint32_t)kMaxWideK || nq == 0 || kk > k_stride) return hipErrorInvalidValue;
     const uint32_t R = wide_regs(kk);
     const uint32_t n = p.grid * kScanWaves * 64 * R;
-    uint64_t* lists = static_cast<uint64_t*>(d_ws);
-    void* sel_ws = static_cast<char*>(d_ws) + ((size_t)nq * n * sizeof(uint64_t) + 255) / 256 * 256;
+    const FlatWideLayout L = flat_wide_layout(d_ws, p, nq, kk);
+    uint64_t* lists = L.lists;
+    void* sel_ws = L.sel_ws;
     const size_t lds = query_lds_bytes(v.metric, v.dim4);
     hipError_t e = hipSuccess;
 #define QV_WIDE(RR)                                                                                              \
@@ -1122,8 +1145,9 @@ static hipError_t route_split_mq(const IndexView& v, const ScanPlan& p, uint32_t
     return launch_merge_lists(partial, grid, nq, k, c.d_rows_out, c.d_dist_out, s);
 }
 static hipError_t route_mq64(const IndexView& v, const ScanPlan& p, const FlatCall& c) {
-    uint64_t* partial = static_cast<uint64_t*>(c.d_ws);
-    void* qblk = static_cast<char*>(c.d_ws) + scan_workspace_bytes(p, c.nq, c.k);   // tail of the workspace
+    const FlatLayout L = flat_layout(c.d_ws, FlatWs::lists, p, c.nq, c.k, v.n_tiles, v.dim);
+    uint64_t* partial = L.partial;
+    void* qblk = L.tail;
     uint32_t g64 = 0;
     if (trace_unfiltered()) fprintf(stderr, "qv: scan kernel = k_flat_scan_mq64 (nq=%u, tiles=%u)\n", c.nq, v.n_tiles);
     const hipError_t e = launch_flat_scan_mq64(v, (int)p.cus, c.d_queries, c.nq, c.k, qblk, partial, &g64, c.s, c.ev0, c.ev1);
@@ -1133,12 +1157,13 @@ static hipError_t route_mq64(const IndexView& v, const ScanPlan& p, const FlatCa
 static hipError_t route_mq(const IndexView& v, const ScanPlan& p, uint32_t qb, const FlatCall& c) {
     const uint32_t nq = c.nq, k = c.k;
     hipStream_t s = c.s;
-    uint64_t* partial = static_cast<uint64_t*>(c.d_ws);
+    const FlatLayout L = flat_layout(c.d_ws, FlatWs::lists, p, nq, k, v.n_tiles, v.dim);
+    uint64_t* partial = L.partial;
     hipError_t e = hipSuccess;
     static const int mq_wg = dev_env_int("QV_MQ_WG_PER_CU", 2);
     const uint32_t want = (v.n_tiles + kScanWaves - 1) / kScanWaves;
     const uint32_t grid = std::max(1u, std::min(want, (uint32_t)mq_wg * (p.grid / 2 ? p.grid / 2 : 1)));   // p.grid = 2 WG/CU * CUs
-    void* qblk = static_cast<char*>(c.d_ws) + scan_workspace_bytes(p, nq, k);   // tail of the workspace
+    void* qblk = L.tail;
     if (trace_unfiltered()) fprintf(stderr, "qv: scan kernel = k_flat_scan_mq QB=%d (nq=%u, tiles=%u)\n", (int)qb, nq, v.n_tiles);
 #define QV_MQ_LAUNCH(MMM, QQ)                                                                                              \
     {                                                                                                                         \
@@ -1178,15 +1203,16 @@ static hipError_t route_bound(const IndexView& v, const ScanPlan& p, const FlatP
         else fprintf(stderr, "qv: scan kernel = k_bound_scan + k_bound_collect + k_bound_rescore (tiles=%u, k=%u)\n", v.n_tiles, k);
     }
     const uint32_t* gate = nullptr;
+    const FlatLayout L = flat_layout(c.d_ws, FlatWs::lists, p, c.nq, k, v.n_tiles, v.dim);   // (the bound scan's buffer behind the exact scan's lists)
     if (c.ev0) (void)hipEventRecord(c.ev0, s);
-    hipError_t e = launch_bound_scan(v, p, c.d_queries, k, static_cast<char*>(c.d_ws) + scan_workspace_bytes(p, 1, k), c.d_tickets + kBoundCtrlWord, c.d_bound_stats, c.d_rows_out, c.d_dist_out, &gate, s,
+    hipError_t e = launch_bound_scan(v, p, c.d_queries, k, L.tail, c.d_tickets + kBoundCtrlWord, c.d_bound_stats, c.d_rows_out, c.d_dist_out, &gate, s,
                                      f.filtered, plane8_first, f.plane6_first && !f.filtered);
     if (e != hipSuccess) return e;
     QV_DISPATCH_METRIC(v.metric, {
         if constexpr (MM == QV_COSINE || MM == QV_DOT || MM == QV_L2) {
             e = set_lds((k_flat_scan<MM, kUnroll, true>), lds);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_flat_scan<MM, kUnroll, true>), dim3(p.grid, 1), dim3(p.block), lds, s, v, c.d_queries, k, static_cast<uint64_t*>(c.d_ws), c.d_tickets, c.d_rows_out, c.d_dist_out, (uint32_t*)nullptr, 0u, gate);
+            hipLaunchKernelGGL((k_flat_scan<MM, kUnroll, true>), dim3(p.grid, 1), dim3(p.block), lds, s, v, c.d_queries, k, L.partial, c.d_tickets, c.d_rows_out, c.d_dist_out, (uint32_t*)nullptr, 0u, gate);
         }
     });
     if (c.ev1) (void)hipEventRecord(c.ev1, s);
@@ -1330,18 +1356,24 @@ hipError_t launch_merge_lists(const uint64_t* d_partial, uint32_t n_lists, uint3
 }
 
 // the exact scan for the queries whose flags are set, decided and listed on the device (see k_flat_scan_redo)
-size_t redo_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k) {
-    return ((size_t)kRedoSlots * p.grid * k * sizeof(uint64_t) + 255) / 256 * 256 + ((size_t)nq * 4 + 255) / 256 * 256 + ((size_t)(nq + 1) * 4 + 255) / 256 * 256;
+struct RedoLayout { uint64_t* partial; uint32_t *list, *count; size_t end, total; };
+static RedoLayout redo_layout(void* base, const ScanPlan& p, uint32_t nq, uint32_t k, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    RedoLayout L{};
+    L.partial = w.take256<uint64_t>((size_t)kRedoSlots * p.grid * k);   // the lists of one round's slots
+    L.list = w.take256<uint32_t>(nq);                                  // the flagged queries, in order
+    L.count = w.take256<uint32_t>((size_t)nq + 1);                     // how many, and behind it the rounds' tickets
+    return w.finish(L);
 }
+size_t redo_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, WsLog* log) { return redo_layout(nullptr, p, nq, k, log).total; }
 hipError_t launch_flat_redo_flagged(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, uint32_t k_stride, const uint32_t* d_flags,
                                     void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets) {
     if (k == 0 || k > (uint32_t)kMaxFusedK || nq == 0 || (h_sets && nq > kBoundSets)) return hipErrorInvalidValue;
     BoundSetTable tab;
     for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
-    char* w = static_cast<char*>(d_ws);
-    uint64_t* partial = reinterpret_cast<uint64_t*>(w); w += ((size_t)kRedoSlots * p.grid * k * sizeof(uint64_t) + 255) / 256 * 256;
-    uint32_t* list = reinterpret_cast<uint32_t*>(w); w += ((size_t)nq * 4 + 255) / 256 * 256;
-    uint32_t* count = reinterpret_cast<uint32_t*>(w);
+    const RedoLayout L = redo_layout(d_ws, p, nq, k);
+    uint64_t* partial = L.partial;
+    uint32_t *list = L.list, *count = L.count;
     hipLaunchKernelGGL(k_redo_compact, dim3(1), dim3(1024), 0, s, d_flags, nq, list, count);
     const size_t lds = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     hipError_t e = hipSuccess;

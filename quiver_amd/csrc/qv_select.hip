@@ -354,25 +354,33 @@ hipError_t launch_select_topk_counted(const uint64_t* d_keys, size_t stride, uin
 
 uint32_t select_cap(uint32_t kk) { return kk <= 4096 ? 8192u : 16384u; }   // sort capacity: twice the largest k it serves (64 / 128 KB of LDS)
 
-size_t select_workspace_bytes(uint32_t nq, uint32_t kk) {
-    return (size_t)nq * (sizeof(SelState) + (size_t)kSelBins * sizeof(uint32_t) + (size_t)select_cap(kk) * sizeof(uint64_t)) + 512;
-}
-
 // the workspace's layout: [nq] states, [nq][kSelBins] histogram words, [nq][cap] kept keys.  select_prepare zeroes the first two
 // (a caller whose keys kernel counts window 0 itself does this BEFORE that kernel and passes window0_counted = true below)
+struct SelectLayout { SelState* st; uint32_t* hist; uint64_t* cand; size_t st_bytes; size_t end, total; };
+static SelectLayout select_layout(void* base, uint32_t nq, uint32_t kk, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    SelectLayout L{};
+    L.st = w.take<SelState>(nq);
+    w.align256();
+    L.st_bytes = w.off;                                                // (the states, rounded up: what select_prepare zeroes in front of the histograms)
+    L.hist = w.take<uint32_t>((size_t)nq * kSelBins);
+    L.cand = w.take<uint64_t>((size_t)nq * select_cap(kk));
+    w.slack(512);                                                      // (the size's own margin: it covers the round-up behind the states)
+    return w.finish(L);
+}
+size_t select_workspace_bytes(uint32_t nq, uint32_t kk, WsLog* log) { return select_layout(nullptr, nq, kk, log).total; }
+
 __global__ void __launch_bounds__(256)
 k_select_zero(uint4* __restrict__ p, size_t n16) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 hipError_t select_prepare(void* d_ws, uint32_t nq, uint32_t kk, SelState** st_out, uint32_t** hist_out, hipStream_t s) {
-    char* w = static_cast<char*>(d_ws);
-    const size_t st_bytes = ((size_t)nq * sizeof(SelState) + 255) / 256 * 256;
-    *st_out = reinterpret_cast<SelState*>(w);
-    *hist_out = reinterpret_cast<uint32_t*>(w + st_bytes);
-    (void)kk;
+    const SelectLayout L = select_layout(d_ws, nq, kk);
+    *st_out = L.st;
+    *hist_out = L.hist;
     // (a kernel of our own: hipMemsetAsync took 43 us for the 4 MB of a 256-query batch)
-    const size_t n16 = (st_bytes + (size_t)nq * kSelBins * sizeof(uint32_t)) / 16;
-    hipLaunchKernelGGL(k_select_zero, dim3((unsigned)std::min<size_t>(1024, (n16 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint4*>(w), n16);
+    const size_t n16 = (L.st_bytes + (size_t)nq * kSelBins * sizeof(uint32_t)) / 16;
+    hipLaunchKernelGGL(k_select_zero, dim3((unsigned)std::min<size_t>(1024, (n16 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint4*>(L.st), n16);
     return hipGetLastError();
 }
 
@@ -380,10 +388,10 @@ hipError_t launch_select_topk(const uint64_t* d_keys, size_t stride, uint32_t n,
                               uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool window0_counted, bool ordered, const uint32_t* d_active) {
     if (nq == 0 || kk == 0 || kk > (uint32_t)kMaxSelectK || kk > k_stride || (n & 1u) || (stride & 1u) || n == 0 || kk > n) return hipErrorInvalidValue;
     const uint32_t cap = select_cap(kk);
-    char* w = static_cast<char*>(d_ws);
-    SelState* st = reinterpret_cast<SelState*>(w);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(w + (((size_t)nq * sizeof(SelState) + 255) / 256 * 256));
-    uint64_t* cand = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(hist) + (size_t)nq * kSelBins * sizeof(uint32_t));
+    const SelectLayout L = select_layout(d_ws, nq, kk);
+    SelState* st = L.st;
+    uint32_t* hist = L.hist;
+    uint64_t* cand = L.cand;
     hipError_t e = hipSuccess;
     // 8 KiB of keys per workgroup and round; enough workgroups to fill the chip, no more than the keys can feed
     const uint32_t grid = std::max(1u, std::min(1024u, (n + 4 * 2 * kSelBlock - 1) / (4 * 2 * kSelBlock)));
