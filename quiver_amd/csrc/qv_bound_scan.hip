@@ -21,8 +21,8 @@ namespace qv {
 //                    row's 2 dim); the UPPER bounds go through k_flat_scan's own selection — wave lists, the workgroups' lists published,
 //                    the last workgroup merges — so the launch ends with H, the exact k-th smallest upper bound over all live rows.
 //                    Any k rows' upper bounds cap the k-th distance: every row of the answer has d_lo <= H.
-//   k_bound_collect  the rows with d_lo <= H (not strict: ties go on) — k plus a handful on ordinary data — listed with one returning
-//                    atomic per wave and batch that has any.
+//   k_bound_collect  the rows with d_lo <= H (not strict: ties go on) — k plus a handful on ordinary data — gathered per workgroup in LDS and
+//                    listed with one returning atomic per workgroup and flush (bound_collect); the list's order is not defined.
 //   k_bound_rescore  a wave per survivor on a small fixed grid: each row requested whole, then walked as ONE float64 chain — row_accumulate's
 //                    chain + finalize, the query's norm as its chain: the exact scan's bits —, the last workgroup merges the lists and writes
 //                    the k best (distance, row) keys where the exact scan writes them.  When the list overflowed, H is not finite (fewer than k rows with a bound), or |q| is not a norm
@@ -35,6 +35,7 @@ typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kBoundCandCap = 4096;       // rows stage 3 walks exactly (an i.i.d. 10M x 768 corpus leaves k + a few)
 constexpr uint32_t kBoundMaxDim = 4096;
 struct BoundCtrl { uint32_t thr_inv, cand_cnt, ticket, flag; };   // thr_inv = ~(ordered image of H): zero = no finite H
+struct BoundQuery8 { double sq, qn, qres, pad; int8_t terms[2 * kBoundMaxDim]; };   // bound8_stage_query's results (the 6-bit stage leaves them in the workspace): [dim] hi terms, [dim] lo terms
 
 template <int U, bool QN>
 __device__ __forceinline__ void bound_block(const u4* __restrict__ p, const float* __restrict__ q_lds, uint32_t s0, float& acc, double& qa) {
@@ -177,30 +178,99 @@ k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl
     (void)bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
 }
 
-// the rows with d_lo <= H, four per thread and step (lo: one query's ordered words; cnt: its counter; cand: its list)
-// cap: the list's capacity (the count goes on past it: the stage behind reads the overflow from it); ids: lo is a compact array and
-// ids[i] the row behind entry i (k_bound_refine8's), null: entry i is row i
-__device__ __forceinline__ void bound_collect(const uint32_t* __restrict__ lo, uint32_t n /* multiple of 64 */, uint32_t H, uint32_t* __restrict__ cnt, uint32_t* __restrict__ cand,
+// the rows with d_lo <= H, eight per thread and step, a chunk of 2048 words per workgroup and step (lo: one query's ordered words; cnt: its
+// counter; cand: its list).  cap: the list's capacity (the count goes on past it by the full number: the stage behind reads the overflow from
+// it); ids: lo is a compact array and ids[i] the row behind entry i (k_bound_refine8's), null: entry i is row i.
+// The slots are reserved per WORKGROUP: a wave counts its chunk's candidates by ballot, its leader reserves in an LDS counter, the lanes put
+// their rows into an LDS buffer of a chunk and a half; when the next chunk could overflow it, and once more at the end of the walk, thread 0 takes ONE
+// returning atomicAdd(cnt, fill) and the workgroup copies its rows to cand[base .. base + fill), below cap only.  (One returning atomic per
+// wave and batch on the one counter word was 10 ns per candidate, all serialised: 59 us for 6 089 candidates of 10M rows, 18 us this
+// way; profiles/LAB_r22_bound_collect.md.)  The buffer holds entry numbers; the compact form's indirection is applied at the flush.  A chunk's trip count is uniform over the workgroup: one barrier per chunk, two more per
+// flush.  No workgroup waits for another; the ORDER of the rows in the list is whatever the reservations make it, and nothing behind depends
+// on it.  The next chunk's words are requested before this one's are looked at.
+constexpr uint32_t kCollectVecs = 2;           // 16-byte requests of a thread per chunk, 1024 words apart
+constexpr uint32_t kCollectChunk = kCollectVecs * 1024;   // words a workgroup looks at per step (256 threads x 4 x kCollectVecs): half the barriers and twice the bytes in flight of one request each
+constexpr uint32_t kCollectBuf = kCollectChunk + kCollectChunk / 2;   // rows gathered between two reservations (12 KiB of LDS): flushed once it is over a third full
+#ifndef QV_COLLECT_GRID
+#define QV_COLLECT_GRID 512u                   // workgroups at most: 40 MB of 10M rows in 17.9 us, 256: 23.8, 1024: 20.2 (profiles/LAB_r22_bound_collect.md)
+#endif
+constexpr uint32_t kBoundCollectGrid = QV_COLLECT_GRID;
+__device__ __forceinline__ void bound_collect(const uint32_t* __restrict__ lo, uint32_t n /* multiple of 16 */, uint32_t H, uint32_t* __restrict__ cnt, uint32_t* __restrict__ cand,
                                               uint32_t cap = kBoundCandCap, const uint32_t* __restrict__ ids = nullptr) {
+    __shared__ uint32_t s_rows[kCollectBuf];
+    __shared__ uint32_t s_cnt[3], s_base;                              // a chunk's count: three words in turn, so that one barrier per chunk is enough (below)
     const uint32_t lane = lane_id();
-    for (uint32_t base = blockIdx.x * 1024u; base < n; base += gridDim.x * 1024u) {
-        const uint32_t i = base + threadIdx.x * 4u;
-        u4 x = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-        if (i < n) x = __builtin_nontemporal_load(reinterpret_cast<const u4*>(lo + i));
-        const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+    const uint32_t stride = gridDim.x * kCollectChunk, mine = threadIdx.x * 4u;
+    if (threadIdx.x < 3u) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    // (entered by the whole workgroup behind a barrier that follows the last write to s_rows; `more`: another chunk follows)
+    auto flush = [&](uint32_t fill, bool more) {
+        if (threadIdx.x == 0) s_base = atomicAdd(cnt, fill);
+        __syncthreads();
+        const uint32_t b0 = s_base;
+        for (uint32_t i = threadIdx.x; i < fill; i += blockDim.x) {
+            if (b0 + i < cap) cand[b0 + i] = ids ? ids[s_rows[i]] : s_rows[i];
+        }
+        if (more) __syncthreads();                                     // the buffer is read before the next chunk writes it
+    };
+    const u4 none = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    uint32_t base = blockIdx.x * kCollectChunk;
+    uint32_t fill = 0, p = 0;                                          // rows in the buffer at the head of this chunk; this chunk's counter (both uniform)
+    // a thread's words of a chunk: requested by EVERY thread — one past the end asks for the array's head and drops it when the words
+    // are looked at — so that the request of the next chunk stays in flight behind this chunk's words (a request under a condition is
+    // waited for where the paths join)
+    bool x_on[kCollectVecs]; u4 x[kCollectVecs];
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const bool c = xs[j] <= H && xs[j] != 0xFFFFFFFFu;
-            const uint64_t m = __ballot(c);
-            if (m) {
-                uint32_t b0 = 0;
-                if (lane == (uint32_t)__builtin_ctzll(m)) b0 = atomicAdd(cnt, (uint32_t)__builtin_popcountll(m));
-                b0 = __builtin_amdgcn_readlane(b0, (uint32_t)__builtin_ctzll(m));
-                const uint32_t slot = b0 + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-                if (c && slot < cap) cand[slot] = ids ? ids[i + (uint32_t)j] : i + (uint32_t)j;
+    for (uint32_t v = 0; v < kCollectVecs; v++) {
+        x_on[v] = base < n && n - base > v * 1024u + mine;
+        x[v] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(lo + (x_on[v] ? base + v * 1024u + mine : 0u)));
+    }
+    while (base < n) {
+        const bool more = n - base > stride;                           // (no sum that could wrap)
+        bool nx_on[kCollectVecs]; u4 nx[kCollectVecs];
+#pragma unroll
+        for (uint32_t v = 0; v < kCollectVecs; v++) {
+            nx_on[v] = more && n - base - stride > v * 1024u + mine;
+            nx[v] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(lo + (nx_on[v] ? base + stride + v * 1024u + mine : 0u)));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        bool c[kCollectVecs * 4]; uint64_t m[kCollectVecs * 4];
+        uint32_t tot = 0;
+#pragma unroll
+        for (uint32_t v = 0; v < kCollectVecs; v++) {
+            if (!x_on[v]) x[v] = none;
+            const uint32_t xs[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                c[v * 4 + j] = xs[j] <= H && xs[j] != 0xFFFFFFFFu;
+                m[v * 4 + j] = __ballot(c[v * 4 + j]);
+                tot += (uint32_t)__builtin_popcountll(m[v * 4 + j]);
             }
         }
+        if (tot) {                                                     // (wave-uniform)
+            uint32_t b0 = 0;
+            if (lane == 0) b0 = atomicAdd(&s_cnt[p], tot);             // LDS
+            b0 = fill + __builtin_amdgcn_readfirstlane(b0);            // fill <= kCollectBuf - kCollectChunk, and a chunk holds kCollectChunk at most
+#pragma unroll
+            for (uint32_t e = 0; e < kCollectVecs * 4; e++) {
+                if (c[e]) s_rows[b0 + (uint32_t)__builtin_popcountll(m[e] & ((1ull << lane) - 1ull))] = base + (e >> 2) * 1024u + mine + (e & 3u);   // (the compact form's indirection: at the flush)
+                b0 += (uint32_t)__builtin_popcountll(m[e]);
+            }
+        }
+        __syncthreads();
+        // this chunk's count is final, and the next chunk counts in another word, so every thread reads the same number.  The word of the
+        // chunk BEFORE this one is zeroed for the chunk after the next: all have read it in front of the barrier above, and it is
+        // counted in again only behind the next chunk's barrier.
+        fill += s_cnt[p];
+        if (threadIdx.x == 0) s_cnt[p == 0u ? 2u : p - 1u] = 0;
+        p = p == 2u ? 0u : p + 1u;
+        if (!more) break;
+        if (fill > kCollectBuf - kCollectChunk) { flush(fill, true); fill = 0; }
+#pragma unroll
+        for (uint32_t v = 0; v < kCollectVecs; v++) { x[v] = nx[v]; x_on[v] = nx_on[v]; }
+        base += stride;
     }
+    if (fill) flush(fill, false);
 }
 __global__ void __launch_bounds__(256)
 k_bound_collect(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand,
@@ -294,7 +364,8 @@ template <int M, bool P8 = false>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand,
                 uint32_t* __restrict__ stats, uint32_t* __restrict__ rows_out, float* __restrict__ dist_out, uint32_t* gate, BoundCtrl* next,
-                uint64_t* __restrict__ partial /* [gridDim.x][k] */) {
+                uint64_t* __restrict__ partial /* [gridDim.x][k] */,
+                const BoundQuery8* __restrict__ qst = nullptr /* behind the 6-bit stage: k_bound_scan6 left |q| there, the same chain over the same values */) {
     if (gate != nullptr && *gate == 0u) return;
     using Q = typename MT<M>::Q;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -320,7 +391,10 @@ k_bound_rescore(IndexView v, const float* __restrict__ query, uint32_t k, BoundC
     }
     stage_query<M>(q_lds, query, v.dim, v.dim4);
     __syncthreads();
-    if (wave == kScanWaves - 1) {
+    if (qst != nullptr) {
+        // (dim dependent float64 steps that no survivor's chain could start ahead of: half of this launch behind the 6-bit stage)
+        if (threadIdx.x == 0) s_qn = qst->qn;
+    } else if (wave == kScanWaves - 1) {
         // |q| as the reference's chain (distances.go:20): cosine's finalize takes it, and every metric's hand-back rule
         double ma = 0.0;
         for (uint32_t i = 0; i < v.dim; i++) { const double a = (double)q_lds[i]; ma = __builtin_fma(a, a, ma); }
@@ -569,11 +643,11 @@ k_bound_scan8(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtr
 //                    into the 8-bit stage's control words.  H8 from the candidates alone is valid: every row of the true top k is a 6-bit
 //                    candidate, so k upper bounds of rows are at hand, and any k rows' upper bounds cap the k-th distance.
 //   k_bound_collect  over the compact array (its length by pointer, the candidates' rows as an indirection) into the 8-bit stage's list,
-//   and the unchanged k_bound_rescore<M, true> finishes.  A search the 6-bit stage cannot decide — more than kBound6CandCap candidates, no
+//   and k_bound_rescore<M, true> finishes, as behind k_bound_scan8 but for |q|: k_bound_scan6 has left it in the workspace (BoundQuery8::qn, the
+//   same in-order chain over the same float32 values: the same bits), so the dim dependent steps are not walked again.  A search the 6-bit stage cannot decide — more than kBound6CandCap candidates, no
 // finite H6, a query it cannot quantise — leaves the 8-bit control words WITHOUT H (every refine wave publishes a dead list), so that re-score
 // hands on to the gated bfloat16 stage: no gated full 8-bit stage in between (a gated launch costs every query 4.9 us).  More than
 // kBoundCandCap survivors of the refine hand on in the same way.  Nothing is read on the host.
-struct BoundQuery8 { double sq, qn, qres, pad; int8_t terms[2 * kBoundMaxDim]; };   // bound8_stage_query's results: [dim] hi terms, [dim] lo terms
 template <int U>
 __device__ __forceinline__ void bound6_block(const u4* __restrict__ p, const u4* __restrict__ qh, const u4* __restrict__ ql, uint32_t g0, i32 (&acc)[4]) {
     u4 x[3 * U];
@@ -1429,7 +1503,7 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
     uint32_t *seed_rows = L.seed_rows, *cand = L.cand, *cand6 = L.cand6, *n8 = L.n8, *lo_all = L.lo_all;
     float* seed_dist = L.seed_dist;
     BoundQuery8* qst = L.qst;
-    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
+    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(kBoundCollectGrid, (n_pad + kCollectChunk - 1u) / kCollectChunk);
     BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
     const size_t lds1 = (size_t)v.dim * sizeof(float) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     // the re-score: the staged query, the waves' lists, a survivor's row per wave; its grid never exceeds stage 1's, whose `partial` it publishes in
@@ -1450,7 +1524,7 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
         auto stage = [&](auto scan, size_t lds_scan, auto rescore, BoundCtrl* c, uint32_t* gate, BoundCtrl* next, auto... scan_gate) {
             hipLaunchKernelGGL(scan, dim3(grid), dim3(kScanBlock), lds_scan, s, v, d_query, k, c, lo_all, partial, seed_rows, seed_dist, scan_gate...);
             hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, c, cand, (const uint32_t*)gate, kBoundCandCap, no_gate, no_gate);
-            hipLaunchKernelGGL(rescore, dim3(rgrid), dim3(kScanBlock), lds2, s, v, d_query, k, c, cand, d_stats, d_rows_out, d_dist_out, gate, next, partial);
+            hipLaunchKernelGGL(rescore, dim3(rgrid), dim3(kScanBlock), lds2, s, v, d_query, k, c, cand, d_stats, d_rows_out, d_dist_out, gate, next, partial, (const BoundQuery8*)nullptr);
         };
         hipError_t e = attrs(k_bound_scan<M, MASKED>, lds1, k_bound_rescore<M>);
         if (e == hipSuccess && plane8_first) e = attrs(k_bound_scan8<M, MASKED>, lds8, k_bound_rescore<M, true>);
@@ -1465,12 +1539,12 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
                 // H: a hand-back), the compact array of 8-bit lower bounds in the head of lo_all, and that stage's collect and re-score finish
                 BoundCtrl *ctrl8 = ctrl + 1, *ctrl6 = ctrl + 2;
                 uint32_t* gate8 = &ctrl8->flag;
-                const uint32_t fgrid = std::min(kBoundRefineGrid, grid), cgrid8 = std::min(cgrid, kBound6CandCap / 1024u);
+                const uint32_t fgrid = std::min(kBoundRefineGrid, grid), cgrid8 = std::min(cgrid, kBound6CandCap / kCollectChunk);
                 hipLaunchKernelGGL(k_bound_scan6<M>, dim3(grid), dim3(kScanBlock), lds8, s, v, d_query, k, ctrl6, lo_all, partial, seed_rows, seed_dist, qst);
                 hipLaunchKernelGGL(k_bound_collect, dim3(cgrid), dim3(256), 0, s, lo_all, n_pad, ctrl6, cand6, no_gate, kBound6CandCap, no_gate, no_gate);
                 hipLaunchKernelGGL(k_bound_refine8<M>, dim3(fgrid), dim3(kScanBlock), lds8, s, v, (const BoundQuery8*)qst, k, ctrl6, ctrl8, cand6, lo_all, n8, partial, seed_rows, seed_dist, d_stats);
                 hipLaunchKernelGGL(k_bound_collect, dim3(cgrid8), dim3(256), 0, s, lo_all, 0u, ctrl8, cand, no_gate, kBoundCandCap, (const uint32_t*)n8, (const uint32_t*)cand6);
-                hipLaunchKernelGGL((k_bound_rescore<M, true>), dim3(rgrid), dim3(kScanBlock), lds2, s, v, d_query, k, ctrl8, cand, d_stats, d_rows_out, d_dist_out, (uint32_t*)nullptr, ctrl, partial);
+                hipLaunchKernelGGL((k_bound_rescore<M, true>), dim3(rgrid), dim3(kScanBlock), lds2, s, v, d_query, k, ctrl8, cand, d_stats, d_rows_out, d_dist_out, (uint32_t*)nullptr, ctrl, partial, (const BoundQuery8*)qst);
                 stage(k_bound_scan<M, MASKED>, lds1, k_bound_rescore<M>, ctrl, gate8, (BoundCtrl*)nullptr, (const uint32_t*)gate8);
             }
         } else if (plane8_first) {
@@ -1606,7 +1680,7 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
     float *seed_dist = L.seed_dist, *qblk = L.qblk;
     double* qnorm = L.qnorm;
     void* redo_ws = L.redo_ws;
-    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(1024u, (n_pad + 1023u) / 1024u);
+    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(kBoundCollectGrid, (n_pad + kCollectChunk - 1u) / kCollectChunk);
     BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
     const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
     hipError_t e = hipSuccess;
