@@ -22,6 +22,7 @@ import (
 type rows interface {
 	add(flat []float32, n int) ([]uint32, error)
 	update(row uint32, v []float32) error
+	updateRows(rows []uint32, flat []float32) error
 	remove(rows []uint32) error
 	search(qs []float32, nq, k int) (rows []uint32, dist []float32, count []uint32, err error)
 	searchSelected(qs []float32, nq, k int, selected []uint32) ([]uint32, []float32, []uint32, error)
@@ -140,6 +141,37 @@ func (x *Index) InsertBatch(vs map[string]vectortypes.F32) error {
 		x.rowOf[id], x.idOf[got[i]] = got[i], id
 	}
 	return nil
+}
+
+// UpdateBatch overwrites the vectors of existing ids in one device call (Collection.UpdateBatch, collection.go:469-529, deletes and
+// re-inserts every vector; here every id keeps its row).  Every id must exist and every vector must have the index's dimension,
+// else nothing is written.  Ids are taken in sorted order, as InsertBatch takes them.
+func (x *Index) UpdateBatch(vs map[string]vectortypes.F32) error {
+	x.mu.Lock()
+	defer x.mu.Unlock()
+	ids := make([]string, 0, len(vs))
+	for id := range vs {
+		ids = append(ids, id)
+	}
+	sort.Strings(ids)
+	rows := make([]uint32, 0, len(ids))
+	flat := make([]float32, 0, len(vs)*x.dim)
+	for _, id := range ids {
+		v := vs[id]
+		if len(v) != x.dim {
+			return fmt.Errorf("vector dimension mismatch: expected %d, got %d", x.dim, len(v))
+		}
+		row, ok := x.rowOf[id]
+		if !ok {
+			return fmt.Errorf("vector with ID %s not found", id)
+		}
+		rows = append(rows, row)
+		flat = append(flat, v...)
+	}
+	if len(ids) == 0 {
+		return nil
+	}
+	return x.dev.updateRows(rows, flat)
 }
 
 // Delete implements core.Index; an unknown id is not an error (exact.go:61-70).
@@ -389,6 +421,14 @@ func (d *oneGPU) add(flat []float32, n int) ([]uint32, error) {
 func (d *oneGPU) update(row uint32, v []float32) error {
 	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
 	if C.qv_index_update(d.h, C.uint32_t(row), f32p(v)) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
+func (d *oneGPU) updateRows(rows []uint32, flat []float32) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	if C.qv_index_update_rows(d.h, u32p(rows), C.uint32_t(len(rows)), f32p(flat)) != C.QV_OK {
 		return lastErr()
 	}
 	return nil

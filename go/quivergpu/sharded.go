@@ -63,6 +63,14 @@ func (d *node) update(row uint32, v []float32) error {
 	return nil
 }
 
+func (d *node) updateRows(rows []uint32, flat []float32) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	if C.qv_sharded_update_rows(d.h, u32p(rows), C.uint32_t(len(rows)), f32p(flat)) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
 func (d *node) remove(rows []uint32) error {
 	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
 	if C.qv_sharded_remove(d.h, u32p(rows), C.uint32_t(len(rows))) != C.QV_OK {

@@ -179,6 +179,30 @@ int qv_index_remove(qv_index* idx, const uint32_t* rows, uint32_t n);
  * path, pkg/core/collection.go:~400: delete + insert under one lock). */
 int qv_index_update(qv_index* idx, uint32_t row, const float* vec);
 
+/* Overwrite n listed rows in one call (Collection.UpdateBatch, pkg/core/collection.go:469-529; slot reuse in
+ * HybridIndex.InsertBatch).  The result is exactly what
+ *     for (i = 0; i < n; i++) qv_index_update(idx, rows[i], vecs + i * dim);
+ * leaves: every listed row is overwritten in place and marked live (a dead row is revived), a row listed more than
+ * once ends with its LAST vector, and every plane the index derives from its rows holds, bit for bit, what the loop
+ * would have left.  rows is HOST memory in both forms; vecs is host [n][dim], d_vecs device [n][dim].
+ * Checked before anything is written: a null index, rows or vectors (QV_ERR_INVALID_ARG; n == 0 returns QV_OK
+ * before the two lists are looked at); any rows[i] >= qv_index_rows -> QV_ERR_OUT_OF_RANGE, nothing changed.
+ * When a call fails with QV_ERR_DEVICE the contents of the listed rows are unspecified; their alive bits as the
+ * index reports them (qv_index_size, the checks of later calls) are what they were before the call.
+ * The device form is synchronous w.r.t. `stream`.  The host form stages the vectors through the index's own buffer
+ * in chunks of at most 256 MiB; entries whose row comes again later in the list are dropped before the list is cut,
+ * so no chunk writes a row another chunk writes.  Threading: as qv_index_add / qv_index_update — the caller keeps
+ * every other call on the index out while one of these runs. */
+int qv_index_update_rows(qv_index* idx, const uint32_t* rows, uint32_t n, const float* vecs);
+int qv_index_update_rows_device(qv_index* idx, const uint32_t* rows, uint32_t n, const float* d_vecs, void* stream);
+
+/* The rule behind both (pure host arithmetic, no device): the entries that survive (the last of each row), sorted by
+ * row — rows_out[m] ascending and distinct, src_out[i] = the position in the list of rows_out[i]'s vector — and the
+ * 64-row tiles they touch: tiles_out[T] ascending, tile_first_out[T + 1] = where each tile's entries start in
+ * rows_out (tile_first_out[T] = m).  Room for n, n, n + 1 and n entries; *n_unique = m, *n_tiles = T. */
+int qv_update_rows_plan(const uint32_t* rows, uint32_t n, uint32_t* rows_out, uint32_t* src_out, uint32_t* tile_first_out,
+                        uint32_t* tiles_out, uint32_t* n_unique, uint32_t* n_tiles);
+
 /* ---- queries -------------------------------------------------------------------- */
 
 /* Number of rows ever added (dead rows included) and number of live rows
@@ -718,7 +742,9 @@ int qv_scan_bound_interval_l2(uint32_t dim, float s, double qn, double rn, float
 #define QV_DEBUG_PLANE6 4     /* the 6-bit plane, raw: [tile][dim / 64][3][64 rows][16 bytes] (qv_scan_quantize_row6's pieces); an index that keeps none: an unknown code */
 #define QV_DEBUG_RRES6  5     /* |r - 4 rscale8 c6| rounded up, one float per row slot */
 #define QV_DEBUG_RSCALE8 6    /* the 8-bit plane's scale, one float per row slot (indexes that keep the 6-bit plane) */
-#define QV_DEBUG_ROWMAJ16 3   /* the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE), raw: rows x dim uint16, rows ever added; QV_ERR_UNSUPPORTED when an index created
+#define QV_DEBUG_PLANE8 7     /* the 8-bit plane, raw: [tile][dim / 16][64 rows][16 bytes]; an index that keeps none: an unknown code */
+#define QV_DEBUG_RRES8  8     /* |r - rscale8 r8| rounded up (NaN: a row the bound declines), one float per row slot */
+#define QV_DEBUG_ROWMAJ16 3  /* the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE), raw: rows x dim uint16, rows ever added; QV_ERR_UNSUPPORTED when an index created
                                  with the flag keeps none; an index created without the flag does not know the code (QV_ERR_INVALID_ARG, as before) */
 int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes);
 
@@ -966,6 +992,10 @@ int qv_sharded_remove(qv_sharded* s, const uint32_t* global_rows, uint32_t n);
 /* qv_index_update / qv_index_get_row / qv_index_get_rows on the shard that owns the row (Collection.Update,
  * pkg/core/collection.go:417-465; hybrid_index.go:537 reads idx.vectors[id]) */
 int qv_sharded_update(qv_sharded* s, uint32_t global_row, const float* vec);
+/* qv_index_update_rows over global rows: what the loop of qv_sharded_update leaves (a repeated row ends with its last
+ * vector).  EVERY global row is checked on every shard before anything is written (QV_ERR_OUT_OF_RANGE: nothing changed on
+ * any shard); then each shard gets its rows, with their vectors gathered, in one qv_index_update_rows. */
+int qv_sharded_update_rows(qv_sharded* s, const uint32_t* global_rows, uint32_t n, const float* vecs /* host [n][dim] */);
 int qv_sharded_get_row(qv_sharded* s, uint32_t global_row, float* vec_out);
 int qv_sharded_get_rows(qv_sharded* s, const uint32_t* global_rows, uint32_t n, float* out /* [n][dim] */);
 /* Same contract as qv_index_search (check order, clamping, padding, ordering, any k); rows_out holds global row ids. */

@@ -19,6 +19,7 @@ QV_FLAG_GRAPH_PLANE = 16       # a row-major cosine / dot index also keeps a bfl
 QV_GRAPH_REJECT_AUTO, QV_GRAPH_REJECT_ALWAYS, QV_GRAPH_REJECT_NEVER = 0, 1, 2
 QV_DEBUG_RNORM, QV_DEBUG_RRES, QV_DEBUG_PLANE, QV_DEBUG_ROWMAJ16 = 0, 1, 2, 3
 QV_DEBUG_PLANE6, QV_DEBUG_RRES6, QV_DEBUG_RSCALE8 = 4, 5, 6
+QV_DEBUG_PLANE8, QV_DEBUG_RRES8 = 7, 8
 QV_FLAG_NO_PLANE6 = 32         # no 6-bit plane beside the 8-bit one (dim * 0.75 + 4 bytes per row)
 QV_RULE_L2_PLANES = 0x101      # such an index, as the qv_scan_* rule functions take it where they take a metric
 QV_BOUND_SCAN_AUTO, QV_BOUND_SCAN_ALWAYS, QV_BOUND_SCAN_NEVER = 0, 1, 2
@@ -62,6 +63,9 @@ PROTOTYPES = {
     "qv_index_add_synthetic": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, _u32p]),
     "qv_index_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "qv_index_update": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "qv_index_update_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "qv_index_update_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "qv_update_rows_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u32p, _u32p]),
     "qv_index_rows": (C.c_uint32, [C.c_void_p]),
     "qv_index_size": (C.c_uint32, [C.c_void_p]),
     "qv_index_dim": (C.c_uint32, [C.c_void_p]),
@@ -172,6 +176,7 @@ PROTOTYPES = {
     "qv_sharded_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "qv_sharded_rows": (C.c_uint64, [C.c_void_p]),
     "qv_sharded_update": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "qv_sharded_update_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "qv_sharded_get_row": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "qv_sharded_get_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "qv_sharded_search_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),

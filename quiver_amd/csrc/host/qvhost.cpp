@@ -14,6 +14,9 @@
 extern "C" {
 int qv_graph_remove(qv_graph* g, const uint32_t* nodes, uint32_t n) __attribute__((weak));
 int qv_graph_export_lists(qv_graph* g, const uint32_t* nodes, const int* levels, uint32_t n, uint32_t* deg_out, uint32_t* links_out) __attribute__((weak));
+// So are the bulk overwrites: without them RowStore::update_many is the loop of update() it stands for.
+int qv_index_update_rows(qv_index* idx, const uint32_t* rows, uint32_t n, const float* vecs) __attribute__((weak));
+int qv_sharded_update_rows(qv_sharded* s, const uint32_t* global_rows, uint32_t n, const float* vecs) __attribute__((weak));
 }
 
 namespace quiver {
@@ -41,6 +44,7 @@ inline double rng_float64(uint64_t* s) { return (double)(sm64_next(s) >> 11) * (
 
 int RowStore::create(uint32_t dim, qv_metric metric, const Placement& w) {
     const uint64_t flags = w.bf16_rows ? QV_FLAG_BF16_ROWS : QV_FLAG_NONE;
+    dim_ = dim;
     if (!w.sharded()) return qv_index_create(&one_, dim, metric, w.first(), flags);
     return qv_sharded_create(&many_, dim, metric, w.devices.data(), (int)w.devices.size(), flags | (w.peer_copy ? QV_SHARDED_PEER_COPY : 0));
 }
@@ -57,6 +61,12 @@ int RowStore::add(const float* rows, uint32_t n, uint32_t* rows_out) {
     return rc;
 }
 int RowStore::update(uint32_t row, const float* v) { return many_ ? qv_sharded_update(many_, row, v) : qv_index_update(one_, row, v); }
+int RowStore::update_many(const uint32_t* rows, uint32_t n, const float* packed) {
+    if (many_ ? qv_sharded_update_rows != nullptr : qv_index_update_rows != nullptr)
+        return many_ ? qv_sharded_update_rows(many_, rows, n, packed) : qv_index_update_rows(one_, rows, n, packed);
+    for (uint32_t i = 0; i < n; i++) { const int rc = update(rows[i], packed + i * (size_t)dim_); if (rc != QV_OK) return rc; }
+    return QV_OK;
+}
 int RowStore::remove(const uint32_t* rows, uint32_t n) { return many_ ? qv_sharded_remove(many_, rows, n) : qv_index_remove(one_, rows, n); }
 int RowStore::search(const float* qs, uint32_t nq, uint32_t k, uint32_t* rows, float* dist, uint32_t* count) {
     if (many_) return qv_sharded_search(many_, qs, nq, k, rows, dist, count);     // batches take the matrix-core filter per shard by themselves
@@ -114,9 +124,24 @@ Error ExactIndex::InsertMany(const std::vector<std::string>& ids, const float* p
         for (auto& id : ids) if (row_of_.count(id) || seen[id]++) return failed(id, fmt("vector with ID %s already exists", id.c_str()));
     }
     size_t i = 0;
-    for (; i < ids.size() && (!free_rows_.empty() || dim_ == 0); i++) {    // reuse tombstoned rows first (and create the index on the first insert)
-        Error e = insertLocked(ids[i], packed + i * (size_t)len, len);
-        if (!e.empty()) { for (size_t j = 0; j < i; j++) (void)deleteLocked(ids[j]); return failed(ids[i], e); }
+    if (dim_ == 0) {                                                   // the first insert creates the index
+        Error e = insertLocked(ids[0], packed, len);
+        if (!e.empty()) return failed(ids[0], e);
+        i = 1;
+    }
+    if (i < ids.size() && !free_rows_.empty()) {                       // reuse tombstoned rows first: one device call for all of them
+        const uint32_t m = (uint32_t)std::min(free_rows_.size(), ids.size() - i);
+        std::vector<uint32_t> rows(m);
+        for (uint32_t j = 0; j < m; j++) rows[j] = free_rows_[free_rows_.size() - 1 - j];   // the slot Insert after Insert gives each id: popped from the back, in id order
+        if (h_.update_many(rows.data(), m, packed + i * (size_t)len) != QV_OK) {            // (the slots stay free: the maps are as they were)
+            Error e = qv_err();
+            (void)h_.remove(rows.data(), m);                           // (the per-row path may have revived some of them)
+            for (size_t j = 0; j < i; j++) (void)deleteLocked(ids[j]);
+            return failed(ids[i], e);
+        }
+        free_rows_.resize(free_rows_.size() - m);
+        for (uint32_t j = 0; j < m; j++) { row_of_[ids[i + j]] = rows[j]; id_of_[rows[j]] = ids[i + j]; }
+        i += m;
     }
     if (i < ids.size()) {                                              // the rest: one device copy
         const uint32_t n = (uint32_t)(ids.size() - i);

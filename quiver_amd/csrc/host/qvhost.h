@@ -64,12 +64,15 @@ public:
     void destroy();
     int add(const float* rows, uint32_t n, uint32_t* rows_out /* [n] */);
     int update(uint32_t row, const float* v);
+    // update() of rows[i] with packed[i], i = 0 .. n - 1, in ONE device call where libqv has one (qv_index_update_rows / qv_sharded_update_rows)
+    int update_many(const uint32_t* rows, uint32_t n, const float* packed /* [n][dim] */);
     int remove(const uint32_t* rows, uint32_t n);
     int search(const float* qs, uint32_t nq, uint32_t k, uint32_t* rows, float* dist, uint32_t* count);
     int search_negative(const float* q, const float* neg, uint32_t k_fetch, uint32_t* rows, float* dist, float* neg_dist, uint32_t* count);
     int distance_rows(const float* q, const uint32_t* rows, uint32_t n, float* out);
     uint64_t rows() const;
 private:
+    uint32_t dim_ = 0;
     qv_index* one_ = nullptr;
     qv_sharded* many_ = nullptr;
 };

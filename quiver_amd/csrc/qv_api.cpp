@@ -375,6 +375,140 @@ int qv_index_update(qv_index* idx, uint32_t row, const float* vec) {
     return QV_OK;
 }
 
+}  // extern "C"
+
+// ---- qv_index_update_rows: the host side of the scattered ingest --------------------------------------------------------------
+namespace {
+
+// keep[i] = 1 unless rows[i] occurs again later in the list (a row listed more than once ends with its LAST vector)
+std::vector<uint8_t> update_rows_keep(const uint32_t* rows, uint32_t n) {
+    std::vector<uint8_t> keep(n, 1);
+    std::vector<uint64_t> key(n);
+    for (uint32_t i = 0; i < n; i++) key[i] = (uint64_t)rows[i] << 32 | i;
+    std::sort(key.begin(), key.end());
+    for (uint32_t i = 0; i + 1 < n; i++) if ((key[i] >> 32) == (key[i + 1] >> 32)) keep[(uint32_t)key[i]] = 0;
+    return keep;
+}
+
+// The kept entries of rows[a, b), sorted by row, and the tiles they touch.  One array, in the order the device reads it:
+// rows_sorted[m] | src[m] (position in the list, counted from a) | tile_first[T + 1] | tiles[T].
+struct UpdatePlan { std::vector<uint32_t> words; uint32_t m = 0, T = 0; };
+UpdatePlan update_rows_plan(const uint32_t* rows, const uint8_t* keep, uint32_t a, uint32_t b) {
+    std::vector<uint64_t> key;
+    key.reserve(b - a);
+    for (uint32_t i = a; i < b; i++) if (keep[i]) key.push_back((uint64_t)rows[i] << 32 | (i - a));
+    std::sort(key.begin(), key.end());
+    UpdatePlan p;
+    p.m = (uint32_t)key.size();
+    for (uint32_t i = 0; i < p.m; i++) if (i == 0 || (key[i] >> 38) != (key[i - 1] >> 38)) p.T++;
+    p.words.resize(2 * (size_t)p.m + 2 * (size_t)p.T + 1);
+    uint32_t* rs = p.words.data(), * src = rs + p.m, * first = src + p.m, * tiles = first + p.T + 1;
+    uint32_t t = 0;
+    for (uint32_t i = 0; i < p.m; i++) {
+        rs[i] = (uint32_t)(key[i] >> 32); src[i] = (uint32_t)key[i];
+        if (i == 0 || (key[i] >> 38) != (key[i - 1] >> 38)) { first[t] = i; tiles[t] = rs[i] >> 6; t++; }
+    }
+    first[p.T] = p.m;
+    return p;
+}
+size_t update_plan_cap_bytes(uint32_t n) { return (4 * (size_t)n + 1) * sizeof(uint32_t); }    // (m <= n entries, T <= m tiles)
+
+// vectors per staged chunk of the host form: 256 MiB of them (QV_UPDATE_ROWS_CHUNK_BYTES, read once: for tests of the chunk seam)
+uint32_t update_rows_chunk(size_t row_bytes) {
+    static const size_t bytes = [] {
+        const char* e = getenv("QV_UPDATE_ROWS_CHUNK_BYTES");
+        const unsigned long long v = e ? strtoull(e, nullptr, 10) : 0;
+        return v ? (size_t)std::min<unsigned long long>(v, 256ull << 20) : (size_t)256 << 20;
+    }();
+    return (uint32_t)std::max<size_t>(1, bytes / row_bytes);
+}
+
+// rows[a, b) of a checked list -> the device, from d_vecs (the vector of rows[i] at d_vecs + (i - a) * dim); d_plan: device room for
+// update_plan_cap_bytes(b - a).  Returns when the stream has finished; the host mirror is the caller's to update.
+int update_rows_apply(qv_index* idx, const uint32_t* rows, const uint8_t* keep, uint32_t a, uint32_t b, const float* d_vecs, uint32_t* d_plan, hipStream_t s) {
+    const UpdatePlan p = update_rows_plan(rows, keep, a, b);
+    if (p.m == 0) return QV_OK;
+    hipError_t e = hipMemcpyAsync(d_plan, p.words.data(), p.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+    const uint32_t* d_rs = d_plan, * d_src = d_rs + p.m, * d_first = d_src + p.m, * d_tiles = d_first + p.T + 1;
+    if (e == hipSuccess) e = qv::launch_update_rows(idx->view(), d_vecs, d_rs, d_src, d_first, d_tiles, p.m, p.T, s);
+    const hipError_t e2 = hipStreamSynchronize(s);                     // (always: p.words is read by the copy until the stream has passed it)
+    if (e == hipSuccess) e = e2;
+    return e == hipSuccess ? QV_OK : fail(QV_ERR_DEVICE, "update_rows failed: %s", hipGetErrorString(e));
+}
+
+int update_rows_check(qv_index* idx, const uint32_t* rows, uint32_t n, const void* vecs) {
+    if (!rows) return fail(QV_ERR_INVALID_ARG, "rows is null");
+    if (!vecs) return fail(QV_ERR_INVALID_ARG, "vectors is null");
+    for (uint32_t i = 0; i < n; i++)
+        if (rows[i] >= idx->n_rows) return fail(QV_ERR_OUT_OF_RANGE, "row %u out of range (rows: %u)", rows[i], idx->n_rows);
+    return QV_OK;
+}
+
+void update_rows_mark(qv_index* idx, const uint32_t* rows, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t bit = 1ull << (rows[i] & 63);
+        if (!(idx->alive_host[rows[i] >> 6] & bit)) { idx->alive_host[rows[i] >> 6] |= bit; idx->n_live++; }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int qv_index_update_rows_device(qv_index* idx, const uint32_t* rows, uint32_t n, const float* d_vecs, void* stream) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (n == 0) return QV_OK;
+    int rc = update_rows_check(idx, rows, n, d_vecs);
+    if (rc != QV_OK) return rc;
+    idx->row_writes++;
+    HIPCHK(hipSetDevice(idx->device));
+    if ((rc = idx->mut_stage.ensure(update_plan_cap_bytes(n)))) return rc;
+    const std::vector<uint8_t> keep = update_rows_keep(rows, n);
+    rc = update_rows_apply(idx, rows, keep.data(), 0, n, d_vecs, static_cast<uint32_t*>(idx->mut_stage.p), static_cast<hipStream_t>(stream));
+    if (rc != QV_OK) return rc;
+    update_rows_mark(idx, rows, n);
+    return QV_OK;
+}
+
+int qv_index_update_rows(qv_index* idx, const uint32_t* rows, uint32_t n, const float* vecs) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (n == 0) return QV_OK;
+    int rc = update_rows_check(idx, rows, n, vecs);
+    if (rc != QV_OK) return rc;
+    idx->row_writes++;
+    HIPCHK(hipSetDevice(idx->device));
+    // duplicates are settled over the WHOLE list first: an entry whose row comes again later is never written, so every chunk is a
+    // scatter of distinct rows and no chunk writes a row another chunk writes
+    const std::vector<uint8_t> keep = update_rows_keep(rows, n);
+    const size_t row_bytes = (size_t)idx->dim * sizeof(float);
+    const uint32_t chunk_rows = std::min(n, update_rows_chunk(row_bytes));
+    const size_t vec_bytes = ((size_t)chunk_rows * row_bytes + 255) & ~(size_t)255;
+    if ((rc = idx->mut_stage.ensure(vec_bytes + update_plan_cap_bytes(chunk_rows)))) return rc;
+    float* d_stage = static_cast<float*>(idx->mut_stage.p);
+    uint32_t* d_plan = reinterpret_cast<uint32_t*>(static_cast<char*>(idx->mut_stage.p) + vec_bytes);
+    for (uint32_t done = 0; done < n; done += chunk_rows) {
+        const uint32_t m = std::min(chunk_rows, n - done);
+        const hipError_t e = hipMemcpy(d_stage, vecs + (size_t)done * idx->dim, (size_t)m * row_bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "hipMemcpy H2D failed: %s", hipGetErrorString(e));
+        if ((rc = update_rows_apply(idx, rows, keep.data(), done, done + m, d_stage, d_plan, nullptr)) != QV_OK) return rc;
+    }
+    if (idx->mut_stage.cap > ((size_t)64 << 20)) idx->mut_stage.release();     // do not keep a bulk buffer around
+    update_rows_mark(idx, rows, n);
+    return QV_OK;
+}
+
+int qv_update_rows_plan(const uint32_t* rows, uint32_t n, uint32_t* rows_out, uint32_t* src_out, uint32_t* tile_first_out, uint32_t* tiles_out,
+                        uint32_t* n_unique, uint32_t* n_tiles) {
+    if (!rows_out || !src_out || !tile_first_out || !tiles_out || !n_unique || !n_tiles || (n && !rows)) return fail(QV_ERR_INVALID_ARG, "a pointer is null");
+    const std::vector<uint8_t> keep = update_rows_keep(rows, n);
+    const UpdatePlan p = update_rows_plan(rows, keep.data(), 0, n);
+    const uint32_t* w = p.words.data();
+    memcpy(rows_out, w, p.m * sizeof(uint32_t)); memcpy(src_out, w + p.m, p.m * sizeof(uint32_t));
+    memcpy(tile_first_out, w + 2 * (size_t)p.m, (p.T + 1) * sizeof(uint32_t)); memcpy(tiles_out, w + 2 * (size_t)p.m + p.T + 1, p.T * sizeof(uint32_t));
+    *n_unique = p.m; *n_tiles = p.T;
+    return QV_OK;
+}
+
 int qv_index_get_row(qv_index* idx, uint32_t row, float* vec_out) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
     if (!vec_out) return fail(QV_ERR_INVALID_ARG, "vec_out is null");
@@ -2003,6 +2137,10 @@ int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {
         if (tiles && !idx->d_plane6) return fail(QV_ERR_UNSUPPORTED, "this index keeps no 6-bit plane");
         if (what == QV_DEBUG_PLANE6) { src = idx->d_plane6; need = tiles * idx->plane6_tile_bytes(); }
         else { src = what == QV_DEBUG_RRES6 ? idx->d_rres6 : idx->d_rscale8; need = tiles * 64 * sizeof(float); }
+    } else if ((what == QV_DEBUG_PLANE8 || what == QV_DEBUG_RRES8) && idx->wants_plane8()) {   // (an index that keeps no 8-bit plane: an unknown code, as for the 6-bit codes)
+        if (tiles && !idx->d_plane8) return fail(QV_ERR_UNSUPPORTED, "this index keeps no 8-bit plane");
+        if (what == QV_DEBUG_PLANE8) { src = idx->d_plane8; need = tiles * idx->plane8_tile_bytes(); }
+        else { src = idx->d_rres8; need = tiles * 64 * sizeof(float); }
     } else return fail(QV_ERR_INVALID_ARG, "what must be 0 (norms), 1 (residuals), 2 (the bfloat16 copy) or 3 (the row-order bfloat16 copy); got %d", what);
     if (bytes < need) return fail(QV_ERR_INVALID_ARG, "%zu bytes given, %zu needed", bytes, need);
     if (need == 0) return QV_OK;

@@ -148,6 +148,12 @@ FlatLayout flat_layout(void* base, FlatWs what, const ScanPlan& p, uint32_t nq, 
 // d_rows [n][dim] row-major on device -> tiles at rows [row0, row0+n); computes rnorm;
 // sets alive bits; also fills rowmaj if present.
 hipError_t launch_ingest(const IndexView& v, const float* d_rows, uint32_t row0, uint32_t n, hipStream_t s);
+// scattered ingest: d_vecs [.][dim] row-major on device; d_rows_sorted[n_unique] ascending and distinct, all below v.n_rows;
+// d_src[i] = the position in d_vecs of row d_rows_sorted[i]'s vector; d_tiles[n_tiles] = the touched tiles, ascending, and
+// d_tile_first[n_tiles + 1] = where each one's entries start in the sorted list.  Listed rows get what launch_ingest gives a row
+// (tiles, rowmaj, rnorm, alive bit); the derived planes of the touched tiles are refreshed by the kernels that serve launch_ingest.
+hipError_t launch_update_rows(const IndexView& v, const float* d_vecs, const uint32_t* d_rows_sorted, const uint32_t* d_src,
+                              const uint32_t* d_tile_first, const uint32_t* d_tiles, uint32_t n_unique, uint32_t n_tiles, hipStream_t s);
 // synthetic rows straight into tile layout (the synthetic-corpus generator of DESIGN.md)
 hipError_t launch_generate(const IndexView& v, uint64_t seed, uint64_t gen_row0, uint32_t row0, uint32_t n, hipStream_t s);
 // tombstone / revive

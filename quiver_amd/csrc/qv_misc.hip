@@ -145,6 +145,121 @@ k_ingest_tiled(IndexView v, const float* __restrict__ src, uint32_t row0, uint32
     }
 }
 
+// ---------------------------------------------------------------- scattered ingest --
+// Overwrite listed rows in place (qv_index_update_rows): the twins of the two kernels above, one workgroup per TOUCHED tile.  The host
+// hands over the list sorted and distinct — rows[m] ascending, src[m] = the position of each row's vector in vecs (the vectors are
+// never permuted), tile_first[b] .. tile_first[b + 1] = the entries of touched tile tiles[b].  A 64-entry LDS table maps the tile's
+// slot to its source vector (kNotListed: the slot keeps what it holds); everything a listed slot gets — the tile layout, the
+// row-major copy, rnorm in element order with ingest's chains and its -1 sentinel, the alive bit — is what ingest gives that row.
+constexpr uint32_t kNotListed = 0xFFFFFFFFu;
+
+// wave per touched tile; lane == slot (every dimension, every alignment of the source)
+__global__ void __launch_bounds__(64)
+k_update_rows(IndexView v, const float* __restrict__ src, const uint32_t* __restrict__ rows, const uint32_t* __restrict__ srcidx,
+              const uint32_t* __restrict__ tile_first, const uint32_t* __restrict__ tiles) {
+    __shared__ uint32_t slot_src[64];
+    const uint32_t t = tiles[blockIdx.x], e0 = tile_first[blockIdx.x], e1 = tile_first[blockIdx.x + 1];
+    const uint32_t lane = threadIdx.x;
+    slot_src[lane] = kNotListed;
+    __syncthreads();
+    if (e0 + lane < e1) slot_src[rows[e0 + lane] & 63u] = srcidx[e0 + lane];    // (distinct rows of one tile: at most 64, distinct slots)
+    __syncthreads();
+    const uint32_t row = t * 64 + lane;
+    const uint32_t from = slot_src[lane];
+    const bool mine = from != kNotListed;
+    if (mine) {
+        const float* s = src + (size_t)from * v.dim;
+        float4* dst = reinterpret_cast<float4*>(v.tiles) + (size_t)t * v.dim4 * 64 + lane;
+        float* rm = v.rowmaj ? v.rowmaj + (size_t)row * v.dim : nullptr;
+        double mb = 0.0; float nb = 0.0f;
+        for (uint32_t c = 0; c < v.dim4; c++) {
+            const uint32_t j = 4 * c;
+            float4 x;
+            x.x = j < v.dim ? s[j] : 0.f; x.y = j + 1 < v.dim ? s[j + 1] : 0.f;
+            x.z = j + 2 < v.dim ? s[j + 2] : 0.f; x.w = j + 3 < v.dim ? s[j + 3] : 0.f;
+            dst[(size_t)c * 64] = x;
+            if (rm) {                                                  // (no contiguous copy serves a scatter: the kernel writes the row-major copy)
+                if (j < v.dim) rm[j] = x.x;
+                if (j + 1 < v.dim) rm[j + 1] = x.y;
+                if (j + 2 < v.dim) rm[j + 2] = x.z;
+                if (j + 3 < v.dim) rm[j + 3] = x.w;
+            }
+            if (v.metric == QV_COSINE || v.metric == QV_DOT || v.metric == QV_L2 || v.metric == QV_L2SQ) {   // as k_ingest
+                mb = __builtin_fma((double)x.x, (double)x.x, mb); mb = __builtin_fma((double)x.y, (double)x.y, mb);
+                mb = __builtin_fma((double)x.z, (double)x.z, mb); mb = __builtin_fma((double)x.w, (double)x.w, mb);
+            } else if (v.metric == QV_COSINE_F32) {
+                float p; p = x.x * x.x; nb = nb + p; p = x.y * x.y; nb = nb + p; p = x.z * x.z; nb = nb + p; p = x.w * x.w; nb = nb + p;
+            }
+        }
+        if (v.metric == QV_COSINE || v.metric == QV_DOT || v.metric == QV_L2 || v.metric == QV_L2SQ) v.rnorm[row] = __builtin_sqrt(mb);
+        else if (v.metric == QV_COSINE_F32) v.rnorm[row] = nb == 0.0f ? -1.0 : (double)(float)__builtin_sqrt((double)nb);
+    }
+    const uint64_t m = __ballot(mine);
+    if (lane == 0 && m) atomicOr(reinterpret_cast<unsigned long long*>(&v.alive[t]), (unsigned long long)m);
+}
+
+// dim a multiple of 4, source 16-byte aligned: k_ingest_tiled's walk — 256-byte runs of a listed row in, 1 KiB runs of a chunk out
+__global__ void __launch_bounds__(256)
+k_update_rows_tiled(IndexView v, const float* __restrict__ src, const uint32_t* __restrict__ rows, const uint32_t* __restrict__ srcidx,
+                    const uint32_t* __restrict__ tile_first, const uint32_t* __restrict__ tiles) {
+    __shared__ float4 stage[64][kIngestCB + 1];
+    __shared__ uint32_t slot_src[64];
+    const uint32_t t = tiles[blockIdx.x], e0 = tile_first[blockIdx.x], e1 = tile_first[blockIdx.x + 1];
+    const uint32_t tid = threadIdx.x;
+    if (tid < 64) slot_src[tid] = kNotListed;
+    __syncthreads();
+    if (e0 + tid < e1) slot_src[rows[e0 + tid] & 63u] = srcidx[e0 + tid];
+    __syncthreads();
+    const float4* s4 = reinterpret_cast<const float4*>(src);
+    float4* tile = reinterpret_cast<float4*>(v.tiles) + (size_t)t * v.dim4 * 64;
+    float4* rm4 = v.rowmaj ? reinterpret_cast<float4*>(v.rowmaj) : nullptr;
+    const bool f64norm = v.metric == QV_COSINE || v.metric == QV_DOT || v.metric == QV_L2 || v.metric == QV_L2SQ;
+    const bool f32norm = v.metric == QV_COSINE_F32;
+    double mb = 0.0; float nb = 0.0f;
+    const uint32_t my_row = t * 64 + tid;                   // wave 0: the row whose constants this lane accumulates
+    const bool my_mine = tid < 64 && slot_src[tid & 63u] != kNotListed;
+    for (uint32_t cb = 0; cb < v.dim4; cb += kIngestCB) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {                       // 16 consecutive threads read 256 contiguous bytes of one listed row's vector
+            const uint32_t idx = tid + 256u * i, r = idx / kIngestCB, ch = idx % kIngestCB;
+            const uint32_t from = slot_src[r];
+            float4 x = {0.f, 0.f, 0.f, 0.f};
+            if (from != kNotListed && cb + ch < v.dim4) {
+                x = s4[(size_t)from * v.dim4 + cb + ch];
+                if (rm4) rm4[(size_t)(t * 64 + r) * v.dim4 + cb + ch] = x;
+            }
+            stage[r][ch] = x;
+        }
+        __syncthreads();
+        if (my_mine) {
+            const uint32_t nch = v.dim4 - cb < (uint32_t)kIngestCB ? v.dim4 - cb : (uint32_t)kIngestCB;
+            for (uint32_t ch = 0; ch < nch; ch++) {
+                const float4 x = stage[tid][ch];
+                if (f64norm) {
+                    mb = __builtin_fma((double)x.x, (double)x.x, mb); mb = __builtin_fma((double)x.y, (double)x.y, mb);
+                    mb = __builtin_fma((double)x.z, (double)x.z, mb); mb = __builtin_fma((double)x.w, (double)x.w, mb);
+                } else if (f32norm) {
+                    float p; p = x.x * x.x; nb = nb + p; p = x.y * x.y; nb = nb + p; p = x.z * x.z; nb = nb + p; p = x.w * x.w; nb = nb + p;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {                       // 64 consecutive threads write the 1 KiB of one chunk (listed slots only)
+            const uint32_t idx = tid + 256u * i, ch = idx / 64, r = idx % 64;
+            if (slot_src[r] != kNotListed && cb + ch < v.dim4) tile[(size_t)(cb + ch) * 64 + r] = stage[r][ch];
+        }
+        __syncthreads();
+    }
+    if (my_mine) {
+        if (f64norm) v.rnorm[my_row] = __builtin_sqrt(mb);
+        else if (f32norm) v.rnorm[my_row] = nb == 0.0f ? -1.0 : (double)(float)__builtin_sqrt((double)nb);
+    }
+    if (tid < 64) {
+        const uint64_t m = __ballot(my_mine);
+        if (tid == 0 && m) atomicOr(reinterpret_cast<unsigned long long*>(&v.alive[t]), (unsigned long long)m);
+    }
+}
+
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -238,12 +353,12 @@ hipError_t launch_distance_pairs(int metric, const float* d_a, const float* d_b,
 // nearest even — what the batched filter would compute on the fly.  One thread per (tile, 8-dim group, row); refreshed by every
 // launcher that writes rows, on the same stream, so the plane is never behind the tiles.
 __global__ void __launch_bounds__(256)
-k_bf16_plane(IndexView v, uint32_t t0, uint32_t n_tiles) {
+k_bf16_plane(IndexView v, uint32_t t0, uint32_t n_tiles, const uint32_t* __restrict__ list) {
     typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
     const uint32_t dim8 = (v.dim4 + 1) / 2;
     const uint64_t total = (uint64_t)n_tiles * dim8 * 64;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t r = (uint32_t)(i & 63), c8 = (uint32_t)((i >> 6) % dim8), t = t0 + (uint32_t)((i >> 6) / dim8);
+        const uint32_t r = (uint32_t)(i & 63), c8 = (uint32_t)((i >> 6) % dim8), ti = (uint32_t)((i >> 6) / dim8), t = list ? list[ti] : t0 + ti;
         const f4* src = reinterpret_cast<const f4*>(v.tiles) + (size_t)t * v.dim4 * 64 + r;
         const f4 a = src[(size_t)(2 * c8) * 64];
         f4 b = {0.f, 0.f, 0.f, 0.f};
@@ -261,8 +376,8 @@ k_bf16_plane(IndexView v, uint32_t t0, uint32_t n_tiles) {
 // float32 step than round-to-nearest) and the order of the additions is free.  Elements whose bfloat16 IMAGE is below 2^-126 in
 // magnitude count whole (an element just under 2^-126 that rounds up to it does not): the matrix core may flush such an operand.
 __global__ void __launch_bounds__(64)
-k_row_residual(IndexView v, uint32_t t0) {
-    const uint32_t t = t0 + blockIdx.x, lane = threadIdx.x;
+k_row_residual(IndexView v, uint32_t t0, const uint32_t* __restrict__ list) {
+    const uint32_t t = list ? list[blockIdx.x] : t0 + blockIdx.x, lane = threadIdx.x;
     const f4* src = reinterpret_cast<const f4*>(v.tiles) + (size_t)t * v.dim4 * 64 + lane;
     double s2 = 0.0;
     auto one = [&](float x) {
@@ -290,8 +405,8 @@ k_row_residual(IndexView v, uint32_t t0) {
 // float32 tiles.  One wave per tile, two walks of the tile: the row's largest magnitude (and whether it has one), then the bytes and
 // the residual |r - scale r8| FROM THE BYTES WRITTEN, in float64, rounded up.  dim is a multiple of 16 (the index keeps no plane otherwise).
 __global__ void __launch_bounds__(64)
-k_row_state8(IndexView v, uint32_t t0) {
-    const uint32_t t = t0 + blockIdx.x, lane = threadIdx.x, steps = v.dim >> 4;
+k_row_state8(IndexView v, uint32_t t0, const uint32_t* __restrict__ list) {
+    const uint32_t t = list ? list[blockIdx.x] : t0 + blockIdx.x, lane = threadIdx.x, steps = v.dim >> 4;
     const f4* src = reinterpret_cast<const f4*>(v.tiles) + (size_t)t * v.dim4 * 64 + lane;
     float maxabs = 0.f; bool bad = false; double n2 = 0.0;
     for (uint32_t c = 0; c < v.dim4; c++) {
@@ -335,8 +450,8 @@ k_row_state8(IndexView v, uint32_t t0) {
 // contiguous KiB of the wave; rres6 = |r - 4 rscale8 c6| from the codes written, in float64, rounded up; a row the 8-bit state declines
 // (rres8 is NaN) is declined here.  dim is a multiple of 64 (the index keeps no 6-bit plane otherwise).
 __global__ void __launch_bounds__(64)
-k_row_state6(IndexView v, uint32_t t0) {
-    const uint32_t t = t0 + blockIdx.x, lane = threadIdx.x, groups = v.dim >> 6;
+k_row_state6(IndexView v, uint32_t t0, const uint32_t* __restrict__ list) {
+    const uint32_t t = list ? list[blockIdx.x] : t0 + blockIdx.x, lane = threadIdx.x, groups = v.dim >> 6;
     const f4* src = reinterpret_cast<const f4*>(v.tiles) + (size_t)t * v.dim4 * 64 + lane;
     const float scale = v.rscale8[(size_t)t * 64 + lane];
     const float res8 = v.rres8[(size_t)t * 64 + lane];
@@ -377,44 +492,46 @@ k_row_state6(IndexView v, uint32_t t0) {
 // One thread per (row, chunk of four elements), the chunk index fastest: a row's 2 * dim bytes are written contiguously.  Whole tiles are
 // written (the storage is whole tiles; slots past the last row hold the zero rows the tiles hold).
 __global__ void __launch_bounds__(256)
-k_rowmaj16(IndexView v, uint32_t t0, uint32_t n_tiles) {
+k_rowmaj16(IndexView v, uint32_t t0, uint32_t n_tiles, const uint32_t* __restrict__ list) {
     typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
     const uint64_t total = (uint64_t)n_tiles * 64 * v.dim4;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t c = (uint32_t)(i % v.dim4);
         const uint64_t rr = i / v.dim4;
-        const uint32_t r = (uint32_t)(rr & 63), t = t0 + (uint32_t)(rr >> 6);
+        const uint32_t r = (uint32_t)(rr & 63), ti = (uint32_t)(rr >> 6), t = list ? list[ti] : t0 + ti;
         const f4 a = reinterpret_cast<const f4*>(v.tiles)[((size_t)t * v.dim4 + c) * 64 + r];
         const bf2 p0 = {(__bf16)a.x, (__bf16)a.y}, p1 = {(__bf16)a.z, (__bf16)a.w};
         uint2 o; o.x = __builtin_bit_cast(uint32_t, p0); o.y = __builtin_bit_cast(uint32_t, p1);
         reinterpret_cast<uint2*>(v.rowmaj16 + ((size_t)t * 64 + r) * v.dim)[c] = o;      // (dim is a multiple of 64 here: dim == 4 * dim4)
     }
 }
-static hipError_t refresh_bf16(const IndexView& v, uint32_t t0, uint32_t t1, hipStream_t s) {
+// The derived planes of n_tiles tiles, behind every write of rows and on its stream: the range [t0, t0 + n_tiles) when list is null, the
+// tiles list[0 .. n_tiles) (device memory, distinct) otherwise.  One body per plane either way: a tile is derived the same whoever asks.
+static hipError_t refresh_bf16(const IndexView& v, uint32_t t0, uint32_t n_tiles, const uint32_t* list, hipStream_t s) {
     if (v.rowmaj16) {                                                  // (never behind the rows either)
-        const uint64_t total = (uint64_t)(t1 - t0 + 1) * 64 * v.dim4;
-        hipLaunchKernelGGL(k_rowmaj16, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, s, v, t0, t1 - t0 + 1);
+        const uint64_t total = (uint64_t)n_tiles * 64 * v.dim4;
+        hipLaunchKernelGGL(k_rowmaj16, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, s, v, t0, n_tiles, list);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     if (v.rres && (v.metric == QV_COSINE || v.metric == QV_DOT || v.metric == QV_L2 || v.metric == QV_L2SQ)) {
-        hipLaunchKernelGGL(k_row_residual, dim3(t1 - t0 + 1), dim3(64), 0, s, v, t0);
+        hipLaunchKernelGGL(k_row_residual, dim3(n_tiles), dim3(64), 0, s, v, t0, list);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     if (v.plane8) {                                                    // (the 8-bit plane and its row state: never behind the tiles either)
-        hipLaunchKernelGGL(k_row_state8, dim3(t1 - t0 + 1), dim3(64), 0, s, v, t0);
+        hipLaunchKernelGGL(k_row_state8, dim3(n_tiles), dim3(64), 0, s, v, t0, list);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         if (v.plane6) {                                                // (behind it: the scale is the 8-bit plane's)
-            hipLaunchKernelGGL(k_row_state6, dim3(t1 - t0 + 1), dim3(64), 0, s, v, t0);
+            hipLaunchKernelGGL(k_row_state6, dim3(n_tiles), dim3(64), 0, s, v, t0, list);
             e = hipGetLastError();
             if (e != hipSuccess) return e;
         }
     }
     if (!v.plane) return hipSuccess;
-    const uint64_t total = (uint64_t)(t1 - t0 + 1) * ((v.dim4 + 1) / 2) * 64;
-    hipLaunchKernelGGL(k_bf16_plane, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, s, v, t0, t1 - t0 + 1);
+    const uint64_t total = (uint64_t)n_tiles * ((v.dim4 + 1) / 2) * 64;
+    hipLaunchKernelGGL(k_bf16_plane, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, s, v, t0, n_tiles, list);
     return hipGetLastError();
 }
 
@@ -425,13 +542,25 @@ hipError_t launch_ingest(const IndexView& v, const float* d_rows, uint32_t row0,
     if ((v.dim & 3) == 0 && tiled == 1 && (reinterpret_cast<uintptr_t>(d_rows) & 15) == 0) {
         hipLaunchKernelGGL(k_ingest_tiled, dim3(t1 - t0 + 1), dim3(256), 0, s, v, d_rows, row0, n, t0);
         hipError_t e0 = hipGetLastError();
-        return e0 != hipSuccess ? e0 : refresh_bf16(v, t0, t1, s);
+        return e0 != hipSuccess ? e0 : refresh_bf16(v, t0, t1 - t0 + 1, nullptr, s);
     }
     hipLaunchKernelGGL(k_ingest, dim3(t1 - t0 + 1), dim3(64), 0, s, v, d_rows, row0, n, t0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (v.rowmaj) e = hipMemcpyAsync(v.rowmaj + (size_t)row0 * v.dim, d_rows, (size_t)n * v.dim * sizeof(float), hipMemcpyDeviceToDevice, s);
-    return e != hipSuccess ? e : refresh_bf16(v, t0, t1, s);
+    return e != hipSuccess ? e : refresh_bf16(v, t0, t1 - t0 + 1, nullptr, s);
+}
+
+hipError_t launch_update_rows(const IndexView& v, const float* d_vecs, const uint32_t* d_rows_sorted, const uint32_t* d_src,
+                              const uint32_t* d_tile_first, const uint32_t* d_tiles, uint32_t n_unique, uint32_t n_tiles, hipStream_t s) {
+    if (n_unique == 0 || n_tiles == 0) return hipSuccess;
+    static const int tiled = dev_env_int("QV_INGEST_TILED", 1);
+    if ((v.dim & 3) == 0 && tiled == 1 && (reinterpret_cast<uintptr_t>(d_vecs) & 15) == 0)
+        hipLaunchKernelGGL(k_update_rows_tiled, dim3(n_tiles), dim3(256), 0, s, v, d_vecs, d_rows_sorted, d_src, d_tile_first, d_tiles);
+    else
+        hipLaunchKernelGGL(k_update_rows, dim3(n_tiles), dim3(64), 0, s, v, d_vecs, d_rows_sorted, d_src, d_tile_first, d_tiles);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : refresh_bf16(v, 0, n_tiles, d_tiles, s);
 }
 
 hipError_t launch_generate(const IndexView& v, uint64_t seed, uint64_t gen_row0, uint32_t row0, uint32_t n, hipStream_t s) {
@@ -439,7 +568,7 @@ hipError_t launch_generate(const IndexView& v, uint64_t seed, uint64_t gen_row0,
     const uint32_t t0 = row0 / 64, t1 = (row0 + n - 1) / 64;
     hipLaunchKernelGGL(k_generate, dim3(t1 - t0 + 1), dim3(64), 0, s, v, seed, gen_row0, row0, n, t0);
     hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : refresh_bf16(v, t0, t1, s);
+    return e != hipSuccess ? e : refresh_bf16(v, t0, t1 - t0 + 1, nullptr, s);
 }
 
 hipError_t launch_set_alive(const IndexView& v, const uint32_t* d_rows, uint32_t n, int alive, hipStream_t s) {

@@ -743,6 +743,27 @@ int qv_sharded_update(qv_sharded* s, uint32_t global_row, const float* vec) {
     return qv_index_update(s->sh[g].idx, local, vec);
 }
 
+int qv_sharded_update_rows(qv_sharded* s, const uint32_t* global_rows, uint32_t n, const float* vecs) {
+    if (!s) return fail(QV_ERR_INVALID_ARG, "handle is null");
+    if (n == 0) return QV_OK;
+    if (!global_rows) return fail(QV_ERR_INVALID_ARG, "rows is null");
+    if (!vecs) return fail(QV_ERR_INVALID_ARG, "vectors is null");
+    std::unique_lock<std::shared_mutex> l(s->mu);
+    reap_retired(s);
+    std::vector<std::vector<uint32_t>> per;
+    std::vector<std::pair<uint32_t, uint32_t>> where;
+    int rc = split_rows(s, global_rows, n, &per, &where);              // every row of every shard first: nothing is written unless all pass
+    if (rc != QV_OK) return rc;
+    for (size_t g = 0; g < per.size(); g++) {
+        if (per[g].empty()) continue;
+        std::vector<float> mine(per[g].size() * (size_t)s->dim);        // this shard's vectors, in list order (the last of a repeated row stays last)
+        for (uint32_t i = 0; i < n; i++)
+            if (where[i].first == g) memcpy(mine.data() + (size_t)where[i].second * s->dim, vecs + (size_t)i * s->dim, (size_t)s->dim * sizeof(float));
+        if ((rc = qv_index_update_rows(s->sh[g].idx, per[g].data(), (uint32_t)per[g].size(), mine.data())) != QV_OK) return rc;
+    }
+    return QV_OK;
+}
+
 int qv_sharded_get_rows(qv_sharded* s, const uint32_t* global_rows, uint32_t n, float* out) {
     if (!s) return fail(QV_ERR_INVALID_ARG, "handle is null");
     if (n == 0) return QV_OK;

@@ -168,6 +168,27 @@ class DeviceIndex:
             raise ValueError(f"vector dimension mismatch: expected {self.dim}, got {vec.size}")
         check(lib().qv_index_update(self._h, row, vec.ctypes.data))
 
+    def _rows_vecs(self, rows, vecs):
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).ravel()
+        vecs = _f32c(vecs)
+        if vecs.ndim == 1:
+            vecs = vecs[None, :]
+        if vecs.ndim != 2 or vecs.shape[1] != self.dim:
+            raise ValueError(f"vector dimension mismatch: expected {self.dim}, got {vecs.shape[-1]}")
+        if vecs.shape[0] != rows.size:
+            raise ValueError(f"{rows.size} rows listed, {vecs.shape[0]} vectors given")
+        return rows, vecs
+
+    def update_rows(self, rows, vecs):
+        """overwrite the listed rows in one call (qv_index_update_rows): what `for r, v in zip(rows, vecs): update(r, v)` leaves"""
+        rows, vecs = self._rows_vecs(rows, vecs)
+        check(lib().qv_index_update_rows(self._h, rows.ctypes.data, rows.size, vecs.ctypes.data))
+
+    def update_rows_device(self, rows, d_ptr: int, stream: int = 0):
+        """the same, the vectors [len(rows), dim] float32 already on the device; the row list stays on the host; synchronous w.r.t. `stream`"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).ravel()
+        check(lib().qv_index_update_rows_device(self._h, rows.ctypes.data, rows.size, d_ptr, stream or None))
+
     # ---- queries ----
     def rows(self) -> int:
         return int(lib().qv_index_rows(self._h))
@@ -452,7 +473,7 @@ class DeviceIndex:
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
     DEBUG_READ = {"rnorm": (0, np.float64), "rres": (1, np.float32), "plane": (2, np.uint16), "rowmaj16": (3, np.uint16),
-                  "plane6": (4, np.uint8), "rres6": (5, np.float32), "rscale8": (6, np.float32)}
+                  "plane6": (4, np.uint8), "rres6": (5, np.float32), "rscale8": (6, np.float32), "plane8": (7, np.uint8), "rres8": (8, np.float32)}
 
     def debug_read(self, what: str) -> np.ndarray:
         """FOR TESTS (qv_index_debug_read): one of the arrays ingest derives per row, as the device holds it — "rnorm" (float64 per row
@@ -465,7 +486,7 @@ class DeviceIndex:
             check(lib().qv_index_debug_read(self._h, code, out.ctypes.data, out.nbytes))
             return out
         tiles = (self.rows() + 63) // 64
-        per_tile = 2 * 64 * 8 * ((self.dim + 15) // 16) if what == "plane" else self.dim * 48 if what == "plane6" else 64     # uint16 words of a tile of the copy: qv_index::bf16_tile_bytes() / 2 (qv_api_internal.h)
+        per_tile = 2 * 64 * 8 * ((self.dim + 15) // 16) if what == "plane" else self.dim * 48 if what == "plane6" else self.dim * 64 if what == "plane8" else 64     # uint16 words of a tile of the copy: qv_index::bf16_tile_bytes() / 2 (qv_api_internal.h)
         out = np.empty(tiles * per_tile, dtype=dtype)
         check(lib().qv_index_debug_read(self._h, code, out.ctypes.data, out.nbytes))
         return out
@@ -903,6 +924,11 @@ class ShardedIndex:
         if vec.size != self.dim:
             raise ValueError(f"vector dimension mismatch: expected {self.dim}, got {vec.size}")
         check(lib().qv_sharded_update(self._h, int(global_row), vec.ctypes.data))
+
+    def update_rows(self, global_rows, vecs):
+        """overwrite the listed global rows in one call (qv_sharded_update_rows): what the loop of update() leaves"""
+        rows, vecs = DeviceIndex._rows_vecs(self, global_rows, vecs)
+        check(lib().qv_sharded_update_rows(self._h, rows.ctypes.data, rows.size, vecs.ctypes.data))
 
     def get_row(self, global_row: int) -> np.ndarray:
         out = np.empty(self.dim, dtype=np.float32)
