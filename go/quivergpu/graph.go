@@ -33,6 +33,9 @@ type GraphConfig struct {
 	// GraphPlane: the vector storage also keeps a bfloat16 copy of the rows in row order (FlagGraphPlane: +2 * dim bytes per row),
 	// on which batch searches can reject neighbours (SetRejectPlane).  Results do not depend on it.
 	GraphPlane bool
+	// GraphPlane8: the vector storage also keeps an int8 image of the rows in row order with a record per row (FlagGraphPlane8:
+	// +dim + 16 bytes per row), on which rejecting batch searches can start (SetRejectImage).  Results do not depend on it.
+	GraphPlane8 bool
 }
 
 // NewGraph creates the vector storage (a qv_index with a row-major copy for the per-hop gathers) and an empty graph over it.
@@ -42,6 +45,9 @@ func NewGraph(dim int, m Metric, device int, capacity int, cfg GraphConfig) (*Gr
 	flags := uint64(C.QV_FLAG_ROWMAJOR)
 	if cfg.GraphPlane {
 		flags |= FlagGraphPlane
+	}
+	if cfg.GraphPlane8 {
+		flags |= FlagGraphPlane8
 	}
 	if C.qv_index_create(&idx, C.uint32_t(dim), C.qv_metric(m), C.int(device), C.uint64_t(flags)) != C.QV_OK {
 		return nil, lastErr()
@@ -221,6 +227,37 @@ func (h *Graph) RejectStats() (RejectStats, error) {
 	defer h.mu.RUnlock()
 	out := make([]uint64, 4)
 	if C.qv_graph_reject_stats(h.g, (*C.uint64_t)(unsafe.Pointer(&out[0]))) != C.QV_OK {
+		return RejectStats{}, lastErr()
+	}
+	return RejectStats{Evals: out[0], Rejected: out[1], Queries: out[2], Plane: out[3] != 0}, nil
+}
+
+// Modes of SetRejectImage (QV_GRAPH_IMAGE_*).
+const (
+	ImageAuto = int(C.QV_GRAPH_IMAGE_AUTO) // the 8-bit image only where it is held and was measured faster (qv.h: cosine, dim 768, 1M to below 2M nodes, 8192 queries or more, list sizes 64 to 256); else the bfloat16 copy
+	Image8Bit = int(C.QV_GRAPH_IMAGE_8BIT) // the 8-bit image wherever it is held, else the bfloat16 copy
+	ImageBF16 = int(C.QV_GRAPH_IMAGE_BF16) // never the 8-bit image
+)
+
+// SetRejectImage chooses which image a rejecting batch search starts on: the storage's row-order 8-bit image (GraphConfig.GraphPlane8)
+// or its bfloat16 copy (qv_graph_set_reject_image).  SetRejectPlane keeps deciding whether a search rejects.  Exclusive, like Insert.
+func (h *Graph) SetRejectImage(mode int) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	h.mu.Lock()
+	defer h.mu.Unlock()
+	if C.qv_graph_set_reject_image(h.g, C.int(mode)) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
+// Reject8Stats is qv_graph_reject8_stats: RejectStats for hops that rejected on the 8-bit image.  Waits for the device.
+func (h *Graph) Reject8Stats() (RejectStats, error) {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	h.mu.RLock()
+	defer h.mu.RUnlock()
+	out := make([]uint64, 4)
+	if C.qv_graph_reject8_stats(h.g, (*C.uint64_t)(unsafe.Pointer(&out[0]))) != C.QV_OK {
 		return RejectStats{}, lastErr()
 	}
 	return RejectStats{Evals: out[0], Rejected: out[1], Queries: out[2], Plane: out[3] != 0}, nil

@@ -46,6 +46,11 @@ const FlagNoPlane6 uint64 = C.QV_FLAG_NO_PLANE6
 // (Graph.SetRejectPlane).  Elsewhere it does nothing.
 const FlagGraphPlane uint64 = C.QV_FLAG_GRAPH_PLANE
 
+// FlagGraphPlane8 (QV_FLAG_GRAPH_PLANE8): a row-major cosine or dot index whose dimension is a multiple of 128 up to 4096 also keeps
+// an int8 image of the rows in row order and a 16-byte record per row (+dim + 16 bytes per row), on which a graph's batch searches
+// can reject neighbours (Graph.SetRejectImage).  Independent of FlagGraphPlane.  Elsewhere it does nothing.
+const FlagGraphPlane8 uint64 = C.QV_FLAG_GRAPH_PLANE8
+
 // Index implements core.Index and core.BatchIndex (pkg/core/collection.go:78-96) on libqv.  String ids and metadata
 // never leave Go; the device sees row numbers, the analogue of hnsw.Node.VectorIndex (pkg/hnsw/hnsw.go:94).
 //

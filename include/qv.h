@@ -136,6 +136,15 @@ typedef enum qv_status {
                                     (qv_graph_set_reject_plane).  Opt-in: without the flag nothing is kept and every traversal launches the
                                     kernels it always launched.  Without QV_FLAG_ROWMAJOR, on another metric or another dimension the flag
                                     does nothing and creation still succeeds; a copy that cannot be allocated is given up alone */
+#define QV_FLAG_GRAPH_PLANE8 64ull /* a QV_FLAG_ROWMAJOR index of metric QV_COSINE or QV_DOT whose dimension is a multiple of 128 up to 4096
+                                    also keeps `rowmaj8`: the rows' int8 image in ROW order, [rows][dim] — the bytes qv_scan_quantize_row8 gives,
+                                    the tile-layout 8-bit plane's where the index holds one — and one 16-byte record per row beside it,
+                                    {double rnorm; float rscale8; float rres8} (+dim + 16 bytes per row), written by every call that writes
+                                    rows.  A graph traversal can then reject neighbours on it (qv_graph_set_reject_image).  Independent of
+                                    QV_FLAG_GRAPH_PLANE (an index may hold either image or both) and of QV_FLAG_NO_SCAN_PLANE (the image
+                                    derives its own scale and residual).  Opt-in: without the flag nothing is kept and nothing is launched
+                                    differently.  Without QV_FLAG_ROWMAJOR, on another metric or another dimension the flag does nothing
+                                    and creation still succeeds; an image that cannot be allocated is given up alone */
 /* FOR THE qv_scan_* RULE FUNCTIONS ONLY: "a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE", where they take a metric.  They accept it
  * wherever they accept QV_COSINE and QV_DOT (plain QV_L2 keeps answering 0); qv_index_metric still answers QV_L2, and qv_index_create
  * rejects the code. */
@@ -746,6 +755,9 @@ int qv_scan_bound_interval_l2(uint32_t dim, float s, double qn, double rn, float
 #define QV_DEBUG_RRES8  8     /* |r - rscale8 r8| rounded up (NaN: a row the bound declines), one float per row slot */
 #define QV_DEBUG_ROWMAJ16 3  /* the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE), raw: rows x dim uint16, rows ever added; QV_ERR_UNSUPPORTED when an index created
                                  with the flag keeps none; an index created without the flag does not know the code (QV_ERR_INVALID_ARG, as before) */
+#define QV_DEBUG_ROWMAJ8 9   /* the row-order 8-bit image (QV_FLAG_GRAPH_PLANE8), raw: rows x dim int8, rows ever added; QV_ERR_UNSUPPORTED when an index created
+                                with the flag keeps none; an index created without the flag: an unknown code, as always */
+#define QV_DEBUG_ROWMETA8 10 /* its records, rows ever added x {double rnorm; float rscale8; float rres8} (16 bytes); the same answers */
 int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes);
 
 /* Device-pointer form of the batched path: enqueues on `stream`, no sync.  d_redo_flags_out[nq]
@@ -942,6 +954,40 @@ int qv_graph_reject_stats(qv_graph* g, uint64_t* out);   /* out: 4 values */
 int qv_graph_reject_applies(int metric, uint32_t dim, uint32_t n_nodes, uint32_t nq, uint32_t ef_search, int cus, int mode, int has_plane,
                             int has_tombstones, uint32_t max_m0);
 
+/* ---- rejecting neighbours on the row-order 8-bit image (QV_FLAG_GRAPH_PLANE8) ----
+ * On an index that keeps `rowmaj8`, a rejecting hop can read 128 elements of each new neighbour per 128-byte piece instead of 64: dim bytes and
+ * one 16-byte record per evaluation, integer dot products against the query's two int8 terms (quantised once per query, resident in LDS beside
+ * its float32 words), the certified interval of the 8-bit bound scan (qv_scan_bound_interval8), and survivors straight to their float32 rows.
+ * Rows, float32 bits, counts and evals_out are those of the unchanged traversal.  qv_graph_set_reject_plane keeps deciding WHETHER a call
+ * rejects; qv_graph_set_reject_image says which image such a call starts on:
+ *   QV_GRAPH_IMAGE_AUTO  the 8-bit image only on indexes that hold it AND in the cells it was measured faster in than the bfloat16 copy and than
+ *                        "never" (profiles/LAB_r23_graph_reject8.md): QV_COSINE, dim == 768, a graph of 1 000 000 to below 2 000 000 nodes, 8192
+ *                        queries or more per call, list size max(ef_search, k) from 64 to 256 — all twelve measured cells: +7 ... +18 % over
+ *                        bfloat16-first, +26 ... +53 % over "never".  In every other cell the bfloat16 copy, or the unchanged kernels where
+ *                        no image is held.  Not measured and therefore not taken: other dimensions (128 among them), 10M nodes,
+ *                        QV_DOT; MaxLevel 16 is not measured and not seen by the rule.  Widths at which the resident terms would cost a
+ *                        traversal per CU (every width from 896 dimensions up) are declined
+ *   QV_GRAPH_IMAGE_8BIT  the 8-bit image wherever it is held and the kernel's conditions hold, else the bfloat16 copy if held
+ *   QV_GRAPH_IMAGE_BF16  never the 8-bit image
+ * An index created without QV_FLAG_GRAPH_PLANE8 behaves exactly as before under every mode.  The environment variable QV_GRAPH_IMAGE
+ * (1 the 8-bit image, 2 the bfloat16 copy; read once per process) sets the default of every graph.  Same exclusion as qv_graph_set_reject_plane.
+ * Unchanged, as for the bfloat16 copy: the latency form (and with it coalesced concurrent callers), the exact-heap kernel, construction
+ * searches, upper levels, graphs with tombstones, more than 32 level-0 links, QV_L2 and the float32-chain metrics; there is no 6-bit graph
+ * image, the float32 row-major copy stays, and dimensions that are not whole 128-element slabs keep no image. */
+#define QV_GRAPH_IMAGE_AUTO 0
+#define QV_GRAPH_IMAGE_8BIT 1
+#define QV_GRAPH_IMAGE_BF16 2
+int qv_graph_set_reject_image(qv_graph* g, int mode);
+/* out[0] = evaluations made in hops that rejected on the 8-bit image, out[1] = the ones of those that were rejected, out[2] = queries that
+ * finished level 0 in that form, out[3] = 1 when the index holds the image.  qv_graph_reject_stats keeps counting bfloat16-copy hops only.
+ * Waits for the device. */
+int qv_graph_reject8_stats(qv_graph* g, uint64_t* out);  /* out: 4 values */
+/* The dispatch's own rule: the arguments of qv_graph_reject_applies, then whether the index holds the 8-bit image and the image mode.
+ * 0 = no rejecting form, 1 = the bfloat16 copy, 2 = the 8-bit image; < 0 = an argument error.  Never non-zero where qv_graph_reject_applies
+ * answers 0 for an index holding that image. */
+int qv_graph_reject_image_applies(int metric, uint32_t dim, uint32_t n_nodes, uint32_t nq, uint32_t ef_search, int cus, int mode, int has_plane,
+                                  int has_tombstones, uint32_t max_m0, int has_image8, int image_mode);
+
 /* ---- one corpus over the GPUs of a node --------------------------------
  * No reference counterpart (the reference is one process on CPU cores): this is what lets the Go host reach all the
  * GPUs of a node through ONE handle — what core.Index (pkg/core/collection.go:78-96) is for one GPU (qv_index),
@@ -960,7 +1006,7 @@ int qv_graph_reject_applies(int metric, uint32_t dim, uint32_t n_nodes, uint32_t
  *                    the k best of the gathered lists, the whole batch at once.  Beyond (a filtered Collection.Search asks
  *                    for k = Index.Size(), collection.go:679-682): every shard ranks its rows (radix sort), the sorted runs
  *                    are exchanged and one stable radix sort on the first device merges them
- *   flags            QV_FLAG_ROWMAJOR, QV_FLAG_BF16_ROWS, QV_FLAG_NO_SCAN_PLANE, QV_FLAG_L2_SCAN_PLANE and QV_FLAG_GRAPH_PLANE pass through to the shards; QV_SHARDED_PEER_COPY replaces the collective with
+ *   flags            QV_FLAG_ROWMAJOR, QV_FLAG_BF16_ROWS, QV_FLAG_NO_SCAN_PLANE, QV_FLAG_L2_SCAN_PLANE, QV_FLAG_GRAPH_PLANE and QV_FLAG_GRAPH_PLANE8 pass through to the shards; QV_SHARDED_PEER_COPY replaces the collective with
  *                    point-to-point copies into the first device (and lets several shards share one device, which
  *                    RCCL does not allow: how the tests exercise 3 and 8 shards on a 1-GPU box)
  * Threading: as qv_index — searches, qv_sharded_distance_rows and qv_sharded_get_row(s) may run concurrently from many

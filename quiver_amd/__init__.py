@@ -8,7 +8,7 @@ mirrors of the reference's host interfaces for this path (``hybrid``, ``hnsw``,
 the Go packages they stand in for.
 """
 from ._lib import QvError, lib, load_library, METRICS, metric_id  # noqa: F401
-from .device_index import DeviceIndex, RowSet, Column, DeviceGraph, GraphReplicas, ShardedIndex, graph_reject_applies  # noqa: F401
+from .device_index import DeviceIndex, RowSet, Column, DeviceGraph, GraphReplicas, ShardedIndex, graph_reject_applies, graph_reject_image_applies  # noqa: F401
 
 
 def scan_bound8_applies_mq(metric, dim: int, rows: int, nq: int, k: int, mode="auto", plane_mode_mq="auto", has_plane8: bool = True) -> bool:
@@ -61,4 +61,4 @@ def batched_filter_route(metric, dim: int, rows: int, nq: int, k: int, filter="a
 
 
 __all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq", "scan_bound8_applies_filtered_mq",
-           "batched_applies_filtered", "batched_filter_route", "graph_reject_applies"]
+           "batched_applies_filtered", "batched_filter_route", "graph_reject_applies", "graph_reject_image_applies"]

@@ -24,7 +24,7 @@ _SIGS = {
     "qvh_exact_search": (_i, [_vp, _vp, _u32, _i, _vp]), "qvh_exact_size": (_i, [_vp]), "qvh_exact_device_rows": (_u32, [_vp]),
     "qvh_hnsw_insert_batch": (_i, [_vp, C.POINTER(_cp), _vp, _u32, _u32, _u32, _u32]), "qvh_hnsw_built_on_device": (_i, [_vp]),
     "qvh_hybrid_exact_device_rows": (_u32, [_vp]), "qvh_hybrid_hnsw_built_on_device": (_i, [_vp]),
-    "qvh_hnsw_new": (_vp, [_i, _i, _i, _i, _i, _i, _i, C.c_uint64]), "qvh_hnsw_free": (None, [_vp]), "qvh_hnsw_set_graph_plane": (None, [_vp, _i]),
+    "qvh_hnsw_new": (_vp, [_i, _i, _i, _i, _i, _i, _i, C.c_uint64]), "qvh_hnsw_free": (None, [_vp]), "qvh_hnsw_set_graph_plane": (None, [_vp, _i]), "qvh_hnsw_set_graph_plane8": (None, [_vp, _i]),
     "qvh_hnsw_insert": (_i, [_vp, _cp, _vp, _u32]), "qvh_hnsw_delete": (_i, [_vp, _cp]),
     "qvh_hnsw_search": (_i, [_vp, _vp, _u32, _i, _vp, _vp]),
     "qvh_hnsw_search_batch": (_i, [_vp, _vp, _u32, _u32, _i, _vp, _vp, _vp]), "qvh_hnsw_search_batch_raw": (_i, [_vp, _vp, _u32, _u32, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),

@@ -17,6 +17,9 @@ QV_FLAG_NO_SCAN_PLANE = 4
 QV_FLAG_L2_SCAN_PLANE = 8      # a QV_L2 index keeps the bfloat16 copy and the 8-bit plane: its searches can take the bound scan
 QV_FLAG_GRAPH_PLANE = 16       # a row-major cosine / dot index also keeps a bfloat16 copy in row order: graph traversals can reject neighbours on it
 QV_GRAPH_REJECT_AUTO, QV_GRAPH_REJECT_ALWAYS, QV_GRAPH_REJECT_NEVER = 0, 1, 2
+QV_FLAG_GRAPH_PLANE8 = 64      # ... and / or an int8 image in row order with a 16-byte record per row: rejecting hops can start on it (qv_graph_set_reject_image)
+QV_GRAPH_IMAGE_AUTO, QV_GRAPH_IMAGE_8BIT, QV_GRAPH_IMAGE_BF16 = 0, 1, 2
+QV_DEBUG_ROWMAJ8, QV_DEBUG_ROWMETA8 = 9, 10
 QV_DEBUG_RNORM, QV_DEBUG_RRES, QV_DEBUG_PLANE, QV_DEBUG_ROWMAJ16 = 0, 1, 2, 3
 QV_DEBUG_PLANE6, QV_DEBUG_RRES6, QV_DEBUG_RSCALE8 = 4, 5, 6
 QV_DEBUG_PLANE8, QV_DEBUG_RRES8 = 7, 8
@@ -162,6 +165,9 @@ PROTOTYPES = {
     "qv_graph_set_reject_plane": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_graph_reject_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_graph_reject_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]),
+    "qv_graph_set_reject_image": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_graph_reject8_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_graph_reject_image_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int]),
     "qv_sharded_span": (C.c_uint32, [C.c_int]),
     "qv_sharded_plan_add": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
     "qv_sharded_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_uint64]),

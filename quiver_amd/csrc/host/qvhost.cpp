@@ -245,6 +245,7 @@ HNSW::HNSW(qv_metric metric, int device, const HNSWConfig& c) : metric_(metric),
     maxLevel_ = c.MaxLevel > 0 ? c.MaxLevel : 16;                      // :235-237
     rng_ = c.seed;
     graph_plane_ = c.GraphPlane;
+    graph_plane8_ = c.GraphPlane8;
 }
 HNSW::~HNSW() { if (dg_ && dg_ != bg_) qv_graph_destroy(dg_); if (bg_) qv_graph_destroy(bg_); if (h_) qv_index_destroy(h_); }
 
@@ -433,7 +434,7 @@ Error HNSW::connectNode(uint32_t nodeIdx, const float* v, int level, int graphLe
 Error HNSW::ensureIndex(uint32_t len) {
     if (!h_) {
         if (len == 0) return "vector dimensions do not match";
-        if (qv_index_create(&h_, len, metric_, device_, QV_FLAG_ROWMAJOR | (graph_plane_ ? QV_FLAG_GRAPH_PLANE : QV_FLAG_NONE)) != QV_OK) return qv_err();   // row gathers are this index's hot path
+        if (qv_index_create(&h_, len, metric_, device_, QV_FLAG_ROWMAJOR | (graph_plane_ ? QV_FLAG_GRAPH_PLANE : QV_FLAG_NONE) | (graph_plane8_ ? QV_FLAG_GRAPH_PLANE8 : QV_FLAG_NONE)) != QV_OK) return qv_err();   // row gathers are this index's hot path
         dim_ = (int)len;
     } else if ((int)len != dim_) {
         if (size_ != 0) return "vector dimensions do not match";       // adapter.go:168 ErrDimensionMismatch from the distance func
@@ -444,7 +445,7 @@ Error HNSW::ensureIndex(uint32_t len) {
         if (bg_) qv_graph_destroy(bg_);
         dg_ = nullptr; bg_ = nullptr; dg_dirty_ = true; bg_synced_ = false;
         qv_index_destroy(h_); h_ = nullptr;
-        if (qv_index_create(&h_, len, metric_, device_, QV_FLAG_ROWMAJOR | (graph_plane_ ? QV_FLAG_GRAPH_PLANE : QV_FLAG_NONE)) != QV_OK) return qv_err();
+        if (qv_index_create(&h_, len, metric_, device_, QV_FLAG_ROWMAJOR | (graph_plane_ ? QV_FLAG_GRAPH_PLANE : QV_FLAG_NONE) | (graph_plane8_ ? QV_FLAG_GRAPH_PLANE8 : QV_FLAG_NONE)) != QV_OK) return qv_err();
         dim_ = (int)len;
         if (!nodes_.empty()) {
             std::vector<float> zeros((size_t)nodes_.size() * len, 0.f);
@@ -1259,6 +1260,7 @@ void* qvh_hnsw_new(int metric, int device, int M, int maxM0, int efC, int efS, i
     return new HNSW((qv_metric)metric, device, c);
 }
 void qvh_hnsw_free(void* p) { delete static_cast<HNSW*>(p); }
+void qvh_hnsw_set_graph_plane8(void* p, int on) { static_cast<HNSW*>(p)->SetGraphPlane8(on != 0); }   // HNSWConfig::GraphPlane8, before the first Insert
 void qvh_hnsw_set_graph_plane(void* p, int on) { static_cast<HNSW*>(p)->SetGraphPlane(on != 0); }   // HNSWConfig::GraphPlane, before the first Insert
 int qvh_hnsw_insert(void* p, const char* id, const float* v, uint32_t len) { return ret(static_cast<HNSW*>(p)->Insert(id, v, len)); }
 int qvh_hnsw_insert_batch(void* p, const char** ids, const float* packed, uint32_t len, uint32_t n, uint32_t batch_max, uint32_t ramp_div) {

@@ -117,6 +117,8 @@ struct HNSWConfig {          // pkg/hnsw/hnsw.go:27-41; defaults hnsw.go:223-237
     uint64_t seed = 1;       // the reference seeds from the wall clock (hnsw.go:248)
     bool GraphPlane = false; // the device index also keeps the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE, +2 * dim bytes per row) on which large
                              // SearchBatch calls reject neighbours (qv_graph_set_reject_plane); results do not depend on it
+    bool GraphPlane8 = false; // ... and / or the row-order 8-bit image with a record per row (QV_FLAG_GRAPH_PLANE8, +dim + 16 bytes per row): the flag bit only —
+                             // which image a rejecting traversal starts on is the library's rule (qv_graph_set_reject_image); results do not depend on it
 };
 
 struct HNSWResult { std::string id; float distance; uint32_t index; };   // hnsw.go:87-95
@@ -144,6 +146,7 @@ public:
     uint32_t Size() const { return size_.load(); }                    // hnsw.go:253-255 atomic.LoadUint32
     // introspection for graph-equality tests
     uint32_t Nodes() const { std::shared_lock<std::shared_mutex> l(mu_); return (uint32_t)nodes_.size(); }
+    void SetGraphPlane8(bool on) { graph_plane8_ = on; } // as HNSWConfig::GraphPlane8; before the first Insert
     void SetGraphPlane(bool on) { graph_plane_ = on; }   // as HNSWConfig::GraphPlane, for faces that build the config field by field; before the first Insert
     // the graph is what InsertBatch built: no Delete or lone Insert since (those keep the device graph current where they can —
     // DeviceState — but the graph is then no longer a batch build's)
@@ -183,6 +186,7 @@ private:
     mutable std::shared_mutex mu_;                 // hnsw.go:58 (the embedded sync.RWMutex)
     std::mutex dg_mu_;                             // the lazily uploaded device copy of the graph
     qv_metric metric_; int device_;
+    bool graph_plane8_ = false;                   // HNSWConfig::GraphPlane8 (SetGraphPlane8 before the first Insert)
     bool graph_plane_ = false;                    // HNSWConfig::GraphPlane (SetGraphPlane before the first Insert)
     qv_index* h_ = nullptr; int dim_ = 0;
     int M_, maxM0_, efC_, efS_, maxLevel_;

@@ -126,6 +126,16 @@ int ensure_rows(qv_index* idx, uint64_t rows, bool exact) {
             (void)hipFree(idx->d_rowmaj16); idx->d_rowmaj16 = nullptr; idx->rowmaj16_lost = true;
         } else e = eg;
     }
+    if (e == hipSuccess && idx->wants_rowmaj8()) {
+        // the row-order 8-bit image and its records (QV_FLAG_GRAPH_PLANE8): the same — given up alone (QV_TEST_ROWMAJ8_OOM: the same for tests)
+        hipError_t eg = getenv("QV_TEST_ROWMAJ8_OOM") ? hipErrorOutOfMemory
+                                                      : regrow(&idx->d_rowmaj8, (size_t)idx->n_rows * idx->dim, new_tiles * 64 * (size_t)idx->dim);
+        if (eg == hipSuccess) eg = regrow(&idx->d_rowmeta8, (size_t)idx->n_rows * sizeof(qv::RowMeta8), new_tiles * 64 * sizeof(qv::RowMeta8));
+        if (eg == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            (void)hipFree(idx->d_rowmaj8); (void)hipFree(idx->d_rowmeta8); idx->d_rowmaj8 = nullptr; idx->d_rowmeta8 = nullptr; idx->rowmaj8_lost = true;
+        } else e = eg;
+    }
     if (e == hipSuccess && idx->wants_plane()) {
         // the bfloat16 copy: required under QV_FLAG_BF16_ROWS; otherwise (the default on cosine / dot indexes and on QV_FLAG_L2_SCAN_PLANE ones, for the single-query bound
         // scan) an accelerator — when it does not fit, the index frees it and carries on without: searches take the exact scan
@@ -249,7 +259,7 @@ void qv_index_destroy(qv_index* idx) {
     (void)hipDeviceSynchronize();
     for (SearchCtx* c : idx->all_ctx) { c->release(); delete c; }
     for (auto& kv : idx->stream_ws) { kv.second->ws.release(); kv.second->tickets.release(); delete kv.second; }
-    (void)hipFree(idx->d_tiles); (void)hipFree(idx->d_rnorm); (void)hipFree(idx->d_alive); (void)hipFree(idx->d_rres); (void)hipFree(idx->d_rowmaj); (void)hipFree(idx->d_rowmaj16); (void)hipFree(idx->d_bf16); (void)hipFree(idx->d_bound_stats);
+    (void)hipFree(idx->d_tiles); (void)hipFree(idx->d_rnorm); (void)hipFree(idx->d_alive); (void)hipFree(idx->d_rres); (void)hipFree(idx->d_rowmaj); (void)hipFree(idx->d_rowmaj16); (void)hipFree(idx->d_rowmaj8); (void)hipFree(idx->d_rowmeta8); (void)hipFree(idx->d_bf16); (void)hipFree(idx->d_bound_stats);
     (void)hipFree(idx->d_plane8); (void)hipFree(idx->d_rscale8); (void)hipFree(idx->d_rres8);
     (void)hipFree(idx->d_plane6); (void)hipFree(idx->d_rres6);
     idx->mut_stage.release();
@@ -2133,6 +2143,10 @@ int qv_index_debug_read(qv_index* idx, int what, void* out, size_t bytes) {
     } else if (what == QV_DEBUG_ROWMAJ16 && (idx->flags & QV_FLAG_GRAPH_PLANE)) {   // (an index created without the flag answers as it always did: an unknown code)
         if (!idx->wants_rowmaj16() || (tiles && !idx->d_rowmaj16)) return fail(QV_ERR_UNSUPPORTED, "this index keeps no row-order bfloat16 copy");
         src = idx->d_rowmaj16; need = (size_t)idx->n_rows * idx->dim * sizeof(uint16_t);
+    } else if ((what == QV_DEBUG_ROWMAJ8 || what == QV_DEBUG_ROWMETA8) && (idx->flags & QV_FLAG_GRAPH_PLANE8)) {   // (without the flag: an unknown code, as always)
+        if (!idx->wants_rowmaj8() || (tiles && !idx->d_rowmaj8)) return fail(QV_ERR_UNSUPPORTED, "this index keeps no row-order 8-bit image");
+        if (what == QV_DEBUG_ROWMAJ8) { src = idx->d_rowmaj8; need = (size_t)idx->n_rows * idx->dim; }
+        else { src = idx->d_rowmeta8; need = (size_t)idx->n_rows * sizeof(qv::RowMeta8); }
     } else if ((what == QV_DEBUG_PLANE6 || what == QV_DEBUG_RRES6 || what == QV_DEBUG_RSCALE8) && idx->wants_plane6()) {   // (an index that keeps no such plane answers as it always did: an unknown code)
         if (tiles && !idx->d_plane6) return fail(QV_ERR_UNSUPPORTED, "this index keeps no 6-bit plane");
         if (what == QV_DEBUG_PLANE6) { src = idx->d_plane6; need = tiles * idx->plane6_tile_bytes(); }

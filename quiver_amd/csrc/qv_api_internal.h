@@ -100,6 +100,9 @@ struct qv_index {
     float* d_rowmaj = nullptr;
     uint16_t* d_rowmaj16 = nullptr;            // the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE): written wherever d_rowmaj is
     bool rowmaj16_lost = false;                // it could not be allocated: the index carries on without it
+    int8_t* d_rowmaj8 = nullptr;               // the row-order 8-bit image (QV_FLAG_GRAPH_PLANE8) and its 16-byte record per row: written wherever d_rowmaj is
+    qv::RowMeta8* d_rowmeta8 = nullptr;
+    bool rowmaj8_lost = false;                 // it could not be allocated: the index carries on without it
     uint16_t* d_bf16 = nullptr;                // the bfloat16 copy (QV_FLAG_BF16_ROWS, and by default on cosine / dot indexes): refreshed by every call that writes rows
     bool plane_lost = false;                   // the default copy could not be allocated: the index carries on without it
     qv::BoundKnobs bound = {};                 // qv_index_set_bound_scan, and by qv::BoundForm the four qv_index_set_bound_plane*
@@ -143,6 +146,7 @@ struct qv_index {
         v.dim = dim; v.dim4 = dim4; v.n_rows = n_rows; v.n_tiles = (n_rows + 63) / 64; v.metric = metric; v.filter = filter;
         v.l2_planes = l2_planes() ? 1 : 0;
         v.rowmaj16 = d_rowmaj16;
+        v.rowmaj8 = d_rowmaj8; v.rowmeta8 = d_rowmeta8;
         v.plane6 = d_plane6; v.rres6 = d_rres6; v.bound_plane6 = bound.plane6;
         return v;
     }
@@ -161,6 +165,11 @@ struct qv_index {
     // the row-order bfloat16 copy a graph's rejecting hops read: asked for, beside the float32 row-major copy, on the bound's metrics, whole 64-element slabs
     bool wants_rowmaj16() const {
         return (flags & QV_FLAG_GRAPH_PLANE) && (flags & QV_FLAG_ROWMAJOR) && !rowmaj16_lost && (metric == QV_COSINE || metric == QV_DOT) && (dim & 63u) == 0 && dim <= 4096;
+    }
+    // the row-order 8-bit image, the same way: whole 128-element slabs, and sums that stay exact in int32 (dim <= 4096).  Independent of the copy above
+    // and of the tile-layout 8-bit plane (QV_FLAG_NO_SCAN_PLANE): k_rowmaj8 derives its own scale and residual
+    bool wants_rowmaj8() const {
+        return (flags & QV_FLAG_GRAPH_PLANE8) && (flags & QV_FLAG_ROWMAJOR) && !rowmaj8_lost && (metric == QV_COSINE || metric == QV_DOT) && (dim & 127u) == 0 && dim <= 4096;
     }
     // ... and the 6-bit plane wherever they keep the 8-bit one, unless told not to (QV_FLAG_NO_PLANE6), on rows of whole 64-dimension groups
     bool wants_plane6() const { return wants_plane8() && !(flags & QV_FLAG_NO_PLANE6) && !plane6_lost && (dim & 63u) == 0; }

@@ -16,6 +16,7 @@
 //                                            (qv_batched.hip: its error bound is per row and per query, not a worst case)
 //   rowmaj  float  [rows][dim]               optional row-major copy (QV_FLAG_ROWMAJOR)
 //   rowmaj16 bf16  [rows][dim]               optional bfloat16 image of it (QV_FLAG_GRAPH_PLANE): what a rejecting graph hop reads
+//   rowmaj8  i8    [rows][dim]               optional int8 image of it (QV_FLAG_GRAPH_PLANE8) and rowmeta8, a 16-byte record per row: what a hop rejecting on 8 bits reads
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,6 +30,9 @@ constexpr int kMaxWideK = 128;         // wave-resident list of 2 keys per lane 
 constexpr int kMaxBatchedK = 4096;     // filter + re-score batches: beyond 64 results per query their selections are radix selections (qv_batched.hip)
 constexpr int kMaxSelectK = 8192;      // one key per row + radix select (qv_select.hip): above it, the full ranking (qv_rank.hip)
 constexpr uint64_t kDeadKey = ~0ull;
+
+// one row of IndexView::rowmeta8: |r| as v.rnorm holds it, and the row's 8-bit scale and residual (rres8 NaN: a row the bound says nothing about)
+struct RowMeta8 { double rnorm; float rscale8; float rres8; };
 
 struct IndexView {
     float*    tiles;
@@ -62,7 +66,12 @@ struct IndexView {
                           // multiple of 64 — never without plane8, whose scale it shares.  Refreshed with it (k_row_state6).
     float*    rres6;      // per row: |r - 4 rscale8 c6| rounded up; NaN = a row the 6-bit bound says nothing about
     int       bound_plane6; // qv_index_set_bound_plane6: 0 the 6-bit stage in front of the 8-bit one from its measured shapes on, 1 whenever that one is taken, 2 never
+    int8_t*   rowmaj8;    // may be null: the rows' int8 image in row order, [rows][dim] (QV_FLAG_GRAPH_PLANE8: cosine / dot, rowmaj kept, dim a multiple of 128
+                          // up to 4096); the bytes bound8_scale / bound8_quant give (plane8's, where that is kept).  Written wherever rowmaj is (k_rowmaj8)
+    RowMeta8* rowmeta8;   // beside it, one record per row: what a rejecting graph hop needs of the row in ONE gather
 };
+
+static_assert(sizeof(RowMeta8) == 16, "one 16-byte record per row");
 
 struct GraphView {
     const int8_t*   level;      // [n] node level, -1 = tombstone
@@ -98,6 +107,8 @@ struct HnswOpts {
     uint32_t        front     = 0;        // set by launch_hnsw_search_wave for its wave-per-query form: which parts of the round-6 hop are on (qv_hnsw.hip)
     uint32_t*       next      = nullptr;  // set by launch_hnsw_search_wave: the call's query counter (zeroed by k_hnsw_prep_queries): a wave slot that
                                           // finishes its traversal takes the next unclaimed query instead of a fixed stride of them
+    uint32_t        rj_image  = 0;        // with rj_stats: 0 = reject on the bfloat16 copy (rj_stats: the graph's bfloat16 counters), 1 = on the 8-bit image
+                                          // (rj_stats: its 8-bit counters) — qv_graph_reject_image_applies' answer minus one
     unsigned long long* rj_stats = nullptr; // [3] the graph's reject counters (qv_graph_reject_stats); non-null = this call asked for the rejecting
                                           // form (qv_graph_reject_applies said yes): launch_hnsw_search_wave takes it where its own conditions hold
 };
@@ -408,6 +419,7 @@ uint32_t hnsw_vis_hash_cap(uint32_t ef);                 // hash entries per wav
 
 // wave-resident form (no LDS heaps); count_out = 0xFFFFFFFE for queries that met equal distances / NaN
 uint32_t hnsw_wave_grid(int cus, int metric, uint32_t dim4);
+bool hnsw_image8_keeps_occupancy(int metric, uint32_t dim4);   // the 8-bit rejecting form's LDS leaves as many traversals per CU as the unchanged kernel's
 uint32_t hnsw_lat_nq_cap(int cus);                        // the largest call launch_hnsw_search_wave hands to its latency form
 hipError_t launch_hub_build(const IndexView& v, const GraphView& g, const uint32_t* d_hub_rows, uint32_t H, float* d_hub_tiles, double* d_hub_rnorm,
                             uint16_t* d_slot_of, uint16_t* d_l0_hub, hipStream_t s);

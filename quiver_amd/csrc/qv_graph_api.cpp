@@ -55,7 +55,10 @@ struct qv_graph {
     // (three device words, allocated and zeroed with the graph: graph_common_init)
     static int reject_default() { static const int m = [] { const char* e = getenv("QV_GRAPH_REJECT"); const int x = e ? atoi(e) : 0; return x == 1 || x == 2 ? x : 0; }(); return m; }
     int reject_mode = reject_default();
-    unsigned long long* d_rj_stats = nullptr;
+    unsigned long long* d_rj_stats = nullptr;   // [0..3) the bfloat16 copy's counters, [4..7) the 8-bit image's (qv_graph_reject8_stats)
+    // which image a rejecting traversal starts on (qv_graph_set_reject_image); QV_GRAPH_IMAGE (1 the 8-bit image, 2 the bfloat16 copy) sets the default
+    static int image_default() { static const int m = [] { const char* e = getenv("QV_GRAPH_IMAGE"); const int x = e ? atoi(e) : 0; return x == 1 || x == 2 ? x : 0; }(); return m; }
+    int image_mode = image_default();
     std::mutex mu;                              // the graph's OWN buffers below (device-form traversals, construction, export): one user at a time
     // host-pointer searches: a context each (pool), and a front that lets concurrent small calls share a traversal batch
     // (qv_coalesce.h).  A traversal is a chain of hops, so a lone batch does not fill the chip and a second caller should not wait for the
@@ -187,8 +190,8 @@ int graph_common_init(qv_graph* g) {
     HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&g->ev_last, hipEventDisableTiming));
     // the reject counters (qv_graph_reject_stats): three device words, zeroed here once — no traversal call allocates or synchronises for them
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g->d_rj_stats), 32));
-    HIPCHK(hipMemset(g->d_rj_stats, 0, 32));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g->d_rj_stats), 64));
+    HIPCHK(hipMemset(g->d_rj_stats, 0, 64));
     HIPCHK(hipStreamSynchronize(nullptr));                              // (the graph's streams are non-blocking: the fill has run before a kernel adds)
     return QV_OK;
 }
@@ -333,9 +336,11 @@ int traverse_wave(qv_graph* g, const float* dq, void* qblk, Buf* table, uint32_t
                   uint32_t* d_rows, float* d_dist, uint32_t* d_cnt, uint32_t* d_ev, hipStream_t s) {
     qv_index* idx = g->idx;
     auto& hb = g->hubs;
-    if (!hubs_possible(g, nq) &&
-        qv_graph_reject_applies(idx->metric, idx->dim, g->g.n_nodes, nq, std::max(ef, k), idx->cus, g->reject_mode, idx->d_rowmaj16 != nullptr, g->g.has_dead ? 1 : 0, g->g.max_m0) == 1) {
-        wo.rj_stats = g->d_rj_stats;
+    if (!hubs_possible(g, nq)) {
+        const int form = qv_graph_reject_image_applies(idx->metric, idx->dim, g->g.n_nodes, nq, std::max(ef, k), idx->cus, g->reject_mode, idx->d_rowmaj16 != nullptr,
+                                                       g->g.has_dead ? 1 : 0, g->g.max_m0, idx->d_rowmaj8 != nullptr && idx->d_rowmeta8 != nullptr, g->image_mode);
+        if (form == 1) wo.rj_stats = g->d_rj_stats;
+        else if (form == 2) { wo.rj_stats = g->d_rj_stats + 4; wo.rj_image = 1; }
     }
     if (hubs_possible(g, nq)) {
         {
@@ -607,6 +612,51 @@ int qv_graph_reject_applies(int metric, uint32_t dim, uint32_t n_nodes, uint32_t
     // AUTO: the measured cells.  Dot, other dimensions, smaller and larger graphs, smaller calls and other list sizes are unmeasured: they keep the unchanged kernels.
     // One dimension and one graph size were measured: the rule takes that dimension and graphs from that size to below twice it.
     return metric == QV_COSINE && dim == 768u && n_nodes >= 1000000u && n_nodes < 2000000u && nq >= 8192u && ef_search >= 64u && ef_search <= 256u ? 1 : 0;
+}
+
+int qv_graph_set_reject_image(qv_graph* g, int mode) {
+    if (!g) return fail(QV_ERR_INVALID_ARG, "graph is null");
+    if (mode < QV_GRAPH_IMAGE_AUTO || mode > QV_GRAPH_IMAGE_BF16) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (auto), 1 (the 8-bit image) or 2 (the bfloat16 copy); got %d", mode);
+    g->image_mode = mode;
+    return QV_OK;
+}
+int qv_graph_reject8_stats(qv_graph* g, uint64_t* out) {
+    if (!g || !out) return fail(QV_ERR_INVALID_ARG, "graph/out is null");
+    out[0] = out[1] = out[2] = 0;
+    out[3] = g->idx->d_rowmaj8 && g->idx->d_rowmeta8 ? 1 : 0;
+    HIPCHK(hipSetDevice(g->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (g->d_rj_stats) {
+        unsigned long long h[3] = {0, 0, 0};
+        HIPCHK(hipMemcpy(h, g->d_rj_stats + 4, sizeof(h), hipMemcpyDeviceToHost));
+        out[0] = h[0]; out[1] = h[1]; out[2] = h[2];
+    }
+    return QV_OK;
+}
+// Which image a rejecting traversal starts on: traverse_wave's rule, stated once.  qv_graph_reject_applies keeps deciding WHETHER a call rejects — each
+// image is asked about as "an index holding that image", so this never answers non-zero where that answers 0.  The 8-bit image needs whole
+// 128-element slabs.  AUTO takes the 8-bit image in the cells it was measured faster in and nothing more (profiles/LAB_r23_graph_reject8.md: 1M x 768,
+// cosine, MaxLevel 1, list sizes 64 / 128 / 256, 8192 and 32768 queries per call — in every one of the twelve cells the slowest 8-bit-first round beat
+// the fastest bfloat16-first round, by 7 - 18 % at the median, and "never" by 26 - 53 %).  Those are the cells AUTO of qv_graph_reject_applies takes, so
+// the test is the same for an index holding both images and for one holding only the 8-bit image; a width at which the resident int8 terms would
+// cost a traversal per CU is declined as well (768 keeps its twelve).
+static bool graph_image8_auto_cell(int metric, uint32_t dim, uint32_t n_nodes, uint32_t nq, uint32_t ef_search) {
+    return metric == QV_COSINE && dim == 768u && n_nodes >= 1000000u && n_nodes < 2000000u && nq >= 8192u && ef_search >= 64u && ef_search <= 256u;
+}
+int qv_graph_reject_image_applies(int metric, uint32_t dim, uint32_t n_nodes, uint32_t nq, uint32_t ef_search, int cus, int mode, int has_plane,
+                                  int has_tombstones, uint32_t max_m0, int has_image8, int image_mode) {
+    if (image_mode < QV_GRAPH_IMAGE_AUTO || image_mode > QV_GRAPH_IMAGE_BF16)
+        return fail(QV_ERR_INVALID_ARG, "image mode must be 0 (auto), 1 (the 8-bit image) or 2 (the bfloat16 copy); got %d", image_mode);
+    const int a16 = qv_graph_reject_applies(metric, dim, n_nodes, nq, ef_search, cus, mode, has_plane, has_tombstones, max_m0);
+    if (a16 < 0) return a16;
+    int a8 = 0;
+    if (has_image8 && image_mode != QV_GRAPH_IMAGE_BF16 && (dim & 127u) == 0 && dim >= 128u) {
+        a8 = qv_graph_reject_applies(metric, dim, n_nodes, nq, ef_search, cus, mode, 1, has_tombstones, max_m0);
+        if (a8 < 0) return a8;
+        if (a8 && image_mode == QV_GRAPH_IMAGE_AUTO)
+            a8 = graph_image8_auto_cell(metric, dim, n_nodes, nq, ef_search) && qv::hnsw_image8_keeps_occupancy(metric, (dim + 3) / 4) ? 1 : 0;
+    }
+    return a8 ? 2 : (a16 ? 1 : 0);
 }
 
 int qv_graph_coalesce_stats(qv_graph* g, uint64_t out[8]) {

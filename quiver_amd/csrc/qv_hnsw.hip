@@ -583,6 +583,103 @@ __device__ __forceinline__ float hnsw_hop_chain16(const IndexView& v, const lds_
     return acc;
 }
 
+// ---- a hop that rejects on the row-order 8-bit image (IndexView::rowmaj8) --------------------------------------------------------
+// The same hop with fewer bytes: slab 0 of every link comes from rowmaj8 — 128 bytes = 128 elements of a row, the same piece shape, swizzle
+// and buffers — and stage 1 walks the new rows' int8 images against the query's two int8 terms (qv_bound.h: qq = 128 hi + lo) with integer dot
+// products.  The sums are exact, so the order a lane walks its row in does not matter and bound_scan_interval8<M> applies as it stands, with
+// the row's norm, scale and residual from ONE 16-byte record (IndexView::rowmeta8).  Survivors go straight to their float32 rows
+// (hnsw_eval_hop_front<M, false>): no bfloat16 stage in between.
+// The query's terms are RESIDENT in LDS, quantised once per query (hnsw_quantize_query8, at the query's first rejecting hop): per slab 64
+// words, [32 words of hi | 32 words of lo], word j = elements 4 j .. 4 j + 3 of the slab.  Slabs 0 and 1 lie in the two query slab buffers —
+// idle at level 0 once the entry point has been evaluated, and every rejecting hop comes after that — and slabs 2.. behind the float32
+// query words: dim * 2 - 512 bytes more per wave slot, 1 KiB at 768 dimensions (hnsw_wave_lds_bytes8).
+__device__ __forceinline__ lds_u32* hnsw_q8_slab(lds_u8* slabs_l, uint32_t dim, uint32_t sl) {
+    lds_u8* qbufs = slabs_l + 2 * kHnswSlabBytes;
+    return (lds_u32*)(sl < 2u ? qbufs + sl * 256u : slabs_l + kHnswWaveFixedLds - 64 * 4 + dim * 4u + (sl - 2u) * 256u);
+}
+// The query of a rejecting traversal, once: numerically what bound8_stage_query (qv_bound_scan.hip) produces — sq = max|q_i| / 16256,
+// qq = rint(q / sq) = 128 hi + lo, qres = |q - sq qq| rounded up — from the float32 words resident in LDS.  false: a query without a scale
+// (a non-finite element, no non-zero element): it walks as before.  Wave-uniform results.
+__device__ __forceinline__ bool hnsw_quantize_query8(const lds_u32* qres_l, lds_u8* slabs_l, uint32_t dim, uint32_t lane, double& sq_out, double& qres_out) {
+    float mx = 0.f; bool bad = false;
+    for (uint32_t i = lane; i < dim; i += 64) { const float x = __uint_as_float(qres_l[i]); bad |= !((x - x) == 0.0f); mx = __builtin_fmaxf(mx, __builtin_fabsf(x)); }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) mx = __builtin_fmaxf(mx, __shfl_xor(mx, m));
+    mx = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(mx)));
+    const bool q_ok = __ballot(bad) == 0ull && mx > 0.0f;
+    const double sq = q_ok ? (double)mx / (double)kBound8QueryMax : 1.0;
+    double r2 = 0.0;
+    for (uint32_t j = lane; j < (dim >> 2); j += 64) {                  // word j of the query: elements 4 j .. 4 j + 3
+        uint32_t wh = 0, wl = 0;
+#pragma unroll 1
+        for (uint32_t e = 0; e < 4; e++) {                            // (not unrolled: four float64 divisions side by side would set the kernel's register count)
+            const double x = q_ok ? (double)__uint_as_float(qres_l[4 * j + e]) : 0.0;
+            const double qq = __builtin_rint(x / sq);                  // |qq| <= 16256
+            const double hi = __builtin_rint(qq * (1.0 / 128.0)), lo = qq - 128.0 * hi;   // |hi| <= 127, |lo| <= 64: exact
+            wh |= ((uint32_t)(int)hi & 0xFFu) << (8 * e); wl |= ((uint32_t)(int)lo & 0xFFu) << (8 * e);
+            const double d = x - sq * qq;
+            r2 = __builtin_fma(d, d, r2);
+        }
+        lds_u32* qs = hnsw_q8_slab(slabs_l, dim, j >> 5);
+        qs[j & 31u] = wh; qs[32u + (j & 31u)] = wl;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) r2 += __shfl_xor(r2, m);
+    // (wave-uniform by construction; said so, so that the two live in scalar registers for the rest of the traversal)
+    auto uniform = [](double x) -> double {
+        const uint64_t u = __builtin_bit_cast(uint64_t, x);
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
+        return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+    };
+    sq_out = uniform(sq);
+    qres_out = uniform(q_ok ? __builtin_sqrt(r2) * (1.0 + 1e-9) + 1e-300 : __builtin_nan(""));
+    return q_ok;
+}
+// One slab of the image: 8 chunks of 16 elements; lane j < 32 of the wave holds hi word j of the slab, lane 32 + j its lo word.
+__device__ __forceinline__ void slab_accumulate_i8(int& acc_hi, int& acc_lo, const lds_u8* buf, uint32_t r, uint32_t qw) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(3))) u4* lds_u4p;
+    const uint32_t mg = r >> 3, mr = r & 7, msw = mr ^ (mg & 1);
+    const lds_u8* mine = buf + mg * 1024 + mr * 128;
+    u4 x[2];
+    x[0] = *(lds_u4p)(mine + ((0u ^ msw) << 4));
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        const int cur = c & 1, nxt = cur ^ 1;
+        if (c + 1 < 8) x[nxt] = *(lds_u4p)(mine + (((uint32_t)(c + 1) ^ msw) << 4));
+#define QV_I8(W, J) acc_hi = __builtin_amdgcn_sdot4(__builtin_amdgcn_readlane((int)qw, 4 * c + J), (int)(W), acc_hi, false); \
+                    acc_lo = __builtin_amdgcn_sdot4(__builtin_amdgcn_readlane((int)qw, 32 + 4 * c + J), (int)(W), acc_lo, false);
+        QV_I8(x[cur].x, 0) QV_I8(x[cur].y, 1) QV_I8(x[cur].z, 2) QV_I8(x[cur].w, 3)
+#undef QV_I8
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// I = sum qq_i r8_i of the rows batch[0..n) (n <= 32) on lanes 0..n-1.  The caller has waited for slab 0 of the image (vmcnt(0)); row r's slab 0
+// sits at adjacency position `pos`, its later slabs at position r.  dim is a multiple of 128, at most 4096: each of the two sums is exact in int32.
+__device__ __forceinline__ long long hnsw_hop_sum8(const IndexView& v, const lds_u32* batch_l, lds_u8* slabs_l, uint32_t n, uint32_t pos, uint32_t lane) {
+    const uint32_t nslab = v.dim >> 7;
+    const bool me = lane < n;
+    DmaRole role;                                                       // (a row of the image is dim / 4 float32 words, dim4 / 4 chunks)
+    dma_role(role, reinterpret_cast<const float*>(v.rowmaj8), v.dim >> 2, batch_l, n, lane);
+    int acc_hi = 0, acc_lo = 0;
+    uint32_t qw = hnsw_q8_slab(slabs_l, v.dim, 0)[lane];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    for (uint32_t sl = 0; sl < nslab; sl++) {
+        if (sl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // slab sl has landed
+        uint32_t qn = 0;
+        if (sl + 1 < nslab) {                                           // the next slab lands while this one is consumed
+            dma_issue_slab<kHnswSlab>(role, sl + 1, v.dim4 >> 2, slabs_l + ((sl + 1) & 1) * kHnswSlabBytes);
+            qn = hnsw_q8_slab(slabs_l, v.dim, sl + 1)[lane];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (me) slab_accumulate_i8(acc_hi, acc_lo, slabs_l + (sl & 1) * kHnswSlabBytes, sl ? lane : pos, qw);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // this slab's buffer is read before it is refilled
+        qw = qn;
+    }
+    return 128ll * (long long)acc_hi + (long long)acc_lo;               // (as bound8_scan_sum: the two sums kept apart, combined in 64 bits)
+}
+
 #ifdef QV_HNSW_P512
 // EXPERIMENT of the measurement build (tools/build_variant.sh p512 qv_hnsw.hip -DQV_HNSW_P512), TIMING ONLY: a hop's rows in groups of 8,
 // 512 contiguous bytes of each row per slab (a quarter of the address translations and DRAM pages of the 128-byte pieces), eight lanes
@@ -1117,8 +1214,10 @@ k_hnsw_search(IndexView v, GraphView g, const typename MT<M>::Q* __restrict__ qb
 
 
 // RJ (W == 1, QLDS, cosine and dot; launch_hnsw_search_wave): level-0 hops of the bucketed path that start with a full list reject on the
-// row-order bfloat16 copy first ("a hop that rejects on the row-order bfloat16 copy" above).  RJ = false is the kernel as it was.
-template <int M, int U, int S, bool QLDS, int W = 1, bool RJ = false>
+// row-order bfloat16 copy first (RJ = kRjBf16, "a hop that rejects on the row-order bfloat16 copy" above) or on the row-order 8-bit image
+// (RJ = kRjImage8, "a hop that rejects on the row-order 8-bit image").  RJ = kRjNone is the kernel as it was.
+constexpr int kRjNone = 0, kRjBf16 = 1, kRjImage8 = 2;
+template <int M, int U, int S, bool QLDS, int W = 1, int RJ = kRjNone>
 __global__ void __launch_bounds__(64 * W)
 k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict__ qblk, const double* __restrict__ qconst, uint32_t nq, uint32_t k, uint32_t ef_search,
                    HnswOpts o,
@@ -1178,7 +1277,12 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
     uint32_t n_eval = 0;
     // RJ: the margin's gamma (once), whether the bound works with this query's norm (once per query, wave-uniform), and the query's counters
     double rj_gamma = 0.0; bool rj_q = false; uint32_t rj_ev = 0, rj_rej = 0;
-    if constexpr (RJ) rj_gamma = bound_scan_gamma(v.dim);
+    if constexpr (RJ == kRjBf16) rj_gamma = bound_scan_gamma(v.dim);
+    // kRjImage8: the query's scale and residual, and whether its terms are in LDS yet (quantised at the query's first rejecting hop)
+    double rj_sq = 1.0, rj_qres = 0.0; bool rj_q8 = false;
+    // the image a rejecting hop's front requests: its base, and float32 words / 16-byte chunks per row as shifts of dim / dim4
+    const float* rj_img = RJ == kRjImage8 ? reinterpret_cast<const float*>(v.rowmaj8) : reinterpret_cast<const float*>(v.rowmaj16);
+    constexpr uint32_t rj_sh = RJ == kRjImage8 ? 2u : 1u;
 
     // distance of the query to batch[lane] for lane < n  ->  64-bit key (all lanes return; dead beyond n)
     auto eval_keys = [&](uint32_t n) -> uint64_t {
@@ -1343,7 +1447,7 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
         q_g = qblk + (size_t)qi * v.dim4 * 4;
         qc.qn = qconst[(size_t)qi * 2]; qc.qn32 = (float)qconst[(size_t)qi * 2 + 1];
         n_eval = 0; tie = false;
-        if constexpr (RJ) { rj_q = bound_scan_norm_ok(qc.qn, v.dim) && o.hub_H == 0; rj_ev = 0; rj_rej = 0; }
+        if constexpr (RJ) { rj_q = bound_scan_norm_ok(qc.qn, v.dim) && o.hub_H == 0; rj_ev = 0; rj_rej = 0; rj_q8 = false; }
         if (front) {                                                    // the query's float32 words into LDS, once per traversal
             const uint32_t qbytes = v.dim * 4u;
             const float* q32 = o.q32 + (size_t)qi * v.dim;
@@ -1424,6 +1528,14 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
                             hl = (o.l0_hub && lane < g.max_m0) ? (uint32_t)o.l0_hub[(size_t)cur * g.max_m0 + lane] : 0xFFFFu;
                         }
                         if (fdeg > 32u) fdeg = 32u;
+                        if constexpr (RJ == kRjImage8) {
+                            if (rj_q && n_list >= ef && !rj_q8) {            // the query's terms, once (nothing reads the query slab buffers any more)
+                                wfence();
+                                rj_q = hnsw_quantize_query8(qres_l, slabs_l, v.dim, lane, rj_sq, rj_qres);
+                                rj_q8 = true;
+                                wfence();
+                            }
+                        }
                         if constexpr (RJ) { if (rj_q && n_list >= ef) { rj_hop = true; rj_w = (uint32_t)(entry_at(ef - 1) >> 32); } }
                         fc = lane < fdeg ? cl : 0xFFFFFFFFu;
                         bool valid = fc < g.n_nodes;
@@ -1439,11 +1551,11 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
                             if (lane < 32u) batch[32 + lane] = (valid && !fhub) ? fc : c0;   // every adjacency position names a row that exists
                             wfence();
                             HTICK(2);
-                            DmaRole r0;                                      // (a rejecting hop: slab 0 of the bfloat16 image, dim / 2 words a row)
-                            dma_role(r0, rj_hop ? reinterpret_cast<const float*>(v.rowmaj16) : v.rowmaj, rj_hop ? v.dim >> 1 : v.dim, batch_l + 32, fdeg, lane);
+                            DmaRole r0;                                      // (a rejecting hop: slab 0 of the image, dim / 2 or dim / 4 words a row)
+                            dma_role(r0, rj_hop ? rj_img : v.rowmaj, rj_hop ? v.dim >> rj_sh : v.dim, batch_l + 32, fdeg, lane);
                             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #ifndef QV_HNSW_P512
-                            dma_issue_slab<kHnswSlab>(r0, 0, rj_hop ? v.dim4 >> 1 : v.dim4, slabs_l);       // slab 0 of every such link, beside the visited test
+                            dma_issue_slab<kHnswSlab>(r0, 0, rj_hop ? v.dim4 >> rj_sh : v.dim4, slabs_l);       // slab 0 of every such link, beside the visited test
 #endif
                         }
                         float dtab = 0.0f;
@@ -1553,7 +1665,30 @@ k_hnsw_search_wave(IndexView v, GraphView g, const typename MT<M>::Q* __restrict
                     float dd = 0.0f;
                     bool rj_keep = true; uint32_t erank = frank;             // RJ: this link survived stage 1; its rank among the survivors
                     if (rj_hop) {
-                        if constexpr (RJ) {
+                        if constexpr (RJ == kRjImage8) {
+                            // stage 1 on the 8-bit image: I of every new row, exactly, the row's record, the interval, and out with the rows whose
+                            // lower end is not below the worst distance the hop started with.  A row the bound says nothing about always survives.
+                            const bool me = lane < nrow;
+                            const uint32_t myrow = me ? batch_l[lane] : 0u;
+                            RowMeta8 rm; rm.rnorm = 0.0; rm.rscale8 = 0.0f; rm.rres8 = 0.0f;
+                            if (me) rm = v.rowmeta8[myrow];                  // (one 16-byte gather: lands beside the image's slabs)
+                            const long long isum = nrow ? hnsw_hop_sum8(v, batch_l, slabs_l, nrow, fpos, lane) : 0ll;
+                            bool keep = false;
+                            if (me) {
+                                float d_lo, d_hi;
+                                const bool sure = bound_scan_interval8<M>(isum, rj_sq, qc.qn, rj_qres, rm.rnorm, rm.rscale8, rm.rres8, v.dim, d_lo, d_hi);
+                                keep = !(sure && d_lo == d_lo && ord_f32(d_lo) >= rj_w);
+                            }
+                            const uint64_t km = __ballot(keep);              // over the compacted rows
+                            const uint32_t ns = (uint32_t)__builtin_popcountll(km);
+                            rj_ev += nb; rj_rej += nrow - ns;
+                            wfence();                                        // stage 1's reads of batch[] are done
+                            if (keep) batch[__builtin_popcountll(km & ((1ull << lane) - 1))] = myrow;
+                            wfence();
+                            if (ns) dd = hnsw_eval_hop_front<M, false>(v, batch_l, slabs_l, qc, ns, 0u, lane, qres_l);
+                            rj_keep = (km >> frank) & 1ull;                  // back at the adjacency positions (frank: the link's compacted lane)
+                            erank = (uint32_t)__builtin_popcountll(km & ((1ull << frank) - 1));
+                        } else if constexpr (RJ == kRjBf16) {
                             // stage 1: S~ of every new row from its image, the bound scan's interval, and out with the rows whose lower end is
                             // not below the worst distance the hop started with.  A row the bound says nothing about always survives.
                             const bool me = lane < nrow;
@@ -1811,6 +1946,17 @@ size_t hnsw_wave_lds_bytes(int /*metric*/, uint32_t dim4) {
     const bool qres = (hnsw_front_bits() & 1u) && (dim4 & 7u) == 0 && dim4 >= 8;      // (a row-major index is the launcher's other condition; without one the room stays unused)
     return (size_t)kHnswWaveFixedLds + (qres ? (size_t)dim4 * 16 : 0);
 }
+// ... and of the form that rejects on the 8-bit image: the query's int8 terms beyond the two query slab buffers (hnsw_q8_slab)
+size_t hnsw_wave_lds_bytes8(int metric, uint32_t dim4) {
+    const size_t q8 = (size_t)dim4 * 8;
+    return hnsw_wave_lds_bytes(metric, dim4) + (q8 > 512 ? q8 - 512 : 0);
+}
+// resident traversals per CU by LDS, at most the cap below: what the 8-bit form must not lower (qv_graph_reject_image_applies declines the widths where it would)
+static uint32_t hnsw_waves_by_lds(size_t lds) { return (uint32_t)std::max<size_t>(1, std::min<size_t>(16, (size_t)(160 * 1024) / lds)); }
+bool hnsw_image8_keeps_occupancy(int metric, uint32_t dim4) {
+    const uint32_t cap = 12;                                               // (QV_HNSW_WAVES_PER_CU's default: the measured setting)
+    return std::min(cap, hnsw_waves_by_lds(hnsw_wave_lds_bytes8(metric, dim4))) == std::min(cap, hnsw_waves_by_lds(hnsw_wave_lds_bytes(metric, dim4)));
+}
 uint32_t hnsw_wave_grid(int cus, int metric, uint32_t dim4) {
     const size_t lds = hnsw_wave_lds_bytes(metric, dim4);
     uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(16, (size_t)(160 * 1024) / lds));
@@ -1896,22 +2042,38 @@ hipError_t launch_hnsw_search_wave(const IndexView& v, const GraphView& g, const
     // The rejecting form (HnswOpts::rj_stats: the caller's rule asked for it): the kernel's own conditions — the bucketed path will be taken at
     // level 0 (front bit 1, no tombstones, at most 32 level-0 links), a plain Search, the image there in whole 64-element slabs, no hubs, and a
     // call beyond the latency form's reach.  Anything else launches the kernels above, as without the flag.
-    const bool rj = on.rj_stats != nullptr && v.rowmaj16 != nullptr && deep && (on.front & 1u) && !o.qlevel && !g.has_dead && g.max_m0 <= 32u && on.hub_H == 0 &&
+    // on.rj_image: the caller's rule chose the 8-bit image — whole 128-element slabs, the image and its records there; where the kernel's conditions
+    // for it fail the call takes the bfloat16 copy only if the caller asked for that (it did not: the counters it passed are the 8-bit ones)
+    const bool rj_cond = on.rj_stats != nullptr && deep && (on.front & 1u) && !o.qlevel && !g.has_dead && g.max_m0 <= 32u && on.hub_H == 0 &&
+                         !on.hist && (v.metric == QV_COSINE || v.metric == QV_DOT) && nq > lat_nq_cap;
+    const bool rj8 = rj_cond && on.rj_image == 1u && v.rowmaj8 != nullptr && v.rowmeta8 != nullptr && (v.dim & 127u) == 0 && v.dim >= 128 && v.dim <= 4096;
+    const size_t lds8 = hnsw_wave_lds_bytes8(v.metric, v.dim4);
+    const bool rj = on.rj_image == 0u && on.rj_stats != nullptr && v.rowmaj16 != nullptr && deep && (on.front & 1u) && !o.qlevel && !g.has_dead && g.max_m0 <= 32u && on.hub_H == 0 &&
                     !on.hist && (v.metric == QV_COSINE || v.metric == QV_DOT) && (v.dim & 63u) == 0 && v.dim >= 64 && nq > lat_nq_cap;
 #define QV_HWR(SS) QV_DISPATCH_METRIC(v.metric, {                                                                     \
         if constexpr (MM == QV_COSINE || MM == QV_DOT) {                                                              \
-            e = set_lds(k_hnsw_search_wave<MM, 4, SS, true, 1, true>, lds);                                           \
+            e = set_lds(k_hnsw_search_wave<MM, 4, SS, true, 1, kRjBf16>, lds);                                        \
             if (e != hipSuccess) return e;                                                                            \
-            hipLaunchKernelGGL((k_hnsw_search_wave<MM, 4, SS, true, 1, true>), dim3(grid), dim3(64), lds, s, v, g, static_cast<const typename MT<MM>::Q*>(d_qblk), \
+            hipLaunchKernelGGL((k_hnsw_search_wave<MM, 4, SS, true, 1, kRjBf16>), dim3(grid), dim3(64), lds, s, v, g, static_cast<const typename MT<MM>::Q*>(d_qblk), \
                                static_cast<const double*>(d_qconst), nq, k, ef, on,                                  \
                                d_rows_out, d_dist_out, d_count_out, d_evals_out);                                     \
         }                                                                                                             \
     })
-#define QV_HW(SS) if (rj) { QV_HWR(SS); } else if (deep) { QV_HWD(SS, true); } else { QV_HWD(SS, false); }
+#define QV_HWR8(SS) QV_DISPATCH_METRIC(v.metric, {                                                                    \
+        if constexpr (MM == QV_COSINE || MM == QV_DOT) {                                                              \
+            e = set_lds(k_hnsw_search_wave<MM, 4, SS, true, 1, kRjImage8>, lds8);                                     \
+            if (e != hipSuccess) return e;                                                                            \
+            hipLaunchKernelGGL((k_hnsw_search_wave<MM, 4, SS, true, 1, kRjImage8>), dim3(grid), dim3(64), lds8, s, v, g, static_cast<const typename MT<MM>::Q*>(d_qblk), \
+                               static_cast<const double*>(d_qconst), nq, k, ef, on,                                  \
+                               d_rows_out, d_dist_out, d_count_out, d_evals_out);                                     \
+        }                                                                                                             \
+    })
+#define QV_HW(SS) if (rj8) { QV_HWR8(SS); } else if (rj) { QV_HWR(SS); } else if (deep) { QV_HWD(SS, true); } else { QV_HWD(SS, false); }
     // list registers: S x 64 entries.  One notch more than efx needs where that is free (<= 128 VGPRs either way), so that a tie
     // group at the end of the result heap has room (ef <= 127 -> S = 2, ef = 128..256 -> S = 4; S = 8 would cost a wave per SIMD)
     if (efx < 128) { QV_HW(2); } else if (efx < 256) { QV_HW(4); } else if (efx < 320) { QV_HW(5); } else if (efx < 512) { QV_HW(8); } else { QV_HW(9); }
 #undef QV_HW
+#undef QV_HWR8
 #undef QV_HWR
 #undef QV_HWD
     return hipGetLastError();

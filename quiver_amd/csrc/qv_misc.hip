@@ -505,12 +505,64 @@ k_rowmaj16(IndexView v, uint32_t t0, uint32_t n_tiles, const uint32_t* __restric
         reinterpret_cast<uint2*>(v.rowmaj16 + ((size_t)t * 64 + r) * v.dim)[c] = o;      // (dim is a multiple of 64 here: dim == 4 * dim4)
     }
 }
+// The row-order 8-bit image (QV_FLAG_GRAPH_PLANE8) of the rows of tiles [t0, t0 + n_tiles) and its records: k_row_state8's quantiser, statement
+// for statement — the scale from the row's largest magnitude, the bytes, the residual in float64 FROM THE BYTES WRITTEN — so the bytes, the
+// scale and the residual are the tile plane's bit for bit where the index keeps one, and the image needs none.  One wave per tile, lane == row:
+// the tile is read as the planes read it, and a lane writes its row's 16 bytes per step to rowmaj8[row][16 s ..).  The record's norm is the
+// one the ingest kernel ahead on the stream left in v.rnorm.  Whole tiles are written, as k_rowmaj16 does.  dim is a multiple of 128 here.
+__global__ void __launch_bounds__(64)
+k_rowmaj8(IndexView v, uint32_t t0, const uint32_t* __restrict__ list) {
+    const uint32_t t = list ? list[blockIdx.x] : t0 + blockIdx.x, lane = threadIdx.x, steps = v.dim >> 4;
+    const f4* src = reinterpret_cast<const f4*>(v.tiles) + (size_t)t * v.dim4 * 64 + lane;
+    float maxabs = 0.f; bool bad = false; double n2 = 0.0;
+    for (uint32_t c = 0; c < v.dim4; c++) {
+        const f4 x = src[(size_t)c * 64];
+        const float e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            bad |= !((e[j] - e[j]) == 0.0f);
+            maxabs = __builtin_fmaxf(maxabs, __builtin_fabsf(e[j]));
+            n2 = __builtin_fma((double)e[j], (double)e[j], n2);
+        }
+    }
+    const float scale = bad ? 0.0f : bound8_scale(maxabs);
+    const float div = scale > 0.0f ? scale : 1.0f;
+    double s2 = 0.0;
+    const size_t row = (size_t)t * 64 + lane;
+    uint4* dst = reinterpret_cast<uint4*>(v.rowmaj8 + row * v.dim);
+    for (uint32_t s = 0; s < steps; s++) {
+        uint32_t w[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const f4 x = src[(size_t)(4 * s + c) * 64];
+            const float e[4] = {x.x, x.y, x.z, x.w};
+            uint32_t word = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int b = scale > 0.0f ? bound8_quant(e[j], div) : 0;
+                const double d = (double)e[j] - (double)scale * (double)b;
+                s2 = __builtin_fma(d, d, s2);
+                word |= ((uint32_t)b & 0xFFu) << (8 * j);
+            }
+            w[c] = word;
+        }
+        uint4 o; o.x = w[0]; o.y = w[1]; o.z = w[2]; o.w = w[3];
+        dst[s] = o;
+    }
+    RowMeta8 m; m.rnorm = v.rnorm[row]; m.rscale8 = scale; m.rres8 = bound8_row_res(bad, maxabs, n2, s2, v.dim);
+    v.rowmeta8[row] = m;
+}
 // The derived planes of n_tiles tiles, behind every write of rows and on its stream: the range [t0, t0 + n_tiles) when list is null, the
 // tiles list[0 .. n_tiles) (device memory, distinct) otherwise.  One body per plane either way: a tile is derived the same whoever asks.
 static hipError_t refresh_bf16(const IndexView& v, uint32_t t0, uint32_t n_tiles, const uint32_t* list, hipStream_t s) {
     if (v.rowmaj16) {                                                  // (never behind the rows either)
         const uint64_t total = (uint64_t)n_tiles * 64 * v.dim4;
         hipLaunchKernelGGL(k_rowmaj16, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, s, v, t0, n_tiles, list);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (v.rowmaj8 && v.rowmeta8) {                                     // (nor the 8-bit image and its records)
+        hipLaunchKernelGGL(k_rowmaj8, dim3(n_tiles), dim3(64), 0, s, v, t0, list);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

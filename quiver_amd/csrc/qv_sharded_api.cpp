@@ -550,7 +550,7 @@ int qv_sharded_create(qv_sharded** out, uint32_t dim, qv_metric metric, const in
     for (int g = 0; g < n_devices && rc == QV_OK; g++) {
         Shard& x = s->sh[(size_t)g];
         x.device = devices[g]; x.base = (uint32_t)g * s->span;
-        rc = qv_index_create(&x.idx, dim, metric, x.device, flags & (QV_FLAG_ROWMAJOR | QV_FLAG_BF16_ROWS | QV_FLAG_NO_SCAN_PLANE | QV_FLAG_L2_SCAN_PLANE | QV_FLAG_GRAPH_PLANE | QV_FLAG_NO_PLANE6));
+        rc = qv_index_create(&x.idx, dim, metric, x.device, flags & (QV_FLAG_ROWMAJOR | QV_FLAG_BF16_ROWS | QV_FLAG_NO_SCAN_PLANE | QV_FLAG_L2_SCAN_PLANE | QV_FLAG_GRAPH_PLANE | QV_FLAG_GRAPH_PLANE8 | QV_FLAG_NO_PLANE6));
     }
     if (rc == QV_OK && !s->rccl) {                                         // peer copies between distinct devices need peer access
         for (int g = 1; g < n_devices; g++) {

@@ -104,7 +104,7 @@ class DeviceIndex:
     default_filter = "auto"        # the filter kernel new indexes choose (set_filter); tests and bench.py compare the kernels through it
 
     def __init__(self, dim: int, metric="cosine", device: int = 0, rowmajor: bool = False, bf16_rows: bool = False, filter=None, scan_plane: bool = True, l2_scan_plane: bool = False,
-                 graph_plane: bool = False, plane6: bool = True):
+                 graph_plane: bool = False, plane6: bool = True, graph_plane8: bool = False):
         self._h = C.c_void_p()
         self.dim = int(dim)
         self.metric = metric_id(metric)
@@ -113,6 +113,7 @@ class DeviceIndex:
                                     (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE) |   # scan_plane=False: no default bfloat16 copy (cosine / dot), no bound scan
                                     (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0) |   # l2_scan_plane=True: an "l2" index keeps the planes cosine / dot keep by default
                                     (0 if plane6 else _lib.QV_FLAG_NO_PLANE6) |   # plane6=False: no 6-bit plane beside the 8-bit one
+                                    (_lib.QV_FLAG_GRAPH_PLANE8 if graph_plane8 else 0) |   # graph_plane8=True (with rowmajor): an int8 image in row order and a record per row for DeviceGraph.set_reject_image
                                     (_lib.QV_FLAG_GRAPH_PLANE if graph_plane else 0)))   # graph_plane=True (with rowmajor): a bfloat16 copy in row order for DeviceGraph.set_reject_plane
         f = filter if filter is not None else DeviceIndex.default_filter
         if f not in ("auto", 0):
@@ -473,16 +474,18 @@ class DeviceIndex:
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
     DEBUG_READ = {"rnorm": (0, np.float64), "rres": (1, np.float32), "plane": (2, np.uint16), "rowmaj16": (3, np.uint16),
-                  "plane6": (4, np.uint8), "rres6": (5, np.float32), "rscale8": (6, np.float32), "plane8": (7, np.uint8), "rres8": (8, np.float32)}
+                  "plane6": (4, np.uint8), "rres6": (5, np.float32), "rscale8": (6, np.float32), "plane8": (7, np.uint8), "rres8": (8, np.float32),
+                  "rowmaj8": (9, np.int8), "rowmeta8": (10, np.dtype([("rnorm", np.float64), ("rscale8", np.float32), ("rres8", np.float32)]))}
 
     def debug_read(self, what: str) -> np.ndarray:
         """FOR TESTS (qv_index_debug_read): one of the arrays ingest derives per row, as the device holds it — "rnorm" (float64 per row
         slot), "rres" (float32 per row slot) or "plane" (the bfloat16 copy as uint16 words in ITS layout: the caller decodes it) — over
-        the tiles in use; "rowmaj16": the row-order bfloat16 copy (graph_plane=True) as uint16 [rows, dim].  Raises
+        the tiles in use; "rowmaj16": the row-order bfloat16 copy (graph_plane=True) as uint16 [rows, dim]; "rowmaj8": the row-order
+        8-bit image (graph_plane8=True) as int8 [rows, dim]; "rowmeta8": its records, a structured array [rows] of rnorm, rscale8, rres8.  Raises
         QvError(QV_ERR_UNSUPPORTED) for an array this index does not keep."""
         code, dtype = self.DEBUG_READ[what]
-        if what == "rowmaj16":
-            out = np.empty((self.rows(), self.dim), dtype=dtype)
+        if what in ("rowmaj16", "rowmaj8", "rowmeta8"):
+            out = np.empty((self.rows(),) if what == "rowmeta8" else (self.rows(), self.dim), dtype=dtype)
             check(lib().qv_index_debug_read(self._h, code, out.ctypes.data, out.nbytes))
             return out
         tiles = (self.rows() + 63) // 64
@@ -773,6 +776,22 @@ class DeviceGraph:
         check(lib().qv_graph_reject_stats(self._g, out))
         return {"evals": int(out[0]), "rejected": int(out[1]), "queries": int(out[2]), "plane": bool(out[3])}
 
+    REJECT_IMAGE = {"auto": 0, "8bit": 1, "bf16": 2}
+
+    def set_reject_image(self, mode):
+        """which image a rejecting traversal starts on: "auto" (the 8-bit image only where the index holds it and it was measured faster: cosine, 768
+        dimensions, 1M to below 2M nodes, 8192 queries or more, list sizes 64 to 256), "8bit" (the row-order 8-bit image wherever it is held — DeviceIndex(..., rowmajor=True, graph_plane8=True) — else the
+        bfloat16 copy) or "bf16" (never the 8-bit image).  set_reject_plane keeps deciding whether a call rejects; results do not depend on
+        either (qv_graph_set_reject_image)."""
+        check(lib().qv_graph_set_reject_image(self._g, self.REJECT_IMAGE.get(mode, mode)))
+
+    def reject8_stats(self) -> dict:
+        """evaluations made in hops that rejected on the 8-bit image, those rejected on it, queries that finished unflagged in that form, and
+        whether the graph's index holds the image (qv_graph_reject8_stats; waits for the device)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_graph_reject8_stats(self._g, out))
+        return {"evals": int(out[0]), "rejected": int(out[1]), "queries": int(out[2]), "plane": bool(out[3])}
+
     def export(self):
         """(levels, l0_deg, l0_links [n, max_m0], up_off, up_links [blocks, 1 + max_m]) — the form qv_graph_create takes"""
         i = self.info()
@@ -839,11 +858,11 @@ class ShardedIndex:
     with peer_copy=True (point-to-point exchange instead of the collective)."""
 
     def __init__(self, dim: int, metric="cosine", devices=(0,), rowmajor: bool = False, peer_copy: bool = False, bf16_rows: bool = False, scan_plane: bool = True, l2_scan_plane: bool = False,
-                 graph_plane: bool = False):
+                 graph_plane: bool = False, graph_plane8: bool = False):
         self._h = C.c_void_p()
         self.dim = int(dim)
         devs = (C.c_int * len(devices))(*[int(d) for d in devices])
-        flags = (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_SHARDED_PEER_COPY if peer_copy else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) | (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE) | (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0) | (_lib.QV_FLAG_GRAPH_PLANE if graph_plane else 0)
+        flags = (_lib.QV_FLAG_ROWMAJOR if rowmajor else 0) | (_lib.QV_SHARDED_PEER_COPY if peer_copy else 0) | (_lib.QV_FLAG_BF16_ROWS if bf16_rows else 0) | (0 if scan_plane else _lib.QV_FLAG_NO_SCAN_PLANE) | (_lib.QV_FLAG_L2_SCAN_PLANE if l2_scan_plane else 0) | (_lib.QV_FLAG_GRAPH_PLANE if graph_plane else 0) | (_lib.QV_FLAG_GRAPH_PLANE8 if graph_plane8 else 0)
         check(lib().qv_sharded_create(C.byref(self._h), self.dim, metric_id(metric), devs, len(devices), flags))
 
     def close(self):
@@ -1026,6 +1045,17 @@ def graph_reject_applies(metric, dim: int, n_nodes: int, nq: int, ef_search: int
     if rc < 0:
         check(rc)
     return bool(rc)
+
+
+def graph_reject_image_applies(metric, dim: int, n_nodes: int, nq: int, ef_search: int, cus: int, mode="auto", has_plane: bool = True, has_tombstones: bool = False,
+                               max_m0: int = 32, has_image8: bool = True, image_mode="auto") -> int:
+    """the traversal dispatch's own rule: the form a DeviceGraph.search call of nq queries takes — 0 no rejecting form, 1 rejecting on the
+    row-order bfloat16 copy, 2 on the row-order 8-bit image (qv_graph_reject_image_applies)"""
+    rc = lib().qv_graph_reject_image_applies(metric_id(metric), dim, n_nodes, nq, ef_search, cus, DeviceGraph.REJECT_PLANE.get(mode, mode), 1 if has_plane else 0,
+                                             1 if has_tombstones else 0, max_m0, 1 if has_image8 else 0, DeviceGraph.REJECT_IMAGE.get(image_mode, image_mode))
+    if rc < 0:
+        check(rc)
+    return int(rc)
 
 
 def graph_batch_size(nodes_linked: int, batch_max: int, ramp_div: int) -> int:

@@ -24,6 +24,7 @@ class Config:                          # hnsw.go:27-41
     DistanceFunc: object = "hnsw_euclidean"
     Seed: int = 1                      # the reference: time.Now().UnixNano() (hnsw.go:248)
     GraphPlane: bool = False           # the device index also keeps the row-order bfloat16 copy (QV_FLAG_GRAPH_PLANE): large batches reject neighbours on it
+    GraphPlane8: bool = False          # ... and / or the row-order 8-bit image with a record per row (QV_FLAG_GRAPH_PLANE8): the flag bit only
 
 
 @dataclass
@@ -45,6 +46,8 @@ class HNSW:
         self._h = hlib().qvh_hnsw_new(_mid(c.DistanceFunc), device, c.M, c.MaxM0, c.EfConstruction, c.EfSearch, c.MaxLevel, c.Seed)
         if c.GraphPlane:
             hlib().qvh_hnsw_set_graph_plane(self._h, 1)
+        if c.GraphPlane8:
+            hlib().qvh_hnsw_set_graph_plane8(self._h, 1)
 
     def __del__(self):
         try:
