@@ -86,6 +86,34 @@ func newIndex(dim int, dev rows) *Index {
 // Close frees the device memory.  Needs exclusion against every other call (qv_index_destroy).
 func (x *Index) Close() { x.mu.Lock(); defer x.mu.Unlock(); x.dev.close() }
 
+// The modes of SetBoundScanWide (QV_BOUND_SCAN_*).
+const (
+	BoundScanAuto   = int(C.QV_BOUND_SCAN_AUTO)
+	BoundScanAlways = int(C.QV_BOUND_SCAN_ALWAYS)
+	BoundScanNever  = int(C.QV_BOUND_SCAN_NEVER)
+)
+
+// SetBoundScanWide (qv_index_set_bound_scan_wide): whether a single unfiltered Search or SearchWithNegative fetch of 65 to 1024 results
+// takes the bound scan's wide form — BoundScanAlways whenever the shape applies, BoundScanNever never, BoundScanAuto the measured shapes
+// (cosine and dot, k <= 1000, from 1M rows of 768 dimensions or 10M rows of 128).  Results are the exact path's either way.  One GPU only: the sharded handle keeps its paths and has no such setter.
+func (x *Index) SetBoundScanWide(mode int) error {
+	x.mu.Lock()
+	defer x.mu.Unlock()
+	d, ok := x.dev.(*oneGPU)
+	if !ok {
+		return errors.New("quivergpu: the wide bound scan is a one-GPU path; a sharded index has no such setter")
+	}
+	return d.setBoundScanWide(mode)
+}
+
+func (d *oneGPU) setBoundScanWide(mode int) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	if C.qv_index_set_bound_scan_wide(d.h, C.int(mode)) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
 // Insert implements core.Index (collection.go:80).  Error strings follow exact.go:45-50.
 func (x *Index) Insert(id string, v vectortypes.F32) error {
 	x.mu.Lock()

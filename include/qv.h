@@ -580,6 +580,40 @@ int qv_scan_bound6_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq,
 int qv_scan_quantize_row6(uint32_t dim, const float* row, float scale8, uint8_t* out_bytes, float* out_res);
 /* ... and those bytes back into the biased codes, out_codes[dim] in 0 .. 63. */
 int qv_scan_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes);
+/* ---- the wide form: 65 to 1024 results ----
+ * The single-query, unfiltered bound scan for 65 <= k <= 1024 (the k <= 64 form's metrics and widths: cosine, dot, QV_L2 indexes created
+ * with QV_FLAG_L2_SCAN_PLANE; a dimension that is a multiple of 16 up to 4096; 8 tiles or more; more live rows than results; an index of
+ * at most 64M rows).  Stage 1 is the k <= 64 form's, on the bfloat16 copy or the 8-bit plane, but publishes every wave's 64 smallest upper
+ * bounds; the threshold is the k-th smallest of their union — the upper bounds of k distinct live rows cap the k-th distance, so every row
+ * of the answer has its lower bound within it; it is the exact k-th smallest upper bound unless one wave's rows hold more than 64 of the
+ * k smallest, and only looser then.  The rows within it — at most QV_BOUND_WIDE_CAND_CAP — get their distances from the float32 rows in
+ * the scan's own arithmetic and a selection takes the k best.  Rows, float32 bits, (distance, row) order, counts and padding are the exact
+ * path's.  A search it cannot decide (more survivors than the list holds, fewer than k rows the bound is sure of, a query whose norm is
+ * not a number, huge or vanishing) goes from the 8-bit stage to the bfloat16 stage and from there to the key-per-row exact path, all
+ * decided on the device.  qv_index_search, qv_index_search_device and qv_index_search_negative reach it.
+ * `mode` takes the QV_BOUND_SCAN_* values.  ALWAYS: whenever the shape applies.  NEVER: never.  AUTO: the measured cells in which the wide
+ * form ran ahead of the exact path at every measured k (65, 100, 128, 129, 256, 1000) by more than both arms' spread
+ * (profiles/LAB_r24_bound_scan_wide.md, tests/bench/bench_bound_scan_wide.py; 1M, 3M and 10M x 768 and 10M x 128, cosine — every one of
+ * them): cosine and dot indexes, k <= 1000, from 1 000 000 rows of 768 dimensions or more and from 10 000 000 rows of 128 to 767
+ * dimensions.  NOT measured and therefore never automatic: fewer than 1M rows, fewer than 128 dimensions, 128 to 767 dimensions below
+ * 10M rows, k above 1000, QV_L2 indexes with the planes; ALWAYS reaches the path there.  Independent of qv_index_set_bound_scan, whose
+ * rule (qv_scan_bound_applies) keeps saying no above k = 64.  Which plane comes first follows qv_index_set_bound_plane:
+ * QV_BOUND_PLANE_8BIT the 8-bit plane where it is held, QV_BOUND_PLANE_BF16 the bfloat16 copy, QV_BOUND_PLANE_AUTO the 8-bit plane in
+ * the cells where it also beat the bfloat16 copy first by the same standard (all of the cells above), the bfloat16 copy elsewhere.
+ * The environment variable QV_BOUND_SCAN_WIDE (1 always, 2 never; read once per process) sets the default of indexes that never call this.
+ * Out of scope and unchanged: shared passes of 2 or more queries, the filtered forms (masks, row sets, where-filters), the 6-bit plane,
+ * k > 1024, and the sharded handle (qv_sharded_* keeps its paths; there is no sharded setter). */
+#define QV_BOUND_WIDE_CAND_CAP 8192   /* rows the wide form's re-score walks at most: 1024 + 4032 (the k <= 64 form's spare over its largest k) and room to the next power of two */
+int qv_index_set_bound_scan_wide(qv_index* idx, int mode);
+/* out[0] = survivors passed to the re-score in the last wide search, out[1] = searches handed back to the exact path so far, out[2] =
+ * searches that took the wide form so far, out[3] = 1 when the index holds the bfloat16 copy.  Waits for the device.
+ * qv_index_bound_scan_stats, qv_index_bound_scan8_stats and qv_index_bound_scan6_stats do not move for wide searches. */
+int qv_index_bound_scan_wide_stats(qv_index* idx, uint64_t out[4]);
+/* Whether a search would take the wide form — the dispatch's own rule, on the host (the dispatch adds what only the index knows: more
+ * LIVE rows than results).  metric as qv_scan_bound_applies takes it, QV_RULE_L2_PLANES included; wide_mode: QV_BOUND_SCAN_*;
+ * plane_mode: QV_BOUND_PLANE_*; has_plane / has_plane8: the index holds the bfloat16 copy / the 8-bit plane.
+ * 0: no wide form; 1: the bfloat16 copy first; 2: the 8-bit plane first; < 0 on an error (an unknown mode). */
+int qv_scan_bound_wide_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, int has_plane, int has_plane8);
 /* ---- the 8-bit stage under a filter ----
  * Which plane serves a single FILTERED query's bound scan first: qv_index_search_masked, qv_index_search_rowsets and
  * qv_index_search_where with one query, their device forms, and a shared pass of the row-set front that holds one caller — at
@@ -723,7 +757,8 @@ int qv_scan_route_ex(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint3
 #define QV_WS_FLAT 12             /* the fused flat search */
 #define QV_WS_ROWSETS_CALL 13     /* the row-set workspace with the call's candidate bitmap behind it */
 #define QV_WS_WHERE_CALL 14       /* ... with the candidate bitmap and the transient sets behind it */
-#define QV_WS_FLAT_PLAIN 0        /* query blocks, or the matrix-core scan's block */
+#define QV_WS_BOUND_WIDE 15       /* the single-query bound scan's wide form, 65 <= k <= 1024; its exact redo's workspace is an alias over the rest */
+#define QV_WS_FLAT_PLAIN 0       /* query blocks, or the matrix-core scan's block */
 #define QV_WS_FLAT_BOUND 1        /* ... or the single-query bound scan's buffer */
 #define QV_WS_FLAT_BOUND_MQ 2     /* ... and the shared bound pass, which has the workspace to itself */
 int qv_scan_workspace_layout(int kind, int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int cus, uint32_t flags,

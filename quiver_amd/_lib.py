@@ -26,6 +26,8 @@ QV_DEBUG_PLANE8, QV_DEBUG_RRES8 = 7, 8
 QV_FLAG_NO_PLANE6 = 32         # no 6-bit plane beside the 8-bit one (dim * 0.75 + 4 bytes per row)
 QV_RULE_L2_PLANES = 0x101      # such an index, as the qv_scan_* rule functions take it where they take a metric
 QV_BOUND_SCAN_AUTO, QV_BOUND_SCAN_ALWAYS, QV_BOUND_SCAN_NEVER = 0, 1, 2
+QV_BOUND_WIDE_CAND_CAP = 8192  # rows the wide bound scan's re-score walks at most (65 <= k <= 1024)
+QV_WS_BOUND_WIDE = 15          # qv_scan_workspace_layout: the wide bound scan's buffer
 QV_FILTERED_BATCH_AUTO, QV_FILTERED_BATCH_ALWAYS, QV_FILTERED_BATCH_NEVER = 0, 1, 2
 QV_COL_F64, QV_COL_U32 = 0, 1
 QV_SET_AND, QV_SET_OR, QV_SET_ANDNOT = 0, 1, 2
@@ -124,6 +126,9 @@ PROTOTYPES = {
     "qv_index_set_bound_plane6": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_sharded_set_bound_plane6": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_bound_scan6_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_index_set_bound_scan_wide": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_bound_scan_wide_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_scan_bound_wide_route": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]),
     "qv_scan_bound6_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "qv_scan_quantize_row6": (C.c_int, [C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, _f32p]),
     "qv_scan_unpack_row6": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -593,6 +593,16 @@ static void profile_end(qv_index* idx, const ProfilePair& p, bool launched, bool
     (void)hipEventDestroy(p.ev0); (void)hipEventDestroy(p.ev1);
 }
 
+// Whether a search of list length kk takes the bound scan's wide form (65 <= kk <= 1024), for the launch (enqueue_search) and for the
+// workspace (search_ws_bytes): 0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.  One unfiltered query whose call carries the
+// stream's ticket words, kk == k_stride, and fewer results than live rows (a k above the live rows keeps its path); the rest is
+// qv::bound_wide_route's answer under the index's two knobs.
+static int wide_route(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, bool filtered) {
+    if (nq != 1 || kk != k_stride || !tickets || filtered || kk >= idx->n_live) return 0;
+    const int metric = idx->l2_planes() ? QV_RULE_L2_PLANES : idx->metric;
+    return qv::bound_wide_route(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide, idx->bound.plane[qv::bound_one], idx->d_bf16 != nullptr, idx->d_plane8 != nullptr);
+}
+
 // what a call may hand enqueue_search beside its queries and outputs
 struct SearchExtras {
     const uint64_t* d_candidates = nullptr;   // row bitmap replacing the tombstone bitmap (filtered search)
@@ -619,6 +629,15 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
                                             x.flag_used, fp.bound() ? idx->d_bound_stats : nullptr, cand_tiles);
         profile_end(idx, pp, e == hipSuccess);
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "%s scan launch failed: %s", fp.route == qv::FlatRoute::small ? "small" : "flat", hipGetErrorString(e));
+        return QV_OK;
+    }
+    // 65 <= k <= 1024, one unfiltered query, where the wide form's rule takes it: the bound scan on the reduced copies, its re-score and
+    // selection, and the gated key-per-row redo behind them — all enqueued by the one launcher
+    if (const int wide = wide_route(idx, nq, kk, k_stride, x.d_tickets != nullptr, x.d_candidates != nullptr)) {
+        const ProfilePair pp = profile_begin(idx, true, s);
+        hipError_t e = qv::launch_bound_scan_wide(v, plan, d_queries, kk, ws, x.d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, d_rows_out, d_dist_out, s, wide == 2);
+        profile_end(idx, pp, e == hipSuccess, true, s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "wide bound scan launch failed: %s", hipGetErrorString(e));
         return QV_OK;
     }
     // 64 < k <= 8192 (the negative-example branches fetch max(2k, 30), hybrid_index.go:516-522; BatchSearch takes any k,
@@ -655,6 +674,7 @@ static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uin
                               : fp.route == qv::FlatRoute::bound || fp.route == qv::FlatRoute::bound8_first ? qv::FlatWs::call_bound : qv::FlatWs::call;
         return qv::flat_layout(nullptr, what, plan, nq, kk, n_tiles, idx->dim).total;
     }
+    if (wide_route(idx, nq, kk, k_stride, tickets, cand_tiles != qv::kBoundNoFilter)) return qv::bound_scan_wide_workspace_bytes(plan, kk, n_tiles, idx->dim);
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
     return qv::full_sort_workspace_bytes(n_tiles);
@@ -951,11 +971,16 @@ int qv_index_search_negative(qv_index* idx, const float* query, const float* neg
     const uint32_t kk = std::min(k_fetch, idx->n_live);
     HostCall hc(idx);
     int rc;
-    if ((rc = hc.open()) || (rc = hc.reserve(2, 1, kk, 2)) || (rc = hc.workspace(search_ws_bytes(idx, 1, kk, kk, false)))) return rc;
+    // (the context's ticket words only where the wide bound scan takes the fetch — max(2k, 30) results, so every k >= 33: without them
+    //  every path is the one this call has always taken)
+    const bool wide = wide_route(idx, 1, kk, kk, true, false) != 0;
+    if ((rc = hc.open()) || (rc = hc.reserve(2, 1, kk, 2)) || (rc = hc.workspace(search_ws_bytes(idx, 1, kk, kk, wide)))) return rc;
+    SearchExtras x;
+    if (wide && (rc = hc.tickets(&x.d_tickets))) return rc;
     hc.stage(query, 1);
     hc.stage(negative, 1, 1);
     if ((rc = hc.send(2))) return rc;
-    rc = enqueue_search(idx, hc.d_queries(), 1, kk, kk, hc.ws(), hc.d_rows(), hc.d_dist(), hc.stream());
+    rc = enqueue_search(idx, hc.d_queries(), 1, kk, kk, hc.ws(), hc.d_rows(), hc.d_dist(), hc.stream(), x);
     if (rc != QV_OK) return rc;
     hipError_t e = qv::launch_distance_rows(idx->view(), hc.d_queries() + idx->dim, hc.d_rows(), kk, hc.d_dist() + kk, hc.stream());   // the second plane: the distances to the negative example
     if (e != hipSuccess) return fail(QV_ERR_DEVICE, "distance_rows launch failed: %s", hipGetErrorString(e));
@@ -2047,6 +2072,29 @@ int qv_index_bound_scan6_stats(qv_index* idx, uint64_t out[4]) {
     return QV_OK;
 }
 
+int qv_index_set_bound_scan_wide(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    idx->bound_wide = mode;
+    return QV_OK;
+}
+
+int qv_index_bound_scan_wide_stats(qv_index* idx, uint64_t out[4]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t h[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kBoundWideStatsWord, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = idx->d_bf16 != nullptr ? 1 : 0;
+    return QV_OK;
+}
+
+int qv_scan_bound_wide_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, int has_plane, int has_plane8) {
+    if (wide_mode < 0 || wide_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mode);
+    if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
+    return qv::bound_wide_route(metric, dim, rows, nq, k, wide_mode, plane_mode, has_plane != 0, has_plane8 != 0);
+}
+
 // The six rule exports: views of the one decision (qv::bound_scan_decide) for a call given without an index.  form: the form the export
 // speaks for (it says no to any other; -1: whichever the call has); want: the stage asked after — plane8_first, or any stage at all.  The
 // 8-bit rules are asked with the bfloat16 copy held; a filtered rule takes every candidate count as a count.
@@ -2198,6 +2246,7 @@ int qv_scan_workspace_layout(int kind, int metric, uint32_t dim, uint64_t rows, 
     switch (kind) {
         case QV_WS_BOUND:            (void)qv::bound_scan_workspace_bytes(p, k, n_tiles, &log); break;
         case QV_WS_BOUND_MQ:         (void)qv::bound_scan_mq_workspace_bytes(p, nq, k, n_tiles, dim, &log); break;
+        case QV_WS_BOUND_WIDE:       (void)qv::bound_scan_wide_workspace_bytes(p, k, n_tiles, dim, &log); break;
         case QV_WS_REDO:             (void)qv::redo_workspace_bytes(p, nq, k, &log); break;
         case QV_WS_SELECT:           (void)qv::select_workspace_bytes(nq, k, &log); break;
         case QV_WS_FLAT_WIDE:        (void)qv::flat_wide_workspace_bytes(p, nq, k, &log); break;

@@ -106,6 +106,7 @@ struct qv_index {
     uint16_t* d_bf16 = nullptr;                // the bfloat16 copy (QV_FLAG_BF16_ROWS, and by default on cosine / dot indexes): refreshed by every call that writes rows
     bool plane_lost = false;                   // the default copy could not be allocated: the index carries on without it
     qv::BoundKnobs bound = {};                 // qv_index_set_bound_scan, and by qv::BoundForm the four qv_index_set_bound_plane*
+    int bound_wide = 0;                        // qv_index_set_bound_scan_wide: QV_BOUND_SCAN_* for the wide form (65 <= k <= 1024), a knob of its own
     int8_t* d_plane8 = nullptr;                // the int8 copy and its row state (scale, residual): kept with the default bfloat16 copy, refreshed with it
     float* d_rscale8 = nullptr;
     float* d_rres8 = nullptr;

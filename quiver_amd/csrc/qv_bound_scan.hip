@@ -1,12 +1,14 @@
 // qv_bound_scan.hip — the bound scan: a fused flat search (k <= 64; cosine, dot, or a Euclidean index created with QV_FLAG_L2_SCAN_PLANE) answered from the index's reduced copies of the rows — the
 // bfloat16 copy, with the 8-bit plane in front of it for one query and for a shared pass of 2 - 8, each unfiltered or filtered — by rejecting
 // rows on a certified interval of the distance (qv_bound.h) and re-scoring the few survivors in the exact scan's arithmetic.  One query, the shared
-// pass of 2 - 8, their filtered forms;
+// pass of 2 - 8, their filtered forms; the wide form of one unfiltered query for 65 to 1024 results (bound_scan_tail_wide, k_bound_collect_wide,
+// k_bound_rescore_wide, launch_bound_scan_wide);
 // the rules that say when each applies; the launchers and workspace sizes; the interval and the 8-bit row state compiled for the host.
 // Which search takes the path is decided by plan_flat (qv_scan.hip); the exact scan that answers what a bound pass hands back
 // (k_flat_scan<., ., true> behind its gate, launch_flat_redo_flagged) and the list merge (launch_merge_lists) live there too.
 #include "qv_kernels.h"
 #include "qv_bound.h"
+#include <stdio.h>
 
 namespace qv {
 
@@ -108,11 +110,29 @@ __device__ __forceinline__ bool bound_scan_tail(uint64_t list, uint64_t thr, uin
     return true;
 }
 
+// The WIDE form's tail (k_bound_scan<., false, true>, k_bound_scan8<., false, true>: one unfiltered query, 65 <= k <= kBoundWideMaxK).  The
+// scan runs with a list length of 64, so a wave ends holding the 64 smallest upper bounds of ITS rows, and every wave's list is published as
+// it stands — [grid][kScanWaves][64] keys, dead keys where a wave saw fewer than 64 live rows — without a merge down to k: the in-wave list
+// and merge_lists_last_workgroup hold 64 keys and do not stretch to 1024.  H is then the k-th smallest key of the UNION of the published
+// lists (launch_select_topk behind this launch; k_bound_collect_wide reads its k-th output).
+//   Certified: the published keys are upper bounds of k DISTINCT live rows (a row is in one wave's list only), and any k live rows' upper
+//   bounds cap the k-th distance — the k-th smallest distance is at most the largest of any k rows' distances, each at most its upper
+//   bound.  So every row of the answer has d_lo <= d <= H.
+//   Exact where it can be: the k smallest upper bounds overall are all published whenever no single wave holds more than 64 of them — a
+//   wave drops only keys larger than its own 64 smallest —, and then H IS the k-th smallest upper bound, the H the k <= 64 form computes.
+//   When one wave's rows hold more than 64 of the k smallest (the nearest rows stored together in tiles of one wave), the dropped ones are
+//   replaced by larger published keys: H is only LOOSER, never too small, and the collect passes a few more rows on.
+//   Fewer than k published live keys (fewer than k rows the bound is sure of): the k-th key is dead, there is no H, the search is handed on.
+// No ticket, no last workgroup: every slot of `lists` is written by its own wave in every launch (the workspace is reused).
+__device__ __forceinline__ void bound_scan_tail_wide(uint64_t list, uint32_t wave, uint32_t lane, uint64_t* __restrict__ lists /* [grid][kScanWaves][64] */) {
+    lists[((size_t)blockIdx.x * kScanWaves + wave) * 64 + lane] = list;
+}
+
 // SKIP (k_bound_scan<., true>: v.alive is a filter's candidate bitmap, alive & set — k_rowset_and's or the masked upload): a tile whose word is
 // zero is not requested, neither its copy nor rnorm nor rres.  Its 64 lower-bound words are WRITTEN as 0xFFFFFFFF all the same: k_bound_collect
 // reads every word and the workspace is reused, so an unwritten tile would hold an earlier search's bounds; 256 bytes stored against dim * 128
 // bytes not read, and the collect stays as it is.  |q|^2 rides along the first tile the wave READS; a wave that reads none publishes a dead list.
-template <int M, bool SKIP = false>
+template <int M, bool SKIP = false, bool WIDE = false /* k = 64 is the list length; the tail publishes the waves' lists (bound_scan_tail_wide) */>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
              uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist,
@@ -175,7 +195,8 @@ k_bound_scan(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl
         for (; t < v.n_tiles; t += tw) finish_tile(t, bound_tile<false>(plane + (size_t)t * steps * 128, q_lds, steps, nullptr), false);
     }
 
-    (void)bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
+    if constexpr (WIDE) bound_scan_tail_wide(list, wave, lane, partial);
+    else (void)bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
 }
 
 // the rows with d_lo <= H, eight per thread and step, a chunk of 2048 words per workgroup and step (lo: one query's ordered words; cnt: its
@@ -581,7 +602,7 @@ __device__ __forceinline__ void bound8_stage_query(const float* __restrict__ que
 // walks and has the next one's in flight behind that tile's bytes; a tile whose word is zero is not requested — plane, rnorm, rscale8, rres8 —
 // and its 64 lower-bound words are written as 0xFFFFFFFF (k_bound_collect reads every word of a reused workspace).  The query's scale, terms
 // and norm are the workgroup's, computed before the walk, so a wave that reads no tile just publishes a dead list.
-template <int M, bool SKIP = false>
+template <int M, bool SKIP = false, bool WIDE = false /* as k_bound_scan's */>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_scan8(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ lo_all /* [n_tiles * 64] */,
               uint64_t* __restrict__ partial /* [grid][k] */, uint32_t* __restrict__ seed_rows, float* __restrict__ seed_dist) {
@@ -624,7 +645,8 @@ k_bound_scan8(IndexView v, const float* __restrict__ query, uint32_t k, BoundCtr
         if (first) { list = wave_sort64(key, lane); thr = readlane64(list, kth); first = false; }
         else list_insert(list, thr, key, kth, lane);
     }
-    (void)bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
+    if constexpr (WIDE) bound_scan_tail_wide(list, wave, lane, partial);
+    else (void)bound_scan_tail(list, thr, wl, wave, lane, k, ctrl, partial, seed_rows, seed_dist);
 }
 
 // ---------------------------------------------------------------- one unfiltered query: reject rows on the 6-bit plane first --
@@ -819,6 +841,132 @@ k_bound_refine8(IndexView v, const BoundQuery8* __restrict__ qst, uint32_t k, Bo
         *n8 = (ns + (uint32_t)kRefineBatch - 1u) / (uint32_t)kRefineBatch * (uint32_t)kRefineBatch;
         ctrl6->cand_cnt = 0; ctrl6->thr_inv = 0;                       // zero, as the words are kept
     }
+}
+
+// ---------------------------------------------------------------- one unfiltered query, 65 <= k <= 1024: the wide form --
+// The k <= 64 form stops at 64 because stage 1 keeps its upper bounds in a wave list of one key per lane and its re-score merges such lists;
+// interval, collect and the exact chain do not depend on k.  The wide form keeps both scan kernels up to their tail and replaces the rest:
+//   k_bound_scan<., false, true> / k_bound_scan8<., false, true>   the walk with a list length of 64; the tail publishes every wave's list
+//                    (bound_scan_tail_wide, where the argument for H stands).
+//   launch_select_topk   the k smallest of the grid x kScanWaves x 64 published keys, sorted: its k-th output is H.
+//   k_bound_collect_wide bound_collect against that H with a list of QV_BOUND_WIDE_CAND_CAP rows; workgroup 0 leaves H in the control words
+//                    (thr_inv, zero = no finite H) for the re-score, as the k <= 64 tail does.
+//   k_bound_rescore_wide a wave per survivor in k_bound_rescore's chain — the exact scan's bits — writing the (distance, row) key into
+//                    keys[slot], dead keys into the slots past the count; the last workgroup (a ticket) decides hand-back, writes the
+//                    counters, the flags and sel[] = {live keys, 1 = answered}.
+//   launch_select_topk_counted   the k best of keys[0 .. count) in (distance, row) order into the caller's arrays — behind sel[1]: zero = it
+//                    leaves the arrays alone.  ONE such launch ends the call, whichever stage answered.
+// Handing on, on the device: the list overflowed, there is no finite H, or bound_scan_norm_ok declines |q|.  The 8-bit stage hands on to the
+// bfloat16 stage, whose four launches are gated on that stage's flag word; the bfloat16 stage hands on to the key-per-row path behind ITS flag
+// (launch_flat_select_redo_one; the caller enqueues nothing more).  The counters are the wide form's own (kBoundWideStatsWord): the k <= 64
+// form's, the 8-bit and the 6-bit stage's do not move.
+constexpr uint32_t kBoundWideCandCap = QV_BOUND_WIDE_CAND_CAP;
+static_assert(kBoundWideCandCap >= kBoundWideMaxK + (kBoundCandCap - (uint32_t)kMaxFusedK), "the spare the k <= 64 form has over its largest k, kept at the largest wide k");
+static_assert(kBoundWideCandCap <= 16384u && kBoundWideCandCap % kCollectChunk == 0, "launch_select_topk_counted takes 16384 keys at most");
+constexpr uint32_t kBoundWideRescoreGrid = 256;   // 1024 waves: a thousand survivors in one round, a full list in eight
+constexpr uint32_t kBoundWideListLen = 64;        // stage 1's list length: one key per lane
+
+__global__ void __launch_bounds__(256)
+k_bound_collect_wide(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple of 64 */, uint32_t k, const uint32_t* __restrict__ seed_rows, const float* __restrict__ seed_dist /* [k] sorted */,
+                     BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand, const uint32_t* __restrict__ gate /* as k_bound_scan's */) {
+    if (gate != nullptr && *gate == 0u) return;
+    const uint32_t H = ord_f32(seed_dist[k - 1]);
+    const bool has_H = seed_rows[k - 1] != 0xFFFFFFFFu && H < 0xFF800000u;   // the k-th published key is a row's, and its bound finite
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->thr_inv = has_H ? ~H : 0u;   // (the re-score behind reads it; cand_cnt is zero: the words are kept so)
+    if (!has_H) return;
+    bound_collect(lo_all, n, H, &ctrl->cand_cnt, cand, kBoundWideCandCap);
+}
+
+// P8: the re-score behind the 8-bit stage (ctrl = that stage's words, next = the bfloat16 stage's): it answers — and clears the bfloat16 stage's
+// flag for the redo behind —, or sets its own flag, the word the bfloat16 stage's launches are gated on.  gate (the bfloat16 stage behind the
+// 8-bit one): as k_bound_rescore's.  keys [kBoundWideCandCap]; sel: [0] the live keys in front of keys[], [1] 1 = a stage has answered.
+template <int M, bool P8>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_rescore_wide(IndexView v, const float* __restrict__ query, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand, uint32_t* __restrict__ stats,
+                     uint64_t* __restrict__ keys, uint32_t* __restrict__ sel, uint32_t* gate, BoundCtrl* next) {
+    if (gate != nullptr && *gate == 0u) return;
+    using Q = typename MT<M>::Q;
+    extern __shared__ __align__(16) unsigned char smem[];
+    Q* q_lds = reinterpret_cast<Q*>(smem);
+    const size_t q_bytes = (((size_t)v.dim4 * 4 * sizeof(Q)) + 15) / 16 * 16;
+    float* rbuf = reinterpret_cast<float*>(smem + q_bytes);           // [kScanWaves][dim4 * 4]: a wave's survivor
+    __shared__ double s_qn;
+    __shared__ uint32_t s_last;
+    const uint32_t cnt = ctrl->cand_cnt, thr_inv = ctrl->thr_inv;
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool decided_early = cnt > kBoundWideCandCap || thr_inv == 0u;   // (handed on whatever |q| is: nothing to walk)
+    const uint32_t ns = decided_early ? 0u : cnt;
+    // as in k_bound_rescore: the workgroups without a survivor only take their ticket, unless they draw the last one
+    const uint32_t active = std::max(1u, std::min((uint32_t)gridDim.x, (ns + kScanWaves - 1) / kScanWaves));
+    const bool idle = blockIdx.x >= active;
+    if (idle) {
+        if (threadIdx.x == 0) s_last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;   // (behind this workgroup's reads of ctrl and the gate)
+        __syncthreads();
+        if (!s_last) return;
+    }
+    stage_query<M>(q_lds, query, v.dim, v.dim4);
+    __syncthreads();
+    if (wave == kScanWaves - 1) {
+        // |q| as the reference's chain (distances.go:20): cosine's finalize takes it, and every metric's hand-back rule
+        double ma = 0.0;
+        for (uint32_t i = 0; i < v.dim; i++) { const double a = (double)q_lds[i]; ma = __builtin_fma(a, a, ma); }
+        if (lane == 0) s_qn = __builtin_sqrt(ma);
+    }
+    __syncthreads();
+    const double qn = s_qn;
+    const bool hand_back = decided_early || !bound_scan_norm_ok(qn, v.dim);   // (the same in every workgroup)
+    if (!hand_back && !idle) {
+        QConst qc; qc.qn = 0.0; qc.qn32 = 0.0f;
+        if constexpr (M == QV_COSINE) qc.qn = qn;
+        const f4* tiles = reinterpret_cast<const f4*>(v.tiles);
+        f4* mine = reinterpret_cast<f4*>(rbuf + (size_t)wave * v.dim4 * 4);
+        for (uint32_t i = blockIdx.x * kScanWaves + wave; i < ns; i += active * kScanWaves) {   // (wave-uniform)
+            const uint32_t row = cand[i];
+            const f4* src = tiles + (size_t)(row >> 6) * v.dim4 * 64 + (row & 63);
+            double rn = 0.0;
+            if constexpr (MT<M>::needs_rnorm) rn = v.rnorm[row];
+            for (uint32_t c0 = 0; c0 < v.dim4; c0 += 256) {
+                f4 x[4];
+#pragma unroll
+                for (uint32_t u = 0; u < 4; u++) { const uint32_t c = c0 + u * 64 + lane; if (c < v.dim4) x[u] = __builtin_nontemporal_load(&src[(size_t)c * 64]); }
+#pragma unroll
+                for (uint32_t u = 0; u < 4; u++) { const uint32_t c = c0 + u * 64 + lane; if (c < v.dim4) mine[c] = x[u]; }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the wave's own LDS writes before its reads of other lanes' chunks
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            typename MT<M>::A acc = 0;
+            for (uint32_t c = 0; c < v.dim4; c++) {                    // ONE chain, element order: row_accumulate's
+                const f4 r = mine[c];
+                const Q* qq = q_lds + (size_t)c * 4;
+                acc1<M>(acc, qq[0], r.x); acc1<M>(acc, qq[1], r.y); acc1<M>(acc, qq[2], r.z); acc1<M>(acc, qq[3], r.w);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // ... and those reads before the next survivor's writes
+            __builtin_amdgcn_wave_barrier();
+            if (lane == 0) keys[i] = make_key(finalize<M>(acc, qc, rn), row);
+        }
+        // the slots past the count: dead keys, whatever an earlier search left there
+        for (uint32_t i = ns + blockIdx.x * kScanBlock + threadIdx.x; i < kBoundWideCandCap; i += active * kScanBlock) keys[i] = kDeadKey;
+    }
+    __syncthreads();
+    if (!idle) {
+        if (threadIdx.x == 0) s_last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;   // (behind this workgroup's reads of ctrl and the gate)
+        __syncthreads();
+    }
+    if (!s_last || threadIdx.x != 0) return;
+    ctrl->ticket = 0;                                                  // for the next launch on these words (stream order)
+    if constexpr (P8) {
+        if (!hand_back) { stats[kBoundWideStatsWord] = cnt; (void)atomicAdd(&stats[kBoundWideStatsWord + 2], 1u); next->flag = 0u; }
+    } else {
+        stats[kBoundWideStatsWord] = cnt;
+        if (hand_back) (void)atomicAdd(&stats[kBoundWideStatsWord + 1], 1u);
+        (void)atomicAdd(&stats[kBoundWideStatsWord + 2], 1u);
+        if (gate != nullptr) *gate = 0u;                               // (every workgroup read it before it took its ticket)
+    }
+    ctrl->flag = hand_back ? 1u : 0u;                                  // the launches behind this one read it
+    sel[0] = hand_back ? 0u : ns; sel[1] = hand_back ? 0u : 1u;
+    ctrl->cand_cnt = 0; ctrl->thr_inv = 0;                             // zero, as the words are kept
 }
 
 // ---------------------------------------------------------------- the bound scan as a shared pass: 2 - 8 queries over the bfloat16 copy --
@@ -1565,6 +1713,118 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
     if (e != hipSuccess) return e;
     *gate_out = &ctrl->flag;
     return hipGetLastError();
+}
+// ---- the wide form (65 <= k <= kBoundWideMaxK): its rule, its buffer, its launches ----
+// The rule is the wide form's own: bound_scan_decide keeps answering none above kMaxFusedK (qv_scan_bound_applies(., k = 65, ALWAYS, .) == 0 is
+// pinned by tests), and the knob is independent of qv_index_set_bound_scan.  NEVER, or a call the kernels cannot serve -> 0.  ALWAYS -> the
+// wide form; the 8-bit plane first under QV_BOUND_PLANE_8BIT where it is held, the bfloat16 copy first otherwise.
+// AUTOMATIC: the cells of profiles/LAB_r24_bound_scan_wide.md in which the wide form ran ahead of the exact path (k_flat_scan_wide up to
+// k = 128, the key-per-row path above) at EVERY measured k — 65, 100, 128, 129, 256, 1000 — by more than both arms' spread, and the 8-bit
+// plane first only where it also beat the bfloat16 copy first by the same standard; cosine, device-pointer calls, five alternating rounds
+// of 20 calls.  us per call, exact / bfloat16 first / 8-bit first (survivors bfloat16 / 8-bit), spreads <= 18 us:
+//   768 dims   1M   k 65: 482 / 313 / 243 (88 / 285)      k 128: 493 / 320 / 257 (194 / 546)    k 1000: 501 / 352 / 301 (1 363 / 3 180)
+//              3M   k 65: 1342 / 768 / 487 (101 / 313)    k 128: 1351 / 774 / 489 (176 / 585)   k 1000: 1396 / 808 / 541 (1 395 / 3 584)
+//              10M  k 65: 4340 / 2416 / 1323 (97 / 320)   k 128: 4350 / 2421 / 1326 (197 / 621) k 1000: 4424 / 2447 / 1371 (1 431 / 4 047)
+//   128 dims   10M  k 65: 778 / 482 / 323 (70 / 114)      k 128: 801 / 488 / 329 (158 / 254)    k 1000: 803 / 508 / 348 (1 179 / 1 759)
+// No cell lost, in either comparison.  NOT measured, so never automatic: fewer than 1M rows; narrower than 128 dimensions; 128 <= dim < 768
+// below 10M rows (nothing between the widths was measured: the other rules' two width classes); k above 1000; QV_L2 indexes with the
+// planes (cosine was measured; dot runs the same kernels over the same bytes and differs in the finalize alone).
+constexpr BoundFloor kBoundWideFloor = {1000000, 128, 10000000};      // the wide form against the exact path
+constexpr BoundFloor kBoundWide8Floor = {1000000, 128, 10000000};     // ... and the 8-bit plane first against the bfloat16 copy first
+constexpr uint32_t kBoundWideAutoMaxK = 1000;                         // the largest measured k
+static bool bound_wide_auto(const BoundFloor& f, int rule_metric, uint32_t dim, uint32_t rows, uint32_t k) {
+    const uint32_t floor = dim >= kBoundWideDim ? f.wide_rows : f.narrow_dim != 0 && dim >= f.narrow_dim ? f.narrow_rows : 0u;
+    return floor != 0 && rows >= floor && k <= kBoundWideAutoMaxK && (rule_metric == QV_COSINE || rule_metric == QV_DOT);
+}
+int bound_wide_route(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, bool has_plane, bool has_plane8) {
+    static const int env_wide = env_int("QV_BOUND_SCAN_WIDE", 0);
+    const int mode = wide_mode ? wide_mode : env_wide;
+    if (mode == 2) return 0;
+    // what the kernels need: one query, the list lengths behind the wave list, the k <= 64 form's metrics and widths, the copy, 8 tiles, more
+    // rows than results (a k that takes every row has nothing to reject), and room for the redo's two key planes
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)rows + 63) / 64);
+    const bool metric_ok = rule_metric == QV_COSINE || rule_metric == QV_DOT || rule_metric == QV_RULE_L2_PLANES;
+    if (nq != 1 || k <= (uint32_t)kMaxFusedK || k > kBoundWideMaxK || !metric_ok || !has_plane) return 0;
+    if ((dim & 15u) != 0 || dim == 0 || dim > kBoundMaxDim || n_tiles < 8 || k >= rows || !flat_select_redo_one_serves(n_tiles)) return 0;
+    if (mode != 1 && !bound_wide_auto(kBoundWideFloor, rule_metric, dim, rows, k)) return 0;
+    const int plane = bound_plane_mode(bound_one, plane_mode);
+    if (plane == 2 || !has_plane8) return 1;
+    return plane == 1 || bound_wide_auto(kBoundWide8Floor, rule_metric, dim, rows, k) ? 2 : 1;
+}
+// the wide form's buffer.  The redo's workspace overlays the rest: it is written only when every bound stage has ended.
+struct BoundWideLayout { void* redo; uint64_t* lists; uint32_t* seed_rows; float* seed_dist; void* sel_ws; uint32_t* cand; uint64_t* keys; uint32_t* sel; uint32_t* lo_all; size_t end, total; };
+static BoundWideLayout bound_wide_layout(void* base, const ScanPlan& p, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    BoundWideLayout L{};
+    WsCarver o = w.overlay();
+    L.redo = o.take<char>(flat_select_redo_one_workspace_bytes(n_tiles, k, dim, (dim + 3) / 4));   // the exact redo of a search handed back (an alias)
+    L.lists = w.take256<uint64_t>((size_t)p.grid * kScanWaves * kBoundWideListLen);   // stage 1's published wave lists
+    L.seed_rows = w.take256<uint32_t>(k);                             // the k smallest published upper bounds' rows ...
+    L.seed_dist = w.take256<float>(k);                                // ... and values, sorted: the k-th is H
+    L.sel_ws = w.take256<char>(select_workspace_bytes(1, k));         // that selection's workspace
+    L.cand = w.take<uint32_t>(kBoundWideCandCap);                     // survivors the re-score walks
+    L.keys = w.take<uint64_t>(kBoundWideCandCap);                     // their exact keys, dead keys behind
+    L.sel = w.take<uint32_t>(64);                                     // [0] live keys, [1] answered (one word of 256 bytes)
+    L.lo_all = w.take<uint32_t>((size_t)n_tiles * 64);                // a lower bound per row slot
+    w.cover(o);
+    return w.finish(L);
+}
+size_t bound_scan_wide_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log) { return bound_wide_layout(nullptr, p, k, n_tiles, dim, log).total; }
+hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
+                                  uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first) {
+    // (whether the path is TAKEN is bound_wide_route's decision; here only what the kernels need)
+    if (bound_wide_route(rule_metric(v), v.dim, v.n_rows, 1, k, 1, plane8_first ? 1 : 2, v.plane != nullptr, v.plane8 != nullptr) != (plane8_first ? 2 : 1) || !d_ctrl || !d_stats)
+        return hipErrorInvalidValue;
+    const uint32_t grid = p.grid;
+    const BoundWideLayout L = bound_wide_layout(d_ws, p, k, v.n_tiles, v.dim);
+    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(kBoundCollectGrid, (n_pad + kCollectChunk - 1u) / kCollectChunk);
+    const uint32_t n_keys = grid * kScanWaves * kBoundWideListLen;    // (even, and more than k: grid x 256 >= rows > k)
+    BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);
+    const size_t lds1 = (size_t)v.dim * sizeof(float) + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    const size_t lds8 = (size_t)v.dim * 2 + (size_t)kScanWaves * 64 * sizeof(uint64_t);
+    const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * v.dim4 * 4 * sizeof(float);
+    const uint32_t rgrid = std::min(kBoundWideRescoreGrid, (kBoundWideCandCap + kScanWaves - 1) / kScanWaves);
+    if (n_keys <= k || (n_keys & 1u)) return hipErrorInvalidValue;
+    static const int trace = env_int("QV_TRACE", 0);                   // (an unfiltered line: one read per process, as qv_scan.hip's)
+    if (trace) {
+        const char* stage = "k_bound_scan wide + select + k_bound_collect_wide + k_bound_rescore_wide";
+        if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8 wide + select + k_bound_collect_wide + k_bound_rescore_wide, then gated %s, then k_select_sort and the gated key-per-row redo (tiles=%u, k=%u)\n", stage, v.n_tiles, k);
+        else fprintf(stderr, "qv: scan kernel = %s, then k_select_sort and the gated key-per-row redo (tiles=%u, k=%u)\n", stage, v.n_tiles, k);
+    }
+    auto run = [&](auto Mc) -> hipError_t {
+        constexpr int M = decltype(Mc)::value;
+        hipError_t e = set_lds(k_bound_scan<M, false, true>, lds1);
+        if (e == hipSuccess) e = set_lds(k_bound_rescore_wide<M, false>, lds2);
+        if (e == hipSuccess && plane8_first) e = set_lds(k_bound_scan8<M, false, true>, lds8);
+        if (e == hipSuccess && plane8_first) e = set_lds(k_bound_rescore_wide<M, true>, lds2);
+        if (e != hipSuccess) return e;
+        // what follows a stage's scan: H, the collect, the re-score — each behind `gate`, the flag of the stage in front (null: none)
+        auto finish = [&](auto rescore, BoundCtrl* c, uint32_t* gate, BoundCtrl* next) -> hipError_t {
+            const hipError_t e2 = launch_select_topk(L.lists, n_keys, n_keys, 1, k, k, L.sel_ws, L.seed_rows, L.seed_dist, s, false, false, gate);
+            if (e2 != hipSuccess) return e2;
+            hipLaunchKernelGGL(k_bound_collect_wide, dim3(cgrid), dim3(256), 0, s, L.lo_all, n_pad, k, (const uint32_t*)L.seed_rows, (const float*)L.seed_dist, c, L.cand, (const uint32_t*)gate);
+            hipLaunchKernelGGL(rescore, dim3(rgrid), dim3(kScanBlock), lds2, s, v, d_query, c, (const uint32_t*)L.cand, d_stats, L.keys, L.sel, gate, next);
+            return hipGetLastError();
+        };
+        if (plane8_first) {
+            BoundCtrl* ctrl8 = ctrl + 1;
+            hipLaunchKernelGGL((k_bound_scan8<M, false, true>), dim3(grid), dim3(kScanBlock), lds8, s, v, d_query, kBoundWideListLen, ctrl8, L.lo_all, L.lists, L.seed_rows, L.seed_dist);
+            e = finish(k_bound_rescore_wide<M, true>, ctrl8, (uint32_t*)nullptr, ctrl);
+            if (e != hipSuccess) return e;
+            uint32_t* gate8 = &ctrl8->flag;
+            hipLaunchKernelGGL((k_bound_scan<M, false, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, kBoundWideListLen, ctrl, L.lo_all, L.lists, L.seed_rows, L.seed_dist, (const uint32_t*)gate8);
+            return finish(k_bound_rescore_wide<M, false>, ctrl, gate8, (BoundCtrl*)nullptr);
+        }
+        hipLaunchKernelGGL((k_bound_scan<M, false, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, kBoundWideListLen, ctrl, L.lo_all, L.lists, L.seed_rows, L.seed_dist, (const uint32_t*)nullptr);
+        return finish(k_bound_rescore_wide<M, false>, ctrl, (uint32_t*)nullptr, (BoundCtrl*)nullptr);
+    };
+    hipError_t e = v.metric == QV_COSINE ? run(std::integral_constant<int, QV_COSINE>{})
+                 : v.metric == QV_DOT  ? run(std::integral_constant<int, QV_DOT>{}) : run(std::integral_constant<int, QV_L2>{});
+    if (e != hipSuccess) return e;
+    // the answer of whichever stage answered (sel[1]), then the exact redo of a search the bfloat16 stage handed back (its flag)
+    e = launch_select_topk_counted(L.keys, kBoundWideCandCap, kBoundWideCandCap, L.sel, 1, k, k, d_rows_out, d_dist_out, s, L.sel + 1);
+    if (e != hipSuccess) return e;
+    return launch_flat_select_redo_one(v, p, d_query, k, k, &ctrl->flag, L.redo, d_rows_out, d_dist_out, s);
 }
 // the interval of one row on the host; 1: a row the bound says nothing about ("unsure"), as host_bound_interval8 reports it
 int host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {

@@ -280,6 +280,21 @@ int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float*
 // (scale8: the row's 8-bit scale, as host_quantize_row8 gives it); and those bytes back into biased codes u[dim]
 int host_quantize_row6(uint32_t dim, const float* row, float scale8, uint8_t* out_bytes, float* out_res);
 int host_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes);
+// The WIDE form of the single-query, unfiltered bound scan, 65 <= k <= kBoundWideMaxK (qv_bound_scan.hip): stage 1 publishes every wave's 64
+// smallest upper bounds, H is the k-th smallest key of their union (launch_select_topk), the collect has a list of QV_BOUND_WIDE_CAND_CAP rows,
+// the re-score writes a key per survivor and launch_select_topk_counted takes the k best.  A search it cannot decide is redone by the
+// key-per-row path behind a device word (launch_flat_select_redo_one).  Whether a search takes it is bound_wide_route's answer — a knob of its
+// own (qv_index_set_bound_scan_wide / QV_BOUND_SCAN_WIDE), independent of bound_scan_decide, which keeps saying no above kMaxFusedK.
+constexpr uint32_t kBoundWideMaxK = 1024;
+constexpr uint32_t kBoundWideStatsWord = 10;   // the wide form's counters: [10] survivors passed to the re-score, [11] hand-backs to the exact path, [12] searches
+// 0: no wide form; 1: the bfloat16 copy first; 2: the 8-bit plane first.  wide_mode: QV_BOUND_SCAN_* (0: QV_BOUND_SCAN_WIDE of the environment,
+// read once, else automatic); plane_mode: the index's qv_index_set_bound_plane (0: QV_BOUND_PLANE, else automatic)
+int bound_wide_route(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, bool has_plane, bool has_plane8);
+size_t bound_scan_wide_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr);
+// d_ctrl: the stream's control words (2 BoundCtrl, kept zero but for the bfloat16 stage's flag, which every search writes before it is read);
+// d_stats: the index's counters.  Enqueues everything, the gated exact redo included: nothing is read on the host.
+hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
+                                  uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first);
 constexpr uint32_t kBound6StatsWord = 7;   // the 6-bit stage's counters: [7] candidates it passed to the refine, [8] hand-backs, [9] searches
 constexpr uint32_t kBound6CandCap = 262144;   // rows the refine walks on the 8-bit plane (1 MiB of the workspace)
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches
@@ -442,6 +457,9 @@ hipError_t select_prepare(void* d_ws, uint32_t nq, uint32_t kk, SelState** st_ou
 hipError_t launch_select_topk(const uint64_t* d_keys, size_t stride, uint32_t n, uint32_t nq, uint32_t kk, uint32_t k_stride, void* d_ws,
                               uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool window0_counted = false, bool ordered = true,
                               const uint32_t* d_active = nullptr /* device word: queries from *d_active on are left alone */);
+// The direct form over lists whose live keys are a counted prefix (n <= 16384; qv_select.hip): only the prefix is read.  d_active as above.
+hipError_t launch_select_topk_counted(const uint64_t* d_keys, size_t stride, uint32_t n, const uint32_t* d_counts, uint32_t nq, uint32_t kk, uint32_t k_stride,
+                                      uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const uint32_t* d_active);
 // 64 < kk <= kMaxWideK: the scan with a list of 2 keys per lane (same stream as launch_flat_topk, no key per row written),
 // then the selection over the waves' lists.  ev0 / ev1 as launch_flat_topk.
 size_t flat_wide_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t kk, WsLog* log = nullptr);
@@ -461,6 +479,13 @@ hipError_t launch_flat_select(const IndexView& v, const ScanPlan& p, const float
 size_t flat_select_redo_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log = nullptr);
 hipError_t launch_flat_select_redo(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride, const uint32_t* d_flags,
                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+
+// ... and for ONE query behind a device word (the wide bound scan's hand-back): *d_flag non-zero = the query is redone, zero = every launch
+// leaves at once.  The lone query rides in a shared pass of two slots, so two queries' keys must fit a group (flat_select_redo_one_serves).
+bool flat_select_redo_one_serves(uint32_t n_tiles);
+size_t flat_select_redo_one_workspace_bytes(uint32_t n_tiles, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log = nullptr);
+hipError_t launch_flat_select_redo_one(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t kk, uint32_t k_stride, const uint32_t* d_flag,
+                                       void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
 
 // Full ranking path (any k): all distances -> 64-bit keys -> stable radix sort -> first k.
 // d_keys_a/d_keys_b: two buffers of n_tiles*64 u64; d_hist: radix histogram workspace.

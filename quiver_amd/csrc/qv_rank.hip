@@ -459,12 +459,26 @@ static FlatSelectRedoLayout flat_select_redo_layout(void* base, uint32_t n_tiles
     return w.finish(L);
 }
 size_t flat_select_redo_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log) { return flat_select_redo_layout(nullptr, n_tiles, nq, kk, dim, dim4, log).total; }
+// nq_slots: the query count the slots and the layout are made for — nq itself, or 2 for a lone query (launch_flat_select_redo_one: the
+// shared passes take two slots or more, so the query rides with an empty one)
+static hipError_t flat_select_redo_impl(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t nq_slots, uint32_t kk, uint32_t k_stride,
+                                        const uint32_t* d_flags, void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
 hipError_t launch_flat_select_redo(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride, const uint32_t* d_flags,
                                    void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
+    return flat_select_redo_impl(v, p, d_queries, nq, nq, kk, k_stride, d_flags, d_ws, d_rows_out, d_dist_out, s);
+}
+bool flat_select_redo_one_serves(uint32_t n_tiles) { return lk_redo_slots(n_tiles, 2) >= 2; }
+size_t flat_select_redo_one_workspace_bytes(uint32_t n_tiles, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log) { return flat_select_redo_layout(nullptr, n_tiles, 2, kk, dim, dim4, log).total; }
+hipError_t launch_flat_select_redo_one(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t kk, uint32_t k_stride, const uint32_t* d_flag,
+                                       void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
+    return flat_select_redo_impl(v, p, d_query, 1, 2, kk, k_stride, d_flag, d_ws, d_rows_out, d_dist_out, s);
+}
+static hipError_t flat_select_redo_impl(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t nq_slots, uint32_t kk, uint32_t k_stride,
+                                        const uint32_t* d_flags, void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
     if (nq == 0) return hipSuccess;
-    const uint32_t slots = lk_redo_slots(v.n_tiles, nq);
+    const uint32_t slots = lk_redo_slots(v.n_tiles, nq_slots);
     if (kk <= (uint32_t)kMaxFusedK || kk > (uint32_t)kMaxSelectK || kk != k_stride || slots < 2) return hipErrorNotSupported;   // (a corpus whose keys leave room for one query at a time: the caller's host path)
-    const FlatSelectRedoLayout L = flat_select_redo_layout(d_ws, v.n_tiles, nq, kk, v.dim, v.dim4);
+    const FlatSelectRedoLayout L = flat_select_redo_layout(d_ws, v.n_tiles, nq_slots, kk, v.dim, v.dim4);
     uint32_t *list = L.list, *count = L.count, *t_rows = L.t_rows;
     float *rq = L.rq, *t_dist = L.t_dist;
     hipLaunchKernelGGL(k_lk_redo_list, dim3(1), dim3(1024), 0, s, d_flags, nq, slots, list, count);

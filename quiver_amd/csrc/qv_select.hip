@@ -342,13 +342,18 @@ k_select_sort(const uint64_t* __restrict__ keys, size_t stride, uint32_t n, uint
 // prefix is read — 2 100 of 16 384 slots at k = 1000.  n <= 16384.
 hipError_t launch_select_topk_counted(const uint64_t* d_keys, size_t stride, uint32_t n, const uint32_t* d_counts, uint32_t nq, uint32_t kk, uint32_t k_stride,
                                       uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
+    return launch_select_topk_counted(d_keys, stride, n, d_counts, nq, kk, k_stride, d_rows_out, d_dist_out, s, nullptr);
+}
+// d_active (a device word, or null): queries from *d_active on are left alone, their outputs untouched (the wide bound scan: zero = handed back)
+hipError_t launch_select_topk_counted(const uint64_t* d_keys, size_t stride, uint32_t n, const uint32_t* d_counts, uint32_t nq, uint32_t kk, uint32_t k_stride,
+                                      uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const uint32_t* d_active) {
     if (nq == 0 || kk == 0 || kk > (uint32_t)kMaxSelectK || kk > k_stride || n == 0 || n > 16384u || kk > n || d_counts == nullptr) return hipErrorInvalidValue;
     uint32_t m_sort = 64;
     while (m_sort < kk) m_sort <<= 1;
     const size_t lds_d = (size_t)std::max<uint32_t>(n, m_sort) * sizeof(uint64_t);
     hipError_t e = set_lds(k_select_sort, lds_d);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_select_sort, dim3(nq), dim3(kSelSortBlock), lds_d, s, d_keys, stride, n, kk, k_stride, n, (SelState*)nullptr, (const uint64_t*)nullptr, d_rows_out, d_dist_out, 0, d_counts);
+    hipLaunchKernelGGL(k_select_sort, dim3(nq), dim3(kSelSortBlock), lds_d, s, d_keys, stride, n, kk, k_stride, n, (SelState*)nullptr, (const uint64_t*)nullptr, d_rows_out, d_dist_out, 0, d_counts, d_active);
     return hipGetLastError();
 }
 

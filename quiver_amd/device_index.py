@@ -424,6 +424,21 @@ class DeviceIndex:
         check(lib().qv_index_bound_scan_stats(self._h, out))
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
+    BOUND_WIDE_CAND_CAP = _lib.QV_BOUND_WIDE_CAND_CAP   # rows the wide form's re-score walks at most
+
+    def set_bound_scan_wide(self, mode):
+        """the wide form of the single-query, unfiltered bound scan, 65 <= k <= 1024: "auto" (the measured shapes: cosine / dot, k <= 1000, from 1M rows of 768 dimensions or 10M rows of 128),
+        "always" (whenever the shape applies), "never"; a knob of its own, independent of set_bound_scan — which plane comes first follows
+        set_bound_plane (qv_index_set_bound_scan_wide)"""
+        check(lib().qv_index_set_bound_scan_wide(self._h, self.BOUND_SCAN.get(mode, mode)))
+
+    def bound_scan_wide_stats(self) -> dict:
+        """survivors the last wide search passed to its re-score, wide searches handed back to the exact path, searches that took the wide
+        form, whether the bfloat16 copy exists"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_index_bound_scan_wide_stats(self._h, out))
+        return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
+
     BOUND_PLANE = {"auto": 0, "8bit": 1, "bf16": 2}
 
     def _set_bound_plane(self, form, mode):
