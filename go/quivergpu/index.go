@@ -114,6 +114,29 @@ func (d *oneGPU) setBoundScanWide(mode int) error {
 	return nil
 }
 
+// SetBoundScanWideFiltered (qv_index_set_bound_scan_wide_filtered): the same for ONE filtered query of 65 to 1024 results — a mask, a row
+// set or a where-filter that leaves more live candidates than results.  A knob of its own, independent of SetBoundScanWide; BoundScanAuto
+// takes the measured shapes only (cosine and dot, k <= 1000, from 1M rows of 768 dimensions or 10M rows of 128, a candidate in at least
+// one 64-row tile in ten).  Results are the exact path's either way.  One GPU only: a sharded index has no such
+// setter (the environment variable QV_BOUND_SCAN_WIDE_FILTERED is the default of its shards too) and its filtered search keeps its path.
+func (x *Index) SetBoundScanWideFiltered(mode int) error {
+	x.mu.Lock()
+	defer x.mu.Unlock()
+	d, ok := x.dev.(*oneGPU)
+	if !ok {
+		return errors.New("quivergpu: the wide bound scan is a one-GPU path; a sharded index has no such setter")
+	}
+	return d.setBoundScanWideFiltered(mode)
+}
+
+func (d *oneGPU) setBoundScanWideFiltered(mode int) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	if C.qv_index_set_bound_scan_wide_filtered(d.h, C.int(mode)) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
 // Insert implements core.Index (collection.go:80).  Error strings follow exact.go:45-50.
 func (x *Index) Insert(id string, v vectortypes.F32) error {
 	x.mu.Lock()

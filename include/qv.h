@@ -601,8 +601,8 @@ int qv_scan_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes);
  * QV_BOUND_PLANE_8BIT the 8-bit plane where it is held, QV_BOUND_PLANE_BF16 the bfloat16 copy, QV_BOUND_PLANE_AUTO the 8-bit plane in
  * the cells where it also beat the bfloat16 copy first by the same standard (all of the cells above), the bfloat16 copy elsewhere.
  * The environment variable QV_BOUND_SCAN_WIDE (1 always, 2 never; read once per process) sets the default of indexes that never call this.
- * Out of scope and unchanged: shared passes of 2 or more queries, the filtered forms (masks, row sets, where-filters), the 6-bit plane,
- * k > 1024, and the sharded handle (qv_sharded_* keeps its paths; there is no sharded setter). */
+ * Out of scope and unchanged: shared passes of 2 or more queries, the 6-bit plane, k > 1024, and the sharded handle (qv_sharded_* keeps
+ * its paths; there is no sharded setter).  The filtered forms have a knob of their own: qv_index_set_bound_scan_wide_filtered, below. */
 #define QV_BOUND_WIDE_CAND_CAP 8192   /* rows the wide form's re-score walks at most: 1024 + 4032 (the k <= 64 form's spare over its largest k) and room to the next power of two */
 int qv_index_set_bound_scan_wide(qv_index* idx, int mode);
 /* out[0] = survivors passed to the re-score in the last wide search, out[1] = searches handed back to the exact path so far, out[2] =
@@ -614,6 +614,39 @@ int qv_index_bound_scan_wide_stats(qv_index* idx, uint64_t out[4]);
  * plane_mode: QV_BOUND_PLANE_*; has_plane / has_plane8: the index holds the bfloat16 copy / the 8-bit plane.
  * 0: no wide form; 1: the bfloat16 copy first; 2: the 8-bit plane first; < 0 on an error (an unknown mode). */
 int qv_scan_bound_wide_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, int has_plane, int has_plane8);
+/* ---- the wide form under a filter ----
+ * ONE filtered query asking for 65 to 1024 results — qv_index_search_masked, qv_index_search_rowsets, qv_index_search_rowsets_device and
+ * qv_index_search_where (whose k > 64 form makes its filter a counted set first) — answered by the wide form over the call's candidate
+ * bitmap (live & selected): stage 1 reads no 64-row tile without a candidate, rows outside the filter are never candidates and never in
+ * the threshold, and the collect, the re-score, the selection and the gated key-per-row redo read the same bitmap.  Rows, float32 bits,
+ * counts and padding are those of the path the call takes otherwise (the filtered wide scan up to 128 results, the key-per-row path above).
+ * On top of the unfiltered form's conditions the call needs a tile with a candidate and MORE live candidates than results: a k that takes
+ * every candidate has nothing to reject, and a shorter set keeps its path and its clamped count.  The counters are the wide form's own
+ * (qv_index_bound_scan_wide_stats); the k <= 64 counters do not move.
+ * `mode` takes the QV_BOUND_SCAN_* values and is a knob of its own: independent of qv_index_set_bound_scan_wide, of qv_index_set_bound_scan
+ * and of the plane knobs.  ALWAYS: whenever the shape applies.  NEVER: never.  AUTO: the measured cells in which the form ran ahead of the
+ * path the filtered call takes today at every measured k (65, 100, 128, 129, 256, 1000) by more than both arms' spread
+ * (profiles/LAB_r25_bound_scan_wide_filtered.md, tests/bench/bench_bound_scan_wide_filtered.py; 1M, 3M and 10M x 768 and 10M x 128, cosine,
+ * filters that leave a candidate in every tile, in 0.476 of the tiles and in one tile in ten — every one of them), never a shape the
+ * unfiltered rule (qv_scan_bound_wide_route under AUTO) declines: cosine and dot indexes, k <= 1000, from 1 000 000 rows of 768 dimensions
+ * or more and from 10 000 000 rows of 128 to 767 dimensions, with a candidate in at least one 64-row tile in ten.  NOT measured and never
+ * automatic: sparser filters, and everything the unfiltered rule leaves out (QV_L2 indexes, fewer rows, k above 1000).  Which plane comes
+ * first follows qv_index_set_bound_plane_filtered: QV_BOUND_PLANE_8BIT the 8-bit plane where it is held, QV_BOUND_PLANE_BF16 the bfloat16
+ * copy, QV_BOUND_PLANE_AUTO the 8-bit plane in the cells where it also beat the bfloat16 copy first by the same standard — 768 dimensions
+ * or more: from 3 000 000 rows at one tile in ten or denser, below that only with a candidate in every tile; 128 to 767 dimensions (from
+ * 10 000 000 rows): a candidate in at least 0.475 of the tiles — and the bfloat16 copy elsewhere.
+ * The environment variable QV_BOUND_SCAN_WIDE_FILTERED (1 always, 2 never; read once per process) sets the default of indexes that never
+ * call this — the per-shard indexes of a sharded handle among them; there is no sharded setter, and the sharded handle's filtered search
+ * (an internal call without the stream's ticket words) keeps its path whatever the variable says.
+ * Out of scope and unchanged: qv_index_search_where_device keeps its k <= 64 limit (its candidate count exists only on the device, and the
+ * selection paths need k <= count); runs of two or more queries naming one set keep their shared key-per-row pass; shared passes at
+ * k > 64. */
+int qv_index_set_bound_scan_wide_filtered(qv_index* idx, int mode);
+/* The filtered form's rule on the host, as the dispatch asks it.  Arguments as qv_scan_bound_wide_route's; plane_mode_filtered:
+ * QV_BOUND_PLANE_* of qv_index_set_bound_plane_filtered; candidate_tiles: the 64-row tiles that hold a candidate; candidates: the live
+ * rows the filter selects.  0: no wide form; 1: the bfloat16 copy first; 2: the 8-bit plane first; < 0 on an error (an unknown mode). */
+int qv_scan_bound_wide_route_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered, int has_plane, int has_plane8,
+                                      uint32_t candidate_tiles, uint64_t candidates);
 /* ---- the 8-bit stage under a filter ----
  * Which plane serves a single FILTERED query's bound scan first: qv_index_search_masked, qv_index_search_rowsets and
  * qv_index_search_where with one query, their device forms, and a shared pass of the row-set front that holds one caller — at

@@ -129,6 +129,8 @@ PROTOTYPES = {
     "qv_index_set_bound_scan_wide": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_bound_scan_wide_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_scan_bound_wide_route": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "qv_index_set_bound_scan_wide_filtered": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_scan_bound_wide_route_filtered": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64]),
     "qv_scan_bound6_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "qv_scan_quantize_row6": (C.c_int, [C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, _f32p]),
     "qv_scan_unpack_row6": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -594,12 +594,18 @@ static void profile_end(qv_index* idx, const ProfilePair& p, bool launched, bool
 }
 
 // Whether a search of list length kk takes the bound scan's wide form (65 <= kk <= 1024), for the launch (enqueue_search) and for the
-// workspace (search_ws_bytes): 0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.  One unfiltered query whose call carries the
-// stream's ticket words, kk == k_stride, and fewer results than live rows (a k above the live rows keeps its path); the rest is
-// qv::bound_wide_route's answer under the index's two knobs.
-static int wide_route(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, bool filtered) {
-    if (nq != 1 || kk != k_stride || !tickets || filtered || kk >= idx->n_live) return 0;
+// workspace (search_ws_bytes): 0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.  One query whose call carries the stream's ticket
+// words, kk == k_stride.  Unfiltered (cand_tiles == kBoundNoFilter): fewer results than live rows (a k above the live rows keeps its path);
+// the rest is qv::bound_wide_route's answer under the index's two knobs.  Filtered: cand_tiles and candidates are the call's candidate tiles
+// and its live candidates as the host counts them, and the answer is qv::bound_wide_route_filtered's under the filtered form's own knob and
+// the single-query filtered plane knob — fewer results than candidates is that rule's own condition.
+static int wide_route(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles, uint64_t candidates) {
+    if (nq != 1 || kk != k_stride || !tickets) return 0;
     const int metric = idx->l2_planes() ? QV_RULE_L2_PLANES : idx->metric;
+    if (cand_tiles != qv::kBoundNoFilter)
+        return qv::bound_wide_route_filtered(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide_filtered, idx->bound.plane[qv::bound_one_filtered], idx->d_bf16 != nullptr,
+                                             idx->d_plane8 != nullptr, cand_tiles, candidates);
+    if (kk >= idx->n_live) return 0;
     return qv::bound_wide_route(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide, idx->bound.plane[qv::bound_one], idx->d_bf16 != nullptr, idx->d_plane8 != nullptr);
 }
 
@@ -607,6 +613,7 @@ static int wide_route(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_
 struct SearchExtras {
     const uint64_t* d_candidates = nullptr;   // row bitmap replacing the tombstone bitmap (filtered search)
     uint32_t candidate_tiles = 0;             // with d_candidates: the tiles that hold a candidate (an upper bound known on the host)
+    uint64_t candidates = 0;                  // with d_candidates: the live rows it selects, where the host counted them (the filtered wide form's rule; 0: not counted)
     uint32_t* d_tickets = nullptr;            // the stream's tickets: allows the single-launch small scan
     uint32_t* done_flag = nullptr;            // one query: the word the last kernel writes done_seq into behind its results; *flag_used: it will
     uint32_t done_seq = 0;
@@ -631,11 +638,11 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "%s scan launch failed: %s", fp.route == qv::FlatRoute::small ? "small" : "flat", hipGetErrorString(e));
         return QV_OK;
     }
-    // 65 <= k <= 1024, one unfiltered query, where the wide form's rule takes it: the bound scan on the reduced copies, its re-score and
-    // selection, and the gated key-per-row redo behind them — all enqueued by the one launcher
-    if (const int wide = wide_route(idx, nq, kk, k_stride, x.d_tickets != nullptr, x.d_candidates != nullptr)) {
+    // 65 <= k <= 1024, one query, unfiltered or over its candidate bitmap, where the wide form's rule takes it: the bound scan on the reduced
+    // copies, its re-score and selection, and the gated key-per-row redo behind them — all enqueued by the one launcher
+    if (const int wide = wide_route(idx, nq, kk, k_stride, x.d_tickets != nullptr, x.d_candidates ? x.candidate_tiles : qv::kBoundNoFilter, x.candidates)) {
         const ProfilePair pp = profile_begin(idx, true, s);
-        hipError_t e = qv::launch_bound_scan_wide(v, plan, d_queries, kk, ws, x.d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, d_rows_out, d_dist_out, s, wide == 2);
+        hipError_t e = qv::launch_bound_scan_wide(v, plan, d_queries, kk, ws, x.d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, d_rows_out, d_dist_out, s, wide == 2, x.d_candidates != nullptr);
         profile_end(idx, pp, e == hipSuccess, true, s);
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "wide bound scan launch failed: %s", hipGetErrorString(e));
         return QV_OK;
@@ -664,8 +671,8 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
     return QV_OK;
 }
 
-// tickets / cand_tiles: as the call will be enqueued (flat_plan) — a call whose route is a bound scan is sized for it, no other call is
-static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles = qv::kBoundNoFilter) {
+// tickets / cand_tiles / candidates: as the call will be enqueued (flat_plan, wide_route) — a call whose route is a bound scan is sized for it, no other call is
+static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles = qv::kBoundNoFilter, uint64_t candidates = 0) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     const qv::ScanPlan plan = qv::plan_scan(n_tiles, idx->cus);
     if (kk <= (uint32_t)qv::kMaxFusedK && kk == k_stride) {
@@ -674,7 +681,7 @@ static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uin
                               : fp.route == qv::FlatRoute::bound || fp.route == qv::FlatRoute::bound8_first ? qv::FlatWs::call_bound : qv::FlatWs::call;
         return qv::flat_layout(nullptr, what, plan, nq, kk, n_tiles, idx->dim).total;
     }
-    if (wide_route(idx, nq, kk, k_stride, tickets, cand_tiles != qv::kBoundNoFilter)) return qv::bound_scan_wide_workspace_bytes(plan, kk, n_tiles, idx->dim);
+    if (wide_route(idx, nq, kk, k_stride, tickets, cand_tiles, candidates)) return qv::bound_scan_wide_workspace_bytes(plan, kk, n_tiles, idx->dim);
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
     return qv::full_sort_workspace_bytes(n_tiles);
@@ -973,7 +980,7 @@ int qv_index_search_negative(qv_index* idx, const float* query, const float* neg
     int rc;
     // (the context's ticket words only where the wide bound scan takes the fetch — max(2k, 30) results, so every k >= 33: without them
     //  every path is the one this call has always taken)
-    const bool wide = wide_route(idx, 1, kk, kk, true, false) != 0;
+    const bool wide = wide_route(idx, 1, kk, kk, true, qv::kBoundNoFilter, 0) != 0;
     if ((rc = hc.open()) || (rc = hc.reserve(2, 1, kk, 2)) || (rc = hc.workspace(search_ws_bytes(idx, 1, kk, kk, wide)))) return rc;
     SearchExtras x;
     if (wide && (rc = hc.tickets(&x.d_tickets))) return rc;
@@ -1015,12 +1022,12 @@ static int masked_pass(qv_index* idx, const float* queries, uint32_t nq, uint32_
     for (uint32_t q = 0; q < nq; q++) count_out[q] = kk;
     if (kk == 0) return QV_OK;
     if ((rc = hc.reserve(nq, nq, kk))) return rc;
-    // the bound scan under the mask when the filtered rule takes it: then, and only then, the call carries the context's ticket words
-    // (without them every path is the one a masked search has always taken)
-    const bool bound = kk <= (uint32_t)qv::kMaxFusedK && flat_plan(idx, nq, kk, true, cand_tiles).bound();
-    if ((rc = hc.workspace(search_ws_bytes(idx, nq, kk, kk, bound, cand_tiles)))) return rc;
+    // the bound scan under the mask when the filtered rule takes it — up to 64 results plan_flat's, from 65 the wide form's —: then, and only
+    // then, the call carries the context's ticket words (without them every path is the one a masked search has always taken)
+    const bool bound = kk <= (uint32_t)qv::kMaxFusedK ? flat_plan(idx, nq, kk, true, cand_tiles).bound() : wide_route(idx, nq, kk, kk, true, cand_tiles, matching) != 0;
+    if ((rc = hc.workspace(search_ws_bytes(idx, nq, kk, kk, bound, cand_tiles, matching)))) return rc;
     SearchExtras x;
-    x.d_candidates = static_cast<const uint64_t*>(c->d_mask.p); x.candidate_tiles = cand_tiles;
+    x.d_candidates = static_cast<const uint64_t*>(c->d_mask.p); x.candidate_tiles = cand_tiles; x.candidates = matching;
     if (bound && (rc = hc.tickets(&x.d_tickets))) return rc;
     hc.stage(queries, nq);
     HIPCHK(hipMemcpyAsync(c->d_mask.p, c->h_mask.p, words * 8, hipMemcpyHostToDevice, c->stream));
@@ -1330,7 +1337,8 @@ static qv::RowSetRef rs_ref(const qv_index* idx, const RsFilter& f) {
 // whatever the first count said; with that rule's mode at "bf16" the first question alone decides, as before.
 // batched: a multi piece of 9 or more queries that takes the matrix-core filter with a set per query (launch_batched with BatchedSets;
 // filtered_batch_takes is the rule) — decided here too, and only for the host forms, whose caller reads the redo flags.
-struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; bool bound8; bool batched = false; };
+// cand: a run's live candidates (rowset_live), counted for k > kMaxFusedK only — the filtered wide form's rule asks for it; 0 otherwise.
+struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; bool bound8; bool batched = false; uint64_t cand = 0; };
 static uint32_t rowsets_cand_tiles(const qv_index* idx, const RsFilter* fl, uint32_t nq, bool transient_every_tile = false) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     uint64_t sum = 0;
@@ -1379,13 +1387,14 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const R
         const qv_rowset* set = fl[q].set;
         const bool transient = fl[q].where != nullptr;                // (only with k <= kMaxFusedK: the k > 64 form of qv_index_search_where makes real sets first)
         // (up to kMaxFusedK the lists are k long whatever the set holds: the scans pad, nothing is counted on the host)
-        const uint32_t kk = k <= (uint32_t)qv::kMaxFusedK ? k : (uint32_t)std::min<uint64_t>(k, rowset_live(idx, set));
+        const uint64_t cand = k <= (uint32_t)qv::kMaxFusedK ? 0 : rowset_live(idx, set);
+        const uint32_t kk = k <= (uint32_t)qv::kMaxFusedK ? k : (uint32_t)std::min<uint64_t>(k, cand);
         // (a set that selects fewer than kk rows has no threshold: the bound pass would only precede the exact scan that answers — reported
         //  as no candidate tile, which the automatic rule declines; "always" still takes the path)
         const bool too_few = !transient && set && set->selected < kk;
         const uint32_t ct = transient ? n_tiles : (set && !too_few ? std::min<uint32_t>(set->tiles, n_tiles) : 0u);
-        pieces.push_back(RowsetPiece{q, e - q, kk, false, false, ct, false});
-        if (kk) ws = std::max(ws, search_ws_bytes(idx, e - q, kk, k, e - q == 1, set || transient ? ct : qv::kBoundNoFilter));   // (as rowsets_enqueue passes them on)
+        pieces.push_back(RowsetPiece{q, e - q, kk, false, false, ct, false, false, cand});
+        if (kk) ws = std::max(ws, search_ws_bytes(idx, e - q, kk, k, e - q == 1, set || transient ? ct : qv::kBoundNoFilter, cand));   // (as rowsets_enqueue passes them on)
         q = e;
     }
     return ws;
@@ -1497,7 +1506,7 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
             cand = d_mask;
         }
         SearchExtras x;
-        x.d_candidates = cand; x.candidate_tiles = p.cand_tiles; x.d_tickets = p.nq == 1 ? d_tickets : nullptr;
+        x.d_candidates = cand; x.candidate_tiles = p.cand_tiles; x.candidates = p.cand; x.d_tickets = p.nq == 1 ? d_tickets : nullptr;
         const int rc = enqueue_search(idx, q, p.nq, p.kk, k, ws, r_out, d_out, s, x);
         if (rc != QV_OK) return rc;
     }
@@ -2079,6 +2088,13 @@ int qv_index_set_bound_scan_wide(qv_index* idx, int mode) {
     return QV_OK;
 }
 
+int qv_index_set_bound_scan_wide_filtered(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    idx->bound_wide_filtered = mode;
+    return QV_OK;
+}
+
 int qv_index_bound_scan_wide_stats(qv_index* idx, uint64_t out[4]) {
     if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
     HIPCHK(hipSetDevice(idx->device));
@@ -2093,6 +2109,14 @@ int qv_scan_bound_wide_route(int metric, uint32_t dim, uint32_t rows, uint32_t n
     if (wide_mode < 0 || wide_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mode);
     if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
     return qv::bound_wide_route(metric, dim, rows, nq, k, wide_mode, plane_mode, has_plane != 0, has_plane8 != 0);
+}
+
+int qv_scan_bound_wide_route_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered, int has_plane, int has_plane8,
+                                      uint32_t candidate_tiles, uint64_t candidates) {
+    if (wide_mode < 0 || wide_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mode);
+    if (plane_mode_filtered < 0 || plane_mode_filtered > QV_BOUND_PLANE_BF16)
+        return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered);
+    return qv::bound_wide_route_filtered(metric, dim, rows, nq, k, wide_mode, plane_mode_filtered, has_plane != 0, has_plane8 != 0, std::min(candidate_tiles, qv::kBoundNoFilter - 1), candidates);   // (a count, never the "no filter" mark)
 }
 
 // The six rule exports: views of the one decision (qv::bound_scan_decide) for a call given without an index.  form: the form the export

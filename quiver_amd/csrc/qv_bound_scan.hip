@@ -1,8 +1,8 @@
 // qv_bound_scan.hip — the bound scan: a fused flat search (k <= 64; cosine, dot, or a Euclidean index created with QV_FLAG_L2_SCAN_PLANE) answered from the index's reduced copies of the rows — the
 // bfloat16 copy, with the 8-bit plane in front of it for one query and for a shared pass of 2 - 8, each unfiltered or filtered — by rejecting
 // rows on a certified interval of the distance (qv_bound.h) and re-scoring the few survivors in the exact scan's arithmetic.  One query, the shared
-// pass of 2 - 8, their filtered forms; the wide form of one unfiltered query for 65 to 1024 results (bound_scan_tail_wide, k_bound_collect_wide,
-// k_bound_rescore_wide, launch_bound_scan_wide);
+// pass of 2 - 8, their filtered forms; the wide form of one query, unfiltered or over a candidate bitmap, for 65 to 1024 results
+// (bound_scan_tail_wide, k_bound_collect_wide, k_bound_rescore_wide, launch_bound_scan_wide);
 // the rules that say when each applies; the launchers and workspace sizes; the interval and the 8-bit row state compiled for the host.
 // Which search takes the path is decided by plan_flat (qv_scan.hip); the exact scan that answers what a bound pass hands back
 // (k_flat_scan<., ., true> behind its gate, launch_flat_redo_flagged) and the list merge (launch_merge_lists) live there too.
@@ -110,7 +110,8 @@ __device__ __forceinline__ bool bound_scan_tail(uint64_t list, uint64_t thr, uin
     return true;
 }
 
-// The WIDE form's tail (k_bound_scan<., false, true>, k_bound_scan8<., false, true>: one unfiltered query, 65 <= k <= kBoundWideMaxK).  The
+// The WIDE form's tail (k_bound_scan<., ., true>, k_bound_scan8<., ., true>: one query, 65 <= k <= kBoundWideMaxK; under SKIP "live" below reads
+// "candidate": v.alive is the call's candidate bitmap).  The
 // scan runs with a list length of 64, so a wave ends holding the 64 smallest upper bounds of ITS rows, and every wave's list is published as
 // it stands — [grid][kScanWaves][64] keys, dead keys where a wave saw fewer than 64 live rows — without a merge down to k: the in-wave list
 // and merge_lists_last_workgroup hold 64 keys and do not stretch to 1024.  H is then the k-th smallest key of the UNION of the published
@@ -123,7 +124,8 @@ __device__ __forceinline__ bool bound_scan_tail(uint64_t list, uint64_t thr, uin
 //   When one wave's rows hold more than 64 of the k smallest (the nearest rows stored together in tiles of one wave), the dropped ones are
 //   replaced by larger published keys: H is only LOOSER, never too small, and the collect passes a few more rows on.
 //   Fewer than k published live keys (fewer than k rows the bound is sure of): the k-th key is dead, there is no H, the search is handed on.
-// No ticket, no last workgroup: every slot of `lists` is written by its own wave in every launch (the workspace is reused).
+// No ticket, no last workgroup: every slot of `lists` is written by its own wave in every launch (the workspace is reused) — a wave that
+// walks no tile, or under SKIP reads none, arrives with the dead list it started with and publishes that.
 __device__ __forceinline__ void bound_scan_tail_wide(uint64_t list, uint32_t wave, uint32_t lane, uint64_t* __restrict__ lists /* [grid][kScanWaves][64] */) {
     lists[((size_t)blockIdx.x * kScanWaves + wave) * 64 + lane] = list;
 }
@@ -843,11 +845,14 @@ k_bound_refine8(IndexView v, const BoundQuery8* __restrict__ qst, uint32_t k, Bo
     }
 }
 
-// ---------------------------------------------------------------- one unfiltered query, 65 <= k <= 1024: the wide form --
+// ---------------------------------------------------------------- one query, 65 <= k <= 1024: the wide form --
 // The k <= 64 form stops at 64 because stage 1 keeps its upper bounds in a wave list of one key per lane and its re-score merges such lists;
 // interval, collect and the exact chain do not depend on k.  The wide form keeps both scan kernels up to their tail and replaces the rest:
-//   k_bound_scan<., false, true> / k_bound_scan8<., false, true>   the walk with a list length of 64; the tail publishes every wave's list
-//                    (bound_scan_tail_wide, where the argument for H stands).
+//   k_bound_scan<., SKIP, true> / k_bound_scan8<., SKIP, true>   the walk with a list length of 64; the tail publishes every wave's list
+//                    (bound_scan_tail_wide, where the argument for H stands).  SKIP: the filtered form — v.alive is the call's candidate
+//                    bitmap (a mask, a row set, a where-filter: alive & selected), tiles without a candidate are not read, their 64
+//                    lower-bound words written as 0xFFFFFFFF all the same; everything behind stage 1 takes its liveness from v.alive and
+//                    serves the bitmap as it stands, the key-per-row redo included (the filtered key-per-row path's own kernels).
 //   launch_select_topk   the k smallest of the grid x kScanWaves x 64 published keys, sorted: its k-th output is H.
 //   k_bound_collect_wide bound_collect against that H with a list of QV_BOUND_WIDE_CAND_CAP rows; workgroup 0 leaves H in the control words
 //                    (thr_inv, zero = no finite H) for the re-score, as the k <= 64 tail does.
@@ -1751,6 +1756,60 @@ int bound_wide_route(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, 
     if (plane == 2 || !has_plane8) return 1;
     return plane == 1 || bound_wide_auto(kBoundWide8Floor, rule_metric, dim, rows, k) ? 2 : 1;
 }
+// The FILTERED wide form's rule (one query over a candidate bitmap: qv_index_search_masked, a row set, a where-filter made into a set): a knob
+// of its own (qv_index_set_bound_scan_wide_filtered / QV_BOUND_SCAN_WIDE_FILTERED), independent of the unfiltered form's and of the k <= 64
+// knobs; the plane it starts on is the single-query filtered plane knob's (bound_one_filtered).  What the kernels need is what the unfiltered
+// form needs, and on top: a tile that holds a candidate, and MORE candidates than results — a k that takes every candidate has nothing to
+// reject, and a shorter set keeps its path and its clamped count.
+// AUTOMATIC: the unfiltered floor (bound_wide_auto: never a shape the unfiltered rule declines — cosine and dot, k <= 1000) and, on top, the
+// cells of profiles/LAB_r25_bound_scan_wide_filtered.md in which the form ran ahead of the path the filtered call takes today (the filtered
+// k_flat_scan_wide up to k = 128, the key-per-row path above) at EVERY measured k — 65, 100, 128, 129, 256, 1000 — by more than both arms'
+// spread, and the 8-bit plane first only where it also beat the bfloat16 copy first by the same standard; cosine, device-pointer row-set
+// calls, five alternating rounds of 20 calls.  A cell is a shape and a candidate-tile fraction f = candidate tiles / tiles, which is what
+// the host can tell apart: every row selected and a random half (f = 1), a random 1 % of the rows (f = 0.476), one tile in ten (f = 0.100).
+// us per call at k = 100, today / bfloat16 first / 8-bit first (spreads <= 9 us at this k):
+//   768 dims   1M   f 1: 494 / 320 / 246     f 0.476: 479 / 232 / 200     f 0.100: 494 / 131 / 158
+//              3M   f 1: 1343 / 776 / 493    f 0.476: 1331 / 468 / 336    f 0.100: 1354 / 311 / 245
+//              10M  f 1: 4339 / 2427 / 1299  f 0.476: 4327 / 1322 / 742   f 0.100: 4339 / 375 / 277
+//   128 dims   10M  f 1: 796 / 526 / 355     f 0.476: 760 / 332 / 240     f 0.100: 778 / 160 / 163
+// The bfloat16 copy first lost NO cell against today's path.  The 8-bit plane first lost against the bfloat16 copy first at f = 0.100 for
+// 1M x 768 (every k: 158 against 131) and for 10M x 128 (five of six k: 163 against 160), and at f = 0.476 for 1M x 768 it did not clear the
+// spread at k = 129 (204 against 229 with a spread of 27): those cells start on the bfloat16 copy.  NOT measured, so never automatic: what
+// the unfiltered rule leaves out (fewer than 1M rows, narrower than 128 dimensions, 128 <= dim < 768 below 10M rows, k above 1000, QV_L2
+// indexes with the planes), and fewer candidate tiles than one in ten.  Fractions in per mille of the tiles; 0 rows: never automatic.
+struct BoundWideFilterFloor {
+    uint32_t wide_rows, wide_frac;        // dim >= kBoundWideDim: from wide_rows rows, ct * 1000 >= n_tiles * wide_frac
+    uint32_t big_rows, big_frac;          // ... from big_rows rows on, big_frac in its place (0 rows: no such size)
+    uint32_t narrow_rows, narrow_frac;    // the unfiltered floor's narrow class (its narrow_dim <= dim < kBoundWideDim)
+};
+constexpr BoundWideFilterFloor kBoundWideFilterFloor = {1000000, 100, 0, 0, 10000000, 100};          // the filtered wide form against today's filtered path
+constexpr BoundWideFilterFloor kBoundWide8FilterFloor = {1000000, 1000, 3000000, 100, 10000000, 475};   // ... and the 8-bit plane first against the bfloat16 copy first
+static_assert(kBoundWide8FilterFloor.wide_rows >= kBoundWideFilterFloor.wide_rows && kBoundWide8FilterFloor.wide_frac >= kBoundWideFilterFloor.wide_frac &&
+              kBoundWide8FilterFloor.big_frac >= kBoundWideFilterFloor.wide_frac && kBoundWide8FilterFloor.narrow_rows >= kBoundWideFilterFloor.narrow_rows &&
+              kBoundWide8FilterFloor.narrow_frac >= kBoundWideFilterFloor.narrow_frac && kBoundWideFilterFloor.wide_rows >= kBoundWideFloor.wide_rows &&
+              kBoundWideFilterFloor.narrow_rows >= kBoundWideFloor.narrow_rows, "8-bit first is never automatic where the form is not, nor the form below the unfiltered floor");
+static bool bound_wide_filtered_auto(const BoundFloor& f, const BoundWideFilterFloor& g, int rule_metric, uint32_t dim, uint32_t rows, uint32_t k, uint32_t candidate_tiles) {
+    if (!bound_wide_auto(f, rule_metric, dim, rows, k)) return false;
+    const uint64_t n_tiles = ((uint64_t)rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
+    const bool wide = dim >= kBoundWideDim, big = wide && g.big_rows != 0 && rows >= g.big_rows;
+    const uint32_t floor = wide ? g.wide_rows : g.narrow_rows, frac = big ? g.big_frac : wide ? g.wide_frac : g.narrow_frac;
+    return ct != 0 && floor != 0 && rows >= floor && ct * 1000 >= n_tiles * frac;
+}
+int bound_wide_route_filtered(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered, bool has_plane, bool has_plane8,
+                              uint32_t candidate_tiles, uint64_t candidates) {
+    static const int env_wide = env_int("QV_BOUND_SCAN_WIDE_FILTERED", 0);
+    const int mode = wide_mode ? wide_mode : env_wide;
+    if (mode == 2) return 0;
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)rows + 63) / 64);
+    const bool metric_ok = rule_metric == QV_COSINE || rule_metric == QV_DOT || rule_metric == QV_RULE_L2_PLANES;
+    if (nq != 1 || k <= (uint32_t)kMaxFusedK || k > kBoundWideMaxK || !metric_ok || !has_plane) return 0;
+    if ((dim & 15u) != 0 || dim == 0 || dim > kBoundMaxDim || n_tiles < 8 || k >= rows || !flat_select_redo_one_serves(n_tiles)) return 0;
+    if (candidate_tiles == 0 || candidates <= (uint64_t)k) return 0;
+    if (mode != 1 && !bound_wide_filtered_auto(kBoundWideFloor, kBoundWideFilterFloor, rule_metric, dim, rows, k, candidate_tiles)) return 0;
+    const int plane = bound_plane_mode(bound_one_filtered, plane_mode_filtered);
+    if (plane == 2 || !has_plane8) return 1;
+    return plane == 1 || bound_wide_filtered_auto(kBoundWide8Floor, kBoundWide8FilterFloor, rule_metric, dim, rows, k, candidate_tiles) ? 2 : 1;
+}
 // the wide form's buffer.  The redo's workspace overlays the rest: it is written only when every bound stage has ended.
 struct BoundWideLayout { void* redo; uint64_t* lists; uint32_t* seed_rows; float* seed_dist; void* sel_ws; uint32_t* cand; uint64_t* keys; uint32_t* sel; uint32_t* lo_all; size_t end, total; };
 static BoundWideLayout bound_wide_layout(void* base, const ScanPlan& p, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr) {
@@ -1771,8 +1830,8 @@ static BoundWideLayout bound_wide_layout(void* base, const ScanPlan& p, uint32_t
 }
 size_t bound_scan_wide_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log) { return bound_wide_layout(nullptr, p, k, n_tiles, dim, log).total; }
 hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                                  uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first) {
-    // (whether the path is TAKEN is bound_wide_route's decision; here only what the kernels need)
+                                  uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first, bool masked) {
+    // (whether the path is TAKEN is bound_wide_route's decision, under a filter bound_wide_route_filtered's; here only what the kernels need)
     if (bound_wide_route(rule_metric(v), v.dim, v.n_rows, 1, k, 1, plane8_first ? 1 : 2, v.plane != nullptr, v.plane8 != nullptr) != (plane8_first ? 2 : 1) || !d_ctrl || !d_stats)
         return hipErrorInvalidValue;
     const uint32_t grid = p.grid;
@@ -1785,17 +1844,18 @@ hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const f
     const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * v.dim4 * 4 * sizeof(float);
     const uint32_t rgrid = std::min(kBoundWideRescoreGrid, (kBoundWideCandCap + kScanWaves - 1) / kScanWaves);
     if (n_keys <= k || (n_keys & 1u)) return hipErrorInvalidValue;
-    static const int trace = env_int("QV_TRACE", 0);                   // (an unfiltered line: one read per process, as qv_scan.hip's)
+    static const int trace = env_int("QV_TRACE", 0);                   // (one read per process, as qv_scan.hip's)
     if (trace) {
-        const char* stage = "k_bound_scan wide + select + k_bound_collect_wide + k_bound_rescore_wide";
-        if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8 wide + select + k_bound_collect_wide + k_bound_rescore_wide, then gated %s, then k_select_sort and the gated key-per-row redo (tiles=%u, k=%u)\n", stage, v.n_tiles, k);
+        const char* stage = masked ? "k_bound_scan wide filtered + select + k_bound_collect_wide + k_bound_rescore_wide" : "k_bound_scan wide + select + k_bound_collect_wide + k_bound_rescore_wide";
+        if (plane8_first) fprintf(stderr, "qv: scan kernel = k_bound_scan8 wide%s + select + k_bound_collect_wide + k_bound_rescore_wide, then gated %s, then k_select_sort and the gated key-per-row redo (tiles=%u, k=%u)\n", masked ? " filtered" : "", stage, v.n_tiles, k);
         else fprintf(stderr, "qv: scan kernel = %s, then k_select_sort and the gated key-per-row redo (tiles=%u, k=%u)\n", stage, v.n_tiles, k);
     }
-    auto run = [&](auto Mc) -> hipError_t {
+    auto run = [&](auto Mc, auto Mk) -> hipError_t {
         constexpr int M = decltype(Mc)::value;
-        hipError_t e = set_lds(k_bound_scan<M, false, true>, lds1);
+        constexpr bool MASKED = decltype(Mk)::value;                  // v.alive is the call's candidate bitmap: stage 1 skips the tiles without a candidate
+        hipError_t e = set_lds(k_bound_scan<M, MASKED, true>, lds1);
         if (e == hipSuccess) e = set_lds(k_bound_rescore_wide<M, false>, lds2);
-        if (e == hipSuccess && plane8_first) e = set_lds(k_bound_scan8<M, false, true>, lds8);
+        if (e == hipSuccess && plane8_first) e = set_lds(k_bound_scan8<M, MASKED, true>, lds8);
         if (e == hipSuccess && plane8_first) e = set_lds(k_bound_rescore_wide<M, true>, lds2);
         if (e != hipSuccess) return e;
         // what follows a stage's scan: H, the collect, the re-score — each behind `gate`, the flag of the stage in front (null: none)
@@ -1808,18 +1868,21 @@ hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const f
         };
         if (plane8_first) {
             BoundCtrl* ctrl8 = ctrl + 1;
-            hipLaunchKernelGGL((k_bound_scan8<M, false, true>), dim3(grid), dim3(kScanBlock), lds8, s, v, d_query, kBoundWideListLen, ctrl8, L.lo_all, L.lists, L.seed_rows, L.seed_dist);
+            hipLaunchKernelGGL((k_bound_scan8<M, MASKED, true>), dim3(grid), dim3(kScanBlock), lds8, s, v, d_query, kBoundWideListLen, ctrl8, L.lo_all, L.lists, L.seed_rows, L.seed_dist);
             e = finish(k_bound_rescore_wide<M, true>, ctrl8, (uint32_t*)nullptr, ctrl);
             if (e != hipSuccess) return e;
             uint32_t* gate8 = &ctrl8->flag;
-            hipLaunchKernelGGL((k_bound_scan<M, false, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, kBoundWideListLen, ctrl, L.lo_all, L.lists, L.seed_rows, L.seed_dist, (const uint32_t*)gate8);
+            hipLaunchKernelGGL((k_bound_scan<M, MASKED, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, kBoundWideListLen, ctrl, L.lo_all, L.lists, L.seed_rows, L.seed_dist, (const uint32_t*)gate8);
             return finish(k_bound_rescore_wide<M, false>, ctrl, gate8, (BoundCtrl*)nullptr);
         }
-        hipLaunchKernelGGL((k_bound_scan<M, false, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, kBoundWideListLen, ctrl, L.lo_all, L.lists, L.seed_rows, L.seed_dist, (const uint32_t*)nullptr);
+        hipLaunchKernelGGL((k_bound_scan<M, MASKED, true>), dim3(grid), dim3(kScanBlock), lds1, s, v, d_query, kBoundWideListLen, ctrl, L.lo_all, L.lists, L.seed_rows, L.seed_dist, (const uint32_t*)nullptr);
         return finish(k_bound_rescore_wide<M, false>, ctrl, (uint32_t*)nullptr, (BoundCtrl*)nullptr);
     };
-    hipError_t e = v.metric == QV_COSINE ? run(std::integral_constant<int, QV_COSINE>{})
-                 : v.metric == QV_DOT  ? run(std::integral_constant<int, QV_DOT>{}) : run(std::integral_constant<int, QV_L2>{});
+    auto run_metric = [&](auto Mk) -> hipError_t {
+        return v.metric == QV_COSINE ? run(std::integral_constant<int, QV_COSINE>{}, Mk)
+             : v.metric == QV_DOT  ? run(std::integral_constant<int, QV_DOT>{}, Mk) : run(std::integral_constant<int, QV_L2>{}, Mk);
+    };
+    hipError_t e = masked ? run_metric(std::true_type{}) : run_metric(std::false_type{});
     if (e != hipSuccess) return e;
     // the answer of whichever stage answered (sel[1]), then the exact redo of a search the bfloat16 stage handed back (its flag)
     e = launch_select_topk_counted(L.keys, kBoundWideCandCap, kBoundWideCandCap, L.sel, 1, k, k, d_rows_out, d_dist_out, s, L.sel + 1);

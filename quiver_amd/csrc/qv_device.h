@@ -280,7 +280,7 @@ int host_quantize_row8(uint32_t dim, const float* row, int8_t* out_bytes, float*
 // (scale8: the row's 8-bit scale, as host_quantize_row8 gives it); and those bytes back into biased codes u[dim]
 int host_quantize_row6(uint32_t dim, const float* row, float scale8, uint8_t* out_bytes, float* out_res);
 int host_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes);
-// The WIDE form of the single-query, unfiltered bound scan, 65 <= k <= kBoundWideMaxK (qv_bound_scan.hip): stage 1 publishes every wave's 64
+// The WIDE form of the single-query bound scan, unfiltered or over a candidate bitmap, 65 <= k <= kBoundWideMaxK (qv_bound_scan.hip): stage 1 publishes every wave's 64
 // smallest upper bounds, H is the k-th smallest key of their union (launch_select_topk), the collect has a list of QV_BOUND_WIDE_CAND_CAP rows,
 // the re-score writes a key per survivor and launch_select_topk_counted takes the k best.  A search it cannot decide is redone by the
 // key-per-row path behind a device word (launch_flat_select_redo_one).  Whether a search takes it is bound_wide_route's answer — a knob of its
@@ -290,11 +290,18 @@ constexpr uint32_t kBoundWideStatsWord = 10;   // the wide form's counters: [10]
 // 0: no wide form; 1: the bfloat16 copy first; 2: the 8-bit plane first.  wide_mode: QV_BOUND_SCAN_* (0: QV_BOUND_SCAN_WIDE of the environment,
 // read once, else automatic); plane_mode: the index's qv_index_set_bound_plane (0: QV_BOUND_PLANE, else automatic)
 int bound_wide_route(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, bool has_plane, bool has_plane8);
+// The same question for ONE query over a candidate bitmap (a mask, a row set, a where-filter made into a set).  wide_mode: the filtered form's own
+// knob (qv_index_set_bound_scan_wide_filtered; 0: QV_BOUND_SCAN_WIDE_FILTERED, else automatic); plane_mode_filtered: the single-query filtered
+// plane knob (qv_index_set_bound_plane_filtered); candidate_tiles: the tiles that hold a candidate, as the host knows them; candidates: the live
+// rows the filter selects — the form needs more of them than results.
+int bound_wide_route_filtered(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered, bool has_plane, bool has_plane8,
+                              uint32_t candidate_tiles, uint64_t candidates);
 size_t bound_scan_wide_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr);
 // d_ctrl: the stream's control words (2 BoundCtrl, kept zero but for the bfloat16 stage's flag, which every search writes before it is read);
 // d_stats: the index's counters.  Enqueues everything, the gated exact redo included: nothing is read on the host.
 hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                                  uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first);
+                                  uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first,
+                                  bool masked = false);   // v.alive is the call's candidate bitmap: stage 1's SKIP forms; the stages behind read v.alive as they stand
 constexpr uint32_t kBound6StatsWord = 7;   // the 6-bit stage's counters: [7] candidates it passed to the refine, [8] hand-backs, [9] searches
 constexpr uint32_t kBound6CandCap = 262144;   // rows the refine walks on the 8-bit plane (1 MiB of the workspace)
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches

@@ -432,6 +432,13 @@ class DeviceIndex:
         set_bound_plane (qv_index_set_bound_scan_wide)"""
         check(lib().qv_index_set_bound_scan_wide(self._h, self.BOUND_SCAN.get(mode, mode)))
 
+    def set_bound_scan_wide_filtered(self, mode):
+        """the wide form for ONE filtered query, 65 <= k <= 1024 (search_masked, search_rowsets, search_rowsets_device, search_where): "auto"
+        (the measured shapes: cosine / dot, k <= 1000, from 1M rows of 768 dimensions or 10M rows of 128, a candidate in one tile in ten or more), "always" (whenever the shape applies and the filter leaves more live candidates than
+        results), "never"; a knob of its own, independent of set_bound_scan_wide — which plane comes first follows set_bound_plane_filtered;
+        the counters are bound_scan_wide_stats' (qv_index_set_bound_scan_wide_filtered)"""
+        check(lib().qv_index_set_bound_scan_wide_filtered(self._h, self.BOUND_SCAN.get(mode, mode)))
+
     def bound_scan_wide_stats(self) -> dict:
         """survivors the last wide search passed to its re-score, wide searches handed back to the exact path, searches that took the wide
         form, whether the bfloat16 copy exists"""
