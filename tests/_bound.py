@@ -129,21 +129,22 @@ def stage1(metric, state, q, rres=None):
     return {"s": s, "lo": lo, "hi": hi, "unsure": unsure, "qn": qn, "dim": dim}
 
 
-def decide(st1, k, alive=None):
+def decide(st1, k, alive=None, cap=CAND_CAP):
     """the rest of stage 1 for one k: the threshold H (the k-th smallest upper bound among the live rows the bound is sure of; None when
     there are fewer than k), which rows are passed on (d_lo <= H; a row the bound says nothing about always), and whether the exact scan
-    has to answer instead (no H, more survivors than the list holds, a query norm the bound does not work with)"""
+    has to answer instead (no H, more survivors than the list holds — `cap` rows: the k <= 64 forms' list unless the caller names another —, a
+    query norm the bound does not work with)"""
     lo, hi, unsure = st1["lo"], st1["hi"], st1["unsure"]
     live = np.ones(len(lo), bool) if alive is None else np.asarray(alive, bool)
     his = np.sort(hi[live & ~unsure])
     H = his[k - 1] if len(his) >= k else None
     passed = live & (unsure | (lo <= (H if H is not None else np.float32(-np.inf))))
-    hand_back = H is None or int(passed.sum()) > CAND_CAP or not query_ok(st1["qn"], st1["dim"])
+    hand_back = H is None or int(passed.sum()) > cap or not query_ok(st1["qn"], st1["dim"])
     return dict(st1, H=H, passed=passed, count=int(passed.sum()), hand_back=hand_back)
 
 
-def reference(metric, state, q, k, alive=None, rres=None):
-    return decide(stage1(metric, state, q, rres), k, alive)
+def reference(metric, state, q, k, alive=None, rres=None, cap=CAND_CAP):
+    return decide(stage1(metric, state, q, rres), k, alive, cap)
 
 
 def oracle_top(metric, rows, q, k, alive=None):

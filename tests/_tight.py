@@ -103,20 +103,21 @@ def planted(metric, dim, k, seed=0):
     return {"rows": rows, "q": q, "target": target, "near": near_at, "band": band_at, "ordinary": ordinary, "k": k, "metric": metric}
 
 
-def conditions(case, alive=None):
-    """(a) - (d) of the planted case on the CPU; -> (the oracle's rows, its float32 distances, the reference's survivor count)"""
+def conditions(case, alive=None, cap=B.CAND_CAP):
+    """(a) - (d) of the planted case on the CPU; -> (the oracle's rows, its float32 distances, the reference's survivor count).  cap: the
+    candidate list (d) is taken against — the k <= 64 forms' unless the caller names the wide form's"""
     metric, rows, q, k, t = case["metric"], case["rows"], case["q"], case["k"], case["target"]
     st = B.RowState(rows)
     er, ed = B.oracle_top(metric, rows, q, k, alive)
     assert t in er.tolist() and er[k - 1] == t, ("(a) r* is the oracle's k-th neighbour", er)
-    ref = B.reference(metric, st, q, k, alive)
+    ref = B.reference(metric, st, q, k, alive, cap=cap)
     assert ref["H"] is not None and not ref["unsure"][t]
     assert ref["H"] == ref["hi"][case["band"]].min(), "H comes from the best competitor"
     assert ref["lo"][t] <= ref["H"], ("(b) r* survives with the residual the reference computes", ref["lo"][t], ref["H"])
     short = st.rres.copy(); short[t] = np.float32(float(st.rres[t]) * SHORT)
-    bad = B.reference(metric, st, q, k, alive, rres=short)
+    bad = B.reference(metric, st, q, k, alive, rres=short, cap=cap)
     assert bad["H"] == ref["H"] and bad["lo"][t] > bad["H"], ("(c) a residual 10 % short rejects r*", bad["lo"][t], bad["H"])
-    assert k <= ref["count"] <= B.CAND_CAP and not ref["hand_back"], ("(d) the survivors fit the candidate list", ref["count"])
+    assert k <= ref["count"] <= cap and not ref["hand_back"], ("(d) the survivors fit the candidate list", ref["count"])
     return er, ed, ref["count"]
 
 

@@ -85,21 +85,33 @@ def test_rows_and_bits_of_the_exact_path(metric, n, dim):
 
 
 def test_nearest_rows_stored_together():
-    """rows 0 .. 1023 are the 1024 nearest: sixteen neighbouring tiles hold the whole answer, so the published lists may hold fewer than k
-    of the k smallest upper bounds — H only looser, or the list overflows — and the results are exact all the same"""
+    """rows 0 .. 1023 are the 1024 nearest: sixteen neighbouring tiles hold the whole answer.  With 3 125 tiles a wave walks two, a stride of
+    tiles apart (tile t belongs to wave t mod (4 * grid), 1 564 waves on 256 compute units), so the sixteen tiles belong to sixteen
+    DIFFERENT waves, each of which publishes all 64 of its near rows: nothing is dropped, H is the exact k-th smallest upper bound, and the
+    survivor count is the CPU model's (tests/_wide.py).  The case in which one wave holds more than it publishes is
+    tests/test_gpu_bound_wide_counts.py's."""
+    from quiver_amd.device_index import device_info
+    from tests import _wide as Wd
     dim, n = 64, 200_000                                                # (3 125 tiles: a wave walks several)
     rng = np.random.default_rng(71)
     q = rng.standard_normal(dim).astype(np.float32)
     rows = rng.standard_normal((n, dim)).astype(np.float32)
     rows[:1024] = (q[None, :] + np.float32(0.05) * rows[:1024]).astype(np.float32)
     idx = make("cosine", dim); idx.add(rows)
+    n_tiles = (n + 63) // 64
+    grid, stride = Wd.plan(n_tiles, device_info(0)["cus"])
+    stages = {plane: Wd.stage_of(0, plane, rows, q) for plane in ARMS}
     for k in (1024, 500):
         er, ed = O.exact_search(0, rows, q, k)
         assert set(er.tolist()) <= set(range(1024))
         for plane in ARMS:
             (r, d, c), inc = both(idx, q, k, plane)
-            assert inc["took"] == 1, inc
+            assert answered(inc), inc
             assert np.array_equal(r[0], er) and np.array_equal(d[0].view(np.uint32), ed.view(np.uint32)), (k, plane)
+            m = Wd.decide_wide(stages[plane], k, np.ones(n, bool), n_tiles, grid)
+            print("k %d %s: survivors %d, the model %d" % (k, plane, inc["cand"], m["count"]))
+            assert not m["hand_back"] and (stride < 16 or m["dropped"] == 0), (k, plane, m["dropped"])
+            assert inc["cand"] == m["count"], (k, plane, inc, m["count"])
     idx.close()
 
 
