@@ -2,6 +2,8 @@
 (`plan`), a host model of what the index must hold after each step (`Model`), and a checker of the per-row arrays the bound scan's
 interval rests on, as DeviceIndex.debug_read returns them (`check_state`).  tests/test_bound_history_cpu.py inspects the schedules and
 shows what the checker catches without a device; tests/test_gpu_bound_history.py replays them on one.  TEST INFRASTRUCTURE ONLY.
+Every round of searches ends with searches of the wide form (65 <= k <= 1024, `WIDE_ROUTES`), whose counters — the survivor count of stage 1
+among them — `Model.predict_wide` gives from tests/_wide.decide_wide over the row states the model keeps step by step.
 
 The layouts are restated HERE in numpy from the comments of quiver_amd/csrc/qv_bound.h and qv_misc.hip — the 8-bit plane [tile][dim / 16]
 [64 rows][16 B], the 6-bit plane [tile][group of 64 dims][3][64 rows][16 B] with the biased code of dims 0 - 47 in the low six bits of byte
@@ -17,6 +19,8 @@ from tests import _bound6 as B6
 from tests import _bound8 as B8
 from tests import _bound_l2 as BL
 from tests import _oracle as O
+from tests import _wide as Wd
+from tests import _widths as W
 from tests.test_gpu_fuzz import _vectors
 from tests.test_gpu_row_state import Expected, check, decode, mixture
 
@@ -28,6 +32,13 @@ FIRST = (300, 449, 512, 513, 700)                   # 300 rows: fewer than 8 til
 KS = (1, 10, 63, 64)
 # (form, plane): one query or a shared pass of 2 - 8, filtered or not, each on either plane; the 6-bit stage in front of one unfiltered query
 ROUTES = (("1", "bf16"), ("1", "8bit"), ("1", "6bit"), ("mq", "bf16"), ("mq", "8bit"), ("1f", "bf16"), ("1f", "8bit"), ("mqf", "bf16"), ("mqf", "8bit"))
+# the wide form of one query's bound scan, 65 <= k <= 1024 (tests/_wide.py): unfiltered ("w") or over a candidate bitmap ("wf"), either plane first
+WIDE_ROUTES = (("w", "bf16"), ("w", "8bit"), ("wf", "bf16"), ("wf", "8bit"))
+KS_WIDE = (65, 100, 129, 500, 1024)
+# zero, nan: queries bound_scan_norm_ok declines; all_but_one: k = live candidates - 1, the largest k the form takes; all: k = live candidates,
+# which the dispatch declines; unsure: k above the candidates the bound is sure of and below the live ones — no finite H
+WIDE_DELIBERATE = ("all_but_one", "zero", "all", "nan", "unsure")
+WIDE_PER_ROUND = 2                                  # wide searches a round of searches gains, a deliberate one among them where one is due
 WRITERS = ("add", "add_synthetic", "add_partial_tile", "add_growth", "update", "update_rows", "update_rows_device", "remove", "revival")
 ARRAYS = ("rnorm", "rres", "plane", "rowmaj16", "plane8", "rres8", "rscale8", "plane6", "rres6")
 FIRST_TILES = 16                                    # the first add reserves max(its tiles, 16) tiles: an add past them grows the arrays
@@ -245,6 +256,66 @@ class Model:
             out["cand6"] = out["cand8"] = out["cand"] = None
         return out
 
+    # ---- the wide form (65 <= k <= 1024) ----
+    def stage_wide(self, arm, q, fault=None, stale=None):
+        """the interval of every row for q as the wide form's stage 1 on `arm` computes it, from the states kept incrementally.  fault
+        "stale" with stale = (row, its previous vector): that row keeps the interval of the vector it held before — a plane a writer missed"""
+        st16, st8, _ = self.states()
+
+        def of(s16, s8):
+            if arm == "8bit" and B8.quantize_query(q) is None:                               # a zero or non-finite query: the intervals tests/_bound8.reference8 gives it
+                r = B8.reference8(self.mid, s8, q, 1)
+                return {"lo": r["lo"], "hi": r["hi"], "unsure": r["unsure"], "qn": B.chain_norm(q), "dim": self.dim}
+            if arm == "8bit":
+                return W.stage8_of(self.mid, s8, q)
+            return BL.stage1(s16, q) if self.cfg["metric"] == "l2" else B.stage1(self.mid, s16, q)
+        st = of(st16, st8)
+        if fault == "stale" and stale is not None:
+            row, vec = stale
+            old = of(B.RowState(vec[None, :]), B8.RowState8(vec[None, :]))
+            st = dict(st, lo=st["lo"].copy(), hi=st["hi"].copy(), unsure=st["unsure"].copy())
+            for f in ("lo", "hi", "unsure"):
+                st[f][row] = old[f][0]
+        return st
+
+    def predict_wide(self, step, cus, fault=None, cache=None):
+        """what bound_scan_wide_stats must show for one forced wide search: the increments of `searches` ("took") and `hand_backs` ("back")
+        and the survivor count of the stage that answered ("cand"; None where the bfloat16 stage hands back too, or the form is not taken).
+        The dispatch takes the form on 8 tiles or more when there are MORE live candidates than results (under a filter that also means a
+        tile with a candidate); the 8-bit stage's count stands where it answers, otherwise the search is the bfloat16 stage's.  The decision
+        is tests/_wide.decide_wide over the call's candidate bitmap; at these sizes a wave owns one tile and publishes all of it (asserted).
+        fault: what tests/test_bound_history_cpu.py plants — "dead" (dead rows keyed: every written row, under a filter every selected
+        one), "unselected" (under a filter, every live row keyed), "rank" (H one rank early), "stale" (stage_wide's)."""
+        arm, q, k = step["plane"], step["qs"][0], step["k"]
+        sel = self.selected(step)[0]
+        live = self.candidates(sel)
+        n_tiles = (self.n + 63) // 64
+        out = {"took": 0, "back": 0, "cand": None}
+        if n_tiles < 8 or not 64 < k <= Wd.MAX_K or k >= int(live.sum()):
+            return out
+        out["took"] = 1
+        grid = Wd.plan(n_tiles, cus)[0]
+        kw = {}
+        if fault == "dead":
+            kw["key_live"] = np.ones(self.n, bool) if sel is None else sel
+        elif fault == "unselected":
+            kw["key_live"] = self.alive
+        elif fault == "rank":
+            kw["rank"] = k - 1
+        stale = (step["stale_row"], step["stale_vec"]) if step.get("stale_row") is not None else None
+        cache = {} if cache is None else cache                                               # (arm, stale) -> intervals: one step under several faults
+        for a in (("8bit", "bf16") if arm == "8bit" else ("bf16",)):
+            key = (a, fault == "stale")
+            if key not in cache:
+                cache[key] = self.stage_wide(a, q, fault, stale)
+            d = Wd.decide_wide(cache[key], k, live, n_tiles, grid, **kw)
+            assert d["dropped"] == 0, (n_tiles, grid, d["dropped"])
+            if not d["hand_back"]:
+                out["cand"] = d["count"]
+                return out
+        out["back"] = 1
+        return out
+
 
 # ---- the schedule ----------------------------------------------------------------------------------------------------------------------
 def _facets(rng, m):
@@ -254,12 +325,22 @@ def _facets(rng, m):
 PREDS = ([("u32", "lt", 6)], [("u32", "in", [1, 3, 5, 7, 8, 9])], [("u32", "ne", 0)], [("f64", "ge", -0.5)], [("f64", "lt", 0.9), ("u32", "ge", 2)])
 
 
-def plan(seed):
+def is_wide(step):
+    return step["kind"] == "search" and step["form"] in ("w", "wf")
+
+
+def plan(seed, wide=True):
     """-> (config, steps): a pure function of the seed.  A step is a dict with "kind": a writer ("add", "add_synthetic", "remove", "update",
-    "update_rows" with "device": bool), "facets", "rowset", or "search" (form, plane, call, qs, k, filt, deliberate)."""
+    "update_rows" with "device": bool), "facets", "rowset", or "search" (form, plane, call, qs, k, filt, deliberate).
+    wide: every round of searches ends with WIDE_PER_ROUND searches of the wide form (`is_wide`; one query, form "w" or "wf", and beside the
+    keys above "stale_row" / "stale_vec": the last overwritten row and its previous vector).  They are drawn from a generator of their own and
+    read the planning model only: without them the steps are plan(seed, wide=False)'s."""
     cfg = config(seed)
     dim, style = cfg["dim"], cfg["style"]
     rng = np.random.default_rng(77_000 + seed)
+    wrng = np.random.default_rng(78_000 + seed)
+    wcount = {"route": 5 * seed, "call": seed, "query": seed}
+    wqueue = [WIDE_DELIBERATE[(seed + i) % len(WIDE_DELIBERATE)] for i in range(len(WIDE_DELIBERATE))]
     m = Model(cfg, derive=False)
     steps, pending, replaced = [], [], []           # blocks whose facets are not set yet; (row, its previous vector) of the last overwrites
     count = {"search": 0, "rows_list": seed, "query": seed, "call": seed}
@@ -381,7 +462,124 @@ def plan(seed):
     def grown():
         return (m.n + 63) // 64 > max(FIRST_TILES, (len(steps[0]["vecs"]) + 63) // 64)
 
+    # ---- the wide searches: drawn from wrng; rng, count, replaced and the planning model are read, never moved ----
+    def wide_query():
+        """a stored row, a row that was just replaced, the previous vector of a replaced row, the vector of a DEAD row (a kernel that keys
+        tombstones puts it at the head of a list), a fresh vector — never one the bound declines"""
+        which = wcount["query"] % 5; wcount["query"] += 1
+        new = [r for r, _ in replaced if not m.declined[r]]
+        old = [v for _, v in replaced if not declined_rows(v[None, :])[0]]
+        dead = np.flatnonzero(~m.alive & ~m.declined)
+        if which == 1 and new:
+            return m.rows[new[-1]].copy()
+        if which == 2 and old:
+            return old[-1].copy()
+        if which == 3 and len(dead):
+            return m.rows[int(wrng.choice(dead))].copy()
+        if which == 4:
+            q = vectors(wrng, 8, dim, "gauss" if style == "mixture" else style)[0].copy()
+            if not declined_rows(q[None, :])[0]:
+                return q
+        return m.rows[int(wrng.choice(np.flatnonzero(m.alive & ~m.declined)))].copy()
+
+    def wide_call():
+        call = ("masked", "rowsets", "where")[wcount["call"] % 3]; wcount["call"] += 1
+        return call
+
+    def wide_filter(call):
+        names = sorted(n for n in m.sets if n != "few")
+        if call == "masked":
+            return wrng.random(m.n) < float(wrng.choice([0.9, 0.6]))
+        if call == "rowsets":
+            return [names[int(wrng.integers(len(names)))]]
+        return [list(PREDS[int(wrng.integers(len(PREDS)))])]
+
+    def wide_counts(step):
+        """(live candidates, of them the ones the bound is sure of)"""
+        live = m.candidates(m.selected(step)[0])
+        return int(live.sum()), int((live & ~m.declined).sum())
+
+    def wide_push(step, k):
+        row, vec = replaced[-1] if replaced else (None, None)
+        step.update(k=int(k), stale_row=row, stale_vec=None if vec is None else vec.copy(),
+                    after={"growth": grown(), "update_rows": any(s["kind"] == "update_rows" for s in steps), "tiles": (m.n + 63) // 64})
+        push(step)
+
+    def wide_step(form, plane, q, deliberate=None):
+        step = {"kind": "search", "form": form, "plane": plane, "qs": q[None, :].copy(), "deliberate": deliberate, "call": "plain", "filt": None}
+        if form == "wf":
+            call = wide_call()
+            step.update(call=call, filt=wide_filter(call))
+        return step
+
+    def wide_k(step):
+        """a member of KS_WIDE below the candidates the bound is sure of: the drawn one, else the largest that is (None: there is none)"""
+        sure = wide_counts(step)[1]
+        k = int(wrng.choice(KS_WIDE))
+        below = [x for x in KS_WIDE if x < sure]
+        return k if k < sure else below[-1] if below else None
+
+    def wide_plain():
+        form, plane = WIDE_ROUTES[wcount["route"] % len(WIDE_ROUTES)]; wcount["route"] += 1
+        step = wide_step(form, plane, wide_query())
+        k = wide_k(step)
+        if k is not None:
+            wide_push(step, k)
+
+    def wide_deliberate(kind):
+        """-> whether the case could be scheduled now"""
+        form, plane = WIDE_ROUTES[wcount["route"] % len(WIDE_ROUTES)]
+        q = m.rows[int(wrng.choice(np.flatnonzero(m.alive & ~m.declined)))].copy()
+        if kind in ("zero", "nan"):
+            if kind == "zero":
+                q[:] = 0.0
+            else:
+                q[dim // 2] = np.nan
+            step = wide_step(form, plane, q, kind)
+            k = wide_k(step)
+        else:
+            # a k of 65 to 1024 fixed by the candidates: unfiltered on a small index, else under a set or a predicate that leaves so few, else
+            # under a mask of about 600 rows (with every row the bound declines in it, where the case needs them)
+            options = [("plain", None)] if form == "w" else []
+            call = wide_call()
+            if call == "rowsets":
+                options += [("rowsets", [n]) for n in sorted(m.sets) if n != "few"]
+            elif call == "where":
+                options += [("where", [list(p)]) for p in PREDS]
+            mask = wrng.random(m.n) < min(1.0, 600.0 / max(int(m.alive.sum()), 1))
+            if kind == "unsure":
+                mask |= m.declined
+            options.append(("masked", mask))
+            step = k = None
+            for call, filt in options:
+                s = {"kind": "search", "form": "w" if call == "plain" else "wf", "plane": plane, "qs": q[None, :].copy(), "deliberate": kind, "call": call, "filt": filt}
+                live, sure = wide_counts(s)
+                want = {"all_but_one": live - 1, "all": live, "unsure": sure + 1 if live - sure >= 2 else 0}[kind]
+                if 65 <= want <= Wd.MAX_K:
+                    step, k = s, want
+                    break
+        if k is None:
+            return False
+        wcount["route"] += 1
+        wide_push(step, k)
+        return True
+
+    def wide_round():
+        left = WIDE_PER_ROUND
+        if (m.n + 63) // 64 >= 8:
+            for kind in list(wqueue):                                                        # one deliberate case a round, the first that can be met
+                if wide_deliberate(kind):
+                    wqueue.remove(kind); left -= 1
+                    break
+        for j in range(left):
+            wide_plain()
+
     def search_round(extra=None):
+        _search_round(extra)
+        if wide:
+            wide_round()
+
+    def _search_round(extra=None):
         for j in range(3):
             form, plane = routes[(5 * seed + count["search"]) % len(routes)]; count["search"] += 1
             search(form, plane)

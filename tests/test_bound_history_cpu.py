@@ -1,7 +1,9 @@
 """tests/_history.py without a device: the schedules tests/test_gpu_bound_history.py replays cover every writer, route, metric and
 dimension (from plan(seed) alone); the state checker passes on arrays fabricated from the host twins and FAILS on each mutant a faulty writer
 or plane kernel would leave; and the CPU models of the three stages hand back at most one search in ten of a schedule beside the deliberate
-ones (a set of fewer than k rows, a zero query, a NaN query)."""
+ones (a set of fewer than k rows, a zero query, a NaN query).  The searches of the wide form (65 <= k <= 1024) that end every round leave
+the rest of a schedule as it was, cover every wide route, k, filtered call and deliberate case, stay within the same cap, and carry survivor
+counts that each planted fault of stage 1 moves (H.Model.predict_wide)."""
 import collections
 import functools
 
@@ -19,13 +21,29 @@ def plans():
     return {seed: H.plan(seed) for seed in H.SEEDS}
 
 
-def test_the_plan_is_a_pure_function_of_the_seed():
-    (c0, s0), (c1, s1) = H.plan(7), H.plan(7)
+def same_plan(p0, p1):
+    (c0, s0), (c1, s1) = p0, p1
     assert c0 == c1 and len(s0) == len(s1)
     for a, b in zip(s0, s1):
         assert a.keys() == b.keys() and a["kind"] == b["kind"]
         for key in a:
             assert repr(a[key]) == repr(b[key]) if not isinstance(a[key], np.ndarray) else np.array_equal(a[key], b[key], equal_nan=True), key
+
+
+def test_the_plan_is_a_pure_function_of_the_seed():
+    same_plan(H.plan(7), H.plan(7))
+    assert any(H.is_wide(s) for s in H.plan(7)[1])
+
+
+@pytest.mark.parametrize("seed", H.SEEDS)
+def test_the_wide_searches_leave_the_schedule_as_it_was(seed):
+    """without its wide steps a plan is plan(seed, wide=False), step by step: they draw from a generator of their own"""
+    cfg, steps = plans()[seed]
+    narrow = [s for s in steps if not H.is_wide(s)]
+    assert len(narrow) < len(steps)
+    before = H.plan(seed, wide=False)
+    same_plan((cfg, narrow), before)
+    assert not any(H.is_wide(s) for s in before[1])
 
 
 def test_the_schedules_cover_every_writer_route_metric_and_dimension():
@@ -41,7 +59,7 @@ def test_the_schedules_cover_every_writer_route_metric_and_dimension():
         n_final = sum(len(s["vecs"]) if s["kind"] == "add" else s["n"] for s in steps if s["kind"] in ("add", "add_synthetic"))
         assert n_final <= 2100 < 4096                                                       # below the candidate list's capacity: no overflow hand-back
         for s in steps:
-            if s["kind"] != "search":
+            if s["kind"] != "search" or H.is_wide(s):                                        # (the wide searches: the test below)
                 continue
             searches += 1
             below += s["after"]["tiles"] < 8
@@ -183,7 +201,7 @@ def test_the_models_hand_back_at_most_one_search_in_ten(seed):
         if s["kind"] != "search":
             m.apply(s)
             continue
-        if s["after"]["tiles"] < 8:
+        if s["after"]["tiles"] < 8 or H.is_wide(s):                                          # (the wide searches: the tests below)
             continue
         back = {"bf16": 0, "8bit": 0, "6bit": 0}
         for q, sel in zip(s["qs"], m.selected(s)):
@@ -200,3 +218,129 @@ def test_the_models_hand_back_at_most_one_search_in_ten(seed):
     print("seed %d (%s, %d dims, %s): %d searches, %d with a predicted hand-back, deliberate %s" % (seed, cfg["metric"], cfg["dim"], cfg["style"], plain, backs, dict(seen)))
     assert backs * 10 <= plain and plain >= 15
     assert set(seen) == {"zero", "nan", "short"}
+
+
+# ---- the wide form (65 <= k <= 1024) ----------------------------------------------------------------------------------------------------------
+CUS = 256                                           # compute units the models lay the grid out for: from 5 on a wave owns one tile at these sizes, whatever the device has
+FAULTS = ("dead", "unselected", "rank", "stale")    # H.Model.predict_wide's
+
+
+def test_the_schedules_cover_every_wide_route_k_call_and_deliberate_case():
+    rm, ks, calls, deliberate, queries = collections.Counter(), collections.Counter(), collections.Counter(), collections.Counter(), collections.Counter()
+    total = below = 0
+    for seed, (cfg, steps) in plans().items():
+        metric, here = cfg["metric"], set()
+        m = H.Model(cfg, derive=False)
+        for s in steps:
+            if s["kind"] != "search":
+                m.apply(s)
+                continue
+            if not H.is_wide(s):
+                continue
+            total += 1
+            below += s["after"]["tiles"] < 8
+            assert len(s["qs"]) == 1 and (s["form"], s["plane"]) in H.WIDE_ROUTES and (s["call"] == "plain") == (s["form"] == "w")
+            assert s["call"] in ("plain", "masked") or (len(s["filt"]) == 1 and s["filt"][0] is not None)   # a single query never names None alone
+            live = m.candidates(m.selected(s)[0])
+            sure = int((live & ~m.declined).sum())
+            q = s["qs"][0]
+            if s["deliberate"]:
+                deliberate[(s["deliberate"], metric)] += 1; here.add(s["deliberate"])
+                assert s["after"]["tiles"] >= 8 and 65 <= s["k"] <= 1024
+            if s["deliberate"] in (None, "zero", "nan"):
+                assert s["k"] in H.KS_WIDE and s["k"] < sure, (seed, s["k"], sure)
+            if s["deliberate"] is None:
+                assert not H.declined_rows(q[None, :])[0]
+                dead = ~m.alive & (m.rows.view(np.uint32) == q.view(np.uint32)[None, :]).all(axis=1)
+                queries["a dead row's vector"] += bool(dead.any())
+                queries["the previous vector of a replaced row"] += s["stale_vec"] is not None and np.array_equal(s["stale_vec"], q)
+            elif s["deliberate"] == "all_but_one":
+                assert s["k"] == int(live.sum()) - 1
+            elif s["deliberate"] == "all":
+                assert s["k"] == int(live.sum())
+            elif s["deliberate"] == "unsure":
+                assert sure < s["k"] < int(live.sum())
+            ks[s["k"]] += 1; calls[s["call"]] += 1
+            if s["after"]["growth"] and s["after"]["update_rows"] and s["after"]["tiles"] >= 8:
+                rm[((s["form"], s["plane"]), metric)] += 1
+        assert {"zero", "nan"} <= here, (seed, here)                                         # every seed reaches 8 tiles
+    print("wide searches: %d, of them on fewer than 8 tiles: %d; calls %s; k %s; queries %s" % (total, below, dict(calls), dict(sorted(ks.items())), dict(queries)))
+    for metric in H.METRICS:
+        print("%-6s wide routes after a growth and an update_rows: %s; deliberate: %s" % (metric, ", ".join("%s/%s x%d" % (r[0], r[1], rm[(r, metric)]) for r in H.WIDE_ROUTES),
+              ", ".join("%s x%d" % (d, deliberate[(d, metric)]) for d in H.WIDE_DELIBERATE)))
+        for r in H.WIDE_ROUTES:
+            assert rm[(r, metric)] >= 3, (r, metric, rm[(r, metric)])
+        for d in H.WIDE_DELIBERATE:
+            assert deliberate[(d, metric)] >= 1, (d, metric)
+    assert set(H.KS_WIDE) <= set(ks) and set(calls) == {"plain", "masked", "rowsets", "where"} and below >= 1
+    assert all(v >= 3 for v in queries.values()) and len(queries) == 2, queries
+
+
+@functools.lru_cache(maxsize=None)
+def wide_evals(seed):
+    """of every wide search of a schedule on 8 tiles or more: (the step, the model's prediction, the prediction with the 8-bit plane first
+    — a hand-back there is one in BOTH stages —, {fault: the prediction under it} for the searches that are not deliberate)"""
+    cfg, steps = plans()[seed]
+    m = H.Model(cfg)
+    out = []
+    for s in steps:
+        if s["kind"] != "search":
+            m.apply(s)
+            continue
+        if not H.is_wide(s) or s["after"]["tiles"] < 8:
+            continue
+        cache = {}
+        want = m.predict_wide(s, CUS, cache=cache)
+        both = m.predict_wide(dict(s, plane="8bit"), CUS, cache=cache)
+        faulty = {}
+        if not s["deliberate"]:
+            for f in FAULTS:
+                if f != "unselected" or s["form"] == "wf":
+                    faulty[f] = m.predict_wide(s, CUS, fault=f, cache=cache)
+        out.append((s, want, both, faulty))
+    return out
+
+
+@pytest.mark.parametrize("seed", MODEL_SEEDS)
+def test_the_wide_model_hands_back_at_most_one_search_in_ten_and_the_deliberate_cases_are_what_they_are_for(seed):
+    cfg = H.config(seed)
+    plain = backs = 0
+    seen = collections.Counter()
+    cands = []
+    for s, want, both, _ in wide_evals(seed):
+        kind = s["deliberate"]
+        if kind is None:
+            assert want["took"] == 1, (s["k"], want)                                         # k is below the candidates the bound is sure of
+            plain += 1; backs += want["back"]
+            cands.append((s["k"], want["cand"]))
+            continue
+        seen[kind] += 1
+        if kind in ("zero", "nan", "unsure"):
+            assert want["took"] == 1 and want["back"] == 1 and both["back"] == 1, (kind, want, both)
+        elif kind == "all":
+            assert want == {"took": 0, "back": 0, "cand": None}, want
+        else:
+            assert want["took"] == 1, want
+    print("seed %d (%s, %d dims, %s): %d wide searches, %d with a predicted hand-back, deliberate %s; (k, survivors) %s"
+          % (seed, cfg["metric"], cfg["dim"], cfg["style"], plain, backs, dict(seen), cands))
+    assert backs * 10 <= plain and plain >= 6
+    assert set(seen) >= {"zero", "nan", "all", "all_but_one"} | ({"unsure"} if cfg["style"] != "gauss" else set()), seen
+
+
+def test_the_wide_survivor_counts_tell_a_faulty_stage_1():
+    """each planted fault changes the predicted survivor count of a scheduled wide search of every metric: dead rows keyed, unselected live
+    rows keyed under a filter, H taken one rank early, the last overwritten row left with its previous vector's interval"""
+    moved, asked = collections.Counter(), collections.Counter()
+    for seed in MODEL_SEEDS:
+        metric = H.config(seed)["metric"]
+        for s, want, _, faulty in wide_evals(seed):
+            for f, got in faulty.items():
+                if want["cand"] is None or got["cand"] is None:
+                    continue
+                asked[(f, metric)] += 1
+                moved[(f, metric)] += got["cand"] != want["cand"]
+    for metric in H.METRICS:
+        print("%-6s searches whose count a fault moves: %s" % (metric, ", ".join("%s %d of %d" % (f, moved[(f, metric)], asked[(f, metric)]) for f in FAULTS)))
+    for metric in H.METRICS:
+        for f in FAULTS:
+            assert moved[(f, metric)] >= 1, (f, metric, asked[(f, metric)])
