@@ -137,6 +137,29 @@ func (d *oneGPU) setBoundScanWideFiltered(mode int) error {
 	return nil
 }
 
+// SetBoundScanWideMq (qv_index_set_bound_scan_wide_mq): the same for ONE unfiltered call of 2 to 8 queries of 65 to 1024 results each — the
+// small batches BatchSearch hands down as they come.  A knob of its own, independent of SetBoundScanWide (which never reaches two or more
+// queries); which plane comes first follows the shared pass's plane knob.  BoundScanAuto takes measured shapes only (cosine and dot, k <= 1000: 2 to 4 queries from 1M rows of
+// 768 dimensions, 5 to 8 queries from 3M, either from 10M rows of 128).
+// Results are the exact path's either way.  One GPU only: a sharded index has no such setter.
+func (x *Index) SetBoundScanWideMq(mode int) error {
+	x.mu.Lock()
+	defer x.mu.Unlock()
+	d, ok := x.dev.(*oneGPU)
+	if !ok {
+		return errors.New("quivergpu: the wide bound scan is a one-GPU path; a sharded index has no such setter")
+	}
+	return d.setBoundScanWideMq(mode)
+}
+
+func (d *oneGPU) setBoundScanWideMq(mode int) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	if C.qv_index_set_bound_scan_wide_mq(d.h, C.int(mode)) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
 // Insert implements core.Index (collection.go:80).  Error strings follow exact.go:45-50.
 func (x *Index) Insert(id string, v vectortypes.F32) error {
 	x.mu.Lock()

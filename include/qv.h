@@ -601,8 +601,9 @@ int qv_scan_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes);
  * QV_BOUND_PLANE_8BIT the 8-bit plane where it is held, QV_BOUND_PLANE_BF16 the bfloat16 copy, QV_BOUND_PLANE_AUTO the 8-bit plane in
  * the cells where it also beat the bfloat16 copy first by the same standard (all of the cells above), the bfloat16 copy elsewhere.
  * The environment variable QV_BOUND_SCAN_WIDE (1 always, 2 never; read once per process) sets the default of indexes that never call this.
- * Out of scope and unchanged: shared passes of 2 or more queries, the 6-bit plane, k > 1024, and the sharded handle (qv_sharded_* keeps
- * its paths; there is no sharded setter).  The filtered forms have a knob of their own: qv_index_set_bound_scan_wide_filtered, below. */
+ * Out of scope and unchanged: the 6-bit plane, k > 1024, and the sharded handle (qv_sharded_* keeps its paths; there is no sharded
+ * setter).  The filtered form and the shared pass of 2 to 8 queries have knobs of their own: qv_index_set_bound_scan_wide_filtered and
+ * qv_index_set_bound_scan_wide_mq, below; this knob never reaches two or more queries. */
 #define QV_BOUND_WIDE_CAND_CAP 8192   /* rows the wide form's re-score walks at most: 1024 + 4032 (the k <= 64 form's spare over its largest k) and room to the next power of two */
 int qv_index_set_bound_scan_wide(qv_index* idx, int mode);
 /* out[0] = survivors passed to the re-score in the last wide search, out[1] = searches handed back to the exact path so far, out[2] =
@@ -639,14 +640,55 @@ int qv_scan_bound_wide_route(int metric, uint32_t dim, uint32_t rows, uint32_t n
  * call this — the per-shard indexes of a sharded handle among them; there is no sharded setter, and the sharded handle's filtered search
  * (an internal call without the stream's ticket words) keeps its path whatever the variable says.
  * Out of scope and unchanged: qv_index_search_where_device keeps its k <= 64 limit (its candidate count exists only on the device, and the
- * selection paths need k <= count); runs of two or more queries naming one set keep their shared key-per-row pass; shared passes at
- * k > 64. */
+ * selection paths need k <= count); runs of two or more queries naming one set keep their shared key-per-row pass; filtered shared
+ * passes at k > 64 (the unfiltered ones: qv_index_set_bound_scan_wide_mq). */
 int qv_index_set_bound_scan_wide_filtered(qv_index* idx, int mode);
 /* The filtered form's rule on the host, as the dispatch asks it.  Arguments as qv_scan_bound_wide_route's; plane_mode_filtered:
  * QV_BOUND_PLANE_* of qv_index_set_bound_plane_filtered; candidate_tiles: the 64-row tiles that hold a candidate; candidates: the live
  * rows the filter selects.  0: no wide form; 1: the bfloat16 copy first; 2: the 8-bit plane first; < 0 on an error (an unknown mode). */
 int qv_scan_bound_wide_route_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered, int has_plane, int has_plane8,
                                       uint32_t candidate_tiles, uint64_t candidates);
+/* ---- the wide form of a shared pass: 2 to 8 queries, 65 to 1024 results ----
+ * ONE unfiltered call of 2 to 8 queries asking for 65 <= k <= 1024 results — qv_index_search, qv_index_search_device and whatever reaches
+ * them with that many queries, such as the short tail of a device batch — answered by the shared bound pass's wide form: the bfloat16 copy
+ * or the 8-bit plane is read ONCE for the pass (the stage-1 kernels of the k <= 64 shared pass, publishing every wave's 64 smallest upper
+ * bounds of every query), and per query the single wide form's funnel follows: the threshold is the k-th smallest of the query's published
+ * bounds, the rows within it — at most QV_BOUND_WIDE_CAND_CAP per query — get their distances from the float32 rows in the scan's own
+ * arithmetic, and one selection over all the queries' lists takes the k best of each.  Rows, float32 bits, (distance, row) order, counts
+ * and padding are the exact path's.  Every query has its own fate, decided on the device: one the 8-bit stage cannot decide (more
+ * survivors than the list holds, fewer than k rows the bound is sure of, a query it cannot quantise) goes on, alone, to the bfloat16
+ * stage, and one that stage cannot decide either (the same, or a norm that is not a number, huge or vanishing) is redone, alone, by the
+ * key-per-row path, whose outputs are then that query's.  The shape: the single wide form's and the k <= 64 shared pass's limits — cosine,
+ * dot, QV_L2 indexes created with QV_FLAG_L2_SCAN_PLANE; a dimension that is a multiple of 16 up to 4096; 8 tiles or more; more live rows
+ * than results; an index of at most 64M rows; nq planes of lower bounds (256 bytes per query and 64-row tile) under 2 GiB.
+ * `mode` takes the QV_BOUND_SCAN_* values and is a knob of its own: independent of qv_index_set_bound_scan_wide (which never reaches two
+ * or more queries, as this one never reaches a single query), of qv_index_set_bound_scan and of the single-query plane knobs.  ALWAYS:
+ * whenever the shape applies.  NEVER: never.  AUTO: only measured cells in which the form ran ahead of the key-per-row shared pass at every
+ * measured k (65, 100, 128, 129, 256, 1000) and every measured nq of its class (2 - 4 queries; 5 - 8 queries) by more than both arms'
+ * spread (profiles/LAB_r26_bound_scan_wide_mq.md, tests/bench/bench_bound_scan_wide_mq.py).  Those cells:
+ * cosine and dot indexes, k <= 1000; 2 to 4 queries from 1 000 000 rows of 768 dimensions or more, 5 to 8 queries from 3 000 000 (at
+ * 1M x 768 the bfloat16 copy first lost to the key-per-row pass with 8 queries at every k and with 5 at k = 1000), either from 10 000 000
+ * rows of 128 to 767 dimensions.  NOT measured and therefore never automatic: fewer than 1M rows, fewer than 128 dimensions, 128 to 767
+ * dimensions below 10M rows, k above 1000, QV_L2 indexes with the planes; ALWAYS reaches the path there.
+ * Which plane comes first follows qv_index_set_bound_plane_mq: QV_BOUND_PLANE_8BIT the 8-bit plane where it is held, QV_BOUND_PLANE_BF16
+ * the bfloat16 copy, QV_BOUND_PLANE_AUTO the 8-bit plane only in cells where it also beat the bfloat16 copy first by the same standard:
+ * all of the cells above except 5 to 8 queries below 768 dimensions (at 10M x 128 it lost to the bfloat16 copy first with 8 queries).
+ * The environment variable QV_BOUND_SCAN_WIDE_MQ (1 always, 2 never; read once per process) sets the default of indexes that never call
+ * this.  Out of scope and unchanged: filtered shared passes at k > 64 (a mask, row sets, where-filters), coalescing concurrent single-query
+ * callers at k > 64, 9 or more queries, k > 1024, the 6-bit plane, and the sharded handle (there is no sharded setter). */
+int qv_index_set_bound_scan_wide_mq(qv_index* idx, int mode);
+/* out[0] = the largest survivor count among the queries of the last wide shared pass, each query counted in the stage that ANSWERED it (a
+ * maximum over the stages that answered: a query the 8-bit stage answered counts with that stage's survivors, one handed on with the
+ * bfloat16 stage's, one handed back to the key-per-row path with nothing), out[1] = queries handed back to the key-per-row path so far,
+ * out[2] = queries that took the form so far, out[3] = 1 when the index holds the bfloat16 copy.  Waits for the device.  No other
+ * counter group moves for these passes, and these do not move for any other search. */
+int qv_index_bound_scan_wide_mq_stats(qv_index* idx, uint64_t out[4]);
+/* Whether a call of nq queries would take the wide shared pass — the dispatch's own rule, on the host (the dispatch adds what only the index
+ * and the call know: more LIVE rows than results, an unfiltered call that carries its stream's ticket words).  Arguments as
+ * qv_scan_bound_wide_route's; wide_mq_mode: QV_BOUND_SCAN_* of qv_index_set_bound_scan_wide_mq; plane_mode_mq: QV_BOUND_PLANE_* of
+ * qv_index_set_bound_plane_mq.  0: no wide shared pass (always for nq < 2 or nq > 8); 1: the bfloat16 copy first; 2: the 8-bit plane
+ * first; < 0 on an error (an unknown mode). */
+int qv_scan_bound_wide_route_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mq_mode, int plane_mode_mq, int has_plane, int has_plane8);
 /* ---- the 8-bit stage under a filter ----
  * Which plane serves a single FILTERED query's bound scan first: qv_index_search_masked, qv_index_search_rowsets and
  * qv_index_search_where with one query, their device forms, and a shared pass of the row-set front that holds one caller — at
@@ -791,6 +833,7 @@ int qv_scan_route_ex(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint3
 #define QV_WS_ROWSETS_CALL 13     /* the row-set workspace with the call's candidate bitmap behind it */
 #define QV_WS_WHERE_CALL 14       /* ... with the candidate bitmap and the transient sets behind it */
 #define QV_WS_BOUND_WIDE 15       /* the single-query bound scan's wide form, 65 <= k <= 1024; its exact redo's workspace is an alias over the rest */
+#define QV_WS_BOUND_WIDE_MQ 16    /* the wide form of the shared bound pass, 2 - 8 queries, 65 <= k <= 1024; the pass's flag words first, the key-per-row redo's workspace an alias over the rest */
 #define QV_WS_FLAT_PLAIN 0       /* query blocks, or the matrix-core scan's block */
 #define QV_WS_FLAT_BOUND 1        /* ... or the single-query bound scan's buffer */
 #define QV_WS_FLAT_BOUND_MQ 2     /* ... and the shared bound pass, which has the workspace to itself */

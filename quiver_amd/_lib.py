@@ -28,6 +28,7 @@ QV_RULE_L2_PLANES = 0x101      # such an index, as the qv_scan_* rule functions 
 QV_BOUND_SCAN_AUTO, QV_BOUND_SCAN_ALWAYS, QV_BOUND_SCAN_NEVER = 0, 1, 2
 QV_BOUND_WIDE_CAND_CAP = 8192  # rows the wide bound scan's re-score walks at most (65 <= k <= 1024)
 QV_WS_BOUND_WIDE = 15          # qv_scan_workspace_layout: the wide bound scan's buffer
+QV_WS_BOUND_WIDE_MQ = 16       # ... and the buffer of its shared pass of 2 - 8 queries
 QV_FILTERED_BATCH_AUTO, QV_FILTERED_BATCH_ALWAYS, QV_FILTERED_BATCH_NEVER = 0, 1, 2
 QV_COL_F64, QV_COL_U32 = 0, 1
 QV_SET_AND, QV_SET_OR, QV_SET_ANDNOT = 0, 1, 2
@@ -129,6 +130,9 @@ PROTOTYPES = {
     "qv_index_set_bound_scan_wide": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_bound_scan_wide_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_scan_bound_wide_route": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "qv_index_set_bound_scan_wide_mq": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_bound_scan_wide_mq_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_scan_bound_wide_route_mq": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]),
     "qv_index_set_bound_scan_wide_filtered": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_scan_bound_wide_route_filtered": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64]),
     "qv_scan_bound6_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

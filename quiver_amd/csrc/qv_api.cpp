@@ -609,6 +609,18 @@ static int wide_route(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_
     return qv::bound_wide_route(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide, idx->bound.plane[qv::bound_one], idx->d_bf16 != nullptr, idx->d_plane8 != nullptr);
 }
 
+// The same question for the wide form of the SHARED pass: an unfiltered call of 2 - 8 queries at 65 <= kk <= 1024 whose call carries the stream's
+// ticket words, kk == k_stride, fewer results than live rows; the rest is qv::bound_wide_route_mq's answer under the form's own knob and the
+// shared pass's plane knob.  0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.
+static int wide_route_mq(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, bool filtered) {
+    if (nq < 2 || kk != k_stride || !tickets || filtered || kk >= idx->n_live) return 0;
+    // H_j is the kk-th of the grid x 256 keys a query's waves publish: a grid too small for that (one or two compute units at a large kk)
+    // keeps its path.  The rule cannot see the grid; the launcher checks the same.
+    if ((uint64_t)qv::plan_scan((idx->n_rows + 63) / 64, idx->cus).grid * 256 <= kk) return 0;
+    const int metric = idx->l2_planes() ? QV_RULE_L2_PLANES : idx->metric;
+    return qv::bound_wide_route_mq(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide_mq, idx->bound.plane[qv::bound_mq], idx->d_bf16 != nullptr, idx->d_plane8 != nullptr);
+}
+
 // what a call may hand enqueue_search beside its queries and outputs
 struct SearchExtras {
     const uint64_t* d_candidates = nullptr;   // row bitmap replacing the tombstone bitmap (filtered search)
@@ -647,6 +659,14 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "wide bound scan launch failed: %s", hipGetErrorString(e));
         return QV_OK;
     }
+    // ... and 2 - 8 unfiltered queries of that length where the wide shared pass's rule takes them: the reduced copy read once for the pass
+    if (const int wide = wide_route_mq(idx, nq, kk, k_stride, x.d_tickets != nullptr, x.d_candidates != nullptr)) {
+        const ProfilePair pp = profile_begin(idx, true, s);
+        hipError_t e = qv::launch_bound_scan_wide_mq(v, plan, d_queries, nq, kk, ws, x.d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, d_rows_out, d_dist_out, s, wide == 2);
+        profile_end(idx, pp, e == hipSuccess, true, s);
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "wide shared bound pass launch failed: %s", hipGetErrorString(e));
+        return QV_OK;
+    }
     // 64 < k <= 8192 (the negative-example branches fetch max(2k, 30), hybrid_index.go:516-522; BatchSearch takes any k,
     // :677-811), and any shorter list whose output stride differs from its length: one key per row, then a radix SELECT
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) {   // (several queries: shared corpus passes through the key-per-row path below)
@@ -682,6 +702,7 @@ static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uin
         return qv::flat_layout(nullptr, what, plan, nq, kk, n_tiles, idx->dim).total;
     }
     if (wide_route(idx, nq, kk, k_stride, tickets, cand_tiles, candidates)) return qv::bound_scan_wide_workspace_bytes(plan, kk, n_tiles, idx->dim);
+    if (wide_route_mq(idx, nq, kk, k_stride, tickets, cand_tiles != qv::kBoundNoFilter)) return qv::bound_scan_wide_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim);
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
     return qv::full_sort_workspace_bytes(n_tiles);
@@ -2105,6 +2126,29 @@ int qv_index_bound_scan_wide_stats(qv_index* idx, uint64_t out[4]) {
     return QV_OK;
 }
 
+int qv_index_set_bound_scan_wide_mq(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    idx->bound_wide_mq = mode;
+    return QV_OK;
+}
+
+int qv_index_bound_scan_wide_mq_stats(qv_index* idx, uint64_t out[4]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t h[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kBoundWideMqStatsWord, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = idx->d_bf16 != nullptr ? 1 : 0;
+    return QV_OK;
+}
+
+int qv_scan_bound_wide_route_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mq_mode, int plane_mode_mq, int has_plane, int has_plane8) {
+    if (wide_mq_mode < 0 || wide_mq_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mq_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mq_mode);
+    if (plane_mode_mq < 0 || plane_mode_mq > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_mq);
+    return qv::bound_wide_route_mq(metric, dim, rows, nq, k, wide_mq_mode, plane_mode_mq, has_plane != 0, has_plane8 != 0);
+}
+
 int qv_scan_bound_wide_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, int has_plane, int has_plane8) {
     if (wide_mode < 0 || wide_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mode);
     if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
@@ -2271,6 +2315,7 @@ int qv_scan_workspace_layout(int kind, int metric, uint32_t dim, uint64_t rows, 
         case QV_WS_BOUND:            (void)qv::bound_scan_workspace_bytes(p, k, n_tiles, &log); break;
         case QV_WS_BOUND_MQ:         (void)qv::bound_scan_mq_workspace_bytes(p, nq, k, n_tiles, dim, &log); break;
         case QV_WS_BOUND_WIDE:       (void)qv::bound_scan_wide_workspace_bytes(p, k, n_tiles, dim, &log); break;
+        case QV_WS_BOUND_WIDE_MQ:    (void)qv::bound_scan_wide_mq_workspace_bytes(p, nq, k, n_tiles, dim, &log); break;
         case QV_WS_REDO:             (void)qv::redo_workspace_bytes(p, nq, k, &log); break;
         case QV_WS_SELECT:           (void)qv::select_workspace_bytes(nq, k, &log); break;
         case QV_WS_FLAT_WIDE:        (void)qv::flat_wide_workspace_bytes(p, nq, k, &log); break;

@@ -108,6 +108,7 @@ struct qv_index {
     qv::BoundKnobs bound = {};                 // qv_index_set_bound_scan, and by qv::BoundForm the four qv_index_set_bound_plane*
     int bound_wide = 0;                        // qv_index_set_bound_scan_wide: QV_BOUND_SCAN_* for the wide form (65 <= k <= 1024), a knob of its own
     int bound_wide_filtered = 0;               // qv_index_set_bound_scan_wide_filtered: the same for ONE filtered query of that length, a knob of its own
+    int bound_wide_mq = 0;                     // qv_index_set_bound_scan_wide_mq: the same for an unfiltered shared pass of 2 - 8 queries of that length, a knob of its own
     int8_t* d_plane8 = nullptr;                // the int8 copy and its row state (scale, residual): kept with the default bfloat16 copy, refreshed with it
     float* d_rscale8 = nullptr;
     float* d_rres8 = nullptr;

@@ -882,14 +882,16 @@ k_bound_collect_wide(const uint32_t* __restrict__ lo_all, uint32_t n /* multiple
     bound_collect(lo_all, n, H, &ctrl->cand_cnt, cand, kBoundWideCandCap);
 }
 
-// P8: the re-score behind the 8-bit stage (ctrl = that stage's words, next = the bfloat16 stage's): it answers — and clears the bfloat16 stage's
-// flag for the redo behind —, or sets its own flag, the word the bfloat16 stage's launches are gated on.  gate (the bfloat16 stage behind the
-// 8-bit one): as k_bound_rescore's.  keys [kBoundWideCandCap]; sel: [0] the live keys in front of keys[], [1] 1 = a stage has answered.
-template <int M, bool P8>
-__global__ void __launch_bounds__(kScanBlock)
-k_bound_rescore_wide(IndexView v, const float* __restrict__ query, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand, uint32_t* __restrict__ stats,
-                     uint64_t* __restrict__ keys, uint32_t* __restrict__ sel, uint32_t* gate, BoundCtrl* next) {
-    if (gate != nullptr && *gate == 0u) return;
+// The walk the two wide re-scores share (k_bound_rescore_wide: one query; k_bound_rescore_wide_mq: query blockIdx.y of a pass), written once so that
+// the bit-exact chain has one place: ONE query's survivors cand[0 .. cnt) -> keys[0 .. cnt), dead keys behind, on a grid of gridDim.x
+// workgroups that share the ticket in ctrl.  Entered by every thread of every workgroup of the query; returns with `last` set in thread 0
+// of the query's LAST workgroup alone (every other workgroup has taken its ticket, so has read whatever it reads of the control words),
+// which then decides: hand_back = the list overflowed, there is no finite H, or bound_scan_norm_ok declines |q|; ns = the live keys; cnt = the
+// collect's count.
+struct BoundWideWalk { bool last, hand_back; uint32_t ns, cnt; };
+template <int M>
+__device__ __forceinline__ BoundWideWalk bound_rescore_wide_walk(const IndexView& v, const float* __restrict__ query, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand,
+                                                                 uint64_t* __restrict__ keys) {
     using Q = typename MT<M>::Q;
     extern __shared__ __align__(16) unsigned char smem[];
     Q* q_lds = reinterpret_cast<Q*>(smem);
@@ -908,7 +910,7 @@ k_bound_rescore_wide(IndexView v, const float* __restrict__ query, BoundCtrl* __
     if (idle) {
         if (threadIdx.x == 0) s_last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;   // (behind this workgroup's reads of ctrl and the gate)
         __syncthreads();
-        if (!s_last) return;
+        if (!s_last) return BoundWideWalk{false, false, 0u, 0u};
     }
     stage_query<M>(q_lds, query, v.dim, v.dim4);
     __syncthreads();
@@ -920,7 +922,7 @@ k_bound_rescore_wide(IndexView v, const float* __restrict__ query, BoundCtrl* __
     }
     __syncthreads();
     const double qn = s_qn;
-    const bool hand_back = decided_early || !bound_scan_norm_ok(qn, v.dim);   // (the same in every workgroup)
+    const bool hand_back = decided_early || !bound_scan_norm_ok(qn, v.dim);   // (the same in every workgroup of the query)
     if (!hand_back && !idle) {
         QConst qc; qc.qn = 0.0; qc.qn32 = 0.0f;
         if constexpr (M == QV_COSINE) qc.qn = qn;
@@ -959,7 +961,21 @@ k_bound_rescore_wide(IndexView v, const float* __restrict__ query, BoundCtrl* __
         if (threadIdx.x == 0) s_last = atomicAdd(&ctrl->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;   // (behind this workgroup's reads of ctrl and the gate)
         __syncthreads();
     }
-    if (!s_last || threadIdx.x != 0) return;
+    return BoundWideWalk{s_last != 0u && threadIdx.x == 0, hand_back, ns, cnt};
+}
+
+// P8: the re-score behind the 8-bit stage (ctrl = that stage's words, next = the bfloat16 stage's): it answers — and clears the bfloat16 stage's
+// flag for the redo behind —, or sets its own flag, the word the bfloat16 stage's launches are gated on.  gate (the bfloat16 stage behind the
+// 8-bit one): as k_bound_rescore's.  keys [kBoundWideCandCap]; sel: [0] the live keys in front of keys[], [1] 1 = a stage has answered.
+template <int M, bool P8>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_rescore_wide(IndexView v, const float* __restrict__ query, BoundCtrl* __restrict__ ctrl, const uint32_t* __restrict__ cand, uint32_t* __restrict__ stats,
+                     uint64_t* __restrict__ keys, uint32_t* __restrict__ sel, uint32_t* gate, BoundCtrl* next) {
+    if (gate != nullptr && *gate == 0u) return;
+    const BoundWideWalk w = bound_rescore_wide_walk<M>(v, query, ctrl, cand, keys);
+    if (!w.last) return;
+    const bool hand_back = w.hand_back;
+    const uint32_t ns = w.ns, cnt = w.cnt;
     ctrl->ticket = 0;                                                  // for the next launch on these words (stream order)
     if constexpr (P8) {
         if (!hand_back) { stats[kBoundWideStatsWord] = cnt; (void)atomicAdd(&stats[kBoundWideStatsWord + 2], 1u); next->flag = 0u; }
@@ -1049,6 +1065,20 @@ __device__ __forceinline__ void bound_block_mq(const u4* __restrict__ p, const f
     }
 }
 
+// The WIDE shared pass's tail (k_bound_scan_mq<., ., false, true>, k_bound_scan8_mq<., ., false, true>): bound_scan_tail_wide per query.  Every
+// wave's list of every query of the pass is published as it stands, lists[j][grid][kScanWaves][64]; H_j is then the k-th smallest key of
+// query j's grid x kScanWaves x 64 keys (one launch_select_topk over the nq arrays).  The argument written at bound_scan_tail_wide holds per
+// query: query j's published keys are upper bounds of DISTINCT live rows — a row is in one wave's list of query j only —, any k of them
+// cap query j's k-th distance, H_j is exact whenever no wave holds more than 64 of query j's k smallest and only looser otherwise, and
+// fewer than k live keys leave query j without H_j (handed on, alone).  No ticket, no LDS: every slot of a query the pass holds is written
+// by its own wave in every launch (a wave that walks no tile publishes the dead lists it started with); slots past nq are never read.
+template <int QB>
+__device__ __forceinline__ void bound_scan_tail_wide_mq(const uint64_t (&list)[QB], uint32_t nq, uint32_t wave, uint32_t lane, uint64_t* __restrict__ lists) {
+#pragma unroll
+    for (int j = 0; j < QB; j++)
+        if ((uint32_t)j < nq) lists[(((size_t)j * gridDim.x + blockIdx.x) * kScanWaves + wave) * 64 + lane] = list[j];
+}
+
 // SETS (k_bound_scan_mq<., ., true>: a pass under filters, query j restricted to am_j = alive & set_j): the sets' (bits, words) pairs arrive as kernel
 // arguments, as in k_rowset_scan_mq, and lane j keeps query j's — eight pairs held as scalars spilled 168 SGPRs there, and this kernel
 // already spends its scalar file on the packed-fma query operands.  rowset_word for the wave's NEXT tile is fetched while the current one is
@@ -1058,14 +1088,18 @@ __device__ __forceinline__ void bound_block_mq(const u4* __restrict__ p, const f
 // rres —; its nq x 64 lower-bound words are written as 0xFFFFFFFF (256 bytes per query against dim * 128 of copy): k_bound_collect_mq
 // reads every word of a workspace that earlier searches have used, and stays as it is.  `first` is the first tile the wave READS.
 // The interval arithmetic is untouched.  A masked call (one bitmap for all queries, in v.alive) is this form with a table of null sets.
-template <int M, int QB, bool SETS = false>
+// WIDE (k_bound_scan_mq<., ., false, true>, k_bound_scan8_mq<., ., false, true>: a shared pass at 65 <= k <= kBoundWideMaxK): the walk with a list
+// length of 64 (k = 64 arrives as the argument), and the tail publishes every wave's list of every query — bound_scan_tail_wide per query
+// (bound_scan_tail_wide_mq below): no merge of the workgroup's waves, no LDS.
+template <int M, int QB, bool SETS = false, bool WIDE = false>
 __global__ void __launch_bounds__(kScanBlock, 2)
 k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __restrict__ qnorm, uint32_t nq, uint32_t k,
-                uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */, SetsArg<SETS> tab,
+                uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k]; WIDE: [nq][grid][kScanWaves][64] */, SetsArg<SETS> tab,
                 const uint32_t* __restrict__ gate = nullptr /* as k_bound_prep_mq's */) {
+    static_assert(!(SETS && WIDE), "the wide shared pass is unfiltered");
     if (gate != nullptr && *gate == 0u) return;
     extern __shared__ __align__(16) unsigned char smem[];
-    uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64]
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64] (WIDE: none)
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves, kth = k - 1;
@@ -1126,6 +1160,7 @@ k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __res
         }
         first = false;
     }
+    if constexpr (WIDE) { bound_scan_tail_wide_mq<QB>(list, nq, wave, lane, partial); return; }
 #pragma unroll
     for (int j = 0; j < QB; j++) wl[((size_t)wave * QB + j) * 64 + lane] = list[j];
     __syncthreads();
@@ -1205,7 +1240,8 @@ constexpr uint32_t kBound8MqHandWord = 16;     // in the pass's 64 flag words: [
 template <int QB>
 __global__ void __launch_bounds__(kScanBlock)
 k_bound_prep8_mq(const float* __restrict__ queries, uint32_t nq, uint32_t dim, int8_t* __restrict__ qterm, double* __restrict__ qpar, uint32_t* __restrict__ hand,
-                 uint32_t* __restrict__ stats) {
+                 uint32_t* __restrict__ max_pass /* the pass's largest survivor count among the form's counters */,
+                 uint32_t* __restrict__ max_stage8 /* ... and the 8-bit stage's own, where the form keeps one (the k <= 64 pass); else null */) {
     __shared__ float s_max[kScanWaves];
     __shared__ uint32_t s_bad[kScanWaves];
     __shared__ double s_res[kScanWaves];
@@ -1213,7 +1249,7 @@ k_bound_prep8_mq(const float* __restrict__ queries, uint32_t nq, uint32_t dim, i
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (j == 0 && threadIdx.x <= kBoundMqMax) hand[threadIdx.x] = 0u;
-    if (j == 0 && threadIdx.x == 0) { stats[0] = 0u; stats[kBound8StatsWord] = 0u; }   // the pass's largest survivor counts (k_bound_rescore_mq)
+    if (j == 0 && threadIdx.x == 0) { *max_pass = 0u; if (max_stage8 != nullptr) *max_stage8 = 0u; }   // the pass's largest survivor counts (k_bound_rescore_mq, k_bound_rescore_wide_mq)
     if (j >= nq) {
         for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) {
             qterm[(((size_t)(i >> 4) * QB + j) * 2) * 16 + (i & 15u)] = 0; qterm[(((size_t)(i >> 4) * QB + j) * 2 + 1) * 16 + (i & 15u)] = 0;
@@ -1301,12 +1337,14 @@ __device__ __forceinline__ void bound8_block_mq(const u4* __restrict__ p, const 
 // a threshold word of 0xFFFFFFFF, which is what sorting 64 dead keys gives.  The pre-test runs over query j's own candidates; a query with
 // no candidate in a tile computes no interval at all.  A wave that reads no tile publishes dead lists.  The integer walk, the int64
 // combination and bound_scan_interval8 are untouched.  A masked call (one bitmap in v.alive) is this form with a table of null sets.
-template <int M, int QB, bool SETS = false>
+// WIDE: as k_bound_scan_mq's — the walk and the pre-test with a list length of 64, the tail bound_scan_tail_wide_mq.
+template <int M, int QB, bool SETS = false, bool WIDE = false>
 __global__ void __launch_bounds__(kScanBlock, 2)
 k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __restrict__ qpar, uint32_t nq, uint32_t k,
-                 uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k] */, SetsArg<SETS> tab) {
+                 uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k]; WIDE: [nq][grid][kScanWaves][64] */, SetsArg<SETS> tab) {
+    static_assert(!(SETS && WIDE), "the wide shared pass is unfiltered");
     extern __shared__ __align__(16) unsigned char smem[];
-    uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64]
+    uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64] (WIDE: none)
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t steps = v.dim >> 4, tw = gridDim.x * kScanWaves, kth = k - 1;
@@ -1383,6 +1421,7 @@ k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __rest
         }
         first = false;
     }
+    if constexpr (WIDE) { bound_scan_tail_wide_mq<QB>(list, nq, wave, lane, partial); return; }
 #pragma unroll
     for (int j = 0; j < QB; j++) wl[((size_t)wave * QB + j) * 64 + lane] = list[j];
     __syncthreads();
@@ -1395,6 +1434,75 @@ k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __rest
             }
         }
     }
+}
+
+// ---------------------------------------------------------------- the shared pass of 2 - 8 queries, 65 <= k <= 1024: the wide form --
+// The wide form of the shared bound pass: the two stage-1 kernels above up to their tail (their WIDE instantiations, a list length of 64, the
+// copy or the plane read ONCE for the pass), and behind them the single wide form's funnel, per query:
+//   launch_select_topk          one launch over the nq arrays of published keys (n = stride = grid x kScanWaves x 64, kk = k): the k-th
+//                               output of query j is H_j.
+//   k_bound_collect_wide_mq     grid (cgrid, nq): bound_collect against H_j with a list of QV_BOUND_WIDE_CAND_CAP rows per query; workgroup 0 of
+//                               query j leaves H_j in ctrl[j].thr_inv (zero = the k-th key is dead or not finite: no H_j).
+//   k_bound_rescore_wide_mq     grid (rgrid, nq): k_bound_rescore_wide's wave-per-survivor chain — the exact scan's bits — per query into
+//                               keys[j][cap], dead keys behind the count.  Query j's LAST workgroup (a ticket in ctrl[j]) decides for
+//                               query j alone: counts[j] (the live keys in front of keys[j]; zero for a query that is not answered here),
+//                               the hand-on word or the redo's flag, the counters; it leaves ctrl[j] zero.
+//   launch_select_topk_counted  ONE launch over all nq key lists ends the pass, whichever stage answered each query, and
+//   launch_flat_select_redo     redoes the queries no stage could decide — the list overflowed, no finite H_j, a norm bound_scan_norm_ok
+//                               declines — through the key-per-row path, alone.  The counted selection runs over EVERY query, with a count
+//                               of zero for a query handed back, and BEFORE the redo: the redo's scatter is the last writer of a handed-back
+//                               query's outputs (stream order), so those are the redo's.
+// With the 8-bit plane first (STAGE 1) a query that stage cannot decide — the above, or a query it cannot quantise (no H_j) — is handed ON to
+// the bfloat16 stage (STAGE 2), whose launches are gated: hand[j] per query, and hand[kBoundMqMax] = nq or 0 for the launches that take one
+// word for the whole pass (launch_select_topk's d_active reads "the first *d_active queries": the hand-on COUNT would cut the pass short).
+// Nothing is read on the host.
+// Counters (kBoundWideMqStatsWord; none of the other groups moves): [13] the largest survivor count among the pass's queries, each in the stage
+// that ANSWERED it — a maximum over the stages that answered: the prep kernel of the pass's first stage clears it, the 8-bit stage's
+// maximum stays when the bfloat16 stage runs for a handed-on query, and a query handed back to the key-per-row path adds nothing;
+// [14] queries handed back to the key-per-row path; [15] queries that took the form.
+__global__ void __launch_bounds__(256)
+k_bound_collect_wide_mq(const uint32_t* __restrict__ lo_all /* [nq][n] */, uint32_t n /* multiple of 64 */, uint32_t k, const uint32_t* __restrict__ seed_rows, const float* __restrict__ seed_dist /* [nq][k] sorted */,
+                        BoundCtrl* __restrict__ ctrl, uint32_t* __restrict__ cand /* [nq][kBoundWideCandCap] */,
+                        const uint32_t* __restrict__ hand /* behind the 8-bit stage: only the queries it handed on (hand[j] != 0) are collected; null: all */) {
+    const uint32_t j = blockIdx.y;
+    if (hand != nullptr && hand[j] == 0u) return;
+    const uint32_t H = ord_f32(seed_dist[(size_t)j * k + k - 1]);
+    const bool has_H = seed_rows[(size_t)j * k + k - 1] != 0xFFFFFFFFu && H < 0xFF800000u;   // the k-th published key is a row's, and its bound finite
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctrl[j].thr_inv = has_H ? ~H : 0u;   // (the re-score behind reads it; cand_cnt is zero: the words are kept so)
+    if (!has_H) return;
+    bound_collect(lo_all + (size_t)j * n, n, H, &ctrl[j].cand_cnt, cand + (size_t)j * kBoundWideCandCap, kBoundWideCandCap);
+}
+
+// STAGE as k_bound_rescore_mq's: 0 the bfloat16 pass alone; 1 the 8-bit stage in front (a query it decides is answered and counted, every
+// other one gets hand[j] set and hand[kBoundMqMax] = nq); 2 the bfloat16 stage behind it (only handed-on queries are walked: an answered
+// query keeps its keys and its count).  flags[j]: the key-per-row redo's; counts[j]: the counted selection's.
+constexpr uint32_t kBoundWideMqCountWord = 32;     // in the pass's 64 flag words: [32, 40) the live keys in front of keys[j]
+template <int M, int STAGE>
+__global__ void __launch_bounds__(kScanBlock)
+k_bound_rescore_wide_mq(IndexView v, const float* __restrict__ queries, BoundCtrl* __restrict__ ctrl_all, const uint32_t* __restrict__ cand_all, uint32_t* __restrict__ stats,
+                        uint64_t* __restrict__ keys_all /* [nq][kBoundWideCandCap] */, uint32_t* __restrict__ flags, uint32_t* __restrict__ hand, uint32_t* __restrict__ counts) {
+    const uint32_t j = blockIdx.y;
+    if constexpr (STAGE == 2) { if (hand[j] == 0u) return; }          // (every workgroup of an answered query: no ticket is taken for it)
+    BoundCtrl* ctrl = ctrl_all + j;
+    const BoundWideWalk w = bound_rescore_wide_walk<M>(v, queries + (size_t)j * v.dim, ctrl, cand_all + (size_t)j * kBoundWideCandCap, keys_all + (size_t)j * kBoundWideCandCap);
+    if (!w.last) return;
+    const bool hand_back = w.hand_back;
+    const uint32_t ns = w.ns, cnt = w.cnt;
+    ctrl->ticket = 0;                                                  // for the next launch on these words (stream order)
+    const bool answered = !hand_back;
+    if (answered) (void)atomicMax(&stats[kBoundWideMqStatsWord], cnt);
+    if constexpr (STAGE == 1) {
+        if (answered) (void)atomicAdd(&stats[kBoundWideMqStatsWord + 2], 1u);
+        else hand[kBoundMqMax] = gridDim.y;                            // nq, not a count (see above); every handing-on query writes the same word
+        hand[j] = answered ? 0u : 1u;
+        flags[j] = 0u;                                                 // (the bfloat16 stage sets it if it hands the query back in turn)
+    } else {
+        if (hand_back) (void)atomicAdd(&stats[kBoundWideMqStatsWord + 1], 1u);
+        (void)atomicAdd(&stats[kBoundWideMqStatsWord + 2], 1u);
+        flags[j] = hand_back ? 1u : 0u;                                // launch_flat_select_redo behind the counted selection reads them
+    }
+    counts[j] = answered ? ns : 0u;
+    ctrl->cand_cnt = 0; ctrl->thr_inv = 0;                             // zero, as the words are kept
 }
 
 // The bound scan (k_bound_scan / k_bound_rescore above): one query, a fused-list k, cosine or dot, the bfloat16 copy at hand, a width the copy
@@ -1889,6 +1997,144 @@ hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const f
     if (e != hipSuccess) return e;
     return launch_flat_select_redo_one(v, p, d_query, k, k, &ctrl->flag, L.redo, d_rows_out, d_dist_out, s);
 }
+// ---- the wide form of the shared pass (2 - 8 queries, 65 <= k <= kBoundWideMaxK): its rule, its buffer, its launches ----
+// A rule and a knob of its own (qv_index_set_bound_scan_wide_mq / QV_BOUND_SCAN_WIDE_MQ): independent of the single-query wide knob, of
+// qv_index_set_bound_scan and of the single-query plane knobs; bound_wide_route keeps answering 0 for nq != 1.  NEVER, or a pass the kernels
+// cannot serve -> 0.  What they need: 2 - 8 unfiltered queries, the k <= 64 pass's and the single wide form's limits — metric, the copy, whole
+// 16-dimension steps, 8 tiles, nq planes of lower bounds under 2 GiB, more rows than results — and an index of at most 64M rows (the redo's
+// shared key passes take two queries' keys at least: flat_select_redo_one_serves).  ALWAYS -> the form; which plane comes first is the
+// shared pass's plane knob (qv_index_set_bound_plane_mq / QV_BOUND_PLANE_MQ): 8-bit first under "8bit" where the plane is held.
+// AUTOMATIC: per class (QB = 4: 2 - 4 queries, QB = 8: 5 - 8) the floors below; a floor of 0 rows is never automatic.  Only measured cells
+// are taken — the form against the key-per-row shared pass (k_flat_keys_mq + the radix selection), 8-bit first against bfloat16 first, each by
+// more than both arms' spread at every measured k and nq of the class (profiles/LAB_r26_bound_scan_wide_mq.md) — so QV_L2 indexes with the
+// planes are reached under ALWAYS alone, and dot is taken where cosine was measured (the same kernels over the same bytes; the finalize differs).
+// Cosine, device-pointer calls, five alternating rounds of 20 calls; nq = 2 and 4 (QB = 4), nq = 5 and 8 (QB = 8); k = 65, 100, 128, 129, 256,
+// 1000.  us per call at k = 100 and 1000, key-per-row / bfloat16 first / 8-bit first (spreads <= 27 us, at 10M x 768 <= 63 us):
+//   768 dims   1M   nq 2: 521 / 379 / 280, 552 / 418 / 351      nq 4: 547 / 424 / 345, 584 / 480 / 438
+//                   nq 5: 598 / 588 / 440, 646 / 641 / 557      nq 8: 596 / 660 / 534, 646 / 757 / 698
+//              3M   nq 2: 1495 / 858 / 547, 1536 / 898 / 611    nq 4: 1473 / 887 / 589, 1539 / 941 / 682
+//                   nq 5: 1556 / 1243 / 782, 1632 / 1330 / 904  nq 8: 1788 / 1367 / 943, 1884 / 1470 / 1116
+//              10M  nq 2: 4872 / 2560 / 1403, 4875 / 2592 / 1469    nq 4: 5237 / 2762 / 1533, 5244 / 2802 / 1621
+//                   nq 5: 5551 / 3568 / 1980, 5561 / 3571 / 2022    nq 8: 6041 / 3846 / 2255, 6047 / 3927 / 2401
+//   128 dims   10M  nq 2: 945 / 534 / 453, 948 / 561 / 476      nq 4: 1158 / 718 / 652, 1161 / 752 / 683
+//                   nq 5: 1259 / 844 / 837, 1262 / 883 / 869    nq 8: 1395 / 1073 / 1134, 1399 / 1110 / 1175
+// LOSSES: at 1M x 768 the bfloat16 copy first lost to the key-per-row pass with 8 queries at every k (by 9 - 17 %) and did not clear the
+// spread with 5 queries at k = 1000, so QB = 8 starts at 3M rows — the 8-bit plane first ran ahead of both there but for 8 queries at
+// k = 1000 (698 against 646), and is not taken either: it is never automatic where the form is not; at 10M x 128 the 8-bit plane first lost
+// to the bfloat16 copy first with 8 queries at every k (by 6 %; with 5 queries it won by 1 - 2 %), so QB = 8 stays on the bfloat16 copy below
+// 768 dimensions.  Every other cell won both comparisons at every k.  NOT measured, so never automatic: fewer than 1M rows; narrower than
+// 128 dimensions; 128 <= dim < 768 below 10M rows; k above 1000; QV_L2 indexes with the planes.  (nq = 3, 6 and 7 were not run: they go with
+// their class, between its two measured fills, as in the k <= 64 rules.)
+constexpr BoundFloor kBoundWideMqFloor[2] = {{1000000, 128, 10000000}, {3000000, 128, 10000000}};   // the form against the key-per-row shared pass, QB = 4 / QB = 8
+constexpr BoundFloor kBoundWideMq8Floor[2] = {{1000000, 128, 10000000}, {3000000, 0, 0}};           // ... and the 8-bit plane first against the bfloat16 copy first
+constexpr bool bound_wide_mq_floors_nest() {
+    for (int c = 0; c < 2; c++) {
+        const BoundFloor &f = kBoundWideMqFloor[c], &p = kBoundWideMq8Floor[c];
+        if (p.wide_rows != 0 && (f.wide_rows == 0 || p.wide_rows < f.wide_rows)) return false;
+        if (p.narrow_rows != 0 && (f.narrow_rows == 0 || p.narrow_rows < f.narrow_rows || p.narrow_dim < f.narrow_dim)) return false;
+    }
+    return true;
+}
+static_assert(bound_wide_mq_floors_nest(), "8-bit first is never automatic where the wide shared pass is not");
+int bound_wide_route_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mq_mode, int plane_mode_mq, bool has_plane, bool has_plane8) {
+    static const int env_wide = env_int("QV_BOUND_SCAN_WIDE_MQ", 0);
+    const int mode = wide_mq_mode ? wide_mq_mode : env_wide;
+    if (mode == 2) return 0;
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)rows + 63) / 64);
+    const bool metric_ok = rule_metric == QV_COSINE || rule_metric == QV_DOT || rule_metric == QV_RULE_L2_PLANES;
+    if (nq < 2 || nq > kBoundMqMax || k <= (uint32_t)kMaxFusedK || k > kBoundWideMaxK || !metric_ok || !has_plane) return 0;
+    if ((dim & 15u) != 0 || dim == 0 || dim > kBoundMaxDim || n_tiles < 8 || k >= rows || !flat_select_redo_one_serves(n_tiles)) return 0;
+    if ((uint64_t)nq * n_tiles * 256 > (2ull << 30)) return 0;
+    const int cls = nq <= 4 ? 0 : 1;
+    if (mode != 1 && !bound_wide_auto(kBoundWideMqFloor[cls], rule_metric, dim, rows, k)) return 0;
+    const int plane = bound_plane_mode(bound_mq, plane_mode_mq);
+    if (plane == 2 || !has_plane8) return 1;
+    return plane == 1 || bound_wide_auto(kBoundWideMq8Floor[cls], rule_metric, dim, rows, k) ? 2 : 1;
+}
+// the wide shared pass's buffer.  The pass's flag words come first and stay: the redo reads its flags from them.  The redo's workspace
+// overlays the rest: it is written only when every bound stage and the counted selection have ended.
+struct BoundWideMqLayout {
+    uint32_t* flags; void* redo; uint64_t* lists; uint32_t* seed_rows; float* seed_dist; void* sel_ws; double* qnorm; float* qblk; uint32_t* cand; uint64_t* keys; uint32_t* lo_all;
+    size_t end, total;
+};
+static BoundWideMqLayout bound_wide_mq_layout(void* base, const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr) {
+    WsCarver w{static_cast<char*>(base), 0, 0, log};
+    BoundWideMqLayout L{};
+    L.flags = w.take<uint32_t>(64);                                   // [0, 8) the redo's flags; [16, 24) hand-on words, [24] nq or 0; [32, 40) the key lists' counts
+    WsCarver o = w.overlay();
+    L.redo = o.take<char>(flat_select_redo_workspace_bytes(n_tiles, nq, k, dim, (dim + 3) / 4));   // the key-per-row redo of the queries handed back (an alias)
+    L.lists = w.take256<uint64_t>((size_t)nq * p.grid * kScanWaves * kBoundWideListLen);   // stage 1's published wave lists, per query
+    L.seed_rows = w.take256<uint32_t>((size_t)nq * k);                // per query the k smallest published upper bounds' rows ...
+    L.seed_dist = w.take256<float>((size_t)nq * k);                   // ... and values, sorted: the k-th is H_j
+    L.sel_ws = w.take256<char>(select_workspace_bytes(nq, k));        // that selection's workspace
+    L.qnorm = w.take<double>(32);                                     // the queries' norms (the 8-bit stage: its three scalars per query)
+    L.qblk = w.take256<float>((size_t)dim * kBoundMqMax);             // the query block (the 8-bit stage: its terms)
+    L.cand = w.take<uint32_t>((size_t)nq * kBoundWideCandCap);        // survivors the re-score walks, per query
+    L.keys = w.take<uint64_t>((size_t)nq * kBoundWideCandCap);        // their exact keys, dead keys behind
+    L.lo_all = w.take<uint32_t>((size_t)nq * n_tiles * 64);           // a lower bound per query and row slot
+    w.cover(o);
+    return w.finish(L);
+}
+size_t bound_scan_wide_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log) { return bound_wide_mq_layout(nullptr, p, nq, k, n_tiles, dim, log).total; }
+hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
+                                     uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first) {
+    // (whether the pass is TAKEN is bound_wide_route_mq's decision; here only what the kernels need)
+    if (bound_wide_route_mq(rule_metric(v), v.dim, v.n_rows, nq, k, 1, plane8_first ? 1 : 2, v.plane != nullptr, v.plane8 != nullptr) != (plane8_first ? 2 : 1) || !d_ctrl || !d_stats)
+        return hipErrorInvalidValue;
+    const uint32_t grid = p.grid;
+    const BoundWideMqLayout L = bound_wide_mq_layout(d_ws, p, nq, k, v.n_tiles, v.dim);
+    const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(kBoundCollectGrid, (n_pad + kCollectChunk - 1u) / kCollectChunk);
+    // keys per query: even.  More than k wherever the grid gives a wave a tile (grid x 256 >= rows > k) or has 2 workgroups per CU on 3 CUs
+    // or more (1536 keys and up; 131 072 on 256 CUs).  The rule cannot see the grid: the dispatch (wide_route_mq, qv_api.cpp) asks the same of
+    // the plan and keeps such a call on its earlier path; a caller that comes here all the same is refused.
+    const uint32_t n_keys = grid * kScanWaves * kBoundWideListLen;
+    if (n_keys <= k || (n_keys & 1u)) return hipErrorInvalidValue;
+    BoundCtrl* ctrl = reinterpret_cast<BoundCtrl*>(d_ctrl);           // kBoundMqMax of them: zero, left zero
+    const size_t lds2 = query_lds_bytes(v.metric, v.dim4) + (size_t)kScanWaves * v.dim4 * 4 * sizeof(float);
+    const uint32_t rgrid = std::min(kBoundWideRescoreGrid, (kBoundWideCandCap + kScanWaves - 1) / kScanWaves);
+    uint32_t *flags = L.flags, *hand = L.flags + kBound8MqHandWord, *counts = L.flags + kBoundWideMqCountWord;
+    static_assert(kBound8MqHandWord + kBoundMqMax + 1 <= kBoundWideMqCountWord && kBoundWideMqCountWord + kBoundMqMax <= 64, "the pass's flag words");
+    const uint32_t* gate = plane8_first ? hand + kBoundMqMax : nullptr;   // nq or 0
+    const uint32_t* hand_in = plane8_first ? hand : nullptr;
+    uint32_t* max_word = d_stats + kBoundWideMqStatsWord;             // the prep kernels clear "the pass's largest survivor count": this form's own word
+    static const int trace = env_int("QV_TRACE", 0);                   // (one read per process, as qv_scan.hip's)
+    if (trace) fprintf(stderr, "qv: scan kernel = %sk_bound_scan_mq wide QB=%d + select + k_bound_collect_wide_mq + k_bound_rescore_wide_mq, then k_select_sort and the flagged key-per-row redo (nq=%u, tiles=%u, k=%u)\n",
+                       plane8_first ? "k_bound_scan8_mq wide + select + k_bound_collect_wide_mq + k_bound_rescore_wide_mq, then gated " : "", nq <= 4 ? 4 : 8, nq, v.n_tiles, k);
+    auto run = [&](auto Mc, auto Qc) -> hipError_t {
+        constexpr int M = decltype(Mc)::value, QB = decltype(Qc)::value;
+        const SetsArg<false> no_sets{};
+        // (the dynamic LDS of every re-score before anything is launched; the wide stage-1 kernels take none)
+        hipError_t e = plane8_first ? set_lds((k_bound_rescore_wide_mq<M, 1>), lds2) : set_lds((k_bound_rescore_wide_mq<M, 0>), lds2);
+        if (e == hipSuccess && plane8_first) e = set_lds((k_bound_rescore_wide_mq<M, 2>), lds2);
+        if (e != hipSuccess) return e;
+        // what follows a stage's scan: H_j, the collect, the re-score.  g: the word the stage's pass-wide launches are gated on (null: none)
+        auto finish = [&](auto rescore, const uint32_t* g, const uint32_t* h_in) -> hipError_t {
+            const hipError_t e2 = launch_select_topk(L.lists, n_keys, n_keys, nq, k, k, L.sel_ws, L.seed_rows, L.seed_dist, s, false, false, g);
+            if (e2 != hipSuccess) return e2;
+            hipLaunchKernelGGL(k_bound_collect_wide_mq, dim3(cgrid, nq), dim3(256), 0, s, (const uint32_t*)L.lo_all, n_pad, k, (const uint32_t*)L.seed_rows, (const float*)L.seed_dist, ctrl, L.cand, h_in);
+            hipLaunchKernelGGL(rescore, dim3(rgrid, nq), dim3(kScanBlock), lds2, s, v, d_queries, ctrl, (const uint32_t*)L.cand, d_stats, L.keys, flags, hand, counts);
+            return hipGetLastError();
+        };
+        if (plane8_first) {
+            hipLaunchKernelGGL((k_bound_prep8_mq<QB>), dim3(QB), dim3(kScanBlock), 0, s, d_queries, nq, v.dim, reinterpret_cast<int8_t*>(L.qblk), L.qnorm, hand, max_word, (uint32_t*)nullptr);
+            hipLaunchKernelGGL((k_bound_scan8_mq<M, QB, false, true>), dim3(grid), dim3(kScanBlock), 0, s, v, reinterpret_cast<const u4*>(L.qblk), (const double*)L.qnorm, nq, kBoundWideListLen, L.lo_all, L.lists, no_sets);
+            e = finish(k_bound_rescore_wide_mq<M, 1>, nullptr, nullptr);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((k_bound_prep_mq<QB>), dim3((v.dim * QB + 255) / 256 + QB), dim3(256), 0, s, d_queries, nq, v.dim, L.qblk, L.qnorm, max_word, gate);
+        hipLaunchKernelGGL((k_bound_scan_mq<M, QB, false, true>), dim3(grid), dim3(kScanBlock), 0, s, v, (const float*)L.qblk, (const double*)L.qnorm, nq, kBoundWideListLen, L.lo_all, L.lists, no_sets, gate);
+        return plane8_first ? finish(k_bound_rescore_wide_mq<M, 2>, gate, hand_in) : finish(k_bound_rescore_wide_mq<M, 0>, nullptr, nullptr);
+    };
+    auto run_qb = [&](auto Mc) -> hipError_t { return nq <= 4 ? run(Mc, std::integral_constant<int, 4>{}) : run(Mc, std::integral_constant<int, 8>{}); };
+    hipError_t e = v.metric == QV_COSINE ? run_qb(std::integral_constant<int, QV_COSINE>{})
+                 : v.metric == QV_DOT  ? run_qb(std::integral_constant<int, QV_DOT>{}) : run_qb(std::integral_constant<int, QV_L2>{});
+    if (e != hipSuccess) return e;
+    // every query's answer from the stage that answered it (a count of zero for a query handed back), THEN the key-per-row redo of the flagged
+    // queries: the counted selection runs over all nq queries and before the redo, so a handed-back query's outputs are the redo's
+    e = launch_select_topk_counted(L.keys, kBoundWideCandCap, kBoundWideCandCap, counts, nq, k, k, d_rows_out, d_dist_out, s, nullptr);
+    if (e != hipSuccess) return e;
+    return launch_flat_select_redo(v, p, d_queries, nq, k, k, flags, L.redo, d_rows_out, d_dist_out, s);
+}
 // the interval of one row on the host; 1: a row the bound says nothing about ("unsure"), as host_bound_interval8 reports it
 int host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {
     const double gamma = bound_scan_gamma(dim);
@@ -2024,7 +2270,7 @@ hipError_t launch_bound_scan_mq(const IndexView& v, const ScanPlan& p, const flo
         if (e == hipSuccess && plane8_first) e = set_lds((k_bound_rescore_mq<M, 2>), lds2);
         if (e != hipSuccess) return e;
         if (plane8_first) {
-            hipLaunchKernelGGL((k_bound_prep8_mq<QB>), dim3(QB), dim3(kScanBlock), 0, s, d_queries, nq, v.dim, reinterpret_cast<int8_t*>(qblk), qnorm, hand, d_stats);
+            hipLaunchKernelGGL((k_bound_prep8_mq<QB>), dim3(QB), dim3(kScanBlock), 0, s, d_queries, nq, v.dim, reinterpret_cast<int8_t*>(qblk), qnorm, hand, d_stats, d_stats + kBound8StatsWord);
             hipLaunchKernelGGL((k_bound_scan8_mq<M, QB, SETS>), dim3(grid), dim3(kScanBlock), lds1, s, v, reinterpret_cast<const u4*>(qblk), qnorm, nq, k, lo_all, partial, sets);
             e = launch_merge_lists(partial, grid, nq, k, seed_rows, seed_dist, s);
             if (e != hipSuccess) return e;

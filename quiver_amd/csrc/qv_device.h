@@ -302,6 +302,22 @@ size_t bound_scan_wide_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n
 hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                                   uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first,
                                   bool masked = false);   // v.alive is the call's candidate bitmap: stage 1's SKIP forms; the stages behind read v.alive as they stand
+// The WIDE form of the SHARED pass: one unfiltered call of 2 - 8 queries at 65 <= k <= kBoundWideMaxK (qv_bound_scan.hip): the shared pass's stage-1
+// kernels with a list length of 64 publish every wave's list of every query, H_j is the k-th smallest of query j's published keys (one
+// launch_select_topk over the nq arrays), the collect and the wave-per-survivor re-score run per query (grid y = query), one
+// launch_select_topk_counted ends the pass, and launch_flat_select_redo behind it redoes, alone, the queries no stage could decide.  Whether a pass
+// takes it is bound_wide_route_mq's answer — a knob of its own (qv_index_set_bound_scan_wide_mq / QV_BOUND_SCAN_WIDE_MQ), independent of
+// bound_wide_route (which keeps answering 0 for nq != 1) and of bound_scan_decide; the plane it starts on is the shared pass's plane knob
+// (qv_index_set_bound_plane_mq / QV_BOUND_PLANE_MQ).
+constexpr uint32_t kBoundWideMqStatsWord = 13;   // its counters: [13] the largest survivor count of the last pass (each query in the stage that answered it), [14] queries handed back to the key-per-row path, [15] queries
+// 0: no wide shared pass; 1: the bfloat16 copy first; 2: the 8-bit plane first.  wide_mq_mode: QV_BOUND_SCAN_* (0: QV_BOUND_SCAN_WIDE_MQ of the
+// environment, read once, else automatic); plane_mode_mq: the index's qv_index_set_bound_plane_mq (0: QV_BOUND_PLANE_MQ, else automatic)
+int bound_wide_route_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mq_mode, int plane_mode_mq, bool has_plane, bool has_plane8);
+size_t bound_scan_wide_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr);
+// d_ctrl: the stream's control words (kBoundMqMax BoundCtrl of which this form uses thr_inv, cand_cnt and ticket: zero on entry, left zero on
+// every exit, hand-backs included); d_stats: the index's counters.  Enqueues everything, the flagged key-per-row redo included: nothing is read on the host.
+hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
+                                     uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first);
 constexpr uint32_t kBound6StatsWord = 7;   // the 6-bit stage's counters: [7] candidates it passed to the refine, [8] hand-backs, [9] searches
 constexpr uint32_t kBound6CandCap = 262144;   // rows the refine walks on the 8-bit plane (1 MiB of the workspace)
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches

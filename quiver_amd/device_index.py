@@ -446,6 +446,21 @@ class DeviceIndex:
         check(lib().qv_index_bound_scan_wide_stats(self._h, out))
         return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
 
+    def set_bound_scan_wide_mq(self, mode):
+        """the wide form of the shared bound pass: ONE unfiltered call of 2 to 8 queries at 65 <= k <= 1024 (search, search_device, the short
+        tail of a device batch): "auto" (the measured shapes: cosine / dot, k <= 1000, 2 - 4 queries from 1M rows of 768 dimensions, 5 - 8 queries from 3M,
+        either from 10M rows of 128), "always" (whenever the shape applies), "never"; a knob of its own, independent of
+        set_bound_scan_wide — which never reaches two or more queries, as this never reaches one — and of set_bound_scan; which plane comes
+        first follows set_bound_plane_mq; the counters are bound_scan_wide_mq_stats' (qv_index_set_bound_scan_wide_mq)"""
+        check(lib().qv_index_set_bound_scan_wide_mq(self._h, self.BOUND_SCAN.get(mode, mode)))
+
+    def bound_scan_wide_mq_stats(self) -> dict:
+        """the largest survivor count among the last wide shared pass's queries (each in the stage that answered it), queries handed back to
+        the key-per-row path, queries that took the form, whether the bfloat16 copy exists"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_index_bound_scan_wide_mq_stats(self._h, out))
+        return {"candidates": int(out[0]), "hand_backs": int(out[1]), "searches": int(out[2]), "plane": bool(out[3])}
+
     BOUND_PLANE = {"auto": 0, "8bit": 1, "bf16": 2}
 
     def _set_bound_plane(self, form, mode):
