@@ -160,6 +160,28 @@ func (d *oneGPU) setBoundScanWideMq(mode int) error {
 	return nil
 }
 
+// SetBoundScanWideFilteredMq (qv_index_set_bound_scan_wide_filtered_mq): the same for ONE filtered call of 2 to 8 queries of 65 to 1024
+// results each, every query over its own set (row sets, where-filters) or all over one mask.  A knob of its own, independent of the three
+// other wide setters; which plane comes first follows the filtered shared pass's plane knob.  BoundScanAuto takes nothing yet: the measured wins
+// depend on the kind of filter, which the rule cannot tell apart, and an unset index launches what it always launched.  Results are the exact path's either way.  One GPU only.
+func (x *Index) SetBoundScanWideFilteredMq(mode int) error {
+	x.mu.Lock()
+	defer x.mu.Unlock()
+	d, ok := x.dev.(*oneGPU)
+	if !ok {
+		return errors.New("quivergpu: the wide bound scan is a one-GPU path; a sharded index has no such setter")
+	}
+	return d.setBoundScanWideFilteredMq(mode)
+}
+
+func (d *oneGPU) setBoundScanWideFilteredMq(mode int) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	if C.qv_index_set_bound_scan_wide_filtered_mq(d.h, C.int(mode)) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
 // Insert implements core.Index (collection.go:80).  Error strings follow exact.go:45-50.
 func (x *Index) Insert(id string, v vectortypes.F32) error {
 	x.mu.Lock()

@@ -640,8 +640,8 @@ int qv_scan_bound_wide_route(int metric, uint32_t dim, uint32_t rows, uint32_t n
  * call this — the per-shard indexes of a sharded handle among them; there is no sharded setter, and the sharded handle's filtered search
  * (an internal call without the stream's ticket words) keeps its path whatever the variable says.
  * Out of scope and unchanged: qv_index_search_where_device keeps its k <= 64 limit (its candidate count exists only on the device, and the
- * selection paths need k <= count); runs of two or more queries naming one set keep their shared key-per-row pass; filtered shared
- * passes at k > 64 (the unfiltered ones: qv_index_set_bound_scan_wide_mq). */
+ * selection paths need k <= count); calls of two or more queries — the filtered shared pass at k > 64 has a knob of its own,
+ * qv_index_set_bound_scan_wide_filtered_mq, which this knob never reaches. */
 int qv_index_set_bound_scan_wide_filtered(qv_index* idx, int mode);
 /* The filtered form's rule on the host, as the dispatch asks it.  Arguments as qv_scan_bound_wide_route's; plane_mode_filtered:
  * QV_BOUND_PLANE_* of qv_index_set_bound_plane_filtered; candidate_tiles: the 64-row tiles that hold a candidate; candidates: the live
@@ -674,8 +674,8 @@ int qv_scan_bound_wide_route_filtered(int metric, uint32_t dim, uint32_t rows, u
  * the bfloat16 copy, QV_BOUND_PLANE_AUTO the 8-bit plane only in cells where it also beat the bfloat16 copy first by the same standard:
  * all of the cells above except 5 to 8 queries below 768 dimensions (at 10M x 128 it lost to the bfloat16 copy first with 8 queries).
  * The environment variable QV_BOUND_SCAN_WIDE_MQ (1 always, 2 never; read once per process) sets the default of indexes that never call
- * this.  Out of scope and unchanged: filtered shared passes at k > 64 (a mask, row sets, where-filters), coalescing concurrent single-query
- * callers at k > 64, 9 or more queries, k > 1024, the 6-bit plane, and the sharded handle (there is no sharded setter). */
+ * this.  Out of scope and unchanged: filtered shared passes at k > 64 (a mask, row sets, where-filters: a form and a knob of their own,
+ * qv_index_set_bound_scan_wide_filtered_mq below, which this knob never reaches), coalescing concurrent single-query callers at k > 64, 9 or more queries, k > 1024, the 6-bit plane, and the sharded handle (there is no sharded setter). */
 int qv_index_set_bound_scan_wide_mq(qv_index* idx, int mode);
 /* out[0] = the largest survivor count among the queries of the last wide shared pass, each query counted in the stage that ANSWERED it (a
  * maximum over the stages that answered: a query the 8-bit stage answered counts with that stage's survivors, one handed on with the
@@ -689,6 +689,40 @@ int qv_index_bound_scan_wide_mq_stats(qv_index* idx, uint64_t out[4]);
  * qv_index_set_bound_plane_mq.  0: no wide shared pass (always for nq < 2 or nq > 8); 1: the bfloat16 copy first; 2: the 8-bit plane
  * first; < 0 on an error (an unknown mode). */
 int qv_scan_bound_wide_route_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mq_mode, int plane_mode_mq, int has_plane, int has_plane8);
+/* ---- the wide form of a FILTERED shared pass: 2 to 8 queries, 65 to 1024 results, a filter per query ----
+ * ONE filtered call of 2 to 8 queries asking for 65 <= k <= 1024 results, each query over its own live & set: qv_index_search_rowsets and
+ * qv_index_search_rowsets_device (a row set or a null set per query), qv_index_search_where (whose k > 64 form makes counted sets first)
+ * and qv_index_search_masked (one bitmap for all its queries).  The wide shared pass above with the sets in its stage 1: the bfloat16
+ * copy or the 8-bit plane is read ONCE for the piece, a tile no query selects is not read, a row outside query j's set is no candidate
+ * of query j and of query j alone, and the threshold of query j is the k-th smallest published bound over ITS candidates.  The funnel
+ * behind is the unfiltered form's, per query; a query no stage can decide (more survivors than QV_BOUND_WIDE_CAND_CAP, no finite
+ * threshold, a norm that is not a number, huge or vanishing) is redone, alone, by the key-per-row path OVER ITS OWN SET.  Rows, float32
+ * bits, (distance, row) order, counts and padding are those of the path the call takes otherwise.
+ * How a call is cut: a maximal run of consecutive queries that each have MORE live candidates than k is cut into pieces of at most 8;
+ * queries naming the same set may share a piece; a run of exactly one such query stays the single-query filtered wide form
+ * (qv_index_set_bound_scan_wide_filtered); a query with k candidates or fewer keeps its path and its clamped count, and the queries on
+ * both sides of it are still answered by the form.  The shape: the unfiltered wide shared pass's limits (above).
+ * `mode` takes the QV_BOUND_SCAN_* values and is a knob of its own, independent of the three other wide knobs, which answer exactly as
+ * they did.  ALWAYS: whenever the shape applies.  NEVER: never.  AUTO: NOTHING YET: with nothing set a filtered call launches what it
+ * always launched.  Measured (profiles/LAB_r27_bound_scan_wide_filtered_mq.md, tests/bench/bench_bound_scan_wide_filtered_mq.py; 1M, 3M,
+ * 10M x 768 and 10M x 128, cosine, 2 / 4 / 5 / 8 queries, k = 65 / 100 / 1000, null sets, a distinct 1 % set per query, one set of a
+ * tile in ten): at 10M x 768 and k = 100 eight queries over distinct 1 % sets take 6.28 ms today, 3.72 ms bfloat16 first and 1.99 ms
+ * 8-bit first, over one tile-in-ten set 6.00 / 1.12 / 0.72 ms.  The form LOST with the bfloat16 copy first for two queries over
+ * distinct 1 % sets at 3M and 10M x 768 (two single-query scans are faster) and for 5 to 8 queries over null sets at 1M x 768; which
+ * path wins depends on the kind of filter, which the automatic rule cannot tell apart yet, so its floors stay empty.  Which plane comes first follows
+ * qv_index_set_bound_plane_filtered_mq (QV_BOUND_PLANE_8BIT: the 8-bit plane where it is held; otherwise the bfloat16 copy).  The
+ * counters are the wide shared pass's (qv_index_bound_scan_wide_mq_stats); no other group moves.  The environment variable
+ * QV_BOUND_SCAN_WIDE_FILTERED_MQ (1 always, 2 never; read once per process) sets the default of indexes that never call this.
+ * Out of scope and unchanged: qv_index_search_where_device above k = 64, the row-set front and coalesced callers at k > 64, 9 or more
+ * queries in a piece, k > 1024, the 6-bit plane, and the sharded handle (there is no sharded setter). */
+int qv_index_set_bound_scan_wide_filtered_mq(qv_index* idx, int mode);
+/* The form's rule on the host, as the dispatch asks it per piece (the dispatch adds what only the call knows: the stream's ticket words, a
+ * grid that publishes more than k keys).  Arguments as qv_scan_bound_wide_route_mq's; plane_mode_filtered_mq: QV_BOUND_PLANE_* of
+ * qv_index_set_bound_plane_filtered_mq; candidate_tiles: the 64-row tiles that hold a candidate of any query of the piece; min_candidates:
+ * the smallest live candidate count among the piece's queries.  0: no (always for nq < 2 or nq > 8, no candidate tile, or
+ * min_candidates <= k); 1: the bfloat16 copy first; 2: the 8-bit plane first; < 0 on an error (an unknown mode). */
+int qv_scan_bound_wide_route_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered_mq, int has_plane, int has_plane8,
+                                         uint32_t candidate_tiles, uint64_t min_candidates);
 /* ---- the 8-bit stage under a filter ----
  * Which plane serves a single FILTERED query's bound scan first: qv_index_search_masked, qv_index_search_rowsets and
  * qv_index_search_where with one query, their device forms, and a shared pass of the row-set front that holds one caller — at

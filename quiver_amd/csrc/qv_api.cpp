@@ -612,12 +612,18 @@ static int wide_route(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_
 // The same question for the wide form of the SHARED pass: an unfiltered call of 2 - 8 queries at 65 <= kk <= 1024 whose call carries the stream's
 // ticket words, kk == k_stride, fewer results than live rows; the rest is qv::bound_wide_route_mq's answer under the form's own knob and the
 // shared pass's plane knob.  0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.
-static int wide_route_mq(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, bool filtered) {
-    if (nq < 2 || kk != k_stride || !tickets || filtered || kk >= idx->n_live) return 0;
+// Filtered (cand_tiles != kBoundNoFilter: 2 - 8 queries over ONE candidate bitmap, or a piece of rowsets_plan's with a set per query): cand_tiles
+// is the piece's candidate tiles and candidates the SMALLEST live candidate count among its queries, and the answer is
+// qv::bound_wide_route_filtered_mq's under that form's own knob and the filtered shared pass's plane knob.
+static int wide_route_mq(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles = qv::kBoundNoFilter, uint64_t candidates = 0) {
+    if (nq < 2 || kk != k_stride || !tickets || kk >= idx->n_live) return 0;
     // H_j is the kk-th of the grid x 256 keys a query's waves publish: a grid too small for that (one or two compute units at a large kk)
     // keeps its path.  The rule cannot see the grid; the launcher checks the same.
     if ((uint64_t)qv::plan_scan((idx->n_rows + 63) / 64, idx->cus).grid * 256 <= kk) return 0;
     const int metric = idx->l2_planes() ? QV_RULE_L2_PLANES : idx->metric;
+    if (cand_tiles != qv::kBoundNoFilter)
+        return qv::bound_wide_route_filtered_mq(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide_filtered_mq, idx->bound.plane[qv::bound_mq_filtered], idx->d_bf16 != nullptr,
+                                                idx->d_plane8 != nullptr, cand_tiles, candidates);
     return qv::bound_wide_route_mq(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide_mq, idx->bound.plane[qv::bound_mq], idx->d_bf16 != nullptr, idx->d_plane8 != nullptr);
 }
 
@@ -659,10 +665,13 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "wide bound scan launch failed: %s", hipGetErrorString(e));
         return QV_OK;
     }
-    // ... and 2 - 8 unfiltered queries of that length where the wide shared pass's rule takes them: the reduced copy read once for the pass
-    if (const int wide = wide_route_mq(idx, nq, kk, k_stride, x.d_tickets != nullptr, x.d_candidates != nullptr)) {
+    // ... and 2 - 8 queries of that length where the wide shared pass's rule takes them: the reduced copy read once for the pass.  Over a
+    // candidate bitmap (one mask for all the queries) it is the filtered form with a table of null sets over v.alive, as at k <= 64
+    if (const int wide = wide_route_mq(idx, nq, kk, k_stride, x.d_tickets != nullptr, x.d_candidates ? x.candidate_tiles : qv::kBoundNoFilter, x.candidates)) {
         const ProfilePair pp = profile_begin(idx, true, s);
-        hipError_t e = qv::launch_bound_scan_wide_mq(v, plan, d_queries, nq, kk, ws, x.d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, d_rows_out, d_dist_out, s, wide == 2);
+        const qv::RowSetRef every[8] = {};
+        hipError_t e = qv::launch_bound_scan_wide_mq(v, plan, d_queries, nq, kk, ws, x.d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, d_rows_out, d_dist_out, s, wide == 2,
+                                                     x.d_candidates ? every : nullptr);
         profile_end(idx, pp, e == hipSuccess, true, s);
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "wide shared bound pass launch failed: %s", hipGetErrorString(e));
         return QV_OK;
@@ -702,7 +711,7 @@ static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uin
         return qv::flat_layout(nullptr, what, plan, nq, kk, n_tiles, idx->dim).total;
     }
     if (wide_route(idx, nq, kk, k_stride, tickets, cand_tiles, candidates)) return qv::bound_scan_wide_workspace_bytes(plan, kk, n_tiles, idx->dim);
-    if (wide_route_mq(idx, nq, kk, k_stride, tickets, cand_tiles != qv::kBoundNoFilter)) return qv::bound_scan_wide_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim);
+    if (wide_route_mq(idx, nq, kk, k_stride, tickets, cand_tiles, candidates)) return qv::bound_scan_wide_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim);
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
     return qv::full_sort_workspace_bytes(n_tiles);
@@ -1045,7 +1054,7 @@ static int masked_pass(qv_index* idx, const float* queries, uint32_t nq, uint32_
     if ((rc = hc.reserve(nq, nq, kk))) return rc;
     // the bound scan under the mask when the filtered rule takes it — up to 64 results plan_flat's, from 65 the wide form's —: then, and only
     // then, the call carries the context's ticket words (without them every path is the one a masked search has always taken)
-    const bool bound = kk <= (uint32_t)qv::kMaxFusedK ? flat_plan(idx, nq, kk, true, cand_tiles).bound() : wide_route(idx, nq, kk, kk, true, cand_tiles, matching) != 0;
+    const bool bound = kk <= (uint32_t)qv::kMaxFusedK ? flat_plan(idx, nq, kk, true, cand_tiles).bound() : wide_route(idx, nq, kk, kk, true, cand_tiles, matching) != 0 || wide_route_mq(idx, nq, kk, kk, true, cand_tiles, matching) != 0;
     if ((rc = hc.workspace(search_ws_bytes(idx, nq, kk, kk, bound, cand_tiles, matching)))) return rc;
     SearchExtras x;
     x.d_candidates = static_cast<const uint64_t*>(c->d_mask.p); x.candidate_tiles = cand_tiles; x.candidates = matching;
@@ -1359,7 +1368,9 @@ static qv::RowSetRef rs_ref(const qv_index* idx, const RsFilter& f) {
 // batched: a multi piece of 9 or more queries that takes the matrix-core filter with a set per query (launch_batched with BatchedSets;
 // filtered_batch_takes is the rule) — decided here too, and only for the host forms, whose caller reads the redo flags.
 // cand: a run's live candidates (rowset_live), counted for k > kMaxFusedK only — the filtered wide form's rule asks for it; 0 otherwise.
-struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; bool bound8; bool batched = false; uint64_t cand = 0; };
+// wide_mq: a piece of 2 - 8 queries at 65 <= k <= 1024, a set per query, that the filtered wide shared pass takes (launch_bound_scan_wide_mq with
+// the sets; 1 the bfloat16 copy first, 2 the 8-bit plane first) — decided here too.  cand is then the smallest live count among its queries.
+struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; bool bound8; bool batched = false; uint64_t cand = 0; int wide_mq = 0; };
 static uint32_t rowsets_cand_tiles(const qv_index* idx, const RsFilter* fl, uint32_t nq, bool transient_every_tile = false) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     uint64_t sum = 0;
@@ -1402,9 +1413,41 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const R
         return std::max(qv::rowset_workspace_bytes(plan, nq, k, idx->dim4), bound ? qv::bound_scan_mq_workspace_bytes(plan, nq, k, n_tiles, idx->dim) : (size_t)0);
     }
     size_t ws = 0;
+    // k > kMaxFusedK: the wide shared pieces first.  A maximal run of consecutive queries that each have MORE live candidates than k, cut into
+    // pieces of at most 8 (evenly: nine are five and four), each asked of the filtered wide shared pass's rule; queries naming one set may
+    // share a piece.  A run of one, a query of k candidates or fewer and a piece the rule declines keep the loop below, as before: with the
+    // rule at "never" — or automatic, which takes nothing yet — wide_at stays empty and this function answers as it always has.
+    std::vector<RowsetPiece> wide_at(0);
+    if (k > (uint32_t)qv::kMaxFusedK && nq >= 2 && wide_route_mq(idx, 2, k, k, true, n_tiles, ~0ull)) {   // (could the form take anything of this index at all?)
+        std::vector<uint64_t> live(nq);
+        for (uint32_t q = 0; q < nq; q++) live[q] = q > 0 && fl[q].set == fl[q - 1].set ? live[q - 1] : rowset_live(idx, fl[q].set);
+        for (uint32_t q = 0; q < nq;) {
+            uint32_t e = q;
+            while (e < nq && !fl[e].where && live[e] > k) e++;
+            const uint32_t len = e - q, parts = (len + 7) / 8;
+            for (uint32_t i = 0, at = q; len >= 2 && i < parts; i++) {
+                const uint32_t m = len / parts + (i < len % parts ? 1u : 0u);
+                const uint32_t ct = rowsets_cand_tiles(idx, fl + at, m);
+                const uint64_t least = *std::min_element(live.begin() + at, live.begin() + at + m);
+                if (const int wide = m >= 2 ? wide_route_mq(idx, m, k, k, true, ct, least) : 0)
+                    wide_at.push_back(RowsetPiece{at, m, k, false, false, ct, false, false, least, wide});
+                at += m;
+            }
+            q = e > q ? e : q + 1;
+        }
+    }
+    size_t next_wide = 0;
     for (uint32_t q = 0; q < nq;) {
+        if (next_wide < wide_at.size() && wide_at[next_wide].q0 == q) {
+            const RowsetPiece& wp = wide_at[next_wide++];
+            pieces.push_back(wp);
+            ws = std::max(ws, qv::bound_scan_wide_mq_workspace_bytes(plan, wp.nq, k, n_tiles, idx->dim));   // (as rowsets_enqueue launches it)
+            q += wp.nq;
+            continue;
+        }
+        const uint32_t stop = next_wide < wide_at.size() ? wide_at[next_wide].q0 : nq;
         uint32_t e = q + 1;
-        while (e < nq && rs_same(fl[e], fl[q])) e++;
+        while (e < stop && rs_same(fl[e], fl[q])) e++;
         const qv_rowset* set = fl[q].set;
         const bool transient = fl[q].where != nullptr;                // (only with k <= kMaxFusedK: the k > 64 form of qv_index_search_where makes real sets first)
         // (up to kMaxFusedK the lists are k long whatever the set holds: the scans pad, nothing is counted on the host)
@@ -1511,6 +1554,16 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
                                  : qv::launch_rowset_topk(v, plan, q, p.nq, k, refs.data(), ws, r_out, d_out, s, pp.ev0, pp.ev1);
             profile_end(idx, pp, e == hipSuccess, bound, s);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set scan launch failed: %s", hipGetErrorString(e));
+            continue;
+        }
+        if (p.wide_mq) {                                              // 65 <= k <= 1024, a set per query: the reduced copy read once for the piece
+            if (!d_tickets) return fail(QV_ERR_DEVICE, "filtered wide shared pass without the stream's control words");
+            qv::RowSetRef refs[8];
+            for (uint32_t i = 0; i < p.nq; i++) refs[i] = rs_ref(idx, fl[p.q0 + i]);
+            const ProfilePair pp = profile_begin(idx, true, s);
+            hipError_t e = qv::launch_bound_scan_wide_mq(v, plan, q, p.nq, k, ws, d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, r_out, d_out, s, p.wide_mq == 2, refs);
+            profile_end(idx, pp, e == hipSuccess, true, s);
+            if (e != hipSuccess) return fail(QV_ERR_DEVICE, "filtered wide shared bound pass launch failed: %s", hipGetErrorString(e));
             continue;
         }
         if (p.kk == 0) {
@@ -2133,6 +2186,13 @@ int qv_index_set_bound_scan_wide_mq(qv_index* idx, int mode) {
     return QV_OK;
 }
 
+int qv_index_set_bound_scan_wide_filtered_mq(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    idx->bound_wide_filtered_mq = mode;
+    return QV_OK;
+}
+
 int qv_index_bound_scan_wide_mq_stats(qv_index* idx, uint64_t out[4]) {
     if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
     HIPCHK(hipSetDevice(idx->device));
@@ -2147,6 +2207,14 @@ int qv_scan_bound_wide_route_mq(int metric, uint32_t dim, uint32_t rows, uint32_
     if (wide_mq_mode < 0 || wide_mq_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mq_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mq_mode);
     if (plane_mode_mq < 0 || plane_mode_mq > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_mq);
     return qv::bound_wide_route_mq(metric, dim, rows, nq, k, wide_mq_mode, plane_mode_mq, has_plane != 0, has_plane8 != 0);
+}
+
+int qv_scan_bound_wide_route_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered_mq, int has_plane, int has_plane8,
+                                         uint32_t candidate_tiles, uint64_t min_candidates) {
+    if (wide_mode < 0 || wide_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mode);
+    if (plane_mode_filtered_mq < 0 || plane_mode_filtered_mq > QV_BOUND_PLANE_BF16)
+        return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered_mq);
+    return qv::bound_wide_route_filtered_mq(metric, dim, rows, nq, k, wide_mode, plane_mode_filtered_mq, has_plane != 0, has_plane8 != 0, std::min(candidate_tiles, qv::kBoundNoFilter - 1), min_candidates);   // (a count, never the "no filter" mark)
 }
 
 int qv_scan_bound_wide_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, int has_plane, int has_plane8) {

@@ -1091,12 +1091,16 @@ __device__ __forceinline__ void bound_scan_tail_wide_mq(const uint64_t (&list)[Q
 // WIDE (k_bound_scan_mq<., ., false, true>, k_bound_scan8_mq<., ., false, true>: a shared pass at 65 <= k <= kBoundWideMaxK): the walk with a list
 // length of 64 (k = 64 arrives as the argument), and the tail publishes every wave's list of every query — bound_scan_tail_wide per query
 // (bound_scan_tail_wide_mq below): no merge of the workgroup's waves, no LDS.
+// SETS and WIDE together (k_bound_scan_mq<., ., true, true>: a filtered shared pass at 65 <= k <= kBoundWideMaxK): the SETS walk up to the WIDE
+// tail, and nothing more.  What the tail publishes for query j is the list the walk kept for it: dead keys from the initialisation for a wave
+// that read no tile — every tile it owns skipped, or none owned —, the sort of 64 dead keys for a wave whose tiles hold no candidate of
+// query j, and otherwise upper bounds of DISTINCT rows of alive & set_j, so bound_scan_tail_wide's argument for H_j holds over query j's own
+// candidates.  `first` stays with the first tile the wave READS (a skipped tile leaves it set), and so does everything that rides on it.
 template <int M, int QB, bool SETS = false, bool WIDE = false>
 __global__ void __launch_bounds__(kScanBlock, 2)
 k_bound_scan_mq(IndexView v, const float* __restrict__ qblk, const double* __restrict__ qnorm, uint32_t nq, uint32_t k,
                 uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k]; WIDE: [nq][grid][kScanWaves][64] */, SetsArg<SETS> tab,
                 const uint32_t* __restrict__ gate = nullptr /* as k_bound_prep_mq's */) {
-    static_assert(!(SETS && WIDE), "the wide shared pass is unfiltered");
     if (gate != nullptr && *gate == 0u) return;
     extern __shared__ __align__(16) unsigned char smem[];
     uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64] (WIDE: none)
@@ -1338,11 +1342,13 @@ __device__ __forceinline__ void bound8_block_mq(const u4* __restrict__ p, const 
 // no candidate in a tile computes no interval at all.  A wave that reads no tile publishes dead lists.  The integer walk, the int64
 // combination and bound_scan_interval8 are untouched.  A masked call (one bitmap in v.alive) is this form with a table of null sets.
 // WIDE: as k_bound_scan_mq's — the walk and the pre-test with a list length of 64, the tail bound_scan_tail_wide_mq.
+// SETS and WIDE together: as k_bound_scan_mq<., ., true, true> — and the pre-test stays per query over a list length of 64: a query without a
+// candidate in the wave's first read tile keeps a threshold word of 0xFFFFFFFF, which passes every live candidate of a later tile on to the
+// insert, so its list is the one the unfiltered walk would keep over its own candidates.
 template <int M, int QB, bool SETS = false, bool WIDE = false>
 __global__ void __launch_bounds__(kScanBlock, 2)
 k_bound_scan8_mq(IndexView v, const u4* __restrict__ qterm, const double* __restrict__ qpar, uint32_t nq, uint32_t k,
                  uint32_t* __restrict__ lo_all /* [nq][n_tiles * 64] */, uint64_t* __restrict__ partial /* [nq][grid][k]; WIDE: [nq][grid][kScanWaves][64] */, SetsArg<SETS> tab) {
-    static_assert(!(SETS && WIDE), "the wide shared pass is unfiltered");
     extern __shared__ __align__(16) unsigned char smem[];
     uint64_t* wl = reinterpret_cast<uint64_t*>(smem);                  // [kScanWaves][QB][64] (WIDE: none)
     const uint32_t lane = lane_id();
@@ -2051,6 +2057,58 @@ int bound_wide_route_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t n
     if (plane == 2 || !has_plane8) return 1;
     return plane == 1 || bound_wide_auto(kBoundWideMq8Floor[cls], rule_metric, dim, rows, k) ? 2 : 1;
 }
+// The FILTERED wide shared pass's rule (2 - 8 queries, each over its own alive & set, or all over one bitmap): a knob of its own
+// (qv_index_set_bound_scan_wide_filtered_mq / QV_BOUND_SCAN_WIDE_FILTERED_MQ), independent of the three other wide knobs — bound_wide_route,
+// bound_wide_route_filtered and bound_wide_route_mq answer as they did —, and the plane of the filtered shared pass's plane knob
+// (bound_mq_filtered).  What the kernels need is what the unfiltered wide shared pass needs (the same walk, funnel and buffer), and on top:
+// a tile that holds a candidate, and MORE candidates than results for EVERY query of the piece — min_candidates is the smallest count among
+// them; a query whose set holds k live rows or fewer has no H_j worth a pass and keeps its path and its clamped count (the dispatch cuts
+// the piece around it).
+// AUTOMATIC: nothing yet — the floors below are all zero rows, so AUTO answers 0 for every shape and with nothing set a filtered call
+// launches what it launches today.  Measured (profiles/LAB_r27_bound_scan_wide_filtered_mq.md; cosine, device-pointer row-set calls, five
+// alternating rounds of 20 calls, nq = 2, 4, 5, 8, k = 65, 100, 1000; today's path is a single-query filtered wide scan per query for distinct
+// sets and the key-per-row shared pass for one set).  us per call at k = 100, today / bfloat16 first / 8-bit first (spreads <= 21 us, at
+// 10M x 768 <= 64 us):
+//   768 dims   1M   null sets   nq 2: 524 / 378 / 290    nq 4: 551 / 428 / 351    nq 5: 603 / 591 / 449    nq 8: 618 / 658 / 540
+//                   1 % each    nq 2: 442 / 328 / 253    nq 4: 898 / 404 / 301    nq 5: 1123 / 528 / 354   nq 8: 1801 / 560 / 383
+//                   tile in ten nq 2: 556 / 189 / 185    nq 4: 587 / 226 / 224    nq 5: 655 / 300 / 266    nq 8: 685 / 335 / 299
+//              3M   null sets   nq 2: 1495 / 865 / 546   nq 4: 1619 / 945 / 636   nq 5: 1711 / 1245 / 804  nq 8: 1792 / 1366 / 961
+//                   1 % each    nq 2: 663 / 722 / 464    nq 4: 1338 / 908 / 581   nq 5: 1673 / 1175 / 674  nq 8: 2679 / 1249 / 732
+//                   tile in ten nq 2: 1526 / 461 / 354   nq 4: 1656 / 543 / 451   nq 5: 1784 / 1156 / 619  nq 8: 1867 / 1282 / 750
+//              10M  null sets   nq 2: 4888 / 2557 / 1452 nq 4: 5322 / 2758 / 1629 nq 5: 5676 / 3547 / 2016 nq 8: 6032 / 3807 / 2327
+//                   1 % each    nq 2: 1578 / 2042 / 1176 nq 4: 3140 / 2640 / 1532 nq 5: 3928 / 3476 / 1795 nq 8: 6278 / 3720 / 1986
+//                   tile in ten nq 2: 4860 / 507 / 373   nq 4: 5287 / 584 / 457   nq 5: 5645 / 994 / 594   nq 8: 6001 / 1123 / 722
+//   128 dims   10M  null sets   nq 2: 1039 / 618 / 478   nq 4: 1156 / 735 / 681   nq 5: 1263 / 869 / 901   nq 8: 1397 / 1101 / 1220
+//                   1 % each    nq 2: 575 / 513 / 380    nq 4: 1243 / 664 / 504   nq 5: 1485 / 768 / 652   nq 8: 2485 / 926 / 816
+//                   tile in ten nq 2: 1043 / 233 / 241   nq 4: 1157 / 312 / 327   nq 5: 1263 / 378 / 388   nq 8: 1397 / 498 / 515
+// LOSSES: the bfloat16 copy first lost to today's path with TWO queries over distinct 1 % sets at 3M and 10M x 768 at every k (two
+// single-query 8-bit-first scans beat one shared bfloat16 pass), and at 1M x 768 with null sets for 8 queries at every k and 5 at k = 1000,
+// where the 8-bit plane first also lost at k = 1000 with 8 queries (705 against 673); the 8-bit plane first lost to the bfloat16 copy
+// first at 10M x 128 for 5 and 8 queries over null sets and for every nq at one tile in ten, and at 1M x 768 at one tile in ten for
+// k = 65 and 1000.  Every other cell won.  The wins therefore depend on the KIND of filter (one set for all against a set per query) as
+// well as on candidate tiles, which BoundWideFilterFloor cannot express: class QB = 4 loses a cell at every measured size of 768
+// dimensions with the bfloat16 copy first.  The tables stay at zero until the rule can tell those apart; "always" reaches the form.
+// Whatever they come to hold, AUTO never takes a shape bound_wide_route_mq declines under AUTO (bound_wide_auto with the unfiltered
+// form's floor is asked first).  NOT measured: sparser filters, QV_L2 with the planes, k above 1000, other widths.
+constexpr BoundWideFilterFloor kBoundWideFilterMqFloor[2] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};    // the form against today's filtered paths, QB = 4 / QB = 8: not measured
+constexpr BoundWideFilterFloor kBoundWide8FilterMqFloor[2] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};   // ... and the 8-bit plane first against the bfloat16 copy first: not measured
+int bound_wide_route_filtered_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered_mq, bool has_plane, bool has_plane8,
+                                 uint32_t candidate_tiles, uint64_t min_candidates) {
+    static const int env_wide = env_int("QV_BOUND_SCAN_WIDE_FILTERED_MQ", 0);
+    const int mode = wide_mode ? wide_mode : env_wide;
+    if (mode == 2) return 0;
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)rows + 63) / 64);
+    const bool metric_ok = rule_metric == QV_COSINE || rule_metric == QV_DOT || rule_metric == QV_RULE_L2_PLANES;
+    if (nq < 2 || nq > kBoundMqMax || k <= (uint32_t)kMaxFusedK || k > kBoundWideMaxK || !metric_ok || !has_plane) return 0;
+    if ((dim & 15u) != 0 || dim == 0 || dim > kBoundMaxDim || n_tiles < 8 || k >= rows || !flat_select_redo_one_serves(n_tiles)) return 0;
+    if ((uint64_t)nq * n_tiles * 256 > (2ull << 30)) return 0;
+    if (candidate_tiles == 0 || min_candidates <= (uint64_t)k) return 0;
+    const int cls = nq <= 4 ? 0 : 1;
+    if (mode != 1 && !bound_wide_filtered_auto(kBoundWideMqFloor[cls], kBoundWideFilterMqFloor[cls], rule_metric, dim, rows, k, candidate_tiles)) return 0;
+    const int plane = bound_plane_mode(bound_mq_filtered, plane_mode_filtered_mq);
+    if (plane == 2 || !has_plane8) return 1;
+    return plane == 1 || bound_wide_filtered_auto(kBoundWideMq8Floor[cls], kBoundWide8FilterMqFloor[cls], rule_metric, dim, rows, k, candidate_tiles) ? 2 : 1;
+}
 // the wide shared pass's buffer.  The pass's flag words come first and stay: the redo reads its flags from them.  The redo's workspace
 // overlays the rest: it is written only when every bound stage and the counted selection have ended.
 struct BoundWideMqLayout {
@@ -2077,10 +2135,16 @@ static BoundWideMqLayout bound_wide_mq_layout(void* base, const ScanPlan& p, uin
 }
 size_t bound_scan_wide_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log) { return bound_wide_mq_layout(nullptr, p, nq, k, n_tiles, dim, log).total; }
 hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                                     uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first) {
-    // (whether the pass is TAKEN is bound_wide_route_mq's decision; here only what the kernels need)
+                                     uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first, const RowSetRef* h_sets) {
+    // (whether the pass is TAKEN is bound_wide_route_mq's decision — bound_wide_route_filtered_mq's with h_sets; here only what the kernels need,
+    // which is the same for both: the sets add no limit of their own)
     if (bound_wide_route_mq(rule_metric(v), v.dim, v.n_rows, nq, k, 1, plane8_first ? 1 : 2, v.plane != nullptr, v.plane8 != nullptr) != (plane8_first ? 2 : 1) || !d_ctrl || !d_stats)
         return hipErrorInvalidValue;
+    // h_sets: query j over alive & h_sets[j] — stage 1's SETS + WIDE forms and the set-carrying redo; everything between them is the unfiltered
+    // form's: the per-query H_j, collect, re-score and counted selection read lower-bound words and keys, and a non-candidate of query j
+    // carries 0xFFFFFFFF and a dead key in query j's plane and list alone
+    BoundSetTable tab;
+    for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
     const uint32_t grid = p.grid;
     const BoundWideMqLayout L = bound_wide_mq_layout(d_ws, p, nq, k, v.n_tiles, v.dim);
     const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(kBoundCollectGrid, (n_pad + kCollectChunk - 1u) / kCollectChunk);
@@ -2098,11 +2162,13 @@ hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, cons
     const uint32_t* hand_in = plane8_first ? hand : nullptr;
     uint32_t* max_word = d_stats + kBoundWideMqStatsWord;             // the prep kernels clear "the pass's largest survivor count": this form's own word
     static const int trace = env_int("QV_TRACE", 0);                   // (one read per process, as qv_scan.hip's)
-    if (trace) fprintf(stderr, "qv: scan kernel = %sk_bound_scan_mq wide QB=%d + select + k_bound_collect_wide_mq + k_bound_rescore_wide_mq, then k_select_sort and the flagged key-per-row redo (nq=%u, tiles=%u, k=%u)\n",
-                       plane8_first ? "k_bound_scan8_mq wide + select + k_bound_collect_wide_mq + k_bound_rescore_wide_mq, then gated " : "", nq <= 4 ? 4 : 8, nq, v.n_tiles, k);
-    auto run = [&](auto Mc, auto Qc) -> hipError_t {
+    if (trace) fprintf(stderr, "qv: scan kernel = %s%sk_bound_scan_mq wide QB=%d + select + k_bound_collect_wide_mq + k_bound_rescore_wide_mq, then k_select_sort and the flagged key-per-row redo (nq=%u, tiles=%u, k=%u)\n",
+                       h_sets ? "(sets) " : "", plane8_first ? "k_bound_scan8_mq wide + select + k_bound_collect_wide_mq + k_bound_rescore_wide_mq, then gated " : "", nq <= 4 ? 4 : 8, nq, v.n_tiles, k);
+    auto run = [&](auto Mc, auto Qc, auto Sc) -> hipError_t {
         constexpr int M = decltype(Mc)::value, QB = decltype(Qc)::value;
-        const SetsArg<false> no_sets{};
+        constexpr bool SETS = decltype(Sc)::value;
+        SetsArg<SETS> sets{};
+        if constexpr (SETS) sets = tab;
         // (the dynamic LDS of every re-score before anything is launched; the wide stage-1 kernels take none)
         hipError_t e = plane8_first ? set_lds((k_bound_rescore_wide_mq<M, 1>), lds2) : set_lds((k_bound_rescore_wide_mq<M, 0>), lds2);
         if (e == hipSuccess && plane8_first) e = set_lds((k_bound_rescore_wide_mq<M, 2>), lds2);
@@ -2117,15 +2183,16 @@ hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, cons
         };
         if (plane8_first) {
             hipLaunchKernelGGL((k_bound_prep8_mq<QB>), dim3(QB), dim3(kScanBlock), 0, s, d_queries, nq, v.dim, reinterpret_cast<int8_t*>(L.qblk), L.qnorm, hand, max_word, (uint32_t*)nullptr);
-            hipLaunchKernelGGL((k_bound_scan8_mq<M, QB, false, true>), dim3(grid), dim3(kScanBlock), 0, s, v, reinterpret_cast<const u4*>(L.qblk), (const double*)L.qnorm, nq, kBoundWideListLen, L.lo_all, L.lists, no_sets);
+            hipLaunchKernelGGL((k_bound_scan8_mq<M, QB, SETS, true>), dim3(grid), dim3(kScanBlock), 0, s, v, reinterpret_cast<const u4*>(L.qblk), (const double*)L.qnorm, nq, kBoundWideListLen, L.lo_all, L.lists, sets);
             e = finish(k_bound_rescore_wide_mq<M, 1>, nullptr, nullptr);
             if (e != hipSuccess) return e;
         }
         hipLaunchKernelGGL((k_bound_prep_mq<QB>), dim3((v.dim * QB + 255) / 256 + QB), dim3(256), 0, s, d_queries, nq, v.dim, L.qblk, L.qnorm, max_word, gate);
-        hipLaunchKernelGGL((k_bound_scan_mq<M, QB, false, true>), dim3(grid), dim3(kScanBlock), 0, s, v, (const float*)L.qblk, (const double*)L.qnorm, nq, kBoundWideListLen, L.lo_all, L.lists, no_sets, gate);
+        hipLaunchKernelGGL((k_bound_scan_mq<M, QB, SETS, true>), dim3(grid), dim3(kScanBlock), 0, s, v, (const float*)L.qblk, (const double*)L.qnorm, nq, kBoundWideListLen, L.lo_all, L.lists, sets, gate);
         return plane8_first ? finish(k_bound_rescore_wide_mq<M, 2>, gate, hand_in) : finish(k_bound_rescore_wide_mq<M, 0>, nullptr, nullptr);
     };
-    auto run_qb = [&](auto Mc) -> hipError_t { return nq <= 4 ? run(Mc, std::integral_constant<int, 4>{}) : run(Mc, std::integral_constant<int, 8>{}); };
+    auto run_sets = [&](auto Mc, auto Qc) -> hipError_t { return h_sets ? run(Mc, Qc, std::true_type{}) : run(Mc, Qc, std::false_type{}); };
+    auto run_qb = [&](auto Mc) -> hipError_t { return nq <= 4 ? run_sets(Mc, std::integral_constant<int, 4>{}) : run_sets(Mc, std::integral_constant<int, 8>{}); };
     hipError_t e = v.metric == QV_COSINE ? run_qb(std::integral_constant<int, QV_COSINE>{})
                  : v.metric == QV_DOT  ? run_qb(std::integral_constant<int, QV_DOT>{}) : run_qb(std::integral_constant<int, QV_L2>{});
     if (e != hipSuccess) return e;
@@ -2133,7 +2200,7 @@ hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, cons
     // queries: the counted selection runs over all nq queries and before the redo, so a handed-back query's outputs are the redo's
     e = launch_select_topk_counted(L.keys, kBoundWideCandCap, kBoundWideCandCap, counts, nq, k, k, d_rows_out, d_dist_out, s, nullptr);
     if (e != hipSuccess) return e;
-    return launch_flat_select_redo(v, p, d_queries, nq, k, k, flags, L.redo, d_rows_out, d_dist_out, s);
+    return launch_flat_select_redo(v, p, d_queries, nq, k, k, flags, L.redo, d_rows_out, d_dist_out, s, h_sets);
 }
 // the interval of one row on the host; 1: a row the bound says nothing about ("unsure"), as host_bound_interval8 reports it
 int host_bound_interval(int metric, uint32_t dim, float s, double qn, double rn, float rres, float* d_lo, float* d_hi) {

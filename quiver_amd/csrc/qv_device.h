@@ -316,8 +316,20 @@ int bound_wide_route_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t n
 size_t bound_scan_wide_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr);
 // d_ctrl: the stream's control words (kBoundMqMax BoundCtrl of which this form uses thr_inv, cand_cnt and ticket: zero on entry, left zero on
 // every exit, hand-backs included); d_stats: the index's counters.  Enqueues everything, the flagged key-per-row redo included: nothing is read on the host.
+// h_sets (optional, a HOST array of nq): the FILTERED form — query j over alive & h_sets[j] (a null entry: every live row; a call with one
+// bitmap for all its queries: v.alive is that bitmap and every entry null).  Stage 1 is k_bound_scan_mq / k_bound_scan8_mq<., ., true, true>, the
+// funnel behind it is the unfiltered form's as it stands (a non-candidate carries 0xFFFFFFFF and a dead key: no kernel behind stage 1 reads
+// a liveness word), and a handed-back query is redone over its own set (launch_flat_select_redo with the sets).  The same workspace.
 hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
-                                     uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first);
+                                     uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first, const RowSetRef* h_sets = nullptr);
+// The FILTERED wide shared pass's rule: 2 - 8 queries at 65 <= k <= kBoundWideMaxK, each over its own alive & set (row sets, null sets, the counted
+// sets of a where search) or all over one bitmap.  A knob of its own (qv_index_set_bound_scan_wide_filtered_mq / QV_BOUND_SCAN_WIDE_FILTERED_MQ),
+// independent of the three other wide knobs, which keep answering as they do; the plane is the filtered shared pass's plane knob
+// (qv_index_set_bound_plane_filtered_mq).  candidate_tiles: the tiles that hold a candidate of any query of the piece, as the host knows them;
+// min_candidates: the smallest live candidate count among the piece's queries — the form needs more than k of them for EVERY query.
+// 0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.  The counters are the wide shared pass's (kBoundWideMqStatsWord).
+int bound_wide_route_filtered_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered_mq, bool has_plane, bool has_plane8,
+                                 uint32_t candidate_tiles, uint64_t min_candidates);
 constexpr uint32_t kBound6StatsWord = 7;   // the 6-bit stage's counters: [7] candidates it passed to the refine, [8] hand-backs, [9] searches
 constexpr uint32_t kBound6CandCap = 262144;   // rows the refine walks on the 8-bit plane (1 MiB of the workspace)
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches
@@ -490,8 +502,11 @@ hipError_t launch_flat_wide(const IndexView& v, const ScanPlan& p, const float* 
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // keys [nq][n_tiles * 64] of nq >= 2 queries, QB (4 or 8) queries per corpus pass (k_flat_keys_mq); d_qws: flat_keys_mq_workspace_bytes
 size_t flat_keys_mq_workspace_bytes(uint32_t nq, uint32_t dim4);
+struct BoundSetTable;
 hipError_t launch_flat_keys_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint64_t* d_keys, void* d_qws, hipStream_t s,
-                               const uint32_t* d_active = nullptr /* device word: only the first *d_active queries are worked on */);
+                               const uint32_t* d_active = nullptr /* device word: only the first *d_active queries are worked on */,
+                               const BoundSetTable* h_tab = nullptr /* with d_active and d_slot_query: slot i over alive & h_tab->e[d_slot_query[i]] (k_flat_keys_mq<., ., ., true>) */,
+                               const uint32_t* d_slot_query = nullptr);
 // scan + selection for nq queries at list length kk <= kMaxSelectK: every query's keys (one 8-byte key per row, k_flat_keys), then
 // launch_select_topk; queries go in groups so that the keys of a group stay under flat_select_group_bytes
 size_t flat_select_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim4, WsLog* log = nullptr);
@@ -500,8 +515,10 @@ hipError_t launch_flat_select(const IndexView& v, const ScanPlan& p, const float
 // The same for the queries whose flags are set (64 < kk <= kMaxSelectK: the batched filter's hand-backs above the wave lists' range), decided
 // and listed on the device: nothing is read back.  Results replace rows / distances [q][k_stride] of those queries.
 size_t flat_select_redo_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log = nullptr);
+// h_sets (optional, a HOST array of nq <= 8 sets: the filtered wide shared pass's hand-backs): flagged query q is redone over alive & h_sets[q] —
+// the same launches with the set-carrying key kernel in k_flat_keys_mq's place, the same workspace.  Null: the kernels this has always launched.
 hipError_t launch_flat_select_redo(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride, const uint32_t* d_flags,
-                                   void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+                                   void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets = nullptr);
 
 // ... and for ONE query behind a device word (the wide bound scan's hand-back): *d_flag non-zero = the query is redone, zero = every launch
 // leaves at once.  The lone query rides in a shared pass of two slots, so two queries' keys must fit a group (flat_select_redo_one_serves).

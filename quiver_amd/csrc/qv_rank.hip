@@ -349,17 +349,21 @@ static FlatSelectLayout flat_select_layout(void* base, uint32_t n_tiles, uint32_
 }
 size_t flat_select_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t kk, uint32_t dim4, WsLog* log) { return flat_select_layout(nullptr, n_tiles, nq, kk, dim4, log).total; }
 static hipError_t flat_select_impl(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
-                                   void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const uint32_t* d_active);
+                                   void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const uint32_t* d_active,
+                                   const BoundSetTable* h_tab = nullptr, const uint32_t* d_slot_query = nullptr);
 hipError_t launch_flat_select(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
                               void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
     return flat_select_impl(v, p, d_queries, nq, kk, k_stride, d_ws, d_rows_out, d_dist_out, s, nullptr);
 }
 // d_active (a device word, or null): only the first *d_active queries are worked on — every kernel's other workgroups leave at once
 // (launch_flat_select_redo: the count is decided on the device).  With it the queries go through the shared passes (nq >= 2, one group).
+// h_tab / d_slot_query (the redo of a filtered wide shared pass; with d_active, one group): query slot i's keys over alive & h_tab->e[d_slot_query[i]].
 static hipError_t flat_select_impl(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride,
-                                   void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const uint32_t* d_active) {
+                                   void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const uint32_t* d_active,
+                                   const BoundSetTable* h_tab, const uint32_t* d_slot_query) {
     const uint32_t n = v.n_tiles * 64;
     const uint32_t g = flat_select_group(v.n_tiles, nq);
+    if (h_tab != nullptr && (d_active == nullptr || g < nq)) return hipErrorInvalidValue;   // (the slots' sets are listed for one group)
     const FlatSelectLayout L = flat_select_layout(d_ws, v.n_tiles, nq, kk, v.dim4);
     uint64_t* keys = L.keys;
     void *sel_ws = L.sel_ws, *qws = L.qws;
@@ -370,7 +374,7 @@ static hipError_t flat_select_impl(const IndexView& v, const ScanPlan& p, const 
         if (m >= 2) {
             // several queries: they share corpus passes (4 or 8 per pass) instead of reading the corpus once each — 8 queries at
             // k = 100 over 1M x 768: one ~0.6 ms pass instead of eight 0.46 ms ones; the selection counts its first window itself
-            hipError_t e2 = launch_flat_keys_mq(v, p, d_queries + (size_t)q0 * v.dim, m, keys, qws, s, d_active);
+            hipError_t e2 = launch_flat_keys_mq(v, p, d_queries + (size_t)q0 * v.dim, m, keys, qws, s, d_active, h_tab, d_slot_query);
             if (e2 != hipSuccess) return e2;
             e2 = launch_select_topk(keys, n, n, m, kk, k_stride, sel_ws, d_rows_out + (size_t)q0 * k_stride, d_dist_out + (size_t)q0 * k_stride, s, false, true, d_active);
             if (e2 != hipSuccess) return e2;
@@ -462,10 +466,15 @@ size_t flat_select_redo_workspace_bytes(uint32_t n_tiles, uint32_t nq, uint32_t 
 // nq_slots: the query count the slots and the layout are made for — nq itself, or 2 for a lone query (launch_flat_select_redo_one: the
 // shared passes take two slots or more, so the query rides with an empty one)
 static hipError_t flat_select_redo_impl(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t nq_slots, uint32_t kk, uint32_t k_stride,
-                                        const uint32_t* d_flags, void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+                                        const uint32_t* d_flags, void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets = nullptr);
+// With sets: a slot finds its query's set through the redo's list (k_flat_keys_mq<., ., ., true> reads list[first + slot] and indexes the table,
+// a kernel argument), so the keys of rows outside alive & set_j are dead before the radix selection sees them.  The key kernel takes the
+// sets rather than a pass of its own behind it: such a pass would read and rewrite slots x n_tiles x 64 keys (80 MB per slot at 10M rows)
+// that the key kernel holds in registers when it decides liveness anyway, and the key kernel with the sets skips the tiles nobody selects.
 hipError_t launch_flat_select_redo(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t kk, uint32_t k_stride, const uint32_t* d_flags,
-                                   void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
-    return flat_select_redo_impl(v, p, d_queries, nq, nq, kk, k_stride, d_flags, d_ws, d_rows_out, d_dist_out, s);
+                                   void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets) {
+    if (h_sets != nullptr && nq > kBoundSets) return hipErrorInvalidValue;
+    return flat_select_redo_impl(v, p, d_queries, nq, nq, kk, k_stride, d_flags, d_ws, d_rows_out, d_dist_out, s, h_sets);
 }
 bool flat_select_redo_one_serves(uint32_t n_tiles) { return lk_redo_slots(n_tiles, 2) >= 2; }
 size_t flat_select_redo_one_workspace_bytes(uint32_t n_tiles, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log) { return flat_select_redo_layout(nullptr, n_tiles, 2, kk, dim, dim4, log).total; }
@@ -474,8 +483,10 @@ hipError_t launch_flat_select_redo_one(const IndexView& v, const ScanPlan& p, co
     return flat_select_redo_impl(v, p, d_query, 1, 2, kk, k_stride, d_flag, d_ws, d_rows_out, d_dist_out, s);
 }
 static hipError_t flat_select_redo_impl(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t nq_slots, uint32_t kk, uint32_t k_stride,
-                                        const uint32_t* d_flags, void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
+                                        const uint32_t* d_flags, void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, const RowSetRef* h_sets) {
     if (nq == 0) return hipSuccess;
+    BoundSetTable tab;
+    for (uint32_t i = 0; i < kBoundSets; i++) tab.e[i] = h_sets && i < nq ? h_sets[i] : RowSetRef{nullptr, 0, 0};
     const uint32_t slots = lk_redo_slots(v.n_tiles, nq_slots);
     if (kk <= (uint32_t)kMaxFusedK || kk > (uint32_t)kMaxSelectK || kk != k_stride || slots < 2) return hipErrorNotSupported;   // (a corpus whose keys leave room for one query at a time: the caller's host path)
     const FlatSelectRedoLayout L = flat_select_redo_layout(d_ws, v.n_tiles, nq_slots, kk, v.dim, v.dim4);
@@ -485,7 +496,7 @@ static hipError_t flat_select_redo_impl(const IndexView& v, const ScanPlan& p, c
     uint32_t round = 0;
     for (uint32_t first = 0; first < nq; first += slots, round++) {
         hipLaunchKernelGGL(k_lk_redo_gather, dim3(slots), dim3(256), 0, s, d_queries, v.dim, list, count, first, rq);
-        hipError_t e = flat_select_impl(v, p, rq, slots, kk, k_stride, L.select_ws, t_rows, t_dist, s, count + 1 + round);
+        hipError_t e = flat_select_impl(v, p, rq, slots, kk, k_stride, L.select_ws, t_rows, t_dist, s, count + 1 + round, h_sets ? &tab : nullptr, list + first);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_lk_redo_scatter, dim3(slots), dim3(256), 0, s, list, count, first, t_rows, t_dist, k_stride, d_rows_out, d_dist_out);
     }

@@ -726,10 +726,19 @@ k_flat_scan_mq(IndexView v, const float* __restrict__ queries, const typename MT
 // (qv_select.hip) for batches that ask for more than 64 results per query and do not go through the matrix-core filter (2 - 8
 // queries, or a metric the filter does not take).  QB queries share a corpus pass, their values arrive as scalar operands
 // (k_flat_scan_mq's SQ form); keys_all [nq][n_tiles * 64].  grid = (workgroups, ceil(nq / QB)).
-template <int M, int U, int QB>
+// SETS (the redo of a FILTERED wide shared pass, launch_flat_select_redo with a table): slot q0 + j holds the vector of query slot_query[q0 + j]
+// of the pass (k_lk_redo_gather put it there), and that query's candidates are alive & tab.e[slot_query[q0 + j]] — the pass's table of at most
+// kBoundSets sets as kernel arguments, indexed on the device because WHICH queries come back is decided there.  Lane j keeps slot q0 + j's
+// (bits, words) pair and fetches its word of the wave's NEXT tile while the current one is walked, as k_bound_scan_mq<., ., true> does; the
+// word comes back per slot with readlane64.  The key of a row outside alive & set_j is a dead key in slot j's plane, so the radix selection
+// behind sees the set and nothing else; a tile no slot selects is not read (dead keys all the same: the planes are a reused workspace), and
+// `first` — the query norms ride along with it — is the first tile the wave READS.  Slots past *active select nothing.  The arithmetic of a
+// key is the form's without sets: the same mq_tile, the same finalize.
+template <int M, int U, int QB, bool SETS = false>
 __global__ void __launch_bounds__(kScanBlock, 2)
 k_flat_keys_mq(IndexView v, const typename MT<M>::Q* __restrict__ qblk, uint32_t nq, uint64_t* __restrict__ keys_all,
-               const uint32_t* __restrict__ active /* null, or a device word: query groups from *active on leave at once (launch_flat_select_redo) */) {
+               const uint32_t* __restrict__ active /* null, or a device word: query groups from *active on leave at once (launch_flat_select_redo) */,
+               SetsArg<SETS> tab = SetsArg<SETS>{}, const uint32_t* __restrict__ slot_query = nullptr /* SETS: the pass's query in each slot, [*active] */) {
     using Q = typename MT<M>::Q;
     using A = typename MT<M>::A;
     const uint32_t lane = lane_id();
@@ -744,7 +753,27 @@ k_flat_keys_mq(IndexView v, const typename MT<M>::Q* __restrict__ qblk, uint32_t
     for (int j = 0; j < QB; j++) { qc[j].qn = 0.0; qc[j].qn32 = 0.0f; }
     const f4* tiles = reinterpret_cast<const f4*>(v.tiles);
     bool first = true;
+    bool mine = false;
+    RowSetRef rs = RowSetRef{nullptr, 0, 0};
+    uint64_t w_next = 0ull;
+    if constexpr (SETS) {
+        static_assert(QB <= (int)kBoundSets, "a slot per lane, a table entry per query of the pass");
+        mine = lane < (uint32_t)QB && q0 + lane < nq && q0 + lane < *active;
+        if (mine) rs = tab.e[slot_query[q0 + lane] & (kBoundSets - 1)];   // lane j: slot q0 + j's set
+        const uint32_t t0 = blockIdx.x * kScanWaves + wave;
+        if (t0 < v.n_tiles) w_next = rowset_word(v.alive, rs, mine, t0);
+    }
     for (uint32_t t = blockIdx.x * kScanWaves + wave; t < v.n_tiles; t += tw) {
+        const uint64_t w = w_next;                                     // (SETS) lane j: alive & set of slot q0 + j, this tile
+        if constexpr (SETS) {
+            if (t + tw < v.n_tiles) w_next = rowset_word(v.alive, rs, mine, t + tw);
+            if (__ballot(w != 0ull) == 0ull) {                         // no slot's candidate in this tile: not read
+#pragma unroll
+                for (int j = 0; j < QB; j++)
+                    if (q0 + j < nq) __builtin_nontemporal_store(kDeadKey, &keys_all[(size_t)(q0 + j) * n + t * 64 + lane]);
+                continue;
+            }
+        }
         A acc[QB], qa[QB];
         if (first) {
             mq_tile<M, U, QB, true>(tiles + (size_t)t * v.dim4 * 64 + lane, q_lds, v.dim4, acc, qa);
@@ -755,9 +784,12 @@ k_flat_keys_mq(IndexView v, const typename MT<M>::Q* __restrict__ qblk, uint32_t
         const uint32_t row = t * 64 + lane;
         double rn = 0.0;
         if constexpr (MT<M>::needs_rnorm) rn = v.rnorm[row];
-        const bool live = (v.alive[t] >> lane) & 1ull;
+        bool live_all = false;
+        if constexpr (!SETS) live_all = (v.alive[t] >> lane) & 1ull;
 #pragma unroll
         for (int j = 0; j < QB; j++) {
+            bool live;
+            if constexpr (SETS) live = (readlane64(w, (uint32_t)j) >> lane) & 1ull; else live = live_all;
             const uint64_t key = live ? make_key(finalize<M>(acc[j], qc[j], rn), row) : kDeadKey;
             if (q0 + j < nq) __builtin_nontemporal_store(key, &keys_all[(size_t)(q0 + j) * n + row]);
         }
@@ -766,7 +798,10 @@ k_flat_keys_mq(IndexView v, const typename MT<M>::Q* __restrict__ qblk, uint32_t
 
 size_t flat_keys_mq_workspace_bytes(uint32_t nq, uint32_t dim4) { return up256((size_t)(nq + 8) * dim4 * 4 * sizeof(double)); }
 // keys of nq >= 2 queries in shared corpus passes; d_qws: flat_keys_mq_workspace_bytes
-hipError_t launch_flat_keys_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint64_t* d_keys, void* d_qws, hipStream_t s, const uint32_t* d_active) {
+// h_tab (optional, a HOST table) with d_slot_query and d_active: the set-carrying form — slot i computes over alive & h_tab->e[d_slot_query[i]]
+hipError_t launch_flat_keys_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint64_t* d_keys, void* d_qws, hipStream_t s, const uint32_t* d_active,
+                               const BoundSetTable* h_tab, const uint32_t* d_slot_query) {
+    if (h_tab != nullptr && (d_active == nullptr || d_slot_query == nullptr)) return hipErrorInvalidValue;
     const uint32_t want = (v.n_tiles + kScanWaves - 1) / kScanWaves;
     const uint32_t grid = std::max(1u, std::min(want, p.grid));
 #define QV_KMQ(MMM, QQ)                                                                                                   \
@@ -775,6 +810,9 @@ hipError_t launch_flat_keys_mq(const IndexView& v, const ScanPlan& p, const floa
         const uint32_t groups = (nq + QQ - 1) / QQ;                                                                       \
         const uint32_t per = v.dim4 * 4 * QQ;                                                                             \
         hipLaunchKernelGGL((k_prep_qblk<MMM, QQ>), dim3((per + 255) / 256, groups), dim3(256), 0, s, d_queries, nq, v.dim, v.dim4, static_cast<QT*>(d_qws)); \
+        if (h_tab != nullptr)                                                                                             \
+            hipLaunchKernelGGL((k_flat_keys_mq<MMM, 4, QQ, true>), dim3(grid, groups), dim3(p.block), 0, s, v, static_cast<const QT*>(d_qws), nq, d_keys, d_active, *h_tab, d_slot_query); \
+        else                                                                                                              \
         hipLaunchKernelGGL((k_flat_keys_mq<MMM, 4, QQ>), dim3(grid, groups), dim3(p.block), 0, s, v, static_cast<const QT*>(d_qws), nq, d_keys, d_active); \
     }
     if (nq >= 5) { QV_DISPATCH_METRIC(v.metric, { QV_KMQ(MM, 8) }); }

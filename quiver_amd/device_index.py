@@ -454,6 +454,14 @@ class DeviceIndex:
         first follows set_bound_plane_mq; the counters are bound_scan_wide_mq_stats' (qv_index_set_bound_scan_wide_mq)"""
         check(lib().qv_index_set_bound_scan_wide_mq(self._h, self.BOUND_SCAN.get(mode, mode)))
 
+    def set_bound_scan_wide_filtered_mq(self, mode):
+        """the wide form of a FILTERED shared pass: one call of 2 to 8 queries at 65 <= k <= 1024, each over its own live & set
+        (search_rowsets, search_rowsets_device, search_where) or all over one mask (search_masked): "auto" (nothing yet: the measured
+        wins depend on the kind of filter, which the rule cannot tell apart, so an unset index launches what it always launched), "always" (every piece of consecutive queries that each have
+        more live candidates than k), "never"; a knob of its own, independent of the three other wide knobs; which plane comes first
+        follows set_bound_plane_filtered_mq; the counters are bound_scan_wide_mq_stats' (qv_index_set_bound_scan_wide_filtered_mq)"""
+        check(lib().qv_index_set_bound_scan_wide_filtered_mq(self._h, self.BOUND_SCAN.get(mode, mode)))
+
     def bound_scan_wide_mq_stats(self) -> dict:
         """the largest survivor count among the last wide shared pass's queries (each in the stage that answered it), queries handed back to
         the key-per-row path, queries that took the form, whether the bfloat16 copy exists"""
