@@ -182,6 +182,37 @@ func (d *oneGPU) setBoundScanWideFilteredMq(mode int) error {
 	return nil
 }
 
+// Modes of SetFilteredBatchWide (QV_FILTERED_BATCH_*).
+const (
+	FilteredBatchAuto   = int(C.QV_FILTERED_BATCH_AUTO)
+	FilteredBatchAlways = int(C.QV_FILTERED_BATCH_ALWAYS)
+	FilteredBatchNever  = int(C.QV_FILTERED_BATCH_NEVER)
+)
+
+// SetFilteredBatchWide (qv_index_set_filtered_batch_wide): whether ONE filtered call of 9 or more queries that want 65 to 1024 results each
+// (row sets or where-filters, one per query: what BatchSearch sends for callers that each carry a facet filter, and the negative-example
+// branches' max(2k, 30)) takes the batched path — the sample bound over each query's set, one matrix-core filter pass for all of them,
+// the large-k exact stage — instead of runs of one set each.  FilteredBatchAlways whenever the shape applies, FilteredBatchNever never;
+// FilteredBatchAuto, the default, takes nothing until cells are measured as won.  Results are the exact filtered scan's either way.
+// One GPU only: a sharded index has no such setter.
+func (x *Index) SetFilteredBatchWide(mode int) error {
+	x.mu.Lock()
+	defer x.mu.Unlock()
+	d, ok := x.dev.(*oneGPU)
+	if !ok {
+		return errors.New("quivergpu: the filtered batch is a one-GPU path; a sharded index has no such setter")
+	}
+	return d.setFilteredBatchWide(mode)
+}
+
+func (d *oneGPU) setFilteredBatchWide(mode int) error {
+	defer pinned()() // qv_last_error is thread-local: the failing call and the read of its message stay on one OS thread
+	if C.qv_index_set_filtered_batch_wide(d.h, C.int(mode)) != C.QV_OK {
+		return lastErr()
+	}
+	return nil
+}
+
 // Insert implements core.Index (collection.go:80).  Error strings follow exact.go:45-50.
 func (x *Index) Insert(id string, v vectortypes.F32) error {
 	x.mu.Lock()

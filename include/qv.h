@@ -480,6 +480,29 @@ int qv_index_filtered_batch_stats(qv_index* idx, uint64_t out[4]);
  * for one tile-aligned set named by every query, which these arguments cannot tell apart; 10M rows and 128 dimensions are
  * unmeasured.  So AUTO takes nothing yet: ask for the path with QV_FILTERED_BATCH_ALWAYS.  Monotone in n_not_sparse. */
 int qv_batched_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse);
+/* ---- filtered batches of 9 or more queries that want 65 to 1024 results each ----
+ * The same path for 64 < k <= 1024, under a mode of its own so that nothing above changes its answer: the sample bound over each
+ * query's set, ONE matrix-core filter pass with batched_cand_cap(k) candidate slots per query and the set test in the flush, then the
+ * unfiltered batch's large-k funnel (intervals, the k-th smallest upper bound, survivors, exact distances, a counted selection) over
+ * candidates of live & set_q only.  Results equal the exact filtered scan's: rows, float32 bits, order, counts, padding — also where a
+ * set holds fewer than k live rows.  Over a large corpus the bound is a guess that is checked behind the filter; its rank is taken per
+ * query on the device, from the query's own in-set sample rows and the set's live rows.  Hand-backs are the same three
+ * kinds, flagged per query and redone alone on the exact filtered paths for k > 64 (the key-per-row scan and selection, or the
+ * filtered wide forms where their own rules take them); sparse_ppm is the one qv_index_set_filtered_batch holds, and
+ * qv_index_filtered_batch_stats counts this path's queries, hand-backs and batches into the same four counters.
+ * Reached from the host forms qv_index_search_rowsets and qv_index_search_where (whose k > 64 form makes real sets first and feeds
+ * them in).  NOT from a pass shared by concurrent callers: the callers' front forms passes up to k = 64 only, so above that every
+ * call runs on its own.  Out of scope as above, and k > 1024.
+ *   mode   QV_FILTERED_BATCH_ALWAYS / _NEVER / _AUTO.  AUTO (the default) takes NOTHING: a cell enters it only once it is measured
+ *          faster than both the cut into runs and the filtered wide shared passes by more than both arms' spread
+ *          (profiles/LAB_r28_filtered_batch_wide.md).  The environment variable QV_FILTERED_BATCH_WIDE (1 always, 2 never; read once
+ *          per process) sets the default of indexes that never call this. */
+int qv_index_set_filtered_batch_wide(qv_index* idx, int mode);
+/* The dispatch's rule for that cell, without an index or a device; arguments as qv_batched_applies_filtered's (AUTO reads
+ * QV_FILTERED_BATCH_WIDE first).  1 / 0, < 0 on an argument error.  0 under NEVER and under AUTO; under ALWAYS 0 for fewer than 9
+ * queries or 9 not-sparse ones, k <= 64 (qv_batched_applies_filtered's cell), k > 1024, a metric or shape the batched path does not
+ * take, QV_FILTER_OFF.  Monotone in n_not_sparse. */
+int qv_batched_applies_filtered_wide(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse);
 /* Which main filter kernel a FILTERED batch of that shape launches, without an index or a device: the batched path's plan for (metric,
  * dim, rows, nq, k, filter), then the substitution a batch with sets applies where the planned kernel has no variant that tests the
  * sets (the register-resident one: the bfloat16-copy kernel or the 256-row eight-wave kernel instead).  has_bf16_plane: the index was

@@ -48,6 +48,16 @@ def batched_applies_filtered(metric, dim: int, rows: int, nq: int, k: int, filte
     return rc == 1
 
 
+def batched_applies_filtered_wide(metric, dim: int, rows: int, nq: int, k: int, filter="auto", mode="auto", n_not_sparse: int | None = None) -> bool:
+    """the same rule for 65 to 1024 results per query (qv_batched_applies_filtered_wide); mode: as set_filtered_batch_wide takes it"""
+    from ._lib import check
+    m = metric_id(metric) if isinstance(metric, str) else int(metric)
+    rc = lib().qv_batched_applies_filtered_wide(m, dim, rows, nq, k, DeviceIndex.FILTERS.get(filter, filter), DeviceIndex.FILTERED_BATCH.get(mode, mode),
+                                                nq if n_not_sparse is None else n_not_sparse)
+    if rc < 0:
+        check(rc)
+    return rc == 1
+
 def batched_filter_route(metric, dim: int, rows: int, nq: int, k: int, filter="auto", bf16_rows: bool = False, cus: int = 256):
     """(padded query count, main filter kernel) of a FILTERED batch of that shape — the batched path's plan and the substitution a batch with
     sets applies, on the host, without an index or a device (qv_batched_filter_route); the kernel as a name of DeviceIndex.BATCHED_FILTERS;
@@ -61,4 +71,4 @@ def batched_filter_route(metric, dim: int, rows: int, nq: int, k: int, filter="a
 
 
 __all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq", "scan_bound8_applies_filtered_mq",
-           "batched_applies_filtered", "batched_filter_route", "graph_reject_applies", "graph_reject_image_applies"]
+           "batched_applies_filtered", "batched_applies_filtered_wide", "batched_filter_route", "graph_reject_applies", "graph_reject_image_applies"]

@@ -1391,7 +1391,13 @@ static uint32_t rowsets_not_sparse(const qv_index* idx, const RsFilter* fl, uint
     return n;
 }
 static bool filtered_batch_takes(const qv_index* idx, uint32_t nq, uint32_t k, const RsFilter* fl) {
-    if (nq < qv::kFilteredBatchMinQueries || k > (uint32_t)qv::kMaxFusedK || idx->n_live < 4 * (uint64_t)k) return false;
+    if (nq < qv::kFilteredBatchMinQueries || idx->n_live < 4 * (uint64_t)k) return false;
+    if (k > (uint32_t)qv::kMaxFusedK) {                               // 65 .. 1024 results: a rule, a mode and a route of their own (every filter is a real set here)
+        if (k > qv::kFilteredBatchWideMaxK) return false;
+        for (uint32_t q = 0; q < nq; q++) if (fl[q].where) return false;
+        if (!qv::filtered_batch_wide_rule(idx->metric, idx->dim, idx->n_rows, nq, k, idx->filter, idx->filtered_batch_wide, rowsets_not_sparse(idx, fl, nq))) return false;
+        return qv::batched_sets_wide_supported(idx->view(), nq, k, idx->cus);
+    }
     if (!qv::filtered_batch_rule(idx->metric, idx->dim, idx->n_rows, nq, k, idx->filter, idx->filtered_batch, rowsets_not_sparse(idx, fl, nq))) return false;
     return qv::batched_sets_supported(idx->view(), nq, k, idx->cus);   // (the route: sample scores from a filter kernel)
 }
@@ -1538,7 +1544,7 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
         if (p.batched) {                                              // sample bound over the sets, the filter, the exact re-score: one corpus pass for the piece
             if (!d_sets || !d_flags_out) return fail(QV_ERR_DEVICE, "filtered batch without its set table");
             const ProfilePair pp = profile_begin(idx);
-            const qv::BatchedSets bs{d_sets + p.q0, qv::filtered_batch_ppm(idx->filtered_batch_ppm)};
+            const qv::BatchedSets bs{d_sets + p.q0, qv::filtered_batch_ppm(idx->filtered_batch_ppm), idx->n_live};
             hipError_t e = qv::launch_batched(v, plan, q, p.nq, k, ws, r_out, d_out, d_flags_out, idx->cus, s, pp.ev0, pp.ev1, &bs);
             profile_end(idx, pp, e == hipSuccess);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "filtered batch launch failed: %s", hipGetErrorString(e));
@@ -1652,7 +1658,11 @@ static int rowsets_pass(qv_index* idx, const float* queries, uint32_t nq, uint32
         const size_t sbytes = (size_t)nq * sizeof(qv::RowSetRef);
         if ((rc = c->h_sets.ensure(sbytes)) || (rc = c->d_sets.ensure(sbytes)) || (rc = c->h_ids.ensure(fbytes))) return rc;
         qv::RowSetRef* refs = static_cast<qv::RowSetRef*>(c->h_sets.p);
-        for (uint32_t q = 0; q < nq; q++) refs[q] = rs_ref(idx, fl[q]);
+        for (uint32_t q = 0; q < nq; q++) {
+            refs[q] = rs_ref(idx, fl[q]);
+            // (above kMaxFusedK results a guessed bound takes its rank from the set's live rows: counted here, once per run of queries naming one set)
+            if (k > (uint32_t)qv::kMaxFusedK && fl[q].set) refs[q].live = q > 0 && fl[q].set == fl[q - 1].set ? refs[q - 1].live : (uint32_t)rowset_live(idx, fl[q].set);
+        }
         HIPCHK(hipMemcpyAsync(c->d_sets.p, c->h_sets.p, sbytes, hipMemcpyHostToDevice, c->stream));
     }
     rc = rowsets_enqueue(idx, hc.d_queries(), nq, k, fl.data(), pieces, hc.ws(), d_mask, hc.d_rows(), hc.d_dist(), hc.stream(), tickets,
@@ -2105,6 +2115,19 @@ int qv_index_set_filtered_batch(qv_index* idx, int mode, uint32_t sparse_ppm) {
     idx->filtered_batch = mode;
     idx->filtered_batch_ppm = sparse_ppm;
     return QV_OK;
+}
+
+int qv_index_set_filtered_batch_wide(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_FILTERED_BATCH_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    idx->filtered_batch_wide = mode;
+    return QV_OK;
+}
+
+int qv_batched_applies_filtered_wide(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse) {
+    if (mode < 0 || mode > QV_FILTERED_BATCH_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
+    return qv::filtered_batch_wide_rule(metric, dim, rows, nq, k, filter, mode, std::min(n_not_sparse, nq)) ? 1 : 0;
 }
 
 int qv_index_filtered_batch_stats(qv_index* idx, uint64_t out[4]) {

@@ -118,6 +118,7 @@ struct qv_index {
     float* d_rres6 = nullptr;
     bool plane6_lost = false;                  // it could not be allocated: the index carries on with the 8-bit plane
     int filtered_batch = 0;                    // qv_index_set_filtered_batch: QV_FILTERED_BATCH_*
+    int filtered_batch_wide = 0;               // qv_index_set_filtered_batch_wide: the same question for 65 .. 1024 results per query
     uint32_t filtered_batch_ppm = 0xFFFFFFFFu; // ... and its sparse floor in millionths of the rows (0xFFFFFFFF: the default, 0: never sparse)
     std::atomic<uint64_t> fb_stats[4] = {};    // qv_index_filtered_batch_stats: queries on the path, handed back (overflow / no bound / failed guess), handed back as sparse, batches
     uint32_t* d_bound_stats = nullptr;         // [0] survivors of the last bound scan, [1] hand-backs, [2] bound scans (written by the kernels)

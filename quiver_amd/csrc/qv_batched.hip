@@ -1571,7 +1571,8 @@ static size_t sample_select_lds_bytes(uint32_t srows, uint32_t k) { return (size
 static bool sample_select_applies(uint32_t srows, uint32_t k) { return srows >= 4096 && (uint64_t)k * sample_select_chunk(srows) <= kSelKeys && k <= 1024; }
 template <int M>
 __global__ void __launch_bounds__(1024)
-k_sample_select(const float* __restrict__ bounds, uint32_t srows, uint32_t k, float gref, float* __restrict__ sample_dist) {
+k_sample_select(const float* __restrict__ bounds, uint32_t srows, uint32_t k, float gref, float* __restrict__ sample_dist,
+                const uint32_t* __restrict__ ranks = nullptr /* a filtered batch's guessed bound: query q's own rank, 1 .. k (k_sets_guess_rank); 0 = no guess, +inf */) {
     extern __shared__ uint32_t s_keys[];                              // k chunks' rows (sample_select_lds_bytes): small k leaves room for a second block per CU
     __shared__ uint32_t s_min[1024];
     __shared__ uint32_t s_bins[256];
@@ -1581,6 +1582,8 @@ k_sample_select(const float* __restrict__ bounds, uint32_t srows, uint32_t k, fl
     const uint32_t qi = blockIdx.x;
     const float* sc = bounds + (size_t)qi * srows;
     const uint32_t chunk = sample_select_chunk(srows);
+    const uint32_t kq = ranks ? ranks[qi] : k;                        // (the output slot and the LDS stay the launch's k: kq <= k)
+    if (kq == 0) { if (t == 0) sample_dist[(size_t)qi * k + (k - 1)] = __builtin_inff(); return; }   // (block-uniform)
     // stage 1: this thread's chunk = rows t, t + 1024, t + 2048, ... (consecutive threads read consecutive bounds): its minimum
     {
         float m = __builtin_inff();
@@ -1595,7 +1598,7 @@ k_sample_select(const float* __restrict__ bounds, uint32_t srows, uint32_t k, fl
     }
     if (t == 0) s_n = 0;
     __syncthreads();
-    const uint32_t t1 = block_kth_smallest(s_min, 1024, k, s_bins, s_scal);
+    const uint32_t t1 = block_kth_smallest(s_min, 1024, kq, s_bins, s_scal);
     uint32_t ukey = t1;
     if (t1 != 0xFFFFFFFFu && t1 < ord_f32(__builtin_inff())) {
         // stage 2: the chunks at or below T1 (beyond kSelKeys / chunk of them — exact ties only — the bound comes from a subset: still k rows)
@@ -1610,7 +1613,7 @@ k_sample_select(const float* __restrict__ bounds, uint32_t srows, uint32_t k, fl
             s_keys[i] = ord_f32(r < srows ? sc[r] : __builtin_inff());
         }
         __syncthreads();
-        ukey = block_kth_smallest(s_keys, total, k, s_bins, s_scal);
+        ukey = block_kth_smallest(s_keys, total, kq, s_bins, s_scal);
     }
     if (t == 0) {
         const float x = ukey == 0xFFFFFFFFu ? __builtin_inff() : unord_f32(ukey);
@@ -2652,7 +2655,10 @@ static BatchedLayout batched_layout(void* base, const IndexView& v, const ScanPl
     L.srows = w.take<uint32_t>(nq * r.k);                   // sample rows/dist
     L.sdist = w.take<float>(nq * r.k);
     w.align256();
-    L.sparts = w.take<float>(nq * r.k * 4);                 // k_sample_bound's partial lists (up to four parts per query)
+    // k_sample_bound's partial lists (up to four parts per query).  Under a guessed bound the bounds live here, query q's at [q * ks + ks - 1]; a
+    // filtered batch above kMaxFusedK results takes ks up to 2 k (batched_sets_adapt: bounds below nq * 2 k) and keeps its nq per-query ranks in the
+    // last quarter, from nq * 3 k (batched_sample_bound) — both inside these nq * 4 k words for every k >= 1, whatever ks the launch settles on.
+    L.sparts = w.take<float>(nq * r.k * 4);
     w.slack(256);                                           // (slack kept from the hand-written version)
     L.ubuf = r.guess ? L.sparts : L.sdist;
     w.align256();
@@ -2671,19 +2677,35 @@ size_t batched_workspace_bytes(const IndexView& v, const ScanPlan& p, uint32_t n
 }
 
 // A filtered batch (BatchedSets) needs every sample row's bound in L.sscore between the score kernel and a selection of its own: the
-// exact-scan sample has no such array, and the group minima mix rows inside and outside a set.  Up to kMaxFusedK results: the candidate
-// lists keep kMfmaCandCap slots, and the exact row-set scans that redo a handed-back query go no further.
+// exact-scan sample has no such array, and the group minima mix rows inside and outside a set.  Above kMaxFusedK results (up to
+// kFilteredBatchWideMaxK) the lists keep batched_cand_cap(k) slots — the flush reads the capacity from the word in front of the counters —
+// and the funnel behind them must be the one that copes with FEWER candidates than k, which a set can leave: k_cand_narrow (H = +inf, every
+// candidate survives) and the counted selection (pads past the survivors).
 static bool batched_sets_route(const BatchedRoute& r) {
-    return r.k <= (uint32_t)kMaxFusedK && r.sample != SampleScores::exact_scan && (r.bound == SampleBound::sample_select || r.bound == SampleBound::histogram);
+    if (r.sample == SampleScores::exact_scan || (r.bound != SampleBound::sample_select && r.bound != SampleBound::histogram)) return false;
+    // (a guessed bound there takes its rank per query, which k_sample_select alone does: a plan whose guess needs the histogram kernels — k chunks of the
+    // sample beyond kSelKeys, which only very large corpora reach — is declined, and the call keeps the paths it had)
+    return r.k <= (uint32_t)kMaxFusedK || (r.k <= kFilteredBatchWideMaxK && r.large_k && r.narrow && r.final_counted && (!r.guess || r.bound == SampleBound::sample_select));
 }
 bool batched_sets_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus) {
     BatchedRoute r;
     return k >= 1 && k <= (uint32_t)kMaxFusedK && batched_supported(v, nq, k) && plan_batched(v, nq, k, cus, true, r) && batched_sets_route(r);
 }
-// The register-resident kernel has no flush variant (its instantiations are many: three operand splits, both row forms): a filtered
-// batch of whole workgroups takes what plan_batched chooses where that kernel does not apply.  Shared by launch_batched and
-// batched_sets_filter, so that what the latter reports is what the former launches.
-static void batched_sets_remap(BatchedRoute& r) {
+// What a batch with sets changes in plan_batched's route, two things.  Shared by launch_batched and batched_sets_filter, so that what the
+// latter reports is what the former launches.
+// First, the main filter: the register-resident kernel has no flush variant (its instantiations are many: three operand splits, both row
+// forms), so a filtered batch of whole workgroups takes what plan_batched chooses where that kernel does not apply.
+// Second, above kMaxFusedK results under a guessed bound (batched_sets_route: the plan's selection is k_sample_select): the rank is the
+// query's own (k_sets_guess_rank), and r.ks becomes the LARGEST rank a query may take — twice the whole sample's, for sets that the strided
+// sample meets up to twice as often as the corpus at large; never more than k_sample_select's LDS holds at this sample (kSelKeys / chunk,
+// which is at least the plan's own rank), and at most 2 k, which keeps the per-query bounds and the ranks inside the sample's
+// partial-list words (batched_layout: sparts).  The workspace does not move: batched_layout sizes by r.k alone.
+static void batched_sets_adapt(BatchedRoute& r) {
+    if (r.k > (uint32_t)kMaxFusedK && r.guess && r.bound == SampleBound::sample_select) {
+        const uint32_t held = kSelKeys / sample_select_chunk(r.sample_rows);
+        r.ks = std::max(r.ks, std::min(std::min(2 * r.ks, 2 * r.k), std::min(std::min(r.sample_rows, held), 1024u)));
+        r.select_lds = sample_select_lds_bytes(r.sample_rows, r.ks);
+    }
     if (r.filter != MainFilter::qreg) return;
     const uint32_t nqb64 = r.nq_pad / 64;
     if (r.bfrows) { r.filter = MainFilter::bf16rows; r.filter_grid = grid_multiple(2 * (uint32_t)r.cus, nqb64 / 4); }
@@ -2698,12 +2720,16 @@ static IndexView shape_view(int metric, uint32_t dim, uint64_t rows, int filter,
     v.bf16 = plane ? &plane_marker : nullptr;
     return v;
 }
+bool batched_sets_wide_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus) {
+    BatchedRoute r;
+    return k > (uint32_t)kMaxFusedK && k <= kFilteredBatchWideMaxK && batched_supported(v, nq, k) && plan_batched(v, nq, k, cus, true, r) && batched_sets_route(r);
+}
 bool batched_sets_filter(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool plane, int cus, uint32_t* nq_pad, int* code) {
     if (rows == 0 || rows > 0xFFFFFFFFull || dim == 0 || cus < 1) return false;
     const IndexView v = shape_view(metric, dim, rows, filter, plane);
     BatchedRoute r;
     if (k < 1 || k > (uint32_t)kMaxFusedK || !batched_supported(v, nq, k) || !plan_batched(v, nq, k, cus, true, r) || !batched_sets_route(r)) return false;
-    batched_sets_remap(r);
+    batched_sets_adapt(r);
     switch (r.filter) {                                     // the codes of include/qv.h (QV_BATCHED_FILTER_*)
         case MainFilter::mfma_f32:      *code = 0; break;
         case MainFilter::bf16x3:        *code = 1; break;
@@ -2751,6 +2777,20 @@ bool filtered_batch_rule(int metric, uint32_t dim, uint64_t rows, uint32_t nq, u
     return kFilteredBatchAutoMeasured && rows >= kFilteredBatchAutoMinRows;
 }
 
+// The same question for kMaxFusedK < k <= kFilteredBatchWideMaxK (the call that today is cut into runs of one set each, or into pieces of at
+// most 8 on the filtered wide shared pass).  A mode and an environment variable of its own (QV_FILTERED_BATCH_WIDE: 1 always, 2 never; read
+// once), so that neither moves what the rule above answers.  Measured: profiles/LAB_r28_filtered_batch_wide.md.  The automatic mode takes
+// nothing: a cell enters kFilteredBatchWideAuto only when that file has it faster than BOTH other arms by more than both arms' spread.
+constexpr bool kFilteredBatchWideAuto = false;
+static int filtered_batch_wide_mode(int mode) { static const int env_mode = env_int("QV_FILTERED_BATCH_WIDE", 0); return mode ? mode : env_mode; }
+bool filtered_batch_wide_rule(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse) {
+    mode = filtered_batch_wide_mode(mode);
+    if (mode != 1 && !kFilteredBatchWideAuto) return false;
+    if (mode == 2 || nq < kFilteredBatchMinQueries || n_not_sparse < kFilteredBatchMinQueries || k <= (uint32_t)kMaxFusedK || k > kFilteredBatchWideMaxK) return false;
+    if (rows == 0 || rows > 0xFFFFFFFFull || dim == 0) return false;
+    return batched_supported(shape_view(metric, dim, rows, filter), nq, k);
+}
+
 // The runtime metric as a compile-time constant M for a generic lambda, over the metrics this path's exact kernels (k_sample_select,
 // k_sample_bound*, k_rescore_select, k_cand_*, k_tp_exact) are instantiated for; the filters' own set: with_filter_metric (qv_filter.h)
 template <typename F> static inline hipError_t with_exact_metric(int metric, F&& f) {
@@ -2767,7 +2807,8 @@ template <typename F> static inline hipError_t with_exact_metric(int metric, F&&
 // selection (launch_sets_sample_mask), so that U_q is the ks-th smallest upper bound over sample & live & set_q: a bound of the k-th
 // distance over live & set_q, as any subset's is
 static hipError_t batched_sample_bound(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, const float* d_queries, void* d_ws, hipStream_t s,
-                                       const RowSetRef* d_sets = nullptr) {
+                                       const BatchedSets* sets = nullptr) {
+    const RowSetRef* d_sets = sets ? sets->d_sets : nullptr;
     const uint32_t nq = r.nq, nq_pad = r.nq_pad, srows = r.sample_rows;
     if (r.sample == SampleScores::exact_scan) {
         IndexView vs = v;
@@ -2787,8 +2828,11 @@ static hipError_t batched_sample_bound(const IndexView& v, const BatchedRoute& r
             hipLaunchKernelGGL(k_bf16x3_filter<M>, dim3(r.sample_grid), dim3(256), 0, s, v, Qbf, L.cq, L.mq, nq_pad, L.cand, L.cscore, L.cnt, L.sscore, srows, r.gstep);
         return hipSuccess;
     });
+    // (a filtered batch's guessed bound above kMaxFusedK results: a rank per query, 1 .. r.ks, in the last quarter of the partial-list words, behind the bounds)
+    uint32_t* ranks = sets && r.guess && r.k > (uint32_t)kMaxFusedK ? reinterpret_cast<uint32_t*>(L.sparts + (size_t)nq * r.k * 3) : nullptr;
     if (d_sets) {
-        const hipError_t e = launch_sets_sample_mask(v, d_sets, nq, L.sscore, srows, r.gstep, L.n_in, s);
+        hipError_t e = launch_sets_sample_mask(v, d_sets, nq, L.sscore, srows, r.gstep, L.n_in, s);
+        if (e == hipSuccess && ranks) e = launch_sets_guess_rank(v, d_sets, nq, r.k, L.n_in, sets->n_live, srows, r.ks, ranks, s);
         if (e != hipSuccess) return e;
     }
     const float gref = (float)filter_gamma(v.dim, 0) * 1.000001f;
@@ -2798,7 +2842,7 @@ static hipError_t batched_sample_bound(const IndexView& v, const BatchedRoute& r
             case SampleBound::scan_kth: case SampleBound::prep_group_min: break;   // (the bound is selected inside k_mfma_prep from the group minima)
             case SampleBound::sample_select: {
                 const hipError_t e = set_lds(k_sample_select<M>, r.select_lds); if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(k_sample_select<M>, dim3(nq), dim3(1024), r.select_lds, s, L.sscore, srows, r.ks, gref, L.ubuf);
+                hipLaunchKernelGGL(k_sample_select<M>, dim3(nq), dim3(1024), r.select_lds, s, L.sscore, srows, r.ks, gref, L.ubuf, ranks);
             } break;
             case SampleBound::histogram:
                 hipLaunchKernelGGL(k_sample_hist<0>, dim3(r.hist_grid, nq), dim3(kSelBlock), 0, s, L.sscore, srows, r.ks, sst, shist);
@@ -2939,12 +2983,12 @@ hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_
     if (!plan_batched(v, nq, k, cus, (reinterpret_cast<uintptr_t>(d_queries) & 15u) == 0, r)) return hipErrorNotSupported;
     const RowSetRef* d_sets = sets ? sets->d_sets : nullptr;
     if (d_sets && !batched_sets_route(r)) return hipErrorNotSupported;   // (a missing route is an error, never an unfiltered answer)
-    if (d_sets) batched_sets_remap(r);
+    if (d_sets) batched_sets_adapt(r);
     const BatchedLayout L = batched_layout(d_ws, v, p, r);
     if (L.end > L.total) return hipErrorInvalidValue;       // (cannot happen: see batched_layout)
     if (d_sets && trace_filtered())
         fprintf(stderr, "qv: filtered batch = k_sets_sample_mask + k_sets_sparse around the filter, nq %u k %u sample %u rows step %u rank %u floor %u ppm\n", nq, k, r.sample_rows, r.gstep, r.ks, sets->sparse_ppm);
-    hipError_t e = batched_sample_bound(v, r, L, d_queries, d_ws, s, d_sets);
+    hipError_t e = batched_sample_bound(v, r, L, d_queries, d_ws, s, sets);
     if (e != hipSuccess) return e;
     batched_prep(v, r, L, d_queries, s, d_sets);
     if (d_sets) {

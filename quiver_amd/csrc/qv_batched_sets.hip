@@ -69,6 +69,40 @@ k_sets_sparse(uint32_t nq, uint32_t nq_pad, const uint32_t* __restrict__ n_in, u
     }
 }
 
+// A guessed bound under a set (more than kMaxFusedK results over a large corpus: batched_guess), one thread per query, behind
+// k_sets_sample_mask.  The unfiltered guess takes rank k S / N + 4 sigma + 2 of the S sample rows: the k-th of N rows is expected there.
+// Under a set the sample that counts is the query's own — its n = n_in[q] live in-set sample rows, drawn from the m live rows of the set
+// (RowSetRef::live, counted by the host; a null set: the index's live rows) — and the k-th of m rows is expected at rank r = k n / m of
+// those n.  For a random set n / m ~ S / N and the rank is the unfiltered one; for a set that the strided sample meets more or less often
+// than the corpus at large (whole tiles, a clustered facet) it is not, and the whole sample's rank would then sit above the k-th row (more
+// candidates than slots) or below it (a failed check).  m unknown (0): the corpus's ratio S / N stands in for n / m.
+// ranks[q] = ceil(r + 4 sqrt(r) + 2), or 0 = NO guess — the set has at most k live rows, its sample cannot carry the rank (rank > n), or
+// the rank exceeds what the selection was sized for (rank_cap) — and the bound is then +inf: every row of the set is a candidate.
+// Whatever the rank, the bound is only a guess: the check behind the filter (k_cand_narrow: H <= U) decides whether the answer stands.
+__global__ void __launch_bounds__(256)
+k_sets_guess_rank(uint32_t nq, const uint32_t* __restrict__ n_in, const RowSetRef* __restrict__ sets, uint32_t k, uint32_t n_rows, uint32_t n_live,
+                  uint32_t sample_rows, uint32_t rank_cap, uint32_t* __restrict__ ranks) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const uint32_t n = n_in[q];
+    const RowSetRef rs = sets[q];
+    const uint32_t m = rs.bits == nullptr ? n_live : rs.live;
+    uint32_t rank = 0;
+    if (n != 0 && (m == 0 || m > k)) {
+        const double r = m != 0 ? (double)k * (double)n / (double)m : (double)k * (double)sample_rows / (double)n_rows;
+        const double want = __builtin_ceil(r + 4.0 * __builtin_sqrt(r) + 2.0);
+        if (want <= (double)n && want <= (double)rank_cap) rank = (uint32_t)want;
+    }
+    ranks[q] = rank;
+}
+
+hipError_t launch_sets_guess_rank(const IndexView& v, const RowSetRef* d_sets, uint32_t nq, uint32_t k, const uint32_t* d_n_in, uint32_t n_live,
+                                  uint32_t sample_rows, uint32_t rank_cap, uint32_t* d_ranks, hipStream_t s) {
+    if (!d_sets || nq == 0 || k == 0 || rank_cap == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sets_guess_rank, dim3((nq + 255) / 256), dim3(256), 0, s, nq, d_n_in, d_sets, k, v.n_rows, n_live, sample_rows, rank_cap, d_ranks);
+    return hipGetLastError();
+}
+
 hipError_t launch_sets_sample_mask(const IndexView& v, const RowSetRef* d_sets, uint32_t nq, float* d_bounds, uint32_t sample_rows, uint32_t gstep,
                                    uint32_t* d_n_in, hipStream_t s) {
     if (!d_sets || nq == 0 || sample_rows == 0 || gstep == 0) return hipErrorInvalidValue;

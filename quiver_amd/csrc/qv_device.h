@@ -371,7 +371,8 @@ hipError_t launch_merge_pairs(const float* d_dist, const uint32_t* d_rows, uint3
 
 // --- row sets (qv_rowset.hip): one candidate bitmap per query ----------------------------------
 // A query's set as the kernels see it: `words` 64-row words at `bits` (rows beyond them are unselected); bits == null: every row.
-struct RowSetRef { const uint64_t* bits; uint32_t words; uint32_t pad_; };
+// live: the set's live rows as the host counted them, filled in only for the table of a filtered batch above kMaxFusedK results (k_sets_guess_rank); 0 = not counted
+struct RowSetRef { const uint64_t* bits; uint32_t words; uint32_t live; };
 // Exact multi-query scan, k <= kMaxFusedK, query q restricted to alive & h_sets[q] (a HOST array: the table travels to the device as
 // kernel arguments, nothing is uploaded).  d_ws: rowset_workspace_bytes.  Writes [nq][k] lists padded with 0xFFFFFFFF / +inf.
 size_t rowset_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t dim4, WsLog* log = nullptr);
@@ -430,11 +431,15 @@ hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_
 // taken over the set, the filter's flush drops rows outside it, and a query whose set holds fewer than sparse_ppm millionths of the sample's
 // rows is handed back without candidates (0: never).  With sets, *d_overflow_out -> [2][nq]: the redo flags, then 1 = handed back as sparse
 // (those are flagged in both).  Same workspace (batched_workspace_bytes).
-struct BatchedSets { const RowSetRef* d_sets; uint32_t sparse_ppm; };
+// Above kMaxFusedK results (up to kFilteredBatchWideMaxK; batched_sets_wide_supported) the same three steps stand in front of the large-k funnel,
+// whose lists keep batched_cand_cap(k) slots; a guessed bound takes its rank per query, from the query's own in-set sample (k_sets_guess_rank:
+// n_live = the index's live rows, the population of a null set; RowSetRef::live that of the others).
+struct BatchedSets { const RowSetRef* d_sets; uint32_t sparse_ppm; uint32_t n_live = 0; };
 // whether launch_batched takes sets for this shape: batched_supported, k <= kMaxFusedK, and a route whose sample scores come from a filter
 // kernel with every row's bound selected outside k_mfma_prep (the exact-scan sample of QV_MFMA_SAMPLE_GEMM is declined)
 bool batched_sets_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus);
 // what plan_batched chose for the sample: its rows, every gstep-th 128-row group of the corpus, and the rank the bound is taken at
+bool batched_sets_wide_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus);   // ... for kMaxFusedK < k <= kFilteredBatchWideMaxK
 bool batched_sample_plan(const IndexView& v, uint32_t nq, uint32_t k, int cus, uint32_t* sample_rows, uint32_t* gstep, uint32_t* rank);
 // The dispatch's rule for a filtered call or shared pass (qv_batched_applies_filtered; mode: QV_FILTERED_BATCH_*, 0 = QV_FILTERED_BATCH of the
 // environment, else automatic): n_not_sparse = the piece's queries whose set the HOST does not know to be below the sparse floor.
@@ -443,6 +448,9 @@ bool filtered_batch_rule(int metric, uint32_t dim, uint64_t rows, uint32_t nq, u
 // applies to a batch with sets.  plane: the index keeps the bfloat16 copy the batched filter reads.  *code: QV_BATCHED_FILTER_* of
 // include/qv.h; false where batched_sets_supported is.
 bool batched_sets_filter(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool plane, int cus, uint32_t* nq_pad, int* code);
+// The same rule for kMaxFusedK < k <= kFilteredBatchWideMaxK (qv_batched_applies_filtered_wide; mode: 0 = QV_FILTERED_BATCH_WIDE of the environment)
+bool filtered_batch_wide_rule(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse);
+constexpr uint32_t kFilteredBatchWideMaxK = 1024;
 constexpr uint32_t kFilteredBatchMinQueries = 9;
 constexpr uint32_t kFilteredBatchDefaultPpm = 10000;      // the sparse floor where the index sets none: a hundredth of the rows
 constexpr uint32_t kFilteredBatchAutoMinRows = 300000;    // automatic mode takes nothing below the smallest measured shape
@@ -450,6 +458,8 @@ inline uint32_t filtered_batch_ppm(uint32_t ppm) { return ppm == 0xFFFFFFFFu ? k
 // qv_batched_sets.hip — the two launches a filtered batch adds around the sample's selection and behind k_mfma_prep
 hipError_t launch_sets_sample_mask(const IndexView& v, const RowSetRef* d_sets, uint32_t nq, float* d_bounds, uint32_t sample_rows, uint32_t gstep,
                                    uint32_t* d_n_in, hipStream_t s);
+hipError_t launch_sets_guess_rank(const IndexView& v, const RowSetRef* d_sets, uint32_t nq, uint32_t k, const uint32_t* d_n_in, uint32_t n_live,
+                                  uint32_t sample_rows, uint32_t rank_cap, uint32_t* d_ranks, hipStream_t s);
 hipError_t launch_sets_sparse(uint32_t nq, uint32_t nq_pad, const uint32_t* d_n_in, uint32_t sample_rows, uint32_t sparse_ppm, float* d_cq, float* d_mq,
                               uint32_t* d_ovf, uint32_t* d_sparse, hipStream_t s);
 

@@ -553,6 +553,13 @@ class DeviceIndex:
         ppm = 0xFFFFFFFF if sparse_ppm is None else int(sparse_ppm)
         check(lib().qv_index_set_filtered_batch(self._h, self.FILTERED_BATCH.get(mode, mode), ppm))
 
+    def set_filtered_batch_wide(self, mode):
+        """the same question for 9 or more FILTERED queries that want 65 to 1024 results each (search_rowsets, search_where): "always" = the
+        batched path with a set per query and the large-k funnel behind it, "never" = runs of one set and the filtered wide shared
+        passes, "auto" (the default) = nothing until cells are measured as won.  The sparse floor is set_filtered_batch's; the path
+        counts into filtered_batch_stats (qv_index_set_filtered_batch_wide)"""
+        check(lib().qv_index_set_filtered_batch_wide(self._h, self.FILTERED_BATCH.get(mode, mode)))
+
     def filtered_batch_stats(self) -> dict:
         """queries that took the filtered batched path, queries it handed back (overflow, no bound, a failed guess), queries it handed back
         as sparse, batches (qv_index_filtered_batch_stats)"""
