@@ -569,7 +569,7 @@ int qv_index_get_rows(qv_index* idx, const uint32_t* rows, uint32_t n, float* ou
 // stream's ticket words (and with them the index's bound-scan counters); cand_tiles: kBoundNoFilter, or a filtered call's candidate tiles.
 static qv::FlatPlan flat_plan(const qv_index* idx, uint32_t nq, uint32_t kk, bool tickets, uint32_t cand_tiles) {
     const qv::IndexView v = idx->view();
-    return qv::plan_flat(v, qv::plan_scan(v.n_tiles, idx->cus), nq, kk, tickets, tickets, cand_tiles);
+    return qv::plan_flat(v, qv::plan_scan(v.n_tiles, idx->cus), nq, kk, tickets, tickets, cand_tiles, idx->bound);
 }
 
 // qv_index_profile: an event pair around one launch — both events or neither (none while profiling is off, or when an event cannot be
@@ -593,38 +593,19 @@ static void profile_end(qv_index* idx, const ProfilePair& p, bool launched, bool
     (void)hipEventDestroy(p.ev0); (void)hipEventDestroy(p.ev1);
 }
 
-// Whether a search of list length kk takes the bound scan's wide form (65 <= kk <= 1024), for the launch (enqueue_search) and for the
-// workspace (search_ws_bytes): 0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.  One query whose call carries the stream's ticket
-// words, kk == k_stride.  Unfiltered (cand_tiles == kBoundNoFilter): fewer results than live rows (a k above the live rows keeps its path);
-// the rest is qv::bound_wide_route's answer under the index's two knobs.  Filtered: cand_tiles and candidates are the call's candidate tiles
-// and its live candidates as the host counts them, and the answer is qv::bound_wide_route_filtered's under the filtered form's own knob and
-// the single-query filtered plane knob — fewer results than candidates is that rule's own condition.
-static int wide_route(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles, uint64_t candidates) {
-    if (nq != 1 || kk != k_stride || !tickets) return 0;
-    const int metric = idx->l2_planes() ? QV_RULE_L2_PLANES : idx->metric;
-    if (cand_tiles != qv::kBoundNoFilter)
-        return qv::bound_wide_route_filtered(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide_filtered, idx->bound.plane[qv::bound_one_filtered], idx->d_bf16 != nullptr,
-                                             idx->d_plane8 != nullptr, cand_tiles, candidates);
-    if (kk >= idx->n_live) return 0;
-    return qv::bound_wide_route(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide, idx->bound.plane[qv::bound_one], idx->d_bf16 != nullptr, idx->d_plane8 != nullptr);
-}
-
-// The same question for the wide form of the SHARED pass: an unfiltered call of 2 - 8 queries at 65 <= kk <= 1024 whose call carries the stream's
-// ticket words, kk == k_stride, fewer results than live rows; the rest is qv::bound_wide_route_mq's answer under the form's own knob and the
-// shared pass's plane knob.  0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.
-// Filtered (cand_tiles != kBoundNoFilter: 2 - 8 queries over ONE candidate bitmap, or a piece of rowsets_plan's with a set per query): cand_tiles
-// is the piece's candidate tiles and candidates the SMALLEST live candidate count among its queries, and the answer is
-// qv::bound_wide_route_filtered_mq's under that form's own knob and the filtered shared pass's plane knob.
-static int wide_route_mq(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles = qv::kBoundNoFilter, uint64_t candidates = 0) {
-    if (nq < 2 || kk != k_stride || !tickets || kk >= idx->n_live) return 0;
-    // H_j is the kk-th of the grid x 256 keys a query's waves publish: a grid too small for that (one or two compute units at a large kk)
-    // keeps its path.  The rule cannot see the grid; the launcher checks the same.
-    if ((uint64_t)qv::plan_scan((idx->n_rows + 63) / 64, idx->cus).grid * 256 <= kk) return 0;
-    const int metric = idx->l2_planes() ? QV_RULE_L2_PLANES : idx->metric;
-    if (cand_tiles != qv::kBoundNoFilter)
-        return qv::bound_wide_route_filtered_mq(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide_filtered_mq, idx->bound.plane[qv::bound_mq_filtered], idx->d_bf16 != nullptr,
-                                                idx->d_plane8 != nullptr, cand_tiles, candidates);
-    return qv::bound_wide_route_mq(metric, idx->dim, idx->n_rows, nq, kk, idx->bound_wide_mq, idx->bound.plane[qv::bound_mq], idx->d_bf16 != nullptr, idx->d_plane8 != nullptr);
+// Whether a search of nq queries of list length kk takes a wide form of the bound scan (65 <= kk <= 1024), and on which plane it starts, for
+// the launch (enqueue_search, rowsets_plan) and for the workspace (search_ws_bytes): qv::bound_wide_decide's answer under the index's knobs,
+// behind what only the host knows.  The call carries the stream's ticket words and kk == k_stride.  cand_tiles: kBoundNoFilter, or the
+// candidate tiles of a filtered call or piece (one bitmap for all its queries, or a set per query); candidates: then the SMALLEST live
+// candidate count among its queries, as the host counts them (fewer results than candidates is the decision's own condition).  Fewer results
+// than live rows (a k above the live rows keeps its path) — but for one filtered query, whose candidates say it.  A shared pass's H_j is the
+// kk-th of the grid x 256 keys a query's waves publish: a grid too small for that (one or two compute units at a large kk) keeps its path;
+// the decision cannot see the grid, the launcher checks the same.
+static qv::BoundStages wide_stages(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles = qv::kBoundNoFilter, uint64_t candidates = 0) {
+    if (kk != k_stride || !tickets) return qv::BoundStages::none;
+    if (kk >= idx->n_live && (nq > 1 || cand_tiles == qv::kBoundNoFilter)) return qv::BoundStages::none;
+    if (nq > 1 && (uint64_t)qv::plan_scan((idx->n_rows + 63) / 64, idx->cus).grid * 256 <= kk) return qv::BoundStages::none;
+    return qv::bound_wide_decide(qv::bound_ask(idx->view(), nq, kk, cand_tiles), candidates, idx->bound);
 }
 
 // what a call may hand enqueue_search beside its queries and outputs
@@ -656,24 +637,19 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "%s scan launch failed: %s", fp.route == qv::FlatRoute::small ? "small" : "flat", hipGetErrorString(e));
         return QV_OK;
     }
-    // 65 <= k <= 1024, one query, unfiltered or over its candidate bitmap, where the wide form's rule takes it: the bound scan on the reduced
-    // copies, its re-score and selection, and the gated key-per-row redo behind them — all enqueued by the one launcher
-    if (const int wide = wide_route(idx, nq, kk, k_stride, x.d_tickets != nullptr, x.d_candidates ? x.candidate_tiles : qv::kBoundNoFilter, x.candidates)) {
-        const ProfilePair pp = profile_begin(idx, true, s);
-        hipError_t e = qv::launch_bound_scan_wide(v, plan, d_queries, kk, ws, x.d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, d_rows_out, d_dist_out, s, wide == 2, x.d_candidates != nullptr);
-        profile_end(idx, pp, e == hipSuccess, true, s);
-        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "wide bound scan launch failed: %s", hipGetErrorString(e));
-        return QV_OK;
-    }
-    // ... and 2 - 8 queries of that length where the wide shared pass's rule takes them: the reduced copy read once for the pass.  Over a
-    // candidate bitmap (one mask for all the queries) it is the filtered form with a table of null sets over v.alive, as at k <= 64
-    if (const int wide = wide_route_mq(idx, nq, kk, k_stride, x.d_tickets != nullptr, x.d_candidates ? x.candidate_tiles : qv::kBoundNoFilter, x.candidates)) {
+    // 65 <= k <= 1024 where the wide forms' decision takes the call: the bound scan on the reduced copies, its re-score and selection, and the
+    // gated key-per-row redo behind them — all enqueued by the one launcher.  One query, unfiltered or over its candidate bitmap; or 2 - 8
+    // queries, the reduced copy read once for the pass — over a candidate bitmap (one mask for all the queries) with a table of null sets
+    // over v.alive, as at k <= 64
+    if (const qv::BoundStages wide = wide_stages(idx, nq, kk, k_stride, x.d_tickets != nullptr, x.d_candidates ? x.candidate_tiles : qv::kBoundNoFilter, x.candidates); wide != qv::BoundStages::none) {
+        const bool plane8_first = wide == qv::BoundStages::plane8_first;
         const ProfilePair pp = profile_begin(idx, true, s);
         const qv::RowSetRef every[8] = {};
-        hipError_t e = qv::launch_bound_scan_wide_mq(v, plan, d_queries, nq, kk, ws, x.d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, d_rows_out, d_dist_out, s, wide == 2,
-                                                     x.d_candidates ? every : nullptr);
+        uint32_t* d_ctrl = x.d_tickets + qv::kBoundCtrlWord;
+        hipError_t e = nq == 1 ? qv::launch_bound_scan_wide(v, plan, d_queries, kk, ws, d_ctrl, idx->d_bound_stats, d_rows_out, d_dist_out, s, plane8_first, x.d_candidates != nullptr)
+                               : qv::launch_bound_scan_wide_mq(v, plan, d_queries, nq, kk, ws, d_ctrl, idx->d_bound_stats, d_rows_out, d_dist_out, s, plane8_first, x.d_candidates ? every : nullptr);
         profile_end(idx, pp, e == hipSuccess, true, s);
-        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "wide shared bound pass launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(QV_ERR_DEVICE, "%s launch failed: %s", nq == 1 ? "wide bound scan" : "wide shared bound pass", hipGetErrorString(e));
         return QV_OK;
     }
     // 64 < k <= 8192 (the negative-example branches fetch max(2k, 30), hybrid_index.go:516-522; BatchSearch takes any k,
@@ -700,7 +676,7 @@ static int enqueue_search(qv_index* idx, const float* d_queries, uint32_t nq, ui
     return QV_OK;
 }
 
-// tickets / cand_tiles / candidates: as the call will be enqueued (flat_plan, wide_route) — a call whose route is a bound scan is sized for it, no other call is
+// tickets / cand_tiles / candidates: as the call will be enqueued (flat_plan, wide_stages) — a call whose route is a bound scan is sized for it, no other call is
 static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uint32_t k_stride, bool tickets, uint32_t cand_tiles = qv::kBoundNoFilter, uint64_t candidates = 0) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     const qv::ScanPlan plan = qv::plan_scan(n_tiles, idx->cus);
@@ -710,8 +686,8 @@ static size_t search_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk, uin
                               : fp.route == qv::FlatRoute::bound || fp.route == qv::FlatRoute::bound8_first ? qv::FlatWs::call_bound : qv::FlatWs::call;
         return qv::flat_layout(nullptr, what, plan, nq, kk, n_tiles, idx->dim).total;
     }
-    if (wide_route(idx, nq, kk, k_stride, tickets, cand_tiles, candidates)) return qv::bound_scan_wide_workspace_bytes(plan, kk, n_tiles, idx->dim);
-    if (wide_route_mq(idx, nq, kk, k_stride, tickets, cand_tiles, candidates)) return qv::bound_scan_wide_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim);
+    if (wide_stages(idx, nq, kk, k_stride, tickets, cand_tiles, candidates) != qv::BoundStages::none)
+        return nq == 1 ? qv::bound_scan_wide_workspace_bytes(plan, kk, n_tiles, idx->dim) : qv::bound_scan_wide_mq_workspace_bytes(plan, nq, kk, n_tiles, idx->dim);
     if (kk > (uint32_t)qv::kMaxFusedK && kk <= (uint32_t)qv::kMaxWideK && nq == 1) return qv::flat_wide_workspace_bytes(plan, nq, kk);
     if (kk <= (uint32_t)qv::kMaxSelectK) return qv::flat_select_workspace_bytes(n_tiles, nq, kk, idx->dim4);
     return qv::full_sort_workspace_bytes(n_tiles);
@@ -1010,7 +986,7 @@ int qv_index_search_negative(qv_index* idx, const float* query, const float* neg
     int rc;
     // (the context's ticket words only where the wide bound scan takes the fetch — max(2k, 30) results, so every k >= 33: without them
     //  every path is the one this call has always taken)
-    const bool wide = wide_route(idx, 1, kk, kk, true, qv::kBoundNoFilter, 0) != 0;
+    const bool wide = wide_stages(idx, 1, kk, kk, true) != qv::BoundStages::none;
     if ((rc = hc.open()) || (rc = hc.reserve(2, 1, kk, 2)) || (rc = hc.workspace(search_ws_bytes(idx, 1, kk, kk, wide)))) return rc;
     SearchExtras x;
     if (wide && (rc = hc.tickets(&x.d_tickets))) return rc;
@@ -1054,7 +1030,7 @@ static int masked_pass(qv_index* idx, const float* queries, uint32_t nq, uint32_
     if ((rc = hc.reserve(nq, nq, kk))) return rc;
     // the bound scan under the mask when the filtered rule takes it — up to 64 results plan_flat's, from 65 the wide form's —: then, and only
     // then, the call carries the context's ticket words (without them every path is the one a masked search has always taken)
-    const bool bound = kk <= (uint32_t)qv::kMaxFusedK ? flat_plan(idx, nq, kk, true, cand_tiles).bound() : wide_route(idx, nq, kk, kk, true, cand_tiles, matching) != 0 || wide_route_mq(idx, nq, kk, kk, true, cand_tiles, matching) != 0;
+    const bool bound = kk <= (uint32_t)qv::kMaxFusedK ? flat_plan(idx, nq, kk, true, cand_tiles).bound() : wide_stages(idx, nq, kk, kk, true, cand_tiles, matching) != qv::BoundStages::none;
     if ((rc = hc.workspace(search_ws_bytes(idx, nq, kk, kk, bound, cand_tiles, matching)))) return rc;
     SearchExtras x;
     x.d_candidates = static_cast<const uint64_t*>(c->d_mask.p); x.candidate_tiles = cand_tiles; x.candidates = matching;
@@ -1369,8 +1345,8 @@ static qv::RowSetRef rs_ref(const qv_index* idx, const RsFilter& f) {
 // filtered_batch_takes is the rule) — decided here too, and only for the host forms, whose caller reads the redo flags.
 // cand: a run's live candidates (rowset_live), counted for k > kMaxFusedK only — the filtered wide form's rule asks for it; 0 otherwise.
 // wide_mq: a piece of 2 - 8 queries at 65 <= k <= 1024, a set per query, that the filtered wide shared pass takes (launch_bound_scan_wide_mq with
-// the sets; 1 the bfloat16 copy first, 2 the 8-bit plane first) — decided here too.  cand is then the smallest live count among its queries.
-struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; bool bound8; bool batched = false; uint64_t cand = 0; int wide_mq = 0; };
+// the sets), and the plane it starts on — decided here too.  cand is then the smallest live count among its queries.
+struct RowsetPiece { uint32_t q0, nq, kk; bool multi; bool bound; uint32_t cand_tiles; bool bound8; bool batched = false; uint64_t cand = 0; qv::BoundStages wide_mq = qv::BoundStages::none; };
 static uint32_t rowsets_cand_tiles(const qv_index* idx, const RsFilter* fl, uint32_t nq, bool transient_every_tile = false) {
     const uint32_t n_tiles = (idx->n_rows + 63) / 64;
     uint64_t sum = 0;
@@ -1412,7 +1388,7 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const R
     if (k <= (uint32_t)qv::kMaxFusedK && nq >= 2) {
         const uint32_t ct = rowsets_cand_tiles(idx, fl, nq);
         const qv::IndexView v = idx->view();
-        const qv::BoundKnobs knobs = qv::bound_knobs(v);
+        const qv::BoundKnobs& knobs = idx->bound;
         const bool bound8 = nq <= 8 && qv::bound_scan_decide(qv::bound_ask(v, nq, k, rowsets_cand_tiles(idx, fl, nq, true)), knobs) == qv::BoundStages::plane8_first;
         const bool bound = bound8 || (nq <= 8 && qv::bound_scan_decide(qv::bound_ask(v, nq, k, ct), knobs) != qv::BoundStages::none);   // (9 or more are not cut into bound passes)
         pieces.push_back(RowsetPiece{0, nq, k, true, bound, ct, bound8});
@@ -1424,7 +1400,7 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const R
     // share a piece.  A run of one, a query of k candidates or fewer and a piece the rule declines keep the loop below, as before: with the
     // rule at "never" — or automatic, which takes nothing yet — wide_at stays empty and this function answers as it always has.
     std::vector<RowsetPiece> wide_at(0);
-    if (k > (uint32_t)qv::kMaxFusedK && nq >= 2 && wide_route_mq(idx, 2, k, k, true, n_tiles, ~0ull)) {   // (could the form take anything of this index at all?)
+    if (k > (uint32_t)qv::kMaxFusedK && nq >= 2 && wide_stages(idx, 2, k, k, true, n_tiles, ~0ull) != qv::BoundStages::none) {   // (could the form take anything of this index at all?)
         std::vector<uint64_t> live(nq);
         for (uint32_t q = 0; q < nq; q++) live[q] = q > 0 && fl[q].set == fl[q - 1].set ? live[q - 1] : rowset_live(idx, fl[q].set);
         for (uint32_t q = 0; q < nq;) {
@@ -1435,7 +1411,7 @@ static size_t rowsets_plan(const qv_index* idx, uint32_t nq, uint32_t k, const R
                 const uint32_t m = len / parts + (i < len % parts ? 1u : 0u);
                 const uint32_t ct = rowsets_cand_tiles(idx, fl + at, m);
                 const uint64_t least = *std::min_element(live.begin() + at, live.begin() + at + m);
-                if (const int wide = m >= 2 ? wide_route_mq(idx, m, k, k, true, ct, least) : 0)
+                if (const qv::BoundStages wide = m >= 2 ? wide_stages(idx, m, k, k, true, ct, least) : qv::BoundStages::none; wide != qv::BoundStages::none)
                     wide_at.push_back(RowsetPiece{at, m, k, false, false, ct, false, false, least, wide});
                 at += m;
             }
@@ -1562,12 +1538,12 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "row-set scan launch failed: %s", hipGetErrorString(e));
             continue;
         }
-        if (p.wide_mq) {                                              // 65 <= k <= 1024, a set per query: the reduced copy read once for the piece
+        if (p.wide_mq != qv::BoundStages::none) {                                              // 65 <= k <= 1024, a set per query: the reduced copy read once for the piece
             if (!d_tickets) return fail(QV_ERR_DEVICE, "filtered wide shared pass without the stream's control words");
             qv::RowSetRef refs[8];
             for (uint32_t i = 0; i < p.nq; i++) refs[i] = rs_ref(idx, fl[p.q0 + i]);
             const ProfilePair pp = profile_begin(idx, true, s);
-            hipError_t e = qv::launch_bound_scan_wide_mq(v, plan, q, p.nq, k, ws, d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, r_out, d_out, s, p.wide_mq == 2, refs);
+            hipError_t e = qv::launch_bound_scan_wide_mq(v, plan, q, p.nq, k, ws, d_tickets + qv::kBoundCtrlWord, idx->d_bound_stats, r_out, d_out, s, p.wide_mq == qv::BoundStages::plane8_first, refs);
             profile_end(idx, pp, e == hipSuccess, true, s);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "filtered wide shared bound pass launch failed: %s", hipGetErrorString(e));
             continue;
@@ -2178,19 +2154,17 @@ int qv_index_bound_scan6_stats(qv_index* idx, uint64_t out[4]) {
     return QV_OK;
 }
 
-int qv_index_set_bound_scan_wide(qv_index* idx, int mode) {
+// the four wide knobs, one per form of the bound scan (qv::BoundForm)
+static int set_bound_wide(qv_index* idx, qv::BoundForm form, int mode) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
     if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    idx->bound_wide = mode;
+    idx->bound.wide[form] = mode;
     return QV_OK;
 }
-
-int qv_index_set_bound_scan_wide_filtered(qv_index* idx, int mode) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    idx->bound_wide_filtered = mode;
-    return QV_OK;
-}
+int qv_index_set_bound_scan_wide(qv_index* idx, int mode) { return set_bound_wide(idx, qv::bound_one, mode); }
+int qv_index_set_bound_scan_wide_filtered(qv_index* idx, int mode) { return set_bound_wide(idx, qv::bound_one_filtered, mode); }
+int qv_index_set_bound_scan_wide_mq(qv_index* idx, int mode) { return set_bound_wide(idx, qv::bound_mq, mode); }
+int qv_index_set_bound_scan_wide_filtered_mq(qv_index* idx, int mode) { return set_bound_wide(idx, qv::bound_mq_filtered, mode); }
 
 int qv_index_bound_scan_wide_stats(qv_index* idx, uint64_t out[4]) {
     if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
@@ -2199,20 +2173,6 @@ int qv_index_bound_scan_wide_stats(qv_index* idx, uint64_t out[4]) {
     uint32_t h[3] = {0, 0, 0};
     HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kBoundWideStatsWord, sizeof(h), hipMemcpyDeviceToHost));
     out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = idx->d_bf16 != nullptr ? 1 : 0;
-    return QV_OK;
-}
-
-int qv_index_set_bound_scan_wide_mq(qv_index* idx, int mode) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    idx->bound_wide_mq = mode;
-    return QV_OK;
-}
-
-int qv_index_set_bound_scan_wide_filtered_mq(qv_index* idx, int mode) {
-    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (mode < 0 || mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    idx->bound_wide_filtered_mq = mode;
     return QV_OK;
 }
 
@@ -2226,32 +2186,40 @@ int qv_index_bound_scan_wide_mq_stats(qv_index* idx, uint64_t out[4]) {
     return QV_OK;
 }
 
-int qv_scan_bound_wide_route_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mq_mode, int plane_mode_mq, int has_plane, int has_plane8) {
-    if (wide_mq_mode < 0 || wide_mq_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mq_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mq_mode);
-    if (plane_mode_mq < 0 || plane_mode_mq > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_mq);
-    return qv::bound_wide_route_mq(metric, dim, rows, nq, k, wide_mq_mode, plane_mode_mq, has_plane != 0, has_plane8 != 0);
-}
-
-int qv_scan_bound_wide_route_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered_mq, int has_plane, int has_plane8,
-                                         uint32_t candidate_tiles, uint64_t min_candidates) {
-    if (wide_mode < 0 || wide_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mode);
-    if (plane_mode_filtered_mq < 0 || plane_mode_filtered_mq > QV_BOUND_PLANE_BF16)
-        return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered_mq must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered_mq);
-    return qv::bound_wide_route_filtered_mq(metric, dim, rows, nq, k, wide_mode, plane_mode_filtered_mq, has_plane != 0, has_plane8 != 0, std::min(candidate_tiles, qv::kBoundNoFilter - 1), min_candidates);   // (a count, never the "no filter" mark)
+static uint32_t as_count(uint32_t candidate_tiles) { return std::min(candidate_tiles, qv::kBoundNoFilter - 1); }
+// The four wide rule exports: views of the one decision (qv::bound_wide_decide) for a call given without an index.  form: the form the
+// export speaks for (it says 0 to any other).  0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.  A filtered rule takes every
+// candidate-tile count as a count, never as the "no filter" mark.
+static int bound_wide_export(qv::BoundForm form, int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, const char* wide_name, int wide_mode, const char* plane_name, int plane_mode,
+                             int has_plane, int has_plane8, uint32_t candidate_tiles, uint64_t min_candidates) {
+    if (wide_mode < 0 || wide_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "%s must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_name, wide_mode);
+    if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "%s must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_name, plane_mode);
+    const qv::BoundAsk ask = {metric, dim, rows, nq, k, candidate_tiles, has_plane != 0, has_plane8 != 0};
+    if (form != qv::bound_form(ask)) return 0;
+    qv::BoundKnobs knobs = {};
+    knobs.wide[form] = wide_mode; knobs.plane[form] = plane_mode;
+    const qv::BoundStages got = qv::bound_wide_decide(ask, min_candidates, knobs);
+    return got == qv::BoundStages::plane8_first ? 2 : got == qv::BoundStages::bf16 ? 1 : 0;
 }
 
 int qv_scan_bound_wide_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, int has_plane, int has_plane8) {
-    if (wide_mode < 0 || wide_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mode);
-    if (plane_mode < 0 || plane_mode > QV_BOUND_PLANE_BF16) return fail(QV_ERR_INVALID_ARG, "plane_mode must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode);
-    return qv::bound_wide_route(metric, dim, rows, nq, k, wide_mode, plane_mode, has_plane != 0, has_plane8 != 0);
+    return bound_wide_export(qv::bound_one, metric, dim, rows, nq, k, "wide_mode", wide_mode, "plane_mode", plane_mode, has_plane, has_plane8, qv::kBoundNoFilter, 0);
 }
 
 int qv_scan_bound_wide_route_filtered(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered, int has_plane, int has_plane8,
                                       uint32_t candidate_tiles, uint64_t candidates) {
-    if (wide_mode < 0 || wide_mode > QV_BOUND_SCAN_NEVER) return fail(QV_ERR_INVALID_ARG, "wide_mode must be 0 (automatic), 1 (always) or 2 (never); got %d", wide_mode);
-    if (plane_mode_filtered < 0 || plane_mode_filtered > QV_BOUND_PLANE_BF16)
-        return fail(QV_ERR_INVALID_ARG, "plane_mode_filtered must be 0 (automatic), 1 (8-bit first) or 2 (bfloat16 only); got %d", plane_mode_filtered);
-    return qv::bound_wide_route_filtered(metric, dim, rows, nq, k, wide_mode, plane_mode_filtered, has_plane != 0, has_plane8 != 0, std::min(candidate_tiles, qv::kBoundNoFilter - 1), candidates);   // (a count, never the "no filter" mark)
+    return bound_wide_export(qv::bound_one_filtered, metric, dim, rows, nq, k, "wide_mode", wide_mode, "plane_mode_filtered", plane_mode_filtered, has_plane, has_plane8,
+                             as_count(candidate_tiles), candidates);
+}
+
+int qv_scan_bound_wide_route_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mq_mode, int plane_mode_mq, int has_plane, int has_plane8) {
+    return bound_wide_export(qv::bound_mq, metric, dim, rows, nq, k, "wide_mq_mode", wide_mq_mode, "plane_mode_mq", plane_mode_mq, has_plane, has_plane8, qv::kBoundNoFilter, 0);
+}
+
+int qv_scan_bound_wide_route_filtered_mq(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered_mq, int has_plane, int has_plane8,
+                                         uint32_t candidate_tiles, uint64_t min_candidates) {
+    return bound_wide_export(qv::bound_mq_filtered, metric, dim, rows, nq, k, "wide_mode", wide_mode, "plane_mode_filtered_mq", plane_mode_filtered_mq, has_plane, has_plane8,
+                             as_count(candidate_tiles), min_candidates);
 }
 
 // The six rule exports: views of the one decision (qv::bound_scan_decide) for a call given without an index.  form: the form the export
@@ -2268,7 +2236,6 @@ static int bound_export(int form, qv::BoundStages want, int metric, uint32_t dim
     const qv::BoundStages got = qv::bound_scan_decide(ask, knobs);
     return (want == qv::BoundStages::plane8_first ? qv::bound_stages_8bit(got) : got != qv::BoundStages::none) ? 1 : 0;
 }
-static uint32_t as_count(uint32_t candidate_tiles) { return std::min(candidate_tiles, qv::kBoundNoFilter - 1); }
 
 int qv_scan_bound8_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int mode, int plane_mode, int has_plane8) {
     return bound_export(qv::bound_one, qv::BoundStages::plane8_first, metric, dim, rows, nq, k, mode, "plane_mode", plane_mode, 1, has_plane8, qv::kBoundNoFilter);

@@ -105,11 +105,7 @@ struct qv_index {
     bool rowmaj8_lost = false;                 // it could not be allocated: the index carries on without it
     uint16_t* d_bf16 = nullptr;                // the bfloat16 copy (QV_FLAG_BF16_ROWS, and by default on cosine / dot indexes): refreshed by every call that writes rows
     bool plane_lost = false;                   // the default copy could not be allocated: the index carries on without it
-    qv::BoundKnobs bound = {};                 // qv_index_set_bound_scan, and by qv::BoundForm the four qv_index_set_bound_plane*
-    int bound_wide = 0;                        // qv_index_set_bound_scan_wide: QV_BOUND_SCAN_* for the wide form (65 <= k <= 1024), a knob of its own
-    int bound_wide_filtered = 0;               // qv_index_set_bound_scan_wide_filtered: the same for ONE filtered query of that length, a knob of its own
-    int bound_wide_mq = 0;                     // qv_index_set_bound_scan_wide_mq: the same for an unfiltered shared pass of 2 - 8 queries of that length, a knob of its own
-    int bound_wide_filtered_mq = 0;            // qv_index_set_bound_scan_wide_filtered_mq: the same for a FILTERED shared pass of 2 - 8 queries of that length, a knob of its own
+    qv::BoundKnobs bound = {};                 // qv_index_set_bound_scan, and by qv::BoundForm the four qv_index_set_bound_plane* and the four qv_index_set_bound_scan_wide*
     int8_t* d_plane8 = nullptr;                // the int8 copy and its row state (scale, residual): kept with the default bfloat16 copy, refreshed with it
     float* d_rscale8 = nullptr;
     float* d_rres8 = nullptr;
@@ -146,13 +142,13 @@ struct qv_index {
     qv::IndexView view() const {
         qv::IndexView v;
         v.tiles = d_tiles; v.rnorm = d_rnorm; v.alive = d_alive; v.rres = d_rres; v.rowmaj = d_rowmaj;
-        v.bf16 = (flags & QV_FLAG_BF16_ROWS) ? d_bf16 : nullptr; v.plane = d_bf16; v.bound_scan = bound.scan;
-        v.plane8 = d_plane8; v.rscale8 = d_rscale8; v.rres8 = d_rres8; v.bound_plane = bound.plane[qv::bound_one]; v.bound_plane_filtered = bound.plane[qv::bound_one_filtered]; v.bound_plane_mq = bound.plane[qv::bound_mq]; v.bound_plane_filtered_mq = bound.plane[qv::bound_mq_filtered];
+        v.bf16 = (flags & QV_FLAG_BF16_ROWS) ? d_bf16 : nullptr; v.plane = d_bf16;
+        v.plane8 = d_plane8; v.rscale8 = d_rscale8; v.rres8 = d_rres8;
         v.dim = dim; v.dim4 = dim4; v.n_rows = n_rows; v.n_tiles = (n_rows + 63) / 64; v.metric = metric; v.filter = filter;
         v.l2_planes = l2_planes() ? 1 : 0;
         v.rowmaj16 = d_rowmaj16;
         v.rowmaj8 = d_rowmaj8; v.rowmeta8 = d_rowmeta8;
-        v.plane6 = d_plane6; v.rres6 = d_rres6; v.bound_plane6 = bound.plane6;
+        v.plane6 = d_plane6; v.rres6 = d_rres6;
         return v;
     }
     // a Euclidean index that asked for the scan planes (QV_FLAG_L2_SCAN_PLANE; on every other metric the flag does nothing)

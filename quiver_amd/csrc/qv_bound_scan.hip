@@ -1513,7 +1513,7 @@ k_bound_rescore_wide_mq(IndexView v, const float* __restrict__ queries, BoundCtr
 
 // The bound scan (k_bound_scan / k_bound_rescore above): one query, a fused-list k, cosine or dot, the bfloat16 copy at hand, a width the copy
 // covers in whole 16-dimension steps.  Automatic from kBoundScanMinRows rows (measured: profiles/LAB_r07_bound_scan.md); the index's setter
-// (IndexView::bound_scan) or QV_BOUND_SCAN = 1 takes it whenever it applies, 2 never.
+// (BoundKnobs::scan) or QV_BOUND_SCAN = 1 takes it whenever it applies, 2 never.
 // 2 - 8 queries (k_bound_scan_mq): the same conditions, and nq planes of lower bounds that stay under 2 GiB.  Its automatic rule is a floor on
 // rows that depends on the width — every query pays 8 bytes per row for its lower bounds whatever the width — per QB: the smallest measured
 // shape from which the path wins at every measured nq and k of that QB (profiles/LAB_r08_bound_scan_mq.md); narrower than
@@ -1541,7 +1541,7 @@ constexpr uint32_t kBoundScanMinRows = 300000;   // one query, us, exact / bound
 constexpr uint32_t kBoundMqMinDim = 768, kBoundMqMinRows4 = 300000, kBoundMqMinRows8 = 1000000;   // rows of at least 768 dimensions: QB = 4 (2 - 4 queries), QB = 8 (5 - 8)
 constexpr uint32_t kBoundMqNarrowDim = 128, kBoundMqNarrowRows = 10000000;                        // 128 <= dim < 768 (nothing between was measured): both QB
 // The 8-bit stage in front of it (k_bound_scan8): one unfiltered query the bound scan takes, on an index that holds the 8-bit plane.  The index's
-// plane setter (IndexView::bound_plane) or QV_BOUND_PLANE = 1 puts it first whenever that holds, 2 never; automatic from the smallest
+// plane setter (BoundKnobs::plane[bound_one]) or QV_BOUND_PLANE = 1 puts it first whenever that holds, 2 never; automatic from the smallest
 // measured row count from which 8-bit-first beats bfloat16-first at every measured k — never below kBoundScanMinRows, so a corpus under
 // that floor runs what it ran before whatever mode forces the bound scan itself.  profiles/LAB_r10_bound_scan_8bit.md; us per query,
 // bfloat16 first / 8-bit first, at k = 1, 10, 64 (the 8-bit stage passes on 3 - 4 times the rows, and one workgroup walks them: its
@@ -1554,7 +1554,7 @@ constexpr uint32_t kBound8MinDim = 768, kBound8MinRows = 3000000;            // 
 constexpr uint32_t kBound8NarrowDim = 128, kBound8NarrowRows = 10000000;     // 128 <= dim < 768 (nothing between was measured)
 // The 8-bit stage in front of an UNFILTERED shared pass of 2 - 8 queries (k_bound_scan8_mq): a pass the bound scan takes (asked with the copy
 // held: the stage never starts a pass the bound scan would not take), the plane held, and the index's shared-pass plane setter
-// (IndexView::bound_plane_mq) or QV_BOUND_PLANE_MQ — a knob of its own — allows it: 1 whenever that holds, 2 never.  Automatic: per QB the
+// (BoundKnobs::plane[bound_mq]) or QV_BOUND_PLANE_MQ — a knob of its own — allows it: 1 whenever that holds, 2 never.  Automatic: per QB the
 // smallest measured row count from which 8-bit-first beat bfloat16-first at every measured k and nq of that QB in both rounds, never below
 // the shared pass's own floors; profiles/LAB_r12_bound_scan8_mq.md.
 // us per call, bfloat16 first / 8-bit first, at k = 1, 10, 64 (the slower round of the 8-bit arm against the faster of the bfloat16 arm):
@@ -1589,7 +1589,7 @@ constexpr uint32_t kBound8MqNarrowDim = 128, kBound8MqNarrowRows4 = 10000000, kB
 constexpr uint32_t kBoundFiltMinDim = 768, kBoundFiltMqRows = 1000000, kBoundFiltBigRows = 10000000, kBoundFiltQb8SmallK = 10;
 // The 8-bit stage in front of a FILTERED single query (k_bound_scan8<., true>): whenever the filtered bound rule takes the search (asked with
 // the copy held: the stage never starts a search the bound scan would not take), one query, the plane held, and the index's filtered plane
-// setter (IndexView::bound_plane_filtered) or QV_BOUND_PLANE_FILTERED — a knob of its own, independent of the unfiltered one — allows it:
+// setter (BoundKnobs::plane[bound_one_filtered]) or QV_BOUND_PLANE_FILTERED — a knob of its own, independent of the unfiltered one — allows it:
 // 1 whenever that holds, 2 never.  Automatic: per candidate fraction f = candidate_tiles / tiles the host can tell apart, the smallest
 // measured row count from which 8-bit-first beat the parent commit's library (bfloat16 first) by more than both arms' spread at EVERY
 // measured k, never below the unfiltered 8-bit floor; 768 dimensions only, so narrower rows are declined.
@@ -1603,7 +1603,7 @@ constexpr uint32_t kBoundFiltMinDim = 768, kBoundFiltMqRows = 1000000, kBoundFil
 //   0.1 < f < 0.9 was not measured: declined.  So: f >= 0.9 from kBound8MinRows rows of kBound8MinDim dimensions or more.
 // The 8-bit stage in front of a FILTERED shared pass of 2 - 8 queries (k_bound_scan8_mq<., ., true>: a mask, a row set per query, where-filters,
 // the row-set front's shared passes): whenever the filtered bound rule takes the pass (asked with the copy held: the stage never starts a pass
-// the filtered bound scan would not take), the plane held, and the index's setter for such passes (IndexView::bound_plane_filtered_mq) or
+// the filtered bound scan would not take), the plane held, and the index's setter for such passes (BoundKnobs::plane[bound_mq_filtered]) or
 // QV_BOUND_PLANE_FILTERED_MQ — a knob of its own, independent of the three others — allows it: 1 whenever that holds, 2 never.
 // Automatic: a cell is taken only when 8-bit first beat bfloat16 first at every measured k, the slower 8-bit round against the faster
 // bfloat16 round, by more than both arms' round-to-round spread; never above what the unfiltered pass's 8-bit floors allow for the same nq, never below
@@ -1628,7 +1628,7 @@ constexpr uint32_t kBoundFiltMinDim = 768, kBoundFiltMqRows = 1000000, kBoundFil
 // So: f >= 0.9 from 3 000 000 rows of 768 dimensions or more, both QB; 1M loses at k = 64 with every tile a candidate.  Spreads <= 83 us at 10M, <= 11 us below.
 constexpr uint32_t kBound8FiltMqMinDim = 768, kBound8FiltMqMinRows4 = 3000000, kBound8FiltMqMinRows8 = 3000000;   // rows of at least 768 dimensions, QB = 4 / QB = 8; 0: never automatic
 // The 6-bit stage in front of the 8-bit one (k_bound_scan6 + k_bound_refine8): one UNFILTERED query the 8-bit stage takes, on an index that
-// holds the 6-bit plane.  The index's setter (IndexView::bound_plane6) or QV_BOUND_PLANE6 = 1 puts it first whenever that holds, 2 never.
+// holds the 6-bit plane.  The index's setter (BoundKnobs::plane6) or QV_BOUND_PLANE6 = 1 puts it first whenever that holds, 2 never.
 // Automatic: the cells in which 6-bit first beat 8-bit first in both rounds by more than the rounds' disagreement, never below the 8-bit
 // stage's own floor; profiles/LAB_r20_bound_scan6.md; us per query, 8-bit first / 6-bit first (candidates of the 6-bit stage), at k = 1, 10, 64:
 //   768 dims   3M  420 / 384 (840), 426 / 443 (5 324), 486 / 615 (15 416): losses from k = 10 on
@@ -1693,7 +1693,6 @@ static int rule_metric(const IndexView& v) { return v.metric == QV_L2 && v.l2_pl
 BoundAsk bound_ask(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles) {
     return {rule_metric(v), v.dim, v.n_rows, nq, k, candidate_tiles, v.plane != nullptr, v.plane8 != nullptr, v.plane8 != nullptr && v.plane6 != nullptr};
 }
-BoundKnobs bound_knobs(const IndexView& v) { return {v.bound_scan, {v.bound_plane, v.bound_plane_filtered, v.bound_plane_mq, v.bound_plane_filtered_mq}, v.bound_plane6}; }
 int bound_scan_mode(int mode) { static const int env_mode = env_int("QV_BOUND_SCAN", 0); return mode ? mode : env_mode; }
 static int bound_plane_mode(BoundForm form, int mode) {                // the form's plane mode in force: the index's own, else its variable (read once)
     static const int env_mode[4] = {env_int("QV_BOUND_PLANE", 0), env_int("QV_BOUND_PLANE_FILTERED", 0), env_int("QV_BOUND_PLANE_MQ", 0), env_int("QV_BOUND_PLANE_FILTERED_MQ", 0)};
@@ -1833,11 +1832,20 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
     *gate_out = &ctrl->flag;
     return hipGetLastError();
 }
-// ---- the wide form (65 <= k <= kBoundWideMaxK): its rule, its buffer, its launches ----
-// The rule is the wide form's own: bound_scan_decide keeps answering none above kMaxFusedK (qv_scan_bound_applies(., k = 65, ALWAYS, .) == 0 is
-// pinned by tests), and the knob is independent of qv_index_set_bound_scan.  NEVER, or a call the kernels cannot serve -> 0.  ALWAYS -> the
-// wide form; the 8-bit plane first under QV_BOUND_PLANE_8BIT where it is held, the bfloat16 copy first otherwise.
-// AUTOMATIC: the cells of profiles/LAB_r24_bound_scan_wide.md in which the wide form ran ahead of the exact path (k_flat_scan_wide up to
+// ---- the wide forms (65 <= k <= kBoundWideMaxK): their ONE decision (bound_wide_decide; the dispatch asks it, the launchers never) ----
+// bound_scan_decide keeps answering none above kMaxFusedK (qv_scan_bound_applies(., k = 65, ALWAYS, .) == 0 is pinned by tests); the wide forms
+// have a decision of their own with the same skeleton, written once below for all four — one query or a shared pass of 2 - 8, unfiltered or
+// filtered: "never" on the FORM's wide knob (BoundKnobs::wide, by BoundForm: a knob of its own per form, independent of the three others and
+// of every k <= 64 knob), or a call the kernels cannot serve (bound_wide_kernels_serve) -> none; the form under "always", else where the
+// automatic rule of the call's class takes it; then the plane it starts on under the form's plane knob (BoundKnobs::plane): "bf16" or no
+// 8-bit plane held -> the bfloat16 copy first, "8bit" -> the 8-bit plane first, else where 8-bit first's automatic rule takes it.  What
+// differs between the forms is data: two tables of measured floors by class (one query, QB = 4: 2 - 4 queries, QB = 8: 5 - 8) and stage
+// (the form against the path the call takes without it; the 8-bit plane first against the bfloat16 copy first).  An automatic rule is the
+// unfiltered floor of its class and, under a filter, the filter's floor ON TOP: a filtered form is never taken below the unfiltered floors.
+// Automatic is cosine and dot only, up to the largest measured k.  A floor of 0 rows is never automatic.
+constexpr uint32_t kBoundWideAutoMaxK = 1000;                         // the largest measured k
+enum { kWideForm = 0, kWidePlane8 = 1 };                              // a table row's two stages
+// ONE QUERY: the cells of profiles/LAB_r24_bound_scan_wide.md in which the wide form ran ahead of the exact path (k_flat_scan_wide up to
 // k = 128, the key-per-row path above) at EVERY measured k — 65, 100, 128, 129, 256, 1000 — by more than both arms' spread, and the 8-bit
 // plane first only where it also beat the bfloat16 copy first by the same standard; cosine, device-pointer calls, five alternating rounds
 // of 20 calls.  us per call, exact / bfloat16 first / 8-bit first (survivors bfloat16 / 8-bit), spreads <= 18 us:
@@ -1848,34 +1856,33 @@ hipError_t launch_bound_scan(const IndexView& v, const ScanPlan& p, const float*
 // No cell lost, in either comparison.  NOT measured, so never automatic: fewer than 1M rows; narrower than 128 dimensions; 128 <= dim < 768
 // below 10M rows (nothing between the widths was measured: the other rules' two width classes); k above 1000; QV_L2 indexes with the
 // planes (cosine was measured; dot runs the same kernels over the same bytes and differs in the finalize alone).
-constexpr BoundFloor kBoundWideFloor = {1000000, 128, 10000000};      // the wide form against the exact path
-constexpr BoundFloor kBoundWide8Floor = {1000000, 128, 10000000};     // ... and the 8-bit plane first against the bfloat16 copy first
-constexpr uint32_t kBoundWideAutoMaxK = 1000;                         // the largest measured k
-static bool bound_wide_auto(const BoundFloor& f, int rule_metric, uint32_t dim, uint32_t rows, uint32_t k) {
-    const uint32_t floor = dim >= kBoundWideDim ? f.wide_rows : f.narrow_dim != 0 && dim >= f.narrow_dim ? f.narrow_rows : 0u;
-    return floor != 0 && rows >= floor && k <= kBoundWideAutoMaxK && (rule_metric == QV_COSINE || rule_metric == QV_DOT);
-}
-int bound_wide_route(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, bool has_plane, bool has_plane8) {
-    static const int env_wide = env_int("QV_BOUND_SCAN_WIDE", 0);
-    const int mode = wide_mode ? wide_mode : env_wide;
-    if (mode == 2) return 0;
-    // what the kernels need: one query, the list lengths behind the wave list, the k <= 64 form's metrics and widths, the copy, 8 tiles, more
-    // rows than results (a k that takes every row has nothing to reject), and room for the redo's two key planes
-    const uint32_t n_tiles = (uint32_t)(((uint64_t)rows + 63) / 64);
-    const bool metric_ok = rule_metric == QV_COSINE || rule_metric == QV_DOT || rule_metric == QV_RULE_L2_PLANES;
-    if (nq != 1 || k <= (uint32_t)kMaxFusedK || k > kBoundWideMaxK || !metric_ok || !has_plane) return 0;
-    if ((dim & 15u) != 0 || dim == 0 || dim > kBoundMaxDim || n_tiles < 8 || k >= rows || !flat_select_redo_one_serves(n_tiles)) return 0;
-    if (mode != 1 && !bound_wide_auto(kBoundWideFloor, rule_metric, dim, rows, k)) return 0;
-    const int plane = bound_plane_mode(bound_one, plane_mode);
-    if (plane == 2 || !has_plane8) return 1;
-    return plane == 1 || bound_wide_auto(kBoundWide8Floor, rule_metric, dim, rows, k) ? 2 : 1;
-}
-// The FILTERED wide form's rule (one query over a candidate bitmap: qv_index_search_masked, a row set, a where-filter made into a set): a knob
-// of its own (qv_index_set_bound_scan_wide_filtered / QV_BOUND_SCAN_WIDE_FILTERED), independent of the unfiltered form's and of the k <= 64
-// knobs; the plane it starts on is the single-query filtered plane knob's (bound_one_filtered).  What the kernels need is what the unfiltered
-// form needs, and on top: a tile that holds a candidate, and MORE candidates than results — a k that takes every candidate has nothing to
-// reject, and a shorter set keeps its path and its clamped count.
-// AUTOMATIC: the unfiltered floor (bound_wide_auto: never a shape the unfiltered rule declines — cosine and dot, k <= 1000) and, on top, the
+constexpr BoundFloor kBoundWideFloor[3][2] = {                        // by class, then stage: {the form against the exact path, the 8-bit plane first against the bfloat16 copy first}
+    {{1000000, 128, 10000000}, {1000000, 128, 10000000}},             // one query
+// A SHARED PASS of 2 - 8 queries, per class: only measured cells are taken — the form against the key-per-row shared pass (k_flat_keys_mq + the
+// radix selection), 8-bit first against bfloat16 first, each by more than both arms' spread at every measured k and nq of the class
+// (profiles/LAB_r26_bound_scan_wide_mq.md) — so QV_L2 indexes with the planes are reached under ALWAYS alone, and dot is taken where cosine
+// was measured (the same kernels over the same bytes; the finalize differs).
+// Cosine, device-pointer calls, five alternating rounds of 20 calls; nq = 2 and 4 (QB = 4), nq = 5 and 8 (QB = 8); k = 65, 100, 128, 129, 256,
+// 1000.  us per call at k = 100 and 1000, key-per-row / bfloat16 first / 8-bit first (spreads <= 27 us, at 10M x 768 <= 63 us):
+//   768 dims   1M   nq 2: 521 / 379 / 280, 552 / 418 / 351      nq 4: 547 / 424 / 345, 584 / 480 / 438
+//                   nq 5: 598 / 588 / 440, 646 / 641 / 557      nq 8: 596 / 660 / 534, 646 / 757 / 698
+//              3M   nq 2: 1495 / 858 / 547, 1536 / 898 / 611    nq 4: 1473 / 887 / 589, 1539 / 941 / 682
+//                   nq 5: 1556 / 1243 / 782, 1632 / 1330 / 904  nq 8: 1788 / 1367 / 943, 1884 / 1470 / 1116
+//              10M  nq 2: 4872 / 2560 / 1403, 4875 / 2592 / 1469    nq 4: 5237 / 2762 / 1533, 5244 / 2802 / 1621
+//                   nq 5: 5551 / 3568 / 1980, 5561 / 3571 / 2022    nq 8: 6041 / 3846 / 2255, 6047 / 3927 / 2401
+//   128 dims   10M  nq 2: 945 / 534 / 453, 948 / 561 / 476      nq 4: 1158 / 718 / 652, 1161 / 752 / 683
+//                   nq 5: 1259 / 844 / 837, 1262 / 883 / 869    nq 8: 1395 / 1073 / 1134, 1399 / 1110 / 1175
+// LOSSES: at 1M x 768 the bfloat16 copy first lost to the key-per-row pass with 8 queries at every k (by 9 - 17 %) and did not clear the
+// spread with 5 queries at k = 1000, so QB = 8 starts at 3M rows — the 8-bit plane first ran ahead of both there but for 8 queries at
+// k = 1000 (698 against 646), and is not taken either: it is never automatic where the form is not; at 10M x 128 the 8-bit plane first lost
+// to the bfloat16 copy first with 8 queries at every k (by 6 %; with 5 queries it won by 1 - 2 %), so QB = 8 stays on the bfloat16 copy below
+// 768 dimensions.  Every other cell won both comparisons at every k.  NOT measured, so never automatic: fewer than 1M rows; narrower than
+// 128 dimensions; 128 <= dim < 768 below 10M rows; k above 1000; QV_L2 indexes with the planes.  (nq = 3, 6 and 7 were not run: they go with
+// their class, between its two measured fills, as in the k <= 64 rules.)
+    {{1000000, 128, 10000000}, {1000000, 128, 10000000}},             // QB = 4, against the key-per-row shared pass
+    {{3000000, 128, 10000000}, {3000000, 0, 0}},                      // QB = 8
+};
+// ONE QUERY OVER A CANDIDATE BITMAP (qv_index_search_masked, a row set, a where-filter made into a set): on top of the unfiltered floor, the
 // cells of profiles/LAB_r25_bound_scan_wide_filtered.md in which the form ran ahead of the path the filtered call takes today (the filtered
 // k_flat_scan_wide up to k = 128, the key-per-row path above) at EVERY measured k — 65, 100, 128, 129, 256, 1000 — by more than both arms'
 // spread, and the 8-bit plane first only where it also beat the bfloat16 copy first by the same standard; cosine, device-pointer row-set
@@ -1896,33 +1903,87 @@ struct BoundWideFilterFloor {
     uint32_t big_rows, big_frac;          // ... from big_rows rows on, big_frac in its place (0 rows: no such size)
     uint32_t narrow_rows, narrow_frac;    // the unfiltered floor's narrow class (its narrow_dim <= dim < kBoundWideDim)
 };
-constexpr BoundWideFilterFloor kBoundWideFilterFloor = {1000000, 100, 0, 0, 10000000, 100};          // the filtered wide form against today's filtered path
-constexpr BoundWideFilterFloor kBoundWide8FilterFloor = {1000000, 1000, 3000000, 100, 10000000, 475};   // ... and the 8-bit plane first against the bfloat16 copy first
-static_assert(kBoundWide8FilterFloor.wide_rows >= kBoundWideFilterFloor.wide_rows && kBoundWide8FilterFloor.wide_frac >= kBoundWideFilterFloor.wide_frac &&
-              kBoundWide8FilterFloor.big_frac >= kBoundWideFilterFloor.wide_frac && kBoundWide8FilterFloor.narrow_rows >= kBoundWideFilterFloor.narrow_rows &&
-              kBoundWide8FilterFloor.narrow_frac >= kBoundWideFilterFloor.narrow_frac && kBoundWideFilterFloor.wide_rows >= kBoundWideFloor.wide_rows &&
-              kBoundWideFilterFloor.narrow_rows >= kBoundWideFloor.narrow_rows, "8-bit first is never automatic where the form is not, nor the form below the unfiltered floor");
-static bool bound_wide_filtered_auto(const BoundFloor& f, const BoundWideFilterFloor& g, int rule_metric, uint32_t dim, uint32_t rows, uint32_t k, uint32_t candidate_tiles) {
-    if (!bound_wide_auto(f, rule_metric, dim, rows, k)) return false;
-    const uint64_t n_tiles = ((uint64_t)rows + 63) / 64, ct = std::min<uint64_t>(candidate_tiles, n_tiles);
-    const bool wide = dim >= kBoundWideDim, big = wide && g.big_rows != 0 && rows >= g.big_rows;
-    const uint32_t floor = wide ? g.wide_rows : g.narrow_rows, frac = big ? g.big_frac : wide ? g.wide_frac : g.narrow_frac;
-    return ct != 0 && floor != 0 && rows >= floor && ct * 1000 >= n_tiles * frac;
+constexpr BoundWideFilterFloor kBoundWideFilterFloor[3][2] = {        // by class, then stage: {the form against today's filtered path, the 8-bit plane first against the bfloat16 copy first}
+    {{1000000, 100, 0, 0, 10000000, 100}, {1000000, 1000, 3000000, 100, 10000000, 475}},   // one query
+// A FILTERED SHARED PASS of 2 - 8 queries (each over its own alive & set, or all over one bitmap): nothing yet — the rows below are all zero
+// rows, so AUTO answers none for every shape and with nothing set a filtered call launches what it launches today.  Measured
+// (profiles/LAB_r27_bound_scan_wide_filtered_mq.md; cosine, device-pointer row-set calls, five
+// alternating rounds of 20 calls, nq = 2, 4, 5, 8, k = 65, 100, 1000; today's path is a single-query filtered wide scan per query for distinct
+// sets and the key-per-row shared pass for one set).  us per call at k = 100, today / bfloat16 first / 8-bit first (spreads <= 21 us, at
+// 10M x 768 <= 64 us):
+//   768 dims   1M   null sets   nq 2: 524 / 378 / 290    nq 4: 551 / 428 / 351    nq 5: 603 / 591 / 449    nq 8: 618 / 658 / 540
+//                   1 % each    nq 2: 442 / 328 / 253    nq 4: 898 / 404 / 301    nq 5: 1123 / 528 / 354   nq 8: 1801 / 560 / 383
+//                   tile in ten nq 2: 556 / 189 / 185    nq 4: 587 / 226 / 224    nq 5: 655 / 300 / 266    nq 8: 685 / 335 / 299
+//              3M   null sets   nq 2: 1495 / 865 / 546   nq 4: 1619 / 945 / 636   nq 5: 1711 / 1245 / 804  nq 8: 1792 / 1366 / 961
+//                   1 % each    nq 2: 663 / 722 / 464    nq 4: 1338 / 908 / 581   nq 5: 1673 / 1175 / 674  nq 8: 2679 / 1249 / 732
+//                   tile in ten nq 2: 1526 / 461 / 354   nq 4: 1656 / 543 / 451   nq 5: 1784 / 1156 / 619  nq 8: 1867 / 1282 / 750
+//              10M  null sets   nq 2: 4888 / 2557 / 1452 nq 4: 5322 / 2758 / 1629 nq 5: 5676 / 3547 / 2016 nq 8: 6032 / 3807 / 2327
+//                   1 % each    nq 2: 1578 / 2042 / 1176 nq 4: 3140 / 2640 / 1532 nq 5: 3928 / 3476 / 1795 nq 8: 6278 / 3720 / 1986
+//                   tile in ten nq 2: 4860 / 507 / 373   nq 4: 5287 / 584 / 457   nq 5: 5645 / 994 / 594   nq 8: 6001 / 1123 / 722
+//   128 dims   10M  null sets   nq 2: 1039 / 618 / 478   nq 4: 1156 / 735 / 681   nq 5: 1263 / 869 / 901   nq 8: 1397 / 1101 / 1220
+//                   1 % each    nq 2: 575 / 513 / 380    nq 4: 1243 / 664 / 504   nq 5: 1485 / 768 / 652   nq 8: 2485 / 926 / 816
+//                   tile in ten nq 2: 1043 / 233 / 241   nq 4: 1157 / 312 / 327   nq 5: 1263 / 378 / 388   nq 8: 1397 / 498 / 515
+// LOSSES: the bfloat16 copy first lost to today's path with TWO queries over distinct 1 % sets at 3M and 10M x 768 at every k (two
+// single-query 8-bit-first scans beat one shared bfloat16 pass), and at 1M x 768 with null sets for 8 queries at every k and 5 at k = 1000,
+// where the 8-bit plane first also lost at k = 1000 with 8 queries (705 against 673); the 8-bit plane first lost to the bfloat16 copy
+// first at 10M x 128 for 5 and 8 queries over null sets and for every nq at one tile in ten, and at 1M x 768 at one tile in ten for
+// k = 65 and 1000.  Every other cell won.  The wins therefore depend on the KIND of filter (one set for all against a set per query) as
+// well as on candidate tiles, which BoundWideFilterFloor cannot express: class QB = 4 loses a cell at every measured size of 768
+// dimensions with the bfloat16 copy first.  The rows stay at zero until the rule can tell those apart; "always" reaches the form.
+// Whatever they come to hold, AUTO never takes a shape the unfiltered shared pass's floor declines (it is asked first).  NOT measured:
+// sparser filters, QV_L2 with the planes, k above 1000, other widths.
+    {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}},                         // QB = 4: not measured well enough to take
+    {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}},                         // QB = 8: the same
+};
+constexpr bool bound_wide_floors_nest() {                             // per class: 8-bit first never automatic where the form is not, nor a filtered floor below the unfiltered one
+    for (int c = 0; c < 3; c++) {
+        const BoundFloor &f = kBoundWideFloor[c][kWideForm], &p = kBoundWideFloor[c][kWidePlane8];
+        const BoundWideFilterFloor &g = kBoundWideFilterFloor[c][kWideForm], &q = kBoundWideFilterFloor[c][kWidePlane8];
+        if (p.wide_rows != 0 && (f.wide_rows == 0 || p.wide_rows < f.wide_rows)) return false;
+        if (p.narrow_rows != 0 && (f.narrow_rows == 0 || p.narrow_rows < f.narrow_rows || p.narrow_dim < f.narrow_dim)) return false;
+        if (g.wide_rows != 0 && g.wide_rows < f.wide_rows) return false;
+        if (g.narrow_rows != 0 && g.narrow_rows < f.narrow_rows) return false;
+        if (q.wide_rows != 0 && (g.wide_rows == 0 || q.wide_rows < g.wide_rows || q.wide_frac < g.wide_frac || q.big_frac < g.wide_frac)) return false;
+        if (q.narrow_rows != 0 && (g.narrow_rows == 0 || q.narrow_rows < g.narrow_rows || q.narrow_frac < g.narrow_frac)) return false;
+    }
+    return true;
 }
-int bound_wide_route_filtered(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered, bool has_plane, bool has_plane8,
-                              uint32_t candidate_tiles, uint64_t candidates) {
-    static const int env_wide = env_int("QV_BOUND_SCAN_WIDE_FILTERED", 0);
-    const int mode = wide_mode ? wide_mode : env_wide;
-    if (mode == 2) return 0;
-    const uint32_t n_tiles = (uint32_t)(((uint64_t)rows + 63) / 64);
-    const bool metric_ok = rule_metric == QV_COSINE || rule_metric == QV_DOT || rule_metric == QV_RULE_L2_PLANES;
-    if (nq != 1 || k <= (uint32_t)kMaxFusedK || k > kBoundWideMaxK || !metric_ok || !has_plane) return 0;
-    if ((dim & 15u) != 0 || dim == 0 || dim > kBoundMaxDim || n_tiles < 8 || k >= rows || !flat_select_redo_one_serves(n_tiles)) return 0;
-    if (candidate_tiles == 0 || candidates <= (uint64_t)k) return 0;
-    if (mode != 1 && !bound_wide_filtered_auto(kBoundWideFloor, kBoundWideFilterFloor, rule_metric, dim, rows, k, candidate_tiles)) return 0;
-    const int plane = bound_plane_mode(bound_one_filtered, plane_mode_filtered);
-    if (plane == 2 || !has_plane8) return 1;
-    return plane == 1 || bound_wide_filtered_auto(kBoundWide8Floor, kBoundWide8FilterFloor, rule_metric, dim, rows, k, candidate_tiles) ? 2 : 1;
+static_assert(bound_wide_floors_nest(), "8-bit first is never automatic where the form is not, nor a filtered form below the unfiltered floor");
+// what the kernels need, whatever the knobs say: 1 - 8 queries, the list lengths behind the wave list, the k <= 64 form's metrics and widths,
+// the copy, 8 tiles, more rows than results (a k that takes every row has nothing to reject), room for the redo's key planes (the lone
+// query rides in a pass of two slots: an index of at most 64M rows), and for a shared pass nq planes of lower bounds under 2 GiB.  A filtered
+// form on top: a tile that holds a candidate, and MORE candidates than results for EVERY query — min_candidates is the smallest live count
+// among them (ignored for an unfiltered ask); a query whose set holds k live rows or fewer keeps its path and its clamped count.
+bool bound_wide_kernels_serve(const BoundAsk& a, uint64_t min_candidates) {
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)a.n_rows + 63) / 64);
+    const bool metric_ok = a.rule_metric == QV_COSINE || a.rule_metric == QV_DOT || a.rule_metric == QV_RULE_L2_PLANES;
+    if (a.nq < 1 || a.nq > kBoundMqMax || a.k <= (uint32_t)kMaxFusedK || a.k > kBoundWideMaxK || !metric_ok || !a.has_plane) return false;
+    if ((a.dim & 15u) != 0 || a.dim == 0 || a.dim > kBoundMaxDim || n_tiles < 8 || a.k >= a.n_rows || !flat_select_redo_one_serves(n_tiles)) return false;
+    if (a.nq > 1 && (uint64_t)a.nq * n_tiles * 256 > (2ull << 30)) return false;
+    return a.candidate_tiles == kBoundNoFilter || (a.candidate_tiles != 0 && min_candidates > (uint64_t)a.k);
+}
+static bool bound_wide_auto(const BoundAsk& a, int stage) {
+    const int cls = a.nq == 1 ? 0 : a.nq <= 4 ? 1 : 2;
+    const BoundFloor& f = kBoundWideFloor[cls][stage];
+    const bool wide = a.dim >= kBoundWideDim;
+    const uint32_t floor = wide ? f.wide_rows : f.narrow_dim != 0 && a.dim >= f.narrow_dim ? f.narrow_rows : 0u;
+    if (floor == 0 || a.n_rows < floor || a.k > kBoundWideAutoMaxK || (a.rule_metric != QV_COSINE && a.rule_metric != QV_DOT)) return false;
+    if (a.candidate_tiles == kBoundNoFilter) return true;
+    const BoundWideFilterFloor& g = kBoundWideFilterFloor[cls][stage];
+    const uint64_t n_tiles = ((uint64_t)a.n_rows + 63) / 64, ct = std::min<uint64_t>(a.candidate_tiles, n_tiles);
+    const bool big = wide && g.big_rows != 0 && a.n_rows >= g.big_rows;
+    const uint32_t gfloor = wide ? g.wide_rows : g.narrow_rows, frac = big ? g.big_frac : wide ? g.wide_frac : g.narrow_frac;
+    return ct != 0 && gfloor != 0 && a.n_rows >= gfloor && ct * 1000 >= n_tiles * frac;
+}
+BoundStages bound_wide_decide(const BoundAsk& a, uint64_t min_candidates, const BoundKnobs& knobs) {
+    static const int env_wide[4] = {env_int("QV_BOUND_SCAN_WIDE", 0), env_int("QV_BOUND_SCAN_WIDE_FILTERED", 0), env_int("QV_BOUND_SCAN_WIDE_MQ", 0), env_int("QV_BOUND_SCAN_WIDE_FILTERED_MQ", 0)};
+    const BoundForm form = bound_form(a);
+    const int mode = knobs.wide[form] ? knobs.wide[form] : env_wide[form];
+    if (mode == 2 || !bound_wide_kernels_serve(a, min_candidates)) return BoundStages::none;
+    if (mode != 1 && !bound_wide_auto(a, kWideForm)) return BoundStages::none;
+    const int plane = bound_plane_mode(form, knobs.plane[form]);
+    if (plane == 2 || !a.has_plane8) return BoundStages::bf16;
+    return plane == 1 || bound_wide_auto(a, kWidePlane8) ? BoundStages::plane8_first : BoundStages::bf16;
 }
 // the wide form's buffer.  The redo's workspace overlays the rest: it is written only when every bound stage has ended.
 struct BoundWideLayout { void* redo; uint64_t* lists; uint32_t* seed_rows; float* seed_dist; void* sel_ws; uint32_t* cand; uint64_t* keys; uint32_t* sel; uint32_t* lo_all; size_t end, total; };
@@ -1945,9 +2006,8 @@ static BoundWideLayout bound_wide_layout(void* base, const ScanPlan& p, uint32_t
 size_t bound_scan_wide_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log) { return bound_wide_layout(nullptr, p, k, n_tiles, dim, log).total; }
 hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                                   uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first, bool masked) {
-    // (whether the path is TAKEN is bound_wide_route's decision, under a filter bound_wide_route_filtered's; here only what the kernels need)
-    if (bound_wide_route(rule_metric(v), v.dim, v.n_rows, 1, k, 1, plane8_first ? 1 : 2, v.plane != nullptr, v.plane8 != nullptr) != (plane8_first ? 2 : 1) || !d_ctrl || !d_stats)
-        return hipErrorInvalidValue;
+    // (whether the path is TAKEN is bound_wide_decide's decision; here only what the kernels need)
+    if (!bound_wide_kernels_serve(bound_ask(v, 1, k, kBoundNoFilter), 0) || (plane8_first && !v.plane8) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
     const uint32_t grid = p.grid;
     const BoundWideLayout L = bound_wide_layout(d_ws, p, k, v.n_tiles, v.dim);
     const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(kBoundCollectGrid, (n_pad + kCollectChunk - 1u) / kCollectChunk);
@@ -2003,112 +2063,7 @@ hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const f
     if (e != hipSuccess) return e;
     return launch_flat_select_redo_one(v, p, d_query, k, k, &ctrl->flag, L.redo, d_rows_out, d_dist_out, s);
 }
-// ---- the wide form of the shared pass (2 - 8 queries, 65 <= k <= kBoundWideMaxK): its rule, its buffer, its launches ----
-// A rule and a knob of its own (qv_index_set_bound_scan_wide_mq / QV_BOUND_SCAN_WIDE_MQ): independent of the single-query wide knob, of
-// qv_index_set_bound_scan and of the single-query plane knobs; bound_wide_route keeps answering 0 for nq != 1.  NEVER, or a pass the kernels
-// cannot serve -> 0.  What they need: 2 - 8 unfiltered queries, the k <= 64 pass's and the single wide form's limits — metric, the copy, whole
-// 16-dimension steps, 8 tiles, nq planes of lower bounds under 2 GiB, more rows than results — and an index of at most 64M rows (the redo's
-// shared key passes take two queries' keys at least: flat_select_redo_one_serves).  ALWAYS -> the form; which plane comes first is the
-// shared pass's plane knob (qv_index_set_bound_plane_mq / QV_BOUND_PLANE_MQ): 8-bit first under "8bit" where the plane is held.
-// AUTOMATIC: per class (QB = 4: 2 - 4 queries, QB = 8: 5 - 8) the floors below; a floor of 0 rows is never automatic.  Only measured cells
-// are taken — the form against the key-per-row shared pass (k_flat_keys_mq + the radix selection), 8-bit first against bfloat16 first, each by
-// more than both arms' spread at every measured k and nq of the class (profiles/LAB_r26_bound_scan_wide_mq.md) — so QV_L2 indexes with the
-// planes are reached under ALWAYS alone, and dot is taken where cosine was measured (the same kernels over the same bytes; the finalize differs).
-// Cosine, device-pointer calls, five alternating rounds of 20 calls; nq = 2 and 4 (QB = 4), nq = 5 and 8 (QB = 8); k = 65, 100, 128, 129, 256,
-// 1000.  us per call at k = 100 and 1000, key-per-row / bfloat16 first / 8-bit first (spreads <= 27 us, at 10M x 768 <= 63 us):
-//   768 dims   1M   nq 2: 521 / 379 / 280, 552 / 418 / 351      nq 4: 547 / 424 / 345, 584 / 480 / 438
-//                   nq 5: 598 / 588 / 440, 646 / 641 / 557      nq 8: 596 / 660 / 534, 646 / 757 / 698
-//              3M   nq 2: 1495 / 858 / 547, 1536 / 898 / 611    nq 4: 1473 / 887 / 589, 1539 / 941 / 682
-//                   nq 5: 1556 / 1243 / 782, 1632 / 1330 / 904  nq 8: 1788 / 1367 / 943, 1884 / 1470 / 1116
-//              10M  nq 2: 4872 / 2560 / 1403, 4875 / 2592 / 1469    nq 4: 5237 / 2762 / 1533, 5244 / 2802 / 1621
-//                   nq 5: 5551 / 3568 / 1980, 5561 / 3571 / 2022    nq 8: 6041 / 3846 / 2255, 6047 / 3927 / 2401
-//   128 dims   10M  nq 2: 945 / 534 / 453, 948 / 561 / 476      nq 4: 1158 / 718 / 652, 1161 / 752 / 683
-//                   nq 5: 1259 / 844 / 837, 1262 / 883 / 869    nq 8: 1395 / 1073 / 1134, 1399 / 1110 / 1175
-// LOSSES: at 1M x 768 the bfloat16 copy first lost to the key-per-row pass with 8 queries at every k (by 9 - 17 %) and did not clear the
-// spread with 5 queries at k = 1000, so QB = 8 starts at 3M rows — the 8-bit plane first ran ahead of both there but for 8 queries at
-// k = 1000 (698 against 646), and is not taken either: it is never automatic where the form is not; at 10M x 128 the 8-bit plane first lost
-// to the bfloat16 copy first with 8 queries at every k (by 6 %; with 5 queries it won by 1 - 2 %), so QB = 8 stays on the bfloat16 copy below
-// 768 dimensions.  Every other cell won both comparisons at every k.  NOT measured, so never automatic: fewer than 1M rows; narrower than
-// 128 dimensions; 128 <= dim < 768 below 10M rows; k above 1000; QV_L2 indexes with the planes.  (nq = 3, 6 and 7 were not run: they go with
-// their class, between its two measured fills, as in the k <= 64 rules.)
-constexpr BoundFloor kBoundWideMqFloor[2] = {{1000000, 128, 10000000}, {3000000, 128, 10000000}};   // the form against the key-per-row shared pass, QB = 4 / QB = 8
-constexpr BoundFloor kBoundWideMq8Floor[2] = {{1000000, 128, 10000000}, {3000000, 0, 0}};           // ... and the 8-bit plane first against the bfloat16 copy first
-constexpr bool bound_wide_mq_floors_nest() {
-    for (int c = 0; c < 2; c++) {
-        const BoundFloor &f = kBoundWideMqFloor[c], &p = kBoundWideMq8Floor[c];
-        if (p.wide_rows != 0 && (f.wide_rows == 0 || p.wide_rows < f.wide_rows)) return false;
-        if (p.narrow_rows != 0 && (f.narrow_rows == 0 || p.narrow_rows < f.narrow_rows || p.narrow_dim < f.narrow_dim)) return false;
-    }
-    return true;
-}
-static_assert(bound_wide_mq_floors_nest(), "8-bit first is never automatic where the wide shared pass is not");
-int bound_wide_route_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mq_mode, int plane_mode_mq, bool has_plane, bool has_plane8) {
-    static const int env_wide = env_int("QV_BOUND_SCAN_WIDE_MQ", 0);
-    const int mode = wide_mq_mode ? wide_mq_mode : env_wide;
-    if (mode == 2) return 0;
-    const uint32_t n_tiles = (uint32_t)(((uint64_t)rows + 63) / 64);
-    const bool metric_ok = rule_metric == QV_COSINE || rule_metric == QV_DOT || rule_metric == QV_RULE_L2_PLANES;
-    if (nq < 2 || nq > kBoundMqMax || k <= (uint32_t)kMaxFusedK || k > kBoundWideMaxK || !metric_ok || !has_plane) return 0;
-    if ((dim & 15u) != 0 || dim == 0 || dim > kBoundMaxDim || n_tiles < 8 || k >= rows || !flat_select_redo_one_serves(n_tiles)) return 0;
-    if ((uint64_t)nq * n_tiles * 256 > (2ull << 30)) return 0;
-    const int cls = nq <= 4 ? 0 : 1;
-    if (mode != 1 && !bound_wide_auto(kBoundWideMqFloor[cls], rule_metric, dim, rows, k)) return 0;
-    const int plane = bound_plane_mode(bound_mq, plane_mode_mq);
-    if (plane == 2 || !has_plane8) return 1;
-    return plane == 1 || bound_wide_auto(kBoundWideMq8Floor[cls], rule_metric, dim, rows, k) ? 2 : 1;
-}
-// The FILTERED wide shared pass's rule (2 - 8 queries, each over its own alive & set, or all over one bitmap): a knob of its own
-// (qv_index_set_bound_scan_wide_filtered_mq / QV_BOUND_SCAN_WIDE_FILTERED_MQ), independent of the three other wide knobs — bound_wide_route,
-// bound_wide_route_filtered and bound_wide_route_mq answer as they did —, and the plane of the filtered shared pass's plane knob
-// (bound_mq_filtered).  What the kernels need is what the unfiltered wide shared pass needs (the same walk, funnel and buffer), and on top:
-// a tile that holds a candidate, and MORE candidates than results for EVERY query of the piece — min_candidates is the smallest count among
-// them; a query whose set holds k live rows or fewer has no H_j worth a pass and keeps its path and its clamped count (the dispatch cuts
-// the piece around it).
-// AUTOMATIC: nothing yet — the floors below are all zero rows, so AUTO answers 0 for every shape and with nothing set a filtered call
-// launches what it launches today.  Measured (profiles/LAB_r27_bound_scan_wide_filtered_mq.md; cosine, device-pointer row-set calls, five
-// alternating rounds of 20 calls, nq = 2, 4, 5, 8, k = 65, 100, 1000; today's path is a single-query filtered wide scan per query for distinct
-// sets and the key-per-row shared pass for one set).  us per call at k = 100, today / bfloat16 first / 8-bit first (spreads <= 21 us, at
-// 10M x 768 <= 64 us):
-//   768 dims   1M   null sets   nq 2: 524 / 378 / 290    nq 4: 551 / 428 / 351    nq 5: 603 / 591 / 449    nq 8: 618 / 658 / 540
-//                   1 % each    nq 2: 442 / 328 / 253    nq 4: 898 / 404 / 301    nq 5: 1123 / 528 / 354   nq 8: 1801 / 560 / 383
-//                   tile in ten nq 2: 556 / 189 / 185    nq 4: 587 / 226 / 224    nq 5: 655 / 300 / 266    nq 8: 685 / 335 / 299
-//              3M   null sets   nq 2: 1495 / 865 / 546   nq 4: 1619 / 945 / 636   nq 5: 1711 / 1245 / 804  nq 8: 1792 / 1366 / 961
-//                   1 % each    nq 2: 663 / 722 / 464    nq 4: 1338 / 908 / 581   nq 5: 1673 / 1175 / 674  nq 8: 2679 / 1249 / 732
-//                   tile in ten nq 2: 1526 / 461 / 354   nq 4: 1656 / 543 / 451   nq 5: 1784 / 1156 / 619  nq 8: 1867 / 1282 / 750
-//              10M  null sets   nq 2: 4888 / 2557 / 1452 nq 4: 5322 / 2758 / 1629 nq 5: 5676 / 3547 / 2016 nq 8: 6032 / 3807 / 2327
-//                   1 % each    nq 2: 1578 / 2042 / 1176 nq 4: 3140 / 2640 / 1532 nq 5: 3928 / 3476 / 1795 nq 8: 6278 / 3720 / 1986
-//                   tile in ten nq 2: 4860 / 507 / 373   nq 4: 5287 / 584 / 457   nq 5: 5645 / 994 / 594   nq 8: 6001 / 1123 / 722
-//   128 dims   10M  null sets   nq 2: 1039 / 618 / 478   nq 4: 1156 / 735 / 681   nq 5: 1263 / 869 / 901   nq 8: 1397 / 1101 / 1220
-//                   1 % each    nq 2: 575 / 513 / 380    nq 4: 1243 / 664 / 504   nq 5: 1485 / 768 / 652   nq 8: 2485 / 926 / 816
-//                   tile in ten nq 2: 1043 / 233 / 241   nq 4: 1157 / 312 / 327   nq 5: 1263 / 378 / 388   nq 8: 1397 / 498 / 515
-// LOSSES: the bfloat16 copy first lost to today's path with TWO queries over distinct 1 % sets at 3M and 10M x 768 at every k (two
-// single-query 8-bit-first scans beat one shared bfloat16 pass), and at 1M x 768 with null sets for 8 queries at every k and 5 at k = 1000,
-// where the 8-bit plane first also lost at k = 1000 with 8 queries (705 against 673); the 8-bit plane first lost to the bfloat16 copy
-// first at 10M x 128 for 5 and 8 queries over null sets and for every nq at one tile in ten, and at 1M x 768 at one tile in ten for
-// k = 65 and 1000.  Every other cell won.  The wins therefore depend on the KIND of filter (one set for all against a set per query) as
-// well as on candidate tiles, which BoundWideFilterFloor cannot express: class QB = 4 loses a cell at every measured size of 768
-// dimensions with the bfloat16 copy first.  The tables stay at zero until the rule can tell those apart; "always" reaches the form.
-// Whatever they come to hold, AUTO never takes a shape bound_wide_route_mq declines under AUTO (bound_wide_auto with the unfiltered
-// form's floor is asked first).  NOT measured: sparser filters, QV_L2 with the planes, k above 1000, other widths.
-constexpr BoundWideFilterFloor kBoundWideFilterMqFloor[2] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};    // the form against today's filtered paths, QB = 4 / QB = 8: not measured
-constexpr BoundWideFilterFloor kBoundWide8FilterMqFloor[2] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};   // ... and the 8-bit plane first against the bfloat16 copy first: not measured
-int bound_wide_route_filtered_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered_mq, bool has_plane, bool has_plane8,
-                                 uint32_t candidate_tiles, uint64_t min_candidates) {
-    static const int env_wide = env_int("QV_BOUND_SCAN_WIDE_FILTERED_MQ", 0);
-    const int mode = wide_mode ? wide_mode : env_wide;
-    if (mode == 2) return 0;
-    const uint32_t n_tiles = (uint32_t)(((uint64_t)rows + 63) / 64);
-    const bool metric_ok = rule_metric == QV_COSINE || rule_metric == QV_DOT || rule_metric == QV_RULE_L2_PLANES;
-    if (nq < 2 || nq > kBoundMqMax || k <= (uint32_t)kMaxFusedK || k > kBoundWideMaxK || !metric_ok || !has_plane) return 0;
-    if ((dim & 15u) != 0 || dim == 0 || dim > kBoundMaxDim || n_tiles < 8 || k >= rows || !flat_select_redo_one_serves(n_tiles)) return 0;
-    if ((uint64_t)nq * n_tiles * 256 > (2ull << 30)) return 0;
-    if (candidate_tiles == 0 || min_candidates <= (uint64_t)k) return 0;
-    const int cls = nq <= 4 ? 0 : 1;
-    if (mode != 1 && !bound_wide_filtered_auto(kBoundWideMqFloor[cls], kBoundWideFilterMqFloor[cls], rule_metric, dim, rows, k, candidate_tiles)) return 0;
-    const int plane = bound_plane_mode(bound_mq_filtered, plane_mode_filtered_mq);
-    if (plane == 2 || !has_plane8) return 1;
-    return plane == 1 || bound_wide_filtered_auto(kBoundWideMq8Floor[cls], kBoundWide8FilterMqFloor[cls], rule_metric, dim, rows, k, candidate_tiles) ? 2 : 1;
-}
+// ---- the wide form of the shared pass (2 - 8 queries, 65 <= k <= kBoundWideMaxK): its buffer, its launches ----
 // the wide shared pass's buffer.  The pass's flag words come first and stay: the redo reads its flags from them.  The redo's workspace
 // overlays the rest: it is written only when every bound stage and the counted selection have ended.
 struct BoundWideMqLayout {
@@ -2136,10 +2091,9 @@ static BoundWideMqLayout bound_wide_mq_layout(void* base, const ScanPlan& p, uin
 size_t bound_scan_wide_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log) { return bound_wide_mq_layout(nullptr, p, nq, k, n_tiles, dim, log).total; }
 hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                                      uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first, const RowSetRef* h_sets) {
-    // (whether the pass is TAKEN is bound_wide_route_mq's decision — bound_wide_route_filtered_mq's with h_sets; here only what the kernels need,
-    // which is the same for both: the sets add no limit of their own)
-    if (bound_wide_route_mq(rule_metric(v), v.dim, v.n_rows, nq, k, 1, plane8_first ? 1 : 2, v.plane != nullptr, v.plane8 != nullptr) != (plane8_first ? 2 : 1) || !d_ctrl || !d_stats)
-        return hipErrorInvalidValue;
+    // (whether the pass is TAKEN is bound_wide_decide's decision; here only what the kernels need, which is the same with and without h_sets:
+    // the sets add no limit of their own)
+    if (nq < 2 || !bound_wide_kernels_serve(bound_ask(v, nq, k, kBoundNoFilter), 0) || (plane8_first && !v.plane8) || !d_ctrl || !d_stats) return hipErrorInvalidValue;
     // h_sets: query j over alive & h_sets[j] — stage 1's SETS + WIDE forms and the set-carrying redo; everything between them is the unfiltered
     // form's: the per-query H_j, collect, re-score and counted selection read lower-bound words and keys, and a non-candidate of query j
     // carries 0xFFFFFFFF and a dead key in query j's plane and list alone
@@ -2149,7 +2103,7 @@ hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, cons
     const BoundWideMqLayout L = bound_wide_mq_layout(d_ws, p, nq, k, v.n_tiles, v.dim);
     const uint32_t n_pad = v.n_tiles * 64, cgrid = std::min(kBoundCollectGrid, (n_pad + kCollectChunk - 1u) / kCollectChunk);
     // keys per query: even.  More than k wherever the grid gives a wave a tile (grid x 256 >= rows > k) or has 2 workgroups per CU on 3 CUs
-    // or more (1536 keys and up; 131 072 on 256 CUs).  The rule cannot see the grid: the dispatch (wide_route_mq, qv_api.cpp) asks the same of
+    // or more (1536 keys and up; 131 072 on 256 CUs).  The rule cannot see the grid: the dispatch (wide_stages, qv_api.cpp) asks the same of
     // the plan and keeps such a call on its earlier path; a caller that comes here all the same is refused.
     const uint32_t n_keys = grid * kScanWaves * kBoundWideListLen;
     if (n_keys <= k || (n_keys & 1u)) return hipErrorInvalidValue;

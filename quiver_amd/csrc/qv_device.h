@@ -50,22 +50,16 @@ struct IndexView {
     uint16_t* plane;      // may be null: the same bfloat16 copy whenever the index keeps one — cosine and dot indexes do by default, for the
                           // single-query bound scan (qv_bound_scan.hip); `bf16` above is set only under QV_FLAG_BF16_ROWS, so the batched path's
                           // choice of kernels is what the flag alone decides.  The calls that write rows refresh `plane`.
-    int       bound_scan; // qv_index_set_bound_scan: 0 from the measured row count on, 1 whenever it applies, 2 never
     int8_t*   plane8;     // may be null: the int8 copy of the rows, [tile][dim/16][64 rows][16 values], one scale per row (k_row_state8);
                           // kept wherever `plane` is kept by default and dim is a multiple of 16 up to 4096.  Refreshed with `plane`.
     float*    rscale8;    // per row: max|r_i| / 127 rounded up (0: no scale)
     float*    rres8;      // per row: |r - rscale8 r8| rounded up; NaN = a row the 8-bit bound says nothing about
-    int       bound_plane; // qv_index_set_bound_plane: 0 the 8-bit stage from its measured row count on, 1 whenever it applies, 2 never
-    int       bound_plane_filtered; // qv_index_set_bound_plane_filtered: the same three values for a filtered single query, a knob of its own
-    int       bound_plane_mq; // qv_index_set_bound_plane_mq: the same three values for an unfiltered shared pass of 2 - 8 queries, a knob of its own
-    int       bound_plane_filtered_mq; // qv_index_set_bound_plane_filtered_mq: the same three values for a filtered shared pass of 2 - 8 queries, a knob of its own
     int       l2_planes;  // a QV_L2 index created with QV_FLAG_L2_SCAN_PLANE: bound_ask asks the rules as QV_RULE_L2_PLANES (0 on every other index)
     uint16_t* rowmaj16;   // may be null: bfloat16 copy of the rows in row order, [rows][dim] (QV_FLAG_GRAPH_PLANE: cosine / dot, rowmaj kept, dim a multiple of
                           // 64 up to 4096); element = (__bf16)x, the conversion k_row_residual measures.  Written wherever rowmaj is (k_rowmaj16)
     uint8_t*  plane6;     // may be null: the 6-bit plane, [tile][dim/64][3][64 rows][16 B] (qv_bound.h: bound6_pack), kept wherever plane8 is kept and dim is a
                           // multiple of 64 — never without plane8, whose scale it shares.  Refreshed with it (k_row_state6).
     float*    rres6;      // per row: |r - 4 rscale8 c6| rounded up; NaN = a row the 6-bit bound says nothing about
-    int       bound_plane6; // qv_index_set_bound_plane6: 0 the 6-bit stage in front of the 8-bit one from its measured shapes on, 1 whenever that one is taken, 2 never
     int8_t*   rowmaj8;    // may be null: the rows' int8 image in row order, [rows][dim] (QV_FLAG_GRAPH_PLANE8: cosine / dot, rowmaj kept, dim a multiple of 128
                           // up to 4096); the bytes bound8_scale / bound8_quant give (plane8's, where that is kept).  Written wherever rowmaj is (k_rowmaj8)
     RowMeta8* rowmeta8;   // beside it, one record per row: what a rejecting graph hop needs of the row in ONE gather
@@ -212,7 +206,8 @@ struct FlatPlan : FlatPass {        // the call's pass; mq64 with more than 32 q
 };
 // tickets / stats: the call carries the stream's ticket words / the index's bound-scan counters; candidate_tiles: kBoundNoFilter, or the
 // tiles that hold a candidate of a filtered call (an upper bound known on the host)
-FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k, bool tickets, bool stats, uint32_t candidate_tiles);
+struct BoundKnobs;
+FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k, bool tickets, bool stats, uint32_t candidate_tiles, const BoundKnobs& knobs);   // knobs: the index's (below)
 // plan_flat without an index or a device (qv_scan_route): the route's number, < 0 for arguments no route serves
 int host_flat_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int cus, int tickets, int bound_mode, int plane_mode, int has_plane, int has_plane8,
                     uint32_t candidate_tiles, int plane_mode_filtered);
@@ -247,13 +242,14 @@ struct BoundKnobs {               // host only.  0: the environment variable dec
     int plane[4];                 // by BoundForm: qv_index_set_bound_plane, _filtered, _mq, _filtered_mq / QV_BOUND_PLANE, _FILTERED, _MQ, _FILTERED_MQ:
                                   // 1 the 8-bit stage first whenever the bound scan takes the call and the plane is held, 2 never
     int plane6 = 0;               // qv_index_set_bound_plane6 / QV_BOUND_PLANE6 (one unfiltered query only): 1 the 6-bit stage first whenever the 8-bit stage would be and the plane is held, 2 never
+    int wide[4] = {0, 0, 0, 0};   // by BoundForm: qv_index_set_bound_scan_wide, _filtered, _mq, _filtered_mq / QV_BOUND_SCAN_WIDE, _FILTERED, _MQ, _FILTERED_MQ: the WIDE
+                                  // form's mode (65 <= k <= kBoundWideMaxK; bound_wide_decide), 1 whenever the kernels serve the call, 2 never — `scan` says nothing there
 };
 enum class BoundStages { none, bf16, plane8_first, plane6_first };   // plane6_first: plane8_first with the 6-bit stage in front (bound_one only)
 inline bool bound_stages_8bit(BoundStages s) { return s == BoundStages::plane8_first || s == BoundStages::plane6_first; }
 BoundStages bound_scan_decide(const BoundAsk& a, const BoundKnobs& knobs);
 bool bound_scan_kernels_serve(const BoundAsk& a);   // the kernels' own limits: metric, k, 1 - 8 queries, the copy, whole 16-dimension steps, 8 tiles, lower bounds under 2 GiB
 BoundAsk bound_ask(const IndexView& v, uint32_t nq, uint32_t k, uint32_t candidate_tiles);
-BoundKnobs bound_knobs(const IndexView& v);
 int bound_scan_mode(int mode);   // the mode in force: the index's own, else QV_BOUND_SCAN (read once)
 // The single-query scan on the bfloat16 copy (qv_bound_scan.hip): stage 1 streams v.plane and lists the rows whose certified lower bound of
 // the distance is within the k-th smallest upper bound, stage 2 computes those rows' distances in the scan's own arithmetic and writes
@@ -283,19 +279,18 @@ int host_unpack_row6(uint32_t dim, const uint8_t* bytes, uint8_t* out_codes);
 // The WIDE form of the single-query bound scan, unfiltered or over a candidate bitmap, 65 <= k <= kBoundWideMaxK (qv_bound_scan.hip): stage 1 publishes every wave's 64
 // smallest upper bounds, H is the k-th smallest key of their union (launch_select_topk), the collect has a list of QV_BOUND_WIDE_CAND_CAP rows,
 // the re-score writes a key per survivor and launch_select_topk_counted takes the k best.  A search it cannot decide is redone by the
-// key-per-row path behind a device word (launch_flat_select_redo_one).  Whether a search takes it is bound_wide_route's answer — a knob of its
-// own (qv_index_set_bound_scan_wide / QV_BOUND_SCAN_WIDE), independent of bound_scan_decide, which keeps saying no above kMaxFusedK.
+// key-per-row path behind a device word (launch_flat_select_redo_one).
+// Whether a call takes a wide form — this one or the shared pass's below, unfiltered or filtered — and on which plane it starts is ONE decision,
+// bound_wide_decide, as bound_scan_decide is for k <= kMaxFusedK (which keeps saying none above it): none, bf16 or plane8_first.  The form
+// follows from bound_form(a); each form has a knob of its own (BoundKnobs::wide) and its own plane knob (BoundKnobs::plane), independent of the
+// others and of BoundKnobs::scan.  min_candidates (a filtered ask; ignored otherwise): the smallest live candidate count among the ask's
+// queries, as the host counts them — a filtered form needs more candidates than results for every query.  The dispatch (qv_api.cpp:
+// wide_stages) asks once per call or piece; the qv_scan_bound_wide_route* exports are views of it; the launchers only check what their
+// kernels need (bound_wide_kernels_serve).
 constexpr uint32_t kBoundWideMaxK = 1024;
 constexpr uint32_t kBoundWideStatsWord = 10;   // the wide form's counters: [10] survivors passed to the re-score, [11] hand-backs to the exact path, [12] searches
-// 0: no wide form; 1: the bfloat16 copy first; 2: the 8-bit plane first.  wide_mode: QV_BOUND_SCAN_* (0: QV_BOUND_SCAN_WIDE of the environment,
-// read once, else automatic); plane_mode: the index's qv_index_set_bound_plane (0: QV_BOUND_PLANE, else automatic)
-int bound_wide_route(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode, bool has_plane, bool has_plane8);
-// The same question for ONE query over a candidate bitmap (a mask, a row set, a where-filter made into a set).  wide_mode: the filtered form's own
-// knob (qv_index_set_bound_scan_wide_filtered; 0: QV_BOUND_SCAN_WIDE_FILTERED, else automatic); plane_mode_filtered: the single-query filtered
-// plane knob (qv_index_set_bound_plane_filtered); candidate_tiles: the tiles that hold a candidate, as the host knows them; candidates: the live
-// rows the filter selects — the form needs more of them than results.
-int bound_wide_route_filtered(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered, bool has_plane, bool has_plane8,
-                              uint32_t candidate_tiles, uint64_t candidates);
+BoundStages bound_wide_decide(const BoundAsk& a, uint64_t min_candidates, const BoundKnobs& knobs);
+bool bound_wide_kernels_serve(const BoundAsk& a, uint64_t min_candidates);
 size_t bound_scan_wide_workspace_bytes(const ScanPlan& p, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr);
 // d_ctrl: the stream's control words (2 BoundCtrl, kept zero but for the bfloat16 stage's flag, which every search writes before it is read);
 // d_stats: the index's counters.  Enqueues everything, the gated exact redo included: nothing is read on the host.
@@ -306,13 +301,9 @@ hipError_t launch_bound_scan_wide(const IndexView& v, const ScanPlan& p, const f
 // kernels with a list length of 64 publish every wave's list of every query, H_j is the k-th smallest of query j's published keys (one
 // launch_select_topk over the nq arrays), the collect and the wave-per-survivor re-score run per query (grid y = query), one
 // launch_select_topk_counted ends the pass, and launch_flat_select_redo behind it redoes, alone, the queries no stage could decide.  Whether a pass
-// takes it is bound_wide_route_mq's answer — a knob of its own (qv_index_set_bound_scan_wide_mq / QV_BOUND_SCAN_WIDE_MQ), independent of
-// bound_wide_route (which keeps answering 0 for nq != 1) and of bound_scan_decide; the plane it starts on is the shared pass's plane knob
-// (qv_index_set_bound_plane_mq / QV_BOUND_PLANE_MQ).
+// takes it is bound_wide_decide's answer (above).  The filtered pass — each query over its own alive & set (row sets, null sets, the counted
+// sets of a where search) or all over one bitmap — is the same launcher with h_sets and the same counters.
 constexpr uint32_t kBoundWideMqStatsWord = 13;   // its counters: [13] the largest survivor count of the last pass (each query in the stage that answered it), [14] queries handed back to the key-per-row path, [15] queries
-// 0: no wide shared pass; 1: the bfloat16 copy first; 2: the 8-bit plane first.  wide_mq_mode: QV_BOUND_SCAN_* (0: QV_BOUND_SCAN_WIDE_MQ of the
-// environment, read once, else automatic); plane_mode_mq: the index's qv_index_set_bound_plane_mq (0: QV_BOUND_PLANE_MQ, else automatic)
-int bound_wide_route_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mq_mode, int plane_mode_mq, bool has_plane, bool has_plane8);
 size_t bound_scan_wide_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32_t k, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr);
 // d_ctrl: the stream's control words (kBoundMqMax BoundCtrl of which this form uses thr_inv, cand_cnt and ticket: zero on entry, left zero on
 // every exit, hand-backs included); d_stats: the index's counters.  Enqueues everything, the flagged key-per-row redo included: nothing is read on the host.
@@ -322,14 +313,6 @@ size_t bound_scan_wide_mq_workspace_bytes(const ScanPlan& p, uint32_t nq, uint32
 // a liveness word), and a handed-back query is redone over its own set (launch_flat_select_redo with the sets).  The same workspace.
 hipError_t launch_bound_scan_wide_mq(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws, uint32_t* d_ctrl, uint32_t* d_stats,
                                      uint32_t* d_rows_out, float* d_dist_out, hipStream_t s, bool plane8_first, const RowSetRef* h_sets = nullptr);
-// The FILTERED wide shared pass's rule: 2 - 8 queries at 65 <= k <= kBoundWideMaxK, each over its own alive & set (row sets, null sets, the counted
-// sets of a where search) or all over one bitmap.  A knob of its own (qv_index_set_bound_scan_wide_filtered_mq / QV_BOUND_SCAN_WIDE_FILTERED_MQ),
-// independent of the three other wide knobs, which keep answering as they do; the plane is the filtered shared pass's plane knob
-// (qv_index_set_bound_plane_filtered_mq).  candidate_tiles: the tiles that hold a candidate of any query of the piece, as the host knows them;
-// min_candidates: the smallest live candidate count among the piece's queries — the form needs more than k of them for EVERY query.
-// 0 no, 1 the bfloat16 copy first, 2 the 8-bit plane first.  The counters are the wide shared pass's (kBoundWideMqStatsWord).
-int bound_wide_route_filtered_mq(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32_t k, int wide_mode, int plane_mode_filtered_mq, bool has_plane, bool has_plane8,
-                                 uint32_t candidate_tiles, uint64_t min_candidates);
 constexpr uint32_t kBound6StatsWord = 7;   // the 6-bit stage's counters: [7] candidates it passed to the refine, [8] hand-backs, [9] searches
 constexpr uint32_t kBound6CandCap = 262144;   // rows the refine walks on the 8-bit plane (1 MiB of the workspace)
 constexpr uint32_t kBound8StatsWord = 4;   // the 8-bit stage's counters in the index's counter words: [4] survivors, [5] hand-backs, [6] searches

@@ -1080,18 +1080,18 @@ static FlatPass plan_shared_pass(const IndexView& v, const ScanPlan& p, uint32_t
     const int qb = mq_qb_forced() ? (f32_acc && mq_qb_forced() == 16 ? 8 : mq_qb_forced()) : (n >= 9 ? (f32_acc ? 8 : 16) : (n >= 5 ? 8 : 4));
     return {FlatRoute::mq, (uint32_t)qb};
 }
-FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k, bool tickets, bool stats, uint32_t candidate_tiles) {
+FlatPlan plan_flat(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k, bool tickets, bool stats, uint32_t candidate_tiles, const BoundKnobs& knobs) {
     FlatPlan f;
     f.filtered = candidate_tiles != kBoundNoFilter;                  // v.alive is a filter's candidate bitmap: one for all queries of the call
     // QV_SCAN_FUSE=0 keeps the two launches of a single query, for measurements
     static const int fuse = dev_env_int("QV_SCAN_FUSE", 1);
-    const BoundStages stages = tickets && stats ? bound_scan_decide(bound_ask(v, nq, k, candidate_tiles), bound_knobs(v)) : BoundStages::none;
+    const BoundStages stages = tickets && stats ? bound_scan_decide(bound_ask(v, nq, k, candidate_tiles), knobs) : BoundStages::none;
     const bool bound_takes = stages != BoundStages::none;
     // 1. a small collection: scan + merge in one launch
     if (!bound_takes && tickets && flat_small_applies(v, nq, k) && !flat_split_applies(v, nq, k)) { f.route = FlatRoute::small; return f; }
     if ((int)nq >= mq_min_queries()) {
         // 2. 2 - 8 queries sharing one pass over the bfloat16 copy (forced on, it goes ahead of the short-corpus form; on its own it leaves that form its shapes)
-        if (nq >= 2 && bound_takes && (bound_scan_mode(v.bound_scan) == 1 || !flat_split_mq_applies(v, nq, k))) {
+        if (nq >= 2 && bound_takes && (bound_scan_mode(knobs.scan) == 1 || !flat_split_mq_applies(v, nq, k))) {
             f.route = FlatRoute::bound_mq; f.qb = nq <= 4 ? 4u : 8u; f.plane8_first = bound_stages_8bit(stages);
             return f;
         }
@@ -1128,12 +1128,12 @@ int host_flat_route(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint32
     IndexView v = {};
     v.l2_planes = l2_planes ? 1 : 0;
     v.dim = dim; v.dim4 = (dim + 3) / 4; v.n_rows = rows; v.n_tiles = (rows + 63) / 64; v.metric = metric;
-    v.bound_scan = bound_mode; v.bound_plane = plane_mode; v.bound_plane_filtered = plane_mode_filtered;
-    v.bound_plane_mq = QV_BOUND_PLANE_BF16; v.bound_plane_filtered_mq = QV_BOUND_PLANE_BF16;   // (the shared pass's plane is a decision inside route 1: no route depends on it)
+    // (the shared pass's plane is a decision inside route 1: no route depends on it)
+    const BoundKnobs knobs = {bound_mode, {plane_mode, plane_mode_filtered, QV_BOUND_PLANE_BF16, QV_BOUND_PLANE_BF16}};
     static uint16_t a_plane; static int8_t a_plane8;                   // (the rules ask whether a copy is held, never what it holds)
     if (has_plane) v.plane = &a_plane;
     if (has_plane8) v.plane8 = &a_plane8;
-    return (int)plan_flat(v, plan_scan(v.n_tiles, cus), nq, k, tickets != 0, tickets != 0, candidate_tiles).route;
+    return (int)plan_flat(v, plan_scan(v.n_tiles, cus), nq, k, tickets != 0, tickets != 0, candidate_tiles, knobs).route;
 }
 
 // QV_TRACE=1: name the scan kernel chosen, on stderr (the unfiltered lines: one read per process; the filtered ones: trace_filtered)
@@ -1366,7 +1366,7 @@ hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const FlatPla
 }
 hipError_t launch_flat_topk(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k,
                             void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s) {
-    return launch_flat_topk(v, p, plan_flat(v, p, nq, k, false, false, kBoundNoFilter), d_queries, nq, k, d_ws, d_rows_out, d_dist_out, s);
+    return launch_flat_topk(v, p, plan_flat(v, p, nq, k, false, false, kBoundNoFilter, BoundKnobs{}), d_queries, nq, k, d_ws, d_rows_out, d_dist_out, s);
 }
 
 
