@@ -437,7 +437,34 @@ int qv_index_search_batched(qv_index* idx, const float* queries, uint32_t nq, ui
 #define QV_FILTER_BF16X3    2
 #define QV_FILTER_BF16X1    3
 #define QV_FILTER_OFF       4   /* no filter: every batch of this index takes the exact scans (what tests of those scans choose) */
+#define QV_FILTER_INT8      5   /* the int8 matrix-core filter on the index's 8-bit plane, where it applies (below); QV_FILTER_AUTO's kernels elsewhere */
 int qv_index_set_filter(qv_index* idx, int filter);
+
+/* ---- QV_FILTER_INT8: the batched filter on the 8-bit plane ----
+ * A cosine or dot index keeps by default an int8 image of its rows (a quarter of their bytes; QV_FLAG_NO_SCAN_PLANE drops it).  Under
+ * QV_FILTER_INT8 an unfiltered batch streams that plane through v_mfma_i32_32x32x32_i8 instead of the float32 rows: the query is quantised
+ * into two int8 terms, the integer score is exact, and a row is kept whenever its score is within ea |r| + eb rres8(row) of the query's
+ * threshold — the 8-bit bound scan's interval (qv_scan_bound_interval8) plus the float32 roundings of the kernel's epilogue.  The exact
+ * re-score decides as ever, so rows, float32 bits, order, counts and padding are what every other filter returns.
+ * The kernel runs only where ALL of these hold: the metric is QV_COSINE or QV_DOT; the index holds the 8-bit plane; the dimension is a
+ * multiple of 32 from 64 to 1024; the batched path itself takes the batch; the batch carries no row sets or where-filters.  Everywhere else
+ * (QV_L2 with or without QV_FLAG_L2_SCAN_PLANE, QV_FLAG_NO_SCAN_PLANE, other dimensions, filtered batches — their kernels are what
+ * qv_batched_filter_route reports for QV_FILTER_AUTO; that export and qv_batched_applies_filtered* keep taking 0 .. 4 only) the batch runs exactly
+ * as under QV_FILTER_AUTO.
+ * QV_FILTER_AUTO never chooses this kernel.
+ * A query the bound declines (a norm that is NaN, huge or vanishing, no scale) is handed back through its redo flag, as an overflowing one is.
+ *
+ * qv_index_int8_filter_stats: out[0] = batches whose main filter was the int8 kernel, out[1] = their queries, out[2] = those of them handed
+ * back, out[3] = 1 when the index holds the 8-bit plane.  Waits for the device; a batch counts once its kernels have run.
+ * qv_batched_int8_applies: the dispatch's own rule without an index or a device — 1 when an unfiltered batch of nq queries, k results, over
+ * `rows` rows of `dim` dimensions takes the int8 kernel under `filter`, else 0.
+ * qv_batched_int8_keeps: the kernel's keep/drop decision compiled for the host — isum_hi / isum_lo = the two integer chains, sq / qn / qres the
+ * query's scale, norm and residual as the 8-bit bound scan computes them, U the query's bound, rn / rscale8 / rres8 the row's state.  1 keep,
+ * 0 drop; QV_ERR_INVALID_ARG for a metric the filter does not serve.  Whenever qv_scan_bound_interval8's d_lo <= U it answers 1. */
+int qv_index_int8_filter_stats(qv_index* idx, uint64_t out[4]);
+int qv_batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_plane8);
+int qv_batched_int8_keeps(int metric, uint32_t dim, int32_t isum_hi, int32_t isum_lo, double sq, double qn, double qres, float U, double rn,
+                          float rscale8, float rres8);
 
 /* ---- filtered batches: 9 or more queries, a filter per query, on the batched path ----
  * A call — or a pass that concurrent callers share — of 9 or more queries, k <= 64, through qv_index_search_rowsets or

@@ -244,7 +244,7 @@ int qv_index_create(qv_index** out, uint32_t dim, qv_metric metric, int device, 
     if (!idx) return fail(QV_ERR_OOM, "out of host memory");
     idx->device = device; idx->cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
     idx->dim = dim; idx->dim4 = (dim + 3) / 4; idx->metric = (int)metric; idx->flags = flags;
-    if (hipMalloc(reinterpret_cast<void**>(&idx->d_bound_stats), 64) != hipSuccess || hipMemset(idx->d_bound_stats, 0, 64) != hipSuccess ||
+    if (hipMalloc(reinterpret_cast<void**>(&idx->d_bound_stats), qv::kIndexStatsWords * sizeof(uint32_t)) != hipSuccess || hipMemset(idx->d_bound_stats, 0, qv::kIndexStatsWords * sizeof(uint32_t)) != hipSuccess ||
         hipStreamSynchronize(nullptr) != hipSuccess) {
         (void)hipFree(idx->d_bound_stats); delete idx;
         return fail(QV_ERR_OOM, "device allocation of the index's counters failed");
@@ -1935,7 +1935,7 @@ static int batched_device_pass(qv_index* idx, const float* d_queries, uint32_t n
     if (rc != QV_OK) return rc;
     const ProfilePair pp = profile_begin(idx);
     uint32_t* d_ovf = nullptr;
-    hipError_t e = qv::launch_batched(v, plan, d_queries, nq, k, ws, d_rows_out, d_dist_out, &d_ovf, idx->cus, s, pp.ev0, pp.ev1);
+    hipError_t e = qv::launch_batched(v, plan, d_queries, nq, k, ws, d_rows_out, d_dist_out, &d_ovf, idx->cus, s, pp.ev0, pp.ev1, nullptr, idx->d_bound_stats);
     profile_end(idx, pp, e == hipSuccess);
     if (e != hipSuccess) return fail(QV_ERR_DEVICE, "batched launch failed: %s", hipGetErrorString(e));
     HIPCHK(hipMemcpyAsync(d_redo_flags_out, d_ovf, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
@@ -1983,7 +1983,7 @@ static int batched_pass(qv_index* idx, const float* queries, uint32_t nq, uint32
         if ((rc = hc.send(nq))) return rc;
         uint32_t* d_ovf = nullptr;
         const ProfilePair pp = profile_begin(idx);
-        hipError_t e = qv::launch_batched(v, plan, hc.d_queries(), nq, kk, hc.ws(), hc.d_rows(), hc.d_dist(), &d_ovf, idx->cus, hc.stream(), pp.ev0, pp.ev1);
+        hipError_t e = qv::launch_batched(v, plan, hc.d_queries(), nq, kk, hc.ws(), hc.d_rows(), hc.d_dist(), &d_ovf, idx->cus, hc.stream(), pp.ev0, pp.ev1, nullptr, idx->d_bound_stats);
         profile_end(idx, pp, e == hipSuccess);
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "batched launch failed: %s", hipGetErrorString(e));
         if ((rc = hc.fetch(nq, kk))) return rc;
@@ -2042,7 +2042,8 @@ int qv_merge_topk_shards_device(const uint32_t* d_packed_lists, const uint32_t* 
 
 int qv_index_set_filter(qv_index* idx, int filter) {
     if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
-    if (filter < 0 || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be 0 (automatic), 1 (fp32 MFMA), 2 (bfloat16 x 3), 3 (bfloat16 x 1) or 4 (off); got %d", filter);
+    if (filter < 0 || filter > QV_FILTER_INT8)
+        return fail(QV_ERR_INVALID_ARG, "filter must be 0 (automatic), 1 (fp32 MFMA), 2 (bfloat16 x 3), 3 (bfloat16 x 1), 4 (off) or 5 (int8 on the 8-bit plane); got %d", filter);
     idx->filter = filter;
     return QV_OK;
 }
@@ -2102,7 +2103,7 @@ int qv_index_set_filtered_batch_wide(qv_index* idx, int mode) {
 
 int qv_batched_applies_filtered_wide(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse) {
     if (mode < 0 || mode > QV_FILTERED_BATCH_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
+    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);   // (QV_FILTER_INT8: a filtered batch runs as under QV_FILTER_AUTO — ask with that)
     return qv::filtered_batch_wide_rule(metric, dim, rows, nq, k, filter, mode, std::min(n_not_sparse, nq)) ? 1 : 0;
 }
 
@@ -2114,13 +2115,14 @@ int qv_index_filtered_batch_stats(qv_index* idx, uint64_t out[4]) {
 
 int qv_batched_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int mode, uint32_t n_not_sparse) {
     if (mode < 0 || mode > QV_FILTERED_BATCH_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
-    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
+    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);   // (QV_FILTER_INT8: as above)
     return qv::filtered_batch_rule(metric, dim, rows, nq, k, filter, mode, std::min(n_not_sparse, nq)) ? 1 : 0;
 }
 
 int qv_batched_filter_route(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_bf16_plane, int cus, uint32_t* nq_pad, int* kernel) {
     if (!nq_pad || !kernel) return fail(QV_ERR_INVALID_ARG, "nq_pad/kernel is null");
-    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
+    // (QV_FILTER_INT8 is not a filter of a FILTERED batch — such a batch runs as under QV_FILTER_AUTO: ask with that)
+    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_OFF) return fail(QV_ERR_INVALID_ARG, "filter must be QV_FILTER_AUTO .. QV_FILTER_OFF; got %d", filter);
     if (cus < 1) return fail(QV_ERR_INVALID_ARG, "cus must be positive; got %d", cus);
     if (!qv::batched_sets_filter(metric, dim, rows, nq, k, filter, has_bf16_plane != 0, cus, nq_pad, kernel))
         return fail(QV_ERR_UNSUPPORTED, "no filtered batched route for %u queries, k %u over %llu rows of %u dimensions", nq, k, (unsigned long long)rows, dim);
@@ -2142,6 +2144,27 @@ int qv_index_bound_scan8_stats(qv_index* idx, uint64_t out[4]) {
     HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kBound8StatsWord, sizeof(h), hipMemcpyDeviceToHost));
     out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = idx->d_plane8 != nullptr ? 1 : 0;
     return QV_OK;
+}
+
+int qv_index_int8_filter_stats(qv_index* idx, uint64_t out[4]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t h[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kInt8FilterStatsWord, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = idx->d_plane8 != nullptr ? 1 : 0;
+    return QV_OK;
+}
+
+int qv_batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_plane8) {
+    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_INT8) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
+    return qv::batched_int8_applies(metric, dim, rows, nq, k, filter, has_plane8 != 0) ? 1 : 0;
+}
+
+int qv_batched_int8_keeps(int metric, uint32_t dim, int32_t isum_hi, int32_t isum_lo, double sq, double qn, double qres, float U, double rn,
+                          float rscale8, float rres8) {
+    const int got = qv::host_int8_filter_keeps(metric, dim, isum_hi, isum_lo, sq, qn, qres, U, rn, rscale8, rres8);
+    return got < 0 ? fail(QV_ERR_INVALID_ARG, "the int8 filter serves QV_COSINE and QV_DOT; got metric %d", metric) : got;
 }
 
 int qv_index_bound_scan6_stats(qv_index* idx, uint64_t out[4]) {

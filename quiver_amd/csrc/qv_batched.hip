@@ -2,6 +2,7 @@
 // (shared helpers, the arithmetic contract and the build flags: qv_kernels.h)
 #include <numeric>
 #include "qv_filter.h"
+#include "qv_bound.h"
 
 namespace qv {
 
@@ -40,7 +41,47 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
         *reinterpret_cast<const RowSetRef**>(cand_cnt - kCandHeadWords) = sets;   // the batch's row sets, for cand_flush (null: unfiltered)
     }
     const uint32_t dim4p = (dim4 + 1) & ~1u;           // chunk count padded to even: the MFMA step eats two chunks
-    if (!(what & 1)) {
+    // the int8 filter (bf16x3 == 3: qv_int8.hip): the query quantised as k_bound_scan8 quantises its own (bound8_split_query), its two int8
+    // operand planes in the order k_int8_filter copies them into LDS — Q8[((qb64 * steps + s) * 4 + 2 * {hi, lo} + query half) * 64 + lane] x 16 bytes,
+    // lane 32 h + j holding dimensions 32 s + 16 h .. + 15 of query 64 qb64 + 32 half + j (a step is 32 dimensions: chunks 2 s and 2 s + 1 of the plane) —
+    // and sq as float32 behind them.  The block is one wave; dim / 16 <= 64 chunks, one per lane.
+    double i8_sq = 1.0, i8_qres = __builtin_nan(""), i8_qn = 0.0;
+    if (bf16x3 == 3) {
+        const uint32_t lane = threadIdx.x;
+        float mx = 0.f; bool bad = false;
+        if (q < nq) for (uint32_t i = lane; i < dim; i += 64) { const float x = queries[(size_t)q * dim + i]; bad |= !((x - x) == 0.0f); mx = __builtin_fmaxf(mx, __builtin_fabsf(x)); }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) mx = __builtin_fmaxf(mx, __shfl_xor(mx, m));
+        const bool q_ok = q < nq && __ballot(bad) == 0ull && mx > 0.0f;
+        i8_sq = q_ok ? (double)mx / (double)kBound8QueryMax : 1.0;
+        double r2 = 0.0;
+        if (lane < dim / 16) {
+            uint32_t hw[4] = {0u, 0u, 0u, 0u}, lw[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+                const double x = q_ok ? (double)queries[(size_t)q * dim + 16 * lane + e] : 0.0;
+                int hi, lo;
+                const double d = bound8_split_query(x, i8_sq, hi, lo);
+                r2 = __builtin_fma(d, d, r2);
+                hw[e >> 2] |= ((uint32_t)hi & 255u) << (8 * (e & 3)); lw[e >> 2] |= ((uint32_t)lo & 255u) << (8 * (e & 3));
+            }
+            if (what & 1) {
+                uint4* Q8 = reinterpret_cast<uint4*>(Qt);
+                const size_t base = (((size_t)(q >> 6) * (dim / 32) + (lane >> 1)) * 4 + ((q >> 5) & 1u)) * 64 + 32 * (lane & 1u) + (q & 31u);
+                Q8[base] = make_uint4(hw[0], hw[1], hw[2], hw[3]); Q8[base + 128] = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+            }
+        }
+        r2 = wave_sum_f64(r2);
+        // |q| as the reference's chain (distances.go:20): 64 values per request, walked in order
+        for (uint32_t b = 0; b < dim && q < nq; b += 64) {
+            const float x = b + lane < dim ? queries[(size_t)q * dim + b + lane] : 0.f;
+            const uint32_t n = dim - b < 64u ? dim - b : 64u;
+            for (uint32_t j = 0; j < n; j++) { const double a = (double)__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), j)); i8_qn = __builtin_fma(a, a, i8_qn); }
+        }
+        i8_qn = __builtin_sqrt(i8_qn);
+        if (q_ok) i8_qres = __builtin_sqrt(r2) * (1.0 + 1e-9) + 1e-300;
+    }
+    if (!(what & 1) || bf16x3 == 3) {
     } else if (bf16x3) {
         // Qbf[(qb32 * steps + s) * 2 + {hi, lo}][64 lanes] x 16 bytes: lane 32h + j holds dims 16s + 8h .. +7 of query 32 qb32 + j
         const uint32_t steps = steps_pad ? steps_pad : (dim4 + 3) / 4;
@@ -160,7 +201,7 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
     __syncthreads();
     if (threadIdx.x == 0 && (what & 2)) {
         float c_ = __uint_as_float(0x7F800000u), m_ = 0.f, b_ = 0.f;       // padded queries: +inf threshold, nothing passes
-        float ea_ = 0.f, eb_ = 0.f;
+        float ea_ = 0.f, eb_ = 0.f, sq32 = 0.f;
         bool given_up = false;
         if (q < nq) {
             const double qn = __builtin_sqrt(n2);
@@ -212,7 +253,13 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
             // do: such a query then lost the rows whose score was -inf.  It is handed back HERE, with the padded queries' constants.
             given_up = qn < (double)filter_tiny_norm(dim) || !(qn < 1.0e18);
             if (given_up) { c_ = __uint_as_float(0x7F800000u); m_ = 0.f; b_ = 0.f; }
+            if (bf16x3 == 3) {
+                // the int8 filter's constants (qv_bound.h: the derivation beside the 8-bit proof); a query its bound declines is handed back here too
+                const Int8QueryConsts kc = metric == QV_COSINE ? int8_filter_query_consts<QV_COSINE>(dim, i8_sq, i8_qn, i8_qres, U) : int8_filter_query_consts<QV_DOT>(dim, i8_sq, i8_qn, i8_qres, U);
+                c_ = kc.c; m_ = kc.m; b_ = kc.b; ea_ = kc.ea; eb_ = kc.eb; given_up = kc.declined; sq32 = kc.sq32;
+            }
         }
+        if (bf16x3 == 3) reinterpret_cast<float*>(reinterpret_cast<char*>(Qt) + (size_t)nq_pad * 2 * dim)[q] = sq32;
         cq[q] = c_; mq[q] = m_; mq[nq_pad + q] = b_;
         eq[2 * q] = ea_; eq[2 * q + 1] = eb_;
         if (q < nq) { cand_cnt[q] = 0; overflow[q] = given_up ? 1u : 0u; }
@@ -2413,6 +2460,7 @@ enum class MainFilter {
     w8x2, w8x2_padded,      // k_bf16x1_filter_w8x2<., 4, 4>, <., 4, 4, true>
     qreg,                   // launch_qreg_filter (qv_qreg.hip)
     q64_plane, q64_f32_rows,   // k_bf16rows_filter_q64<., 4, 4>, <., 2, 4, true>
+    int8_plane,             // launch_int8_filter (qv_int8.hip): never plan_batched's choice — batched_int8_adapt's, for an index under QV_FILTER_INT8
 #ifdef QV_VARIANTS
     mfma_f32_nj2,           // k_mfma_filter<., 2>
     one_term_4w,            // k_bf16x3_filter_shared<., 1, 8>
@@ -2711,6 +2759,19 @@ static void batched_sets_adapt(BatchedRoute& r) {
     if (r.bfrows) { r.filter = MainFilter::bf16rows; r.filter_grid = grid_multiple(2 * (uint32_t)r.cus, nqb64 / 4); }
     else r.filter = MainFilter::w8x2;
 }
+// The int8 filter (QV_FILTER_INT8): the rule, and what it changes in plan_batched's route — the main filter and the operands k_mfma_prep lays out
+// for it (its mode 3, after the sample stage has read the bfloat16 ones); the sample stage, nq_pad, the candidate slots, the exact stage and every
+// workspace size stay plan_batched's (the operand planes take 2 dim bytes per padded query of a region that holds 4 dim + 576).
+static bool int8_shape(int metric, uint32_t dim, int filter, bool has_plane8) {
+    return filter == QV_FILTER_INT8 && (metric == QV_COSINE || metric == QV_DOT) && has_plane8 && (dim & 31u) == 0 && dim >= 64 && dim <= 1024;
+}
+static void batched_int8_adapt(BatchedRoute& r, const IndexView& v) {
+    const uint32_t blocks = (r.nq + 63) / 64;                         // (the 64-query blocks that hold a real query: the others leave at once)
+    r.filter = MainFilter::int8_plane; r.bfrows = false;
+    r.filter_grid = std::max(1u, (uint32_t)r.cus / blocks);
+    r.filter_lds = int8_filter_lds_bytes(v.dim);
+    r.gmode = 3; r.prep_what = 3; r.prep_steps = 0u;
+}
 // an index's shape as the rules that take no index see it (filtered_batch_rule, batched_sets_filter); plane: it keeps the bfloat16 copy the
 // batched filter reads (QV_FLAG_BF16_ROWS) — the plan asks only whether there is one, so the view carries a marker that nothing reads through
 static IndexView shape_view(int metric, uint32_t dim, uint64_t rows, int filter, bool plane = false) {
@@ -2719,6 +2780,10 @@ static IndexView shape_view(int metric, uint32_t dim, uint64_t rows, int filter,
     v.metric = metric; v.dim = dim; v.dim4 = (dim + 3) / 4; v.n_rows = (uint32_t)rows; v.n_tiles = (uint32_t)((rows + 63) / 64); v.filter = filter;
     v.bf16 = plane ? &plane_marker : nullptr;
     return v;
+}
+bool batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8) {
+    if (rows == 0 || rows > 0xFFFFFFFFull || !int8_shape(metric, dim, filter, has_plane8)) return false;
+    return k >= 1 && batched_supported(shape_view(metric, dim, rows, filter), nq, k);
 }
 bool batched_sets_wide_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus) {
     BatchedRoute r;
@@ -2871,6 +2936,7 @@ static void batched_prep(const IndexView& v, const BatchedRoute& r, const Batche
 static hipError_t batched_filter(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, hipStream_t s, bool sets = false) {
     const uint4* Qbf = reinterpret_cast<const uint4*>(L.Qt);
     if (r.filter == MainFilter::qreg) return sets ? hipErrorNotSupported : launch_qreg_filter(v, Qbf, L.cq, L.mq, r.nq_pad, L.cand, L.cscore, L.cnt, r.bfrows, r.cus, s);
+    if (r.filter == MainFilter::int8_plane) return sets ? hipErrorNotSupported : launch_int8_filter(v, L.Qt, L.cq, L.mq, r.nq, r.nq_pad, L.cand, L.cscore, L.cnt, r.filter_grid, r.filter_lds, s);
     // every filter kernel takes the same arguments (the operands as float32 or bfloat16 planes), some a sample's after them
     auto go = [&](auto kernel, auto* Q, uint32_t block, auto... sample_args) {
         const hipError_t e = set_lds(kernel, r.filter_lds); if (e != hipSuccess) return e;
@@ -2978,10 +3044,16 @@ static hipError_t batched_exact(const IndexView& v, const BatchedRoute& r, const
 
 hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws,
                           uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
-                          hipEvent_t ev0, hipEvent_t ev1, const BatchedSets* sets) {
+                          hipEvent_t ev0, hipEvent_t ev1, const BatchedSets* sets, uint32_t* d_stats) {
     BatchedRoute r;
     if (!plan_batched(v, nq, k, cus, (reinterpret_cast<uintptr_t>(d_queries) & 15u) == 0, r)) return hipErrorNotSupported;
     const RowSetRef* d_sets = sets ? sets->d_sets : nullptr;
+    // the int8 filter, decided once: an unfiltered batch of an index that asks for it and holds the plane.  Behind it a candidate's interval is
+    // eq[0] |r| + eq[1] rres8(row): the exact stage reads its residuals through a view whose array is the 8-bit plane's.
+    const bool int8 = !d_sets && int8_shape(v.metric, v.dim, v.filter, v.plane8 != nullptr && v.rscale8 != nullptr && v.rres8 != nullptr);
+    if (int8) batched_int8_adapt(r, v);
+    IndexView vx = v;
+    if (int8) vx.rres = v.rres8;
     if (d_sets && !batched_sets_route(r)) return hipErrorNotSupported;   // (a missing route is an error, never an unfiltered answer)
     if (d_sets) batched_sets_adapt(r);
     const BatchedLayout L = batched_layout(d_ws, v, p, r);
@@ -3001,8 +3073,9 @@ hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_
     e = batched_filter(v, r, L, s, d_sets != nullptr);
     if (e != hipSuccess) return e;
     if (ev1) (void)hipEventRecord(ev1, s);
-    e = batched_exact(v, r, L, d_queries, d_rows_out, d_dist_out, s);
+    e = batched_exact(vx, r, L, d_queries, d_rows_out, d_dist_out, s);
     if (e != hipSuccess) return e;
+    if (int8 && d_stats) { e = launch_int8_filter_count(L.ovf, nq, d_stats, s); if (e != hipSuccess) return e; }
     *d_overflow_out = L.ovf;
     return hipGetLastError();
 }

@@ -169,4 +169,75 @@ __host__ __device__ __forceinline__ bool bound_scan_interval8(long long isum, do
     return true;
 }
 
+// one element of the query's quantisation, for every kernel that quantises a query (bound8_stage_query, k_bound_prep8_mq, k_mfma_prep's
+// int8 mode): qq = rint(x / sq) = 128 hi + lo with |hi| <= 127, |lo| <= 64 (exact); returns x - sq qq, the element's part of qres
+__host__ __device__ static inline double bound8_split_query(double x, double sq, int& hi, int& lo) {
+    const double qq = __builtin_rint(x / sq);                          // |qq| <= 16256
+    const double h = __builtin_rint(qq * (1.0 / 128.0)), l = qq - 128.0 * h;
+    hi = (int)h; lo = (int)l;
+    return x - sq * qq;
+}
+
+// ---- the batched int8 filter (k_int8_filter, qv_int8.hip): the same integers from the matrix cores, the test in float32 ----
+// The filter serves 9 or more queries per pass, so its epilogue is float32 like the other filter kernels': S~32 = fl(fl(sq32 scale) fl(I)) with
+// sq32 = (float)sq, I = 128 I_hi + I_lo exact in int32 (dim <= 1024: 1024 * 16256 * 127 < 2^31).  Against the proof above, whose S~ is the real
+// number sq scale I up to 2.3e-16:
+//   sq32 = sq (1 + d1), fl(I) = I (1 + d2), two float32 products (1 + d3)(1 + d4), |d_i| <= 2^-24: |S~32 - sq scale I| <= 2.4e-7 |qh.rh|
+//   <= 2.4e-7 (|q| + qres)(|r| + rres8); a product in float32's subnormal range loses at most 2^-149 * 2^31 < 4e-36 absolutely, below
+//   1e-7 |q||r| for norms the bound works with (bound_scan_norm_ok: both at least 1e-14).  The candidate's stored score IS S~32: no further rounding.
+// With kInt8FilterEps = 3e-7 for the roundings (and this line's own) and 1e-7 |q| for underflow, |S~32 - S| <= ea |r| + eb rres8,
+//   ea = qres + (1e-12 + 3e-7)(|q| + qres) + 1e-7 |q|,   eb = |q| + qres + (1e-12 + 3e-7)(|q| + qres),
+// each times 1 + 1e-9 and rounded up to float32: the form every consumer behind the filter reads (eq[0] |r| + eq[1] res(row), res = rres8).
+// The threshold is the one-term bfloat16 filter's (filter_threshold, qv_filter.h) with these constants: a row of the top k has d <= U, hence
+// S >= (1 - U)|q||r| (cosine) or S >= 1 - U (dot) up to the 4e-7 kept in c, and S~32 >= S - ea |r| - eb rres8; m carries ea + 1e-6 |q| (the
+// float32 roundings of the threshold's own three operations), c is rounded down, m and b up, |r| up.
+constexpr double kInt8FilterEps = 3e-7;
+__host__ __device__ static inline float bound_f32_up(float x) {
+    if (!(x == x) || x == __builtin_inff()) return x;
+    union { float f; uint32_t u; } c; c.f = x;
+    if (x == 0.0f) { c.u = 1u; return c.f; }
+    c.u = x > 0.0f ? c.u + 1 : c.u - 1;
+    return c.f;
+}
+__host__ __device__ static inline float bound_f32_down(float x) { return -bound_f32_up(-x); }
+
+// what k_mfma_prep leaves per query for the int8 filter; declined: the query is handed back (redo flag) and nothing passes for it
+struct Int8QueryConsts { float c, m, b, ea, eb, sq32; bool declined; };
+template <int M>
+__host__ __device__ static inline Int8QueryConsts int8_filter_query_consts(uint32_t dim, double sq, double qn, double qres, double U) {
+    static_assert(M == QV_COSINE || M == QV_DOT, "the int8 filter's metrics");
+    Int8QueryConsts k;
+    k.declined = !(bound_scan_norm_ok(qn, dim) && qres >= 0.0 && qres < 1.0e18 && sq > 0.0 && sq < 1.0e36);
+    if (k.declined) { k.c = __builtin_inff(); k.m = k.b = k.ea = k.eb = 0.f; k.sq32 = 0.f; return k; }
+    const double both = (1e-12 + kInt8FilterEps) * (qn + qres);
+    const double ea = (qres + both + 1e-7 * qn) * (1.0 + 1e-9), eb = (qn + qres + both) * (1.0 + 1e-9);
+    k.ea = bound_f32_up((float)ea); k.eb = bound_f32_up((float)eb);
+    k.sq32 = (float)sq;
+    double c = M == QV_COSINE ? (1.0 - U - 4e-7) * qn : (1.0 - U - 4e-7 * (1.0 + __builtin_fabs(U)));
+    double m = ea + 1e-6 * qn;
+    k.b = k.eb;
+    if (!(U == U) || U > 3.0e38) { c = -3.0e38; m = 0.0; k.b = 0.f; }   // no bound: everything is a candidate (overflow -> exact path)
+    k.c = bound_f32_down((float)c);
+    k.m = bound_f32_up((float)m);
+    return k;
+}
+// the score the epilogue tests and the candidate list stores
+__host__ __device__ __forceinline__ float int8_filter_score(int isum_hi, int isum_lo, float sq32, float rscale8) {
+    return (sq32 * rscale8) * (float)(128 * isum_hi + isum_lo);
+}
+// a row the 8-bit bound says nothing about (always a candidate, its score NaN): rn = |r| rounded up to float32
+__host__ __device__ __forceinline__ bool int8_filter_row_unsure(float rn, float rscale8, float rres8, float tiny_rn) {
+    return rn < tiny_rn || !(rn < 1.0e18f) || !(rres8 >= 0.0f && rres8 < 1.0e18f) || !(rscale8 > 0.0f && rscale8 < 1.0e36f);
+}
+// cm: what the kernel keeps per query in the place of c (cosine: c - m, so that the margin's |r| part rides on the same product)
+template <int M> __host__ __device__ __forceinline__ float int8_filter_cm(float c, float m) { return M == QV_COSINE ? c - m : c; }
+// monotone in cm (up), m and b (down), so the same function of a block's (min cm, max m, max b) is a lower bound of its thresholds
+template <int M> __host__ __device__ __forceinline__ float int8_filter_threshold(float cm, float m, float b, float rn, float rres8) {
+    return M == QV_COSINE ? cm * rn - b * rres8 - 1e-30f : cm - m * rn - b * rres8;
+}
+// THE decision, for the kernel's dense pass and for the host (qv_batched_int8_keeps): keep the row as a candidate of the query?
+template <int M> __host__ __device__ __forceinline__ bool int8_filter_keeps(float score, float cm, float m, float b, float rn, float rres8, bool unsure) {
+    return unsure || !(score < int8_filter_threshold<M>(cm, m, b, rn, rres8));
+}
+
 }  // namespace qv

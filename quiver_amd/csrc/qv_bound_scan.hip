@@ -565,11 +565,10 @@ __device__ __forceinline__ void bound8_stage_query(const float* __restrict__ que
     int qs = 0;
     for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) {
         const double x = q_ok ? (double)query[i] : 0.0;
-        const double qq = __builtin_rint(x / sq);                      // |qq| <= 16256
-        const double hi = __builtin_rint(qq * (1.0 / 128.0)), lo = qq - 128.0 * hi;   // |hi| <= 127, |lo| <= 64: exact
-        qh8[i] = (int8_t)(int)hi; ql8[i] = (int8_t)(int)lo;
-        if constexpr (SUM) qs += (int)qq;                              // (exact: dim * 16256 < 2^31)
-        const double d = x - sq * qq;
+        int hi, lo;
+        const double d = bound8_split_query(x, sq, hi, lo);            // |hi| <= 127, |lo| <= 64: exact
+        qh8[i] = (int8_t)hi; ql8[i] = (int8_t)lo;
+        if constexpr (SUM) qs += 128 * hi + lo;                        // (exact: dim * 16256 < 2^31)
         r2 = __builtin_fma(d, d, r2);
     }
     r2 = wave_sum_f64(r2);
@@ -1277,11 +1276,10 @@ k_bound_prep8_mq(const float* __restrict__ queries, uint32_t nq, uint32_t dim, i
     double r2 = 0.0;
     for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) {
         const double x = q_ok ? (double)query[i] : 0.0;
-        const double qq = __builtin_rint(x / sq);                      // |qq| <= 16256
-        const double hi = __builtin_rint(qq * (1.0 / 128.0)), lo = qq - 128.0 * hi;   // |hi| <= 127, |lo| <= 64: exact
-        qterm[(((size_t)(i >> 4) * QB + j) * 2) * 16 + (i & 15u)] = (int8_t)(int)hi;
-        qterm[(((size_t)(i >> 4) * QB + j) * 2 + 1) * 16 + (i & 15u)] = (int8_t)(int)lo;
-        const double d = x - sq * qq;
+        int hi, lo;
+        const double d = bound8_split_query(x, sq, hi, lo);            // |hi| <= 127, |lo| <= 64: exact
+        qterm[(((size_t)(i >> 4) * QB + j) * 2) * 16 + (i & 15u)] = (int8_t)hi;
+        qterm[(((size_t)(i >> 4) * QB + j) * 2 + 1) * 16 + (i & 15u)] = (int8_t)lo;
         r2 = __builtin_fma(d, d, r2);
     }
     r2 = wave_sum_f64(r2);

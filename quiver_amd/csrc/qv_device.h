@@ -409,7 +409,8 @@ bool   batched_supported(const IndexView& v, uint32_t nq, uint32_t k);
 size_t batched_workspace_bytes(const IndexView& v, const ScanPlan& p, uint32_t nq, uint32_t k);
 hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws,
                           uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
-                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const struct BatchedSets* sets = nullptr);
+                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const struct BatchedSets* sets = nullptr,
+                          uint32_t* d_stats = nullptr /* the index's counter words: an unfiltered batch under QV_FILTER_INT8 counts itself at kInt8FilterStatsWord */);
 // A filtered batch, k <= kMaxFusedK: query q over alive & d_sets[q] (a DEVICE array of nq sets; null bits = every row).  The sample's bound is
 // taken over the set, the filter's flush drops rows outside it, and a query whose set holds fewer than sparse_ppm millionths of the sample's
 // rows is handed back without candidates (0: never).  With sets, *d_overflow_out -> [2][nq]: the redo flags, then 1 = handed back as sparse
@@ -450,6 +451,22 @@ hipError_t launch_sets_sparse(uint32_t nq, uint32_t nq_pad, const uint32_t* d_n_
 bool qreg_filter_applies(const IndexView& v, uint32_t nq_pad, bool bfrows);
 hipError_t launch_qreg_filter(const IndexView& v, const uint4* Qbf, const float* cq, const float* mq, uint32_t nq_pad, uint32_t* cand, float* cscore,
                               uint32_t* cnt, bool bfrows, int cus, hipStream_t s);
+
+// The int8 matrix-core filter on the 8-bit plane (qv_int8.hip; QV_FILTER_INT8).  The rule: the index asks for it, cosine or dot, plane8 held, a
+// dimension that is a multiple of 32 from 64 to 1024, and the batched path itself applies; a batch with sets never takes it (launch_batched).
+bool batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8);
+// the index's counter words: 0 - 3 the bound scan, kBound8StatsWord 4 - 6, kBound6StatsWord 7 - 9, kBoundWideStatsWord 10 - 12, kBoundWideMqStatsWord 13 - 15, and
+// the int8 filter's own: [16] batches whose main filter was k_int8_filter, [17] their queries, [18] those handed back
+constexpr uint32_t kInt8FilterStatsWord = 16;
+constexpr uint32_t kIndexStatsWords = 20;      // what the index allocates (and clears) for all of them
+static_assert(kInt8FilterStatsWord + 3 <= kIndexStatsWords, "the int8 filter's counters lie inside the allocation");
+size_t int8_filter_lds_bytes(uint32_t dim);
+// Q8: k_mfma_prep's int8 operand planes, sq32 [nq_pad] behind them; the same constants, candidate lists and redo flags as every other filter kernel
+hipError_t launch_int8_filter(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq, uint32_t nq_pad, uint32_t* cand, float* cscore,
+                              uint32_t* cnt, uint32_t grid_x /* workgroups per 64-query block */, size_t lds, hipStream_t s);
+hipError_t launch_int8_filter_count(const uint32_t* d_redo, uint32_t nq, uint32_t* d_stats, hipStream_t s);
+// k_int8_filter's keep/drop decision on the host (qv_batched_int8_keeps): 1 keep, 0 drop, -1 a metric the filter does not serve
+int host_int8_filter_keeps(int metric, uint32_t dim, int32_t isum_hi, int32_t isum_lo, double sq, double qn, double qres, float U, double rn, float rscale8, float rres8);
 
 // Device-resident HNSW traversal (hnsw.go:471-713), one wave per query.
 size_t   hnsw_lds_bytes(uint32_t ef);

@@ -229,10 +229,20 @@ __device__ __forceinline__ float rn2c_of(float rn) {
 constexpr uint32_t kEpiEntryWords = 20;                               // 16 scores, row, |r| up, |r - bf16(r)| up, flags (i | half << 1 | unsure << 2)
 struct EpiDump { uint32_t* area; uint32_t cap; };                     // this WAVE's dump area in LDS, cap entries of kEpiEntryWords words (16-byte aligned)
 
+// The per-(query, row) decision of the dense pass, as a functor: keep(ql, score, rn, rho, unsure) for query slot ql of the wave's block.  This one is the
+// float32 and bfloat16 filters' (filter_threshold over the workgroup's constants in LDS); the int8 filter brings its own (qv_int8.hip).
+template <int METRIC> struct EpiKeepThreshold {
+    const float* sc; const float* sm; uint32_t qbase;
+    __device__ __forceinline__ bool operator()(uint32_t ql, float score, float rn, float rho, bool unsure) const {
+        const float c = sc[qbase + ql];
+        const float thr = filter_threshold<METRIC>(c, sm[qbase + ql], sm[kEpiQ + qbase + ql], rn, rn2c_of(rn), rho);
+        return (!(score < thr) || unsure) && c < 3.0e38f;             // (padded query slots carry +inf)
+    }
+};
 // the dense pass: entries [0, n) of the wave's dump area, 16 (entry, score) pairs per entry, 64 pairs per round
-template <int METRIC, bool SETS>
-__device__ __forceinline__ void epi_dense_pass(const EpiDump& du, uint32_t n, const float* sc, const float* sm, uint32_t qbase, uint32_t qglobal,
-                                               const CandQueue& cqu, uint32_t& cqn, const CandOutT<SETS>& out) {
+template <bool SETS, typename Keep>
+__device__ __forceinline__ void epi_dense_pass_with(const EpiDump& du, uint32_t n, const Keep& keep, uint32_t qglobal,
+                                                    const CandQueue& cqu, uint32_t& cqn, const CandOutT<SETS>& out) {
     __threadfence_block();                                            // the dump's LDS writes, before other lanes of the wave read them
     const uint32_t lane = lane_id();
     for (uint32_t p = lane; p < 16 * n + 63; p += 64) {              // the loop count is wave-uniform (cand_push is a wave operation)
@@ -242,10 +252,7 @@ __device__ __forceinline__ void epi_dense_pass(const EpiDump& du, uint32_t n, co
             const uint32_t r = p & 15, fl = d[19];
             const uint32_t ql = 32 * (fl & 1) + (r & 3) + 8 * (r >> 2) + 4 * ((fl >> 1) & 1);
             score = __uint_as_float(d[r]); row = d[16];
-            const float c = sc[qbase + ql];
-            const float rn = __uint_as_float(d[17]);
-            const float thr = filter_threshold<METRIC>(c, sm[qbase + ql], sm[kEpiQ + qbase + ql], rn, rn2c_of(rn), __uint_as_float(d[18]));
-            take = (!(score < thr) || (fl >> 2)) && c < 3.0e38f;      // (padded query slots carry +inf)
+            take = keep(ql, score, __uint_as_float(d[17]), __uint_as_float(d[18]), (fl >> 2) != 0);
             if (fl >> 2) score = __builtin_nanf("");                  // a row the scores say nothing about: the exact pass must not read an interval out of this one either
             q = qglobal + ql;
         }
@@ -253,6 +260,11 @@ __device__ __forceinline__ void epi_dense_pass(const EpiDump& du, uint32_t n, co
         if (m) cand_push(cqu, cqn, m, q, row, score, out);
         if (p - lane + 64 >= 16 * n) break;
     }
+}
+template <int METRIC, bool SETS>
+__device__ __forceinline__ void epi_dense_pass(const EpiDump& du, uint32_t n, const float* sc, const float* sm, uint32_t qbase, uint32_t qglobal,
+                                               const CandQueue& cqu, uint32_t& cqn, const CandOutT<SETS>& out) {
+    epi_dense_pass_with(du, n, EpiKeepThreshold<METRIC>{sc, sm, qbase}, qglobal, cqu, cqn, out);
 }
 
 // acc[i][j][r] = S~[query qglobal + 32*i + (r&3)+8*(r>>2)+4*half][row 64*(t0|t1) + 32*(j&1) + l31]; the wave's queries start at sc[qbase] / sm[qbase]
@@ -317,14 +329,14 @@ __device__ __forceinline__ uint64_t epi_level1(const f16v& a, float cmin, float 
     return __ballot((!(mx < thr_lo) || unsure) && live);
 }
 // the dump of one row block whose level-1 mask pm is not empty (wave-uniform call)
-template <int METRIC, bool SETS>
-__device__ __forceinline__ void epi_dump(const f16v& a, uint64_t pm, uint32_t row, float rn, float rho, uint32_t i, uint32_t half, bool unsure,
-                                         const float* sc, const float* sm, uint32_t qbase, uint32_t qglobal, const CandQueue& cqu, uint32_t& cqn,
-                                         const CandOutT<SETS>& out, const EpiDump& du, uint32_t& n) {
+template <bool SETS, typename Keep>
+__device__ __forceinline__ void epi_dump_with(const f16v& a, uint64_t pm, uint32_t row, float rn, float rho, uint32_t i, uint32_t half, bool unsure,
+                                              const Keep& keep, uint32_t qglobal, const CandQueue& cqu, uint32_t& cqn,
+                                              const CandOutT<SETS>& out, const EpiDump& du, uint32_t& n) {
     const bool pre = (pm >> lane_id()) & 1ull;
     const uint32_t cnt = (uint32_t)__builtin_popcountll(pm), rank = (uint32_t)__builtin_popcountll(pm & ((1ull << lane_id()) - 1ull));
     for (uint32_t done = 0; done < cnt;) {                  // one round, unless the dump area fills up (wave-uniform loop)
-        if (n == du.cap) { epi_dense_pass<METRIC>(du, n, sc, sm, qbase, qglobal, cqu, cqn, out); n = 0; __threadfence_block(); }
+        if (n == du.cap) { epi_dense_pass_with(du, n, keep, qglobal, cqu, cqn, out); n = 0; __threadfence_block(); }
         const uint32_t now = (du.cap - n) < (cnt - done) ? (du.cap - n) : (cnt - done);
         if (pre && rank >= done && rank < done + now) {
             uint32_t* d = du.area + (n + rank - done) * kEpiEntryWords;
@@ -335,6 +347,12 @@ __device__ __forceinline__ void epi_dump(const f16v& a, uint64_t pm, uint32_t ro
         }
         n += now; done += now;
     }
+}
+template <int METRIC, bool SETS>
+__device__ __forceinline__ void epi_dump(const f16v& a, uint64_t pm, uint32_t row, float rn, float rho, uint32_t i, uint32_t half, bool unsure,
+                                         const float* sc, const float* sm, uint32_t qbase, uint32_t qglobal, const CandQueue& cqu, uint32_t& cqn,
+                                         const CandOutT<SETS>& out, const EpiDump& du, uint32_t& n) {
+    epi_dump_with(a, pm, row, rn, rho, i, half, unsure, EpiKeepThreshold<METRIC>{sc, sm, qbase}, qglobal, cqu, cqn, out, du, n);
 }
 template <int METRIC, bool SETS>
 __device__ __forceinline__ void filter_epilogue_finish(const float* sc, const float* sm, uint32_t qbase, uint32_t qglobal, const CandQueue& cqu, uint32_t& cqn,

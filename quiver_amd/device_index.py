@@ -409,7 +409,7 @@ class DeviceIndex:
         check(lib().qv_distance_rows_device(self._h, d_query, d_rows, n, d_out, stream))
 
 
-    FILTERS = {"auto": 0, "fp32": 1, "bf16x3": 2, "bf16x1": 3, "off": 4}
+    FILTERS = {"auto": 0, "fp32": 1, "bf16x3": 2, "bf16x1": 3, "off": 4, "int8": 5}
 
     BOUND_SCAN = {"auto": 0, "always": 1, "never": 2}
 
@@ -540,8 +540,16 @@ class DeviceIndex:
         return out
 
     def set_filter(self, filter):
-        """the batched path's filter kernel: "auto", "fp32" (fp32 MFMA chain), "bf16x3", "bf16x1", or "off" — exact scans only (qv_index_set_filter)"""
+        """the batched path's filter kernel: "auto", "fp32" (fp32 MFMA chain), "bf16x3", "bf16x1", "off" — exact scans only — or "int8": the int8
+        matrix-core filter on the 8-bit plane where it applies (batched_int8_applies), "auto" elsewhere (qv_index_set_filter)"""
         check(lib().qv_index_set_filter(self._h, self.FILTERS.get(filter, filter)))
+
+    def int8_filter_stats(self) -> tuple:
+        """(batches whose main filter was the int8 kernel on the 8-bit plane, their queries, those of them handed back, 1 when the index holds
+        the plane) — set_filter("int8"); waits for the device (qv_index_int8_filter_stats)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_index_int8_filter_stats(self._h, out))
+        return tuple(int(x) for x in out)
 
     FILTERED_BATCH = {"auto": 0, "always": 1, "never": 2}
 
