@@ -466,6 +466,30 @@ int qv_batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq
 int qv_batched_int8_keeps(int metric, uint32_t dim, int32_t isum_hi, int32_t isum_lo, double sq, double qn, double qres, float U, double rn,
                           float rscale8, float rres8);
 
+/* ---- QV_FILTER_INT8 has two kernels ----
+ * The block kernel serves one 64-query block per workgroup, so a batch of more than 64 queries walks the plane once per block.  The shared-row
+ * kernel serves whole groups of 256 queries per workgroup — their int8 operands stay resident in registers, the plane's rows arrive by LDS-DMA
+ * and are read once per group — and applies where ALL of these hold: the int8 filter itself applies (qv_batched_int8_applies); the piece holds
+ * more than 128 queries (it is padded to a multiple of 256); the dimension is 128, 384, 512 or 768.  Both kernels make the same decision per
+ * (query, row) (qv_batched_int8_keeps) and the exact re-score decides as ever, so results do not depend on the form.
+ * qv_index_set_int8_form: QV_INT8_FORM_SHARED takes the shared-row kernel wherever it applies, QV_INT8_FORM_BLOCKS never, QV_INT8_FORM_AUTO
+ * only in the cells where it was measured faster than the block kernel by more than both arms' spread — today QV_COSINE at 768 dimensions
+ * from 10 million rows, where the plane no longer fits the caches (profiles/LAB_r31_int8_shared.md; at 1M rows the two measure the same).
+ * Needs external exclusion against running searches, like qv_index_set_filter.  The environment variable QV_INT8_FORM (1 / 2, read once per
+ * process) sets the default of indexes that never call this.
+ * qv_index_int8_shared_stats: out[0] = batches whose main filter was the shared-row kernel, out[1] = their queries; qv_index_int8_filter_stats
+ * counts these batches too.  Waits for the device; a batch counts once its kernels have run.
+ * qv_batched_int8_form: the dispatch's own rule without an index or a device — 0 where no int8 kernel runs (exactly where
+ * qv_batched_int8_applies is 0), 1 where the call's first piece takes the block kernel, 2 where it takes the shared-row kernel (a call is cut
+ * as qv_index_search_batched cuts it: a remainder of up to 64 queries behind a multiple of 256 is a piece of its own, on the block kernel);
+ * QV_ERR_INVALID_ARG (< 0) for a mode or filter outside their ranges. */
+#define QV_INT8_FORM_AUTO   0
+#define QV_INT8_FORM_SHARED 1
+#define QV_INT8_FORM_BLOCKS 2
+int qv_index_set_int8_form(qv_index* idx, int mode);
+int qv_index_int8_shared_stats(qv_index* idx, uint64_t out[2]);
+int qv_batched_int8_form(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_plane8, int mode);
+
 /* ---- filtered batches: 9 or more queries, a filter per query, on the batched path ----
  * A call — or a pass that concurrent callers share — of 9 or more queries, k <= 64, through qv_index_search_rowsets or
  * qv_index_search_where can take the batched path above instead of ceil(nq / 8) or ceil(nq / 16) exact corpus passes: the sample bound

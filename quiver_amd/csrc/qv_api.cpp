@@ -1935,7 +1935,7 @@ static int batched_device_pass(qv_index* idx, const float* d_queries, uint32_t n
     if (rc != QV_OK) return rc;
     const ProfilePair pp = profile_begin(idx);
     uint32_t* d_ovf = nullptr;
-    hipError_t e = qv::launch_batched(v, plan, d_queries, nq, k, ws, d_rows_out, d_dist_out, &d_ovf, idx->cus, s, pp.ev0, pp.ev1, nullptr, idx->d_bound_stats);
+    hipError_t e = qv::launch_batched(v, plan, d_queries, nq, k, ws, d_rows_out, d_dist_out, &d_ovf, idx->cus, s, pp.ev0, pp.ev1, nullptr, idx->d_bound_stats, idx->int8_form);
     profile_end(idx, pp, e == hipSuccess);
     if (e != hipSuccess) return fail(QV_ERR_DEVICE, "batched launch failed: %s", hipGetErrorString(e));
     HIPCHK(hipMemcpyAsync(d_redo_flags_out, d_ovf, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
@@ -1983,7 +1983,7 @@ static int batched_pass(qv_index* idx, const float* queries, uint32_t nq, uint32
         if ((rc = hc.send(nq))) return rc;
         uint32_t* d_ovf = nullptr;
         const ProfilePair pp = profile_begin(idx);
-        hipError_t e = qv::launch_batched(v, plan, hc.d_queries(), nq, kk, hc.ws(), hc.d_rows(), hc.d_dist(), &d_ovf, idx->cus, hc.stream(), pp.ev0, pp.ev1, nullptr, idx->d_bound_stats);
+        hipError_t e = qv::launch_batched(v, plan, hc.d_queries(), nq, kk, hc.ws(), hc.d_rows(), hc.d_dist(), &d_ovf, idx->cus, hc.stream(), pp.ev0, pp.ev1, nullptr, idx->d_bound_stats, idx->int8_form);
         profile_end(idx, pp, e == hipSuccess);
         if (e != hipSuccess) return fail(QV_ERR_DEVICE, "batched launch failed: %s", hipGetErrorString(e));
         if ((rc = hc.fetch(nq, kk))) return rc;
@@ -2159,6 +2159,34 @@ int qv_index_int8_filter_stats(qv_index* idx, uint64_t out[4]) {
 int qv_batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_plane8) {
     if (filter < QV_FILTER_AUTO || filter > QV_FILTER_INT8) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
     return qv::batched_int8_applies(metric, dim, rows, nq, k, filter, has_plane8 != 0) ? 1 : 0;
+}
+
+int qv_index_set_int8_form(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_INT8_FORM_BLOCKS) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (the shared-row kernel wherever it applies) or 2 (the block kernel only); got %d", mode);
+    idx->int8_form = mode;
+    return QV_OK;
+}
+
+int qv_index_int8_shared_stats(qv_index* idx, uint64_t out[2]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t h[2] = {0, 0};
+    HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kInt8SharedStatsWord, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1];
+    return QV_OK;
+}
+
+int qv_batched_int8_form(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_plane8, int mode) {
+    if (mode < 0 || mode > QV_INT8_FORM_BLOCKS) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (shared) or 2 (blocks); got %d", mode);
+    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_INT8) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
+    if (!qv::batched_int8_applies(metric, dim, rows, nq, k, filter, has_plane8 != 0)) return 0;
+    // the call's first piece, as qv_index_search_batched* cut it: a pass of at most kHostBatch queries, its short remainder (short_tail) apart
+    uint32_t piece = std::min(nq, kHostBatch);
+    const uint32_t tail = short_tail(piece);
+    if (tail && (tail <= 8 || qv::batched_int8_applies(metric, dim, rows, tail, k, filter, has_plane8 != 0))) piece -= tail;
+    return qv::batched_int8_form(metric, dim, rows, piece, k, filter, has_plane8 != 0, mode);
 }
 
 int qv_batched_int8_keeps(int metric, uint32_t dim, int32_t isum_hi, int32_t isum_lo, double sq, double qn, double qres, float U, double rn,

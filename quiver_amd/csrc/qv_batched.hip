@@ -2461,6 +2461,7 @@ enum class MainFilter {
     qreg,                   // launch_qreg_filter (qv_qreg.hip)
     q64_plane, q64_f32_rows,   // k_bf16rows_filter_q64<., 4, 4>, <., 2, 4, true>
     int8_plane,             // launch_int8_filter (qv_int8.hip): never plan_batched's choice — batched_int8_adapt's, for an index under QV_FILTER_INT8
+    int8_shared,            // launch_int8_shared_filter (qv_int8.hip): the same, for whole groups of 256 queries (int8_shared_route)
 #ifdef QV_VARIANTS
     mfma_f32_nj2,           // k_mfma_filter<., 2>
     one_term_4w,            // k_bf16x3_filter_shared<., 1, 8>
@@ -2765,12 +2766,36 @@ static void batched_sets_adapt(BatchedRoute& r) {
 static bool int8_shape(int metric, uint32_t dim, int filter, bool has_plane8) {
     return filter == QV_FILTER_INT8 && (metric == QV_COSINE || metric == QV_DOT) && has_plane8 && (dim & 31u) == 0 && dim >= 64 && dim <= 1024;
 }
-static void batched_int8_adapt(BatchedRoute& r, const IndexView& v) {
+// Which of its two kernels: the shared-row form (k_int8_shared_filter) serves pieces padded to whole groups of 256 queries — more than 128 —
+// at the dimensions it is instantiated for.  form: QV_INT8_FORM_* (qv_index_set_int8_form); QV_INT8_FORM (1 / 2, read once) is the default of
+// indexes that never called the setter.  SHARED: wherever it applies; BLOCKS: never; automatic: the cells where it was measured faster than
+// the block kernel by more than both arms' spread, and no class of shape that was not measured.
+// Measured (profiles/LAB_r31_int8_shared.md; cosine, us per batch, block kernel / shared-row kernel): 10M x 768 at 129 queries 3983 / 3709, 256:
+// 4972 / 4071 (k = 64: 5194 / 4405), 1024: 18900 / 15721 — the plane no longer fits L2 and the block kernel streams it once per block.  1M x 768
+// (129, 256, 1024 queries, k = 10 and 64, with and without QV_FLAG_BF16_ROWS) and 10M x 128: the ranges overlap — both kernels issue the same
+// matrix instructions and the plane comes out of L2.  Dot, 384 and 512 dimensions and corpora between 1M and 10M rows were not measured.
+constexpr uint64_t kInt8SharedAutoMinRows = 10000000;                // the smallest corpus at which the shared-row form was measured ahead
+static bool int8_shared_auto(int metric, uint32_t dim, uint64_t rows) { return metric == QV_COSINE && dim == 768 && rows >= kInt8SharedAutoMinRows; }
+static int int8_form_mode(int form) { static const int env_form = env_int("QV_INT8_FORM", 0); return form ? form : (env_form == 1 || env_form == 2 ? env_form : 0); }
+static bool int8_shared_route(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t nq_pad, int form) {
+    form = int8_form_mode(form);
+    // (up to 128 queries are padded to a group too under the one-term filter's rule, batched_nq_pad: two of its four waves would hold padding only)
+    if (form == QV_INT8_FORM_BLOCKS || nq <= 128 || (nq_pad & 255u) || !int8_shared_has_dim(dim)) return false;
+    return form == QV_INT8_FORM_SHARED || int8_shared_auto(metric, dim, rows);
+}
+static void batched_int8_adapt(BatchedRoute& r, const IndexView& v, int form) {
+    r.bfrows = false;
+    r.gmode = 3; r.prep_what = 3; r.prep_steps = 0u;
+    if (int8_shared_route(v.metric, v.dim, v.n_rows, r.nq, r.nq_pad, form)) {
+        r.filter = MainFilter::int8_shared;
+        r.filter_grid = grid_multiple((uint32_t)r.cus, r.nq_pad >> 8);   // as the qreg route's: one workgroup per CU, a multiple of the groups
+        r.filter_lds = 0;
+        return;
+    }
     const uint32_t blocks = (r.nq + 63) / 64;                         // (the 64-query blocks that hold a real query: the others leave at once)
-    r.filter = MainFilter::int8_plane; r.bfrows = false;
+    r.filter = MainFilter::int8_plane;
     r.filter_grid = std::max(1u, (uint32_t)r.cus / blocks);
     r.filter_lds = int8_filter_lds_bytes(v.dim);
-    r.gmode = 3; r.prep_what = 3; r.prep_steps = 0u;
 }
 // an index's shape as the rules that take no index see it (filtered_batch_rule, batched_sets_filter); plane: it keeps the bfloat16 copy the
 // batched filter reads (QV_FLAG_BF16_ROWS) — the plan asks only whether there is one, so the view carries a marker that nothing reads through
@@ -2784,6 +2809,10 @@ static IndexView shape_view(int metric, uint32_t dim, uint64_t rows, int filter,
 bool batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8) {
     if (rows == 0 || rows > 0xFFFFFFFFull || !int8_shape(metric, dim, filter, has_plane8)) return false;
     return k >= 1 && batched_supported(shape_view(metric, dim, rows, filter), nq, k);
+}
+int batched_int8_form(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8, int mode) {
+    if (!batched_int8_applies(metric, dim, rows, nq, k, filter, has_plane8)) return 0;
+    return int8_shared_route(metric, dim, rows, nq, batched_nq_pad(nq, shape_view(metric, dim, rows, filter)), mode) ? 2 : 1;
 }
 bool batched_sets_wide_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus) {
     BatchedRoute r;
@@ -2937,6 +2966,7 @@ static hipError_t batched_filter(const IndexView& v, const BatchedRoute& r, cons
     const uint4* Qbf = reinterpret_cast<const uint4*>(L.Qt);
     if (r.filter == MainFilter::qreg) return sets ? hipErrorNotSupported : launch_qreg_filter(v, Qbf, L.cq, L.mq, r.nq_pad, L.cand, L.cscore, L.cnt, r.bfrows, r.cus, s);
     if (r.filter == MainFilter::int8_plane) return sets ? hipErrorNotSupported : launch_int8_filter(v, L.Qt, L.cq, L.mq, r.nq, r.nq_pad, L.cand, L.cscore, L.cnt, r.filter_grid, r.filter_lds, s);
+    if (r.filter == MainFilter::int8_shared) return sets ? hipErrorNotSupported : launch_int8_shared_filter(v, L.Qt, L.cq, L.mq, r.nq_pad, L.cand, L.cscore, L.cnt, r.filter_grid, s);
     // every filter kernel takes the same arguments (the operands as float32 or bfloat16 planes), some a sample's after them
     auto go = [&](auto kernel, auto* Q, uint32_t block, auto... sample_args) {
         const hipError_t e = set_lds(kernel, r.filter_lds); if (e != hipSuccess) return e;
@@ -3044,14 +3074,14 @@ static hipError_t batched_exact(const IndexView& v, const BatchedRoute& r, const
 
 hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws,
                           uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
-                          hipEvent_t ev0, hipEvent_t ev1, const BatchedSets* sets, uint32_t* d_stats) {
+                          hipEvent_t ev0, hipEvent_t ev1, const BatchedSets* sets, uint32_t* d_stats, int int8_form) {
     BatchedRoute r;
     if (!plan_batched(v, nq, k, cus, (reinterpret_cast<uintptr_t>(d_queries) & 15u) == 0, r)) return hipErrorNotSupported;
     const RowSetRef* d_sets = sets ? sets->d_sets : nullptr;
     // the int8 filter, decided once: an unfiltered batch of an index that asks for it and holds the plane.  Behind it a candidate's interval is
     // eq[0] |r| + eq[1] rres8(row): the exact stage reads its residuals through a view whose array is the 8-bit plane's.
     const bool int8 = !d_sets && int8_shape(v.metric, v.dim, v.filter, v.plane8 != nullptr && v.rscale8 != nullptr && v.rres8 != nullptr);
-    if (int8) batched_int8_adapt(r, v);
+    if (int8) batched_int8_adapt(r, v, int8_form);
     IndexView vx = v;
     if (int8) vx.rres = v.rres8;
     if (d_sets && !batched_sets_route(r)) return hipErrorNotSupported;   // (a missing route is an error, never an unfiltered answer)
@@ -3075,7 +3105,7 @@ hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_
     if (ev1) (void)hipEventRecord(ev1, s);
     e = batched_exact(vx, r, L, d_queries, d_rows_out, d_dist_out, s);
     if (e != hipSuccess) return e;
-    if (int8 && d_stats) { e = launch_int8_filter_count(L.ovf, nq, d_stats, s); if (e != hipSuccess) return e; }
+    if (int8 && d_stats) { e = launch_int8_filter_count(L.ovf, nq, d_stats, r.filter == MainFilter::int8_shared, s); if (e != hipSuccess) return e; }
     *d_overflow_out = L.ovf;
     return hipGetLastError();
 }

@@ -410,7 +410,8 @@ size_t batched_workspace_bytes(const IndexView& v, const ScanPlan& p, uint32_t n
 hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws,
                           uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
                           hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const struct BatchedSets* sets = nullptr,
-                          uint32_t* d_stats = nullptr /* the index's counter words: an unfiltered batch under QV_FILTER_INT8 counts itself at kInt8FilterStatsWord */);
+                          uint32_t* d_stats = nullptr /* the index's counter words: an unfiltered batch under QV_FILTER_INT8 counts itself at kInt8FilterStatsWord */,
+                          int int8_form = 0 /* QV_INT8_FORM_* (qv_index_set_int8_form) */);
 // A filtered batch, k <= kMaxFusedK: query q over alive & d_sets[q] (a DEVICE array of nq sets; null bits = every row).  The sample's bound is
 // taken over the set, the filter's flush drops rows outside it, and a query whose set holds fewer than sparse_ppm millionths of the sample's
 // rows is handed back without candidates (0: never).  With sets, *d_overflow_out -> [2][nq]: the redo flags, then 1 = handed back as sparse
@@ -458,13 +459,24 @@ bool batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq, 
 // the index's counter words: 0 - 3 the bound scan, kBound8StatsWord 4 - 6, kBound6StatsWord 7 - 9, kBoundWideStatsWord 10 - 12, kBoundWideMqStatsWord 13 - 15, and
 // the int8 filter's own: [16] batches whose main filter was k_int8_filter, [17] their queries, [18] those handed back
 constexpr uint32_t kInt8FilterStatsWord = 16;
-constexpr uint32_t kIndexStatsWords = 20;      // what the index allocates (and clears) for all of them
-static_assert(kInt8FilterStatsWord + 3 <= kIndexStatsWords, "the int8 filter's counters lie inside the allocation");
+// ... and of those, the shared-row form's: [19] batches whose main filter was k_int8_shared_filter, [20] their queries
+constexpr uint32_t kInt8SharedStatsWord = 19;
+constexpr uint32_t kIndexStatsWords = 22;      // what the index allocates (and clears) for all of them
+static_assert(kInt8FilterStatsWord + 3 <= kInt8SharedStatsWord, "the int8 filter's counters end where the shared-row form's begin");
+static_assert(kInt8SharedStatsWord + 2 <= kIndexStatsWords, "the int8 filter's counters lie inside the allocation");
 size_t int8_filter_lds_bytes(uint32_t dim);
 // Q8: k_mfma_prep's int8 operand planes, sq32 [nq_pad] behind them; the same constants, candidate lists and redo flags as every other filter kernel
 hipError_t launch_int8_filter(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq, uint32_t nq_pad, uint32_t* cand, float* cscore,
                               uint32_t* cnt, uint32_t grid_x /* workgroups per 64-query block */, size_t lds, hipStream_t s);
-hipError_t launch_int8_filter_count(const uint32_t* d_redo, uint32_t nq, uint32_t* d_stats, hipStream_t s);
+hipError_t launch_int8_filter_count(const uint32_t* d_redo, uint32_t nq, uint32_t* d_stats, bool shared, hipStream_t s);
+// The shared-row form (k_int8_shared_filter): one workgroup per CU and 256-query group, the group's operands resident in registers, the plane read
+// once per group.  grid: a multiple of nq_pad / 256.  The same operands, constants and candidate lists as launch_int8_filter.
+bool int8_shared_has_dim(uint32_t dim);
+hipError_t launch_int8_shared_filter(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq_pad, uint32_t* cand, float* cscore, uint32_t* cnt,
+                                     uint32_t grid, hipStream_t s);
+// Which int8 kernel a piece of nq queries takes (qv_batched_int8_form): 0 none — exactly where batched_int8_applies is false —, 1 k_int8_filter,
+// 2 the shared-row form.  mode: QV_INT8_FORM_* (0 = QV_INT8_FORM of the environment, else the measured cells).
+int batched_int8_form(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8, int mode);
 // k_int8_filter's keep/drop decision on the host (qv_batched_int8_keeps): 1 keep, 0 drop, -1 a metric the filter does not serve
 int host_int8_filter_keeps(int metric, uint32_t dim, int32_t isum_hi, int32_t isum_lo, double sq, double qn, double qres, float U, double rn, float rscale8, float rres8);
 

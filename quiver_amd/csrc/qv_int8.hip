@@ -22,6 +22,7 @@
 // interval out of it.  Candidates leave through the wave's queue and cand_flush, as in every other filter kernel.
 #include "qv_filter.h"
 #include "qv_bound.h"
+#include "qv_lds_dma.h"
 
 namespace qv {
 
@@ -32,6 +33,9 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 #define QV_INT8_RING 6                                                // (8: 256 registers and 5 spilled, 24 bytes of scratch per lane)
 #endif
 constexpr int kInt8Ring = QV_INT8_RING;                               // steps in flight per wave
+#ifndef QV_INT8_SHARED_LSTEPS
+#define QV_INT8_SHARED_LSTEPS 2                                      // the shared-row form at 768 dimensions: steps whose operands live in LDS
+#endif
 
 // the workgroup's per-query constants in LDS: cm (int8_filter_cm), m, b by query; sq32 in the accumulators' order, [lane half][query half][16]
 struct Int8Lds { float cm[64], m[64], b[64], sq[2][2][16]; };
@@ -186,15 +190,258 @@ hipError_t launch_int8_filter(const IndexView& v, const void* Q8, const float* c
     return div ? go(k_int8_filter<QV_DOT, kInt8Ring, true>) : go(k_int8_filter<QV_DOT, kInt8Ring, false>);
 }
 
+// ---- the shared-row form (k_int8_shared_filter): whole groups of 256 queries, the plane read ONCE per group ----
+// k_int8_filter above serves one 64-query block per workgroup, so a batch of four blocks walks the plane four times.  Here a workgroup is four waves,
+// one per SIMD, 512 registers each, and serves 256 queries (k_qreg_filter's shape, qv_qreg.hip): wave w keeps the hi and lo operands of queries
+// 64 w .. 64 w + 63 of its group for ALL dimensions — four 16-byte A operands per 32-dimension step, 384 registers at 768 dimensions: the first
+// ASTEPS steps in the accumulation registers (the matrix instruction is issued from inline assembly and reads them there), the next in vector
+// registers, the last LSTEPS in LDS (the valve that keeps the kernel under 512 registers).  k_mfma_prep's operand planes are read as they are: wave w
+// of group g takes 64-query block 4 g + w.
+// Rows: both 32-row blocks of a tile at once would need 128 accumulators beside the operands, so the unit of work is ONE 32-row block of a tile —
+// 64 accumulators, [hi, lo][query half] — and the LDS-DMA gathers exactly that block: lane (half, l31) of a request moves the 16 bytes of chunk
+// 2 s + half of row 32 j + l31 (512 contiguous bytes per lane half) and LDS receives them lane after lane, which IS step s's B operand in lane
+// order: one conflict-free 16-byte LDS read per step and wave, no LDS byte that is not a row byte of the block in flight.  A stage of the ring is
+// four steps of a block (4 KiB), one request per wave; NST stages, requested NST - 1 ahead of their use, ONE barrier per stage (16 matrix
+// instructions per wave).  Waits are explicit (qv_lds_dma.h): s_waitcnt vmcnt(NST - 3) for the wave's own request of the NEXT stage, then the
+// workgroup barrier for the other waves' — a stage is certified one ahead so that a stage's last step can already read the next one's first operand.
+// The row constants (norms, scales, residuals, the alive word: 2 KiB of LDS per tile) travel the same way, two requests per wave in front of a tile's
+// first stage, so the epilogue never waits behind the ring; requests the compiler does not see only make the counted waits more conservative.
+// Every wave reaches every barrier and issues every request it owes the ring, whatever its queries are (padded queries carry zero operands and
+// +inf constants: nothing passes).  Behind a workgroup's last block the cursor requests that block again: in bounds, read by nobody.
+// The epilogue is k_int8_filter's, through the same functions, per 32-row block.
+constexpr int kI8sStageSteps = 4, kI8sStageBytes = kI8sStageSteps * 1024;
+constexpr int kI8sRcTiles = 8, kI8sRcWords = 512;
+
+// A out of the accumulation registers (AG) or a vector register; ZERO: C = 0 (a block's first step).  volatile: the statements stay in the order
+// written.  The two wait states in front cover an operand that the vector ALU wrote just before (a copy the register allocator may place there).
+template <bool AG, bool ZERO>
+__device__ __forceinline__ void mfma_i8(i32x16& acc, const i32x4& a, const i32x4& b) {
+    if constexpr (ZERO) {
+        if constexpr (AG) asm volatile("s_nop 1\n\tv_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "=&v"(acc) : "a"(a), "v"(b));
+        else asm volatile("s_nop 1\n\tv_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
+    } else {
+        if constexpr (AG) asm volatile("s_nop 1\n\tv_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+v"(acc) : "a"(a), "v"(b));
+        else asm volatile("s_nop 1\n\tv_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+    }
+}
+
+// STEPS: 32-dimension steps (dim = 32 STEPS exactly).  The A operands of steps [0, ASTEPS) live in accumulation registers, of the last LSTEPS steps
+// in LDS, of the steps between in vector registers.  NST ring stages.
+template <int METRIC, int STEPS, int ASTEPS, int LSTEPS, int NST>
+__global__ void __launch_bounds__(256, 1)
+k_int8_shared_filter(IndexView v, const uint4* __restrict__ Q8, const float* __restrict__ sq32, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq_pad,
+                     uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt) {
+    constexpr int NSTG = STEPS / kI8sStageSteps;                     // stages per 32-row block
+    constexpr int VSTEPS = STEPS - ASTEPS - LSTEPS, RSTEPS = STEPS - LSTEPS;
+    static_assert(STEPS % kI8sStageSteps == 0 && NSTG >= 1 && NST >= 4 && LSTEPS >= 0 && LSTEPS < STEPS && VSTEPS >= 0 && ASTEPS >= 0 && ASTEPS <= 16, "shape");
+    // the producer runs at most NST - 1 stages ahead: that many tiles' constants, and one more, must not wrap onto the consumer's
+    static_assert((NST - 1) / (2 * NSTG) + 2 <= kI8sRcTiles, "the row constants' ring");
+    __shared__ __align__(16) Int8Lds s_k[4];                         // per wave: its 64 queries' constants
+    __shared__ __align__(1024) unsigned char s_ring[NST][kI8sStageBytes];
+    __shared__ __align__(16) i32x4 s_a[4][LSTEPS > 0 ? LSTEPS : 1][4][64];
+    // per tile: norms (64 doubles) in words [0, 128), scales [128, 192), residuals [192, 256), the alive word at 256 + 64 wave (one copy per wave)
+    __shared__ __align__(16) uint32_t s_rc[kI8sRcTiles][kI8sRcWords];
+    constexpr bool SETS = false;                                     // (a filtered batch never takes this kernel: launch_batched)
+    QV_CAND_QUEUE(cqu, 4, 128);                                      // 6 KiB
+    QV_EPI_DUMP(du, 4, 16);                                          // 5 KiB
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t groups = nq_pad >> 8;
+    const uint32_t stride = gridDim.x / groups;
+    // which 256-query group and which tiles: the workgroups that walk the SAME tiles share an XCD's L2 (filter_block_role, qv_filter.h)
+    uint32_t qb256, first;
+    filter_block_role(groups, qb256, first);
+    Int8Lds& kw = s_k[wave];
+    {
+        const uint32_t ql = lane, q = 256 * qb256 + 64 * wave + ql, w = ql & 31u;
+        const float c = cq[q], m = mq[q];
+        kw.cm[ql] = int8_filter_cm<METRIC>(c, m); kw.m[ql] = m; kw.b[ql] = mq[nq_pad + q];
+        kw.sq[(w >> 2) & 1u][ql >> 5][(w & 3u) | ((w >> 3) << 2)] = sq32[q];   // ql = 32 i + (r & 3) + 8 (r >> 2) + 4 half, inverted
+    }
+    // the wave's operands: 64-query block 4 qb256 + wave; step s, operand o = 2 {hi, lo} + query half
+    i32x4 Aa[ASTEPS > 0 ? ASTEPS : 1][4], Av[VSTEPS > 0 ? VSTEPS : 1][4];
+    {
+        const i32x4* a = reinterpret_cast<const i32x4*>(Q8) + (size_t)(4 * qb256 + wave) * STEPS * 256 + lane;
+#pragma unroll
+        for (int s = 0; s < ASTEPS; s++)
+#pragma unroll
+            for (int o = 0; o < 4; o++) Aa[s][o] = a[(size_t)(s * 4 + o) * 64];
+#pragma unroll
+        for (int s = 0; s < VSTEPS; s++)
+#pragma unroll
+            for (int o = 0; o < 4; o++) Av[s][o] = a[(size_t)((ASTEPS + s) * 4 + o) * 64];
+#pragma unroll
+        for (int s = 0; s < LSTEPS; s++)
+#pragma unroll
+            for (int o = 0; o < 4; o++) s_a[wave][s][o][lane] = a[(size_t)((RSTEPS + s) * 4 + o) * 64];
+    }
+    // every operand is "used" here, so that the compiler waits for these loads HERE and not — with vmcnt(0), the whole ring drained — at their
+    // first use inside the loop
+#pragma unroll
+    for (int s = 0; s < ASTEPS; s++) { asm volatile("" :: "a"(Aa[s][0]), "a"(Aa[s][1]), "a"(Aa[s][2]), "a"(Aa[s][3])); }
+#pragma unroll
+    for (int s = 0; s < VSTEPS; s++) { asm volatile("" :: "v"(Av[s][0]), "v"(Av[s][1]), "v"(Av[s][2]), "v"(Av[s][3])); }
+    __syncthreads();
+    if (stride == 0 || first >= v.n_tiles) return;                   // (the whole workgroup)
+    const uint32_t n_half = 2 * ((v.n_tiles - first + stride - 1) / stride);   // the 32-row blocks this workgroup walks
+    const uint32_t half = lane >> 5, l31 = lane & 31;
+    float cmin[2], mmax[2], bmax[2];                                 // per query half: what bounds the 16 thresholds of this lane's accumulators from below
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        float cm = __builtin_inff(), mm = 0.f, bm = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const uint32_t ql = 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
+            cm = fminf(cm, kw.cm[ql]); mm = fmaxf(mm, kw.m[ql]); bm = fmaxf(bm, kw.b[ql]);
+        }
+        cmin[i] = cm; mmax[i] = mm; bmax[i] = bm;
+    }
+    const float tiny = filter_tiny_norm(v.dim);
+    const Int8Keep<METRIC> keep{kw};
+    const uint32_t qglobal = 256 * qb256 + 64 * wave;
+    const uint32_t ring_addr = (uint32_t)(size_t)(qlds_u8*)&s_ring[0][0];
+    const uint32_t rc_addr = (uint32_t)(size_t)(qlds_u8*)&s_rc[0][0];
+    const uint32_t lane16 = lane * 16;
+    const uint32_t lane_goff = half * 1024 + l31 * 16;               // chunk `half` of the step, row l31 of the block
+    constexpr size_t tile_bytes = (size_t)STEPS * 2048;
+    const unsigned char* plane = reinterpret_cast<const unsigned char*>(v.plane8);
+    const unsigned char* rc_base = wave < 2 ? reinterpret_cast<const unsigned char*>(v.rnorm) + 256 * wave
+                                 : (wave == 2 ? reinterpret_cast<const unsigned char*>(v.rscale8) : reinterpret_cast<const unsigned char*>(v.rres8));
+    const uint32_t rc_mul = wave < 2 ? 512u : 256u;                  // bytes per tile in this wave's array
+    // producer cursor: block p_h of this workgroup's sequence (tile p_h / 2, row block p_h & 1), stage p_s of it, ring slot p_slot
+    uint32_t p_h = 0, p_s = 0, p_slot = 0;
+    auto request_stage = [&]() {
+        const uint32_t ph = p_h < n_half ? p_h : n_half - 1;         // past the end: the last block again (lands in a slot nobody reads)
+        const uint32_t t = first + (ph >> 1) * stride;
+        if (p_s == 0 && (p_h & 1u) == 0) {                           // a tile's constants, in front of its first stage
+            const uint32_t dst = rc_addr + ((p_h >> 1) & (kI8sRcTiles - 1)) * (kI8sRcWords * 4) + 256 * wave;
+            dma_words(rc_base + (size_t)t * rc_mul, lane * 4, dst);
+            dma_words(reinterpret_cast<const unsigned char*>(v.alive) + (size_t)t * 8, (lane & 1u) * 4, dst + 1024);
+        }
+        dma_piece<0>(plane + (size_t)t * tile_bytes + (size_t)(kI8sStageSteps * p_s + wave) * 2048 + (ph & 1u) * 512, lane_goff, ring_addr + p_slot * kI8sStageBytes + 1024 * wave);
+        p_s++; if (p_s == (uint32_t)NSTG) { p_s = 0; p_h++; }
+        p_slot++; if (p_slot == (uint32_t)NST) p_slot = 0;
+    };
+#pragma unroll
+    for (int i = 0; i < NST - 1; i++) request_stage();
+    wait_vmcnt<NST - 2>();
+    __syncthreads();                                                 // the first stage is there
+    uint32_t c_slot = 0;
+    for (uint32_t hi = 0; hi < n_half; hi++) {
+        const uint32_t t = first + (hi >> 1) * stride, j = hi & 1u;
+        i32x16 acc[2][2];                                            // [hi, lo][query half]
+        i32x4 b[2];                                                  // this step's B operand and the next one's
+        i32x4 al[4];                                                 // a step's A operands out of LDS (the last LSTEPS steps)
+#pragma unroll
+        for (int st = 0; st < NSTG; st++) {
+            wait_vmcnt<NST - 3>();                                   // this wave's request of the NEXT stage has landed
+            __syncthreads();                                         // ... and everybody's; the slot consumed before this one is free
+            const uint32_t slot1 = c_slot + 1 == (uint32_t)NST ? 0u : c_slot + 1;
+            const unsigned char* sp = &s_ring[0][0] + c_slot * kI8sStageBytes + lane16;
+            const unsigned char* sp1 = &s_ring[0][0] + slot1 * kI8sStageBytes + lane16;
+            if (st == 0) b[0] = *reinterpret_cast<const i32x4*>(sp);  // (once per block: the epilogue carries no operand across)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int s = 0; s < kI8sStageSteps; s++) {
+                const int gs = st * kI8sStageSteps + s;
+                const bool has_next = gs + 1 < STEPS;
+                const unsigned char* np = s + 1 < kI8sStageSteps ? sp + (s + 1) * 1024 : sp1;
+                const bool ag = gs < ASTEPS, lds_a = gs >= RSTEPS, lds_an = gs + 1 >= RSTEPS && gs + 1 < STEPS;
+                const int ln = gs + 1 - RSTEPS >= 0 && lds_an ? gs + 1 - RSTEPS : 0;
+                const i32x4& bb = b[gs & 1];
+#define QV_I8_A(O) (ag ? Aa[ag ? gs : 0][O] : (lds_a ? al[O] : Av[!ag && !lds_a ? gs - ASTEPS : 0][O]))
+#define QV_I8_MF(ACC, O) { if (gs == 0) { if (ag) mfma_i8<true, true>(ACC, QV_I8_A(O), bb); else mfma_i8<false, true>(ACC, QV_I8_A(O), bb); } \
+                           else if (ag) mfma_i8<true, false>(ACC, QV_I8_A(O), bb); else mfma_i8<false, false>(ACC, QV_I8_A(O), bb); }
+                QV_I8_MF(acc[0][0], 0)
+                if (has_next) b[(gs + 1) & 1] = *reinterpret_cast<const i32x4*>(np);   // the next step's operand is requested
+                if (lds_an) al[0] = s_a[wave][ln][0][lane];
+                __builtin_amdgcn_sched_barrier(0);
+                QV_I8_MF(acc[0][1], 1)
+                if (s == 1) request_stage();                         // one row request per stage and wave
+                if (lds_an) al[1] = s_a[wave][ln][1][lane];
+                __builtin_amdgcn_sched_barrier(0);
+                QV_I8_MF(acc[1][0], 2)
+                if (lds_an) al[2] = s_a[wave][ln][2][lane];
+                __builtin_amdgcn_sched_barrier(0);
+                QV_I8_MF(acc[1][1], 3)
+                if (lds_an) al[3] = s_a[wave][ln][3][lane];
+                __builtin_amdgcn_sched_barrier(0);
+#undef QV_I8_MF
+#undef QV_I8_A
+            }
+            c_slot = slot1;
+        }
+        const uint32_t* rc = s_rc[(hi >> 1) & (kI8sRcTiles - 1)];
+        const double rnd = *reinterpret_cast<const double*>(rc + 2 * (32 * j + l31));
+        const float rsc = __uint_as_float(rc[128 + 32 * j + l31]), rho = __uint_as_float(rc[192 + 32 * j + l31]);
+        const uint64_t alv = *reinterpret_cast<const uint64_t*>(rc + 256 + 64 * wave);
+        // the last matrix instructions' results, before vector instructions read them (20 wait states; the statement names the accumulators so
+        // that nothing that reads them is scheduled ahead of it)
+        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]));
+        const uint32_t row = t * 64 + 32 * j + l31;
+        const bool live = (alv >> (32 * j + l31)) & 1ull;
+        const float rn = bound_f32_up((float)rnd);
+        const bool unsure = int8_filter_row_unsure(rn, rsc, rho, tiny);
+        uint32_t n = 0;
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            f16v a;
+#pragma unroll
+            for (int e = 0; e < 16; e++) a[e] = int8_filter_score(acc[0][i][e], acc[1][i][e], kw.sq[half][i][e], rsc);
+            const float m0 = __builtin_fmaxf(__builtin_fmaxf(a[0], a[1]), a[2]), m1 = __builtin_fmaxf(__builtin_fmaxf(a[3], a[4]), a[5]);
+            const float m2 = __builtin_fmaxf(__builtin_fmaxf(a[6], a[7]), a[8]), m3 = __builtin_fmaxf(__builtin_fmaxf(a[9], a[10]), a[11]);
+            const float m4 = __builtin_fmaxf(__builtin_fmaxf(a[12], a[13]), a[14]);
+            const float mx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(m0, m1), m2), __builtin_fmaxf(__builtin_fmaxf(m3, m4), a[15]));
+            // level 1: the threshold is monotone in cm (up), m and b (down), so this is a lower bound of the block's 16 thresholds
+            const float thr_lo = int8_filter_threshold<METRIC>(cmin[i], mmax[i], bmax[i], rn, rho);
+            const uint64_t pm = __ballot((!(mx < thr_lo) || unsure) && live);
+            if (__builtin_expect(pm != 0, 0)) epi_dump_with(a, pm, row, rn, rho, (uint32_t)i, half, unsure, keep, qglobal, cqu, cqu_n, cqu_out, du, n);
+        }
+        if (n) epi_dense_pass_with(du, n, keep, qglobal, cqu, cqu_n, cqu_out);
+    }
+    wait_vmcnt<0>();                                                 // the requests past the end, before the workgroup's LDS is released
+    cand_flush(cqu, cqu_n, cqu_out);
+}
+
+// Which dimensions have an instantiation: 128, 384, 512 and 768 (<STEPS, in accumulation registers, in LDS, ring stages>; 768 dimensions keep 16
+// steps' operands in the 256 accumulation registers, 6 in vector registers and 2 in LDS — profiles/int8_shared_resources.txt).  Every other
+// dimension the int8 filter serves keeps k_int8_filter; 800 - 1024 in any case: their operands do not fit.
+bool int8_shared_has_dim(uint32_t dim) { return dim == 128 || dim == 384 || dim == 512 || dim == 768; }
+
+hipError_t launch_int8_shared_filter(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq_pad, uint32_t* cand, float* cscore, uint32_t* cnt,
+                                     uint32_t grid, hipStream_t s) {
+    const uint32_t groups = nq_pad >> 8;
+    if (v.plane8 == nullptr || v.rscale8 == nullptr || v.rres8 == nullptr || !int8_shared_has_dim(v.dim) || (v.metric != QV_COSINE && v.metric != QV_DOT)) return hipErrorInvalidValue;   // (a missing route is an error)
+    if (groups == 0 || (nq_pad & 255u) || grid == 0 || grid % groups) return hipErrorInvalidValue;
+    const uint4* q8 = static_cast<const uint4*>(Q8);
+    const float* sq32 = reinterpret_cast<const float*>(static_cast<const char*>(Q8) + (size_t)nq_pad * 2 * v.dim);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, v, q8, sq32, cq, mq, nq_pad, cand, cscore, cnt);
+        return hipGetLastError();
+    };
+    auto by_dim = [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        switch (v.dim) {
+            case 128: return go(k_int8_shared_filter<M, 4, 4, 0, 8>);
+            case 384: return go(k_int8_shared_filter<M, 12, 12, 0, 12>);
+            case 512: return go(k_int8_shared_filter<M, 16, 16, 0, 16>);
+            default:  return go(k_int8_shared_filter<M, 24, 16, QV_INT8_SHARED_LSTEPS, 16>);
+        }
+    };
+    return v.metric == QV_COSINE ? by_dim(std::integral_constant<int, QV_COSINE>{}) : by_dim(std::integral_constant<int, QV_DOT>{});
+}
+
 // the batch's counters, behind its last kernel: batches, queries, queries handed back (their redo flags)
-__global__ void __launch_bounds__(256) k_int8_filter_count(const uint32_t* __restrict__ redo, uint32_t nq, uint32_t* __restrict__ stats) {
+// shared: the main filter was the shared-row form — counted in its own words too, so that kInt8FilterStatsWord's count BOTH forms
+__global__ void __launch_bounds__(256) k_int8_filter_count(const uint32_t* __restrict__ redo, uint32_t nq, uint32_t* __restrict__ stats, uint32_t shared) {
     uint32_t n = 0;
     for (uint32_t q = threadIdx.x; q < nq; q += 256) n += redo[q] ? 1u : 0u;
     if (n) (void)atomicAdd(&stats[kInt8FilterStatsWord + 2], n);
     if (threadIdx.x == 0) { (void)atomicAdd(&stats[kInt8FilterStatsWord], 1u); (void)atomicAdd(&stats[kInt8FilterStatsWord + 1], nq); }
+    if (threadIdx.x == 0 && shared) { (void)atomicAdd(&stats[kInt8SharedStatsWord], 1u); (void)atomicAdd(&stats[kInt8SharedStatsWord + 1], nq); }
 }
-hipError_t launch_int8_filter_count(const uint32_t* d_redo, uint32_t nq, uint32_t* d_stats, hipStream_t s) {
-    hipLaunchKernelGGL(k_int8_filter_count, dim3(1), dim3(256), 0, s, d_redo, nq, d_stats);
+hipError_t launch_int8_filter_count(const uint32_t* d_redo, uint32_t nq, uint32_t* d_stats, bool shared, hipStream_t s) {
+    hipLaunchKernelGGL(k_int8_filter_count, dim3(1), dim3(256), 0, s, d_redo, nq, d_stats, shared ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -24,34 +24,9 @@
 // the kernel (1.47 under the bare chain of its matrix instructions, 255 us) — it is at its power limit, and what was saved is energy:
 // the query operands' L2 -> L1 traffic and half the LDS reads.
 #include "qv_filter.h"
+#include "qv_lds_dma.h"
 
 namespace qv {
-
-typedef __attribute__((address_space(3))) unsigned char qlds_u8;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// one 1-KiB request of a stage: lane l moves bytes [16 l, 16 l + 16); src (wave-uniform) and the LDS byte address both take `off`.
-// (The same request through a buffer descriptor — base in the descriptor, the piece's offset in a scalar register — measures the same:
-// 518 / 393 us against 517 / 388; what a request costs the issuing wave, ~55 ns, is not its address arithmetic.)
-template <int OFF>
-__device__ __forceinline__ void dma_piece(const void* src, uint32_t lane16, uint32_t lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\t"
-                 "s_nop 0\n\t"
-                 "global_load_lds_dwordx4 %0, %1 offset:%3 nt"
-                 :: "v"(lane16), "s"(src), "s"(lds_byte_addr), "n"(OFF) : "memory");   // (m0 is written; the compiler keeps nothing in it across statements in this kernel: no movrel, GWS or LDS-DMA builtins)
-}
-
-// 256 bytes, one dword per lane (byte offset voff from the wave-uniform src), to lds_byte_addr + 4 lane: the row constants of a tile
-__device__ __forceinline__ void dma_words(const void* src, uint32_t voff, uint32_t lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\t"
-                 "s_nop 0\n\t"
-                 "global_load_lds_dword %0, %1"
-                 :: "v"(voff), "s"(src), "s"(lds_byte_addr) : "memory");
-}
 
 // The matrix instruction from inline assembly: the A operand straight out of the accumulation registers (AG) — the compiler's own
 // allocation keeps what does not fit the 256 vector registers there too, but copies it out with four v_accvgpr_read before every

@@ -551,6 +551,21 @@ class DeviceIndex:
         check(lib().qv_index_int8_filter_stats(self._h, out))
         return tuple(int(x) for x in out)
 
+    INT8_FORMS = {"auto": 0, "shared": 1, "blocks": 2}
+
+    def set_int8_form(self, mode):
+        """which of the int8 filter's two kernels a batch of more than 128 queries takes: "shared" — the shared-row kernel (256 queries'
+        operands resident in registers, the plane read once per group) wherever it applies (batched_int8_form), "blocks" — the block kernel
+        only, "auto" — the measured cells (qv_index_set_int8_form)"""
+        check(lib().qv_index_set_int8_form(self._h, self.INT8_FORMS.get(mode, mode)))
+
+    def int8_shared_stats(self) -> tuple:
+        """(batches whose main filter was the int8 filter's shared-row kernel, their queries) — int8_filter_stats counts them too; waits for the
+        device (qv_index_int8_shared_stats)"""
+        out = (C.c_uint64 * 2)()
+        check(lib().qv_index_int8_shared_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
     FILTERED_BATCH = {"auto": 0, "always": 1, "never": 2}
 
     def set_filtered_batch(self, mode, sparse_ppm=None):
