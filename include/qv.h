@@ -447,8 +447,9 @@ int qv_index_set_filter(qv_index* idx, int filter);
  * threshold — the 8-bit bound scan's interval (qv_scan_bound_interval8) plus the float32 roundings of the kernel's epilogue.  The exact
  * re-score decides as ever, so rows, float32 bits, order, counts and padding are what every other filter returns.
  * The kernel runs only where ALL of these hold: the metric is QV_COSINE or QV_DOT; the index holds the 8-bit plane; the dimension is a
- * multiple of 32 from 64 to 1024; the batched path itself takes the batch; the batch carries no row sets or where-filters.  Everywhere else
- * (QV_L2 with or without QV_FLAG_L2_SCAN_PLANE, QV_FLAG_NO_SCAN_PLANE, other dimensions, filtered batches — their kernels are what
+ * multiple of 32 from 64 to 1024; the batched path itself takes the batch; the batch carries no row sets or where-filters — or it does and
+ * the index asked for the sets form (qv_index_set_int8_filtered, below).  Everywhere else
+ * (QV_L2 with or without QV_FLAG_L2_SCAN_PLANE, QV_FLAG_NO_SCAN_PLANE, other dimensions, filtered batches without that mode — their kernels are what
  * qv_batched_filter_route reports for QV_FILTER_AUTO; that export and qv_batched_applies_filtered* keep taking 0 .. 4 only) the batch runs exactly
  * as under QV_FILTER_AUTO.
  * QV_FILTER_AUTO never chooses this kernel.
@@ -489,6 +490,29 @@ int qv_batched_int8_keeps(int metric, uint32_t dim, int32_t isum_hi, int32_t isu
 int qv_index_set_int8_form(qv_index* idx, int mode);
 int qv_index_int8_shared_stats(qv_index* idx, uint64_t out[2]);
 int qv_batched_int8_form(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_plane8, int mode);
+
+/* ---- QV_FILTER_INT8 under filters: the sets form ----
+ * A filtered batch (below: 9 or more queries, a row set, no set or a where-filter per query) keeps its bfloat16 / float32 filter kernels under
+ * QV_FILTER_INT8 alone.  qv_index_set_int8_filtered moves it onto the int8 kernel's sets form: a pre-pass lists, per block of 64 queries, the
+ * tiles in which some query of the block selects a live row; the kernel reads the 8-bit plane of those tiles only, and tests every (query, row)
+ * pair against the query's set before it can become a candidate.  Results are what the exact filtered scan returns for live & set_q, as with
+ * every other filter.  Whether a filtered call goes batched at all stays with qv_index_set_filtered_batch / _wide; this setter only says which
+ * kernel filters it.  The rule: qv_batched_int8_applies holds for the piece, the filtered batch has a route for that k (up to 1024), and the mode
+ * says so — QV_INT8_FILTERED_ALWAYS wherever the rule holds, QV_INT8_FILTERED_NEVER nowhere, QV_INT8_FILTERED_AUTO (the default) only in measured
+ * cells, of which there are none yet: the kernel has not been measured against the present filters.  A filtered piece always takes the block
+ * kernel, whatever qv_index_set_int8_form says.  Needs external exclusion against running searches, like qv_index_set_filter.  The environment
+ * variable QV_INT8_FILTERED (1 / 2, read once per process) sets the default of indexes that never call this.
+ * qv_index_int8_filtered_stats: out[0] = filtered batches whose main filter was the int8 kernel, out[1] = their queries, out[2] = (block, tile)
+ * visits the tile lists skipped, out[3] = visits possible (blocks that hold a real query x tiles).  Waits for the device; a batch counts once its
+ * kernels have run.  qv_index_int8_filter_stats counts these batches too.
+ * qv_batched_int8_applies_filtered: the rule on the host, without an index or a device: 1 or 0; QV_ERR_INVALID_ARG (< 0) for a mode or filter
+ * outside their ranges. */
+#define QV_INT8_FILTERED_AUTO   0
+#define QV_INT8_FILTERED_ALWAYS 1
+#define QV_INT8_FILTERED_NEVER  2
+int qv_index_set_int8_filtered(qv_index* idx, int mode);
+int qv_index_int8_filtered_stats(qv_index* idx, uint64_t out[4]);
+int qv_batched_int8_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_plane8, int mode);
 
 /* ---- filtered batches: 9 or more queries, a filter per query, on the batched path ----
  * A call — or a pass that concurrent callers share — of 9 or more queries, k <= 64, through qv_index_search_rowsets or

@@ -70,6 +70,17 @@ def batched_int8_form(metric, dim: int, rows: int, nq: int, k: int, filter="int8
     return rc
 
 
+def batched_int8_applies_filtered(metric, dim: int, rows: int, nq: int, k: int, filter="int8", has_plane8: bool = True, mode="auto") -> bool:
+    """whether a FILTERED batch of nq queries would take the int8 kernel's sets form — the dispatch's own rule, on the host
+    (qv_batched_int8_applies_filtered); mode: as set_int8_filtered takes it"""
+    from ._lib import check
+    m = metric_id(metric) if isinstance(metric, str) else int(metric)
+    rc = lib().qv_batched_int8_applies_filtered(m, dim, rows, nq, k, DeviceIndex.FILTERS.get(filter, filter), 1 if has_plane8 else 0, DeviceIndex.INT8_FILTERED.get(mode, mode))
+    if rc < 0:
+        check(rc)
+    return rc == 1
+
+
 def batched_applies_filtered_wide(metric, dim: int, rows: int, nq: int, k: int, filter="auto", mode="auto", n_not_sparse: int | None = None) -> bool:
     """the same rule for 65 to 1024 results per query (qv_batched_applies_filtered_wide); mode: as set_filtered_batch_wide takes it"""
     from ._lib import check
@@ -93,4 +104,4 @@ def batched_filter_route(metric, dim: int, rows: int, nq: int, k: int, filter="a
 
 
 __all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq", "scan_bound8_applies_filtered_mq",
-           "batched_applies_filtered", "batched_int8_applies", "batched_int8_form", "batched_applies_filtered_wide", "batched_filter_route", "graph_reject_applies", "graph_reject_image_applies"]
+           "batched_applies_filtered", "batched_int8_applies", "batched_int8_form", "batched_int8_applies_filtered", "batched_applies_filtered_wide", "batched_filter_route", "graph_reject_applies", "graph_reject_image_applies"]

@@ -132,6 +132,9 @@ PROTOTYPES = {
     "qv_index_set_int8_form": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_int8_shared_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_batched_int8_form": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
+    "qv_index_set_int8_filtered": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_int8_filtered_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_batched_int8_applies_filtered": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "qv_index_set_bound_plane6": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_sharded_set_bound_plane6": (C.c_int, [C.c_void_p, C.c_int]),
     "qv_index_bound_scan6_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -1521,7 +1521,7 @@ static int rowsets_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, u
             if (!d_sets || !d_flags_out) return fail(QV_ERR_DEVICE, "filtered batch without its set table");
             const ProfilePair pp = profile_begin(idx);
             const qv::BatchedSets bs{d_sets + p.q0, qv::filtered_batch_ppm(idx->filtered_batch_ppm), idx->n_live};
-            hipError_t e = qv::launch_batched(v, plan, q, p.nq, k, ws, r_out, d_out, d_flags_out, idx->cus, s, pp.ev0, pp.ev1, &bs);
+            hipError_t e = qv::launch_batched(v, plan, q, p.nq, k, ws, r_out, d_out, d_flags_out, idx->cus, s, pp.ev0, pp.ev1, &bs, idx->d_bound_stats, idx->int8_form, idx->int8_filtered);
             profile_end(idx, pp, e == hipSuccess);
             if (e != hipSuccess) return fail(QV_ERR_DEVICE, "filtered batch launch failed: %s", hipGetErrorString(e));
             continue;
@@ -2187,6 +2187,29 @@ int qv_batched_int8_form(int metric, uint32_t dim, uint64_t rows, uint32_t nq, u
     const uint32_t tail = short_tail(piece);
     if (tail && (tail <= 8 || qv::batched_int8_applies(metric, dim, rows, tail, k, filter, has_plane8 != 0))) piece -= tail;
     return qv::batched_int8_form(metric, dim, rows, piece, k, filter, has_plane8 != 0, mode);
+}
+
+int qv_index_set_int8_filtered(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_INT8_FILTERED_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (the int8 sets kernel wherever its rule holds) or 2 (never); got %d", mode);
+    idx->int8_filtered = mode;
+    return QV_OK;
+}
+
+int qv_index_int8_filtered_stats(qv_index* idx, uint64_t out[4]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t h[6] = {0, 0, 0, 0, 0, 0};
+    HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kInt8FilteredStatsWord, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1]; out[2] = (uint64_t)h[2] | (uint64_t)h[3] << 32; out[3] = (uint64_t)h[4] | (uint64_t)h[5] << 32;
+    return QV_OK;
+}
+
+int qv_batched_int8_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, int has_plane8, int mode) {
+    if (mode < 0 || mode > QV_INT8_FILTERED_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    if (filter < QV_FILTER_AUTO || filter > QV_FILTER_INT8) return fail(QV_ERR_INVALID_ARG, "filter must be one of QV_FILTER_*; got %d", filter);
+    return qv::batched_int8_applies_filtered(metric, dim, rows, nq, k, filter, has_plane8 != 0, mode) ? 1 : 0;
 }
 
 int qv_batched_int8_keeps(int metric, uint32_t dim, int32_t isum_hi, int32_t isum_lo, double sq, double qn, double qres, float U, double rn,

@@ -91,6 +91,7 @@ struct qv_index {
     uint64_t flags = 0;
     int filter = 0;                            // qv_index_set_filter
     int int8_form = 0;                         // qv_index_set_int8_form: QV_INT8_FORM_*
+    int int8_filtered = 0;                     // qv_index_set_int8_filtered: QV_INT8_FILTERED_*
     uint32_t n_rows = 0, n_live = 0;
     uint64_t row_writes = 0;                   // bumped by every call that writes row CONTENTS (add / update): copies kept elsewhere (a graph's hubs) compare it
     uint64_t cap_tiles = 0;

@@ -2814,6 +2814,25 @@ int batched_int8_form(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint
     if (!batched_int8_applies(metric, dim, rows, nq, k, filter, has_plane8)) return 0;
     return int8_shared_route(metric, dim, rows, nq, batched_nq_pad(nq, shape_view(metric, dim, rows, filter)), mode) ? 2 : 1;
 }
+// A batch WITH sets on the int8 kernel's sets form (k_int8_filter<., ., ., true> behind k_int8_tiles): int8_shape, the filtered batch's own route, and
+// a mode of its own (qv_index_set_int8_filtered; QV_INT8_FILTERED, 1 / 2, read once, is the default of indexes that never called the setter), so
+// that QV_FILTER_INT8 alone leaves a filtered batch on the kernels it had.  Always the block kernel, whatever qv_index_set_int8_form says.  The
+// tile lists alias the sample's scores (L.sscore: every selection that reads them has run before k_mfma_prep's second launch), 64 sample_rows words
+// per block for n_tiles + 1 — which every plan's sample gives (at least 8192 rows, and n_rows / 1536 of them); a forced smaller one declines.
+// Unmeasured: the automatic mode takes no cell (kInt8FilteredAuto).
+constexpr bool kInt8FilteredAuto = false;
+static int int8_filtered_mode(int mode) { static const int env_mode = env_int("QV_INT8_FILTERED", 0); return mode ? mode : (env_mode == 1 || env_mode == 2 ? env_mode : 0); }
+static bool int8_filtered_route(const BatchedRoute& r, const IndexView& v, bool has_plane8, int mode) {
+    mode = int8_filtered_mode(mode);
+    if (mode == QV_INT8_FILTERED_NEVER || (mode != QV_INT8_FILTERED_ALWAYS && !kInt8FilteredAuto)) return false;
+    return int8_shape(v.metric, v.dim, v.filter, has_plane8) && batched_sets_route(r) && (uint64_t)64 * r.sample_rows >= (uint64_t)v.n_tiles + 64;
+}
+bool batched_int8_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8, int mode) {
+    if (!batched_int8_applies(metric, dim, rows, nq, k, filter, has_plane8) || k > kFilteredBatchWideMaxK) return false;
+    const IndexView v = shape_view(metric, dim, rows, filter);
+    BatchedRoute r;
+    return plan_batched(v, nq, k, 1, true, r) && int8_filtered_route(r, v, has_plane8, mode);
+}
 bool batched_sets_wide_supported(const IndexView& v, uint32_t nq, uint32_t k, int cus) {
     BatchedRoute r;
     return k > (uint32_t)kMaxFusedK && k <= kFilteredBatchWideMaxK && batched_supported(v, nq, k) && plan_batched(v, nq, k, cus, true, r) && batched_sets_route(r);
@@ -2960,12 +2979,19 @@ static void batched_prep(const IndexView& v, const BatchedRoute& r, const Batche
 }
 
 // 3. MFMA filter
-// sets: a filtered batch — the kernels' flush variant that tests every record against its query's set (CandOutT<true>, qv_filter.h); an unfiltered
-// batch launches exactly the instantiations it launched before
-static hipError_t batched_filter(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, hipStream_t s, bool sets = false) {
+// sets: a filtered batch — the kernels' flush variant that tests every record against its query's set (CandOutT<true>, qv_filter.h), or, on the int8
+// route (int8_filtered_route), the sets form that tests in its epilogue and skips tiles; an unfiltered batch launches exactly the instantiations it
+// launched before
+static hipError_t batched_filter(const IndexView& v, const BatchedRoute& r, const BatchedLayout& L, hipStream_t s, const RowSetRef* sets = nullptr) {
     const uint4* Qbf = reinterpret_cast<const uint4*>(L.Qt);
     if (r.filter == MainFilter::qreg) return sets ? hipErrorNotSupported : launch_qreg_filter(v, Qbf, L.cq, L.mq, r.nq_pad, L.cand, L.cscore, L.cnt, r.bfrows, r.cus, s);
-    if (r.filter == MainFilter::int8_plane) return sets ? hipErrorNotSupported : launch_int8_filter(v, L.Qt, L.cq, L.mq, r.nq, r.nq_pad, L.cand, L.cscore, L.cnt, r.filter_grid, r.filter_lds, s);
+    if (r.filter == MainFilter::int8_plane && sets) {                // the sets form: the pre-pass's tile lists, then the kernel that walks them (part of the filter's time)
+        uint32_t* tile_cnt = reinterpret_cast<uint32_t*>(L.sscore);   // (int8_filtered_route: the sample's scores are spent, and hold them)
+        uint32_t* tile_list = tile_cnt + (r.nq_pad / 64 + 63) / 64 * 64;
+        const hipError_t e = launch_int8_tiles(v, sets, r.nq, tile_list, tile_cnt, s);
+        return e != hipSuccess ? e : launch_int8_filter_sets(v, L.Qt, L.cq, L.mq, r.nq, r.nq_pad, L.cand, L.cscore, L.cnt, tile_list, tile_cnt, r.filter_grid, r.filter_lds, s);
+    }
+    if (r.filter == MainFilter::int8_plane) return launch_int8_filter(v, L.Qt, L.cq, L.mq, r.nq, r.nq_pad, L.cand, L.cscore, L.cnt, r.filter_grid, r.filter_lds, s);
     if (r.filter == MainFilter::int8_shared) return sets ? hipErrorNotSupported : launch_int8_shared_filter(v, L.Qt, L.cq, L.mq, r.nq_pad, L.cand, L.cscore, L.cnt, r.filter_grid, s);
     // every filter kernel takes the same arguments (the operands as float32 or bfloat16 planes), some a sample's after them
     auto go = [&](auto kernel, auto* Q, uint32_t block, auto... sample_args) {
@@ -3074,14 +3100,17 @@ static hipError_t batched_exact(const IndexView& v, const BatchedRoute& r, const
 
 hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_queries, uint32_t nq, uint32_t k, void* d_ws,
                           uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
-                          hipEvent_t ev0, hipEvent_t ev1, const BatchedSets* sets, uint32_t* d_stats, int int8_form) {
+                          hipEvent_t ev0, hipEvent_t ev1, const BatchedSets* sets, uint32_t* d_stats, int int8_form, int int8_filtered) {
     BatchedRoute r;
     if (!plan_batched(v, nq, k, cus, (reinterpret_cast<uintptr_t>(d_queries) & 15u) == 0, r)) return hipErrorNotSupported;
     const RowSetRef* d_sets = sets ? sets->d_sets : nullptr;
-    // the int8 filter, decided once: an unfiltered batch of an index that asks for it and holds the plane.  Behind it a candidate's interval is
+    // the int8 filter, decided once: an unfiltered batch of an index that asks for it and holds the plane — or a batch with sets under
+    // QV_INT8_FILTERED_* (int8_filtered_route), always on the block kernel.  Behind it a candidate's interval is
     // eq[0] |r| + eq[1] rres8(row): the exact stage reads its residuals through a view whose array is the 8-bit plane's.
-    const bool int8 = !d_sets && int8_shape(v.metric, v.dim, v.filter, v.plane8 != nullptr && v.rscale8 != nullptr && v.rres8 != nullptr);
-    if (int8) batched_int8_adapt(r, v, int8_form);
+    const bool has_plane8 = v.plane8 != nullptr && v.rscale8 != nullptr && v.rres8 != nullptr;
+    const bool int8 = d_sets ? int8_filtered_route(r, v, has_plane8, int8_filtered) : int8_shape(v.metric, v.dim, v.filter, has_plane8);
+    if (int8) batched_int8_adapt(r, v, d_sets ? QV_INT8_FORM_BLOCKS : int8_form);
+    if (int8 && d_sets) r.filter_lds = int8_filter_sets_lds_bytes(v.dim);
     IndexView vx = v;
     if (int8) vx.rres = v.rres8;
     if (d_sets && !batched_sets_route(r)) return hipErrorNotSupported;   // (a missing route is an error, never an unfiltered answer)
@@ -3100,9 +3129,10 @@ hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_
         if (e != hipSuccess) return e;
     }
     if (ev0) (void)hipEventRecord(ev0, s);
-    e = batched_filter(v, r, L, s, d_sets != nullptr);
+    e = batched_filter(v, r, L, s, d_sets);
     if (e != hipSuccess) return e;
     if (ev1) (void)hipEventRecord(ev1, s);
+    if (int8 && d_sets && d_stats) { e = launch_int8_filtered_count(reinterpret_cast<const uint32_t*>(L.sscore), nq, v.n_tiles, d_stats, s); if (e != hipSuccess) return e; }
     e = batched_exact(vx, r, L, d_queries, d_rows_out, d_dist_out, s);
     if (e != hipSuccess) return e;
     if (int8 && d_stats) { e = launch_int8_filter_count(L.ovf, nq, d_stats, r.filter == MainFilter::int8_shared, s); if (e != hipSuccess) return e; }

@@ -13,6 +13,8 @@
 //      flush then drops.  Below a share of sparse_ppm millionths (counted here, on the sample) that work outgrows the exact row-set
 //      scan's: k_sets_sparse gives such a query the padded queries' constants (+inf threshold, nothing passes) and flags it for the
 //      host's redo.  A mis-route costs time, never bits.
+// (The int8 kernel's sets form — qv_int8.hip, opt-in — is the one filter that knows the sets: it replaces 2's flush test and reads no tile that
+// no query of a block selects; 1 and 3 stand in front of it unchanged.)
 #include "qv_kernels.h"
 
 namespace qv {

@@ -411,7 +411,8 @@ hipError_t launch_batched(const IndexView& v, const ScanPlan& p, const float* d_
                           uint32_t* d_rows_out, float* d_dist_out, uint32_t** d_overflow_out, int cus, hipStream_t s,
                           hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const struct BatchedSets* sets = nullptr,
                           uint32_t* d_stats = nullptr /* the index's counter words: an unfiltered batch under QV_FILTER_INT8 counts itself at kInt8FilterStatsWord */,
-                          int int8_form = 0 /* QV_INT8_FORM_* (qv_index_set_int8_form) */);
+                          int int8_form = 0 /* QV_INT8_FORM_* (qv_index_set_int8_form) */,
+                          int int8_filtered = 0 /* QV_INT8_FILTERED_* (qv_index_set_int8_filtered): a batch with sets on the int8 kernel's sets form */);
 // A filtered batch, k <= kMaxFusedK: query q over alive & d_sets[q] (a DEVICE array of nq sets; null bits = every row).  The sample's bound is
 // taken over the set, the filter's flush drops rows outside it, and a query whose set holds fewer than sparse_ppm millionths of the sample's
 // rows is handed back without candidates (0: never).  With sets, *d_overflow_out -> [2][nq]: the redo flags, then 1 = handed back as sparse
@@ -454,14 +455,18 @@ hipError_t launch_qreg_filter(const IndexView& v, const uint4* Qbf, const float*
                               uint32_t* cnt, bool bfrows, int cus, hipStream_t s);
 
 // The int8 matrix-core filter on the 8-bit plane (qv_int8.hip; QV_FILTER_INT8).  The rule: the index asks for it, cosine or dot, plane8 held, a
-// dimension that is a multiple of 32 from 64 to 1024, and the batched path itself applies; a batch with sets never takes it (launch_batched).
+// dimension that is a multiple of 32 from 64 to 1024, and the batched path itself applies; a batch with sets takes its sets form, and only under
+// QV_INT8_FILTERED_* (batched_int8_applies_filtered).
 bool batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8);
 // the index's counter words: 0 - 3 the bound scan, kBound8StatsWord 4 - 6, kBound6StatsWord 7 - 9, kBoundWideStatsWord 10 - 12, kBoundWideMqStatsWord 13 - 15, and
 // the int8 filter's own: [16] batches whose main filter was k_int8_filter, [17] their queries, [18] those handed back
 constexpr uint32_t kInt8FilterStatsWord = 16;
 // ... and of those, the shared-row form's: [19] batches whose main filter was k_int8_shared_filter, [20] their queries
 constexpr uint32_t kInt8SharedStatsWord = 19;
-constexpr uint32_t kIndexStatsWords = 22;      // what the index allocates (and clears) for all of them
+// ... and a FILTERED batch's on the sets form: [22] batches, [23] their queries, [24 - 25] (block, tile) visits skipped, [26 - 27] visits possible (64-bit)
+constexpr uint32_t kInt8FilteredStatsWord = 22;
+constexpr uint32_t kIndexStatsWords = 28;      // what the index allocates (and clears) for all of them
+static_assert(kInt8SharedStatsWord + 2 <= kInt8FilteredStatsWord && kInt8FilteredStatsWord % 2 == 0 && kInt8FilteredStatsWord + 6 <= kIndexStatsWords, "the sets form's counters: 64-bit words, inside the allocation");
 static_assert(kInt8FilterStatsWord + 3 <= kInt8SharedStatsWord, "the int8 filter's counters end where the shared-row form's begin");
 static_assert(kInt8SharedStatsWord + 2 <= kIndexStatsWords, "the int8 filter's counters lie inside the allocation");
 size_t int8_filter_lds_bytes(uint32_t dim);
@@ -469,6 +474,18 @@ size_t int8_filter_lds_bytes(uint32_t dim);
 hipError_t launch_int8_filter(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq, uint32_t nq_pad, uint32_t* cand, float* cscore,
                               uint32_t* cnt, uint32_t grid_x /* workgroups per 64-query block */, size_t lds, hipStream_t s);
 hipError_t launch_int8_filter_count(const uint32_t* d_redo, uint32_t nq, uint32_t* d_stats, bool shared, hipStream_t s);
+// The sets form, for a filtered batch (QV_INT8_FILTERED_*).  launch_int8_tiles: per 64-query block that holds a real query, the tiles in which
+// some real query of the block selects a live row — tile_list[block][n_tiles] in any order, tile_cnt[block].  launch_int8_filter_sets:
+// k_int8_filter walking those lists, each (query, row) pair tested against the query's set in the epilogue (d_sets reaches it through the words
+// in front of the counters, as every flush variant's).  launch_int8_filtered_count: the batch's counters at kInt8FilteredStatsWord.
+size_t int8_filter_sets_lds_bytes(uint32_t dim);
+hipError_t launch_int8_tiles(const IndexView& v, const RowSetRef* d_sets, uint32_t nq, uint32_t* tile_list, uint32_t* tile_cnt, hipStream_t s);
+hipError_t launch_int8_filter_sets(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq, uint32_t nq_pad, uint32_t* cand, float* cscore,
+                                   uint32_t* cnt, const uint32_t* tile_list, const uint32_t* tile_cnt, uint32_t grid_x, size_t lds, hipStream_t s);
+hipError_t launch_int8_filtered_count(const uint32_t* tile_cnt, uint32_t nq, uint32_t n_tiles, uint32_t* d_stats, hipStream_t s);
+// The rule for a batch with sets (qv_batched_int8_applies_filtered): batched_int8_applies, the filtered batch's own route for that k, and the mode
+// (QV_INT8_FILTERED_*: 0 = QV_INT8_FILTERED of the environment, else the measured cells — none yet)
+bool batched_int8_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8, int mode);
 // The shared-row form (k_int8_shared_filter): one workgroup per CU and 256-query group, the group's operands resident in registers, the plane read
 // once per group.  grid: a multiple of nq_pad / 256.  The same operands, constants and candidate lists as launch_int8_filter.
 bool int8_shared_has_dim(uint32_t dim);

@@ -20,6 +20,8 @@
 // and slots past the last row never pass (the alive words decide, not the plane's bytes); a live row the 8-bit bound says nothing about
 // (rres8 NaN, rscale8 0 or out of range, a norm that is vanishing or huge) always passes, with a NaN score so that nothing behind reads an
 // interval out of it.  Candidates leave through the wave's queue and cand_flush, as in every other filter kernel.
+// A FILTERED batch (a row set per query) takes the same kernel in its sets form (template parameter TS, behind k_int8_tiles; opt-in,
+// qv_index_set_int8_filtered): it reads only the tiles some query of the block selects and decides membership per (query, row) in the epilogue.
 #include "qv_filter.h"
 #include "qv_bound.h"
 #include "qv_lds_dma.h"
@@ -33,6 +35,11 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 #define QV_INT8_RING 6                                                // (8: 256 registers and 5 spilled, 24 bytes of scratch per lane)
 #endif
 constexpr int kInt8Ring = QV_INT8_RING;                               // steps in flight per wave
+#ifndef QV_INT8_SETS_RING
+#define QV_INT8_SETS_RING 6                                          // the sets form's own depth (profiles/int8_filtered_resources.txt)
+#endif
+constexpr int kInt8SetsRing = QV_INT8_SETS_RING;
+constexpr size_t kInt8SetWordBytes = 8 * 512;                         // the sets form: 64 set words per wave, behind the operands in LDS
 #ifndef QV_INT8_SHARED_LSTEPS
 #define QV_INT8_SHARED_LSTEPS 2                                      // the shared-row form at 768 dimensions: steps whose operands live in LDS
 #endif
@@ -49,17 +56,40 @@ template <int METRIC> struct Int8Keep {
     }
 };
 
+// The sets form's (TS): a (query, row) pair outside the query's set reaches the dump as kInt8OutOfSet — the epilogue writes it over the pair's score,
+// and no pair inside a set carries it (int8_in_set_score) — so membership is tested HERE, in front of `unsure`, which keeps a row whatever its score.
+constexpr uint32_t kInt8OutOfSet = 0xFF800000u;                       // -inf: never raises a block's maximum either
+template <int METRIC> struct Int8KeepSets {
+    const Int8Lds& k;
+    __device__ __forceinline__ bool operator()(uint32_t ql, float score, float rn, float rho, bool unsure) const {
+        return __float_as_uint(score) != kInt8OutOfSet && Int8Keep<METRIC>{k}(ql, score, rn, rho, unsure);
+    }
+};
+// a pair inside its query's set never carries the mark: a score of -inf says what -FLT_MAX says (below every threshold that is not -inf itself; no
+// interval is read out of either: k_rescore_select's |S| < 3e38)
+__device__ __forceinline__ float int8_in_set_score(float s) { return __float_as_uint(s) == kInt8OutOfSet ? -3.4028234663852886e38f : s; }
+
 // R: the ring's depth in steps.  DIV: the dimension's steps are a multiple of R, so no step of the unrolled ring is ever idle (768 dimensions:
 // 24 steps at R = 6): the loop body is then free of branches.  Every other step count — 1024 dimensions' 32 among them — runs the form whose idle
 // ring steps are skipped by wave-uniform branches.
-template <int METRIC, int R, bool DIV>
+// TS: the sets form, for a filtered batch (a row set per query).  Three things differ, all behind `if constexpr`, so that an unfiltered batch runs
+// the instructions it always ran.  The walk: a wave takes its share of the block's TILE LIST (k_int8_tiles below: the tiles in which some real query
+// of the block selects a live row) instead of every tile, and the ring runs on into the next LISTED tile — looked up one entry ahead, so the
+// number is there when a tile's last steps need it; an empty list: the block leaves before it copies an operand.  The set words: lane q of a wave
+// loads set_q's word of the tile beside the row constants (the block's 64 RowSetRefs sit in LDS behind the operands) and parks it in the wave's
+// 512-byte slot — [row block][query], so that the 16 queries of an accumulator block are four 16-byte LDS reads.  Level 1: a pair outside its
+// query's set gets kInt8OutOfSet for a score before the block maximum, and an unsure row passes only where one of the block's 16 queries holds
+// it; the dump carries the replaced scores and Int8KeepSets reads membership from them.  No out-of-set pair reaches the wave's queue, so the
+// flush is the plain one (CandOutT<false>): no set is read per record.
+template <int METRIC, int R, bool DIV, bool TS = false>
 __global__ void __launch_bounds__(512, 1)
 k_int8_filter(IndexView v, const uint4* __restrict__ Q8, const float* __restrict__ sq32, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq, uint32_t nq_pad,
-              uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt) {
+              uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt,
+              const uint32_t* __restrict__ tile_list, const uint32_t* __restrict__ tile_cnt /* TS: [blocks][n_tiles] and [blocks], k_int8_tiles */) {
     extern __shared__ __align__(16) unsigned char smem_i8[];
     uint4* s_a = reinterpret_cast<uint4*>(smem_i8);                  // [step][hi, lo][query half][lane]
     __shared__ __align__(16) Int8Lds s_k;
-    constexpr bool SETS = false;                                     // (a filtered batch never takes this kernel: launch_batched)
+    constexpr bool SETS = false;                                     // the flush never tests a set: a filtered batch (TS) decides membership in its epilogue
     QV_CAND_QUEUE(cqu, 8, 128);                                      // 12 KiB: the query operands take up to 128 KiB of the 160
     QV_EPI_DUMP(du, 8, 16);                                          // 10 KiB
     const uint32_t qb = blockIdx.y;
@@ -67,6 +97,18 @@ k_int8_filter(IndexView v, const uint4* __restrict__ Q8, const float* __restrict
     const uint32_t lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t steps = v.dim / 32, chunks = v.dim / 16;
+    uint32_t n_list = 0;
+    const uint32_t* list = nullptr;
+    uint32_t* s_sw = nullptr;                                         // TS: this wave's set words, [row block][query]
+    RowSetRef* s_rs = nullptr;                                        // TS: the block's sets (a padded query: an empty one)
+    if constexpr (TS) {
+        n_list = tile_cnt[qb];
+        if (n_list == 0) return;                                     // no tile holds a live row that a query of this block selects
+        list = tile_list + (size_t)qb * v.n_tiles;
+        s_sw = reinterpret_cast<uint32_t*>(smem_i8 + (size_t)v.dim * 128) + wave * 128;
+        s_rs = reinterpret_cast<RowSetRef*>(smem_i8 + (size_t)v.dim * 128 + kInt8SetWordBytes);
+        if (threadIdx.x < 64) s_rs[threadIdx.x] = 64 * qb + threadIdx.x < nq ? cand_sets(cand_cnt)[64 * qb + threadIdx.x] : RowSetRef{reinterpret_cast<const uint64_t*>(cand_cnt), 0u, 0u};
+    }
     for (uint32_t i = threadIdx.x; i < steps * 256; i += 512) s_a[i] = Q8[(size_t)qb * steps * 256 + i];
     if (threadIdx.x < 64) {
         const uint32_t ql = threadIdx.x, q = 64 * qb + ql, w = ql & 31u;
@@ -88,21 +130,36 @@ k_int8_filter(IndexView v, const uint4* __restrict__ Q8, const float* __restrict
         cmin[i] = cm; mmax[i] = mm; bmax[i] = bm;
     }
     const float tiny = filter_tiny_norm(v.dim);
-    const Int8Keep<METRIC> keep{s_k};
+    const std::conditional_t<TS, Int8KeepSets<METRIC>, Int8Keep<METRIC>> keep{s_k};
     const i32x4* plane = reinterpret_cast<const i32x4*>(v.plane8);
     const uint32_t gw = blockIdx.x * 8 + wave, tw = gridDim.x * 8;
+    // TS: `at` walks the list, g_next / g_next2 are the tiles one and two entries ahead (past the end: the last one again)
+    const uint32_t n_walk = TS ? n_list : v.n_tiles;
+    uint32_t last_at = 0, g_next = 0, g_next2 = 0;
+    auto listed = [&](uint32_t at) { return list[at < n_walk ? at : last_at]; };
+    if constexpr (TS) if (gw < n_walk) {
+        last_at = n_walk - 1 - (n_walk - 1 - gw) % tw;               // the wave's last entry, gw + m tw: in bounds, read by nobody when requested again
+        g_next = listed(gw); g_next2 = listed(gw + tw);
+    }
     // block j of tile t at step 0: chunk `half` of rows 32 j + l31; a step is two chunks on (128 pieces)
     auto base = [&](uint32_t t, int j) { return plane + ((size_t)t * chunks + half) * 64 + 32 * j + l31; };
     i32x4 rb[R][2];
     bool primed = false;
-    for (uint32_t g = gw; g < v.n_tiles; g += tw) {
-        const uint32_t gn = g + tw < v.n_tiles ? g + tw : g;       // past the wave's last tile: the same tile again (in bounds, read by nobody)
+    for (uint32_t at = gw; at < n_walk; at += tw) {
+        uint32_t g, gn;
+        if constexpr (TS) { g = g_next; gn = g_next2; g_next = g_next2; g_next2 = listed(at + 2 * tw); }
+        else { g = at; gn = g + tw < v.n_tiles ? g + tw : g; }       // past the wave's last tile: the same tile again (in bounds, read by nobody)
         const i32x4* p[2] = {base(g, 0), base(g, 1)};
         const i32x4* np[2] = {base(gn, 0), base(gn, 1)};
         double rnd[2]; float rsc[2], rho[2];
 #pragma unroll
         for (int j = 0; j < 2; j++) { const size_t row = (size_t)g * 64 + 32 * j + l31; rnd[j] = v.rnorm[row]; rsc[j] = v.rscale8[row]; rho[j] = v.rres8[row]; }
         const uint64_t alv = v.alive[g];
+        uint64_t setw = 0;                                           // TS: word g of set (64 qb + lane)
+        if constexpr (TS) {
+            const RowSetRef rs = s_rs[lane];
+            setw = rs.bits == nullptr ? ~0ull : (g < rs.words ? rs.bits[g] : 0ull);
+        }
         i32x16 acc[2][2][2];                                         // [hi, lo][query half][row block]
 #pragma unroll
         for (int t = 0; t < 2; t++)
@@ -144,6 +201,11 @@ k_int8_filter(IndexView v, const uint4* __restrict__ Q8, const float* __restrict
             }
         }
         uint32_t n = 0;
+        if constexpr (TS) {
+            __threadfence_block();                                   // (the last tile's reads of the slot, before these writes)
+            s_sw[lane] = (uint32_t)setw; s_sw[64 + lane] = (uint32_t)(setw >> 32);
+            __threadfence_block();
+        }
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const uint32_t row = g * 64 + 32 * j + l31;
@@ -153,15 +215,31 @@ k_int8_filter(IndexView v, const uint4* __restrict__ Q8, const float* __restrict
 #pragma unroll
             for (int i = 0; i < 2; i++) {
                 f16v a;
+                uint32_t held = 1u;                                  // TS: some query of this block's 16 holds the row
+                if constexpr (TS) {
+                    // the 16 queries 32 i + 4 half + (e & 3) + 8 (e >> 2): four runs of four words
+                    const uint4* wv = reinterpret_cast<const uint4*>(s_sw + 64 * j + 32 * i + 4 * half);
+                    const uint4 w0 = wv[0], w1 = wv[2], w2 = wv[4], w3 = wv[6];
+                    const uint32_t w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+                    const uint32_t bit = 1u << l31;
+                    held = 0u;
 #pragma unroll
-                for (int e = 0; e < 16; e++) a[e] = int8_filter_score(acc[0][i][j][e], acc[1][i][j][e], s_k.sq[half][i][e], rsc[j]);
+                    for (int e = 0; e < 16; e++) {
+                        const uint32_t in = w[e] & bit;
+                        held |= in;
+                        a[e] = in ? int8_in_set_score(int8_filter_score(acc[0][i][j][e], acc[1][i][j][e], s_k.sq[half][i][e], rsc[j])) : __uint_as_float(kInt8OutOfSet);
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 16; e++) a[e] = int8_filter_score(acc[0][i][j][e], acc[1][i][j][e], s_k.sq[half][i][e], rsc[j]);
+                }
                 const float m0 = __builtin_fmaxf(__builtin_fmaxf(a[0], a[1]), a[2]), m1 = __builtin_fmaxf(__builtin_fmaxf(a[3], a[4]), a[5]);
                 const float m2 = __builtin_fmaxf(__builtin_fmaxf(a[6], a[7]), a[8]), m3 = __builtin_fmaxf(__builtin_fmaxf(a[9], a[10]), a[11]);
                 const float m4 = __builtin_fmaxf(__builtin_fmaxf(a[12], a[13]), a[14]);
                 const float mx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(m0, m1), m2), __builtin_fmaxf(__builtin_fmaxf(m3, m4), a[15]));
                 // level 1: the threshold is monotone in cm (up), m and b (down), so this is a lower bound of the block's 16 thresholds
                 const float thr_lo = int8_filter_threshold<METRIC>(cmin[i], mmax[i], bmax[i], rn, rho[j]);
-                const uint64_t pm = __ballot((!(mx < thr_lo) || unsure) && live);
+                const uint64_t pm = __ballot((!(mx < thr_lo) || unsure) && live && (!TS || held != 0u));
                 if (__builtin_expect(pm != 0, 0)) epi_dump_with(a, pm, row, rn, rho[j], (uint32_t)i, half, unsure, keep, 64 * qb, cqu, cqu_n, cqu_out, du, n);
             }
         }
@@ -171,6 +249,7 @@ k_int8_filter(IndexView v, const uint4* __restrict__ Q8, const float* __restrict
 }
 
 size_t int8_filter_lds_bytes(uint32_t dim) { return (size_t)dim * 128; }
+size_t int8_filter_sets_lds_bytes(uint32_t dim) { return (size_t)dim * 128 + kInt8SetWordBytes + 64 * sizeof(RowSetRef); }
 
 hipError_t launch_int8_filter(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq, uint32_t nq_pad, uint32_t* cand, float* cscore,
                               uint32_t* cnt, uint32_t grid_x, size_t lds, hipStream_t s) {
@@ -182,12 +261,70 @@ hipError_t launch_int8_filter(const IndexView& v, const void* Q8, const float* c
     const float* sq32 = reinterpret_cast<const float*>(static_cast<const char*>(Q8) + (size_t)nq_pad * 2 * v.dim);
     auto go = [&](auto kernel) {
         const hipError_t e = set_lds(kernel, lds); if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, grid, dim3(512), lds, s, v, q8, sq32, cq, mq, nq, nq_pad, cand, cscore, cnt);
+        hipLaunchKernelGGL(kernel, grid, dim3(512), lds, s, v, q8, sq32, cq, mq, nq, nq_pad, cand, cscore, cnt, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
         return hipGetLastError();
     };
     const bool div = steps % kInt8Ring == 0;
     if (v.metric == QV_COSINE) return div ? go(k_int8_filter<QV_COSINE, kInt8Ring, true>) : go(k_int8_filter<QV_COSINE, kInt8Ring, false>);
     return div ? go(k_int8_filter<QV_DOT, kInt8Ring, true>) : go(k_int8_filter<QV_DOT, kInt8Ring, false>);
+}
+
+// ---- the sets form's pre-pass (k_int8_tiles): which tiles a 64-query block reads ----
+// grid (ceil(n_tiles / 256), blocks that hold a real query), a thread per tile g: cand(g) = alive[g] & OR over the block's real queries of set_q[g]
+// (a null set: all ones; words past a set's length: zero).  The loop over the queries is wave-uniform — the table entry is a scalar load — and the
+// 64 lanes read consecutive words of ONE bitmap.  A wave reserves its tiles' slots in the block's list with one atomicAdd on the block's count (zeroed
+// by k_int8_tiles_clear: no memset node, so that the sequence can be captured) and writes them in lane order; the list's order across waves is whatever
+// the atomics give, and no result depends on it.
+__global__ void __launch_bounds__(256) k_int8_tiles_clear(uint32_t* __restrict__ tile_cnt, uint32_t blocks) {
+    for (uint32_t i = threadIdx.x; i < blocks; i += 256) tile_cnt[i] = 0u;
+}
+__global__ void __launch_bounds__(256)
+k_int8_tiles(const uint64_t* __restrict__ alive, uint32_t n_tiles, const RowSetRef* __restrict__ sets, uint32_t nq, uint32_t* __restrict__ tile_list, uint32_t* __restrict__ tile_cnt) {
+    const uint32_t b = blockIdx.y, g = blockIdx.x * 256 + threadIdx.x, lane = lane_id();
+    const uint32_t nreal = nq - 64 * b < 64 ? nq - 64 * b : 64u;
+    uint64_t any = 0ull;
+    if (g < n_tiles) {
+        const uint64_t live = alive[g];
+        for (uint32_t i = 0; i < nreal && any != ~0ull; i++) {      // (a lane that has seen every bit stops reading)
+            const RowSetRef rs = sets[64 * b + i];
+            any |= rs.bits == nullptr ? ~0ull : (g < rs.words ? rs.bits[g] : 0ull);
+        }
+        any &= live;
+    }
+    const uint64_t m = __ballot(any != 0ull);
+    if (m == 0ull) return;                                           // (wave-uniform)
+    uint32_t at = 0;
+    if (lane == 0) at = atomicAdd(&tile_cnt[b], (uint32_t)__builtin_popcountll(m));
+    at = __builtin_amdgcn_readfirstlane(at);
+    // (at most one slot per tile is ever reserved: the list's n_tiles words hold them all)
+    if (any != 0ull) tile_list[(size_t)b * n_tiles + at + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = g;
+}
+hipError_t launch_int8_tiles(const IndexView& v, const RowSetRef* d_sets, uint32_t nq, uint32_t* tile_list, uint32_t* tile_cnt, hipStream_t s) {
+    const uint32_t blocks = (nq + 63) / 64;
+    if (!d_sets || nq == 0 || v.n_tiles == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_int8_tiles_clear, dim3(1), dim3(256), 0, s, tile_cnt, blocks);
+    hipLaunchKernelGGL(k_int8_tiles, dim3((v.n_tiles + 255) / 256, blocks), dim3(256), 0, s, v.alive, v.n_tiles, d_sets, nq, tile_list, tile_cnt);
+    return hipGetLastError();
+}
+
+// the sets form: launch_int8_filter's arguments, the pre-pass's lists and counts; lds: int8_filter_sets_lds_bytes.  The batch's RowSetRef table is the one
+// k_mfma_prep left in front of the counters (cand_sets).
+hipError_t launch_int8_filter_sets(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq, uint32_t nq_pad, uint32_t* cand, float* cscore,
+                                   uint32_t* cnt, const uint32_t* tile_list, const uint32_t* tile_cnt, uint32_t grid_x, size_t lds, hipStream_t s) {
+    if (v.plane8 == nullptr || (v.dim & 31u) || v.dim < 64 || v.dim > 1024 || (v.metric != QV_COSINE && v.metric != QV_DOT)) return hipErrorInvalidValue;   // (a missing route is an error)
+    if (grid_x == 0 || lds < int8_filter_sets_lds_bytes(v.dim) || !tile_list || !tile_cnt) return hipErrorInvalidValue;
+    const uint32_t steps = v.dim / 32;
+    const dim3 grid(grid_x, (nq + 63) / 64);                         // (the blocks that hold a real query: the pre-pass's)
+    const uint4* q8 = static_cast<const uint4*>(Q8);
+    const float* sq32 = reinterpret_cast<const float*>(static_cast<const char*>(Q8) + (size_t)nq_pad * 2 * v.dim);
+    auto go = [&](auto kernel) {
+        const hipError_t e = set_lds(kernel, lds); if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, grid, dim3(512), lds, s, v, q8, sq32, cq, mq, nq, nq_pad, cand, cscore, cnt, tile_list, tile_cnt);
+        return hipGetLastError();
+    };
+    const bool div = steps % kInt8SetsRing == 0;
+    if (v.metric == QV_COSINE) return div ? go(k_int8_filter<QV_COSINE, kInt8SetsRing, true, true>) : go(k_int8_filter<QV_COSINE, kInt8SetsRing, false, true>);
+    return div ? go(k_int8_filter<QV_DOT, kInt8SetsRing, true, true>) : go(k_int8_filter<QV_DOT, kInt8SetsRing, false, true>);
 }
 
 // ---- the shared-row form (k_int8_shared_filter): whole groups of 256 queries, the plane read ONCE per group ----
@@ -442,6 +579,23 @@ __global__ void __launch_bounds__(256) k_int8_filter_count(const uint32_t* __res
 }
 hipError_t launch_int8_filter_count(const uint32_t* d_redo, uint32_t nq, uint32_t* d_stats, bool shared, hipStream_t s) {
     hipLaunchKernelGGL(k_int8_filter_count, dim3(1), dim3(256), 0, s, d_redo, nq, d_stats, shared ? 1u : 0u);
+    return hipGetLastError();
+}
+
+// ... and a filtered batch's own (kInt8FilteredStatsWord): batches, queries, and — 64-bit, summed here from the lists' counts — the (block, tile)
+// visits the lists skipped and those possible (blocks with a real query x n_tiles)
+__global__ void __launch_bounds__(256) k_int8_filtered_count(const uint32_t* __restrict__ tile_cnt, uint32_t blocks, uint32_t n_tiles, uint32_t nq, uint32_t* __restrict__ stats) {
+    unsigned long long skipped = 0ull;
+    for (uint32_t b = threadIdx.x; b < blocks; b += 256) skipped += n_tiles - tile_cnt[b];
+    unsigned long long* wide = reinterpret_cast<unsigned long long*>(stats + kInt8FilteredStatsWord + 2);
+    if (skipped) (void)atomicAdd(&wide[0], skipped);
+    if (threadIdx.x == 0) {
+        (void)atomicAdd(&stats[kInt8FilteredStatsWord], 1u); (void)atomicAdd(&stats[kInt8FilteredStatsWord + 1], nq);
+        (void)atomicAdd(&wide[1], (unsigned long long)blocks * n_tiles);
+    }
+}
+hipError_t launch_int8_filtered_count(const uint32_t* tile_cnt, uint32_t nq, uint32_t n_tiles, uint32_t* d_stats, hipStream_t s) {
+    hipLaunchKernelGGL(k_int8_filtered_count, dim3(1), dim3(256), 0, s, tile_cnt, (nq + 63) / 64, n_tiles, nq, d_stats);
     return hipGetLastError();
 }
 

@@ -566,6 +566,24 @@ class DeviceIndex:
         check(lib().qv_index_int8_shared_stats(self._h, out))
         return tuple(int(x) for x in out)
 
+    INT8_FILTERED = {"auto": 0, "always": 1, "never": 2}
+
+    def set_int8_filtered(self, mode):
+        """which kernel filters a FILTERED batch (set_filtered_batch / _wide decide whether there is one) of an index under set_filter("int8"):
+        "always" — the int8 kernel's sets form wherever its rule holds (batched_int8_applies_filtered): the 8-bit plane of only the tiles some
+        query of a 64-query block selects, every (query, row) pair tested against the query's set; "never"; "auto" — the measured cells, none
+        yet (qv_index_set_int8_filtered)"""
+        if isinstance(mode, str) and mode not in self.INT8_FILTERED:
+            raise ValueError(f"mode must be one of {sorted(self.INT8_FILTERED)}; got {mode!r}")
+        check(lib().qv_index_set_int8_filtered(self._h, self.INT8_FILTERED.get(mode, mode)))
+
+    def int8_filtered_stats(self) -> tuple:
+        """(filtered batches whose main filter was the int8 kernel's sets form, their queries, (block, tile) visits its tile lists skipped, visits
+        possible) — int8_filter_stats counts the batches too; waits for the device (qv_index_int8_filtered_stats)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_index_int8_filtered_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
     FILTERED_BATCH = {"auto": 0, "always": 1, "never": 2}
 
     def set_filtered_batch(self, mode, sparse_ppm=None):
