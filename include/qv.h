@@ -447,8 +447,10 @@ int qv_index_set_filter(qv_index* idx, int filter);
  * threshold — the 8-bit bound scan's interval (qv_scan_bound_interval8) plus the float32 roundings of the kernel's epilogue.  The exact
  * re-score decides as ever, so rows, float32 bits, order, counts and padding are what every other filter returns.
  * The kernel runs only where ALL of these hold: the metric is QV_COSINE or QV_DOT; the index holds the 8-bit plane; the dimension is a
- * multiple of 32 from 64 to 1024; the batched path itself takes the batch; the batch carries no row sets or where-filters — or it does and
- * the index asked for the sets form (qv_index_set_int8_filtered, below).  Everywhere else
+ * multiple of 32 from 64 to 4096; the batched path itself takes the batch; the batch carries no row sets or where-filters — or it does, the
+ * dimension is at most 1024 and the index asked for the sets form (qv_index_set_int8_filtered, below).  Up to 1024 dimensions a block's query
+ * operands stay in LDS; from 1056 they pass through it in panels of 16 steps (k_int8_wide_filter) and the two integer chains are summed in
+ * float64, since 128 I_hi + I_lo leaves int32 there; the shared-row kernel (below) keeps its four dimensions.  Everywhere else
  * (QV_L2 with or without QV_FLAG_L2_SCAN_PLANE, QV_FLAG_NO_SCAN_PLANE, other dimensions, filtered batches without that mode — their kernels are what
  * qv_batched_filter_route reports for QV_FILTER_AUTO; that export and qv_batched_applies_filtered* keep taking 0 .. 4 only) the batch runs exactly
  * as under QV_FILTER_AUTO.

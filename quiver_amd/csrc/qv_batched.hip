@@ -44,7 +44,7 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
     // the int8 filter (bf16x3 == 3: qv_int8.hip): the query quantised as k_bound_scan8 quantises its own (bound8_split_query), its two int8
     // operand planes in the order k_int8_filter copies them into LDS — Q8[((qb64 * steps + s) * 4 + 2 * {hi, lo} + query half) * 64 + lane] x 16 bytes,
     // lane 32 h + j holding dimensions 32 s + 16 h .. + 15 of query 64 qb64 + 32 half + j (a step is 32 dimensions: chunks 2 s and 2 s + 1 of the plane) —
-    // and sq as float32 behind them.  The block is one wave; dim / 16 <= 64 chunks, one per lane.
+    // and sq as float32 behind them.  The block is one wave; lane l takes chunks l, l + 64, ... of the dim / 16 (up to 256 at 4096 dimensions).
     double i8_sq = 1.0, i8_qres = __builtin_nan(""), i8_qn = 0.0;
     if (bf16x3 == 3) {
         const uint32_t lane = threadIdx.x;
@@ -55,11 +55,11 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
         const bool q_ok = q < nq && __ballot(bad) == 0ull && mx > 0.0f;
         i8_sq = q_ok ? (double)mx / (double)kBound8QueryMax : 1.0;
         double r2 = 0.0;
-        if (lane < dim / 16) {
+        for (uint32_t ch = lane; ch < dim / 16; ch += 64) {          // (one chunk per lane up to 1024 dimensions, up to four at 4096)
             uint32_t hw[4] = {0u, 0u, 0u, 0u}, lw[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                const double x = q_ok ? (double)queries[(size_t)q * dim + 16 * lane + e] : 0.0;
+                const double x = q_ok ? (double)queries[(size_t)q * dim + 16 * ch + e] : 0.0;
                 int hi, lo;
                 const double d = bound8_split_query(x, i8_sq, hi, lo);
                 r2 = __builtin_fma(d, d, r2);
@@ -67,7 +67,7 @@ __global__ void k_mfma_prep(const float* __restrict__ queries, uint32_t nq, uint
             }
             if (what & 1) {
                 uint4* Q8 = reinterpret_cast<uint4*>(Qt);
-                const size_t base = (((size_t)(q >> 6) * (dim / 32) + (lane >> 1)) * 4 + ((q >> 5) & 1u)) * 64 + 32 * (lane & 1u) + (q & 31u);
+                const size_t base = (((size_t)(q >> 6) * (dim / 32) + (ch >> 1)) * 4 + ((q >> 5) & 1u)) * 64 + 32 * (ch & 1u) + (q & 31u);
                 Q8[base] = make_uint4(hw[0], hw[1], hw[2], hw[3]); Q8[base + 128] = make_uint4(lw[0], lw[1], lw[2], lw[3]);
             }
         }
@@ -2764,8 +2764,10 @@ static void batched_sets_adapt(BatchedRoute& r) {
 // for it (its mode 3, after the sample stage has read the bfloat16 ones); the sample stage, nq_pad, the candidate slots, the exact stage and every
 // workspace size stay plan_batched's (the operand planes take 2 dim bytes per padded query of a region that holds 4 dim + 576).
 static bool int8_shape(int metric, uint32_t dim, int filter, bool has_plane8) {
-    return filter == QV_FILTER_INT8 && (metric == QV_COSINE || metric == QV_DOT) && has_plane8 && (dim & 31u) == 0 && dim >= 64 && dim <= 1024;
+    return filter == QV_FILTER_INT8 && (metric == QV_COSINE || metric == QV_DOT) && has_plane8 && (dim & 31u) == 0 && dim >= 64 && dim <= 4096;
 }
+// above this the block kernel is its panel form (k_int8_wide_filter): unfiltered batches only — the sets form keeps k_int8_filter's range
+constexpr uint32_t kInt8ResidentMaxDim = 1024;
 // Which of its two kernels: the shared-row form (k_int8_shared_filter) serves pieces padded to whole groups of 256 queries — more than 128 —
 // at the dimensions it is instantiated for.  form: QV_INT8_FORM_* (qv_index_set_int8_form); QV_INT8_FORM (1 / 2, read once) is the default of
 // indexes that never called the setter.  SHARED: wherever it applies; BLOCKS: never; automatic: the cells where it was measured faster than
@@ -2825,7 +2827,7 @@ static int int8_filtered_mode(int mode) { static const int env_mode = env_int("Q
 static bool int8_filtered_route(const BatchedRoute& r, const IndexView& v, bool has_plane8, int mode) {
     mode = int8_filtered_mode(mode);
     if (mode == QV_INT8_FILTERED_NEVER || (mode != QV_INT8_FILTERED_ALWAYS && !kInt8FilteredAuto)) return false;
-    return int8_shape(v.metric, v.dim, v.filter, has_plane8) && batched_sets_route(r) && (uint64_t)64 * r.sample_rows >= (uint64_t)v.n_tiles + 64;
+    return int8_shape(v.metric, v.dim, v.filter, has_plane8) && v.dim <= kInt8ResidentMaxDim && batched_sets_route(r) && (uint64_t)64 * r.sample_rows >= (uint64_t)v.n_tiles + 64;
 }
 bool batched_int8_applies_filtered(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8, int mode) {
     if (!batched_int8_applies(metric, dim, rows, nq, k, filter, has_plane8) || k > kFilteredBatchWideMaxK) return false;

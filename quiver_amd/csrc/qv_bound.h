@@ -191,7 +191,19 @@ __host__ __device__ static inline double bound8_split_query(double x, double sq,
 // The threshold is the one-term bfloat16 filter's (filter_threshold, qv_filter.h) with these constants: a row of the top k has d <= U, hence
 // S >= (1 - U)|q||r| (cosine) or S >= 1 - U (dot) up to the 4e-7 kept in c, and S~32 >= S - ea |r| - eb rres8; m carries ea + 1e-6 |q| (the
 // float32 roundings of the threshold's own three operations), c is rounded down, m and b up, |r| up.
+//
+// 1056 to 4096 dimensions (k_int8_wide_filter): the derivation re-read line by line for dim <= 4096.
+//   The chains: |I_hi| <= 4096 * 127 * 127 and |I_lo| <= 4096 * 64 * 127, each exact in int32 — the accumulators do not change.  Their combination
+//   |I| <= 4096 * 16256 * 127 < 2^33 no longer is: int8_filter_score_wide forms 128 I_hi + I_lo in float64 (both terms and their sum are integers
+//   below 2^53: exact) and rounds it to float32 ONCE, so fl(I) = I (1 + d2) holds as written, and with it the 2.4e-7 of the four roundings.
+//   The proof above: its chain term is stated for dim <= 4096 already (4.6e-13, inside the 1e-12), and nothing else in it reads the dimension.
+//   Underflow: fl(sq32 scale) in the subnormal range is off by at most 2^-149, times |fl(I)| < 2^33 (1 + 2^-24) < 2^34: 2^-149 * 2^34 = 2.4e-35,
+//   and the last product's own 2^-149 beside it.  The norm floor (bound_scan_norm_ok, filter_tiny_norm: 1e-14 up to 4096 dimensions) gives
+//   |q||r| >= 1e-28, so 1e-7 |q||r| >= 1e-35 does NOT cover that as written.  The wide form's ea therefore carries 3e-7 |q| for underflow
+//   (kInt8WideUnderflow; 3e-35 at the floor); eb, c and the threshold's 1e-6 |q| are as above, and up to 1024 dimensions every constant is as it was.
 constexpr double kInt8FilterEps = 3e-7;
+constexpr uint32_t kInt8WideFromDim = 1025;      // from here the wide form: int8_filter_score_wide and kInt8WideUnderflow
+constexpr double kInt8WideUnderflow = 3e-7;
 __host__ __device__ static inline float bound_f32_up(float x) {
     if (!(x == x) || x == __builtin_inff()) return x;
     union { float f; uint32_t u; } c; c.f = x;
@@ -210,7 +222,8 @@ __host__ __device__ static inline Int8QueryConsts int8_filter_query_consts(uint3
     k.declined = !(bound_scan_norm_ok(qn, dim) && qres >= 0.0 && qres < 1.0e18 && sq > 0.0 && sq < 1.0e36);
     if (k.declined) { k.c = __builtin_inff(); k.m = k.b = k.ea = k.eb = 0.f; k.sq32 = 0.f; return k; }
     const double both = (1e-12 + kInt8FilterEps) * (qn + qres);
-    const double ea = (qres + both + 1e-7 * qn) * (1.0 + 1e-9), eb = (qn + qres + both) * (1.0 + 1e-9);
+    const double under = dim >= kInt8WideFromDim ? kInt8WideUnderflow : 1e-7;
+    const double ea = (qres + both + under * qn) * (1.0 + 1e-9), eb = (qn + qres + both) * (1.0 + 1e-9);
     k.ea = bound_f32_up((float)ea); k.eb = bound_f32_up((float)eb);
     k.sq32 = (float)sq;
     double c = M == QV_COSINE ? (1.0 - U - 4e-7) * qn : (1.0 - U - 4e-7 * (1.0 + __builtin_fabs(U)));
@@ -224,6 +237,10 @@ __host__ __device__ static inline Int8QueryConsts int8_filter_query_consts(uint3
 // the score the epilogue tests and the candidate list stores
 __host__ __device__ __forceinline__ float int8_filter_score(int isum_hi, int isum_lo, float sq32, float rscale8) {
     return (sq32 * rscale8) * (float)(128 * isum_hi + isum_lo);
+}
+// ... above 1024 dimensions, where 128 I_hi + I_lo leaves int32: the sum exact in float64, one rounding to float32
+__host__ __device__ __forceinline__ float int8_filter_score_wide(int isum_hi, int isum_lo, float sq32, float rscale8) {
+    return (sq32 * rscale8) * (float)(128.0 * (double)isum_hi + (double)isum_lo);
 }
 // a row the 8-bit bound says nothing about (always a candidate, its score NaN): rn = |r| rounded up to float32
 __host__ __device__ __forceinline__ bool int8_filter_row_unsure(float rn, float rscale8, float rres8, float tiny_rn) {

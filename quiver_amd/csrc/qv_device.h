@@ -455,8 +455,8 @@ hipError_t launch_qreg_filter(const IndexView& v, const uint4* Qbf, const float*
                               uint32_t* cnt, bool bfrows, int cus, hipStream_t s);
 
 // The int8 matrix-core filter on the 8-bit plane (qv_int8.hip; QV_FILTER_INT8).  The rule: the index asks for it, cosine or dot, plane8 held, a
-// dimension that is a multiple of 32 from 64 to 1024, and the batched path itself applies; a batch with sets takes its sets form, and only under
-// QV_INT8_FILTERED_* (batched_int8_applies_filtered).
+// dimension that is a multiple of 32 from 64 to 4096 (from 1056: the panel kernel, k_int8_wide_filter, behind launch_int8_filter), and the batched
+// path itself applies; a batch with sets takes its sets form, up to 1024 dimensions and only under QV_INT8_FILTERED_* (batched_int8_applies_filtered).
 bool batched_int8_applies(int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int filter, bool has_plane8);
 // the index's counter words: 0 - 3 the bound scan, kBound8StatsWord 4 - 6, kBound6StatsWord 7 - 9, kBoundWideStatsWord 10 - 12, kBoundWideMqStatsWord 13 - 15, and
 // the int8 filter's own: [16] batches whose main filter was k_int8_filter, [17] their queries, [18] those handed back

@@ -4,6 +4,7 @@
 // residual per row): a quarter of the float32 rows' bytes, and a 16-byte piece of it is exactly one lane's operand of v_mfma_i32_32x32x32_i8.
 // The query is quantised as the 8-bit bound scan quantises its own, qq = 128 hi + lo (k_mfma_prep's int8 mode, bound8_split_query), so a score is
 // two integer chains, I = 128 I_hi + I_lo, exact in int32 up to 1024 dimensions — the integers of qv_bound.h's 8-bit proof, for 64 queries at once.
+// (1056 to 4096 dimensions: k_int8_wide_filter below — the same workgroup with the operands passing through LDS in panels, the sum in float64.)
 //
 // Workgroup: eight waves (two per SIMD, 256 registers each), one workgroup per CU and 64-query block (blockIdx.y); a block that holds no real
 // query leaves at once.  All eight waves work for the SAME 64 queries: their hi and lo operands, 128 dim bytes (96 KiB at 768 dimensions, 128 KiB
@@ -248,13 +249,205 @@ k_int8_filter(IndexView v, const uint4* __restrict__ Q8, const float* __restrict
     cand_flush(cqu, cqu_n, cqu_out);
 }
 
-size_t int8_filter_lds_bytes(uint32_t dim) { return (size_t)dim * 128; }
+// ---- 1056 to 4096 dimensions (k_int8_wide_filter): the block kernel with its operands passing through LDS in panels ----
+// Above 1024 dimensions a block's operands (128 dim bytes: 192 KiB at 1536 dimensions, 512 KiB at 4096) no longer fit LDS, and 128 I_hi + I_lo no
+// longer fits int32.  The workgroup is k_int8_filter's — eight waves, one 64-query block, each wave streaming its own 64-row tiles through a ring
+// of R = 4 steps into 128 accumulators — and two things change.
+// Operands: a tile's steps are cut into revolutions of the ring (R steps, 16 KiB of Q8 in the order the prep wrote them; the last one of a tile
+// may be short), and the revolutions of tile after tile — the operands are the same for every tile — form ONE stream that passes through LDS in
+// panels of kInt8WideRevs = 4 revolutions (16 steps, 64 KiB).  LDS holds two panels.  While the waves compute revolution n, the workgroup copies
+// revolution n + 4 — its place in the next panel — out of L2: every thread loads two 16-byte pieces in front of the revolution's matrix
+// instructions and stores them to LDS behind them.  Plain loads and stores, so that the compiler counts them with the ring's (an LDS-DMA request
+// it does not see makes every counted wait behind it drain the ring); 8 registers.
+// Lockstep: ONE workgroup barrier per panel, in front of its first revolution: the panel's operands are stored, and nobody reads the other panel
+// any more, which the next four revolutions overwrite.  Rounds, revolutions and hence barriers are counted from blockIdx.x, gridDim.x and n_tiles
+// alone: round r gives wave w tile 8 blockIdx.x + w + 8 gridDim.x r, and a wave whose tile lies past the last one (a workgroup's last round
+// only) still walks every revolution of the round, copies its share of the operands and meets every barrier; it skips the row loads, the matrix
+// instructions and the epilogue.  No wave leaves the loop before the others.
+// DIV, as in k_int8_filter: 4 divides the dimension's steps — every multiple of 128 dimensions — so no step of a revolution is idle and the loop
+// body is free of branches; otherwise idle steps are skipped by wave-uniform branches (behind which the compiler drains the ring at every step).
+// Score: int8_filter_score_wide (qv_bound.h: the sum in float64, rounded once).  Everything else — row constants, level 1, the dump, the dense
+// pass, the queue and its flush — is k_int8_filter's, through the same functions.
+constexpr uint32_t kInt8WideMinDim = 1056, kInt8WideMaxDim = 4096;
+constexpr int kInt8WideRing = 4, kInt8WideRevs = 4;                   // steps per revolution, revolutions per panel
+
+template <int METRIC, bool DIV>
+__global__ void __launch_bounds__(512, 1)
+k_int8_wide_filter(IndexView v, const uint4* __restrict__ Q8, const float* __restrict__ sq32, const float* __restrict__ cq, const float* __restrict__ mq, uint32_t nq, uint32_t nq_pad,
+                   uint32_t* __restrict__ cand_rows, float* __restrict__ cand_score, uint32_t* __restrict__ cand_cnt) {
+    constexpr int R = kInt8WideRing, NREV = kInt8WideRevs;
+    constexpr uint32_t kRev = R * 256, kSlots = 2 * NREV;            // 16-byte pieces per revolution; revolutions LDS holds
+    static_assert(R * 256 == 2 * 512 && (kSlots & (kSlots - 1)) == 0, "two pieces per thread and revolution; the slots wrap by a mask");
+    extern __shared__ __align__(16) unsigned char smem_i8w[];
+    uint4* s_a = reinterpret_cast<uint4*>(smem_i8w);                 // [slot][step of the revolution][hi, lo][query half][lane]
+    __shared__ __align__(16) Int8Lds s_k;
+    constexpr bool SETS = false;
+    QV_CAND_QUEUE(cqu, 8, 128);                                      // 12 KiB
+    QV_EPI_DUMP(du, 8, 16);                                          // 10 KiB
+    const uint32_t qb = blockIdx.y;
+    if (64 * qb >= nq) return;                                       // a block made only of padding (the whole workgroup)
+    const uint32_t lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t steps = v.dim / 32, chunks = v.dim / 16;
+    const uint32_t revs = (steps + R - 1) / R;                       // revolutions per tile
+    // workgroup-uniform: the rounds this workgroup runs — as many as its FIRST wave has tiles
+    const uint32_t wg_first = blockIdx.x * 8, tw = gridDim.x * 8;
+    if (wg_first >= v.n_tiles) return;                               // (the whole workgroup, before its first barrier)
+    const uint32_t rounds = (v.n_tiles - wg_first + tw - 1) / tw;
+    const uint4* q8 = Q8 + (size_t)qb * steps * 256;
+    const uint32_t q8_last = steps * 256 - 1;                        // (a short revolution's pieces past the operands: the last piece again, into LDS nobody reads)
+    // the stream's first panel: revolutions 0 .. NREV - 1 of a tile (revs > NREV: steps >= 33)
+    for (uint32_t i = threadIdx.x; i < NREV * kRev; i += 512) s_a[i] = q8[i];
+    if (threadIdx.x < 64) {
+        const uint32_t ql = threadIdx.x, q = 64 * qb + ql, w = ql & 31u;
+        const float c = cq[q], m = mq[q];
+        s_k.cm[ql] = int8_filter_cm<METRIC>(c, m); s_k.m[ql] = m; s_k.b[ql] = mq[nq_pad + q];
+        s_k.sq[(w >> 2) & 1u][ql >> 5][(w & 3u) | ((w >> 3) << 2)] = sq32[q];   // ql = 32 i + (r & 3) + 8 (r >> 2) + 4 half, inverted
+    }
+    __syncthreads();
+    const uint32_t half = lane >> 5, l31 = lane & 31;
+    float cmin[2], mmax[2], bmax[2];                                 // per query half: what bounds the 16 thresholds of this lane's accumulators from below
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        float cm = __builtin_inff(), mm = 0.f, bm = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const uint32_t ql = 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
+            cm = fminf(cm, s_k.cm[ql]); mm = fmaxf(mm, s_k.m[ql]); bm = fmaxf(bm, s_k.b[ql]);
+        }
+        cmin[i] = cm; mmax[i] = mm; bmax[i] = bm;
+    }
+    const float tiny = filter_tiny_norm(v.dim);
+    const Int8Keep<METRIC> keep{s_k};
+    const i32x4* plane = reinterpret_cast<const i32x4*>(v.plane8);
+    const uint32_t gw = wg_first + wave;
+    // block j of tile t at step 0: chunk `half` of rows 32 j + l31; a step is two chunks on (128 pieces)
+    auto base = [&](uint32_t t, int j) { return plane + ((size_t)t * chunks + half) * 64 + 32 * j + l31; };
+    i32x4 rb[R][2];
+    // the stream's cursors (workgroup-uniform): the slot the next revolution is computed from and its place in its panel; the revolution of a
+    // tile that is copied next — NREV ahead — and its slot
+    uint32_t c_slot = 0, c_in = 0, s_rev = NREV, s_slot = NREV;
+    // one round: a tile's revolutions.  ACT: this wave has a tile (wave-uniform, one compiled body each, so that neither holds a conditional load)
+    auto round_of = [&](auto act_c, uint32_t g, bool first) {
+        constexpr bool ACT = decltype(act_c)::value;
+        const uint32_t gn = g + tw < v.n_tiles ? g + tw : g;         // past the wave's last tile: the same tile again (in bounds, read by nobody)
+        const i32x4* p[2] = {plane, plane};
+        const i32x4* np[2] = {plane, plane};
+        double rnd[2] = {0.0, 0.0}; float rsc[2] = {0.f, 0.f}, rho[2] = {0.f, 0.f};
+        uint64_t alv = 0;
+        i32x16 acc[2][2][2];                                         // [hi, lo][query half][row block]: across the tile's revolutions and panels
+        if constexpr (ACT) {
+            p[0] = base(g, 0); p[1] = base(g, 1); np[0] = base(gn, 0); np[1] = base(gn, 1);
+#pragma unroll
+            for (int j = 0; j < 2; j++) { const size_t row = (size_t)g * 64 + 32 * j + l31; rnd[j] = v.rnorm[row]; rsc[j] = v.rscale8[row]; rho[j] = v.rres8[row]; }
+            alv = v.alive[g];
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+#pragma unroll
+                    for (int j = 0; j < 2; j++)
+#pragma unroll
+                        for (int e = 0; e < 16; e++) acc[t][i][j][e] = 0;
+            if (first) {                                             // (steps > R: every slot has a step)
+#pragma unroll
+                for (int k = 0; k < R; k++) { rb[k][0] = __builtin_nontemporal_load(p[0] + (size_t)k * 128); rb[k][1] = __builtin_nontemporal_load(p[1] + (size_t)k * 128); }
+            }
+        }
+        for (uint32_t rv = 0; rv < revs; rv++) {
+            if (c_in == 0) __syncthreads();                          // a panel's first revolution: its operands are stored; the other panel is free
+            // revolution s_rev of a tile, for the slot NREV ahead: two pieces per thread (unconditional: past the stream's end they land in LDS nobody reads)
+            const uint32_t i0 = s_rev * kRev + threadIdx.x, i1 = i0 + 512;
+            const uint4 sg0 = q8[DIV || i0 < q8_last ? i0 : q8_last], sg1 = q8[DIV || i1 < q8_last ? i1 : q8_last];
+            if constexpr (ACT) {
+                const uint4* pa = s_a + c_slot * kRev + lane;
+#pragma unroll
+                for (int k = 0; k < R; k++) {
+                    const uint32_t s_ = rv * R + k;
+                    if (DIV || s_ < steps) {
+                        const uint4* ap = pa + k * 256;
+                        const i32x4 ah0 = __builtin_bit_cast(i32x4, ap[0]), ah1 = __builtin_bit_cast(i32x4, ap[64]);
+                        const i32x4 al0 = __builtin_bit_cast(i32x4, ap[128]), al1 = __builtin_bit_cast(i32x4, ap[192]);
+#pragma unroll
+                        for (int j = 0; j < 2; j++) {
+                            acc[0][0][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah0, rb[k][j], acc[0][0][j], 0, 0, 0);
+                            acc[0][1][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah1, rb[k][j], acc[0][1][j], 0, 0, 0);
+                            acc[1][0][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(al0, rb[k][j], acc[1][0][j], 0, 0, 0);
+                            acc[1][1][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(al1, rb[k][j], acc[1][1][j], 0, 0, 0);
+                        }
+                        // the slot is free: step s_ + R of this tile, or — behind the tile's last R steps — step k of the wave's next tile
+                        const bool here = s_ + R < steps;
+                        const size_t off = (size_t)(here ? s_ + R : (uint32_t)k) * 128;
+                        rb[k][0] = __builtin_nontemporal_load((here ? p[0] : np[0]) + off);
+                        rb[k][1] = __builtin_nontemporal_load((here ? p[1] : np[1]) + off);
+                    }
+                }
+            }
+            s_a[s_slot * kRev + threadIdx.x] = sg0; s_a[s_slot * kRev + threadIdx.x + 512] = sg1;
+            c_slot = (c_slot + 1) & (kSlots - 1); s_slot = (s_slot + 1) & (kSlots - 1);
+            c_in = c_in + 1 == (uint32_t)NREV ? 0u : c_in + 1;
+            s_rev = s_rev + 1 == revs ? 0u : s_rev + 1;
+        }
+        if constexpr (ACT) {
+            uint32_t n = 0;
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const uint32_t row = g * 64 + 32 * j + l31;
+                const bool live = (alv >> (32 * j + l31)) & 1ull;
+                const float rn = bound_f32_up((float)rnd[j]);
+                const bool unsure = int8_filter_row_unsure(rn, rsc[j], rho[j], tiny);
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    f16v a;
+#pragma unroll
+                    for (int e = 0; e < 16; e++) a[e] = int8_filter_score_wide(acc[0][i][j][e], acc[1][i][j][e], s_k.sq[half][i][e], rsc[j]);
+                    const float m0 = __builtin_fmaxf(__builtin_fmaxf(a[0], a[1]), a[2]), m1 = __builtin_fmaxf(__builtin_fmaxf(a[3], a[4]), a[5]);
+                    const float m2 = __builtin_fmaxf(__builtin_fmaxf(a[6], a[7]), a[8]), m3 = __builtin_fmaxf(__builtin_fmaxf(a[9], a[10]), a[11]);
+                    const float m4 = __builtin_fmaxf(__builtin_fmaxf(a[12], a[13]), a[14]);
+                    const float mx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(m0, m1), m2), __builtin_fmaxf(__builtin_fmaxf(m3, m4), a[15]));
+                    // level 1: the threshold is monotone in cm (up), m and b (down), so this is a lower bound of the block's 16 thresholds
+                    const float thr_lo = int8_filter_threshold<METRIC>(cmin[i], mmax[i], bmax[i], rn, rho[j]);
+                    const uint64_t pm = __ballot((!(mx < thr_lo) || unsure) && live);
+                    if (__builtin_expect(pm != 0, 0)) epi_dump_with(a, pm, row, rn, rho[j], (uint32_t)i, half, unsure, keep, 64 * qb, cqu, cqu_n, cqu_out, du, n);
+                }
+            }
+            if (n) epi_dense_pass_with(du, n, keep, 64 * qb, cqu, cqu_n, cqu_out);
+        }
+    };
+    // every wave runs every round of the workgroup; only the last one can find a wave without a tile
+    for (uint32_t rd = 0; rd < rounds; rd++) {
+        const uint32_t g = gw + rd * tw;
+        if (g < v.n_tiles) round_of(std::true_type{}, g, rd == 0);
+        else round_of(std::false_type{}, g, false);
+    }
+    cand_flush(cqu, cqu_n, cqu_out);
+}
+
+size_t int8_wide_filter_lds_bytes() { return (size_t)2 * kInt8WideRevs * kInt8WideRing * 4096; }
+static hipError_t launch_int8_wide_filter(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq, uint32_t nq_pad, uint32_t* cand, float* cscore,
+                                          uint32_t* cnt, uint32_t grid_x, size_t lds, hipStream_t s) {
+    if (v.rscale8 == nullptr || v.rres8 == nullptr || lds < int8_wide_filter_lds_bytes()) return hipErrorInvalidValue;   // (the rest: launch_int8_filter's guard)
+    const dim3 grid(grid_x, nq_pad / 64);
+    const uint4* q8 = static_cast<const uint4*>(Q8);
+    const float* sq32 = reinterpret_cast<const float*>(static_cast<const char*>(Q8) + (size_t)nq_pad * 2 * v.dim);
+    auto go = [&](auto kernel) {
+        const hipError_t e = set_lds(kernel, lds); if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, grid, dim3(512), lds, s, v, q8, sq32, cq, mq, nq, nq_pad, cand, cscore, cnt);
+        return hipGetLastError();
+    };
+    const bool div = (v.dim / 32) % kInt8WideRing == 0;
+    if (v.metric == QV_COSINE) return div ? go(k_int8_wide_filter<QV_COSINE, true>) : go(k_int8_wide_filter<QV_COSINE, false>);
+    return div ? go(k_int8_wide_filter<QV_DOT, true>) : go(k_int8_wide_filter<QV_DOT, false>);
+}
+
+size_t int8_filter_lds_bytes(uint32_t dim) { return dim >= kInt8WideMinDim ? int8_wide_filter_lds_bytes() : (size_t)dim * 128; }
 size_t int8_filter_sets_lds_bytes(uint32_t dim) { return (size_t)dim * 128 + kInt8SetWordBytes + 64 * sizeof(RowSetRef); }
 
 hipError_t launch_int8_filter(const IndexView& v, const void* Q8, const float* cq, const float* mq, uint32_t nq, uint32_t nq_pad, uint32_t* cand, float* cscore,
                               uint32_t* cnt, uint32_t grid_x, size_t lds, hipStream_t s) {
-    if (v.plane8 == nullptr || (v.dim & 31u) || v.dim < 64 || v.dim > 1024 || (v.metric != QV_COSINE && v.metric != QV_DOT)) return hipErrorInvalidValue;   // (a missing route is an error)
+    if (v.plane8 == nullptr || (v.dim & 31u) || v.dim < 64 || v.dim > kInt8WideMaxDim || (v.metric != QV_COSINE && v.metric != QV_DOT)) return hipErrorInvalidValue;   // (a missing route is an error)
     if (grid_x == 0 || lds < int8_filter_lds_bytes(v.dim)) return hipErrorInvalidValue;
+    if (v.dim >= kInt8WideMinDim) return launch_int8_wide_filter(v, Q8, cq, mq, nq, nq_pad, cand, cscore, cnt, grid_x, lds, s);   // 1056 to 4096 dimensions: the panel kernel
     const uint32_t steps = v.dim / 32;
     const dim3 grid(grid_x, nq_pad / 64);                            // (the route's: batched_int8_adapt)
     const uint4* q8 = static_cast<const uint4*>(Q8);
@@ -607,7 +800,9 @@ int host_int8_filter_keeps(int metric, uint32_t dim, int32_t isum_hi, int32_t is
         if (kc.declined) return 1;                                     // (the query is handed back: nothing is decided by its scores)
         const float rnf = bound_f32_up((float)rn);
         const bool unsure = int8_filter_row_unsure(rnf, rscale8, rres8, filter_tiny_norm(dim));
-        return int8_filter_keeps<M>(int8_filter_score(isum_hi, isum_lo, kc.sq32, rscale8), int8_filter_cm<M>(kc.c, kc.m), kc.m, kc.b, rnf, rres8, unsure) ? 1 : 0;
+        // (the score as the dimension's kernel forms it: above 1024 dimensions the sum leaves int32)
+        const float score = dim >= kInt8WideFromDim ? int8_filter_score_wide(isum_hi, isum_lo, kc.sq32, rscale8) : int8_filter_score(isum_hi, isum_lo, kc.sq32, rscale8);
+        return int8_filter_keeps<M>(score, int8_filter_cm<M>(kc.c, kc.m), kc.m, kc.b, rnf, rres8, unsure) ? 1 : 0;
     };
     return metric == QV_COSINE ? f(std::integral_constant<int, QV_COSINE>{}) : f(std::integral_constant<int, QV_DOT>{});
 }
