@@ -968,11 +968,43 @@ int qv_scan_route_ex(int metric, uint32_t dim, uint32_t rows, uint32_t nq, uint3
 #define QV_WS_WHERE_CALL 14       /* ... with the candidate bitmap and the transient sets behind it */
 #define QV_WS_BOUND_WIDE 15       /* the single-query bound scan's wide form, 65 <= k <= 1024; its exact redo's workspace is an alias over the rest */
 #define QV_WS_BOUND_WIDE_MQ 16    /* the wide form of the shared bound pass, 2 - 8 queries, 65 <= k <= 1024; the pass's flag words first, the key-per-row redo's workspace an alias over the rest */
+#define QV_WS_RANGE 17            /* a range search's piece (k = max_results): counters, the queries' 8-bit terms, the candidate buffer, the key buffer, the key-per-row redo and its selection */
 #define QV_WS_FLAT_PLAIN 0       /* query blocks, or the matrix-core scan's block */
 #define QV_WS_FLAT_BOUND 1        /* ... or the single-query bound scan's buffer */
 #define QV_WS_FLAT_BOUND_MQ 2     /* ... and the shared bound pass, which has the workspace to itself */
 int qv_scan_workspace_layout(int kind, int metric, uint32_t dim, uint64_t rows, uint32_t nq, uint32_t k, int cus, uint32_t flags,
                              uint64_t* total, uint64_t* end, uint32_t* n_regions, uint64_t* regions, uint32_t cap);
+/* ---- range search: every row within a radius ----
+ * A live row matches query q exactly when its float32 distance d — the bits qv_index_search returns for the pair — satisfies
+ * d <= radius[q] in float32.  A NaN distance never matches; a NaN radius matches nothing; a radius of +inf matches every live row whose
+ * distance is not NaN.  Per query: matches_out[q] = the number of matching rows; count_out[q] = min(matches, max_results); the first
+ * count_out[q] entries of rows_out / dist_out ([nq][max_results]) are the matching rows in (distance, row) order and the rest is padded
+ * as qv_index_search pads (row 0xFFFFFFFF, distance +inf).  With more matches than max_results the rows returned are the max_results
+ * nearest: what qv_index_search with k = max_results returns, cut at the radius.  max_results: 1 .. QV_RANGE_MAX_RESULTS and nq >= 1,
+ * else QV_ERR_INVALID_ARG; every metric is served; an index without a live row gives zero counts.
+ * The device-pointer form enqueues everything on `stream` and reads nothing on the host; it writes no count: the padding and
+ * d_matches_out say it.
+ * Where a call starts: the exact range scan (the exact scan's arithmetic with the threshold test in the place of its lists) by default and
+ * for every metric; under QV_RANGE_PLANE_ALWAYS, on a cosine / dot index (or a Euclidean one created with QV_FLAG_L2_SCAN_PLANE) that keeps
+ * the 8-bit plane, a stage that rejects rows on a certified lower bound of the distance read from that plane and re-scores the survivors
+ * exactly — the same results, bit for bit.  QV_RANGE_PLANE_AUTO takes the plane nowhere until a shape is measured faster.  The
+ * environment variable QV_RANGE_PLANE (1 / 2, read once per process) sets the default of an index that was not told.
+ * qv_index_range_stats: out[0] queries of range calls, out[1] of them started on the 8-bit plane, out[2] of those handed back to the
+ * exact range scan (more candidates than the stage keeps), out[3] candidates re-scored.
+ * qv_scan_range_applies: the rule, on the host, without an index or a device — 1 = the call starts on the 8-bit plane, 0 = the exact
+ * range scan, < 0 on an error; metric as qv_scan_bound_applies takes it (QV_RULE_L2_PLANES included). */
+#define QV_RANGE_MAX_RESULTS 8192            /* the radix selection's range */
+#define QV_RANGE_PLANE_AUTO   0
+#define QV_RANGE_PLANE_ALWAYS 1
+#define QV_RANGE_PLANE_NEVER  2
+int qv_index_search_range(qv_index* idx, const float* queries, uint32_t nq, const float* radius /* [nq] */, uint32_t max_results,
+                          uint32_t* rows_out, float* dist_out, uint32_t* count_out /* [nq]: rows written */, uint64_t* matches_out /* [nq]: rows within the radius */);
+int qv_index_search_range_device(qv_index* idx, const float* d_queries, uint32_t nq, const float* d_radius, uint32_t max_results,
+                                 uint32_t* d_rows_out, float* d_dist_out, uint64_t* d_matches_out, void* stream);
+int qv_index_set_range_plane(qv_index* idx, int mode);
+int qv_index_range_stats(qv_index* idx, uint64_t out[4]);   /* calls' queries, of them started on the 8-bit plane, of those handed back, candidates re-scored */
+int qv_scan_range_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, int mode, int has_plane8);   /* the rule, no index, no device */
+
 /* The interval stage 1 derives for one row, on the host (the kernel's own function compiled for the CPU; metric QV_COSINE or
  * QV_DOT; every other metric: QV_ERR_UNSUPPORTED — QV_L2 included, whose interval is qv_scan_bound_interval_l2 below): s = the float32 chain of the query times the row's bfloat16 copy, qn = |query|, rn = |row|, rres = |row - bf16(row)|
  * rounded up.  Returns 1 when the row is one the bound says nothing about (always a survivor), 0 otherwise with

@@ -11,6 +11,18 @@ from ._lib import QvError, lib, load_library, METRICS, metric_id  # noqa: F401
 from .device_index import DeviceIndex, RowSet, Column, DeviceGraph, GraphReplicas, ShardedIndex, graph_reject_applies, graph_reject_image_applies  # noqa: F401
 
 
+def scan_range_applies(metric, dim: int, rows: int, nq: int = 1, mode="auto", has_plane8: bool = True) -> bool:
+    """whether a range search of nq queries would start on the 8-bit plane — the dispatch's own rule, on the host, without an index or a
+    device (qv_scan_range_applies); metric: a name or an id (QV_RULE_L2_PLANES for a Euclidean index that keeps the planes), mode: as
+    set_range_plane takes it"""
+    from ._lib import check
+    m = metric_id(metric) if isinstance(metric, str) else int(metric)
+    rc = lib().qv_scan_range_applies(m, dim, rows, nq, DeviceIndex.RANGE_PLANE.get(mode, mode), 1 if has_plane8 else 0)
+    if rc < 0:
+        check(rc)
+    return rc == 1
+
+
 def scan_bound8_applies_mq(metric, dim: int, rows: int, nq: int, k: int, mode="auto", plane_mode_mq="auto", has_plane8: bool = True) -> bool:
     """whether an unfiltered shared pass of nq queries would start on the 8-bit plane — the dispatch's own rule, on the host, without an index
     or a device (qv_scan_bound8_applies_mq); metric: a name or an id, mode / plane_mode_mq: as set_bound_scan / set_bound_plane_mq take them"""
@@ -103,5 +115,5 @@ def batched_filter_route(metric, dim: int, rows: int, nq: int, k: int, filter="a
     return int(pad.value), DeviceIndex.BATCHED_FILTERS[code.value]
 
 
-__all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_bound8_applies_mq", "scan_bound8_applies_filtered_mq",
+__all__ = ["QvError", "lib", "load_library", "METRICS", "metric_id", "DeviceIndex", "RowSet", "Column", "DeviceGraph", "GraphReplicas", "ShardedIndex", "scan_range_applies", "scan_bound8_applies_mq", "scan_bound8_applies_filtered_mq",
            "batched_applies_filtered", "batched_int8_applies", "batched_int8_form", "batched_int8_applies_filtered", "batched_applies_filtered_wide", "batched_filter_route", "graph_reject_applies", "graph_reject_image_applies"]

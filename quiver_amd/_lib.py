@@ -82,6 +82,11 @@ PROTOTYPES = {
     "qv_index_coalesce_early_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_graph_coalesce_early_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "qv_index_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qv_index_search_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qv_index_search_range_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qv_index_set_range_plane": (C.c_int, [C.c_void_p, C.c_int]),
+    "qv_index_range_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "qv_scan_range_applies": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
     "qv_index_search_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qv_rowset_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     "qv_rowset_set_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]),

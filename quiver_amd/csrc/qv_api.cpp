@@ -1901,6 +1901,105 @@ int qv_index_search_device(qv_index* idx, const float* d_queries, uint32_t nq, u
     return enqueue_search(idx, d_queries, nq, kk, k, ws, d_rows_out, d_dist_out, s, x);
 }
 
+// ---- range search (qv_range.hip) ----
+static bool range_on_plane(const qv_index* idx, uint32_t nq) {
+    return qv::range_plane_applies(idx->l2_planes() ? QV_RULE_L2_PLANES : idx->metric, idx->dim, idx->n_rows, nq, idx->range_plane, idx->d_plane8 != nullptr);
+}
+static size_t range_ws_bytes(const qv_index* idx, uint32_t nq, uint32_t kk) { return qv::range_workspace_bytes(nq, kk, (idx->n_rows + 63) / 64, idx->dim); }
+// a call's queries in pieces of kRangePiece, all enqueued on s; outputs [nq][kk]
+static int range_enqueue(qv_index* idx, const float* d_queries, uint32_t nq, const float* d_radius, uint32_t kk, void* ws,
+                         uint32_t* d_rows_out, float* d_dist_out, uint64_t* d_matches_out, hipStream_t s) {
+    const qv::IndexView v = idx->view();
+    const qv::ScanPlan p = qv::plan_scan(v.n_tiles, idx->cus);
+    for (uint32_t q0 = 0; q0 < nq; q0 += qv::kRangePiece) {
+        const uint32_t m = std::min(qv::kRangePiece, nq - q0);
+        HIPCHK(qv::launch_range_search(v, p, d_queries + (size_t)q0 * idx->dim, d_radius + q0, m, kk, range_on_plane(idx, m), ws, idx->d_bound_stats,
+                                       d_rows_out + (size_t)q0 * kk, d_dist_out + (size_t)q0 * kk, d_matches_out + q0, s));
+    }
+    return QV_OK;
+}
+static int range_check(const qv_index* idx, uint32_t nq, uint32_t max_results, bool pointers) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (nq == 0) return fail(QV_ERR_INVALID_ARG, "a range search takes one query at least");
+    if (max_results == 0 || max_results > QV_RANGE_MAX_RESULTS) return fail(QV_ERR_INVALID_ARG, "max_results must be 1 .. %d; got %u", QV_RANGE_MAX_RESULTS, max_results);
+    if (!pointers) return fail(QV_ERR_INVALID_ARG, "a null pointer among the queries, the radii and the outputs");
+    return QV_OK;
+}
+
+int qv_index_search_range_device(qv_index* idx, const float* d_queries, uint32_t nq, const float* d_radius, uint32_t max_results,
+                                 uint32_t* d_rows_out, float* d_dist_out, uint64_t* d_matches_out, void* stream) {
+    if (const int rc = range_check(idx, nq, max_results, d_queries && d_radius && d_rows_out && d_dist_out && d_matches_out); rc != QV_OK) return rc;
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (idx->n_live == 0) {
+        HIPCHK(qv::launch_range_pad(d_matches_out, nq, s));
+        return pad_lists(d_rows_out, d_dist_out, (size_t)nq * max_results, s);
+    }
+    void* ws = nullptr;
+    std::unique_lock<std::mutex> ws_hold;
+    if (const int rc = stream_workspace(idx, s, range_ws_bytes(idx, nq, max_results), &ws, &ws_hold); rc != QV_OK) return rc;
+    return range_enqueue(idx, d_queries, nq, d_radius, max_results, ws, d_rows_out, d_dist_out, d_matches_out, s);
+}
+
+// one staged pass of at most kHostBatch queries: the radii ride behind the match counts in the context's id buffers
+static int range_pass(qv_index* idx, const float* queries, uint32_t nq, const float* radius, uint32_t kk, uint32_t* rows_out, float* dist_out,
+                      uint32_t* count_out, uint64_t* matches_out) {
+    HostCall hc(idx);
+    int rc;
+    const size_t aux = (size_t)nq * (sizeof(uint64_t) + sizeof(float));
+    if ((rc = hc.open()) || (rc = hc.reserve(nq, nq, kk)) || (rc = hc.workspace(range_ws_bytes(idx, nq, kk))) || (rc = hc.c->d_ids.ensure(aux)) || (rc = hc.c->h_ids.ensure(aux))) return rc;
+    uint64_t* h_m = static_cast<uint64_t*>(hc.c->h_ids.p); uint64_t* d_m = static_cast<uint64_t*>(hc.c->d_ids.p);
+    float* h_r = reinterpret_cast<float*>(h_m + nq); float* d_r = reinterpret_cast<float*>(d_m + nq);
+    hc.stage(queries, nq);
+    memcpy(h_r, radius, (size_t)nq * sizeof(float));
+    if ((rc = hc.send(nq))) return rc;
+    HIPCHK(hipMemcpyAsync(d_r, h_r, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, hc.stream()));
+    if ((rc = range_enqueue(idx, hc.d_queries(), nq, d_r, kk, hc.ws(), hc.d_rows(), hc.d_dist(), d_m, hc.stream())) || (rc = hc.fetch(nq, kk))) return rc;
+    HIPCHK(hipMemcpyAsync(h_m, d_m, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, hc.stream()));
+    if ((rc = hc.sync())) return rc;
+    hc.deliver(nq, kk, kk, kk, rows_out, dist_out);
+    for (uint32_t q = 0; q < nq; q++) { matches_out[q] = h_m[q]; count_out[q] = (uint32_t)std::min<uint64_t>(h_m[q], kk); }
+    return QV_OK;
+}
+
+int qv_index_search_range(qv_index* idx, const float* queries, uint32_t nq, const float* radius, uint32_t max_results,
+                          uint32_t* rows_out, float* dist_out, uint32_t* count_out, uint64_t* matches_out) {
+    if (const int rc = range_check(idx, nq, max_results, queries && radius && rows_out && dist_out && count_out && matches_out); rc != QV_OK) return rc;
+    if (idx->n_live == 0) {
+        for (uint32_t q = 0; q < nq; q++) { count_out[q] = 0; matches_out[q] = 0; }
+        for (size_t i = 0; i < (size_t)nq * max_results; i++) { rows_out[i] = 0xFFFFFFFFu; dist_out[i] = __builtin_inff(); }
+        return QV_OK;
+    }
+    return in_passes(nq, kHostBatch, [&](uint32_t q0, uint32_t m) {
+        return range_pass(idx, queries + (size_t)q0 * idx->dim, m, radius + q0, max_results, rows_out + (size_t)q0 * max_results, dist_out + (size_t)q0 * max_results,
+                          count_out + q0, matches_out + q0);
+    });
+}
+
+int qv_index_set_range_plane(qv_index* idx, int mode) {
+    if (!idx) return fail(QV_ERR_INVALID_ARG, "index is null");
+    if (mode < 0 || mode > QV_RANGE_PLANE_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    idx->range_plane = mode;
+    return QV_OK;
+}
+
+int qv_index_range_stats(qv_index* idx, uint64_t out[4]) {
+    if (!idx || !out) return fail(QV_ERR_INVALID_ARG, "index/out is null");
+    HIPCHK(hipSetDevice(idx->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint32_t h[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(h, idx->d_bound_stats + qv::kRangeStatsWord, sizeof(h), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; i++) out[i] = h[i];
+    return QV_OK;
+}
+
+int qv_scan_range_applies(int metric, uint32_t dim, uint32_t rows, uint32_t nq, int mode, int has_plane8) {
+    if (!((metric >= QV_COSINE && metric <= QV_L2SQ_F64) || metric == QV_RULE_L2_PLANES) || dim == 0 || rows == 0 || nq == 0)
+        return fail(QV_ERR_INVALID_ARG, "no range search has these arguments (metric %d, dim %u, rows %u, nq %u)", metric, dim, rows, nq);
+    if (mode < 0 || mode > QV_RANGE_PLANE_NEVER) return fail(QV_ERR_INVALID_ARG, "mode must be 0 (automatic), 1 (always) or 2 (never); got %d", mode);
+    return qv::range_plane_applies(metric, dim, rows, nq, mode, has_plane8 != 0) ? 1 : 0;
+}
+
 // the short tail of an unfiltered batch: one the exact scan's shared pass takes (up to 8 queries) or the filter itself
 static uint32_t batched_tail(const qv::IndexView& v, uint32_t nq, uint32_t k) {
     const uint32_t rem = short_tail(nq);
@@ -2458,6 +2557,10 @@ int qv_scan_workspace_layout(int kind, int metric, uint32_t dim, uint64_t rows, 
         case QV_WS_FULL_SORT:        (void)qv::full_sort_workspace_bytes(n_tiles, &log); break;
         case QV_WS_MQ64:             (void)qv::mq64_workspace_bytes(nq, dim4, &log); break;
         case QV_WS_ROWSET:           (void)qv::rowset_workspace_bytes(p, nq, k, dim4, &log); break;
+        case QV_WS_RANGE:
+            if (k > QV_RANGE_MAX_RESULTS) return fail(QV_ERR_INVALID_ARG, "a range search returns %d rows per query at most; got %u", QV_RANGE_MAX_RESULTS, k);
+            (void)qv::range_workspace_bytes(nq, k, n_tiles, dim, &log);
+            break;
         case QV_WS_FLAT:
             if (flags > QV_WS_FLAT_BOUND_MQ) return fail(QV_ERR_INVALID_ARG, "flags must be one of QV_WS_FLAT_*; got %u", flags);
             (void)qv::flat_layout(nullptr, flags == QV_WS_FLAT_BOUND_MQ ? qv::FlatWs::call_bound_mq : flags == QV_WS_FLAT_BOUND ? qv::FlatWs::call_bound : qv::FlatWs::call, p, nq, k, n_tiles, dim, &log);

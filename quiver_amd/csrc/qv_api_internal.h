@@ -115,6 +115,7 @@ struct qv_index {
     uint8_t* d_plane6 = nullptr;               // the 6-bit plane and its residual: kept with the 8-bit plane (whose scale it shares), refreshed with it
     float* d_rres6 = nullptr;
     bool plane6_lost = false;                  // it could not be allocated: the index carries on with the 8-bit plane
+    int range_plane = 0;                       // qv_index_set_range_plane: QV_RANGE_PLANE_*
     int filtered_batch = 0;                    // qv_index_set_filtered_batch: QV_FILTERED_BATCH_*
     int filtered_batch_wide = 0;               // qv_index_set_filtered_batch_wide: the same question for 65 .. 1024 results per query
     uint32_t filtered_batch_ppm = 0xFFFFFFFFu; // ... and its sparse floor in millionths of the rows (0xFFFFFFFF: the default, 0: never sparse)

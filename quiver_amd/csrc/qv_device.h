@@ -465,7 +465,7 @@ constexpr uint32_t kInt8FilterStatsWord = 16;
 constexpr uint32_t kInt8SharedStatsWord = 19;
 // ... and a FILTERED batch's on the sets form: [22] batches, [23] their queries, [24 - 25] (block, tile) visits skipped, [26 - 27] visits possible (64-bit)
 constexpr uint32_t kInt8FilteredStatsWord = 22;
-constexpr uint32_t kIndexStatsWords = 28;      // what the index allocates (and clears) for all of them
+constexpr uint32_t kIndexStatsWords = 32;      // what the index allocates (and clears) for all of them (28 - 31: the range search's, kRangeStatsWord)
 static_assert(kInt8SharedStatsWord + 2 <= kInt8FilteredStatsWord && kInt8FilteredStatsWord % 2 == 0 && kInt8FilteredStatsWord + 6 <= kIndexStatsWords, "the sets form's counters: 64-bit words, inside the allocation");
 static_assert(kInt8FilterStatsWord + 3 <= kInt8SharedStatsWord, "the int8 filter's counters end where the shared-row form's begin");
 static_assert(kInt8SharedStatsWord + 2 <= kIndexStatsWords, "the int8 filter's counters lie inside the allocation");
@@ -565,6 +565,23 @@ bool flat_select_redo_one_serves(uint32_t n_tiles);
 size_t flat_select_redo_one_workspace_bytes(uint32_t n_tiles, uint32_t kk, uint32_t dim, uint32_t dim4, WsLog* log = nullptr);
 hipError_t launch_flat_select_redo_one(const IndexView& v, const ScanPlan& p, const float* d_query, uint32_t kk, uint32_t k_stride, const uint32_t* d_flag,
                                        void* d_ws, uint32_t* d_rows_out, float* d_dist_out, hipStream_t s);
+
+// Range search (qv_range.hip): per query every live row with d <= radius[q], the first kk of them in (distance, row) order, and the match
+// count.  A call goes in pieces of at most kRangePiece queries.  plane: stage 1 on the 8-bit plane (k_range_scan8) and a wave per survivor
+// (k_range_rescore) in front of the exact range scan (k_range_scan_exact), which then answers only what stage 1 hands back; otherwise that
+// scan answers every query.  range_plane_applies is the whole rule (qv_scan_range_applies); range_plane_mode the mode in force (the index's
+// own, else QV_RANGE_PLANE, read once).  d_stats: the index's counter words, the range search's at kRangeStatsWord: [0] queries, [1] of them
+// started on the 8-bit plane, [2] of those handed back, [3] candidates re-scored.  Nothing is read on the host.
+constexpr uint32_t kRangePiece = 64;           // queries per pass: 24 MiB of candidate and key buffers
+constexpr uint32_t kRangeKeyCap = 16384;       // keys per query: what launch_select_topk_counted takes, twice QV_RANGE_MAX_RESULTS
+constexpr uint32_t kRangeCandCap = 65536;      // stage 1's survivors per query; more: the query is handed back
+constexpr uint32_t kRangeStatsWord = 28;
+int range_plane_mode(int mode);
+bool range_plane_applies(int rule_metric, uint32_t dim, uint32_t rows, uint32_t nq, int mode, bool has_plane8);
+size_t range_workspace_bytes(uint32_t nq, uint32_t kk, uint32_t n_tiles, uint32_t dim, WsLog* log = nullptr);
+hipError_t launch_range_search(const IndexView& v, const ScanPlan& p, const float* d_queries, const float* d_radius, uint32_t nq, uint32_t kk, bool plane,
+                               void* d_ws, uint32_t* d_stats, uint32_t* d_rows_out, float* d_dist_out, uint64_t* d_matches, hipStream_t s);
+hipError_t launch_range_pad(uint64_t* d_matches, uint32_t nq, hipStream_t s);   // zero match counts (an index without a live row)
 
 // Full ranking path (any k): all distances -> 64-bit keys -> stable radix sort -> first k.
 // d_keys_a/d_keys_b: two buffers of n_tiles*64 u64; d_hist: radix histogram workspace.

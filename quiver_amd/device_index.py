@@ -231,6 +231,41 @@ class DeviceIndex:
     def search_device(self, d_queries: int, nq: int, k: int, d_rows_out: int, d_dist_out: int, stream: int = 0):
         check(lib().qv_index_search_device(self._h, d_queries, nq, k, d_rows_out, d_dist_out, stream))
 
+    RANGE_PLANE = {"auto": 0, "always": 1, "never": 2}
+
+    def search_range(self, queries, radius, max_results: int):
+        """every live row within radius[q] of query q (float32 distance <= radius), the nearest max_results of them in (distance, row) order
+        -> (rows [nq, max_results] uint32, dist [nq, max_results] float32, count [nq] uint32 = rows written, matches [nq] uint64 = rows
+        within the radius); padded with 0xFFFFFFFF / +inf (qv_index_search_range)"""
+        q = _f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dimension mismatch: expected {self.dim}, got {q.shape[1]}")
+        nq = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
+        kk = max(int(max_results), 0)
+        rows = np.full((nq, max(kk, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full((nq, max(kk, 1)), np.inf, dtype=np.float32)
+        count = np.zeros(nq, dtype=np.uint32)
+        matches = np.zeros(nq, dtype=np.uint64)
+        check(lib().qv_index_search_range(self._h, q.ctypes.data, nq, r.ctypes.data, kk, rows.ctypes.data, dist.ctypes.data, count.ctypes.data, matches.ctypes.data))
+        return rows[:, :kk], dist[:, :kk], count, matches
+
+    def search_range_device(self, d_queries: int, nq: int, d_radius: int, max_results: int, d_rows_out: int, d_dist_out: int, d_matches_out: int, stream: int = 0):
+        check(lib().qv_index_search_range_device(self._h, d_queries, nq, d_radius, max_results, d_rows_out, d_dist_out, d_matches_out, stream))
+
+    def set_range_plane(self, mode):
+        """where a range search starts: "always" (on the 8-bit plane wherever the index keeps it), "never" (the exact range scan), "auto"
+        (the measured shapes: none yet) (qv_index_set_range_plane)"""
+        check(lib().qv_index_set_range_plane(self._h, self.RANGE_PLANE.get(mode, mode)))
+
+    def range_stats(self):
+        """(queries of range calls, of them started on the 8-bit plane, of those handed back to the exact range scan, candidates re-scored)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().qv_index_range_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
     def search_masked(self, queries, k: int, mask):
         """exact top-k among the rows selected by `mask` (bool [rows] or packed uint64 words): filtered search without a full ranking"""
         q = _f32c(queries)
